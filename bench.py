@@ -1,6 +1,11 @@
 #!/usr/bin/env python3
-"""bench.py -- EPPM hot path on MI355X: Mflow-vectors/s (`value`, `ms_per_step`) on 1024x436 Sintel-shape pairs, and the single-pair
-latency beside it (`latency_ms_per_pair`: one pair, one stream, nothing else in flight -- the "ms/frame-pair" half of BASELINE.json's metric).
+"""bench.py -- EPPM hot path on MI355X: Mflow-vectors/s (`value`, `ms_per_step`) on 1024x436 Sintel-shape pairs, and with --full the
+single-pair latency beside it (`latency_ms_per_pair`: one pair, one stream, nothing else in flight -- the "ms/frame-pair" half of BASELINE.json's metric).
+
+A plain run (`bench.py --gpus 1 --steps N --warmup W`) does only what the headline figure needs: it generates the pairs, creates the
+contexts, warms up, times the N steps once (--repeats 1), writes the flow of the last step with --dump-outputs DIR, and prints the
+result line (contract fields + config).  Everything else described below -- the correctness checks, roofline, single-stream,
+other-config, host-boundary, tolerance-library and CPU legs, and five repeats of the window -- runs with --full.
 
 A step = one pass of the hot path (set_data's device part: prefilter + pyramid + census, then
 compute_flow: PatchMatch fwd/bwd at 1/4 res, L-R check, outlier removal, weighted median, hole fill,
@@ -9,10 +14,10 @@ already resident in HBM; the float2 flow stays in HBM.  Consecutive steps are is
 batch contexts (eppm_create_batch: every kernel launch covers the group's pairs -- the quarter-resolution stages of ONE pair
 are too few pixels to fill 256 CUs), round robin over --inflight such contexts (default 3), each on its own HIP
 stream, so that the tail of one launch overlaps the next context's work; every step's work runs inside the timed
-region; `--batch 1` issues one context per step.  The timed window of exactly --steps steps is run --repeats (5) times,
+region; `--batch 1` issues one context per step.  The timed window of exactly --steps steps is run --repeats (1; 5 with --full) times,
 each bracketed by barrier + synchronize; the median is reported, min / max beside it.
 
-The line proves its own correctness: the pairs of the timed region are pairs (rank * P + j) mod 64 of BASELINE configs[2]'s 64 pairs
+With --full the line proves its own correctness: the pairs of the timed region are pairs (rank * P + j) mod 64 of BASELINE configs[2]'s 64 pairs
 (seeds 1234 + index), whose CPU-oracle flows are committed as sha256 (tests/golden/MANIFEST_config3.json); after the last repeat
 every flow the timed region wrote is hashed and compared: `timed_region_verified: {ok, of}` at every N.
 
@@ -20,11 +25,11 @@ N > 1 (`--gpus N`): one process per GPU, each rank its own pairs (independent pa
 collective: SURVEY 8e); value = pairs of all ranks * W*H / max-over-ranks time.  When RANK is not in the
 environment (plain `python bench.py --gpus N`) this process only spawns the N rank processes -- before
 importing torch or touching HIP -- relays rank 0's JSON line and exits non-zero if any rank failed; under
-`torch.distributed.run` (RANK set) it is a rank itself.  At N > 1 (or with `--verify-config3`) every rank also runs its share of
+`torch.distributed.run` (RANK set) it is a rank itself.  With --full at N > 1 (or with `--verify-config3`) every rank also runs its share of
 configs[2]'s 64 pairs (pair i -> rank i mod N) through the host boundary and checks each flow against the same hashes
 (`config3_verified`; a pair whose synthetic images differ on this host counts as unverified, never as OK).
 
-Prints ONE JSON line: the contract fields, `timed_region_verified`, `roofline` (dominant kernel = the candidate refine; its launch
+Prints ONE JSON line: the contract fields and, with --full, `timed_region_verified`, `roofline` (dominant kernel = the candidate refine; its launch
 duration by HIP events from a one-context pass of the same launches; bound "valu" with the HBM form beside it, from
 profiles/pmc_constants.json when that was measured on these device sources), `path_valu_roofline` (the whole path against the VALU
 issue peak) and, on rank 0 at N = 1: `latency_ms_per_pair`, `stage_ms` and `valu_roofline` from a single-stream pass, `other_configs`
@@ -73,20 +78,33 @@ def parse_args(known_only=False):
                          "covers the whole group; --inflight such contexts are kept in flight")
     ap.add_argument("--pairs-per-gpu", type=int, default=8, help="size of the config-3 leg (distinct pairs per GPU)")
     ap.add_argument("--dist-backend", default="nccl", choices=["nccl", "gloo"])
-    ap.add_argument("--repeats", type=int, default=5,
-                    help="the timed window of exactly --steps steps is run this many times back to back; the median is reported (min/max beside it)")
+    ap.add_argument("--full", action="store_true",
+                    help="everything beyond the headline figure: the timed region's flows checked against the committed oracle hashes, roofline and "
+                         "single-stream legs, other configurations, the host boundary, the tolerance library and the CPU baseline.  Without it a run "
+                         "sets up, warms up, times --steps steps once and prints the result line")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write the flow of the last timed step (what compute_flow_device hands its caller: float32, "
+                         "height x width x 2) to DIR/flow.npy; rank 0 only")
+    ap.add_argument("--repeats", type=int, default=None,
+                    help="the timed window of exactly --steps steps is run this many times back to back; the median is reported (min/max beside it).  "
+                         "Default: 1, or 5 with --full")
     ap.add_argument("--verify-config3", dest="verify_config3", action="store_true", default=None,
                     help="BASELINE configs[2] with a correctness bit: this rank's share of the 64 pairs (pair i -> rank i mod N, seeds 1234+i) through the "
-                         "host boundary, every flow checked against tests/golden/MANIFEST_config3.json.  Default: on when --gpus > 1")
+                         "host boundary, every flow checked against tests/golden/MANIFEST_config3.json.  Default: on with --full when --gpus > 1")
     ap.add_argument("--no-verify-config3", dest="verify_config3", action="store_false")
     ap.add_argument("--library", default="tol" if os.environ.get("EPPM_HIP_VARIANT") == "tol" else "exact", choices=["exact", "tol"],
                     help="exact: libeppm_hip.so, bit-identical to the oracle (the default, and what `value` always is); tol: the tolerance library "
                          "libeppm_hip_tol.so (not bit-identical, <= 1e-3 px EPE on the bundled pair) -- the run the default line embeds as `tolerance_mode`")
-    ap.add_argument("--no-tolerance-mode", action="store_true", help="skip the tolerance_mode leg (a child run of this script with --library tol)")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--no-extras", action="store_true", help="skip host_boundary / cold / config3 / single-stream / other-config legs (profiling runs)")
-    ap.add_argument("--no-other-configs", action="store_true", help="skip the 1920x1080 and 3840x2160 R=17 legs (other_configs)")
-    return ap.parse_known_args()[0] if known_only else ap.parse_args()
+    ap.add_argument("--no-tolerance-mode", action="store_true", help="with --full: skip the tolerance_mode leg (a child run of this script with --library tol)")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: skip the CPU baseline")
+    ap.add_argument("--no-extras", action="store_true", help="with --full: skip host_boundary / cold / config3 / single-stream / other-config legs (profiling runs)")
+    ap.add_argument("--no-other-configs", action="store_true", help="with --full: skip the 1920x1080 and 3840x2160 R=17 legs (other_configs)")
+    args = ap.parse_known_args()[0] if known_only else ap.parse_args()
+    if args.repeats is None:
+        args.repeats = 5 if args.full else 1
+    if not args.full:               # a plain run: the headline figure only
+        args.no_extras = args.no_cpu_baseline = args.no_tolerance_mode = args.no_other_configs = True
+    return args
 
 
 def parse_args_known():
@@ -199,7 +217,7 @@ def worker(args):
     sys.stdout.flush()
     json_fd = os.dup(1)
     os.dup2(2, 1)
-    verify3 = (world > 1) if args.verify_config3 is None else bool(args.verify_config3)
+    verify3 = (world > 1 and args.full) if args.verify_config3 is None else bool(args.verify_config3)
     other_cfgs = world == 1 and not args.no_extras and not args.no_other_configs and (args.width, args.height, args.patch_r, args.propagation) == (W, H, 9, 0)
     S = max(1, args.inflight)
     NB = max(1, args.batch)
@@ -310,15 +328,17 @@ def worker(args):
 
     # ---- the timed region: exactly --steps steps, bracketed by barrier + synchronize; run --repeats times, median reported ----
     tengs = bengs if NB > 1 else engs
-    for e in tengs:                            # HIP events around the dominant kernel only, from a per-context pool
-        e.enable_stage_timing(2)
-        e.stage_times(clear=True)
+    if args.full:
+        for e in tengs:                        # HIP events around the dominant kernel only, from a per-context pool
+            e.enable_stage_timing(2)
+            e.stage_times(clear=True)
     dts = []
     for _ in range(max(1, args.repeats)):
-        # outside the timed window: every output buffer is poisoned, so that the hashes below can only match flows THIS repeat wrote
-        # (the warm-up and the earlier repeats wrote the same flows into the same buffers)
-        for x in inputs:
-            x[2].fill_(float("nan"))
+        if args.full:
+            # outside the timed window: every output buffer is poisoned, so that the hashes below can only match flows THIS repeat wrote
+            # (the warm-up and the earlier repeats wrote the same flows into the same buffers)
+            for x in inputs:
+                x[2].fill_(float("nan"))
         barrier()
         t0 = time.perf_counter()
         run_steps(0, args.steps, S * NB)
@@ -326,16 +346,24 @@ def worker(args):
         barrier()
         dts.append(all_max(time.perf_counter() - t0))
     dt = float(np.median(dts))
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, inputs[(args.steps - 1) % (S * NB)][2].cpu().numpy())
+    bindings = [numa]
+    if world > 1:
+        bindings = [None] * world
+        dist.all_gather_object(bindings, numa, group=ctl)
+    if not args.full:
+        if rank == 0:
+            write_line(json_fd, headline(args, world, w, h, dt, dts, S, NB, bindings))
+        if world > 1:
+            dist.destroy_process_group()
+        return
     # every flow the timed region wrote (step i -> buffer i mod S*NB) against the committed oracle hash of its pair
     tv = plan.verify_timed([(j, inputs[j][2]) for j in sorted({i % (S * NB) for i in range(args.steps)})], host_pairs)
     if world > 1:
         t = torch.tensor(tv, dtype=torch.int64)
         dist.all_reduce(t, group=ctl)
         tv = [int(x) for x in t]
-    bindings = [numa]
-    if world > 1:
-        bindings = [None] * world
-        dist.all_gather_object(bindings, numa, group=ctl)
     dom_timed = []
     for e in tengs:
         dom_timed += e.stage_times(clear=True)
@@ -445,23 +473,8 @@ def worker(args):
                         note="profiles/pmc_constants.json has no entry measured on these device sources: VALU instruction count and HBM traffic unknown")
         roof.update({"avg_launch_ms": dom_ms, "avg_launch_ms_timed_region": dom_ms_timed, "pairs_per_launch": NB,
                      "dominant_kernel_ms_per_step": 2 * dom_ms / NB})
-        vals = sorted(world * args.steps * w * h / d / 1e6 for d in dts)
-        out = {
-            "metric": "Mflow-vectors/sec", "value": world * args.steps * w * h / dt / 1e6, "unit": "Mflow-vectors/s",
-            "n_gpus": world, "steps": args.steps, "warmup": args.warmup, "ms_per_step": dt / args.steps * 1e3,
-            "higher_is_better": True, "scaling": "weak", "vs_baseline": None, "dtype": "f32", "data": "synthetic",
-            "repeats": len(dts), "value_min": vals[0], "value_max": vals[-1], "ms_per_step_by_repeat": [d / args.steps * 1e3 for d in dts],
-            "config": {"workload": f"single {w}x{h} Sintel-shape synthetic pair per step, full 3-level pyramid, patch_r={args.patch_r}, "
-                                   + ("" if args.propagation == 0 else f"PROPAGATION MODE {args.propagation} (not the reference's live scheme: other flows), ") +
-                                   
-                                   f"default defs.h parameters; {world} rank(s), independent pairs; inputs: RGBA planes resident in HBM before the "
-                                   "timed region; outputs: interleaved float2 flow left in HBM (the PCIe-inclusive window of the reference API -- host "
-                                   "RGB in, host u/v out -- is `host_boundary`)",
-                       "inputs": "device-resident RGBA", "outputs": "device-resident float2 flow",
-                       "pairs_per_step_per_gpu": 1, "pairs_in_flight_per_gpu": S * NB, "pairs_per_launch": NB, "contexts_in_flight": S,
-                       "width": w, "height": h,
-                       "host_binding": {"what": "each rank's host threads bound to the CPUs of its GPU's NUMA node (eppm_bind_thread_to_device; "
-                                                "numa_node -1 = topology not visible, unbound)", "ranks": bindings}},
+        out = headline(args, world, w, h, dt, dts, S, NB, bindings)
+        out.update({
             "timed_region_verified": {"ok": tv[0], "of": tv[1], "inputs_differ_on_this_host": tv[2], "all_ok": tv[0] == tv[1] and tv[1] > 0,
                                       "what": "sha256 of every flow the last repeat of the timed region left in HBM (all ranks) == the CPU oracle's flow of that "
                                               "pair, tests/golden/MANIFEST_config3.json" if plan.man3 else plan.why_unverifiable},
@@ -470,7 +483,7 @@ def worker(args):
             "epe_vs_synthetic_gt_note": "flow QUALITY of the algorithm on the synthetic pair, not parity (the oracle's own flow has exactly this error): band-limited "
                                         "noise with two motion layers is hard for EPPM -- 43 % of the quarter-resolution matches fail the left-right check and 63 % are "
                                         "holes after the outlier vote, against 26 % / 33 % on the natural pair of other_configs.natural_1024x436 and 24 % / 27 % on the bundled pair (DESIGN.md section 5)",
-        }
+        })
         out.update(extras)
         out["path_valu_roofline"] = path_valu_roofline(pmc, NB, dt / args.steps)
         if world == 1 and not args.no_extras:
@@ -490,15 +503,60 @@ def worker(args):
                 for e in engs + bengs:
                     e.synchronize()
                 out["tolerance_mode"] = tolerance_mode(args)
-        out["library"] = "exact (libeppm_hip.so: every flow bit-identical to the CPU oracle)" if args.library == "exact" else "tol (libeppm_hip_tol.so: NOT bit-identical)"
         if world == 1 and not args.no_cpu_baseline:
             unbind_all_threads(host_cpus)          # the CPU baseline gets the whole host, not the GPU's NUMA node
             out["cpu_baseline"] = cpu_baseline(w, h)
-        data = (json.dumps(out) + "\n").encode()
-        while data:
-            data = data[os.write(json_fd, data):]
+        write_line(json_fd, out)
     if world > 1:
         dist.destroy_process_group()
+
+
+def headline(args, world, w, h, dt, dts, S, NB, bindings):
+    """The result line of every run: the contract fields and the configuration of the timed region (a plain run prints only this)."""
+    vals = sorted(world * args.steps * w * h / d / 1e6 for d in dts)
+    return {
+        "metric": "Mflow-vectors/sec", "value": world * args.steps * w * h / dt / 1e6, "unit": "Mflow-vectors/s",
+        "n_gpus": world, "steps": args.steps, "warmup": args.warmup, "ms_per_step": dt / args.steps * 1e3,
+        "higher_is_better": True, "scaling": "weak", "vs_baseline": None, "dtype": "f32", "data": "synthetic",
+        "repeats": len(dts), "value_min": vals[0], "value_max": vals[-1], "ms_per_step_by_repeat": [d / args.steps * 1e3 for d in dts],
+        "config": {"workload": f"single {w}x{h} Sintel-shape synthetic pair per step, full 3-level pyramid, patch_r={args.patch_r}, "
+                               + ("" if args.propagation == 0 else f"PROPAGATION MODE {args.propagation} (not the reference's live scheme: other flows), ") +
+                               f"default defs.h parameters; {world} rank(s), independent pairs; inputs: RGBA planes resident in HBM before the "
+                               "timed region; outputs: interleaved float2 flow left in HBM (the PCIe-inclusive window of the reference API -- host "
+                               "RGB in, host u/v out -- is `host_boundary`, with --full)",
+                   "inputs": "device-resident RGBA", "outputs": "device-resident float2 flow",
+                   "pairs_per_step_per_gpu": 1, "pairs_in_flight_per_gpu": S * NB, "pairs_per_launch": NB, "contexts_in_flight": S,
+                   "width": w, "height": h,
+                   "host_binding": {"what": "each rank's host threads bound to the CPUs of its GPU's NUMA node (eppm_bind_thread_to_device; "
+                                            "numa_node -1 = topology not visible, unbound)", "ranks": bindings}},
+        "library": "exact (libeppm_hip.so: every flow bit-identical to the CPU oracle)" if args.library == "exact" else "tol (libeppm_hip_tol.so: NOT bit-identical)",
+    }
+
+
+def write_line(fd, out):
+    """The ONE JSON line, written to the saved stdout (file descriptor 1 points at stderr for the life of a rank)."""
+    data = (json.dumps(out) + "\n").encode()
+    while data:
+        data = data[os.write(fd, data):]
+
+
+DUMP_LIMIT_BYTES = 64_000_000       # 64 MB in all, .npy headers included
+
+
+def dump_outputs(d, flow):
+    """--dump-outputs DIR: the flow of the last timed step as DIR/flow.npy (float32, h x w x 2), as a caller of compute_flow_device receives
+    it.  A flow larger than 64 MB (e.g. --width 3840 --height 2160 is 66 MB) is replaced by a fixed sample: DIR/flow_sample.npy holds the
+    vectors of 2M pixels drawn without replacement by numpy's default_rng(0), DIR/flow_sample_index.npy their flat pixel indices (float64)."""
+    import numpy as np
+    os.makedirs(d, exist_ok=True)
+    flow = np.ascontiguousarray(flow, dtype=np.float32)
+    if flow.nbytes + 4096 <= DUMP_LIMIT_BYTES:
+        np.save(os.path.join(d, "flow.npy"), flow)
+        return
+    v = flow.reshape(-1, flow.shape[-1])
+    idx = np.sort(np.random.default_rng(0).choice(v.shape[0], size=2 << 20, replace=False))
+    np.save(os.path.join(d, "flow_sample.npy"), v[idx])
+    np.save(os.path.join(d, "flow_sample_index.npy"), idx.astype(np.float64))
 
 
 def unbind_all_threads(cpus):
@@ -801,7 +859,7 @@ def tolerance_mode(args):
                       "check, outlier vote, weighted median, hole filling, flow smoothing -- is the exact library's code)",
            "parity": "NOT bit-identical; north_star's bar: mean EPE <= 1e-3 px against the oracle on frame10/frame11 (asserted by -m gpu tests)"}
     try:
-        cmd = [sys.executable, os.path.abspath(__file__), "--library", "tol", "--steps", str(args.steps), "--warmup", str(args.warmup),
+        cmd = [sys.executable, os.path.abspath(__file__), "--full", "--library", "tol", "--steps", str(args.steps), "--warmup", str(args.warmup),
                "--batch", str(args.batch), "--inflight", str(args.inflight), "--repeats", str(args.repeats), "--no-cpu-baseline", "--no-tolerance-mode"]
         if args.no_other_configs:
             cmd.append("--no-other-configs")

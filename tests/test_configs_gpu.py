@@ -689,7 +689,7 @@ def test_bench_two_ranks_share_one_gpu(backend):
     and (default at N > 1) every rank's share of the 64 config-3 pairs against the committed oracle hashes."""
     env = dict(os.environ, EPPM_BENCH_SHARE_GPU="1")
     env.pop("RANK", None)
-    out = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "2", "--steps", "6", "--warmup", "3", "--dist-backend", backend,
+    out = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--full", "--gpus", "2", "--steps", "6", "--warmup", "3", "--dist-backend", backend,
                           "--no-extras", "--no-cpu-baseline"] + (["--no-verify-config3"] if backend == "nccl" else []),
                          env=env, capture_output=True, text=True, timeout=900)
     assert out.returncode == 0, out.stderr[-2000:]
@@ -722,7 +722,7 @@ def test_bench_eight_ranks_share_one_gpu():
     for k in ("RANK", "LOCAL_RANK", "WORLD_SIZE"):
         env.pop(k, None)
     t0 = time.time()
-    out = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "8", "--steps", "16", "--dist-backend", "gloo", "--no-extras",
+    out = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--full", "--gpus", "8", "--steps", "16", "--dist-backend", "gloo", "--no-extras",
                           "--no-cpu-baseline"], env=env, capture_output=True, text=True, timeout=900)
     wall = time.time() - t0
     assert out.returncode == 0, out.stderr[-3000:]
@@ -740,12 +740,12 @@ def test_bench_eight_ranks_share_one_gpu():
 
 
 def test_bench_default_line_is_self_verifying():
-    """The one line the driver records (python bench.py at N = 1): every flow of the timed region hashed against the committed oracle
+    """The whole line of `python bench.py --full` at N = 1: every flow of the timed region hashed against the committed oracle
     flows, the single-pair latency beside ms_per_step, BASELINE configs[3] and [4] as `other_configs` (each checked against its oracle
-    hash), roofline + cpu_baseline.  Fewer steps than the default keep the test short; everything else is the default path."""
+    hash), roofline + cpu_baseline.  Fewer steps than the default keep the test short; everything else is the default --full path."""
     env = dict(os.environ)
     env.pop("RANK", None)
-    out = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--steps", "20", "--warmup", "5", "--repeats", "2"], env=env, capture_output=True, text=True, timeout=1500)
+    out = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--full", "--steps", "20", "--warmup", "5", "--repeats", "2"], env=env, capture_output=True, text=True, timeout=1500)
     assert out.returncode == 0, out.stderr[-2000:]
     d = json.loads([ln for ln in out.stdout.splitlines() if ln.startswith("{")][-1])
     tv = d["timed_region_verified"]
@@ -782,6 +782,29 @@ def test_bench_default_line_is_self_verifying():
     hb = d["host_boundary"]
     assert "error" not in hb and hb["pipelined"] > 0 and hb["sync"] > 0
 
+
+def test_bench_plain_run_times_its_steps_and_dumps_the_last_flow(tmp_path):
+    """`python bench.py --gpus 1 --steps N --warmup W` without --full: exactly N timed steps in one window, the contract fields and nothing
+    of the --full legs; --dump-outputs writes the flow of the last step (step N-1 -> timed pair N-1 of the 64 config-3 pairs) and it is
+    the CPU oracle's flow of that pair, bit for bit (tests/golden/MANIFEST_config3.json)."""
+    env = dict(os.environ)
+    env.pop("RANK", None)
+    d = tmp_path / "out"
+    out = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1", "--steps", "5", "--warmup", "2", "--dump-outputs", str(d)],
+                         env=env, capture_output=True, text=True, timeout=600)
+    assert out.returncode == 0, out.stderr[-2000:]
+    line = [ln for ln in out.stdout.splitlines() if ln.strip()]
+    assert len(line) == 1, out.stdout[:2000]
+    r = json.loads(line[0])
+    assert r["steps"] == 5 and r["repeats"] == 1 and len(r["ms_per_step_by_repeat"]) == 1 and r["ms_per_step"] > 0
+    assert r["metric"] == "Mflow-vectors/sec" and r["unit"] == "Mflow-vectors/s" and r["higher_is_better"] is True and r["dtype"] == "f32"
+    assert abs(r["value"] - 1024 * 436 / (r["ms_per_step"] * 1e-3) / 1e6) < 1e-6 * r["value"]
+    assert not {"timed_region_verified", "roofline", "other_configs", "tolerance_mode", "cpu_baseline", "host_boundary"} & set(r), sorted(r)
+    assert sorted(os.listdir(d)) == ["flow.npy"]
+    f = np.load(d / "flow.npy")
+    assert f.dtype == np.float32 and f.shape == (436, 1024, 2)
+    man = json.load(open(os.path.join(GOLDEN, "MANIFEST_config3.json")))
+    assert hashlib.sha256(np.ascontiguousarray(f[..., 0]).tobytes() + np.ascontiguousarray(f[..., 1]).tobytes()).hexdigest() == man["pairs"]["4"]["flow_sha256"]
 
 # ---------------------------------------------------------------------------------------------------
 # the tolerance library (libeppm_hip_tol.so: integer-domain tables / one hardware exp2 instead of the two software exp of the patch

@@ -272,3 +272,42 @@ def test_synth_cache_and_worker_processes_reproduce_the_generator(tmp_path, monk
         for g, w_ in zip(got, want):
             assert all(np.array_equal(a, b) and a.dtype == b.dtype for a, b in zip(g, w_)), attempt
     assert len(list((tmp_path / "cache").iterdir())) == 2
+
+
+def test_bench_plain_run_and_full_run_options(monkeypatch):
+    """A plain `bench.py --gpus 1 --steps N --warmup W` times its N steps once and runs none of the --full legs; --full restores the five
+    repeats and the legs, each of which its --no-* switch still turns off."""
+    import bench
+    monkeypatch.setattr(sys, "argv", ["bench.py", "--gpus", "1", "--steps", "7", "--warmup", "2"])
+    a = bench.parse_args()
+    assert (a.steps, a.warmup, a.repeats, a.full, a.dump_outputs) == (7, 2, 1, False, None)
+    assert a.no_extras and a.no_cpu_baseline and a.no_tolerance_mode and a.no_other_configs
+    monkeypatch.setattr(sys, "argv", ["bench.py", "--full", "--no-cpu-baseline", "--dump-outputs", "d"])
+    a = bench.parse_args()
+    assert (a.repeats, a.full, a.dump_outputs) == (5, True, "d")
+    assert a.no_cpu_baseline and not (a.no_extras or a.no_tolerance_mode or a.no_other_configs)
+    monkeypatch.setattr(sys, "argv", ["bench.py", "--repeats", "3"])
+    assert bench.parse_args().repeats == 3
+
+
+def test_bench_dump_outputs_writes_the_flow_or_a_fixed_sample(tmp_path):
+    """--dump-outputs: a flow up to 64 MB is written whole as float32; a larger one (3840x2160 is 66 MB) as a seeded sample of its vectors
+    with their flat pixel indices, the same from run to run, 64 MB at most in all."""
+    import numpy as np
+    import bench
+    small = np.random.default_rng(1).standard_normal((436, 1024, 2)).astype(np.float32)
+    bench.dump_outputs(str(tmp_path / "s"), small)
+    assert os.listdir(tmp_path / "s") == ["flow.npy"]
+    got = np.load(tmp_path / "s" / "flow.npy")
+    assert got.dtype == np.float32 and np.array_equal(got, small)
+    big = np.arange(2160 * 3840 * 2, dtype=np.float32).reshape(2160, 3840, 2)
+    for d in ("b1", "b2"):
+        bench.dump_outputs(str(tmp_path / d), big)
+    assert sorted(os.listdir(tmp_path / "b1")) == ["flow_sample.npy", "flow_sample_index.npy"]
+    sizes = sum(os.path.getsize(tmp_path / "b1" / f) for f in os.listdir(tmp_path / "b1"))
+    assert sizes <= 64_000_000, sizes
+    v, idx = np.load(tmp_path / "b1" / "flow_sample.npy"), np.load(tmp_path / "b1" / "flow_sample_index.npy")
+    assert v.dtype == np.float32 and idx.dtype == np.float64 and len(np.unique(idx)) == len(idx) == len(v)
+    assert np.array_equal(v, big.reshape(-1, 2)[idx.astype(np.int64)])
+    for f in ("flow_sample.npy", "flow_sample_index.npy"):
+        assert np.array_equal(np.load(tmp_path / "b1" / f), np.load(tmp_path / "b2" / f))

@@ -20,7 +20,7 @@ O=$R/gpurun_out
 mkdir -p $O
 MODE=$1
 TAG=${TAG:-r06}
-QUIET="--no-cpu-baseline --no-extras"
+QUIET="--full --no-cpu-baseline --no-extras"
 # a variant that is missing or misspelt must stop the job, not benchmark the previous library under the new label; the test library
 # travels with the product library (the pytest process computes with it) and a variant without one is an error for the modes that need it.
 # LIB=tol: the variants are builds of the tolerance library (tools/build_variant.sh with TOL=1), run with EPPM_HIP_VARIANT=tol
@@ -53,10 +53,10 @@ case $MODE in
 test)
   cd $R && timeout ${TEST_TIMEOUT:-3000} python -m pytest tests -m gpu ${PYTEST_ARGS:--x -q} ${K:+-k "$K"} 2>&1 | tail -${TAIL:-15} | tee $O/gpu_tests_latest.txt ;;
 bench)
-  cd $R && python bench.py $BENCH_ARGS > $O/bench_latest.json 2> $O/bench_latest.err; tail -3 $O/bench_latest.err; cut -c1-400 $O/bench_latest.json ;;
+  cd $R && python bench.py --full $BENCH_ARGS > $O/bench_latest.json 2> $O/bench_latest.err; tail -3 $O/bench_latest.err; cut -c1-400 $O/bench_latest.json ;;
 quick)
   cd $R && timeout ${TEST_TIMEOUT:-3000} python -m pytest tests -m gpu ${PYTEST_ARGS:--x -q} 2>&1 | tail -15 | tee $O/gpu_tests_latest.txt
-  python bench.py --steps 48 --warmup 6 --no-cpu-baseline --no-other-configs $BENCH_ARGS > $O/bench_latest.json 2> $O/bench_latest.err; tail -3 $O/bench_latest.err
+  python bench.py --full --steps 48 --warmup 6 --no-cpu-baseline --no-other-configs $BENCH_ARGS > $O/bench_latest.json 2> $O/bench_latest.err; tail -3 $O/bench_latest.err
   python - <<'PY'
 import json
 d = json.load(open('gpurun_out/bench_latest.json'))
@@ -151,11 +151,11 @@ LIST
   # the constants the bench lines below report (valid for exactly these device sources), derived on the box from the passes above
   cd $R && python tools/store_profiles.py $T > $OT/pmc_constants_summary.json 2> $OT/store_profiles.err
   if [ -z "$PMC_ONLY" ]; then
-    python bench.py > $OT/bench_default.json 2> $OT/bench_default.err; cut -c1-220 $OT/bench_default.json
-    python bench.py --steps 20 --warmup 5 > $OT/bench_like_driver.json 2>/dev/null
+    python bench.py --full > $OT/bench_default.json 2> $OT/bench_default.err; cut -c1-220 $OT/bench_default.json
+    python bench.py --full --steps 20 --warmup 5 > $OT/bench_like_driver.json 2>/dev/null
     python bench.py --batch 1 --inflight 3 $QUIET > $OT/bench_streams3.json 2>/dev/null
     # the driver's N > 1 launch form, two ranks sharing this box's one GPU (RCCL refuses two ranks per device: the ranks agree on gloo)
-    EPPM_BENCH_SHARE_GPU=1 python -m torch.distributed.run --nnodes=1 --nproc-per-node 2 --master-addr 127.0.0.1 --master-port 29517 bench.py --gpus 2 --steps 16 --warmup 4 --no-cpu-baseline > $OT/bench_torchrun_2ranks_1gpu.json 2> $OT/bench_torchrun.err; cut -c1-160 $OT/bench_torchrun_2ranks_1gpu.json
+    EPPM_BENCH_SHARE_GPU=1 python -m torch.distributed.run --nnodes=1 --nproc-per-node 2 --master-addr 127.0.0.1 --master-port 29517 bench.py --full --gpus 2 --steps 16 --warmup 4 --no-cpu-baseline > $OT/bench_torchrun_2ranks_1gpu.json 2> $OT/bench_torchrun.err; cut -c1-160 $OT/bench_torchrun_2ranks_1gpu.json
     prof_env
     rocprofv3 --kernel-trace --stats --output-format csv -d $OT/stats_default -- python3 $R/bench.py $QUIET > $OT/bench_under_rocprof.json 2>/dev/null
     rocprofv3 --kernel-trace --stats --output-format csv -d $OT/stats_single -- python3 $R/bench.py --steps 30 --warmup 3 --batch 1 --inflight 1 $COMMON > /dev/null 2>&1
