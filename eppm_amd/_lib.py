@@ -36,6 +36,8 @@ SYMBOLS = [
     "eppm_compute_begin_into", "eppm_batch_compute_begin_into",
     "eppm_load_ppm", "eppm_ppm_size", "eppm_save_flo", "eppm_load_flo", "eppm_flo_size", "eppm_flow_error",
     "eppm_flow_error_border", "eppm_flow_error_percentage", "eppm_flow_cutoff", "eppm_flow_to_color_host",
+    "eppm_compute_bidirectional", "eppm_compute_bidirectional_device", "eppm_batch_compute_bidirectional", "eppm_set_occlusion_params",
+    "eppm_fb_occlusion", "eppm_fb_occlusion_host",
 ]
 
 

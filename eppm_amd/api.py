@@ -10,7 +10,8 @@ short2 = np.dtype([("x", "i2"), ("y", "i2")])
 float2 = np.dtype([("x", "f4"), ("y", "f4")])
 
 _PLANE_DTYPES = {"img1": uchar4, "img2": uchar4, "census1": np.uint8, "census2": np.uint8, "nnf1": short2,
-                 "nnf2": short2, "cost1": np.float32, "cost2": np.float32, "flow": float2}
+                 "nnf2": short2, "cost1": np.float32, "cost2": np.float32, "flow": float2,
+                 "flow_bwd": float2, "occ1": np.uint8, "occ2": np.uint8}
 
 
 def Params(**kw):
@@ -82,6 +83,7 @@ class EPPM:
         check(lib().eppm_create(C.byref(ctx), int(h), int(w), int(self._device),
                                 C.byref(self._params) if self._params is not None else None), "eppm_create")
         self._ctx, self.h, self.w = ctx, int(h), int(w)
+        self._occ_params = (0.01, 0.5)          # the new context's defaults
 
     def set_data(self, img1, img2):
         """RGB->RGBA, H2D, prefilter, pyramid, census (driver .cpp:159-168).  Returns True like the reference."""
@@ -110,6 +112,32 @@ class EPPM:
         u, v = self._out(out)
         check(lib().eppm_compute(self._ctx, u.ctypes.data_as(C.c_void_p), v.ctypes.data_as(C.c_void_p)), "eppm_compute")
         return u, v
+
+    def set_occlusion_params(self, alpha=0.01, beta=0.5):
+        """alpha, beta of the occlusion masks' forward-backward criterion (eppm_set_occlusion_params)."""
+        self._need()
+        check(lib().eppm_set_occlusion_params(self._ctx, C.c_float(alpha), C.c_float(beta)), "eppm_set_occlusion_params")
+        self._occ_params = (float(alpha), float(beta))
+
+    def compute_flow_bidirectional(self, alpha=None, beta=None):
+        """(u, v, bu, bv, occ1, occ2): the forward flow (== compute_flow), the backward flow (image 2 -> image 1) and the uint8
+        occlusion masks of image 1's / image 2's pixels (0 consistent, 1 inconsistent, 2 leaves the frame, 3 unknown vector).
+        alpha / beta given: set the criterion's parameters first (eppm_set_occlusion_params; the other keeps its value)."""
+        self._need()
+        if alpha is not None or beta is not None:
+            a0, b0 = getattr(self, "_occ_params", (0.01, 0.5))
+            self._occ_params = (a0 if alpha is None else float(alpha), b0 if beta is None else float(beta))
+            self.set_occlusion_params(*self._occ_params)
+        f = [np.empty((self.h, self.w), np.float32) for _ in range(4)]
+        o = [np.empty((self.h, self.w), np.uint8) for _ in range(2)]
+        check(lib().eppm_compute_bidirectional(self._ctx, *[a.ctypes.data_as(C.c_void_p) for a in f + o]), "eppm_compute_bidirectional")
+        return (*f, *o)
+
+    def compute_flow_bidirectional_device(self, d_flow=None, d_flow_bwd=None, d_occ1=None, d_occ2=None):
+        """eppm_compute_bidirectional_device: asynchronous, device addresses (or None) of the two float2 flows and the two masks."""
+        self._need()
+        ptrs = [C.c_void_p(p) if p else None for p in (d_flow, d_flow_bwd, d_occ1, d_occ2)]
+        check(lib().eppm_compute_bidirectional_device(self._ctx, *ptrs), "eppm_compute_bidirectional_device")
 
     def compute_flow_color(self, max_disp=(20.0, 20.0)):
         """The optional color_flow output of compute_flow (driver .cpp:308-314): (h, w, 3) uint8 R,G,B of the last flow."""
@@ -259,6 +287,16 @@ class EPPMBatch:
         u, v = self._outs(out)
         check(lib().eppm_batch_compute(self._ctx, self._ptrs(u), self._ptrs(v)), "eppm_batch_compute")
         return list(zip(u, v))
+
+    def compute_flow_bidirectional(self):
+        """[(u, v, bu, bv, occ1, occ2)] for the active pairs (eppm_batch_compute_bidirectional); see EPPM.compute_flow_bidirectional."""
+        f = [[np.empty((self.h, self.w), np.float32) for _ in range(self.n)] for _ in range(4)]
+        o = [[np.empty((self.h, self.w), np.uint8) for _ in range(self.n)] for _ in range(2)]
+        check(lib().eppm_batch_compute_bidirectional(self._ctx, *[self._ptrs(t) for t in f + o]), "eppm_batch_compute_bidirectional")
+        return list(zip(*f, *o))
+
+    def set_occlusion_params(self, alpha=0.01, beta=0.5):
+        check(lib().eppm_set_occlusion_params(self._ctx, C.c_float(alpha), C.c_float(beta)), "eppm_set_occlusion_params")
 
     def compute_flow_device(self, d_flows=None):
         check(lib().eppm_batch_compute_device(self._ctx, self._ptrs(list(d_flows)) if d_flows is not None else None), "eppm_batch_compute_device")

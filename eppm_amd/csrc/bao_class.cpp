@@ -6,6 +6,8 @@
 #include <stdlib.h>
 #include <string.h>
 
+#include <vector>
+
 #include "../../include/bao_flow_patchmatch_multiscale_cuda.h"
 #include "../../include/eppm.h"
 
@@ -232,4 +234,54 @@ void bao_flow_patchmatch_multiscale_cuda::compute_flow(float** disp1_x, float** 
             for (int j = 0; j < m_w; j++)
                 for (int c = 0; c < 3; c++) color_flow[i][j][c] = rgb[((size_t)i * m_w + j) * 3 + c];
     }
+}
+
+// compute_flow + the backward flow and the occlusion masks (eppm_compute_bidirectional).  Contiguous tables are written in place; any
+// other layout goes through a host buffer and the row pointers, as in compute_flow.
+void bao_flow_patchmatch_multiscale_cuda::compute_flow_bidirectional(float** disp1_x, float** disp1_y, float** disp2_x, float** disp2_y,
+                                                                      unsigned char** occ1, unsigned char** occ2)
+{
+    if (!m_ctx || !disp1_x || !disp1_y || !disp2_x || !disp2_y) return;
+    const size_t n = (size_t)m_h * m_w;
+    float** ftab[4] = {disp1_x, disp1_y, disp2_x, disp2_y};
+    unsigned char** otab[2] = {occ1, occ2};
+    float* f[4];
+    unsigned char* o[2] = {NULL, NULL};
+    std::vector<float> fstage;
+    std::vector<unsigned char> ostage;
+    for (int k = 0; k < 4; k++) {
+        f[k] = contiguous_plane(m_priv, ftab[k], m_h, m_w);
+        if (!f[k]) {
+            if (fstage.empty()) fstage.resize(n * 4);
+            f[k] = fstage.data() + n * k;
+        }
+    }
+    for (int k = 0; k < 2; k++) {
+        if (!otab[k]) continue;
+        bool block = true;
+        for (int i = 1; i < m_h && block; i++) block = (otab[k][i] == otab[k][0] + (size_t)i * m_w);
+        if (block) { o[k] = otab[k][0]; continue; }
+        if (ostage.empty()) ostage.resize(n * 2);
+        o[k] = ostage.data() + n * k;
+    }
+    if (eppm_compute_bidirectional(m_ctx, f[0], f[1], f[2], f[3], o[0], o[1]) != EPPM_OK) {
+        fprintf(stderr, "bao_flow_patchmatch_multiscale_cuda::compute_flow_bidirectional: %s\n", eppm_last_error());
+        return;
+    }
+    for (int k = 0; k < 4; k++)
+        if (f[k] != ftab[k][0])
+            for (int i = 0; i < m_h; i++) memcpy(ftab[k][i], f[k] + (size_t)i * m_w, sizeof(float) * m_w);
+    for (int k = 0; k < 2; k++)
+        if (o[k] && o[k] != otab[k][0])
+            for (int i = 0; i < m_h; i++) memcpy(otab[k][i], o[k] + (size_t)i * m_w, m_w);
+}
+
+bool bao_flow_patchmatch_multiscale_cuda::set_occlusion_params(float alpha, float beta)
+{
+    if (!m_ctx) return false;
+    if (eppm_set_occlusion_params(m_ctx, alpha, beta) != EPPM_OK) {
+        fprintf(stderr, "bao_flow_patchmatch_multiscale_cuda::set_occlusion_params: %s\n", eppm_last_error());
+        return false;
+    }
+    return true;
 }

@@ -62,6 +62,18 @@ struct eppm_ctx {
     std::vector<float*> out_u, out_v;   // per active pair: where eppm_compute_begin_into sent the planes directly (NULL: staging)
     HostHold out_hold;                  // the registered blocks those planes lie in, in use until eppm_compute_end
     bool have_images = false, have_flow = false;
+    // Bidirectional calls (eppm_compute_bidirectional*): their own allocation, made by the first such call -- a forward-only context never
+    // has it.  npairs blocks bwd_stride bytes apart, each: the backward flow pyramid, then the host boundary's planar bu | bv (h*w*8 bytes)
+    // followed by occ1 and occ2 (h*w bytes each).  The backward path itself runs in slab planes the forward path has finished with
+    // (flow_tmp, d_uv, nnf2 / nnf_tmp2, wmf_ws, c2f_cost9); each level's result is copied into bflow.
+    char* bwd = nullptr;
+    size_t bwd_stride = 0, bwd_bytes = 0, h_bwd_bytes = 0;
+    float* bflow[kMaxLevels] = {};
+    float* d_buv = nullptr;
+    uint8_t *occ1 = nullptr, *occ2 = nullptr;
+    uint8_t* h_bwd = nullptr;           // pinned, npairs x (bu | bv | occ1 | occ2), allocated on the first host-boundary bidirectional call
+    float occ_alpha = 0.01f, occ_beta = 0.5f;
+    bool have_bwd = false;              // the planes above hold the last call's results
     int timing = 0;                     // 0 off, 1 every stage, 2 only the dominant kernel (the candidate refine)
     std::vector<StageEv> ev;
     std::vector<StageEv> ev_prep;
@@ -133,6 +145,8 @@ extern "C" int eppm_destroy(eppm_ctx* c)
     }
     if (c->ev_h2d) (void)hipEventDestroy(c->ev_h2d);
     cache_free(c->h_flow, c->h_flow_bytes, true, c->device);
+    cache_free(c->bwd, c->bwd_bytes, false, c->device);
+    cache_free(c->h_bwd, c->h_bwd_bytes, true, c->device);
     rng_free(c->rng);
     if (c->own_stream && c->stream) pooled_stream_destroy(c->stream, c->device);
     delete c;
@@ -463,6 +477,7 @@ static int compute_all(eppm_ctx* c)
 {
     if (!c->have_images) return set_err(EPPM_ERR_STATE, "eppm_compute: no images set");
     HIPCHK(hipSetDevice(c->device));
+    c->have_bwd = false;
     hipStream_t s = c->stream;
     const Batch bt = c->bt();
     const int L = c->nl - 1;                                            // pm_layer, driver :219
@@ -518,6 +533,103 @@ static int compute_all(eppm_ctx* c)
     return EPPM_OK;
 }
 
+// ---- bidirectional calls: the backward flow (the reference's commented-out branch, driver :243-245, completed symmetrically) and the
+// forward-backward occlusion masks.  DESIGN.md section 10. ----
+
+// the backward planes of every pair: one allocation, made on the first bidirectional call and kept until eppm_destroy
+static int bwd_alloc(eppm_ctx* c)
+{
+    if (c->bwd) return EPPM_OK;
+    size_t off = 0;
+    auto take = [&](size_t bytes) { const size_t o = off; off = (off + bytes + 255) & ~(size_t)255; return o; };
+    size_t flow_off[kMaxLevels];
+    for (int l = 0; l < c->nl; l++) flow_off[l] = take((size_t)c->W[l] * c->H[l] * 8);
+    const size_t n = (size_t)c->h * c->w;
+    const size_t out_off = take(n * 10);                 // bu | bv | occ1 | occ2: one device-to-host copy per pair
+    c->bwd_stride = (off + 4095) & ~(size_t)4095;
+    const size_t bytes = c->bwd_stride * c->npairs;
+    const hipError_t e = cache_alloc((void**)&c->bwd, bytes, false, c->device);
+    if (e != hipSuccess) { (void)hipGetLastError(); c->bwd = nullptr; return set_err(EPPM_ERR_HIP, "hipMalloc of %zu bytes (backward planes) failed: %s", bytes, hipGetErrorString(e)); }
+    c->bwd_bytes = bytes;
+    for (int l = 0; l < c->nl; l++) c->bflow[l] = (float*)(c->bwd + flow_off[l]);
+    c->d_buv = (float*)(c->bwd + out_off);
+    c->occ1 = (uint8_t*)(c->bwd + out_off + n * 8);
+    c->occ2 = c->occ1 + n;
+    return EPPM_OK;
+}
+
+// level l's backward flow of every active pair: from a slab plane (pairs `stride` apart) into bflow[l] (pairs `bwd_stride` apart)
+static int keep_bwd(eppm_ctx* c, int l, const float* src)
+{
+    const size_t bytes = (size_t)c->W[l] * c->H[l] * 8;
+    for (int k = 0; k < c->n_active; k++)
+        HIPCHK(hipMemcpyAsync(c->bwd + (size_t)k * c->bwd_stride + ((char*)c->bflow[l] - c->bwd), c->of_pair(src, k), bytes, hipMemcpyDeviceToDevice, c->stream));
+    return EPPM_OK;
+}
+
+// After compute_all, on the same stream: the backward branch from (nnf2, cost2) as the two-pass left-right check left them, then both
+// occlusion masks.  Every kernel is the forward path's, with image 2 as the guide and the refine's planes swapped.
+static int backward_all(eppm_ctx* c)
+{
+    hipStream_t s = c->stream;
+    const Batch bt = c->bt();
+    const int L = c->nl - 1;
+    const int lw = c->W[L], lh = c->H[L];
+
+    stage_begin(c, c->ev, "l2_post_bwd");
+    launch_outlier(c->nnf_tmp2, c->cost2, c->nnf2, lw, lh, lw, lw, s, bt);
+    std::swap(c->nnf2, c->nnf_tmp2);
+    if (launch_wmf(c->nnf2, c->nnf_tmp2, c->img2[L], (int)(c->ipitch[L] / 4), lw, lh, lw, c->lut_wmf, c->prm.wmf_iters, 1, c->wmf_ws, s, bt) != c->nnf2)
+        std::swap(c->nnf2, c->nnf_tmp2);
+    launch_fill_holes(c->nnf_tmp2, c->nnf2, c->img2[L], (int)(c->ipitch[L] / 4), lw, lh, lw, s, bt);
+    std::swap(c->nnf2, c->nnf_tmp2);
+    float* cur = c->flow_tmp[L];                     // the flow so far, in a slab plane
+    launch_nnf2flow(cur, lw, c->nnf2, lw, lw, lh, s, bt);
+    if (L > 0) CHK(keep_bwd(c, L, cur));
+    stage_end(c, c->ev);
+
+    // level l: resize + refine in flow_tmp[l], smoothing into d_uv (h*w float2: room for any level; the forward flow is split into it
+    // only after this branch)
+    float* scratch = c->d_uv;
+    static const char* up_names[] = {"upsample_bwd_L0", "upsample_bwd_L1", "upsample_bwd_L2", "upsample_bwd_L3", "upsample_bwd_L4", "upsample_bwd_L5", "upsample_bwd_L6"};
+    static const char* rf_names[] = {"c2f_refine_bwd_L0", "c2f_refine_bwd_L1", "c2f_refine_bwd_L2", "c2f_refine_bwd_L3", "c2f_refine_bwd_L4", "c2f_refine_bwd_L5", "c2f_refine_bwd_L6"};
+    static const char* bl_names[] = {"flow_blf_bwd_L0", "flow_blf_bwd_L1", "flow_blf_bwd_L2", "flow_blf_bwd_L3", "flow_blf_bwd_L4", "flow_blf_bwd_L5", "flow_blf_bwd_L6"};
+    for (int l = L - 1; l >= 0; l--) {
+        stage_begin(c, c->ev, up_names[l]);
+        launch_resize_flow(c->flow_tmp[l], c->H[l], c->W[l], cur, c->H[l + 1], c->W[l + 1], 2.0f, 2.0f, s, bt);
+        stage_end(c, c->ev);
+        stage_begin(c, c->ev, rf_names[l]);
+        launch_c2f_refine(planes(c, l, true), c->flow_tmp[l], c->lut_pm, c->prm.patch_r, c->c2f_cost9[l], s, bt, c->opt_no_split != 0);
+        stage_end(c, c->ev);
+        stage_begin(c, c->ev, bl_names[l]);
+        launch_flow_blf(scratch, c->flow_tmp[l], c->img2[l], (int)(c->ipitch[l] / 4), c->W[l], c->H[l], c->W[l], c->lut_blf, s, bt);
+        cur = scratch;
+        if (l > 0) CHK(keep_bwd(c, l, cur));
+        stage_end(c, c->ev);
+    }
+    stage_begin(c, c->ev, "flow_blf_bwd_final");
+    float* out = (cur == scratch) ? c->flow_tmp[0] : scratch;
+    launch_flow_blf(out, cur, c->img2[0], (int)(c->ipitch[0] / 4), c->W[0], c->H[0], c->W[0], c->lut_blf, s, bt);
+    CHK(keep_bwd(c, 0, out));
+    stage_end(c, c->ev);
+
+    stage_begin(c, c->ev, "fb_occlusion");
+    launch_fb_occlusion(c->occ1, c->occ2, c->flow[0], c->stride, c->bflow[0], c->bwd_stride, c->h, c->w, c->occ_alpha, c->occ_beta, bt.n, 2, s);
+    stage_end(c, c->ev);
+    HIPCHK(hipGetLastError());
+    c->have_bwd = true;
+    return EPPM_OK;
+}
+
+static int compute_bidir_all(eppm_ctx* c)
+{
+    if (!c->have_images) return set_err(EPPM_ERR_STATE, "eppm_compute_bidirectional: no images set");
+    HIPCHK(hipSetDevice(c->device));
+    CHK(bwd_alloc(c));
+    CHK(compute_all(c));
+    return backward_all(c);
+}
+
 extern "C" int eppm_compute_device(eppm_ctx* c, void* d_flow)
 {
     if (!c) return set_err(EPPM_ERR_ARG, "NULL ctx");
@@ -540,11 +652,21 @@ extern "C" int eppm_batch_compute_device(eppm_ctx* c, void* const* d_flows)
 // de-interleave (on the device) and the device-to-host copies and returns; end waits.  When begin knows the destination planes
 // and they lie in registered memory, the copy engine writes them directly; otherwise the planes land in the context's pinned
 // staging and end copies them out.
-static int compute_begin_impl(eppm_ctx* c, int n_out, float* const* u, float* const* v)
+static int compute_begin_impl(eppm_ctx* c, int n_out, float* const* u, float* const* v, bool bidir)
 {
-    CHK(compute_all(c));
+    CHK(bidir ? compute_bidir_all(c) : compute_all(c));
     const size_t n = (size_t)c->h * c->w;
     launch_split_flow(c->d_uv, c->flow[0], (int)n, c->stream, c->bt());                                                           // driver :302-306, on the device
+    if (bidir) {
+        // bu | bv | occ1 | occ2 of every active pair into the pinned staging (one copy each)
+        launch_split_flow(c->d_buv, c->bflow[0], (int)n, c->stream, Batch{c->n_active, c->bwd_stride});
+        if (!c->h_bwd) {
+            HIPCHK(cache_alloc((void**)&c->h_bwd, n * 10 * c->npairs, true, c->device));
+            c->h_bwd_bytes = n * 10 * c->npairs;
+        }
+        for (int k = 0; k < c->n_active; k++)
+            HIPCHK(hipMemcpyAsync(c->h_bwd + (size_t)k * n * 10, c->bwd + (size_t)k * c->bwd_stride + ((char*)c->d_buv - c->bwd), n * 10, hipMemcpyDeviceToHost, c->stream));
+    }
     for (int k = 0; k < c->n_active; k++) {                                                                                       // driver :299
         float* du = (u && k < n_out) ? u[k] : nullptr;
         float* dv = (v && k < n_out) ? v[k] : nullptr;
@@ -565,9 +687,9 @@ static int compute_begin_impl(eppm_ctx* c, int n_out, float* const* u, float* co
     c->flow_pending = true;
     return EPPM_OK;
 }
-static int compute_begin(eppm_ctx* c, int n_out, float* const* u, float* const* v)
+static int compute_begin(eppm_ctx* c, int n_out, float* const* u, float* const* v, bool bidir = false)
 {
-    const int r = compute_begin_impl(c, n_out, u, v);
+    const int r = compute_begin_impl(c, n_out, u, v, bidir);
     if (r != EPPM_OK && !c->out_hold.v.empty()) {
         // eppm_compute_end will refuse to run (nothing is pending): the planes held so far must not stay in use until the context dies.
         // Copies already queued into them drain first.
@@ -641,6 +763,64 @@ extern "C" int eppm_batch_compute(eppm_ctx* c, float* const* u, float* const* v)
     return compute_end(c, c->n_active, u, v);
 }
 
+// the backward outputs of a finished bidirectional call, from the pinned staging; NULL tables / entries are skipped
+static void bwd_copy_out(eppm_ctx* c, int n_out, float* const* bu, float* const* bv, uint8_t* const* o1, uint8_t* const* o2)
+{
+    const size_t n = (size_t)c->h * c->w;
+    for (int k = 0; k < n_out && k < c->n_active; k++) {
+        const uint8_t* src = c->h_bwd + (size_t)k * n * 10;
+        if (bu && bu[k]) memcpy(bu[k], src, n * 4);
+        if (bv && bv[k]) memcpy(bv[k], src + n * 4, n * 4);
+        if (o1 && o1[k]) memcpy(o1[k], src + n * 8, n);
+        if (o2 && o2[k]) memcpy(o2[k], src + n * 9, n);
+    }
+}
+
+static int compute_bidir(eppm_ctx* c, int n_out, float* const* u, float* const* v, float* const* bu, float* const* bv, uint8_t* const* o1,
+                         uint8_t* const* o2)
+{
+    if (c->flow_pending) return set_err(EPPM_ERR_STATE, "eppm_compute_bidirectional: an eppm_compute_begin is pending");
+    CHK(compute_begin(c, n_out, u, v, true));
+    CHK(compute_end(c, n_out, u, v));
+    bwd_copy_out(c, n_out, bu, bv, o1, o2);
+    return EPPM_OK;
+}
+
+extern "C" int eppm_compute_bidirectional(eppm_ctx* c, float* u, float* v, float* bu, float* bv, uint8_t* occ1, uint8_t* occ2)
+{
+    if (!c || !u || !v) return set_err(EPPM_ERR_ARG, "eppm_compute_bidirectional: NULL argument");
+    return compute_bidir(c, 1, &u, &v, &bu, &bv, &occ1, &occ2);
+}
+
+extern "C" int eppm_batch_compute_bidirectional(eppm_ctx* c, float* const* u, float* const* v, float* const* bu, float* const* bv,
+                                                uint8_t* const* occ1, uint8_t* const* occ2)
+{
+    if (!c || !u || !v) return set_err(EPPM_ERR_ARG, "eppm_batch_compute_bidirectional: NULL argument");
+    return compute_bidir(c, c->n_active, u, v, bu, bv, occ1, occ2);
+}
+
+extern "C" int eppm_compute_bidirectional_device(eppm_ctx* c, void* d_flow, void* d_flow_bwd, void* d_occ1, void* d_occ2)
+{
+    if (!c) return set_err(EPPM_ERR_ARG, "eppm_compute_bidirectional_device: NULL ctx");
+    CHK(compute_bidir_all(c));
+    const size_t n = (size_t)c->h * c->w;
+    if (d_flow) HIPCHK(hipMemcpyAsync(d_flow, c->flow[0], n * 8, hipMemcpyDeviceToDevice, c->stream));
+    if (d_flow_bwd) HIPCHK(hipMemcpyAsync(d_flow_bwd, c->bflow[0], n * 8, hipMemcpyDeviceToDevice, c->stream));
+    if (d_occ1) HIPCHK(hipMemcpyAsync(d_occ1, c->occ1, n, hipMemcpyDeviceToDevice, c->stream));
+    if (d_occ2) HIPCHK(hipMemcpyAsync(d_occ2, c->occ2, n, hipMemcpyDeviceToDevice, c->stream));
+    return EPPM_OK;
+}
+
+extern "C" int eppm_set_occlusion_params(eppm_ctx* c, float alpha, float beta)
+{
+    if (!c) return set_err(EPPM_ERR_ARG, "eppm_set_occlusion_params: NULL ctx");
+    if (!(alpha >= 0 && isfinite(alpha)) || !(beta >= 0 && isfinite(beta)))
+        return set_err(EPPM_ERR_ARG, "eppm_set_occlusion_params: alpha %g, beta %g must be finite and >= 0", alpha, beta);
+    c->occ_alpha = alpha;
+    c->occ_beta = beta;
+    return EPPM_OK;
+}
+
 extern "C" int eppm_synchronize(eppm_ctx* c)
 {
     if (!c) return set_err(EPPM_ERR_ARG, "NULL ctx");
@@ -681,16 +861,23 @@ extern "C" int eppm_batch_get_plane(eppm_ctx* c, int pair, const char* name, int
     HIPCHK(hipStreamSynchronize(c->stream));
     const int w = c->W[level], h = c->H[level], L = c->nl - 1;
     const void* src = nullptr;
-    size_t esz = 0, pitch = 0;
+    size_t esz = 0, pitch = 0, pstride = c->stride;
     std::string n(name);
     if (n == "img1" || n == "img2") { src = (n == "img1") ? c->img1[level] : c->img2[level]; esz = 4; pitch = c->ipitch[level]; }
     else if (n == "census1" || n == "census2") { src = (n == "census1") ? c->cen1[level] : c->cen2[level]; esz = 1; pitch = c->cpitch[level]; }
     else if (n == "flow") { src = c->flow[level]; esz = 8; pitch = (size_t)w * 8; }
     else if (level == L && (n == "nnf1" || n == "nnf2")) { src = (n == "nnf1") ? c->nnf1 : c->nnf2; esz = 4; pitch = (size_t)w * 4; }
     else if (level == L && (n == "cost1" || n == "cost2")) { src = (n == "cost1") ? c->cost1 : c->cost2; esz = 4; pitch = (size_t)w * 4; }
+    else if (n == "flow_bwd" || (level == 0 && (n == "occ1" || n == "occ2"))) {
+        if (!c->have_bwd) return set_err(EPPM_ERR_STATE, "eppm_get_plane: '%s' needs a bidirectional call first", name);
+        if (n == "flow_bwd") { src = c->bflow[level]; esz = 8; }
+        else { src = (n == "occ1") ? c->occ1 : c->occ2; esz = 1; }
+        pitch = (size_t)w * esz;
+        pstride = c->bwd_stride;
+    }
     else return set_err(EPPM_ERR_ARG, "eppm_get_plane: unknown plane '%s' at level %d", name, level);
     if (dst_bytes < (size_t)w * h * esz) return set_err(EPPM_ERR_ARG, "eppm_get_plane: dst too small");
-    HIPCHK(hipMemcpy2D(dst, (size_t)w * esz, c->of_pair((const char*)src, pair), pitch, (size_t)w * esz, h, hipMemcpyDeviceToHost));
+    HIPCHK(hipMemcpy2D(dst, (size_t)w * esz, (const char*)src + (size_t)pair * pstride, pitch, (size_t)w * esz, h, hipMemcpyDeviceToHost));
     return EPPM_OK;
 }
 

@@ -173,6 +173,12 @@ void launch_flow_blf(float* out, const float* in, const uint32_t* img, int ipitc
 // interleaved float2 flow -> planar u | v (2*n floats) on the device: compute_flow's de-interleave, driver :302-306
 void launch_split_flow(float* uv, const float* flow, int n, hipStream_t s, Batch bt = kOnePair);
 
+// ---- occlusion masks of a bidirectional call (k_occ.hip; the test itself: fb_occlusion.h) ----
+// ndir 2: occ1 <- (F fwd, G bwd) and occ2 <- (F bwd, G fwd) for npairs pairs (fwd at fwd_stride, bwd / occ1 / occ2 at bwd_stride bytes apart);
+// ndir 1: occ1 <- (F fwd, G bwd) of one pair (npairs 1).  Fields: h*w float2, masks: h*w bytes, all unpitched.
+void launch_fb_occlusion(uint8_t* occ1, uint8_t* occ2, const float* fwd, size_t fwd_stride, const float* bwd, size_t bwd_stride, int h, int w,
+                         float alpha, float beta, int npairs, int ndir, hipStream_t s);
+
 // ---- flow colour coding (k_color.hip) ----
 // rgba: h*w packed R | G<<8 | B<<16 (alpha 0); flow: h*w float2
 void launch_flow_to_color(uint32_t* rgba, const float* flow, int h, int w, float max_disp_x, float max_disp_y, hipStream_t s, Batch bt = kOnePair);

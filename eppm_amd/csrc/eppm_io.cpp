@@ -10,6 +10,7 @@
 #include <vector>
 
 #include "../../include/eppm.h"
+#include "fb_occlusion.h"
 
 static int read_ppm_header(FILE* f, int* type, int* w, int* h)
 {
@@ -234,5 +235,22 @@ extern "C" int eppm_flow_to_color_host(uint8_t* rgb, const float* u, const float
             o[b] = (uint8_t)(int)(255.0 * col);            // computeColor writes B,G,R; bao_convert_flow_to_colorshow swaps to R,G,B
         }
     }
+    return EPPM_OK;
+}
+
+// the occlusion masks' criterion on host flows (fb_occlusion.h, the kernel's own per-pixel function): occ[y*w+x] for F = (u, v), G = (bu, bv)
+extern "C" int eppm_fb_occlusion_host(uint8_t* occ, const float* u, const float* v, const float* bu, const float* bv, int h, int w, float alpha,
+                                      float beta)
+{
+    if (!occ || !u || !v || !bu || !bv || h < 1 || w < 1) return EPPM_ERR_ARG;
+    if (!(alpha >= 0 && isfinite(alpha)) || !(beta >= 0 && isfinite(beta))) return EPPM_ERR_ARG;
+    const size_t n = (size_t)h * w;
+    std::vector<float> G(n * 2);
+    for (size_t i = 0; i < n; i++) { G[2 * i] = bu[i]; G[2 * i + 1] = bv[i]; }
+    for (int y = 0; y < h; y++)
+        for (int x = 0; x < w; x++) {
+            const size_t i = (size_t)y * w + x;
+            occ[i] = eppm::fb_occlusion_pixel(x, y, u[i], v[i], G.data(), h, w, alpha, beta);
+        }
     return EPPM_OK;
 }

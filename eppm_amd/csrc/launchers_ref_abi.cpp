@@ -432,6 +432,17 @@ extern "C" int eppm_flow_to_color(eppm_uchar4* d_rgba, const eppm_float2* d_flow
     launch_flow_to_color((uint32_t*)d_rgba, (const float*)d_flow, h, w, max_disp_x, max_disp_y, g_stream);
     return finish();
 }
+// ---- the occlusion kernel of a bidirectional call on caller planes (k_occ.hip; eppm_fb_occlusion_host is its host form) ----
+extern "C" int eppm_fb_occlusion(uint8_t* d_occ, const eppm_float2* d_flow, const eppm_float2* d_other, int h, int w, float alpha, float beta)
+{
+    if (!d_occ || !d_flow || !d_other || h < 1 || w < 1) return set_err(EPPM_ERR_ARG, "eppm_fb_occlusion: bad argument");
+    if (!(alpha >= 0 && isfinite(alpha)) || !(beta >= 0 && isfinite(beta)))
+        return set_err(EPPM_ERR_ARG, "eppm_fb_occlusion: alpha %g, beta %g must be finite and >= 0", alpha, beta);
+    LAUNCHER_BEGIN_INT;
+    (void)ds;
+    launch_fb_occlusion(d_occ, nullptr, (const float*)d_flow, 0, (const float*)d_other, 0, h, w, alpha, beta, 1, 1, g_stream);
+    return finish();
+}
 // the C++-linkage symbol the reference's driver declares at :64 (defaults 100,100 there; the live call passes 20,20)
 void bao_cuda_convert_flow_to_colorshow(uchar4* rgbflow, float2* flow_vec, int h, int w, float max_disp_x, float max_disp_y)
 {

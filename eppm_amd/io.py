@@ -78,3 +78,16 @@ def flow_to_color(u, v):
     check(lib().eppm_flow_to_color_host(rgb.ctypes.data_as(C.c_void_p), u.ctypes.data_as(C.c_void_p), v.ctypes.data_as(C.c_void_p), h, w),
           "eppm_flow_to_color_host")
     return rgb
+
+
+def fb_occlusion(u, v, bu, bv, alpha=0.01, beta=0.5):
+    """(h, w) uint8 forward-backward occlusion mask of the pixels of (u, v)'s image against the other direction's flow (bu, bv):
+    0 consistent, 1 inconsistent, 2 leaves the frame, 3 unknown vector (eppm_fb_occlusion_host; the bidirectional call's kernel)."""
+    arrs = [np.ascontiguousarray(a, np.float32) for a in (u, v, bu, bv)]
+    h, w = arrs[0].shape
+    if any(a.shape != (h, w) for a in arrs):
+        raise ValueError("fb_occlusion: the four planes must have one shape")
+    occ = np.empty((h, w), np.uint8)
+    check(lib().eppm_fb_occlusion_host(occ.ctypes.data_as(C.c_void_p), *[a.ctypes.data_as(C.c_void_p) for a in arrs], h, w,
+                                       C.c_float(alpha), C.c_float(beta)), "eppm_fb_occlusion_host")
+    return occ

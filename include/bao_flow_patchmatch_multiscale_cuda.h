@@ -42,6 +42,14 @@ public:
     // is destroyed or init() is called again.  false: unknown name.
     bool set_option(const char* name, long long value);
     eppm_ctx* handle() const { return m_ctx; }
+    // compute_flow plus the backward flow (image 2 -> image 1) and the forward-backward occlusion masks (eppm_compute_bidirectional):
+    // disp1_x, disp1_y receive what compute_flow writes, disp2_x, disp2_y the backward flow (the demo's disp2_x / disp2_y, main.cpp:46-51),
+    // occ1 / occ2 (optional, h row pointers to w bytes) the masks of image 1's / image 2's pixels: 0 consistent, 1 inconsistent, 2 leaves
+    // the frame, 3 unknown vector.  Same row-pointer tables, contiguous-block and pin_caller_buffers handling as compute_flow.
+    void compute_flow_bidirectional(float** disp1_x, float** disp1_y, float** disp2_x, float** disp2_y, unsigned char** occ1 = NULL,
+                                    unsigned char** occ2 = NULL);
+    // alpha, beta of the masks' criterion (eppm_set_occlusion_params; defaults 0.01, 0.5); after init().  false: bad values or no context
+    bool set_occlusion_params(float alpha, float beta);
 
 private:
     void _destroy();

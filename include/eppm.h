@@ -149,8 +149,38 @@ int  eppm_level_dims(const eppm_ctx* ctx, int level, int* h, int* w);
 
 /* Copy an internal plane to the host, tightly packed (row = w elements).  Names:
  *  "img1","img2" (uchar4), "census1","census2" (u8), "nnf1","nnf2" (short2), "cost1","cost2" (f32),
- *  "flow" (float2).  Valid after the stage that produces it has run. */
+ *  "flow" (float2).  Valid after the stage that produces it has run.
+ *  After a bidirectional call (below) also: "flow_bwd" (float2, every level: the backward flow as that level left it), "occ1", "occ2"
+ *  (u8, level 0: the occlusion masks), and "nnf2" at the PatchMatch level is the backward NNF after hole filling.  A later
+ *  forward-only compute invalidates "flow_bwd", "occ1" and "occ2" (EPPM_ERR_STATE). */
 int  eppm_get_plane(eppm_ctx* ctx, const char* name, int level, void* dst, size_t dst_bytes);
+
+/* ----------------------------------------------------------------------------------------
+ * bidirectional flow with forward-backward occlusion masks.  Opt-in: a context that never makes one of these
+ * calls allocates and launches exactly what it did without them.  The first call on a context allocates its backward planes (npairs
+ * of them on a batch context); eppm_destroy frees them.
+ *  forward (u, v): bit-identical to eppm_compute's.
+ *  backward (bu, bv): image 2 -> image 1, from the backward NNF the coarsest level's PatchMatch computes anyway (the reference's
+ *    commented-out branch, driver .cpp:243-245, completed symmetrically): outlier removal, weighted median, hole filling and every
+ *    coarse-to-fine level guided by image 2.  NOT the forward flow of the swapped pair (that would draw other random numbers).
+ *  occ1 / occ2: h*w bytes each, for image 1's / image 2's pixels: 0 consistent, 1 inconsistent (|F + G(x + F)|^2 > alpha (|F|^2 +
+ *    |G|^2) + beta, G bilinear, or a tap of G unknown), 2 the vector leaves the frame, 3 the vector is unknown (|component| > 1e9, NaN).
+ * The pipelined eppm_compute_begin / eppm_compute_end forms have no bidirectional counterpart.
+ * -------------------------------------------------------------------------------------- */
+/* forward-backward: u,v forward (== eppm_compute), bu,bv backward, occ1/occ2 h*w bytes (codes 0..3 above); any of bu,bv,occ1,occ2 may be NULL.
+ * Synchronous. */
+int  eppm_compute_bidirectional(eppm_ctx* ctx, float* u, float* v, float* bu, float* bv, uint8_t* occ1, uint8_t* occ2);
+/* asynchronous; interleaved float2 flows and h*w-byte masks of pair 0 into device memory; NULLs allowed (results stay in the context:
+ * eppm_get_plane) */
+int  eppm_compute_bidirectional_device(eppm_ctx* ctx, void* d_flow, void* d_flow_bwd, void* d_occ1, void* d_occ2);
+/* every active pair; u, v: n plane pointers (required); bu, bv, occ1, occ2: NULL or n pointers (NULL entries allowed).  Synchronous. */
+int  eppm_batch_compute_bidirectional(eppm_ctx* ctx, float* const* u, float* const* v, float* const* bu, float* const* bv,
+                                      uint8_t* const* occ1, uint8_t* const* occ2);
+/* alpha, beta of the masks' criterion (defaults 0.01, 0.5: Sundaram, Brox & Keutzer, ECCV 2010); both finite, >= 0 */
+int  eppm_set_occlusion_params(eppm_ctx* ctx, float alpha, float beta);
+/* the kernel alone on unpitched device planes (like eppm_flow_to_color): d_occ h*w bytes for F = d_flow, G = d_other (h*w float2
+ * each); on the launcher stream, synchronous like the other launchers */
+int  eppm_fb_occlusion(uint8_t* d_occ, const eppm_float2* d_flow, const eppm_float2* d_other, int h, int w, float alpha, float beta);
 
 /* Per-stage device times in ms (hipEvent pairs on the context's stream), one entry per stage per
  * call since the last eppm_clear_stage_times (names repeat across calls; prepare entries first).
@@ -158,7 +188,8 @@ int  eppm_get_plane(eppm_ctx* ctx, const char* name, int level, void* dst, size_
 int  eppm_stage_times(eppm_ctx* ctx, const char** names, float* ms, int max);
 int  eppm_clear_stage_times(eppm_ctx* ctx);
 /* 0: no events (default); 1: an event pair around every stage; 2: only around the dominant kernel (the candidate
- * refine, entries "c2f_refine_L<l>").  Events come from a per-context pool: none is created in a steady-state step. */
+ * refine, entries "c2f_refine_L<l>").  A bidirectional call adds (mode 1) "l2_post_bwd", "upsample_bwd_L<l>", "c2f_refine_bwd_L<l>",
+ * "flow_blf_bwd_L<l>", "flow_blf_bwd_final" and "fb_occlusion".  Events come from a per-context pool: none is created in a steady-state step. */
 int  eppm_enable_stage_timing(eppm_ctx* ctx, int on);
 
 const char* eppm_last_error(void);
@@ -302,6 +333,10 @@ int  eppm_flow_error_percentage(const float* u, const float* v, const float* gt_
                                 uint8_t* error_map, float* fraction);
 /* Both components clamped to [-|cutoff|, |cutoff|]; unknown vectors pass through unless cut_invalid (bao_flow_cutoff, :166-197). */
 int  eppm_flow_cutoff(float* u_out, float* v_out, const float* u, const float* v, int h, int w, int cutoff, int cut_invalid);
+/* The occlusion criterion above on host planes (flows read from .flo files): occ h*w bytes for F = (u, v), G = (bu, bv); bit-identical
+ * to eppm_fb_occlusion. */
+int  eppm_fb_occlusion_host(uint8_t* occ, const float* u, const float* v, const float* bu, const float* bv, int h, int w,
+                            float alpha, float beta);
 /* Host colour coding scaled by the field's largest known radius, unknown vectors black; rgb: h*w*3 bytes R,G,B
  * (bao_convert_flow_to_colorshow, :200-231, on Middlebury's computeColor, 3rdparty/middlebury/colorcode.cpp:30-85).  Where the
  * reference is undefined this is defined: a field with no motion or no known vector (largest radius 0: 0/0 there, then

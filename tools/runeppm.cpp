@@ -17,6 +17,8 @@
 //   --pin             set_option("pin_caller_buffers", 1): the class registers the image and flow blocks for DMA, no host copies
 //   --out file.flo    output name (same as the third positional argument)
 //   --gt file.flo     print EPE / AAE of the result against a ground-truth .flo (bao_flow_tools.cpp:64-111)
+//   --backward f.flo  the timed window runs compute_flow_bidirectional instead: also write the backward flow (image 2 -> image 1)
+//   --occlusion f.pgm ... and image 1's occlusion mask as a P5 PGM: 0 consistent, 255 inconsistent, 128 leaves the frame, 64 unknown
 #include <atomic>
 #include <chrono>
 #include <cstdio>
@@ -44,7 +46,7 @@ struct Array3 {       // bao_alloc<T>(n,r,c): one contiguous block reachable thr
 };
 
 struct Options {
-    const char *f1 = "frame10.ppm", *f2 = "frame11.ppm", *fo = "flow.flo", *gt = nullptr;
+    const char *f1 = "frame10.ppm", *f2 = "frame11.ppm", *fo = "flow.flo", *gt = nullptr, *fb = nullptr, *focc = nullptr;
     int sw = 0, sh = 0, pairs = 1, gpus = 1, batch = 1;
     std::vector<std::pair<std::string, long long>> opts;
 };
@@ -94,7 +96,8 @@ static bool apply_opt(eppm_params& p, const std::string& name, long long v)
 static int usage()
 {
     fprintf(stderr, "usage: runeppm [--size WxH] [--seed N] [--levels N] [--patch-r N] [--iters N] [--propagation M]\n"
-                    "               [--pin] [--pairs P] [--gpus G] [--batch B] [--gt file.flo] [--out file.flo] [img1.ppm img2.ppm [out.flo]]\n");
+                    "               [--pin] [--pairs P] [--gpus G] [--batch B] [--gt file.flo] [--out file.flo] [--backward file.flo]\n"
+                    "               [--occlusion file.pgm] [img1.ppm img2.ppm [out.flo]]\n");
     return 2;
 }
 
@@ -119,6 +122,8 @@ int main(int argc, char** argv)
         else if (!strcmp(a, "--pin")) o.opts.push_back({"pin_caller_buffers", 1});
         else if (!strcmp(a, "--gt")) { if (i + 1 >= argc) return usage(); o.gt = argv[++i]; }
         else if (!strcmp(a, "--out")) { if (i + 1 >= argc) return usage(); o.fo = argv[++i]; }
+        else if (!strcmp(a, "--backward")) { if (i + 1 >= argc) return usage(); o.fb = argv[++i]; }
+        else if (!strcmp(a, "--occlusion")) { if (i + 1 >= argc) return usage(); o.focc = argv[++i]; }
         else if (a[0] == '-' && a[1] == '-') return usage();
         else pos.push_back(a);
     }
@@ -151,6 +156,16 @@ int main(int argc, char** argv)
     std::vector<float> u((size_t)h * w, 0.f), v((size_t)h * w, 0.f);
     std::vector<float*> ur(h), vr(h);
     for (int i = 0; i < h; i++) { ur[i] = &u[(size_t)i * w]; vr[i] = &v[(size_t)i * w]; }
+    const bool bidir = o.fb || o.focc;
+    std::vector<float> bu, bv;                      // backward flow and image 1's occlusion mask (--backward / --occlusion)
+    std::vector<unsigned char> occ;
+    std::vector<float*> bur, bvr;
+    std::vector<unsigned char*> occr;
+    if (bidir) {
+        bu.assign((size_t)h * w, 0.f); bv.assign((size_t)h * w, 0.f); occ.assign((size_t)h * w, 0);
+        bur.resize(h); bvr.resize(h); occr.resize(h);
+        for (int i = 0; i < h; i++) { bur[i] = &bu[(size_t)i * w]; bvr[i] = &bv[(size_t)i * w]; occr[i] = &occ[(size_t)i * w]; }
+    }
 
     printf("Processing (image size %d * %d * %d)...\n", w, h, nch);
     {
@@ -160,9 +175,10 @@ int main(int argc, char** argv)
         auto t0 = std::chrono::steady_clock::now();
         eppm.init(img1.p(), img2.p(), h, w);                             // main.cpp:63-64: the reference's timed window
         if (!eppm.handle()) return 1;
-        eppm.compute_flow(ur.data(), vr.data());
+        if (bidir) eppm.compute_flow_bidirectional(ur.data(), vr.data(), bur.data(), bvr.data(), occr.data());
+        else eppm.compute_flow(ur.data(), vr.data());
         auto t1 = std::chrono::steady_clock::now();
-        printf("GPU: %.3f s (init + compute_flow)\n", std::chrono::duration<double>(t1 - t0).count());
+        printf("GPU: %.3f s (init + %s)\n", std::chrono::duration<double>(t1 - t0).count(), bidir ? "compute_flow_bidirectional" : "compute_flow");
     }
 
     // steady state: contexts created once, pairs streamed through set_data + compute_flow
@@ -255,5 +271,14 @@ int main(int argc, char** argv)
     }
     printf("Saving flo file...%d*%d\n", h, w);
     if (eppm_save_flo(o.fo, u.data(), v.data(), h, w) != EPPM_OK) { fprintf(stderr, "cannot write %s\n", o.fo); return 1; }
+    if (o.fb && eppm_save_flo(o.fb, bu.data(), bv.data(), h, w) != EPPM_OK) { fprintf(stderr, "cannot write %s\n", o.fb); return 1; }
+    if (o.focc) {
+        static const unsigned char grey[4] = {0, 255, 128, 64};      // consistent, inconsistent, leaves the frame, unknown
+        FILE* f = fopen(o.focc, "wb");
+        bool ok = f && fprintf(f, "P5\n%d %d\n255\n", w, h) > 0;
+        for (size_t i = 0; ok && i < occ.size(); i++) ok = fputc(grey[occ[i] & 3], f) != EOF;
+        if (f && fclose(f) != 0) ok = false;
+        if (!ok) { fprintf(stderr, "cannot write %s\n", o.focc); return 1; }
+    }
     return 0;
 }
