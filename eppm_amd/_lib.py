@@ -38,6 +38,7 @@ SYMBOLS = [
     "eppm_flow_error_border", "eppm_flow_error_percentage", "eppm_flow_cutoff", "eppm_flow_to_color_host",
     "eppm_compute_bidirectional", "eppm_compute_bidirectional_device", "eppm_batch_compute_bidirectional", "eppm_set_occlusion_params",
     "eppm_fb_occlusion", "eppm_fb_occlusion_host",
+    "eppm_interpolate", "eppm_interpolate_device", "eppm_batch_interpolate", "eppm_interpolate_frames", "eppm_interpolate_host",
 ]
 
 

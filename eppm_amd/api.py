@@ -55,6 +55,13 @@ def pinned_empty(shape, dtype=np.uint8):
     return np.frombuffer(buf, dtype=dtype, count=int(np.prod(shape))).reshape(shape)
 
 
+def _times(times):
+    ts = [float(t) for t in times]
+    if not ts:
+        raise EppmError("interpolate: at least one time")
+    return (C.c_float * len(ts))(*ts)
+
+
 class EPPM:
     """``init`` / ``set_data`` / ``compute_flow`` as in bao_flow_patchmatch_multiscale_cuda.h:36-44.
 
@@ -138,6 +145,25 @@ class EPPM:
         self._need()
         ptrs = [C.c_void_p(p) if p else None for p in (d_flow, d_flow_bwd, d_occ1, d_occ2)]
         check(lib().eppm_compute_bidirectional_device(self._ctx, *ptrs), "eppm_compute_bidirectional_device")
+
+    def interpolate(self, times):
+        """Frames at the given times between image 1 (t = 0) and image 2 (t = 1) from the last compute_flow_bidirectional
+        (eppm_interpolate): a list of (h, w, 3) uint8 R,G,B arrays."""
+        self._need()
+        ts = _times(times)
+        out = [np.empty((self.h, self.w, 3), np.uint8) for _ in range(len(ts))]
+        ptrs = (C.c_void_p * len(out))(*[a.ctypes.data for a in out])
+        check(lib().eppm_interpolate(self._ctx, len(ts), ts, ptrs, C.c_size_t(self.w * 3)), "eppm_interpolate")
+        return out
+
+    def interpolate_device(self, times, d_ptrs, pitch):
+        """eppm_interpolate_device: asynchronous on the context's stream; d_ptrs: one device RGBA plane (pitch bytes per row) per time."""
+        self._need()
+        ts = _times(times)
+        if len(d_ptrs) != len(ts):
+            raise EppmError("interpolate_device: one device plane per time")
+        ptrs = (C.c_void_p * len(ts))(*d_ptrs)
+        check(lib().eppm_interpolate_device(self._ctx, len(ts), ts, ptrs, C.c_size_t(pitch)), "eppm_interpolate_device")
 
     def compute_flow_color(self, max_disp=(20.0, 20.0)):
         """The optional color_flow output of compute_flow (driver .cpp:308-314): (h, w, 3) uint8 R,G,B of the last flow."""
@@ -297,6 +323,14 @@ class EPPMBatch:
 
     def set_occlusion_params(self, alpha=0.01, beta=0.5):
         check(lib().eppm_set_occlusion_params(self._ctx, C.c_float(alpha), C.c_float(beta)), "eppm_set_occlusion_params")
+
+    def interpolate(self, times):
+        """[[frame at times[k] for k] for each active pair] after compute_flow_bidirectional (eppm_batch_interpolate)."""
+        ts = _times(times)
+        out = [[np.empty((self.h, self.w, 3), np.uint8) for _ in range(len(ts))] for _ in range(self.n)]
+        flat = [a for row in out for a in row]
+        check(lib().eppm_batch_interpolate(self._ctx, len(ts), ts, self._ptrs(flat), C.c_size_t(self.w * 3)), "eppm_batch_interpolate")
+        return out
 
     def compute_flow_device(self, d_flows=None):
         check(lib().eppm_batch_compute_device(self._ctx, self._ptrs(list(d_flows)) if d_flows is not None else None), "eppm_batch_compute_device")

@@ -285,3 +285,20 @@ bool bao_flow_patchmatch_multiscale_cuda::set_occlusion_params(float alpha, floa
     }
     return true;
 }
+
+// the frame at time t between the images of the last compute_flow_bidirectional (eppm_interpolate); img_t: h x w x 3 R,G,B row-pointer
+// tables (bao_alloc<unsigned char>(h, w, 3), as init's images)
+bool bao_flow_patchmatch_multiscale_cuda::interpolate_frame(float t, unsigned char*** img_t)
+{
+    if (!m_ctx || !img_t) return false;
+    std::vector<unsigned char> rgb((size_t)m_h * m_w * 3);
+    uint8_t* out = rgb.data();
+    if (eppm_interpolate(m_ctx, 1, &t, &out, (size_t)m_w * 3) != EPPM_OK) {
+        fprintf(stderr, "bao_flow_patchmatch_multiscale_cuda::interpolate_frame: %s\n", eppm_last_error());
+        return false;
+    }
+    for (int i = 0; i < m_h; i++)
+        for (int j = 0; j < m_w; j++)
+            for (int c = 0; c < 3; c++) img_t[i][j][c] = rgb[((size_t)i * m_w + j) * 3 + c];
+    return true;
+}

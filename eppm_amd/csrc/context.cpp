@@ -1,6 +1,7 @@
 // context.cpp -- eppm_ctx, the object behind class bao_flow_patchmatch_multiscale_cuda: create / destroy (init, _destroy: driver
 // :112-157, :170-209), set_images (set_data :159-168 + _prepare_data :212-215), compute (compute_flow :217-306), planes, stage times.
 #include "api_internal.h"
+#include "interp.h"
 
 using namespace eppm;
 
@@ -74,6 +75,16 @@ struct eppm_ctx {
     uint8_t* h_bwd = nullptr;           // pinned, npairs x (bu | bv | occ1 | occ2), allocated on the first host-boundary bidirectional call
     float occ_alpha = 0.01f, occ_beta = 0.5f;
     bool have_bwd = false;              // the planes above hold the last call's results
+    bool bwd_images = false;            // ... and the raw images they were computed from are still the context's (no set_images since)
+    // Frame interpolation (eppm_interpolate*): its own allocation, made by the first such call, for npairs x
+    // kInterpChunk slots: the splat keys, the two fill planes (itp_plane elements per slot each) and the packed RGB outputs of the
+    // host-pointer forms (h*w*3 bytes per slot); h_itp: pinned copy of those outputs, allocated on the first host-pointer call.
+    char* itp = nullptr;
+    size_t itp_bytes = 0, itp_plane = 0, h_itp_bytes = 0;
+    uint64_t* itp_keys = nullptr;
+    int32_t *itp_fill1 = nullptr, *itp_fill2 = nullptr;
+    uint8_t* itp_rgb = nullptr;
+    uint8_t* h_itp = nullptr;
     int timing = 0;                     // 0 off, 1 every stage, 2 only the dominant kernel (the candidate refine)
     std::vector<StageEv> ev;
     std::vector<StageEv> ev_prep;
@@ -147,6 +158,8 @@ extern "C" int eppm_destroy(eppm_ctx* c)
     cache_free(c->h_flow, c->h_flow_bytes, true, c->device);
     cache_free(c->bwd, c->bwd_bytes, false, c->device);
     cache_free(c->h_bwd, c->h_bwd_bytes, true, c->device);
+    cache_free(c->itp, c->itp_bytes, false, c->device);
+    cache_free(c->h_itp, c->h_itp_bytes, true, c->device);
     rng_free(c->rng);
     if (c->own_stream && c->stream) pooled_stream_destroy(c->stream, c->device);
     delete c;
@@ -362,6 +375,7 @@ static int prepare(eppm_ctx* c)
     HIPCHK(hipGetLastError());
     c->have_images = true;
     c->have_flow = false;
+    c->bwd_images = false;
     return EPPM_OK;
 }
 
@@ -618,6 +632,7 @@ static int backward_all(eppm_ctx* c)
     stage_end(c, c->ev);
     HIPCHK(hipGetLastError());
     c->have_bwd = true;
+    c->bwd_images = true;
     return EPPM_OK;
 }
 
@@ -818,6 +833,124 @@ extern "C" int eppm_set_occlusion_params(eppm_ctx* c, float alpha, float beta)
         return set_err(EPPM_ERR_ARG, "eppm_set_occlusion_params: alpha %g, beta %g must be finite and >= 0", alpha, beta);
     c->occ_alpha = alpha;
     c->occ_beta = beta;
+    return EPPM_OK;
+}
+
+// ---- frame interpolation: the raw RGBA frames (written only by set_images, read only by prepare), the level-0
+// forward flow and both masks of the last bidirectional call, all still in the context ----
+
+static int itp_alloc(eppm_ctx* c)
+{
+    if (c->itp) return EPPM_OK;
+    const size_t n = (size_t)c->h * c->w, slots = (size_t)c->npairs * kInterpChunk;
+    const size_t plane = (n + 63) & ~(size_t)63;
+    const size_t keys = slots * plane * 8, fills = slots * plane * 4, rgb = slots * n * 3;
+    const size_t bytes = keys + 2 * fills + rgb;
+    const hipError_t e = cache_alloc((void**)&c->itp, bytes, false, c->device);
+    if (e != hipSuccess) { (void)hipGetLastError(); c->itp = nullptr; return set_err(EPPM_ERR_HIP, "hipMalloc of %zu bytes (interpolation scratch) failed: %s", bytes, hipGetErrorString(e)); }
+    c->itp_bytes = bytes;
+    c->itp_plane = plane;
+    c->itp_keys = (uint64_t*)c->itp;
+    c->itp_fill1 = (int32_t*)(c->itp + keys);
+    c->itp_fill2 = (int32_t*)(c->itp + keys + fills);
+    c->itp_rgb = (uint8_t*)(c->itp + keys + 2 * fills);
+    return EPPM_OK;
+}
+
+static int interp_check(eppm_ctx* c, const char* what, int nt, const float* t)
+{
+    if (nt < 1 || !t) return set_err(EPPM_ERR_ARG, "%s: nt %d, t %p", what, nt, (const void*)t);
+    for (int k = 0; k < nt; k++)
+        if (!interp_t_ok(t[k])) return set_err(EPPM_ERR_ARG, "%s: t[%d] = %g outside [0, 1]", what, k, t[k]);
+    if (c->flow_pending) return set_err(EPPM_ERR_STATE, "%s: an eppm_compute_begin is pending", what);
+    if (!c->have_bwd || !c->bwd_images) return set_err(EPPM_ERR_STATE, "%s: needs a bidirectional call on the current images", what);
+    return EPPM_OK;
+}
+
+// times t[k0 .. k0+nt) of the first npairs pairs: splat, fill, blend into the packed RGB scratch (d_rgba NULL) or into d_rgba[k0 + k] (pair 0)
+static int interp_chunk(eppm_ctx* c, int npairs, int k0, int nt, const float* t, void* const* d_rgba, size_t pitch)
+{
+    InterpArgs a{};
+    a.img1 = (const uint8_t*)c->raw1; a.img2 = (const uint8_t*)c->raw2; a.img_pitch = c->raw_pitch; a.img_stride = c->stride;
+    a.flow = c->flow[0]; a.flow_stride = c->stride;
+    a.occ1 = c->occ1; a.occ2 = c->occ2; a.occ_stride = c->bwd_stride;
+    a.keys = c->itp_keys; a.fill1 = c->itp_fill1; a.fill2 = c->itp_fill2; a.plane = c->itp_plane;
+    a.rgb = d_rgba ? nullptr : c->itp_rgb;
+    a.rgba_pitch = pitch;
+    a.h = c->h; a.w = c->w; a.nt = nt;
+    for (int k = 0; k < kInterpChunk; k++) {
+        a.t[k] = k < nt ? t[k0 + k] : 0.0f;
+        a.rgba[k] = (d_rgba && k < nt) ? (uint8_t*)d_rgba[k0 + k] : nullptr;
+    }
+    stage_begin(c, c->ev, "interp_splat");
+    launch_interp_splat(a, npairs, c->stream);
+    stage_end(c, c->ev);
+    stage_begin(c, c->ev, "interp_fill");
+    launch_interp_fill(a, npairs, c->stream);
+    stage_end(c, c->ev);
+    stage_begin(c, c->ev, "interp_blend");
+    launch_interp_blend(a, npairs, c->stream);
+    stage_end(c, c->ev);
+    HIPCHK(hipGetLastError());
+    return EPPM_OK;
+}
+
+// host-pointer forms: each chunk's packed RGB outputs cross PCIe once (3 B/px) into the pinned copy, then into the caller's rows
+static int interp_host(eppm_ctx* c, const char* what, int npairs, int nt, const float* t, uint8_t* const* rgb, size_t row_stride)
+{
+    CHK(interp_check(c, what, nt, t));
+    if (!rgb) return set_err(EPPM_ERR_ARG, "%s: NULL rgb", what);
+    for (int k = 0; k < npairs * nt; k++)
+        if (!rgb[k]) return set_err(EPPM_ERR_ARG, "%s: NULL rgb[%d]", what, k);
+    if (row_stride < (size_t)c->w * 3) return set_err(EPPM_ERR_ARG, "%s: row_stride %zu < 3*w", what, row_stride);
+    HIPCHK(hipSetDevice(c->device));
+    CHK(itp_alloc(c));
+    const size_t img = (size_t)c->h * c->w * 3, row = (size_t)c->w * 3;
+    if (!c->h_itp) {
+        HIPCHK(cache_alloc((void**)&c->h_itp, img * c->npairs * kInterpChunk, true, c->device));
+        c->h_itp_bytes = img * c->npairs * kInterpChunk;
+    }
+    for (int k0 = 0; k0 < nt; k0 += kInterpChunk) {
+        const int m = nt - k0 < kInterpChunk ? nt - k0 : kInterpChunk;
+        CHK(interp_chunk(c, npairs, k0, m, t, nullptr, 0));
+        HIPCHK(hipMemcpyAsync(c->h_itp, c->itp_rgb, img * npairs * m, hipMemcpyDeviceToHost, c->stream));
+        HIPCHK(hipStreamSynchronize(c->stream));
+        for (int p = 0; p < npairs; p++)
+            for (int k = 0; k < m; k++) {
+                const uint8_t* src = c->h_itp + img * ((size_t)p * m + k);
+                uint8_t* dst = rgb[(size_t)p * nt + k0 + k];
+                if (row_stride == row) memcpy(dst, src, img);
+                else
+                    for (int y = 0; y < c->h; y++) memcpy(dst + (size_t)y * row_stride, src + (size_t)y * row, row);
+            }
+    }
+    return EPPM_OK;
+}
+
+extern "C" int eppm_interpolate(eppm_ctx* c, int nt, const float* t, uint8_t* const* rgb, size_t row_stride)
+{
+    if (!c) return set_err(EPPM_ERR_ARG, "eppm_interpolate: NULL ctx");
+    return interp_host(c, "eppm_interpolate", 1, nt, t, rgb, row_stride);
+}
+
+extern "C" int eppm_batch_interpolate(eppm_ctx* c, int nt, const float* t, uint8_t* const* rgb, size_t row_stride)
+{
+    if (!c) return set_err(EPPM_ERR_ARG, "eppm_batch_interpolate: NULL ctx");
+    return interp_host(c, "eppm_batch_interpolate", c->n_active, nt, t, rgb, row_stride);
+}
+
+extern "C" int eppm_interpolate_device(eppm_ctx* c, int nt, const float* t, void* const* d_rgba, size_t pitch)
+{
+    if (!c) return set_err(EPPM_ERR_ARG, "eppm_interpolate_device: NULL ctx");
+    CHK(interp_check(c, "eppm_interpolate_device", nt, t));
+    if (!d_rgba) return set_err(EPPM_ERR_ARG, "eppm_interpolate_device: NULL d_rgba");
+    for (int k = 0; k < nt; k++)
+        if (!d_rgba[k]) return set_err(EPPM_ERR_ARG, "eppm_interpolate_device: NULL d_rgba[%d]", k);
+    if (pitch < (size_t)c->w * 4 || (pitch & 3)) return set_err(EPPM_ERR_ARG, "eppm_interpolate_device: bad pitch %zu", pitch);
+    HIPCHK(hipSetDevice(c->device));
+    CHK(itp_alloc(c));
+    for (int k0 = 0; k0 < nt; k0 += kInterpChunk)
+        CHK(interp_chunk(c, 1, k0, nt - k0 < kInterpChunk ? nt - k0 : kInterpChunk, t, d_rgba, pitch));
     return EPPM_OK;
 }
 

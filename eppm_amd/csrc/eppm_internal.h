@@ -179,6 +179,34 @@ void launch_split_flow(float* uv, const float* flow, int n, hipStream_t s, Batch
 void launch_fb_occlusion(uint8_t* occ1, uint8_t* occ2, const float* fwd, size_t fwd_stride, const float* bwd, size_t bwd_stride, int h, int w,
                          float alpha, float beta, int npairs, int ndir, hipStream_t s);
 
+// ---- frame interpolation (k_interp.hip; the per-pixel arithmetic: interp.h) ----
+// One launch covers npairs pairs x nt times (nt <= kInterpChunk): slot z = pair * nt + k.  Inputs of pair p lie p * (their stride) bytes past
+// pair 0's; the scratch planes of slot z lie z * plane ELEMENTS past slot 0's.  Images: RGBA words, img_pitch bytes per row; flow: h*w float2,
+// masks: h*w bytes, unpitched.  Output: packed RGB (rgb != NULL, slot z at z*h*w*3 bytes) or RGBA words of pair 0 into rgba[k] (pitch bytes).
+constexpr int kInterpChunk = 4;
+struct InterpArgs {
+    const uint8_t* img1;
+    const uint8_t* img2;
+    size_t img_pitch, img_stride;
+    const float* flow;
+    size_t flow_stride;
+    const uint8_t* occ1;
+    const uint8_t* occ2;
+    size_t occ_stride;
+    uint64_t* keys;              // splat keys (all ones: nothing splatted)
+    int32_t* fill1;              // pass 1: source index of the vector, -1 a hole
+    int32_t* fill2;              // pass 2: written only where fill1 holds a hole
+    size_t plane;
+    uint8_t* rgb;
+    uint8_t* rgba[kInterpChunk];
+    size_t rgba_pitch;
+    int h, w, nt;
+    float t[kInterpChunk];
+};
+void launch_interp_splat(const InterpArgs& a, int npairs, hipStream_t s);      // clears the keys, then splats
+void launch_interp_fill(const InterpArgs& a, int npairs, hipStream_t s);       // both fill passes
+void launch_interp_blend(const InterpArgs& a, int npairs, hipStream_t s);
+
 // ---- flow colour coding (k_color.hip) ----
 // rgba: h*w packed R | G<<8 | B<<16 (alpha 0); flow: h*w float2
 void launch_flow_to_color(uint32_t* rgba, const float* flow, int h, int w, float max_disp_x, float max_disp_y, hipStream_t s, Batch bt = kOnePair);

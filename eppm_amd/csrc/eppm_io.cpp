@@ -11,6 +11,7 @@
 
 #include "../../include/eppm.h"
 #include "fb_occlusion.h"
+#include "interp.h"
 
 static int read_ppm_header(FILE* f, int* type, int* w, int* h)
 {
@@ -251,6 +252,93 @@ extern "C" int eppm_fb_occlusion_host(uint8_t* occ, const float* u, const float*
         for (int x = 0; x < w; x++) {
             const size_t i = (size_t)y * w + x;
             occ[i] = eppm::fb_occlusion_pixel(x, y, u[i], v[i], G.data(), h, w, alpha, beta);
+        }
+    return EPPM_OK;
+}
+
+// frame interpolation on host planes.  The splat, the blend and every other float operation are interp.h's, the
+// kernels' own; the minimum over the keys and the two fill passes are plain sequential loops written here (scans of the nearest filled pixel),
+// independent of the kernels' searches.  rgb_out, rgb1, rgb2: h rows of w R,G,B triplets, packed.
+extern "C" int eppm_interpolate_host(uint8_t* rgb_out, const uint8_t* rgb1, const uint8_t* rgb2, const float* u, const float* v, const uint8_t* occ1,
+                                     const uint8_t* occ2, int h, int w, float t)
+{
+    if (!rgb_out || !rgb1 || !rgb2 || !u || !v || !occ1 || !occ2 || h < 1 || w < 1 || !eppm::interp_t_ok(t)) return EPPM_ERR_ARG;
+    const size_t n = (size_t)h * w;
+    if (eppm::interp_endpoint(t)) {
+        memcpy(rgb_out, t == 0.0f ? rgb1 : rgb2, n * 3);
+        return EPPM_OK;
+    }
+    auto word = [](const uint8_t* p) { return (uint32_t)p[0] | ((uint32_t)p[1] << 8) | ((uint32_t)p[2] << 16); };
+    auto img1 = [&](int x, int y) { return word(rgb1 + ((size_t)y * w + x) * 3); };
+    auto img2 = [&](int x, int y) { return word(rgb2 + ((size_t)y * w + x) * 3); };
+    // (a) splat
+    std::vector<uint64_t> key(n, eppm::kInterpHole);
+    for (int y = 0; y < h; y++)
+        for (int x = 0; x < w; x++) {
+            const size_t i = (size_t)y * w + x;
+            if (!eppm::fb_known(u[i], v[i])) continue;
+            uint64_t k;
+            int bx, by;
+            if (!eppm::interp_splat_pixel(x, y, u[i], v[i], t, h, w, img1(x, y), occ1[i] != 0, img2, &k, &bx, &by)) continue;
+            for (int ty = by; ty <= by + 1; ty++)
+                for (int tx = bx; tx <= bx + 1; tx++)
+                    if (ty >= 0 && ty < h && tx >= 0 && tx < w && k < key[(size_t)ty * w + tx]) key[(size_t)ty * w + tx] = k;
+        }
+    // (b) pass 1: nearest splatted pixel left, right, up, down (running last-seen indices), ties in that order
+    std::vector<long long> src(n, -1);
+    for (size_t i = 0; i < n; i++)
+        if (key[i] != eppm::kInterpHole) src[i] = (long long)(uint32_t)key[i];
+    std::vector<int> lft(n, -1), rgt(n, -1), up(n, -1), dn(n, -1);      // column / row of the nearest splatted pixel, -1 none
+    for (int y = 0; y < h; y++) {
+        int last = -1;
+        for (int x = 0; x < w; x++) { lft[(size_t)y * w + x] = last; if (src[(size_t)y * w + x] >= 0) last = x; }
+        last = -1;
+        for (int x = w - 1; x >= 0; x--) { rgt[(size_t)y * w + x] = last; if (src[(size_t)y * w + x] >= 0) last = x; }
+    }
+    for (int x = 0; x < w; x++) {
+        int last = -1;
+        for (int y = 0; y < h; y++) { up[(size_t)y * w + x] = last; if (src[(size_t)y * w + x] >= 0) last = y; }
+        last = -1;
+        for (int y = h - 1; y >= 0; y--) { dn[(size_t)y * w + x] = last; if (src[(size_t)y * w + x] >= 0) last = y; }
+    }
+    std::vector<long long> f1(src);
+    for (int y = 0; y < h; y++)
+        for (int x = 0; x < w; x++) {
+            const size_t i = (size_t)y * w + x;
+            if (src[i] >= 0) continue;
+            long long best = -1;
+            int bd = INT_MAX;
+            if (lft[i] >= 0 && x - lft[i] < bd) { bd = x - lft[i]; best = src[(size_t)y * w + lft[i]]; }
+            if (rgt[i] >= 0 && rgt[i] - x < bd) { bd = rgt[i] - x; best = src[(size_t)y * w + rgt[i]]; }
+            if (up[i] >= 0 && y - up[i] < bd) { bd = y - up[i]; best = src[(size_t)up[i] * w + x]; }
+            if (dn[i] >= 0 && dn[i] - y < bd) { bd = dn[i] - y; best = src[(size_t)dn[i] * w + x]; }
+            f1[i] = best;
+        }
+    // (b) pass 2: nearest filled pixel of pass 1's result in the row, ties to the left
+    std::vector<long long> f2(f1);
+    for (int y = 0; y < h; y++) {
+        const long long* row = &f1[(size_t)y * w];
+        int last = -1;
+        std::vector<int> l(w), r(w);
+        for (int x = 0; x < w; x++) { l[x] = last; if (row[x] >= 0) last = x; }
+        last = -1;
+        for (int x = w - 1; x >= 0; x--) { r[x] = last; if (row[x] >= 0) last = x; }
+        for (int x = 0; x < w; x++) {
+            if (row[x] >= 0) continue;
+            if (l[x] >= 0 && (r[x] < 0 || x - l[x] <= r[x] - x)) f2[(size_t)y * w + x] = row[l[x]];
+            else if (r[x] >= 0) f2[(size_t)y * w + x] = row[r[x]];
+        }
+    }
+    // (c) blend
+    auto o1 = [&](int x, int y) { return occ1[(size_t)y * w + x]; };
+    auto o2 = [&](int x, int y) { return occ2[(size_t)y * w + x]; };
+    for (int y = 0; y < h; y++)
+        for (int x = 0; x < w; x++) {
+            const size_t i = (size_t)y * w + x;
+            const long long s = f2[i];
+            const float ux = s >= 0 ? u[s] : 0.0f, uy = s >= 0 ? v[s] : 0.0f;
+            const uint32_t p = eppm::interp_blend_pixel(x, y, ux, uy, t, h, w, img1, img2, o1, o2);
+            rgb_out[i * 3] = (uint8_t)p; rgb_out[i * 3 + 1] = (uint8_t)(p >> 8); rgb_out[i * 3 + 2] = (uint8_t)(p >> 16);
         }
     return EPPM_OK;
 }

@@ -13,8 +13,8 @@ namespace {
 struct DevState {
     float *lut_pm = nullptr, *lut_wmf = nullptr, *lut_blf = nullptr;
     int lut_R = -1;
-    void* scratch[6] = {nullptr, nullptr, nullptr, nullptr, nullptr, nullptr};
-    size_t scratch_bytes[6] = {0, 0, 0, 0, 0, 0};
+    void* scratch[7] = {nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr};
+    size_t scratch_bytes[7] = {0, 0, 0, 0, 0, 0, 0};
     std::map<std::tuple<int, int, int, unsigned long long>, eppm_pm_rng*> rngs;
 };
 std::mutex g_mu;
@@ -441,6 +441,31 @@ extern "C" int eppm_fb_occlusion(uint8_t* d_occ, const eppm_float2* d_flow, cons
     LAUNCHER_BEGIN_INT;
     (void)ds;
     launch_fb_occlusion(d_occ, nullptr, (const float*)d_flow, 0, (const float*)d_other, 0, h, w, alpha, beta, 1, 1, g_stream);
+    return finish();
+}
+// ---- frame interpolation on caller planes (k_interp.hip; eppm_interpolate_host is its host form): one pair, one time ----
+extern "C" int eppm_interpolate_frames(void* d_rgba_out, size_t out_pitch, const void* d_rgba1, const void* d_rgba2, size_t in_pitch,
+                                       const eppm_float2* d_flow, const uint8_t* d_occ1, const uint8_t* d_occ2, int h, int w, float t)
+{
+    if (!d_rgba_out || !d_rgba1 || !d_rgba2 || !d_flow || !d_occ1 || !d_occ2 || h < 1 || w < 1) return set_err(EPPM_ERR_ARG, "eppm_interpolate_frames: bad argument");
+    if (!(t >= 0.0f && t <= 1.0f)) return set_err(EPPM_ERR_ARG, "eppm_interpolate_frames: t = %g outside [0, 1]", t);
+    if (in_pitch < (size_t)w * 4 || out_pitch < (size_t)w * 4 || (in_pitch & 3) || (out_pitch & 3))
+        return set_err(EPPM_ERR_ARG, "eppm_interpolate_frames: bad pitch %zu / %zu", in_pitch, out_pitch);
+    if ((unsigned long long)h * (unsigned long long)w >= (1ULL << 31)) return set_err(EPPM_ERR_ARG, "eppm_interpolate_frames: size %dx%d out of range", w, h);
+    LAUNCHER_BEGIN_INT;
+    const size_t plane = ((size_t)h * w + 63) & ~(size_t)63;
+    void* scr = nullptr;
+    CHK(get_scratch(ds, plane * 16, &scr, 6));          // keys | fill1 | fill2
+    InterpArgs a{};
+    a.img1 = (const uint8_t*)d_rgba1; a.img2 = (const uint8_t*)d_rgba2; a.img_pitch = in_pitch;
+    a.flow = (const float*)d_flow;
+    a.occ1 = d_occ1; a.occ2 = d_occ2;
+    a.keys = (uint64_t*)scr; a.fill1 = (int32_t*)((char*)scr + plane * 8); a.fill2 = (int32_t*)((char*)scr + plane * 12); a.plane = plane;
+    a.rgba[0] = (uint8_t*)d_rgba_out; a.rgba_pitch = out_pitch;
+    a.h = h; a.w = w; a.nt = 1; a.t[0] = t;
+    launch_interp_splat(a, 1, g_stream);
+    launch_interp_fill(a, 1, g_stream);
+    launch_interp_blend(a, 1, g_stream);
     return finish();
 }
 // the C++-linkage symbol the reference's driver declares at :64 (defaults 100,100 there; the live call passes 20,20)

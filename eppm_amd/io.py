@@ -91,3 +91,21 @@ def fb_occlusion(u, v, bu, bv, alpha=0.01, beta=0.5):
     check(lib().eppm_fb_occlusion_host(occ.ctypes.data_as(C.c_void_p), *[a.ctypes.data_as(C.c_void_p) for a in arrs], h, w,
                                        C.c_float(alpha), C.c_float(beta)), "eppm_fb_occlusion_host")
     return occ
+
+
+def interpolate(img1, img2, u, v, occ1, occ2, t):
+    """(h, w, 3) uint8 frame at time t between img1 (t = 0) and img2 (t = 1) from the forward flow (u, v) and the occlusion masks of
+    both images (eppm_interpolate_host; byte-identical to the kernels)."""
+    a = np.ascontiguousarray(img1, np.uint8)
+    b = np.ascontiguousarray(img2, np.uint8)
+    u = np.ascontiguousarray(u, np.float32)
+    v = np.ascontiguousarray(v, np.float32)
+    o1 = np.ascontiguousarray(occ1, np.uint8)
+    o2 = np.ascontiguousarray(occ2, np.uint8)
+    h, w = u.shape
+    if a.shape != (h, w, 3) or b.shape != (h, w, 3) or v.shape != (h, w) or o1.shape != (h, w) or o2.shape != (h, w):
+        raise ValueError("interpolate: images (h, w, 3), flow and masks (h, w)")
+    out = np.empty((h, w, 3), np.uint8)
+    check(lib().eppm_interpolate_host(out.ctypes.data_as(C.c_void_p), *[x.ctypes.data_as(C.c_void_p) for x in (a, b, u, v, o1, o2)], h, w,
+                                      C.c_float(t)), "eppm_interpolate_host")
+    return out

@@ -182,6 +182,31 @@ int  eppm_set_occlusion_params(eppm_ctx* ctx, float alpha, float beta);
  * each); on the launcher stream, synchronous like the other launchers */
 int  eppm_fb_occlusion(uint8_t* d_occ, const eppm_float2* d_flow, const eppm_float2* d_other, int h, int w, float alpha, float beta);
 
+/* ----------------------------------------------------------------------------------------
+ * frame interpolation.  The frame at time t between image 1 (t = 0) and image 2 (t = 1) from the forward flow and
+ * the two occlusion masks of the last bidirectional call (Baker et al., IJCV 2011, section 3.3, made deterministic): splat the forward
+ * flow to time t (consistent vectors first, then the lowest photo cost, then the lowest source index), fill the holes, sample both frames
+ * along the splatted vector and let the masks choose which frame(s) to trust.  t = 0 / t = 1 return the input frames byte for byte; any
+ * other t must lie in (0, 1) (else EPPM_ERR_ARG, NaN included).  The context forms are valid after eppm_compute_bidirectional* and until the
+ * next eppm_set_images* or forward-only compute (EPPM_ERR_STATE outside that window); they read the images, the forward flow and the masks
+ * where the context keeps them.  The first call allocates the context's interpolation scratch (kept until eppm_destroy); times are
+ * processed four per launch.  Outputs: h rows of w R,G,B triplets row_stride bytes apart (host), or RGBA words with alpha 255 (device).
+ * -------------------------------------------------------------------------------------- */
+/* pair 0; rgb: nt host images, one per time t[k].  Synchronous. */
+int  eppm_interpolate(eppm_ctx* ctx, int nt, const float* t, uint8_t* const* rgb, size_t row_stride);
+/* pair 0; d_rgba: nt device RGBA planes of `pitch` bytes per row.  Asynchronous on the context's stream (no host synchronisation, no
+ * allocation after the first call: usable inside stream capture). */
+int  eppm_interpolate_device(eppm_ctx* ctx, int nt, const float* t, void* const* d_rgba, size_t pitch);
+/* every active pair: rgb[pair * nt + k] receives pair `pair` at time t[k].  Synchronous. */
+int  eppm_batch_interpolate(eppm_ctx* ctx, int nt, const float* t, uint8_t* const* rgb, size_t row_stride);
+/* the kernels alone on caller planes: RGBA inputs (in_pitch bytes per row, alpha ignored) and output (out_pitch), h*w float2 forward flow,
+ * h*w-byte masks, all device pointers; on the launcher stream, synchronous like eppm_fb_occlusion */
+int  eppm_interpolate_frames(void* d_rgba_out, size_t out_pitch, const void* d_rgba1, const void* d_rgba2, size_t in_pitch,
+                             const eppm_float2* d_flow, const uint8_t* d_occ1, const uint8_t* d_occ2, int h, int w, float t);
+/* host form on packed RGB images and planar flows: byte-identical to the kernels */
+int  eppm_interpolate_host(uint8_t* rgb_out, const uint8_t* rgb1, const uint8_t* rgb2, const float* u, const float* v, const uint8_t* occ1,
+                           const uint8_t* occ2, int h, int w, float t);
+
 /* Per-stage device times in ms (hipEvent pairs on the context's stream), one entry per stage per
  * call since the last eppm_clear_stage_times (names repeat across calls; prepare entries first).
  * names[i] points to static strings.  Returns the number of entries written (<= max). */
@@ -189,7 +214,8 @@ int  eppm_stage_times(eppm_ctx* ctx, const char** names, float* ms, int max);
 int  eppm_clear_stage_times(eppm_ctx* ctx);
 /* 0: no events (default); 1: an event pair around every stage; 2: only around the dominant kernel (the candidate
  * refine, entries "c2f_refine_L<l>").  A bidirectional call adds (mode 1) "l2_post_bwd", "upsample_bwd_L<l>", "c2f_refine_bwd_L<l>",
- * "flow_blf_bwd_L<l>", "flow_blf_bwd_final" and "fb_occlusion".  Events come from a per-context pool: none is created in a steady-state step. */
+ * "flow_blf_bwd_L<l>", "flow_blf_bwd_final" and "fb_occlusion"; an interpolation call "interp_splat", "interp_fill" and "interp_blend"
+ * (mode 1, once per group of four times).  Events come from a per-context pool: none is created in a steady-state step. */
 int  eppm_enable_stage_timing(eppm_ctx* ctx, int on);
 
 const char* eppm_last_error(void);

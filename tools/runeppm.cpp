@@ -19,6 +19,8 @@
 //   --gt file.flo     print EPE / AAE of the result against a ground-truth .flo (bao_flow_tools.cpp:64-111)
 //   --backward f.flo  the timed window runs compute_flow_bidirectional instead: also write the backward flow (image 2 -> image 1)
 //   --occlusion f.pgm ... and image 1's occlusion mask as a P5 PGM: 0 consistent, 255 inconsistent, 128 leaves the frame, 64 unknown
+//   --interpolate T f.ppm  (repeatable) implies the bidirectional call; after the timed window, write the frame at time T in [0, 1]
+//                     between image 1 and image 2 (interpolate_frame) as a P6 PPM
 #include <atomic>
 #include <chrono>
 #include <cstdio>
@@ -49,6 +51,7 @@ struct Options {
     const char *f1 = "frame10.ppm", *f2 = "frame11.ppm", *fo = "flow.flo", *gt = nullptr, *fb = nullptr, *focc = nullptr;
     int sw = 0, sh = 0, pairs = 1, gpus = 1, batch = 1;
     std::vector<std::pair<std::string, long long>> opts;
+    std::vector<std::pair<float, const char*>> interp;     // --interpolate T file.ppm
 };
 
 static unsigned hash32(unsigned x)
@@ -97,7 +100,7 @@ static int usage()
 {
     fprintf(stderr, "usage: runeppm [--size WxH] [--seed N] [--levels N] [--patch-r N] [--iters N] [--propagation M]\n"
                     "               [--pin] [--pairs P] [--gpus G] [--batch B] [--gt file.flo] [--out file.flo] [--backward file.flo]\n"
-                    "               [--occlusion file.pgm] [img1.ppm img2.ppm [out.flo]]\n");
+                    "               [--occlusion file.pgm] [--interpolate T file.ppm]... [img1.ppm img2.ppm [out.flo]]\n");
     return 2;
 }
 
@@ -124,6 +127,13 @@ int main(int argc, char** argv)
         else if (!strcmp(a, "--out")) { if (i + 1 >= argc) return usage(); o.fo = argv[++i]; }
         else if (!strcmp(a, "--backward")) { if (i + 1 >= argc) return usage(); o.fb = argv[++i]; }
         else if (!strcmp(a, "--occlusion")) { if (i + 1 >= argc) return usage(); o.focc = argv[++i]; }
+        else if (!strcmp(a, "--interpolate")) {
+            if (i + 2 >= argc) return usage();
+            char* end = nullptr;
+            const float t = strtof(argv[++i], &end);
+            if (!end || *end || !(t >= 0.0f && t <= 1.0f)) return usage();
+            o.interp.push_back({t, argv[++i]});
+        }
         else if (a[0] == '-' && a[1] == '-') return usage();
         else pos.push_back(a);
     }
@@ -156,7 +166,9 @@ int main(int argc, char** argv)
     std::vector<float> u((size_t)h * w, 0.f), v((size_t)h * w, 0.f);
     std::vector<float*> ur(h), vr(h);
     for (int i = 0; i < h; i++) { ur[i] = &u[(size_t)i * w]; vr[i] = &v[(size_t)i * w]; }
-    const bool bidir = o.fb || o.focc;
+    const bool bidir = o.fb || o.focc || !o.interp.empty();
+    std::vector<Array3<unsigned char>> frames;      // --interpolate outputs
+    for (size_t k = 0; k < o.interp.size(); k++) frames.emplace_back(h, w, 3);
     std::vector<float> bu, bv;                      // backward flow and image 1's occlusion mask (--backward / --occlusion)
     std::vector<unsigned char> occ;
     std::vector<float*> bur, bvr;
@@ -179,6 +191,8 @@ int main(int argc, char** argv)
         else eppm.compute_flow(ur.data(), vr.data());
         auto t1 = std::chrono::steady_clock::now();
         printf("GPU: %.3f s (init + %s)\n", std::chrono::duration<double>(t1 - t0).count(), bidir ? "compute_flow_bidirectional" : "compute_flow");
+        for (size_t k = 0; k < o.interp.size(); k++)
+            if (!eppm.interpolate_frame(o.interp[k].first, frames[k].p())) return 1;
     }
 
     // steady state: contexts created once, pairs streamed through set_data + compute_flow
@@ -279,6 +293,12 @@ int main(int argc, char** argv)
         for (size_t i = 0; ok && i < occ.size(); i++) ok = fputc(grey[occ[i] & 3], f) != EOF;
         if (f && fclose(f) != 0) ok = false;
         if (!ok) { fprintf(stderr, "cannot write %s\n", o.focc); return 1; }
+    }
+    for (size_t k = 0; k < o.interp.size(); k++) {
+        FILE* f = fopen(o.interp[k].second, "wb");
+        bool ok = f && fprintf(f, "P6\n%d %d\n255\n", w, h) > 0 && fwrite(frames[k].store.data(), 1, frames[k].store.size(), f) == frames[k].store.size();
+        if (f && fclose(f) != 0) ok = false;
+        if (!ok) { fprintf(stderr, "cannot write %s\n", o.interp[k].second); return 1; }
     }
     return 0;
 }
