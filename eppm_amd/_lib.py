@@ -15,6 +15,18 @@ class CParams(C.Structure):
                 ("levels", C.c_int)]
 
 
+class CTrackParams(C.Structure):
+    _fields_ = [("spacing", C.c_int), ("min_eig", C.c_int64), ("fb_alpha", C.c_float), ("fb_beta", C.c_float), ("mb_alpha", C.c_float),
+                ("mb_beta", C.c_float), ("capacity", C.c_int)]
+
+
+class CTrackCounts(C.Structure):
+    _fields_ = [("live", C.c_int), ("ended", C.c_int), ("seeded", C.c_int), ("dropped", C.c_int), ("frame", C.c_int), ("next_id", C.c_int)]
+
+    def as_dict(self):
+        return {k: int(getattr(self, k)) for k, _ in self._fields_}
+
+
 _lib = None
 
 # every symbol include/eppm.h declares (tests check that the library exports all of them)
@@ -39,6 +51,8 @@ SYMBOLS = [
     "eppm_compute_bidirectional", "eppm_compute_bidirectional_device", "eppm_batch_compute_bidirectional", "eppm_set_occlusion_params",
     "eppm_fb_occlusion", "eppm_fb_occlusion_host",
     "eppm_interpolate", "eppm_interpolate_device", "eppm_batch_interpolate", "eppm_interpolate_frames", "eppm_interpolate_host",
+    "eppm_track_default_params", "eppm_track_capacity", "eppm_tracker_create", "eppm_tracker_destroy", "eppm_track_step",
+    "eppm_track_step_frames", "eppm_tracker_get", "eppm_tracker_get_ended", "eppm_tracker_set", "eppm_track_step_host", "eppm_track_seeds_host",
 ]
 
 

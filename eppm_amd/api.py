@@ -3,7 +3,7 @@ import ctypes as C
 
 import numpy as np
 
-from ._lib import CParams, EppmError, check, lib
+from ._lib import CParams, CTrackCounts, CTrackParams, EppmError, check, lib
 
 uchar4 = np.dtype([("x", "u1"), ("y", "u1"), ("z", "u1"), ("w", "u1")])
 short2 = np.dtype([("x", "i2"), ("y", "i2")])
@@ -60,6 +60,126 @@ def _times(times):
     if not ts:
         raise EppmError("interpolate: at least one time")
     return (C.c_float * len(ts))(*ts)
+
+
+def TrackParams(params=None, **kw):
+    """eppm_track_params with the defaults of DESIGN.md section 12 (spacing 8, min_eig 2500, fb_alpha 0.01, fb_beta 0.5, mb_alpha 0.01,
+    mb_beta 0.002, capacity 0: 4 x the number of cells); params: a CTrackParams to start from instead."""
+    p = CTrackParams()
+    if params is not None:
+        C.memmove(C.byref(p), C.byref(params), C.sizeof(p))
+    else:
+        check(lib().eppm_track_default_params(C.byref(p)), "eppm_track_default_params")
+    for k, v in kw.items():
+        if not hasattr(p, k):
+            raise TypeError(f"unknown track parameter {k}")
+        setattr(p, k, v)
+    return p
+
+
+class Tracker:
+    """Dense point trajectories over the pairs of a context (eppm_tracker_*).  ctx: an EPPM or EPPMBatch; every
+    step() advances the tracks by pair `pair` of the context's last compute_flow_bidirectional.  The tracker is its own allocation on the
+    context's device; close() frees it."""
+
+    def __init__(self, ctx, pair=0, params=None, **track_params):
+        self._t = C.c_void_p()
+        self.ctx, self.pair = ctx, int(pair)
+        self.params = TrackParams(params, **track_params)
+        check(lib().eppm_tracker_create(ctx._ctx, C.byref(self.params), C.byref(self._t)), "eppm_tracker_create")
+        self.capacity = lib().eppm_track_capacity(C.byref(self.params), ctx.h, ctx.w)
+
+    def step(self, pair=None, ctx=None):
+        """One step on pair `pair` (default: the tracker's) of ctx (default: the tracker's); asynchronous on the context's stream."""
+        c = self.ctx if ctx is None else ctx
+        check(lib().eppm_track_step(self._t, c._ctx, self.pair if pair is None else int(pair)), "eppm_track_step")
+
+    def step_frames(self, d_rgba1, d_rgba2, pitch, d_flow, d_flow_bwd):
+        """eppm_track_step_frames: one step on caller device planes (addresses), synchronous."""
+        check(lib().eppm_track_step_frames(self._t, C.c_void_p(d_rgba1), C.c_void_p(d_rgba2), C.c_size_t(pitch), C.c_void_p(d_flow),
+                                           C.c_void_p(d_flow_bwd), self.ctx.h, self.ctx.w), "eppm_track_step_frames")
+
+    def counts(self):
+        c = CTrackCounts()
+        check(lib().eppm_tracker_get(self._t, 0, None, None, None, C.byref(c)), "eppm_tracker_get")
+        return c.as_dict()
+
+    def tracks(self):
+        """(ids int32 (n,), starts int32 (n,), xy float32 (n, 2)): the live tracks, positions in the current frame."""
+        n = self.counts()["live"]
+        ids, starts, xy = np.empty(n, np.int32), np.empty(n, np.int32), np.empty((n, 2), np.float32)
+        c = CTrackCounts()
+        check(lib().eppm_tracker_get(self._t, n, ids.ctypes.data_as(C.c_void_p), starts.ctypes.data_as(C.c_void_p),
+                                     xy.ctypes.data_as(C.c_void_p), C.byref(c)), "eppm_tracker_get")
+        return ids, starts, xy
+
+    def ended(self):
+        """(ids, starts, xy (last positions, in the frame before the last step), reasons 1..4, counts dict) of the last step."""
+        n = self.counts()["ended"]
+        ids, starts, why = np.empty(n, np.int32), np.empty(n, np.int32), np.empty(n, np.int32)
+        xy = np.empty((n, 2), np.float32)
+        c = CTrackCounts()
+        check(lib().eppm_tracker_get_ended(self._t, n, ids.ctypes.data_as(C.c_void_p), starts.ctypes.data_as(C.c_void_p),
+                                           xy.ctypes.data_as(C.c_void_p), why.ctypes.data_as(C.c_void_p), C.byref(c)), "eppm_tracker_get_ended")
+        return ids, starts, xy, why, c.as_dict()
+
+    def set(self, ids, starts, xy, next_id, frame):
+        """Load a state (eppm_tracker_set): tracks at positions inside the frame, the next id and the current frame."""
+        ids = np.ascontiguousarray(ids, np.int32)
+        starts = np.ascontiguousarray(starts, np.int32)
+        xy = np.ascontiguousarray(xy, np.float32).reshape(-1, 2)
+        if not (len(ids) == len(starts) == len(xy)):
+            raise EppmError("Tracker.set: ids, starts and xy of one length")
+        check(lib().eppm_tracker_set(self._t, len(ids), ids.ctypes.data_as(C.c_void_p), starts.ctypes.data_as(C.c_void_p),
+                                     xy.ctypes.data_as(C.c_void_p), int(next_id), int(frame)), "eppm_tracker_set")
+
+    def close(self):
+        if self._t:
+            lib().eppm_tracker_destroy(self._t)
+            self._t = C.c_void_p()
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
+def track_sequence(frames, params=None, **track_params):
+    """Dense point trajectories through a list of (h, w, 3) uint8 frames: one bidirectional call on a batch of the consecutive pairs, then
+    one tracker step per pair.  Returns {track id: {"start": first frame, "positions": (n, 2) float32 positions in frames start ..
+    start + n - 1, "reason": the end reason 1..4, or None while alive}}.  params: the flow's eppm Params; track_params: TrackParams'."""
+    from . import io
+    frames = [np.ascontiguousarray(f, np.uint8) for f in frames]
+    if len(frames) < 2:
+        raise EppmError("track_sequence: at least two frames")
+    h, w, _ = frames[0].shape
+    bat = EPPMBatch(h, w, len(frames) - 1, params=params)
+    trk = None
+    try:
+        bat.set_data(list(zip(frames[:-1], frames[1:])))
+        bat.compute_flow_bidirectional()
+        trk = Tracker(bat, 0, **track_params)
+        seeds = io.track_seeds(frames[0], trk.params)[:trk.capacity]
+        out = {k: {"start": 0, "positions": [xy], "reason": None} for k, xy in enumerate(seeds)}
+        for k in range(len(frames) - 1):
+            trk.step(k)
+            e_ids, _, _, why, _ = trk.ended()
+            for i, r in zip(e_ids.tolist(), why.tolist()):
+                out[i]["reason"] = int(r)
+            ids, starts, xy = trk.tracks()
+            for i, s0, p in zip(ids.tolist(), starts.tolist(), xy):
+                if i in out:
+                    out[i]["positions"].append(p)
+                else:
+                    out[i] = {"start": int(s0), "positions": [p], "reason": None}
+    finally:
+        if trk is not None:
+            trk.close()
+        bat.close()
+    for t in out.values():
+        t["positions"] = np.asarray(t["positions"], np.float32).reshape(-1, 2)
+    return out
 
 
 class EPPM:

@@ -136,3 +136,14 @@ EPPM_HIDDEN void run_patchmatch(eppm::PmBatch& b, eppm_pm_rng* rng, const float*
 
 // ---- state of the context-less launchers that test_hooks.cpp and the colour entry points share (launchers_ref_abi.cpp) ----
 EPPM_HIDDEN int launcher_finish();
+
+// ---- what a tracker (tracker.cpp) reads of a context (context.cpp) ----
+// the planes of one pair in the window of eppm_interpolate* (EPPM_ERR_ARG: other dimensions / device, a pair that is not active;
+// EPPM_ERR_STATE: outside the window), and the context's stream; sets the context's device current
+EPPM_HIDDEN int ctx_track_inputs(eppm_ctx* c, int pair, int h, int w, int device, const char* what, eppm::TrackIn* in, hipStream_t* s);
+EPPM_HIDDEN int ctx_device(const eppm_ctx* c, int* h, int* w);             // the device; h, w: the context's size
+EPPM_HIDDEN void ctx_stage_begin(eppm_ctx* c, const char* name);           // a stage-timing entry on the context's stream (mode 1)
+EPPM_HIDDEN void ctx_stage_end(eppm_ctx* c);
+// the launcher stream of the context-less launchers (launchers_ref_abi.cpp) runs eppm_track_step_frames through this (tracker.cpp)
+EPPM_HIDDEN int tracker_step_on(eppm_tracker* t, const eppm::TrackIn& in, hipStream_t s, eppm_ctx* timing);
+EPPM_HIDDEN int tracker_device(const eppm_tracker* t, int* h, int* w);

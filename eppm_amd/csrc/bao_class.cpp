@@ -302,3 +302,23 @@ bool bao_flow_patchmatch_multiscale_cuda::interpolate_frame(float t, unsigned ch
             for (int c = 0; c < 3; c++) img_t[i][j][c] = rgb[((size_t)i * m_w + j) * 3 + c];
     return true;
 }
+
+eppm_tracker* bao_flow_patchmatch_multiscale_cuda::create_tracker(const eppm_track_params* p)
+{
+    eppm_tracker* t = NULL;
+    if (!m_ctx || eppm_tracker_create(m_ctx, p, &t) != EPPM_OK) {
+        fprintf(stderr, "bao_flow_patchmatch_multiscale_cuda::create_tracker: %s\n", m_ctx ? eppm_last_error() : "no context");
+        return NULL;
+    }
+    return t;
+}
+
+bool bao_flow_patchmatch_multiscale_cuda::track_step(eppm_tracker* t)
+{
+    if (!m_ctx || !t) return false;
+    if (eppm_track_step(t, m_ctx, 0) != EPPM_OK) {
+        fprintf(stderr, "bao_flow_patchmatch_multiscale_cuda::track_step: %s\n", eppm_last_error());
+        return false;
+    }
+    return true;
+}

@@ -954,6 +954,38 @@ extern "C" int eppm_interpolate_device(eppm_ctx* c, int nt, const float* t, void
     return EPPM_OK;
 }
 
+// ---- dense point trajectories (tracker.cpp): the raw frames, the level-0 forward flow and the level-0 backward flow
+// of one pair, in the window of eppm_interpolate* ----
+
+int ctx_track_inputs(eppm_ctx* c, int pair, int h, int w, int device, const char* what, TrackIn* in, hipStream_t* s)
+{
+    if (c->h != h || c->w != w || c->device != device)
+        return set_err(EPPM_ERR_ARG, "%s: the tracker is %dx%d on device %d, the context %dx%d on device %d", what, w, h, device, c->w, c->h, c->device);
+    if (pair < 0 || pair >= c->n_active) return set_err(EPPM_ERR_ARG, "%s: pair %d, the context has %d active", what, pair, c->n_active);
+    if (c->flow_pending) return set_err(EPPM_ERR_STATE, "%s: an eppm_compute_begin is pending", what);
+    if (!c->have_bwd || !c->bwd_images) return set_err(EPPM_ERR_STATE, "%s: needs a bidirectional call on the current images", what);
+    HIPCHK(hipSetDevice(c->device));
+    in->img1 = (const uint8_t*)c->of_pair(c->raw1, pair);
+    in->img2 = (const uint8_t*)c->of_pair(c->raw2, pair);
+    in->pitch = c->raw_pitch;
+    in->fwd = c->of_pair(c->flow[0], pair);
+    in->bwd = (const float*)(c->bwd + (size_t)pair * c->bwd_stride + ((char*)c->bflow[0] - c->bwd));
+    in->h = c->h;
+    in->w = c->w;
+    *s = c->stream;
+    return EPPM_OK;
+}
+
+int ctx_device(const eppm_ctx* c, int* h, int* w)
+{
+    *h = c->h;
+    *w = c->w;
+    return c->device;
+}
+
+void ctx_stage_begin(eppm_ctx* c, const char* name) { stage_begin(c, c->ev, name); }
+void ctx_stage_end(eppm_ctx* c) { stage_end(c, c->ev); }
+
 extern "C" int eppm_synchronize(eppm_ctx* c)
 {
     if (!c) return set_err(EPPM_ERR_ARG, "NULL ctx");

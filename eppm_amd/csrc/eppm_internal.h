@@ -207,6 +207,44 @@ void launch_interp_splat(const InterpArgs& a, int npairs, hipStream_t s);      /
 void launch_interp_fill(const InterpArgs& a, int npairs, hipStream_t s);       // both fill passes
 void launch_interp_blend(const InterpArgs& a, int npairs, hipStream_t s);
 
+// ---- dense point trajectories (k_track.hip; the per-point arithmetic: track.h) ----
+// The device counters of a tracker (int32 each): the live count, the next id, the frame, the last step's dropped / ended / seeded counts,
+// and what the kernels of one step hand to each other.
+enum {
+    kTrackCntLive, kTrackCntNextId, kTrackCntFrame, kTrackCntDropped, kTrackCntEnded, kTrackCntSeeded,
+    kTrackCntIdBase, kTrackCntSurv, kTrackCntPrevLive, kTrackCntSeeded0, kTrackCntDropped0, kTrackCntN = 16
+};
+struct TrackRec;
+struct TrackDev {                   // a tracker's allocation (tracker.cpp) as the kernels see it
+    struct {
+        int spacing;
+        long long min_eig;
+        float fb_alpha, fb_beta, mb_alpha, mb_beta;
+    } p;
+    int cap, ncells, ncx;
+    float* npos;                    // cap float2: the advanced positions
+    uint8_t* stat;                  // cap: the end reasons of the last advance (0 alive)
+    TrackRec* ended;                // cap: the last step's ended tracks
+    int32_t* ended_reason;          // cap
+    uint8_t* cov;                   // ncells: coverage of frame k+1 (zero between steps)
+    uint8_t* flags;                 // ncells: seed flags
+    int32_t *blk_s, *blk_e;         // per slot block: survivor / ended counts, then their offsets
+    int32_t* blk_c;                 // per cell block: seed counts, then their offsets
+    int32_t* cnt;                   // kTrackCntN counters
+};
+struct TrackIn {                    // the planes of one pair: RGBA images (pitch bytes per row), h*w float2 forward / backward flows
+    const uint8_t* img1;
+    const uint8_t* img2;
+    size_t pitch;
+    const float* fwd;
+    const float* bwd;
+    int h, w;
+};
+void launch_track_seed0(const TrackDev& d, const TrackIn& in, TrackRec* cur, hipStream_t s);     // frame 0 and no live track: seed image 1
+void launch_track_advance(const TrackDev& d, const TrackIn& in, const TrackRec* cur, hipStream_t s);
+void launch_track_seed(const TrackDev& d, const TrackIn& in, hipStream_t s);
+void launch_track_compact(const TrackDev& d, const TrackIn& in, const TrackRec* cur, TrackRec* next, hipStream_t s);
+
 // ---- flow colour coding (k_color.hip) ----
 // rgba: h*w packed R | G<<8 | B<<16 (alpha 0); flow: h*w float2
 void launch_flow_to_color(uint32_t* rgba, const float* flow, int h, int w, float max_disp_x, float max_disp_y, hipStream_t s, Batch bt = kOnePair);

@@ -468,6 +468,24 @@ extern "C" int eppm_interpolate_frames(void* d_rgba_out, size_t out_pitch, const
     launch_interp_blend(a, 1, g_stream);
     return finish();
 }
+// ---- one track step on caller planes (k_track.hip; eppm_track_step_host is its host form) ----
+extern "C" int eppm_track_step_frames(eppm_tracker* t, const void* d_rgba1, const void* d_rgba2, size_t pitch, const eppm_float2* d_flow,
+                                      const eppm_float2* d_flow_bwd, int h, int w)
+{
+    if (!t || !d_rgba1 || !d_rgba2 || !d_flow || !d_flow_bwd) return set_err(EPPM_ERR_ARG, "eppm_track_step_frames: NULL argument");
+    int th, tw;
+    const int device = tracker_device(t, &th, &tw);
+    if (h != th || w != tw) return set_err(EPPM_ERR_ARG, "eppm_track_step_frames: %dx%d planes, the tracker is %dx%d", w, h, tw, th);
+    if (pitch < (size_t)w * 4 || (pitch & 3)) return set_err(EPPM_ERR_ARG, "eppm_track_step_frames: bad pitch %zu", pitch);
+    std::lock_guard<std::mutex> lk(g_mu);
+    int d = 0;
+    HIPCHK(hipGetDevice(&d));
+    if (d != device) return set_err(EPPM_ERR_ARG, "eppm_track_step_frames: the tracker lives on device %d, the current device is %d", device, d);
+    TrackIn in{(const uint8_t*)d_rgba1, (const uint8_t*)d_rgba2, pitch, (const float*)d_flow, (const float*)d_flow_bwd, h, w};
+    CHK(tracker_step_on(t, in, g_stream, nullptr));
+    HIPCHK(hipStreamSynchronize(g_stream));
+    return finish();
+}
 // the C++-linkage symbol the reference's driver declares at :64 (defaults 100,100 there; the live call passes 20,20)
 void bao_cuda_convert_flow_to_colorshow(uchar4* rgbflow, float2* flow_vec, int h, int w, float max_disp_x, float max_disp_y)
 {

@@ -109,3 +109,53 @@ def interpolate(img1, img2, u, v, occ1, occ2, t):
     check(lib().eppm_interpolate_host(out.ctypes.data_as(C.c_void_p), *[x.ctypes.data_as(C.c_void_p) for x in (a, b, u, v, o1, o2)], h, w,
                                       C.c_float(t)), "eppm_interpolate_host")
     return out
+
+
+def _track_params(params, kw):
+    from .api import TrackParams
+    return TrackParams(params, **kw)
+
+
+def track_seeds(img, params=None, **track_params):
+    """(n, 2) float32: the seeds of the textured cells of an (h, w, 3) uint8 image in cell order (eppm_track_seeds_host, DESIGN.md
+    section 12)."""
+    p = _track_params(params, track_params)
+    a = np.ascontiguousarray(img, np.uint8)
+    h, w, _ = a.shape
+    n = C.c_int()
+    check(lib().eppm_track_seeds_host(C.byref(p), a.ctypes.data_as(C.c_void_p), h, w, 0, None, C.byref(n)), "eppm_track_seeds_host")
+    xy = np.empty((n.value, 2), np.float32)
+    check(lib().eppm_track_seeds_host(C.byref(p), a.ctypes.data_as(C.c_void_p), h, w, n.value, xy.ctypes.data_as(C.c_void_p), C.byref(n)),
+          "eppm_track_seeds_host")
+    return xy
+
+
+def track_step_host(img1, img2, u, v, bu, bv, ids=(), starts=(), xy=(), next_id=0, frame=0, params=None, **track_params):
+    """One track step on the host (eppm_track_step_host; byte-identical to the kernels).  img1 / img2: (h, w, 3)
+    uint8 frames k and k+1; (u, v) forward, (bu, bv) backward flow; the state: tracks (ids, starts, xy (n, 2) in frame k), next_id, frame.
+    Returns a dict: ids, starts, xy (the live tracks in frame k+1), ended_ids, ended_starts, ended_xy, reasons, and the counts."""
+    from ._lib import CTrackCounts
+    p = _track_params(params, track_params)
+    a = np.ascontiguousarray(img1, np.uint8)
+    b = np.ascontiguousarray(img2, np.uint8)
+    fl = [np.ascontiguousarray(x, np.float32) for x in (u, v, bu, bv)]
+    h, w = fl[0].shape
+    if a.shape != (h, w, 3) or b.shape != (h, w, 3) or any(x.shape != (h, w) for x in fl):
+        raise ValueError("track_step_host: images (h, w, 3), flows (h, w)")
+    ids = np.ascontiguousarray(ids, np.int32).ravel()
+    starts = np.ascontiguousarray(starts, np.int32).ravel()
+    xy = np.ascontiguousarray(xy, np.float32).reshape(-1, 2)
+    cap = lib().eppm_track_capacity(C.byref(p), h, w)
+    if cap < 0:
+        check(1, "eppm_track_capacity")
+    o_ids, o_st, e_ids, e_st, why = (np.empty(cap, np.int32) for _ in range(5))
+    o_xy, e_xy = np.empty((cap, 2), np.float32), np.empty((cap, 2), np.float32)
+    cnt = CTrackCounts()
+    ptr = lambda x: x.ctypes.data_as(C.c_void_p)       # noqa: E731
+    check(lib().eppm_track_step_host(C.byref(p), ptr(a), ptr(b), *[ptr(x) for x in fl], h, w, len(ids), ptr(ids), ptr(starts), ptr(xy),
+                                     int(next_id), int(frame), ptr(o_ids), ptr(o_st), ptr(o_xy), ptr(e_ids), ptr(e_st), ptr(e_xy), ptr(why),
+                                     C.byref(cnt)), "eppm_track_step_host")
+    c = cnt.as_dict()
+    n, m = c["live"], c["ended"]
+    return dict(ids=o_ids[:n].copy(), starts=o_st[:n].copy(), xy=o_xy[:n].copy(), ended_ids=e_ids[:m].copy(), ended_starts=e_st[:m].copy(),
+                ended_xy=e_xy[:m].copy(), reasons=why[:m].copy(), **c)

@@ -18,6 +18,8 @@
 #include "bao_basic_cuda.h"   /* as the reference's header does (:31): callers get bao_timer_gpu / bao_timer_gpu_cpu through it */
 
 struct eppm_ctx;
+struct eppm_tracker;
+struct eppm_track_params;
 
 class bao_flow_patchmatch_multiscale_cuda
 {
@@ -54,6 +56,11 @@ public:
     // compute_flow_bidirectional and until the next set_data; img_t: h x w x 3 R,G,B row-pointer tables (bao_alloc<unsigned char>(h, w, 3),
     // the layout of init's images).  false: no such call yet, bad t, or no context
     bool interpolate_frame(float t, unsigned char*** img_t);
+    // dense point trajectories (eppm_tracker*): a tracker on this object's context (p NULL: the defaults; NULL: no
+    // context or bad parameters), which the caller destroys (eppm_tracker_destroy) before init() or the destructor; track_step advances it
+    // by the pair of the last compute_flow_bidirectional (eppm_track_step; false outside that window); the tracks: eppm_tracker_get
+    eppm_tracker* create_tracker(const eppm_track_params* p = NULL);
+    bool track_step(eppm_tracker* t);
 
 private:
     void _destroy();

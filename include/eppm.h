@@ -207,6 +207,63 @@ int  eppm_interpolate_frames(void* d_rgba_out, size_t out_pitch, const void* d_r
 int  eppm_interpolate_host(uint8_t* rgb_out, const uint8_t* rgb1, const uint8_t* rgb2, const float* u, const float* v, const uint8_t* occ1,
                            const uint8_t* occ2, int h, int w, float t);
 
+/* ----------------------------------------------------------------------------------------
+ * dense point trajectories (Sundaram, Brox & Keutzer, ECCV 2010).  Points seeded on a grid of spacing x spacing
+ * cells, where the 5x5 structure tensor of R+G+B has lambda_min >= min_eig (exact integers), move by the bilinearly sampled forward flow;
+ * a track ends where the forward flow is unknown (reason 1), where it leaves the frame (2), where the forward-backward check fails (3) or
+ * at a motion boundary (4); every uncovered textured cell of the new frame is seeded again.  One step advances a tracker by one pair.
+ * A tracker is a separate allocation on its context's device (the context's own allocations do not change).  Tracks are ordered:
+ * survivors keep their order, new seeds follow in cell order with consecutive ids; seeds past the capacity are dropped (the highest
+ * cells first).  The kernels, the host form and any two runs give the same bytes.
+ * -------------------------------------------------------------------------------------- */
+typedef struct eppm_track_params {
+    int     spacing;             /* cell side in pixels, >= 1 (8) */
+    int64_t min_eig;             /* texture threshold on lambda_min of the integer structure tensor, 0 .. 2^40 (2500) */
+    float   fb_alpha, fb_beta;   /* forward-backward check, as the occlusion masks' (0.01, 0.5) */
+    float   mb_alpha, mb_beta;   /* motion boundary: |grad u|^2 + |grad v|^2 > mb_alpha |w|^2 + mb_beta ends a track (0.01, 0.002) */
+    int     capacity;            /* track slots, <= 2^26; 0: 4 x the number of cells */
+} eppm_track_params;
+typedef struct {
+    int live;                    /* live tracks (positions in the current frame) */
+    int ended, seeded, dropped;  /* of the last step */
+    int frame;                   /* the current frame: steps since frame 0 */
+    int next_id;                 /* the id of the next seed */
+} eppm_track_counts;
+typedef struct eppm_tracker eppm_tracker;
+
+int  eppm_track_default_params(eppm_track_params* p);
+/* the capacity a tracker of these parameters has on an h x w frame (-1: bad parameters) */
+int  eppm_track_capacity(const eppm_track_params* p, int h, int w);
+/* p NULL: the defaults.  Frame 0, no track, next id 0. */
+int  eppm_tracker_create(eppm_ctx* ctx, const eppm_track_params* p, eppm_tracker** out);
+int  eppm_tracker_destroy(eppm_tracker* t);
+/* one step on pair `pair` of the context (images, forward and backward flow of its last bidirectional call); valid in the window of
+ * eppm_interpolate* (EPPM_ERR_STATE outside it); EPPM_ERR_ARG for a context of other dimensions or another device, or a pair that is not
+ * active.  At frame 0 with no live track the step first seeds image 1.  Asynchronous on the context's stream: no host synchronisation,
+ * no allocation.  Consecutive pairs of one batch context stepped 0, 1, ... with one tracker chain them. */
+int  eppm_track_step(eppm_tracker* t, eppm_ctx* ctx, int pair);
+/* the same kernels on caller planes: RGBA images (pitch bytes per row, alpha ignored), h*w float2 forward and backward flows, all device
+ * pointers of the tracker's size; on the launcher stream, synchronous */
+int  eppm_track_step_frames(eppm_tracker* t, const void* d_rgba1, const void* d_rgba2, size_t pitch, const eppm_float2* d_flow,
+                            const eppm_float2* d_flow_bwd, int h, int w);
+/* synchronous.  The first min(live, max) live tracks: ids, start frames, positions (x, y pairs) in the current frame; any array may be
+ * NULL; counts: NULL or the counters */
+int  eppm_tracker_get(eppm_tracker* t, int max, int32_t* ids, int32_t* starts, float* xy, eppm_track_counts* counts);
+/* synchronous.  The last step's first min(ended, max) ended tracks: ids, start frames, last positions (in the frame before the step),
+ * reasons 1..4 */
+int  eppm_tracker_get_ended(eppm_tracker* t, int max, int32_t* ids, int32_t* starts, float* xy, int32_t* reasons, eppm_track_counts* counts);
+/* synchronous.  Load a state: n <= capacity tracks at finite positions inside the frame, the next id (>= 0) and the frame (>= 0);
+ * the last step's counts become 0 */
+int  eppm_tracker_set(eppm_tracker* t, int n, const int32_t* ids, const int32_t* starts, const float* xy, int next_id, int frame);
+/* host form of one step on packed RGB images and planar flows (u, v forward; bu, bv backward): sequential loops, byte-identical to the
+ * kernels.  In: n tracks (ids, starts, xy), next_id, frame.  Out: arrays of eppm_track_capacity entries (xy: twice that); counts */
+int  eppm_track_step_host(const eppm_track_params* p, const uint8_t* rgb1, const uint8_t* rgb2, const float* u, const float* v, const float* bu,
+                          const float* bv, int h, int w, int n, const int32_t* ids, const int32_t* starts, const float* xy, int next_id, int frame,
+                          int32_t* out_ids, int32_t* out_starts, float* out_xy, int32_t* end_ids, int32_t* end_starts, float* end_xy,
+                          int32_t* end_reasons, eppm_track_counts* counts);
+/* the seeds of the textured cells of a packed RGB image in cell order: *n of them, the first min(*n, max) written to xy */
+int  eppm_track_seeds_host(const eppm_track_params* p, const uint8_t* rgb, int h, int w, int max, float* xy, int* n);
+
 /* Per-stage device times in ms (hipEvent pairs on the context's stream), one entry per stage per
  * call since the last eppm_clear_stage_times (names repeat across calls; prepare entries first).
  * names[i] points to static strings.  Returns the number of entries written (<= max). */
@@ -215,7 +272,8 @@ int  eppm_clear_stage_times(eppm_ctx* ctx);
 /* 0: no events (default); 1: an event pair around every stage; 2: only around the dominant kernel (the candidate
  * refine, entries "c2f_refine_L<l>").  A bidirectional call adds (mode 1) "l2_post_bwd", "upsample_bwd_L<l>", "c2f_refine_bwd_L<l>",
  * "flow_blf_bwd_L<l>", "flow_blf_bwd_final" and "fb_occlusion"; an interpolation call "interp_splat", "interp_fill" and "interp_blend"
- * (mode 1, once per group of four times).  Events come from a per-context pool: none is created in a steady-state step. */
+ * (mode 1, once per group of four times); a track step "track_advance", "track_seed" and "track_compact" (mode 1; the step that seeds
+ * frame 0 adds a "track_seed" before "track_advance").  Events come from a per-context pool: none is created in a steady-state step. */
 int  eppm_enable_stage_timing(eppm_ctx* ctx, int on);
 
 const char* eppm_last_error(void);
