@@ -33,7 +33,7 @@ struct eppm_ctx {
     uint8_t *cen1[kMaxLevels] = {}, *cen2[kMaxLevels] = {};
     void *pk1[kMaxLevels] = {}, *pk2[kMaxLevels] = {};       // float4 texel planes {r,g,b,census}, linear (pitch = w)
     uint32_t *pc1[kMaxLevels] = {}, *pc2[kMaxLevels] = {};   // the same texels in 4 bytes, at the levels the LDS-window refine runs on
-    uint32_t *pp1 = nullptr, *pp2 = nullptr;                 // tolerance library: column-parity planes of pc at the PatchMatch level (PlanesH::pp1)
+    uint32_t *pp1 = nullptr, *pp2 = nullptr;                 // column-parity planes of pc at the PatchMatch level (PlanesH::pp1)
     int pp_pitch = 0, pp_pad = 0;
     int16_t *nnf1 = nullptr, *nnf2 = nullptr, *nnf_tmp = nullptr, *nnf_tmp2 = nullptr;
     float *cost1 = nullptr, *cost2 = nullptr;
@@ -218,12 +218,16 @@ static int ctx_alloc(eppm_ctx* c)
     }
     const int L = c->nl - 1;
     const size_t n2 = (size_t)c->W[L] * c->H[L];
-#ifdef EPPM_TOL
-    c->pp_pad = (c->prm.patch_r + 2) & ~1;                  // even and >= R + 1: a target column is in [0, w], a sample within R of it
-    c->pp_pitch = parity_pitch(c->W[L], c->pp_pad);
-    plane((void**)&c->pp1, (size_t)2 * c->H[L] * c->pp_pitch * 4);
-    plane((void**)&c->pp2, (size_t)2 * c->H[L] * c->pp_pitch * 4);
+    // column-parity planes: the tolerance library reads them at both radii, the exact library at radius 9 (k_patchmatch.hip: pm_has_parity)
+#ifndef EPPM_TOL
+    if (c->prm.patch_r == 9)
 #endif
+    {
+        c->pp_pad = (c->prm.patch_r + 2) & ~1;              // even and >= R + 1: a target column is in [0, w], a sample within R of it
+        c->pp_pitch = parity_pitch(c->W[L], c->pp_pad);
+        plane((void**)&c->pp1, (size_t)2 * c->H[L] * c->pp_pitch * 4);
+        plane((void**)&c->pp2, (size_t)2 * c->H[L] * c->pp_pitch * 4);
+    }
     plane((void**)&c->nnf1, n2 * 4);
     plane((void**)&c->nnf2, n2 * 4);
     plane((void**)&c->nnf_tmp, n2 * 4);
@@ -1070,3 +1074,15 @@ extern "C" int eppm_compute_color(eppm_ctx* c, uint8_t* rgb, size_t row_stride, 
         }
     return EPPM_OK;
 }
+
+#ifdef EPPM_TEST_HOOKS
+// test library (include/eppm_test.h): the column-parity planes of a context's PatchMatch level and which kernels read them
+extern "C" int eppm_probe_pm_parity(const eppm_ctx* c, int* pitch, int* pad, int* kernels)
+{
+    if (!c || !pitch || !pad || !kernels) return set_err(EPPM_ERR_ARG, "eppm_probe_pm_parity: NULL argument");
+    *pitch = c->pp1 ? c->pp_pitch : 0;
+    *pad = c->pp1 ? c->pp_pad : 0;
+    *kernels = c->pp1 ? pm_parity_kernels(c->prm.patch_r) : 0;
+    return EPPM_OK;
+}
+#endif

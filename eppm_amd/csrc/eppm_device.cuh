@@ -121,6 +121,9 @@ struct Planes {
     int pitch;              // pixels
 };
 
+typedef uint32_t u32x4 __attribute__((ext_vector_type(4)));     // the words of a dwordx4 / dwordx2 buffer load (PlanesH::pp2 rows)
+typedef uint32_t u32x2 __attribute__((ext_vector_type(2)));
+
 #ifndef EPPM_TOL
 // The census byte is stored shifted left by 2, so that w1 ^ w2 is the byte offset of entry (c1 ^ c2) in a
 // 256-entry table cnx[b] = cn[popcount(b)]: xor + LDS read + add (4 VALU cycles fewer per sample than
@@ -136,6 +139,16 @@ __device__ __forceinline__ float4 make_texel(uint32_t rgba, uint32_t census)
 __device__ __forceinline__ float census_cost(const float* __restrict__ cnx, uint32_t w1, uint32_t w2)
 {
     return *reinterpret_cast<const float*>(reinterpret_cast<const char*>(cnx) + (EPPM_CENSUS_POPCNT ? (uint32_t)__builtin_popcount(w1 ^ w2) : (w1 ^ w2)));
+}
+// a word {R, G, B, census} of the 4-byte planes -> exactly make_texel(w, w >> 24): v_cvt_f32_ubyte0/1/2 read each byte in place (no
+// shift, no mask), the exact /255 is div_const's two operations per channel (a single multiply by fl(1/255) is wrong for 126 of the 256
+// bytes), and one v_perm replicates the census byte: 10 VALU instructions per texel.  The argument of unpack_texel's tolerance form
+// (a register holding 2) is not needed here.
+__device__ __forceinline__ float4 unpack_texel(uint32_t w, uint32_t)
+{
+    static_assert(EPPM_CENSUS_POPCNT, "the census byte replicated into its word (make_texel)");
+    const rgbf c = unpack_rgb(w);
+    return make_float4(c.x, c.y, c.z, __uint_as_float(__builtin_amdgcn_perm(w, w, 0x03030303u)));
 }
 #else
 // ---- the tolerance library (libeppm_hip_tol.so, -DEPPM_TOL) ------------------------------------------------
@@ -329,8 +342,6 @@ __device__ __forceinline__ float4 unpack_texel(uint32_t w, uint32_t two)
     static_assert(kTolScale == 4u, "the shift above");
     return make_float4(__uint_as_float(r), __uint_as_float(g), __uint_as_float(b), __uint_as_float(__builtin_amdgcn_perm(w, w, 0x03030303u)));
 }
-typedef uint32_t u32x4 __attribute__((ext_vector_type(4)));
-typedef uint32_t u32x2 __attribute__((ext_vector_type(2)));
 // cost_term = the sample's cost (NOT yet multiplied by its weight: patch_accum fuses that), weight_term = its weight
 __device__ __forceinline__ void patch_terms(const float4 q1, const float4 q2, const rgbf c1, const rgbf c2, float gsp,
                                             const TolTables& T, float& cost_term, float& weight_term)

@@ -136,6 +136,9 @@ struct PmRngDev {
 void launch_pm_rand_table(const PmRngDev& rng, uint32_t* work, int16_t* tab, int G, hipStream_t s);
 void launch_pm_init_field(const PmBatch& b, const PmRngDev& rng, hipStream_t s);
 void launch_pm_cost_field(const PmBatch& b, const float* lut, int R, hipStream_t s);
+// the PatchMatch kernels that read the column-parity planes at patch radius R when the planes exist: 1 random search, 2 phase A of the
+// sweeps, 4 cost field
+int pm_parity_kernels(int R);
 // one directional sweep; returns true when the result is in nnf_alt (caller swaps nnf/nnf_alt)
 // speculative: the two-launch form for iterations in which few candidates are accepted (k_patchmatch.hip, k_pm_sweep_spec); same results
 bool launch_pm_sweep(PmBatch& b, const float* lut, int R, int seg_len, int dir, hipStream_t s, bool speculative = false);
@@ -252,6 +255,7 @@ void launch_flow_to_color(uint32_t* rgba, const float* flow, int h, int w, float
 // ---- probes (k_prepare.hip) ----
 void launch_probe_delta(const float* x, float* y, int n, const float* delta_tab, hipStream_t s);
 void launch_probe(const float* x, float* y, int n, int which, hipStream_t s);
+void launch_probe_unpack(const uint32_t* w, float* y, int n, hipStream_t s);
 
 // ---- host XORWOW (xorwow_host.cpp) ----
 struct XorwowState { uint32_t v[5]; uint32_t d; };

@@ -153,10 +153,11 @@ template <int M> __device__ __forceinline__ float patch_dist_any(const Planes&, 
 // PK = 1: the target texels are gathered from the 4-byte plane pc2 = {R, G, B, census} and converted at use (make_texel, the function
 // that built the float4 plane: the same bits).  A 64-lane gather of 4 bytes costs the L1 38 clocks where one of 16 bytes costs 52-78
 // (tools/ubench/gather_rate.hip), the conversion 12 VALU instructions per texel: for launches whose search runs at the L1's lane
-// rate with VALU slots to spare -- radius 17, or one small pair per launch -- not for the batched radius-9 launches (VALU bound).
-// PK = 2 (tolerance library): the S samples of a patch row are S consecutive words of the target's column-parity plane (PlanesH::pp2):
-// 3 gathers per row of 10 samples (16 + 16 + 8 bytes) instead of 10, unpacked by unpack_texel.  With the patch term at a third of its
-// exact instruction count these kernels run at the L1's lane rate; this divides their gathers by 3.3.
+// rate with VALU slots to spare -- radius 17, or one small pair per launch.
+// PK = 2: the S samples of a patch row are S consecutive words of the target's column-parity plane (PlanesH::pp2): 3 gathers per row of
+// 10 samples (16 + 16 + 8 bytes) instead of 10, unpacked by unpack_texel.  These kernels run at the L1's lane rate; this divides their
+// gathers by 3.3.  The exact library pays 10 VALU instructions per texel for its exact unpack and still wins at radius 9 in the search
+// (TA busy 0.86 -> 0.36, 314 -> 280 us per 8-pair launch) and the cost field, not in phase A.
 // (The source half of a sample's weight is the same for the six guesses of a pixel; forming it once per workgroup in LDS -- 26 KB,
 // [sample][pixel] -- and a barrier LOSES here as it did in the exact library: search 215 -> 234 us per 8-pair launch, bench 304 -> 298,
 // profiles/r06x_c_search_hoist.txt.)
@@ -174,7 +175,6 @@ __device__ __forceinline__ float search_patch_dist(const Planes& P, const LUT& L
     PatchSum sum;
     constexpr int CS = tol_chunk(RT);          // tolerance library: chunk of the canonical summation order (PatchSum)
     static_assert(S % CS == 0, "whole chunks per row");
-#ifdef EPPM_TOL
     if constexpr (PK == 2) {
         static_assert(S % 4 == 2, "a row = whole dwordx4 gathers + one dwordx2");
         // buffer loads: a dwordx4 at a 4-byte aligned per-lane offset in ONE instruction (a global load of that alignment is split by the
@@ -212,7 +212,6 @@ EPPM_PM_UNROLL((TU))
         }
         return sum.result();
     }
-#endif
     const uint32_t* __restrict__ pc2 = PH.pc2;
     for (int ii = 0; ii < S; ii++) {
         const int i = 2 * ii - RT;
@@ -268,14 +267,33 @@ __global__ __launch_bounds__(256) void k_pm_cost_field_tile(PmBatch B, const flo
     pr.cost[y * B.cpitch + x] = search_patch_dist<RT, PK>(P, L, R, s_src, TW, threadIdx.x, threadIdx.y, x, y, dx, dy, pr.P);
 }
 
-// tolerance library: every problem of the launch has its target's column-parity plane (PlanesH::pp2)
-static bool pm_has_parity(const PmBatch& b)
+// every problem of the launch has its target's column-parity plane (PlanesH::pp2).  Exact library: per kernel, radius 9 only, where
+// the A/B measurement adopted it (EPPM_PARITY_*); the tolerance library: every kernel, both radii.
+#ifndef EPPM_PARITY_SEARCH
+#define EPPM_PARITY_SEARCH 1
+#endif
+#ifndef EPPM_PARITY_SPEC
+#define EPPM_PARITY_SPEC 0
+#endif
+#ifndef EPPM_PARITY_COST
+#define EPPM_PARITY_COST 1
+#endif
+static bool pm_parity_adopted(int R, bool exact_adopts)
 {
 #ifdef EPPM_TOL
-    return b.p[0].P.pp2 && (b.n < 2 || b.p[1].P.pp2);
+    (void)exact_adopts;
+    return R == 9 || R == 17;
 #else
-    return false;
+    return exact_adopts && R == 9;
 #endif
+}
+static bool pm_has_parity(const PmBatch& b, int R, bool exact_adopts)
+{
+    return pm_parity_adopted(R, exact_adopts) && b.p[0].P.pp2 && (b.n < 2 || b.p[1].P.pp2);
+}
+int pm_parity_kernels(int R)
+{
+    return (pm_parity_adopted(R, EPPM_PARITY_SEARCH) ? 1 : 0) | (pm_parity_adopted(R, EPPM_PARITY_SPEC) ? 2 : 0) | (pm_parity_adopted(R, EPPM_PARITY_COST) ? 4 : 0);
 }
 
 void launch_pm_cost_field(const PmBatch& b, const float* lut, int R, hipStream_t s)
@@ -285,8 +303,8 @@ void launch_pm_cost_field(const PmBatch& b, const float* lut, int R, hipStream_t
 #ifndef EPPM_COST_FIELD_TILE
 #define EPPM_COST_FIELD_TILE 1
 #endif
-    if (EPPM_COST_FIELD_TILE && R == 9 && pm_has_parity(b)) hipLaunchKernelGGL((k_pm_cost_field_tile<9, 2>), grid, block, 0, s, b, lut, R);
-    else if (EPPM_COST_FIELD_TILE && R == 17 && pm_has_parity(b)) hipLaunchKernelGGL((k_pm_cost_field_tile<17, 2>), grid, block, 0, s, b, lut, R);
+    if (EPPM_COST_FIELD_TILE && R == 9 && pm_has_parity(b, R, EPPM_PARITY_COST)) hipLaunchKernelGGL((k_pm_cost_field_tile<9, 2>), grid, block, 0, s, b, lut, R);
+    else if (EPPM_COST_FIELD_TILE && R == 17 && pm_has_parity(b, R, EPPM_PARITY_COST)) hipLaunchKernelGGL((k_pm_cost_field_tile<17, 2>), grid, block, 0, s, b, lut, R);
     else if (EPPM_COST_FIELD_TILE && R == 9) hipLaunchKernelGGL(k_pm_cost_field_tile<9>, grid, block, 0, s, b, lut, R);
     else if (EPPM_COST_FIELD_TILE && R == 17) hipLaunchKernelGGL(k_pm_cost_field_tile<17>, grid, block, 0, s, b, lut, R);
     else hipLaunchKernelGGL(k_pm_cost_field, grid, block, 0, s, b, lut, R);
@@ -1013,7 +1031,7 @@ static void launch_sweep_spec(const PmBatch& b, const float* lut, int R, int dir
 {
     const int w = b.p[0].P.w, h = b.p[0].P.h, gx = (w + kBlock - 1) / kBlock, gy = (h + kBlock - 1) / kBlock;
     dim3 grid(gx * gy * (b.n * b.npairs)), block(256);
-    if (pm_has_parity(b)) {
+    if (pm_has_parity(b, RT, EPPM_PARITY_SPEC)) {
         switch (dir) {
             case 0: hipLaunchKernelGGL((k_pm_sweep_spec<RT, true, false, 2>), grid, block, 0, s, b, lut, R, gx, seg_len, nseg); break;
             case 1: hipLaunchKernelGGL((k_pm_sweep_spec<RT, false, false, 2>), grid, block, 0, s, b, lut, R, gx, seg_len, nseg); break;
@@ -1158,8 +1176,8 @@ bool launch_pm_sweeps_merged(PmBatch& b, const float* lut, int R, int seg_len, i
     b.nseg_row = (w + seg_len - 1) / seg_len;
     b.nseg_col = (h + seg_len - 1) / seg_len;
     dim3 grid(gx * gy * (b.n * b.npairs)), block(256);
-    if (R == 9 && pm_has_parity(b)) hipLaunchKernelGGL((k_pm_spec_all<9, 2>), grid, block, 0, s, b, lut, R, gx);
-    else if (pm_has_parity(b)) hipLaunchKernelGGL((k_pm_spec_all<17, 2>), grid, block, 0, s, b, lut, R, gx);
+    if (R == 9 && pm_has_parity(b, R, EPPM_PARITY_SPEC)) hipLaunchKernelGGL((k_pm_spec_all<9, 2>), grid, block, 0, s, b, lut, R, gx);
+    else if (pm_has_parity(b, R, EPPM_PARITY_SPEC)) hipLaunchKernelGGL((k_pm_spec_all<17, 2>), grid, block, 0, s, b, lut, R, gx);
     else if (R == 9) hipLaunchKernelGGL(k_pm_spec_all<9>, grid, block, 0, s, b, lut, R, gx);
     else hipLaunchKernelGGL(k_pm_spec_all<17>, grid, block, 0, s, b, lut, R, gx);
     for (int dir = 0; dir < 4; dir++) {
@@ -1431,7 +1449,7 @@ void launch_pm_random_search(const PmBatch& b, const PmRngDev& rng, const float*
 #ifndef EPPM_SEARCH_HALF_BELOW_WGS
 #define EPPM_SEARCH_HALF_BELOW_WGS 1024       // under four quarter-workgroups per CU: eighth-block workgroups (PatchMatch of one 1024x436 pair 1.362 -> 1.330 ms;
 #endif                                        // at 4080 workgroups, one 1920x1080 pair, they lose: 4.49 -> 4.57 ms)
-        if (pm_has_parity(b)) {                                                        // tolerance library: column-parity target planes
+        if (pm_has_parity(b, R, EPPM_PARITY_SEARCH)) {                                 // column-parity target planes
             if (R == 9 && (int)grid.x < EPPM_SEARCH_HALF_BELOW_WGS)
                 hipLaunchKernelGGL((k_pm_random_search<9, 2, true, 2>), dim3(grid.x * 2), dim3(32 * num_guess), 0, s, b, rng, lut, R, search_range, num_guess);
             else if (R == 9) hipLaunchKernelGGL((k_pm_random_search<9, 2, true>), grid, blockt, 0, s, b, rng, lut, R, search_range, num_guess);

@@ -38,6 +38,20 @@ void launch_probe_delta(const float* x, float* y, int n, const float* tab, hipSt
 {
     hipLaunchKernelGGL(k_probe_delta, dim3((n + 255) / 256), dim3(256), 0, s, x, y, n, tab);
 }
+// y[2i] = unpack_texel(w[i]) (the exact library's read of a column-parity plane word), y[2i + 1] = make_texel(w[i], w[i] >> 24) (the
+// function that builds the float4 plane): the two must agree bit for bit
+__global__ __launch_bounds__(256) void k_probe_unpack(const uint32_t* __restrict__ w, float4* __restrict__ y, int n)
+{
+    const int i = blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= n) return;
+    const uint32_t v = w[i];
+    y[2 * i] = unpack_texel(v, 2u);
+    y[2 * i + 1] = make_texel(v, v >> 24);
+}
+void launch_probe_unpack(const uint32_t* w, float* y, int n, hipStream_t s)
+{
+    hipLaunchKernelGGL(k_probe_unpack, dim3((n + 255) / 256), dim3(256), 0, s, w, (float4*)y, n);
+}
 void launch_probe(const float* x, float* y, int n, int which, hipStream_t s)
 {
     hipLaunchKernelGGL(k_probe, dim3((n + 255) / 256), dim3(256), 0, s, x, y, n, which);

@@ -62,3 +62,17 @@ extern "C" int eppm_probe_delta_table(const float* x, float* y, int n, int which
     (void)hipFree(dx); (void)hipFree(dy); (void)hipFree(lut);
     return launcher_finish();
 }
+// y[8i .. 8i+3] = unpack_texel(w[i]), y[8i+4 .. 8i+7] = make_texel(w[i], w[i] >> 24)
+extern "C" int eppm_probe_unpack_texel(const uint32_t* w, float* y, int n)
+{
+    if (!w || !y || n < 1) return set_err(EPPM_ERR_ARG, "eppm_probe_unpack_texel: bad argument");
+    uint32_t* dw = nullptr;
+    float* dy = nullptr;
+    HIPCHK(hipMalloc(&dw, (size_t)n * 4));
+    HIPCHK(hipMalloc(&dy, (size_t)n * 32));
+    HIPCHK(hipMemcpy(dw, w, (size_t)n * 4, hipMemcpyHostToDevice));
+    launch_probe_unpack(dw, dy, n, nullptr);
+    HIPCHK(hipMemcpy(y, dy, (size_t)n * 32, hipMemcpyDeviceToHost));
+    (void)hipFree(dw); (void)hipFree(dy);
+    return launcher_finish();
+}

@@ -3,7 +3,7 @@
  *
  * libeppm_hip_test.so is libeppm_hip.so's own objects (every kernel, the launchers, the C++ class: the same .o files) with
  * eppm_api.cpp compiled once more with -DEPPM_TEST_HOOKS and k_probe.hip added (eppm_amd/csrc/Makefile).  It exports everything
- * include/eppm.h declares plus the four entry points below; the product library exports none of them and has no switch a host
+ * include/eppm.h declares plus the entry points below; the product library exports none of them and has no switch a host
  * program could flip: `nm -D libeppm_hip.so | grep -c "eppm_test\|eppm_probe"` is 0 (tests/test_abi_cpu.py).
  * The parity tests load the test library; bench.py, smoke(), the CLI and the C++ class link the product library.
  */
@@ -37,6 +37,12 @@ int  eppm_probe_div_const(const float* x, float* y, int n, int which); /* 0: /(.
  * (eppm_device.cuh: DeltaTab): y[i] = table(x[i]); which = 0: 1 - exp(-d^2/(.1f*.1f)) of the patch data term, 1: exp(-d^2/(.02f*.02f)) of
  * the smoothing and weighted-median weights.  x must be such distances (|a/255 - b/255| of two bytes, as floats). */
 int  eppm_probe_delta_table(const float* x, float* y, int n, int which);
+/* a word {R, G, B, census} of the 4-byte texel planes read as the exact library's PatchMatch kernels read a column-parity plane word
+ * (eppm_device.cuh: unpack_texel) and as the float4 plane is built from it (make_texel): y[8i .. 8i+3] and y[8i+4 .. 8i+7], n words */
+int  eppm_probe_unpack_texel(const uint32_t* w, float* y, int n);
+/* the column-parity planes of a context's PatchMatch level: words per row of one parity plane and padding columns (0, 0: none), and
+ * which kernels read them (bit 0 random search, bit 1 phase A of the sweeps, bit 2 cost field; 0 without planes) */
+int  eppm_probe_pm_parity(const eppm_ctx* ctx, int* pitch, int* pad, int* kernels);
 
 #ifdef __cplusplus
 }
