@@ -53,12 +53,14 @@ SYMBOLS = [
     "eppm_interpolate", "eppm_interpolate_device", "eppm_batch_interpolate", "eppm_interpolate_frames", "eppm_interpolate_host",
     "eppm_track_default_params", "eppm_track_capacity", "eppm_tracker_create", "eppm_tracker_destroy", "eppm_track_step",
     "eppm_track_step_frames", "eppm_tracker_get", "eppm_tracker_get_ended", "eppm_tracker_set", "eppm_track_step_host", "eppm_track_seeds_host",
+    "eppm_push_image", "eppm_push_image_device", "eppm_set_temporal", "eppm_temporal_reset", "eppm_temporal_valid", "eppm_temporal_prior_host",
+    "eppm_temporal_prior",
 ]
 
 
 # what include/eppm_test.h adds, exported by libeppm_hip_test.so only (the parity tests' switches and arithmetic probes)
 TEST_SYMBOLS = ["eppm_test_set_option", "eppm_probe_c2f_window", "eppm_probe_fast_exp", "eppm_probe_div_const", "eppm_probe_delta_table",
-                "eppm_probe_unpack_texel", "eppm_probe_pm_parity"]
+                "eppm_probe_unpack_texel", "eppm_probe_pm_parity", "eppm_probe_ctx_rng_states"]
 
 _variant = None
 

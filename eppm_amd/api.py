@@ -11,7 +11,8 @@ float2 = np.dtype([("x", "f4"), ("y", "f4")])
 
 _PLANE_DTYPES = {"img1": uchar4, "img2": uchar4, "census1": np.uint8, "census2": np.uint8, "nnf1": short2,
                  "nnf2": short2, "cost1": np.float32, "cost2": np.float32, "flow": float2,
-                 "flow_bwd": float2, "occ1": np.uint8, "occ2": np.uint8}
+                 "flow_bwd": float2, "occ1": np.uint8, "occ2": np.uint8,
+                 "prior1": short2, "prior2": short2, "nnf_init1": short2, "nnf_init2": short2, "cost_init1": np.float32, "cost_init2": np.float32}
 
 
 def Params(**kw):
@@ -145,14 +146,86 @@ class Tracker:
             pass
 
 
-def track_sequence(frames, params=None, **track_params):
+def flow_sequence(frames, params=None, temporal=True, bidirectional=False):
+    """The flows of the consecutive pairs of a clip ((h, w, 3) uint8 frames) through ONE context: the first pair by set_data, every later
+    frame by push_frame (only the new frame is uploaded and prepared), with temporal mode (each pair's PatchMatch starts from the previous
+    pair's result moved along its motion) unless temporal=False.  Returns a list of (u, v), or of (u, v, bu, bv, occ1, occ2) with
+    bidirectional=True.  Memory does not grow with the clip."""
+    frames = [np.ascontiguousarray(f, np.uint8) for f in frames]
+    if len(frames) < 2:
+        raise EppmError("flow_sequence: at least two frames")
+    h, w, _ = frames[0].shape
+    e = EPPM(params=params)
+    out = []
+    try:
+        e.init(h, w)
+        e.set_temporal(temporal)
+        for k in range(len(frames) - 1):
+            if k == 0:
+                e.set_data(frames[0], frames[1])
+            else:
+                e.push_frame(frames[k + 1])
+            out.append(e.compute_flow_bidirectional() if bidirectional else e.compute_flow())
+    finally:
+        e.close()
+    return out
+
+
+def _track_collect(out, trk):
+    """one step's ended and live tracks into track_sequence's dictionary"""
+    e_ids, _, _, why, _ = trk.ended()
+    for i, r in zip(e_ids.tolist(), why.tolist()):
+        out[i]["reason"] = int(r)
+    ids, starts, xy = trk.tracks()
+    for i, s0, p in zip(ids.tolist(), starts.tolist(), xy):
+        if i in out:
+            out[i]["positions"].append(p)
+        else:
+            out[i] = {"start": int(s0), "positions": [p], "reason": None}
+
+
+def _track_sequence_streaming(frames, params, track_params):
+    from . import io
+    h, w, _ = frames[0].shape
+    e = EPPM(params=params)
+    trk = None
+    try:
+        e.init(h, w)
+        e.set_temporal(True)
+        for k in range(len(frames) - 1):
+            if k == 0:
+                e.set_data(frames[0], frames[1])
+            else:
+                e.push_frame(frames[k + 1])
+            e.compute_flow_bidirectional_device()
+            if trk is None:
+                trk = Tracker(e, 0, **track_params)
+                seeds = io.track_seeds(frames[0], trk.params)[:trk.capacity]
+                out = {i: {"start": 0, "positions": [xy], "reason": None} for i, xy in enumerate(seeds)}
+            trk.step()
+            _track_collect(out, trk)
+    finally:
+        if trk is not None:
+            trk.close()
+        e.close()
+    for t in out.values():
+        t["positions"] = np.asarray(t["positions"], np.float32).reshape(-1, 2)
+    return out
+
+
+def track_sequence(frames, params=None, streaming=False, **track_params):
     """Dense point trajectories through a list of (h, w, 3) uint8 frames: one bidirectional call on a batch of the consecutive pairs, then
     one tracker step per pair.  Returns {track id: {"start": first frame, "positions": (n, 2) float32 positions in frames start ..
-    start + n - 1, "reason": the end reason 1..4, or None while alive}}.  params: the flow's eppm Params; track_params: TrackParams'."""
+    start + n - 1, "reason": the end reason 1..4, or None while alive}}.  params: the flow's eppm Params; track_params: TrackParams'.
+    streaming=True: one single-pair context instead of the batch -- push_frame and temporal mode, one bidirectional call and one tracker
+    step per pair --, so that memory does not grow with the clip; the flows from the second pair on start from a temporal prior and are
+    not bit for bit the batch's."""
     from . import io
     frames = [np.ascontiguousarray(f, np.uint8) for f in frames]
     if len(frames) < 2:
         raise EppmError("track_sequence: at least two frames")
+    if streaming:
+        return _track_sequence_streaming(frames, params, track_params)
     h, w, _ = frames[0].shape
     bat = EPPMBatch(h, w, len(frames) - 1, params=params)
     trk = None
@@ -222,6 +295,34 @@ class EPPM:
         check(lib().eppm_set_images(self._ctx, a.ctypes.data_as(C.c_void_p), b.ctypes.data_as(C.c_void_p),
                                     C.c_size_t(self.w * 3)), "eppm_set_images")
         return True
+
+    # -- streaming -------------------------------------------------------
+    def push_frame(self, img):
+        """Image 2 becomes image 1, img becomes image 2 (eppm_push_image): only img is uploaded and prepared."""
+        self._need()
+        a = np.ascontiguousarray(img, np.uint8)
+        if a.shape != (self.h, self.w, 3):
+            raise EppmError(f"push_frame: the image must be ({self.h},{self.w},3) uint8")
+        check(lib().eppm_push_image(self._ctx, a.ctypes.data_as(C.c_void_p), C.c_size_t(self.w * 3)), "eppm_push_image")
+
+    def push_frame_device(self, d_rgba, pitch):
+        self._need()
+        check(lib().eppm_push_image_device(self._ctx, C.c_void_p(d_rgba), C.c_size_t(pitch)), "eppm_push_image_device")
+
+    def set_temporal(self, on=True):
+        """Temporal mode (eppm_set_temporal): a compute after push_frame starts PatchMatch from the previous pair's result moved along its
+        own motion; set_data starts a new clip."""
+        self._need()
+        check(lib().eppm_set_temporal(self._ctx, int(bool(on))), "eppm_set_temporal")
+
+    def temporal_reset(self):
+        """Drop the previous pair's fields: the next compute is a cold run (eppm_temporal_reset)."""
+        self._need()
+        check(lib().eppm_temporal_reset(self._ctx), "eppm_temporal_reset")
+
+    def temporal_valid(self):
+        self._need()
+        return bool(lib().eppm_temporal_valid(self._ctx))
 
     def _out(self, out):
         if out is None:

@@ -130,6 +130,9 @@ EPPM_HIDDEN void sweep(eppm::PmBatch& b, const float* lut, const eppm_params& pr
 EPPM_HIDDEN void jump(eppm::PmBatch& b, const float* lut, const eppm_params& prm, hipStream_t s);
 EPPM_HIDDEN void neighbor(eppm::PmBatch& b, const float* lut, const eppm_params& prm, int launches, hipStream_t s);
 EPPM_HIDDEN void run_patchmatch(eppm::PmBatch& b, eppm_pm_rng* rng, const float* lut, const eppm_params& prm, hipStream_t s, int spec_mode);
+// run_patchmatch = pm_start (random field + cost field) then pm_iterate (num_iter x [sweeps + search])
+EPPM_HIDDEN void pm_start(eppm::PmBatch& b, eppm_pm_rng* rng, const float* lut, const eppm_params& prm, hipStream_t s);
+EPPM_HIDDEN void pm_iterate(eppm::PmBatch& b, eppm_pm_rng* rng, const float* lut, const eppm_params& prm, hipStream_t s, int spec_mode);
 #ifndef EPPM_SWEEP_CACHE
 #define EPPM_SWEEP_CACHE 1
 #endif

@@ -2,6 +2,7 @@
 // :112-157, :170-209), set_images (set_data :159-168 + _prepare_data :212-215), compute (compute_flow :217-306), planes, stage times.
 #include "api_internal.h"
 #include "interp.h"
+#include "temporal.h"
 
 using namespace eppm;
 
@@ -85,6 +86,19 @@ struct eppm_ctx {
     int32_t *itp_fill1 = nullptr, *itp_fill2 = nullptr;
     uint8_t* itp_rgb = nullptr;
     uint8_t* h_itp = nullptr;
+    // Streaming mode (eppm_set_temporal; single-pair contexts only): its own allocation, made by the first compute
+    // with the mode on.  Level-L planes, unpitched: the two displacement snapshots of the last compute (prev_fwd: the field nnf2flow
+    // converted, prev_bwd: the raw backward NNF), the two advected priors, the seeded start as the select kernel left it, and the landing
+    // keys of both directions (kTemporalNoKey between launches).
+    bool temporal = false;
+    bool tmp_snap = false;              // the snapshots hold the last compute's pair, and no frame has been pushed since
+    bool tmp_valid = false;             // armed by a push that found such snapshots: the next compute starts from their prior
+    bool tmp_seeded = false;            // the last compute started from a prior: prior*, nnf_init*, cost_init* are its planes
+    char* tmp = nullptr;
+    size_t tmp_bytes = 0;
+    int16_t *prev_fwd = nullptr, *prev_bwd = nullptr, *prior1 = nullptr, *prior2 = nullptr, *nnf_init1 = nullptr, *nnf_init2 = nullptr;
+    float *cost_init1 = nullptr, *cost_init2 = nullptr;
+    int32_t* tmp_keys = nullptr;        // 2 x W[L]*H[L]
     int timing = 0;                     // 0 off, 1 every stage, 2 only the dominant kernel (the candidate refine)
     std::vector<StageEv> ev;
     std::vector<StageEv> ev_prep;
@@ -133,6 +147,12 @@ static void stage_end(eppm_ctx* c, std::vector<StageEv>& v, bool dominant = fals
     if (!stage_on(c, dominant)) return;
     (void)hipEventRecord(v.back().b, c->stream);
 }
+// closes entry `idx` (stages opened after it have been closed: a stage inside a stage)
+static void stage_end_at(eppm_ctx* c, std::vector<StageEv>& v, size_t idx)
+{
+    if (!stage_on(c, false)) return;
+    (void)hipEventRecord(v[idx].b, c->stream);
+}
 static void clear_events(eppm_ctx* c, std::vector<StageEv>& v)
 {
     for (auto& e : v) { c->ev_pool.push_back(e.a); c->ev_pool.push_back(e.b); }
@@ -160,6 +180,7 @@ extern "C" int eppm_destroy(eppm_ctx* c)
     cache_free(c->h_bwd, c->h_bwd_bytes, true, c->device);
     cache_free(c->itp, c->itp_bytes, false, c->device);
     cache_free(c->h_itp, c->h_itp_bytes, true, c->device);
+    cache_free(c->tmp, c->tmp_bytes, false, c->device);
     rng_free(c->rng);
     if (c->own_stream && c->stream) pooled_stream_destroy(c->stream, c->device);
     delete c;
@@ -327,15 +348,17 @@ extern "C" int eppm_enable_stage_timing(eppm_ctx* c, int on)
 }
 
 // ---- prepare: refine :1060-1071 + .cuh:642-664.  The two frames of every active pair share every launch; the raw
-// RGBA planes of the active pairs are in the slabs already. ----
-static int prepare(eppm_ctx* c)
+// RGBA planes of the active pairs are in the slabs already.  only2: image 2 alone (eppm_push_image: image 1's planes are the previous
+// pair's image-2 planes); every kernel is per pixel of one image, so its planes equal those of a launch that covers both images. ----
+static int prepare(eppm_ctx* c, bool only2 = false)
 {
     stage_begin(c, c->ev_prep, "prepare");
     hipStream_t s = c->stream;
     const Batch bt = c->bt();
     uint32_t **p1 = c->img1, **p2 = c->img2, **tmp = c->tmpu;
     const int p0 = (int)(c->ipitch[0] / 4);
-    launch_gauss_rgba2(p1[0], c->raw1, p2[0], c->raw2, p0, c->H[0], c->W[0], .5f, 2, s, bt);    // refine :1063-1064
+    if (only2) launch_gauss_rgba(p2[0], c->raw2, p0, c->H[0], c->W[0], .5f, 2, s, bt);
+    else launch_gauss_rgba2(p1[0], c->raw1, p2[0], c->raw2, p0, c->H[0], c->W[0], .5f, 2, s, bt);    // refine :1063-1064
     const float ratio = 0.5f;                                                             // PYR_RATIO
     const float baseSigma = (1 / ratio - 1);
     const int n = (int)(log(0.25) / (double)logf(ratio));   // C++ float overload in the reference: n = 1
@@ -349,9 +372,10 @@ static int prepare(eppm_ctx* c)
         const int pj = (int)(c->ipitch[j] / 4), pi = (int)(c->ipitch[i] / 4);
         if (gauss_decimate2_ok(c->H[i], c->W[i], c->H[j], c->W[j], r, radius)) {
             // exact 2:1 step: blur only the pixels the decimation keeps (a quarter of the level)
-            launch_gauss_decimate2(p1[i], p1[j], p2[i], p2[j], 2, pi, c->H[i], c->W[i], pj, c->H[j], c->W[j], sigma, radius, s, bt);
+            if (only2) launch_gauss_decimate2(p2[i], p2[j], p2[i], p2[j], 1, pi, c->H[i], c->W[i], pj, c->H[j], c->W[j], sigma, radius, s, bt);
+            else launch_gauss_decimate2(p1[i], p1[j], p2[i], p2[j], 2, pi, c->H[i], c->W[i], pj, c->H[j], c->W[j], sigma, radius, s, bt);
         } else {
-            for (int k = 0; k < 2; k++) {
+            for (int k = only2 ? 1 : 0; k < 2; k++) {
                 uint32_t** pyr = k ? p2 : p1;
                 launch_gauss_rgba(tmp[j], pyr[j], pj, c->H[j], c->W[j], sigma, radius, s, bt);
                 launch_resize_rgba(pyr[i], pi, c->H[i], c->W[i], tmp[j], pj, c->H[j], c->W[j], r, s, bt);
@@ -360,7 +384,7 @@ static int prepare(eppm_ctx* c)
     }
     CensusBatch cb;
     cb.n = 0;
-    for (int k = 0; k < 2; k++)
+    for (int k = only2 ? 1 : 0; k < 2; k++)
         for (int i = 0; i < c->nl; i++) {
             CensusJob& J = cb.job[cb.n++];
             J.census = k ? c->cen2[i] : c->cen1[i]; J.cpitch = (int)c->cpitch[i];
@@ -372,7 +396,7 @@ static int prepare(eppm_ctx* c)
     launch_census_batch(cb, s, bt);
     if (c->pp1) {
         const int L = c->nl - 1;
-        launch_parity_planes(c->pp1, c->pp_pitch, c->pp_pad, c->pc1[L], c->W[L], c->W[L], c->H[L], s, bt);
+        if (!only2) launch_parity_planes(c->pp1, c->pp_pitch, c->pp_pad, c->pc1[L], c->W[L], c->W[L], c->H[L], s, bt);
         launch_parity_planes(c->pp2, c->pp_pitch, c->pp_pad, c->pc2[L], c->W[L], c->W[L], c->H[L], s, bt);
     }
     stage_end(c, c->ev_prep);
@@ -433,6 +457,7 @@ static int set_images_host_impl(eppm_ctx* c, int n, const uint8_t* const* rgb1, 
         HIPCHK(hipEventRecord(c->ev_h2d, c->stream));
     }
     c->n_active = n;
+    c->tmp_valid = c->tmp_snap = false; // a new pair is a new clip
     const int p0 = (int)(c->raw_pitch / 4);
     launch_rgb_to_rgba(c->raw1, p0, c->d_rgb, c->h, c->w, c->stream, c->bt());
     launch_rgb_to_rgba(c->raw2, p0, c->d_rgb + img, c->h, c->w, c->stream, c->bt());
@@ -475,6 +500,7 @@ static int set_images_device(eppm_ctx* c, int n, const void* const* d1, const vo
         HIPCHK(hipMemcpy2DAsync(c->of_pair(c->raw2, k), c->raw_pitch, d2[k], pitch, (size_t)c->w * 4, c->h, hipMemcpyDeviceToDevice, c->stream));
     }
     c->n_active = n;
+    c->tmp_valid = c->tmp_snap = false;
     return prepare(c);
 }
 
@@ -491,6 +517,131 @@ extern "C" int eppm_batch_set_images_device(eppm_ctx* c, int n, const void* cons
     return set_images_device(c, n, d_rgba1, d_rgba2, pitch);
 }
 
+// ---- frame push: image 2 becomes image 1 by exchanging the context's plane pointers -- the raw frame, every
+// pyramid level, census plane and texel plane of the old image 2 are kept --, the new frame becomes image 2 and is prepared alone ----
+static int push_check(eppm_ctx* c, const char* what)
+{
+    if (c->npairs != 1) return set_err(EPPM_ERR_ARG, "%s: a batch context has no previous pair (its pairs run concurrently)", what);
+    if (!c->have_images) return set_err(EPPM_ERR_STATE, "%s: no pair set yet (eppm_set_images first)", what);
+    if (c->flow_pending) return set_err(EPPM_ERR_STATE, "%s: an eppm_compute_begin is pending", what);
+    return EPPM_OK;
+}
+// also arms the temporal prior: the snapshots describe the pair that ends in the new image 1 only directly after that pair's compute
+static void push_swap(eppm_ctx* c)
+{
+    c->tmp_valid = c->temporal && c->tmp_snap;
+    c->tmp_snap = false;
+    std::swap(c->raw1, c->raw2);
+    for (int l = 0; l < c->nl; l++) {
+        std::swap(c->img1[l], c->img2[l]);
+        std::swap(c->cen1[l], c->cen2[l]);
+        std::swap(c->pk1[l], c->pk2[l]);
+        std::swap(c->pc1[l], c->pc2[l]);
+    }
+    std::swap(c->pp1, c->pp2);
+}
+
+static int push_image_host_impl(eppm_ctx* c, const uint8_t* rgb, size_t row_stride, HostHold& hold)
+{
+    if (row_stride < (size_t)c->w * 3) return set_err(EPPM_ERR_ARG, "eppm_push_image: row_stride %zu < 3*w", row_stride);
+    HIPCHK(hipSetDevice(c->device));
+    const size_t row = (size_t)c->w * 3, img = row * c->h, span = row_stride * (c->h - 1) + row;
+    uint8_t* dst = c->d_rgb + img;                       // image 2's half of the RGB staging plane
+    bool direct = false;
+    if (hold.add(rgb, span)) {
+        if (row_stride == row) HIPCHK(hipMemcpyAsync(dst, rgb, img, hipMemcpyHostToDevice, c->stream));
+        else HIPCHK(hipMemcpy2DAsync(dst, row, rgb, row_stride, row, c->h, hipMemcpyHostToDevice, c->stream));
+        direct = true;
+    } else {
+        const int q = c->rgb_cur;
+        if (!c->h_rgb[q]) {
+            c->h_rgb_bytes = img * 2 * c->npairs;
+            HIPCHK(cache_alloc((void**)&c->h_rgb[q], c->h_rgb_bytes, true, c->device));
+            HIPCHK(hipEventCreateWithFlags(&c->ev_rgb[q], hipEventDisableTiming));
+        } else {
+            HIPCHK(hipEventSynchronize(c->ev_rgb[q]));
+        }
+        uint8_t* h = c->h_rgb[q] + img;
+        if (row_stride == row) memcpy(h, rgb, img);
+        else
+            for (int y = 0; y < c->h; y++) memcpy(h + (size_t)y * row, rgb + (size_t)y * row_stride, row);
+        HIPCHK(hipMemcpyAsync(dst, h, img, hipMemcpyHostToDevice, c->stream));
+        HIPCHK(hipEventRecord(c->ev_rgb[q], c->stream));
+        c->rgb_cur ^= 1;
+    }
+    if (direct) {
+        if (!c->ev_h2d) HIPCHK(hipEventCreateWithFlags(&c->ev_h2d, hipEventDisableTiming));
+        HIPCHK(hipEventRecord(c->ev_h2d, c->stream));
+    }
+    push_swap(c);
+    launch_rgb_to_rgba(c->raw2, (int)(c->raw_pitch / 4), dst, c->h, c->w, c->stream, c->bt());
+    const int r = prepare(c, true);
+    if (direct) HIPCHK(hipEventSynchronize(c->ev_h2d));
+    return r;
+}
+
+extern "C" int eppm_push_image(eppm_ctx* c, const uint8_t* rgb, size_t row_stride)
+{
+    if (!c || !rgb) return set_err(EPPM_ERR_ARG, "eppm_push_image: NULL argument");
+    CHK(push_check(c, "eppm_push_image"));
+    HostHold hold;
+    const int r = push_image_host_impl(c, rgb, row_stride, hold);
+    if (r != EPPM_OK && !hold.v.empty()) (void)hipStreamSynchronize(c->stream);
+    return r;
+}
+
+extern "C" int eppm_push_image_device(eppm_ctx* c, const void* d_rgba, size_t pitch)
+{
+    if (!c || !d_rgba) return set_err(EPPM_ERR_ARG, "eppm_push_image_device: NULL argument");
+    CHK(push_check(c, "eppm_push_image_device"));
+    if (pitch < (size_t)c->w * 4 || (pitch & 3)) return set_err(EPPM_ERR_ARG, "eppm_push_image_device: bad pitch %zu", pitch);
+    HIPCHK(hipSetDevice(c->device));
+    // into the old image 1's raw plane, which the swap then makes image 2's: a copy that fails leaves the context on its old pair
+    HIPCHK(hipMemcpy2DAsync(c->raw1, c->raw_pitch, d_rgba, pitch, (size_t)c->w * 4, c->h, hipMemcpyDeviceToDevice, c->stream));
+    push_swap(c);
+    return prepare(c, true);
+}
+
+// ---- temporal mode ----
+static int tmp_alloc(eppm_ctx* c)
+{
+    if (c->tmp) return EPPM_OK;
+    const int L = c->nl - 1;
+    const size_t n2 = (size_t)c->W[L] * c->H[L];
+    size_t off = 0;
+    auto take = [&](size_t bytes) { const size_t o = off; off = (off + bytes + 255) & ~(size_t)255; return o; };
+    size_t o[9];
+    for (int k = 0; k < 8; k++) o[k] = take(n2 * 4);       // six short2 planes, two float planes
+    o[8] = take(n2 * 4 * 2);                               // the keys of both directions
+    const hipError_t e = cache_alloc((void**)&c->tmp, off, false, c->device);
+    if (e != hipSuccess) { (void)hipGetLastError(); c->tmp = nullptr; return set_err(EPPM_ERR_HIP, "hipMalloc of %zu bytes (temporal planes) failed: %s", off, hipGetErrorString(e)); }
+    c->tmp_bytes = off;
+    c->prev_fwd = (int16_t*)(c->tmp + o[0]); c->prev_bwd = (int16_t*)(c->tmp + o[1]);
+    c->prior1 = (int16_t*)(c->tmp + o[2]);   c->prior2 = (int16_t*)(c->tmp + o[3]);
+    c->nnf_init1 = (int16_t*)(c->tmp + o[4]); c->nnf_init2 = (int16_t*)(c->tmp + o[5]);
+    c->cost_init1 = (float*)(c->tmp + o[6]);  c->cost_init2 = (float*)(c->tmp + o[7]);
+    c->tmp_keys = (int32_t*)(c->tmp + o[8]);
+    launch_temporal_keys_init(c->tmp_keys, (int)(2 * n2), c->stream);
+    HIPCHK(hipGetLastError());
+    return EPPM_OK;
+}
+
+extern "C" int eppm_set_temporal(eppm_ctx* c, int on)
+{
+    if (!c) return set_err(EPPM_ERR_ARG, "eppm_set_temporal: NULL ctx");
+    if (on && c->npairs != 1) return set_err(EPPM_ERR_ARG, "eppm_set_temporal: a batch context has no previous pair (its pairs run concurrently)");
+    c->temporal = on != 0;
+    if (!on) c->tmp_valid = c->tmp_snap = false;
+    return EPPM_OK;
+}
+extern "C" int eppm_temporal_reset(eppm_ctx* c)
+{
+    if (!c) return set_err(EPPM_ERR_ARG, "eppm_temporal_reset: NULL ctx");
+    c->tmp_valid = c->tmp_snap = false;
+    return EPPM_OK;
+}
+extern "C" int eppm_temporal_valid(const eppm_ctx* c) { return c && c->temporal && c->tmp_valid ? 1 : 0; }
+
 static int compute_all(eppm_ctx* c)
 {
     if (!c->have_images) return set_err(EPPM_ERR_STATE, "eppm_compute: no images set");
@@ -501,6 +652,23 @@ static int compute_all(eppm_ctx* c)
     const int L = c->nl - 1;                                            // pm_layer, driver :219
     const int lw = c->W[L], lh = c->H[L];
 
+    // temporal mode: the snapshots of the previous pair of the clip, advected, seed this pair's PatchMatch; without them the run is cold
+    const bool tmode = c->temporal, seeded = tmode && c->tmp_valid;
+    c->tmp_seeded = false;
+    if (tmode) CHK(tmp_alloc(c));
+    if (seeded) {
+        TemporalArgs a;
+        a.prev[0] = c->prev_fwd; a.prior[0] = c->prior1; a.keys[0] = c->tmp_keys; a.step[0] = 1;
+        a.prev[1] = c->prev_bwd; a.prior[1] = c->prior2; a.keys[1] = c->tmp_keys + (size_t)lw * lh; a.step[1] = -1;
+        a.w = lw; a.h = lh; a.ndir = 2;
+        stage_begin(c, c->ev, "temporal_advect");
+        launch_temporal_splat(a, s);
+        launch_temporal_gather(a, s);
+        stage_end(c, c->ev);
+    }
+    c->tmp_valid = c->tmp_snap = false;
+
+    const size_t pm_entry = c->ev.size();
     stage_begin(c, c->ev, "patchmatch");
     {
         PmBatch b;
@@ -510,9 +678,21 @@ static int compute_all(eppm_ctx* c)
         b.wl_units = pm_worklist_units(lw, lh, c->prm.seg_len);
         b.p[0] = mk_problem(planes(c, L, false), c->cost1, c->nnf1, c->nnf_tmp, c->rng, 0, c->spec1, EPPM_SWEEP_CACHE ? c->scand1 : nullptr, sweep_list_on(c->opt_sweep_spec) ? c->wl1 : nullptr, c->seed1);     // driver :223
         b.p[1] = mk_problem(planes(c, L, true), c->cost2, c->nnf2, c->nnf_tmp2, c->rng, 1, c->spec2, EPPM_SWEEP_CACHE ? c->scand2 : nullptr, sweep_list_on(c->opt_sweep_spec) ? c->wl2 : nullptr, c->seed2);     // driver :224
-        run_patchmatch(b, c->rng, c->lut_pm, c->prm, s, c->opt_sweep_spec);
+        if (!seeded) run_patchmatch(b, c->rng, c->lut_pm, c->prm, s, c->opt_sweep_spec);
+        else {
+            // the random field and its costs as in a cold run (the generator states too), then the prior where it is strictly cheaper
+            pm_start(b, c->rng, c->lut_pm, c->prm, s);
+            PmSeed sd;
+            sd.prior[0] = c->prior1; sd.nnf_init[0] = c->nnf_init1; sd.cost_init[0] = c->cost_init1;
+            sd.prior[1] = c->prior2; sd.nnf_init[1] = c->nnf_init2; sd.cost_init[1] = c->cost_init2;
+            stage_begin(c, c->ev, "temporal_select");
+            launch_pm_cost_select(b, sd, c->lut_pm, c->prm.patch_r, s);
+            stage_end(c, c->ev);
+            pm_iterate(b, c->rng, c->lut_pm, c->prm, s, c->opt_sweep_spec);
+        }
     }
-    stage_end(c, c->ev);
+    stage_end_at(c, c->ev, pm_entry);
+    if (tmode) launch_temporal_snapshot(c->prev_bwd, c->nnf2, lw, lw, lh, s);          // the raw backward NNF, before the left-right check
 
     stage_begin(c, c->ev, "l2_post");
     launch_lr_check(c->nnf1, c->cost1, c->nnf2, lw, lh, lw, lw, s, bt);                                      // driver :233
@@ -524,7 +704,8 @@ static int compute_all(eppm_ctx* c)
         std::swap(c->nnf1, c->nnf_tmp);
     launch_fill_holes(c->nnf_tmp, c->nnf1, c->img1[L], (int)(c->ipitch[L] / 4), lw, lh, lw, s, bt);          // driver :240
     std::swap(c->nnf1, c->nnf_tmp);
-    launch_nnf2flow(c->flow[L], lw, c->nnf1, lw, lw, lh, s, bt);                                             // driver :258
+    if (tmode) launch_nnf2flow_snapshot(c->flow[L], lw, c->prev_fwd, c->nnf1, lw, lw, lh, s);
+    else launch_nnf2flow(c->flow[L], lw, c->nnf1, lw, lw, lh, s, bt);                                        // driver :258
     stage_end(c, c->ev);
 
     static const char* up_names[] = {"upsample_L0", "upsample_L1", "upsample_L2", "upsample_L3", "upsample_L4", "upsample_L5", "upsample_L6"};
@@ -548,6 +729,8 @@ static int compute_all(eppm_ctx* c)
     stage_end(c, c->ev);
     HIPCHK(hipGetLastError());
     c->have_flow = true;
+    c->tmp_snap = tmode;                // a prior is armed by the next push, not by another compute on this pair
+    c->tmp_seeded = seeded;
     return EPPM_OK;
 }
 
@@ -1044,6 +1227,13 @@ extern "C" int eppm_batch_get_plane(eppm_ctx* c, int pair, const char* name, int
         pitch = (size_t)w * esz;
         pstride = c->bwd_stride;
     }
+    else if (level == L && (n == "prior1" || n == "prior2" || n == "nnf_init1" || n == "nnf_init2" || n == "cost_init1" || n == "cost_init2")) {
+        if (!c->tmp_seeded) return set_err(EPPM_ERR_STATE, "eppm_get_plane: '%s' needs a compute that started from a temporal prior", name);
+        src = n == "prior1" ? (void*)c->prior1 : n == "prior2" ? (void*)c->prior2 : n == "nnf_init1" ? (void*)c->nnf_init1 : n == "nnf_init2" ? (void*)c->nnf_init2
+            : n == "cost_init1" ? (void*)c->cost_init1 : (void*)c->cost_init2;
+        esz = 4; pitch = (size_t)w * 4;
+        pstride = 0;
+    }
     else return set_err(EPPM_ERR_ARG, "eppm_get_plane: unknown plane '%s' at level %d", name, level);
     if (dst_bytes < (size_t)w * h * esz) return set_err(EPPM_ERR_ARG, "eppm_get_plane: dst too small");
     HIPCHK(hipMemcpy2D(dst, (size_t)w * esz, (const char*)src + (size_t)pair * pstride, pitch, (size_t)w * esz, h, hipMemcpyDeviceToHost));
@@ -1083,6 +1273,17 @@ extern "C" int eppm_probe_pm_parity(const eppm_ctx* c, int* pitch, int* pad, int
     *pitch = c->pp1 ? c->pp_pitch : 0;
     *pad = c->pp1 ? c->pp_pad : 0;
     *kernels = c->pp1 ? pm_parity_kernels(c->prm.patch_r) : 0;
+    return EPPM_OK;
+}
+// the per-block XORWOW states of a context's PatchMatch generator where its last run left them (as eppm_pm_rng_block_states)
+extern "C" int eppm_probe_ctx_rng_states(eppm_ctx* c, uint32_t* dst, size_t dst_words)
+{
+    if (!c || !dst) return set_err(EPPM_ERR_ARG, "eppm_probe_ctx_rng_states: NULL argument");
+    const int nb = c->rng->gx * c->rng->gy;
+    if (dst_words < (size_t)nb * 6) return set_err(EPPM_ERR_ARG, "eppm_probe_ctx_rng_states: dst too small");
+    HIPCHK(hipSetDevice(c->device));
+    HIPCHK(hipStreamSynchronize(c->stream));
+    HIPCHK(hipMemcpy2D(dst, 24, c->rng->work[0][c->rng->cur[0]], 64 * 24, 24, nb, hipMemcpyDeviceToHost));
     return EPPM_OK;
 }
 #endif

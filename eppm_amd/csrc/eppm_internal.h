@@ -152,6 +152,36 @@ void launch_pm_neighbor(const PmBatch& b, const float* lut, int R, hipStream_t s
 void launch_pm_random_search(const PmBatch& b, const PmRngDev& rng, const float* lut, int R, int search_range, int num_guess,
                              hipStream_t s);
 
+// The seeded start of a streaming context's PatchMatch, after launch_pm_init_field + launch_pm_cost_field on the same
+// batch (one pair): the cost of every pixel's temporal prior (an absolute target like an NNF entry; a component <= kInvalid: none), and
+// the prior kept where it exists and its cost is STRICTLY lower than the random match's -- the cost-field kernel with a compare in front of
+// its store.  Writes nnf and cost, and copies of both into nnf_init / cost_init (unpitched; what eppm_get_plane shows); the evaluation
+// cache, the work lists and the generator states stay as launch_pm_init_field left them.
+struct PmSeed {
+    const int16_t* prior[2];     // short2 per pixel of problem k, unpitched
+    int16_t* nnf_init[2];
+    float* cost_init[2];
+};
+void launch_pm_cost_select(const PmBatch& b, const PmSeed& seed, const float* lut, int R, hipStream_t s);
+
+// ---- temporal prior (k_temporal.hip; the rule itself: temporal.h) ----
+// Up to two directions per launch: prev[d] a displacement snapshot, prior[d] the advected targets, keys[d] w*h ints that hold
+// kTemporalNoKey between launches (launch_temporal_keys_init once; the gather pass restores them), step[d] +1 forward / -1 backward.
+struct TemporalArgs {
+    const int16_t* prev[2];
+    int16_t* prior[2];
+    int32_t* keys[2];
+    int step[2];
+    int w, h, ndir;
+};
+void launch_temporal_keys_init(int32_t* keys, int n, hipStream_t s);
+void launch_temporal_splat(const TemporalArgs& a, hipStream_t s);
+void launch_temporal_gather(const TemporalArgs& a, hipStream_t s);
+// prev <- the displacements of a field of stored matches (nnf_pitch in short2 elements)
+void launch_temporal_snapshot(int16_t* prev, const int16_t* nnf, int nnf_pitch, int w, int h, hipStream_t s);
+// launch_nnf2flow of one pair and the snapshot of the same field in one launch
+void launch_nnf2flow_snapshot(float* flow, int flow_pitch, int16_t* prev, const int16_t* nnf, int nnf_pitch, int w, int h, hipStream_t s);
+
 // ---- level-2 post-processing (k_post.hip) ----
 void launch_lr_check(int16_t* nnf1, float* cost1, const int16_t* nnf2, int w, int h, int cost_pitch, int nnf_pitch, hipStream_t s, Batch bt = kOnePair);
 void launch_outlier(int16_t* nnf_out, float* cost, const int16_t* nnf_in, int w, int h, int cost_pitch, int nnf_pitch, hipStream_t s, Batch bt = kOnePair);

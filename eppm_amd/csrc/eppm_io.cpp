@@ -12,6 +12,7 @@
 #include "../../include/eppm.h"
 #include "fb_occlusion.h"
 #include "interp.h"
+#include "temporal.h"
 
 static int read_ppm_header(FILE* f, int* type, int* w, int* h)
 {
@@ -252,6 +253,30 @@ extern "C" int eppm_fb_occlusion_host(uint8_t* occ, const float* u, const float*
         for (int x = 0; x < w; x++) {
             const size_t i = (size_t)y * w + x;
             occ[i] = eppm::fb_occlusion_pixel(x, y, u[i], v[i], G.data(), h, w, alpha, beta);
+        }
+    return EPPM_OK;
+}
+
+// the temporal prior on host planes (temporal.h): the landing competition as a sequential minimum over the source
+// indices, the targets by the kernels' own function.  prev: h*w displacements, prior: h*w absolute targets.
+extern "C" int eppm_temporal_prior_host(eppm_short2* prior, const eppm_short2* prev, int h, int w, int backward)
+{
+    if (!prior || !prev || h < 1 || w < 1 || h > 32767 || w > 32767) return EPPM_ERR_ARG;
+    const size_t n = (size_t)h * w;
+    if (n >= ((size_t)1 << 30)) return EPPM_ERR_ARG;
+    const int step = backward ? -1 : 1;
+    std::vector<int> keys(n, eppm::kTemporalNoKey);
+    for (int y = 0; y < h; y++)
+        for (int x = 0; x < w; x++) {
+            const int i = y * w + x;
+            int qx, qy;
+            if (eppm::temporal_landing(x, y, prev[i].x, prev[i].y, step, w, h, &qx, &qy) && i < keys[(size_t)qy * w + qx]) keys[(size_t)qy * w + qx] = i;
+        }
+    for (int y = 0; y < h; y++)
+        for (int x = 0; x < w; x++) {
+            const int i = y * w + x, k = keys[i];
+            const bool won = k != eppm::kTemporalNoKey;
+            eppm::temporal_target(x, y, won, won ? prev[k].x : 0, won ? prev[k].y : 0, w, h, &prior[i].x, &prior[i].y);
         }
     return EPPM_OK;
 }

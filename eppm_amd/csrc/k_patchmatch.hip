@@ -243,6 +243,20 @@ EPPM_PM_UNROLL((TU))
     return sum.result();
 }
 
+// the source samples of the workgroup's 16x16 block, clamped at load, for the cost-field kernels (k_pm_cost_field_tile and the seeded
+// start's k_pm_cost_select_tile evaluate from the same tile)
+template <int RT>
+__device__ __forceinline__ void pm_stage_cost_tile(float4* __restrict__ s_src, const Planes& P, int tid)
+{
+    constexpr int TW = kBlock + 2 * RT;
+    const int x0 = blockIdx.x * kBlock - RT, y0 = blockIdx.y * kBlock - RT;
+    for (int t = tid; t < TW * TW; t += 256) {
+        const int sy = iclamp(y0 + t / TW, 0, P.h - 1), sx = iclamp(x0 + t % TW, 0, P.w - 1);
+        s_src[t] = P.pk1[(unsigned)(sy * P.pitch + sx)];
+    }
+    __syncthreads();
+}
+
 // the cost field with the source samples of the 16x16 block from an LDS tile, as in the search and in phase A of the sweeps (radius 9 / 17)
 template <int RT, int PK = 0>
 __global__ __launch_bounds__(256) void k_pm_cost_field_tile(PmBatch B, const float* __restrict__ lut, int R)
@@ -255,12 +269,7 @@ __global__ __launch_bounds__(256) void k_pm_cost_field_tile(PmBatch B, const flo
     load_patch_lut(L, lut, R, tid, 256);
     const PmProblem pr = pm_problem(B, blockIdx.z);
     const Planes P = to_dev(pr.P);
-    const int x0 = blockIdx.x * kBlock - RT, y0 = blockIdx.y * kBlock - RT;
-    for (int t = tid; t < TW * TW; t += 256) {
-        const int sy = iclamp(y0 + t / TW, 0, P.h - 1), sx = iclamp(x0 + t % TW, 0, P.w - 1);
-        s_src[t] = P.pk1[(unsigned)(sy * P.pitch + sx)];
-    }
-    __syncthreads();
+    pm_stage_cost_tile<RT>(s_src, P, tid);
     const int x = blockIdx.x * kBlock + threadIdx.x, y = blockIdx.y * kBlock + threadIdx.y;
     if (x >= P.w || y >= P.h) return;
     const int dx = pr.nnf[(y * B.npitch + x) * 2], dy = pr.nnf[(y * B.npitch + x) * 2 + 1];
@@ -296,18 +305,97 @@ int pm_parity_kernels(int R)
     return (pm_parity_adopted(R, EPPM_PARITY_SEARCH) ? 1 : 0) | (pm_parity_adopted(R, EPPM_PARITY_SPEC) ? 2 : 0) | (pm_parity_adopted(R, EPPM_PARITY_COST) ? 4 : 0);
 }
 
+// which cost-field kernel a launch takes (the plain field and the seeded start's select pick by ONE rule, so that a prior's cost is the
+// cost the field would give the same match): 0 any radius, 1 / 2 the LDS tile at radius 9 / 17, 3 / 4 the same reading the parity planes
+#ifndef EPPM_COST_FIELD_TILE
+#define EPPM_COST_FIELD_TILE 1
+#endif
+static int pm_cost_kernel(const PmBatch& b, int R)
+{
+    if (!EPPM_COST_FIELD_TILE || (R != 9 && R != 17)) return 0;
+    return (R == 9 ? 1 : 2) + (pm_has_parity(b, R, EPPM_PARITY_COST) ? 2 : 0);
+}
+
 void launch_pm_cost_field(const PmBatch& b, const float* lut, int R, hipStream_t s)
 {
     const int w = b.p[0].P.w, h = b.p[0].P.h;
     dim3 grid((w + kBlock - 1) / kBlock, (h + kBlock - 1) / kBlock, b.n * b.npairs), block(kBlock, kBlock);
-#ifndef EPPM_COST_FIELD_TILE
-#define EPPM_COST_FIELD_TILE 1
-#endif
-    if (EPPM_COST_FIELD_TILE && R == 9 && pm_has_parity(b, R, EPPM_PARITY_COST)) hipLaunchKernelGGL((k_pm_cost_field_tile<9, 2>), grid, block, 0, s, b, lut, R);
-    else if (EPPM_COST_FIELD_TILE && R == 17 && pm_has_parity(b, R, EPPM_PARITY_COST)) hipLaunchKernelGGL((k_pm_cost_field_tile<17, 2>), grid, block, 0, s, b, lut, R);
-    else if (EPPM_COST_FIELD_TILE && R == 9) hipLaunchKernelGGL(k_pm_cost_field_tile<9>, grid, block, 0, s, b, lut, R);
-    else if (EPPM_COST_FIELD_TILE && R == 17) hipLaunchKernelGGL(k_pm_cost_field_tile<17>, grid, block, 0, s, b, lut, R);
-    else hipLaunchKernelGGL(k_pm_cost_field, grid, block, 0, s, b, lut, R);
+    switch (pm_cost_kernel(b, R)) {
+    case 3: hipLaunchKernelGGL((k_pm_cost_field_tile<9, 2>), grid, block, 0, s, b, lut, R); break;
+    case 4: hipLaunchKernelGGL((k_pm_cost_field_tile<17, 2>), grid, block, 0, s, b, lut, R); break;
+    case 1: hipLaunchKernelGGL(k_pm_cost_field_tile<9>, grid, block, 0, s, b, lut, R); break;
+    case 2: hipLaunchKernelGGL(k_pm_cost_field_tile<17>, grid, block, 0, s, b, lut, R); break;
+    default: hipLaunchKernelGGL(k_pm_cost_field, grid, block, 0, s, b, lut, R);
+    }
+}
+
+// The seeded start (eppm_internal.h: PmSeed): the cost-field kernels above, evaluating the temporal prior instead of the stored match and
+// keeping it where it is strictly cheaper.  Same evaluation function per radius and library as launch_pm_cost_field picks, so a prior's cost
+// is bit for bit what the cost field would give that match.  A pixel without a prior skips its evaluation.
+__device__ __forceinline__ void pm_select_store(const PmProblem& pr, const PmBatch& B, const PmSeed& S, int k, int w, int x, int y, bool has,
+                                                int px, int py, float pc)
+{
+    const int ni = (y * B.npitch + x) * 2, ci = y * B.cpitch + x;
+    int nx = pr.nnf[ni], ny = pr.nnf[ni + 1];
+    float c = pr.cost[ci];
+    if (has && pc < c) {
+        nx = px; ny = py; c = pc;
+        pr.nnf[ni] = (int16_t)nx; pr.nnf[ni + 1] = (int16_t)ny;
+        pr.cost[ci] = c;
+    }
+    S.nnf_init[k][(y * w + x) * 2] = (int16_t)nx;
+    S.nnf_init[k][(y * w + x) * 2 + 1] = (int16_t)ny;
+    S.cost_init[k][y * w + x] = c;
+}
+
+__global__ __launch_bounds__(256) void k_pm_cost_select(PmBatch B, PmSeed S, const float* __restrict__ lut, int R)
+{
+    __shared__ EPPM_LUT_ALIGN PatchLut L;
+    load_patch_lut(L, lut, R, threadIdx.y * kBlock + threadIdx.x, 256);
+    __syncthreads();
+    const int k = blockIdx.z;
+    const PmProblem pr = pm_problem(B, blockIdx.z);
+    const Planes P = to_dev(pr.P);
+    const int x = blockIdx.x * kBlock + threadIdx.x, y = blockIdx.y * kBlock + threadIdx.y;
+    if (x >= P.w || y >= P.h) return;
+    const int px = S.prior[k][(y * P.w + x) * 2], py = S.prior[k][(y * P.w + x) * 2 + 1];
+    const bool has = px > kInvalid && py > kInvalid;
+    const float pc = has ? patch_dist(P, L, R, x, y, px, py) : 0.0f;
+    pm_select_store(pr, B, S, k, P.w, x, y, has, px, py, pc);
+}
+
+template <int RT, int PK = 0>
+__global__ __launch_bounds__(256) void k_pm_cost_select_tile(PmBatch B, PmSeed S, const float* __restrict__ lut, int R)
+{
+    using LUT = typename SearchLut<RT>::type;
+    constexpr int TW = kBlock + 2 * RT;
+    __shared__ float4 s_src[TW * TW];
+    __shared__ EPPM_LUT_ALIGN LUT L;
+    const int tid = threadIdx.y * kBlock + threadIdx.x;
+    load_patch_lut(L, lut, R, tid, 256);
+    const int k = blockIdx.z;                   // one pair: problem k of the launch is direction k
+    const PmProblem pr = pm_problem(B, blockIdx.z);
+    const Planes P = to_dev(pr.P);
+    pm_stage_cost_tile<RT>(s_src, P, tid);
+    const int x = blockIdx.x * kBlock + threadIdx.x, y = blockIdx.y * kBlock + threadIdx.y;
+    if (x >= P.w || y >= P.h) return;
+    const int px = S.prior[k][(y * P.w + x) * 2], py = S.prior[k][(y * P.w + x) * 2 + 1];
+    const bool has = px > kInvalid && py > kInvalid;
+    const float pc = has ? search_patch_dist<RT, PK>(P, L, R, s_src, TW, threadIdx.x, threadIdx.y, x, y, px, py, pr.P) : 0.0f;
+    pm_select_store(pr, B, S, k, P.w, x, y, has, px, py, pc);
+}
+
+void launch_pm_cost_select(const PmBatch& b, const PmSeed& seed, const float* lut, int R, hipStream_t s)
+{
+    const int w = b.p[0].P.w, h = b.p[0].P.h;
+    dim3 grid((w + kBlock - 1) / kBlock, (h + kBlock - 1) / kBlock, b.n), block(kBlock, kBlock);      // one pair: a batch has no previous pair
+    switch (pm_cost_kernel(b, R)) {
+    case 3: hipLaunchKernelGGL((k_pm_cost_select_tile<9, 2>), grid, block, 0, s, b, seed, lut, R); break;
+    case 4: hipLaunchKernelGGL((k_pm_cost_select_tile<17, 2>), grid, block, 0, s, b, seed, lut, R); break;
+    case 1: hipLaunchKernelGGL(k_pm_cost_select_tile<9>, grid, block, 0, s, b, seed, lut, R); break;
+    case 2: hipLaunchKernelGGL(k_pm_cost_select_tile<17>, grid, block, 0, s, b, seed, lut, R); break;
+    default: hipLaunchKernelGGL(k_pm_cost_select, grid, block, 0, s, b, seed, lut, R);
+    }
 }
 
 // ---------------------------------------------------------------------------------------------------

@@ -443,6 +443,22 @@ extern "C" int eppm_fb_occlusion(uint8_t* d_occ, const eppm_float2* d_flow, cons
     launch_fb_occlusion(d_occ, nullptr, (const float*)d_flow, 0, (const float*)d_other, 0, h, w, alpha, beta, 1, 1, g_stream);
     return finish();
 }
+// ---- the temporal prior on caller planes (k_temporal.hip; eppm_temporal_prior_host is its host form): one direction ----
+extern "C" int eppm_temporal_prior(eppm_short2* d_prior, const eppm_short2* d_prev, int h, int w, int backward)
+{
+    if (!d_prior || !d_prev || h < 1 || w < 1 || h > 32767 || w > 32767) return set_err(EPPM_ERR_ARG, "eppm_temporal_prior: bad argument");
+    if ((unsigned long long)h * (unsigned long long)w >= (1ULL << 30)) return set_err(EPPM_ERR_ARG, "eppm_temporal_prior: size %dx%d out of range", w, h);
+    LAUNCHER_BEGIN_INT;
+    void* keys = nullptr;
+    CHK(get_scratch(ds, (size_t)w * h * 4, &keys, 6));
+    TemporalArgs a{};
+    a.prev[0] = (const int16_t*)d_prev; a.prior[0] = (int16_t*)d_prior; a.keys[0] = (int32_t*)keys; a.step[0] = backward ? -1 : 1;
+    a.w = w; a.h = h; a.ndir = 1;
+    launch_temporal_keys_init(a.keys[0], w * h, g_stream);
+    launch_temporal_splat(a, g_stream);
+    launch_temporal_gather(a, g_stream);
+    return finish();
+}
 // ---- frame interpolation on caller planes (k_interp.hip; eppm_interpolate_host is its host form): one pair, one time ----
 extern "C" int eppm_interpolate_frames(void* d_rgba_out, size_t out_pitch, const void* d_rgba1, const void* d_rgba2, size_t in_pitch,
                                        const eppm_float2* d_flow, const uint8_t* d_occ1, const uint8_t* d_occ2, int h, int w, float t)

@@ -93,9 +93,18 @@ void neighbor(PmBatch& b, const float* lut, const eppm_params& prm, int launches
 // returns with the NNF of problem k in b.p[k].nnf (an even number of sweeps: the caller's buffer)
 void run_patchmatch(PmBatch& b, eppm_pm_rng* rng, const float* lut, const eppm_params& prm, hipStream_t s, int spec_mode)
 {
+    pm_start(b, rng, lut, prm, s);
+    pm_iterate(b, rng, lut, prm, s, spec_mode);
+}
+// the random field and its costs; a streaming context puts its seeded start (launch_pm_cost_select) between this and the iterations
+void pm_start(PmBatch& b, eppm_pm_rng* rng, const float* lut, const eppm_params& prm, hipStream_t s)
+{
     b.sweep_seq = 0;
     launch_pm_init_field(b, rng->dev(), s);
     launch_pm_cost_field(b, lut, prm.patch_r, s);
+}
+void pm_iterate(PmBatch& b, eppm_pm_rng* rng, const float* lut, const eppm_params& prm, hipStream_t s, int spec_mode)
+{
     for (int it = 0; it < prm.num_iter; it++) {
         if (prm.propagation == 1) jump(b, lut, prm, s);
         else if (prm.propagation == 2) neighbor(b, lut, prm, 10, s);

@@ -93,6 +93,18 @@ def fb_occlusion(u, v, bu, bv, alpha=0.01, beta=0.5):
     return occ
 
 
+def temporal_prior(prev, backward=False):
+    """(h, w) short2 prior of a streaming context's next pair from a displacement snapshot of the previous one (eppm_temporal_prior_host,
+    DESIGN.md section 13): prev holds displacements (a component <= -10000: unknown), the result absolute targets ((-10000, -10000): no prior)."""
+    from .api import short2
+    prev = np.ascontiguousarray(prev, short2)
+    h, w = prev.shape
+    out = np.empty((h, w), short2)
+    check(lib().eppm_temporal_prior_host(out.ctypes.data_as(C.c_void_p), prev.ctypes.data_as(C.c_void_p), h, w, int(bool(backward))),
+          "eppm_temporal_prior_host")
+    return out
+
+
 def interpolate(img1, img2, u, v, occ1, occ2, t):
     """(h, w, 3) uint8 frame at time t between img1 (t = 0) and img2 (t = 1) from the forward flow (u, v) and the occlusion masks of
     both images (eppm_interpolate_host; byte-identical to the kernels)."""

@@ -299,6 +299,15 @@ def flow_smoothing(flow, img):
     return f.get()
 
 
+def temporal_prior(prev, backward=False):
+    """eppm_temporal_prior (the advection kernels of a streaming context) on a numpy displacement field."""
+    d_prev = Dev(np.ascontiguousarray(prev, short2))
+    d_out = Dev(shape=prev.shape, dtype=short2)
+    check(lib().eppm_temporal_prior(d_out.ptr, d_prev.ptr, d_prev.h, d_prev.w, int(bool(backward))), "eppm_temporal_prior")
+    check(lib().eppm_device_synchronize(), "eppm_device_synchronize")
+    return d_out.get()
+
+
 def flow_to_color(flow, max_disp_x=20.0, max_disp_y=20.0):
     """bao_cuda_convert_flow_to_colorshow (float2 form, basic/bao_basic_cuda.cuh:839-845): (h,w) float2 -> (h,w) uchar4 {R,G,B,0}."""
     h, w = flow.shape

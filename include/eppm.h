@@ -152,7 +152,10 @@ int  eppm_level_dims(const eppm_ctx* ctx, int level, int* h, int* w);
  *  "flow" (float2).  Valid after the stage that produces it has run.
  *  After a bidirectional call (below) also: "flow_bwd" (float2, every level: the backward flow as that level left it), "occ1", "occ2"
  *  (u8, level 0: the occlusion masks), and "nnf2" at the PatchMatch level is the backward NNF after hole filling.  A later
- *  forward-only compute invalidates "flow_bwd", "occ1" and "occ2" (EPPM_ERR_STATE). */
+ *  forward-only compute invalidates "flow_bwd", "occ1" and "occ2" (EPPM_ERR_STATE).
+ *  After a compute that started from a temporal prior (below; EPPM_ERR_STATE otherwise), at the PatchMatch level: "prior1", "prior2" (short2:
+ *  the advected targets of the forward / backward problem), "nnf_init1", "nnf_init2" (short2) and "cost_init1", "cost_init2" (f32): the
+ *  field and its costs as the iterations found them. */
 int  eppm_get_plane(eppm_ctx* ctx, const char* name, int level, void* dst, size_t dst_bytes);
 
 /* ----------------------------------------------------------------------------------------
@@ -264,6 +267,34 @@ int  eppm_track_step_host(const eppm_track_params* p, const uint8_t* rgb1, const
 /* the seeds of the textured cells of a packed RGB image in cell order: *n of them, the first min(*n, max) written to xy */
 int  eppm_track_seeds_host(const eppm_track_params* p, const uint8_t* rgb, int h, int w, int max, float* xy, int* n);
 
+/* ----------------------------------------------------------------------------------------
+ * streaming video: one single-pair context walks a clip.  Opt-in: a context that never calls these allocates and
+ * launches exactly what it did without them.
+ *  frame push: image 2 becomes image 1 and the new frame becomes image 2.  The raw frame, the pyramid, the census and the texel planes of
+ *    the old image 2 are kept (the context exchanges its plane pointers); only the new frame is uploaded and prepared.  After
+ *    eppm_set_images(A, B), eppm_push_image(C) every plane and every flow equals those after eppm_set_images(B, C), bit for bit.
+ *    EPPM_ERR_STATE before the first eppm_set_images*; EPPM_ERR_ARG on a batch context (its pairs run concurrently: there is no previous pair).
+ *  temporal mode: every compute keeps two level-L displacement fields (L = the PatchMatch level; an allocation of its own, made by the first
+ *    compute with the mode on): the forward field that is converted to the level's flow, and the raw backward NNF.  The next compute moves
+ *    each along its own motion (a pixel with displacement d lands on p + d -- p - d for the backward field -- and keeps d; of several
+ *    sources the smallest index wins) and starts PatchMatch from that prior wherever its cost is strictly lower than the random match's;
+ *    the random field, the random search's numbers and the iterations are those of a cold run.  The prior is armed by eppm_push_image*
+ *    directly after a compute: a second compute on the same pair, or a compute after two pushes in a row, is a cold run.  eppm_set_images*
+ *    drops the fields (a new pair is a new clip), eppm_temporal_reset drops them by hand; a cold run is bit for bit eppm_compute's.  Works with eppm_compute*, eppm_compute_bidirectional* and therefore eppm_track_step.  EPPM_ERR_ARG on a batch
+ *    context.
+ * -------------------------------------------------------------------------------------- */
+int  eppm_push_image(eppm_ctx* ctx, const uint8_t* rgb, size_t row_stride);
+/* device-resident RGBA frame, as eppm_set_images_device's */
+int  eppm_push_image_device(eppm_ctx* ctx, const void* d_rgba, size_t pitch);
+int  eppm_set_temporal(eppm_ctx* ctx, int on);      /* off (default) also drops the fields */
+int  eppm_temporal_reset(eppm_ctx* ctx);            /* the next compute is cold */
+int  eppm_temporal_valid(const eppm_ctx* ctx);      /* 1: the next compute will start from a prior; 0 otherwise */
+/* The advection rule on host memory (no GPU needed).  prev: h*w displacements (a component <= -10000: unknown vector); prior: h*w absolute
+ * targets as an NNF holds them, (-10000, -10000) where a pixel has no prior; backward != 0: the step's sign is flipped (q = p - d). */
+int  eppm_temporal_prior_host(eppm_short2* prior, const eppm_short2* prev, int h, int w, int backward);
+/* the kernels alone on unpitched device planes; on the launcher stream, like eppm_fb_occlusion */
+int  eppm_temporal_prior(eppm_short2* d_prior, const eppm_short2* d_prev, int h, int w, int backward);
+
 /* Per-stage device times in ms (hipEvent pairs on the context's stream), one entry per stage per
  * call since the last eppm_clear_stage_times (names repeat across calls; prepare entries first).
  * names[i] points to static strings.  Returns the number of entries written (<= max). */
@@ -273,7 +304,8 @@ int  eppm_clear_stage_times(eppm_ctx* ctx);
  * refine, entries "c2f_refine_L<l>").  A bidirectional call adds (mode 1) "l2_post_bwd", "upsample_bwd_L<l>", "c2f_refine_bwd_L<l>",
  * "flow_blf_bwd_L<l>", "flow_blf_bwd_final" and "fb_occlusion"; an interpolation call "interp_splat", "interp_fill" and "interp_blend"
  * (mode 1, once per group of four times); a track step "track_advance", "track_seed" and "track_compact" (mode 1; the step that seeds
- * frame 0 adds a "track_seed" before "track_advance").  Events come from a per-context pool: none is created in a steady-state step. */
+ * frame 0 adds a "track_seed" before "track_advance"); a compute that starts from a temporal prior "temporal_advect" (before "patchmatch") and
+ * "temporal_select" (inside it: "patchmatch" includes its time).  Events come from a per-context pool: none is created in a steady-state step. */
 int  eppm_enable_stage_timing(eppm_ctx* ctx, int on);
 
 const char* eppm_last_error(void);

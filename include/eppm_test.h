@@ -43,6 +43,9 @@ int  eppm_probe_unpack_texel(const uint32_t* w, float* y, int n);
 /* the column-parity planes of a context's PatchMatch level: words per row of one parity plane and padding columns (0, 0: none), and
  * which kernels read them (bit 0 random search, bit 1 phase A of the sweeps, bit 2 cost field; 0 without planes) */
 int  eppm_probe_pm_parity(const eppm_ctx* ctx, int* pitch, int* pad, int* kernels);
+/* the per-block XORWOW states of a context's PatchMatch generator where its last run left them: 6 x uint32 per 16x16 block of the
+ * PatchMatch level, as eppm_pm_rng_block_states (a seeded run of a streaming context must leave what a cold run leaves) */
+int  eppm_probe_ctx_rng_states(eppm_ctx* ctx, uint32_t* dst, size_t dst_words);
 
 #ifdef __cplusplus
 }

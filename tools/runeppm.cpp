@@ -21,6 +21,14 @@
 //   --occlusion f.pgm ... and image 1's occlusion mask as a P5 PGM: 0 consistent, 255 inconsistent, 128 leaves the frame, 64 unknown
 //   --interpolate T f.ppm  (repeatable) implies the bidirectional call; after the timed window, write the frame at time T in [0, 1]
 //                     between image 1 and image 2 (interpolate_frame) as a P6 PPM
+//
+//   runeppm [options] --sequence f0.ppm f1.ppm f2.ppm ... --out-prefix P [--temporal 0|1]
+//
+//                     a clip through ONE context: the first pair by eppm_set_images, every later frame by
+//                     eppm_push_image; the flow of frames k-1 -> k is written to P_<k as four digits>.flo (P_0001.flo ...).
+//                     --temporal 1 (default): every pair after the first starts PatchMatch from the previous pair's result moved
+//                     along its motion; 0: every pair is a cold run (bit for bit the two-image form's flow).  Of the options above
+//                     --seed, --levels, --patch-r, --iters and --propagation apply.
 #include <atomic>
 #include <chrono>
 #include <cstdio>
@@ -52,6 +60,9 @@ struct Options {
     int sw = 0, sh = 0, pairs = 1, gpus = 1, batch = 1;
     std::vector<std::pair<std::string, long long>> opts;
     std::vector<std::pair<float, const char*>> interp;     // --interpolate T file.ppm
+    std::vector<const char*> seq;                           // --sequence frames
+    const char* prefix = nullptr;                           // --out-prefix
+    int temporal = 1;                                       // --temporal
 };
 
 static unsigned hash32(unsigned x)
@@ -100,8 +111,56 @@ static int usage()
 {
     fprintf(stderr, "usage: runeppm [--size WxH] [--seed N] [--levels N] [--patch-r N] [--iters N] [--propagation M]\n"
                     "               [--pin] [--pairs P] [--gpus G] [--batch B] [--gt file.flo] [--out file.flo] [--backward file.flo]\n"
-                    "               [--occlusion file.pgm] [--interpolate T file.ppm]... [img1.ppm img2.ppm [out.flo]]\n");
+                    "               [--occlusion file.pgm] [--interpolate T file.ppm]... [img1.ppm img2.ppm [out.flo]]\n"
+                    "       runeppm [--seed N] [--levels N] [--patch-r N] [--iters N] [--propagation M]\n"
+                    "               --sequence f0.ppm f1.ppm [f2.ppm ...] --out-prefix P [--temporal 0|1]\n");
     return 2;
+}
+
+// --sequence: the clip through one context of the C ABI (frame push, temporal mode)
+static int run_sequence(const Options& o)
+{
+    eppm_params prm;
+    eppm_default_params(&prm);
+    for (auto& kv : o.opts) {
+        if (kv.first == "seed") prm.seed = (unsigned long long)kv.second;
+        else if (kv.first == "levels") prm.levels = (int)kv.second;
+        else if (kv.first == "patch_r") prm.patch_r = (int)kv.second;
+        else if (kv.first == "num_iter") prm.num_iter = (int)kv.second;
+        else if (kv.first == "propagation") prm.propagation = (int)kv.second;
+    }
+    int h = 0, w = 0, nch = 3;
+    if (eppm_ppm_size(o.seq[0], &h, &w) != EPPM_OK) { fprintf(stderr, "cannot read %s\n", o.seq[0]); return 1; }
+    std::vector<std::vector<unsigned char>> img(2, std::vector<unsigned char>((size_t)h * w * 3));
+    std::vector<float> u((size_t)h * w), v((size_t)h * w);
+    eppm_ctx* ctx = nullptr;
+    auto fail = [&](const char* what) { fprintf(stderr, "%s: %s\n", what, eppm_last_error()); if (ctx) eppm_destroy(ctx); return 1; };
+    if (eppm_create(&ctx, h, w, 0, &prm) != EPPM_OK) return fail("eppm_create");
+    if (eppm_set_temporal(ctx, o.temporal) != EPPM_OK) return fail("eppm_set_temporal");
+    double total = 0;
+    for (size_t k = 0; k < o.seq.size(); k++) {
+        int hk = 0, wk = 0;
+        std::vector<unsigned char>& cur = img[k == 0 ? 0 : 1];
+        if (eppm_ppm_size(o.seq[k], &hk, &wk) != EPPM_OK || hk != h || wk != w || eppm_load_ppm(o.seq[k], cur.data(), h, w, &nch) != EPPM_OK) {
+            fprintf(stderr, "cannot read %s (or its size differs from the first frame's)\n", o.seq[k]);
+            eppm_destroy(ctx);
+            return 1;
+        }
+        if (k == 0) continue;
+        const auto t0 = std::chrono::steady_clock::now();
+        if (k == 1) { if (eppm_set_images(ctx, img[0].data(), img[1].data(), (size_t)w * 3) != EPPM_OK) return fail("eppm_set_images"); }
+        else if (eppm_push_image(ctx, cur.data(), (size_t)w * 3) != EPPM_OK) return fail("eppm_push_image");
+        if (eppm_compute(ctx, u.data(), v.data()) != EPPM_OK) return fail("eppm_compute");
+        const double ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
+        total += ms;
+        char name[4096];
+        snprintf(name, sizeof name, "%s_%04zu.flo", o.prefix, k);
+        if (eppm_save_flo(name, u.data(), v.data(), h, w) != EPPM_OK) { fprintf(stderr, "cannot write %s\n", name); eppm_destroy(ctx); return 1; }
+        printf("pair %zu: %.3f ms%s -> %s\n", k, ms, (o.temporal && k > 1) ? " (seeded)" : "", name);
+    }
+    printf("%zu pairs, %.3f ms per pair\n", o.seq.size() - 1, total / (double)(o.seq.size() - 1));
+    eppm_destroy(ctx);
+    return 0;
 }
 
 int main(int argc, char** argv)
@@ -134,8 +193,21 @@ int main(int argc, char** argv)
             if (!end || *end || !(t >= 0.0f && t <= 1.0f)) return usage();
             o.interp.push_back({t, argv[++i]});
         }
+        else if (!strcmp(a, "--sequence")) { while (i + 1 < argc && !(argv[i + 1][0] == '-' && argv[i + 1][1] == '-')) o.seq.push_back(argv[++i]); if (o.seq.empty()) return usage(); }
+        else if (!strcmp(a, "--out-prefix")) { if (i + 1 >= argc) return usage(); o.prefix = argv[++i]; }
+        else if (!strcmp(a, "--temporal")) { if (!val(&v) || (v != 0 && v != 1)) return usage(); o.temporal = (int)v; }
         else if (a[0] == '-' && a[1] == '-') return usage();
         else pos.push_back(a);
+    }
+    if (!o.seq.empty() || o.prefix) {
+        if (o.seq.size() < 2 || !o.prefix || !pos.empty()) return usage();
+        // the options of the two-image form that a clip has no meaning for are refused, not ignored
+        const Options d;
+        bool pin = false;
+        for (auto& kv : o.opts) pin = pin || kv.first == "pin_caller_buffers";
+        if (pin || o.sw || o.pairs != d.pairs || o.gpus != d.gpus || o.batch != d.batch || o.gt || o.fo != d.fo || o.fb || o.focc || !o.interp.empty())
+            return usage();
+        return run_sequence(o);
     }
     if (pos.size() == 1 || pos.size() > 3) return usage();
     if (pos.size() >= 2) { o.f1 = pos[0]; o.f2 = pos[1]; }
