@@ -58,7 +58,7 @@ SYMBOLS = [
 ]
 
 
-# what include/eppm_test.h adds, exported by libeppm_hip_test.so only (the parity tests' switches and arithmetic probes)
+# what include/eppm_test.h adds, exported by libeppm_hip_test.so and libeppm_hip_tol_test.so only (the parity tests' switches and arithmetic probes)
 TEST_SYMBOLS = ["eppm_test_set_option", "eppm_probe_c2f_window", "eppm_probe_fast_exp", "eppm_probe_div_const", "eppm_probe_delta_table",
                 "eppm_probe_unpack_texel", "eppm_probe_pm_parity", "eppm_probe_ctx_rng_states"]
 
@@ -68,7 +68,9 @@ _variant = None
 def select_library(variant):
     """Which build this PROCESS loads: "" the product library (default), "test" libeppm_hip_test.so (the same objects plus the test
     hooks of include/eppm_test.h: tests/conftest.py selects it for the pytest process; child processes -- bench.py, the CLI, smoke() --
-    are not affected), "tol" the tolerance library (libeppm_hip_tol.so, not bit-identical).  Must be called before the first lib()."""
+    are not affected), "tol" the tolerance library (libeppm_hip_tol.so, not bit-identical), "tol_test" the tolerance library's objects plus
+    the same test hooks (libeppm_hip_tol_test.so: what the children of tests/test_tolerance_stages_gpu.py load; the probes of formulas the
+    tolerance patch term does not have return EPPM_ERR_ARG there).  Must be called before the first lib()."""
     global _variant
     if _lib is not None and variant != _variant:
         raise EppmError("select_library: a library is loaded already")

@@ -9,16 +9,18 @@ _CSRC = os.path.join(_HERE, "csrc")
 def lib_path(variant=None):
     """The product library (bit-identical to the oracle); variant="test": the parity tests' library (libeppm_hip_test.so: the same objects +
     include/eppm_test.h); variant="tol": the tolerance library (libeppm_hip_tol.so: integer-domain tables in the patch term, NOT
-    bit-identical, inside 1e-3 px EPE on the bundled pair; never the default).  variant=None reads EPPM_HIP_VARIANT from the environment."""
+    bit-identical, inside 1e-3 px EPE on the bundled pair; never the default); variant="tol_test": the tolerance library's own objects + the
+    test hooks (libeppm_hip_tol_test.so: the stage parity tests of the tolerance kernels).  variant=None reads EPPM_HIP_VARIANT from the
+    environment."""
     variant = variant if variant is not None else os.environ.get("EPPM_HIP_VARIANT", "")
-    if variant not in ("", "exact", "tol", "test"):
+    if variant not in ("", "exact", "tol", "test", "tol_test"):
         raise ValueError(f"unknown library variant {variant!r}")
-    name = {"tol": "libeppm_hip_tol.so", "test": "libeppm_hip_test.so"}.get(variant, "libeppm_hip.so")
+    name = {"tol": "libeppm_hip_tol.so", "test": "libeppm_hip_test.so", "tol_test": "libeppm_hip_tol_test.so"}.get(variant, "libeppm_hip.so")
     return os.path.join(_HERE, "lib", name)
 
 
 def _stale():
-    outs = [lib_path(""), lib_path("test"), lib_path("tol")]
+    outs = [lib_path(""), lib_path("test"), lib_path("tol"), lib_path("tol_test")]
     if not all(os.path.exists(o) for o in outs):
         return True
     t = min(os.path.getmtime(o) for o in outs)
@@ -30,7 +32,8 @@ def _stale():
 
 def build(force=False, verbose=False):
     """Compile every HIP kernel + the C ABI into eppm_amd/lib/libeppm_hip.so, the parity tests' libeppm_hip_test.so, the tolerance library
-    libeppm_hip_tol.so (the same sources with -DEPPM_TOL; never loaded unless asked for) and the runeppm CLI."""
+    libeppm_hip_tol.so (the same sources with -DEPPM_TOL; never loaded unless asked for), its test build libeppm_hip_tol_test.so and the
+    runeppm CLI."""
     if not force and not _stale():
         return lib_path("")
     if not os.path.exists("/opt/rocm/bin/hipcc"):

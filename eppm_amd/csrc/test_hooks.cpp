@@ -1,5 +1,5 @@
 // test_hooks.cpp -- libeppm_hip_test.so only (include/eppm_test.h): the kernel-variant switches and arithmetic probes of the parity
-// tests.  The product library is linked without this file and exports none of it.
+// tests.  The product libraries are linked without this file and export none of it (with -DEPPM_TOL=1: libeppm_hip_tol_test.so).
 #define EPPM_TEST_HOOKS 1
 #include "api_internal.h"
 

@@ -6,6 +6,10 @@
  * include/eppm.h declares plus the entry points below; the product library exports none of them and has no switch a host
  * program could flip: `nm -D libeppm_hip.so | grep -c "eppm_test\|eppm_probe"` is 0 (tests/test_abi_cpu.py).
  * The parity tests load the test library; bench.py, smoke(), the CLI and the C++ class link the product library.
+ *
+ * libeppm_hip_tol_test.so is the same construction on the tolerance library's objects (-DEPPM_TOL): the stage parity tests of the
+ * tolerance kernels load it in child processes.  Everything below works there -- eppm_probe_c2f_window reports that build's own window
+ * (50 rows) --, except that eppm_probe_delta_table(which = 0) returns EPPM_ERR_ARG: the tolerance patch term has no such table.
  */
 #ifndef EPPM_TEST_H_
 #define EPPM_TEST_H_

@@ -61,6 +61,19 @@ def test_test_hooks_live_in_the_test_library_only():
     readers = {f[:-4] for f in os.listdir(csrc) if f.endswith(".cpp") and f != "test_hooks.cpp" and re.search(r"\bopt_(rand_table|sweep_spec|no_split)\(\)", open(os.path.join(csrc, f)).read())}
     assert readers == {"rng_tables", "context", "launchers_ref_abi"}, readers
     assert eppm_amd.lib()._name == eppm_amd.lib_path("test")                   # what the pytest process itself computes with
+    # the tolerance library has a test build of the same kind (tests/test_tolerance_stages_gpu.py): neither product library exports a hook,
+    # both test libraries export all of them and nothing else on top of their product library, and the new one names its arithmetic
+    tol, tol_test = _exported(eppm_amd.lib_path("tol")), _exported(eppm_amd.lib_path("tol_test"))
+    for product in (prod, tol):
+        assert not (set(product) & set(_lib.TEST_SYMBOLS))
+        assert not [s for s in product if s.startswith("eppm_test") or s.startswith("eppm_probe")]
+    for hooked in (test, tol_test):
+        assert set(_lib.TEST_SYMBOLS) <= set(hooked) and _declared("eppm.h") <= hooked
+    assert {s for s in tol_test - tol if not s.startswith("_")} == hooks
+    assert "OBJS_TT = $(filter-out $(HOOKED:%=$(OBJT)/%.o),$(OBJS_TOL)) $(HOOKED:%=$(OBJT)/%_test.o) $(OBJT)/test_hooks.o $(OBJT)/k_probe.o" in mk
+    T = C.CDLL(eppm_amd.lib_path("tol_test"))
+    T.eppm_version.restype = C.c_char_p
+    assert b"tolerance arithmetic" in T.eppm_version() and b"not bit-identical" in T.eppm_version()
 
 
 def test_host_registry_under_thread_sanitizer(tmp_path):

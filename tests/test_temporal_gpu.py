@@ -456,8 +456,8 @@ print(json.dumps(out))
 def test_tolerance_library_stream_inside_the_envelope(tmp_path):
     """The tolerance library against the exact one on the same streams, with both halves of section 9.4's synthetic-pair envelope: mean
     EPE <= 3e-2 px and <= 1e-3 of the pixels off by more than 1 px; push == set_images holds inside the library bit for bit.  The stage
-    planes (nnf_init*, cost_init*), the oracle chain and the generator-state probe are NOT run for it: the oracle states the exact
-    arithmetic, and the probes live in the test library, of which no -DEPPM_TOL build exists."""
+    planes (nnf_init*, cost_init*), the oracle chain and the generator-state probe are run for it in
+    test_tolerance_stages_gpu.py::test_seeded_context_equals_the_oracle_chain (the tolerance library's test build, the oracle's variant)."""
     res = {}
     for variant in ("", "tol"):
         d = tmp_path / (variant or "exact")
