@@ -1,7 +1,7 @@
 // api_common.cpp -- errors, version, parameters, host-side look-up tables and pyramid geometry of the C ABI (include/eppm.h).
 //
 // The driver behind the ABI follows bao_flow_patchmatch_multiscale_cuda.cpp: init :112-157, set_data :159-168,
-// _prepare_data :212-215, compute_flow :217-306 (context.cpp).  Dead work of the reference is not reproduced: the
+// _prepare_data :212-215, compute_flow :217-306 (context.cpp, ctx_images.cpp, ctx_compute.cpp).  Dead work of the reference is not reproduced: the
 // level-1/0 weighted-median calls on never-initialised planes (driver :281), the debug D2H
 // of the level-2 flow (:265-270) and the per-call RNG cudaMalloc (kernel.cu:1767).
 #include "api_internal.h"

@@ -6,7 +6,11 @@
 //   rng_tables.cpp         XORWOW generator objects and their shared read-only tables
 //   mem_cache.cpp          slabs, pinned staging buffers and streams of destroyed contexts, kept for the next one
 //   pm_driver.cpp          baoCudaPatchMatch's host loop (sweep forms by iteration, search), shared by contexts and stage launchers
-//   context.cpp            eppm_ctx: create / destroy / set_images / compute / planes / stage times (the class's init, set_data, compute_flow)
+//   context.h              eppm_ctx and what its four translation units share; included by them alone
+//   context.cpp            eppm_ctx: create / destroy / planes / stage times (the class's init), the only one of the four that reads opt_*
+//   ctx_images.cpp         set_images, push_image, prepare, the host upload of one image (the class's set_data)
+//   ctx_compute.cpp        compute in all its forms, the post-PatchMatch branch of both directions, temporal mode (the class's compute_flow)
+//   ctx_interp.cpp         frame interpolation, the tracker's view of a context
 //   device_api.cpp         device-memory plumbing of the ABI (malloc / memcpy / NUMA binding)
 //   launchers_ref_abi.cpp  the reference's live extern "C" stage launchers and the sub-stage entry points of the parity tests
 //   test_hooks.cpp         libeppm_hip_test.so only: include/eppm_test.h
@@ -140,7 +144,7 @@ EPPM_HIDDEN void pm_iterate(eppm::PmBatch& b, eppm_pm_rng* rng, const float* lut
 // ---- state of the context-less launchers that test_hooks.cpp and the colour entry points share (launchers_ref_abi.cpp) ----
 EPPM_HIDDEN int launcher_finish();
 
-// ---- what a tracker (tracker.cpp) reads of a context (context.cpp) ----
+// ---- what a tracker (tracker.cpp) reads of a context (ctx_interp.cpp, context.cpp) ----
 // the planes of one pair in the window of eppm_interpolate* (EPPM_ERR_ARG: other dimensions / device, a pair that is not active;
 // EPPM_ERR_STATE: outside the window), and the context's stream; sets the context's device current
 EPPM_HIDDEN int ctx_track_inputs(eppm_ctx* c, int pair, int h, int w, int device, const char* what, eppm::TrackIn* in, hipStream_t* s);

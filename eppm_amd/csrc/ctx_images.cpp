@@ -1,0 +1,239 @@
+// ctx_images.cpp -- the images of a context (context.h): set_images (set_data, driver :159-168, + _prepare_data :212-215) from host and
+// device memory, the frame push of the streaming mode, and the host upload of one image that both share.
+#include "context.h"
+
+using namespace eppm;
+
+// ---- prepare: refine :1060-1071 + .cuh:642-664.  The two frames of every active pair share every launch; the raw
+// RGBA planes of the active pairs are in the slabs already.  only2: image 2 alone (eppm_push_image: image 1's planes are the previous
+// pair's image-2 planes); every kernel is per pixel of one image, so its planes equal those of a launch that covers both images. ----
+static int prepare(eppm_ctx* c, bool only2 = false)
+{
+    stage_begin(c, c->ev_prep, "prepare");
+    hipStream_t s = c->stream;
+    const Batch bt = c->bt();
+    uint32_t **p1 = c->img1, **p2 = c->img2, **tmp = c->tmpu;
+    const int p0 = (int)(c->ipitch[0] / 4);
+    if (only2) launch_gauss_rgba(p2[0], c->raw2, p0, c->H[0], c->W[0], .5f, 2, s, bt);
+    else launch_gauss_rgba2(p1[0], c->raw1, p2[0], c->raw2, p0, c->H[0], c->W[0], .5f, 2, s, bt);    // refine :1063-1064
+    const float ratio = 0.5f;                                                             // PYR_RATIO
+    const float baseSigma = (1 / ratio - 1);
+    const int n = (int)(log(0.25) / (double)logf(ratio));   // C++ float overload in the reference: n = 1
+    const float nSigma = baseSigma * n;
+    for (int i = 1; i < c->nl; i++) {
+        // source level j, blur (sigma, radius), resize ratio r: .cuh:647-663
+        const int j = (i <= n) ? 0 : i - n;
+        const float sigma = (i <= n) ? baseSigma * i : nSigma;
+        const float r = (i <= n) ? (float)pow(ratio, i) : (float)pow(ratio, i) * c->W[0] / c->W[j];
+        const int radius = (int)(sigma * 3);
+        const int pj = (int)(c->ipitch[j] / 4), pi = (int)(c->ipitch[i] / 4);
+        if (gauss_decimate2_ok(c->H[i], c->W[i], c->H[j], c->W[j], r, radius)) {
+            // exact 2:1 step: blur only the pixels the decimation keeps (a quarter of the level)
+            if (only2) launch_gauss_decimate2(p2[i], p2[j], p2[i], p2[j], 1, pi, c->H[i], c->W[i], pj, c->H[j], c->W[j], sigma, radius, s, bt);
+            else launch_gauss_decimate2(p1[i], p1[j], p2[i], p2[j], 2, pi, c->H[i], c->W[i], pj, c->H[j], c->W[j], sigma, radius, s, bt);
+        } else {
+            for (int k = only2 ? 1 : 0; k < 2; k++) {
+                uint32_t** pyr = k ? p2 : p1;
+                launch_gauss_rgba(tmp[j], pyr[j], pj, c->H[j], c->W[j], sigma, radius, s, bt);
+                launch_resize_rgba(pyr[i], pi, c->H[i], c->W[i], tmp[j], pj, c->H[j], c->W[j], r, s, bt);
+            }
+        }
+    }
+    CensusBatch cb;
+    cb.n = 0;
+    for (int k = only2 ? 1 : 0; k < 2; k++)
+        for (int i = 0; i < c->nl; i++) {
+            CensusJob& J = cb.job[cb.n++];
+            J.census = k ? c->cen2[i] : c->cen1[i]; J.cpitch = (int)c->cpitch[i];
+            J.texels = k ? c->pk2[i] : c->pk1[i];   J.tpitch = c->W[i];
+            J.img = k ? c->img2[i] : c->img1[i];    J.ipitch = (int)(c->ipitch[i] / 4);
+            J.w = c->W[i]; J.h = c->H[i]; J.first_block = 0;
+            J.packed = k ? c->pc2[i] : c->pc1[i];
+        }
+    launch_census_batch(cb, s, bt);
+    if (c->pp1) {
+        const int L = c->nl - 1;
+        if (!only2) launch_parity_planes(c->pp1, c->pp_pitch, c->pp_pad, c->pc1[L], c->W[L], c->W[L], c->H[L], s, bt);
+        launch_parity_planes(c->pp2, c->pp_pitch, c->pp_pad, c->pc2[L], c->W[L], c->W[L], c->H[L], s, bt);
+    }
+    stage_end(c, c->ev_prep);
+    HIPCHK(hipGetLastError());
+    c->have_images = true;
+    c->have_flow = false;
+    c->bwd_images = false;
+    return EPPM_OK;
+}
+
+// One host RGB image (rows row_stride bytes apart) -> dst in the slab's d_rgb plane, on the stream.  An image inside memory registered
+// with eppm_host_register / eppm_host_alloc is read by the copy engine where it lies (*direct; `hold` keeps its block in use until the
+// caller has seen the DMA complete).  Any other image goes through image `slot` of the current pinned staging buffer (one host copy):
+// the first such image of a call (*staged still false) allocates the buffer and its event, or waits for the H2D that last read it.
+static int upload_rgb(eppm_ctx* c, uint8_t* dst, const uint8_t* src, size_t row_stride, HostHold& hold, int slot, bool* direct, bool* staged)
+{
+    const size_t row = (size_t)c->w * 3, img = row * c->h, span = row_stride * (c->h - 1) + row;
+    if (hold.add(src, span)) {
+        if (row_stride == row) HIPCHK(hipMemcpyAsync(dst, src, img, hipMemcpyHostToDevice, c->stream));
+        else HIPCHK(hipMemcpy2DAsync(dst, row, src, row_stride, row, c->h, hipMemcpyHostToDevice, c->stream));
+        *direct = true;
+        return EPPM_OK;
+    }
+    const int q = c->rgb_cur;
+    if (!*staged) {
+        HIPCHK(pinned_lazy(&c->h_rgb[q], &c->h_rgb_bytes, img * 2 * c->npairs, c->device));
+        if (!c->ev_rgb[q]) HIPCHK(hipEventCreateWithFlags(&c->ev_rgb[q], hipEventDisableTiming));
+        else HIPCHK(hipEventSynchronize(c->ev_rgb[q]));
+    }
+    uint8_t* h = c->h_rgb[q] + (size_t)slot * img;
+    copy_rows(h, row, src, row_stride, row, c->h);
+    HIPCHK(hipMemcpyAsync(dst, h, img, hipMemcpyHostToDevice, c->stream));
+    *staged = true;
+    return EPPM_OK;
+}
+// what a call that uploaded images owes the stream before its kernels: the staging buffer's event, and the mark of the in-place reads
+static int upload_done(eppm_ctx* c, bool direct, bool staged)
+{
+    if (staged) {
+        HIPCHK(hipEventRecord(c->ev_rgb[c->rgb_cur], c->stream));
+        c->rgb_cur ^= 1;
+    }
+    if (direct) {
+        if (!c->ev_h2d) HIPCHK(hipEventCreateWithFlags(&c->ev_h2d, hipEventDisableTiming));
+        HIPCHK(hipEventRecord(c->ev_h2d, c->stream));
+    }
+    return EPPM_OK;
+}
+
+// host RGB of pairs 0..n-1 -> H2D -> RGBA planes (bao_rgb2rgba, alpha = 0) -> prepare
+static int set_images_host_impl(eppm_ctx* c, int n, const uint8_t* const* rgb1, const uint8_t* const* rgb2, size_t row_stride, HostHold& hold)
+{
+    if (row_stride < (size_t)c->w * 3) return set_err(EPPM_ERR_ARG, "eppm_set_images: row_stride %zu < 3*w", row_stride);
+    HIPCHK(hipSetDevice(c->device));
+    const size_t img = (size_t)c->w * 3 * c->h;
+    for (int k = 0; k < n; k++)
+        if (!rgb1[k] || !rgb2[k]) return set_err(EPPM_ERR_ARG, "eppm_set_images: NULL image");
+    bool staged = false, direct = false;
+    for (int k = 0; k < n; k++)
+        for (int f = 0; f < 2; f++)
+            CHK(upload_rgb(c, c->of_pair(c->d_rgb, k) + (size_t)f * img, f ? rgb2[k] : rgb1[k], row_stride, hold, k * 2 + f, &direct, &staged));
+    CHK(upload_done(c, direct, staged));
+    c->n_active = n;
+    c->tmp_valid = c->tmp_snap = false; // a new pair is a new clip
+    const int p0 = (int)(c->raw_pitch / 4);
+    launch_rgb_to_rgba(c->raw1, p0, c->d_rgb, c->h, c->w, c->stream, c->bt());
+    launch_rgb_to_rgba(c->raw2, p0, c->d_rgb + img, c->h, c->w, c->stream, c->bt());
+    const int r = prepare(c);
+    // set_data's contract (a synchronous cudaMemcpy in the reference, driver :165-166): when the call returns the caller may reuse
+    // its images.  Staged images were copied above; for images read in place, wait for their DMA (the kernels are queued already).
+    if (direct) HIPCHK(hipEventSynchronize(c->ev_h2d));
+    return r;
+}
+static int set_images_host(eppm_ctx* c, int n, const uint8_t* const* rgb1, const uint8_t* const* rgb2, size_t row_stride)
+{
+    HostHold hold;
+    const int r = set_images_host_impl(c, n, rgb1, rgb2, row_stride, hold);
+    if (r != EPPM_OK && !hold.v.empty()) (void)hipStreamSynchronize(c->stream);     // nothing may still read the blocks when `hold` lets them go
+    return r;
+}
+
+extern "C" int eppm_set_images(eppm_ctx* c, const uint8_t* rgb1, const uint8_t* rgb2, size_t row_stride)
+{
+    if (!c || !rgb1 || !rgb2) return set_err(EPPM_ERR_ARG, "eppm_set_images: NULL argument");
+    return set_images_host(c, 1, &rgb1, &rgb2, row_stride);
+}
+
+extern "C" int eppm_batch_set_images(eppm_ctx* c, int n, const uint8_t* const* rgb1, const uint8_t* const* rgb2, size_t row_stride)
+{
+    if (!c || !rgb1 || !rgb2) return set_err(EPPM_ERR_ARG, "eppm_batch_set_images: NULL argument");
+    if (n < 1 || n > c->npairs) return set_err(EPPM_ERR_ARG, "eppm_batch_set_images: %d pairs, context holds %d", n, c->npairs);
+    return set_images_host(c, n, rgb1, rgb2, row_stride);
+}
+
+// device-resident RGBA of pairs 0..n-1: copied into the slabs' raw planes in stream order (the caller's planes are not
+// read after the copies complete, and never in place), then prepare
+static int set_images_device(eppm_ctx* c, int n, const void* const* d1, const void* const* d2, size_t pitch)
+{
+    if (pitch < (size_t)c->w * 4 || (pitch & 3)) return set_err(EPPM_ERR_ARG, "eppm_set_images_device: bad pitch %zu", pitch);
+    HIPCHK(hipSetDevice(c->device));
+    for (int k = 0; k < n; k++) {
+        if (!d1[k] || !d2[k]) return set_err(EPPM_ERR_ARG, "eppm_set_images_device: NULL image");
+        HIPCHK(hipMemcpy2DAsync(c->of_pair(c->raw1, k), c->raw_pitch, d1[k], pitch, (size_t)c->w * 4, c->h, hipMemcpyDeviceToDevice, c->stream));
+        HIPCHK(hipMemcpy2DAsync(c->of_pair(c->raw2, k), c->raw_pitch, d2[k], pitch, (size_t)c->w * 4, c->h, hipMemcpyDeviceToDevice, c->stream));
+    }
+    c->n_active = n;
+    c->tmp_valid = c->tmp_snap = false;
+    return prepare(c);
+}
+
+extern "C" int eppm_set_images_device(eppm_ctx* c, const void* d1, const void* d2, size_t pitch)
+{
+    if (!c || !d1 || !d2) return set_err(EPPM_ERR_ARG, "eppm_set_images_device: NULL argument");
+    return set_images_device(c, 1, &d1, &d2, pitch);
+}
+
+extern "C" int eppm_batch_set_images_device(eppm_ctx* c, int n, const void* const* d_rgba1, const void* const* d_rgba2, size_t pitch)
+{
+    if (!c || !d_rgba1 || !d_rgba2) return set_err(EPPM_ERR_ARG, "eppm_batch_set_images_device: NULL argument");
+    if (n < 1 || n > c->npairs) return set_err(EPPM_ERR_ARG, "eppm_batch_set_images_device: %d pairs, context holds %d", n, c->npairs);
+    return set_images_device(c, n, d_rgba1, d_rgba2, pitch);
+}
+
+// ---- frame push: image 2 becomes image 1 by exchanging the context's plane pointers -- the raw frame, every
+// pyramid level, census plane and texel plane of the old image 2 are kept --, the new frame becomes image 2 and is prepared alone ----
+static int push_check(eppm_ctx* c, const char* what)
+{
+    if (c->npairs != 1) return set_err(EPPM_ERR_ARG, "%s: a batch context has no previous pair (its pairs run concurrently)", what);
+    if (!c->have_images) return set_err(EPPM_ERR_STATE, "%s: no pair set yet (eppm_set_images first)", what);
+    if (c->flow_pending) return set_err(EPPM_ERR_STATE, "%s: an eppm_compute_begin is pending", what);
+    return EPPM_OK;
+}
+// also arms the temporal prior: the snapshots describe the pair that ends in the new image 1 only directly after that pair's compute
+static void push_swap(eppm_ctx* c)
+{
+    c->tmp_valid = c->temporal && c->tmp_snap;
+    c->tmp_snap = false;
+    std::swap(c->raw1, c->raw2);
+    for (int l = 0; l < c->nl; l++) {
+        std::swap(c->img1[l], c->img2[l]);
+        std::swap(c->cen1[l], c->cen2[l]);
+        std::swap(c->pk1[l], c->pk2[l]);
+        std::swap(c->pc1[l], c->pc2[l]);
+    }
+    std::swap(c->pp1, c->pp2);
+}
+
+static int push_image_host_impl(eppm_ctx* c, const uint8_t* rgb, size_t row_stride, HostHold& hold)
+{
+    if (row_stride < (size_t)c->w * 3) return set_err(EPPM_ERR_ARG, "eppm_push_image: row_stride %zu < 3*w", row_stride);
+    HIPCHK(hipSetDevice(c->device));
+    uint8_t* dst = c->d_rgb + (size_t)c->w * 3 * c->h;     // image 2's half of the RGB staging plane, and of the pinned staging (slot 1)
+    bool staged = false, direct = false;
+    CHK(upload_rgb(c, dst, rgb, row_stride, hold, 1, &direct, &staged));
+    CHK(upload_done(c, direct, staged));
+    push_swap(c);
+    launch_rgb_to_rgba(c->raw2, (int)(c->raw_pitch / 4), dst, c->h, c->w, c->stream, c->bt());
+    const int r = prepare(c, true);
+    if (direct) HIPCHK(hipEventSynchronize(c->ev_h2d));
+    return r;
+}
+
+extern "C" int eppm_push_image(eppm_ctx* c, const uint8_t* rgb, size_t row_stride)
+{
+    if (!c || !rgb) return set_err(EPPM_ERR_ARG, "eppm_push_image: NULL argument");
+    CHK(push_check(c, "eppm_push_image"));
+    HostHold hold;
+    const int r = push_image_host_impl(c, rgb, row_stride, hold);
+    if (r != EPPM_OK && !hold.v.empty()) (void)hipStreamSynchronize(c->stream);
+    return r;
+}
+
+extern "C" int eppm_push_image_device(eppm_ctx* c, const void* d_rgba, size_t pitch)
+{
+    if (!c || !d_rgba) return set_err(EPPM_ERR_ARG, "eppm_push_image_device: NULL argument");
+    CHK(push_check(c, "eppm_push_image_device"));
+    if (pitch < (size_t)c->w * 4 || (pitch & 3)) return set_err(EPPM_ERR_ARG, "eppm_push_image_device: bad pitch %zu", pitch);
+    HIPCHK(hipSetDevice(c->device));
+    // into the old image 1's raw plane, which the swap then makes image 2's: a copy that fails leaves the context on its old pair
+    HIPCHK(hipMemcpy2DAsync(c->raw1, c->raw_pitch, d_rgba, pitch, (size_t)c->w * 4, c->h, hipMemcpyDeviceToDevice, c->stream));
+    push_swap(c);
+    return prepare(c, true);
+}

@@ -1,0 +1,133 @@
+// ctx_interp.cpp -- what reads the results of a context's (context.h) last bidirectional call: frame interpolation and the tracker.
+#include "context.h"
+#include "interp.h"
+
+using namespace eppm;
+
+// ---- frame interpolation: the raw RGBA frames (written only by set_images, read only by prepare), the level-0
+// forward flow and both masks of the last bidirectional call, all still in the context ----
+
+static int itp_alloc(eppm_ctx* c)
+{
+    if (c->itp) return EPPM_OK;
+    const size_t n = (size_t)c->h * c->w, slots = (size_t)c->npairs * kInterpChunk;
+    const size_t plane = (n + 63) & ~(size_t)63;
+    const size_t keys = slots * plane * 8, fills = slots * plane * 4, rgb = slots * n * 3;
+    Carve cv;                           // (every size but the last is a multiple of 256 bytes)
+    cv.plane(&c->itp_keys, keys);
+    for (int32_t** p : {&c->itp_fill1, &c->itp_fill2}) cv.plane(p, fills);
+    cv.plane(&c->itp_rgb, rgb);
+    CHK(cv.alloc(&c->itp, &c->itp_bytes, keys + 2 * fills + rgb, c->device, "interpolation scratch"));
+    c->itp_plane = plane;
+    return EPPM_OK;
+}
+
+static int interp_check(eppm_ctx* c, const char* what, int nt, const float* t)
+{
+    if (nt < 1 || !t) return set_err(EPPM_ERR_ARG, "%s: nt %d, t %p", what, nt, (const void*)t);
+    for (int k = 0; k < nt; k++)
+        if (!interp_t_ok(t[k])) return set_err(EPPM_ERR_ARG, "%s: t[%d] = %g outside [0, 1]", what, k, t[k]);
+    if (c->flow_pending) return set_err(EPPM_ERR_STATE, "%s: an eppm_compute_begin is pending", what);
+    if (!c->have_bwd || !c->bwd_images) return set_err(EPPM_ERR_STATE, "%s: needs a bidirectional call on the current images", what);
+    return EPPM_OK;
+}
+
+// times t[k0 .. k0+nt) of the first npairs pairs: splat, fill, blend into the packed RGB scratch (d_rgba NULL) or into d_rgba[k0 + k] (pair 0)
+static int interp_chunk(eppm_ctx* c, int npairs, int k0, int nt, const float* t, void* const* d_rgba, size_t pitch)
+{
+    InterpArgs a{};
+    a.img1 = (const uint8_t*)c->raw1; a.img2 = (const uint8_t*)c->raw2; a.img_pitch = c->raw_pitch; a.img_stride = c->stride;
+    a.flow = c->flow[0]; a.flow_stride = c->stride;
+    a.occ1 = c->occ1; a.occ2 = c->occ2; a.occ_stride = c->bwd_stride;
+    a.keys = c->itp_keys; a.fill1 = c->itp_fill1; a.fill2 = c->itp_fill2; a.plane = c->itp_plane;
+    a.rgb = d_rgba ? nullptr : c->itp_rgb;
+    a.rgba_pitch = pitch;
+    a.h = c->h; a.w = c->w; a.nt = nt;
+    for (int k = 0; k < kInterpChunk; k++) {
+        a.t[k] = k < nt ? t[k0 + k] : 0.0f;
+        a.rgba[k] = (d_rgba && k < nt) ? (uint8_t*)d_rgba[k0 + k] : nullptr;
+    }
+    stage_begin(c, c->ev, "interp_splat");
+    launch_interp_splat(a, npairs, c->stream);
+    stage_end(c, c->ev);
+    stage_begin(c, c->ev, "interp_fill");
+    launch_interp_fill(a, npairs, c->stream);
+    stage_end(c, c->ev);
+    stage_begin(c, c->ev, "interp_blend");
+    launch_interp_blend(a, npairs, c->stream);
+    stage_end(c, c->ev);
+    HIPCHK(hipGetLastError());
+    return EPPM_OK;
+}
+
+// host-pointer forms: each chunk's packed RGB outputs cross PCIe once (3 B/px) into the pinned copy, then into the caller's rows
+static int interp_host(eppm_ctx* c, const char* what, int npairs, int nt, const float* t, uint8_t* const* rgb, size_t row_stride)
+{
+    CHK(interp_check(c, what, nt, t));
+    if (!rgb) return set_err(EPPM_ERR_ARG, "%s: NULL rgb", what);
+    for (int k = 0; k < npairs * nt; k++)
+        if (!rgb[k]) return set_err(EPPM_ERR_ARG, "%s: NULL rgb[%d]", what, k);
+    if (row_stride < (size_t)c->w * 3) return set_err(EPPM_ERR_ARG, "%s: row_stride %zu < 3*w", what, row_stride);
+    HIPCHK(hipSetDevice(c->device));
+    CHK(itp_alloc(c));
+    const size_t img = (size_t)c->h * c->w * 3, row = (size_t)c->w * 3;
+    HIPCHK(pinned_lazy(&c->h_itp, &c->h_itp_bytes, img * c->npairs * kInterpChunk, c->device));
+    for (int k0 = 0; k0 < nt; k0 += kInterpChunk) {
+        const int m = nt - k0 < kInterpChunk ? nt - k0 : kInterpChunk;
+        CHK(interp_chunk(c, npairs, k0, m, t, nullptr, 0));
+        HIPCHK(hipMemcpyAsync(c->h_itp, c->itp_rgb, img * npairs * m, hipMemcpyDeviceToHost, c->stream));
+        HIPCHK(hipStreamSynchronize(c->stream));
+        for (int p = 0; p < npairs; p++)
+            for (int k = 0; k < m; k++) copy_rows(rgb[(size_t)p * nt + k0 + k], row_stride, c->h_itp + img * ((size_t)p * m + k), row, row, c->h);
+    }
+    return EPPM_OK;
+}
+
+extern "C" int eppm_interpolate(eppm_ctx* c, int nt, const float* t, uint8_t* const* rgb, size_t row_stride)
+{
+    if (!c) return set_err(EPPM_ERR_ARG, "eppm_interpolate: NULL ctx");
+    return interp_host(c, "eppm_interpolate", 1, nt, t, rgb, row_stride);
+}
+
+extern "C" int eppm_batch_interpolate(eppm_ctx* c, int nt, const float* t, uint8_t* const* rgb, size_t row_stride)
+{
+    if (!c) return set_err(EPPM_ERR_ARG, "eppm_batch_interpolate: NULL ctx");
+    return interp_host(c, "eppm_batch_interpolate", c->n_active, nt, t, rgb, row_stride);
+}
+
+extern "C" int eppm_interpolate_device(eppm_ctx* c, int nt, const float* t, void* const* d_rgba, size_t pitch)
+{
+    if (!c) return set_err(EPPM_ERR_ARG, "eppm_interpolate_device: NULL ctx");
+    CHK(interp_check(c, "eppm_interpolate_device", nt, t));
+    if (!d_rgba) return set_err(EPPM_ERR_ARG, "eppm_interpolate_device: NULL d_rgba");
+    for (int k = 0; k < nt; k++)
+        if (!d_rgba[k]) return set_err(EPPM_ERR_ARG, "eppm_interpolate_device: NULL d_rgba[%d]", k);
+    if (pitch < (size_t)c->w * 4 || (pitch & 3)) return set_err(EPPM_ERR_ARG, "eppm_interpolate_device: bad pitch %zu", pitch);
+    HIPCHK(hipSetDevice(c->device));
+    CHK(itp_alloc(c));
+    for (int k0 = 0; k0 < nt; k0 += kInterpChunk)
+        CHK(interp_chunk(c, 1, k0, nt - k0 < kInterpChunk ? nt - k0 : kInterpChunk, t, d_rgba, pitch));
+    return EPPM_OK;
+}
+
+// ---- dense point trajectories (tracker.cpp): the raw frames, the level-0 forward flow and the level-0 backward flow
+// of one pair, in the window of eppm_interpolate* ----
+
+int ctx_track_inputs(eppm_ctx* c, int pair, int h, int w, int device, const char* what, TrackIn* in, hipStream_t* s)
+{
+    if (c->h != h || c->w != w || c->device != device)
+        return set_err(EPPM_ERR_ARG, "%s: the tracker is %dx%d on device %d, the context %dx%d on device %d", what, w, h, device, c->w, c->h, c->device);
+    if (pair < 0 || pair >= c->n_active) return set_err(EPPM_ERR_ARG, "%s: pair %d, the context has %d active", what, pair, c->n_active);
+    if (c->flow_pending) return set_err(EPPM_ERR_STATE, "%s: an eppm_compute_begin is pending", what);
+    if (!c->have_bwd || !c->bwd_images) return set_err(EPPM_ERR_STATE, "%s: needs a bidirectional call on the current images", what);
+    HIPCHK(hipSetDevice(c->device));
+    in->img1 = (const uint8_t*)c->of_pair(c->raw1, pair);
+    in->img2 = (const uint8_t*)c->of_pair(c->raw2, pair);
+    in->pitch = c->raw_pitch;
+    in->fwd = c->of_pair(c->flow[0], pair);
+    in->bwd = c->of_bwd_pair(c->bflow[0], pair);
+    in->h = c->h;
+    in->w = c->w;
+    *s = c->stream;
+    return EPPM_OK;
+}

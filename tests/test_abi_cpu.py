@@ -47,7 +47,7 @@ def test_library_exports_every_declared_symbol():
 def test_test_hooks_live_in_the_test_library_only():
     """include/eppm_test.h = the switches and probes of the parity tests.  The product library exports none of them (nothing matching
     eppm_test* / eppm_probe*), the test library exports them on top of everything include/eppm.h declares, and the two are linked from the
-    same objects except eppm_api.o (compiled with / without -DEPPM_TEST_HOOKS) and the probe kernel."""
+    same objects except those of the Makefile's HOOKED sources (compiled with / without -DEPPM_TEST_HOOKS), test_hooks.o and the probe kernel."""
     hooks = _declared("eppm_test.h")
     assert hooks == set(_lib.TEST_SYMBOLS) and not (hooks & _declared("eppm.h"))
     prod, test = _exported(eppm_amd.lib_path("")), _exported(eppm_amd.lib_path("test"))

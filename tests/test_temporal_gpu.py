@@ -98,6 +98,46 @@ def test_push_equals_set_images(h, w, device_form):
     e.close(); ref.close()
 
 
+def test_push_host_memory_forms_equal_set_images(crop):
+    """eppm_push_image from every kind of caller memory, temporal mode off: plain contiguous memory and plain memory with padded rows (both
+    through the pinned staging, whose two buffers wrap around: set_data took the first), then padded rows in memory from eppm_host_alloc
+    (read in place by DMA; the source is overwritten as soon as the call returns).  After each push the planes of both images at every
+    level and the flow equal those of set_data on the same pair in a second context, bit for bit."""
+    import eppm_amd
+    from eppm_amd._lib import check
+    L = eppm_amd.lib()
+    a, b = crop
+    h, w = 120, 160
+    f = [a, b, np.roll(b, 3, axis=1), np.roll(b, (2, -4), axis=(0, 1)), b]
+    stride = 3 * (w + 13)
+    plain = f[2].copy()
+    padded = np.full((h, w + 13, 3), 0xA5, np.uint8)
+    padded[:, :w] = f[3]
+    pinned = eppm_amd.pinned_empty((h, w + 13, 3))
+    pinned[:] = 0x5A
+    pinned[:, :w] = f[4]
+    sources = [(plain, 3 * w, "plain"), (padded, stride, "plain, padded rows"), (pinned, stride, "registered, padded rows")]
+    for src, _, what in sources:
+        assert L.eppm_host_is_registered(C.c_void_p(src.ctypes.data), C.c_size_t(src.nbytes)) == int(src is pinned), what
+    ref = eppm_amd.EPPM()
+    ref.init(h, w)
+    e = eppm_amd.EPPM()
+    e.init(h, w)
+    e.set_data(f[0], f[1])
+    e.compute_flow()
+    for i, (src, row_stride, what) in enumerate(sources, start=1):
+        check(L.eppm_push_image(e._ctx, C.c_void_p(src.ctypes.data), C.c_size_t(row_stride)), "eppm_push_image")
+        if src is pinned:
+            src[:] = 0                       # the push has consumed the image when it returns
+        ref.set_data(f[i], f[i + 1])
+        want, got = all_planes(ref), all_planes(e)
+        for k in want:
+            eq(got[k], want[k], f"plane {k} after push {i} ({what})")
+        (u, v), (wu, wv) = e.compute_flow(), ref.compute_flow()
+        eq(u, wu, f"u after push {i} ({what})"); eq(v, wv, f"v after push {i} ({what})")
+    e.close(); ref.close()
+
+
 def test_state_errors_and_defaults():
     import eppm_amd
     L = eppm_amd.lib()
