@@ -73,7 +73,7 @@ static int ctx_alloc(eppm_ctx* c)
     }
     const int L = c->nl - 1;
     const size_t n2 = (size_t)c->W[L] * c->H[L];
-    // column-parity planes: the tolerance library reads them at both radii, the exact library at radius 9 (k_patchmatch.hip: pm_has_parity)
+    // column-parity planes: the tolerance library reads them at both radii, the exact library at radius 9 (pm_device.cuh: pm_has_parity)
 #ifndef EPPM_TOL
     if (c->prm.patch_r == 9)
 #endif

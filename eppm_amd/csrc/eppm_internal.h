@@ -71,7 +71,7 @@ void launch_pack(void* texels, int tpitch, const uint32_t* img, int ipitch, cons
 void launch_delta_values(float* t2, int n, int which, hipStream_t s);
 void launch_rgb_to_rgba(uint32_t* out, int pitch_px, const uint8_t* rgb, int h, int w, hipStream_t s, Batch bt = kOnePair);
 
-// ---- PatchMatch (k_patchmatch.hip) ----
+// ---- PatchMatch (k_pm_field.hip, k_pm_sweep.hip, k_pm_search.hip; shared: pm_device.cuh) ----
 // One PatchMatch problem = (source planes, target planes, NNF, cost).  The forward (1->2) and backward (2->1)
 // problems of a pair have the same size and run in the same launches (blockIdx.z / blockIdx.y selects one).
 struct PmProblem {
@@ -83,10 +83,10 @@ struct PmProblem {
     // direction d at element offset d * PmBatch::cache_plane.  The patch cost is a pure function of (pixel, candidate) while the
     // images stand, so a sweep that meets the candidate it evaluated for this pixel last time -- the neighbour's match did not
     // change between two iterations, the normal case once the field has converged -- takes the cost from here.  spec doubles as
-    // phase A's hand-over plane to phase B (k_patchmatch.hip).  scand == NULL: no cache (every candidate is evaluated).
+    // phase A's hand-over plane to phase B (k_pm_sweep.hip).  scand == NULL: no cache (every candidate is evaluated).
     float* spec = nullptr;
     int32_t* scand = nullptr;   // x | y << 16 of the cached candidate; -1 = empty (no candidate has both coordinates -1)
-    // Work list of the speculative sweeps (k_patchmatch.hip): phase A names the chains on which some candidate of the rejection path
+    // Work list of the speculative sweeps (k_pm_sweep.hip): phase A names the chains on which some candidate of the rejection path
     // would be ACCEPTED -- every other chain leaves its pixels as they are, and phase B walks the listed chains only.  Layout:
     // word 0, 1: list lengths of the even / odd sweeps of a run (ping-pong: a sweep's phase A clears the other one);
     // [16, 16 + units): stamp per unit (two adjacent segments of a line) = 1 + number of the last sweep that listed it;
@@ -94,7 +94,7 @@ struct PmProblem {
     // Merged form (one phase A for the four sweeps of an iteration): words 8 + 4 * (iteration & 1) + d: list length of direction d;
     // [16 + (2 + d) * units, ..): stamps of direction d = 1 + the iteration that listed the unit last; [16 + (6 + d) * units, ..): its list.
     uint32_t* wl = nullptr;
-    // Merged form of the speculative sweeps (k_patchmatch.hip, k_pm_spec_all): the field as it stood before each direction's sweep of the
+    // Merged form of the speculative sweeps (k_pm_sweep.hip, k_pm_spec_all): the field as it stood before each direction's sweep of the
     // current iteration, four short2 planes (direction d at int16 offset d * PmBatch::seed_plane) -- where the in-place sweeps read their seeds.
     int16_t* seed = nullptr;
     uint32_t* rng_work;       // [nblocks][64][6] XORWOW lane states read by the random search
@@ -140,7 +140,7 @@ void launch_pm_cost_field(const PmBatch& b, const float* lut, int R, hipStream_t
 // sweeps, 4 cost field
 int pm_parity_kernels(int R);
 // one directional sweep; returns true when the result is in nnf_alt (caller swaps nnf/nnf_alt)
-// speculative: the two-launch form for iterations in which few candidates are accepted (k_patchmatch.hip, k_pm_sweep_spec); same results
+// speculative: the two-launch form for iterations in which few candidates are accepted (k_pm_sweep.hip, k_pm_sweep_spec); same results
 bool launch_pm_sweep(PmBatch& b, const float* lut, int R, int seg_len, int dir, hipStream_t s, bool speculative = false);
 // The four sweeps of one iteration in the merged speculative form (k_pm_spec_all + four in-place launches over the listed chains): same
 // results, in place in nnf.  Returns false (nothing launched) when the problems lack the planes or the radius has no instantiation.

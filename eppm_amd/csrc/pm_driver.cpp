@@ -25,7 +25,7 @@ void search(PmBatch& b, eppm_pm_rng* rng, const float* lut, const eppm_params& p
         rng->cur[k] ^= 1;
     }
 }
-// The sweeps of an iteration run in the speculative two-launch form (k_patchmatch.hip: k_pm_sweep_spec + phase B) once most
+// The sweeps of an iteration run in the speculative two-launch form (k_pm_sweep.hip: k_pm_sweep_spec + phase B) once most
 // candidates are rejected: in the third iteration (index 2) one step in eight to one in four still follows an accepted
 // candidate, from the fourth on fewer than one in ten (tools/sweep_stats.py), and a step that follows a rejection needs no
 // dependent evaluation.  Same results either way; from iteration 2 / 3 measured equal within 0.5 %, from 0 or 1 slower.
@@ -46,7 +46,7 @@ static bool sweep_speculative(int iteration, long long pixels, int m)
 {
     return m < 0 ? (iteration >= EPPM_SPEC_FROM_ITER && pixels >= EPPM_SPEC_MIN_PIXELS) : m != 0;
 }
-// From this iteration on the four speculative sweeps share ONE phase A (k_patchmatch.hip, k_pm_spec_all: the merged form): the field has
+// From this iteration on the four speculative sweeps share ONE phase A (k_pm_sweep.hip, k_pm_spec_all: the merged form): the field has
 // converged far enough that a phase-A launch costs its launch, and four of them per iteration are three too many.  The threshold depends
 // on the size of a PROBLEM, not of the launch (round 5, A/B within one lease, profiles/r05x_c_merged_threshold_by_size.txt): the merged
 // phase A touches every pixel for four directions at once, and on a 480x270 or 960x540 problem that pays two iterations later than on

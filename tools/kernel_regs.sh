@@ -1,5 +1,5 @@
 #!/bin/bash
-# VGPR / SGPR / LDS / scratch of every kernel in a HIP source: tools/kernel_regs.sh eppm_amd/csrc/k_patchmatch.hip [extra hipcc flags]
+# VGPR / SGPR / LDS / scratch of every kernel in a HIP source: tools/kernel_regs.sh eppm_amd/csrc/k_pm_sweep.hip [extra hipcc flags]
 # (compiles the device code to assembly for gfx950 and reads the .amdhsa_ metadata)
 src=$1; shift
 out=$(mktemp /tmp/kregs.XXXXXX.s)
