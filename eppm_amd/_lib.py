@@ -59,7 +59,7 @@ SYMBOLS = [
 
 
 # what include/eppm_test.h adds, exported by libeppm_hip_test.so and libeppm_hip_tol_test.so only (the parity tests' switches and arithmetic probes)
-TEST_SYMBOLS = ["eppm_test_set_option", "eppm_probe_c2f_window", "eppm_probe_fast_exp", "eppm_probe_div_const", "eppm_probe_delta_table",
+TEST_SYMBOLS = ["eppm_test_set_option", "eppm_probe_c2f_window", "eppm_probe_dispatch", "eppm_probe_fast_exp", "eppm_probe_div_const", "eppm_probe_delta_table",
                 "eppm_probe_unpack_texel", "eppm_probe_pm_parity", "eppm_probe_ctx_rng_states"]
 
 _variant = None
@@ -98,3 +98,12 @@ def check(status, what=""):
 
 def check_launcher(what=""):
     check(lib().eppm_launcher_status(), what)
+
+
+def probe_dispatch(stage, *args, nout=1):
+    """eppm_probe_dispatch (test libraries; include/eppm_test.h): what a launcher decides for a launch of that size -- the launchers' own
+    host functions, no GPU needed.  Returns a tuple of nout ints."""
+    a = (C.c_int * len(args))(*[int(v) for v in args])
+    out = (C.c_int * nout)()
+    check(lib().eppm_probe_dispatch(stage.encode(), a, len(args), out, nout), f"eppm_probe_dispatch {stage}")
+    return tuple(out)

@@ -78,16 +78,19 @@ EPPM_HIDDEN int upload_blf_lut(float** dst);              // g[0..2*POSTPROC_BLF
 // which sets the DEFAULTS a context copies when it is created (eppm_ctx::opt_*) and what the context-less stage launchers read; a context
 // in use is never affected.
 #ifdef EPPM_TEST_HOOKS
-EPPM_HIDDEN extern std::atomic<int> g_opt_rand_table;       // "rand_table": 0 = contexts created afterwards draw while they search (the form above 512 MB)
+EPPM_HIDDEN extern std::atomic<int> g_opt_rand_table;       // "rand_table": 0 = contexts created afterwards draw while they search (the form above 512 MB); 2 = 1, and eppm_pm_random_search reads a table too
 EPPM_HIDDEN extern std::atomic<int> g_opt_sweep_spec;       // "sweep_spec": -1 by iteration, 0 never, 1 always, 2 always and without the work list, 3 always in the merged form
 EPPM_HIDDEN extern std::atomic<int> g_opt_no_split;         // "c2f_no_split"
+EPPM_HIDDEN extern std::atomic<int> g_opt_force_split;      // "c2f_force_split": the refine's stage launchers bring the split path's scratch
 static inline int opt_rand_table() { return g_opt_rand_table.load(); }
 static inline int opt_sweep_spec() { return g_opt_sweep_spec.load(); }
 static inline int opt_no_split() { return g_opt_no_split.load(); }
+static inline int opt_force_split() { return g_opt_force_split.load(); }
 #else
 static constexpr int opt_rand_table() { return 1; }
 static constexpr int opt_sweep_spec() { return -1; }
 static constexpr int opt_no_split() { return 0; }
+static constexpr int opt_force_split() { return 0; }
 #endif
 
 // ---- caller memory registered for DMA: host_registry.h (header-only logic), bound to HIP by host_registry.cpp ----

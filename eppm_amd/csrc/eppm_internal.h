@@ -28,6 +28,11 @@ struct Batch {
 };
 constexpr Batch kOnePair = {1, 0};
 
+// Dispatch decisions: a launcher that chooses between kernels by the size of its launch asks ONE host function below, and the test
+// libraries ask the same function (include/eppm_test.h: eppm_probe_dispatch), so that a test can pick shapes on either side of a
+// threshold without repeating the constant.  Pure host arithmetic; not exported.
+#define EPPM_DECISION __attribute__((visibility("hidden")))
+
 struct PlanesH {            // host-side mirror of eppm::Planes: float4 texel planes {r,g,b,census bits}, pitch in pixels
     const void* pk1;
     const void* pk2;
@@ -151,6 +156,14 @@ void launch_pm_jump(const PmBatch& b, const float* lut, int R, int step, hipStre
 void launch_pm_neighbor(const PmBatch& b, const float* lut, int R, hipStream_t s);
 void launch_pm_random_search(const PmBatch& b, const PmRngDev& rng, const float* lut, int R, int search_range, int num_guess,
                              hipStream_t s);
+// rows of a 16x16 block per workgroup of the random search: 4 (a quarter block, a wave per guess) or 2 (an eighth block: small launches
+// at radius 9 that read numbers drawn ahead, `table`); problems = directions per pair
+EPPM_DECISION int pm_search_rows(int w, int h, int R, int problems, int npairs, bool table);
+// The classic sweep's kernel for one direction.  lpc: lanes per chain (0: no cooperative kernel at this radius, k_pm_seg_propagate);
+// small: the launch cannot fill the chip (radius 9: twice the lanes per chain in the exact library); pre: the chains' pixels are fetched
+// before the first step (given the evaluation cache, PmProblem::scand); tile: the source tile fits LDS, otherwise the sweep gathers.
+struct SweepForm { int lpc; bool small, pre, tile; };
+EPPM_DECISION SweepForm pm_sweep_form(int w, int h, int R, int seg_len, int dir, int problems, int npairs);
 
 // The seeded start of a streaming context's PatchMatch, after launch_pm_init_field + launch_pm_cost_field on the same
 // batch (one pair): the cost of every pixel's temporal prior (an absolute target like an NNF entry; a component <= kInvalid: none), and
@@ -196,12 +209,15 @@ void launch_nnf2flow(float* flow, int flow_pitch, const int16_t* nnf, int nnf_pi
 // ---- coarse to fine (k_c2f.hip) ----
 void launch_resize_flow(float* out, int outH, int outW, const float* in, int h, int w, float ratio, float post_scale, hipStream_t s, Batch bt = kOnePair);
 void launch_mul_scalar(float* flow, float scale, int h, int w, hipStream_t s);
-bool c2f_refine_wants_split(int w, int h, int R, int npairs = 1, bool no_split = false);
+// workgroups per tile of the candidate refine: 0 (one launch, no scratch), or 3 / 4 (k_c2f_refine_tiled<R, 3 | 4> + k_c2f_select)
+EPPM_DECISION int c2f_refine_split_factor(int w, int h, int R, int npairs = 1, bool no_split = false);
+bool c2f_refine_wants_split(int w, int h, int R, int npairs = 1, bool no_split = false);      // c2f_refine_split_factor(..) != 0
 bool c2f_window_span(int R, int* span_x, int* span_y);          // test support: admissible centre spread of the LDS-window kernels
 // cost9: scratch of 36 floats per pixel for launches that c2f_refine_wants_split(), or NULL
 void launch_c2f_refine(const PlanesH& P, float* flow, const float* lut, int R, float* cost9, hipStream_t s, Batch bt = kOnePair, bool no_split = false);
 void launch_flow_blf(float* out, const float* in, const uint32_t* img, int ipitch, int w, int h, int flow_pitch,
                      const float* blf_lut, hipStream_t s, Batch bt = kOnePair);
+EPPM_DECISION int flow_blf_pixels_per_lane(int w, int h, int npairs = 1);      // of the smoothing: 2 (k_flow_blf<2>, large launches) or 1
 
 // interleaved float2 flow -> planar u | v (2*n floats) on the device: compute_flow's de-interleave, driver :302-306
 void launch_split_flow(float* uv, const float* flow, int n, hipStream_t s, Batch bt = kOnePair);

@@ -834,17 +834,22 @@ bool c2f_window_span(int R, int* span_x, int* span_y)
 }
 
 // no_split (a context's "c2f_no_split" option): never split, so that small images go through the LDS-window kernels too
-bool c2f_refine_wants_split(int w, int h, int R, int npairs, bool no_split)
+int c2f_refine_split_factor(int w, int h, int R, int npairs, bool no_split)
 {
-    if (no_split) return false;
-    const int tiles = ((w + kBlock - 1) / kBlock) * ((h + kBlock - 1) / kBlock) * npairs;
+    if (no_split || !(R == 9 || R == 17)) return 0;
+    if (!((w + R < 32764) && (h + R < 32764))) return 0;      // range of the offset-table identity (c2f_pass)
+    const int tiles = ((w + kBlock - 1) / kBlock) * ((h + kBlock - 1) / kBlock);
 #ifndef EPPM_C2F_SPLIT_BELOW_WAVES
 #define EPPM_C2F_SPLIT_BELOW_WAVES 1024              // fewer than 1 wave per SIMD on 256 CUs (at 256 threads per tile)
 #endif
     // Round 2 split below 3 waves per SIMD, which sent level 1 of ONE 1024x436 pair (448 tiles) through the split gather kernel:
     // 0.367 ms and a 16 MB scratch plane of 36 costs per pixel; the LDS-window kernel does the same launch in 0.364 ms without it.
-    return (R == 9 || R == 17) && tiles * 4 < EPPM_C2F_SPLIT_BELOW_WAVES;
+    if (!(tiles * npairs * 4 < EPPM_C2F_SPLIT_BELOW_WAVES)) return 0;
+    // 3 or 4 workgroups per tile: the factor whose workgroup count divides more evenly over the 256 CUs
+    auto imbalance = [&](int f) { const int wgs = tiles * f * npairs; return (float)((wgs + 255) / 256) * 256.0f / (float)wgs; };
+    return (imbalance(4) < imbalance(3)) ? 4 : 3;
 }
+bool c2f_refine_wants_split(int w, int h, int R, int npairs, bool no_split) { return c2f_refine_split_factor(w, h, R, npairs, no_split) != 0; }
 
 // cost9: scratch of 36 floats per pixel, or NULL (never split)
 void launch_c2f_refine(const PlanesH& P, float* flow, const float* lut, int R, float* cost9, hipStream_t s, Batch bt, bool no_split)
@@ -854,10 +859,7 @@ void launch_c2f_refine(const PlanesH& P, float* flow, const float* lut, int R, f
     const int per_xcd = (tiles + 7) / 8;
     dim3 grid1(per_xcd * 8, bt.n);               // x: padded so every XCD gets the same number of slots; y: pair
     const bool table_ok = (P.w + R < 32764) && (P.h + R < 32764);     // range of the offset-table identity (c2f_pass)
-    if (cost9 && table_ok && c2f_refine_wants_split(P.w, P.h, R, bt.n, no_split)) {
-        // 3 or 4 workgroups per tile: the factor whose workgroup count divides more evenly over the 256 CUs
-        auto imbalance = [&](int f) { const int wgs = tiles * f * bt.n; return (float)((wgs + 255) / 256) * 256.0f / (float)wgs; };
-        const int f = (imbalance(4) < imbalance(3)) ? 4 : 3;
+    if (const int f = cost9 ? c2f_refine_split_factor(P.w, P.h, R, bt.n, no_split) : 0) {
         dim3 gridf(per_xcd * f * 8, bt.n), gs((P.w + 63) / 64, (P.h + 3) / 4, bt.n), bs(64, 4);
         if (f == 3) {
             if (R == 9) hipLaunchKernelGGL((k_c2f_refine_tiled<9, 3>), gridf, block, 0, s, P, flow, lut, cost9, bt.stride);
@@ -1016,14 +1018,18 @@ EPPM_UNROLL(EPPM_BLF_UNROLL)
         out[((ya + 1) * fpitch + x) * 2 + 1] = oy;
     }
 }
+int flow_blf_pixels_per_lane(int w, int h, int npairs)
+{
+    const int wgs2 = ((w + BT_W - 1) / BT_W) * ((h + 15) / 16) * npairs;
+    // two pixels per lane halve the LDS traffic but double the work quantum: they pay from about 8 workgroups per CU
+    // (1920x1080: 0.96 vs 1.03 ms); below that the finer quantum balances the 256 CUs better (1024x436: 0.25 vs 0.27 ms)
+    return wgs2 >= 8 * 256 ? 2 : 1;
+}
 void launch_flow_blf(float* out, const float* in, const uint32_t* img, int ipitch, int w, int h, int flow_pitch,
                      const float* blf_lut, hipStream_t s, Batch bt)
 {
     dim3 block(BT_W, 8);
-    const int wgs2 = ((w + BT_W - 1) / BT_W) * ((h + 15) / 16) * bt.n;
-    // two pixels per lane halve the LDS traffic but double the work quantum: they pay from about 8 workgroups per CU
-    // (1920x1080: 0.96 vs 1.03 ms); below that the finer quantum balances the 256 CUs better (1024x436: 0.25 vs 0.27 ms)
-    if (wgs2 >= 8 * 256) {
+    if (flow_blf_pixels_per_lane(w, h, bt.n) == 2) {
         hipLaunchKernelGGL(k_flow_blf<2>, dim3((w + BT_W - 1) / BT_W, (h + 15) / 16, bt.n), block, 0, s, out, in, img, ipitch, w, h, flow_pitch, blf_lut, bt.stride);
     } else {
         hipLaunchKernelGGL(k_flow_blf<1>, dim3((w + BT_W - 1) / BT_W, (h + 7) / 8, bt.n), block, 0, s, out, in, img, ipitch, w, h, flow_pitch, blf_lut, bt.stride);

@@ -161,6 +161,12 @@ __global__ __launch_bounds__(576) EPPM_SEARCH_OCC void k_pm_random_search(PmBatc
     }
 }
 
+int pm_search_rows(int w, int h, int R, int problems, int npairs, bool table)
+{
+    const int quarter_wgs = ((w + kBlock - 1) / kBlock) * ((h + kBlock - 1) / kBlock) * 4 * problems * npairs;
+    return (table && R == 9 && quarter_wgs < EPPM_SEARCH_HALF_BELOW_WGS) ? 2 : 4;
+}
+
 void launch_pm_random_search(const PmBatch& b, const PmRngDev& rng, const float* lut, int R, int search_range, int num_guess,
                              hipStream_t s)
 {
@@ -168,14 +174,15 @@ void launch_pm_random_search(const PmBatch& b, const PmRngDev& rng, const float*
     const bool have_pc = b.p[0].P.pc2 && (b.n < 2 || b.p[1].P.pc2);
     if (rng.rand_tab && (R == 9 || R == 17)) {                                         // numbers drawn ahead: G waves per workgroup
         dim3 blockt(64 * num_guess);
+        const bool half = pm_search_rows(b.p[0].P.w, b.p[0].P.h, R, b.n, b.npairs, true) == 2;      // (radius 9 only)
         if (pm_has_parity(b, R, EPPM_PARITY_SEARCH)) {                                 // column-parity target planes
-            if (R == 9 && (int)grid.x < EPPM_SEARCH_HALF_BELOW_WGS)
+            if (half)
                 hipLaunchKernelGGL((k_pm_random_search<9, 2, true, 2>), dim3(grid.x * 2), dim3(32 * num_guess), 0, s, b, rng, lut, R, search_range, num_guess);
             else if (R == 9) hipLaunchKernelGGL((k_pm_random_search<9, 2, true>), grid, blockt, 0, s, b, rng, lut, R, search_range, num_guess);
             else hipLaunchKernelGGL((k_pm_random_search<17, 2, true>), grid, blockt, 0, s, b, rng, lut, R, search_range, num_guess);
             return;
         }
-        if (R == 9 && (int)grid.x < EPPM_SEARCH_HALF_BELOW_WGS) {
+        if (half) {
             hipLaunchKernelGGL((k_pm_random_search<9, 0, true, 2>), dim3(grid.x * 2), dim3(32 * num_guess), 0, s, b, rng, lut, R, search_range, num_guess);
             return;
         }

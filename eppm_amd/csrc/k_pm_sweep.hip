@@ -595,12 +595,13 @@ static void with_dir(int dir, F&& f)
 // the chains of one direction: `lines` lines of len pixels, each cut into nseg segments of seg_len steps
 struct SweepGeom {
     int len, lines, nseg;
-    SweepGeom(const PmBatch& b, int dir, int seg_len)
+    SweepGeom(int w, int h, int dir, int seg_len)
     {
         const bool is_row = (dir == 0 || dir == 2);
-        len = is_row ? b.p[0].P.w : b.p[0].P.h; lines = is_row ? b.p[0].P.h : b.p[0].P.w;
+        len = is_row ? w : h; lines = is_row ? h : w;
         nseg = (len + seg_len - 1) / seg_len;
     }
+    SweepGeom(const PmBatch& b, int dir, int seg_len) : SweepGeom(b.p[0].P.w, b.p[0].P.h, dir, seg_len) {}
     int nseg_pad() const { return (nseg + 1) & ~1; }                                    // segments 0 and 1 of a line in one workgroup
     int wgs(int cpb) const { return (lines * nseg_pad() + cpb - 1) / cpb; }             // workgroups of cpb chains, without a tile
 };
@@ -645,16 +646,39 @@ static void launch_sweep_t(const PmBatch& b, const float* lut, int seg_len, int 
 }
 // the classic form: source tile in LDS while it stays small (EPPM_SWEEP_TILE); very long segments gather
 template <int R, int LPC, bool PRE = false>
-static void launch_sweep_r(const PmBatch& b, const float* lut, int seg_len, int dir, const SweepGeom& g, hipStream_t s)
+static void launch_sweep_r(const PmBatch& b, const float* lut, int seg_len, int dir, const SweepGeom& g, const SweepForm& f, hipStream_t s)
 {
-    const size_t lds = (size_t)(R + 2 * SweepTile<LPC>::LINES) * ((SweepTile<LPC>::SEGS * seg_len + 2 * R) | 1) * 16;
-    if (PRE && seg_len <= kSpecMaxSteps && b.p[0].scand) {
-        if (EPPM_SWEEP_TILE && lds <= 32 * 1024) launch_sweep_t<R, LPC, true, PRE>(b, lut, seg_len, dir, g, s);
+    if (PRE && f.pre && b.p[0].scand) {
+        if (f.tile) launch_sweep_t<R, LPC, true, PRE>(b, lut, seg_len, dir, g, s);
         else launch_sweep_t<R, LPC, false, PRE>(b, lut, seg_len, dir, g, s);
         return;
     }
-    if (EPPM_SWEEP_TILE && lds <= 32 * 1024) launch_sweep_t<R, LPC, true>(b, lut, seg_len, dir, g, s);
+    if (f.tile) launch_sweep_t<R, LPC, true>(b, lut, seg_len, dir, g, s);
     else launch_sweep_t<R, LPC, false>(b, lut, seg_len, dir, g, s);
+}
+
+#ifdef EPPM_TOL
+constexpr int kLpc9Small = EPPM_LPC9;          // one dealing of the samples (coop_chunk): small launches only fetch up front
+#else
+constexpr int kLpc9Small = 2 * EPPM_LPC9;
+#endif
+SweepForm pm_sweep_form(int w, int h, int R, int seg_len, int dir, int problems, int npairs)
+{
+    SweepForm f = {0, false, false, false};
+    if (!(R == 9 || R == 17) || seg_len < 1) return f;
+    f.lpc = EPPM_LPC17;
+    if (R == 9) {
+        // 16 lanes per chain, or twice as many for launches that cannot fill the chip (EPPM_LPC_SWITCH_WAVES)
+        const SweepGeom g(w, h, dir, seg_len);
+        const int chains = g.lines * g.nseg_pad() * problems * npairs;
+        f.small = chains * 16 / 64 < EPPM_LPC_SWITCH_WAVES;
+        f.lpc = f.small ? kLpc9Small : EPPM_LPC9;
+        f.pre = (EPPM_SWEEP_PRE >= (f.small ? 1 : 2)) && seg_len <= kSpecMaxSteps;
+    }
+    const int cpb = 256 / f.lpc, segs = (cpb >= 16) ? 4 : 2, lines = cpb / segs;           // SweepTile<LPC>
+    const size_t lds = (size_t)(R + 2 * lines) * ((segs * seg_len + 2 * R) | 1) * 16;
+    f.tile = EPPM_SWEEP_TILE && lds <= 32 * 1024;
+    return f;
 }
 
 bool launch_pm_sweep(PmBatch& b, const float* lut, int R, int seg_len, int dir, hipStream_t s, bool speculative)
@@ -666,19 +690,13 @@ bool launch_pm_sweep(PmBatch& b, const float* lut, int R, int seg_len, int dir, 
         else { launch_sweep_spec<17>(b, lut, R, dir, seg_len, g.nseg, s); launch_sweep_b<17, EPPM_LPC17_SPEC>(b, lut, seg_len, dir, g, s); }
         return true;
     }
+    const SweepForm f = pm_sweep_form(b.p[0].P.w, b.p[0].P.h, R, seg_len, dir, b.n, b.npairs);
     if (R == 9) {
-        // 16 lanes per chain, or twice as many for launches that cannot fill the chip (EPPM_LPC_SWITCH_WAVES)
-        const int chains = g.lines * g.nseg_pad() * b.n * b.npairs;
-#ifdef EPPM_TOL
-        constexpr int LPC_SMALL = EPPM_LPC9;          // one dealing of the samples (coop_chunk): small launches only fetch up front
-#else
-        constexpr int LPC_SMALL = 2 * EPPM_LPC9;
-#endif
-        if (chains * 16 / 64 < EPPM_LPC_SWITCH_WAVES) launch_sweep_r<9, LPC_SMALL, (EPPM_SWEEP_PRE >= 1)>(b, lut, seg_len, dir, g, s);
-        else launch_sweep_r<9, EPPM_LPC9, (EPPM_SWEEP_PRE >= 2)>(b, lut, seg_len, dir, g, s);
+        if (f.small) launch_sweep_r<9, kLpc9Small, (EPPM_SWEEP_PRE >= 1)>(b, lut, seg_len, dir, g, f, s);
+        else launch_sweep_r<9, EPPM_LPC9, (EPPM_SWEEP_PRE >= 2)>(b, lut, seg_len, dir, g, f, s);
         return true;
     }
-    if (R == 17) { launch_sweep_r<17, EPPM_LPC17>(b, lut, seg_len, dir, g, s); return true; }
+    if (R == 17) { launch_sweep_r<17, EPPM_LPC17>(b, lut, seg_len, dir, g, f, s); return true; }
     if (g.nseg > 1024) return false;   // eppm_create / the launchers validate sizes
     const int lpb = g.nseg < 256 ? 256 / g.nseg : 1;
     const int threads = ((g.nseg * lpb + 63) / 64) * 64;

@@ -13,8 +13,8 @@ namespace {
 struct DevState {
     float *lut_pm = nullptr, *lut_wmf = nullptr, *lut_blf = nullptr;
     int lut_R = -1;
-    void* scratch[7] = {nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr};
-    size_t scratch_bytes[7] = {0, 0, 0, 0, 0, 0, 0};
+    void* scratch[9] = {nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr};
+    size_t scratch_bytes[9] = {0, 0, 0, 0, 0, 0, 0, 0, 0};
     std::map<std::tuple<int, int, int, unsigned long long>, eppm_pm_rng*> rngs;
 };
 std::mutex g_mu;
@@ -75,6 +75,17 @@ int mk_planes(DevState* ds, PlanesH* out, const void* i1, const void* i2, const 
     return EPPM_OK;
 }
 int finish() { HIPCHK(hipGetLastError()); return EPPM_OK; }
+// the split refine's scratch of 36 costs per pixel (slot 8) under the test switch "c2f_force_split", else NULL: the stage launchers
+// of the candidate refine have no such plane of their own and never split
+int split_scratch(DevState* ds, int w, int h, float** out)
+{
+    *out = nullptr;
+    if (!opt_force_split()) return EPPM_OK;
+    void* p = nullptr;
+    CHK(get_scratch(ds, (size_t)w * h * 36 * 4, &p, 8));
+    *out = (float*)p;
+    return EPPM_OK;
+}
 // device-to-device copy on the launcher stream whose failure reaches eppm_launcher_status()
 int copy_d2d(void* dst, const void* src, size_t bytes)
 {
@@ -224,6 +235,17 @@ extern "C" int eppm_pm_random_search(eppm_pm_rng* r, float* d_cost, eppm_short2*
     PlanesH P;
     CHK(mk_planes(ds, &P, i1, i2, c1, c2, w, h, img_pitch, census_pitch));
     b.p[0] = mk_problem(P, d_cost, (int16_t*)d_nnf, nullptr, r, 0);
+    if (opt_rand_table() == 2 && (g_prm.patch_r == 9 || g_prm.patch_r == 17)) {
+        // test switch: this launch reads its numbers drawn ahead, as a context's searches do -- one launch's table (slot 7) drawn from
+        // the generator's current states, which k_pm_rand_table leaves where the streaming search would have left them
+        void* tab = nullptr;
+        CHK(get_scratch(ds, (size_t)r->gx * r->gy * 512 * r->G * sizeof(int16_t), &tab, 7));
+        PmRngDev d = r->dev();
+        launch_pm_rand_table(d, r->work[0][r->cur[0]], (int16_t*)tab, r->G, g_stream);
+        d.rand_tab = (const int16_t*)tab;
+        launch_pm_random_search(b, d, ds->lut_pm, g_prm.patch_r, g_prm.search_range, g_prm.num_guess, g_stream);
+        return finish();
+    }
     search(b, r, ds->lut_pm, g_prm, g_stream);
     return finish();
 }
@@ -392,7 +414,9 @@ extern "C" void baoCudaBLFCostFilterRefine(eppm_float2* d_flow_vec, eppm_uchar4*
     PlanesH P;
     g_launch_status = mk_planes(ds, &P, d_img1, d_img2, d_census1, d_census2, w, h, img_pitch, census_pitch);
     if (g_launch_status != EPPM_OK) return;
-    launch_c2f_refine(P, (float*)d_flow_vec, ds->lut_pm, g_prm.patch_r, nullptr, g_stream, kOnePair, opt_no_split() != 0);
+    float* cost9 = nullptr;
+    if ((g_launch_status = split_scratch(ds, w, h, &cost9)) != EPPM_OK) return;
+    launch_c2f_refine(P, (float*)d_flow_vec, ds->lut_pm, g_prm.patch_r, cost9, g_stream, kOnePair, opt_no_split() != 0);
     g_launch_status = finish();
 }
 
@@ -408,7 +432,9 @@ extern "C" void baoCudaBLF_C2F(eppm_float2** pFlowPyr, eppm_uchar4** pImgPyr1, e
     PlanesH P;
     g_launch_status = mk_planes(ds, &P, pImgPyr1[l], pImgPyr2[l], pCensusPyr1[l], pCensusPyr2[l], arrW[l], arrH[l], arrPitchUchar4[l], arrPitchUchar1[l]);
     if (g_launch_status != EPPM_OK) return;
-    launch_c2f_refine(P, (float*)pFlowPyr[l], ds->lut_pm, g_prm.patch_r, nullptr, g_stream, kOnePair, opt_no_split() != 0);                       // refine :1086
+    float* cost9 = nullptr;
+    if ((g_launch_status = split_scratch(ds, arrW[l], arrH[l], &cost9)) != EPPM_OK) return;
+    launch_c2f_refine(P, (float*)pFlowPyr[l], ds->lut_pm, g_prm.patch_r, cost9, g_stream, kOnePair, opt_no_split() != 0);                         // refine :1086
     g_launch_status = finish();
 }
 

@@ -8,6 +8,7 @@ using namespace eppm;
 std::atomic<int> g_opt_rand_table{1};
 std::atomic<int> g_opt_sweep_spec{-1};
 std::atomic<int> g_opt_no_split{0};
+std::atomic<int> g_opt_force_split{0};
 
 static int probe(const float* x, float* y, int n, int which)
 {
@@ -24,6 +25,7 @@ extern "C" int eppm_test_set_option(const char* name, int value)
 {
     if (!name) return set_err(EPPM_ERR_ARG, "eppm_test_set_option: NULL name");
     if (!strcmp(name, "c2f_no_split")) { g_opt_no_split.store(value); return EPPM_OK; }
+    if (!strcmp(name, "c2f_force_split")) { g_opt_force_split.store(value); return EPPM_OK; }
     if (!strcmp(name, "sweep_spec")) { g_opt_sweep_spec.store(value); return EPPM_OK; }
     if (!strcmp(name, "rand_table")) { g_opt_rand_table.store(value); return EPPM_OK; }
     return set_err(EPPM_ERR_ARG, "eppm_test_set_option: unknown option '%s'", name);
@@ -33,6 +35,38 @@ extern "C" int eppm_probe_c2f_window(int patch_r, int* span_x, int* span_y)
     if (!span_x || !span_y) return set_err(EPPM_ERR_ARG, "eppm_probe_c2f_window: NULL argument");
     if (!c2f_window_span(patch_r, span_x, span_y)) return set_err(EPPM_ERR_ARG, "no LDS-window refine kernel for patch_r %d", patch_r);
     return EPPM_OK;
+}
+// the launchers' own decision functions (eppm_internal.h: EPPM_DECISION), on the host alone
+extern "C" int eppm_probe_dispatch(const char* stage, const int* args, int nargs, int* out, int nout)
+{
+    if (!stage || !args || !out) return set_err(EPPM_ERR_ARG, "eppm_probe_dispatch: NULL argument");
+    auto shape = [&](int want_args, int want_out) -> int {
+        if (nargs == want_args && nout == want_out && args[0] >= 1 && args[1] >= 1) return EPPM_OK;
+        return set_err(EPPM_ERR_ARG, "eppm_probe_dispatch: '%s' takes %d arguments (w, h >= 1 first) and gives %d results", stage, want_args, want_out);
+    };
+    if (!strcmp(stage, "smoothing")) {          // w, h, npairs -> pixels per lane
+        CHK(shape(3, 1));
+        out[0] = flow_blf_pixels_per_lane(args[0], args[1], args[2]);
+        return EPPM_OK;
+    }
+    if (!strcmp(stage, "refine")) {             // w, h, R, npairs, no_split -> split factor
+        CHK(shape(5, 1));
+        out[0] = c2f_refine_split_factor(args[0], args[1], args[2], args[3], args[4] != 0);
+        return EPPM_OK;
+    }
+    if (!strcmp(stage, "search")) {             // w, h, R, problems, npairs, table -> rows per workgroup
+        CHK(shape(6, 1));
+        out[0] = pm_search_rows(args[0], args[1], args[2], args[3], args[4], args[5] != 0);
+        return EPPM_OK;
+    }
+    if (!strcmp(stage, "sweep")) {              // w, h, R, seg_len, dir, problems, npairs -> lanes per chain, up-front fetch, source tile in LDS
+        CHK(shape(7, 3));
+        if (args[3] < 1) return set_err(EPPM_ERR_ARG, "eppm_probe_dispatch: seg_len %d", args[3]);
+        const SweepForm f = pm_sweep_form(args[0], args[1], args[2], args[3], args[4], args[5], args[6]);
+        out[0] = f.lpc; out[1] = f.pre; out[2] = f.tile;
+        return EPPM_OK;
+    }
+    return set_err(EPPM_ERR_ARG, "eppm_probe_dispatch: unknown stage '%s'", stage);
 }
 extern "C" int eppm_probe_fast_exp(const float* x, float* y, int n) { return probe(x, y, n, 0); }
 extern "C" int eppm_probe_div_const(const float* x, float* y, int n, int which) { return probe(x, y, n, 1 + which); }

@@ -8,7 +8,7 @@ import ctypes as C
 
 import numpy as np
 
-from ._lib import CParams, check, check_launcher, lib
+from ._lib import CParams, check, check_launcher, lib, probe_dispatch  # noqa: F401
 from .api import float2, short2, uchar4
 
 

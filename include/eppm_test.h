@@ -23,17 +23,29 @@ extern "C" {
 /* switches with which the parity tests steer launches onto a specific kernel variant (a host program never needs them;
  * every variant computes the same bits).  A call sets the DEFAULT that contexts created afterwards copy, and what the context-less stage
  * launchers below read; a context that exists already is not affected.  "c2f_no_split" = 1: the candidate refine is never split over
- * several workgroups per tile, so that small images run the LDS-window kernels too.  "sweep_spec": -1 (default) the sweeps of PatchMatch
+ * several workgroups per tile, so that small images run the LDS-window kernels too.  "c2f_force_split" = 1: the context-less stage launchers
+ * of the candidate refine (baoCudaBLFCostFilterRefine, baoCudaBLF_C2F), which otherwise never split, bring the scratch of 36 costs per
+ * pixel and split wherever the library's decision (eppm_probe_dispatch "refine") says so; "c2f_no_split" still wins.  "sweep_spec": -1 (default) the sweeps of PatchMatch
  * iterations >= 2 (the third on) run in the speculative two-launch form when a launch covers at least 100 000 pixels (two 1024x436 pairs,
  * one 1920x1080 pair), 0 never, 1 always (also in eppm_pm_seg_propagate, which otherwise runs the classic form), 2 always and without
  * the work list (phase B walks every chain), 3 always and in the merged form (one phase A for the four sweeps of an iteration, the form the
  * library takes by itself from the sixth iteration on -- from the eighth on problems of more than 65 536 pixels, i.e. the quarter-resolution
  * level of 1920x1080 and 3840x2160 pairs).  "rand_table": 1 (default) a context's random searches read numbers drawn ahead per geometry,
- * 0 they draw while they search -- the form a context takes by itself when the table would exceed 512 MB. */
+ * 0 they draw while they search -- the form a context takes by itself when the table would exceed 512 MB; 2: as 1, and the stand-alone
+ * eppm_pm_random_search, which otherwise draws while it searches, reads its launch's numbers drawn ahead as well (radius 9 and 17). */
 int  eppm_test_set_option(const char* name, int value);
 /* admissible spread (max - min, pixels) of a 16x16 tile's candidate centres for which the LDS-window refine kernels stage the
  * target window; wider tiles take the per-access path inside the same launch (patch_r 9 or 17) */
 int  eppm_probe_c2f_window(int patch_r, int* span_x, int* span_y);
+/* What the launchers decide by the size of a launch, answered by the functions the launchers themselves ask; pure host code, no GPU
+ * needed.  stage, args -> out:
+ *   "smoothing"  w, h, npairs                            -> pixels per lane: 1 (k_flow_blf<1>) or 2 (k_flow_blf<2>)
+ *   "refine"     w, h, patch_r, npairs, no_split         -> workgroups per tile of the candidate refine: 0 (no split), 3 or 4
+ *   "search"     w, h, patch_r, problems, npairs, table  -> rows of a 16x16 block per workgroup: 4 (quarter block) or 2 (eighth block)
+ *   "sweep"      w, h, patch_r, seg_len, dir, problems, npairs -> classic sweep: lanes per chain (0: generic kernel), up-front fetch
+ *                                                           (given an evaluation cache), source tile in LDS (0: the sweep gathers)
+ * problems = directions per pair in the launch (1 or 2).  EPPM_ERR_ARG for another stage or argument count. */
+int  eppm_probe_dispatch(const char* stage, const int* args, int nargs, int* out, int nout);
 /* device-side arithmetic probes (parity of the shared float formulas): y[i] = f(x[i]) for n host floats */
 int  eppm_probe_fast_exp(const float* x, float* y, int n);
 int  eppm_probe_div_const(const float* x, float* y, int n, int which); /* 0: /(.1f*.1f) 1: /(.02f*.02f) 2: unorm8 (x = 0..255) */

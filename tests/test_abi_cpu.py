@@ -58,7 +58,7 @@ def test_test_hooks_live_in_the_test_library_only():
     assert "HOOKED = rng_tables context launchers_ref_abi" in mk
     assert "OBJS_T = $(filter-out $(HOOKED:%=$(OBJ)/%.o),$(OBJS)) $(HOOKED:%=$(OBJ)/%_test.o) $(OBJ)/test_hooks.o $(OBJ)/k_probe.o" in mk
     csrc = os.path.join(ROOT, "eppm_amd", "csrc")            # the switches are read where the Makefile says, and nowhere else
-    readers = {f[:-4] for f in os.listdir(csrc) if f.endswith(".cpp") and f != "test_hooks.cpp" and re.search(r"\bopt_(rand_table|sweep_spec|no_split)\(\)", open(os.path.join(csrc, f)).read())}
+    readers = {f[:-4] for f in os.listdir(csrc) if f.endswith(".cpp") and f != "test_hooks.cpp" and re.search(r"\bopt_(rand_table|sweep_spec|no_split|force_split)\(\)", open(os.path.join(csrc, f)).read())}
     assert readers == {"rng_tables", "context", "launchers_ref_abi"}, readers
     assert eppm_amd.lib()._name == eppm_amd.lib_path("test")                   # what the pytest process itself computes with
     # the tolerance library has a test build of the same kind (tests/test_tolerance_stages_gpu.py): neither product library exports a hook,

@@ -236,98 +236,111 @@ def test_c2f(S, O, crop_stages):
     eq(S.c2f_refine(fl, P1), O.c2f_refine(fl, st["img1_L1"], st["img2_L1"], st["cen1_L1"], st["cen2_L1"]), "refine with unknown flow")
 
 
+def refine_battery(S, O, planes, R, full=None, extras=False):
+    """The flows with which the candidate refine is compared with the oracle at patch radius R on `planes` (img1, img2, census1, census2):
+    constant, tiles at the exact admissible spread of the LDS-window kernels, one below and one past it, per-pixel random jumps, and noisy
+    flow.  full (default: at radius 9): also both signs and the mixed pairs of the spread, targets far outside the image (window rows
+    and columns clamped at load) and unknown vectors with one fully unknown tile.  extras: ragged sizes and NaN costs on planes of
+    their own.  Shared by test_c2f_refine_window_and_fallback_paths (window kernels) and tests/test_variants_gpu.py (split path)."""
+    import ctypes as C
+    import eppm_amd
+    from eppm_amd import lib
+    i1, i2, c1, c2 = planes
+    P0 = S.PlaneSet(i1, i2, c1, c2)
+    h, w = i1.shape
+    rng = np.random.default_rng(21 if R == 9 else 2117)
+    full = (R == 9) if full is None else full
+    op = O.default_params(patch_r=R)
+    S.set_params(eppm_amd.Params(patch_r=R))
+    try:
+        def run(fx, fy, what):
+            f = np.zeros((h, w), O.float2)
+            f["x"], f["y"] = np.asarray(fx).astype(np.float32), np.asarray(fy).astype(np.float32)
+            eq(S.c2f_refine(f, P0), O.c2f_refine(f, i1, i2, c1, c2, op), "R=%d %dx%d %s" % (R, w, h, what))
+
+        z = np.zeros((h, w))
+        if full:
+            run(z + 3.7, z - 2.2, "constant flow (coherent everywhere)")
+        # The admissible spread of a tile's candidate centres (eppm_probe_c2f_window).  Shifting the LAST column (row) of every
+        # 16x16 tile by d makes the spread exactly 15 + d: one below the limit, at the limit (the window's last column / row is
+        # read), and one past it (fallback).  An off-by-one here reads a texel of the next window row: caught bit for bit.
+        sx, sy = C.c_int(), C.c_int()
+        spreads = ((-1, -1), (0, 0), (1, 1), (0, -40), (-40, 0)) + (((1, -40), (-40, 1)) if full else ())
+        if R in (9, 17):
+            assert lib().eppm_probe_c2f_window(R, C.byref(sx), C.byref(sy)) == 0
+        else:
+            spreads = ()                                      # the generic kernel has no window
+        for dxs, dys in spreads:
+            fx, fy = z.copy(), z.copy()
+            fx[:, 15::16] = sx.value - 15 + dxs
+            fy[15::16, :] = sy.value - 15 + dys
+            run(fx, fy, "centre spread = limit %+d (x), limit %+d (y)" % (dxs, dys))
+            if full:
+                fx, fy = z.copy(), z.copy()                   # the same with the first column / row pulled the other way
+                fx[:, 0::16] = -(sx.value - 15 + dxs)
+                fy[0::16, :] = -(sy.value - 15 + dys)
+                run(fx, fy, "centre spread = limit %+d (x), limit %+d (y), negative side" % (dxs, dys))
+        if not full:
+            run(z + 2.0, z - 1.0, "constant flow")
+        jump = 40 if R == 9 else 30
+        run(rng.integers(-jump, jump + 1, (h, w)), rng.integers(-jump, jump + 1, (h, w)), "random jumps (incoherent)")
+        if full:
+            run(z - 300.0, z + 250.0, "targets far outside the image")
+            fx, fy = rng.normal(0, 1.5, (h, w)) + 5, rng.normal(0, 1.5, (h, w)) - 4
+            m = rng.random((h, w)) < 0.1
+            fx[m] = 1e10
+            fy[m] = 1e10
+            fx[:16, :16] = 1e10            # a tile without any known pixel
+            fy[:16, :16] = 1e10
+            run(fx, fy, "noisy flow with unknown vectors")
+        else:
+            run(rng.normal(0, 2.5, (h, w)) + 6, rng.normal(0, 2.5, (h, w)) - 3, "noisy flow")
+        if not extras:
+            return
+        # ragged sizes (no dimension a multiple of 16, images smaller than a window): tiles cut by the image edge, windows
+        # clamped on every side
+        for (hh, ww) in ((77, 101), (33, 250), (130, 47), (17, 19)):
+            a = np.zeros((hh, ww), O.uchar4)
+            b = np.zeros((hh, ww), O.uchar4)
+            for ch in ("x", "y", "z"):
+                base = rng.integers(0, 256, (hh, ww))
+                a[ch] = base
+                b[ch] = np.roll(base, (2, -3), axis=(0, 1))
+            ca, cb = O.census(a), O.census(b)
+            Pr = S.PlaneSet(a, b, ca, cb)
+            f = np.zeros((hh, ww), O.float2)
+            f["x"] = (rng.normal(0, 2.0, (hh, ww)) - 3).astype(np.float32)
+            f["y"] = (rng.normal(0, 2.0, (hh, ww)) + 2).astype(np.float32)
+            eq(S.c2f_refine(f, Pr), O.c2f_refine(f, a, b, ca, cb, op), "R=%d ragged %dx%d" % (R, ww, hh))
+        # NaN costs (black source, white target: every range weight underflows to 0, cost = 0/0): the nested __min and the strict <
+        # of the candidate loop must treat them as the reference's expressions do
+        a = np.zeros((64, 96), O.uchar4)
+        b = np.zeros((64, 96), O.uchar4)
+        for ch in ("x", "y", "z"):
+            b[ch] = 255
+        b["x"][20:40, 30:60] = 0          # a patch where some candidates do get finite costs
+        b["y"][20:40, 30:60] = 0
+        b["z"][20:40, 30:60] = 0
+        ca, cb = O.census(a), O.census(b)
+        f = np.zeros((64, 96), O.float2)
+        f["x"] = rng.integers(-2, 3, (64, 96)).astype(np.float32)
+        f["y"] = rng.integers(-2, 3, (64, 96)).astype(np.float32)
+        eq(S.c2f_refine(f, S.PlaneSet(a, b, ca, cb)), O.c2f_refine(f, a, b, ca, cb, op), "R=%d NaN costs" % R)
+    finally:
+        S.set_params(None)
+
+
 def test_c2f_refine_window_and_fallback_paths(S, O, crop_stages):
     """k_c2f_refine_win stages the target window of a tile in LDS when the tile's candidate centres are coherent and falls back
     to per-access gathers otherwise.  Flows that exercise both inside one launch: constant, tiles at the exact admissible
     spread (33 x 25) and one past it, per-pixel random jumps, vectors pointing far outside the image (window rows and columns
-    clamped at load), and unknown vectors mixed in."""
+    clamped at load), and unknown vectors mixed in; ragged sizes and NaN costs (refine_battery).  The stage launcher has no scratch
+    for the split path, so every launch here takes the window kernels; tests/test_variants_gpu.py runs the same battery split."""
     st = crop_stages
-    i1, i2, c1, c2 = st["img1_L0"], st["img2_L0"], st["cen1_L0"], st["cen2_L0"]
-    P0 = S.PlaneSet(i1, i2, c1, c2)
-    h, w = i1.shape
-    rng = np.random.default_rng(21)
-
-    def run(fx, fy, what):
-        f = np.zeros((h, w), O.float2)
-        f["x"], f["y"] = fx.astype(np.float32), fy.astype(np.float32)
-        eq(S.c2f_refine(f, P0), O.c2f_refine(f, i1, i2, c1, c2), what)
-
-    z = np.zeros((h, w))
-    run(z + 3.7, z - 2.2, "constant flow (coherent everywhere)")
-    # The admissible spread of a tile's candidate centres (eppm_probe_c2f_window).  Shifting the LAST column (row) of every
-    # 16x16 tile by d makes the spread exactly 15 + d: one below the limit, at the limit (the window's last column / row is
-    # read), and one past it (fallback).  An off-by-one here reads a texel of the next window row: caught bit for bit.
-    import ctypes as C
-    from eppm_amd import lib
-    sx, sy = C.c_int(), C.c_int()
-    assert lib().eppm_probe_c2f_window(9, C.byref(sx), C.byref(sy)) == 0
-    for dxs, dys in ((-1, -1), (0, 0), (1, 1), (0, -40), (-40, 0), (1, -40), (-40, 1)):
-        fx, fy = z.copy(), z.copy()
-        fx[:, 15::16] = sx.value - 15 + dxs
-        fy[15::16, :] = sy.value - 15 + dys
-        run(fx, fy, "centre spread = limit %+d (x), limit %+d (y)" % (dxs, dys))
-        fx, fy = z.copy(), z.copy()                   # the same with the first column / row pulled the other way
-        fx[:, 0::16] = -(sx.value - 15 + dxs)
-        fy[0::16, :] = -(sy.value - 15 + dys)
-        run(fx, fy, "centre spread = limit %+d (x), limit %+d (y), negative side" % (dxs, dys))
-    run(rng.integers(-40, 41, (h, w)), rng.integers(-40, 41, (h, w)), "random jumps (incoherent)")
-    run(z - 300.0, z + 250.0, "targets far outside the image")
-    fx, fy = rng.normal(0, 1.5, (h, w)) + 5, rng.normal(0, 1.5, (h, w)) - 4
-    m = rng.random((h, w)) < 0.1
-    fx[m] = 1e10
-    fy[m] = 1e10
-    fx[:16, :16] = 1e10            # a tile without any known pixel
-    fy[:16, :16] = 1e10
-    run(fx, fy, "noisy flow with unknown vectors")
-    # ragged sizes (no dimension a multiple of 16, images smaller than a window): tiles cut by the image edge, windows
-    # clamped on every side
-    for (hh, ww) in ((77, 101), (33, 250), (130, 47), (17, 19)):
-        a = np.zeros((hh, ww), O.uchar4)
-        b = np.zeros((hh, ww), O.uchar4)
-        for ch in ("x", "y", "z"):
-            base = rng.integers(0, 256, (hh, ww))
-            a[ch] = base
-            b[ch] = np.roll(base, (2, -3), axis=(0, 1))
-        ca, cb = O.census(a), O.census(b)
-        Pr = S.PlaneSet(a, b, ca, cb)
-        f = np.zeros((hh, ww), O.float2)
-        f["x"] = (rng.normal(0, 2.0, (hh, ww)) - 3).astype(np.float32)
-        f["y"] = (rng.normal(0, 2.0, (hh, ww)) + 2).astype(np.float32)
-        eq(S.c2f_refine(f, Pr), O.c2f_refine(f, a, b, ca, cb), "ragged %dx%d" % (ww, hh))
-    # NaN costs (black source, white target: every range weight underflows to 0, cost = 0/0): the nested __min and the strict <
-    # of the candidate loop must treat them as the reference's expressions do
-    a = np.zeros((64, 96), O.uchar4)
-    b = np.zeros((64, 96), O.uchar4)
-    for ch in ("x", "y", "z"):
-        b[ch] = 255
-    b["x"][20:40, 30:60] = 0          # a patch where some candidates do get finite costs
-    b["y"][20:40, 30:60] = 0
-    b["z"][20:40, 30:60] = 0
-    ca, cb = O.census(a), O.census(b)
-    f = np.zeros((64, 96), O.float2)
-    f["x"] = rng.integers(-2, 3, (64, 96)).astype(np.float32)
-    f["y"] = rng.integers(-2, 3, (64, 96)).astype(np.float32)
-    eq(S.c2f_refine(f, S.PlaneSet(a, b, ca, cb)), O.c2f_refine(f, a, b, ca, cb), "NaN costs")
+    planes = st["img1_L0"], st["img2_L0"], st["cen1_L0"], st["cen2_L0"]
+    refine_battery(S, O, planes, 9, extras=True)
     # patch radius 17: k_c2f_refine_win4 (1024-thread workgroups, four pass groups, 80x72-texel window)
-    import eppm_amd
-    p17 = eppm_amd.Params(patch_r=17)
-    S.set_params(p17)
-    try:
-        assert lib().eppm_probe_c2f_window(17, C.byref(sx), C.byref(sy)) == 0
-        for dxs, dys in ((-1, -1), (0, 0), (1, 1), (0, -40), (-40, 0)):
-            fx, fy = z.copy(), z.copy()
-            fx[:, 15::16] = sx.value - 15 + dxs
-            fy[15::16, :] = sy.value - 15 + dys
-            f = np.zeros((h, w), O.float2)
-            f["x"], f["y"] = fx.astype(np.float32), fy.astype(np.float32)
-            eq(S.c2f_refine(f, P0), O.c2f_refine(f, i1, i2, c1, c2, O.default_params(patch_r=17)), "R=17 centre spread = limit %+d (x), %+d (y)" % (dxs, dys))
-        for fx, fy, what in ((z + 2.0, z - 1.0, "R=17 constant flow"), (rng.integers(-30, 31, (h, w)), rng.integers(-30, 31, (h, w)), "R=17 random jumps"),
-                             (rng.normal(0, 2.5, (h, w)) + 6, rng.normal(0, 2.5, (h, w)) - 3, "R=17 noisy flow")):
-            f = np.zeros((h, w), O.float2)
-            f["x"], f["y"] = fx.astype(np.float32), fy.astype(np.float32)
-            eq(S.c2f_refine(f, P0), O.c2f_refine(f, i1, i2, c1, c2, O.default_params(patch_r=17)), what)
-    finally:
-        S.set_params(None)
+    refine_battery(S, O, planes, 17)
 
 
 def test_end_to_end_crop(crop, crop_stages):

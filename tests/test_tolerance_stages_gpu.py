@@ -75,6 +75,20 @@ def test_patchmatch_launcher_and_optional_propagations_equal_the_oracle_variant(
     run_child("launcher", seconds=600)
 
 
+@pytest.mark.parametrize("stage,patch_r,group", [
+    ("search", 9, "above"), ("search", 9, "below"), ("search", 17, "above"), ("search", 17, "below"),
+    ("sweep", 9, "small"), ("sweep", 9, "large"), ("sweep", 9, "thin"), ("sweep", 9, "tall"),
+    ("sweep", 17, "small"), ("sweep", 17, "large"), ("sweep", 17, "thin"), ("sweep", 17, "tall"),
+])
+def test_size_dependent_variants_equal_the_oracle_variant(stage, patch_r, group):
+    """parts c and d of tests/test_variants_gpu.py on the tolerance library, whose search and sweep kernels are its own code: one search
+    launch on each side of the eighth-block boundary (numbers drawn ahead and drawn while searching, the random and the arbitrary
+    start field), and the classic sweep's four directions on small and large launches, strips, and both sides of the LDS tile's limit;
+    shapes from this library's own dispatch probe"""
+    out = run_child("variants", stage, patch_r, group, seconds=120)
+    assert out.count("case ") >= 1
+
+
 # ---- (b) ----
 
 def test_one_cost_one_bit_pattern_tolerance_library():

@@ -261,6 +261,29 @@ def part_launcher():
                 S.set_params(None)
 
 
+def variant_cases(stage, patch_r, group):
+    """the cases of tests/test_variants_gpu.py's parts c ("search") and d ("sweep") of one radius and group (the first word of their
+    names), built from THIS library's dispatch probe"""
+    import test_variants_cpu as V
+    cases = {"search": V.search_cases, "sweep": V.sweep_cases}[stage]()
+    return [c for c in cases if c[4] == int(patch_r) and c[0].split("_")[0] == group]
+
+
+def part_variants(stage, patch_r, group):
+    """every size-dependent variant of the search and the classic sweep (lanes per chain in this library: EPPM_LPC9 = 32 either way, the
+    small launches fetch up front) against the oracle variant (7, 1), every bit"""
+    import test_variants_gpu as G
+    from eppm_amd import stages as S
+    from oracle import oracle as O
+    cases = variant_cases(stage, patch_r, group)
+    assert cases
+    run = {"search": G.run_search_case, "sweep": G.run_sweep_case}[stage]
+    with tol_variant(*PM_VARIANT):
+        for case in cases:
+            run(S, O, case, variant=PM_VARIANT)
+            print("case", case[0], case[-1], "OK")
+
+
 # ---- (b) one cost, one bit pattern, whichever kernel wrote it (no oracle) ----
 
 TIE_CASES = [("crop_L1", dict()), ("flat11", dict()), ("flat12", dict()), ("flat13", dict(patch_r=17)), ("flat14", dict(patch_r=5, seg_len=7)),
@@ -630,7 +653,7 @@ def part_probes():
     e.close()
 
 
-PARTS = {"substages": part_substages, "arbitrary_nnf": part_arbitrary_nnf, "launcher": part_launcher, "tie_invariant": part_tie_invariant,
+PARTS = {"variants": part_variants, "substages": part_substages, "arbitrary_nnf": part_arbitrary_nnf, "launcher": part_launcher, "tie_invariant": part_tie_invariant,
          "refine": part_refine, "refine_launcher": part_refine_launcher, "context": part_context, "context_seeded": part_context_seeded,
          "probes": part_probes}
 
