@@ -206,15 +206,17 @@ void launch_fill_holes(int16_t* nnf_out, const int16_t* nnf_in, const uint32_t* 
                        hipStream_t s, Batch bt = kOnePair);
 void launch_nnf2flow(float* flow, int flow_pitch, const int16_t* nnf, int nnf_pitch, int w, int h, hipStream_t s, Batch bt = kOnePair);
 
-// ---- coarse to fine (k_c2f.hip) ----
+// ---- coarse to fine: flow up one level (k_c2f_resize.hip) ----
 void launch_resize_flow(float* out, int outH, int outW, const float* in, int h, int w, float ratio, float post_scale, hipStream_t s, Batch bt = kOnePair);
 void launch_mul_scalar(float* flow, float scale, int h, int w, hipStream_t s);
+// ---- coarse to fine: candidate refine (k_c2f_refine.hip, c2f_device.cuh) ----
 // workgroups per tile of the candidate refine: 0 (one launch, no scratch), or 3 / 4 (k_c2f_refine_tiled<R, 3 | 4> + k_c2f_select)
 EPPM_DECISION int c2f_refine_split_factor(int w, int h, int R, int npairs = 1, bool no_split = false);
 bool c2f_refine_wants_split(int w, int h, int R, int npairs = 1, bool no_split = false);      // c2f_refine_split_factor(..) != 0
 bool c2f_window_span(int R, int* span_x, int* span_y);          // test support: admissible centre spread of the LDS-window kernels
 // cost9: scratch of 36 floats per pixel for launches that c2f_refine_wants_split(), or NULL
 void launch_c2f_refine(const PlanesH& P, float* flow, const float* lut, int R, float* cost9, hipStream_t s, Batch bt = kOnePair, bool no_split = false);
+// ---- coarse to fine: joint-bilateral smoothing (k_flow_blf.hip) ----
 void launch_flow_blf(float* out, const float* in, const uint32_t* img, int ipitch, int w, int h, int flow_pitch,
                      const float* blf_lut, hipStream_t s, Batch bt = kOnePair);
 EPPM_DECISION int flow_blf_pixels_per_lane(int w, int h, int npairs = 1);      // of the smoothing: 2 (k_flow_blf<2>, large launches) or 1

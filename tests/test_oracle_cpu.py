@@ -271,7 +271,7 @@ def test_parallel_propagate_rule():
 
 def test_planefit_offsets():
     """The affine passes of the plane-fitting cost (kernel.cu:334-513) sample image 2 at
-    floor(((x+j + uu) + j*A) + i*B) in float.  x+j+uu is an integer M; the HIP refine kernel (k_c2f.hip, c2f_pass)
+    floor(((x+j + uu) + j*A) + i*B) in float.  x+j+uu is an integer M; the HIP refine kernel (c2f_device.cuh, c2f_pass)
     relies on floor(...) == M + floor(fl(fl(j*A) + fl(i*B))) for every M an image can produce, and on the y offset
     taking at most two consecutive values along a sample row.  Exhaustive over M for both instantiated radii."""
     f = np.float32
