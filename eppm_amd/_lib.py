@@ -55,6 +55,8 @@ SYMBOLS = [
     "eppm_track_step_frames", "eppm_tracker_get", "eppm_tracker_get_ended", "eppm_tracker_set", "eppm_track_step_host", "eppm_track_seeds_host",
     "eppm_push_image", "eppm_push_image_device", "eppm_set_temporal", "eppm_temporal_reset", "eppm_temporal_valid", "eppm_temporal_prior_host",
     "eppm_temporal_prior",
+    "eppm_batch_set_temporal", "eppm_batch_push_images", "eppm_batch_push_images_device", "eppm_batch_temporal_valid", "eppm_batch_temporal_reset",
+    "eppm_temporal_prior_batch",
 ]
 
 

@@ -171,6 +171,64 @@ def flow_sequence(frames, params=None, temporal=True, bidirectional=False):
     return out
 
 
+def _sequence_plan(lengths, slots):
+    """The schedule of flow_sequences, a pure function: clips of the given lengths (frames, >= 2 each) through min(slots, len(lengths))
+    slots.  Yields one list per step with one (clip, frame, new_clip, keep) per slot: frame `frame` of clip `clip` becomes the slot's image
+    2 at that step.  Step 0 is the set_data step (image 1 is the clip's frame 0, frame = 1); every later step is a push.  keep: the pair
+    the slot then holds is (frame - 1, frame) of `clip` and its flow is wanted.  A slot whose clip has ended takes the next clip of the
+    queue (frame 0 with new_clip set; the pair across the cut is not kept); a slot with nothing left is fed its last frame again."""
+    lengths = [int(n) for n in lengths]
+    if not lengths or min(lengths) < 2:
+        raise EppmError("flow_sequences: every clip needs at least two frames")
+    n = min(int(slots), len(lengths))
+    if n < 1:
+        raise EppmError("flow_sequences: at least one slot")
+    cur = [[k, 1] for k in range(n)]            # per slot: its clip and the frame that is its image 2
+    queue = list(range(n, len(lengths)))
+    yield [(k, 1, False, True) for k in range(n)]
+    while queue or any(f + 1 < lengths[c] for c, f in cur):
+        step = []
+        for slot in cur:
+            c, f = slot
+            if f + 1 < lengths[c]:
+                slot[1] = f + 1
+                step.append((c, f + 1, False, True))
+            elif queue:
+                slot[0], slot[1] = queue.pop(0), 0
+                step.append((slot[0], 0, True, False))
+            else:
+                step.append((c, f, False, False))
+        yield step
+
+
+def flow_sequences(clips, slots=8, params=None, temporal=True, bidirectional=False):
+    """flow_sequence for many clips at once: any number of clips of one frame size and of any lengths (two frames at least) through ONE
+    batch context of min(slots, len(clips)) slots, every slot advanced by one frame per step (push_frames; temporal mode per slot unless
+    temporal=False).  A slot whose clip ends takes the next clip in the queue.  Returns one list of flows per clip, in the order given, each
+    what flow_sequence(clip) returns."""
+    clips = [[np.ascontiguousarray(f, np.uint8) for f in clip] for clip in clips]
+    plan = _sequence_plan([len(c) for c in clips], slots)
+    h, w, _ = clips[0][0].shape
+    out = [[] for _ in clips]
+    e = None
+    try:
+        for t, step in enumerate(plan):
+            if t == 0:
+                e = EPPMBatch(h, w, len(step), params=params)
+                e.set_temporal(temporal)
+                e.set_data([(clips[c][0], clips[c][1]) for c, _, _, _ in step])
+            else:
+                e.push_frames([clips[c][f] for c, f, _, _ in step], [cut for _, _, cut, _ in step])
+            res = e.compute_flow_bidirectional() if bidirectional else e.compute_flow()
+            for (c, _, _, keep), r in zip(step, res):
+                if keep:
+                    out[c].append(r)
+    finally:
+        if e is not None:
+            e.close()
+    return out
+
+
 def _track_collect(out, trk):
     """one step's ended and live tracks into track_sequence's dictionary"""
     e_ids, _, _, why, _ = trk.ended()
@@ -515,6 +573,43 @@ class EPPMBatch:
         check(lib().eppm_batch_set_images_device(self._ctx, len(d1), self._ptrs(list(d1)), self._ptrs(list(d2)), C.c_size_t(pitch)),
               "eppm_batch_set_images_device")
         self.n = len(d1)
+
+    # -- batch streaming: one clip per slot ----------------------------------
+    @staticmethod
+    def _cuts(new_clip, n):
+        if new_clip is None:
+            return None
+        if len(new_clip) != n:
+            raise EppmError("new_clip: one flag per frame")
+        return (C.c_uint8 * n)(*[int(bool(x)) for x in new_clip])
+
+    def push_frames(self, frames, new_clip=None):
+        """Slot k's image 2 becomes its image 1 and frames[k] its image 2 (eppm_batch_push_images): only the new frames are uploaded and
+        prepared.  One frame per active pair; new_clip[k] true: frames[k] is the first frame of another clip (the pair across the cut and
+        the clip's first pair are cold runs)."""
+        a = [np.ascontiguousarray(f, np.uint8) for f in frames]
+        for x in a:
+            if x.shape != (self.h, self.w, 3):
+                raise EppmError(f"push_frames: images must be ({self.h},{self.w},3) uint8")
+        check(lib().eppm_batch_push_images(self._ctx, len(a), self._ptrs(a), C.c_size_t(self.w * 3), self._cuts(new_clip, len(a))), "eppm_batch_push_images")
+
+    def push_frames_device(self, ptrs, pitch, new_clip=None):
+        """ptrs: one device address of an RGBA plane per active pair (eppm_batch_push_images_device)."""
+        ptrs = list(ptrs)
+        check(lib().eppm_batch_push_images_device(self._ctx, len(ptrs), self._ptrs(ptrs), C.c_size_t(pitch), self._cuts(new_clip, len(ptrs))),
+              "eppm_batch_push_images_device")
+
+    def set_temporal(self, on=True):
+        """Temporal mode per slot (eppm_batch_set_temporal): after push_frames a slot's compute starts PatchMatch from the slot's previous
+        pair moved along its own motion; set_data starts a new clip in every slot."""
+        check(lib().eppm_batch_set_temporal(self._ctx, int(bool(on))), "eppm_batch_set_temporal")
+
+    def temporal_valid(self, pair):
+        return bool(lib().eppm_batch_temporal_valid(self._ctx, int(pair)))
+
+    def temporal_reset(self, pair=None):
+        """The slot's next compute is a cold run; pair=None: every slot's (eppm_batch_temporal_reset)."""
+        check(lib().eppm_batch_temporal_reset(self._ctx, -1 if pair is None else int(pair)), "eppm_batch_temporal_reset")
 
     def _outs(self, out=None):
         if out is not None:

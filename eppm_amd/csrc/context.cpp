@@ -102,6 +102,7 @@ static int ctx_alloc(eppm_ctx* c)
     CHK(shared_luts(c->device, c->prm.patch_r, &c->lut_pm, &c->lut_wmf, &c->lut_blf));
     c->out_u.assign(c->npairs, nullptr);
     c->out_v.assign(c->npairs, nullptr);
+    for (auto* v : {&c->tmp_snap, &c->tmp_valid, &c->tmp_seeded, &c->tmp_cut}) v->assign(c->npairs, 0);
     return EPPM_OK;
 }
 
@@ -232,11 +233,11 @@ extern "C" int eppm_batch_get_plane(eppm_ctx* c, int pair, const char* name, int
         pstride = c->bwd_stride;
     }
     else if (level == L && (n == "prior1" || n == "prior2" || n == "nnf_init1" || n == "nnf_init2" || n == "cost_init1" || n == "cost_init2")) {
-        if (!c->tmp_seeded) return set_err(EPPM_ERR_STATE, "eppm_get_plane: '%s' needs a compute that started from a temporal prior", name);
+        if (!c->tmp_seeded[pair]) return set_err(EPPM_ERR_STATE, "eppm_get_plane: '%s' needs a compute that started from a temporal prior", name);
         src = n == "prior1" ? (void*)c->prior1 : n == "prior2" ? (void*)c->prior2 : n == "nnf_init1" ? (void*)c->nnf_init1 : n == "nnf_init2" ? (void*)c->nnf_init2
             : n == "cost_init1" ? (void*)c->cost_init1 : (void*)c->cost_init2;
         esz = 4; pitch = (size_t)w * 4;
-        pstride = 0;
+        pstride = c->tmp_stride;
     }
     else return set_err(EPPM_ERR_ARG, "eppm_get_plane: unknown plane '%s' at level %d", name, level);
     if (dst_bytes < (size_t)w * h * esz) return set_err(EPPM_ERR_ARG, "eppm_get_plane: dst too small");

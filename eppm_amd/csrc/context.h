@@ -3,6 +3,8 @@
 // No member may depend on EPPM_TEST_HOOKS: the test library links context_test.o against the product's other objects.
 #pragma once
 
+#include <algorithm>
+
 #include "api_internal.h"
 
 struct StageEv { const char* name; hipEvent_t a, b; };
@@ -81,19 +83,23 @@ struct eppm_ctx {
     int32_t *itp_fill1 = nullptr, *itp_fill2 = nullptr;
     uint8_t* itp_rgb = nullptr;
     uint8_t* h_itp = nullptr;
-    // Streaming mode (eppm_set_temporal; single-pair contexts only): its own allocation, made by the first compute
-    // with the mode on.  Level-L planes, unpitched: the two displacement snapshots of the last compute (prev_fwd: the field nnf2flow
-    // converted, prev_bwd: the raw backward NNF), the two advected priors, the seeded start as the select kernel left it, and the landing
-    // keys of both directions (kTemporalNoKey between launches).
+    // Streaming mode (eppm_set_temporal / eppm_batch_set_temporal): its own allocation, made by the first compute
+    // with the mode on: npairs blocks tmp_stride bytes apart, one per slot (the members below are slot 0's).  Level-L planes, unpitched: the
+    // two displacement snapshots of the last compute (prev_fwd: the field nnf2flow converted, prev_bwd: the raw backward NNF), the two
+    // advected priors, the seeded start as the select kernel left it, and the landing keys of both directions (kTemporalNoKey between
+    // launches).  The state is per slot (npairs entries each; a single-pair context has one):
     bool temporal = false;
-    bool tmp_snap = false;              // the snapshots hold the last compute's pair, and no frame has been pushed since
-    bool tmp_valid = false;             // armed by a push that found such snapshots: the next compute starts from their prior
-    bool tmp_seeded = false;            // the last compute started from a prior: prior*, nnf_init*, cost_init* are its planes
+    std::vector<uint8_t> tmp_snap;      // the snapshots hold the last compute's pair of this slot's clip, and no frame has been pushed since
+    std::vector<uint8_t> tmp_valid;     // armed by a push that found such snapshots: the next compute starts the slot from their prior
+    std::vector<uint8_t> tmp_seeded;    // the slot's last compute started from a prior: prior*, nnf_init*, cost_init* are its planes
+    std::vector<uint8_t> tmp_cut;       // the slot's image 2 is the first frame of another clip: its pair leaves no snapshot
     char* tmp = nullptr;
-    size_t tmp_bytes = 0;
+    size_t tmp_bytes = 0, tmp_stride = 0;
     int16_t *prev_fwd = nullptr, *prev_bwd = nullptr, *prior1 = nullptr, *prior2 = nullptr, *nnf_init1 = nullptr, *nnf_init2 = nullptr;
     float *cost_init1 = nullptr, *cost_init2 = nullptr;
     int32_t* tmp_keys = nullptr;        // 2 x W[L]*H[L]
+    // every slot starts a new clip (set_images*, the mode switched off)
+    void tmp_drop() { std::fill(tmp_valid.begin(), tmp_valid.end(), 0); std::fill(tmp_snap.begin(), tmp_snap.end(), 0); std::fill(tmp_cut.begin(), tmp_cut.end(), 0); }
     int timing = 0;                     // 0 off, 1 every stage, 2 only the dominant kernel (the candidate refine)
     std::vector<StageEv> ev;
     std::vector<StageEv> ev_prep;

@@ -6,6 +6,7 @@
 using namespace eppm;
 
 // ---- temporal mode ----
+// one block per slot (context.h): 40 bytes per level-L pixel, every plane at a 256-byte aligned offset
 static int tmp_alloc(eppm_ctx* c)
 {
     if (c->tmp) return EPPM_OK;
@@ -15,27 +16,49 @@ static int tmp_alloc(eppm_ctx* c)
     for (int16_t** p : {&c->prev_fwd, &c->prev_bwd, &c->prior1, &c->prior2, &c->nnf_init1, &c->nnf_init2}) cv.plane(p, n2 * 4);
     for (float** p : {&c->cost_init1, &c->cost_init2}) cv.plane(p, n2 * 4);
     cv.plane(&c->tmp_keys, n2 * 4 * 2);                    // the keys of both directions
-    CHK(cv.alloc(&c->tmp, &c->tmp_bytes, cv.off, c->device, "temporal planes"));
-    launch_temporal_keys_init(c->tmp_keys, (int)(2 * n2), c->stream);
+    c->tmp_stride = cv.off;
+    CHK(cv.alloc(&c->tmp, &c->tmp_bytes, c->tmp_stride * c->npairs, c->device, "temporal planes"));
+    for (int k = 0; k < c->npairs; k++) launch_temporal_keys_init((int32_t*)((char*)c->tmp_keys + (size_t)k * c->tmp_stride), (int)(2 * n2), c->stream);
     HIPCHK(hipGetLastError());
     return EPPM_OK;
 }
 
+static int set_temporal(eppm_ctx* c, int on)
+{
+    c->temporal = on != 0;
+    if (!on) c->tmp_drop();
+    return EPPM_OK;
+}
 extern "C" int eppm_set_temporal(eppm_ctx* c, int on)
 {
     if (!c) return set_err(EPPM_ERR_ARG, "eppm_set_temporal: NULL ctx");
-    if (on && c->npairs != 1) return set_err(EPPM_ERR_ARG, "eppm_set_temporal: a batch context has no previous pair (its pairs run concurrently)");
-    c->temporal = on != 0;
-    if (!on) c->tmp_valid = c->tmp_snap = false;
-    return EPPM_OK;
+    if (on && c->npairs != 1) return set_err(EPPM_ERR_ARG, "eppm_set_temporal: a batch context streams through eppm_batch_set_temporal (one clip per slot)");
+    return set_temporal(c, on);
 }
 extern "C" int eppm_temporal_reset(eppm_ctx* c)
 {
     if (!c) return set_err(EPPM_ERR_ARG, "eppm_temporal_reset: NULL ctx");
-    c->tmp_valid = c->tmp_snap = false;
+    return eppm_batch_temporal_reset(c, 0);
+}
+extern "C" int eppm_temporal_valid(const eppm_ctx* c) { return eppm_batch_temporal_valid(c, 0); }
+
+// the batch forms: one clip per slot (include/eppm.h)
+extern "C" int eppm_batch_set_temporal(eppm_ctx* c, int on)
+{
+    if (!c) return set_err(EPPM_ERR_ARG, "eppm_batch_set_temporal: NULL ctx");
+    return set_temporal(c, on);
+}
+extern "C" int eppm_batch_temporal_reset(eppm_ctx* c, int pair)
+{
+    if (!c) return set_err(EPPM_ERR_ARG, "eppm_batch_temporal_reset: NULL ctx");
+    if (pair >= c->npairs) return set_err(EPPM_ERR_ARG, "eppm_batch_temporal_reset: pair %d, context holds %d", pair, c->npairs);
+    for (int k = pair < 0 ? 0 : pair; k < (pair < 0 ? c->npairs : pair + 1); k++) c->tmp_valid[k] = c->tmp_snap[k] = 0;
     return EPPM_OK;
 }
-extern "C" int eppm_temporal_valid(const eppm_ctx* c) { return c && c->temporal && c->tmp_valid ? 1 : 0; }
+extern "C" int eppm_batch_temporal_valid(const eppm_ctx* c, int pair)
+{
+    return c && pair >= 0 && pair < c->npairs && c->temporal && c->tmp_valid[pair] ? 1 : 0;
+}
 
 // ---- the post-PatchMatch branch (driver :237-289): outlier vote, weighted median, hole fill, NNF -> flow at the PatchMatch level, then
 // per level upsample, candidate refine, smoothing, then the final smoothing.  One direction of it: ----
@@ -44,7 +67,7 @@ struct Branch {
     float* cost;
     uint32_t* const* guide;         // the pyramid of the image the field is defined on
     bool swap, bwd, dominant;       // planes(): image 2 against image 1; stage names carry "_bwd"; the refine is timing mode 2's stage
-    int16_t* snapshot;              // not NULL: the converted field is kept as well (launch_nnf2flow_snapshot, single pair)
+    int16_t* snapshot;              // not NULL: the converted field of every pair is kept as well (launch_nnf2flow_snapshot), tmp_stride apart
     // level l is resized and refined in a[l] and smoothed into b[l]; the final smoothing writes level 0's plane that does not hold its input
     float *a[kMaxLevels], *b[kMaxLevels];
 };
@@ -74,7 +97,7 @@ static void branch_nnf2flow(eppm_ctx* c, Branch& d)
         std::swap(d.nnf, d.nnf_alt);
     launch_fill_holes(d.nnf_alt, d.nnf, d.guide[L], gp, lw, lh, lw, s, bt);                                  // driver :240
     std::swap(d.nnf, d.nnf_alt);
-    if (d.snapshot) launch_nnf2flow_snapshot(d.a[L], lw, d.snapshot, d.nnf, lw, lw, lh, s);
+    if (d.snapshot) launch_nnf2flow_snapshot(d.a[L], lw, d.snapshot, c->tmp_stride, d.nnf, lw, lw, lh, s, bt);
     else launch_nnf2flow(d.a[L], lw, d.nnf, lw, lw, lh, s, bt);                                              // driver :258
 }
 
@@ -124,21 +147,27 @@ static int compute_all(eppm_ctx* c)
     const Batch bt = c->bt();
     const int L = c->nl - 1, lw = c->W[L], lh = c->H[L];                // pm_layer, driver :219
 
-    // temporal mode: the snapshots of the previous pair of the clip, advected, seed this pair's PatchMatch; without them the run is cold
-    const bool tmode = c->temporal, seeded = tmode && c->tmp_valid;
-    c->tmp_seeded = false;
-    if (tmode) CHK(tmp_alloc(c));
-    if (seeded) {
-        TemporalArgs a;
-        a.prev[0] = c->prev_fwd; a.prior[0] = c->prior1; a.keys[0] = c->tmp_keys; a.step[0] = 1;
-        a.prev[1] = c->prev_bwd; a.prior[1] = c->prior2; a.keys[1] = c->tmp_keys + (size_t)lw * lh; a.step[1] = -1;
-        a.w = lw; a.h = lh; a.ndir = 2;
-        stage_begin(c, c->ev, "temporal_advect");
-        launch_temporal_splat(a, s);
-        launch_temporal_gather(a, s);
-        stage_end(c, c->ev);
+    // temporal mode: per slot, the snapshots of the previous pair of the slot's clip, advected, seed this pair's PatchMatch; a slot without
+    // them gets "no prior" everywhere, which leaves it a cold run's bits; no slot with them: the run is the cold one
+    const bool tmode = c->temporal;
+    bool seeded = false;
+    std::fill(c->tmp_seeded.begin(), c->tmp_seeded.end(), 0);
+    if (tmode) {
+        CHK(tmp_alloc(c));
+        TemporalArgs a{};
+        for (int k = 0; k < bt.n; k++)
+            if (c->tmp_valid[k]) { a.armed[k >> 5] |= 1u << (k & 31); seeded = true; }
+        if (seeded) {
+            a.prev[0] = c->prev_fwd; a.prior[0] = c->prior1; a.keys[0] = c->tmp_keys; a.step[0] = 1;
+            a.prev[1] = c->prev_bwd; a.prior[1] = c->prior2; a.keys[1] = c->tmp_keys + (size_t)lw * lh; a.step[1] = -1;
+            a.w = lw; a.h = lh; a.ndir = 2; a.nslots = bt.n; a.stride = c->tmp_stride;
+            stage_begin(c, c->ev, "temporal_advect");
+            launch_temporal_splat(a, s);
+            launch_temporal_gather(a, s);
+            stage_end(c, c->ev);
+        }
     }
-    c->tmp_valid = c->tmp_snap = false;
+    std::fill(c->tmp_snap.begin(), c->tmp_snap.end(), 0);
 
     const size_t pm_entry = c->ev.size();
     stage_begin(c, c->ev, "patchmatch");
@@ -157,6 +186,7 @@ static int compute_all(eppm_ctx* c)
             PmSeed sd;
             sd.prior[0] = c->prior1; sd.nnf_init[0] = c->nnf_init1; sd.cost_init[0] = c->cost_init1;
             sd.prior[1] = c->prior2; sd.nnf_init[1] = c->nnf_init2; sd.cost_init[1] = c->cost_init2;
+            sd.stride = c->tmp_stride;
             stage_begin(c, c->ev, "temporal_select");
             launch_pm_cost_select(b, sd, c->lut_pm, c->prm.patch_r, s);
             stage_end(c, c->ev);
@@ -164,7 +194,7 @@ static int compute_all(eppm_ctx* c)
         }
     }
     stage_end_at(c, c->ev, pm_entry);
-    if (tmode) launch_temporal_snapshot(c->prev_bwd, c->nnf2, lw, lw, lh, s);          // the raw backward NNF, before the left-right check
+    if (tmode) launch_temporal_snapshot(c->prev_bwd, c->tmp_stride, c->nnf2, lw, lw, lh, s, bt);     // the raw backward NNF, before the left-right check
 
     stage_begin(c, c->ev, "l2_post");
     launch_lr_check(c->nnf1, c->cost1, c->nnf2, lw, lh, lw, lw, s, bt);                                      // driver :233
@@ -176,8 +206,12 @@ static int compute_all(eppm_ctx* c)
     CHK(branch_c2f(c, d, keep_fwd));
     HIPCHK(hipGetLastError());
     c->have_flow = true;
-    c->tmp_snap = tmode;                // a prior is armed by the next push, not by another compute on this pair
-    c->tmp_seeded = seeded;
+    // a prior is armed by the next push, not by another compute on this pair; the pair across a cut leaves none
+    for (int k = 0; k < bt.n; k++) {
+        c->tmp_snap[k] = tmode && !c->tmp_cut[k];
+        c->tmp_seeded[k] = tmode && c->tmp_valid[k];
+    }
+    std::fill(c->tmp_valid.begin(), c->tmp_valid.end(), 0);
     return EPPM_OK;
 }
 

@@ -117,7 +117,7 @@ static int set_images_host_impl(eppm_ctx* c, int n, const uint8_t* const* rgb1, 
             CHK(upload_rgb(c, c->of_pair(c->d_rgb, k) + (size_t)f * img, f ? rgb2[k] : rgb1[k], row_stride, hold, k * 2 + f, &direct, &staged));
     CHK(upload_done(c, direct, staged));
     c->n_active = n;
-    c->tmp_valid = c->tmp_snap = false; // a new pair is a new clip
+    c->tmp_drop();                      // a new pair is a new clip, in every slot
     const int p0 = (int)(c->raw_pitch / 4);
     launch_rgb_to_rgba(c->raw1, p0, c->d_rgb, c->h, c->w, c->stream, c->bt());
     launch_rgb_to_rgba(c->raw2, p0, c->d_rgb + img, c->h, c->w, c->stream, c->bt());
@@ -160,7 +160,7 @@ static int set_images_device(eppm_ctx* c, int n, const void* const* d1, const vo
         HIPCHK(hipMemcpy2DAsync(c->of_pair(c->raw2, k), c->raw_pitch, d2[k], pitch, (size_t)c->w * 4, c->h, hipMemcpyDeviceToDevice, c->stream));
     }
     c->n_active = n;
-    c->tmp_valid = c->tmp_snap = false;
+    c->tmp_drop();
     return prepare(c);
 }
 
@@ -178,19 +178,25 @@ extern "C" int eppm_batch_set_images_device(eppm_ctx* c, int n, const void* cons
 }
 
 // ---- frame push: image 2 becomes image 1 by exchanging the context's plane pointers -- the raw frame, every
-// pyramid level, census plane and texel plane of the old image 2 are kept --, the new frame becomes image 2 and is prepared alone ----
-static int push_check(eppm_ctx* c, const char* what)
+// pyramid level, census plane and texel plane of the old image 2 are kept --, the new frame becomes image 2 and is prepared alone.  The
+// pointers are pair 0's and every pair's planes lie at the same offsets of its slab, so one exchange serves every slot of a batch. ----
+static int push_check(eppm_ctx* c, const char* what, bool batch = false)
 {
-    if (c->npairs != 1) return set_err(EPPM_ERR_ARG, "%s: a batch context has no previous pair (its pairs run concurrently)", what);
+    if (!batch && c->npairs != 1) return set_err(EPPM_ERR_ARG, "%s: a batch context takes one frame per slot (eppm_batch_push_images)", what);
     if (!c->have_images) return set_err(EPPM_ERR_STATE, "%s: no pair set yet (eppm_set_images first)", what);
     if (c->flow_pending) return set_err(EPPM_ERR_STATE, "%s: an eppm_compute_begin is pending", what);
     return EPPM_OK;
 }
-// also arms the temporal prior: the snapshots describe the pair that ends in the new image 1 only directly after that pair's compute
-static void push_swap(eppm_ctx* c)
+// also arms the temporal prior, per slot: the snapshots describe the pair that ends in the new image 1 only directly after that pair's
+// compute, and only when the new frame continues the slot's clip (new_clip: NULL, or a byte per active pair)
+static void push_swap(eppm_ctx* c, const uint8_t* new_clip = nullptr)
 {
-    c->tmp_valid = c->temporal && c->tmp_snap;
-    c->tmp_snap = false;
+    for (int k = 0; k < c->n_active; k++) {
+        const bool cut = new_clip && new_clip[k];
+        c->tmp_valid[k] = c->temporal && c->tmp_snap[k] && !cut;
+        c->tmp_snap[k] = 0;
+        c->tmp_cut[k] = cut;
+    }
     std::swap(c->raw1, c->raw2);
     for (int l = 0; l < c->nl; l++) {
         std::swap(c->img1[l], c->img2[l]);
@@ -235,5 +241,50 @@ extern "C" int eppm_push_image_device(eppm_ctx* c, const void* d_rgba, size_t pi
     // into the old image 1's raw plane, which the swap then makes image 2's: a copy that fails leaves the context on its old pair
     HIPCHK(hipMemcpy2DAsync(c->raw1, c->raw_pitch, d_rgba, pitch, (size_t)c->w * 4, c->h, hipMemcpyDeviceToDevice, c->stream));
     push_swap(c);
+    return prepare(c, true);
+}
+
+// ---- the batch forms: one new frame per active pair, slot k's into its image-2 half of d_rgb (pinned staging slot 2k + 1) ----
+static int push_images_host_impl(eppm_ctx* c, int n, const uint8_t* const* rgb, size_t row_stride, const uint8_t* new_clip, HostHold& hold)
+{
+    if (row_stride < (size_t)c->w * 3) return set_err(EPPM_ERR_ARG, "eppm_batch_push_images: row_stride %zu < 3*w", row_stride);
+    for (int k = 0; k < n; k++)
+        if (!rgb[k]) return set_err(EPPM_ERR_ARG, "eppm_batch_push_images: NULL image");
+    HIPCHK(hipSetDevice(c->device));
+    const size_t img = (size_t)c->w * 3 * c->h;
+    bool staged = false, direct = false;
+    for (int k = 0; k < n; k++) CHK(upload_rgb(c, c->of_pair(c->d_rgb, k) + img, rgb[k], row_stride, hold, k * 2 + 1, &direct, &staged));
+    CHK(upload_done(c, direct, staged));
+    push_swap(c, new_clip);
+    launch_rgb_to_rgba(c->raw2, (int)(c->raw_pitch / 4), c->d_rgb + img, c->h, c->w, c->stream, c->bt());
+    const int r = prepare(c, true);
+    if (direct) HIPCHK(hipEventSynchronize(c->ev_h2d));
+    return r;
+}
+
+extern "C" int eppm_batch_push_images(eppm_ctx* c, int n, const uint8_t* const* rgb, size_t row_stride, const uint8_t* new_clip)
+{
+    if (!c || !rgb) return set_err(EPPM_ERR_ARG, "eppm_batch_push_images: NULL argument");
+    CHK(push_check(c, "eppm_batch_push_images", true));
+    if (n != c->n_active) return set_err(EPPM_ERR_ARG, "eppm_batch_push_images: %d frames, %d pairs are active", n, c->n_active);
+    HostHold hold;
+    const int r = push_images_host_impl(c, n, rgb, row_stride, new_clip, hold);
+    if (r != EPPM_OK && !hold.v.empty()) (void)hipStreamSynchronize(c->stream);
+    return r;
+}
+
+extern "C" int eppm_batch_push_images_device(eppm_ctx* c, int n, const void* const* d_rgba, size_t pitch, const uint8_t* new_clip)
+{
+    if (!c || !d_rgba) return set_err(EPPM_ERR_ARG, "eppm_batch_push_images_device: NULL argument");
+    CHK(push_check(c, "eppm_batch_push_images_device", true));
+    if (n != c->n_active) return set_err(EPPM_ERR_ARG, "eppm_batch_push_images_device: %d frames, %d pairs are active", n, c->n_active);
+    if (pitch < (size_t)c->w * 4 || (pitch & 3)) return set_err(EPPM_ERR_ARG, "eppm_batch_push_images_device: bad pitch %zu", pitch);
+    for (int k = 0; k < n; k++)
+        if (!d_rgba[k]) return set_err(EPPM_ERR_ARG, "eppm_batch_push_images_device: NULL image");
+    HIPCHK(hipSetDevice(c->device));
+    // into the old image 1's raw planes, which the swap then makes image 2's
+    for (int k = 0; k < n; k++)
+        HIPCHK(hipMemcpy2DAsync(c->of_pair(c->raw1, k), c->raw_pitch, d_rgba[k], pitch, (size_t)c->w * 4, c->h, hipMemcpyDeviceToDevice, c->stream));
+    push_swap(c, new_clip);
     return prepare(c, true);
 }

@@ -166,34 +166,44 @@ struct SweepForm { int lpc; bool small, pre, tile; };
 EPPM_DECISION SweepForm pm_sweep_form(int w, int h, int R, int seg_len, int dir, int problems, int npairs);
 
 // The seeded start of a streaming context's PatchMatch, after launch_pm_init_field + launch_pm_cost_field on the same
-// batch (one pair): the cost of every pixel's temporal prior (an absolute target like an NNF entry; a component <= kInvalid: none), and
-// the prior kept where it exists and its cost is STRICTLY lower than the random match's -- the cost-field kernel with a compare in front of
+// batch: the cost of every pixel's temporal prior (an absolute target like an NNF entry; a component <= kInvalid: none), and the prior
+// kept where it exists and its cost is STRICTLY lower than the random match's -- the cost-field kernel with a compare in front of
 // its store.  Writes nnf and cost, and copies of both into nnf_init / cost_init (unpitched; what eppm_get_plane shows); the evaluation
-// cache, the work lists and the generator states stay as launch_pm_init_field left them.
+// cache, the work lists and the generator states stay as launch_pm_init_field left them.  One launch covers every problem of the batch: the
+// planes below are slot 0's, slot k's lie k * stride bytes further.  A slot whose prior holds "none" everywhere keeps the cold start's bits.
 struct PmSeed {
-    const int16_t* prior[2];     // short2 per pixel of problem k, unpitched
+    const int16_t* prior[2];     // short2 per pixel of direction k, unpitched
     int16_t* nnf_init[2];
     float* cost_init[2];
+    size_t stride = 0;           // bytes between the slots' planes
 };
 void launch_pm_cost_select(const PmBatch& b, const PmSeed& seed, const float* lut, int R, hipStream_t s);
 
 // ---- temporal prior (k_temporal.hip; the rule itself: temporal.h) ----
-// Up to two directions per launch: prev[d] a displacement snapshot, prior[d] the advected targets, keys[d] w*h ints that hold
-// kTemporalNoKey between launches (launch_temporal_keys_init once; the gather pass restores them), step[d] +1 forward / -1 backward.
+// Up to two directions and nslots slots per launch: prev[d] a displacement snapshot, prior[d] the advected targets, keys[d] w*h ints that
+// hold kTemporalNoKey between launches (launch_temporal_keys_init once; the gather pass restores them), step[d] +1 forward / -1 backward.
+// The pointers are slot 0's; slot k's planes lie k * stride bytes further.  armed: bit k set = slot k has a snapshot to advect; a slot whose
+// bit is clear is skipped by the splat and gets "no prior" everywhere from the gather.  The flags travel in the kernel arguments, so
+// arming costs no copy, no allocation and no synchronisation.
+constexpr int kTemporalMaxSlots = 4096;      // eppm_create_batch's limit on npairs
 struct TemporalArgs {
     const int16_t* prev[2];
     int16_t* prior[2];
     int32_t* keys[2];
     int step[2];
     int w, h, ndir;
+    int nslots;
+    size_t stride;
+    uint32_t armed[kTemporalMaxSlots / 32];
 };
 void launch_temporal_keys_init(int32_t* keys, int n, hipStream_t s);
 void launch_temporal_splat(const TemporalArgs& a, hipStream_t s);
 void launch_temporal_gather(const TemporalArgs& a, hipStream_t s);
-// prev <- the displacements of a field of stored matches (nnf_pitch in short2 elements)
-void launch_temporal_snapshot(int16_t* prev, const int16_t* nnf, int nnf_pitch, int w, int h, hipStream_t s);
-// launch_nnf2flow of one pair and the snapshot of the same field in one launch
-void launch_nnf2flow_snapshot(float* flow, int flow_pitch, int16_t* prev, const int16_t* nnf, int nnf_pitch, int w, int h, hipStream_t s);
+// prev <- the displacements of a field of stored matches (nnf_pitch in short2 elements); pair k's snapshot lies k * prev_stride bytes further
+void launch_temporal_snapshot(int16_t* prev, size_t prev_stride, const int16_t* nnf, int nnf_pitch, int w, int h, hipStream_t s, Batch bt = kOnePair);
+// launch_nnf2flow and the snapshot of the same field in one launch
+void launch_nnf2flow_snapshot(float* flow, int flow_pitch, int16_t* prev, size_t prev_stride, const int16_t* nnf, int nnf_pitch, int w, int h,
+                              hipStream_t s, Batch bt = kOnePair);
 
 // ---- level-2 post-processing (k_post.hip) ----
 void launch_lr_check(int16_t* nnf1, float* cost1, const int16_t* nnf2, int w, int h, int cost_pitch, int nnf_pitch, hipStream_t s, Batch bt = kOnePair);

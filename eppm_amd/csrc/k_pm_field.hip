@@ -111,8 +111,15 @@ void launch_pm_cost_field(const PmBatch& b, const float* lut, int R, hipStream_t
 
 // The seeded start (eppm_internal.h: PmSeed): the cost-field kernels above, evaluating the temporal prior instead of the stored match and
 // keeping it where it is strictly cheaper.  Same evaluation function per radius and library as launch_pm_cost_field picks, so a prior's cost
-// is bit for bit what the cost field would give that match.  A pixel without a prior skips its evaluation.
-__device__ __forceinline__ void pm_select_store(const PmProblem& pr, const PmBatch& B, const PmSeed& S, int k, int w, int x, int y, bool has,
+// is bit for bit what the cost field would give that match.  A pixel without a prior skips its evaluation.  Problem z of the launch is
+// direction z % n of slot z / n (pm_problem's decomposition): the prior and the copies are that slot's planes of that direction.
+struct PmSeedDir { const int16_t* prior; int16_t* nnf_init; float* cost_init; };
+__device__ __forceinline__ PmSeedDir pm_seed_dir(const PmBatch& B, const PmSeed& S, unsigned z)
+{
+    const unsigned k = z % (unsigned)B.n, slot = z / (unsigned)B.n;
+    return PmSeedDir{pair_ptr(S.prior[k], S.stride, slot), pair_ptr(S.nnf_init[k], S.stride, slot), pair_ptr(S.cost_init[k], S.stride, slot)};
+}
+__device__ __forceinline__ void pm_select_store(const PmProblem& pr, const PmBatch& B, const PmSeedDir& D, int w, int x, int y, bool has,
                                                 int px, int py, float pc)
 {
     const int ni = (y * B.npitch + x) * 2, ci = y * B.cpitch + x;
@@ -123,9 +130,9 @@ __device__ __forceinline__ void pm_select_store(const PmProblem& pr, const PmBat
         pr.nnf[ni] = (int16_t)nx; pr.nnf[ni + 1] = (int16_t)ny;
         pr.cost[ci] = c;
     }
-    S.nnf_init[k][(y * w + x) * 2] = (int16_t)nx;
-    S.nnf_init[k][(y * w + x) * 2 + 1] = (int16_t)ny;
-    S.cost_init[k][y * w + x] = c;
+    D.nnf_init[(y * w + x) * 2] = (int16_t)nx;
+    D.nnf_init[(y * w + x) * 2 + 1] = (int16_t)ny;
+    D.cost_init[y * w + x] = c;
 }
 
 __global__ __launch_bounds__(256) void k_pm_cost_select(PmBatch B, PmSeed S, const float* __restrict__ lut, int R)
@@ -133,15 +140,15 @@ __global__ __launch_bounds__(256) void k_pm_cost_select(PmBatch B, PmSeed S, con
     __shared__ EPPM_LUT_ALIGN PatchLut L;
     load_patch_lut(L, lut, R, threadIdx.y * kBlock + threadIdx.x, 256);
     __syncthreads();
-    const int k = blockIdx.z;
+    const PmSeedDir D = pm_seed_dir(B, S, blockIdx.z);
     const PmProblem pr = pm_problem(B, blockIdx.z);
     const Planes P = to_dev(pr.P);
     const int x = blockIdx.x * kBlock + threadIdx.x, y = blockIdx.y * kBlock + threadIdx.y;
     if (x >= P.w || y >= P.h) return;
-    const int px = S.prior[k][(y * P.w + x) * 2], py = S.prior[k][(y * P.w + x) * 2 + 1];
+    const int px = D.prior[(y * P.w + x) * 2], py = D.prior[(y * P.w + x) * 2 + 1];
     const bool has = px > kInvalid && py > kInvalid;
     const float pc = has ? patch_dist(P, L, R, x, y, px, py) : 0.0f;
-    pm_select_store(pr, B, S, k, P.w, x, y, has, px, py, pc);
+    pm_select_store(pr, B, D, P.w, x, y, has, px, py, pc);
 }
 
 template <int RT, int PK = 0>
@@ -153,23 +160,23 @@ __global__ __launch_bounds__(256) void k_pm_cost_select_tile(PmBatch B, PmSeed S
     __shared__ EPPM_LUT_ALIGN LUT L;
     const int tid = threadIdx.y * kBlock + threadIdx.x;
     load_patch_lut(L, lut, R, tid, 256);
-    const int k = blockIdx.z;                   // one pair: problem k of the launch is direction k
+    const PmSeedDir D = pm_seed_dir(B, S, blockIdx.z);
     const PmProblem pr = pm_problem(B, blockIdx.z);
     const Planes P = to_dev(pr.P);
     pm_stage_tile<RT>(s_src, P, blockIdx.x, blockIdx.y, tid);
     __syncthreads();
     const int x = blockIdx.x * kBlock + threadIdx.x, y = blockIdx.y * kBlock + threadIdx.y;
     if (x >= P.w || y >= P.h) return;
-    const int px = S.prior[k][(y * P.w + x) * 2], py = S.prior[k][(y * P.w + x) * 2 + 1];
+    const int px = D.prior[(y * P.w + x) * 2], py = D.prior[(y * P.w + x) * 2 + 1];
     const bool has = px > kInvalid && py > kInvalid;
     const float pc = has ? search_patch_dist<RT, PK>(P, L, R, s_src, TW, threadIdx.x, threadIdx.y, x, y, px, py, pr.P) : 0.0f;
-    pm_select_store(pr, B, S, k, P.w, x, y, has, px, py, pc);
+    pm_select_store(pr, B, D, P.w, x, y, has, px, py, pc);
 }
 
 void launch_pm_cost_select(const PmBatch& b, const PmSeed& seed, const float* lut, int R, hipStream_t s)
 {
     const int w = b.p[0].P.w, h = b.p[0].P.h;
-    dim3 grid((w + kBlock - 1) / kBlock, (h + kBlock - 1) / kBlock, b.n), block(kBlock, kBlock);      // one pair: a batch has no previous pair
+    dim3 grid((w + kBlock - 1) / kBlock, (h + kBlock - 1) / kBlock, b.n * b.npairs), block(kBlock, kBlock);
     switch (pm_cost_kernel(b, R)) {
     case 3: hipLaunchKernelGGL((k_pm_cost_select_tile<9, 2>), grid, block, 0, s, b, seed, lut, R); break;
     case 4: hipLaunchKernelGGL((k_pm_cost_select_tile<17, 2>), grid, block, 0, s, b, seed, lut, R); break;

@@ -479,8 +479,28 @@ extern "C" int eppm_temporal_prior(eppm_short2* d_prior, const eppm_short2* d_pr
     CHK(get_scratch(ds, (size_t)w * h * 4, &keys, 6));
     TemporalArgs a{};
     a.prev[0] = (const int16_t*)d_prev; a.prior[0] = (int16_t*)d_prior; a.keys[0] = (int32_t*)keys; a.step[0] = backward ? -1 : 1;
-    a.w = w; a.h = h; a.ndir = 1;
+    a.w = w; a.h = h; a.ndir = 1; a.nslots = 1; a.armed[0] = 1u;
     launch_temporal_keys_init(a.keys[0], w * h, g_stream);
+    launch_temporal_splat(a, g_stream);
+    launch_temporal_gather(a, g_stream);
+    return finish();
+}
+// the same on npairs slots in one launch each (slot k's planes lie k*h*w short2 after slot 0's); armed: NULL (all) or a byte per slot
+extern "C" int eppm_temporal_prior_batch(eppm_short2* d_prior, const eppm_short2* d_prev, int h, int w, int backward, int npairs, const uint8_t* armed)
+{
+    if (!d_prior || !d_prev || h < 1 || w < 1 || h > 32767 || w > 32767 || npairs < 1 || npairs > kTemporalMaxSlots)
+        return set_err(EPPM_ERR_ARG, "eppm_temporal_prior_batch: bad argument");
+    if ((unsigned long long)h * (unsigned long long)w * (unsigned long long)npairs >= (1ULL << 30))
+        return set_err(EPPM_ERR_ARG, "eppm_temporal_prior_batch: %d slots of %dx%d out of range", npairs, w, h);
+    LAUNCHER_BEGIN_INT;
+    void* keys = nullptr;
+    CHK(get_scratch(ds, (size_t)w * h * 4 * npairs, &keys, 6));
+    TemporalArgs a{};
+    a.prev[0] = (const int16_t*)d_prev; a.prior[0] = (int16_t*)d_prior; a.keys[0] = (int32_t*)keys; a.step[0] = backward ? -1 : 1;
+    a.w = w; a.h = h; a.ndir = 1; a.nslots = npairs; a.stride = (size_t)w * h * 4;
+    for (int k = 0; k < npairs; k++)
+        if (!armed || armed[k]) a.armed[k >> 5] |= 1u << (k & 31);
+    launch_temporal_keys_init(a.keys[0], w * h * npairs, g_stream);
     launch_temporal_splat(a, g_stream);
     launch_temporal_gather(a, g_stream);
     return finish();

@@ -308,6 +308,22 @@ def temporal_prior(prev, backward=False):
     return d_out.get()
 
 
+def temporal_prior_batch(prevs, backward=False, armed=None, calls=1):
+    """eppm_temporal_prior_batch on (npairs, h, w) short2 displacement fields: every slot in one splat and one gather launch; armed: None
+    (all) or a flag per slot.  calls > 1: the call is repeated on the same device planes, and the result of every call is returned."""
+    prevs = np.ascontiguousarray(prevs, short2)
+    n, h, w = prevs.shape
+    d_prev = Dev(prevs.reshape(n * h, w))
+    d_out = Dev(shape=(n * h, w), dtype=short2)
+    flags = None if armed is None else (C.c_uint8 * n)(*[int(bool(x)) for x in armed])
+    out = []
+    for _ in range(calls):
+        check(lib().eppm_temporal_prior_batch(d_out.ptr, d_prev.ptr, h, w, int(bool(backward)), n, flags), "eppm_temporal_prior_batch")
+        check(lib().eppm_device_synchronize(), "eppm_device_synchronize")
+        out.append(d_out.get().reshape(n, h, w))
+    return out[0] if calls == 1 else out
+
+
 def flow_to_color(flow, max_disp_x=20.0, max_disp_y=20.0):
     """bao_cuda_convert_flow_to_colorshow (float2 form, basic/bao_basic_cuda.cuh:839-845): (h,w) float2 -> (h,w) uchar4 {R,G,B,0}."""
     h, w = flow.shape

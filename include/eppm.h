@@ -295,6 +295,36 @@ int  eppm_temporal_prior_host(eppm_short2* prior, const eppm_short2* prev, int h
 /* the kernels alone on unpitched device planes; on the launcher stream, like eppm_fb_occlusion */
 int  eppm_temporal_prior(eppm_short2* d_prior, const eppm_short2* d_prev, int h, int w, int backward);
 
+/* ----------------------------------------------------------------------------------------
+ * batch streaming: one clip per slot of a batch context, every slot advanced by one frame per step.  Valid on any
+ * context of eppm_create_batch (npairs = 1 included); eppm_push_image* and eppm_set_temporal keep refusing a batch context.  Opt-in like the
+ * single-pair calls: a batch context that never calls these allocates and launches exactly what it did without them.
+ *  push: n must equal the number of active pairs (EPPM_ERR_ARG).  Slot k's image 2 becomes its image 1 and rgb[k] its image 2; only the new
+ *    frames are uploaded and prepared.  After eppm_batch_set_images(A_k, B_k), eppm_batch_push_images(C_k) every plane and every flow of
+ *    slot k equals those after eppm_batch_set_images(B_k, C_k), bit for bit.  EPPM_ERR_STATE before the first eppm_batch_set_images*, or
+ *    while an eppm_compute_begin* is pending.  The host form returns when the caller may reuse the images.
+ *  new_clip: NULL, or n bytes; non-zero: the frame pushed into slot k is the first frame of another clip.  The pair the slot now holds
+ *    (the old clip's last frame, the new clip's first) is computed like any other -- every launch covers every slot; its flow is the
+ *    caller's to discard -- but neither starts from a prior nor leaves one: the pair across the cut and the new clip's first pair are cold
+ *    runs, its second pair is seeded.
+ *  temporal mode, per slot k:   compute: seeded[k] = valid[k], snap[k] = !cut[k], valid[k] = 0
+ *                               push:    valid[k] = snap[k] && !new_clip[k], snap[k] = 0, cut[k] = new_clip[k]
+ *    eppm_batch_set_images* drops every slot's fields, eppm_batch_temporal_reset(k) those of slot k (k < 0: of every slot).  A slot that is
+ *    not seeded gets the cold run's bits whatever its neighbours do: its flows are eppm_batch_compute's.  The temporal planes are npairs
+ *    blocks of 40 bytes per PatchMatch-level pixel (each plane rounded up to 256 bytes), allocated by the first compute with the mode on.
+ *    Works with eppm_batch_compute, _compute_device, _compute_begin_into / _end, _compute_bidirectional and eppm_track_step(t, ctx, pair).
+ *    eppm_batch_get_plane(ctx, k, "prior1" ...) is valid for a slot whose last compute was seeded (EPPM_ERR_STATE otherwise).
+ * -------------------------------------------------------------------------------------- */
+int  eppm_batch_set_temporal(eppm_ctx* ctx, int on);          /* off (default) also drops every slot's fields */
+int  eppm_batch_push_images(eppm_ctx* ctx, int n, const uint8_t* const* rgb, size_t row_stride, const uint8_t* new_clip);
+/* device-resident RGBA frames, as eppm_batch_set_images_device's */
+int  eppm_batch_push_images_device(eppm_ctx* ctx, int n, const void* const* d_rgba, size_t pitch, const uint8_t* new_clip);
+int  eppm_batch_temporal_valid(const eppm_ctx* ctx, int pair);    /* 1: the slot's next compute will start from a prior; 0 otherwise */
+int  eppm_batch_temporal_reset(eppm_ctx* ctx, int pair);          /* the slot's next compute is cold; pair < 0: every slot's */
+/* the advection kernels alone on caller planes: npairs slots of h*w short2 each, both planes unpitched and slot after slot, one splat and
+ * one gather launch for all of them; armed: NULL (all) or npairs bytes (host memory), an unarmed slot gets "no prior" everywhere */
+int  eppm_temporal_prior_batch(eppm_short2* d_prior, const eppm_short2* d_prev, int h, int w, int backward, int npairs, const uint8_t* armed);
+
 /* Per-stage device times in ms (hipEvent pairs on the context's stream), one entry per stage per
  * call since the last eppm_clear_stage_times (names repeat across calls; prepare entries first).
  * names[i] points to static strings.  Returns the number of entries written (<= max). */
