@@ -57,6 +57,7 @@ SYMBOLS = [
     "eppm_temporal_prior",
     "eppm_batch_set_temporal", "eppm_batch_push_images", "eppm_batch_push_images_device", "eppm_batch_temporal_valid", "eppm_batch_temporal_reset",
     "eppm_temporal_prior_batch",
+    "eppm_set_stop_level", "eppm_stop_level", "eppm_flow_upsample",
 ]
 
 

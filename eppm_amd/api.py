@@ -146,11 +146,19 @@ class Tracker:
             pass
 
 
-def flow_sequence(frames, params=None, temporal=True, bidirectional=False):
+def _level(level):
+    """a stop level as a plain int; anything that is not an integer is refused before the library is touched"""
+    if isinstance(level, (bool, np.bool_)) or not isinstance(level, (int, np.integer)):
+        raise EppmError(f"stop level must be an integer, not {level!r}")
+    return int(level)
+
+
+def flow_sequence(frames, params=None, temporal=True, bidirectional=False, stop_level=0):
     """The flows of the consecutive pairs of a clip ((h, w, 3) uint8 frames) through ONE context: the first pair by set_data, every later
     frame by push_frame (only the new frame is uploaded and prepared), with temporal mode (each pair's PatchMatch starts from the previous
     pair's result moved along its motion) unless temporal=False.  Returns a list of (u, v), or of (u, v, bu, bv, occ1, occ2) with
-    bidirectional=True.  Memory does not grow with the clip."""
+    bidirectional=True.  Memory does not grow with the clip.  stop_level: draft mode (EPPM.set_stop_level)."""
+    stop_level = _level(stop_level)
     frames = [np.ascontiguousarray(f, np.uint8) for f in frames]
     if len(frames) < 2:
         raise EppmError("flow_sequence: at least two frames")
@@ -160,6 +168,7 @@ def flow_sequence(frames, params=None, temporal=True, bidirectional=False):
     try:
         e.init(h, w)
         e.set_temporal(temporal)
+        e.set_stop_level(stop_level)
         for k in range(len(frames) - 1):
             if k == 0:
                 e.set_data(frames[0], frames[1])
@@ -201,11 +210,12 @@ def _sequence_plan(lengths, slots):
         yield step
 
 
-def flow_sequences(clips, slots=8, params=None, temporal=True, bidirectional=False):
+def flow_sequences(clips, slots=8, params=None, temporal=True, bidirectional=False, stop_level=0):
     """flow_sequence for many clips at once: any number of clips of one frame size and of any lengths (two frames at least) through ONE
     batch context of min(slots, len(clips)) slots, every slot advanced by one frame per step (push_frames; temporal mode per slot unless
     temporal=False).  A slot whose clip ends takes the next clip in the queue.  Returns one list of flows per clip, in the order given, each
-    what flow_sequence(clip) returns."""
+    what flow_sequence(clip) returns.  stop_level: draft mode (EPPMBatch.set_stop_level)."""
+    stop_level = _level(stop_level)
     clips = [[np.ascontiguousarray(f, np.uint8) for f in clip] for clip in clips]
     plan = _sequence_plan([len(c) for c in clips], slots)
     h, w, _ = clips[0][0].shape
@@ -216,6 +226,7 @@ def flow_sequences(clips, slots=8, params=None, temporal=True, bidirectional=Fal
             if t == 0:
                 e = EPPMBatch(h, w, len(step), params=params)
                 e.set_temporal(temporal)
+                e.set_stop_level(stop_level)
                 e.set_data([(clips[c][0], clips[c][1]) for c, _, _, _ in step])
             else:
                 e.push_frames([clips[c][f] for c, f, _, _ in step], [cut for _, _, cut, _ in step])
@@ -242,7 +253,7 @@ def _track_collect(out, trk):
             out[i] = {"start": int(s0), "positions": [p], "reason": None}
 
 
-def _track_sequence_streaming(frames, params, track_params):
+def _track_sequence_streaming(frames, params, track_params, stop_level=0):
     from . import io
     h, w, _ = frames[0].shape
     e = EPPM(params=params)
@@ -250,6 +261,7 @@ def _track_sequence_streaming(frames, params, track_params):
     try:
         e.init(h, w)
         e.set_temporal(True)
+        e.set_stop_level(stop_level)
         for k in range(len(frames) - 1):
             if k == 0:
                 e.set_data(frames[0], frames[1])
@@ -271,23 +283,25 @@ def _track_sequence_streaming(frames, params, track_params):
     return out
 
 
-def track_sequence(frames, params=None, streaming=False, **track_params):
+def track_sequence(frames, params=None, streaming=False, stop_level=0, **track_params):
     """Dense point trajectories through a list of (h, w, 3) uint8 frames: one bidirectional call on a batch of the consecutive pairs, then
     one tracker step per pair.  Returns {track id: {"start": first frame, "positions": (n, 2) float32 positions in frames start ..
     start + n - 1, "reason": the end reason 1..4, or None while alive}}.  params: the flow's eppm Params; track_params: TrackParams'.
     streaming=True: one single-pair context instead of the batch -- push_frame and temporal mode, one bidirectional call and one tracker
     step per pair --, so that memory does not grow with the clip; the flows from the second pair on start from a temporal prior and are
-    not bit for bit the batch's."""
+    not bit for bit the batch's.  stop_level: draft mode (EPPM.set_stop_level): the tracker runs on the draft flows."""
     from . import io
+    stop_level = _level(stop_level)
     frames = [np.ascontiguousarray(f, np.uint8) for f in frames]
     if len(frames) < 2:
         raise EppmError("track_sequence: at least two frames")
     if streaming:
-        return _track_sequence_streaming(frames, params, track_params)
+        return _track_sequence_streaming(frames, params, track_params, stop_level)
     h, w, _ = frames[0].shape
     bat = EPPMBatch(h, w, len(frames) - 1, params=params)
     trk = None
     try:
+        bat.set_stop_level(stop_level)
         bat.set_data(list(zip(frames[:-1], frames[1:])))
         bat.compute_flow_bidirectional()
         trk = Tracker(bat, 0, **track_params)
@@ -372,6 +386,17 @@ class EPPM:
         own motion; set_data starts a new clip."""
         self._need()
         check(lib().eppm_set_temporal(self._ctx, int(bool(on))), "eppm_set_temporal")
+
+    def set_stop_level(self, level):
+        """Draft mode (eppm_set_stop_level): the pyramid levels below `level` are upsampled edge-aware from the level
+        above (one launch each) instead of being refined and smoothed; 0 (default): the full path.  Takes effect at the next compute."""
+        level = _level(level)
+        self._need()
+        check(lib().eppm_set_stop_level(self._ctx, level), "eppm_set_stop_level")
+
+    def stop_level(self):
+        self._need()
+        return int(lib().eppm_stop_level(self._ctx))
 
     def temporal_reset(self):
         """Drop the previous pair's fields: the next compute is a cold run (eppm_temporal_reset)."""
@@ -582,6 +607,14 @@ class EPPMBatch:
         if len(new_clip) != n:
             raise EppmError("new_clip: one flag per frame")
         return (C.c_uint8 * n)(*[int(bool(x)) for x in new_clip])
+
+    def set_stop_level(self, level):
+        """Draft mode for every slot (eppm_set_stop_level; EPPM.set_stop_level)."""
+        level = _level(level)
+        check(lib().eppm_set_stop_level(self._ctx, level), "eppm_set_stop_level")
+
+    def stop_level(self):
+        return int(lib().eppm_stop_level(self._ctx))
 
     def push_frames(self, frames, new_clip=None):
         """Slot k's image 2 becomes its image 1 and frames[k] its image 2 (eppm_batch_push_images): only the new frames are uploaded and

@@ -286,6 +286,16 @@ bool bao_flow_patchmatch_multiscale_cuda::set_occlusion_params(float alpha, floa
     return true;
 }
 
+bool bao_flow_patchmatch_multiscale_cuda::set_stop_level(int level)
+{
+    if (!m_ctx) return false;
+    if (eppm_set_stop_level(m_ctx, level) != EPPM_OK) {
+        fprintf(stderr, "bao_flow_patchmatch_multiscale_cuda::set_stop_level: %s\n", eppm_last_error());
+        return false;
+    }
+    return true;
+}
+
 // the frame at time t between the images of the last compute_flow_bidirectional (eppm_interpolate); img_t: h x w x 3 R,G,B row-pointer
 // tables (bao_alloc<unsigned char>(h, w, 3), as init's images)
 bool bao_flow_patchmatch_multiscale_cuda::interpolate_frame(float t, unsigned char*** img_t)

@@ -20,6 +20,7 @@ struct eppm_ctx {
     int opt_sweep_spec = -1, opt_no_split = 0;     // kernel-variant switches, copied from the process defaults at creation (test support)
     eppm_params prm;
     int h = 0, w = 0, nl = 0;
+    int stop_level = 0;                 // draft mode (eppm_set_stop_level): levels below it are upsampled, not refined
     int npairs = 1, n_active = 1;
     char* slab = nullptr;
     size_t stride = 0;

@@ -73,13 +73,13 @@ struct Branch {
 };
 
 // "upsample_L2", "c2f_refine_bwd_L0", ...: the per-level stage names of both directions, built once when the library is loaded
-enum { kStageUp, kStageRefine, kStageBlf };
+enum { kStageUp, kStageRefine, kStageBlf, kStageJbu };
 static const struct EPPM_HIDDEN LevelStageNames {
-    char s[3][2][kMaxLevels][24];       // [stage][backward][level]
+    char s[4][2][kMaxLevels][24];       // [stage][backward][level]
     LevelStageNames()
     {
-        const char* base[3] = {"upsample", "c2f_refine", "flow_blf"};
-        for (int k = 0; k < 3; k++)
+        const char* base[4] = {"upsample", "c2f_refine", "flow_blf", "flow_jbu"};
+        for (int k = 0; k < 4; k++)
             for (int b = 0; b < 2; b++)
                 for (int l = 0; l < kMaxLevels; l++) snprintf(s[k][b][l], sizeof s[k][b][l], "%s%s_L%d", base[k], b ? "_bwd" : "", l);
     }
@@ -103,14 +103,26 @@ static void branch_nnf2flow(eppm_ctx* c, Branch& d)
 
 // The levels below it (driver :275-289).  keep(c, l, r): r holds level l's result -- what level l's smoothing wrote for l > 0, what the
 // final smoothing wrote for level 0 --; called inside that stage, before anything overwrites r.
+// Draft mode (stop_level s > 0): the levels below s are one upsampling launch each, written into the level's plane
+// that is not the launch's input (the backward branch smooths every level into the same plane), and no final smoothing follows.
 static int branch_c2f(eppm_ctx* c, Branch& d, int (*keep)(eppm_ctx*, int, float*))
 {
     hipStream_t s = c->stream;
     const Batch bt = c->bt();
     const int L = c->nl - 1;
     auto blf = [&](float* dst, const float* src, int l) { launch_flow_blf(dst, src, d.guide[l], (int)(c->ipitch[l] / 4), c->W[l], c->H[l], c->W[l], c->lut_blf, s, bt); };
+    const int stop = c->stop_level;
     float* r = d.a[L];
     for (int l = L - 1; l >= 0; l--) {
+        if (l < stop) {
+            stage_begin(c, c->ev, level_stage.s[kStageJbu][d.bwd][l]);
+            float* out = (r == d.b[l]) ? d.a[l] : d.b[l];
+            launch_flow_jbu(out, r, d.guide[l], (int)(c->ipitch[l] / 4), c->W[l], c->H[l], c->W[l + 1], c->H[l + 1], c->lut_blf, s, bt);
+            r = out;
+            CHK(keep(c, l, r));
+            stage_end(c, c->ev);
+            continue;
+        }
         stage_begin(c, c->ev, level_stage.s[kStageUp][d.bwd][l]);
         launch_resize_flow(d.a[l], c->H[l], c->W[l], r, c->H[l + 1], c->W[l + 1], 2.0f, 2.0f, s, bt);        // refine :1082-1083
         stage_end(c, c->ev);
@@ -123,6 +135,7 @@ static int branch_c2f(eppm_ctx* c, Branch& d, int (*keep)(eppm_ctx*, int, float*
         if (l > 0) CHK(keep(c, l, r));
         stage_end(c, c->ev);
     }
+    if (stop > 0) return EPPM_OK;
     stage_begin(c, c->ev, d.bwd ? "flow_blf_bwd_final" : "flow_blf_final");
     float* out = (r == d.b[0]) ? d.a[0] : d.b[0];
     blf(out, r, 0);                                                                                          // driver :289
@@ -448,6 +461,18 @@ extern "C" int eppm_compute_bidirectional_device(eppm_ctx* c, void* d_flow, void
     if (d_occ2) HIPCHK(hipMemcpyAsync(d_occ2, c->occ2, n, hipMemcpyDeviceToDevice, c->stream));
     return EPPM_OK;
 }
+
+// ---- draft mode ----
+extern "C" int eppm_set_stop_level(eppm_ctx* c, int level)
+{
+    if (!c) return set_err(EPPM_ERR_ARG, "eppm_set_stop_level: NULL ctx");
+    if (level < 0 || level > c->nl - 1) return set_err(EPPM_ERR_ARG, "eppm_set_stop_level: level %d outside 0 .. %d", level, c->nl - 1);
+    if (c->flow_pending) return set_err(EPPM_ERR_STATE, "eppm_set_stop_level: an eppm_compute_begin is pending");
+    c->stop_level = level;
+    c->have_flow = c->have_bwd = false;          // the planes are another setting's: interpolate / track wait for the next compute
+    return EPPM_OK;
+}
+extern "C" int eppm_stop_level(const eppm_ctx* c) { return c ? c->stop_level : -1; }
 
 extern "C" int eppm_set_occlusion_params(eppm_ctx* c, float alpha, float beta)
 {

@@ -230,6 +230,11 @@ void launch_c2f_refine(const PlanesH& P, float* flow, const float* lut, int R, f
 void launch_flow_blf(float* out, const float* in, const uint32_t* img, int ipitch, int w, int h, int flow_pitch,
                      const float* blf_lut, hipStream_t s, Batch bt = kOnePair);
 EPPM_DECISION int flow_blf_pixels_per_lane(int w, int h, int npairs = 1);      // of the smoothing: 2 (k_flow_blf<2>, large launches) or 1
+// ---- draft mode: joint-bilateral upsampling (k_flow_jbu.hip) ----
+// out (h x w float2, unpitched) = the smoothing of the doubled, 2x-replicated coarse flow (hc x wc float2, unpitched; rows and columns past
+// its edge repeat the last one) guided by img; the replicated plane is never written.  Pixels per lane by flow_blf_pixels_per_lane.
+void launch_flow_jbu(float* out, const float* in_coarse, const uint32_t* img, int ipitch, int w, int h, int wc, int hc, const float* blf_lut,
+                     hipStream_t s, Batch bt = kOnePair);
 
 // interleaved float2 flow -> planar u | v (2*n floats) on the device: compute_flow's de-interleave, driver :302-306
 void launch_split_flow(float* uv, const float* flow, int n, hipStream_t s, Batch bt = kOnePair);

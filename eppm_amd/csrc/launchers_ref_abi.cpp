@@ -269,6 +269,19 @@ extern "C" int eppm_resize_flow(eppm_float2* d_out, int outH, int outW, const ep
     launch_resize_flow((float*)d_out, outH, outW, (const float*)d_in, h, w, ratio, 1.0f, g_stream);
     return finish();
 }
+// draft mode's upsampling (k_flow_jbu.hip) on caller planes; synchronous
+extern "C" int eppm_flow_upsample(eppm_float2* d_out, int h, int w, const eppm_float2* d_coarse, int hc, int wc, const eppm_uchar4* d_guide,
+                                  size_t guide_pitch)
+{
+    if (!d_out || !d_coarse || !d_guide || h < 1 || w < 1 || hc < 1 || wc < 1) return set_err(EPPM_ERR_ARG, "eppm_flow_upsample: bad argument");
+    if (guide_pitch < (size_t)w * 4 || (guide_pitch & 3)) return set_err(EPPM_ERR_ARG, "eppm_flow_upsample: bad pitch %zu", guide_pitch);
+    if ((unsigned long long)h * (unsigned long long)guide_pitch >= (1ULL << 32) || (unsigned long long)h * (unsigned long long)w >= (1ULL << 30))
+        return set_err(EPPM_ERR_ARG, "eppm_flow_upsample: size %dx%d out of range", w, h);
+    LAUNCHER_BEGIN_INT;
+    launch_flow_jbu((float*)d_out, (const float*)d_coarse, (const uint32_t*)d_guide, (int)(guide_pitch / 4), w, h, wc, hc, ds->lut_blf, g_stream);
+    HIPCHK(hipStreamSynchronize(g_stream));
+    return finish();
+}
 
 // ---------------------------------------------------------------------------------------------------
 // the reference's live extern "C" launchers (driver :40-62)

@@ -267,6 +267,16 @@ def resize_flow(flow, out_h, out_w, ratio=2.0):
     return b.get()
 
 
+def flow_upsample(coarse, img):
+    """eppm_flow_upsample (draft mode's kernel): the (hc, wc) float2 flow `coarse` up to the size of the uchar4 guide
+    image, in one launch."""
+    h, w = img.shape
+    hc, wc = coarse.shape
+    a, i, b = Dev(coarse), Dev(img, pitched=True), Dev(shape=(h, w), dtype=float2)
+    check(lib().eppm_flow_upsample(b.ptr, h, w, a.ptr, hc, wc, i.ptr, _sz(i.pitch)), "eppm_flow_upsample")
+    return b.get()
+
+
 def c2f_refine(flow, P):
     """baoCudaBLFCostFilterRefine"""
     f = Dev(flow)

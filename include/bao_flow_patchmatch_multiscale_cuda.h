@@ -52,6 +52,9 @@ public:
                                     unsigned char** occ2 = NULL);
     // alpha, beta of the masks' criterion (eppm_set_occlusion_params; defaults 0.01, 0.5); after init().  false: bad values or no context
     bool set_occlusion_params(float alpha, float beta);
+    // draft mode (eppm_set_stop_level): the levels below `level` are upsampled edge-aware instead of refined; 0
+    // (default) = the full path.  After init(); holds until the next init().  false: level outside 0 .. levels - 1 or no context
+    bool set_stop_level(int level);
     // the frame at time t in [0, 1] between image 1 (t = 0) and image 2 (t = 1) (eppm_interpolate): valid after
     // compute_flow_bidirectional and until the next set_data; img_t: h x w x 3 R,G,B row-pointer tables (bao_alloc<unsigned char>(h, w, 3),
     // the layout of init's images).  false: no such call yet, bad t, or no context

@@ -181,6 +181,19 @@ int  eppm_batch_compute_bidirectional(eppm_ctx* ctx, float* const* u, float* con
                                       uint8_t* const* occ1, uint8_t* const* occ2);
 /* alpha, beta of the masks' criterion (defaults 0.01, 0.5: Sundaram, Brox & Keutzer, ECCV 2010); both finite, >= 0 */
 int  eppm_set_occlusion_params(eppm_ctx* ctx, float alpha, float beta);
+/* ----------------------------------------------------------------------------------------
+ * draft mode: the stop level s of a context, single or batch, 0 <= s <= eppm_num_levels - 1, default 0 = the full
+ * path.  With s > 0 the levels eppm_num_levels - 1 .. s run as always (flow[s] is the full path's flow[s], bit for bit), and every level
+ * l < s is ONE launch instead of resize + candidate refine + smoothing: flow[l] = the flow smoothing, guided by level l's image, of the
+ * doubled and 2x-replicated flow[l + 1] (eppm_flow_upsample); no final smoothing follows.  The backward branch of the bidirectional
+ * calls does the same with image 2 as the guide, and the masks, the interpolation, the tracker and the streaming calls work on the
+ * draft flows unchanged.  No memory is added.  Takes effect at the next compute; the flows of the last compute stop being valid for
+ * eppm_interpolate* / eppm_track_step (EPPM_ERR_STATE until the next compute).  EPPM_ERR_ARG outside 0 .. eppm_num_levels - 1;
+ * EPPM_ERR_STATE, and nothing changes, while an eppm_compute_begin is pending.  Stage
+ * names: "flow_jbu_L<l>", "flow_jbu_bwd_L<l>".
+ * -------------------------------------------------------------------------------------- */
+int  eppm_set_stop_level(eppm_ctx* ctx, int level);
+int  eppm_stop_level(const eppm_ctx* ctx);           /* -1: NULL context */
 /* the kernel alone on unpitched device planes (like eppm_flow_to_color): d_occ h*w bytes for F = d_flow, G = d_other (h*w float2
  * each); on the launcher stream, synchronous like the other launchers */
 int  eppm_fb_occlusion(uint8_t* d_occ, const eppm_float2* d_flow, const eppm_float2* d_other, int h, int w, float alpha, float beta);
@@ -460,6 +473,11 @@ int  eppm_gauss_filter_rgba(eppm_uchar4* d_out, const eppm_uchar4* d_in, size_t 
 int  eppm_resize_rgba(eppm_uchar4* d_out, size_t out_pitch, int outH, int outW, const eppm_uchar4* d_in, size_t in_pitch,
         int h, int w, float ratio);
 int  eppm_resize_flow(eppm_float2* d_out, int outH, int outW, const eppm_float2* d_in, int h, int w, float ratio);
+/* Draft mode's upsampling alone, on unpitched float2 device planes: d_out (h x w) = the flow smoothing, guided by
+ * d_guide (h x w RGBA, guide_pitch bytes per row), of the plane whose pixel (x, y) holds 2 * d_coarse[min(y >> 1, hc - 1)][min(x >> 1, wc - 1)]
+ * (d_coarse: hc x wc).  One launch; the replicated plane is never written.  On the launcher stream, synchronous. */
+int  eppm_flow_upsample(eppm_float2* d_out, int h, int w, const eppm_float2* d_coarse, int hc, int wc, const eppm_uchar4* d_guide,
+        size_t guide_pitch);
 /* ----------------------------------------------------------------------------------------
  * file formats used by the reference's CLI (main.cpp:56-69)
  * -------------------------------------------------------------------------------------- */

@@ -13,6 +13,7 @@
 #   tcp         TA/TCP/TD counters per kernel (is a gather kernel L1 bound?)
 #   pmiter      every PatchMatch launch of one run in order, with durations (BENCH_ARGS)
 #   clock       shader clock and power under load                      inflight    throughput vs contexts in flight
+#   draft       draft mode: tools/draft_times.py on both libraries -> draft_times_{exact,tol}.json in the output folder
 #   round       everything profiles/ of a round comes from (TAG=r04_x; PMC_ONLY=1, SKIP_TESTS=1)
 set -o pipefail
 R=${GRAFT_REPO_ROOT:-$(cd "$(dirname "$0")/.." && pwd)}
@@ -109,6 +110,11 @@ clock)
     echo "t=$i $(rocm-smi --showclocks 2>&1 | grep -i 'sclk' | head -1 | sed 's/.*(//;s/).*//') $(rocm-smi --showpower 2>&1 | grep -i 'power' | head -1 | sed 's/.*: //')"
     sleep 1; kill -0 $BP 2>/dev/null || break; done
   wait $BP; cut -c1-160 /tmp/b.json ;;
+draft)
+  cd $R; for l in exact tol; do
+    timeout -k 10 ${DRAFT_TIMEOUT:-420} python tools/draft_times.py --lib $l ${DRAFT_ARGS} > $O/draft_times_$l.json || exit 1
+    cut -c1-300 $O/draft_times_$l.json
+  done ;;
 inflight)
   cd $R; for S in ${INFLIGHT:-1 2 3 4 6}; do
     python bench.py --steps 96 --warmup 8 --inflight $S $QUIET $BENCH_ARGS 2>/dev/null | python -c "import json,sys; d=json.loads(sys.stdin.read()); print('inflight $S pairs in flight',d['config']['pairs_in_flight_per_gpu'],'ms/step %.3f'%d['ms_per_step'],'Mvec/s %.1f'%d['value'])"

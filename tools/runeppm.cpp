@@ -10,6 +10,8 @@
 //   --patch-r N       patch radius (PATCH_R 9, defs.h:44)
 //   --iters N         PatchMatch iterations (NUM_ITER 10, defs.h:45)
 //   --propagation M   0 segmented sweeps (live in the reference), 1 jump flood, 2 4-neighbour
+//   --stop-level N    draft mode: the levels below N are upsampled edge-aware instead of refined; 0 (default) the
+//                     full path, at most levels - 1
 //   --pairs P         process the pair P times in steady state (set_data + compute_flow); throughput is printed
 //   --gpus G          G worker threads, one context per GPU; the P pairs are dealt round-robin (pair i -> GPU i mod G)
 //   --batch B         each worker runs its pairs B at a time through a batch context (eppm_create_batch: every kernel launch
@@ -28,7 +30,7 @@
 //                     eppm_push_image; the flow of frames k-1 -> k is written to P_<k as four digits>.flo (P_0001.flo ...).
 //                     --temporal 1 (default): every pair after the first starts PatchMatch from the previous pair's result moved
 //                     along its motion; 0: every pair is a cold run (bit for bit the two-image form's flow).  Of the options above
-//                     --seed, --levels, --patch-r, --iters and --propagation apply.
+//                     --seed, --levels, --patch-r, --iters, --propagation and --stop-level apply.
 #include <atomic>
 #include <chrono>
 #include <cstdio>
@@ -63,6 +65,7 @@ struct Options {
     std::vector<const char*> seq;                           // --sequence frames
     const char* prefix = nullptr;                           // --out-prefix
     int temporal = 1;                                       // --temporal
+    int stop_level = 0;                                     // --stop-level
 };
 
 static unsigned hash32(unsigned x)
@@ -109,10 +112,10 @@ static bool apply_opt(eppm_params& p, const std::string& name, long long v)
 
 static int usage()
 {
-    fprintf(stderr, "usage: runeppm [--size WxH] [--seed N] [--levels N] [--patch-r N] [--iters N] [--propagation M]\n"
+    fprintf(stderr, "usage: runeppm [--size WxH] [--seed N] [--levels N] [--patch-r N] [--iters N] [--propagation M] [--stop-level N]\n"
                     "               [--pin] [--pairs P] [--gpus G] [--batch B] [--gt file.flo] [--out file.flo] [--backward file.flo]\n"
                     "               [--occlusion file.pgm] [--interpolate T file.ppm]... [img1.ppm img2.ppm [out.flo]]\n"
-                    "       runeppm [--seed N] [--levels N] [--patch-r N] [--iters N] [--propagation M]\n"
+                    "       runeppm [--seed N] [--levels N] [--patch-r N] [--iters N] [--propagation M] [--stop-level N]\n"
                     "               --sequence f0.ppm f1.ppm [f2.ppm ...] --out-prefix P [--temporal 0|1]\n");
     return 2;
 }
@@ -137,6 +140,7 @@ static int run_sequence(const Options& o)
     auto fail = [&](const char* what) { fprintf(stderr, "%s: %s\n", what, eppm_last_error()); if (ctx) eppm_destroy(ctx); return 1; };
     if (eppm_create(&ctx, h, w, 0, &prm) != EPPM_OK) return fail("eppm_create");
     if (eppm_set_temporal(ctx, o.temporal) != EPPM_OK) return fail("eppm_set_temporal");
+    if (eppm_set_stop_level(ctx, o.stop_level) != EPPM_OK) { fprintf(stderr, "--stop-level: %s\n", eppm_last_error()); eppm_destroy(ctx); return usage(); }
     double total = 0;
     for (size_t k = 0; k < o.seq.size(); k++) {
         int hk = 0, wk = 0;
@@ -178,6 +182,13 @@ int main(int argc, char** argv)
         else if (!strcmp(a, "--patch-r")) { if (!val(&v)) return usage(); o.opts.push_back({"patch_r", v}); }
         else if (!strcmp(a, "--iters")) { if (!val(&v)) return usage(); o.opts.push_back({"num_iter", v}); }
         else if (!strcmp(a, "--propagation")) { if (!val(&v)) return usage(); o.opts.push_back({"propagation", v}); }
+        else if (!strcmp(a, "--stop-level")) {
+            if (i + 1 >= argc) return usage();
+            char* end = nullptr;
+            const long n = strtol(argv[++i], &end, 10);
+            if (!end || end == argv[i] || *end || n < 0 || n > 1000) return usage();
+            o.stop_level = (int)n;
+        }
         else if (!strcmp(a, "--pairs")) { if (!val(&v) || v < 1) return usage(); o.pairs = (int)v; }
         else if (!strcmp(a, "--gpus")) { if (!val(&v) || v < 1) return usage(); o.gpus = (int)v; }
         else if (!strcmp(a, "--batch")) { if (!val(&v) || v < 1) return usage(); o.batch = (int)v; }
@@ -259,6 +270,7 @@ int main(int argc, char** argv)
         auto t0 = std::chrono::steady_clock::now();
         eppm.init(img1.p(), img2.p(), h, w);                             // main.cpp:63-64: the reference's timed window
         if (!eppm.handle()) return 1;
+        if (o.stop_level && !eppm.set_stop_level(o.stop_level)) return usage();
         if (bidir) eppm.compute_flow_bidirectional(ur.data(), vr.data(), bur.data(), bvr.data(), occr.data());
         else eppm.compute_flow(ur.data(), vr.data());
         auto t1 = std::chrono::steady_clock::now();
@@ -287,6 +299,7 @@ int main(int argc, char** argv)
                     for (auto& kv : o.opts) apply_opt(prm, kv.first, kv.second);
                     eppm_ctx* c = nullptr;
                     if (eppm_create_batch(&c, h, w, dev, &prm, o.batch) != EPPM_OK) { failed[g] = 1; ready++; return; }
+                    if (eppm_set_stop_level(c, o.stop_level) != EPPM_OK) { failed[g] = 1; ready++; eppm_destroy(c); return; }
                     std::vector<std::vector<float>> bu(o.batch, std::vector<float>((size_t)h * w)), bv(o.batch, std::vector<float>((size_t)h * w));
                     std::vector<const uint8_t*> a1(o.batch, img1.store.data()), a2(o.batch, img2.store.data());
                     std::vector<float*> pu(o.batch), pv(o.batch);
@@ -314,7 +327,7 @@ int main(int argc, char** argv)
                 e.set_device(dev);
                 for (auto& kv : o.opts) e.set_option(kv.first.c_str(), kv.second);
                 e.init(h, w);
-                if (!e.handle()) { failed[g] = 1; ready++; return; }
+                if (!e.handle() || !e.set_stop_level(o.stop_level)) { failed[g] = 1; ready++; return; }
                 std::vector<float> lu((size_t)h * w), lv((size_t)h * w);
                 std::vector<float*> lur(h), lvr(h);
                 for (int i = 0; i < h; i++) { lur[i] = &lu[(size_t)i * w]; lvr[i] = &lv[(size_t)i * w]; }
