@@ -20,6 +20,10 @@ class CTrackParams(C.Structure):
                 ("mb_beta", C.c_float), ("capacity", C.c_int)]
 
 
+class CTFilterParams(C.Structure):
+    _fields_ = [("thresh", C.c_float), ("n_max", C.c_int)]
+
+
 class CTrackCounts(C.Structure):
     _fields_ = [("live", C.c_int), ("ended", C.c_int), ("seeded", C.c_int), ("dropped", C.c_int), ("frame", C.c_int), ("next_id", C.c_int)]
 
@@ -58,6 +62,9 @@ SYMBOLS = [
     "eppm_batch_set_temporal", "eppm_batch_push_images", "eppm_batch_push_images_device", "eppm_batch_temporal_valid", "eppm_batch_temporal_reset",
     "eppm_temporal_prior_batch",
     "eppm_set_stop_level", "eppm_stop_level", "eppm_flow_upsample",
+    "eppm_tfilter_default_params", "eppm_tfilter_create", "eppm_tfilter_create_size", "eppm_tfilter_destroy", "eppm_tfilter_reset", "eppm_tfilter_step",
+    "eppm_tfilter_step_frames", "eppm_tfilter_get", "eppm_tfilter_get_device", "eppm_tfilter_get_state", "eppm_tfilter_set_state",
+    "eppm_tfilter_seed_host", "eppm_tfilter_step_host",
 ]
 
 

@@ -3,7 +3,7 @@ import ctypes as C
 
 import numpy as np
 
-from ._lib import CParams, CTrackCounts, CTrackParams, EppmError, check, lib
+from ._lib import CParams, CTFilterParams, CTrackCounts, CTrackParams, EppmError, check, lib
 
 uchar4 = np.dtype([("x", "u1"), ("y", "u1"), ("z", "u1"), ("w", "u1")])
 short2 = np.dtype([("x", "i2"), ("y", "i2")])
@@ -146,6 +146,80 @@ class Tracker:
             pass
 
 
+class TemporalFilter:
+    """Motion-compensated temporal denoising over the pairs of a context (eppm_tfilter_*).  ctx: an EPPM or an
+    EPPMBatch; one slot per pair of it.  Every step() moves the active pairs' slots from image 1 to image 2 of the context's last
+    compute_flow_bidirectional*.  The filter is its own allocation on the context's device; close() frees it."""
+
+    def __init__(self, ctx, thresh=40.0, n_max=8, size=None, slots=1, device=0):
+        """ctx None: a filter without a context, for step_frames on caller planes (eppm_tfilter_create_size): size = (h, w), `slots` slots."""
+        self._f = C.c_void_p()
+        self.ctx = ctx
+        self.params = CTFilterParams(float(thresh), int(n_max))
+        if ctx is None:
+            self.h, self.w, self.nslots = int(size[0]), int(size[1]), int(slots)
+            check(lib().eppm_tfilter_create_size(self.h, self.w, self.nslots, int(device), C.byref(self.params), C.byref(self._f)),
+                  "eppm_tfilter_create_size")
+            return
+        check(lib().eppm_tfilter_create(ctx._ctx, C.byref(self.params), C.byref(self._f)), "eppm_tfilter_create")
+        self.h, self.w = ctx.h, ctx.w
+        self.nslots = int(lib().eppm_batch_size(ctx._ctx))
+
+    def step(self, cut=None, ctx=None):
+        """One step of every active pair's slot; cut: None, or one flag per active pair (true: the pair's image 2 is the first frame of
+        another clip).  Asynchronous on the context's stream."""
+        c = self.ctx if ctx is None else ctx
+        flags = None if cut is None else (C.c_uint8 * len(cut))(*[int(bool(x)) for x in cut])
+        if flags is not None and len(cut) != getattr(c, "n", 1):
+            raise EppmError("TemporalFilter.step: one cut flag per active pair")
+        check(lib().eppm_tfilter_step(self._f, c._ctx, flags), "eppm_tfilter_step")
+
+    def step_frames(self, slot, d_rgba1, d_rgba2, pitch, d_flow_bwd, d_occ2, cut=False):
+        """eppm_tfilter_step_frames: one step of one slot on caller device planes (addresses), synchronous."""
+        check(lib().eppm_tfilter_step_frames(self._f, int(slot), C.c_void_p(d_rgba1), C.c_void_p(d_rgba2), C.c_size_t(pitch),
+                                             C.c_void_p(d_flow_bwd), C.c_void_p(d_occ2), int(bool(cut))), "eppm_tfilter_step_frames")
+
+    def frame(self, slot=0):
+        """(h, w, 3) uint8: the slot's filtered frame."""
+        rgb = np.empty((self.h, self.w, 3), np.uint8)
+        check(lib().eppm_tfilter_get(self._f, int(slot), rgb.ctypes.data_as(C.c_void_p), C.c_size_t(self.w * 3)), "eppm_tfilter_get")
+        return rgb
+
+    def frames(self):
+        """The filtered frames of the context's active pairs' slots."""
+        return [self.frame(k) for k in range(getattr(self.ctx, "n", 1))]
+
+    def frame_device(self, slot, d_rgba, pitch):
+        check(lib().eppm_tfilter_get_device(self._f, int(slot), C.c_void_p(d_rgba), C.c_size_t(pitch)), "eppm_tfilter_get_device")
+
+    def state(self, slot=0):
+        """(h, w, 4) float32 {R, G, B, n}: the slot's state."""
+        acc = np.empty((self.h, self.w, 4), np.float32)
+        check(lib().eppm_tfilter_get_state(self._f, int(slot), acc.ctypes.data_as(C.c_void_p)), "eppm_tfilter_get_state")
+        return acc
+
+    def set_state(self, slot, acc):
+        acc = np.ascontiguousarray(acc, np.float32)
+        if acc.shape != (self.h, self.w, 4):
+            raise EppmError(f"TemporalFilter.set_state: the state must be ({self.h},{self.w},4) float32")
+        check(lib().eppm_tfilter_set_state(self._f, int(slot), acc.ctypes.data_as(C.c_void_p)), "eppm_tfilter_set_state")
+
+    def reset(self, slot=None):
+        """The slot is empty again (slot=None: every slot): its next step starts from its pair's image 1."""
+        check(lib().eppm_tfilter_reset(self._f, -1 if slot is None else int(slot)), "eppm_tfilter_reset")
+
+    def close(self):
+        if self._f:
+            lib().eppm_tfilter_destroy(self._f)
+            self._f = C.c_void_p()
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
 def _level(level):
     """a stop level as a plain int; anything that is not an integer is refused before the library is touched"""
     if isinstance(level, (bool, np.bool_)) or not isinstance(level, (int, np.integer)):
@@ -235,6 +309,73 @@ def flow_sequences(clips, slots=8, params=None, temporal=True, bidirectional=Fal
                 if keep:
                     out[c].append(r)
     finally:
+        if e is not None:
+            e.close()
+    return out
+
+
+def denoise_sequence(frames, params=None, thresh=40.0, n_max=8, temporal=True, stop_level=0):
+    """A clip ((h, w, 3) uint8 frames) denoised by the motion-compensated temporal filter (TemporalFilter): one
+    streaming context -- set_data, then push_frame --, one bidirectional call on the device and one filter step per pair.  Returns
+    len(frames) frames; the first is the input itself.  Memory does not grow with the clip.  params: the flow's eppm Params; temporal /
+    stop_level: the flow's temporal and draft modes."""
+    stop_level = _level(stop_level)
+    frames = [np.ascontiguousarray(f, np.uint8) for f in frames]
+    if len(frames) < 2:
+        raise EppmError("denoise_sequence: at least two frames")
+    h, w, _ = frames[0].shape
+    e = EPPM(params=params)
+    flt = None
+    out = [frames[0].copy()]
+    try:
+        e.init(h, w)
+        e.set_temporal(temporal)
+        e.set_stop_level(stop_level)
+        flt = TemporalFilter(e, thresh, n_max)
+        for k in range(len(frames) - 1):
+            if k == 0:
+                e.set_data(frames[0], frames[1])
+            else:
+                e.push_frame(frames[k + 1])
+            e.compute_flow_bidirectional_device()
+            flt.step()
+            out.append(flt.frame(0))
+    finally:
+        if flt is not None:
+            flt.close()
+        e.close()
+    return out
+
+
+def denoise_sequences(clips, slots=8, params=None, thresh=40.0, n_max=8, temporal=True, stop_level=0):
+    """denoise_sequence for many clips at once: clips of one frame size and of any lengths (two frames at least) through ONE batch context
+    of min(slots, len(clips)) slots and one TemporalFilter, on flow_sequences' schedule.  A slot that takes the next clip of the queue
+    passes `cut` for that step: its output is that clip's frame 0.  Returns one list of frames per clip, each what denoise_sequence(clip)
+    returns."""
+    stop_level = _level(stop_level)
+    clips = [[np.ascontiguousarray(f, np.uint8) for f in clip] for clip in clips]
+    plan = _sequence_plan([len(c) for c in clips], slots)
+    h, w, _ = clips[0][0].shape
+    out = [[c[0].copy()] for c in clips]
+    e = flt = None
+    try:
+        for t, step in enumerate(plan):
+            if t == 0:
+                e = EPPMBatch(h, w, len(step), params=params)
+                e.set_temporal(temporal)
+                e.set_stop_level(stop_level)
+                flt = TemporalFilter(e, thresh, n_max)
+                e.set_data([(clips[c][0], clips[c][1]) for c, _, _, _ in step])
+            else:
+                e.push_frames([clips[c][f] for c, f, _, _ in step], [cut for _, _, cut, _ in step])
+            e.compute_flow_bidirectional_device()
+            flt.step([cut for _, _, cut, _ in step])
+            for slot, (c, _, _, keep) in enumerate(step):
+                if keep:
+                    out[c].append(flt.frame(slot))
+    finally:
+        if flt is not None:
+            flt.close()
         if e is not None:
             e.close()
     return out
@@ -669,6 +810,11 @@ class EPPMBatch:
         o = [[np.empty((self.h, self.w), np.uint8) for _ in range(self.n)] for _ in range(2)]
         check(lib().eppm_batch_compute_bidirectional(self._ctx, *[self._ptrs(t) for t in f + o]), "eppm_batch_compute_bidirectional")
         return list(zip(*f, *o))
+
+    def compute_flow_bidirectional_device(self):
+        """eppm_compute_bidirectional_device on every active pair: asynchronous, the results stay in the context (plane(), interpolate(),
+        Tracker, TemporalFilter)."""
+        check(lib().eppm_compute_bidirectional_device(self._ctx, None, None, None, None), "eppm_compute_bidirectional_device")
 
     def set_occlusion_params(self, alpha=0.01, beta=0.5):
         check(lib().eppm_set_occlusion_params(self._ctx, C.c_float(alpha), C.c_float(beta)), "eppm_set_occlusion_params")

@@ -1,4 +1,5 @@
-// ctx_interp.cpp -- what reads the results of a context's (context.h) last bidirectional call: frame interpolation and the tracker.
+// ctx_interp.cpp -- what reads the results of a context's (context.h) last bidirectional call: frame interpolation, the tracker and the
+// temporal filter.
 #include "context.h"
 #include "interp.h"
 
@@ -128,6 +129,30 @@ int ctx_track_inputs(eppm_ctx* c, int pair, int h, int w, int device, const char
     in->bwd = c->of_bwd_pair(c->bflow[0], pair);
     in->h = c->h;
     in->w = c->w;
+    *s = c->stream;
+    return EPPM_OK;
+}
+
+// ---- motion-compensated temporal filter (tfilter.cpp): the raw frames, the level-0 backward flow and occ2 of every
+// active pair, in the window of eppm_interpolate* ----
+
+int ctx_tfilter_inputs(eppm_ctx* c, int h, int w, int device, int nslots, const char* what, TFilterArgs* in, hipStream_t* s)
+{
+    if (c->h != h || c->w != w || c->device != device)
+        return set_err(EPPM_ERR_ARG, "%s: the filter is %dx%d on device %d, the context %dx%d on device %d", what, w, h, device, c->w, c->h, c->device);
+    if (c->n_active > nslots) return set_err(EPPM_ERR_ARG, "%s: the context has %d active pairs, the filter %d slots", what, c->n_active, nslots);
+    if (c->flow_pending) return set_err(EPPM_ERR_STATE, "%s: an eppm_compute_begin is pending", what);
+    if (!c->have_bwd || !c->bwd_images) return set_err(EPPM_ERR_STATE, "%s: needs a bidirectional call on the current images", what);
+    HIPCHK(hipSetDevice(c->device));
+    in->img1 = (const uint8_t*)c->raw1;
+    in->img2 = (const uint8_t*)c->raw2;
+    in->img_pitch = c->raw_pitch;
+    in->img_stride = c->stride;
+    in->bwd = c->bflow[0];
+    in->bwd_stride = c->bwd_stride;
+    in->occ2 = c->occ2;
+    in->occ_stride = c->bwd_stride;
+    in->n = c->n_active;
     *s = c->stream;
     return EPPM_OK;
 }

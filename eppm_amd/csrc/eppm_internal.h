@@ -311,6 +311,31 @@ void launch_track_advance(const TrackDev& d, const TrackIn& in, const TrackRec* 
 void launch_track_seed(const TrackDev& d, const TrackIn& in, hipStream_t s);
 void launch_track_compact(const TrackDev& d, const TrackIn& in, const TrackRec* cur, TrackRec* next, hipStream_t s);
 
+// ---- motion-compensated temporal filter (k_tfilter.hip; the per-pixel arithmetic: tfilter.h) ----
+// One launch steps n pairs: pair k's inputs (image 1 / image 2: RGBA words, img_pitch bytes per row; bwd: h*w float2; occ2: h*w bytes) lie
+// k * (their stride) bytes past pair 0's and feed slot slot0 + k, whose block (state 0 | state 1: h*w float4 each | out: h*w RGBA words)
+// lies (slot0 + k) * slot_stride bytes past slot 0's.  The per-slot bits travel in the kernel arguments as TemporalArgs::armed does: cur
+// (which state is the previous one; the step writes the other), empty (the slot has no state: the previous state is image 1's seed) and
+// cut (image 2 starts another clip), so a step costs no copy, no allocation and no synchronisation.
+struct TFilterArgs {
+    const uint8_t* img1;
+    const uint8_t* img2;
+    size_t img_pitch, img_stride;
+    const float* bwd;
+    size_t bwd_stride;
+    const uint8_t* occ2;
+    size_t occ_stride;
+    float* st0;
+    float* st1;
+    uint32_t* out;
+    size_t slot_stride;
+    int h, w, n, slot0;
+    float thresh;
+    int n_max;
+    uint32_t cur[kTemporalMaxSlots / 32], empty[kTemporalMaxSlots / 32], cut[kTemporalMaxSlots / 32];
+};
+void launch_tfilter_step(const TFilterArgs& a, hipStream_t s);
+
 // ---- flow colour coding (k_color.hip) ----
 // rgba: h*w packed R | G<<8 | B<<16 (alpha 0); flow: h*w float2
 void launch_flow_to_color(uint32_t* rgba, const float* flow, int h, int w, float max_disp_x, float max_disp_y, hipStream_t s, Batch bt = kOnePair);

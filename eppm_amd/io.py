@@ -171,3 +171,38 @@ def track_step_host(img1, img2, u, v, bu, bv, ids=(), starts=(), xy=(), next_id=
     n, m = c["live"], c["ended"]
     return dict(ids=o_ids[:n].copy(), starts=o_st[:n].copy(), xy=o_xy[:n].copy(), ended_ids=e_ids[:m].copy(), ended_starts=e_st[:m].copy(),
                 ended_xy=e_xy[:m].copy(), reasons=why[:m].copy(), **c)
+
+
+def _tfilter_params(thresh, n_max):
+    from ._lib import CTFilterParams
+    return CTFilterParams(float(thresh), int(n_max))
+
+
+def tfilter_seed_host(img):
+    """(h, w, 4) float32 {R, G, B, 1}: the temporal filter's state of a clip's first frame (eppm_tfilter_seed_host)."""
+    a = np.ascontiguousarray(img, np.uint8)
+    if a.ndim != 3 or a.shape[2] != 3:
+        raise ValueError("tfilter_seed_host: the image must be (h, w, 3)")
+    h, w, _ = a.shape
+    acc = np.empty((h, w, 4), np.float32)
+    check(lib().eppm_tfilter_seed_host(acc.ctypes.data_as(C.c_void_p), a.ctypes.data_as(C.c_void_p), h, w), "eppm_tfilter_seed_host")
+    return acc
+
+
+def tfilter_step_host(acc, img2, bu, bv, occ2, thresh=40.0, n_max=8, cut=False):
+    """One step of the temporal filter on the host (eppm_tfilter_step_host; bit-identical to the kernel).  acc: the
+    (h, w, 4) float32 state of image 1; img2: the new (h, w, 3) uint8 frame; (bu, bv): the backward flow image 2 -> image 1; occ2: the
+    occlusion mask of image 2's pixels; cut: img2 starts another clip.  Returns (new state, filtered (h, w, 3) uint8 frame)."""
+    p = _tfilter_params(thresh, n_max)
+    acc = np.ascontiguousarray(acc, np.float32)
+    b = np.ascontiguousarray(img2, np.uint8)
+    bu = np.ascontiguousarray(bu, np.float32)
+    bv = np.ascontiguousarray(bv, np.float32)
+    o = np.ascontiguousarray(occ2, np.uint8)
+    h, w = bu.shape
+    if acc.shape != (h, w, 4) or b.shape != (h, w, 3) or bv.shape != (h, w) or o.shape != (h, w):
+        raise ValueError("tfilter_step_host: state (h, w, 4), image (h, w, 3), flow and mask (h, w)")
+    out, rgb = np.empty((h, w, 4), np.float32), np.empty((h, w, 3), np.uint8)
+    check(lib().eppm_tfilter_step_host(C.byref(p), out.ctypes.data_as(C.c_void_p), rgb.ctypes.data_as(C.c_void_p),
+                                       *[x.ctypes.data_as(C.c_void_p) for x in (acc, b, bu, bv, o)], h, w, int(bool(cut))), "eppm_tfilter_step_host")
+    return out, rgb

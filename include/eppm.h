@@ -338,6 +338,56 @@ int  eppm_batch_temporal_reset(eppm_ctx* ctx, int pair);          /* the slot's 
  * one gather launch for all of them; armed: NULL (all) or npairs bytes (host memory), an unarmed slot gets "no prior" everywhere */
 int  eppm_temporal_prior_batch(eppm_short2* d_prior, const eppm_short2* d_prev, int h, int w, int backward, int npairs, const uint8_t* armed);
 
+/* ----------------------------------------------------------------------------------------
+ * motion-compensated temporal denoising: a recursive filter that averages every pixel of a streamed clip along its
+ * own trajectory.  A filter holds one slot per pair of its context: per pixel the running mean {R, G, B} and the count n of the frames in
+ * it (h*w float4, row-major).  One step moves every covered slot from image 1 to image 2 of its pair: a pixel whose backward vector is
+ * known, stays inside the frame and is not occluded (occ2 == 0) samples the previous state bilinearly at its source, and if the sample is
+ * within thresh of the new pixel (sum of the three absolute differences) blends the new pixel in with weight 1 / n, n = min(n_prev + 1,
+ * n_max); every other pixel starts again from the new frame with n = 1.  The kernel equals eppm_tfilter_step_host bit for bit, in both
+ * libraries.  A filter is a separate allocation on its context's device (36 bytes per pixel and slot: two states and the RGBA output), made
+ * by eppm_tfilter_create and freed by eppm_tfilter_destroy; a context that never creates one allocates and launches exactly what it did
+ * without.  A slot that has never been stepped, or after eppm_tfilter_reset, is empty: its first step reads the seed of image 1
+ * ({R, G, B, 1}) as the previous state.
+ * -------------------------------------------------------------------------------------- */
+typedef struct eppm_tfilter_params {
+    float thresh;                /* largest |dR| + |dG| + |dB| between the new pixel and the compensated mean that still blends (40); finite, >= 0 */
+    int   n_max;                 /* the longest average, 1 .. 255 (8) */
+} eppm_tfilter_params;
+typedef struct eppm_tfilter eppm_tfilter;
+
+int  eppm_tfilter_default_params(eppm_tfilter_params* p);
+/* p NULL: the defaults.  One slot per pair of ctx (eppm_batch_size), on its device; every slot empty. */
+int  eppm_tfilter_create(eppm_ctx* ctx, const eppm_tfilter_params* p, eppm_tfilter** out);
+/* a filter without a context, for eppm_tfilter_step_frames on caller planes: nslots slots of h x w pixels (any size from 1 x 1) on `device` */
+int  eppm_tfilter_create_size(int h, int w, int nslots, int device, const eppm_tfilter_params* p, eppm_tfilter** out);
+int  eppm_tfilter_destroy(eppm_tfilter* f);                 /* NULL is fine */
+int  eppm_tfilter_reset(eppm_tfilter* f, int slot);         /* the slot is empty again; slot < 0: every slot */
+/* One step of slots 0 .. active pairs - 1 on the pairs of ctx's last eppm_compute_bidirectional* (the raw frames, the level-0 backward flow
+ * and occ2): valid in the window of eppm_interpolate* (EPPM_ERR_STATE outside it); EPPM_ERR_ARG for a context of other dimensions, another
+ * device or more active pairs than the filter has slots.  cut: NULL, or one flag per active pair; non-zero: image 2 of that pair is the
+ * first frame of another clip, the slot's state becomes its seed.  A slot the step does not cover keeps its state.  One launch,
+ * asynchronous on the context's stream: no copy, no allocation, no host synchronisation. */
+int  eppm_tfilter_step(eppm_tfilter* f, eppm_ctx* ctx, const uint8_t* cut);
+/* the same step of one slot on caller device planes of the filter's size (RGBA images of `pitch` bytes per row, h*w float2 backward flow,
+ * h*w mask bytes); on the launcher stream, synchronous.  d_rgba1 is read only if the slot is empty.  Whatever the planes hold, nothing
+ * outside them is read. */
+int  eppm_tfilter_step_frames(eppm_tfilter* f, int slot, const void* d_rgba1, const void* d_rgba2, size_t pitch, const eppm_float2* d_flow_bwd,
+                              const uint8_t* d_occ2, int cut);
+/* the slot's filtered frame (EPPM_ERR_STATE on an empty slot): packed RGB to the host, synchronous ... */
+int  eppm_tfilter_get(eppm_tfilter* f, int slot, uint8_t* rgb, size_t row_stride);
+/* ... or RGBA words (alpha 255) into a device plane, asynchronous on the stream of the filter's last step */
+int  eppm_tfilter_get_device(eppm_tfilter* f, int slot, void* d_rgba, size_t pitch);
+/* synchronous.  The slot's state, h*w*4 floats {R, G, B, n} (EPPM_ERR_STATE on an empty slot) / load one: the slot is no longer empty */
+int  eppm_tfilter_get_state(eppm_tfilter* f, int slot, float* acc);
+int  eppm_tfilter_set_state(eppm_tfilter* f, int slot, const float* acc);
+/* host forms (no GPU needed): the seed of a packed RGB frame, and one step from acc_in (image 1's state) to acc_out and the packed RGB
+ * output rgb_out; rgb2: image 2, (bu, bv): the backward flow, occ2: the mask.  acc_out must not be acc_in.  The step of an empty slot is
+ * eppm_tfilter_seed_host(image 1) followed by this. */
+int  eppm_tfilter_seed_host(float* acc, const uint8_t* rgb, int h, int w);
+int  eppm_tfilter_step_host(const eppm_tfilter_params* p, float* acc_out, uint8_t* rgb_out, const float* acc_in, const uint8_t* rgb2,
+                            const float* bu, const float* bv, const uint8_t* occ2, int h, int w, int cut);
+
 /* Per-stage device times in ms (hipEvent pairs on the context's stream), one entry per stage per
  * call since the last eppm_clear_stage_times (names repeat across calls; prepare entries first).
  * names[i] points to static strings.  Returns the number of entries written (<= max). */
@@ -348,7 +398,7 @@ int  eppm_clear_stage_times(eppm_ctx* ctx);
  * "flow_blf_bwd_L<l>", "flow_blf_bwd_final" and "fb_occlusion"; an interpolation call "interp_splat", "interp_fill" and "interp_blend"
  * (mode 1, once per group of four times); a track step "track_advance", "track_seed" and "track_compact" (mode 1; the step that seeds
  * frame 0 adds a "track_seed" before "track_advance"); a compute that starts from a temporal prior "temporal_advect" (before "patchmatch") and
- * "temporal_select" (inside it: "patchmatch" includes its time).  Events come from a per-context pool: none is created in a steady-state step. */
+ * "temporal_select" (inside it: "patchmatch" includes its time); a temporal-filter step "tfilter_step".  Events come from a per-context pool: none is created in a steady-state step. */
 int  eppm_enable_stage_timing(eppm_ctx* ctx, int on);
 
 const char* eppm_last_error(void);

@@ -31,6 +31,10 @@
 //                     --temporal 1 (default): every pair after the first starts PatchMatch from the previous pair's result moved
 //                     along its motion; 0: every pair is a cold run (bit for bit the two-image form's flow).  Of the options above
 //                     --seed, --levels, --patch-r, --iters, --propagation and --stop-level apply.
+//                     --denoise: every pair runs the bidirectional call (the forward flows written are the same) followed by one step
+//                     of the motion-compensated temporal filter; the filtered frames are written to
+//                     P_dn_0000.ppm (the first frame itself), P_dn_0001.ppm ...  --denoise-thresh T (default 40) and
+//                     --denoise-frames N (the longest average, default 8) set its parameters and imply --denoise.
 #include <atomic>
 #include <chrono>
 #include <cstdio>
@@ -66,6 +70,9 @@ struct Options {
     const char* prefix = nullptr;                           // --out-prefix
     int temporal = 1;                                       // --temporal
     int stop_level = 0;                                     // --stop-level
+    bool denoise = false;                                   // --denoise
+    float dn_thresh = 40.0f;                                // --denoise-thresh
+    int dn_frames = 8;                                      // --denoise-frames
 };
 
 static unsigned hash32(unsigned x)
@@ -116,11 +123,21 @@ static int usage()
                     "               [--pin] [--pairs P] [--gpus G] [--batch B] [--gt file.flo] [--out file.flo] [--backward file.flo]\n"
                     "               [--occlusion file.pgm] [--interpolate T file.ppm]... [img1.ppm img2.ppm [out.flo]]\n"
                     "       runeppm [--seed N] [--levels N] [--patch-r N] [--iters N] [--propagation M] [--stop-level N]\n"
-                    "               --sequence f0.ppm f1.ppm [f2.ppm ...] --out-prefix P [--temporal 0|1]\n");
+                    "               --sequence f0.ppm f1.ppm [f2.ppm ...] --out-prefix P [--temporal 0|1]\n"
+                    "               [--denoise] [--denoise-thresh T] [--denoise-frames N]\n");
     return 2;
 }
 
-// --sequence: the clip through one context of the C ABI (frame push, temporal mode)
+static bool write_ppm(const char* name, const unsigned char* rgb, int h, int w)
+{
+    FILE* f = fopen(name, "wb");
+    if (!f) return false;
+    bool ok = fprintf(f, "P6\n%d %d\n255\n", w, h) > 0 && fwrite(rgb, 1, (size_t)h * w * 3, f) == (size_t)h * w * 3;
+    ok = fclose(f) == 0 && ok;
+    return ok;
+}
+
+// --sequence: the clip through one context of the C ABI (frame push, temporal mode; --denoise: the temporal filter on top)
 static int run_sequence(const Options& o)
 {
     eppm_params prm;
@@ -137,8 +154,16 @@ static int run_sequence(const Options& o)
     std::vector<std::vector<unsigned char>> img(2, std::vector<unsigned char>((size_t)h * w * 3));
     std::vector<float> u((size_t)h * w), v((size_t)h * w);
     eppm_ctx* ctx = nullptr;
-    auto fail = [&](const char* what) { fprintf(stderr, "%s: %s\n", what, eppm_last_error()); if (ctx) eppm_destroy(ctx); return 1; };
+    eppm_tfilter* flt = nullptr;
+    auto fail = [&](const char* what) { fprintf(stderr, "%s: %s\n", what, eppm_last_error()); eppm_tfilter_destroy(flt); if (ctx) eppm_destroy(ctx); return 1; };
     if (eppm_create(&ctx, h, w, 0, &prm) != EPPM_OK) return fail("eppm_create");
+    std::vector<unsigned char> dn;
+    char name[4096];
+    if (o.denoise) {
+        const eppm_tfilter_params tp = {o.dn_thresh, o.dn_frames};
+        if (eppm_tfilter_create(ctx, &tp, &flt) != EPPM_OK) return fail("eppm_tfilter_create");
+        dn.resize((size_t)h * w * 3);
+    }
     if (eppm_set_temporal(ctx, o.temporal) != EPPM_OK) return fail("eppm_set_temporal");
     if (eppm_set_stop_level(ctx, o.stop_level) != EPPM_OK) { fprintf(stderr, "--stop-level: %s\n", eppm_last_error()); eppm_destroy(ctx); return usage(); }
     double total = 0;
@@ -147,22 +172,38 @@ static int run_sequence(const Options& o)
         std::vector<unsigned char>& cur = img[k == 0 ? 0 : 1];
         if (eppm_ppm_size(o.seq[k], &hk, &wk) != EPPM_OK || hk != h || wk != w || eppm_load_ppm(o.seq[k], cur.data(), h, w, &nch) != EPPM_OK) {
             fprintf(stderr, "cannot read %s (or its size differs from the first frame's)\n", o.seq[k]);
+            eppm_tfilter_destroy(flt);
             eppm_destroy(ctx);
             return 1;
         }
-        if (k == 0) continue;
+        if (k == 0) {
+            if (o.denoise) {
+                snprintf(name, sizeof name, "%s_dn_0000.ppm", o.prefix);
+                if (!write_ppm(name, cur.data(), h, w)) { fprintf(stderr, "cannot write %s\n", name); eppm_tfilter_destroy(flt); eppm_destroy(ctx); return 1; }
+            }
+            continue;
+        }
         const auto t0 = std::chrono::steady_clock::now();
         if (k == 1) { if (eppm_set_images(ctx, img[0].data(), img[1].data(), (size_t)w * 3) != EPPM_OK) return fail("eppm_set_images"); }
         else if (eppm_push_image(ctx, cur.data(), (size_t)w * 3) != EPPM_OK) return fail("eppm_push_image");
-        if (eppm_compute(ctx, u.data(), v.data()) != EPPM_OK) return fail("eppm_compute");
+        if (!o.denoise) { if (eppm_compute(ctx, u.data(), v.data()) != EPPM_OK) return fail("eppm_compute"); }
+        else {
+            if (eppm_compute_bidirectional(ctx, u.data(), v.data(), nullptr, nullptr, nullptr, nullptr) != EPPM_OK) return fail("eppm_compute_bidirectional");
+            if (eppm_tfilter_step(flt, ctx, nullptr) != EPPM_OK) return fail("eppm_tfilter_step");
+            if (eppm_tfilter_get(flt, 0, dn.data(), (size_t)w * 3) != EPPM_OK) return fail("eppm_tfilter_get");
+        }
         const double ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
         total += ms;
-        char name[4096];
         snprintf(name, sizeof name, "%s_%04zu.flo", o.prefix, k);
-        if (eppm_save_flo(name, u.data(), v.data(), h, w) != EPPM_OK) { fprintf(stderr, "cannot write %s\n", name); eppm_destroy(ctx); return 1; }
+        if (eppm_save_flo(name, u.data(), v.data(), h, w) != EPPM_OK) { fprintf(stderr, "cannot write %s\n", name); eppm_tfilter_destroy(flt); eppm_destroy(ctx); return 1; }
         printf("pair %zu: %.3f ms%s -> %s\n", k, ms, (o.temporal && k > 1) ? " (seeded)" : "", name);
+        if (o.denoise) {
+            snprintf(name, sizeof name, "%s_dn_%04zu.ppm", o.prefix, k);
+            if (!write_ppm(name, dn.data(), h, w)) { fprintf(stderr, "cannot write %s\n", name); eppm_tfilter_destroy(flt); eppm_destroy(ctx); return 1; }
+        }
     }
     printf("%zu pairs, %.3f ms per pair\n", o.seq.size() - 1, total / (double)(o.seq.size() - 1));
+    eppm_tfilter_destroy(flt);
     eppm_destroy(ctx);
     return 0;
 }
@@ -206,6 +247,15 @@ int main(int argc, char** argv)
         }
         else if (!strcmp(a, "--sequence")) { while (i + 1 < argc && !(argv[i + 1][0] == '-' && argv[i + 1][1] == '-')) o.seq.push_back(argv[++i]); if (o.seq.empty()) return usage(); }
         else if (!strcmp(a, "--out-prefix")) { if (i + 1 >= argc) return usage(); o.prefix = argv[++i]; }
+        else if (!strcmp(a, "--denoise")) o.denoise = true;
+        else if (!strcmp(a, "--denoise-thresh")) {
+            if (i + 1 >= argc) return usage();
+            char* end = nullptr;
+            o.dn_thresh = strtof(argv[++i], &end);
+            if (!end || end == argv[i] || *end) return usage();
+            o.denoise = true;
+        }
+        else if (!strcmp(a, "--denoise-frames")) { if (!val(&v) || v < 1 || v > 255) return usage(); o.dn_frames = (int)v; o.denoise = true; }
         else if (!strcmp(a, "--temporal")) { if (!val(&v) || (v != 0 && v != 1)) return usage(); o.temporal = (int)v; }
         else if (a[0] == '-' && a[1] == '-') return usage();
         else pos.push_back(a);
@@ -220,6 +270,7 @@ int main(int argc, char** argv)
             return usage();
         return run_sequence(o);
     }
+    if (o.denoise) return usage();             // the filter walks a clip
     if (pos.size() == 1 || pos.size() > 3) return usage();
     if (pos.size() >= 2) { o.f1 = pos[0]; o.f2 = pos[1]; }
     if (pos.size() == 3) o.fo = pos[2];
