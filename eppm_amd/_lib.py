@@ -24,6 +24,19 @@ class CTFilterParams(C.Structure):
     _fields_ = [("thresh", C.c_float), ("n_max", C.c_int)]
 
 
+class CStabParams(C.Structure):
+    _fields_ = [("tau", C.c_float), ("iters", C.c_int), ("smooth", C.c_float)]
+
+
+class CGMotionModel(C.Structure):
+    _fields_ = [("p", C.c_double * 6), ("n_valid", C.c_int64), ("n_inliers", C.c_int64), ("valid", C.c_int), ("passes", C.c_int)]
+
+    def as_dict(self):
+        import numpy as np
+        return dict(p=np.array(self.p[:], np.float64), n_valid=int(self.n_valid), n_inliers=int(self.n_inliers), valid=int(self.valid),
+                    passes=int(self.passes))
+
+
 class CTrackCounts(C.Structure):
     _fields_ = [("live", C.c_int), ("ended", C.c_int), ("seeded", C.c_int), ("dropped", C.c_int), ("frame", C.c_int), ("next_id", C.c_int)]
 
@@ -65,6 +78,9 @@ SYMBOLS = [
     "eppm_tfilter_default_params", "eppm_tfilter_create", "eppm_tfilter_create_size", "eppm_tfilter_destroy", "eppm_tfilter_reset", "eppm_tfilter_step",
     "eppm_tfilter_step_frames", "eppm_tfilter_get", "eppm_tfilter_get_device", "eppm_tfilter_get_state", "eppm_tfilter_set_state",
     "eppm_tfilter_seed_host", "eppm_tfilter_step_host",
+    "eppm_stab_default_params", "eppm_stab_create", "eppm_stab_create_size", "eppm_stab_destroy", "eppm_stab_reset", "eppm_stab_step",
+    "eppm_stab_step_frames", "eppm_stab_get", "eppm_stab_get_device", "eppm_stab_get_mask", "eppm_stab_get_model", "eppm_stab_get_path",
+    "eppm_stab_set_path", "eppm_gmotion_fit_host", "eppm_stab_update_host", "eppm_stab_warp_host",
 ]
 
 

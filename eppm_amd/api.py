@@ -3,7 +3,7 @@ import ctypes as C
 
 import numpy as np
 
-from ._lib import CParams, CTFilterParams, CTrackCounts, CTrackParams, EppmError, check, lib
+from ._lib import CGMotionModel, CParams, CStabParams, CTFilterParams, CTrackCounts, CTrackParams, EppmError, check, lib
 
 uchar4 = np.dtype([("x", "u1"), ("y", "u1"), ("z", "u1"), ("w", "u1")])
 short2 = np.dtype([("x", "i2"), ("y", "i2")])
@@ -220,6 +220,97 @@ class TemporalFilter:
             pass
 
 
+class Stabilizer:
+    """Global camera motion and video stabilisation over the pairs of a context (eppm_stab_*).  ctx: an EPPM or an
+    EPPMBatch; one slot per pair of it.  Every step() fits the camera motion of the active pairs of the context's last
+    compute_flow_bidirectional*, moves the slots' paths and renders image 2 from the smoothed camera.  The stabiliser is its own allocation
+    on the context's device; close() frees it."""
+
+    def __init__(self, ctx, tau=1.0, iters=3, smooth=0.9, size=None, slots=1, device=0):
+        """ctx None: a stabiliser without a context, for step_frames on caller planes (eppm_stab_create_size): size = (h, w), `slots` slots."""
+        self._f = C.c_void_p()
+        self.ctx = ctx
+        self.params = CStabParams(float(tau), int(iters), float(smooth))
+        if ctx is None:
+            if size is None or len(size) != 2:
+                raise EppmError("Stabilizer: without a context, size=(h, w) is required")
+            self.h, self.w, self.nslots = int(size[0]), int(size[1]), int(slots)
+            check(lib().eppm_stab_create_size(self.h, self.w, self.nslots, int(device), C.byref(self.params), C.byref(self._f)),
+                  "eppm_stab_create_size")
+            return
+        check(lib().eppm_stab_create(ctx._ctx, C.byref(self.params), C.byref(self._f)), "eppm_stab_create")
+        self.h, self.w = ctx.h, ctx.w
+        self.nslots = int(lib().eppm_batch_size(ctx._ctx))
+
+    def step(self, cut=None, ctx=None):
+        """One step of every active pair's slot; cut: None, or one flag per active pair (true: the pair's image 2 is the first frame of
+        another clip).  Asynchronous on the context's stream."""
+        c = self.ctx if ctx is None else ctx
+        flags = None if cut is None else (C.c_uint8 * len(cut))(*[int(bool(x)) for x in cut])
+        if flags is not None and len(cut) != getattr(c, "n", 1):
+            raise EppmError("Stabilizer.step: one cut flag per active pair")
+        check(lib().eppm_stab_step(self._f, c._ctx, flags), "eppm_stab_step")
+
+    def step_frames(self, slot, d_rgba2, pitch, d_flow, d_occ1, cut=False):
+        """eppm_stab_step_frames: one step of one slot on caller device planes (addresses), synchronous."""
+        check(lib().eppm_stab_step_frames(self._f, int(slot), C.c_void_p(d_rgba2), C.c_size_t(pitch), C.c_void_p(d_flow), C.c_void_p(d_occ1),
+                                          int(bool(cut))), "eppm_stab_step_frames")
+
+    def frame(self, slot=0):
+        """(h, w, 3) uint8: the slot's stabilised frame."""
+        rgb = np.empty((self.h, self.w, 3), np.uint8)
+        check(lib().eppm_stab_get(self._f, int(slot), rgb.ctypes.data_as(C.c_void_p), C.c_size_t(self.w * 3)), "eppm_stab_get")
+        return rgb
+
+    def frames(self):
+        """The stabilised frames of the context's active pairs' slots."""
+        return [self.frame(k) for k in range(getattr(self.ctx, "n", 1))]
+
+    def frame_device(self, slot, d_rgba, pitch):
+        check(lib().eppm_stab_get_device(self._f, int(slot), C.c_void_p(d_rgba), C.c_size_t(pitch)), "eppm_stab_get_device")
+
+    def mask(self, slot=0):
+        """(h, w) uint8: 0 the pixel of image 1 moves with the camera, 1 it moves on its own, 2 it has no valid vector."""
+        m = np.empty((self.h, self.w), np.uint8)
+        check(lib().eppm_stab_get_mask(self._f, int(slot), m.ctypes.data_as(C.c_void_p)), "eppm_stab_get_mask")
+        return m
+
+    def model(self, slot=0):
+        """The camera motion of the slot's last pair: dict(p (6 float64, displacement form), n_valid, n_inliers, valid, passes)."""
+        m = CGMotionModel()
+        check(lib().eppm_stab_get_model(self._f, int(slot), C.byref(m)), "eppm_stab_get_model")
+        return m.as_dict()
+
+    def path(self, slot=0, counts=False):
+        """(C, S): the camera path and the smoothed path, six float64 {a00, a01, a10, a11, tx, ty} each; counts=True adds (frames,
+        invalid_steps)."""
+        p = np.empty(12, np.float64)
+        n, bad = C.c_int64(), C.c_int64()
+        check(lib().eppm_stab_get_path(self._f, int(slot), p.ctypes.data_as(C.c_void_p), C.byref(n), C.byref(bad)), "eppm_stab_get_path")
+        return (p[:6].copy(), p[6:].copy(), (n.value, bad.value)) if counts else (p[:6].copy(), p[6:].copy())
+
+    def set_path(self, slot, c, s):
+        p = np.ascontiguousarray(np.concatenate([np.asarray(c, np.float64).ravel(), np.asarray(s, np.float64).ravel()]))
+        if p.shape != (12,):
+            raise EppmError("Stabilizer.set_path: C and S are six numbers each")
+        check(lib().eppm_stab_set_path(self._f, int(slot), p.ctypes.data_as(C.c_void_p)), "eppm_stab_set_path")
+
+    def reset(self, slot=None):
+        """The slot is empty again (slot=None: every slot): its next step starts from the identity."""
+        check(lib().eppm_stab_reset(self._f, -1 if slot is None else int(slot)), "eppm_stab_reset")
+
+    def close(self):
+        if self._f:
+            lib().eppm_stab_destroy(self._f)
+            self._f = C.c_void_p()
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
 def _level(level):
     """a stop level as a plain int; anything that is not an integer is refused before the library is touched"""
     if isinstance(level, (bool, np.bool_)) or not isinstance(level, (int, np.integer)):
@@ -379,6 +470,79 @@ def denoise_sequences(clips, slots=8, params=None, thresh=40.0, n_max=8, tempora
         if e is not None:
             e.close()
     return out
+
+
+def stabilize_sequence(frames, params=None, tau=1.0, iters=3, smooth=0.9, temporal=True, stop_level=0, masks=False):
+    """A clip ((h, w, 3) uint8 frames) re-rendered from a smoothed camera path (Stabilizer): one streaming context --
+    set_data, then push_frame --, one bidirectional call on the device and one stabiliser step per pair.  Returns len(frames) frames; the
+    first is the input itself.  masks=True: (frames, masks, models) with one motion mask of image 1 and one model per pair.  params: the
+    flow's eppm Params; temporal / stop_level: the flow's temporal and draft modes."""
+    stop_level = _level(stop_level)
+    frames = [np.ascontiguousarray(f, np.uint8) for f in frames]
+    if len(frames) < 2:
+        raise EppmError("stabilize_sequence: at least two frames")
+    h, w, _ = frames[0].shape
+    e = EPPM(params=params)
+    stab = None
+    out, mk, md = [frames[0].copy()], [], []
+    try:
+        e.init(h, w)
+        e.set_temporal(temporal)
+        e.set_stop_level(stop_level)
+        stab = Stabilizer(e, tau, iters, smooth)
+        for k in range(len(frames) - 1):
+            if k == 0:
+                e.set_data(frames[0], frames[1])
+            else:
+                e.push_frame(frames[k + 1])
+            e.compute_flow_bidirectional_device()
+            stab.step()
+            out.append(stab.frame(0))
+            if masks:
+                mk.append(stab.mask(0))
+                md.append(stab.model(0))
+    finally:
+        if stab is not None:
+            stab.close()
+        e.close()
+    return (out, mk, md) if masks else out
+
+
+def stabilize_sequences(clips, slots=8, params=None, tau=1.0, iters=3, smooth=0.9, temporal=True, stop_level=0, masks=False):
+    """stabilize_sequence for many clips at once: clips of one frame size and of any lengths (two frames at least) through ONE batch context
+    of min(slots, len(clips)) slots and one Stabilizer, on flow_sequences' schedule.  A slot that takes the next clip of the queue passes
+    `cut` for that step: its output is that clip's frame 0.  Returns one result per clip, each what stabilize_sequence(clip) returns."""
+    stop_level = _level(stop_level)
+    clips = [[np.ascontiguousarray(f, np.uint8) for f in clip] for clip in clips]
+    plan = _sequence_plan([len(c) for c in clips], slots)
+    h, w, _ = clips[0][0].shape
+    out = [[c[0].copy()] for c in clips]
+    mk, md = [[] for _ in clips], [[] for _ in clips]
+    e = stab = None
+    try:
+        for t, step in enumerate(plan):
+            if t == 0:
+                e = EPPMBatch(h, w, len(step), params=params)
+                e.set_temporal(temporal)
+                e.set_stop_level(stop_level)
+                stab = Stabilizer(e, tau, iters, smooth)
+                e.set_data([(clips[c][0], clips[c][1]) for c, _, _, _ in step])
+            else:
+                e.push_frames([clips[c][f] for c, f, _, _ in step], [cut for _, _, cut, _ in step])
+            e.compute_flow_bidirectional_device()
+            stab.step([cut for _, _, cut, _ in step])
+            for slot, (c, _, _, keep) in enumerate(step):
+                if keep:
+                    out[c].append(stab.frame(slot))
+                    if masks:
+                        mk[c].append(stab.mask(slot))
+                        md[c].append(stab.model(slot))
+    finally:
+        if stab is not None:
+            stab.close()
+        if e is not None:
+            e.close()
+    return [(o, m, d) for o, m, d in zip(out, mk, md)] if masks else out
 
 
 def _track_collect(out, trk):

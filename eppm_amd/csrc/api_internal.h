@@ -10,7 +10,7 @@
 //   context.cpp            eppm_ctx: create / destroy / planes / stage times (the class's init), the only one of the four that reads opt_*
 //   ctx_images.cpp         set_images, push_image, prepare, the host upload of one image (the class's set_data)
 //   ctx_compute.cpp        compute in all its forms, the post-PatchMatch branch of both directions, temporal mode (the class's compute_flow)
-//   ctx_interp.cpp         frame interpolation, the tracker's and the temporal filter's view of a context
+//   ctx_interp.cpp         frame interpolation, the tracker's, the temporal filter's and the stabiliser's view of a context
 //   device_api.cpp         device-memory plumbing of the ABI (malloc / memcpy / NUMA binding)
 //   launchers_ref_abi.cpp  the reference's live extern "C" stage launchers and the sub-stage entry points of the parity tests
 //   test_hooks.cpp         libeppm_hip_test.so only: include/eppm_test.h
@@ -166,3 +166,10 @@ EPPM_HIDDEN int ctx_tfilter_inputs(eppm_ctx* c, int h, int w, int device, int ns
 // slots slot0 .. slot0 + in.n - 1 from the input members of in; cut: NULL or one flag per pair
 EPPM_HIDDEN int tfilter_step_on(eppm_tfilter* f, eppm::TFilterArgs& in, int slot0, const uint8_t* cut, hipStream_t s, eppm_ctx* timing);
 EPPM_HIDDEN int tfilter_device(const eppm_tfilter* f, int* h, int* w, int* nslots);
+
+// ---- what a stabiliser (stabilizer.cpp) reads of a context (ctx_interp.cpp) ----
+// the input members of *in (image 2, the level-0 forward flow, occ1) for every active pair, under ctx_tfilter_inputs' rules
+EPPM_HIDDEN int ctx_stab_inputs(eppm_ctx* c, int h, int w, int device, int nslots, const char* what, eppm::StabArgs* in, hipStream_t* s);
+// the launcher stream of the context-less launchers (launchers_ref_abi.cpp) runs eppm_stab_step_frames through this (stabilizer.cpp)
+EPPM_HIDDEN int stab_step_on(eppm_stab* f, eppm::StabArgs& in, int slot0, const uint8_t* cut, hipStream_t s, eppm_ctx* timing);
+EPPM_HIDDEN int stab_device(const eppm_stab* f, int* h, int* w, int* nslots);

@@ -336,6 +336,31 @@ struct TFilterArgs {
 };
 void launch_tfilter_step(const TFilterArgs& a, hipStream_t s);
 
+// ---- global camera motion and stabilisation (k_gmotion.hip; the arithmetic: gmotion.h) ----
+// One step covers n pairs: pair k's inputs (image 2: RGBA words, img_pitch bytes per row; fwd: h*w float2; occ1: h*w bytes) lie k * (their
+// stride) bytes past pair 0's and feed slot slot0 + k, whose block lies (slot0 + k) * slot_stride bytes past `mem`: tiles_x * tiles_y slabs
+// of 128 bytes (the twelve sums of one accumulate block, 64 x 16 pixels) | GmModel | GmState (at off_model, 256 bytes together) | out:
+// h*w RGBA words (off_out) | mask: h*w bytes (off_mask).  A step is iters x (accumulate, solve) and one warp launch; `pass` is the
+// launch's pass.  The per-slot bits travel in the kernel arguments as TFilterArgs' do: empty (the slot's state is the identity whatever
+// the block holds) and cut (image 2 starts another clip).  The state is read and written by one lane of one launch, in place.
+constexpr int kGmTileW = 64, kGmTileH = 16, kGmSlabBytes = 128;
+struct StabArgs {
+    const uint8_t* img2;
+    size_t img_pitch, img_stride;
+    const float* fwd;
+    size_t fwd_stride;
+    const uint8_t* occ1;
+    size_t occ_stride;
+    char* mem;
+    size_t slot_stride, off_model, off_out, off_mask;
+    int h, w, n, slot0, tiles_x, tiles_y, iters, pass;
+    float tau2, smooth;
+    uint32_t empty[kTemporalMaxSlots / 32], cut[kTemporalMaxSlots / 32];
+};
+void launch_gmotion_accumulate(const StabArgs& a, hipStream_t s);
+void launch_gmotion_solve(const StabArgs& a, hipStream_t s);
+void launch_stab_warp(const StabArgs& a, hipStream_t s);
+
 // ---- flow colour coding (k_color.hip) ----
 // rgba: h*w packed R | G<<8 | B<<16 (alpha 0); flow: h*w float2
 void launch_flow_to_color(uint32_t* rgba, const float* flow, int h, int w, float max_disp_x, float max_disp_y, hipStream_t s, Batch bt = kOnePair);

@@ -583,6 +583,28 @@ extern "C" int eppm_tfilter_step_frames(eppm_tfilter* f, int slot, const void* d
     HIPCHK(hipStreamSynchronize(g_stream));
     return finish();
 }
+// ---- one stabiliser step of one slot on caller planes (k_gmotion.hip; the host forms: eppm_gmotion_fit_host, eppm_stab_update_host,
+// eppm_stab_warp_host) ----
+extern "C" int eppm_stab_step_frames(eppm_stab* f, int slot, const void* d_rgba2, size_t pitch, const eppm_float2* d_flow, const uint8_t* d_occ1, int cut)
+{
+    if (!f || !d_rgba2 || !d_flow || !d_occ1) return set_err(EPPM_ERR_ARG, "eppm_stab_step_frames: NULL argument");
+    int h, w, nslots;
+    const int device = stab_device(f, &h, &w, &nslots);
+    if (slot < 0 || slot >= nslots) return set_err(EPPM_ERR_ARG, "eppm_stab_step_frames: slot %d, the stabiliser has %d", slot, nslots);
+    if (pitch < (size_t)w * 4 || (pitch & 3)) return set_err(EPPM_ERR_ARG, "eppm_stab_step_frames: bad pitch %zu", pitch);
+    std::lock_guard<std::mutex> lk(g_mu);
+    int d = 0;
+    HIPCHK(hipGetDevice(&d));
+    if (d != device) return set_err(EPPM_ERR_ARG, "eppm_stab_step_frames: the stabiliser lives on device %d, the current device is %d", device, d);
+    StabArgs in{};
+    in.img2 = (const uint8_t*)d_rgba2; in.img_pitch = pitch;
+    in.fwd = (const float*)d_flow; in.occ1 = d_occ1;
+    in.n = 1;
+    const uint8_t c = cut != 0;
+    CHK(stab_step_on(f, in, slot, &c, g_stream, nullptr));
+    HIPCHK(hipStreamSynchronize(g_stream));
+    return finish();
+}
 // the C++-linkage symbol the reference's driver declares at :64 (defaults 100,100 there; the live call passes 20,20)
 void bao_cuda_convert_flow_to_colorshow(uchar4* rgbflow, float2* flow_vec, int h, int w, float max_disp_x, float max_disp_y)
 {

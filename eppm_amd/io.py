@@ -206,3 +206,63 @@ def tfilter_step_host(acc, img2, bu, bv, occ2, thresh=40.0, n_max=8, cut=False):
     check(lib().eppm_tfilter_step_host(C.byref(p), out.ctypes.data_as(C.c_void_p), rgb.ctypes.data_as(C.c_void_p),
                                        *[x.ctypes.data_as(C.c_void_p) for x in (acc, b, bu, bv, o)], h, w, int(bool(cut))), "eppm_tfilter_step_host")
     return out, rgb
+
+
+def _stab_params(tau, iters, smooth):
+    from ._lib import CStabParams
+    return CStabParams(float(tau), int(iters), float(smooth))
+
+
+def gmotion_fit_host(u, v, occ1, tau=1.0, iters=3):
+    """The camera motion of one pair on the host (eppm_gmotion_fit_host; bit-identical to the kernels).  (u, v): the
+    forward flow; occ1: the occlusion mask of image 1's pixels.  Returns (model dict as Stabilizer.model, (h, w) uint8 motion mask)."""
+    from ._lib import CGMotionModel
+    p = _stab_params(tau, iters, 0.0)
+    u = np.ascontiguousarray(u, np.float32)
+    v = np.ascontiguousarray(v, np.float32)
+    o = np.ascontiguousarray(occ1, np.uint8)
+    h, w = u.shape
+    if v.shape != (h, w) or o.shape != (h, w):
+        raise ValueError("gmotion_fit_host: flow and mask (h, w)")
+    m = CGMotionModel()
+    mask = np.empty((h, w), np.uint8)
+    check(lib().eppm_gmotion_fit_host(C.byref(p), *[x.ctypes.data_as(C.c_void_p) for x in (u, v, o)], h, w, C.byref(m),
+                                      mask.ctypes.data_as(C.c_void_p)), "eppm_gmotion_fit_host")
+    return m.as_dict(), mask
+
+
+def stab_identity():
+    """The paths of a clip's first frame: (C, S), the identity in (A, t) form."""
+    one = np.array([1.0, 0.0, 0.0, 1.0, 0.0, 0.0])
+    return one.copy(), one.copy()
+
+
+def stab_update_host(c, s, model, smooth=0.9, cut=False, counts=(0, 0)):
+    """One update of a slot's paths with a pair's model on the host (eppm_stab_update_host).  c, s: six float64 each (stab_identity() for
+    a clip's first pair); model: a dict with p and valid.  Returns (C, S, wf (6 float32), (frames, invalid_steps))."""
+    from ._lib import CGMotionModel
+    p = _stab_params(1.0, 1, smooth)
+    path = np.ascontiguousarray(np.concatenate([np.asarray(c, np.float64).ravel(), np.asarray(s, np.float64).ravel()]))
+    if path.shape != (12,):
+        raise ValueError("stab_update_host: C and S are six numbers each")
+    m = CGMotionModel()
+    m.p[:] = [float(x) for x in model["p"]]
+    m.valid = int(model["valid"])
+    n = (C.c_int64 * 2)(int(counts[0]), int(counts[1]))
+    wf = np.empty(6, np.float32)
+    check(lib().eppm_stab_update_host(C.byref(p), path.ctypes.data_as(C.c_void_p), n, C.byref(m), int(bool(cut)), wf.ctypes.data_as(C.c_void_p)),
+          "eppm_stab_update_host")
+    return path[:6].copy(), path[6:].copy(), wf, (int(n[0]), int(n[1]))
+
+
+def stab_warp_host(wf, img2):
+    """The stabilised frame on the host (eppm_stab_warp_host): the (h, w, 3) uint8 image 2 sampled at the warp wf (6 float32)."""
+    wf = np.ascontiguousarray(wf, np.float32)
+    b = np.ascontiguousarray(img2, np.uint8)
+    if wf.shape != (6,) or b.ndim != 3 or b.shape[2] != 3:
+        raise ValueError("stab_warp_host: wf (6,), image (h, w, 3)")
+    h, w, _ = b.shape
+    out = np.empty((h, w, 3), np.uint8)
+    check(lib().eppm_stab_warp_host(wf.ctypes.data_as(C.c_void_p), b.ctypes.data_as(C.c_void_p), h, w, out.ctypes.data_as(C.c_void_p)),
+          "eppm_stab_warp_host")
+    return out

@@ -388,6 +388,68 @@ int  eppm_tfilter_seed_host(float* acc, const uint8_t* rgb, int h, int w);
 int  eppm_tfilter_step_host(const eppm_tfilter_params* p, float* acc_out, uint8_t* rgb_out, const float* acc_in, const uint8_t* rgb2,
                             const float* bu, const float* bv, const uint8_t* occ2, int h, int w, int cut);
 
+/* ----------------------------------------------------------------------------------------
+ * global camera motion and video stabilisation.  One step, after eppm_compute_bidirectional* on a streamed clip's
+ * next pair, (a) fits an affine camera motion to the pair's level-0 forward flow by iters passes of least squares on the inliers of the
+ * pass before (pixels with occ1 == 0 and a known vector of at most 8192 px; an inlier's residual is at most tau), (b) classifies every
+ * pixel of image 1 against the final model (mask bytes: 0 moves with the camera, 1 moves on its own, 2 not valid), (c) appends the model to
+ * the slot's camera path C (frame 0 -> current frame), moves the smoothed path S towards it (S = smooth * S + (1 - smooth) * C), and
+ * (d) renders image 2 from the smoothed camera: the output pixel (x, y) samples image 2 bilinearly at (C o S^-1)(x, y), {0, 0, 0} where
+ * that leaves the frame.  A motion in displacement form is six numbers p: T(x, y) = (x + p0 + p1 X + p2 Y, y + p3 + p4 X + p5 Y) with
+ * X = 2x - (w - 1), Y = 2y - (h - 1); a path in (A, t) form is {a00, a01, a10, a11, tx, ty} in coordinates centred on the frame.  The sums of
+ * a pass are 64-bit integers (vectors quantised to 1/256 px), so the kernels equal the host forms bit for bit, in both libraries and on
+ * every run.  A stabiliser is a separate allocation on its context's device (per slot 5 bytes per pixel -- the RGBA output and the mask --,
+ * 128 bytes per tile of 64 x 16 pixels and 256 bytes of model and state), made by eppm_stab_create and freed by eppm_stab_destroy; a
+ * context that never creates one allocates and launches exactly what it did without.  Frames of at most 8192 x 8192 and 2^26 pixels.
+ * -------------------------------------------------------------------------------------- */
+typedef struct eppm_stab_params {
+    float tau;                   /* largest residual of an inlier in pixels (1); finite, > 0 */
+    int   iters;                 /* passes of the fit, 1 .. 8 (3) */
+    float smooth;                /* share of the smoothed path that survives a step, 0 .. 1 (0.9); 1: tripod lock, 0: pass-through */
+} eppm_stab_params;
+typedef struct eppm_gmotion_model {
+    double  p[6];                /* displacement form; all 0 when not valid */
+    int64_t n_valid;             /* valid pixels (the first pass's) */
+    int64_t n_inliers;           /* pixels the last pass summed: the valid inliers of the pass before it */
+    int     valid;               /* at least 3 pixels that are not collinear */
+    int     passes;              /* passes run: iters, or fewer when one left no valid model */
+} eppm_gmotion_model;
+typedef struct eppm_stab eppm_stab;
+
+int  eppm_stab_default_params(eppm_stab_params* p);
+/* p NULL: the defaults.  One slot per pair of ctx (eppm_batch_size), on its device; every slot empty (its path is the identity). */
+int  eppm_stab_create(eppm_ctx* ctx, const eppm_stab_params* p, eppm_stab** out);
+/* a stabiliser without a context, for eppm_stab_step_frames on caller planes: nslots slots of h x w pixels on `device` */
+int  eppm_stab_create_size(int h, int w, int nslots, int device, const eppm_stab_params* p, eppm_stab** out);
+int  eppm_stab_destroy(eppm_stab* stab);                  /* NULL is fine */
+int  eppm_stab_reset(eppm_stab* stab, int slot);          /* the slot is empty again; slot < 0: every slot */
+/* One step of slots 0 .. active pairs - 1 on the pairs of ctx's last eppm_compute_bidirectional* (the raw image 2, the level-0 forward
+ * flow and occ1): valid in the window of eppm_interpolate* (EPPM_ERR_STATE outside it); EPPM_ERR_ARG for a context of other dimensions,
+ * another device or more active pairs than the stabiliser has slots.  cut: NULL, or one flag per active pair; non-zero: image 2 of that
+ * pair is the first frame of another clip: the slot's paths become the identity and its output is image 2.  A slot the step does not cover
+ * keeps its state.  2 * iters + 1 launches, asynchronous on the context's stream: no copy, no allocation, no host synchronisation. */
+int  eppm_stab_step(eppm_stab* stab, eppm_ctx* ctx, const uint8_t* cut);
+/* the same step of one slot on caller device planes of the stabiliser's size (an RGBA image of `pitch` bytes per row, h*w float2 forward
+ * flow, h*w mask bytes); on the launcher stream, synchronous.  Whatever the planes hold, nothing outside them is read. */
+int  eppm_stab_step_frames(eppm_stab* stab, int slot, const void* d_rgba2, size_t pitch, const eppm_float2* d_flow, const uint8_t* d_occ1, int cut);
+/* of a slot's last step (EPPM_ERR_STATE on a slot that has none): the stabilised frame as packed RGB to the host, synchronous ... */
+int  eppm_stab_get(eppm_stab* stab, int slot, uint8_t* rgb, size_t row_stride);
+/* ... or RGBA words (alpha 255) into a device plane, asynchronous on the stream of the last step; the h*w mask bytes; the pair's model */
+int  eppm_stab_get_device(eppm_stab* stab, int slot, void* d_rgba, size_t pitch);
+int  eppm_stab_get_mask(eppm_stab* stab, int slot, uint8_t* mask);
+int  eppm_stab_get_model(eppm_stab* stab, int slot, eppm_gmotion_model* model);
+/* synchronous.  path: twelve doubles, C then S in (A, t) form (the identity for an empty slot); frames / invalid_steps (NULL: not wanted):
+ * the updates since the last cut and how many of them had no valid model.  set_path loads C and S: the slot is no longer empty. */
+int  eppm_stab_get_path(eppm_stab* stab, int slot, double* path, int64_t* frames, int64_t* invalid_steps);
+int  eppm_stab_set_path(eppm_stab* stab, int slot, const double* path);
+/* host forms (no GPU needed).  The fit of one pair: (u, v) the forward flow, occ1 the mask of image 1; mask: NULL or h*w bytes.  One
+ * update of a path (twelve doubles, in place; the identity for a clip's first pair) and its counts (NULL, or {frames, invalid_steps}, in
+ * place) with a pair's model; wf: the six float32 of the warp in displacement form.  The warp of a packed RGB image 2 by wf. */
+int  eppm_gmotion_fit_host(const eppm_stab_params* p, const float* u, const float* v, const uint8_t* occ1, int h, int w,
+                           eppm_gmotion_model* model, uint8_t* mask);
+int  eppm_stab_update_host(const eppm_stab_params* p, double* path, int64_t* counts, const eppm_gmotion_model* model, int cut, float* wf);
+int  eppm_stab_warp_host(const float* wf, const uint8_t* rgb2, int h, int w, uint8_t* rgb_out);
+
 /* Per-stage device times in ms (hipEvent pairs on the context's stream), one entry per stage per
  * call since the last eppm_clear_stage_times (names repeat across calls; prepare entries first).
  * names[i] points to static strings.  Returns the number of entries written (<= max). */
@@ -398,7 +460,7 @@ int  eppm_clear_stage_times(eppm_ctx* ctx);
  * "flow_blf_bwd_L<l>", "flow_blf_bwd_final" and "fb_occlusion"; an interpolation call "interp_splat", "interp_fill" and "interp_blend"
  * (mode 1, once per group of four times); a track step "track_advance", "track_seed" and "track_compact" (mode 1; the step that seeds
  * frame 0 adds a "track_seed" before "track_advance"); a compute that starts from a temporal prior "temporal_advect" (before "patchmatch") and
- * "temporal_select" (inside it: "patchmatch" includes its time); a temporal-filter step "tfilter_step".  Events come from a per-context pool: none is created in a steady-state step. */
+ * "temporal_select" (inside it: "patchmatch" includes its time); a temporal-filter step "tfilter_step"; a stabiliser step "stab_fit" (every accumulate and solve launch) and "stab_warp".  Events come from a per-context pool: none is created in a steady-state step. */
 int  eppm_enable_stage_timing(eppm_ctx* ctx, int on);
 
 const char* eppm_last_error(void);

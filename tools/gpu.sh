@@ -15,6 +15,7 @@
 #   clock       shader clock and power under load                      inflight    throughput vs contexts in flight
 #   draft       draft mode: tools/draft_times.py on both libraries -> draft_times_{exact,tol}.json in the output folder
 #   tfilter     the temporal filter: tools/tfilter_times.py on both libraries -> tfilter_times_{exact,tol}.json
+#   stab        the stabiliser: tools/stab_times.py on both libraries -> stab_times_{exact,tol}.json
 #   round       everything profiles/ of a round comes from (TAG=r04_x; PMC_ONLY=1, SKIP_TESTS=1)
 set -o pipefail
 R=${GRAFT_REPO_ROOT:-$(cd "$(dirname "$0")/.." && pwd)}
@@ -121,6 +122,11 @@ tfilter)
     timeout -k 10 ${TFILTER_TIMEOUT:-300} python tools/tfilter_times.py --lib $l ${TFILTER_ARGS} > $O/tfilter_times_$l.json || exit 1
     cut -c1-400 $O/tfilter_times_$l.json
   done ;;
+stab)
+  cd $R; for l in exact tol; do
+    timeout -k 10 ${STAB_TIMEOUT:-300} python tools/stab_times.py --lib $l ${STAB_ARGS} > $O/stab_times_$l.json || exit 1
+    cut -c1-400 $O/stab_times_$l.json
+  done ;;
 inflight)
   cd $R; for S in ${INFLIGHT:-1 2 3 4 6}; do
     python bench.py --steps 96 --warmup 8 --inflight $S $QUIET $BENCH_ARGS 2>/dev/null | python -c "import json,sys; d=json.loads(sys.stdin.read()); print('inflight $S pairs in flight',d['config']['pairs_in_flight_per_gpu'],'ms/step %.3f'%d['ms_per_step'],'Mvec/s %.1f'%d['value'])"
@@ -178,5 +184,5 @@ LIST
   fi
   ls $OT ;;
 *)
-  sed -n 2,18p "$0"; exit 1 ;;
+  sed -n 2,19p "$0"; exit 1 ;;
 esac

@@ -35,6 +35,10 @@
 //                     of the motion-compensated temporal filter; the filtered frames are written to
 //                     P_dn_0000.ppm (the first frame itself), P_dn_0001.ppm ...  --denoise-thresh T (default 40) and
 //                     --denoise-frames N (the longest average, default 8) set its parameters and imply --denoise.
+//                     --stabilize: every pair runs the bidirectional call followed by one step of the stabiliser (DESIGN.md section 16:
+//                     the camera motion fitted to the forward flow, the frame re-rendered from the smoothed camera path); the frames are
+//                     written to P_st_0000.ppm (the first frame itself), P_st_0001.ppm ...  --smooth S (0 .. 1, default 0.9; 1: tripod
+//                     lock) sets the smoothing and implies --stabilize.
 #include <atomic>
 #include <chrono>
 #include <cstdio>
@@ -73,6 +77,8 @@ struct Options {
     bool denoise = false;                                   // --denoise
     float dn_thresh = 40.0f;                                // --denoise-thresh
     int dn_frames = 8;                                      // --denoise-frames
+    bool stabilize = false;                                 // --stabilize
+    float smooth = 0.9f;                                    // --smooth
 };
 
 static unsigned hash32(unsigned x)
@@ -124,7 +130,7 @@ static int usage()
                     "               [--occlusion file.pgm] [--interpolate T file.ppm]... [img1.ppm img2.ppm [out.flo]]\n"
                     "       runeppm [--seed N] [--levels N] [--patch-r N] [--iters N] [--propagation M] [--stop-level N]\n"
                     "               --sequence f0.ppm f1.ppm [f2.ppm ...] --out-prefix P [--temporal 0|1]\n"
-                    "               [--denoise] [--denoise-thresh T] [--denoise-frames N]\n");
+                    "               [--denoise] [--denoise-thresh T] [--denoise-frames N] [--stabilize] [--smooth S]\n");
     return 2;
 }
 
@@ -137,7 +143,8 @@ static bool write_ppm(const char* name, const unsigned char* rgb, int h, int w)
     return ok;
 }
 
-// --sequence: the clip through one context of the C ABI (frame push, temporal mode; --denoise: the temporal filter on top)
+// --sequence: the clip through one context of the C ABI (frame push, temporal mode; --denoise: the temporal filter on top; --stabilize:
+// the stabiliser on top)
 static int run_sequence(const Options& o)
 {
     eppm_params prm;
@@ -155,10 +162,18 @@ static int run_sequence(const Options& o)
     std::vector<float> u((size_t)h * w), v((size_t)h * w);
     eppm_ctx* ctx = nullptr;
     eppm_tfilter* flt = nullptr;
-    auto fail = [&](const char* what) { fprintf(stderr, "%s: %s\n", what, eppm_last_error()); eppm_tfilter_destroy(flt); if (ctx) eppm_destroy(ctx); return 1; };
+    eppm_stab* stab = nullptr;
+    auto fail = [&](const char* what) { fprintf(stderr, "%s: %s\n", what, eppm_last_error()); eppm_stab_destroy(stab); eppm_tfilter_destroy(flt); if (ctx) eppm_destroy(ctx); return 1; };
     if (eppm_create(&ctx, h, w, 0, &prm) != EPPM_OK) return fail("eppm_create");
-    std::vector<unsigned char> dn;
+    std::vector<unsigned char> dn, st;
     char name[4096];
+    if (o.stabilize) {
+        eppm_stab_params sp;
+        eppm_stab_default_params(&sp);
+        sp.smooth = o.smooth;
+        if (eppm_stab_create(ctx, &sp, &stab) != EPPM_OK) return fail("eppm_stab_create");
+        st.resize((size_t)h * w * 3);
+    }
     if (o.denoise) {
         const eppm_tfilter_params tp = {o.dn_thresh, o.dn_frames};
         if (eppm_tfilter_create(ctx, &tp, &flt) != EPPM_OK) return fail("eppm_tfilter_create");
@@ -172,6 +187,7 @@ static int run_sequence(const Options& o)
         std::vector<unsigned char>& cur = img[k == 0 ? 0 : 1];
         if (eppm_ppm_size(o.seq[k], &hk, &wk) != EPPM_OK || hk != h || wk != w || eppm_load_ppm(o.seq[k], cur.data(), h, w, &nch) != EPPM_OK) {
             fprintf(stderr, "cannot read %s (or its size differs from the first frame's)\n", o.seq[k]);
+            eppm_stab_destroy(stab);
             eppm_tfilter_destroy(flt);
             eppm_destroy(ctx);
             return 1;
@@ -179,30 +195,41 @@ static int run_sequence(const Options& o)
         if (k == 0) {
             if (o.denoise) {
                 snprintf(name, sizeof name, "%s_dn_0000.ppm", o.prefix);
-                if (!write_ppm(name, cur.data(), h, w)) { fprintf(stderr, "cannot write %s\n", name); eppm_tfilter_destroy(flt); eppm_destroy(ctx); return 1; }
+                if (!write_ppm(name, cur.data(), h, w)) { fprintf(stderr, "cannot write %s\n", name); eppm_stab_destroy(stab); eppm_tfilter_destroy(flt); eppm_destroy(ctx); return 1; }
+            }
+            if (o.stabilize) {
+                snprintf(name, sizeof name, "%s_st_0000.ppm", o.prefix);
+                if (!write_ppm(name, cur.data(), h, w)) { fprintf(stderr, "cannot write %s\n", name); eppm_stab_destroy(stab); eppm_tfilter_destroy(flt); eppm_destroy(ctx); return 1; }
             }
             continue;
         }
         const auto t0 = std::chrono::steady_clock::now();
         if (k == 1) { if (eppm_set_images(ctx, img[0].data(), img[1].data(), (size_t)w * 3) != EPPM_OK) return fail("eppm_set_images"); }
         else if (eppm_push_image(ctx, cur.data(), (size_t)w * 3) != EPPM_OK) return fail("eppm_push_image");
-        if (!o.denoise) { if (eppm_compute(ctx, u.data(), v.data()) != EPPM_OK) return fail("eppm_compute"); }
+        if (!o.denoise && !o.stabilize) { if (eppm_compute(ctx, u.data(), v.data()) != EPPM_OK) return fail("eppm_compute"); }
         else {
             if (eppm_compute_bidirectional(ctx, u.data(), v.data(), nullptr, nullptr, nullptr, nullptr) != EPPM_OK) return fail("eppm_compute_bidirectional");
-            if (eppm_tfilter_step(flt, ctx, nullptr) != EPPM_OK) return fail("eppm_tfilter_step");
-            if (eppm_tfilter_get(flt, 0, dn.data(), (size_t)w * 3) != EPPM_OK) return fail("eppm_tfilter_get");
+            if (o.denoise && eppm_tfilter_step(flt, ctx, nullptr) != EPPM_OK) return fail("eppm_tfilter_step");
+            if (o.stabilize && eppm_stab_step(stab, ctx, nullptr) != EPPM_OK) return fail("eppm_stab_step");
+            if (o.denoise && eppm_tfilter_get(flt, 0, dn.data(), (size_t)w * 3) != EPPM_OK) return fail("eppm_tfilter_get");
+            if (o.stabilize && eppm_stab_get(stab, 0, st.data(), (size_t)w * 3) != EPPM_OK) return fail("eppm_stab_get");
         }
         const double ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
         total += ms;
         snprintf(name, sizeof name, "%s_%04zu.flo", o.prefix, k);
-        if (eppm_save_flo(name, u.data(), v.data(), h, w) != EPPM_OK) { fprintf(stderr, "cannot write %s\n", name); eppm_tfilter_destroy(flt); eppm_destroy(ctx); return 1; }
+        if (eppm_save_flo(name, u.data(), v.data(), h, w) != EPPM_OK) { fprintf(stderr, "cannot write %s\n", name); eppm_stab_destroy(stab); eppm_tfilter_destroy(flt); eppm_destroy(ctx); return 1; }
         printf("pair %zu: %.3f ms%s -> %s\n", k, ms, (o.temporal && k > 1) ? " (seeded)" : "", name);
         if (o.denoise) {
             snprintf(name, sizeof name, "%s_dn_%04zu.ppm", o.prefix, k);
-            if (!write_ppm(name, dn.data(), h, w)) { fprintf(stderr, "cannot write %s\n", name); eppm_tfilter_destroy(flt); eppm_destroy(ctx); return 1; }
+            if (!write_ppm(name, dn.data(), h, w)) { fprintf(stderr, "cannot write %s\n", name); eppm_stab_destroy(stab); eppm_tfilter_destroy(flt); eppm_destroy(ctx); return 1; }
+        }
+        if (o.stabilize) {
+            snprintf(name, sizeof name, "%s_st_%04zu.ppm", o.prefix, k);
+            if (!write_ppm(name, st.data(), h, w)) { fprintf(stderr, "cannot write %s\n", name); eppm_stab_destroy(stab); eppm_tfilter_destroy(flt); eppm_destroy(ctx); return 1; }
         }
     }
     printf("%zu pairs, %.3f ms per pair\n", o.seq.size() - 1, total / (double)(o.seq.size() - 1));
+    eppm_stab_destroy(stab);
     eppm_tfilter_destroy(flt);
     eppm_destroy(ctx);
     return 0;
@@ -256,6 +283,14 @@ int main(int argc, char** argv)
             o.denoise = true;
         }
         else if (!strcmp(a, "--denoise-frames")) { if (!val(&v) || v < 1 || v > 255) return usage(); o.dn_frames = (int)v; o.denoise = true; }
+        else if (!strcmp(a, "--stabilize")) o.stabilize = true;
+        else if (!strcmp(a, "--smooth")) {
+            if (i + 1 >= argc) return usage();
+            char* end = nullptr;
+            o.smooth = strtof(argv[++i], &end);
+            if (!end || end == argv[i] || *end || !(o.smooth >= 0.0f && o.smooth <= 1.0f)) return usage();
+            o.stabilize = true;
+        }
         else if (!strcmp(a, "--temporal")) { if (!val(&v) || (v != 0 && v != 1)) return usage(); o.temporal = (int)v; }
         else if (a[0] == '-' && a[1] == '-') return usage();
         else pos.push_back(a);
@@ -270,7 +305,7 @@ int main(int argc, char** argv)
             return usage();
         return run_sequence(o);
     }
-    if (o.denoise) return usage();             // the filter walks a clip
+    if (o.denoise || o.stabilize) return usage();             // the filter and the stabiliser walk a clip
     if (pos.size() == 1 || pos.size() > 3) return usage();
     if (pos.size() >= 2) { o.f1 = pos[0]; o.f2 = pos[1]; }
     if (pos.size() == 3) o.fo = pos[2];
