@@ -37,6 +37,19 @@ class CGMotionModel(C.Structure):
                     passes=int(self.passes))
 
 
+class CCutParams(C.Structure):
+    _fields_ = [("lost_permille", C.c_int), ("residual_max", C.c_float)]
+
+
+class CCutStats(C.Structure):
+    _fields_ = [("n", C.c_int64), ("c1", C.c_int64 * 4), ("c2", C.c_int64 * 4), ("n_tracked", C.c_int64), ("sad", C.c_int64), ("cut", C.c_int32),
+                ("stepped", C.c_int32)]
+
+    def as_dict(self):
+        return dict(n=int(self.n), c1=[int(x) for x in self.c1], c2=[int(x) for x in self.c2], n_tracked=int(self.n_tracked), sad=int(self.sad),
+                    cut=int(self.cut), stepped=int(self.stepped))
+
+
 class CTrackCounts(C.Structure):
     _fields_ = [("live", C.c_int), ("ended", C.c_int), ("seeded", C.c_int), ("dropped", C.c_int), ("frame", C.c_int), ("next_id", C.c_int)]
 
@@ -81,6 +94,8 @@ SYMBOLS = [
     "eppm_stab_default_params", "eppm_stab_create", "eppm_stab_create_size", "eppm_stab_destroy", "eppm_stab_reset", "eppm_stab_step",
     "eppm_stab_step_frames", "eppm_stab_get", "eppm_stab_get_device", "eppm_stab_get_mask", "eppm_stab_get_model", "eppm_stab_get_path",
     "eppm_stab_set_path", "eppm_gmotion_fit_host", "eppm_stab_update_host", "eppm_stab_warp_host",
+    "eppm_cutdet_default_params", "eppm_cutdet_create", "eppm_cutdet_create_size", "eppm_cutdet_destroy", "eppm_cutdet_step",
+    "eppm_cutdet_step_frames", "eppm_cutdet_get", "eppm_cutdet_cuts", "eppm_cutdet_host",
 ]
 
 

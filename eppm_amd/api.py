@@ -3,7 +3,7 @@ import ctypes as C
 
 import numpy as np
 
-from ._lib import CGMotionModel, CParams, CStabParams, CTFilterParams, CTrackCounts, CTrackParams, EppmError, check, lib
+from ._lib import CCutParams, CCutStats, CGMotionModel, CParams, CStabParams, CTFilterParams, CTrackCounts, CTrackParams, EppmError, check, lib
 
 uchar4 = np.dtype([("x", "u1"), ("y", "u1"), ("z", "u1"), ("w", "u1")])
 short2 = np.dtype([("x", "i2"), ("y", "i2")])
@@ -311,6 +311,63 @@ class Stabilizer:
             pass
 
 
+class CutDetector:
+    """Scene-cut detection from the bidirectional flow over the pairs of a context (eppm_cutdet_*).  ctx: an EPPM or
+    an EPPMBatch; one slot per pair of it.  Every step() counts, for the active pairs of the context's last compute_flow_bidirectional*,
+    the pixels that found no consistent partner in the other frame and decides whether the pair crosses a cut.  The detector is its own
+    allocation on the context's device; close() frees it."""
+
+    def __init__(self, ctx, lost_permille=530, residual_max=-1.0, size=None, slots=1, device=0):
+        """ctx None: a detector without a context, for step_frames on caller planes (eppm_cutdet_create_size): size = (h, w), `slots` slots."""
+        self._f = C.c_void_p()
+        self.ctx = ctx
+        self.params = CCutParams(int(lost_permille), float(residual_max))
+        if ctx is None:
+            if size is None or len(size) != 2:
+                raise EppmError("CutDetector: without a context, size=(h, w) is required")
+            self.h, self.w, self.nslots = int(size[0]), int(size[1]), int(slots)
+            check(lib().eppm_cutdet_create_size(self.h, self.w, self.nslots, int(device), C.byref(self.params), C.byref(self._f)),
+                  "eppm_cutdet_create_size")
+            return
+        check(lib().eppm_cutdet_create(ctx._ctx, C.byref(self.params), C.byref(self._f)), "eppm_cutdet_create")
+        self.h, self.w = ctx.h, ctx.w
+        self.nslots = int(lib().eppm_batch_size(ctx._ctx))
+
+    def step(self, ctx=None):
+        """One step of every active pair's slot.  Asynchronous on the context's stream."""
+        c = self.ctx if ctx is None else ctx
+        check(lib().eppm_cutdet_step(self._f, c._ctx), "eppm_cutdet_step")
+
+    def step_frames(self, slot, d_rgba1, d_rgba2, pitch, d_flow_bwd, d_occ1, d_occ2):
+        """eppm_cutdet_step_frames: one step of one slot on caller device planes (addresses), synchronous."""
+        check(lib().eppm_cutdet_step_frames(self._f, int(slot), C.c_void_p(d_rgba1), C.c_void_p(d_rgba2), C.c_size_t(pitch), C.c_void_p(d_flow_bwd),
+                                            C.c_void_p(d_occ1), C.c_void_p(d_occ2)), "eppm_cutdet_step_frames")
+
+    def stats(self, slot=0):
+        """The record of the slot's last step: dict(n, c1 (4 counts), c2, n_tracked, sad, cut, stepped)."""
+        st = CCutStats()
+        check(lib().eppm_cutdet_get(self._f, int(slot), C.byref(st)), "eppm_cutdet_get")
+        return st.as_dict()
+
+    def cuts(self, n=None):
+        """The verdicts of slots 0 .. n - 1 (default: the context's active pairs) as a list of bools: one small copy, synchronous."""
+        n = int(getattr(self.ctx, "n", 1) if n is None else n)
+        out = (C.c_uint8 * max(n, 1))()
+        check(lib().eppm_cutdet_cuts(self._f, n, out), "eppm_cutdet_cuts")
+        return [bool(x) for x in out[:n]]
+
+    def close(self):
+        if self._f:
+            lib().eppm_cutdet_destroy(self._f)
+            self._f = C.c_void_p()
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
 def _level(level):
     """a stop level as a plain int; anything that is not an integer is refused before the library is touched"""
     if isinstance(level, (bool, np.bool_)) or not isinstance(level, (int, np.integer)):
@@ -318,31 +375,90 @@ def _level(level):
     return int(level)
 
 
-def flow_sequence(frames, params=None, temporal=True, bidirectional=False, stop_level=0):
+def _auto_cut_step(e, det):
+    """auto_cut: one detector step on the context's last bidirectional call; every detected slot's next compute becomes a cold run
+    (temporal_reset), so the pair across the cut leaves no prior.  Returns the verdicts of the active pairs."""
+    det.step()
+    cuts = det.cuts()
+    for slot, c in enumerate(cuts):
+        if c:
+            if isinstance(e, EPPMBatch):
+                e.temporal_reset(slot)
+            else:
+                e.temporal_reset()
+    return cuts
+
+
+def detect_cuts(frames, params=None, stop_level=0, **cut_params):
+    """Scene cuts of a clip ((h, w, 3) uint8 frames): one streaming context, one bidirectional call on the device and one CutDetector step
+    per consecutive pair.  Returns (cuts, stats): one bool and one record (CutDetector.stats) per pair; cuts[k] true: frame k + 1 starts
+    another shot.  After a detected cut the next pair is a cold run.  cut_params: CutDetector's lost_permille and residual_max."""
+    stop_level = _level(stop_level)
+    frames = [np.ascontiguousarray(f, np.uint8) for f in frames]
+    if len(frames) < 2:
+        raise EppmError("detect_cuts: at least two frames")
+    h, w, _ = frames[0].shape
+    e = EPPM(params=params)
+    det = None
+    cuts, stats = [], []
+    try:
+        e.init(h, w)
+        e.set_temporal(True)
+        e.set_stop_level(stop_level)
+        det = CutDetector(e, **cut_params)
+        for k in range(len(frames) - 1):
+            if k == 0:
+                e.set_data(frames[0], frames[1])
+            else:
+                e.push_frame(frames[k + 1])
+            e.compute_flow_bidirectional_device()
+            cuts.append(_auto_cut_step(e, det)[0])
+            stats.append(det.stats(0))
+    finally:
+        if det is not None:
+            det.close()
+        e.close()
+    return cuts, stats
+
+
+def flow_sequence(frames, params=None, temporal=True, bidirectional=False, stop_level=0, auto_cut=False, **cut_params):
     """The flows of the consecutive pairs of a clip ((h, w, 3) uint8 frames) through ONE context: the first pair by set_data, every later
     frame by push_frame (only the new frame is uploaded and prepared), with temporal mode (each pair's PatchMatch starts from the previous
     pair's result moved along its motion) unless temporal=False.  Returns a list of (u, v), or of (u, v, bu, bv, occ1, occ2) with
-    bidirectional=True.  Memory does not grow with the clip.  stop_level: draft mode (EPPM.set_stop_level)."""
+    bidirectional=True.  Memory does not grow with the clip.  stop_level: draft mode (EPPM.set_stop_level).  auto_cut=True: every pair is
+    computed bidirectionally (its forward flow is compute_flow's) and a CutDetector (cut_params: its lost_permille / residual_max) decides
+    whether it crosses a scene cut; the pair after a cut is a cold run.  Returns (flows, cuts) then: one bool per pair, and the flow of a
+    cut pair is of no use."""
     stop_level = _level(stop_level)
     frames = [np.ascontiguousarray(f, np.uint8) for f in frames]
     if len(frames) < 2:
         raise EppmError("flow_sequence: at least two frames")
     h, w, _ = frames[0].shape
     e = EPPM(params=params)
-    out = []
+    det = None
+    out, cuts = [], []
     try:
         e.init(h, w)
         e.set_temporal(temporal)
         e.set_stop_level(stop_level)
+        if auto_cut:
+            det = CutDetector(e, **cut_params)
         for k in range(len(frames) - 1):
             if k == 0:
                 e.set_data(frames[0], frames[1])
             else:
                 e.push_frame(frames[k + 1])
-            out.append(e.compute_flow_bidirectional() if bidirectional else e.compute_flow())
+            if auto_cut:
+                r = e.compute_flow_bidirectional()
+                out.append(r if bidirectional else r[:2])
+                cuts.append(_auto_cut_step(e, det)[0])
+            else:
+                out.append(e.compute_flow_bidirectional() if bidirectional else e.compute_flow())
     finally:
+        if det is not None:
+            det.close()
         e.close()
-    return out
+    return (out, cuts) if auto_cut else out
 
 
 def _sequence_plan(lengths, slots):
@@ -375,80 +491,100 @@ def _sequence_plan(lengths, slots):
         yield step
 
 
-def flow_sequences(clips, slots=8, params=None, temporal=True, bidirectional=False, stop_level=0):
+def flow_sequences(clips, slots=8, params=None, temporal=True, bidirectional=False, stop_level=0, auto_cut=False, **cut_params):
     """flow_sequence for many clips at once: any number of clips of one frame size and of any lengths (two frames at least) through ONE
     batch context of min(slots, len(clips)) slots, every slot advanced by one frame per step (push_frames; temporal mode per slot unless
     temporal=False).  A slot whose clip ends takes the next clip in the queue.  Returns one list of flows per clip, in the order given, each
-    what flow_sequence(clip) returns.  stop_level: draft mode (EPPMBatch.set_stop_level)."""
+    what flow_sequence(clip) returns.  stop_level: draft mode (EPPMBatch.set_stop_level).  auto_cut=True: flow_sequence's, per slot; returns
+    (flows, cuts), one list per clip each."""
     stop_level = _level(stop_level)
     clips = [[np.ascontiguousarray(f, np.uint8) for f in clip] for clip in clips]
     plan = _sequence_plan([len(c) for c in clips], slots)
     h, w, _ = clips[0][0].shape
     out = [[] for _ in clips]
-    e = None
+    cuts = [[] for _ in clips]
+    e = det = None
     try:
         for t, step in enumerate(plan):
             if t == 0:
                 e = EPPMBatch(h, w, len(step), params=params)
                 e.set_temporal(temporal)
                 e.set_stop_level(stop_level)
+                if auto_cut:
+                    det = CutDetector(e, **cut_params)
                 e.set_data([(clips[c][0], clips[c][1]) for c, _, _, _ in step])
             else:
                 e.push_frames([clips[c][f] for c, f, _, _ in step], [cut for _, _, cut, _ in step])
-            res = e.compute_flow_bidirectional() if bidirectional else e.compute_flow()
-            for (c, _, _, keep), r in zip(step, res):
+            if auto_cut:
+                res = e.compute_flow_bidirectional()
+                found = _auto_cut_step(e, det)
+                if not bidirectional:
+                    res = [r[:2] for r in res]
+            else:
+                res = e.compute_flow_bidirectional() if bidirectional else e.compute_flow()
+            for slot, ((c, _, _, keep), r) in enumerate(zip(step, res)):
                 if keep:
                     out[c].append(r)
+                    if auto_cut:
+                        cuts[c].append(found[slot])
     finally:
+        if det is not None:
+            det.close()
         if e is not None:
             e.close()
-    return out
+    return (out, cuts) if auto_cut else out
 
 
-def denoise_sequence(frames, params=None, thresh=40.0, n_max=8, temporal=True, stop_level=0):
+def denoise_sequence(frames, params=None, thresh=40.0, n_max=8, temporal=True, stop_level=0, auto_cut=False, **cut_params):
     """A clip ((h, w, 3) uint8 frames) denoised by the motion-compensated temporal filter (TemporalFilter): one
     streaming context -- set_data, then push_frame --, one bidirectional call on the device and one filter step per pair.  Returns
     len(frames) frames; the first is the input itself.  Memory does not grow with the clip.  params: the flow's eppm Params; temporal /
-    stop_level: the flow's temporal and draft modes."""
+    stop_level: the flow's temporal and draft modes.  auto_cut=True: a CutDetector (cut_params: its lost_permille / residual_max) looks at
+    every pair before the filter does; a frame that starts another shot restarts the filter and the flow's temporal prior, so the result
+    is what denoise_sequence returns for every shot on its own (one host read of the verdict per step)."""
     stop_level = _level(stop_level)
     frames = [np.ascontiguousarray(f, np.uint8) for f in frames]
     if len(frames) < 2:
         raise EppmError("denoise_sequence: at least two frames")
     h, w, _ = frames[0].shape
     e = EPPM(params=params)
-    flt = None
+    flt = det = None
     out = [frames[0].copy()]
     try:
         e.init(h, w)
         e.set_temporal(temporal)
         e.set_stop_level(stop_level)
         flt = TemporalFilter(e, thresh, n_max)
+        if auto_cut:
+            det = CutDetector(e, **cut_params)
         for k in range(len(frames) - 1):
             if k == 0:
                 e.set_data(frames[0], frames[1])
             else:
                 e.push_frame(frames[k + 1])
             e.compute_flow_bidirectional_device()
-            flt.step()
+            flt.step(_auto_cut_step(e, det) if auto_cut else None)
             out.append(flt.frame(0))
     finally:
+        if det is not None:
+            det.close()
         if flt is not None:
             flt.close()
         e.close()
     return out
 
 
-def denoise_sequences(clips, slots=8, params=None, thresh=40.0, n_max=8, temporal=True, stop_level=0):
+def denoise_sequences(clips, slots=8, params=None, thresh=40.0, n_max=8, temporal=True, stop_level=0, auto_cut=False, **cut_params):
     """denoise_sequence for many clips at once: clips of one frame size and of any lengths (two frames at least) through ONE batch context
     of min(slots, len(clips)) slots and one TemporalFilter, on flow_sequences' schedule.  A slot that takes the next clip of the queue
     passes `cut` for that step: its output is that clip's frame 0.  Returns one list of frames per clip, each what denoise_sequence(clip)
-    returns."""
+    returns.  auto_cut=True: denoise_sequence's, per slot; the detector's verdicts are ORed into the schedule's cut flags."""
     stop_level = _level(stop_level)
     clips = [[np.ascontiguousarray(f, np.uint8) for f in clip] for clip in clips]
     plan = _sequence_plan([len(c) for c in clips], slots)
     h, w, _ = clips[0][0].shape
     out = [[c[0].copy()] for c in clips]
-    e = flt = None
+    e = flt = det = None
     try:
         for t, step in enumerate(plan):
             if t == 0:
@@ -456,15 +592,22 @@ def denoise_sequences(clips, slots=8, params=None, thresh=40.0, n_max=8, tempora
                 e.set_temporal(temporal)
                 e.set_stop_level(stop_level)
                 flt = TemporalFilter(e, thresh, n_max)
+                if auto_cut:
+                    det = CutDetector(e, **cut_params)
                 e.set_data([(clips[c][0], clips[c][1]) for c, _, _, _ in step])
             else:
                 e.push_frames([clips[c][f] for c, f, _, _ in step], [cut for _, _, cut, _ in step])
             e.compute_flow_bidirectional_device()
-            flt.step([cut for _, _, cut, _ in step])
+            flags = [cut for _, _, cut, _ in step]
+            if auto_cut:
+                flags = [a or b for a, b in zip(flags, _auto_cut_step(e, det))]
+            flt.step(flags)
             for slot, (c, _, _, keep) in enumerate(step):
                 if keep:
                     out[c].append(flt.frame(slot))
     finally:
+        if det is not None:
+            det.close()
         if flt is not None:
             flt.close()
         if e is not None:
@@ -472,53 +615,61 @@ def denoise_sequences(clips, slots=8, params=None, thresh=40.0, n_max=8, tempora
     return out
 
 
-def stabilize_sequence(frames, params=None, tau=1.0, iters=3, smooth=0.9, temporal=True, stop_level=0, masks=False):
+def stabilize_sequence(frames, params=None, tau=1.0, iters=3, smooth=0.9, temporal=True, stop_level=0, masks=False, auto_cut=False, **cut_params):
     """A clip ((h, w, 3) uint8 frames) re-rendered from a smoothed camera path (Stabilizer): one streaming context --
     set_data, then push_frame --, one bidirectional call on the device and one stabiliser step per pair.  Returns len(frames) frames; the
     first is the input itself.  masks=True: (frames, masks, models) with one motion mask of image 1 and one model per pair.  params: the
-    flow's eppm Params; temporal / stop_level: the flow's temporal and draft modes."""
+    flow's eppm Params; temporal / stop_level: the flow's temporal and draft modes.  auto_cut=True: a CutDetector (cut_params: its
+    lost_permille / residual_max) looks at every pair before the stabiliser does; a frame that starts another shot restarts the camera
+    path and the flow's temporal prior, so the frames are what stabilize_sequence returns for every shot on its own."""
     stop_level = _level(stop_level)
     frames = [np.ascontiguousarray(f, np.uint8) for f in frames]
     if len(frames) < 2:
         raise EppmError("stabilize_sequence: at least two frames")
     h, w, _ = frames[0].shape
     e = EPPM(params=params)
-    stab = None
+    stab = det = None
     out, mk, md = [frames[0].copy()], [], []
     try:
         e.init(h, w)
         e.set_temporal(temporal)
         e.set_stop_level(stop_level)
         stab = Stabilizer(e, tau, iters, smooth)
+        if auto_cut:
+            det = CutDetector(e, **cut_params)
         for k in range(len(frames) - 1):
             if k == 0:
                 e.set_data(frames[0], frames[1])
             else:
                 e.push_frame(frames[k + 1])
             e.compute_flow_bidirectional_device()
-            stab.step()
+            stab.step(_auto_cut_step(e, det) if auto_cut else None)
             out.append(stab.frame(0))
             if masks:
                 mk.append(stab.mask(0))
                 md.append(stab.model(0))
     finally:
+        if det is not None:
+            det.close()
         if stab is not None:
             stab.close()
         e.close()
     return (out, mk, md) if masks else out
 
 
-def stabilize_sequences(clips, slots=8, params=None, tau=1.0, iters=3, smooth=0.9, temporal=True, stop_level=0, masks=False):
+def stabilize_sequences(clips, slots=8, params=None, tau=1.0, iters=3, smooth=0.9, temporal=True, stop_level=0, masks=False, auto_cut=False,
+                        **cut_params):
     """stabilize_sequence for many clips at once: clips of one frame size and of any lengths (two frames at least) through ONE batch context
     of min(slots, len(clips)) slots and one Stabilizer, on flow_sequences' schedule.  A slot that takes the next clip of the queue passes
-    `cut` for that step: its output is that clip's frame 0.  Returns one result per clip, each what stabilize_sequence(clip) returns."""
+    `cut` for that step: its output is that clip's frame 0.  Returns one result per clip, each what stabilize_sequence(clip) returns.
+    auto_cut=True: stabilize_sequence's, per slot; the detector's verdicts are ORed into the schedule's cut flags."""
     stop_level = _level(stop_level)
     clips = [[np.ascontiguousarray(f, np.uint8) for f in clip] for clip in clips]
     plan = _sequence_plan([len(c) for c in clips], slots)
     h, w, _ = clips[0][0].shape
     out = [[c[0].copy()] for c in clips]
     mk, md = [[] for _ in clips], [[] for _ in clips]
-    e = stab = None
+    e = stab = det = None
     try:
         for t, step in enumerate(plan):
             if t == 0:
@@ -526,11 +677,16 @@ def stabilize_sequences(clips, slots=8, params=None, tau=1.0, iters=3, smooth=0.
                 e.set_temporal(temporal)
                 e.set_stop_level(stop_level)
                 stab = Stabilizer(e, tau, iters, smooth)
+                if auto_cut:
+                    det = CutDetector(e, **cut_params)
                 e.set_data([(clips[c][0], clips[c][1]) for c, _, _, _ in step])
             else:
                 e.push_frames([clips[c][f] for c, f, _, _ in step], [cut for _, _, cut, _ in step])
             e.compute_flow_bidirectional_device()
-            stab.step([cut for _, _, cut, _ in step])
+            flags = [cut for _, _, cut, _ in step]
+            if auto_cut:
+                flags = [a or b for a, b in zip(flags, _auto_cut_step(e, det))]
+            stab.step(flags)
             for slot, (c, _, _, keep) in enumerate(step):
                 if keep:
                     out[c].append(stab.frame(slot))
@@ -538,6 +694,8 @@ def stabilize_sequences(clips, slots=8, params=None, tau=1.0, iters=3, smooth=0.
                         mk[c].append(stab.mask(slot))
                         md[c].append(stab.model(slot))
     finally:
+        if det is not None:
+            det.close()
         if stab is not None:
             stab.close()
         if e is not None:

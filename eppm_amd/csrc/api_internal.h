@@ -10,7 +10,7 @@
 //   context.cpp            eppm_ctx: create / destroy / planes / stage times (the class's init), the only one of the four that reads opt_*
 //   ctx_images.cpp         set_images, push_image, prepare, the host upload of one image (the class's set_data)
 //   ctx_compute.cpp        compute in all its forms, the post-PatchMatch branch of both directions, temporal mode (the class's compute_flow)
-//   ctx_interp.cpp         frame interpolation, the tracker's, the temporal filter's and the stabiliser's view of a context
+//   ctx_interp.cpp         frame interpolation, the tracker's, the temporal filter's, the stabiliser's and the cut detector's view of a context
 //   device_api.cpp         device-memory plumbing of the ABI (malloc / memcpy / NUMA binding)
 //   launchers_ref_abi.cpp  the reference's live extern "C" stage launchers and the sub-stage entry points of the parity tests
 //   test_hooks.cpp         libeppm_hip_test.so only: include/eppm_test.h
@@ -173,3 +173,10 @@ EPPM_HIDDEN int ctx_stab_inputs(eppm_ctx* c, int h, int w, int device, int nslot
 // the launcher stream of the context-less launchers (launchers_ref_abi.cpp) runs eppm_stab_step_frames through this (stabilizer.cpp)
 EPPM_HIDDEN int stab_step_on(eppm_stab* f, eppm::StabArgs& in, int slot0, const uint8_t* cut, hipStream_t s, eppm_ctx* timing);
 EPPM_HIDDEN int stab_device(const eppm_stab* f, int* h, int* w, int* nslots);
+
+// ---- what a cut detector (cutdet.cpp) reads of a context (ctx_interp.cpp) ----
+// the input members of *in (both raw images, the level-0 backward flow, occ1 and occ2) for every active pair, under ctx_tfilter_inputs' rules
+EPPM_HIDDEN int ctx_cutdet_inputs(eppm_ctx* c, int h, int w, int device, int nslots, const char* what, eppm::CutArgs* in, hipStream_t* s);
+// the launcher stream of the context-less launchers (launchers_ref_abi.cpp) runs eppm_cutdet_step_frames through this (cutdet.cpp)
+EPPM_HIDDEN int cutdet_step_on(eppm_cutdet* f, eppm::CutArgs& in, int slot0, hipStream_t s, eppm_ctx* timing);
+EPPM_HIDDEN int cutdet_device(const eppm_cutdet* f, int* h, int* w, int* nslots);

@@ -1,5 +1,5 @@
 // ctx_interp.cpp -- what reads the results of a context's (context.h) last bidirectional call: frame interpolation, the tracker, the
-// temporal filter and the stabiliser.
+// temporal filter, the stabiliser and the cut detector.
 #include "context.h"
 #include "interp.h"
 
@@ -174,6 +174,31 @@ int ctx_stab_inputs(eppm_ctx* c, int h, int w, int device, int nslots, const cha
     in->fwd = c->flow[0];
     in->fwd_stride = c->stride;
     in->occ1 = c->occ1;
+    in->occ_stride = c->bwd_stride;
+    in->n = c->n_active;
+    *s = c->stream;
+    return EPPM_OK;
+}
+
+// ---- scene-cut detection (cutdet.cpp): both raw images, the level-0 backward flow and both masks of every active
+// pair, in the window of eppm_interpolate* ----
+
+int ctx_cutdet_inputs(eppm_ctx* c, int h, int w, int device, int nslots, const char* what, CutArgs* in, hipStream_t* s)
+{
+    if (c->h != h || c->w != w || c->device != device)
+        return set_err(EPPM_ERR_ARG, "%s: the detector is %dx%d on device %d, the context %dx%d on device %d", what, w, h, device, c->w, c->h, c->device);
+    if (c->n_active > nslots) return set_err(EPPM_ERR_ARG, "%s: the context has %d active pairs, the detector %d slots", what, c->n_active, nslots);
+    if (c->flow_pending) return set_err(EPPM_ERR_STATE, "%s: an eppm_compute_begin is pending", what);
+    if (!c->have_bwd || !c->bwd_images) return set_err(EPPM_ERR_STATE, "%s: needs a bidirectional call on the current images", what);
+    HIPCHK(hipSetDevice(c->device));
+    in->img1 = (const uint8_t*)c->raw1;
+    in->img2 = (const uint8_t*)c->raw2;
+    in->img_pitch = c->raw_pitch;
+    in->img_stride = c->stride;
+    in->bwd = c->bflow[0];
+    in->bwd_stride = c->bwd_stride;
+    in->occ1 = c->occ1;
+    in->occ2 = c->occ2;
     in->occ_stride = c->bwd_stride;
     in->n = c->n_active;
     *s = c->stream;

@@ -361,6 +361,30 @@ void launch_gmotion_accumulate(const StabArgs& a, hipStream_t s);
 void launch_gmotion_solve(const StabArgs& a, hipStream_t s);
 void launch_stab_warp(const StabArgs& a, hipStream_t s);
 
+// ---- scene-cut detection (k_cutdet.hip; the arithmetic: cutdet.h) ----
+// One step covers n pairs: pair k's inputs (image 1 / image 2: RGBA words, img_pitch bytes per row; bwd: h*w float2; occ1 / occ2: h*w
+// bytes) lie k * (their stride) bytes past pair 0's and feed slot slot0 + k.  The detector's allocation `mem`: one record (CutRecord) per
+// slot, 128 bytes apart, then per slot (off_slabs + slot * slab_stride) tiles_x * tiles_y slabs of 64 bytes (the ten uint32 sums of one
+// accumulate block, 64 x 16 pixels).  A step is one accumulate and one finish launch; the thresholds travel in the kernel arguments.
+constexpr int kCutTileW = 64, kCutTileH = 16, kCutSlabBytes = 64;
+struct CutArgs {
+    const uint8_t* img1;
+    const uint8_t* img2;
+    size_t img_pitch, img_stride;
+    const float* bwd;
+    size_t bwd_stride;
+    const uint8_t* occ1;
+    const uint8_t* occ2;
+    size_t occ_stride;
+    char* mem;
+    size_t off_slabs, slab_stride;
+    int h, w, n, slot0, tiles_x, tiles_y;
+    int lost_permille;
+    long long r16;
+};
+void launch_cutdet_accumulate(const CutArgs& a, hipStream_t s);
+void launch_cutdet_finish(const CutArgs& a, hipStream_t s);
+
 // ---- flow colour coding (k_color.hip) ----
 // rgba: h*w packed R | G<<8 | B<<16 (alpha 0); flow: h*w float2
 void launch_flow_to_color(uint32_t* rgba, const float* flow, int h, int w, float max_disp_x, float max_disp_y, hipStream_t s, Batch bt = kOnePair);

@@ -266,3 +266,24 @@ def stab_warp_host(wf, img2):
     check(lib().eppm_stab_warp_host(wf.ctypes.data_as(C.c_void_p), b.ctypes.data_as(C.c_void_p), h, w, out.ctypes.data_as(C.c_void_p)),
           "eppm_stab_warp_host")
     return out
+
+
+def cutdet_host(img1, img2, bu, bv, occ1, occ2, lost_permille=530, residual_max=-1.0):
+    """The cut detector's record of one pair on the host (eppm_cutdet_host; equal to the kernels in every number).
+    img1, img2: (h, w, 3) uint8; (bu, bv): the backward flow; occ1, occ2: the occlusion masks.  Returns the dict of CutDetector.stats."""
+    from ._lib import CCutParams, CCutStats
+    p = CCutParams(int(lost_permille), float(residual_max))
+    a = np.ascontiguousarray(img1, np.uint8)
+    b = np.ascontiguousarray(img2, np.uint8)
+    bu = np.ascontiguousarray(bu, np.float32)
+    bv = np.ascontiguousarray(bv, np.float32)
+    o1 = np.ascontiguousarray(occ1, np.uint8)
+    o2 = np.ascontiguousarray(occ2, np.uint8)
+    if a.ndim != 3 or a.shape[2] != 3:
+        raise ValueError("cutdet_host: images (h, w, 3)")
+    h, w, _ = a.shape
+    if b.shape != (h, w, 3) or any(x.shape != (h, w) for x in (bu, bv, o1, o2)):
+        raise ValueError("cutdet_host: images (h, w, 3), flow and masks (h, w)")
+    st = CCutStats()
+    check(lib().eppm_cutdet_host(C.byref(p), *[x.ctypes.data_as(C.c_void_p) for x in (a, b, bu, bv, o1, o2)], h, w, C.byref(st)), "eppm_cutdet_host")
+    return st.as_dict()

@@ -450,6 +450,54 @@ int  eppm_gmotion_fit_host(const eppm_stab_params* p, const float* u, const floa
 int  eppm_stab_update_host(const eppm_stab_params* p, double* path, int64_t* counts, const eppm_gmotion_model* model, int cut, float* wf);
 int  eppm_stab_warp_host(const float* wf, const uint8_t* rgb2, int h, int w, uint8_t* rgb_out);
 
+/* ----------------------------------------------------------------------------------------
+ * scene-cut detection from the bidirectional flow.  One step, after eppm_compute_bidirectional* on a streamed
+ * clip's next pair, counts per slot the pixels of image 1 and image 2 by their occlusion class (mask bytes 0, 1, 2 and 3; a byte above 3
+ * counts as 3), the tracked pixels of image 2 -- occ2 == 0, a known backward vector and a source inside the frame -- and over them the sum
+ * of |Y(image 2) - Y(image 1 at the nearest pixel of the source)|, Y = (77 R + 150 G + 29 B + 128) >> 8.  With n = h*w and
+ * lost = min(n - c1[0], n - n_tracked), the pair is a cut iff lost * 1000 > lost_permille * n, or (residual_max >= 0, n_tracked > 0 and)
+ * sad * 16 > rint(residual_max * 16) * n_tracked: equality is not a cut.  Every sum is an integer, so the kernels equal eppm_cutdet_host
+ * in every number, in both libraries and on every run.  A detector is a separate allocation on its context's device (per slot 128 bytes of
+ * record and 64 bytes per tile of 64 x 16 pixels), made by eppm_cutdet_create and freed by eppm_cutdet_destroy; a context that never
+ * creates one allocates and launches exactly what it did without.  Frames of at most 8192 x 8192 and 2^26 pixels.
+ * -------------------------------------------------------------------------------------- */
+typedef struct eppm_cut_params {
+    int   lost_permille;         /* a pair that loses more than this share of its pixels on both sides is a cut, 0 .. 1000 (530) */
+    float residual_max;          /* largest mean |dY| over the tracked pixels that is not a cut, 0 .. 255; negative: the test is off (-1) */
+} eppm_cut_params;
+typedef struct eppm_cut_stats {
+    int64_t n;                   /* h*w */
+    int64_t c1[4], c2[4];        /* pixels of image 1 / image 2 by occlusion class */
+    int64_t n_tracked;           /* tracked pixels of image 2 */
+    int64_t sad;                 /* sum of their absolute luma differences */
+    int32_t cut;                 /* the verdict */
+    int32_t stepped;             /* 1 */
+} eppm_cut_stats;
+typedef struct eppm_cutdet eppm_cutdet;
+
+int  eppm_cutdet_default_params(eppm_cut_params* p);
+/* p NULL: the defaults.  One slot per pair of ctx (eppm_batch_size), on its device; no slot has a record. */
+int  eppm_cutdet_create(eppm_ctx* ctx, const eppm_cut_params* p, eppm_cutdet** out);
+/* a detector without a context, for eppm_cutdet_step_frames on caller planes: nslots slots of h x w pixels on `device` */
+int  eppm_cutdet_create_size(int h, int w, int nslots, int device, const eppm_cut_params* p, eppm_cutdet** out);
+int  eppm_cutdet_destroy(eppm_cutdet* det);                /* NULL is fine */
+/* One step of slots 0 .. active pairs - 1 on the pairs of ctx's last eppm_compute_bidirectional* (the raw frames, the level-0 backward
+ * flow and both masks): valid in the window of eppm_interpolate* (EPPM_ERR_STATE outside it); EPPM_ERR_ARG for a context of other
+ * dimensions, another device or more active pairs than the detector has slots.  A slot the step does not cover keeps its record.  Two
+ * launches, asynchronous on the context's stream: no copy, no allocation, no host synchronisation. */
+int  eppm_cutdet_step(eppm_cutdet* det, eppm_ctx* ctx);
+/* the same step of one slot on caller device planes of the detector's size (RGBA images of `pitch` bytes per row, h*w float2 backward
+ * flow, h*w mask bytes each); on the launcher stream, synchronous.  Whatever the planes hold, nothing outside them is read. */
+int  eppm_cutdet_step_frames(eppm_cutdet* det, int slot, const void* d_rgba1, const void* d_rgba2, size_t pitch, const eppm_float2* d_flow_bwd,
+                             const uint8_t* d_occ1, const uint8_t* d_occ2);
+/* synchronous.  The record of a slot's last step (EPPM_ERR_STATE on a slot that has none) / the verdicts of slots 0 .. n - 1 in one small
+ * copy (0 for a slot without a step) */
+int  eppm_cutdet_get(eppm_cutdet* det, int slot, eppm_cut_stats* stats);
+int  eppm_cutdet_cuts(eppm_cutdet* det, int n, uint8_t* cut);
+/* host form (no GPU needed): packed RGB images, (bu, bv) the backward flow, the two masks */
+int  eppm_cutdet_host(const eppm_cut_params* p, const uint8_t* rgb1, const uint8_t* rgb2, const float* bu, const float* bv,
+                      const uint8_t* occ1, const uint8_t* occ2, int h, int w, eppm_cut_stats* stats);
+
 /* Per-stage device times in ms (hipEvent pairs on the context's stream), one entry per stage per
  * call since the last eppm_clear_stage_times (names repeat across calls; prepare entries first).
  * names[i] points to static strings.  Returns the number of entries written (<= max). */
@@ -460,7 +508,7 @@ int  eppm_clear_stage_times(eppm_ctx* ctx);
  * "flow_blf_bwd_L<l>", "flow_blf_bwd_final" and "fb_occlusion"; an interpolation call "interp_splat", "interp_fill" and "interp_blend"
  * (mode 1, once per group of four times); a track step "track_advance", "track_seed" and "track_compact" (mode 1; the step that seeds
  * frame 0 adds a "track_seed" before "track_advance"); a compute that starts from a temporal prior "temporal_advect" (before "patchmatch") and
- * "temporal_select" (inside it: "patchmatch" includes its time); a temporal-filter step "tfilter_step"; a stabiliser step "stab_fit" (every accumulate and solve launch) and "stab_warp".  Events come from a per-context pool: none is created in a steady-state step. */
+ * "temporal_select" (inside it: "patchmatch" includes its time); a temporal-filter step "tfilter_step"; a stabiliser step "stab_fit" (every accumulate and solve launch) and "stab_warp"; a cut-detector step "cutdet".  Events come from a per-context pool: none is created in a steady-state step. */
 int  eppm_enable_stage_timing(eppm_ctx* ctx, int on);
 
 const char* eppm_last_error(void);

@@ -16,6 +16,7 @@
 #   draft       draft mode: tools/draft_times.py on both libraries -> draft_times_{exact,tol}.json in the output folder
 #   tfilter     the temporal filter: tools/tfilter_times.py on both libraries -> tfilter_times_{exact,tol}.json
 #   stab        the stabiliser: tools/stab_times.py on both libraries -> stab_times_{exact,tol}.json
+#   cutdet      the cut detector: tools/cutdet_times.py --shares on both libraries -> cutdet_times_{exact,tol}.json
 #   round       everything profiles/ of a round comes from (TAG=r04_x; PMC_ONLY=1, SKIP_TESTS=1)
 set -o pipefail
 R=${GRAFT_REPO_ROOT:-$(cd "$(dirname "$0")/.." && pwd)}
@@ -126,6 +127,11 @@ stab)
   cd $R; for l in exact tol; do
     timeout -k 10 ${STAB_TIMEOUT:-300} python tools/stab_times.py --lib $l ${STAB_ARGS} > $O/stab_times_$l.json || exit 1
     cut -c1-400 $O/stab_times_$l.json
+  done ;;
+cutdet)
+  cd $R; for l in exact tol; do
+    timeout -k 10 ${CUTDET_TIMEOUT:-300} python tools/cutdet_times.py --lib $l --shares ${CUTDET_ARGS} > $O/cutdet_times_$l.json || exit 1
+    cut -c1-400 $O/cutdet_times_$l.json
   done ;;
 inflight)
   cd $R; for S in ${INFLIGHT:-1 2 3 4 6}; do

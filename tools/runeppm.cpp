@@ -39,6 +39,11 @@
 //                     the camera motion fitted to the forward flow, the frame re-rendered from the smoothed camera path); the frames are
 //                     written to P_st_0000.ppm (the first frame itself), P_st_0001.ppm ...  --smooth S (0 .. 1, default 0.9; 1: tripod
 //                     lock) sets the smoothing and implies --stabilize.
+//                     --auto-cut: every pair runs the bidirectional call followed by one step of the cut detector (DESIGN.md section
+//                     17); a frame that starts another shot restarts the flow's temporal prior and, with --denoise / --stabilize, the
+//                     filter and the camera path.  P_cuts.txt gets one line per pair: its index, the verdict and the record's integers
+//                     (n, c1[0..3], c2[0..3], n_tracked, sad).  --cut-lost N (0 .. 1000, default 530) sets the share of lost pixels,
+//                     in permille, above which a pair is a cut, and implies --auto-cut.
 #include <atomic>
 #include <chrono>
 #include <cstdio>
@@ -79,6 +84,8 @@ struct Options {
     int dn_frames = 8;                                      // --denoise-frames
     bool stabilize = false;                                 // --stabilize
     float smooth = 0.9f;                                    // --smooth
+    bool auto_cut = false;                                  // --auto-cut
+    int cut_lost = 530;                                     // --cut-lost
 };
 
 static unsigned hash32(unsigned x)
@@ -130,7 +137,8 @@ static int usage()
                     "               [--occlusion file.pgm] [--interpolate T file.ppm]... [img1.ppm img2.ppm [out.flo]]\n"
                     "       runeppm [--seed N] [--levels N] [--patch-r N] [--iters N] [--propagation M] [--stop-level N]\n"
                     "               --sequence f0.ppm f1.ppm [f2.ppm ...] --out-prefix P [--temporal 0|1]\n"
-                    "               [--denoise] [--denoise-thresh T] [--denoise-frames N] [--stabilize] [--smooth S]\n");
+                    "               [--denoise] [--denoise-thresh T] [--denoise-frames N] [--stabilize] [--smooth S]\n"
+                    "               [--auto-cut] [--cut-lost N]\n");
     return 2;
 }
 
@@ -163,7 +171,9 @@ static int run_sequence(const Options& o)
     eppm_ctx* ctx = nullptr;
     eppm_tfilter* flt = nullptr;
     eppm_stab* stab = nullptr;
-    auto fail = [&](const char* what) { fprintf(stderr, "%s: %s\n", what, eppm_last_error()); eppm_stab_destroy(stab); eppm_tfilter_destroy(flt); if (ctx) eppm_destroy(ctx); return 1; };
+    eppm_cutdet* det = nullptr;
+    FILE* cuts = nullptr;
+    auto fail = [&](const char* what) { fprintf(stderr, "%s: %s\n", what, eppm_last_error()); if (cuts) fclose(cuts); eppm_cutdet_destroy(det); eppm_stab_destroy(stab); eppm_tfilter_destroy(flt); if (ctx) eppm_destroy(ctx); return 1; };
     if (eppm_create(&ctx, h, w, 0, &prm) != EPPM_OK) return fail("eppm_create");
     std::vector<unsigned char> dn, st;
     char name[4096];
@@ -179,14 +189,29 @@ static int run_sequence(const Options& o)
         if (eppm_tfilter_create(ctx, &tp, &flt) != EPPM_OK) return fail("eppm_tfilter_create");
         dn.resize((size_t)h * w * 3);
     }
+    if (o.auto_cut) {
+        eppm_cut_params cp;
+        eppm_cutdet_default_params(&cp);
+        cp.lost_permille = o.cut_lost;
+        if (eppm_cutdet_create(ctx, &cp, &det) != EPPM_OK) return fail("eppm_cutdet_create");
+        snprintf(name, sizeof name, "%s_cuts.txt", o.prefix);
+        if (!(cuts = fopen(name, "w"))) { fprintf(stderr, "cannot write %s\n", name); eppm_cutdet_destroy(det); eppm_stab_destroy(stab); eppm_tfilter_destroy(flt); eppm_destroy(ctx); return 1; }
+    }
     if (eppm_set_temporal(ctx, o.temporal) != EPPM_OK) return fail("eppm_set_temporal");
-    if (eppm_set_stop_level(ctx, o.stop_level) != EPPM_OK) { fprintf(stderr, "--stop-level: %s\n", eppm_last_error()); eppm_destroy(ctx); return usage(); }
+    if (eppm_set_stop_level(ctx, o.stop_level) != EPPM_OK) {
+        fprintf(stderr, "--stop-level: %s\n", eppm_last_error());
+        if (cuts) fclose(cuts);
+        eppm_cutdet_destroy(det); eppm_stab_destroy(stab); eppm_tfilter_destroy(flt); eppm_destroy(ctx);
+        return usage();
+    }
     double total = 0;
     for (size_t k = 0; k < o.seq.size(); k++) {
         int hk = 0, wk = 0;
         std::vector<unsigned char>& cur = img[k == 0 ? 0 : 1];
         if (eppm_ppm_size(o.seq[k], &hk, &wk) != EPPM_OK || hk != h || wk != w || eppm_load_ppm(o.seq[k], cur.data(), h, w, &nch) != EPPM_OK) {
             fprintf(stderr, "cannot read %s (or its size differs from the first frame's)\n", o.seq[k]);
+            if (cuts) fclose(cuts);
+            eppm_cutdet_destroy(det);
             eppm_stab_destroy(stab);
             eppm_tfilter_destroy(flt);
             eppm_destroy(ctx);
@@ -195,43 +220,58 @@ static int run_sequence(const Options& o)
         if (k == 0) {
             if (o.denoise) {
                 snprintf(name, sizeof name, "%s_dn_0000.ppm", o.prefix);
-                if (!write_ppm(name, cur.data(), h, w)) { fprintf(stderr, "cannot write %s\n", name); eppm_stab_destroy(stab); eppm_tfilter_destroy(flt); eppm_destroy(ctx); return 1; }
+                if (!write_ppm(name, cur.data(), h, w)) { fprintf(stderr, "cannot write %s\n", name); if (cuts) fclose(cuts); eppm_cutdet_destroy(det); eppm_stab_destroy(stab); eppm_tfilter_destroy(flt); eppm_destroy(ctx); return 1; }
             }
             if (o.stabilize) {
                 snprintf(name, sizeof name, "%s_st_0000.ppm", o.prefix);
-                if (!write_ppm(name, cur.data(), h, w)) { fprintf(stderr, "cannot write %s\n", name); eppm_stab_destroy(stab); eppm_tfilter_destroy(flt); eppm_destroy(ctx); return 1; }
+                if (!write_ppm(name, cur.data(), h, w)) { fprintf(stderr, "cannot write %s\n", name); if (cuts) fclose(cuts); eppm_cutdet_destroy(det); eppm_stab_destroy(stab); eppm_tfilter_destroy(flt); eppm_destroy(ctx); return 1; }
             }
             continue;
         }
         const auto t0 = std::chrono::steady_clock::now();
         if (k == 1) { if (eppm_set_images(ctx, img[0].data(), img[1].data(), (size_t)w * 3) != EPPM_OK) return fail("eppm_set_images"); }
         else if (eppm_push_image(ctx, cur.data(), (size_t)w * 3) != EPPM_OK) return fail("eppm_push_image");
-        if (!o.denoise && !o.stabilize) { if (eppm_compute(ctx, u.data(), v.data()) != EPPM_OK) return fail("eppm_compute"); }
+        if (!o.denoise && !o.stabilize && !o.auto_cut) { if (eppm_compute(ctx, u.data(), v.data()) != EPPM_OK) return fail("eppm_compute"); }
         else {
             if (eppm_compute_bidirectional(ctx, u.data(), v.data(), nullptr, nullptr, nullptr, nullptr) != EPPM_OK) return fail("eppm_compute_bidirectional");
-            if (o.denoise && eppm_tfilter_step(flt, ctx, nullptr) != EPPM_OK) return fail("eppm_tfilter_step");
-            if (o.stabilize && eppm_stab_step(stab, ctx, nullptr) != EPPM_OK) return fail("eppm_stab_step");
+            uint8_t cut = 0;
+            if (o.auto_cut) {
+                eppm_cut_stats cs;
+                if (eppm_cutdet_step(det, ctx) != EPPM_OK) return fail("eppm_cutdet_step");
+                if (eppm_cutdet_cuts(det, 1, &cut) != EPPM_OK) return fail("eppm_cutdet_cuts");
+                if (eppm_cutdet_get(det, 0, &cs) != EPPM_OK) return fail("eppm_cutdet_get");
+                if (cut && eppm_temporal_reset(ctx) != EPPM_OK) return fail("eppm_temporal_reset");
+                fprintf(cuts, "%zu %d %lld", k - 1, (int)cs.cut, (long long)cs.n);
+                for (int j = 0; j < 4; j++) fprintf(cuts, " %lld", (long long)cs.c1[j]);
+                for (int j = 0; j < 4; j++) fprintf(cuts, " %lld", (long long)cs.c2[j]);
+                fprintf(cuts, " %lld %lld\n", (long long)cs.n_tracked, (long long)cs.sad);
+            }
+            if (o.denoise && eppm_tfilter_step(flt, ctx, o.auto_cut ? &cut : nullptr) != EPPM_OK) return fail("eppm_tfilter_step");
+            if (o.stabilize && eppm_stab_step(stab, ctx, o.auto_cut ? &cut : nullptr) != EPPM_OK) return fail("eppm_stab_step");
             if (o.denoise && eppm_tfilter_get(flt, 0, dn.data(), (size_t)w * 3) != EPPM_OK) return fail("eppm_tfilter_get");
             if (o.stabilize && eppm_stab_get(stab, 0, st.data(), (size_t)w * 3) != EPPM_OK) return fail("eppm_stab_get");
         }
         const double ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
         total += ms;
         snprintf(name, sizeof name, "%s_%04zu.flo", o.prefix, k);
-        if (eppm_save_flo(name, u.data(), v.data(), h, w) != EPPM_OK) { fprintf(stderr, "cannot write %s\n", name); eppm_stab_destroy(stab); eppm_tfilter_destroy(flt); eppm_destroy(ctx); return 1; }
+        if (eppm_save_flo(name, u.data(), v.data(), h, w) != EPPM_OK) { fprintf(stderr, "cannot write %s\n", name); if (cuts) fclose(cuts); eppm_cutdet_destroy(det); eppm_stab_destroy(stab); eppm_tfilter_destroy(flt); eppm_destroy(ctx); return 1; }
         printf("pair %zu: %.3f ms%s -> %s\n", k, ms, (o.temporal && k > 1) ? " (seeded)" : "", name);
         if (o.denoise) {
             snprintf(name, sizeof name, "%s_dn_%04zu.ppm", o.prefix, k);
-            if (!write_ppm(name, dn.data(), h, w)) { fprintf(stderr, "cannot write %s\n", name); eppm_stab_destroy(stab); eppm_tfilter_destroy(flt); eppm_destroy(ctx); return 1; }
+            if (!write_ppm(name, dn.data(), h, w)) { fprintf(stderr, "cannot write %s\n", name); if (cuts) fclose(cuts); eppm_cutdet_destroy(det); eppm_stab_destroy(stab); eppm_tfilter_destroy(flt); eppm_destroy(ctx); return 1; }
         }
         if (o.stabilize) {
             snprintf(name, sizeof name, "%s_st_%04zu.ppm", o.prefix, k);
-            if (!write_ppm(name, st.data(), h, w)) { fprintf(stderr, "cannot write %s\n", name); eppm_stab_destroy(stab); eppm_tfilter_destroy(flt); eppm_destroy(ctx); return 1; }
+            if (!write_ppm(name, st.data(), h, w)) { fprintf(stderr, "cannot write %s\n", name); if (cuts) fclose(cuts); eppm_cutdet_destroy(det); eppm_stab_destroy(stab); eppm_tfilter_destroy(flt); eppm_destroy(ctx); return 1; }
         }
     }
     printf("%zu pairs, %.3f ms per pair\n", o.seq.size() - 1, total / (double)(o.seq.size() - 1));
+    const bool cuts_ok = !cuts || fclose(cuts) == 0;
+    eppm_cutdet_destroy(det);
     eppm_stab_destroy(stab);
     eppm_tfilter_destroy(flt);
     eppm_destroy(ctx);
+    if (!cuts_ok) { fprintf(stderr, "cannot write %s_cuts.txt\n", o.prefix); return 1; }
     return 0;
 }
 
@@ -291,6 +331,8 @@ int main(int argc, char** argv)
             if (!end || end == argv[i] || *end || !(o.smooth >= 0.0f && o.smooth <= 1.0f)) return usage();
             o.stabilize = true;
         }
+        else if (!strcmp(a, "--auto-cut")) o.auto_cut = true;
+        else if (!strcmp(a, "--cut-lost")) { if (!val(&v) || v < 0 || v > 1000) return usage(); o.cut_lost = (int)v; o.auto_cut = true; }
         else if (!strcmp(a, "--temporal")) { if (!val(&v) || (v != 0 && v != 1)) return usage(); o.temporal = (int)v; }
         else if (a[0] == '-' && a[1] == '-') return usage();
         else pos.push_back(a);
@@ -305,7 +347,7 @@ int main(int argc, char** argv)
             return usage();
         return run_sequence(o);
     }
-    if (o.denoise || o.stabilize) return usage();             // the filter and the stabiliser walk a clip
+    if (o.denoise || o.stabilize || o.auto_cut) return usage();     // the filter, the stabiliser and the cut detector walk a clip
     if (pos.size() == 1 || pos.size() > 3) return usage();
     if (pos.size() >= 2) { o.f1 = pos[0]; o.f2 = pos[1]; }
     if (pos.size() == 3) o.fo = pos[2];
