@@ -259,6 +259,70 @@ __device__ __forceinline__ void c2f_term(const LUT& L, const C2fSample& s, const
 }
 #endif
 
+// The N terms of one sample, term k with the centre c2[k], the target texel q2[k] and the sums (cs[k], ws[k]).
+// They are written in PHASES across the terms -- the distances, the data term's first-level reads, the census reads, the second-level
+// reads, the weights, the accumulation (tolerance library: offsets and exponent arguments, td[] reads, cn[] reads, exponentials,
+// accumulation) -- so that the order of the source already is the interleaved schedule: N LDS round trips in flight together and N
+// exponent polynomials side by side.  Term by term (N x c2f_term) the scheduler has to find that order itself, and where its attempt
+// does not fit the kernel's register budget it keeps the source order: passes 4/3 of k_c2f_refine_win<9> ran one term after the other,
+// each waiting out two LDS round trips of its own (profiles/refine_schedule_isa.txt; DESIGN.md section 8 rows 51-55 for the forms that
+// were measured and not kept).  Every term is c2f_term operation for operation, and a sum receives its terms in the same order: the
+// same bits.
+template <int N, class LUT>
+__device__ __forceinline__ void c2f_terms(const LUT& L, const C2fSample& s, const rgbf (&c2)[N], const float4 (&q2)[N], float (&cs)[N], float (&ws)[N])
+{
+#if !defined(EPPM_TOL) && !EPPM_DELTA_PATCH
+#pragma unroll
+    for (int k = 0; k < N; k++) c2f_term(L, s, c2[k], q2[k], cs[k], ws[k]);
+#elif defined(EPPM_TOL)
+    uint32_t od[N], oc[N];
+    float arg[N], cost[N], cen[N];
+#pragma unroll
+    for (int k = 0; k < N; k++) {
+        const rgbf p2 = texel_rgb(q2[k]);
+        od[k] = linf_off(s.p1, p2);
+        oc[k] = (uint32_t)__builtin_popcount(s.k1 ^ __float_as_uint(q2[k].w));
+        arg[k] = tol_exp_arg_scaled(c2[k], p2, s.lsrc);
+    }
+#pragma unroll
+    for (int k = 0; k < N; k++) cost[k] = tol_at(L.tab().td, od[k]);
+#pragma unroll
+    for (int k = 0; k < N; k++) cen[k] = tol_at(L.tab().cn, oc[k]);
+#pragma unroll
+    for (int k = 0; k < N; k++) arg[k] = __builtin_amdgcn_exp2f(arg[k]);
+#pragma unroll
+    for (int k = 0; k < N; k++) patch_accum(cs[k], ws[k], cost[k] + cen[k], arg[k]);
+#else
+    float d[N], temp[N], cen[N], cost[N], weight[N];
+    uint32_t t1[N];
+#pragma unroll
+    for (int k = 0; k < N; k++) {
+        const rgbf p2 = texel_rgb(q2[k]);
+        d[k] = max_abs_diff(s.p1, p2);
+        temp[k] = max_abs_diff(c2[k], p2);
+    }
+#pragma unroll
+    for (int k = 0; k < N; k++) t1[k] = delta_lookup_l1(L.D, d[k]);
+#pragma unroll
+    for (int k = 0; k < N; k++) cen[k] = census_cost(L.cnx, s.k1, __float_as_uint(q2[k].w));
+#pragma unroll
+    for (int k = 0; k < N; k++) cost[k] = delta_lookup_l2(d[k], t1[k]);
+#pragma unroll
+    for (int k = 0; k < N; k++) {
+        temp[k] *= temp[k];
+        weight[k] = fast_exp(div_ad2(-(s.a2 + temp[k])));
+        weight[k] *= s.gsp;
+    }
+#pragma unroll
+    for (int k = 0; k < N; k++) {
+        cost[k] += cen[k];
+        cost[k] *= weight[k];
+        cs[k] += cost[k];
+        ws[k] += weight[k];
+    }
+#endif
+}
+
 // One affine pass (PASS 0: the plain grid) of the candidates (cx, ccy-1), (cx, ccy), (cx, ccy+1): one x offset m, the three y offsets n.
 // run: the running minimum over the passes, or (RAW, or the first pass run: PASS 3) this pass's cost.
 // WIN: the target texels come from an LDS window of the target image instead of per-lane gathers (k_c2f_refine_win):
@@ -319,8 +383,9 @@ EPPM_UNROLL(EPPM_C2F_UNROLL)
 }
 
 // Two affine passes of one candidate column evaluated together from the LDS window: the source sample, its range term a^2 and
-// the spatial weight are formed once per sample for the 6 (pass, row candidate) terms; each of the 6 pairs of running sums
-// still adds its terms in the reference's sample order.  outA / outB: raw costs of pass PA / PB for the three row candidates.
+// the spatial weight are formed once per sample for the 6 (pass, row candidate) terms, which are evaluated together (c2f_terms); each
+// of the 6 pairs of running sums still adds its terms in the reference's sample order.  outA / outB: raw costs of pass PA / PB for the
+// three row candidates.
 template <int R, int PA, int PB, int WW>
 __device__ __forceinline__ void c2f_pass2_win(const PatchLutT<R + 1>& L, const float4* __restrict__ s_src, int TW, int tx, int ty,
                                               const rgbf c1, const rgbf (&c2)[3], const float4* __restrict__ s_win, int wbase,
@@ -330,7 +395,8 @@ __device__ __forceinline__ void c2f_pass2_win(const PatchLutT<R + 1>& L, const f
     constexpr int TA = (PA == 0) ? 0 : PA - 1, TB = (PB == 0) ? 0 : PB - 1;
     const C2fTables<R>& T = c2f_tables<R>();
     const rgbf c1w = c2f_weight_centre(c1), c2w[3] = {c2f_weight_centre(c2[0]), c2f_weight_centre(c2[1]), c2f_weight_centre(c2[2])};
-    float csA[3] = {0.0f, 0.0f, 0.0f}, wsA[3] = {0.0f, 0.0f, 0.0f}, csB[3] = {0.0f, 0.0f, 0.0f}, wsB[3] = {0.0f, 0.0f, 0.0f};
+    const rgbf c2w6[6] = {c2w[0], c2w[1], c2w[2], c2w[0], c2w[1], c2w[2]};
+    float cs[6] = {0.0f, 0.0f, 0.0f, 0.0f, 0.0f, 0.0f}, ws[6] = {0.0f, 0.0f, 0.0f, 0.0f, 0.0f, 0.0f};      // pass PA's three row candidates, then pass PB's
 #pragma unroll 1
     for (int ii = 0; ii < S; ii++) {
         const int rdyA = (PA == 0) ? 2 * ii - R : T.rowdy[TA][ii];
@@ -342,18 +408,14 @@ EPPM_UNROLL(EPPM_C2F_UNROLL)
             const int soffB = (rdyB + ((PB != 0) ? T.off[TB][ii * S + jj].up : 0)) * (WW * 16) + ((PB == 0) ? (2 * jj - R) * 16 : T.off[TB][ii * S + jj].dx16);
             const char* wa = reinterpret_cast<const char*>(s_win) + (wbase + soffA);
             const char* wb = reinterpret_cast<const char*>(s_win) + (wbase + soffB);
-            float4 qa[3], qb[3];
+            float4 q[6];
 #pragma unroll
-            for (int n = 0; n < 3; n++) { qa[n] = *reinterpret_cast<const float4*>(wa + n * (WW * 16)); qb[n] = *reinterpret_cast<const float4*>(wb + n * (WW * 16)); }
-#pragma unroll
-            for (int n = 0; n < 3; n++) {
-                c2f_term(L, smp, c2w[n], qa[n], csA[n], wsA[n]);
-                c2f_term(L, smp, c2w[n], qb[n], csB[n], wsB[n]);
-            }
+            for (int n = 0; n < 3; n++) { q[n] = *reinterpret_cast<const float4*>(wa + n * (WW * 16)); q[3 + n] = *reinterpret_cast<const float4*>(wb + n * (WW * 16)); }
+            c2f_terms<6>(L, smp, c2w6, q, cs, ws);
         }
     }
 #pragma unroll
-    for (int n = 0; n < 3; n++) { outA[n] = csA[n] / wsA[n]; outB[n] = csB[n] / wsB[n]; }
+    for (int n = 0; n < 3; n++) { outA[n] = cs[n] / ws[n]; outB[n] = cs[3 + n] / ws[3 + n]; }
 }
 
 }  // namespace eppm

@@ -199,7 +199,9 @@ struct DeltaTab {
 typedef const __attribute__((address_space(3))) float lds_cfloat;
 typedef const __attribute__((address_space(3))) int lds_cint;
 __device__ __forceinline__ uint32_t lds_addr(const void* p) { return (uint32_t)(uintptr_t)(const __attribute__((address_space(3))) void*)p; }
-__device__ __forceinline__ float delta_lookup(const DeltaTab& D, float d)
+// delta_lookup_l1: the first-level read t1[kd]; delta_lookup_l2: the entry's read.  Apart for a caller that issues the first-level reads
+// of several terms before any second-level one (c2f_device.cuh: c2f_terms); delta_lookup is one after the other.
+__device__ __forceinline__ uint32_t delta_lookup_l1(const DeltaTab& D, float d)
 {
     // The address of t1[kd] in ONE full-rate instruction: a float below 2^-125 has the bits of its value in units of 2^-149, so an fma whose
     // RESULT lies there is an integer -- fma(d, 1020 * 2^-149, &t1 * 2^-149) = &t1 + round(1020 d) = &t1 + 4 kd exactly, the distances of a
@@ -207,9 +209,10 @@ __device__ __forceinline__ float delta_lookup(const DeltaTab& D, float d)
     // need too).  t1[kd] already contains &t2 (load_delta_tab), so (bits(d) << 2) + t1[kd] is the entry's address: v_fma, ds_read,
     // v_lshl_add, ds_read = 6 issue cycles (the offset forms cost v_fma, v_cvt_u32, v_and + an address add, and v_lshlrev, v_add3: 18).
     const uint32_t a1 = __float_as_uint(__builtin_fmaf(d, __uint_as_float(1020u), __uint_as_float(lds_addr(D.t1))));
-    const uint32_t a2 = (__float_as_uint(d) << 2) + (uint32_t)*reinterpret_cast<lds_cint*>(a1);
-    return *reinterpret_cast<lds_cfloat*>(a2);
+    return (uint32_t)*reinterpret_cast<lds_cint*>(a1);
 }
+__device__ __forceinline__ float delta_lookup_l2(float d, uint32_t t1) { return *reinterpret_cast<lds_cfloat*>((__float_as_uint(d) << 2) + t1); }
+__device__ __forceinline__ float delta_lookup(const DeltaTab& D, float d) { return delta_lookup_l2(d, delta_lookup_l1(D, d)); }
 // The same look-up by OFFSETS, for a table that is a __shared__ object of its own (the smoothing, the weighted median): its address is a
 // compile-time constant the compiler folds into the reads' immediate offsets, and the address form only costs such a kernel registers
 // (smoothing 155 -> 165 VGPRs, 565 -> 584 us).  Table staged with load_delta_tab<false>.

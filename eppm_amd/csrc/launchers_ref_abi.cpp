@@ -451,6 +451,34 @@ extern "C" void baoCudaBLF_C2F(eppm_float2** pFlowPyr, eppm_uchar4** pImgPyr1, e
     g_launch_status = finish();
 }
 
+#ifdef EPPM_TEST_HOOKS
+// include/eppm_test.h: the candidate refine of npairs pairs of one size in ONE launch, as a batch context issues it (blockIdx.y = pair).
+// Caller planes unpitched, pair after pair.  A Batch has one byte stride for the texel planes and the flow, so the flow fields are spread
+// to the texel planes' stride in scratch (slot 0) for the launch and gathered back.
+extern "C" int eppm_test_c2f_refine_batch(float* d_flow, const uint32_t* d_img1, const uint32_t* d_img2, const uint8_t* d_census1,
+        const uint8_t* d_census2, int w, int h, int npairs)
+{
+    if (!d_flow || !d_img1 || !d_img2 || !d_census1 || !d_census2 || w < 1 || h < 1 || npairs < 1)
+        return set_err(EPPM_ERR_ARG, "eppm_test_c2f_refine_batch: bad argument");
+    LAUNCHER_BEGIN_INT;
+    const size_t n = (size_t)w * h, stride = n * 16;
+    void *a = nullptr, *b = nullptr, *f = nullptr;
+    CHK(get_scratch(ds, stride * npairs, &a, 2));
+    CHK(get_scratch(ds, stride * npairs, &b, 3));
+    CHK(get_scratch(ds, stride * npairs, &f, 0));
+    for (int p = 0; p < npairs; p++) {
+        launch_pack((char*)a + p * stride, w, d_img1 + p * n, w, d_census1 + p * n, w, w, h, g_stream);
+        launch_pack((char*)b + p * stride, w, d_img2 + p * n, w, d_census2 + p * n, w, w, h, g_stream);
+        CHK(copy_d2d((char*)f + p * stride, d_flow + p * n * 2, n * 8));
+    }
+    PlanesH P;
+    P.pk1 = a; P.pk2 = b; P.w = w; P.h = h; P.pitch = w;
+    launch_c2f_refine(P, (float*)f, ds->lut_pm, g_prm.patch_r, nullptr, g_stream, Batch{npairs, stride}, opt_no_split() != 0);
+    for (int p = 0; p < npairs; p++) CHK(copy_d2d(d_flow + p * n * 2, (char*)f + p * stride, n * 8));
+    return finish();
+}
+#endif
+
 extern "C" void baoCudaFlowSmoothing(eppm_float2* d_flow, eppm_uchar4* d_img, int w, int h, size_t img_pitch, size_t flow_pitch)
 {
     LAUNCHER_BEGIN;

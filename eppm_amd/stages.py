@@ -285,6 +285,18 @@ def c2f_refine(flow, P):
     return f.get()
 
 
+def c2f_refine_batch(flows, planes):
+    """eppm_test_c2f_refine_batch (test library): the candidate refine of len(flows) pairs of one size in ONE launch, as a batch context
+    issues it.  flows: (h, w) float2 per pair; planes: (img1, img2, census1, census2) per pair.  Returns the refined flow per pair."""
+    n = len(flows)
+    h, w = flows[0].shape
+    f = Dev(np.concatenate([np.ascontiguousarray(x, float2) for x in flows]))
+    i1, i2, c1, c2 = (Dev(np.concatenate([np.ascontiguousarray(p[k]) for p in planes])) for k in range(4))
+    check(lib().eppm_test_c2f_refine_batch(f.ptr, i1.ptr, i2.ptr, c1.ptr, c2.ptr, w, h, n), "eppm_test_c2f_refine_batch")
+    out = f.get()
+    return [out[k * h:(k + 1) * h] for k in range(n)]
+
+
 def blf_c2f(flow_coarse, P_fine, coarse_dims):
     """baoCudaBLF_C2F from level l+1 (flow_coarse) to level l (P_fine): upsample x2, x2.0, candidate refine."""
     ch, cw = coarse_dims

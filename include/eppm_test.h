@@ -37,6 +37,11 @@ int  eppm_test_set_option(const char* name, int value);
 /* admissible spread (max - min, pixels) of a 16x16 tile's candidate centres for which the LDS-window refine kernels stage the
  * target window; wider tiles take the per-access path inside the same launch (patch_r 9 or 17) */
 int  eppm_probe_c2f_window(int patch_r, int* span_x, int* span_y);
+/* the candidate refine (baoCudaBLFCostFilterRefine) of npairs pairs of one size in ONE launch, as a batch context issues it: device planes
+ * unpitched and pair after pair -- flow npairs x h x w float2 (refined in place), images npairs x h x w RGBA words, census npairs x h x w
+ * bytes.  Patch radius from eppm_set_launcher_params; never split ("c2f_no_split" or not: this entry brings no cost scratch). */
+int  eppm_test_c2f_refine_batch(float* d_flow, const uint32_t* d_img1, const uint32_t* d_img2, const uint8_t* d_census1,
+                                const uint8_t* d_census2, int w, int h, int npairs);
 /* What the launchers decide by the size of a launch, answered by the functions the launchers themselves ask; pure host code, no GPU
  * needed.  stage, args -> out:
  *   "smoothing"  w, h, npairs                            -> pixels per lane: 1 (k_flow_blf<1>) or 2 (k_flow_blf<2>)
