@@ -90,7 +90,8 @@ def _nearest(valid, axis, reverse):
     return np.concatenate([np.delete(nxt, 0, axis), np.full_like(np.take(nxt, [0], axis), n)], axis=axis)
 
 
-def interpolate_np(img1, img2, u, v, occ1, occ2, t):
+def interpolate_np(img1, img2, u, v, occ1, occ2, t, parts=None):
+    """parts: a dict that receives the splat mask and the two fill passes' source planes (-1: a hole), for the ledger."""
     f32 = np.float32
     t = f32(t)
     if t == 0:
@@ -138,6 +139,8 @@ def interpolate_np(img1, img2, u, v, occ1, occ2, t):
     dl = np.where(L >= 0, xs - L, big)
     dr = np.where(R < w, R - xs, big)
     f2 = np.where(filled, f1, np.where((dl <= dr) & (dl < big), f1[ys, np.clip(L, 0, w - 1)], np.where(dr < big, f1[ys, np.clip(R, 0, w - 1)], -1)))
+    if parts is not None:
+        parts.update(splat=splat, f1=f1, f2=f2)
     # (c) blend
     ux = np.where(f2 >= 0, u.ravel()[np.maximum(f2, 0)], f32(0)).astype(f32)
     uy = np.where(f2 >= 0, v.ravel()[np.maximum(f2, 0)], f32(0)).astype(f32)
@@ -210,6 +213,40 @@ def interpolation_cases():
         u = rng.uniform(-3, 3, (h, w)).astype(np.float32)
         v = rng.uniform(-3, 3, (h, w)).astype(np.float32)
         cases.append((f"size{h}x{w}", img(h, w), img(h, w), u, v, occ(h, w), occ(h, w)))
+    return cases + block_edge_cases()
+
+
+BLOCK_EDGE_SIZES = ((63, 3), (64, 4), (65, 5), (129, 9))       # (w, h) around the kernels' 64x4 blocks (k_interp.hip: interp_grid)
+
+
+def block_edge_cases():
+    """Frames one short of, equal to and one past a 64x4 block in both directions, and two blocks and a pixel wide.  Per size: a smooth
+    flow with the special values; then a single known vector in the first and in the last pixel (the fill passes walk a whole row and
+    column, up to 128 steps) and known vectors in column 0 only (every hole walks left, up to 128 steps)."""
+    rng = np.random.default_rng(30)
+    img = lambda h, w: rng.integers(0, 256, (h, w, 3), dtype=np.uint8)                   # noqa: E731
+    occ = lambda h, w: rng.choice(np.array([0, 0, 0, 1, 2, 3], np.uint8), (h, w))         # noqa: E731
+    cases = []
+    for w, h in BLOCK_EDGE_SIZES:
+        add = lambda name, u, v: cases.append((f"{name}_{w}x{h}", img(h, w), img(h, w), u, v, occ(h, w), occ(h, w)))   # noqa: E731
+        u, v = smooth_flow(rng, h, w, 3.0)
+        for a in (u, v):
+            idx = rng.choice(a.size, 12, replace=False)
+            a.reshape(-1)[idx[:6]] = np.nan
+            a.reshape(-1)[idx[6:]] = 1e10 * rng.choice([-1, 1], 6)
+        u[h - 1, w - 3:] = 1e9
+        add("edge_random", u, v)
+        nan = np.full((h, w), np.nan, np.float32)
+        u, v = nan.copy(), nan.copy()
+        u[0, 0], v[0, 0] = 1.5, 0.75
+        add("corner_only", u, v)
+        u, v = nan.copy(), nan.copy()
+        u[h - 1, w - 1], v[h - 1, w - 1] = -1.5, -0.75
+        add("far_corner_only", u, v)
+        u, v = nan.copy(), nan.copy()
+        u[:, 0] = rng.uniform(0, 2, h).astype(np.float32)
+        v[:, 0] = rng.uniform(-1, 1, h).astype(np.float32)
+        add("column_only", u, v)
     return cases
 
 
@@ -222,6 +259,38 @@ def test_host_form_equals_numpy_restatement(case):
         assert got.dtype == np.uint8 and got.shape == a.shape
         bad = int((got != want).any(-1).sum())
         assert bad == 0, f"{name} t={t}: {bad} of {u.size} pixels differ"
+
+
+def test_block_edge_ledger():
+    """What the single-vector cases reach at 129x9 (t = 0.5), from the restatement's own planes: pass 1 leaves holes that pass 2 fills, and
+    both walk more than a block's width.  The splatted pixels' columns are filled in every row by pass 1, so pass 2 finds a filled pixel in
+    every row: with one known vector no row can stay unfilled (only a frame without any splat keeps holes: `all_unknown`)."""
+    cases = {c[0]: c for c in block_edge_cases()}
+    assert len(cases) == 4 * len(BLOCK_EDGE_SIZES)
+    for name, col in (("far_corner_only_129x9", 128), ("corner_only_129x9", 0)):
+        _, a, b, u, v, o1, o2 = cases[name]
+        h, w = u.shape
+        src = int(np.nonzero(np.isfinite(u).ravel())[0][0])
+        parts = {}
+        interpolate_np(a, b, u, v, o1, o2, 0.5, parts)
+        splat, f1, f2 = parts["splat"], parts["f1"], parts["f2"]
+        ys, xs = np.nonzero(splat)
+        assert 0 < len(xs) <= 4 and (abs(xs - col) <= 2).all()
+        hole1 = f1 < 0
+        assert hole1.any() and (f2[hole1] == src).all() and (f1[~hole1] == src).all()
+        rows, cols = np.unique(ys), np.unique(xs)
+        assert not hole1[rows].any() and not hole1[:, cols].any()                   # pass 1: the splats' rows and columns, whole
+        assert hole1[np.setdiff1d(np.arange(h), rows)][:, np.setdiff1d(np.arange(w), cols)].all()  # and nothing else
+        assert (f2 >= 0).all()
+    # column 0 only: every row is splatted near its left end; the holes right of it walk left through two blocks
+    _, a, b, u, v, o1, o2 = cases["column_only_129x9"]
+    parts = {}
+    interpolate_np(a, b, u, v, o1, o2, 0.5, parts)
+    assert parts["splat"][:, :3].any(1).all() and not parts["splat"][:, 4:].any() and (parts["f1"] >= 0).all()
+    # the smooth cases hold NaN, +-1e10 and 1e9, and both known and unknown vectors in the last row
+    for w, h in BLOCK_EDGE_SIZES:
+        u, v = cases[f"edge_random_{w}x{h}"][3:5]
+        assert np.isnan(u).any() and (np.abs(u) == np.float32(1e10)).any() and (u == np.float32(1e9)).any() and np.isnan(v).any()
 
 
 def test_endpoints_return_the_inputs():

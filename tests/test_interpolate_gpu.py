@@ -151,6 +151,30 @@ def test_batch_equals_single_pairs():
     bat.close()
 
 
+def test_batch_equals_host_form_across_chunks():
+    """blockIdx.z = pair * nt + k: k_interp_splat / k_interp_blend take the pair as z / nt, the fill passes the time as z % nt.  Three
+    different pairs, six times in two chunks (four, then two), the endpoints at k == 1 and k == 3 of the first: every frame of every slot
+    against the host form on that slot's own outputs, not against another context."""
+    import eppm_amd
+    from eppm_amd import io, synth
+    h, w = 45, 67
+    pairs = [synth.make_pair(h, w, seed=310 + k, max_flow=2.0 + 2 * k)[:2] for k in range(3)]
+    assert not any(np.array_equal(pairs[i][0], pairs[j][0]) for i in range(3) for j in range(i))
+    times = [0.5, 0.0, 0.25, 1.0, 0.7, 1e-7]
+    bat = eppm_amd.EPPMBatch(h, w, 3)
+    bat.set_data(pairs)
+    outs = bat.compute_flow_bidirectional()
+    got = bat.interpolate(times)
+    assert len(got) == 3 and all(len(g) == len(times) for g in got)
+    for k, ((a, b), (u, v, bu, bv, o1, o2)) in enumerate(zip(pairs, outs)):
+        for t, g in zip(times, got[k]):
+            same(g, io.interpolate(a, b, u, v, o1, o2, t), f"slot {k} t={t}")
+    for k, (g0, g1) in enumerate(zip(got, bat.interpolate(times))):
+        for t, x, y in zip(times, g0, g1):
+            same(y, x, f"repeated call: slot {k} t={t}")
+    bat.close()
+
+
 def test_state_errors_and_stage_names(crop):
     import eppm_amd
     from eppm_amd._lib import lib

@@ -6,12 +6,13 @@ import json
 import os
 import subprocess
 import sys
+import time
 
 import numpy as np
 import pytest
 
 from conftest import ROOT
-from test_tracks_cpu import same_state, tracking_cases
+from test_tracks_cpu import SCAN_T, TB, long_list_case, long_list_cases, long_list_steps, same_state, tracking_cases
 
 pytestmark = pytest.mark.gpu
 
@@ -502,3 +503,59 @@ def test_tolerance_library_tracks_its_own_flows():
     out = json.loads(p.stdout.strip().splitlines()[-1])
     assert out["n"] > 200 and out["clear"] > 100, out
     assert out["median"] <= E2E_MEDIAN_BOUND and out["p95"] <= E2E_P95_BOUND and out["survival"] >= E2E_SURVIVAL_MIN, out
+
+
+@pytest.mark.parametrize("name", [c[0] for c in long_list_cases()])
+def test_kernels_equal_host_form_on_long_lists(name):
+    """The launch shapes at which a lane of k_track_scan / k_track_scan0 owns 2, 3 and 5 block counts (and 1, at the last shape that
+    does): lists of up to 1 051 355 tracks on a 64x48 frame and 262 810 cells on 641x410 (test_tracks_cpu.long_list_cases, whose ledger
+    says what each reaches).  Two steps, the second on the first's compacted list; a second fresh tracker repeats the first bit for bit.
+
+    Kept last in this file, and each case returns its blocks to the runtime: the lists differ in size from case to case, and
+    test_memory_is_the_trackers_own above compares the device's free bytes with a level it measures in this process.
+
+    Measured on one MI355X, seconds per case for both trackers, their four steps and the two host-form steps (nbc 1 on the 64x48 frame):
+      case              n        nbs  per  s     | case              n        nbs  per  s
+      nbs1024_full      262107   1024  1   0.06  | nbs1024_room5     262102   1024  1   0.05
+      nbs1024_boundary  261889   1024  1   0.01  | nbs1024_hollow    200      1024  1   0.05
+      nbs1025_full      262363   1025  2   0.05  | nbs1025_room5     262358   1025  2   0.08
+      nbs1025_boundary  262145   1025  2   0.03  | nbs1025_hollow    200      1025  2   0.08
+      nbs1088_full      278491   1088  2   0.07  | nbs1088_room5     278486   1088  2   0.08
+      nbs1088_boundary  278273   1088  2   0.03  | nbs1088_hollow    200      1088  2   0.00
+      nbs2049_full      524507   2049  3   0.11  | nbs2049_room5     524502   2049  3   0.10
+      nbs2049_boundary  524289   2049  3   0.03  | nbs2049_hollow    200      2049  3   0.00
+      nbs4107_full      1051355  4107  5   0.19  | nbs4107_room5     1051350  4107  5   0.21
+      nbs4107_boundary  1051137  4107  5   0.10  | nbs4107_hollow    200      4107  5   0.00
+      cells_empty       0        4107  5   0.07  | cells_loaded      716801   4107  5   0.13     (641x410: nbc 1027, per 2 for the cells)"""
+    from eppm_amd._lib import lib
+    case = long_list_case(name)
+    _, a, b, u, v, bu, bv, p, st = case
+    h, w = u.shape
+    t0 = time.perf_counter()
+    first = None
+    for run in range(2):
+        fs = FramesStepper(h, w, **p)
+        try:
+            state = dict(EMPTY)
+            if st is not None:
+                fs.t.set(*st)
+                state = dict(ids=st[0], starts=st[1], xy=st[2], next_id=st[3], frame=st[4])
+            got_all = []
+            for k, c in long_list_steps(case):
+                got = fs.step(*c[1:7])
+                if run == 0:
+                    same_state(got, _host_step(*c[1:7], state, p), f"{name} step {k}")
+                else:
+                    same_state(got, first[k], f"{name} step {k}: second tracker")
+                got_all.append(got)
+                state = got
+            cap = fs.t.capacity
+        finally:
+            fs.close()
+            assert lib().eppm_release_cached_memory() == 0
+        first = first or got_all
+    ncells = -(-w // p["spacing"]) * -(-h // p["spacing"])
+    nbs, nbc = -(-cap // TB), -(-ncells // TB)
+    print(json.dumps({"case": name, "n": 0 if st is None else len(st[0]), "capacity": cap, "nbs": nbs, "nbc": nbc, "per_slots": -(-nbs // SCAN_T),
+                      "per_cells": -(-nbc // SCAN_T), "live": [g["live"] for g in first], "ended": [g["ended"] for g in first],
+                      "seconds": round(time.perf_counter() - t0, 2)}))
