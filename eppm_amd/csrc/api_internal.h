@@ -82,15 +82,18 @@ EPPM_HIDDEN extern std::atomic<int> g_opt_rand_table;       // "rand_table": 0 =
 EPPM_HIDDEN extern std::atomic<int> g_opt_sweep_spec;       // "sweep_spec": -1 by iteration, 0 never, 1 always, 2 always and without the work list, 3 always in the merged form
 EPPM_HIDDEN extern std::atomic<int> g_opt_no_split;         // "c2f_no_split"
 EPPM_HIDDEN extern std::atomic<int> g_opt_force_split;      // "c2f_force_split": the refine's stage launchers bring the split path's scratch
+EPPM_HIDDEN extern std::atomic<int> g_opt_search_pre;       // "search_pre_from": -1 the library's threshold, else the first iteration of the two-phase search
 static inline int opt_rand_table() { return g_opt_rand_table.load(); }
 static inline int opt_sweep_spec() { return g_opt_sweep_spec.load(); }
 static inline int opt_no_split() { return g_opt_no_split.load(); }
 static inline int opt_force_split() { return g_opt_force_split.load(); }
+static inline int opt_search_pre() { return g_opt_search_pre.load(); }
 #else
 static constexpr int opt_rand_table() { return 1; }
 static constexpr int opt_sweep_spec() { return -1; }
 static constexpr int opt_no_split() { return 0; }
 static constexpr int opt_force_split() { return 0; }
+static constexpr int opt_search_pre() { return -1; }
 #endif
 
 // ---- caller memory registered for DMA: host_registry.h (header-only logic), bound to HIP by host_registry.cpp ----
@@ -130,16 +133,17 @@ EPPM_HIDDEN void pooled_stream_destroy(hipStream_t s, int device);
 
 // ---- baoCudaPatchMatch's host loop (pm_driver.cpp) ----
 EPPM_HIDDEN eppm::PmProblem mk_problem(const eppm::PlanesH& P, float* cost, int16_t* nnf, int16_t* nnf_alt, eppm_pm_rng* rng, int k, float* spec = nullptr,
-                                       int32_t* scand = nullptr, uint32_t* wl = nullptr, int16_t* seed = nullptr);
-EPPM_HIDDEN void search(eppm::PmBatch& b, eppm_pm_rng* rng, const float* lut, const eppm_params& prm, hipStream_t s, int launch_no = -1);
+                                       int32_t* scand = nullptr, uint32_t* wl = nullptr, int16_t* seed = nullptr, float* restw = nullptr);
+EPPM_HIDDEN void search(eppm::PmBatch& b, eppm_pm_rng* rng, const float* lut, const eppm_params& prm, hipStream_t s, int launch_no = -1, bool pretest = false);
 EPPM_HIDDEN bool sweep_list_on(int mode);
 EPPM_HIDDEN void sweep(eppm::PmBatch& b, const float* lut, const eppm_params& prm, int dir, hipStream_t s, bool speculative = false);
 EPPM_HIDDEN void jump(eppm::PmBatch& b, const float* lut, const eppm_params& prm, hipStream_t s);
 EPPM_HIDDEN void neighbor(eppm::PmBatch& b, const float* lut, const eppm_params& prm, int launches, hipStream_t s);
-EPPM_HIDDEN void run_patchmatch(eppm::PmBatch& b, eppm_pm_rng* rng, const float* lut, const eppm_params& prm, hipStream_t s, int spec_mode);
-// run_patchmatch = pm_start (random field + cost field) then pm_iterate (num_iter x [sweeps + search])
-EPPM_HIDDEN void pm_start(eppm::PmBatch& b, eppm_pm_rng* rng, const float* lut, const eppm_params& prm, hipStream_t s);
-EPPM_HIDDEN void pm_iterate(eppm::PmBatch& b, eppm_pm_rng* rng, const float* lut, const eppm_params& prm, hipStream_t s, int spec_mode);
+// pre_from: -1 the library's own threshold for the two-phase search (eppm_internal.h: pm_search_pretest), else the test switch's
+EPPM_HIDDEN void run_patchmatch(eppm::PmBatch& b, eppm_pm_rng* rng, const float* lut, const eppm_params& prm, hipStream_t s, int spec_mode, int pre_from = -1);
+// run_patchmatch = pm_start (random field + cost field, the rest-weight planes) then pm_iterate (num_iter x [sweeps + search])
+EPPM_HIDDEN void pm_start(eppm::PmBatch& b, eppm_pm_rng* rng, const float* lut, const eppm_params& prm, hipStream_t s, int pre_from = -1);
+EPPM_HIDDEN void pm_iterate(eppm::PmBatch& b, eppm_pm_rng* rng, const float* lut, const eppm_params& prm, hipStream_t s, int spec_mode, int pre_from = -1);
 #ifndef EPPM_SWEEP_CACHE
 #define EPPM_SWEEP_CACHE 1
 #endif

@@ -85,6 +85,10 @@ static int ctx_alloc(eppm_ctx* c)
     for (int16_t** p : {&c->nnf1, &c->nnf2, &c->nnf_tmp, &c->nnf_tmp2}) cv.plane(p, n2 * 4);
     for (float** p : {&c->cost1, &c->cost2}) cv.plane(p, n2 * 4);
     for (float** p : {&c->spec1, &c->spec2}) cv.plane(p, n2 * 4 * 4);
+    // rest-weight planes of the two-phase search (PmProblem::restw): only where a launch of this context can take that form -- the decision
+    // is monotone in the pairs per launch, so the full batch answers for every smaller one
+    if (pm_search_pretest_form(c->W[L], c->H[L], c->prm.patch_r, 2, c->npairs))
+        for (float** p : {&c->restw1, &c->restw2}) cv.plane(p, n2 * 4);
     for (int32_t** p : {&c->scand1, &c->scand2}) cv.plane(p, n2 * 4 * 4);
     for (uint32_t** p : {&c->wl1, &c->wl2}) cv.plane(p, pm_worklist_words(c->W[L], c->H[L], c->prm.seg_len) * 4);
     for (int16_t** p : {&c->seed1, &c->seed2}) cv.plane(p, n2 * 4 * 4);
@@ -121,7 +125,7 @@ extern "C" int eppm_create_batch(eppm_ctx** out, int h, int w, int device, const
     HIPCHK(hipSetDevice(device));
     eppm_ctx* c = new eppm_ctx();
     c->device = device; c->prm = p; c->h = h; c->w = w; c->npairs = npairs; c->n_active = 1;
-    c->opt_sweep_spec = opt_sweep_spec(); c->opt_no_split = opt_no_split();
+    c->opt_sweep_spec = opt_sweep_spec(); c->opt_no_split = opt_no_split(); c->opt_search_pre = opt_search_pre();
     c->nl = pyr_init_dim(c->H, c->W, h, w, p.levels, 0.5f);
     const int L = c->nl - 1;
     if (c->H[L] < 1 || c->W[L] < 1 || (c->W[L] + p.seg_len - 1) / p.seg_len > 1024 || (c->H[L] + p.seg_len - 1) / p.seg_len > 1024) {

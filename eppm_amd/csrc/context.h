@@ -17,7 +17,7 @@ struct eppm_ctx {
     int device = 0;
     hipStream_t stream = nullptr;
     bool own_stream = false;
-    int opt_sweep_spec = -1, opt_no_split = 0;     // kernel-variant switches, copied from the process defaults at creation (test support)
+    int opt_sweep_spec = -1, opt_no_split = 0, opt_search_pre = -1;     // kernel-variant switches, copied from the process defaults at creation (test support)
     eppm_params prm;
     int h = 0, w = 0, nl = 0;
     int stop_level = 0;                 // draft mode (eppm_set_stop_level): levels below it are upsampled, not refined
@@ -39,6 +39,7 @@ struct eppm_ctx {
     float *spec1 = nullptr, *spec2 = nullptr;   // evaluation cache of the sweeps (PmProblem::spec / scand): four direction planes each
     int32_t *scand1 = nullptr, *scand2 = nullptr;
     uint32_t *wl1 = nullptr, *wl2 = nullptr;    // work lists of the speculative sweeps (PmProblem::wl)
+    float *restw1 = nullptr, *restw2 = nullptr; // rest-weight planes of the two-phase search (PmProblem::restw), radius 9
     int16_t *seed1 = nullptr, *seed2 = nullptr; // merged form: the field before each direction's sweep (PmProblem::seed), four planes each
     uint32_t* wmf_ws = nullptr;        // work lists + counters of the weighted median
     bool flow_pending = false;         // eppm_compute_begin issued, eppm_compute_end not yet

@@ -190,12 +190,12 @@ static int compute_all(eppm_ctx* c)
         b.cache_plane = (size_t)lw * lh;
         b.seed_plane = (size_t)lw * lh * 2;
         b.wl_units = pm_worklist_units(lw, lh, c->prm.seg_len);
-        b.p[0] = mk_problem(planes(c, L, false), c->cost1, c->nnf1, c->nnf_tmp, c->rng, 0, c->spec1, EPPM_SWEEP_CACHE ? c->scand1 : nullptr, sweep_list_on(c->opt_sweep_spec) ? c->wl1 : nullptr, c->seed1);     // driver :223
-        b.p[1] = mk_problem(planes(c, L, true), c->cost2, c->nnf2, c->nnf_tmp2, c->rng, 1, c->spec2, EPPM_SWEEP_CACHE ? c->scand2 : nullptr, sweep_list_on(c->opt_sweep_spec) ? c->wl2 : nullptr, c->seed2);     // driver :224
-        if (!seeded) run_patchmatch(b, c->rng, c->lut_pm, c->prm, s, c->opt_sweep_spec);
+        b.p[0] = mk_problem(planes(c, L, false), c->cost1, c->nnf1, c->nnf_tmp, c->rng, 0, c->spec1, EPPM_SWEEP_CACHE ? c->scand1 : nullptr, sweep_list_on(c->opt_sweep_spec) ? c->wl1 : nullptr, c->seed1, c->restw1);     // driver :223
+        b.p[1] = mk_problem(planes(c, L, true), c->cost2, c->nnf2, c->nnf_tmp2, c->rng, 1, c->spec2, EPPM_SWEEP_CACHE ? c->scand2 : nullptr, sweep_list_on(c->opt_sweep_spec) ? c->wl2 : nullptr, c->seed2, c->restw2);     // driver :224
+        if (!seeded) run_patchmatch(b, c->rng, c->lut_pm, c->prm, s, c->opt_sweep_spec, c->opt_search_pre);
         else {
             // the random field and its costs as in a cold run (the generator states too), then the prior where it is strictly cheaper
-            pm_start(b, c->rng, c->lut_pm, c->prm, s);
+            pm_start(b, c->rng, c->lut_pm, c->prm, s, c->opt_search_pre);
             PmSeed sd;
             sd.prior[0] = c->prior1; sd.nnf_init[0] = c->nnf_init1; sd.cost_init[0] = c->cost_init1;
             sd.prior[1] = c->prior2; sd.nnf_init[1] = c->nnf_init2; sd.cost_init[1] = c->cost_init2;
@@ -203,7 +203,7 @@ static int compute_all(eppm_ctx* c)
             stage_begin(c, c->ev, "temporal_select");
             launch_pm_cost_select(b, sd, c->lut_pm, c->prm.patch_r, s);
             stage_end(c, c->ev);
-            pm_iterate(b, c->rng, c->lut_pm, c->prm, s, c->opt_sweep_spec);
+            pm_iterate(b, c->rng, c->lut_pm, c->prm, s, c->opt_sweep_spec, c->opt_search_pre);
         }
     }
     stage_end_at(c, c->ev, pm_entry);

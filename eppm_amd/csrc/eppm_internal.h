@@ -104,6 +104,9 @@ struct PmProblem {
     int16_t* seed = nullptr;
     uint32_t* rng_work;       // [nblocks][64][6] XORWOW lane states read by the random search
     uint32_t* rng_work_next;  // ... written by it (ping-pong: four workgroups read each block's state, one advances it)
+    // Rest-weight plane of the two-phase search (k_pm_search.hip; cost pitch): per pixel an upper bound, formed from the source image
+    // alone, of the weights of the patch rows the search's pre-test leaves out.  NULL: every search runs in the one-phase form.
+    float* restw = nullptr;
 };
 struct PmBatch {
     PmProblem p[2];      // the problems of pair 0; pair k's are `stride` bytes further (every pointer of PmProblem)
@@ -154,8 +157,23 @@ bool launch_pm_sweeps_merged(PmBatch& b, const float* lut, int R, int seg_len, i
 void launch_pm_jump(const PmBatch& b, const float* lut, int R, int step, hipStream_t s);
 // one 4-neighbour propagation launch (d_neighbor_propagate); reads nnf, writes nnf_alt (caller swaps)
 void launch_pm_neighbor(const PmBatch& b, const float* lut, int R, hipStream_t s);
+// pretest: the two-phase form (same results; quarter-block workgroups whatever pm_search_rows says: the caller asked pm_search_pretest)
+// where the launch has what it needs (pm_search_pretest_ready), the one-phase form otherwise
 void launch_pm_random_search(const PmBatch& b, const PmRngDev& rng, const float* lut, int R, int search_range, int num_guess,
-                             hipStream_t s);
+                             hipStream_t s, bool pretest = false);
+// fills PmProblem::restw of every problem of the batch (radius 9, exact library; nothing otherwise): once per PatchMatch run, after the images stand
+void launch_pm_rest_weight(const PmBatch& b, const float* lut, int R, hipStream_t s);
+bool pm_search_pretest_ready(const PmBatch& b, const PmRngDev& rng, int R);
+// test support: the pre-test's sums N and D_A of every pixel with its stored match as the guess, per direction k into n[k] / d[k] (cost
+// pitch; pair 0's planes, pair p's lie p * PmBatch::stride bytes further); needs the parity planes (radius 9, exact library)
+struct PmPretestSums { float* n[2]; float* d[2]; };
+void launch_pm_pretest_probe(const PmBatch& b, const float* lut, int R, const PmPretestSums& out, hipStream_t s);
+// whether a launch of that size has a two-phase form at all: radius 9, quarter-block workgroups (pm_search_rows == 4), exact library; and
+// whether the search of PatchMatch iteration `iteration` (0, 1, ..) takes it: from iteration EPPM_SEARCH_PRE_FROM on (negative: never)
+EPPM_DECISION bool pm_search_pretest_form(int w, int h, int R, int problems, int npairs);
+EPPM_DECISION bool pm_search_pretest(int iteration, int w, int h, int R, int problems, int npairs);
+// the build's knobs of the pre-test at patch radius R: first centre row and number of centre rows, threshold iteration, epsilon
+EPPM_DECISION void pm_search_pretest_knobs(int R, int* row0, int* rows, int* from, float* eps);
 // rows of a 16x16 block per workgroup of the random search: 4 (a quarter block, a wave per guess) or 2 (an eighth block: small launches
 // at radius 9 that read numbers drawn ahead, `table`); problems = directions per pair
 EPPM_DECISION int pm_search_rows(int w, int h, int R, int problems, int npairs, bool table);

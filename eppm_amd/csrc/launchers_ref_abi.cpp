@@ -479,6 +479,85 @@ extern "C" int eppm_test_c2f_refine_batch(float* d_flow, const uint32_t* d_img1,
 }
 #endif
 
+#ifdef EPPM_TEST_HOOKS
+// include/eppm_test.h: ONE random-search launch over npairs x ndir problems as a context issues it -- census and texel planes, the
+// column-parity planes, numbers drawn ahead (slot 7) and, for pretest != 0, the rest-weight planes, laid out pair after pair in a slab of
+// one stride (slot 0).  Caller planes unpitched: images pair after pair, fields and costs problem after problem (pair p, direction k at
+// p * ndir + k; direction 1 matches image 2 against image 1).
+extern "C" int eppm_test_pm_search(eppm_pm_rng* r, float* d_cost, eppm_short2* d_nnf, const uint32_t* d_img1, const uint32_t* d_img2, int w, int h,
+                                   int ndir, int npairs, int pretest, float* d_restw, float* d_pre_n, float* d_pre_d)
+{
+    if (!r || !d_cost || !d_nnf || !d_img1 || !d_img2 || w != r->w || h != r->h || ndir < 1 || ndir > 2 || npairs < 1)
+        return set_err(EPPM_ERR_ARG, "eppm_test_pm_search: bad argument");
+    LAUNCHER_BEGIN_INT;
+    const int R = g_prm.patch_r;
+    if (r->G != g_prm.num_guess || (R != 9 && R != 17)) return set_err(EPPM_ERR_ARG, "eppm_test_pm_search: num_guess %d / patch_r %d", r->G, R);
+    const size_t n = (size_t)w * h;
+    const int pad = (R + 2) & ~1, ppitch = parity_pitch(w, pad);
+    size_t off = 0;
+    auto carve = [&](size_t bytes) { const size_t o = off; off = (off + bytes + 255) & ~(size_t)255; return o; };
+    size_t o_img[2], o_cen[2], o_pk[2], o_pc[2], o_pp[2], o_cost[2], o_nnf[2], o_rw[2], o_pn[2], o_pd[2];
+    for (int k = 0; k < 2; k++) { o_img[k] = carve(n * 4); o_cen[k] = carve(n); o_pk[k] = carve(n * 16); o_pc[k] = carve(n * 4); o_pp[k] = carve((size_t)2 * h * ppitch * 4); }
+    for (int k = 0; k < ndir; k++) { o_cost[k] = carve(n * 4); o_nnf[k] = carve(n * 4); o_rw[k] = carve(n * 4); o_pn[k] = carve(n * 4); o_pd[k] = carve(n * 4); }
+    const size_t stride = (off + 4095) & ~(size_t)4095;
+    void *slab = nullptr, *tab = nullptr;
+    CHK(get_scratch(ds, stride * npairs, &slab, 0));
+    CHK(get_scratch(ds, (size_t)r->gx * r->gy * 512 * r->G * sizeof(int16_t), &tab, 7));
+    char* S = (char*)slab;
+    for (int p = 0; p < npairs; p++) {
+        CHK(copy_d2d(S + p * stride + o_img[0], d_img1 + p * n, n * 4));
+        CHK(copy_d2d(S + p * stride + o_img[1], d_img2 + p * n, n * 4));
+        for (int k = 0; k < ndir; k++) {
+            CHK(copy_d2d(S + p * stride + o_cost[k], d_cost + (p * ndir + k) * n, n * 4));
+            CHK(copy_d2d(S + p * stride + o_nnf[k], (const char*)d_nnf + (p * ndir + k) * n * 4, n * 4));
+        }
+    }
+    const Batch bt{npairs, stride};
+    CensusBatch cb;
+    cb.n = 2;
+    for (int k = 0; k < 2; k++) {
+        CensusJob& J = cb.job[k];
+        J.census = (uint8_t*)(S + o_cen[k]); J.cpitch = w; J.texels = S + o_pk[k]; J.tpitch = w; J.img = (const uint32_t*)(S + o_img[k]); J.ipitch = w;
+        J.w = w; J.h = h; J.first_block = 0; J.packed = (uint32_t*)(S + o_pc[k]);
+    }
+    launch_census_batch(cb, g_stream, bt);
+    for (int k = 0; k < 2; k++) launch_parity_planes((uint32_t*)(S + o_pp[k]), ppitch, pad, (const uint32_t*)(S + o_pc[k]), w, w, h, g_stream, bt);
+    PmBatch b;
+    b.n = ndir; b.cpitch = w; b.npitch = w; b.npairs = npairs; b.stride = stride;
+    for (int k = 0; k < ndir; k++) {
+        PlanesH P;
+        P.pk1 = S + o_pk[k]; P.pk2 = S + o_pk[k ^ 1]; P.w = w; P.h = h; P.pitch = w;
+        P.pc1 = (const uint32_t*)(S + o_pc[k]); P.pc2 = (const uint32_t*)(S + o_pc[k ^ 1]);
+        P.pp1 = (const uint32_t*)(S + o_pp[k]); P.pp2 = (const uint32_t*)(S + o_pp[k ^ 1]); P.pp_pitch = ppitch; P.pp_pad = pad;
+        b.p[k] = mk_problem(P, (float*)(S + o_cost[k]), (int16_t*)(S + o_nnf[k]), nullptr, nullptr, 0, nullptr, nullptr, nullptr, nullptr, (float*)(S + o_rw[k]));
+    }
+    PmRngDev d = r->dev();
+    launch_pm_rand_table(d, r->work[0][r->cur[0]], (int16_t*)tab, r->G, g_stream);
+    d.rand_tab = (const int16_t*)tab;
+    if (pretest) {
+        if (!pm_search_pretest_ready(b, d, R)) return set_err(EPPM_ERR_ARG, "eppm_test_pm_search: no two-phase search at patch_r %d", R);
+        launch_pm_rest_weight(b, ds->lut_pm, R, g_stream);
+        if (d_pre_n && d_pre_d) {          // the sums of the fields as they stand BEFORE the search
+            PmPretestSums ps{};
+            for (int k = 0; k < ndir; k++) { ps.n[k] = (float*)(S + o_pn[k]); ps.d[k] = (float*)(S + o_pd[k]); }
+            launch_pm_pretest_probe(b, ds->lut_pm, R, ps, g_stream);
+        }
+    }
+    launch_pm_random_search(b, d, ds->lut_pm, R, g_prm.search_range, g_prm.num_guess, g_stream, pretest != 0);
+    for (int p = 0; p < npairs; p++)
+        for (int k = 0; k < ndir; k++) {
+            CHK(copy_d2d(d_cost + (p * ndir + k) * n, S + p * stride + o_cost[k], n * 4));
+            CHK(copy_d2d((char*)d_nnf + (p * ndir + k) * n * 4, S + p * stride + o_nnf[k], n * 4));
+            if (pretest && d_restw) CHK(copy_d2d(d_restw + (p * ndir + k) * n, S + p * stride + o_rw[k], n * 4));
+            if (pretest && d_pre_n && d_pre_d) {
+                CHK(copy_d2d(d_pre_n + (p * ndir + k) * n, S + p * stride + o_pn[k], n * 4));
+                CHK(copy_d2d(d_pre_d + (p * ndir + k) * n, S + p * stride + o_pd[k], n * 4));
+            }
+        }
+    return finish();
+}
+#endif
+
 extern "C" void baoCudaFlowSmoothing(eppm_float2* d_flow, eppm_uchar4* d_img, int w, int h, size_t img_pitch, size_t flow_pitch)
 {
     LAUNCHER_BEGIN;

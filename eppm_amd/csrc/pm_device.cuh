@@ -105,6 +105,20 @@
 #ifndef EPPM_SEARCH_PK17
 #define EPPM_SEARCH_PK17 1                    // the streaming search at radius 17 gathers the 4-byte target plane (PK = 1)
 #endif
+// The two-phase search (k_pm_random_search<.., PRE = true>): a guess whose cost can be PROVED not to beat the
+// pixel's stored cost from a few centre rows of its patch is never evaluated in full.
+#ifndef EPPM_SEARCH_PRE_ROWS
+#define EPPM_SEARCH_PRE_ROWS 4                // centre rows of the patch the pre-test evaluates (radius 9: rows 3-6 of 0-9, 40 of 100 samples)
+#endif
+#ifndef EPPM_SEARCH_PRE_FROM
+#define EPPM_SEARCH_PRE_FROM 2                // first PatchMatch iteration whose search runs in the two-phase form; negative: never
+#endif
+#ifndef EPPM_SEARCH_PRE_COOP_MAX
+#define EPPM_SEARCH_PRE_COOP_MAX 96           // up to so many survivors in a workgroup, phase 2 gives each 16 lanes (all waves work) instead of one lane
+#endif
+#ifndef EPPM_SEARCH_PRE_EPS
+#define EPPM_SEARCH_PRE_EPS 0x1p-13f          // shrinks the lower bound: >= 4 x the float error of its two sides (tests/test_search_pretest_cpu.py)
+#endif
 
 namespace eppm {
 
@@ -136,6 +150,7 @@ __device__ __forceinline__ PmProblem pm_problem(const PmBatch& B, unsigned q)
     p.seed = pair_ptr_opt(p.seed, B.stride, pair);
     p.rng_work = pair_ptr_opt(p.rng_work, B.stride, pair);
     p.rng_work_next = pair_ptr_opt(p.rng_work_next, B.stride, pair);
+    p.restw = pair_ptr_opt(p.restw, B.stride, pair);
     return p;
 }
 
@@ -251,6 +266,54 @@ EPPM_PM_UNROLL((TU))
     }
     return sum.result();
 }
+
+constexpr int pre_row0(int S) { return (S - EPPM_SEARCH_PRE_ROWS) / 2; }        // first of the centre rows of the two-phase search's pre-test
+#ifndef EPPM_TOL
+// ---- the pre-test of the two-phase search (exact library) ----
+// A patch cost is cs / ws = sum c_k w_k / sum w_k with c_k >= 0 and w_k = gsp_k fast_exp(-(a2_k + t_k) / s): a2_k is the SOURCE half of the
+// weight's argument (the pixel against its own sample), t_k >= 0 the target half, so w_k <= u_k := gsp_k fast_exp(-a2_k / s) whatever the
+// guess.  With A = the EPPM_SEARCH_PRE_ROWS centre rows of the patch:  cs / ws >= sum_A c_k w_k / (sum_A w_k + sum_{not A} u_k).
+// u_k of one sample: patch_terms' weight with the target half of its argument left out
+__device__ __forceinline__ float rest_weight_term(const rgbf c1, const float4 q1, float gsp)
+{
+    float a2 = max_abs_diff(c1, texel_rgb(q1));
+    a2 *= a2;
+    return fast_exp(div_ad2(-a2)) * gsp;
+}
+// sum_A c_k w_k and sum_A w_k of a guess: rows A of search_patch_dist's parity-plane form (PK = 2) -- the same loads, the same terms, row major
+template <int RT, class LUT>
+__device__ __forceinline__ void search_patch_centre_rows(const Planes& P, const LUT& L, const float4* __restrict__ s_src, int TW, int tx, int ty,
+                                                         int x2, int y2, const PlanesH& PH, float& cs, float& ws)
+{
+    constexpr int S = RT + 1, I0 = pre_row0(S);
+    static_assert(S % 4 == 2 && EPPM_SEARCH_PRE_ROWS >= 1 && EPPM_SEARCH_PRE_ROWS <= S, "rows of whole dwordx4 gathers + one dwordx2");
+    const int pitch16 = P.pitch << 4;
+    const rgbf c1 = texel_rgb(s_src[(ty + RT) * TW + tx + RT]);
+    const rgbf c2 = texel_rgb(texel_at(P.pk2, texel_off(pitch16, P.w, P.h, x2, y2)));
+    const __amdgpu_buffer_rsrc_t rs = __builtin_amdgcn_make_buffer_rsrc(const_cast<uint32_t*>(PH.pp2), 0, 2 * P.h * PH.pp_pitch * 4, 0x00020000);
+    const int xp = x2 - RT + PH.pp_pad;
+    const int rb = ((xp & 1) * P.h) * PH.pp_pitch + (xp >> 1);
+    cs = 0.0f; ws = 0.0f;
+#pragma unroll 2
+    for (int ii = I0; ii < I0 + EPPM_SEARCH_PRE_ROWS; ii++) {
+        const int ro = (rb + iclamp(y2 + 2 * ii - RT, 0, P.h - 1) * PH.pp_pitch) * 4;
+        const float4* __restrict__ srow = s_src + (ty + 2 * ii) * TW + tx;
+        uint32_t wq[S];
+#pragma unroll
+        for (int g = 0; g < S / 4; g++) {
+            const u32x4 v = __builtin_amdgcn_raw_buffer_load_b128(rs, ro + 16 * g, 0, 0);
+            wq[4 * g] = v.x; wq[4 * g + 1] = v.y; wq[4 * g + 2] = v.z; wq[4 * g + 3] = v.w;
+        }
+        { const u32x2 v = __builtin_amdgcn_raw_buffer_load_b64(rs, ro + 4 * (S - 2), 0, 0); wq[S - 2] = v.x; wq[S - 1] = v.y; }
+EPPM_PM_UNROLL(((S % 5 == 0) ? 5 : S))
+        for (int jj = 0; jj < S; jj++) {
+            float ct, wt;
+            patch_terms(srow[2 * jj], unpack_texel(wq[jj], 0u), c1, c2, L.gsp[ii * S + jj], L.tab(), ct, wt);
+            patch_accum(cs, ws, ct, wt);
+        }
+    }
+}
+#endif
 
 // the (kBlock + 2 RT)^2 source samples around the 16x16 block (bx, by), clamped at load, staged by the 256 threads of a workgroup (no
 // barrier): the cost-field kernels (k_pm_cost_field_tile and the seeded start's k_pm_cost_select_tile evaluate from the same tile)

@@ -6,20 +6,21 @@
 using namespace eppm;
 
 // ---- baoCudaPatchMatch (kernel.cu:1760-1826) for one problem or for the forward+backward pair at once ----
-PmProblem mk_problem(const PlanesH& P, float* cost, int16_t* nnf, int16_t* nnf_alt, eppm_pm_rng* rng, int k, float* spec, int32_t* scand, uint32_t* wl, int16_t* seed)
+PmProblem mk_problem(const PlanesH& P, float* cost, int16_t* nnf, int16_t* nnf_alt, eppm_pm_rng* rng, int k, float* spec, int32_t* scand, uint32_t* wl, int16_t* seed,
+                     float* restw)
 {
     PmProblem p;
-    p.P = P; p.cost = cost; p.nnf = nnf; p.nnf_alt = nnf_alt; p.spec = spec; p.scand = scand; p.wl = wl; p.seed = seed;
+    p.P = P; p.cost = cost; p.nnf = nnf; p.nnf_alt = nnf_alt; p.spec = spec; p.scand = scand; p.wl = wl; p.seed = seed; p.restw = restw;
     p.rng_work = rng ? rng->work[k][rng->cur[k]] : nullptr;
     p.rng_work_next = rng ? rng->work[k][rng->cur[k] ^ 1] : nullptr;
     return p;
 }
 // one random search on the batch; afterwards the advanced RNG states are the current ones
-void search(PmBatch& b, eppm_pm_rng* rng, const float* lut, const eppm_params& prm, hipStream_t s, int launch_no)
+void search(PmBatch& b, eppm_pm_rng* rng, const float* lut, const eppm_params& prm, hipStream_t s, int launch_no, bool pretest)
 {
     PmRngDev d = rng->dev();
     if (rng->rand_tab && launch_no >= 0) d.rand_tab = rng->rand_tab + (size_t)launch_no * rng->rand_stride;
-    launch_pm_random_search(b, d, lut, prm.patch_r, prm.search_range, prm.num_guess, s);
+    launch_pm_random_search(b, d, lut, prm.patch_r, prm.search_range, prm.num_guess, s, pretest);
     for (int k = 0; k < b.n; k++) {
         std::swap(b.p[k].rng_work, b.p[k].rng_work_next);
         rng->cur[k] ^= 1;
@@ -90,20 +91,34 @@ void neighbor(PmBatch& b, const float* lut, const eppm_params& prm, int launches
         for (int k = 0; k < b.n; k++) std::swap(b.p[k].nnf, b.p[k].nnf_alt);
     }
 }
-// returns with the NNF of problem k in b.p[k].nnf (an even number of sweeps: the caller's buffer)
-void run_patchmatch(PmBatch& b, eppm_pm_rng* rng, const float* lut, const eppm_params& prm, hipStream_t s, int spec_mode)
+// Whether the search of iteration `it` runs in the two-phase form (k_pm_search.hip).  pre_from < 0: the library's own decision; otherwise the
+// test switch "search_pre_from" moves the threshold (beyond the last iteration: never) and leaves the rest of the decision alone.
+static bool search_pretest(const PmBatch& b, const eppm_params& prm, int it, int pre_from)
 {
-    pm_start(b, rng, lut, prm, s);
-    pm_iterate(b, rng, lut, prm, s, spec_mode);
+    const int w = b.p[0].P.w, h = b.p[0].P.h;
+    if (pre_from < 0) return pm_search_pretest(it, w, h, prm.patch_r, b.n, b.npairs);
+    return it >= pre_from && pm_search_pretest_form(w, h, prm.patch_r, b.n, b.npairs);
+}
+// returns with the NNF of problem k in b.p[k].nnf (an even number of sweeps: the caller's buffer)
+void run_patchmatch(PmBatch& b, eppm_pm_rng* rng, const float* lut, const eppm_params& prm, hipStream_t s, int spec_mode, int pre_from)
+{
+    pm_start(b, rng, lut, prm, s, pre_from);
+    pm_iterate(b, rng, lut, prm, s, spec_mode, pre_from);
 }
 // the random field and its costs; a streaming context puts its seeded start (launch_pm_cost_select) between this and the iterations
-void pm_start(PmBatch& b, eppm_pm_rng* rng, const float* lut, const eppm_params& prm, hipStream_t s)
+void pm_start(PmBatch& b, eppm_pm_rng* rng, const float* lut, const eppm_params& prm, hipStream_t s, int pre_from)
 {
     b.sweep_seq = 0;
     launch_pm_init_field(b, rng->dev(), s);
     launch_pm_cost_field(b, lut, prm.patch_r, s);
+    // the rest-weight planes of the two-phase searches of this run: they depend on the source images alone (the decision is monotone in
+    // the iteration: the last one answers for all)
+    PmRngDev d = rng->dev();
+    d.rand_tab = rng->rand_tab;
+    if (prm.num_iter > 0 && search_pretest(b, prm, prm.num_iter - 1, pre_from) && pm_search_pretest_ready(b, d, prm.patch_r))
+        launch_pm_rest_weight(b, lut, prm.patch_r, s);
 }
-void pm_iterate(PmBatch& b, eppm_pm_rng* rng, const float* lut, const eppm_params& prm, hipStream_t s, int spec_mode)
+void pm_iterate(PmBatch& b, eppm_pm_rng* rng, const float* lut, const eppm_params& prm, hipStream_t s, int spec_mode, int pre_from)
 {
     for (int it = 0; it < prm.num_iter; it++) {
         if (prm.propagation == 1) jump(b, lut, prm, s);
@@ -113,7 +128,7 @@ void pm_iterate(PmBatch& b, eppm_pm_rng* rng, const float* lut, const eppm_param
             if (sweeps_merged(it, pixels, problem_pixels, spec_mode) && launch_pm_sweeps_merged(b, lut, prm.patch_r, prm.seg_len, it, s)) { /* in place */ }
             else for (int dir = 0; dir < 4; dir++) sweep(b, lut, prm, dir, s, sweep_speculative(it, pixels, spec_mode));
         }
-        search(b, rng, lut, prm, s, it);
+        search(b, rng, lut, prm, s, it, search_pretest(b, prm, it, pre_from));
     }
 }
 

@@ -9,6 +9,7 @@ std::atomic<int> g_opt_rand_table{1};
 std::atomic<int> g_opt_sweep_spec{-1};
 std::atomic<int> g_opt_no_split{0};
 std::atomic<int> g_opt_force_split{0};
+std::atomic<int> g_opt_search_pre{-1};
 
 static int probe(const float* x, float* y, int n, int which)
 {
@@ -28,6 +29,7 @@ extern "C" int eppm_test_set_option(const char* name, int value)
     if (!strcmp(name, "c2f_force_split")) { g_opt_force_split.store(value); return EPPM_OK; }
     if (!strcmp(name, "sweep_spec")) { g_opt_sweep_spec.store(value); return EPPM_OK; }
     if (!strcmp(name, "rand_table")) { g_opt_rand_table.store(value); return EPPM_OK; }
+    if (!strcmp(name, "search_pre_from")) { g_opt_search_pre.store(value); return EPPM_OK; }
     return set_err(EPPM_ERR_ARG, "eppm_test_set_option: unknown option '%s'", name);
 }
 extern "C" int eppm_probe_c2f_window(int patch_r, int* span_x, int* span_y)
@@ -67,6 +69,15 @@ extern "C" int eppm_probe_dispatch(const char* stage, const int* args, int nargs
         return EPPM_OK;
     }
     return set_err(EPPM_ERR_ARG, "eppm_probe_dispatch: unknown stage '%s'", stage);
+}
+// the two-phase search's decision (eppm_internal.h: pm_search_pretest) and the knobs its pre-test was built with
+extern "C" int eppm_probe_search_pretest(int iteration, int w, int h, int patch_r, int problems, int npairs, int* out, float* eps)
+{
+    if (!out || !eps || iteration < 0 || w < 1 || h < 1 || patch_r < 1 || problems < 1 || npairs < 1) return set_err(EPPM_ERR_ARG, "eppm_probe_search_pretest: bad argument");
+    out[0] = pm_search_pretest(iteration, w, h, patch_r, problems, npairs) ? 1 : 0;
+    pm_search_pretest_knobs(patch_r, &out[1], &out[2], &out[3], eps);
+    out[4] = pm_search_pretest_form(w, h, patch_r, problems, npairs) ? 1 : 0;
+    return EPPM_OK;
 }
 extern "C" int eppm_probe_fast_exp(const float* x, float* y, int n) { return probe(x, y, n, 0); }
 extern "C" int eppm_probe_div_const(const float* x, float* y, int n, int which) { return probe(x, y, n, 1 + which); }

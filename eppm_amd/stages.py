@@ -212,6 +212,35 @@ def pm_random_search(rng, cost, nnf, P):
     return c.get(), n.get()
 
 
+def pm_search_launch(rng, costs, nnfs, pairs, ndir=1, pretest=False, sums=False):
+    """eppm_test_pm_search (test library): ONE random-search launch over len(pairs) x ndir problems as a context issues it (parity planes,
+    numbers drawn ahead).  pairs: (img1, img2) uchar4 per pair; costs / nnfs: one per problem, pair p's direction k at p * ndir + k.
+    pretest: the two-phase form.  Returns (costs, nnfs, rest-weight planes or None), one array per problem; sums (with pretest): also the
+    pre-test's (N, D_A) planes of every pixel with its match in nnfs as the guess, as a fourth and fifth list."""
+    h, w = nnfs[0].shape
+    n = len(nnfs)
+    assert n == len(pairs) * ndir == len(costs)
+    c = Dev(np.concatenate([np.ascontiguousarray(x, np.float32) for x in costs]))
+    f = Dev(np.concatenate([np.ascontiguousarray(x, short2) for x in nnfs]))
+    i1, i2 = (Dev(np.concatenate([np.ascontiguousarray(p[k], uchar4) for p in pairs])) for k in range(2))
+    u = Dev(shape=(n * h, w), dtype=np.float32) if pretest else None
+    pn, pd = (Dev(shape=(n * h, w), dtype=np.float32) for _ in range(2)) if pretest and sums else (None, None)
+    check(lib().eppm_test_pm_search(rng.p, c.ptr, f.ptr, i1.ptr, i2.ptr, w, h, ndir, len(pairs), int(pretest), u.ptr if u else None,
+                                    pn.ptr if pn else None, pd.ptr if pd else None), "eppm_test_pm_search")
+    split = lambda a: [a[k * h:(k + 1) * h] for k in range(n)]  # noqa: E731
+    out = (split(c.get()), split(f.get()), split(u.get()) if u else None)
+    return out + (split(pn.get()), split(pd.get())) if pn else out
+
+
+def probe_search_pretest(iteration, w, h, patch_r=9, problems=2, npairs=1):
+    """eppm_probe_search_pretest (test library, no GPU needed): (two-phase form at this iteration?, first centre row, centre rows, threshold
+    iteration, eps, has the launch a two-phase form at all?)"""
+    out = (C.c_int * 5)()
+    eps = C.c_float()
+    check(lib().eppm_probe_search_pretest(iteration, w, h, patch_r, problems, npairs, out, C.byref(eps)), "eppm_probe_search_pretest")
+    return bool(out[0]), out[1], out[2], out[3], eps.value, bool(out[4])
+
+
 def patchmatch(P):
     """baoCudaPatchMatch -> (nnf, cost)"""
     n, c = Dev(shape=(P.h, P.w), dtype=short2), Dev(shape=(P.h, P.w), dtype=np.float32)

@@ -32,7 +32,10 @@ extern "C" {
  * library takes by itself from the sixth iteration on -- from the eighth on problems of more than 65 536 pixels, i.e. the quarter-resolution
  * level of 1920x1080 and 3840x2160 pairs).  "rand_table": 1 (default) a context's random searches read numbers drawn ahead per geometry,
  * 0 they draw while they search -- the form a context takes by itself when the table would exceed 512 MB; 2: as 1, and the stand-alone
- * eppm_pm_random_search, which otherwise draws while it searches, reads its launch's numbers drawn ahead as well (radius 9 and 17). */
+ * eppm_pm_random_search, which otherwise draws while it searches, reads its launch's numbers drawn ahead as well (radius 9 and 17).
+ * "search_pre_from": -1 (default) a context's random searches take the two-phase form (pre-test on the centre rows, then the survivors
+ * in full) from the iteration the library itself chooses (eppm_probe_search_pretest), k >= 0: from iteration k on -- beyond the last
+ * iteration: never --, wherever the launch has a two-phase form at all (patch radius 9, quarter-block workgroups). */
 int  eppm_test_set_option(const char* name, int value);
 /* admissible spread (max - min, pixels) of a 16x16 tile's candidate centres for which the LDS-window refine kernels stage the
  * target window; wider tiles take the per-access path inside the same launch (patch_r 9 or 17) */
@@ -42,6 +45,22 @@ int  eppm_probe_c2f_window(int patch_r, int* span_x, int* span_y);
  * bytes.  Patch radius from eppm_set_launcher_params; never split ("c2f_no_split" or not: this entry brings no cost scratch). */
 int  eppm_test_c2f_refine_batch(float* d_flow, const uint32_t* d_img1, const uint32_t* d_img2, const uint8_t* d_census1,
                                 const uint8_t* d_census2, int w, int h, int npairs);
+/* ONE random-search launch over npairs x ndir problems of one size, as a context issues it: the entry builds the census and texel planes,
+ * the column-parity planes and the launch's numbers drawn ahead from r's current states (which it advances by one launch, as
+ * eppm_pm_random_search does).  Device planes unpitched: images npairs x h x w RGBA words; d_nnf (short2) and d_cost, searched in place,
+ * (npairs * ndir) x h x w with pair p's direction k at p * ndir + k -- direction 0 matches image 1 against image 2, direction 1 image 2
+ * against image 1.  pretest = 0: the one-phase kernel; 1: the rest-weight planes are filled (copied to d_restw, laid out as d_cost, unless
+ * NULL) and the launch takes the two-phase form in quarter-block workgroups whatever its size -- EPPM_ERR_ARG at patch radius 17.  Patch radius (9 or 17),
+ * search range and guesses from eppm_set_launcher_params.  d_pre_n, d_pre_d (both or neither; laid out as d_cost; pretest = 1 only): the
+ * pre-test's two sums -- cost-weighted and plain weight sum over the centre rows -- of every pixel with its match in d_nnf AS PASSED IN as the
+ * guess, formed by the search kernel's own helper on its own tile before the search runs. */
+int  eppm_test_pm_search(eppm_pm_rng* r, float* d_cost, eppm_short2* d_nnf, const uint32_t* d_img1, const uint32_t* d_img2, int w, int h,
+                         int ndir, int npairs, int pretest, float* d_restw, float* d_pre_n, float* d_pre_d);
+/* Whether the random search of PatchMatch iteration `iteration` (0, 1, ..) of a launch of that size takes the two-phase form (the driver's
+ * own decision function; pure host code): out[0] = 1 / 0; and the knobs this build's pre-test was compiled with: out[1] the first and
+ * out[2] the number of the patch rows it evaluates, out[3] the threshold iteration (negative: never), *eps the factor 1 - eps that
+ * shrinks its lower bound; out[4] = 1 / 0: a launch of that size has a two-phase form at all (what "search_pre_from" can switch on). */
+int  eppm_probe_search_pretest(int iteration, int w, int h, int patch_r, int problems, int npairs, int* out, float* eps);
 /* What the launchers decide by the size of a launch, answered by the functions the launchers themselves ask; pure host code, no GPU
  * needed.  stage, args -> out:
  *   "smoothing"  w, h, npairs                            -> pixels per lane: 1 (k_flow_blf<1>) or 2 (k_flow_blf<2>)
