@@ -50,6 +50,10 @@ class CCutStats(C.Structure):
                     cut=int(self.cut), stepped=int(self.stepped))
 
 
+class CMBlurParams(C.Structure):
+    _fields_ = [("shutter", C.c_float), ("max_radius", C.c_float), ("taps", C.c_int)]
+
+
 class CTrackCounts(C.Structure):
     _fields_ = [("live", C.c_int), ("ended", C.c_int), ("seeded", C.c_int), ("dropped", C.c_int), ("frame", C.c_int), ("next_id", C.c_int)]
 
@@ -96,6 +100,8 @@ SYMBOLS = [
     "eppm_stab_set_path", "eppm_gmotion_fit_host", "eppm_stab_update_host", "eppm_stab_warp_host",
     "eppm_cutdet_default_params", "eppm_cutdet_create", "eppm_cutdet_create_size", "eppm_cutdet_destroy", "eppm_cutdet_step",
     "eppm_cutdet_step_frames", "eppm_cutdet_get", "eppm_cutdet_cuts", "eppm_cutdet_host",
+    "eppm_mblur_default_params", "eppm_motion_blur", "eppm_motion_blur_device", "eppm_batch_motion_blur", "eppm_motion_blur_frames",
+    "eppm_motion_blur_host",
 ]
 
 

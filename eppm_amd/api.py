@@ -3,7 +3,7 @@ import ctypes as C
 
 import numpy as np
 
-from ._lib import CCutParams, CCutStats, CGMotionModel, CParams, CStabParams, CTFilterParams, CTrackCounts, CTrackParams, EppmError, check, lib
+from ._lib import CCutParams, CCutStats, CGMotionModel, CMBlurParams, CParams, CStabParams, CTFilterParams, CTrackCounts, CTrackParams, EppmError, check, lib
 
 uchar4 = np.dtype([("x", "u1"), ("y", "u1"), ("z", "u1"), ("w", "u1")])
 short2 = np.dtype([("x", "i2"), ("y", "i2")])
@@ -61,6 +61,17 @@ def _times(times):
     if not ts:
         raise EppmError("interpolate: at least one time")
     return (C.c_float * len(ts))(*ts)
+
+
+def MBlurParams(**kw):
+    """eppm_mblur_params with the defaults of DESIGN.md section 18 (shutter 0.5, max_radius 16, taps 8)."""
+    p = CMBlurParams()
+    check(lib().eppm_mblur_default_params(C.byref(p)), "eppm_mblur_default_params")
+    for k, v in kw.items():
+        if not hasattr(p, k):
+            raise TypeError(f"unknown motion-blur parameter {k}")
+        setattr(p, k, v)
+    return p
 
 
 def TrackParams(params=None, **kw):
@@ -459,6 +470,40 @@ def flow_sequence(frames, params=None, temporal=True, bidirectional=False, stop_
             det.close()
         e.close()
     return (out, cuts) if auto_cut else out
+
+
+def motion_blur_sequence(frames, params=None, shutter=0.5, max_radius=16, taps=8, temporal=True, stop_level=0):
+    """A clip ((h, w, 3) uint8 frames) with a synthetic shutter (EPPM.motion_blur): one streaming context --
+    set_data, then push_frame --, a forward-only compute per pair and its image 1 blurred along the forward flow; the last pair is computed
+    bidirectionally and gives the clip's last frame too, blurred along the backward flow.  Returns len(frames) frames.  Memory does not grow
+    with the clip.  params: the flow's eppm Params; temporal / stop_level: the flow's temporal and draft modes."""
+    stop_level = _level(stop_level)
+    frames = [np.ascontiguousarray(f, np.uint8) for f in frames]
+    if len(frames) < 2:
+        raise EppmError("motion_blur_sequence: at least two frames")
+    h, w, _ = frames[0].shape
+    blur = dict(shutter=shutter, max_radius=max_radius, taps=taps)
+    e = EPPM(params=params)
+    out = []
+    try:
+        e.init(h, w)
+        e.set_temporal(temporal)
+        e.set_stop_level(stop_level)
+        for k in range(len(frames) - 1):
+            if k == 0:
+                e.set_data(frames[0], frames[1])
+            else:
+                e.push_frame(frames[k + 1])
+            if k < len(frames) - 2:
+                e.compute_flow()
+                out.append(e.motion_blur(frame=0, **blur))
+            else:
+                e.compute_flow_bidirectional_device()
+                out.append(e.motion_blur(frame=0, **blur))
+                out.append(e.motion_blur(frame=1, **blur))
+    finally:
+        e.close()
+    return out
 
 
 def _sequence_plan(lengths, slots):
@@ -932,6 +977,23 @@ class EPPM:
         ptrs = (C.c_void_p * len(ts))(*d_ptrs)
         check(lib().eppm_interpolate_device(self._ctx, len(ts), ts, ptrs, C.c_size_t(pitch)), "eppm_interpolate_device")
 
+    def motion_blur(self, shutter=0.5, max_radius=16, taps=8, frame=0):
+        """The frame as a camera with an open shutter would have recorded it (eppm_motion_blur): an (h, w, 3) uint8
+        R,G,B array.  frame=0: image 1 along the forward flow, after any compute of the current images; frame=1: image 2 along the backward
+        flow, after compute_flow_bidirectional.  shutter: the open fraction of the frame interval; max_radius: the longest half-vector
+        in pixels; taps: taps to each side of a pixel."""
+        self._need()
+        p = MBlurParams(shutter=shutter, max_radius=max_radius, taps=taps)
+        out = np.empty((self.h, self.w, 3), np.uint8)
+        check(lib().eppm_motion_blur(self._ctx, C.byref(p), int(frame), out.ctypes.data_as(C.c_void_p), C.c_size_t(self.w * 3)), "eppm_motion_blur")
+        return out
+
+    def motion_blur_device(self, d_rgba, pitch, shutter=0.5, max_radius=16, taps=8, frame=0):
+        """eppm_motion_blur_device: asynchronous on the context's stream; d_rgba: a device RGBA plane of pitch bytes per row."""
+        self._need()
+        p = MBlurParams(shutter=shutter, max_radius=max_radius, taps=taps)
+        check(lib().eppm_motion_blur_device(self._ctx, C.byref(p), int(frame), C.c_void_p(d_rgba), C.c_size_t(pitch)), "eppm_motion_blur_device")
+
     def compute_flow_color(self, max_disp=(20.0, 20.0)):
         """The optional color_flow output of compute_flow (driver .cpp:308-314): (h, w, 3) uint8 R,G,B of the last flow."""
         self._need()
@@ -1147,6 +1209,13 @@ class EPPMBatch:
         out = [[np.empty((self.h, self.w, 3), np.uint8) for _ in range(len(ts))] for _ in range(self.n)]
         flat = [a for row in out for a in row]
         check(lib().eppm_batch_interpolate(self._ctx, len(ts), ts, self._ptrs(flat), C.c_size_t(self.w * 3)), "eppm_batch_interpolate")
+        return out
+
+    def motion_blur(self, shutter=0.5, max_radius=16, taps=8, frame=0):
+        """[blurred frame for each active pair] (eppm_batch_motion_blur); see EPPM.motion_blur."""
+        p = MBlurParams(shutter=shutter, max_radius=max_radius, taps=taps)
+        out = [np.empty((self.h, self.w, 3), np.uint8) for _ in range(self.n)]
+        check(lib().eppm_batch_motion_blur(self._ctx, C.byref(p), int(frame), self._ptrs(out), C.c_size_t(self.w * 3)), "eppm_batch_motion_blur")
         return out
 
     def compute_flow_device(self, d_flows=None):

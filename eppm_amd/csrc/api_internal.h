@@ -10,7 +10,8 @@
 //   context.cpp            eppm_ctx: create / destroy / planes / stage times (the class's init), the only one of the four that reads opt_*
 //   ctx_images.cpp         set_images, push_image, prepare, the host upload of one image (the class's set_data)
 //   ctx_compute.cpp        compute in all its forms, the post-PatchMatch branch of both directions, temporal mode (the class's compute_flow)
-//   ctx_interp.cpp         frame interpolation, the tracker's, the temporal filter's, the stabiliser's and the cut detector's view of a context
+//   ctx_interp.cpp         frame interpolation, the synthetic shutter, the tracker's, the temporal filter's, the stabiliser's and the cut
+//                          detector's view of a context
 //   device_api.cpp         device-memory plumbing of the ABI (malloc / memcpy / NUMA binding)
 //   launchers_ref_abi.cpp  the reference's live extern "C" stage launchers and the sub-stage entry points of the parity tests
 //   test_hooks.cpp         libeppm_hip_test.so only: include/eppm_test.h

@@ -85,6 +85,15 @@ struct eppm_ctx {
     int32_t *itp_fill1 = nullptr, *itp_fill2 = nullptr;
     uint8_t* itp_rgb = nullptr;
     uint8_t* h_itp = nullptr;
+    // Synthetic shutter (eppm_motion_blur*): its own allocation, made by the first such call, for npairs pairs: the
+    // packed planes (mbl_plane words per pair), the tile keys (mbl_tplane per pair) and the packed RGB outputs of the host-pointer forms
+    // (h*w*3 bytes per pair); h_mbl: pinned copy of those outputs, allocated on the first host-pointer call.
+    char* mbl = nullptr;
+    size_t mbl_bytes = 0, mbl_plane = 0, mbl_tplane = 0, h_mbl_bytes = 0;
+    uint32_t* mbl_packed = nullptr;
+    uint64_t* mbl_tkeys = nullptr;
+    uint8_t* mbl_rgb = nullptr;
+    uint8_t* h_mbl = nullptr;
     // Streaming mode (eppm_set_temporal / eppm_batch_set_temporal): its own allocation, made by the first compute
     // with the mode on: npairs blocks tmp_stride bytes apart, one per slot (the members below are slot 0's).  Level-L planes, unpitched: the
     // two displacement snapshots of the last compute (prev_fwd: the field nnf2flow converted, prev_bwd: the raw backward NNF), the two

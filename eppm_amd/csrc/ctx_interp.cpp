@@ -1,7 +1,8 @@
-// ctx_interp.cpp -- what reads the results of a context's (context.h) last bidirectional call: frame interpolation, the tracker, the
-// temporal filter, the stabiliser and the cut detector.
+// ctx_interp.cpp -- what reads the results of a context's (context.h) last call: frame interpolation, the synthetic shutter, the tracker,
+// the temporal filter, the stabiliser and the cut detector.
 #include "context.h"
 #include "interp.h"
+#include "mblur.h"
 
 using namespace eppm;
 
@@ -109,6 +110,106 @@ extern "C" int eppm_interpolate_device(eppm_ctx* c, int nt, const float* t, void
     for (int k0 = 0; k0 < nt; k0 += kInterpChunk)
         CHK(interp_chunk(c, 1, k0, nt - k0 < kInterpChunk ? nt - k0 : kInterpChunk, t, d_rgba, pitch));
     return EPPM_OK;
+}
+
+// ---- synthetic shutter: one raw RGBA frame and the level-0 flow defined on it.  frame 0: image 1 and the forward
+// flow, after any compute of the current images; frame 1: image 2 and the backward flow, in the window of eppm_interpolate* ----
+
+static int mbl_alloc(eppm_ctx* c)
+{
+    if (c->mbl) return EPPM_OK;
+    const size_t n = (size_t)c->h * c->w;
+    const size_t plane = (n + 63) & ~(size_t)63;
+    const size_t tplane = ((size_t)((c->h + kMBlurTile - 1) / kMBlurTile) * ((c->w + kMBlurTile - 1) / kMBlurTile) + 31) & ~(size_t)31;
+    const size_t packed = c->npairs * plane * 4, keys = c->npairs * tplane * 8, rgb = c->npairs * n * 3;
+    Carve cv;                           // (every size but the last is a multiple of 256 bytes)
+    cv.plane(&c->mbl_packed, packed);
+    cv.plane(&c->mbl_tkeys, keys);
+    cv.plane(&c->mbl_rgb, rgb);
+    CHK(cv.alloc(&c->mbl, &c->mbl_bytes, packed + keys + rgb, c->device, "motion-blur scratch"));
+    c->mbl_plane = plane;
+    c->mbl_tplane = tplane;
+    return EPPM_OK;
+}
+
+static int mblur_check(eppm_ctx* c, const char* what, const eppm_mblur_params* p, int frame, eppm_mblur_params* prm)
+{
+    if (p) *prm = *p;
+    else (void)eppm_mblur_default_params(prm);
+    if (!mblur_params_ok(prm->shutter, prm->max_radius, prm->taps))
+        return set_err(EPPM_ERR_ARG, "%s: shutter %g (0 < s <= 1), max_radius %g (1 .. 31), taps %d (1 .. 32)", what, prm->shutter, prm->max_radius, prm->taps);
+    if (frame != 0 && frame != 1) return set_err(EPPM_ERR_ARG, "%s: frame %d (0: image 1, 1: image 2)", what, frame);
+    if (c->flow_pending) return set_err(EPPM_ERR_STATE, "%s: an eppm_compute_begin is pending", what);
+    if (frame == 0 && !c->have_flow) return set_err(EPPM_ERR_STATE, "%s: frame 0 needs a compute on the current images", what);
+    if (frame == 1 && (!c->have_flow || !c->have_bwd || !c->bwd_images))
+        return set_err(EPPM_ERR_STATE, "%s: frame 1 needs a bidirectional call on the current images", what);
+    return EPPM_OK;
+}
+
+// the first npairs pairs: pack, gather into the packed RGB scratch (d_rgba NULL) or into d_rgba (pair 0)
+static int mblur_run(eppm_ctx* c, const eppm_mblur_params& prm, int frame, int npairs, void* d_rgba, size_t pitch)
+{
+    MBlurArgs a{};
+    a.img = (const uint8_t*)(frame ? c->raw2 : c->raw1); a.img_pitch = c->raw_pitch; a.img_stride = c->stride;
+    a.flow = frame ? c->bflow[0] : c->flow[0]; a.flow_stride = frame ? c->bwd_stride : c->stride;
+    a.packed = c->mbl_packed; a.tkeys = c->mbl_tkeys; a.plane = c->mbl_plane; a.tplane = c->mbl_tplane;
+    a.rgb = d_rgba ? nullptr : c->mbl_rgb;
+    a.rgba = (uint8_t*)d_rgba; a.rgba_pitch = pitch;
+    a.h = c->h; a.w = c->w;
+    a.tiles_x = (c->w + kMBlurTile - 1) / kMBlurTile; a.tiles_y = (c->h + kMBlurTile - 1) / kMBlurTile;
+    a.shutter = prm.shutter; a.max_radius = prm.max_radius; a.taps = prm.taps;
+    stage_begin(c, c->ev, "mblur_pack");
+    launch_mblur_pack(a, npairs, c->stream);
+    stage_end(c, c->ev);
+    stage_begin(c, c->ev, "mblur_gather");
+    launch_mblur_gather(a, npairs, c->stream);
+    stage_end(c, c->ev);
+    HIPCHK(hipGetLastError());
+    return EPPM_OK;
+}
+
+// host-pointer forms: the packed RGB outputs cross PCIe once (3 B/px) into the pinned copy, then into the caller's rows
+static int mblur_host(eppm_ctx* c, const char* what, const eppm_mblur_params* p, int frame, int npairs, uint8_t* const* rgb, size_t row_stride)
+{
+    eppm_mblur_params prm;
+    CHK(mblur_check(c, what, p, frame, &prm));
+    if (!rgb) return set_err(EPPM_ERR_ARG, "%s: NULL rgb", what);
+    for (int k = 0; k < npairs; k++)
+        if (!rgb[k]) return set_err(EPPM_ERR_ARG, "%s: NULL rgb[%d]", what, k);
+    if (row_stride < (size_t)c->w * 3) return set_err(EPPM_ERR_ARG, "%s: row_stride %zu < 3*w", what, row_stride);
+    HIPCHK(hipSetDevice(c->device));
+    CHK(mbl_alloc(c));
+    const size_t img = (size_t)c->h * c->w * 3, row = (size_t)c->w * 3;
+    HIPCHK(pinned_lazy(&c->h_mbl, &c->h_mbl_bytes, img * c->npairs, c->device));
+    CHK(mblur_run(c, prm, frame, npairs, nullptr, 0));
+    HIPCHK(hipMemcpyAsync(c->h_mbl, c->mbl_rgb, img * npairs, hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(hipStreamSynchronize(c->stream));
+    for (int k = 0; k < npairs; k++) copy_rows(rgb[k], row_stride, c->h_mbl + img * k, row, row, c->h);
+    return EPPM_OK;
+}
+
+extern "C" int eppm_motion_blur(eppm_ctx* c, const eppm_mblur_params* p, int frame, uint8_t* rgb, size_t row_stride)
+{
+    if (!c) return set_err(EPPM_ERR_ARG, "eppm_motion_blur: NULL ctx");
+    return mblur_host(c, "eppm_motion_blur", p, frame, 1, &rgb, row_stride);
+}
+
+extern "C" int eppm_batch_motion_blur(eppm_ctx* c, const eppm_mblur_params* p, int frame, uint8_t* const* rgb, size_t row_stride)
+{
+    if (!c) return set_err(EPPM_ERR_ARG, "eppm_batch_motion_blur: NULL ctx");
+    return mblur_host(c, "eppm_batch_motion_blur", p, frame, c->n_active, rgb, row_stride);
+}
+
+extern "C" int eppm_motion_blur_device(eppm_ctx* c, const eppm_mblur_params* p, int frame, void* d_rgba, size_t pitch)
+{
+    if (!c) return set_err(EPPM_ERR_ARG, "eppm_motion_blur_device: NULL ctx");
+    eppm_mblur_params prm;
+    CHK(mblur_check(c, "eppm_motion_blur_device", p, frame, &prm));
+    if (!d_rgba) return set_err(EPPM_ERR_ARG, "eppm_motion_blur_device: NULL d_rgba");
+    if (pitch < (size_t)c->w * 4 || (pitch & 3)) return set_err(EPPM_ERR_ARG, "eppm_motion_blur_device: bad pitch %zu", pitch);
+    HIPCHK(hipSetDevice(c->device));
+    CHK(mbl_alloc(c));
+    return mblur_run(c, prm, frame, 1, d_rgba, pitch);
 }
 
 // ---- dense point trajectories (tracker.cpp): the raw frames, the level-0 forward flow and the level-0 backward flow

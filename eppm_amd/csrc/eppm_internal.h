@@ -291,6 +291,28 @@ void launch_interp_splat(const InterpArgs& a, int npairs, hipStream_t s);      /
 void launch_interp_fill(const InterpArgs& a, int npairs, hipStream_t s);       // both fill passes
 void launch_interp_blend(const InterpArgs& a, int npairs, hipStream_t s);
 
+// ---- synthetic shutter (k_mblur.hip; the per-pixel arithmetic: mblur.h) ----
+// One launch covers npairs pairs.  Inputs of pair p lie p * (their stride) bytes past pair 0's; its packed plane p * plane words, its tile
+// keys p * tplane keys and its packed RGB output p*h*w*3 bytes past pair 0's.  Image: RGBA words, img_pitch bytes per row; flow: h*w float2,
+// unpitched.  Output: packed RGB (rgb != NULL) or RGBA words of pair 0 into rgba (rgba_pitch bytes per row).
+struct MBlurArgs {
+    const uint8_t* img;
+    size_t img_pitch, img_stride;
+    const float* flow;
+    size_t flow_stride;
+    uint32_t* packed;            // {R, G, B, mq} per pixel, unpitched
+    uint64_t* tkeys;             // the maximum key of each 32x32 tile, tiles_y rows of tiles_x
+    size_t plane, tplane;
+    uint8_t* rgb;
+    uint8_t* rgba;
+    size_t rgba_pitch;
+    int h, w, tiles_x, tiles_y;
+    float shutter, max_radius;
+    int taps;
+};
+void launch_mblur_pack(const MBlurArgs& a, int npairs, hipStream_t s);
+void launch_mblur_gather(const MBlurArgs& a, int npairs, hipStream_t s);
+
 // ---- dense point trajectories (k_track.hip; the per-point arithmetic: track.h) ----
 // The device counters of a tracker (int32 each): the live count, the next id, the frame, the last step's dropped / ended / seeded counts,
 // and what the kernels of one step hand to each other.

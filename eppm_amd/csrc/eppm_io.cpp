@@ -12,6 +12,7 @@
 #include "../../include/eppm.h"
 #include "fb_occlusion.h"
 #include "interp.h"
+#include "mblur.h"
 #include "temporal.h"
 
 static int read_ppm_header(FILE* f, int* type, int* w, int* h)
@@ -364,6 +365,57 @@ extern "C" int eppm_interpolate_host(uint8_t* rgb_out, const uint8_t* rgb1, cons
             const float ux = s >= 0 ? u[s] : 0.0f, uy = s >= 0 ? v[s] : 0.0f;
             const uint32_t p = eppm::interp_blend_pixel(x, y, ux, uy, t, h, w, img1, img2, o1, o2);
             rgb_out[i * 3] = (uint8_t)p; rgb_out[i * 3 + 1] = (uint8_t)(p >> 8); rgb_out[i * 3 + 2] = (uint8_t)(p >> 16);
+        }
+    return EPPM_OK;
+}
+
+// synthetic shutter on host planes.  The half-vector, the packed word, the key and the gather are mblur.h's, the
+// kernels' own; the maximum over the keys is a plain scan written here (tile maxima, then the up to 3x3 tiles around each tile).
+// rgb_out, rgb: h rows of w R,G,B triplets, packed.
+extern "C" int eppm_mblur_default_params(eppm_mblur_params* p)
+{
+    if (!p) return EPPM_ERR_ARG;
+    p->shutter = 0.5f;
+    p->max_radius = 16.0f;
+    p->taps = 8;
+    return EPPM_OK;
+}
+
+extern "C" int eppm_motion_blur_host(uint8_t* rgb_out, const uint8_t* rgb, const float* u, const float* v, int h, int w, const eppm_mblur_params* params)
+{
+    eppm_mblur_params prm;
+    if (params) prm = *params;
+    else (void)eppm_mblur_default_params(&prm);
+    if (!rgb_out || !rgb || !u || !v || h < 1 || w < 1 || h > 8192 || w > 8192 || (long long)h * w > (1LL << 26)) return EPPM_ERR_ARG;
+    if (!eppm::mblur_params_ok(prm.shutter, prm.max_radius, prm.taps)) return EPPM_ERR_ARG;
+    const size_t n = (size_t)h * w;
+    const int T = eppm::kMBlurTile, tx = (w + T - 1) / T, ty = (h + T - 1) / T;
+    std::vector<uint32_t> packed(n);
+    std::vector<uint64_t> tkey((size_t)tx * ty, 0);
+    for (int y = 0; y < h; y++)
+        for (int x = 0; x < w; x++) {
+            const size_t i = (size_t)y * w + x;
+            const eppm::MBlurVec hv = eppm::mblur_half_vector(u[i], v[i], prm.shutter, prm.max_radius);
+            packed[i] = eppm::mblur_pack((uint32_t)rgb[i * 3] | ((uint32_t)rgb[i * 3 + 1] << 8) | ((uint32_t)rgb[i * 3 + 2] << 16), hv.m);
+            const uint64_t k = eppm::mblur_key(hv.m, (uint32_t)i);
+            uint64_t& t = tkey[(size_t)(y / T) * tx + x / T];
+            if (k > t) t = k;
+        }
+    auto pk = [&](int x, int y) { return packed[(size_t)y * w + x]; };
+    for (int by = 0; by < ty; by++)
+        for (int bx = 0; bx < tx; bx++) {
+            uint64_t K = 0;
+            for (int qy = by > 0 ? by - 1 : 0; qy <= by + 1 && qy < ty; qy++)
+                for (int qx = bx > 0 ? bx - 1 : 0; qx <= bx + 1 && qx < tx; qx++)
+                    if (tkey[(size_t)qy * tx + qx] > K) K = tkey[(size_t)qy * tx + qx];
+            const size_t j = eppm::mblur_key_pixel(K);
+            const eppm::MBlurVec d = eppm::mblur_half_vector(u[j], v[j], prm.shutter, prm.max_radius);
+            for (int y = by * T; y < by * T + T && y < h; y++)
+                for (int x = bx * T; x < bx * T + T && x < w; x++) {
+                    const size_t i = (size_t)y * w + x;
+                    const uint32_t p = eppm::mblur_gather_pixel(x, y, d.hx, d.hy, d.m, prm.taps, h, w, pk);
+                    rgb_out[i * 3] = (uint8_t)p; rgb_out[i * 3 + 1] = (uint8_t)(p >> 8); rgb_out[i * 3 + 2] = (uint8_t)(p >> 16);
+                }
         }
     return EPPM_OK;
 }

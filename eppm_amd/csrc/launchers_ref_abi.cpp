@@ -2,6 +2,7 @@
 // sub-stage entry points the parity tests drive, all on per-device state kept here (the reference keeps the equivalent in file-scope
 // textures, __constant__ tables and g_d_rand_states: SURVEY F12).
 #include "api_internal.h"
+#include "mblur.h"
 
 using namespace eppm;
 
@@ -648,6 +649,37 @@ extern "C" int eppm_interpolate_frames(void* d_rgba_out, size_t out_pitch, const
     launch_interp_splat(a, 1, g_stream);
     launch_interp_fill(a, 1, g_stream);
     launch_interp_blend(a, 1, g_stream);
+    return finish();
+}
+// ---- the synthetic shutter on caller planes (k_mblur.hip; eppm_motion_blur_host is its host form): one frame ----
+extern "C" int eppm_motion_blur_frames(void* d_rgba_out, size_t out_pitch, const void* d_rgba, size_t in_pitch, const eppm_float2* d_flow, int h, int w,
+                                       const eppm_mblur_params* params)
+{
+    eppm_mblur_params prm;
+    if (params) prm = *params;
+    else (void)eppm_mblur_default_params(&prm);
+    if (!d_rgba_out || !d_rgba || !d_flow || h < 1 || w < 1) return set_err(EPPM_ERR_ARG, "eppm_motion_blur_frames: bad argument");
+    if (!mblur_params_ok(prm.shutter, prm.max_radius, prm.taps))
+        return set_err(EPPM_ERR_ARG, "eppm_motion_blur_frames: shutter %g (0 < s <= 1), max_radius %g (1 .. 31), taps %d (1 .. 32)", prm.shutter, prm.max_radius, prm.taps);
+    if (in_pitch < (size_t)w * 4 || out_pitch < (size_t)w * 4 || (in_pitch & 3) || (out_pitch & 3))
+        return set_err(EPPM_ERR_ARG, "eppm_motion_blur_frames: bad pitch %zu / %zu", in_pitch, out_pitch);
+    if (h > 8192 || w > 8192 || (unsigned long long)h * (unsigned long long)w > (1ULL << 26))
+        return set_err(EPPM_ERR_ARG, "eppm_motion_blur_frames: size %dx%d out of range", w, h);
+    LAUNCHER_BEGIN_INT;
+    MBlurArgs a{};
+    a.tiles_x = (w + kMBlurTile - 1) / kMBlurTile; a.tiles_y = (h + kMBlurTile - 1) / kMBlurTile;
+    a.plane = ((size_t)h * w + 63) & ~(size_t)63; a.tplane = (size_t)a.tiles_x * a.tiles_y;
+    void* scr = nullptr;
+    CHK(get_scratch(ds, a.plane * 4 + a.tplane * 8, &scr, 6));          // packed | tile keys
+    a.img = (const uint8_t*)d_rgba; a.img_pitch = in_pitch;
+    a.flow = (const float*)d_flow;
+    a.packed = (uint32_t*)scr; a.tkeys = (uint64_t*)((char*)scr + a.plane * 4);
+    a.rgba = (uint8_t*)d_rgba_out; a.rgba_pitch = out_pitch;
+    a.h = h; a.w = w;
+    a.shutter = prm.shutter; a.max_radius = prm.max_radius; a.taps = prm.taps;
+    launch_mblur_pack(a, 1, g_stream);
+    launch_mblur_gather(a, 1, g_stream);
+    HIPCHK(hipStreamSynchronize(g_stream));
     return finish();
 }
 // ---- one track step on caller planes (k_track.hip; eppm_track_step_host is its host form) ----

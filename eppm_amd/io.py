@@ -123,6 +123,24 @@ def interpolate(img1, img2, u, v, occ1, occ2, t):
     return out
 
 
+def motion_blur_host(img, u, v, shutter=0.5, max_radius=16, taps=8):
+    """(h, w, 3) uint8 frame: img as a camera with an open shutter would have recorded it, blurred along its flow (u, v)
+    (eppm_motion_blur_host; byte-identical to the kernels).  shutter: the open fraction of the frame interval,
+    max_radius: the longest half-vector in pixels, taps: taps to each side of a pixel."""
+    from .api import MBlurParams
+    a = np.ascontiguousarray(img, np.uint8)
+    u = np.ascontiguousarray(u, np.float32)
+    v = np.ascontiguousarray(v, np.float32)
+    if u.ndim != 2 or a.shape != (*u.shape, 3) or v.shape != u.shape:
+        raise ValueError("motion_blur_host: image (h, w, 3), flow (h, w)")
+    h, w = u.shape
+    p = MBlurParams(shutter=shutter, max_radius=max_radius, taps=taps)
+    out = np.empty((h, w, 3), np.uint8)
+    check(lib().eppm_motion_blur_host(out.ctypes.data_as(C.c_void_p), *[x.ctypes.data_as(C.c_void_p) for x in (a, u, v)], h, w, C.byref(p)),
+          "eppm_motion_blur_host")
+    return out
+
+
 def _track_params(params, kw):
     from .api import TrackParams
     return TrackParams(params, **kw)

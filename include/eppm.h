@@ -224,6 +224,42 @@ int  eppm_interpolate_host(uint8_t* rgb_out, const uint8_t* rgb1, const uint8_t*
                            const uint8_t* occ2, int h, int w, float t);
 
 /* ----------------------------------------------------------------------------------------
+ * synthetic shutter: motion blur of a frame along its flow (a depth-free form of the tile-dominant reconstruction
+ * filter of McGuire et al., I3D 2012).  The frame as a camera whose shutter stays open for `shutter` of the frame interval, centred on the
+ * frame, would have recorded it: every pixel averages 2*taps + 1 single-pixel taps along the longest half-vector (0.5 * shutter * flow,
+ * clamped to max_radius) of the up to 3x3 tiles of 32x32 pixels around its own; a tap counts when the pixel there sweeps over the output
+ * pixel or the output pixel's own motion sweeps over it, and every other tap counts as the output pixel itself.  A uniform motion gives
+ * the box filter along it; where the longest half-vector is below half a pixel (static regions; unknown or NaN flow counts as zero) the
+ * frame comes back byte for byte.  Every weight is 0 or 1 and every sum an integer: the kernels, the host form and both libraries give
+ * the same bytes.  The context forms read the raw frame and the level-0 flow where the context keeps them and change no plane of it:
+ *   frame 0: image 1 along the forward flow, valid after ANY compute of the current images (forward-only included) and until the next
+ *            eppm_set_images* / eppm_push_image*;
+ *   frame 1: image 2 along the backward flow, valid in the window of eppm_interpolate*.
+ * EPPM_ERR_STATE outside these windows; EPPM_ERR_ARG for parameters out of range (NaN included).  params NULL: the defaults.  The first
+ * call allocates the context's motion-blur scratch (about 7 bytes per pixel and pair, kept until eppm_destroy).  Outputs: h rows of w
+ * R,G,B triplets row_stride bytes apart (host), or RGBA words with alpha 255 (device).  Stage names: "mblur_pack", "mblur_gather".
+ * -------------------------------------------------------------------------------------- */
+typedef struct eppm_mblur_params {
+    float shutter;               /* open fraction of the frame interval, 0 < shutter <= 1 (0.5) */
+    float max_radius;            /* longest half-vector in pixels, 1 .. 31 (16) */
+    int   taps;                  /* taps to each side of the pixel, 1 .. 32 (8): the filter reads 2*taps + 1 */
+} eppm_mblur_params;
+int  eppm_mblur_default_params(eppm_mblur_params* p);
+/* pair 0; rgb: one host image.  Synchronous. */
+int  eppm_motion_blur(eppm_ctx* ctx, const eppm_mblur_params* params, int frame, uint8_t* rgb, size_t row_stride);
+/* pair 0; d_rgba: a device RGBA plane of `pitch` bytes per row.  Asynchronous on the context's stream (no host synchronisation, no
+ * allocation after the first call: usable inside stream capture). */
+int  eppm_motion_blur_device(eppm_ctx* ctx, const eppm_mblur_params* params, int frame, void* d_rgba, size_t pitch);
+/* every active pair: rgb[pair] receives pair `pair`.  Synchronous. */
+int  eppm_batch_motion_blur(eppm_ctx* ctx, const eppm_mblur_params* params, int frame, uint8_t* const* rgb, size_t row_stride);
+/* the kernels alone on caller planes, any size from 1x1 up to 8192x8192 and 2^26 pixels: RGBA input (in_pitch bytes per row, alpha
+ * ignored) and output (out_pitch), h*w float2 flow, all device pointers; on the launcher stream, synchronous */
+int  eppm_motion_blur_frames(void* d_rgba_out, size_t out_pitch, const void* d_rgba, size_t in_pitch, const eppm_float2* d_flow,
+                             int h, int w, const eppm_mblur_params* params);
+/* host form on a packed RGB image and a planar flow (no GPU needed): byte-identical to the kernels */
+int  eppm_motion_blur_host(uint8_t* rgb_out, const uint8_t* rgb, const float* u, const float* v, int h, int w, const eppm_mblur_params* params);
+
+/* ----------------------------------------------------------------------------------------
  * dense point trajectories (Sundaram, Brox & Keutzer, ECCV 2010).  Points seeded on a grid of spacing x spacing
  * cells, where the 5x5 structure tensor of R+G+B has lambda_min >= min_eig (exact integers), move by the bilinearly sampled forward flow;
  * a track ends where the forward flow is unknown (reason 1), where it leaves the frame (2), where the forward-backward check fails (3) or
@@ -508,7 +544,7 @@ int  eppm_clear_stage_times(eppm_ctx* ctx);
  * "flow_blf_bwd_L<l>", "flow_blf_bwd_final" and "fb_occlusion"; an interpolation call "interp_splat", "interp_fill" and "interp_blend"
  * (mode 1, once per group of four times); a track step "track_advance", "track_seed" and "track_compact" (mode 1; the step that seeds
  * frame 0 adds a "track_seed" before "track_advance"); a compute that starts from a temporal prior "temporal_advect" (before "patchmatch") and
- * "temporal_select" (inside it: "patchmatch" includes its time); a temporal-filter step "tfilter_step"; a stabiliser step "stab_fit" (every accumulate and solve launch) and "stab_warp"; a cut-detector step "cutdet".  Events come from a per-context pool: none is created in a steady-state step. */
+ * "temporal_select" (inside it: "patchmatch" includes its time); a temporal-filter step "tfilter_step"; a stabiliser step "stab_fit" (every accumulate and solve launch) and "stab_warp"; a cut-detector step "cutdet"; a motion-blur call "mblur_pack" and "mblur_gather".  Events come from a per-context pool: none is created in a steady-state step. */
 int  eppm_enable_stage_timing(eppm_ctx* ctx, int on);
 
 const char* eppm_last_error(void);

@@ -1,0 +1,86 @@
+// The host form of the synthetic shutter (eppm_amd/csrc/eppm_io.cpp: eppm_motion_blur_host, no GPU code) under ASan + UBSan + float-cast
+// checks: degenerate sizes, NaN, inf and huge vectors, every parameter extreme.  Exactly sized heap planes, so that a tap one pixel outside
+// the frame is a report.  Built and run by tests/test_mblur_cpu.py::test_host_form_under_sanitizers; prints "ok" when every call returned
+// what it should and the sanitizers stayed silent.
+#include <math.h>
+#include <stdio.h>
+#include <stdlib.h>
+#include <string.h>
+
+#include <vector>
+
+#include "../../include/eppm.h"
+
+static int fails = 0;
+#define CHECK(c) do { if (!(c)) { printf("FAIL line %d: %s\n", __LINE__, #c); fails++; } } while (0)
+
+static uint32_t rnd_state = 12345u;
+static uint32_t rnd() { rnd_state = rnd_state * 1664525u + 1013904223u; return rnd_state >> 8; }
+
+// field kinds: 0 zero, 1 uniform large, 2 random with NaN / inf / huge / unknown entries, 3 all NaN, 4 all inf, 5 all 3e38, 6 all 1e9 (the
+// largest known component), 7 diagonal beyond every radius with alternating signs
+static void fill(std::vector<float>& u, std::vector<float>& v, int kind)
+{
+    static const float special[] = {NAN, INFINITY, -INFINITY, 1e10f, -1e10f, 3e38f, -3e38f, 1e9f, -1e9f, 1e-30f, 1e-45f, -0.0f, 62.0f, -61.99f};
+    for (size_t i = 0; i < u.size(); i++) {
+        switch (kind) {
+        case 0: u[i] = v[i] = 0.0f; break;
+        case 1: u[i] = 57.0f; v[i] = -33.0f; break;
+        case 2:
+            u[i] = (float)(rnd() % 2001) / 10.0f - 100.0f;
+            v[i] = (float)(rnd() % 2001) / 10.0f - 100.0f;
+            if (rnd() % 5 == 0) u[i] = special[rnd() % (sizeof(special) / sizeof(special[0]))];
+            if (rnd() % 5 == 0) v[i] = special[rnd() % (sizeof(special) / sizeof(special[0]))];
+            break;
+        case 3: u[i] = v[i] = NAN; break;
+        case 4: u[i] = INFINITY; v[i] = -INFINITY; break;
+        case 5: u[i] = v[i] = 3e38f; break;
+        case 6: u[i] = 1e9f; v[i] = -1e9f; break;
+        default: u[i] = (i & 1) ? 500.0f : -500.0f; v[i] = (i & 2) ? 500.0f : -500.0f; break;
+        }
+    }
+}
+
+int main()
+{
+    static const int sizes[][2] = {{1, 1}, {1, 2}, {2, 1}, {1, 40}, {40, 1}, {3, 3}, {31, 33}, {32, 32}, {33, 65}, {70, 5}};
+    static const eppm_mblur_params prms[] = {{0.5f, 16.0f, 8}, {1.0f, 31.0f, 32}, {1.0f, 1.0f, 1}, {1e-6f, 31.0f, 32}, {1.0f, 31.0f, 1}, {0.25f, 7.5f, 3}};
+    for (const auto& sz : sizes) {
+        const int h = sz[0], w = sz[1];
+        const size_t n = (size_t)h * w;
+        for (int kind = 0; kind < 8; kind++) {
+            std::vector<float> u(n), v(n);
+            fill(u, v, kind);
+            std::vector<uint8_t> img(n * 3), out(n * 3);
+            for (auto& b : img) b = (uint8_t)rnd();
+            for (const auto& p : prms) {
+                memset(out.data(), 0xee, out.size());
+                CHECK(eppm_motion_blur_host(out.data(), img.data(), u.data(), v.data(), h, w, &p) == EPPM_OK);
+                if (kind == 0 || kind == 3 || kind == 4 || kind == 5) CHECK(memcmp(out.data(), img.data(), out.size()) == 0);
+            }
+            CHECK(eppm_motion_blur_host(out.data(), img.data(), u.data(), v.data(), h, w, NULL) == EPPM_OK);
+        }
+    }
+    // arguments
+    {
+        std::vector<float> u(4, 0.0f);
+        std::vector<uint8_t> img(12, 0), out(12);
+        eppm_mblur_params p;
+        CHECK(eppm_mblur_default_params(&p) == EPPM_OK && p.shutter == 0.5f && p.max_radius == 16.0f && p.taps == 8);
+        CHECK(eppm_mblur_default_params(NULL) == EPPM_ERR_ARG);
+        const eppm_mblur_params bad[] = {{0.0f, 16.0f, 8}, {1.5f, 16.0f, 8}, {NAN, 16.0f, 8}, {0.5f, 0.5f, 8}, {0.5f, 32.0f, 8}, {0.5f, NAN, 8},
+                                         {0.5f, INFINITY, 8}, {0.5f, 16.0f, 0}, {0.5f, 16.0f, 33}, {0.5f, 16.0f, -1}};
+        for (const auto& b : bad) CHECK(eppm_motion_blur_host(out.data(), img.data(), u.data(), u.data(), 2, 2, &b) == EPPM_ERR_ARG);
+        CHECK(eppm_motion_blur_host(NULL, img.data(), u.data(), u.data(), 2, 2, &p) == EPPM_ERR_ARG);
+        CHECK(eppm_motion_blur_host(out.data(), NULL, u.data(), u.data(), 2, 2, &p) == EPPM_ERR_ARG);
+        CHECK(eppm_motion_blur_host(out.data(), img.data(), NULL, u.data(), 2, 2, &p) == EPPM_ERR_ARG);
+        CHECK(eppm_motion_blur_host(out.data(), img.data(), u.data(), NULL, 2, 2, &p) == EPPM_ERR_ARG);
+        CHECK(eppm_motion_blur_host(out.data(), img.data(), u.data(), u.data(), 0, 2, &p) == EPPM_ERR_ARG);
+        CHECK(eppm_motion_blur_host(out.data(), img.data(), u.data(), u.data(), 2, -1, &p) == EPPM_ERR_ARG);
+        CHECK(eppm_motion_blur_host(out.data(), img.data(), u.data(), u.data(), 8193, 1, &p) == EPPM_ERR_ARG);
+        CHECK(eppm_motion_blur_host(out.data(), img.data(), u.data(), u.data(), 8192 * 2, 8192, &p) == EPPM_ERR_ARG);
+    }
+    if (fails) return 1;
+    printf("ok\n");
+    return 0;
+}

@@ -17,6 +17,7 @@
 #   tfilter     the temporal filter: tools/tfilter_times.py on both libraries -> tfilter_times_{exact,tol}.json
 #   stab        the stabiliser: tools/stab_times.py on both libraries -> stab_times_{exact,tol}.json
 #   cutdet      the cut detector: tools/cutdet_times.py --shares on both libraries -> cutdet_times_{exact,tol}.json
+#   mblur       the synthetic shutter: tools/mblur_times.py on both libraries -> mblur_times_{exact,tol}.json
 #   round       everything profiles/ of a round comes from (TAG=r04_x; PMC_ONLY=1, SKIP_TESTS=1)
 set -o pipefail
 R=${GRAFT_REPO_ROOT:-$(cd "$(dirname "$0")/.." && pwd)}
@@ -133,6 +134,11 @@ cutdet)
     timeout -k 10 ${CUTDET_TIMEOUT:-300} python tools/cutdet_times.py --lib $l --shares ${CUTDET_ARGS} > $O/cutdet_times_$l.json || exit 1
     cut -c1-400 $O/cutdet_times_$l.json
   done ;;
+mblur)
+  cd $R; for l in exact tol; do
+    timeout -k 10 ${MBLUR_TIMEOUT:-300} python tools/mblur_times.py --lib $l ${MBLUR_ARGS} > $O/mblur_times_$l.json || exit 1
+    cut -c1-400 $O/mblur_times_$l.json
+  done ;;
 inflight)
   cd $R; for S in ${INFLIGHT:-1 2 3 4 6}; do
     python bench.py --steps 96 --warmup 8 --inflight $S $QUIET $BENCH_ARGS 2>/dev/null | python -c "import json,sys; d=json.loads(sys.stdin.read()); print('inflight $S pairs in flight',d['config']['pairs_in_flight_per_gpu'],'ms/step %.3f'%d['ms_per_step'],'Mvec/s %.1f'%d['value'])"
@@ -190,5 +196,5 @@ LIST
   fi
   ls $OT ;;
 *)
-  sed -n 2,19p "$0"; exit 1 ;;
+  sed -n 2,20p "$0"; exit 1 ;;
 esac

@@ -23,6 +23,10 @@
 //   --occlusion f.pgm ... and image 1's occlusion mask as a P5 PGM: 0 consistent, 255 inconsistent, 128 leaves the frame, 64 unknown
 //   --interpolate T f.ppm  (repeatable) implies the bidirectional call; after the timed window, write the frame at time T in [0, 1]
 //                     between image 1 and image 2 (interpolate_frame) as a P6 PPM
+//   --motion-blur S f.ppm  after the timed window, write image 1 as a camera whose shutter stays open for S of the frame interval
+//                     (0 < S <= 1) would have recorded it: blurred along the forward flow (eppm_motion_blur), as
+//                     a P6 PPM.  --blur-radius R (1 .. 31, default 16): the longest half-vector in pixels; --blur-taps N (1 .. 32,
+//                     default 8): taps to each side of a pixel
 //
 //   runeppm [options] --sequence f0.ppm f1.ppm f2.ppm ... --out-prefix P [--temporal 0|1]
 //
@@ -44,6 +48,10 @@
 //                     filter and the camera path.  P_cuts.txt gets one line per pair: its index, the verdict and the record's integers
 //                     (n, c1[0..3], c2[0..3], n_tracked, sad).  --cut-lost N (0 .. 1000, default 530) sets the share of lost pixels,
 //                     in permille, above which a pair is a cut, and implies --auto-cut.
+//                     --motion-blur S (no file name here): every frame with the synthetic shutter is written to
+//                     P_mb_0000.ppm, P_mb_0001.ppm ...: frame k - 1 blurred along the forward flow of the pair k - 1 -> k; the last pair
+//                     runs the bidirectional call and gives the clip's last frame too, blurred along its backward flow.  --blur-radius
+//                     and --blur-taps as above.
 #include <atomic>
 #include <chrono>
 #include <cstdio>
@@ -86,6 +94,10 @@ struct Options {
     float smooth = 0.9f;                                    // --smooth
     bool auto_cut = false;                                  // --auto-cut
     int cut_lost = 530;                                     // --cut-lost
+    bool mblur = false;                                     // --motion-blur
+    const char* mblur_file = nullptr;                       // ... its file (the two-image form)
+    eppm_mblur_params mb = {0.5f, 16.0f, 8};                // --motion-blur S, --blur-radius, --blur-taps
+    bool mb_set = false;                                    // --blur-radius or --blur-taps given
 };
 
 static unsigned hash32(unsigned x)
@@ -134,11 +146,12 @@ static int usage()
 {
     fprintf(stderr, "usage: runeppm [--size WxH] [--seed N] [--levels N] [--patch-r N] [--iters N] [--propagation M] [--stop-level N]\n"
                     "               [--pin] [--pairs P] [--gpus G] [--batch B] [--gt file.flo] [--out file.flo] [--backward file.flo]\n"
-                    "               [--occlusion file.pgm] [--interpolate T file.ppm]... [img1.ppm img2.ppm [out.flo]]\n"
+                    "               [--occlusion file.pgm] [--interpolate T file.ppm]... [--motion-blur S file.ppm]\n"
+                    "               [--blur-radius R] [--blur-taps N] [img1.ppm img2.ppm [out.flo]]\n"
                     "       runeppm [--seed N] [--levels N] [--patch-r N] [--iters N] [--propagation M] [--stop-level N]\n"
                     "               --sequence f0.ppm f1.ppm [f2.ppm ...] --out-prefix P [--temporal 0|1]\n"
                     "               [--denoise] [--denoise-thresh T] [--denoise-frames N] [--stabilize] [--smooth S]\n"
-                    "               [--auto-cut] [--cut-lost N]\n");
+                    "               [--auto-cut] [--cut-lost N] [--motion-blur S] [--blur-radius R] [--blur-taps N]\n");
     return 2;
 }
 
@@ -175,7 +188,8 @@ static int run_sequence(const Options& o)
     FILE* cuts = nullptr;
     auto fail = [&](const char* what) { fprintf(stderr, "%s: %s\n", what, eppm_last_error()); if (cuts) fclose(cuts); eppm_cutdet_destroy(det); eppm_stab_destroy(stab); eppm_tfilter_destroy(flt); if (ctx) eppm_destroy(ctx); return 1; };
     if (eppm_create(&ctx, h, w, 0, &prm) != EPPM_OK) return fail("eppm_create");
-    std::vector<unsigned char> dn, st;
+    std::vector<unsigned char> dn, st, mb;
+    if (o.mblur) mb.resize((size_t)h * w * 3);
     char name[4096];
     if (o.stabilize) {
         eppm_stab_params sp;
@@ -231,7 +245,8 @@ static int run_sequence(const Options& o)
         const auto t0 = std::chrono::steady_clock::now();
         if (k == 1) { if (eppm_set_images(ctx, img[0].data(), img[1].data(), (size_t)w * 3) != EPPM_OK) return fail("eppm_set_images"); }
         else if (eppm_push_image(ctx, cur.data(), (size_t)w * 3) != EPPM_OK) return fail("eppm_push_image");
-        if (!o.denoise && !o.stabilize && !o.auto_cut) { if (eppm_compute(ctx, u.data(), v.data()) != EPPM_OK) return fail("eppm_compute"); }
+        const bool last = k + 1 == o.seq.size();
+        if (!o.denoise && !o.stabilize && !o.auto_cut && !(o.mblur && last)) { if (eppm_compute(ctx, u.data(), v.data()) != EPPM_OK) return fail("eppm_compute"); }
         else {
             if (eppm_compute_bidirectional(ctx, u.data(), v.data(), nullptr, nullptr, nullptr, nullptr) != EPPM_OK) return fail("eppm_compute_bidirectional");
             uint8_t cut = 0;
@@ -263,6 +278,11 @@ static int run_sequence(const Options& o)
         if (o.stabilize) {
             snprintf(name, sizeof name, "%s_st_%04zu.ppm", o.prefix, k);
             if (!write_ppm(name, st.data(), h, w)) { fprintf(stderr, "cannot write %s\n", name); if (cuts) fclose(cuts); eppm_cutdet_destroy(det); eppm_stab_destroy(stab); eppm_tfilter_destroy(flt); eppm_destroy(ctx); return 1; }
+        }
+        for (int fr = 0; o.mblur && fr <= (last ? 1 : 0); fr++) {       // frame k - 1 from the forward flow; the clip's last frame from the backward flow
+            if (eppm_motion_blur(ctx, &o.mb, fr, mb.data(), (size_t)w * 3) != EPPM_OK) return fail("eppm_motion_blur");
+            snprintf(name, sizeof name, "%s_mb_%04zu.ppm", o.prefix, k - 1 + fr);
+            if (!write_ppm(name, mb.data(), h, w)) { fprintf(stderr, "cannot write %s\n", name); if (cuts) fclose(cuts); eppm_cutdet_destroy(det); eppm_stab_destroy(stab); eppm_tfilter_destroy(flt); eppm_destroy(ctx); return 1; }
         }
     }
     printf("%zu pairs, %.3f ms per pair\n", o.seq.size() - 1, total / (double)(o.seq.size() - 1));
@@ -312,6 +332,22 @@ int main(int argc, char** argv)
             if (!end || *end || !(t >= 0.0f && t <= 1.0f)) return usage();
             o.interp.push_back({t, argv[++i]});
         }
+        else if (!strcmp(a, "--motion-blur")) {       // the value, then (two-image form) the file: resolved once the form is known
+            if (i + 1 >= argc) return usage();
+            char* end = nullptr;
+            o.mb.shutter = strtof(argv[++i], &end);
+            if (!end || end == argv[i] || *end || !(o.mb.shutter > 0.0f && o.mb.shutter <= 1.0f)) return usage();
+            o.mblur = true;
+            if (i + 1 < argc && !(argv[i + 1][0] == '-' && argv[i + 1][1] == '-')) o.mblur_file = argv[++i];
+        }
+        else if (!strcmp(a, "--blur-radius")) {
+            if (i + 1 >= argc) return usage();
+            char* end = nullptr;
+            o.mb.max_radius = strtof(argv[++i], &end);
+            if (!end || end == argv[i] || *end || !(o.mb.max_radius >= 1.0f && o.mb.max_radius <= 31.0f)) return usage();
+            o.mb_set = true;
+        }
+        else if (!strcmp(a, "--blur-taps")) { if (!val(&v) || v < 1 || v > 32) return usage(); o.mb.taps = (int)v; o.mb_set = true; }
         else if (!strcmp(a, "--sequence")) { while (i + 1 < argc && !(argv[i + 1][0] == '-' && argv[i + 1][1] == '-')) o.seq.push_back(argv[++i]); if (o.seq.empty()) return usage(); }
         else if (!strcmp(a, "--out-prefix")) { if (i + 1 >= argc) return usage(); o.prefix = argv[++i]; }
         else if (!strcmp(a, "--denoise")) o.denoise = true;
@@ -339,6 +375,7 @@ int main(int argc, char** argv)
     }
     if (!o.seq.empty() || o.prefix) {
         if (o.seq.size() < 2 || !o.prefix || !pos.empty()) return usage();
+        if (o.mblur_file || (o.mb_set && !o.mblur)) return usage();       // a clip's blurred frames are named by the prefix
         // the options of the two-image form that a clip has no meaning for are refused, not ignored
         const Options d;
         bool pin = false;
@@ -348,6 +385,7 @@ int main(int argc, char** argv)
         return run_sequence(o);
     }
     if (o.denoise || o.stabilize || o.auto_cut) return usage();     // the filter, the stabiliser and the cut detector walk a clip
+    if ((o.mblur && !o.mblur_file) || (o.mb_set && !o.mblur)) return usage();
     if (pos.size() == 1 || pos.size() > 3) return usage();
     if (pos.size() >= 2) { o.f1 = pos[0]; o.f2 = pos[1]; }
     if (pos.size() == 3) o.fo = pos[2];
@@ -380,6 +418,8 @@ int main(int argc, char** argv)
     const bool bidir = o.fb || o.focc || !o.interp.empty();
     std::vector<Array3<unsigned char>> frames;      // --interpolate outputs
     for (size_t k = 0; k < o.interp.size(); k++) frames.emplace_back(h, w, 3);
+    std::vector<unsigned char> blurred;             // --motion-blur output
+    if (o.mblur) blurred.resize((size_t)h * w * 3);
     std::vector<float> bu, bv;                      // backward flow and image 1's occlusion mask (--backward / --occlusion)
     std::vector<unsigned char> occ;
     std::vector<float*> bur, bvr;
@@ -405,6 +445,10 @@ int main(int argc, char** argv)
         printf("GPU: %.3f s (init + %s)\n", std::chrono::duration<double>(t1 - t0).count(), bidir ? "compute_flow_bidirectional" : "compute_flow");
         for (size_t k = 0; k < o.interp.size(); k++)
             if (!eppm.interpolate_frame(o.interp[k].first, frames[k].p())) return 1;
+        if (o.mblur && eppm_motion_blur(eppm.handle(), &o.mb, 0, blurred.data(), (size_t)w * 3) != EPPM_OK) {
+            fprintf(stderr, "eppm_motion_blur: %s\n", eppm_last_error());
+            return 1;
+        }
     }
 
     // steady state: contexts created once, pairs streamed through set_data + compute_flow
@@ -513,5 +557,6 @@ int main(int argc, char** argv)
         if (f && fclose(f) != 0) ok = false;
         if (!ok) { fprintf(stderr, "cannot write %s\n", o.interp[k].second); return 1; }
     }
+    if (o.mblur && !write_ppm(o.mblur_file, blurred.data(), h, w)) { fprintf(stderr, "cannot write %s\n", o.mblur_file); return 1; }
     return 0;
 }
