@@ -54,6 +54,10 @@ class CMBlurParams(C.Structure):
     _fields_ = [("shutter", C.c_float), ("max_radius", C.c_float), ("taps", C.c_int)]
 
 
+class CCMapParams(C.Structure):
+    _fields_ = [("thresh", C.c_float), ("tear", C.c_float), ("use_occ", C.c_int)]
+
+
 class CTrackCounts(C.Structure):
     _fields_ = [("live", C.c_int), ("ended", C.c_int), ("seeded", C.c_int), ("dropped", C.c_int), ("frame", C.c_int), ("next_id", C.c_int)]
 
@@ -102,6 +106,9 @@ SYMBOLS = [
     "eppm_cutdet_step_frames", "eppm_cutdet_get", "eppm_cutdet_cuts", "eppm_cutdet_host",
     "eppm_mblur_default_params", "eppm_motion_blur", "eppm_motion_blur_device", "eppm_batch_motion_blur", "eppm_motion_blur_frames",
     "eppm_motion_blur_host",
+    "eppm_cmap_default_params", "eppm_cmap_create", "eppm_cmap_create_size", "eppm_cmap_destroy", "eppm_cmap_reset", "eppm_cmap_step",
+    "eppm_cmap_step_frames", "eppm_cmap_get_state", "eppm_cmap_set_state", "eppm_cmap_set_layer", "eppm_cmap_render", "eppm_cmap_render_device",
+    "eppm_cmap_age", "eppm_cmap_step_host", "eppm_cmap_render_host",
 ]
 
 

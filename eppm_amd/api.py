@@ -3,7 +3,8 @@ import ctypes as C
 
 import numpy as np
 
-from ._lib import CCutParams, CCutStats, CGMotionModel, CMBlurParams, CParams, CStabParams, CTFilterParams, CTrackCounts, CTrackParams, EppmError, check, lib
+from .io import cmap_seed
+from ._lib import CCMapParams, CCutParams, CCutStats, CGMotionModel, CMBlurParams, CParams, CStabParams, CTFilterParams, CTrackCounts, CTrackParams, EppmError, check, lib
 
 uchar4 = np.dtype([("x", "u1"), ("y", "u1"), ("z", "u1"), ("w", "u1")])
 short2 = np.dtype([("x", "i2"), ("y", "i2")])
@@ -379,6 +380,118 @@ class CutDetector:
             pass
 
 
+def CMapParams(**kw):
+    """eppm_cmap_params with the defaults of DESIGN.md section 19 (thresh 90, tear 2, use_occ 1)."""
+    p = CCMapParams()
+    check(lib().eppm_cmap_default_params(C.byref(p)), "eppm_cmap_default_params")
+    for k, v in kw.items():
+        if not hasattr(p, k):
+            raise TypeError(f"unknown correspondence-map parameter {k}")
+        setattr(p, k, v)
+    return p
+
+
+class CorrespondenceMap:
+    """Dense correspondence maps to an anchor frame over the pairs of a context (eppm_cmap_*).  ctx: an EPPM or an
+    EPPMBatch; one slot per pair of it.  Every step() moves the active pairs' slots from image 1 to image 2 of the context's last
+    compute_flow_bidirectional*: map(slot)[y, x] is then the position in the slot's anchor frame that pixel (x, y) of image 2 shows, and
+    render(slot) the slot's layer composited over image 2 through that map.  The object is its own allocation on the context's device;
+    close() frees it.  params: CMapParams' thresh, tear and use_occ."""
+
+    def __init__(self, ctx, size=None, slots=1, device=0, **params):
+        """ctx None: a map without a context, for step_frames on caller planes (eppm_cmap_create_size): size = (h, w), `slots` slots."""
+        self._f = C.c_void_p()
+        self.ctx = ctx
+        self.params = CMapParams(**params)
+        if ctx is None:
+            self.h, self.w, self.nslots = int(size[0]), int(size[1]), int(slots)
+            check(lib().eppm_cmap_create_size(self.h, self.w, self.nslots, int(device), C.byref(self.params), C.byref(self._f)),
+                  "eppm_cmap_create_size")
+            return
+        check(lib().eppm_cmap_create(ctx._ctx, C.byref(self.params), C.byref(self._f)), "eppm_cmap_create")
+        self.h, self.w = ctx.h, ctx.w
+        self.nslots = int(lib().eppm_batch_size(ctx._ctx))
+
+    def step(self, cut=None, ctx=None):
+        """One step of every active pair's slot, and its render; cut: None, or one flag per active pair (true: the pair's image 2 is the
+        first frame of another clip and becomes the slot's anchor).  Asynchronous on the context's stream."""
+        c = self.ctx if ctx is None else ctx
+        flags = None if cut is None else (C.c_uint8 * len(cut))(*[int(bool(x)) for x in cut])
+        if flags is not None and len(cut) != getattr(c, "n", 1):
+            raise EppmError("CorrespondenceMap.step: one cut flag per active pair")
+        check(lib().eppm_cmap_step(self._f, c._ctx, flags), "eppm_cmap_step")
+
+    def step_frames(self, slot, d_rgba1, d_rgba2, pitch, d_flow_bwd, d_occ2, cut=False):
+        """eppm_cmap_step_frames: one step of one slot on caller device planes (addresses), synchronous."""
+        check(lib().eppm_cmap_step_frames(self._f, int(slot), C.c_void_p(d_rgba1), C.c_void_p(d_rgba2), C.c_size_t(pitch),
+                                          C.c_void_p(d_flow_bwd), C.c_void_p(d_occ2), int(bool(cut))), "eppm_cmap_step_frames")
+
+    def map(self, slot=0):
+        """(h, w, 2) float32 (sx, sy): the slot's map; a lost pixel holds (1e10, 1e10)."""
+        xy = np.empty((self.h, self.w, 2), np.float32)
+        check(lib().eppm_cmap_get_state(self._f, int(slot), xy.ctypes.data_as(C.c_void_p)), "eppm_cmap_get_state")
+        return xy
+
+    state = map
+
+    def known(self, slot=0):
+        """(h, w) bool: the pixels of the current frame whose position in the anchor frame is known."""
+        m = self.map(slot)
+        with np.errstate(invalid="ignore"):
+            return (np.abs(m[..., 0]) <= np.float32(1e9)) & (np.abs(m[..., 1]) <= np.float32(1e9))
+
+    def set_state(self, slot, xy, anchor):
+        """Load a map and its (h, w, 3) uint8 anchor frame, which also becomes the slot's current frame (eppm_cmap_set_state)."""
+        xy = np.ascontiguousarray(xy, np.float32)
+        a = np.ascontiguousarray(anchor, np.uint8)
+        if xy.shape != (self.h, self.w, 2) or a.shape != (self.h, self.w, 3):
+            raise EppmError(f"CorrespondenceMap.set_state: a ({self.h},{self.w},2) float32 map and a ({self.h},{self.w},3) uint8 anchor")
+        check(lib().eppm_cmap_set_state(self._f, int(slot), xy.ctypes.data_as(C.c_void_p), a.ctypes.data_as(C.c_void_p), C.c_size_t(self.w * 3)),
+              "eppm_cmap_set_state")
+
+    def set_layer(self, rgba, slot=0):
+        """The slot's layer: (h, w, 4) uint8 RGBA with straight alpha, in the anchor frame's geometry; None: the default layer (the anchor
+        frame with alpha 255)."""
+        if rgba is None:
+            check(lib().eppm_cmap_set_layer(self._f, int(slot), None, C.c_size_t(0)), "eppm_cmap_set_layer")
+            return
+        a = np.ascontiguousarray(rgba, np.uint8)
+        if a.shape != (self.h, self.w, 4):
+            raise EppmError(f"CorrespondenceMap.set_layer: the layer must be ({self.h},{self.w},4) uint8")
+        check(lib().eppm_cmap_set_layer(self._f, int(slot), a.ctypes.data_as(C.c_void_p), C.c_size_t(self.w * 4)), "eppm_cmap_set_layer")
+
+    def render(self, slot=0):
+        """(h, w, 3) uint8: the slot's layer composited over its current frame through its map."""
+        rgb = np.empty((self.h, self.w, 3), np.uint8)
+        check(lib().eppm_cmap_render(self._f, int(slot), rgb.ctypes.data_as(C.c_void_p), C.c_size_t(self.w * 3)), "eppm_cmap_render")
+        return rgb
+
+    def render_device(self, slot, d_rgba, pitch):
+        check(lib().eppm_cmap_render_device(self._f, int(slot), C.c_void_p(d_rgba), C.c_size_t(pitch)), "eppm_cmap_render_device")
+
+    def age(self, slot=0):
+        """Steps since the slot's anchor frame."""
+        a = int(lib().eppm_cmap_age(self._f, int(slot)))
+        if a < 0:
+            raise EppmError(f"eppm_cmap_age: {lib().eppm_last_error().decode()}")
+        return a
+
+    def reset(self, slot=None):
+        """The slot is empty again (slot=None: every slot): its next step anchors on its pair's image 1."""
+        check(lib().eppm_cmap_reset(self._f, -1 if slot is None else int(slot)), "eppm_cmap_reset")
+
+    def close(self):
+        if self._f:
+            lib().eppm_cmap_destroy(self._f)
+            self._f = C.c_void_p()
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
 def _level(level):
     """a stop level as a plain int; anything that is not an integer is refused before the library is touched"""
     if isinstance(level, (bool, np.bool_)) or not isinstance(level, (int, np.integer)):
@@ -655,6 +768,126 @@ def denoise_sequences(clips, slots=8, params=None, thresh=40.0, n_max=8, tempora
             det.close()
         if flt is not None:
             flt.close()
+        if e is not None:
+            e.close()
+    return out
+
+
+def _cmap_split(kw):
+    """the keyword arguments of propagate_layer(s): CMapParams' go to the map, CutDetector's to the detector"""
+    cm = {k: kw.pop(k) for k in ("thresh", "tear", "use_occ") if k in kw}
+    cut = {k: kw.pop(k) for k in ("lost_permille", "residual_max") if k in kw}
+    if kw:
+        raise TypeError(f"unknown parameter {sorted(kw)[0]}")
+    return cm, cut
+
+
+def propagate_layer(frames, layer_rgba, auto_cut=False, stop_level=None, maps=False, **params):
+    """A layer painted on a clip's first frame follows the surface through the clip (CorrespondenceMap): frames are
+    (h, w, 3) uint8, layer_rgba is (h, w, 4) uint8 with straight alpha in frame 0's geometry.  One streaming context -- set_data, then
+    push_frame --, one bidirectional call on the device and one map step per pair; every output frame samples the layer ONCE, at the
+    composed map.  Returns len(frames) frames; frame 0 is the layer composited through the seed map.  Memory does not grow with the clip.
+    params: CMapParams' thresh, tear and use_occ, and with auto_cut=True CutDetector's lost_permille and residual_max: a detector looks at
+    every pair before the map does, a frame that starts another shot re-anchors the map on itself, and from then on the layer is not drawn
+    (it belongs to the first shot): those frames are the input frames.  stop_level: the flow's draft mode (None: full quality).
+    maps=True: returns (frames, maps), one (h, w, 2) float32 map per frame."""
+    cm_params, cut_params = _cmap_split(dict(params))
+    if cut_params and not auto_cut:
+        raise TypeError("propagate_layer: lost_permille and residual_max need auto_cut=True")
+    frames = [np.ascontiguousarray(f, np.uint8) for f in frames]
+    if len(frames) < 2:
+        raise EppmError("propagate_layer: at least two frames")
+    h, w, _ = frames[0].shape
+    e = EPPM()
+    cm = det = None
+    out, mp = [], []
+    drawn = True
+    try:
+        e.init(h, w)
+        e.set_temporal(True)
+        if stop_level is not None:
+            e.set_stop_level(_level(stop_level))
+        cm = CorrespondenceMap(e, **cm_params)
+        if auto_cut:
+            det = CutDetector(e, **cut_params)
+        cm.set_state(0, cmap_seed(h, w), frames[0])
+        cm.set_layer(layer_rgba, 0)
+        out.append(cm.render(0))
+        if maps:
+            mp.append(cm.map(0))
+        for k in range(len(frames) - 1):
+            if k == 0:
+                e.set_data(frames[0], frames[1])
+            else:
+                e.push_frame(frames[k + 1])
+            e.compute_flow_bidirectional_device()
+            cuts = _auto_cut_step(e, det) if auto_cut else None
+            cm.step(cuts)
+            if cuts is not None and cuts[0]:
+                drawn = False
+            out.append(cm.render(0) if drawn else frames[k + 1].copy())
+            if maps:
+                mp.append(cm.map(0))
+    finally:
+        if det is not None:
+            det.close()
+        if cm is not None:
+            cm.close()
+        e.close()
+    return (out, mp) if maps else out
+
+
+def propagate_layers(clips, layers, slots=8, auto_cut=False, stop_level=None, **params):
+    """propagate_layer for many clips at once: clips of one frame size and of any lengths (two frames at least), one layer per clip, through
+    ONE batch context of min(slots, len(clips)) slots and one CorrespondenceMap, on flow_sequences' schedule.  A slot that takes the next
+    clip of the queue passes `cut` for that step and takes that clip's layer: its output is the layer over that clip's frame 0.  Returns one
+    list of frames per clip, each what propagate_layer(clip, layer) returns."""
+    cm_params, cut_params = _cmap_split(dict(params))
+    if cut_params and not auto_cut:
+        raise TypeError("propagate_layers: lost_permille and residual_max need auto_cut=True")
+    clips = [[np.ascontiguousarray(f, np.uint8) for f in clip] for clip in clips]
+    layers = list(layers)
+    if len(layers) != len(clips):
+        raise EppmError("propagate_layers: one layer per clip")
+    plan = _sequence_plan([len(c) for c in clips], slots)
+    h, w, _ = clips[0][0].shape
+    out = [[] for _ in clips]
+    e = cm = det = None
+    try:
+        for t, step in enumerate(plan):
+            if t == 0:
+                e = EPPMBatch(h, w, len(step), params=None)
+                e.set_temporal(True)
+                if stop_level is not None:
+                    e.set_stop_level(_level(stop_level))
+                cm = CorrespondenceMap(e, **cm_params)
+                if auto_cut:
+                    det = CutDetector(e, **cut_params)
+                drawn = [True] * len(step)
+                for slot, (c, _, _, _) in enumerate(step):
+                    cm.set_state(slot, cmap_seed(h, w), clips[c][0])
+                    cm.set_layer(layers[c], slot)
+                    out[c].append(cm.render(slot))
+                e.set_data([(clips[c][0], clips[c][1]) for c, _, _, _ in step])
+            else:
+                e.push_frames([clips[c][f] for c, f, _, _ in step], [cut for _, _, cut, _ in step])
+            e.compute_flow_bidirectional_device()
+            found = _auto_cut_step(e, det) if auto_cut else [False] * len(step)
+            cm.step([cut or bool(fc) for (_, _, cut, _), fc in zip(step, found)])
+            for slot, ((c, f, new_clip, keep), fc) in enumerate(zip(step, found)):
+                if new_clip:                     # the slot's map was re-anchored on frame 0 of clip c: its layer from here on
+                    cm.set_layer(layers[c], slot)
+                    drawn[slot] = True
+                    out[c].append(cm.render(slot))
+                elif keep:
+                    if fc:
+                        drawn[slot] = False
+                    out[c].append(cm.render(slot) if drawn[slot] else clips[c][f].copy())
+    finally:
+        if det is not None:
+            det.close()
+        if cm is not None:
+            cm.close()
         if e is not None:
             e.close()
     return out

@@ -172,6 +172,12 @@ EPPM_HIDDEN int ctx_tfilter_inputs(eppm_ctx* c, int h, int w, int device, int ns
 EPPM_HIDDEN int tfilter_step_on(eppm_tfilter* f, eppm::TFilterArgs& in, int slot0, const uint8_t* cut, hipStream_t s, eppm_ctx* timing);
 EPPM_HIDDEN int tfilter_device(const eppm_tfilter* f, int* h, int* w, int* nslots);
 
+// ---- a correspondence map (cmap.cpp) reads what a temporal filter reads of a context (ctx_tfilter_inputs) ----
+// the launcher stream of the context-less launchers (launchers_ref_abi.cpp) runs eppm_cmap_step_frames through this (cmap.cpp):
+// slots slot0 .. slot0 + in.n - 1 from the input members of in, then their render; cut: NULL or one flag per pair
+EPPM_HIDDEN int cmap_step_on(eppm_cmap* f, eppm::CMapArgs& in, int slot0, const uint8_t* cut, hipStream_t s, eppm_ctx* timing);
+EPPM_HIDDEN int cmap_device(const eppm_cmap* f, int* h, int* w, int* nslots);
+
 // ---- what a stabiliser (stabilizer.cpp) reads of a context (ctx_interp.cpp) ----
 // the input members of *in (image 2, the level-0 forward flow, occ1) for every active pair, under ctx_tfilter_inputs' rules
 EPPM_HIDDEN int ctx_stab_inputs(eppm_ctx* c, int h, int w, int device, int nslots, const char* what, eppm::StabArgs* in, hipStream_t* s);

@@ -425,6 +425,31 @@ struct CutArgs {
 void launch_cutdet_accumulate(const CutArgs& a, hipStream_t s);
 void launch_cutdet_finish(const CutArgs& a, hipStream_t s);
 
+// ---- dense correspondence map to an anchor frame (k_cmap.hip; the arithmetic: cmap.h) ----
+// One step covers n pairs: pair k's inputs (TFilterArgs' planes) lie k * (their stride) bytes past pair 0's and feed slot slot0 + k, whose
+// block lies (slot0 + k) * slot_stride bytes past `mem`: map 0 | map 1 (h*w float2 each) | anchor | frame | layer | out (h*w RGBA words
+// each, from off_anchor on).  The per-slot bits travel in the kernel arguments as TFilterArgs' do: cur (which map
+// is the previous one; the step writes the other), empty (the slot has no state: the previous map is the seed, the anchor image 1, which
+// the step also stores), cut (image 2 starts another clip: seed, and image 2 becomes the anchor) and deflayer (the render reads the
+// anchor with alpha 255 in place of the layer plane).  The render launch covers slots slot0 .. slot0 + n - 1 and reads nothing of a pair.
+struct CMapArgs {
+    const uint8_t* img1;
+    const uint8_t* img2;
+    size_t img_pitch, img_stride;
+    const float* bwd;
+    size_t bwd_stride;
+    const uint8_t* occ2;
+    size_t occ_stride;
+    char* mem;
+    size_t slot_stride, off_anchor;
+    int h, w, n, slot0;
+    float thresh, tear;
+    int use_occ;
+    uint32_t cur[kTemporalMaxSlots / 32], empty[kTemporalMaxSlots / 32], cut[kTemporalMaxSlots / 32], deflayer[kTemporalMaxSlots / 32];
+};
+void launch_cmap_step(const CMapArgs& a, hipStream_t s);
+void launch_cmap_render(const CMapArgs& a, hipStream_t s);
+
 // ---- flow colour coding (k_color.hip) ----
 // rgba: h*w packed R | G<<8 | B<<16 (alpha 0); flow: h*w float2
 void launch_flow_to_color(uint32_t* rgba, const float* flow, int h, int w, float max_disp_x, float max_disp_y, hipStream_t s, Batch bt = kOnePair);

@@ -765,6 +765,28 @@ extern "C" int eppm_cutdet_step_frames(eppm_cutdet* f, int slot, const void* d_r
     HIPCHK(hipStreamSynchronize(g_stream));
     return finish();
 }
+// ---- one correspondence-map step of one slot on caller planes (k_cmap.hip; eppm_cmap_step_host is its host form) ----
+extern "C" int eppm_cmap_step_frames(eppm_cmap* f, int slot, const void* d_rgba1, const void* d_rgba2, size_t pitch, const eppm_float2* d_flow_bwd,
+                                     const uint8_t* d_occ2, int cut)
+{
+    if (!f || !d_rgba1 || !d_rgba2 || !d_flow_bwd || !d_occ2) return set_err(EPPM_ERR_ARG, "eppm_cmap_step_frames: NULL argument");
+    int h, w, nslots;
+    const int device = cmap_device(f, &h, &w, &nslots);
+    if (slot < 0 || slot >= nslots) return set_err(EPPM_ERR_ARG, "eppm_cmap_step_frames: slot %d, the map has %d", slot, nslots);
+    if (pitch < (size_t)w * 4 || (pitch & 3)) return set_err(EPPM_ERR_ARG, "eppm_cmap_step_frames: bad pitch %zu", pitch);
+    std::lock_guard<std::mutex> lk(g_mu);
+    int d = 0;
+    HIPCHK(hipGetDevice(&d));
+    if (d != device) return set_err(EPPM_ERR_ARG, "eppm_cmap_step_frames: the map lives on device %d, the current device is %d", device, d);
+    CMapArgs in{};
+    in.img1 = (const uint8_t*)d_rgba1; in.img2 = (const uint8_t*)d_rgba2; in.img_pitch = pitch;
+    in.bwd = (const float*)d_flow_bwd; in.occ2 = d_occ2;
+    in.n = 1;
+    const uint8_t c = cut != 0;
+    CHK(cmap_step_on(f, in, slot, &c, g_stream, nullptr));
+    HIPCHK(hipStreamSynchronize(g_stream));
+    return finish();
+}
 // the C++-linkage symbol the reference's driver declares at :64 (defaults 100,100 there; the live call passes 20,20)
 void bao_cuda_convert_flow_to_colorshow(uchar4* rgbflow, float2* flow_vec, int h, int w, float max_disp_x, float max_disp_y)
 {

@@ -226,6 +226,56 @@ def tfilter_step_host(acc, img2, bu, bv, occ2, thresh=40.0, n_max=8, cut=False):
     return out, rgb
 
 
+def cmap_seed(h, w):
+    """(h, w, 2) float32: the seed of a correspondence map, map(x, y) = (x, y)."""
+    m = np.empty((int(h), int(w), 2), np.float32)
+    m[..., 0] = np.arange(int(w), dtype=np.float32)[None, :]
+    m[..., 1] = np.arange(int(h), dtype=np.float32)[:, None]
+    return m
+
+
+def cmap_step_host(cmap, anchor, img2, bu, bv, occ2, thresh=90.0, tear=2.0, use_occ=1, cut=False):
+    """One step of a correspondence map on the host (eppm_cmap_step_host; bit-identical to the kernel).  cmap: the
+    (h, w, 2) float32 map of image 1, or None for the seed (what an empty slot reads); anchor: the (h, w, 3) uint8 anchor frame (image 1
+    for an empty slot); img2: the new frame; (bu, bv): the backward flow image 2 -> image 1; occ2: the occlusion mask of image 2's pixels;
+    cut: img2 starts another clip (the result is the seed, and img2 is the caller's next anchor).  Returns the new (h, w, 2) map."""
+    from ._lib import CCMapParams
+    p = CCMapParams(float(thresh), float(tear), int(use_occ))
+    a = np.ascontiguousarray(anchor, np.uint8)
+    b = np.ascontiguousarray(img2, np.uint8)
+    bu = np.ascontiguousarray(bu, np.float32)
+    bv = np.ascontiguousarray(bv, np.float32)
+    o = np.ascontiguousarray(occ2, np.uint8)
+    h, w = bu.shape
+    m = None if cmap is None else np.ascontiguousarray(cmap, np.float32)
+    if (m is not None and m.shape != (h, w, 2)) or a.shape != (h, w, 3) or b.shape != (h, w, 3) or bv.shape != (h, w) or o.shape != (h, w):
+        raise ValueError("cmap_step_host: map (h, w, 2), images (h, w, 3), flow and mask (h, w)")
+    out = np.empty((h, w, 2), np.float32)
+    check(lib().eppm_cmap_step_host(C.byref(p), out.ctypes.data_as(C.c_void_p), None if m is None else m.ctypes.data_as(C.c_void_p),
+                                    *[x.ctypes.data_as(C.c_void_p) for x in (a, b, bu, bv, o)], h, w, int(bool(cut))), "eppm_cmap_step_host")
+    return out
+
+
+def cmap_render_host(cmap, cur, layer=None, anchor=None):
+    """The render of a correspondence map on the host (eppm_cmap_render_host; bit-identical to the kernel): the (h, w, 4) uint8 RGBA layer
+    (straight alpha, in the anchor frame's geometry) sampled at the (h, w, 2) map and composited over the current (h, w, 3) frame.
+    layer=None: the default layer, the (h, w, 3) anchor frame with alpha 255.  Returns (h, w, 3) uint8."""
+    m = np.ascontiguousarray(cmap, np.float32)
+    c = np.ascontiguousarray(cur, np.uint8)
+    h, w, _ = c.shape
+    lay = None if layer is None else np.ascontiguousarray(layer, np.uint8)
+    anc = None if anchor is None else np.ascontiguousarray(anchor, np.uint8)
+    if lay is None and anc is None:
+        raise ValueError("cmap_render_host: a layer or an anchor frame")
+    if m.shape != (h, w, 2) or c.shape != (h, w, 3) or (lay is not None and lay.shape != (h, w, 4)) or (anc is not None and anc.shape != (h, w, 3)):
+        raise ValueError("cmap_render_host: map (h, w, 2), frame and anchor (h, w, 3), layer (h, w, 4)")
+    out = np.empty((h, w, 3), np.uint8)
+    check(lib().eppm_cmap_render_host(out.ctypes.data_as(C.c_void_p), m.ctypes.data_as(C.c_void_p), c.ctypes.data_as(C.c_void_p),
+                                      None if lay is None else lay.ctypes.data_as(C.c_void_p),
+                                      None if anc is None else anc.ctypes.data_as(C.c_void_p), h, w), "eppm_cmap_render_host")
+    return out
+
+
 def _stab_params(tau, iters, smooth):
     from ._lib import CStabParams
     return CStabParams(float(tau), int(iters), float(smooth))

@@ -534,6 +534,72 @@ int  eppm_cutdet_cuts(eppm_cutdet* det, int n, uint8_t* cut);
 int  eppm_cutdet_host(const eppm_cut_params* p, const uint8_t* rgb1, const uint8_t* rgb2, const float* bu, const float* bv,
                       const uint8_t* occ1, const uint8_t* occ2, int h, int w, eppm_cut_stats* stats);
 
+/* ----------------------------------------------------------------------------------------
+ * dense correspondence maps to an anchor frame and layer propagation.  A map holds one slot per pair of its
+ * context: per pixel of the current frame the position (sx, sy) in the slot's anchor frame that the pixel shows (h*w float2, row-major;
+ * a lost pixel holds (1e10, 1e10), and any value with a component above 1e9 in magnitude or NaN reads as lost), the anchor frame, the
+ * current frame and a layer (RGBA, straight alpha; by default the anchor frame with alpha 255).  One step moves every covered slot from
+ * image 1 to image 2 of its pair by composing the map with the backward flow: a pixel whose backward vector is known, stays inside the
+ * frame and (use_occ) is not occluded samples the previous map at its source -- bilinearly where the four taps are known and within
+ * `tear` of the nearest tap in both components, otherwise the nearest tap translated --, and is kept if the anchor frame sampled
+ * bilinearly at the result is within thresh of the new pixel (sum of the three absolute differences); every other pixel is lost.  The
+ * render composites the layer, sampled once at the map, over the current frame; lost pixels show the current frame.  The kernels equal
+ * eppm_cmap_step_host and eppm_cmap_render_host bit for bit, in both libraries.  A map is a separate allocation on its context's device
+ * (32 bytes per pixel and slot: two maps, the anchor, the frame, the layer and the output), made by eppm_cmap_create and freed by
+ * eppm_cmap_destroy; a context that never creates one allocates and launches exactly what it did without.  A slot that has never been
+ * stepped, or after eppm_cmap_reset, is empty: its first step reads the identity as the previous map and image 1 as the anchor, which it
+ * also stores.  Frames of at most 8192 x 8192 and 2^26 pixels.  Stage names: "cmap_step", "cmap_render".
+ * -------------------------------------------------------------------------------------- */
+typedef struct eppm_cmap_params {
+    float thresh;                /* largest |dR| + |dG| + |dB| between the new pixel and the anchor at the composed position that keeps it (90); finite, >= 0 */
+    float tear;                  /* largest difference between a tap of the map and the nearest tap that still blends the four (2); finite, >= 0 */
+    int   use_occ;               /* 1: a pixel with occ2 != 0 is lost (1); 0: the mask is not read into the decision */
+} eppm_cmap_params;
+typedef struct eppm_cmap eppm_cmap;
+
+int  eppm_cmap_default_params(eppm_cmap_params* p);
+/* p NULL: the defaults.  One slot per pair of ctx (eppm_batch_size), on its device; every slot empty. */
+int  eppm_cmap_create(eppm_ctx* ctx, const eppm_cmap_params* p, eppm_cmap** out);
+/* a map without a context, for eppm_cmap_step_frames on caller planes: nslots slots of h x w pixels (any size from 1 x 1) on `device` */
+int  eppm_cmap_create_size(int h, int w, int nslots, int device, const eppm_cmap_params* p, eppm_cmap** out);
+int  eppm_cmap_destroy(eppm_cmap* cm);                    /* NULL is fine */
+int  eppm_cmap_reset(eppm_cmap* cm, int slot);            /* the slot is empty again; slot < 0: every slot */
+/* One step of slots 0 .. active pairs - 1 on the pairs of ctx's last eppm_compute_bidirectional* (the raw frames, the level-0 backward flow
+ * and occ2): valid in the window of eppm_interpolate* (EPPM_ERR_STATE outside it); EPPM_ERR_ARG for a context of other dimensions, another
+ * device or more active pairs than the map has slots.  cut: NULL, or one flag per active pair; non-zero: image 2 of that pair is the
+ * first frame of another clip: the slot's map becomes the identity and image 2 its anchor.  A slot the step does not cover keeps its
+ * state.  Two launches (the step, and the render of the covered slots), asynchronous on the context's stream: no copy, no allocation, no
+ * host synchronisation. */
+int  eppm_cmap_step(eppm_cmap* cm, eppm_ctx* ctx, const uint8_t* cut);
+/* the same step of one slot on caller device planes of the map's size (RGBA images of `pitch` bytes per row, h*w float2 backward flow,
+ * h*w mask bytes); on the launcher stream, synchronous.  d_rgba1 is read only if the slot is empty.  Whatever the planes hold, nothing
+ * outside them is read. */
+int  eppm_cmap_step_frames(eppm_cmap* cm, int slot, const void* d_rgba1, const void* d_rgba2, size_t pitch, const eppm_float2* d_flow_bwd,
+                           const uint8_t* d_occ2, int cut);
+/* synchronous.  The slot's map, h*w*2 floats (EPPM_ERR_STATE on an empty slot) / load a map and its anchor frame (packed RGB), which also
+ * becomes the slot's current frame: the slot is no longer empty and its age is 0 */
+int  eppm_cmap_get_state(eppm_cmap* cm, int slot, float* xy);
+int  eppm_cmap_set_state(eppm_cmap* cm, int slot, const float* xy, const uint8_t* anchor_rgb, size_t row_stride);
+/* synchronous.  The slot's layer: h rows of w RGBA quadruples, straight alpha, in the anchor frame's geometry; NULL: the default layer
+ * again (the anchor frame with alpha 255, followed across re-anchoring).  Allowed on an empty slot. */
+int  eppm_cmap_set_layer(eppm_cmap* cm, int slot, const uint8_t* rgba, size_t row_stride);
+/* the slot's layer composited over its current frame through its map (EPPM_ERR_STATE on a slot that has never been stepped or loaded):
+ * packed RGB to the host, synchronous ... */
+int  eppm_cmap_render(eppm_cmap* cm, int slot, uint8_t* rgb, size_t row_stride);
+/* ... or RGBA words (alpha 255) into a device plane, asynchronous on the stream of the map's last step.  A step renders the slots it
+ * covers; these calls launch the render again only if the layer or the state was set since. */
+int  eppm_cmap_render_device(eppm_cmap* cm, int slot, void* d_rgba, size_t pitch);
+/* steps since the slot's anchor frame (0 after a cut step or eppm_cmap_set_state); -1 and an error for an empty slot or a bad argument */
+int  eppm_cmap_age(eppm_cmap* cm, int slot);
+/* host forms (no GPU needed).  One step from map_in (image 1's map; NULL: the identity, as an empty slot reads it) to map_out, which must
+ * not be map_in; anchor_rgb: the anchor frame (image 1 for an empty slot), rgb2: image 2, (bu, bv): the backward flow, occ2: the mask.
+ * After a cut step the caller's anchor is rgb2.  The render of a map over the current frame rgb_cur: layer_rgba, or NULL for the default
+ * layer made of anchor_rgb (which is read in that case only). */
+int  eppm_cmap_step_host(const eppm_cmap_params* p, float* map_out, const float* map_in, const uint8_t* anchor_rgb, const uint8_t* rgb2,
+                         const float* bu, const float* bv, const uint8_t* occ2, int h, int w, int cut);
+int  eppm_cmap_render_host(uint8_t* rgb_out, const float* map, const uint8_t* rgb_cur, const uint8_t* layer_rgba, const uint8_t* anchor_rgb,
+                           int h, int w);
+
 /* Per-stage device times in ms (hipEvent pairs on the context's stream), one entry per stage per
  * call since the last eppm_clear_stage_times (names repeat across calls; prepare entries first).
  * names[i] points to static strings.  Returns the number of entries written (<= max). */
@@ -544,7 +610,7 @@ int  eppm_clear_stage_times(eppm_ctx* ctx);
  * "flow_blf_bwd_L<l>", "flow_blf_bwd_final" and "fb_occlusion"; an interpolation call "interp_splat", "interp_fill" and "interp_blend"
  * (mode 1, once per group of four times); a track step "track_advance", "track_seed" and "track_compact" (mode 1; the step that seeds
  * frame 0 adds a "track_seed" before "track_advance"); a compute that starts from a temporal prior "temporal_advect" (before "patchmatch") and
- * "temporal_select" (inside it: "patchmatch" includes its time); a temporal-filter step "tfilter_step"; a stabiliser step "stab_fit" (every accumulate and solve launch) and "stab_warp"; a cut-detector step "cutdet"; a motion-blur call "mblur_pack" and "mblur_gather".  Events come from a per-context pool: none is created in a steady-state step. */
+ * "temporal_select" (inside it: "patchmatch" includes its time); a temporal-filter step "tfilter_step"; a stabiliser step "stab_fit" (every accumulate and solve launch) and "stab_warp"; a cut-detector step "cutdet"; a motion-blur call "mblur_pack" and "mblur_gather"; a correspondence-map step "cmap_step" and "cmap_render".  Events come from a per-context pool: none is created in a steady-state step. */
 int  eppm_enable_stage_timing(eppm_ctx* ctx, int on);
 
 const char* eppm_last_error(void);

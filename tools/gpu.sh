@@ -18,6 +18,7 @@
 #   stab        the stabiliser: tools/stab_times.py on both libraries -> stab_times_{exact,tol}.json
 #   cutdet      the cut detector: tools/cutdet_times.py --shares on both libraries -> cutdet_times_{exact,tol}.json
 #   mblur       the synthetic shutter: tools/mblur_times.py on both libraries -> mblur_times_{exact,tol}.json
+#   cmap        the correspondence map: tools/cmap_times.py on both libraries -> cmap_times_{exact,tol}.json
 #   round       everything profiles/ of a round comes from (TAG=r04_x; PMC_ONLY=1, SKIP_TESTS=1)
 set -o pipefail
 R=${GRAFT_REPO_ROOT:-$(cd "$(dirname "$0")/.." && pwd)}
@@ -138,6 +139,11 @@ mblur)
   cd $R; for l in exact tol; do
     timeout -k 10 ${MBLUR_TIMEOUT:-300} python tools/mblur_times.py --lib $l ${MBLUR_ARGS} > $O/mblur_times_$l.json || exit 1
     cut -c1-400 $O/mblur_times_$l.json
+  done ;;
+cmap)
+  cd $R; for l in exact tol; do
+    timeout -k 10 ${CMAP_TIMEOUT:-300} python tools/cmap_times.py --lib $l ${CMAP_ARGS} > $O/cmap_times_$l.json || exit 1
+    cut -c1-400 $O/cmap_times_$l.json
   done ;;
 inflight)
   cd $R; for S in ${INFLIGHT:-1 2 3 4 6}; do

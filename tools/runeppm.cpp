@@ -52,6 +52,11 @@
 //                     P_mb_0000.ppm, P_mb_0001.ppm ...: frame k - 1 blurred along the forward flow of the pair k - 1 -> k; the last pair
 //                     runs the bidirectional call and gives the clip's last frame too, blurred along its backward flow.  --blur-radius
 //                     and --blur-taps as above.
+//                     --propagate layer.ppm alpha.ppm: a layer painted on the first frame follows the surface through the clip
+//                     (DESIGN.md section 19): every pair runs the bidirectional call followed by one step of a correspondence map to
+//                     the first frame, and the layer (alpha: the first channel of the second file), sampled once at the map, is
+//                     composited over every frame: P_pl_0000.ppm (through the identity), P_pl_0001.ppm ...  With --auto-cut a frame
+//                     that starts another shot re-anchors the map, and from there on the frames are written as they are.
 #include <atomic>
 #include <chrono>
 #include <cstdio>
@@ -98,6 +103,7 @@ struct Options {
     const char* mblur_file = nullptr;                       // ... its file (the two-image form)
     eppm_mblur_params mb = {0.5f, 16.0f, 8};                // --motion-blur S, --blur-radius, --blur-taps
     bool mb_set = false;                                    // --blur-radius or --blur-taps given
+    const char *pl_layer = nullptr, *pl_alpha = nullptr;    // --propagate layer.ppm alpha.ppm
 };
 
 static unsigned hash32(unsigned x)
@@ -151,7 +157,8 @@ static int usage()
                     "       runeppm [--seed N] [--levels N] [--patch-r N] [--iters N] [--propagation M] [--stop-level N]\n"
                     "               --sequence f0.ppm f1.ppm [f2.ppm ...] --out-prefix P [--temporal 0|1]\n"
                     "               [--denoise] [--denoise-thresh T] [--denoise-frames N] [--stabilize] [--smooth S]\n"
-                    "               [--auto-cut] [--cut-lost N] [--motion-blur S] [--blur-radius R] [--blur-taps N]\n");
+                    "               [--auto-cut] [--cut-lost N] [--motion-blur S] [--blur-radius R] [--blur-taps N]\n"
+                    "               [--propagate layer.ppm alpha.ppm]\n");
     return 2;
 }
 
@@ -185,10 +192,12 @@ static int run_sequence(const Options& o)
     eppm_tfilter* flt = nullptr;
     eppm_stab* stab = nullptr;
     eppm_cutdet* det = nullptr;
+    eppm_cmap* cm = nullptr;
     FILE* cuts = nullptr;
-    auto fail = [&](const char* what) { fprintf(stderr, "%s: %s\n", what, eppm_last_error()); if (cuts) fclose(cuts); eppm_cutdet_destroy(det); eppm_stab_destroy(stab); eppm_tfilter_destroy(flt); if (ctx) eppm_destroy(ctx); return 1; };
+    auto fail = [&](const char* what) { fprintf(stderr, "%s: %s\n", what, eppm_last_error()); if (cuts) fclose(cuts); eppm_cmap_destroy(cm); eppm_cutdet_destroy(det); eppm_stab_destroy(stab); eppm_tfilter_destroy(flt); if (ctx) eppm_destroy(ctx); return 1; };
     if (eppm_create(&ctx, h, w, 0, &prm) != EPPM_OK) return fail("eppm_create");
-    std::vector<unsigned char> dn, st, mb;
+    std::vector<unsigned char> dn, st, mb, pl, layer;
+    bool pl_drawn = true;               // --propagate: no cut so far
     if (o.mblur) mb.resize((size_t)h * w * 3);
     char name[4096];
     if (o.stabilize) {
@@ -203,19 +212,38 @@ static int run_sequence(const Options& o)
         if (eppm_tfilter_create(ctx, &tp, &flt) != EPPM_OK) return fail("eppm_tfilter_create");
         dn.resize((size_t)h * w * 3);
     }
+    if (o.pl_layer) {
+        int hl = 0, wl = 0;
+        std::vector<unsigned char> rgb((size_t)h * w * 3), alpha((size_t)h * w * 3);
+        for (int j = 0; j < 2; j++) {
+            const char* f = j ? o.pl_alpha : o.pl_layer;
+            if (eppm_ppm_size(f, &hl, &wl) != EPPM_OK || hl != h || wl != w || eppm_load_ppm(f, (j ? alpha : rgb).data(), h, w, &nch) != EPPM_OK) {
+                fprintf(stderr, "cannot read %s (or its size differs from the first frame's)\n", f);
+                eppm_stab_destroy(stab); eppm_tfilter_destroy(flt); eppm_destroy(ctx);
+                return 1;
+            }
+        }
+        layer.resize((size_t)h * w * 4);
+        for (size_t i = 0; i < (size_t)h * w; i++) {
+            for (int c = 0; c < 3; c++) layer[4 * i + c] = rgb[3 * i + c];
+            layer[4 * i + 3] = alpha[3 * i];
+        }
+        if (eppm_cmap_create(ctx, nullptr, &cm) != EPPM_OK) return fail("eppm_cmap_create");
+        pl.resize((size_t)h * w * 3);
+    }
     if (o.auto_cut) {
         eppm_cut_params cp;
         eppm_cutdet_default_params(&cp);
         cp.lost_permille = o.cut_lost;
         if (eppm_cutdet_create(ctx, &cp, &det) != EPPM_OK) return fail("eppm_cutdet_create");
         snprintf(name, sizeof name, "%s_cuts.txt", o.prefix);
-        if (!(cuts = fopen(name, "w"))) { fprintf(stderr, "cannot write %s\n", name); eppm_cutdet_destroy(det); eppm_stab_destroy(stab); eppm_tfilter_destroy(flt); eppm_destroy(ctx); return 1; }
+        if (!(cuts = fopen(name, "w"))) { fprintf(stderr, "cannot write %s\n", name); eppm_cmap_destroy(cm); eppm_cutdet_destroy(det); eppm_stab_destroy(stab); eppm_tfilter_destroy(flt); eppm_destroy(ctx); return 1; }
     }
     if (eppm_set_temporal(ctx, o.temporal) != EPPM_OK) return fail("eppm_set_temporal");
     if (eppm_set_stop_level(ctx, o.stop_level) != EPPM_OK) {
         fprintf(stderr, "--stop-level: %s\n", eppm_last_error());
         if (cuts) fclose(cuts);
-        eppm_cutdet_destroy(det); eppm_stab_destroy(stab); eppm_tfilter_destroy(flt); eppm_destroy(ctx);
+        eppm_cmap_destroy(cm); eppm_cutdet_destroy(det); eppm_stab_destroy(stab); eppm_tfilter_destroy(flt); eppm_destroy(ctx);
         return usage();
     }
     double total = 0;
@@ -225,7 +253,7 @@ static int run_sequence(const Options& o)
         if (eppm_ppm_size(o.seq[k], &hk, &wk) != EPPM_OK || hk != h || wk != w || eppm_load_ppm(o.seq[k], cur.data(), h, w, &nch) != EPPM_OK) {
             fprintf(stderr, "cannot read %s (or its size differs from the first frame's)\n", o.seq[k]);
             if (cuts) fclose(cuts);
-            eppm_cutdet_destroy(det);
+            eppm_cmap_destroy(cm); eppm_cutdet_destroy(det);
             eppm_stab_destroy(stab);
             eppm_tfilter_destroy(flt);
             eppm_destroy(ctx);
@@ -234,11 +262,21 @@ static int run_sequence(const Options& o)
         if (k == 0) {
             if (o.denoise) {
                 snprintf(name, sizeof name, "%s_dn_0000.ppm", o.prefix);
-                if (!write_ppm(name, cur.data(), h, w)) { fprintf(stderr, "cannot write %s\n", name); if (cuts) fclose(cuts); eppm_cutdet_destroy(det); eppm_stab_destroy(stab); eppm_tfilter_destroy(flt); eppm_destroy(ctx); return 1; }
+                if (!write_ppm(name, cur.data(), h, w)) { fprintf(stderr, "cannot write %s\n", name); if (cuts) fclose(cuts); eppm_cmap_destroy(cm); eppm_cutdet_destroy(det); eppm_stab_destroy(stab); eppm_tfilter_destroy(flt); eppm_destroy(ctx); return 1; }
+            }
+            if (cm) {                  // the layer through the identity map: the first frame is its own anchor
+                std::vector<float> seed((size_t)h * w * 2);
+                for (int y = 0; y < h; y++)
+                    for (int x = 0; x < w; x++) { seed[((size_t)y * w + x) * 2] = (float)x; seed[((size_t)y * w + x) * 2 + 1] = (float)y; }
+                if (eppm_cmap_set_state(cm, 0, seed.data(), cur.data(), (size_t)w * 3) != EPPM_OK) return fail("eppm_cmap_set_state");
+                if (eppm_cmap_set_layer(cm, 0, layer.data(), (size_t)w * 4) != EPPM_OK) return fail("eppm_cmap_set_layer");
+                if (eppm_cmap_render(cm, 0, pl.data(), (size_t)w * 3) != EPPM_OK) return fail("eppm_cmap_render");
+                snprintf(name, sizeof name, "%s_pl_0000.ppm", o.prefix);
+                if (!write_ppm(name, pl.data(), h, w)) { fprintf(stderr, "cannot write %s\n", name); return fail("write"); }
             }
             if (o.stabilize) {
                 snprintf(name, sizeof name, "%s_st_0000.ppm", o.prefix);
-                if (!write_ppm(name, cur.data(), h, w)) { fprintf(stderr, "cannot write %s\n", name); if (cuts) fclose(cuts); eppm_cutdet_destroy(det); eppm_stab_destroy(stab); eppm_tfilter_destroy(flt); eppm_destroy(ctx); return 1; }
+                if (!write_ppm(name, cur.data(), h, w)) { fprintf(stderr, "cannot write %s\n", name); if (cuts) fclose(cuts); eppm_cmap_destroy(cm); eppm_cutdet_destroy(det); eppm_stab_destroy(stab); eppm_tfilter_destroy(flt); eppm_destroy(ctx); return 1; }
             }
             continue;
         }
@@ -246,7 +284,7 @@ static int run_sequence(const Options& o)
         if (k == 1) { if (eppm_set_images(ctx, img[0].data(), img[1].data(), (size_t)w * 3) != EPPM_OK) return fail("eppm_set_images"); }
         else if (eppm_push_image(ctx, cur.data(), (size_t)w * 3) != EPPM_OK) return fail("eppm_push_image");
         const bool last = k + 1 == o.seq.size();
-        if (!o.denoise && !o.stabilize && !o.auto_cut && !(o.mblur && last)) { if (eppm_compute(ctx, u.data(), v.data()) != EPPM_OK) return fail("eppm_compute"); }
+        if (!o.denoise && !o.stabilize && !o.auto_cut && !cm && !(o.mblur && last)) { if (eppm_compute(ctx, u.data(), v.data()) != EPPM_OK) return fail("eppm_compute"); }
         else {
             if (eppm_compute_bidirectional(ctx, u.data(), v.data(), nullptr, nullptr, nullptr, nullptr) != EPPM_OK) return fail("eppm_compute_bidirectional");
             uint8_t cut = 0;
@@ -263,31 +301,41 @@ static int run_sequence(const Options& o)
             }
             if (o.denoise && eppm_tfilter_step(flt, ctx, o.auto_cut ? &cut : nullptr) != EPPM_OK) return fail("eppm_tfilter_step");
             if (o.stabilize && eppm_stab_step(stab, ctx, o.auto_cut ? &cut : nullptr) != EPPM_OK) return fail("eppm_stab_step");
+            if (cm) {
+                if (eppm_cmap_step(cm, ctx, o.auto_cut ? &cut : nullptr) != EPPM_OK) return fail("eppm_cmap_step");
+                if (cut) pl_drawn = false;              // the layer belongs to the first shot
+                if (pl_drawn) { if (eppm_cmap_render(cm, 0, pl.data(), (size_t)w * 3) != EPPM_OK) return fail("eppm_cmap_render"); }
+                else pl = cur;
+            }
             if (o.denoise && eppm_tfilter_get(flt, 0, dn.data(), (size_t)w * 3) != EPPM_OK) return fail("eppm_tfilter_get");
             if (o.stabilize && eppm_stab_get(stab, 0, st.data(), (size_t)w * 3) != EPPM_OK) return fail("eppm_stab_get");
         }
         const double ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
         total += ms;
         snprintf(name, sizeof name, "%s_%04zu.flo", o.prefix, k);
-        if (eppm_save_flo(name, u.data(), v.data(), h, w) != EPPM_OK) { fprintf(stderr, "cannot write %s\n", name); if (cuts) fclose(cuts); eppm_cutdet_destroy(det); eppm_stab_destroy(stab); eppm_tfilter_destroy(flt); eppm_destroy(ctx); return 1; }
+        if (eppm_save_flo(name, u.data(), v.data(), h, w) != EPPM_OK) { fprintf(stderr, "cannot write %s\n", name); if (cuts) fclose(cuts); eppm_cmap_destroy(cm); eppm_cutdet_destroy(det); eppm_stab_destroy(stab); eppm_tfilter_destroy(flt); eppm_destroy(ctx); return 1; }
         printf("pair %zu: %.3f ms%s -> %s\n", k, ms, (o.temporal && k > 1) ? " (seeded)" : "", name);
         if (o.denoise) {
             snprintf(name, sizeof name, "%s_dn_%04zu.ppm", o.prefix, k);
-            if (!write_ppm(name, dn.data(), h, w)) { fprintf(stderr, "cannot write %s\n", name); if (cuts) fclose(cuts); eppm_cutdet_destroy(det); eppm_stab_destroy(stab); eppm_tfilter_destroy(flt); eppm_destroy(ctx); return 1; }
+            if (!write_ppm(name, dn.data(), h, w)) { fprintf(stderr, "cannot write %s\n", name); if (cuts) fclose(cuts); eppm_cmap_destroy(cm); eppm_cutdet_destroy(det); eppm_stab_destroy(stab); eppm_tfilter_destroy(flt); eppm_destroy(ctx); return 1; }
         }
         if (o.stabilize) {
             snprintf(name, sizeof name, "%s_st_%04zu.ppm", o.prefix, k);
-            if (!write_ppm(name, st.data(), h, w)) { fprintf(stderr, "cannot write %s\n", name); if (cuts) fclose(cuts); eppm_cutdet_destroy(det); eppm_stab_destroy(stab); eppm_tfilter_destroy(flt); eppm_destroy(ctx); return 1; }
+            if (!write_ppm(name, st.data(), h, w)) { fprintf(stderr, "cannot write %s\n", name); if (cuts) fclose(cuts); eppm_cmap_destroy(cm); eppm_cutdet_destroy(det); eppm_stab_destroy(stab); eppm_tfilter_destroy(flt); eppm_destroy(ctx); return 1; }
+        }
+        if (cm) {
+            snprintf(name, sizeof name, "%s_pl_%04zu.ppm", o.prefix, k);
+            if (!write_ppm(name, pl.data(), h, w)) { fprintf(stderr, "cannot write %s\n", name); return fail("write"); }
         }
         for (int fr = 0; o.mblur && fr <= (last ? 1 : 0); fr++) {       // frame k - 1 from the forward flow; the clip's last frame from the backward flow
             if (eppm_motion_blur(ctx, &o.mb, fr, mb.data(), (size_t)w * 3) != EPPM_OK) return fail("eppm_motion_blur");
             snprintf(name, sizeof name, "%s_mb_%04zu.ppm", o.prefix, k - 1 + fr);
-            if (!write_ppm(name, mb.data(), h, w)) { fprintf(stderr, "cannot write %s\n", name); if (cuts) fclose(cuts); eppm_cutdet_destroy(det); eppm_stab_destroy(stab); eppm_tfilter_destroy(flt); eppm_destroy(ctx); return 1; }
+            if (!write_ppm(name, mb.data(), h, w)) { fprintf(stderr, "cannot write %s\n", name); if (cuts) fclose(cuts); eppm_cmap_destroy(cm); eppm_cutdet_destroy(det); eppm_stab_destroy(stab); eppm_tfilter_destroy(flt); eppm_destroy(ctx); return 1; }
         }
     }
     printf("%zu pairs, %.3f ms per pair\n", o.seq.size() - 1, total / (double)(o.seq.size() - 1));
     const bool cuts_ok = !cuts || fclose(cuts) == 0;
-    eppm_cutdet_destroy(det);
+    eppm_cmap_destroy(cm); eppm_cutdet_destroy(det);
     eppm_stab_destroy(stab);
     eppm_tfilter_destroy(flt);
     eppm_destroy(ctx);
@@ -369,6 +417,7 @@ int main(int argc, char** argv)
         }
         else if (!strcmp(a, "--auto-cut")) o.auto_cut = true;
         else if (!strcmp(a, "--cut-lost")) { if (!val(&v) || v < 0 || v > 1000) return usage(); o.cut_lost = (int)v; o.auto_cut = true; }
+        else if (!strcmp(a, "--propagate")) { if (i + 2 >= argc) return usage(); o.pl_layer = argv[++i]; o.pl_alpha = argv[++i]; }
         else if (!strcmp(a, "--temporal")) { if (!val(&v) || (v != 0 && v != 1)) return usage(); o.temporal = (int)v; }
         else if (a[0] == '-' && a[1] == '-') return usage();
         else pos.push_back(a);
@@ -384,7 +433,7 @@ int main(int argc, char** argv)
             return usage();
         return run_sequence(o);
     }
-    if (o.denoise || o.stabilize || o.auto_cut) return usage();     // the filter, the stabiliser and the cut detector walk a clip
+    if (o.denoise || o.stabilize || o.auto_cut || o.pl_layer) return usage();     // the filter, the stabiliser, the cut detector and the map walk a clip
     if ((o.mblur && !o.mblur_file) || (o.mb_set && !o.mblur)) return usage();
     if (pos.size() == 1 || pos.size() > 3) return usage();
     if (pos.size() >= 2) { o.f1 = pos[0]; o.f2 = pos[1]; }
