@@ -58,6 +58,26 @@ class CCMapParams(C.Structure):
     _fields_ = [("thresh", C.c_float), ("tear", C.c_float), ("use_occ", C.c_int)]
 
 
+class CObjectsParams(C.Structure):
+    _fields_ = [("tau", C.c_float), ("iters", C.c_int), ("connectivity", C.c_int), ("min_area", C.c_int), ("max_objects", C.c_int),
+                ("min_overlap", C.c_int)]
+
+
+class CObject(C.Structure):
+    _fields_ = [("id", C.c_int32), ("age", C.c_int32), ("area", C.c_int32), ("x0", C.c_int32), ("y0", C.c_int32), ("x1", C.c_int32),
+                ("y1", C.c_int32), ("n_flow", C.c_int32), ("sum_x", C.c_int64), ("sum_y", C.c_int64), ("sum_qu", C.c_int64), ("sum_qv", C.c_int64)]
+
+    def as_dict(self):
+        return {k: int(getattr(self, k)) for k, _ in self._fields_}
+
+
+class CObjectsCounts(C.Structure):
+    _fields_ = [("n", C.c_int32), ("n_found", C.c_int32), ("n_components", C.c_int32), ("next_id", C.c_int32)]
+
+    def as_dict(self):
+        return {k: int(getattr(self, k)) for k, _ in self._fields_}
+
+
 class CTrackCounts(C.Structure):
     _fields_ = [("live", C.c_int), ("ended", C.c_int), ("seeded", C.c_int), ("dropped", C.c_int), ("frame", C.c_int), ("next_id", C.c_int)]
 
@@ -109,6 +129,9 @@ SYMBOLS = [
     "eppm_cmap_default_params", "eppm_cmap_create", "eppm_cmap_create_size", "eppm_cmap_destroy", "eppm_cmap_reset", "eppm_cmap_step",
     "eppm_cmap_step_frames", "eppm_cmap_get_state", "eppm_cmap_set_state", "eppm_cmap_set_layer", "eppm_cmap_render", "eppm_cmap_render_device",
     "eppm_cmap_age", "eppm_cmap_step_host", "eppm_cmap_render_host",
+    "eppm_objects_default_params", "eppm_objects_create", "eppm_objects_create_size", "eppm_objects_destroy", "eppm_objects_reset",
+    "eppm_objects_step", "eppm_objects_step_frames", "eppm_objects_get", "eppm_objects_get_labels", "eppm_objects_get_state",
+    "eppm_objects_set_state", "eppm_objects_label_host", "eppm_objects_carry_host", "eppm_objects_assign_host",
 ]
 
 

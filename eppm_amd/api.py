@@ -3,8 +3,8 @@ import ctypes as C
 
 import numpy as np
 
-from .io import cmap_seed
-from ._lib import CCMapParams, CCutParams, CCutStats, CGMotionModel, CMBlurParams, CParams, CStabParams, CTFilterParams, CTrackCounts, CTrackParams, EppmError, check, lib
+from .io import cmap_seed, object_record
+from ._lib import CObject, CObjectsCounts, CObjectsParams, CCMapParams, CCutParams, CCutStats, CGMotionModel, CMBlurParams, CParams, CStabParams, CTFilterParams, CTrackCounts, CTrackParams, EppmError, check, lib
 
 uchar4 = np.dtype([("x", "u1"), ("y", "u1"), ("z", "u1"), ("w", "u1")])
 short2 = np.dtype([("x", "i2"), ("y", "i2")])
@@ -492,6 +492,122 @@ class CorrespondenceMap:
             pass
 
 
+def ObjectsParams(**kw):
+    """eppm_objects_params with the defaults of DESIGN.md section 20 (tau 1, iters 3, connectivity 8, min_area 16, max_objects 64,
+    min_overlap 4)."""
+    p = CObjectsParams()
+    check(lib().eppm_objects_default_params(C.byref(p)), "eppm_objects_default_params")
+    for k, v in kw.items():
+        if not hasattr(p, k):
+            raise TypeError(f"unknown object-detector parameter {k}")
+        setattr(p, k, v)
+    return p
+
+
+class ObjectDetector:
+    """Moving objects over the pairs of a context (eppm_objects_*): the connected components of the motion mask of
+    image 1 (what moves against the camera), with a box, an area, a velocity and an id that survives from one pair to the next.  ctx: an
+    EPPM or an EPPMBatch; one slot per pair of it.  Every step() works on the active pairs of the context's last
+    compute_flow_bidirectional*.  The detector is its own allocation on the context's device; close() frees it.  params: ObjectsParams'
+    tau, iters, connectivity, min_area, max_objects and min_overlap."""
+
+    def __init__(self, ctx, size=None, slots=1, device=0, **params):
+        """ctx None: a detector without a context, for step_frames on caller planes (eppm_objects_create_size): size = (h, w), `slots`
+        slots."""
+        self._f = C.c_void_p()
+        self.ctx = ctx
+        self.params = ObjectsParams(**params)
+        if ctx is None:
+            if size is None or len(size) != 2:
+                raise EppmError("ObjectDetector: without a context, size=(h, w) is required")
+            self.h, self.w, self.nslots = int(size[0]), int(size[1]), int(slots)
+            check(lib().eppm_objects_create_size(self.h, self.w, self.nslots, int(device), C.byref(self.params), C.byref(self._f)),
+                  "eppm_objects_create_size")
+            return
+        check(lib().eppm_objects_create(ctx._ctx, C.byref(self.params), C.byref(self._f)), "eppm_objects_create")
+        self.h, self.w = ctx.h, ctx.w
+        self.nslots = int(lib().eppm_batch_size(ctx._ctx))
+
+    def step(self, cut=None, ctx=None):
+        """One step of every active pair's slot; cut: None, or one flag per active pair (true: the pair's image 2 is the first frame of
+        another clip, nothing is carried to it).  Asynchronous on the context's stream."""
+        c = self.ctx if ctx is None else ctx
+        flags = None if cut is None else (C.c_uint8 * len(cut))(*[int(bool(x)) for x in cut])
+        if flags is not None and len(cut) != getattr(c, "n", 1):
+            raise EppmError("ObjectDetector.step: one cut flag per active pair")
+        check(lib().eppm_objects_step(self._f, c._ctx, flags), "eppm_objects_step")
+
+    def step_frames(self, slot, d_mask, d_flow, d_flow_bwd=None, d_occ2=None, cut=False):
+        """eppm_objects_step_frames: the kernels alone for one slot on caller device planes (addresses), synchronous."""
+        check(lib().eppm_objects_step_frames(self._f, int(slot), C.c_void_p(d_mask), C.c_void_p(d_flow), C.c_void_p(d_flow_bwd),
+                                             C.c_void_p(d_occ2), int(bool(cut))), "eppm_objects_step_frames")
+
+    def _get(self, slot):
+        n = int(self.params.max_objects)
+        rec = (CObject * n)()
+        cnt = CObjectsCounts()
+        check(lib().eppm_objects_get(self._f, int(slot), n, rec, C.byref(cnt)), "eppm_objects_get")
+        return rec, cnt
+
+    def objects(self, slot=0):
+        """The slot's objects in label order: dicts of id, age, area, x0, y0, x1, y1, n_flow, sum_x, sum_y, sum_qu, sum_qv, and derived
+        in float64 centroid (x, y) and velocity (u, v) in pixels per frame (None without a valid vector)."""
+        rec, cnt = self._get(slot)
+        return [object_record(rec[k]) for k in range(cnt.n)]
+
+    def counts(self, slot=0):
+        """dict n, n_found, n_components, next_id."""
+        return self._get(slot)[1].as_dict()
+
+    def labels(self, slot=0):
+        """(h, w) uint8: per pixel of image 1 the index (1 .. n) of its object in objects(slot), 0 for none."""
+        lab = np.empty((self.h, self.w), np.uint8)
+        check(lib().eppm_objects_get_labels(self._f, int(slot), lab.ctypes.data_as(C.c_void_p)), "eppm_objects_get_labels")
+        return lab
+
+    def id_map(self, slot=0):
+        """(h, w) int32: per pixel the id of its object, 0 for none."""
+        rec, cnt = self._get(slot)
+        lut = np.zeros(256, np.int32)
+        for k in range(cnt.n):
+            lut[k + 1] = rec[k].id
+        return lut[self.labels(slot)]
+
+    def state(self, slot=0):
+        """(carried (h, w) uint8, prev_id, prev_age (256 int32 each), next_id): what the slot's next step starts from."""
+        car = np.empty((self.h, self.w), np.uint8)
+        pid, page = np.empty(256, np.int32), np.empty(256, np.int32)
+        nxt = C.c_int32()
+        check(lib().eppm_objects_get_state(self._f, int(slot), *[x.ctypes.data_as(C.c_void_p) for x in (car, pid, page)], C.byref(nxt)),
+              "eppm_objects_get_state")
+        return car, pid, page, int(nxt.value)
+
+    def set_state(self, slot, carried, prev_id, prev_age, next_id):
+        car = np.ascontiguousarray(carried, np.uint8)
+        pid, page = np.ascontiguousarray(prev_id, np.int32), np.ascontiguousarray(prev_age, np.int32)
+        if car.shape != (self.h, self.w) or pid.shape != (256,) or page.shape != (256,):
+            raise EppmError(f"ObjectDetector.set_state: a ({self.h},{self.w}) uint8 plane and two tables of 256 int32")
+        if not -2 ** 31 <= int(next_id) < 2 ** 31:
+            raise EppmError("ObjectDetector.set_state: status 1: next_id is not an int32")
+        check(lib().eppm_objects_set_state(self._f, int(slot), *[x.ctypes.data_as(C.c_void_p) for x in (car, pid, page)], C.c_int32(int(next_id))),
+              "eppm_objects_set_state")
+
+    def reset(self, slot=None):
+        """The slot is empty again (slot=None: every slot): nothing carried, the next id is 1."""
+        check(lib().eppm_objects_reset(self._f, -1 if slot is None else int(slot)), "eppm_objects_reset")
+
+    def close(self):
+        if self._f:
+            lib().eppm_objects_destroy(self._f)
+            self._f = C.c_void_p()
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
 def _level(level):
     """a stop level as a plain int; anything that is not an integer is refused before the library is touched"""
     if isinstance(level, (bool, np.bool_)) or not isinstance(level, (int, np.integer)):
@@ -891,6 +1007,107 @@ def propagate_layers(clips, layers, slots=8, auto_cut=False, stop_level=None, **
         if e is not None:
             e.close()
     return out
+
+
+def _objects_split(kw):
+    """the keyword arguments of detect_objects(_sequences): ObjectsParams' go to the detector, CutDetector's to the cut detector"""
+    ob = {k: kw.pop(k) for k in ("tau", "iters", "connectivity", "min_area", "max_objects", "min_overlap") if k in kw}
+    cut = {k: kw.pop(k) for k in ("lost_permille", "residual_max") if k in kw}
+    if kw:
+        raise TypeError(f"unknown parameter {sorted(kw)[0]}")
+    return ob, cut
+
+
+def detect_objects(frames, auto_cut=False, stop_level=None, labels=False, **params):
+    """The moving objects of every consecutive pair of a clip ((h, w, 3) uint8 frames; ObjectDetector): one
+    streaming context -- set_data, then push_frame --, one bidirectional call on the device and one detector step per pair.  Returns one
+    list of object dicts (ObjectDetector.objects) per pair: the objects of the pair's first frame; an id persists while the object is
+    followed.  Memory does not grow with the clip.  params: ObjectsParams', and with auto_cut=True CutDetector's lost_permille and
+    residual_max: a pair that the cut detector calls a cut carries nothing over, so the objects of the next pair are all new.
+    stop_level: the flow's draft mode (None: full quality).  labels=True: returns (objects, labels), one (h, w) uint8 plane per pair."""
+    ob_params, cut_params = _objects_split(dict(params))
+    if cut_params and not auto_cut:
+        raise TypeError("detect_objects: lost_permille and residual_max need auto_cut=True")
+    frames = [np.ascontiguousarray(f, np.uint8) for f in frames]
+    if len(frames) < 2:
+        raise EppmError("detect_objects: at least two frames")
+    h, w, _ = frames[0].shape
+    e = EPPM()
+    od = det = None
+    out, planes = [], []
+    try:
+        e.init(h, w)
+        e.set_temporal(True)
+        if stop_level is not None:
+            e.set_stop_level(_level(stop_level))
+        od = ObjectDetector(e, **ob_params)
+        if auto_cut:
+            det = CutDetector(e, **cut_params)
+        for k in range(len(frames) - 1):
+            if k == 0:
+                e.set_data(frames[0], frames[1])
+            else:
+                e.push_frame(frames[k + 1])
+            e.compute_flow_bidirectional_device()
+            od.step(_auto_cut_step(e, det) if auto_cut else None)
+            out.append(od.objects(0))
+            if labels:
+                planes.append(od.labels(0))
+    finally:
+        if det is not None:
+            det.close()
+        if od is not None:
+            od.close()
+        e.close()
+    return (out, planes) if labels else out
+
+
+def detect_objects_sequences(clips, slots=8, auto_cut=False, stop_level=None, labels=False, **params):
+    """detect_objects for many clips at once: clips of one frame size and of any lengths (two frames at least) through ONE batch context
+    of min(slots, len(clips)) slots and one ObjectDetector, on flow_sequences' schedule.  A slot that takes the next clip of the queue is
+    reset after that step, so the clip's ids start at 1.  Returns one list per clip, each what detect_objects(clip) returns."""
+    ob_params, cut_params = _objects_split(dict(params))
+    if cut_params and not auto_cut:
+        raise TypeError("detect_objects_sequences: lost_permille and residual_max need auto_cut=True")
+    clips = [[np.ascontiguousarray(f, np.uint8) for f in clip] for clip in clips]
+    plan = _sequence_plan([len(c) for c in clips], slots)
+    h, w, _ = clips[0][0].shape
+    out = [[] for _ in clips]
+    planes = [[] for _ in clips]
+    e = od = det = None
+    try:
+        for t, step in enumerate(plan):
+            if t == 0:
+                e = EPPMBatch(h, w, len(step), params=None)
+                e.set_temporal(True)
+                if stop_level is not None:
+                    e.set_stop_level(_level(stop_level))
+                od = ObjectDetector(e, **ob_params)
+                if auto_cut:
+                    det = CutDetector(e, **cut_params)
+                e.set_data([(clips[c][0], clips[c][1]) for c, _, _, _ in step])
+            else:
+                e.push_frames([clips[c][f] for c, f, _, _ in step], [cut for _, _, cut, _ in step])
+            e.compute_flow_bidirectional_device()
+            flags = [cut for _, _, cut, _ in step]
+            if auto_cut:
+                flags = [a or bool(b) for a, b in zip(flags, _auto_cut_step(e, det))]
+            od.step(flags)
+            for slot, (c, _, new_clip, keep) in enumerate(step):
+                if new_clip:
+                    od.reset(slot)
+                elif keep:
+                    out[c].append(od.objects(slot))
+                    if labels:
+                        planes[c].append(od.labels(slot))
+    finally:
+        if det is not None:
+            det.close()
+        if od is not None:
+            od.close()
+        if e is not None:
+            e.close()
+    return (out, planes) if labels else out
 
 
 def stabilize_sequence(frames, params=None, tau=1.0, iters=3, smooth=0.9, temporal=True, stop_level=0, masks=False, auto_cut=False, **cut_params):

@@ -184,6 +184,17 @@ EPPM_HIDDEN int ctx_stab_inputs(eppm_ctx* c, int h, int w, int device, int nslot
 // the launcher stream of the context-less launchers (launchers_ref_abi.cpp) runs eppm_stab_step_frames through this (stabilizer.cpp)
 EPPM_HIDDEN int stab_step_on(eppm_stab* f, eppm::StabArgs& in, int slot0, const uint8_t* cut, hipStream_t s, eppm_ctx* timing);
 EPPM_HIDDEN int stab_device(const eppm_stab* f, int* h, int* w, int* nslots);
+// slot 0's device mask plane (h*w bytes; what eppm_stab_get_mask copies) and the distance in bytes to the next slot's: read by the object
+// detector's private stabiliser (objects.cpp)
+EPPM_HIDDEN const uint8_t* stab_mask_device(const eppm_stab* f, size_t* slot_stride);
+
+// ---- an object detector (objects.cpp) reads what a stabiliser and a temporal filter read of a context ----
+// the launcher stream of the context-less launchers (launchers_ref_abi.cpp) runs eppm_objects_step_frames through this (objects.cpp):
+// slots slot0 .. slot0 + in.n - 1 from the input members of in; cut: NULL or one flag per pair
+EPPM_HIDDEN int objects_step_on(eppm_objects* f, eppm::ObjArgs& in, int slot0, const uint8_t* cut, hipStream_t s, eppm_ctx* timing);
+EPPM_HIDDEN int objects_device(const eppm_objects* f, int* h, int* w, int* nslots);
+// the slot's error word after the detector's last step (waits for it): EPPM_ERR_STATE if a kernel's loop hit its cap
+EPPM_HIDDEN int objects_slot_status(eppm_objects* f, int slot, const char* what);
 
 // ---- what a cut detector (cutdet.cpp) reads of a context (ctx_interp.cpp) ----
 // the input members of *in (both raw images, the level-0 backward flow, occ1 and occ2) for every active pair, under ctx_tfilter_inputs' rules

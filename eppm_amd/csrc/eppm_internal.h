@@ -450,6 +450,37 @@ struct CMapArgs {
 void launch_cmap_step(const CMapArgs& a, hipStream_t s);
 void launch_cmap_render(const CMapArgs& a, hipStream_t s);
 
+// ---- moving-object detection (k_objects.hip; the semantics: objects.h) ----
+// One step covers n pairs: pair k's inputs (mask: h*w bytes; fwd / bwd: h*w float2; occ2: h*w bytes) lie k * (their stride) bytes past
+// pair 0's and feed slot slot0 + k, whose block lies (slot0 + k) * slot_stride bytes past `mem`: parent | root | area (h*w words each) |
+// labels | carried (h*w bytes each) | chunk counts (2 words per chunk of 1024 indices) | records (256 x 64 B, entry = label) | votes
+// ((max_objects + 1)^2 words) | header (32 B), prev_id, prev_age (256 words each).  bwd NULL: no carry (the carried plane becomes zero).
+// The per-slot bits travel in the kernel arguments as TFilterArgs' do: empty (the carried plane counts as zero and next_id as 1) and cut
+// (image 2 starts another clip: the carried plane becomes zero).
+struct ObjArgs {
+    const uint8_t* mask;
+    size_t mask_stride;
+    const float* fwd;
+    size_t fwd_stride;
+    const float* bwd;
+    size_t bwd_stride;
+    const uint8_t* occ2;
+    size_t occ_stride;
+    char* mem;
+    size_t slot_stride, off_root, off_area, off_labels, off_carried, off_chunks, off_rec, off_votes, off_hdr;
+    int h, w, n, slot0;
+    int tiles_x, tiles_y, nchunks;
+    int connectivity, min_area, max_objects, min_overlap;
+    uint32_t empty[kTemporalMaxSlots / 32], cut[kTemporalMaxSlots / 32];
+};
+// a slot's header on the device; err: a loop of a kernel hit its iteration cap (never, unless the code is wrong)
+struct ObjHeader {
+    int32_t n, n_found, n_components, next_id;
+    uint32_t err, pad[3];
+};
+void launch_objects_label(const ObjArgs& a, hipStream_t s);       // tile, merge, flatten + areas, count, scan, number, label + records + votes
+void launch_objects_assign(const ObjArgs& a, hipStream_t s);      // the identity rule, then the carry
+
 // ---- flow colour coding (k_color.hip) ----
 // rgba: h*w packed R | G<<8 | B<<16 (alpha 0); flow: h*w float2
 void launch_flow_to_color(uint32_t* rgba, const float* flow, int h, int w, float max_disp_x, float max_disp_y, hipStream_t s, Batch bt = kOnePair);

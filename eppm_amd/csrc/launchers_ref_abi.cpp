@@ -787,6 +787,29 @@ extern "C" int eppm_cmap_step_frames(eppm_cmap* f, int slot, const void* d_rgba1
     HIPCHK(hipStreamSynchronize(g_stream));
     return finish();
 }
+// ---- one object-detector step of one slot on caller planes, without a fit (k_objects.hip; the host forms: eppm_objects_label_host,
+// eppm_objects_assign_host, eppm_objects_carry_host) ----
+extern "C" int eppm_objects_step_frames(eppm_objects* f, int slot, const uint8_t* d_mask, const eppm_float2* d_flow, const eppm_float2* d_flow_bwd,
+                                        const uint8_t* d_occ2, int cut)
+{
+    if (!f || !d_mask || !d_flow) return set_err(EPPM_ERR_ARG, "eppm_objects_step_frames: NULL argument");
+    int h, w, nslots;
+    const int device = objects_device(f, &h, &w, &nslots);
+    if (slot < 0 || slot >= nslots) return set_err(EPPM_ERR_ARG, "eppm_objects_step_frames: slot %d, the detector has %d", slot, nslots);
+    std::lock_guard<std::mutex> lk(g_mu);
+    int d = 0;
+    HIPCHK(hipGetDevice(&d));
+    if (d != device) return set_err(EPPM_ERR_ARG, "eppm_objects_step_frames: the detector lives on device %d, the current device is %d", device, d);
+    ObjArgs in{};
+    in.mask = d_mask; in.fwd = (const float*)d_flow;
+    if (d_flow_bwd && d_occ2) in.bwd = (const float*)d_flow_bwd, in.occ2 = d_occ2;
+    in.n = 1;
+    const uint8_t c = cut != 0;
+    CHK(objects_step_on(f, in, slot, &c, g_stream, nullptr));
+    HIPCHK(hipStreamSynchronize(g_stream));
+    CHK(finish());
+    return objects_slot_status(f, slot, "eppm_objects_step_frames");
+}
 // the C++-linkage symbol the reference's driver declares at :64 (defaults 100,100 there; the live call passes 20,20)
 void bao_cuda_convert_flow_to_colorshow(uchar4* rgbflow, float2* flow_vec, int h, int w, float max_disp_x, float max_disp_y)
 {

@@ -355,3 +355,81 @@ def cutdet_host(img1, img2, bu, bv, occ1, occ2, lost_permille=530, residual_max=
     st = CCutStats()
     check(lib().eppm_cutdet_host(C.byref(p), *[x.ctypes.data_as(C.c_void_p) for x in (a, b, bu, bv, o1, o2)], h, w, C.byref(st)), "eppm_cutdet_host")
     return st.as_dict()
+
+
+def _objects_params(connectivity=8, min_area=16, max_objects=64, min_overlap=4, tau=1.0, iters=3):
+    from ._lib import CObjectsParams
+    return CObjectsParams(float(tau), int(iters), int(connectivity), int(min_area), int(max_objects), int(min_overlap))
+
+
+def object_record(rec):
+    """A record of the C ABI (eppm_object) as a dict, with what the host derives in float64: centroid (x, y) = sum / area and the mean
+    velocity (u, v) = sum_q / (256 n_flow) in pixels per frame, None without a valid vector."""
+    d = rec.as_dict()
+    d["centroid"] = (d["sum_x"] / d["area"], d["sum_y"] / d["area"]) if d["area"] else None
+    d["velocity"] = (d["sum_qu"] / (256.0 * d["n_flow"]), d["sum_qv"] / (256.0 * d["n_flow"])) if d["n_flow"] else None
+    return d
+
+
+def objects_label_host(mask, u, v, connectivity=8, min_area=16, max_objects=64):
+    """Labelling on the host (eppm_objects_label_host; equal to the kernels in every number).  mask: (h, w) uint8,
+    1 is foreground; (u, v): the forward flow.  Returns (labels (h, w) uint8, records: a list of n dicts with id and age 0, counts: dict
+    n, n_found, n_components)."""
+    from ._lib import CObject, CObjectsCounts
+    p = _objects_params(connectivity, min_area, max_objects)
+    m = np.ascontiguousarray(mask, np.uint8)
+    u = np.ascontiguousarray(u, np.float32)
+    v = np.ascontiguousarray(v, np.float32)
+    if m.ndim != 2 or u.shape != m.shape or v.shape != m.shape:
+        raise ValueError("objects_label_host: mask and flow (h, w)")
+    h, w = m.shape
+    labels = np.empty((h, w), np.uint8)
+    rec = (CObject * max(int(max_objects), 1))()
+    cnt = CObjectsCounts()
+    check(lib().eppm_objects_label_host(C.byref(p), *[x.ctypes.data_as(C.c_void_p) for x in (m, u, v)], h, w, labels.ctypes.data_as(C.c_void_p),
+                                        rec, C.byref(cnt)), "eppm_objects_label_host")
+    counts = cnt.as_dict()
+    del counts["next_id"]
+    return labels, [object_record(rec[k]) for k in range(cnt.n)], counts
+
+
+def objects_carry_host(labels, bu, bv, occ2):
+    """The labels as the next pair's image 1 sees them (eppm_objects_carry_host): (h, w) uint8."""
+    lab = np.ascontiguousarray(labels, np.uint8)
+    bu = np.ascontiguousarray(bu, np.float32)
+    bv = np.ascontiguousarray(bv, np.float32)
+    o = np.ascontiguousarray(occ2, np.uint8)
+    if lab.ndim != 2 or any(x.shape != lab.shape for x in (bu, bv, o)):
+        raise ValueError("objects_carry_host: labels, flow and mask (h, w)")
+    h, w = lab.shape
+    out = np.empty((h, w), np.uint8)
+    check(lib().eppm_objects_carry_host(*[x.ctypes.data_as(C.c_void_p) for x in (lab, bu, bv, o)], h, w, out.ctypes.data_as(C.c_void_p)),
+          "eppm_objects_carry_host")
+    return out
+
+
+def objects_state():
+    """The state of an empty slot's tables: (prev_id, prev_age, next_id) = (256 zeros, 256 zeros, 1)."""
+    return np.zeros(256, np.int32), np.zeros(256, np.int32), 1
+
+
+def objects_assign_host(labels, n, carried, prev_id, prev_age, next_id, max_objects=64, min_overlap=4):
+    """The identity rule on the host (eppm_objects_assign_host): the n objects of `labels` against the carried plane (None: all zero) and
+    the previous objects' tables.  Returns (ids, ages: n ints each, prev_id, prev_age: the new 256-entry int32 tables, next_id)."""
+    from ._lib import CObject
+    p = _objects_params(8, 1, max_objects, min_overlap)
+    lab = np.ascontiguousarray(labels, np.uint8)
+    car = None if carried is None else np.ascontiguousarray(carried, np.uint8)
+    if lab.ndim != 2 or (car is not None and car.shape != lab.shape):
+        raise ValueError("objects_assign_host: labels and carried (h, w)")
+    pid = np.array(prev_id, np.int32).copy()
+    page = np.array(prev_age, np.int32).copy()
+    if pid.shape != (256,) or page.shape != (256,):
+        raise ValueError("objects_assign_host: prev_id and prev_age are 256 entries each")
+    h, w = lab.shape
+    rec = (CObject * max(int(n), 1))()
+    nxt = C.c_int32(int(next_id))
+    check(lib().eppm_objects_assign_host(C.byref(p), lab.ctypes.data_as(C.c_void_p), None if car is None else car.ctypes.data_as(C.c_void_p), h, w,
+                                         int(n), pid.ctypes.data_as(C.c_void_p), page.ctypes.data_as(C.c_void_p), C.byref(nxt), rec),
+          "eppm_objects_assign_host")
+    return [int(rec[k].id) for k in range(n)], [int(rec[k].age) for k in range(n)], pid, page, int(nxt.value)

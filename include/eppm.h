@@ -600,6 +600,86 @@ int  eppm_cmap_step_host(const eppm_cmap_params* p, float* map_out, const float*
 int  eppm_cmap_render_host(uint8_t* rgb_out, const float* map, const uint8_t* rgb_cur, const uint8_t* layer_rgba, const uint8_t* anchor_rgb,
                            int h, int w);
 
+/* ----------------------------------------------------------------------------------------
+ * moving-object detection: the connected components of the stabiliser's motion mask as objects.  A detector holds
+ * one slot per pair of its context.  One step fits the camera motion of every active pair with a private stabiliser (tau, iters: section
+ * 16's), takes the pixels of image 1 whose mask byte is 1 ("moves on its own") as foreground, labels its components under 4- or
+ * 8-connectivity, drops those smaller than min_area, numbers the others 1, 2, ... in increasing order of their root (the smallest linear
+ * index y*w + x of a component) and reports the first max_objects of them: a label byte per pixel (0: background, dropped or beyond
+ * max_objects) and one integer record per object.  At the end of the step the labels are carried along the backward flow to image 2; at
+ * the next step an object inherits the id of the previous object that most of its carried pixels voted for, if it is that object's
+ * largest claimant and the overlap is at least min_overlap pixels; every other object takes the slot's next id.  A split leaves the old id
+ * with the larger part, a merge keeps the dominant previous object's id.  All results are integers, independent of any summation order:
+ * the kernels equal eppm_objects_label_host, eppm_objects_assign_host and eppm_objects_carry_host bit for bit, in both libraries, on
+ * every run.  A detector is a separate allocation on its context's device (14 bytes per pixel and slot plus tables, and its stabiliser's
+ * 5), made by eppm_objects_create and freed by eppm_objects_destroy; a context that never creates one allocates and launches exactly
+ * what it did without.  A slot that has never been stepped, or after eppm_objects_reset, is empty: its carried plane counts as zero and
+ * its next id is 1.  Frames of at most 8192 x 8192 and 2^26 pixels.  Stage names: "objects_fit", "objects_label", "objects_assign".
+ * -------------------------------------------------------------------------------------- */
+typedef struct eppm_objects_params {
+    float tau;                   /* the fit's inlier radius in pixels (1); finite, > 0 */
+    int   iters;                 /* the fit's passes (3); 1 .. 8 */
+    int   connectivity;          /* 4 or 8 (8) */
+    int   min_area;              /* smallest component that is an object (16); >= 1 */
+    int   max_objects;           /* objects reported per slot (64); 1 .. 255 */
+    int   min_overlap;           /* carried pixels an object needs to inherit an id (4); >= 1 */
+} eppm_objects_params;
+typedef struct eppm_object {
+    int32_t id, age;             /* the identity, and the steps it has been inherited for */
+    int32_t area;
+    int32_t x0, y0, x1, y1;      /* inclusive bounding box */
+    int32_t n_flow;              /* pixels of the object with a valid forward vector (known, |u|, |v| <= 8192) */
+    int64_t sum_x, sum_y;        /* over the object's pixels: the centroid is sum / area */
+    int64_t sum_qu, sum_qv;      /* over the n_flow pixels: (int)rintf(u * 256); the mean velocity is sum / (256 * n_flow) */
+} eppm_object;
+typedef struct eppm_objects_counts {
+    int32_t n;                   /* objects reported: min(n_found, max_objects) */
+    int32_t n_found;             /* components with area >= min_area */
+    int32_t n_components;        /* components of the foreground */
+    int32_t next_id;             /* the id the slot's next new object takes */
+} eppm_objects_counts;
+typedef struct eppm_objects eppm_objects;
+
+int  eppm_objects_default_params(eppm_objects_params* p);
+/* p NULL: the defaults.  One slot per pair of ctx (eppm_batch_size), on its device; every slot empty. */
+int  eppm_objects_create(eppm_ctx* ctx, const eppm_objects_params* p, eppm_objects** out);
+/* a detector without a context: nslots slots of h x w pixels (any size from 1 x 1) on `device` */
+int  eppm_objects_create_size(int h, int w, int nslots, int device, const eppm_objects_params* p, eppm_objects** out);
+int  eppm_objects_destroy(eppm_objects* det);             /* NULL is fine */
+int  eppm_objects_reset(eppm_objects* det, int slot);     /* the slot is empty again (next_id 1); slot < 0: every slot.  Synchronous */
+/* One step of slots 0 .. active pairs - 1 on the pairs of ctx's last eppm_compute_bidirectional* (the level-0 flows, occ1 and occ2), under
+ * eppm_stab_step's rules: valid in the window of eppm_interpolate* (EPPM_ERR_STATE outside it); EPPM_ERR_ARG for a context of other
+ * dimensions, another device or more active pairs than the detector has slots.  cut: NULL, or one flag per active pair; non-zero: image 2
+ * of that pair is the first frame of another clip, so nothing is carried to it: the slot's carried plane becomes zero and every object of
+ * its next step is new (next_id keeps counting).  A slot the step does not cover keeps its state.  A fixed sequence of launches,
+ * asynchronous on the context's stream: no copy, no allocation, no host synchronisation. */
+int  eppm_objects_step(eppm_objects* det, eppm_ctx* ctx, const uint8_t* cut);
+/* the kernels alone, without a fit, for one slot on caller device planes of the detector's size: h*w mask bytes (1: foreground), h*w
+ * float2 forward flow, and h*w float2 backward flow with h*w occ2 bytes; either of the last two NULL: no carry, the carried plane becomes
+ * zero.  On the launcher stream, synchronous.  Whatever the planes hold, nothing outside them is read. */
+int  eppm_objects_step_frames(eppm_objects* det, int slot, const uint8_t* d_mask, const eppm_float2* d_flow, const eppm_float2* d_flow_bwd,
+                              const uint8_t* d_occ2, int cut);
+/* synchronous; EPPM_ERR_STATE on a slot that has never been stepped, and -- with a message that says so -- if a loop of a kernel hit
+ * its iteration cap in the slot's last steps (a defect of the library, never an input's fault; eppm_objects_reset clears it).
+ * The first min(n, max) records, in label order, and the counts (either may be NULL) / the h*w label bytes */
+int  eppm_objects_get(eppm_objects* det, int slot, int max, eppm_object* records, eppm_objects_counts* counts);
+int  eppm_objects_get_labels(eppm_objects* det, int slot, uint8_t* labels);
+/* synchronous.  A slot's state between two steps: the carried plane (h*w bytes: the last labels as image 2's pixels see them), the ids
+ * and ages of the last objects (256 entries each, indexed by label; entry 0 and those beyond the last n are 0) and next_id.  An empty
+ * slot gives zeros and next_id 1.  set_state makes the slot non-empty; next_id outside [1, 2^30] or an age outside [0, 2^30] is
+ * EPPM_ERR_ARG.  A carried byte above max_objects counts as 0. */
+int  eppm_objects_get_state(eppm_objects* det, int slot, uint8_t* carried, int32_t* prev_id, int32_t* prev_age, int32_t* next_id);
+int  eppm_objects_set_state(eppm_objects* det, int slot, const uint8_t* carried, const int32_t* prev_id, const int32_t* prev_age, int32_t next_id);
+/* host forms (no GPU needed; plain sequential code).  label: mask, u, v (h*w each) to the label bytes, max_objects records (id and age 0)
+ * and counts (next_id is not touched).  carry: the labels to image 2 along the backward flow (bu, bv) and occ2.  assign: the identity
+ * rule for the n objects of `labels` against the carried plane (NULL: all zero), reading and rewriting the 256-entry tables and *next_id
+ * and setting id and age of the n records. */
+int  eppm_objects_label_host(const eppm_objects_params* p, const uint8_t* mask, const float* u, const float* v, int h, int w, uint8_t* labels,
+                             eppm_object* records, eppm_objects_counts* counts);
+int  eppm_objects_carry_host(const uint8_t* labels, const float* bu, const float* bv, const uint8_t* occ2, int h, int w, uint8_t* carried);
+int  eppm_objects_assign_host(const eppm_objects_params* p, const uint8_t* labels, const uint8_t* carried, int h, int w, int n, int32_t* prev_id,
+                              int32_t* prev_age, int32_t* next_id, eppm_object* records);
+
 /* Per-stage device times in ms (hipEvent pairs on the context's stream), one entry per stage per
  * call since the last eppm_clear_stage_times (names repeat across calls; prepare entries first).
  * names[i] points to static strings.  Returns the number of entries written (<= max). */
@@ -610,7 +690,7 @@ int  eppm_clear_stage_times(eppm_ctx* ctx);
  * "flow_blf_bwd_L<l>", "flow_blf_bwd_final" and "fb_occlusion"; an interpolation call "interp_splat", "interp_fill" and "interp_blend"
  * (mode 1, once per group of four times); a track step "track_advance", "track_seed" and "track_compact" (mode 1; the step that seeds
  * frame 0 adds a "track_seed" before "track_advance"); a compute that starts from a temporal prior "temporal_advect" (before "patchmatch") and
- * "temporal_select" (inside it: "patchmatch" includes its time); a temporal-filter step "tfilter_step"; a stabiliser step "stab_fit" (every accumulate and solve launch) and "stab_warp"; a cut-detector step "cutdet"; a motion-blur call "mblur_pack" and "mblur_gather"; a correspondence-map step "cmap_step" and "cmap_render".  Events come from a per-context pool: none is created in a steady-state step. */
+ * "temporal_select" (inside it: "patchmatch" includes its time); a temporal-filter step "tfilter_step"; a stabiliser step "stab_fit" (every accumulate and solve launch) and "stab_warp"; a cut-detector step "cutdet"; a motion-blur call "mblur_pack" and "mblur_gather"; a correspondence-map step "cmap_step" and "cmap_render"; an object-detector step "objects_fit" (its stabiliser's launches), "objects_label" and "objects_assign".  Events come from a per-context pool: none is created in a steady-state step. */
 int  eppm_enable_stage_timing(eppm_ctx* ctx, int on);
 
 const char* eppm_last_error(void);

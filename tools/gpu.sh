@@ -19,6 +19,7 @@
 #   cutdet      the cut detector: tools/cutdet_times.py --shares on both libraries -> cutdet_times_{exact,tol}.json
 #   mblur       the synthetic shutter: tools/mblur_times.py on both libraries -> mblur_times_{exact,tol}.json
 #   cmap        the correspondence map: tools/cmap_times.py on both libraries -> cmap_times_{exact,tol}.json
+#   objects     the object detector: tools/objects_times.py on both libraries -> objects_times_{exact,tol}.json
 #   round       everything profiles/ of a round comes from (TAG=r04_x; PMC_ONLY=1, SKIP_TESTS=1)
 set -o pipefail
 R=${GRAFT_REPO_ROOT:-$(cd "$(dirname "$0")/.." && pwd)}
@@ -144,6 +145,11 @@ cmap)
   cd $R; for l in exact tol; do
     timeout -k 10 ${CMAP_TIMEOUT:-300} python tools/cmap_times.py --lib $l ${CMAP_ARGS} > $O/cmap_times_$l.json || exit 1
     cut -c1-400 $O/cmap_times_$l.json
+  done ;;
+objects)
+  cd $R; for l in exact tol; do
+    timeout -k 10 ${OBJECTS_TIMEOUT:-300} python tools/objects_times.py --lib $l ${OBJECTS_ARGS} > $O/objects_times_$l.json || exit 1
+    cut -c1-400 $O/objects_times_$l.json
   done ;;
 inflight)
   cd $R; for S in ${INFLIGHT:-1 2 3 4 6}; do

@@ -57,6 +57,12 @@
 //                     the first frame, and the layer (alpha: the first channel of the second file), sampled once at the map, is
 //                     composited over every frame: P_pl_0000.ppm (through the identity), P_pl_0001.ppm ...  With --auto-cut a frame
 //                     that starts another shot re-anchors the map, and from there on the frames are written as they are.
+//                     --objects: every pair runs the bidirectional call followed by one step of the object detector (DESIGN.md section
+//                     20: the connected components of what moves against the camera).  P_ob_0001.pgm ... get the label bytes of every
+//                     pair's first frame, P_objects.txt one line per object: the pair's index, id, age, area, the box x0 y0 x1 y1, the
+//                     centroid and the mean velocity in pixels per frame (nan nan without a valid vector).  --min-area N and
+//                     --max-objects N (1 .. 255) set its parameters and imply --objects.  With --auto-cut nothing is carried across a
+//                     cut: the objects after it take new ids.
 #include <atomic>
 #include <chrono>
 #include <cstdio>
@@ -104,6 +110,8 @@ struct Options {
     eppm_mblur_params mb = {0.5f, 16.0f, 8};                // --motion-blur S, --blur-radius, --blur-taps
     bool mb_set = false;                                    // --blur-radius or --blur-taps given
     const char *pl_layer = nullptr, *pl_alpha = nullptr;    // --propagate layer.ppm alpha.ppm
+    bool objects = false;                                   // --objects
+    int ob_min_area = 0, ob_max = 0;                        // --min-area, --max-objects (0: the default)
 };
 
 static unsigned hash32(unsigned x)
@@ -158,7 +166,7 @@ static int usage()
                     "               --sequence f0.ppm f1.ppm [f2.ppm ...] --out-prefix P [--temporal 0|1]\n"
                     "               [--denoise] [--denoise-thresh T] [--denoise-frames N] [--stabilize] [--smooth S]\n"
                     "               [--auto-cut] [--cut-lost N] [--motion-blur S] [--blur-radius R] [--blur-taps N]\n"
-                    "               [--propagate layer.ppm alpha.ppm]\n");
+                    "               [--propagate layer.ppm alpha.ppm] [--objects] [--min-area N] [--max-objects N]\n");
     return 2;
 }
 
@@ -193,8 +201,10 @@ static int run_sequence(const Options& o)
     eppm_stab* stab = nullptr;
     eppm_cutdet* det = nullptr;
     eppm_cmap* cm = nullptr;
+    eppm_objects* od = nullptr;
     FILE* cuts = nullptr;
-    auto fail = [&](const char* what) { fprintf(stderr, "%s: %s\n", what, eppm_last_error()); if (cuts) fclose(cuts); eppm_cmap_destroy(cm); eppm_cutdet_destroy(det); eppm_stab_destroy(stab); eppm_tfilter_destroy(flt); if (ctx) eppm_destroy(ctx); return 1; };
+    FILE* obf = nullptr;
+    auto fail = [&](const char* what) { fprintf(stderr, "%s: %s\n", what, eppm_last_error()); if (cuts) fclose(cuts); if (obf) fclose(obf); eppm_objects_destroy(od); eppm_cmap_destroy(cm); eppm_cutdet_destroy(det); eppm_stab_destroy(stab); eppm_tfilter_destroy(flt); if (ctx) eppm_destroy(ctx); return 1; };
     if (eppm_create(&ctx, h, w, 0, &prm) != EPPM_OK) return fail("eppm_create");
     std::vector<unsigned char> dn, st, mb, pl, layer;
     bool pl_drawn = true;               // --propagate: no cut so far
@@ -237,13 +247,26 @@ static int run_sequence(const Options& o)
         cp.lost_permille = o.cut_lost;
         if (eppm_cutdet_create(ctx, &cp, &det) != EPPM_OK) return fail("eppm_cutdet_create");
         snprintf(name, sizeof name, "%s_cuts.txt", o.prefix);
-        if (!(cuts = fopen(name, "w"))) { fprintf(stderr, "cannot write %s\n", name); eppm_cmap_destroy(cm); eppm_cutdet_destroy(det); eppm_stab_destroy(stab); eppm_tfilter_destroy(flt); eppm_destroy(ctx); return 1; }
+        if (!(cuts = fopen(name, "w"))) { fprintf(stderr, "cannot write %s\n", name); eppm_objects_destroy(od); eppm_cmap_destroy(cm); eppm_cutdet_destroy(det); eppm_stab_destroy(stab); eppm_tfilter_destroy(flt); eppm_destroy(ctx); return 1; }
+    }
+    std::vector<unsigned char> ob_labels;
+    std::vector<eppm_object> ob_rec;
+    if (o.objects) {
+        eppm_objects_params op;
+        eppm_objects_default_params(&op);
+        if (o.ob_min_area) op.min_area = o.ob_min_area;
+        if (o.ob_max) op.max_objects = o.ob_max;
+        if (eppm_objects_create(ctx, &op, &od) != EPPM_OK) return fail("eppm_objects_create");
+        ob_labels.resize((size_t)h * w);
+        ob_rec.resize(op.max_objects);
+        snprintf(name, sizeof name, "%s_objects.txt", o.prefix);
+        if (!(obf = fopen(name, "w"))) { fprintf(stderr, "cannot write %s\n", name); return fail("fopen"); }
     }
     if (eppm_set_temporal(ctx, o.temporal) != EPPM_OK) return fail("eppm_set_temporal");
     if (eppm_set_stop_level(ctx, o.stop_level) != EPPM_OK) {
         fprintf(stderr, "--stop-level: %s\n", eppm_last_error());
-        if (cuts) fclose(cuts);
-        eppm_cmap_destroy(cm); eppm_cutdet_destroy(det); eppm_stab_destroy(stab); eppm_tfilter_destroy(flt); eppm_destroy(ctx);
+        if (cuts) fclose(cuts); if (obf) fclose(obf);
+        eppm_objects_destroy(od); eppm_cmap_destroy(cm); eppm_cutdet_destroy(det); eppm_stab_destroy(stab); eppm_tfilter_destroy(flt); eppm_destroy(ctx);
         return usage();
     }
     double total = 0;
@@ -252,8 +275,8 @@ static int run_sequence(const Options& o)
         std::vector<unsigned char>& cur = img[k == 0 ? 0 : 1];
         if (eppm_ppm_size(o.seq[k], &hk, &wk) != EPPM_OK || hk != h || wk != w || eppm_load_ppm(o.seq[k], cur.data(), h, w, &nch) != EPPM_OK) {
             fprintf(stderr, "cannot read %s (or its size differs from the first frame's)\n", o.seq[k]);
-            if (cuts) fclose(cuts);
-            eppm_cmap_destroy(cm); eppm_cutdet_destroy(det);
+            if (cuts) fclose(cuts); if (obf) fclose(obf);
+            eppm_objects_destroy(od); eppm_cmap_destroy(cm); eppm_cutdet_destroy(det);
             eppm_stab_destroy(stab);
             eppm_tfilter_destroy(flt);
             eppm_destroy(ctx);
@@ -262,7 +285,7 @@ static int run_sequence(const Options& o)
         if (k == 0) {
             if (o.denoise) {
                 snprintf(name, sizeof name, "%s_dn_0000.ppm", o.prefix);
-                if (!write_ppm(name, cur.data(), h, w)) { fprintf(stderr, "cannot write %s\n", name); if (cuts) fclose(cuts); eppm_cmap_destroy(cm); eppm_cutdet_destroy(det); eppm_stab_destroy(stab); eppm_tfilter_destroy(flt); eppm_destroy(ctx); return 1; }
+                if (!write_ppm(name, cur.data(), h, w)) { fprintf(stderr, "cannot write %s\n", name); if (cuts) fclose(cuts); if (obf) fclose(obf); eppm_objects_destroy(od); eppm_cmap_destroy(cm); eppm_cutdet_destroy(det); eppm_stab_destroy(stab); eppm_tfilter_destroy(flt); eppm_destroy(ctx); return 1; }
             }
             if (cm) {                  // the layer through the identity map: the first frame is its own anchor
                 std::vector<float> seed((size_t)h * w * 2);
@@ -276,7 +299,7 @@ static int run_sequence(const Options& o)
             }
             if (o.stabilize) {
                 snprintf(name, sizeof name, "%s_st_0000.ppm", o.prefix);
-                if (!write_ppm(name, cur.data(), h, w)) { fprintf(stderr, "cannot write %s\n", name); if (cuts) fclose(cuts); eppm_cmap_destroy(cm); eppm_cutdet_destroy(det); eppm_stab_destroy(stab); eppm_tfilter_destroy(flt); eppm_destroy(ctx); return 1; }
+                if (!write_ppm(name, cur.data(), h, w)) { fprintf(stderr, "cannot write %s\n", name); if (cuts) fclose(cuts); if (obf) fclose(obf); eppm_objects_destroy(od); eppm_cmap_destroy(cm); eppm_cutdet_destroy(det); eppm_stab_destroy(stab); eppm_tfilter_destroy(flt); eppm_destroy(ctx); return 1; }
             }
             continue;
         }
@@ -284,7 +307,7 @@ static int run_sequence(const Options& o)
         if (k == 1) { if (eppm_set_images(ctx, img[0].data(), img[1].data(), (size_t)w * 3) != EPPM_OK) return fail("eppm_set_images"); }
         else if (eppm_push_image(ctx, cur.data(), (size_t)w * 3) != EPPM_OK) return fail("eppm_push_image");
         const bool last = k + 1 == o.seq.size();
-        if (!o.denoise && !o.stabilize && !o.auto_cut && !cm && !(o.mblur && last)) { if (eppm_compute(ctx, u.data(), v.data()) != EPPM_OK) return fail("eppm_compute"); }
+        if (!o.denoise && !o.stabilize && !o.auto_cut && !cm && !od && !(o.mblur && last)) { if (eppm_compute(ctx, u.data(), v.data()) != EPPM_OK) return fail("eppm_compute"); }
         else {
             if (eppm_compute_bidirectional(ctx, u.data(), v.data(), nullptr, nullptr, nullptr, nullptr) != EPPM_OK) return fail("eppm_compute_bidirectional");
             uint8_t cut = 0;
@@ -307,21 +330,39 @@ static int run_sequence(const Options& o)
                 if (pl_drawn) { if (eppm_cmap_render(cm, 0, pl.data(), (size_t)w * 3) != EPPM_OK) return fail("eppm_cmap_render"); }
                 else pl = cur;
             }
+            if (od) {
+                eppm_objects_counts oc;
+                if (eppm_objects_step(od, ctx, o.auto_cut ? &cut : nullptr) != EPPM_OK) return fail("eppm_objects_step");
+                if (eppm_objects_get(od, 0, (int)ob_rec.size(), ob_rec.data(), &oc) != EPPM_OK) return fail("eppm_objects_get");
+                if (eppm_objects_get_labels(od, 0, ob_labels.data()) != EPPM_OK) return fail("eppm_objects_get_labels");
+                for (int j = 0; j < oc.n; j++) {
+                    const eppm_object& r = ob_rec[j];
+                    fprintf(obf, "%zu %d %d %d %d %d %d %d %.6f %.6f", k - 1, r.id, r.age, r.area, r.x0, r.y0, r.x1, r.y1, (double)r.sum_x / r.area,
+                            (double)r.sum_y / r.area);
+                    if (r.n_flow) fprintf(obf, " %.6f %.6f\n", (double)r.sum_qu / (256.0 * r.n_flow), (double)r.sum_qv / (256.0 * r.n_flow));
+                    else fprintf(obf, " nan nan\n");
+                }
+                snprintf(name, sizeof name, "%s_ob_%04zu.pgm", o.prefix, k);
+                FILE* f = fopen(name, "wb");
+                bool ok = f && fprintf(f, "P5\n%d %d\n255\n", w, h) > 0 && fwrite(ob_labels.data(), 1, ob_labels.size(), f) == ob_labels.size();
+                if (f) ok = fclose(f) == 0 && ok;
+                if (!ok) { fprintf(stderr, "cannot write %s\n", name); return fail("write"); }
+            }
             if (o.denoise && eppm_tfilter_get(flt, 0, dn.data(), (size_t)w * 3) != EPPM_OK) return fail("eppm_tfilter_get");
             if (o.stabilize && eppm_stab_get(stab, 0, st.data(), (size_t)w * 3) != EPPM_OK) return fail("eppm_stab_get");
         }
         const double ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
         total += ms;
         snprintf(name, sizeof name, "%s_%04zu.flo", o.prefix, k);
-        if (eppm_save_flo(name, u.data(), v.data(), h, w) != EPPM_OK) { fprintf(stderr, "cannot write %s\n", name); if (cuts) fclose(cuts); eppm_cmap_destroy(cm); eppm_cutdet_destroy(det); eppm_stab_destroy(stab); eppm_tfilter_destroy(flt); eppm_destroy(ctx); return 1; }
+        if (eppm_save_flo(name, u.data(), v.data(), h, w) != EPPM_OK) { fprintf(stderr, "cannot write %s\n", name); if (cuts) fclose(cuts); if (obf) fclose(obf); eppm_objects_destroy(od); eppm_cmap_destroy(cm); eppm_cutdet_destroy(det); eppm_stab_destroy(stab); eppm_tfilter_destroy(flt); eppm_destroy(ctx); return 1; }
         printf("pair %zu: %.3f ms%s -> %s\n", k, ms, (o.temporal && k > 1) ? " (seeded)" : "", name);
         if (o.denoise) {
             snprintf(name, sizeof name, "%s_dn_%04zu.ppm", o.prefix, k);
-            if (!write_ppm(name, dn.data(), h, w)) { fprintf(stderr, "cannot write %s\n", name); if (cuts) fclose(cuts); eppm_cmap_destroy(cm); eppm_cutdet_destroy(det); eppm_stab_destroy(stab); eppm_tfilter_destroy(flt); eppm_destroy(ctx); return 1; }
+            if (!write_ppm(name, dn.data(), h, w)) { fprintf(stderr, "cannot write %s\n", name); if (cuts) fclose(cuts); if (obf) fclose(obf); eppm_objects_destroy(od); eppm_cmap_destroy(cm); eppm_cutdet_destroy(det); eppm_stab_destroy(stab); eppm_tfilter_destroy(flt); eppm_destroy(ctx); return 1; }
         }
         if (o.stabilize) {
             snprintf(name, sizeof name, "%s_st_%04zu.ppm", o.prefix, k);
-            if (!write_ppm(name, st.data(), h, w)) { fprintf(stderr, "cannot write %s\n", name); if (cuts) fclose(cuts); eppm_cmap_destroy(cm); eppm_cutdet_destroy(det); eppm_stab_destroy(stab); eppm_tfilter_destroy(flt); eppm_destroy(ctx); return 1; }
+            if (!write_ppm(name, st.data(), h, w)) { fprintf(stderr, "cannot write %s\n", name); if (cuts) fclose(cuts); if (obf) fclose(obf); eppm_objects_destroy(od); eppm_cmap_destroy(cm); eppm_cutdet_destroy(det); eppm_stab_destroy(stab); eppm_tfilter_destroy(flt); eppm_destroy(ctx); return 1; }
         }
         if (cm) {
             snprintf(name, sizeof name, "%s_pl_%04zu.ppm", o.prefix, k);
@@ -330,16 +371,18 @@ static int run_sequence(const Options& o)
         for (int fr = 0; o.mblur && fr <= (last ? 1 : 0); fr++) {       // frame k - 1 from the forward flow; the clip's last frame from the backward flow
             if (eppm_motion_blur(ctx, &o.mb, fr, mb.data(), (size_t)w * 3) != EPPM_OK) return fail("eppm_motion_blur");
             snprintf(name, sizeof name, "%s_mb_%04zu.ppm", o.prefix, k - 1 + fr);
-            if (!write_ppm(name, mb.data(), h, w)) { fprintf(stderr, "cannot write %s\n", name); if (cuts) fclose(cuts); eppm_cmap_destroy(cm); eppm_cutdet_destroy(det); eppm_stab_destroy(stab); eppm_tfilter_destroy(flt); eppm_destroy(ctx); return 1; }
+            if (!write_ppm(name, mb.data(), h, w)) { fprintf(stderr, "cannot write %s\n", name); if (cuts) fclose(cuts); if (obf) fclose(obf); eppm_objects_destroy(od); eppm_cmap_destroy(cm); eppm_cutdet_destroy(det); eppm_stab_destroy(stab); eppm_tfilter_destroy(flt); eppm_destroy(ctx); return 1; }
         }
     }
     printf("%zu pairs, %.3f ms per pair\n", o.seq.size() - 1, total / (double)(o.seq.size() - 1));
     const bool cuts_ok = !cuts || fclose(cuts) == 0;
-    eppm_cmap_destroy(cm); eppm_cutdet_destroy(det);
+    const bool obf_ok = !obf || fclose(obf) == 0;
+    eppm_objects_destroy(od); eppm_cmap_destroy(cm); eppm_cutdet_destroy(det);
     eppm_stab_destroy(stab);
     eppm_tfilter_destroy(flt);
     eppm_destroy(ctx);
     if (!cuts_ok) { fprintf(stderr, "cannot write %s_cuts.txt\n", o.prefix); return 1; }
+    if (!obf_ok) { fprintf(stderr, "cannot write %s_objects.txt\n", o.prefix); return 1; }
     return 0;
 }
 
@@ -418,6 +461,9 @@ int main(int argc, char** argv)
         else if (!strcmp(a, "--auto-cut")) o.auto_cut = true;
         else if (!strcmp(a, "--cut-lost")) { if (!val(&v) || v < 0 || v > 1000) return usage(); o.cut_lost = (int)v; o.auto_cut = true; }
         else if (!strcmp(a, "--propagate")) { if (i + 2 >= argc) return usage(); o.pl_layer = argv[++i]; o.pl_alpha = argv[++i]; }
+        else if (!strcmp(a, "--objects")) o.objects = true;
+        else if (!strcmp(a, "--min-area")) { if (!val(&v) || v < 1 || v > 0x7fffffff) return usage(); o.ob_min_area = (int)v; o.objects = true; }
+        else if (!strcmp(a, "--max-objects")) { if (!val(&v) || v < 1 || v > 255) return usage(); o.ob_max = (int)v; o.objects = true; }
         else if (!strcmp(a, "--temporal")) { if (!val(&v) || (v != 0 && v != 1)) return usage(); o.temporal = (int)v; }
         else if (a[0] == '-' && a[1] == '-') return usage();
         else pos.push_back(a);
@@ -433,7 +479,7 @@ int main(int argc, char** argv)
             return usage();
         return run_sequence(o);
     }
-    if (o.denoise || o.stabilize || o.auto_cut || o.pl_layer) return usage();     // the filter, the stabiliser, the cut detector and the map walk a clip
+    if (o.denoise || o.stabilize || o.auto_cut || o.pl_layer || o.objects) return usage();     // the filter, the stabiliser, the cut detector, the map and the object detector walk a clip
     if ((o.mblur && !o.mblur_file) || (o.mb_set && !o.mblur)) return usage();
     if (pos.size() == 1 || pos.size() > 3) return usage();
     if (pos.size() >= 2) { o.f1 = pos[0]; o.f2 = pos[1]; }
