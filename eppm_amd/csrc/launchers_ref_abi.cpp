@@ -45,9 +45,20 @@ int get_scratch(DevState* s, size_t bytes, void** out, int slot = 0)
         (void)hipStreamSynchronize(g_stream);
         (void)hipFree(s->scratch[slot]);
         s->scratch[slot] = nullptr; s->scratch_bytes[slot] = 0;
-        HIPCHK(hipMalloc(&s->scratch[slot], bytes));
+        hipError_t e = hipMalloc(&s->scratch[slot], bytes);
+#ifdef EPPM_TEST_HOOKS
+        e = alloc_fill(e, s->scratch[slot], bytes, false);      // test library: "alloc_fill"
+#endif
+        HIPCHK(e);
         s->scratch_bytes[slot] = bytes;
     }
+#ifdef EPPM_TEST_HOOKS
+    // a slot's contents live for one call, but the block lives as long as the process: under "alloc_fill" every hand-out is a new block
+    else if (opt_alloc_fill() >= 0) {
+        (void)hipStreamSynchronize(g_stream);
+        HIPCHK(alloc_fill(hipSuccess, s->scratch[slot], s->scratch_bytes[slot], false));
+    }
+#endif
     *out = s->scratch[slot];
     return EPPM_OK;
 }

@@ -18,7 +18,17 @@ constexpr size_t kMemCacheDeviceBytes = (size_t)3 << 30, kMemCachePinnedBytes = 
 constexpr int kMemCacheBlocks = 12;
 }  // namespace
 
+static hipError_t cache_take(void** p, size_t bytes, bool pinned, int device);
 hipError_t cache_alloc(void** p, size_t bytes, bool pinned, int device)
+{
+    const hipError_t e = cache_take(p, bytes, pinned, device);
+#ifdef EPPM_TEST_HOOKS
+    return alloc_fill(e, e == hipSuccess ? *p : nullptr, bytes, pinned);      // fresh, recycled or from the retry alike (test library: "alloc_fill")
+#else
+    return e;
+#endif
+}
+static hipError_t cache_take(void** p, size_t bytes, bool pinned, int device)
 {
     if (EPPM_MEM_CACHE) {
         std::lock_guard<std::mutex> lk(g_memcache_mu);

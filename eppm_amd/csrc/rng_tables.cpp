@@ -4,6 +4,17 @@
 
 using namespace eppm;
 
+// every hipMalloc below that a kernel or a copy then writes into (test library: "alloc_fill" poisons the block first)
+static hipError_t dev_alloc(void** p, size_t bytes)
+{
+    const hipError_t e = hipMalloc(p, bytes);
+#ifdef EPPM_TEST_HOOKS
+    return alloc_fill(e, e == hipSuccess ? *p : nullptr, bytes, false);
+#else
+    return e;
+#endif
+}
+
 // The read-only tables of a generator -- every block's start states for the init draw and the first search, and the GF(2) skip matrix --
 // depend only on (device, w, h, num_guess, seed): building them walks every block's stream on the host (0.4 M draws at 1024x436) and
 // raises a 160x160 bit matrix to a power, 1.5 ms of the 3.3 ms a context takes to create.  Contexts of one geometry share one copy;
@@ -69,9 +80,9 @@ static int rngtab_acquire(RngTables** out, int device, int w, int h, const eppm_
     std::vector<uint32_t> mat(160 * 5);
     xorwow_skip_matrix(skip, mat.data());
     t->skip_weyl = 362437u * (uint32_t)skip;
-    hipError_t e = hipMalloc(&t->init_tab, words * 4);
-    if (e == hipSuccess) e = hipMalloc(&t->iter_tab, words * 4);
-    if (e == hipSuccess) e = hipMalloc(&t->skip_mat, mat.size() * 4);
+    hipError_t e = dev_alloc((void**)&t->init_tab, words * 4);
+    if (e == hipSuccess) e = dev_alloc((void**)&t->iter_tab, words * 4);
+    if (e == hipSuccess) e = dev_alloc((void**)&t->skip_mat, mat.size() * 4);
     if (e == hipSuccess) e = hipMemcpy(t->init_tab, it.data(), words * 4, hipMemcpyHostToDevice);
     if (e == hipSuccess) e = hipMemcpy(t->iter_tab, st.data(), words * 4, hipMemcpyHostToDevice);
     if (e == hipSuccess) e = hipMemcpy(t->skip_mat, mat.data(), mat.size() * 4, hipMemcpyHostToDevice);
@@ -107,8 +118,8 @@ static const int16_t* rngtab_rand_table(RngTables* t, int iters, size_t* stride)
     int16_t* tab = nullptr;
     uint32_t* work = nullptr;
     const size_t state_bytes = (size_t)nb * 64 * 6 * 4;
-    if (hipMalloc(&tab, bytes) != hipSuccess) { (void)hipGetLastError(); return nullptr; }
-    if (hipMalloc(&work, state_bytes) != hipSuccess) { (void)hipGetLastError(); (void)hipFree(tab); return nullptr; }
+    if (dev_alloc((void**)&tab, bytes) != hipSuccess) { (void)hipGetLastError(); return nullptr; }
+    if (dev_alloc((void**)&work, state_bytes) != hipSuccess) { (void)hipGetLastError(); (void)hipFree(tab); return nullptr; }
     PmRngDev d;
     d.init_tab = t->init_tab; d.iter_tab = t->iter_tab; d.skip_mat = t->skip_mat; d.skip_weyl = t->skip_weyl; d.per_lane = t->per_lane; d.gx = gx; d.gy = gy;
     hipError_t e = hipMemcpy(work, t->iter_tab, state_bytes, hipMemcpyDeviceToDevice);
@@ -155,7 +166,7 @@ int rng_create(eppm_pm_rng** out, int w, int h, const eppm_params& p, bool alloc
     if (!alloc_work) r->rand_tab = rngtab_rand_table(r->tables, p.num_iter, &r->rand_stride);      // contexts; the stand-alone generator objects stream
     if (alloc_work) {       // (a context's states live in its slab and are set by k_pm_init_field at the start of every PatchMatch run)
         for (int k = 0; k < 2; k++)
-            for (int q = 0; q < 2; q++) HIPCHK(hipMalloc(&r->work[k][q], words * 4));
+            for (int q = 0; q < 2; q++) HIPCHK(dev_alloc((void**)&r->work[k][q], words * 4));
         HIPCHK(hipMemcpy(r->work[0][0], r->iter_tab, words * 4, hipMemcpyDeviceToDevice));
         HIPCHK(hipMemcpy(r->work[1][0], r->iter_tab, words * 4, hipMemcpyDeviceToDevice));
     }

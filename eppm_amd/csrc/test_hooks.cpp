@@ -10,6 +10,17 @@ std::atomic<int> g_opt_sweep_spec{-1};
 std::atomic<int> g_opt_no_split{0};
 std::atomic<int> g_opt_force_split{0};
 std::atomic<int> g_opt_search_pre{-1};
+std::atomic<int> g_opt_alloc_fill{-1};
+
+// "alloc_fill": the block an allocation site is about to hand out, filled with the chosen byte (api_internal.h)
+hipError_t alloc_fill(hipError_t e, void* p, size_t bytes, bool pinned)
+{
+    const int v = opt_alloc_fill();
+    if (e != hipSuccess || v < 0 || !p || !bytes) return e;
+    if (pinned) { memset(p, v, bytes); return hipSuccess; }
+    e = hipMemset(p, v, bytes);
+    return e == hipSuccess ? hipDeviceSynchronize() : e;
+}
 
 static int probe(const float* x, float* y, int n, int which)
 {
@@ -30,6 +41,11 @@ extern "C" int eppm_test_set_option(const char* name, int value)
     if (!strcmp(name, "sweep_spec")) { g_opt_sweep_spec.store(value); return EPPM_OK; }
     if (!strcmp(name, "rand_table")) { g_opt_rand_table.store(value); return EPPM_OK; }
     if (!strcmp(name, "search_pre_from")) { g_opt_search_pre.store(value); return EPPM_OK; }
+    if (!strcmp(name, "alloc_fill")) {
+        if (value < -1 || value > 255) return set_err(EPPM_ERR_ARG, "eppm_test_set_option: alloc_fill %d is neither -1 (off) nor a byte", value);
+        g_opt_alloc_fill.store(value);
+        return EPPM_OK;
+    }
     return set_err(EPPM_ERR_ARG, "eppm_test_set_option: unknown option '%s'", name);
 }
 extern "C" int eppm_probe_c2f_window(int patch_r, int* span_x, int* span_y)

@@ -35,7 +35,14 @@ extern "C" {
  * eppm_pm_random_search, which otherwise draws while it searches, reads its launch's numbers drawn ahead as well (radius 9 and 17).
  * "search_pre_from": -1 (default) a context's random searches take the two-phase form (pre-test on the centre rows, then the survivors
  * in full) from the iteration the library itself chooses (eppm_probe_search_pretest), k >= 0: from iteration k on -- beyond the last
- * iteration: never --, wherever the launch has a two-phase form at all (patch radius 9, quarter-block workgroups). */
+ * iteration: never --, wherever the launch has a two-phase form at all (patch radius 9, quarter-block workgroups).
+ * "alloc_fill" is of another kind: it selects no kernel, it poisons memory.  -1 (default) off; 0..255: every block the library allocates
+ * from then on -- a context's slab and its lazily made blocks (backward flow, interpolation, motion blur, streaming), the pinned staging
+ * buffers, the state blocks of the attachments (tracker, temporal filter, stabiliser, cut detector, correspondence map, object detector),
+ * whether fresh, taken from the cache of destroyed contexts' blocks or allocated again after that cache was emptied, and the generator
+ * tables, generator work states and the stage launchers' scratch (at every call that asks for a slot) -- is filled with that byte before its pointer is handed out (device
+ * blocks: hipMemset + hipDeviceSynchronize; pinned blocks: memset); any other value: EPPM_ERR_ARG.  Every result must be the same bits
+ * under every fill: nothing may read what nothing wrote ("Write-before-read of every allocation"; tests/test_alloc_fill_gpu.py). */
 int  eppm_test_set_option(const char* name, int value);
 /* admissible spread (max - min, pixels) of a 16x16 tile's candidate centres for which the LDS-window refine kernels stage the
  * target window; wider tiles take the per-access path inside the same launch (patch_r 9 or 17) */
