@@ -63,6 +63,11 @@ class CObjectsParams(C.Structure):
                 ("min_overlap", C.c_int)]
 
 
+class CPlateParams(C.Structure):
+    _fields_ = [("tau", C.c_float), ("iters", C.c_int), ("margin_x", C.c_int), ("margin_y", C.c_int), ("grow", C.c_int), ("accept_invalid", C.c_int),
+                ("thresh", C.c_float), ("n_max", C.c_int), ("min_count", C.c_int)]
+
+
 class CObject(C.Structure):
     _fields_ = [("id", C.c_int32), ("age", C.c_int32), ("area", C.c_int32), ("x0", C.c_int32), ("y0", C.c_int32), ("x1", C.c_int32),
                 ("y1", C.c_int32), ("n_flow", C.c_int32), ("sum_x", C.c_int64), ("sum_y", C.c_int64), ("sum_qu", C.c_int64), ("sum_qv", C.c_int64)]
@@ -132,6 +137,10 @@ SYMBOLS = [
     "eppm_objects_default_params", "eppm_objects_create", "eppm_objects_create_size", "eppm_objects_destroy", "eppm_objects_reset",
     "eppm_objects_step", "eppm_objects_step_frames", "eppm_objects_get", "eppm_objects_get_labels", "eppm_objects_get_state",
     "eppm_objects_set_state", "eppm_objects_label_host", "eppm_objects_carry_host", "eppm_objects_assign_host",
+    "eppm_plate_default_params", "eppm_plate_create", "eppm_plate_create_size", "eppm_plate_destroy", "eppm_plate_reset", "eppm_plate_canvas_dims",
+    "eppm_plate_step", "eppm_plate_step_frames", "eppm_plate_render", "eppm_plate_render_frames", "eppm_plate_get", "eppm_plate_get_device",
+    "eppm_plate_get_mask", "eppm_plate_get_path", "eppm_plate_set_path", "eppm_plate_get_state", "eppm_plate_set_state",
+    "eppm_plate_forms_host", "eppm_plate_block_host", "eppm_plate_accumulate_host", "eppm_plate_render_host",
 ]
 
 
@@ -164,8 +173,29 @@ def lib():
         L = C.CDLL(path)
         L.eppm_last_error.restype = C.c_char_p
         L.eppm_version.restype = C.c_char_p
+        _plate_signatures(L)
         _lib = L
     return _lib
+
+
+def _plate_signatures(L):
+    """argument types of eppm_plate_*: size_t and pointer arguments in the middle of long lists, so they are declared, not wrapped per call"""
+    P, I, Z, F = C.c_void_p, C.c_int, C.c_size_t, C.c_float
+    sig = {
+        "eppm_plate_default_params": [P], "eppm_plate_create": [P, P, P], "eppm_plate_create_size": [I, I, I, I, P, P], "eppm_plate_destroy": [P],
+        "eppm_plate_reset": [P, I], "eppm_plate_canvas_dims": [P, P, P], "eppm_plate_step": [P, P, P],
+        "eppm_plate_step_frames": [P, I, P, Z, P, P, I], "eppm_plate_render": [P, P, I, P, Z, P],
+        "eppm_plate_render_frames": [P, I, P, Z, P, P, P, Z, P], "eppm_plate_get": [P, I, P, Z, P], "eppm_plate_get_device": [P, I, P, Z],
+        "eppm_plate_get_mask": [P, I, P], "eppm_plate_get_path": [P, I, P], "eppm_plate_set_path": [P, I, P], "eppm_plate_get_state": [P, I, P],
+        "eppm_plate_set_state": [P, I, P], "eppm_plate_forms_host": [P, P, P, P], "eppm_plate_block_host": [P, P, I, I, P],
+        "eppm_plate_accumulate_host": [P, P, P, P, I, I, P], "eppm_plate_render_host": [P, P, I, P, P, I, I, P, P, P],
+    }
+    for name, args in sig.items():
+        fn = getattr(L, name, None)
+        if fn is None:              # a library built before the plate existed still loads (A/B runs); its plate calls fail at the call
+            continue
+        fn.argtypes = args
+        fn.restype = I
 
 
 def check(status, what=""):

@@ -4,7 +4,7 @@ import ctypes as C
 import numpy as np
 
 from .io import cmap_seed, object_record
-from ._lib import CObject, CObjectsCounts, CObjectsParams, CCMapParams, CCutParams, CCutStats, CGMotionModel, CMBlurParams, CParams, CStabParams, CTFilterParams, CTrackCounts, CTrackParams, EppmError, check, lib
+from ._lib import CObject, CObjectsCounts, CObjectsParams, CPlateParams, CCMapParams, CCutParams, CCutStats, CGMotionModel, CMBlurParams, CParams, CStabParams, CTFilterParams, CTrackCounts, CTrackParams, EppmError, check, lib
 
 uchar4 = np.dtype([("x", "u1"), ("y", "u1"), ("z", "u1"), ("w", "u1")])
 short2 = np.dtype([("x", "i2"), ("y", "i2")])
@@ -608,6 +608,165 @@ class ObjectDetector:
             pass
 
 
+def PlateParams(**kw):
+    """eppm_plate_params with the defaults of DESIGN.md section 22 (tau 1, iters 3, margin_x 0, margin_y 0, grow 2, accept_invalid 0,
+    thresh 40, n_max 64, min_count 2)."""
+    p = CPlateParams()
+    check(lib().eppm_plate_default_params(C.byref(p)), "eppm_plate_default_params")
+    for k, v in kw.items():
+        if not hasattr(p, k):
+            raise TypeError(f"unknown background-plate parameter {k}")
+        setattr(p, k, v)
+    return p
+
+
+class BackgroundPlate:
+    """The scene behind the moving objects over the pairs of a context (eppm_plate_*): per slot a canvas in the
+    coordinates of the clip's first frame that accumulates, pair by pair, what image 1 shows outside the grown motion mask, along the
+    camera path the fits compose; and image 1 with its moving objects painted out from that canvas.  ctx: an EPPM or an EPPMBatch; one
+    slot per pair of it.  Every step() works on the active pairs of the context's last compute_flow_bidirectional*.  The plate is its own
+    allocation on the context's device; close() frees it.  params: PlateParams' tau, iters, margin_x, margin_y, grow, accept_invalid,
+    thresh, n_max and min_count."""
+
+    def __init__(self, ctx, size=None, slots=1, device=0, **params):
+        """ctx None: a plate without a context, for step_frames / render_frames on caller planes (eppm_plate_create_size): size = (h, w),
+        `slots` slots."""
+        self._f = C.c_void_p()
+        self.ctx = ctx
+        self.params = PlateParams(**params)
+        if ctx is None:
+            if size is None or len(size) != 2:
+                raise EppmError("BackgroundPlate: without a context, size=(h, w) is required")
+            self.h, self.w, self.nslots = int(size[0]), int(size[1]), int(slots)
+            check(lib().eppm_plate_create_size(self.h, self.w, self.nslots, int(device), C.byref(self.params), C.byref(self._f)),
+                  "eppm_plate_create_size")
+        else:
+            check(lib().eppm_plate_create(ctx._ctx, C.byref(self.params), C.byref(self._f)), "eppm_plate_create")
+            self.h, self.w = ctx.h, ctx.w
+            self.nslots = int(lib().eppm_batch_size(ctx._ctx))
+        self.ch, self.cw = self.h + 2 * int(self.params.margin_y), self.w + 2 * int(self.params.margin_x)
+
+    def step(self, cut=None, ctx=None):
+        """One step of every active pair's slot: image 1 of the pair is accumulated, then the path advances to image 2.  cut: None, or one
+        flag per active pair (true: the pair's image 2 is the first frame of another clip; the path becomes the identity, the canvas is
+        kept).  Asynchronous on the context's stream."""
+        c = self.ctx if ctx is None else ctx
+        flags = None if cut is None else (C.c_uint8 * len(cut))(*[int(bool(x)) for x in cut])
+        if flags is not None and len(cut) != getattr(c, "n", 1):
+            raise EppmError("BackgroundPlate.step: one cut flag per active pair")
+        check(lib().eppm_plate_step(self._f, c._ctx, flags), "eppm_plate_step")
+
+    @staticmethod
+    def _path(path):
+        if path is None:
+            return None, None
+        p = np.ascontiguousarray(path, np.float64)
+        if p.shape != (6,):
+            raise EppmError("BackgroundPlate: a path is six numbers {a00, a01, a10, a11, tx, ty}")
+        return p, p.ctypes.data_as(C.c_void_p)
+
+    def step_frames(self, slot, d_rgba, pitch, d_mask, path=None, cut=False):
+        """eppm_plate_step_frames: the kernels alone for one slot on caller device planes (addresses), synchronous.  path: six float64 that
+        become the slot's path for this step, None: the slot's own."""
+        keep, ptr = self._path(path)
+        check(lib().eppm_plate_step_frames(self._f, int(slot), d_rgba, int(pitch), d_mask, ptr, int(bool(cut))), "eppm_plate_step_frames")
+
+    def render(self, slot=0, ctx=None):
+        """(image 1 of the slot's last stepped pair with its blocked pixels filled from the canvas: (h, w, 3) uint8; the fill bytes: (h, w)
+        uint8, 0 free, 1 filled, 2 blocked and not filled)."""
+        c = self.ctx if ctx is None else ctx
+        out, fill = np.empty((self.h, self.w, 3), np.uint8), np.empty((self.h, self.w), np.uint8)
+        check(lib().eppm_plate_render(self._f, c._ctx, int(slot), out.ctypes.data_as(C.c_void_p), self.w * 3, fill.ctypes.data_as(C.c_void_p)),
+              "eppm_plate_render")
+        return out, fill
+
+    def render_frames(self, slot, d_rgba, pitch, d_mask, path, d_rgba_out, out_pitch, d_fill):
+        """eppm_plate_render_frames: the render alone on caller device planes (addresses) against the slot's canvas, synchronous."""
+        keep, ptr = self._path(path)
+        check(lib().eppm_plate_render_frames(self._f, int(slot), d_rgba, int(pitch), d_mask, ptr, d_rgba_out, int(out_pitch), d_fill),
+              "eppm_plate_render_frames")
+
+    def render_frame(self, slot, frame, mask, path=None):
+        """render_frames for host planes: an (h, w, 3) uint8 frame, its (h, w) uint8 mask and its path, uploaded, rendered and read back.
+        Returns (frame with the blocked pixels filled, fill bytes)."""
+        from .stages import Dev
+        f = np.ascontiguousarray(frame, np.uint8)
+        m = np.ascontiguousarray(mask, np.uint8)
+        if f.shape != (self.h, self.w, 3) or m.shape != (self.h, self.w):
+            raise EppmError(f"BackgroundPlate.render_frame: a ({self.h},{self.w},3) frame and a ({self.h},{self.w}) mask")
+        rgba = np.zeros((self.h, self.w, 4), np.uint8)
+        rgba[..., :3] = f
+        bufs = [Dev(rgba.view(np.uint32)[..., 0]), Dev(m), Dev(shape=(self.h, self.w), dtype=np.uint32), Dev(shape=(self.h, self.w), dtype=np.uint8)]
+        try:
+            self.render_frames(slot, bufs[0].ptr, bufs[0].pitch, bufs[1].ptr, path, bufs[2].ptr, bufs[2].pitch, bufs[3].ptr)
+            out = np.ascontiguousarray(bufs[2].get()).view(np.uint8).reshape(self.h, self.w, 4)[..., :3].copy()
+            return out, bufs[3].get()
+        finally:
+            for b in bufs:
+                b.free()
+
+    def _get(self, slot, want_cov):
+        rgb = np.empty((self.ch, self.cw, 3), np.uint8)
+        cov = np.empty((self.ch, self.cw), np.uint8) if want_cov else None
+        check(lib().eppm_plate_get(self._f, int(slot), rgb.ctypes.data_as(C.c_void_p), self.cw * 3, None if cov is None else cov.ctypes.data_as(C.c_void_p)),
+              "eppm_plate_get")
+        return rgb, cov
+
+    def plate(self, slot=0):
+        """The canvas as an (h + 2*margin_y, w + 2*margin_x, 3) uint8 image; the clip's first frame sits at (margin_x, margin_y)."""
+        return self._get(slot, False)[0]
+
+    def coverage(self, slot=0):
+        """Per canvas pixel min(n, 255): how often its value has been confirmed; 0: nothing seen there."""
+        return self._get(slot, True)[1]
+
+    def get_device(self, slot, d_rgba, pitch):
+        check(lib().eppm_plate_get_device(self._f, int(slot), d_rgba, int(pitch)), "eppm_plate_get_device")
+
+    def mask(self, slot=0):
+        """(h, w) uint8: the fit's mask of the slot's last step (0 moves with the camera, 1 moves on its own, 2 not valid)."""
+        m = np.empty((self.h, self.w), np.uint8)
+        check(lib().eppm_plate_get_mask(self._f, int(slot), m.ctypes.data_as(C.c_void_p)), "eppm_plate_get_mask")
+        return m
+
+    def path(self, slot=0):
+        """The slot's camera path, frame 0 -> image 1 of the next pair: six float64 {a00, a01, a10, a11, tx, ty}."""
+        p = np.empty(6, np.float64)
+        check(lib().eppm_plate_get_path(self._f, int(slot), p.ctypes.data_as(C.c_void_p)), "eppm_plate_get_path")
+        return p
+
+    def set_path(self, slot, path):
+        keep, ptr = self._path(np.asarray(path))
+        check(lib().eppm_plate_set_path(self._f, int(slot), ptr), "eppm_plate_set_path")
+
+    def state(self, slot=0):
+        """(ch, cw, 4) float32: per canvas pixel the running mean {R, G, B} and its count n."""
+        st = np.empty((self.ch, self.cw, 4), np.float32)
+        check(lib().eppm_plate_get_state(self._f, int(slot), st.ctypes.data_as(C.c_void_p)), "eppm_plate_get_state")
+        return st
+
+    def set_state(self, slot, state):
+        st = np.ascontiguousarray(state, np.float32)
+        if st.shape != (self.ch, self.cw, 4):
+            raise EppmError(f"BackgroundPlate.set_state: a ({self.ch},{self.cw},4) float32 array")
+        check(lib().eppm_plate_set_state(self._f, int(slot), st.ctypes.data_as(C.c_void_p)), "eppm_plate_set_state")
+
+    def reset(self, slot=None):
+        """The slot is empty again (slot=None: every slot): no canvas, the path the identity."""
+        check(lib().eppm_plate_reset(self._f, -1 if slot is None else int(slot)), "eppm_plate_reset")
+
+    def close(self):
+        if self._f:
+            lib().eppm_plate_destroy(self._f)
+            self._f = C.c_void_p()
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
 def _level(level):
     """a stop level as a plain int; anything that is not an integer is refused before the library is touched"""
     if isinstance(level, (bool, np.bool_)) or not isinstance(level, (int, np.integer)):
@@ -1108,6 +1267,140 @@ def detect_objects_sequences(clips, slots=8, auto_cut=False, stop_level=None, la
         if e is not None:
             e.close()
     return (out, planes) if labels else out
+
+
+_PLATE_KEYS = ("tau", "iters", "margin_x", "margin_y", "grow", "accept_invalid", "thresh", "n_max", "min_count")
+
+
+def _plate_split(kw):
+    """the keyword arguments of background_plate(s) and remove_objects_sequence: PlateParams' go to the plate, CutDetector's to the cut detector"""
+    pl = {k: kw.pop(k) for k in _PLATE_KEYS if k in kw}
+    cut = {k: kw.pop(k) for k in ("lost_permille", "residual_max") if k in kw}
+    if kw:
+        raise TypeError(f"unknown parameter {sorted(kw)[0]}")
+    return pl, cut
+
+
+def _plate_clip(frames, auto_cut, stop_level, params, per_pair=None):
+    """one streaming context and one BackgroundPlate over a clip; per_pair(plate, k, path): called after pair k's step with the path that
+    step used.  Returns (the frames, the plate): the plate is still open, the caller closes it; the context is closed."""
+    pl_params, cut_params = _plate_split(dict(params))
+    if cut_params and not auto_cut:
+        raise TypeError("background plate: lost_permille and residual_max need auto_cut=True")
+    frames = [np.ascontiguousarray(f, np.uint8) for f in frames]
+    if len(frames) < 2:
+        raise EppmError("background plate: at least two frames")
+    h, w, _ = frames[0].shape
+    e = EPPM()
+    pl = det = None
+    try:
+        e.init(h, w)
+        e.set_temporal(True)
+        if stop_level is not None:
+            e.set_stop_level(_level(stop_level))
+        pl = BackgroundPlate(e, **pl_params)
+        if auto_cut:
+            det = CutDetector(e, **cut_params)
+        for k in range(len(frames) - 1):
+            if k == 0:
+                e.set_data(frames[0], frames[1])
+            else:
+                e.push_frame(frames[k + 1])
+            e.compute_flow_bidirectional_device()
+            path = pl.path(0) if per_pair is not None else None
+            pl.step(_auto_cut_step(e, det) if auto_cut else None)
+            if per_pair is not None:
+                per_pair(pl, k, path)
+        return frames, pl
+    except BaseException:
+        if pl is not None:
+            pl.close()
+        raise
+    finally:
+        if det is not None:
+            det.close()
+        e.close()
+
+
+def background_plate(frames, auto_cut=False, stop_level=None, **params):
+    """The background plate of a clip ((h, w, 3) uint8 frames; BackgroundPlate): one streaming context -- set_data,
+    then push_frame --, one bidirectional call on the device and one plate step per pair.  Returns (plate, coverage): the canvas as an
+    (h + 2*margin_y, w + 2*margin_x, 3) uint8 image in the coordinates of the first frame, and per pixel how often its value was
+    confirmed (0: never seen).  The last frame of the clip has no pair of its own and is not accumulated.  params: PlateParams', and with
+    auto_cut=True CutDetector's lost_permille and residual_max: after a pair the cut detector calls a cut the path starts again at the
+    identity and the canvas is kept.  stop_level: the flow's draft mode (None: full quality)."""
+    _, pl = _plate_clip(frames, auto_cut, stop_level, params)
+    try:
+        return pl.plate(0), pl.coverage(0)
+    finally:
+        pl.close()
+
+
+def remove_objects_sequence(frames, auto_cut=False, stop_level=None, **params):
+    """The frames of a clip with their moving objects painted out from the clip's background plate, in two passes over one plate.  Pass 1
+    steps the clip as background_plate does and keeps each pair's mask and path on the host; pass 2 renders every frame against the
+    FINISHED plate (BackgroundPlate.render_frame), so a frame is also filled from what only later frames reveal.  Returns (frames, fills):
+    one (h, w, 3) uint8 image and one (h, w) uint8 fill plane (0 free, 1 filled, 2 blocked and not filled) per input frame.  The last
+    frame of a clip has no pair of its own -- no mask, no path --, so it is returned unchanged with fill 0."""
+    kept = []
+    frames, pl = _plate_clip(frames, auto_cut, stop_level, params, per_pair=lambda p, k, path: kept.append((p.mask(0), path)))
+    try:
+        out, fills = [], []
+        for k, (mask, path) in enumerate(kept):
+            o, f = pl.render_frame(0, frames[k], mask, path)
+            out.append(o)
+            fills.append(f)
+        out.append(frames[-1].copy())
+        fills.append(np.zeros(frames[-1].shape[:2], np.uint8))
+        return out, fills
+    finally:
+        pl.close()
+
+
+def background_plates(clips, slots=8, auto_cut=False, stop_level=None, **params):
+    """background_plate for many clips at once: clips of one frame size and of any lengths (two frames at least) through ONE batch context
+    of min(slots, len(clips)) slots and one BackgroundPlate, on flow_sequences' schedule.  A clip's plate is read after the step of its
+    last pair; a slot that takes the next clip of the queue is reset after that step.  Returns one (plate, coverage) per clip, each what
+    background_plate(clip) returns."""
+    pl_params, cut_params = _plate_split(dict(params))
+    if cut_params and not auto_cut:
+        raise TypeError("background_plates: lost_permille and residual_max need auto_cut=True")
+    clips = [[np.ascontiguousarray(f, np.uint8) for f in clip] for clip in clips]
+    plan = _sequence_plan([len(c) for c in clips], slots)
+    h, w, _ = clips[0][0].shape
+    out = [None for _ in clips]
+    e = pl = det = None
+    try:
+        for t, step in enumerate(plan):
+            if t == 0:
+                e = EPPMBatch(h, w, len(step), params=None)
+                e.set_temporal(True)
+                if stop_level is not None:
+                    e.set_stop_level(_level(stop_level))
+                pl = BackgroundPlate(e, **pl_params)
+                if auto_cut:
+                    det = CutDetector(e, **cut_params)
+                e.set_data([(clips[c][0], clips[c][1]) for c, _, _, _ in step])
+            else:
+                e.push_frames([clips[c][f] for c, f, _, _ in step], [cut for _, _, cut, _ in step])
+            e.compute_flow_bidirectional_device()
+            flags = [cut for _, _, cut, _ in step]
+            if auto_cut:
+                flags = [a or bool(b) for a, b in zip(flags, _auto_cut_step(e, det))]
+            pl.step(flags)
+            for slot, (c, f, new_clip, keep) in enumerate(step):
+                if new_clip:
+                    pl.reset(slot)
+                elif keep and f == len(clips[c]) - 1:
+                    out[c] = (pl.plate(slot), pl.coverage(slot))
+    finally:
+        if det is not None:
+            det.close()
+        if pl is not None:
+            pl.close()
+        if e is not None:
+            e.close()
+    return out
 
 
 def stabilize_sequence(frames, params=None, tau=1.0, iters=3, smooth=0.9, temporal=True, stop_level=0, masks=False, auto_cut=False, **cut_params):

@@ -194,6 +194,21 @@ EPPM_HIDDEN int stab_device(const eppm_stab* f, int* h, int* w, int* nslots);
 // detector's private stabiliser (objects.cpp)
 EPPM_HIDDEN const uint8_t* stab_mask_device(const eppm_stab* f, size_t* slot_stride);
 
+// slot 0's device model (a GmModel; what eppm_stab_get_model copies) and the distance in bytes to the next slot's: read by the background
+// plate's private stabiliser (plate.cpp)
+EPPM_HIDDEN const char* stab_model_device(const eppm_stab* f, size_t* slot_stride);
+
+// ---- a background plate (plate.cpp) reads what a stabiliser reads of a context, and image 1 ----
+// slots slot0 .. slot0 + in.n - 1 from the input members of in (img1, mask, model); cut: NULL or one flag per pair
+EPPM_HIDDEN int plate_step_on(eppm_plate* f, eppm::PlateArgs& in, int slot0, const uint8_t* cut, hipStream_t s, eppm_ctx* timing);
+// the launcher stream of the context-less launchers (launchers_ref_abi.cpp) runs eppm_plate_step_frames and eppm_plate_render_frames
+// through these; path NULL: the slot's own
+EPPM_HIDDEN int plate_step_frames_on(eppm_plate* f, int slot, const void* d_rgba, size_t pitch, const uint8_t* d_mask, const double* path, int cut, hipStream_t s);
+EPPM_HIDDEN int plate_render_frames_on(eppm_plate* f, int slot, const void* d_rgba, size_t pitch, const uint8_t* d_mask, const double* path, void* d_out,
+                                       size_t out_pitch, uint8_t* d_fill, hipStream_t s);
+EPPM_HIDDEN int plate_device(const eppm_plate* f, int* h, int* w, int* nslots);
+EPPM_HIDDEN int plate_slot_check(const eppm_plate* f, int slot, bool need_states, const char* what);
+
 // ---- an object detector (objects.cpp) reads what a stabiliser and a temporal filter read of a context ----
 // the launcher stream of the context-less launchers (launchers_ref_abi.cpp) runs eppm_objects_step_frames through this (objects.cpp):
 // slots slot0 .. slot0 + in.n - 1 from the input members of in; cut: NULL or one flag per pair

@@ -481,6 +481,45 @@ struct ObjHeader {
 void launch_objects_label(const ObjArgs& a, hipStream_t s);       // tile, merge, flatten + areas, count, scan, number, label + records + votes
 void launch_objects_assign(const ObjArgs& a, hipStream_t s);      // the identity rule, then the carry
 
+// ---- background plates (k_plate.hip; the arithmetic: plate.h) ----
+// One step covers n pairs: pair k's inputs (image 1: RGBA words, img_pitch bytes per row; mask: h*w bytes; model: the pair's GmModel, or
+// NULL for a step without a fit) lie k * (their stride) bytes past pair 0's and feed slot slot0 + k, whose block lies (slot0 + k) *
+// slot_stride bytes past `mem`: canvas (ch*cw float4, ch = h + 2*my, cw = w + 2*mx) | two blocked planes of h*w bytes each, the dilated
+// mask of the last step and of the last render on a caller's mask (off_b: the one this launch writes or reads) | PlateRec (off_rec).  The per-slot bits travel in the kernel arguments
+// as TFilterArgs' do: empty (every canvas state counts as n = 0 and is not read) and cut (image 2 starts another clip: the path becomes
+// the identity after the step).  A render covers one slot and carries its forms in the arguments.
+struct PlateArgs {
+    const uint8_t* img1;
+    size_t img_pitch, img_stride;
+    const uint8_t* mask;
+    size_t mask_stride;
+    const char* model;
+    size_t model_stride;
+    char* mem;
+    size_t slot_stride, off_b, off_rec;
+    int h, w, ch, cw, mx, my, n, slot0;
+    int grow, accept_invalid, n_max, min_count, phase;
+    float thresh;
+    uint32_t empty[kTemporalMaxSlots / 32], cut[kTemporalMaxSlots / 32];
+};
+struct PlateRenderArgs {
+    const uint8_t* img1;
+    size_t img_pitch;
+    const char* canvas;             // the slot's ch*cw float4
+    const uint8_t* blocked;         // h*w bytes
+    uint32_t* out;
+    size_t out_pitch;               // bytes per row of out
+    uint8_t* fill;                  // h*w bytes
+    int h, w, ch, cw, mx, my, min_count, ok;
+    float inv[6];
+};
+void launch_plate_path(const PlateArgs& a, hipStream_t s);          // a.phase 0: the forms of P; 1: P advanced by the model, the identity after a cut
+void launch_plate_block(const PlateArgs& a, hipStream_t s);         // mask -> the plane at off_b
+void launch_plate_accumulate(const PlateArgs& a, hipStream_t s);
+void launch_plate_render(const PlateRenderArgs& a, hipStream_t s);
+// the canvas states as RGBA words (cw words per row) and coverage bytes
+void launch_plate_word(const char* canvas, uint32_t* words, uint8_t* cov, int ch, int cw, hipStream_t s);
+
 // ---- flow colour coding (k_color.hip) ----
 // rgba: h*w packed R | G<<8 | B<<16 (alpha 0); flow: h*w float2
 void launch_flow_to_color(uint32_t* rgba, const float* flow, int h, int w, float max_disp_x, float max_disp_y, hipStream_t s, Batch bt = kOnePair);

@@ -821,6 +821,39 @@ extern "C" int eppm_objects_step_frames(eppm_objects* f, int slot, const uint8_t
     CHK(finish());
     return objects_slot_status(f, slot, "eppm_objects_step_frames");
 }
+// ---- one background-plate step / render of one slot on caller planes, without a fit (k_plate.hip; the host forms: eppm_plate_forms_host,
+// eppm_plate_block_host, eppm_plate_accumulate_host, eppm_plate_render_host) ----
+extern "C" int eppm_plate_step_frames(eppm_plate* f, int slot, const void* d_rgba, size_t pitch, const uint8_t* d_mask, const double* path, int cut)
+{
+    if (!f || !d_rgba || !d_mask) return set_err(EPPM_ERR_ARG, "eppm_plate_step_frames: NULL argument");
+    int h, w, nslots;
+    const int device = plate_device(f, &h, &w, &nslots);
+    CHK(plate_slot_check(f, slot, false, "eppm_plate_step_frames"));
+    if (pitch < (size_t)w * 4 || (pitch & 3)) return set_err(EPPM_ERR_ARG, "eppm_plate_step_frames: bad pitch %zu", pitch);
+    std::lock_guard<std::mutex> lk(g_mu);
+    int d = 0;
+    HIPCHK(hipGetDevice(&d));
+    if (d != device) return set_err(EPPM_ERR_ARG, "eppm_plate_step_frames: the plate lives on device %d, the current device is %d", device, d);
+    CHK(plate_step_frames_on(f, slot, d_rgba, pitch, d_mask, path, cut, g_stream));
+    HIPCHK(hipStreamSynchronize(g_stream));
+    return finish();
+}
+extern "C" int eppm_plate_render_frames(eppm_plate* f, int slot, const void* d_rgba, size_t pitch, const uint8_t* d_mask, const double* path, void* d_rgba_out,
+                                        size_t out_pitch, uint8_t* d_fill)
+{
+    if (!f || !d_rgba || !d_mask || !d_rgba_out || !d_fill) return set_err(EPPM_ERR_ARG, "eppm_plate_render_frames: NULL argument");
+    int h, w, nslots;
+    const int device = plate_device(f, &h, &w, &nslots);
+    CHK(plate_slot_check(f, slot, true, "eppm_plate_render_frames"));
+    if (pitch < (size_t)w * 4 || (pitch & 3) || out_pitch < (size_t)w * 4 || (out_pitch & 3))
+        return set_err(EPPM_ERR_ARG, "eppm_plate_render_frames: bad pitch %zu / %zu", pitch, out_pitch);
+    std::lock_guard<std::mutex> lk(g_mu);
+    int d = 0;
+    HIPCHK(hipGetDevice(&d));
+    if (d != device) return set_err(EPPM_ERR_ARG, "eppm_plate_render_frames: the plate lives on device %d, the current device is %d", device, d);
+    CHK(plate_render_frames_on(f, slot, d_rgba, pitch, d_mask, path, d_rgba_out, out_pitch, d_fill, g_stream));
+    return finish();
+}
 // the C++-linkage symbol the reference's driver declares at :64 (defaults 100,100 there; the live call passes 20,20)
 void bao_cuda_convert_flow_to_colorshow(uchar4* rgbflow, float2* flow_vec, int h, int w, float max_disp_x, float max_disp_y)
 {

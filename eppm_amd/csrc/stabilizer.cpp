@@ -167,6 +167,12 @@ const uint8_t* stab_mask_device(const eppm_stab* f, size_t* slot_stride)
     return f->mask(0);
 }
 
+const char* stab_model_device(const eppm_stab* f, size_t* slot_stride)
+{
+    *slot_stride = f->stride;
+    return (const char*)f->model(0);
+}
+
 // one step of slots slot0 .. slot0 + in.n - 1 on stream s; in: the pairs' planes (the other members are filled in here); cut: NULL or one
 // flag per pair.  timing: the context whose stage-timing entries receive the stages, or NULL
 int stab_step_on(eppm_stab* f, StabArgs& in, int slot0, const uint8_t* cut, hipStream_t s, eppm_ctx* timing)

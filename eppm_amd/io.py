@@ -433,3 +433,73 @@ def objects_assign_host(labels, n, carried, prev_id, prev_age, next_id, max_obje
                                          int(n), pid.ctypes.data_as(C.c_void_p), page.ctypes.data_as(C.c_void_p), C.byref(nxt), rec),
           "eppm_objects_assign_host")
     return [int(rec[k].id) for k in range(n)], [int(rec[k].age) for k in range(n)], pid, page, int(nxt.value)
+
+
+def _plate_params(margins=(0, 0), grow=2, accept_invalid=False, thresh=40.0, n_max=64, min_count=2):
+    from ._lib import CPlateParams
+    return CPlateParams(1.0, 3, int(margins[0]), int(margins[1]), int(grow), int(bool(accept_invalid)), float(thresh), int(n_max), int(min_count))
+
+
+def _vp(a):
+    return a.ctypes.data_as(C.c_void_p)
+
+
+def plate_forms_host(path):
+    """The two displacement forms of a camera path on the host (eppm_plate_forms_host; bit-identical to the
+    kernel).  path: six float64 {a00, a01, a10, a11, tx, ty}.  Returns (fwd, inv (6 float32 each), ok)."""
+    p = np.ascontiguousarray(path, np.float64)
+    if p.shape != (6,):
+        raise ValueError("plate_forms_host: a path is six numbers")
+    fwd, inv = np.empty(6, np.float32), np.empty(6, np.float32)
+    ok = C.c_int()
+    check(lib().eppm_plate_forms_host(_vp(p), _vp(fwd), _vp(inv), C.byref(ok)), "eppm_plate_forms_host")
+    return fwd, inv, bool(ok.value)
+
+
+def plate_block_host(mask, grow=2, accept_invalid=False):
+    """The blocked plane of a motion mask on the host (eppm_plate_block_host): (h, w) uint8, 1 where a blocked byte lies within `grow`."""
+    m = np.ascontiguousarray(mask, np.uint8)
+    if m.ndim != 2:
+        raise ValueError("plate_block_host: mask (h, w)")
+    h, w = m.shape
+    p = _plate_params(grow=grow, accept_invalid=accept_invalid)
+    out = np.empty((h, w), np.uint8)
+    check(lib().eppm_plate_block_host(C.byref(p), _vp(m), h, w, _vp(out)), "eppm_plate_block_host")
+    return out
+
+
+def plate_accumulate_host(state, fwd, img1, blocked, margins=(0, 0), thresh=40.0, n_max=64):
+    """One frame accumulated into canvas states on the host (eppm_plate_accumulate_host).  state: (h + 2*my, w + 2*mx, 4) float32 {R, G, B,
+    n} (all zero: an empty canvas); fwd: 6 float32; img1: (h, w, 3) uint8; blocked: (h, w) uint8.  Returns the new states (a copy)."""
+    a = np.ascontiguousarray(img1, np.uint8)
+    b = np.ascontiguousarray(blocked, np.uint8)
+    f = np.ascontiguousarray(fwd, np.float32)
+    if a.ndim != 3 or a.shape[2] != 3 or b.shape != a.shape[:2] or f.shape != (6,):
+        raise ValueError("plate_accumulate_host: image (h, w, 3), blocked (h, w), fwd (6,)")
+    h, w, _ = a.shape
+    st = np.array(state, np.float32, order="C")
+    if st.shape != (h + 2 * int(margins[1]), w + 2 * int(margins[0]), 4):
+        raise ValueError("plate_accumulate_host: state (h + 2*my, w + 2*mx, 4)")
+    p = _plate_params(margins=margins, thresh=thresh, n_max=n_max)
+    check(lib().eppm_plate_accumulate_host(C.byref(p), _vp(f), _vp(a), _vp(b), h, w, _vp(st)), "eppm_plate_accumulate_host")
+    return st
+
+
+def plate_render_host(state, inv, ok, img1, blocked, margins=(0, 0), min_count=2):
+    """A frame with its blocked pixels filled from canvas states on the host (eppm_plate_render_host).  Returns ((h, w, 3) uint8, fill
+    (h, w) uint8: 0 free, 1 filled, 2 blocked and not filled)."""
+    a = np.ascontiguousarray(img1, np.uint8)
+    b = np.ascontiguousarray(blocked, np.uint8)
+    f = np.ascontiguousarray(inv, np.float32)
+    st = np.ascontiguousarray(state, np.float32)
+    if a.ndim != 3 or a.shape[2] != 3 or b.shape != a.shape[:2] or f.shape != (6,):
+        raise ValueError("plate_render_host: image (h, w, 3), blocked (h, w), inv (6,)")
+    h, w, _ = a.shape
+    if st.shape != (h + 2 * int(margins[1]), w + 2 * int(margins[0]), 4):
+        raise ValueError("plate_render_host: state (h + 2*my, w + 2*mx, 4)")
+    p = _plate_params(margins=margins, min_count=min_count)
+    out, fill = np.empty((h, w, 3), np.uint8), np.empty((h, w), np.uint8)
+    check(lib().eppm_plate_render_host(C.byref(p), _vp(f), int(bool(ok)), _vp(a), _vp(b), h, w, _vp(st), _vp(out), _vp(fill)),
+          "eppm_plate_render_host")
+    return out, fill
+

@@ -680,6 +680,80 @@ int  eppm_objects_carry_host(const uint8_t* labels, const float* bu, const float
 int  eppm_objects_assign_host(const eppm_objects_params* p, const uint8_t* labels, const uint8_t* carried, int h, int w, int n, int32_t* prev_id,
                               int32_t* prev_age, int32_t* next_id, eppm_object* records);
 
+/* ----------------------------------------------------------------------------------------
+ * Background plates: the scene behind the moving objects, aligned to the clip's first frame, and frames with the
+ * moving objects painted out from it.  A plate is an attachment like the stabiliser: one slot per pair, its own allocation, nothing
+ * launched for a context that never creates one.  A slot owns a canvas of (h + 2*margin_y) x (w + 2*margin_x) pixels in the coordinates of
+ * the clip's first frame (the anchor), which sits at canvas offset (margin_x, margin_y); per canvas pixel a running mean {R, G, B, n}
+ * (float4).  A step on a pair fits the camera's motion (the stabiliser's fit), dilates its mask by `grow` into a blocked plane, and
+ * accumulates IMAGE 1 of the pair: every canvas pixel whose position under the slot's camera path P (frame 0 -> image 1) lies inside the
+ * frame with no blocked tap takes the bilinear sample c: an empty state (!(n >= 1)) becomes {c, 1}; a sample within `thresh` (sum of
+ * absolute differences) of the mean joins it, n' = min(n + 1, n_max); any other lowers n by one, so a value contradicted more often than
+ * confirmed empties and is replaced.  Then P advances by the pair's model (unchanged by an invalid one).  A path with !(|det A| > 1e-6)
+ * accumulates nothing.  The render fills the blocked pixels of image 1 from the canvas: fill byte 0 = free (the image), 1 = filled (every
+ * one of the four canvas taps has n >= min_count), 2 = blocked but not filled (the image).  Whatever the inputs hold -- NaN paths, any
+ * mask bytes, any states -- nothing outside the frame or the canvas is read.  Every kernel gathers: the same bits on every run, equal to
+ * the host forms below.
+ * -------------------------------------------------------------------------------------- */
+typedef struct eppm_plate_params {
+    float tau;                   /* the fit's inlier radius in pixels (1); finite, > 0 */
+    int   iters;                 /* the fit's passes (3); 1 .. 8 */
+    int   margin_x, margin_y;    /* canvas margins (0, 0); >= 0, the canvas within 8192 x 8192 and 2^26 pixels */
+    int   grow;                  /* dilation radius of the mask (2); 0 .. 8 */
+    int   accept_invalid;        /* mask bytes other than 0 and 1 (not valid) count as free (0: they block) */
+    float thresh;                /* a sample this close to the mean confirms it (40); finite, >= 0 */
+    int   n_max;                 /* the count's cap (64); 1 .. 255 */
+    int   min_count;             /* a canvas tap fills with at least this count (2); 1 .. 255 */
+} eppm_plate_params;
+typedef struct eppm_plate eppm_plate;
+
+int  eppm_plate_default_params(eppm_plate_params* p);
+/* p NULL: the defaults.  One slot per pair of ctx (eppm_batch_size), on its device; every slot empty, its path the identity. */
+int  eppm_plate_create(eppm_ctx* ctx, const eppm_plate_params* p, eppm_plate** out);
+/* a plate without a context: nslots slots of h x w pixels (any size from 1 x 1) on `device` */
+int  eppm_plate_create_size(int h, int w, int nslots, int device, const eppm_plate_params* p, eppm_plate** out);
+int  eppm_plate_destroy(eppm_plate* plate);               /* NULL is fine */
+int  eppm_plate_reset(eppm_plate* plate, int slot);       /* the slot is empty again, its path the identity; slot < 0: every slot.  Synchronous */
+int  eppm_plate_canvas_dims(const eppm_plate* plate, int* ch, int* cw);
+/* One step of slots 0 .. active pairs - 1 on the pairs of ctx's last eppm_compute_bidirectional*, under eppm_stab_step's window, rules
+ * and error codes.  cut: NULL, or one flag per active pair; non-zero: image 2 of that pair starts another clip: image 1 is still
+ * accumulated, then the path becomes the identity and the canvas is kept (eppm_plate_reset empties it).  A fixed sequence of launches,
+ * asynchronous on the context's stream: no copy, no allocation, no host synchronisation. */
+int  eppm_plate_step(eppm_plate* plate, eppm_ctx* ctx, const uint8_t* cut);
+/* the kernels alone, without a fit, for one slot on caller device planes: image 1 (RGBA words, pitch bytes per row) and h*w mask bytes
+ * (0 free, 1 blocked, others not valid).  path6: the slot's path {a00, a01, a10, a11, tx, ty} for this step (it is stored), NULL: the
+ * slot's own; without a model the path does not advance.  On the launcher stream, synchronous. */
+int  eppm_plate_step_frames(eppm_plate* plate, int slot, const void* d_rgba, size_t pitch, const uint8_t* d_mask, const double* path6, int cut);
+/* image 1 of the last stepped pair of `slot` with its blocked pixels filled from the canvas (h*w*3 bytes, row_stride >= 3*w) and the fill
+ * bytes (h*w, or NULL); in eppm_plate_step's window.  Synchronous.  EPPM_ERR_STATE on an empty slot. */
+int  eppm_plate_render(eppm_plate* plate, eppm_ctx* ctx, int slot, uint8_t* rgb, size_t row_stride, uint8_t* fill);
+/* the render alone on caller device planes, against the slot's canvas as it is: the frame, its mask and its path (NULL: the slot's own)
+ * to h*w RGBA words (out_pitch bytes per row) and h*w fill bytes.  The slot's path is not changed.  On the launcher stream, synchronous. */
+int  eppm_plate_render_frames(eppm_plate* plate, int slot, const void* d_rgba, size_t pitch, const uint8_t* d_mask, const double* path6,
+                              void* d_rgba_out, size_t out_pitch, uint8_t* d_fill);
+/* synchronous; EPPM_ERR_STATE on an empty slot.  The canvas as ch*cw*3 bytes (row_stride >= 3*cw) and its coverage (ch*cw bytes:
+ * min(n, 255), 0 for !(n >= 1); or NULL) / as RGBA words on the device / the fit's mask of the last step (h*w bytes; EPPM_ERR_STATE when
+ * that step had no fit), for the two-pass use: step a clip keeping each pair's mask and path, then eppm_plate_render_frames every frame
+ * against the finished plate */
+int  eppm_plate_get(eppm_plate* plate, int slot, uint8_t* rgb, size_t row_stride, uint8_t* coverage);
+int  eppm_plate_get_device(eppm_plate* plate, int slot, void* d_rgba, size_t pitch);
+int  eppm_plate_get_mask(eppm_plate* plate, int slot, uint8_t* mask);
+/* synchronous.  The slot's path (six doubles; the identity for an empty slot) and its canvas states (ch*cw float4 {R, G, B, n};
+ * get_state: EPPM_ERR_STATE on an empty slot; set_state makes the slot non-empty) */
+int  eppm_plate_get_path(eppm_plate* plate, int slot, double* path6);
+int  eppm_plate_set_path(eppm_plate* plate, int slot, const double* path6);
+int  eppm_plate_get_state(eppm_plate* plate, int slot, float* state);
+int  eppm_plate_set_state(eppm_plate* plate, int slot, const float* state);
+/* host forms (no GPU needed; plain sequential code; p supplies margins, grow, accept_invalid, thresh, n_max and min_count).  forms: a
+ * path's two six-float displacement forms and whether it is valid.  block: the dilated blocked plane of a mask.  accumulate: one frame
+ * (h*w*3 bytes) into the canvas states, in place (an empty canvas is all zero).  render: the frame with its blocked pixels filled
+ * (h*w*3 bytes) and the fill bytes (or NULL). */
+int  eppm_plate_forms_host(const double* path6, float* fwd, float* inv, int* ok);
+int  eppm_plate_block_host(const eppm_plate_params* p, const uint8_t* mask, int h, int w, uint8_t* blocked);
+int  eppm_plate_accumulate_host(const eppm_plate_params* p, const float* fwd, const uint8_t* rgb, const uint8_t* blocked, int h, int w, float* state);
+int  eppm_plate_render_host(const eppm_plate_params* p, const float* inv, int ok, const uint8_t* rgb, const uint8_t* blocked, int h, int w,
+                            const float* state, uint8_t* rgb_out, uint8_t* fill);
+
 /* Per-stage device times in ms (hipEvent pairs on the context's stream), one entry per stage per
  * call since the last eppm_clear_stage_times (names repeat across calls; prepare entries first).
  * names[i] points to static strings.  Returns the number of entries written (<= max). */
@@ -690,7 +764,7 @@ int  eppm_clear_stage_times(eppm_ctx* ctx);
  * "flow_blf_bwd_L<l>", "flow_blf_bwd_final" and "fb_occlusion"; an interpolation call "interp_splat", "interp_fill" and "interp_blend"
  * (mode 1, once per group of four times); a track step "track_advance", "track_seed" and "track_compact" (mode 1; the step that seeds
  * frame 0 adds a "track_seed" before "track_advance"); a compute that starts from a temporal prior "temporal_advect" (before "patchmatch") and
- * "temporal_select" (inside it: "patchmatch" includes its time); a temporal-filter step "tfilter_step"; a stabiliser step "stab_fit" (every accumulate and solve launch) and "stab_warp"; a cut-detector step "cutdet"; a motion-blur call "mblur_pack" and "mblur_gather"; a correspondence-map step "cmap_step" and "cmap_render"; an object-detector step "objects_fit" (its stabiliser's launches), "objects_label" and "objects_assign".  Events come from a per-context pool: none is created in a steady-state step. */
+ * "temporal_select" (inside it: "patchmatch" includes its time); a temporal-filter step "tfilter_step"; a stabiliser step "stab_fit" (every accumulate and solve launch) and "stab_warp"; a cut-detector step "cutdet"; a motion-blur call "mblur_pack" and "mblur_gather"; a correspondence-map step "cmap_step" and "cmap_render"; an object-detector step "objects_fit" (its stabiliser's launches), "objects_label" and "objects_assign"; a background-plate step "plate_fit" (its stabiliser's launches), "plate_block" and "plate_accumulate", its render "plate_render".  Events come from a per-context pool: none is created in a steady-state step. */
 int  eppm_enable_stage_timing(eppm_ctx* ctx, int on);
 
 const char* eppm_last_error(void);

@@ -20,6 +20,7 @@
 #   mblur       the synthetic shutter: tools/mblur_times.py on both libraries -> mblur_times_{exact,tol}.json
 #   cmap        the correspondence map: tools/cmap_times.py on both libraries -> cmap_times_{exact,tol}.json
 #   objects     the object detector: tools/objects_times.py on both libraries -> objects_times_{exact,tol}.json
+#   plate       the background plate: tools/plate_times.py on both libraries -> plate_times_{exact,tol}.json
 #   round       everything profiles/ of a round comes from (TAG=r04_x; PMC_ONLY=1, SKIP_TESTS=1)
 set -o pipefail
 R=${GRAFT_REPO_ROOT:-$(cd "$(dirname "$0")/.." && pwd)}
@@ -150,6 +151,11 @@ objects)
   cd $R; for l in exact tol; do
     timeout -k 10 ${OBJECTS_TIMEOUT:-300} python tools/objects_times.py --lib $l ${OBJECTS_ARGS} > $O/objects_times_$l.json || exit 1
     cut -c1-400 $O/objects_times_$l.json
+  done ;;
+plate)
+  cd $R; for l in exact tol; do
+    timeout -k 10 ${PLATE_TIMEOUT:-300} python tools/plate_times.py --lib $l ${PLATE_ARGS} > $O/plate_times_$l.json || exit 1
+    cut -c1-400 $O/plate_times_$l.json
   done ;;
 inflight)
   cd $R; for S in ${INFLIGHT:-1 2 3 4 6}; do

@@ -63,6 +63,12 @@
 //                     centroid and the mean velocity in pixels per frame (nan nan without a valid vector).  --min-area N and
 //                     --max-objects N (1 .. 255) set its parameters and imply --objects.  With --auto-cut nothing is carried across a
 //                     cut: the objects after it take new ids.
+//                     --plate: every pair runs the bidirectional call followed by one step of a background plate (DESIGN.md section
+//                     22): P_plate.ppm is the scene behind the moving objects in the first frame's coordinates, with --plate-margin MX
+//                     MY on a canvas that much larger on every side (a panning camera), P_plate_cov.pgm how often each of its pixels
+//                     was confirmed (0: never seen).  --remove-objects (implies --plate): a second pass renders every frame against
+//                     the finished plate: P_ro_0000.ppm ... are the frames with their moving objects painted out; the frames, masks and
+//                     paths of the first pass are kept in host memory.  The last frame has no pair of its own and is written unchanged.
 #include <atomic>
 #include <chrono>
 #include <cstdio>
@@ -111,6 +117,8 @@ struct Options {
     bool mb_set = false;                                    // --blur-radius or --blur-taps given
     const char *pl_layer = nullptr, *pl_alpha = nullptr;    // --propagate layer.ppm alpha.ppm
     bool objects = false;                                   // --objects
+    bool plate = false, remove_objects = false;             // --plate, --remove-objects
+    int plate_mx = 0, plate_my = 0;                         // --plate-margin
     int ob_min_area = 0, ob_max = 0;                        // --min-area, --max-objects (0: the default)
 };
 
@@ -166,7 +174,8 @@ static int usage()
                     "               --sequence f0.ppm f1.ppm [f2.ppm ...] --out-prefix P [--temporal 0|1]\n"
                     "               [--denoise] [--denoise-thresh T] [--denoise-frames N] [--stabilize] [--smooth S]\n"
                     "               [--auto-cut] [--cut-lost N] [--motion-blur S] [--blur-radius R] [--blur-taps N]\n"
-                    "               [--propagate layer.ppm alpha.ppm] [--objects] [--min-area N] [--max-objects N]\n");
+                    "               [--propagate layer.ppm alpha.ppm] [--objects] [--min-area N] [--max-objects N]\n"
+                    "               [--plate] [--plate-margin MX MY] [--remove-objects]\n");
     return 2;
 }
 
@@ -202,6 +211,9 @@ static int run_sequence(const Options& o)
     eppm_cutdet* det = nullptr;
     eppm_cmap* cm = nullptr;
     eppm_objects* od = nullptr;
+    struct PlateGuard { eppm_plate* p = nullptr; ~PlateGuard() { eppm_plate_destroy(p); } } plt;          // freed on every way out
+    std::vector<std::vector<unsigned char>> ro_frames, ro_masks;          // --remove-objects: what the second pass needs of the first
+    std::vector<std::vector<double>> ro_paths;
     FILE* cuts = nullptr;
     FILE* obf = nullptr;
     auto fail = [&](const char* what) { fprintf(stderr, "%s: %s\n", what, eppm_last_error()); if (cuts) fclose(cuts); if (obf) fclose(obf); eppm_objects_destroy(od); eppm_cmap_destroy(cm); eppm_cutdet_destroy(det); eppm_stab_destroy(stab); eppm_tfilter_destroy(flt); if (ctx) eppm_destroy(ctx); return 1; };
@@ -262,6 +274,12 @@ static int run_sequence(const Options& o)
         snprintf(name, sizeof name, "%s_objects.txt", o.prefix);
         if (!(obf = fopen(name, "w"))) { fprintf(stderr, "cannot write %s\n", name); return fail("fopen"); }
     }
+    if (o.plate) {
+        eppm_plate_params pp;
+        eppm_plate_default_params(&pp);
+        pp.margin_x = o.plate_mx; pp.margin_y = o.plate_my;
+        if (eppm_plate_create(ctx, &pp, &plt.p) != EPPM_OK) return fail("eppm_plate_create");
+    }
     if (eppm_set_temporal(ctx, o.temporal) != EPPM_OK) return fail("eppm_set_temporal");
     if (eppm_set_stop_level(ctx, o.stop_level) != EPPM_OK) {
         fprintf(stderr, "--stop-level: %s\n", eppm_last_error());
@@ -282,6 +300,7 @@ static int run_sequence(const Options& o)
             eppm_destroy(ctx);
             return 1;
         }
+        if (o.remove_objects) ro_frames.push_back(cur);
         if (k == 0) {
             if (o.denoise) {
                 snprintf(name, sizeof name, "%s_dn_0000.ppm", o.prefix);
@@ -307,7 +326,7 @@ static int run_sequence(const Options& o)
         if (k == 1) { if (eppm_set_images(ctx, img[0].data(), img[1].data(), (size_t)w * 3) != EPPM_OK) return fail("eppm_set_images"); }
         else if (eppm_push_image(ctx, cur.data(), (size_t)w * 3) != EPPM_OK) return fail("eppm_push_image");
         const bool last = k + 1 == o.seq.size();
-        if (!o.denoise && !o.stabilize && !o.auto_cut && !cm && !od && !(o.mblur && last)) { if (eppm_compute(ctx, u.data(), v.data()) != EPPM_OK) return fail("eppm_compute"); }
+        if (!o.denoise && !o.stabilize && !o.auto_cut && !cm && !od && !plt.p && !(o.mblur && last)) { if (eppm_compute(ctx, u.data(), v.data()) != EPPM_OK) return fail("eppm_compute"); }
         else {
             if (eppm_compute_bidirectional(ctx, u.data(), v.data(), nullptr, nullptr, nullptr, nullptr) != EPPM_OK) return fail("eppm_compute_bidirectional");
             uint8_t cut = 0;
@@ -348,6 +367,17 @@ static int run_sequence(const Options& o)
                 if (f) ok = fclose(f) == 0 && ok;
                 if (!ok) { fprintf(stderr, "cannot write %s\n", name); return fail("write"); }
             }
+            if (plt.p) {
+                if (o.remove_objects) {              // the path that ends at this pair's image 1, before the step advances it
+                    ro_paths.emplace_back(6);
+                    if (eppm_plate_get_path(plt.p, 0, ro_paths.back().data()) != EPPM_OK) return fail("eppm_plate_get_path");
+                }
+                if (eppm_plate_step(plt.p, ctx, o.auto_cut ? &cut : nullptr) != EPPM_OK) return fail("eppm_plate_step");
+                if (o.remove_objects) {
+                    ro_masks.emplace_back((size_t)h * w);
+                    if (eppm_plate_get_mask(plt.p, 0, ro_masks.back().data()) != EPPM_OK) return fail("eppm_plate_get_mask");
+                }
+            }
             if (o.denoise && eppm_tfilter_get(flt, 0, dn.data(), (size_t)w * 3) != EPPM_OK) return fail("eppm_tfilter_get");
             if (o.stabilize && eppm_stab_get(stab, 0, st.data(), (size_t)w * 3) != EPPM_OK) return fail("eppm_stab_get");
         }
@@ -375,8 +405,51 @@ static int run_sequence(const Options& o)
         }
     }
     printf("%zu pairs, %.3f ms per pair\n", o.seq.size() - 1, total / (double)(o.seq.size() - 1));
+    if (plt.p) {
+        int ch = 0, cw = 0;
+        if (eppm_plate_canvas_dims(plt.p, &ch, &cw) != EPPM_OK) return fail("eppm_plate_canvas_dims");
+        std::vector<unsigned char> canvas((size_t)ch * cw * 3), cov((size_t)ch * cw);
+        if (eppm_plate_get(plt.p, 0, canvas.data(), (size_t)cw * 3, cov.data()) != EPPM_OK) return fail("eppm_plate_get");
+        snprintf(name, sizeof name, "%s_plate.ppm", o.prefix);
+        if (!write_ppm(name, canvas.data(), ch, cw)) { fprintf(stderr, "cannot write %s\n", name); return fail("write"); }
+        snprintf(name, sizeof name, "%s_plate_cov.pgm", o.prefix);
+        FILE* f = fopen(name, "wb");
+        bool ok = f && fprintf(f, "P5\n%d %d\n255\n", cw, ch) > 0 && fwrite(cov.data(), 1, cov.size(), f) == cov.size();
+        if (f) ok = fclose(f) == 0 && ok;
+        if (!ok) { fprintf(stderr, "cannot write %s\n", name); return fail("write"); }
+        printf("plate %dx%d -> %s_plate.ppm, %s_plate_cov.pgm\n", cw, ch, o.prefix, o.prefix);
+    }
+    if (o.remove_objects) {              // the second pass: every frame against the finished plate, on device planes of our own
+        const size_t px = (size_t)h * w;
+        void* d[4] = {nullptr, nullptr, nullptr, nullptr};          // frame (RGBA), mask, output (RGBA), fill
+        const size_t bytes[4] = {px * 4, px, px * 4, px};
+        auto release = [&]() { for (void* p : d) if (p) eppm_free_device(p); };
+        for (int j = 0; j < 4; j++)
+            if (eppm_malloc_device(&d[j], bytes[j]) != EPPM_OK) { release(); return fail("eppm_malloc_device"); }
+        std::vector<unsigned char> rgba(px * 4), out(px * 3);
+        size_t filled = 0;
+        for (size_t k = 0; k < ro_frames.size(); k++) {
+            out = ro_frames[k];
+            if (k < ro_masks.size()) {
+                for (size_t i = 0; i < px; i++) { rgba[4 * i] = out[3 * i]; rgba[4 * i + 1] = out[3 * i + 1]; rgba[4 * i + 2] = out[3 * i + 2]; rgba[4 * i + 3] = 0; }
+                if (eppm_memcpy_h2d(d[0], rgba.data(), bytes[0]) != EPPM_OK || eppm_memcpy_h2d(d[1], ro_masks[k].data(), bytes[1]) != EPPM_OK ||
+                    eppm_plate_render_frames(plt.p, 0, d[0], (size_t)w * 4, (const uint8_t*)d[1], ro_paths[k].data(), d[2], (size_t)w * 4, (uint8_t*)d[3]) != EPPM_OK ||
+                    eppm_memcpy_d2h(rgba.data(), d[2], bytes[2]) != EPPM_OK || eppm_memcpy_d2h(ro_masks[k].data(), d[3], bytes[3]) != EPPM_OK) {
+                    release();
+                    return fail("eppm_plate_render_frames");
+                }
+                for (size_t i = 0; i < px; i++) { out[3 * i] = rgba[4 * i]; out[3 * i + 1] = rgba[4 * i + 1]; out[3 * i + 2] = rgba[4 * i + 2]; filled += ro_masks[k][i] == 1; }
+            }
+            snprintf(name, sizeof name, "%s_ro_%04zu.ppm", o.prefix, k);
+            if (!write_ppm(name, out.data(), h, w)) { fprintf(stderr, "cannot write %s\n", name); release(); return fail("write"); }
+        }
+        release();
+        printf("%zu frames with %zu pixels filled from the plate -> %s_ro_0000.ppm ...\n", ro_frames.size(), filled, o.prefix);
+    }
     const bool cuts_ok = !cuts || fclose(cuts) == 0;
     const bool obf_ok = !obf || fclose(obf) == 0;
+    eppm_plate_destroy(plt.p);
+    plt.p = nullptr;
     eppm_objects_destroy(od); eppm_cmap_destroy(cm); eppm_cutdet_destroy(det);
     eppm_stab_destroy(stab);
     eppm_tfilter_destroy(flt);
@@ -462,6 +535,13 @@ int main(int argc, char** argv)
         else if (!strcmp(a, "--cut-lost")) { if (!val(&v) || v < 0 || v > 1000) return usage(); o.cut_lost = (int)v; o.auto_cut = true; }
         else if (!strcmp(a, "--propagate")) { if (i + 2 >= argc) return usage(); o.pl_layer = argv[++i]; o.pl_alpha = argv[++i]; }
         else if (!strcmp(a, "--objects")) o.objects = true;
+        else if (!strcmp(a, "--plate")) o.plate = true;
+        else if (!strcmp(a, "--remove-objects")) o.plate = o.remove_objects = true;
+        else if (!strcmp(a, "--plate-margin")) {
+            long long mx, my;
+            if (!val(&mx) || !val(&my) || mx < 0 || my < 0 || mx > 8192 || my > 8192) return usage();
+            o.plate_mx = (int)mx; o.plate_my = (int)my; o.plate = true;
+        }
         else if (!strcmp(a, "--min-area")) { if (!val(&v) || v < 1 || v > 0x7fffffff) return usage(); o.ob_min_area = (int)v; o.objects = true; }
         else if (!strcmp(a, "--max-objects")) { if (!val(&v) || v < 1 || v > 255) return usage(); o.ob_max = (int)v; o.objects = true; }
         else if (!strcmp(a, "--temporal")) { if (!val(&v) || (v != 0 && v != 1)) return usage(); o.temporal = (int)v; }
@@ -479,7 +559,7 @@ int main(int argc, char** argv)
             return usage();
         return run_sequence(o);
     }
-    if (o.denoise || o.stabilize || o.auto_cut || o.pl_layer || o.objects) return usage();     // the filter, the stabiliser, the cut detector, the map and the object detector walk a clip
+    if (o.denoise || o.stabilize || o.auto_cut || o.pl_layer || o.objects || o.plate) return usage();     // the filter, the stabiliser, the cut detector, the map and the object detector walk a clip
     if ((o.mblur && !o.mblur_file) || (o.mb_set && !o.mblur)) return usage();
     if (pos.size() == 1 || pos.size() > 3) return usage();
     if (pos.size() >= 2) { o.f1 = pos[0]; o.f2 = pos[1]; }
