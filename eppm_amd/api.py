@@ -90,10 +90,73 @@ def TrackParams(params=None, **kw):
     return p
 
 
-class Tracker:
+class _Handle:
+    """An object that owns one C handle: the attribute named by _handle, destroyed by eppm_<_prefix>_destroy."""
+    _prefix, _handle = None, "_f"
+
+    def close(self):
+        if getattr(self, self._handle, None):
+            getattr(lib(), f"eppm_{self._prefix}_destroy")(getattr(self, self._handle))
+            setattr(self, self._handle, C.c_void_p())
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
+class _SlotObject(_Handle):
+    """What the per-clip objects with one slot per pair of a context share.  A class names its C prefix
+    (eppm_<_prefix>_*) and sets self.params, an instance of its parameter struct, before _open."""
+
+    def _open(self, ctx, size, slots, device):
+        """eppm_<prefix>_create on a context, or (ctx None) eppm_<prefix>_create_size: size = (h, w), `slots` slots on `device`."""
+        self._f = C.c_void_p()
+        self.ctx = ctx
+        name = f"eppm_{self._prefix}_create"
+        if ctx is None:
+            if size is None or len(size) != 2:
+                raise EppmError(f"{type(self).__name__}: without a context, size=(h, w) is required")
+            self.h, self.w, self.nslots = int(size[0]), int(size[1]), int(slots)
+            check(getattr(lib(), name + "_size")(self.h, self.w, self.nslots, int(device), C.byref(self.params), C.byref(self._f)), name + "_size")
+            return
+        check(getattr(lib(), name)(ctx._ctx, C.byref(self.params), C.byref(self._f)), name)
+        self.h, self.w = ctx.h, ctx.w
+        self.nslots = int(lib().eppm_batch_size(ctx._ctx))
+
+    def _call(self, fn, *args):
+        check(getattr(lib(), f"eppm_{self._prefix}_{fn}")(self._f, *args), f"eppm_{self._prefix}_{fn}")
+
+    def _rgb(self, fn, slot):
+        """(h, w, 3) uint8 from eppm_<prefix>_<fn>(slot, rgb, row_stride)"""
+        rgb = np.empty((self.h, self.w, 3), np.uint8)
+        self._call(fn, int(slot), rgb.ctypes.data_as(C.c_void_p), C.c_size_t(self.w * 3))
+        return rgb
+
+
+class _ClipObject(_SlotObject):
+    """A slot object whose slots carry a state from pair to pair (every one but the cut detector): a cut restarts it, reset empties it."""
+
+    def step(self, cut=None, ctx=None):
+        """One step of every active pair's slot; cut: None, or one flag per active pair (true: the pair's image 2 is the first frame of
+        another clip; what that means for the slot: the class's description).  Asynchronous on the context's stream."""
+        c = self.ctx if ctx is None else ctx
+        flags = None if cut is None else (C.c_uint8 * len(cut))(*[int(bool(x)) for x in cut])
+        if flags is not None and len(cut) != getattr(c, "n", 1):
+            raise EppmError(f"{type(self).__name__}.step: one cut flag per active pair")
+        self._call("step", c._ctx, flags)
+
+    def reset(self, slot=None):
+        """The slot is empty again (slot=None: every slot); what its next step starts from: the class's description."""
+        self._call("reset", -1 if slot is None else int(slot))
+
+
+class Tracker(_Handle):
     """Dense point trajectories over the pairs of a context (eppm_tracker_*).  ctx: an EPPM or EPPMBatch; every
     step() advances the tracks by pair `pair` of the context's last compute_flow_bidirectional.  The tracker is its own allocation on the
     context's device; close() frees it."""
+    _prefix, _handle = "tracker", "_t"
 
     def __init__(self, ctx, pair=0, params=None, **track_params):
         self._t = C.c_void_p()
@@ -146,45 +209,18 @@ class Tracker:
         check(lib().eppm_tracker_set(self._t, len(ids), ids.ctypes.data_as(C.c_void_p), starts.ctypes.data_as(C.c_void_p),
                                      xy.ctypes.data_as(C.c_void_p), int(next_id), int(frame)), "eppm_tracker_set")
 
-    def close(self):
-        if self._t:
-            lib().eppm_tracker_destroy(self._t)
-            self._t = C.c_void_p()
 
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
-
-
-class TemporalFilter:
+class TemporalFilter(_ClipObject):
     """Motion-compensated temporal denoising over the pairs of a context (eppm_tfilter_*).  ctx: an EPPM or an
     EPPMBatch; one slot per pair of it.  Every step() moves the active pairs' slots from image 1 to image 2 of the context's last
-    compute_flow_bidirectional*.  The filter is its own allocation on the context's device; close() frees it."""
+    compute_flow_bidirectional*; an empty slot (new, or after reset()) starts from its pair's image 1.  The filter is its own allocation on
+    the context's device; close() frees it."""
+    _prefix = "tfilter"
 
     def __init__(self, ctx, thresh=40.0, n_max=8, size=None, slots=1, device=0):
         """ctx None: a filter without a context, for step_frames on caller planes (eppm_tfilter_create_size): size = (h, w), `slots` slots."""
-        self._f = C.c_void_p()
-        self.ctx = ctx
         self.params = CTFilterParams(float(thresh), int(n_max))
-        if ctx is None:
-            self.h, self.w, self.nslots = int(size[0]), int(size[1]), int(slots)
-            check(lib().eppm_tfilter_create_size(self.h, self.w, self.nslots, int(device), C.byref(self.params), C.byref(self._f)),
-                  "eppm_tfilter_create_size")
-            return
-        check(lib().eppm_tfilter_create(ctx._ctx, C.byref(self.params), C.byref(self._f)), "eppm_tfilter_create")
-        self.h, self.w = ctx.h, ctx.w
-        self.nslots = int(lib().eppm_batch_size(ctx._ctx))
-
-    def step(self, cut=None, ctx=None):
-        """One step of every active pair's slot; cut: None, or one flag per active pair (true: the pair's image 2 is the first frame of
-        another clip).  Asynchronous on the context's stream."""
-        c = self.ctx if ctx is None else ctx
-        flags = None if cut is None else (C.c_uint8 * len(cut))(*[int(bool(x)) for x in cut])
-        if flags is not None and len(cut) != getattr(c, "n", 1):
-            raise EppmError("TemporalFilter.step: one cut flag per active pair")
-        check(lib().eppm_tfilter_step(self._f, c._ctx, flags), "eppm_tfilter_step")
+        self._open(ctx, size, slots, device)
 
     def step_frames(self, slot, d_rgba1, d_rgba2, pitch, d_flow_bwd, d_occ2, cut=False):
         """eppm_tfilter_step_frames: one step of one slot on caller device planes (addresses), synchronous."""
@@ -193,9 +229,7 @@ class TemporalFilter:
 
     def frame(self, slot=0):
         """(h, w, 3) uint8: the slot's filtered frame."""
-        rgb = np.empty((self.h, self.w, 3), np.uint8)
-        check(lib().eppm_tfilter_get(self._f, int(slot), rgb.ctypes.data_as(C.c_void_p), C.c_size_t(self.w * 3)), "eppm_tfilter_get")
-        return rgb
+        return self._rgb("get", slot)
 
     def frames(self):
         """The filtered frames of the context's active pairs' slots."""
@@ -216,52 +250,18 @@ class TemporalFilter:
             raise EppmError(f"TemporalFilter.set_state: the state must be ({self.h},{self.w},4) float32")
         check(lib().eppm_tfilter_set_state(self._f, int(slot), acc.ctypes.data_as(C.c_void_p)), "eppm_tfilter_set_state")
 
-    def reset(self, slot=None):
-        """The slot is empty again (slot=None: every slot): its next step starts from its pair's image 1."""
-        check(lib().eppm_tfilter_reset(self._f, -1 if slot is None else int(slot)), "eppm_tfilter_reset")
 
-    def close(self):
-        if self._f:
-            lib().eppm_tfilter_destroy(self._f)
-            self._f = C.c_void_p()
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
-
-
-class Stabilizer:
+class Stabilizer(_ClipObject):
     """Global camera motion and video stabilisation over the pairs of a context (eppm_stab_*).  ctx: an EPPM or an
     EPPMBatch; one slot per pair of it.  Every step() fits the camera motion of the active pairs of the context's last
-    compute_flow_bidirectional*, moves the slots' paths and renders image 2 from the smoothed camera.  The stabiliser is its own allocation
-    on the context's device; close() frees it."""
+    compute_flow_bidirectional*, moves the slots' paths and renders image 2 from the smoothed camera; an empty slot (new, or after reset())
+    starts from the identity.  The stabiliser is its own allocation on the context's device; close() frees it."""
+    _prefix = "stab"
 
     def __init__(self, ctx, tau=1.0, iters=3, smooth=0.9, size=None, slots=1, device=0):
         """ctx None: a stabiliser without a context, for step_frames on caller planes (eppm_stab_create_size): size = (h, w), `slots` slots."""
-        self._f = C.c_void_p()
-        self.ctx = ctx
         self.params = CStabParams(float(tau), int(iters), float(smooth))
-        if ctx is None:
-            if size is None or len(size) != 2:
-                raise EppmError("Stabilizer: without a context, size=(h, w) is required")
-            self.h, self.w, self.nslots = int(size[0]), int(size[1]), int(slots)
-            check(lib().eppm_stab_create_size(self.h, self.w, self.nslots, int(device), C.byref(self.params), C.byref(self._f)),
-                  "eppm_stab_create_size")
-            return
-        check(lib().eppm_stab_create(ctx._ctx, C.byref(self.params), C.byref(self._f)), "eppm_stab_create")
-        self.h, self.w = ctx.h, ctx.w
-        self.nslots = int(lib().eppm_batch_size(ctx._ctx))
-
-    def step(self, cut=None, ctx=None):
-        """One step of every active pair's slot; cut: None, or one flag per active pair (true: the pair's image 2 is the first frame of
-        another clip).  Asynchronous on the context's stream."""
-        c = self.ctx if ctx is None else ctx
-        flags = None if cut is None else (C.c_uint8 * len(cut))(*[int(bool(x)) for x in cut])
-        if flags is not None and len(cut) != getattr(c, "n", 1):
-            raise EppmError("Stabilizer.step: one cut flag per active pair")
-        check(lib().eppm_stab_step(self._f, c._ctx, flags), "eppm_stab_step")
+        self._open(ctx, size, slots, device)
 
     def step_frames(self, slot, d_rgba2, pitch, d_flow, d_occ1, cut=False):
         """eppm_stab_step_frames: one step of one slot on caller device planes (addresses), synchronous."""
@@ -270,9 +270,7 @@ class Stabilizer:
 
     def frame(self, slot=0):
         """(h, w, 3) uint8: the slot's stabilised frame."""
-        rgb = np.empty((self.h, self.w, 3), np.uint8)
-        check(lib().eppm_stab_get(self._f, int(slot), rgb.ctypes.data_as(C.c_void_p), C.c_size_t(self.w * 3)), "eppm_stab_get")
-        return rgb
+        return self._rgb("get", slot)
 
     def frames(self):
         """The stabilised frames of the context's active pairs' slots."""
@@ -307,43 +305,18 @@ class Stabilizer:
             raise EppmError("Stabilizer.set_path: C and S are six numbers each")
         check(lib().eppm_stab_set_path(self._f, int(slot), p.ctypes.data_as(C.c_void_p)), "eppm_stab_set_path")
 
-    def reset(self, slot=None):
-        """The slot is empty again (slot=None: every slot): its next step starts from the identity."""
-        check(lib().eppm_stab_reset(self._f, -1 if slot is None else int(slot)), "eppm_stab_reset")
 
-    def close(self):
-        if self._f:
-            lib().eppm_stab_destroy(self._f)
-            self._f = C.c_void_p()
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
-
-
-class CutDetector:
+class CutDetector(_SlotObject):
     """Scene-cut detection from the bidirectional flow over the pairs of a context (eppm_cutdet_*).  ctx: an EPPM or
     an EPPMBatch; one slot per pair of it.  Every step() counts, for the active pairs of the context's last compute_flow_bidirectional*,
     the pixels that found no consistent partner in the other frame and decides whether the pair crosses a cut.  The detector is its own
     allocation on the context's device; close() frees it."""
+    _prefix = "cutdet"
 
     def __init__(self, ctx, lost_permille=530, residual_max=-1.0, size=None, slots=1, device=0):
         """ctx None: a detector without a context, for step_frames on caller planes (eppm_cutdet_create_size): size = (h, w), `slots` slots."""
-        self._f = C.c_void_p()
-        self.ctx = ctx
         self.params = CCutParams(int(lost_permille), float(residual_max))
-        if ctx is None:
-            if size is None or len(size) != 2:
-                raise EppmError("CutDetector: without a context, size=(h, w) is required")
-            self.h, self.w, self.nslots = int(size[0]), int(size[1]), int(slots)
-            check(lib().eppm_cutdet_create_size(self.h, self.w, self.nslots, int(device), C.byref(self.params), C.byref(self._f)),
-                  "eppm_cutdet_create_size")
-            return
-        check(lib().eppm_cutdet_create(ctx._ctx, C.byref(self.params), C.byref(self._f)), "eppm_cutdet_create")
-        self.h, self.w = ctx.h, ctx.w
-        self.nslots = int(lib().eppm_batch_size(ctx._ctx))
+        self._open(ctx, size, slots, device)
 
     def step(self, ctx=None):
         """One step of every active pair's slot.  Asynchronous on the context's stream."""
@@ -368,17 +341,6 @@ class CutDetector:
         check(lib().eppm_cutdet_cuts(self._f, n, out), "eppm_cutdet_cuts")
         return [bool(x) for x in out[:n]]
 
-    def close(self):
-        if self._f:
-            lib().eppm_cutdet_destroy(self._f)
-            self._f = C.c_void_p()
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
-
 
 def CMapParams(**kw):
     """eppm_cmap_params with the defaults of DESIGN.md section 19 (thresh 90, tear 2, use_occ 1)."""
@@ -391,35 +353,19 @@ def CMapParams(**kw):
     return p
 
 
-class CorrespondenceMap:
+class CorrespondenceMap(_ClipObject):
     """Dense correspondence maps to an anchor frame over the pairs of a context (eppm_cmap_*).  ctx: an EPPM or an
     EPPMBatch; one slot per pair of it.  Every step() moves the active pairs' slots from image 1 to image 2 of the context's last
     compute_flow_bidirectional*: map(slot)[y, x] is then the position in the slot's anchor frame that pixel (x, y) of image 2 shows, and
-    render(slot) the slot's layer composited over image 2 through that map.  The object is its own allocation on the context's device;
-    close() frees it.  params: CMapParams' thresh, tear and use_occ."""
+    render(slot) the slot's layer composited over image 2 through that map.  A step renders too; an empty slot (new, or after reset())
+    anchors on its pair's image 1, a slot whose pair is flagged as a cut on that pair's image 2.  The object is its own allocation on the
+    context's device; close() frees it.  params: CMapParams' thresh, tear and use_occ."""
+    _prefix = "cmap"
 
     def __init__(self, ctx, size=None, slots=1, device=0, **params):
         """ctx None: a map without a context, for step_frames on caller planes (eppm_cmap_create_size): size = (h, w), `slots` slots."""
-        self._f = C.c_void_p()
-        self.ctx = ctx
         self.params = CMapParams(**params)
-        if ctx is None:
-            self.h, self.w, self.nslots = int(size[0]), int(size[1]), int(slots)
-            check(lib().eppm_cmap_create_size(self.h, self.w, self.nslots, int(device), C.byref(self.params), C.byref(self._f)),
-                  "eppm_cmap_create_size")
-            return
-        check(lib().eppm_cmap_create(ctx._ctx, C.byref(self.params), C.byref(self._f)), "eppm_cmap_create")
-        self.h, self.w = ctx.h, ctx.w
-        self.nslots = int(lib().eppm_batch_size(ctx._ctx))
-
-    def step(self, cut=None, ctx=None):
-        """One step of every active pair's slot, and its render; cut: None, or one flag per active pair (true: the pair's image 2 is the
-        first frame of another clip and becomes the slot's anchor).  Asynchronous on the context's stream."""
-        c = self.ctx if ctx is None else ctx
-        flags = None if cut is None else (C.c_uint8 * len(cut))(*[int(bool(x)) for x in cut])
-        if flags is not None and len(cut) != getattr(c, "n", 1):
-            raise EppmError("CorrespondenceMap.step: one cut flag per active pair")
-        check(lib().eppm_cmap_step(self._f, c._ctx, flags), "eppm_cmap_step")
+        self._open(ctx, size, slots, device)
 
     def step_frames(self, slot, d_rgba1, d_rgba2, pitch, d_flow_bwd, d_occ2, cut=False):
         """eppm_cmap_step_frames: one step of one slot on caller device planes (addresses), synchronous."""
@@ -462,9 +408,7 @@ class CorrespondenceMap:
 
     def render(self, slot=0):
         """(h, w, 3) uint8: the slot's layer composited over its current frame through its map."""
-        rgb = np.empty((self.h, self.w, 3), np.uint8)
-        check(lib().eppm_cmap_render(self._f, int(slot), rgb.ctypes.data_as(C.c_void_p), C.c_size_t(self.w * 3)), "eppm_cmap_render")
-        return rgb
+        return self._rgb("render", slot)
 
     def render_device(self, slot, d_rgba, pitch):
         check(lib().eppm_cmap_render_device(self._f, int(slot), C.c_void_p(d_rgba), C.c_size_t(pitch)), "eppm_cmap_render_device")
@@ -475,21 +419,6 @@ class CorrespondenceMap:
         if a < 0:
             raise EppmError(f"eppm_cmap_age: {lib().eppm_last_error().decode()}")
         return a
-
-    def reset(self, slot=None):
-        """The slot is empty again (slot=None: every slot): its next step anchors on its pair's image 1."""
-        check(lib().eppm_cmap_reset(self._f, -1 if slot is None else int(slot)), "eppm_cmap_reset")
-
-    def close(self):
-        if self._f:
-            lib().eppm_cmap_destroy(self._f)
-            self._f = C.c_void_p()
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
 
 
 def ObjectsParams(**kw):
@@ -504,38 +433,20 @@ def ObjectsParams(**kw):
     return p
 
 
-class ObjectDetector:
+class ObjectDetector(_ClipObject):
     """Moving objects over the pairs of a context (eppm_objects_*): the connected components of the motion mask of
     image 1 (what moves against the camera), with a box, an area, a velocity and an id that survives from one pair to the next.  ctx: an
     EPPM or an EPPMBatch; one slot per pair of it.  Every step() works on the active pairs of the context's last
-    compute_flow_bidirectional*.  The detector is its own allocation on the context's device; close() frees it.  params: ObjectsParams'
-    tau, iters, connectivity, min_area, max_objects and min_overlap."""
+    compute_flow_bidirectional*; nothing is carried into an empty slot (new, or after reset(): the next id is 1) or across a pair flagged
+    as a cut.  The detector is its own allocation on the context's device; close() frees it.  params: ObjectsParams' tau, iters,
+    connectivity, min_area, max_objects and min_overlap."""
+    _prefix = "objects"
 
     def __init__(self, ctx, size=None, slots=1, device=0, **params):
         """ctx None: a detector without a context, for step_frames on caller planes (eppm_objects_create_size): size = (h, w), `slots`
         slots."""
-        self._f = C.c_void_p()
-        self.ctx = ctx
         self.params = ObjectsParams(**params)
-        if ctx is None:
-            if size is None or len(size) != 2:
-                raise EppmError("ObjectDetector: without a context, size=(h, w) is required")
-            self.h, self.w, self.nslots = int(size[0]), int(size[1]), int(slots)
-            check(lib().eppm_objects_create_size(self.h, self.w, self.nslots, int(device), C.byref(self.params), C.byref(self._f)),
-                  "eppm_objects_create_size")
-            return
-        check(lib().eppm_objects_create(ctx._ctx, C.byref(self.params), C.byref(self._f)), "eppm_objects_create")
-        self.h, self.w = ctx.h, ctx.w
-        self.nslots = int(lib().eppm_batch_size(ctx._ctx))
-
-    def step(self, cut=None, ctx=None):
-        """One step of every active pair's slot; cut: None, or one flag per active pair (true: the pair's image 2 is the first frame of
-        another clip, nothing is carried to it).  Asynchronous on the context's stream."""
-        c = self.ctx if ctx is None else ctx
-        flags = None if cut is None else (C.c_uint8 * len(cut))(*[int(bool(x)) for x in cut])
-        if flags is not None and len(cut) != getattr(c, "n", 1):
-            raise EppmError("ObjectDetector.step: one cut flag per active pair")
-        check(lib().eppm_objects_step(self._f, c._ctx, flags), "eppm_objects_step")
+        self._open(ctx, size, slots, device)
 
     def step_frames(self, slot, d_mask, d_flow, d_flow_bwd=None, d_occ2=None, cut=False):
         """eppm_objects_step_frames: the kernels alone for one slot on caller device planes (addresses), synchronous."""
@@ -592,21 +503,6 @@ class ObjectDetector:
         check(lib().eppm_objects_set_state(self._f, int(slot), *[x.ctypes.data_as(C.c_void_p) for x in (car, pid, page)], C.c_int32(int(next_id))),
               "eppm_objects_set_state")
 
-    def reset(self, slot=None):
-        """The slot is empty again (slot=None: every slot): nothing carried, the next id is 1."""
-        check(lib().eppm_objects_reset(self._f, -1 if slot is None else int(slot)), "eppm_objects_reset")
-
-    def close(self):
-        if self._f:
-            lib().eppm_objects_destroy(self._f)
-            self._f = C.c_void_p()
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
-
 
 def PlateParams(**kw):
     """eppm_plate_params with the defaults of DESIGN.md section 22 (tau 1, iters 3, margin_x 0, margin_y 0, grow 2, accept_invalid 0,
@@ -620,41 +516,22 @@ def PlateParams(**kw):
     return p
 
 
-class BackgroundPlate:
+class BackgroundPlate(_ClipObject):
     """The scene behind the moving objects over the pairs of a context (eppm_plate_*): per slot a canvas in the
     coordinates of the clip's first frame that accumulates, pair by pair, what image 1 shows outside the grown motion mask, along the
     camera path the fits compose; and image 1 with its moving objects painted out from that canvas.  ctx: an EPPM or an EPPMBatch; one
-    slot per pair of it.  Every step() works on the active pairs of the context's last compute_flow_bidirectional*.  The plate is its own
-    allocation on the context's device; close() frees it.  params: PlateParams' tau, iters, margin_x, margin_y, grow, accept_invalid,
-    thresh, n_max and min_count."""
+    slot per pair of it.  Every step() works on the active pairs of the context's last compute_flow_bidirectional*: image 1 of the pair is
+    accumulated, then the path advances to image 2 (a pair flagged as a cut: the path becomes the identity, the canvas is kept).  An empty
+    slot (new, or after reset()) has no canvas and the identity as its path.  The plate is its own allocation on the context's device;
+    close() frees it.  params: PlateParams' tau, iters, margin_x, margin_y, grow, accept_invalid, thresh, n_max and min_count."""
+    _prefix = "plate"
 
     def __init__(self, ctx, size=None, slots=1, device=0, **params):
         """ctx None: a plate without a context, for step_frames / render_frames on caller planes (eppm_plate_create_size): size = (h, w),
         `slots` slots."""
-        self._f = C.c_void_p()
-        self.ctx = ctx
         self.params = PlateParams(**params)
-        if ctx is None:
-            if size is None or len(size) != 2:
-                raise EppmError("BackgroundPlate: without a context, size=(h, w) is required")
-            self.h, self.w, self.nslots = int(size[0]), int(size[1]), int(slots)
-            check(lib().eppm_plate_create_size(self.h, self.w, self.nslots, int(device), C.byref(self.params), C.byref(self._f)),
-                  "eppm_plate_create_size")
-        else:
-            check(lib().eppm_plate_create(ctx._ctx, C.byref(self.params), C.byref(self._f)), "eppm_plate_create")
-            self.h, self.w = ctx.h, ctx.w
-            self.nslots = int(lib().eppm_batch_size(ctx._ctx))
+        self._open(ctx, size, slots, device)
         self.ch, self.cw = self.h + 2 * int(self.params.margin_y), self.w + 2 * int(self.params.margin_x)
-
-    def step(self, cut=None, ctx=None):
-        """One step of every active pair's slot: image 1 of the pair is accumulated, then the path advances to image 2.  cut: None, or one
-        flag per active pair (true: the pair's image 2 is the first frame of another clip; the path becomes the identity, the canvas is
-        kept).  Asynchronous on the context's stream."""
-        c = self.ctx if ctx is None else ctx
-        flags = None if cut is None else (C.c_uint8 * len(cut))(*[int(bool(x)) for x in cut])
-        if flags is not None and len(cut) != getattr(c, "n", 1):
-            raise EppmError("BackgroundPlate.step: one cut flag per active pair")
-        check(lib().eppm_plate_step(self._f, c._ctx, flags), "eppm_plate_step")
 
     @staticmethod
     def _path(path):
@@ -750,21 +627,6 @@ class BackgroundPlate:
         if st.shape != (self.ch, self.cw, 4):
             raise EppmError(f"BackgroundPlate.set_state: a ({self.ch},{self.cw},4) float32 array")
         check(lib().eppm_plate_set_state(self._f, int(slot), st.ctypes.data_as(C.c_void_p)), "eppm_plate_set_state")
-
-    def reset(self, slot=None):
-        """The slot is empty again (slot=None: every slot): no canvas, the path the identity."""
-        check(lib().eppm_plate_reset(self._f, -1 if slot is None else int(slot)), "eppm_plate_reset")
-
-    def close(self):
-        if self._f:
-            lib().eppm_plate_destroy(self._f)
-            self._f = C.c_void_p()
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
 
 
 def _level(level):

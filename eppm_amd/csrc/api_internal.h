@@ -10,8 +10,9 @@
 //   context.cpp            eppm_ctx: create / destroy / planes / stage times (the class's init), the only one of the four that reads opt_*
 //   ctx_images.cpp         set_images, push_image, prepare, the host upload of one image (the class's set_data)
 //   ctx_compute.cpp        compute in all its forms, the post-PatchMatch branch of both directions, temporal mode (the class's compute_flow)
-//   ctx_interp.cpp         frame interpolation, the synthetic shutter, the tracker's, the temporal filter's, the stabiliser's and the cut
-//                          detector's view of a context
+//   ctx_interp.cpp         frame interpolation, the synthetic shutter, the stage objects' view of a context
+//   stage_object.h/.cpp    the core of the seven per-clip stage objects (tracker.cpp, tfilter.cpp, stabilizer.cpp, cutdet.cpp, cmap.cpp,
+//                          objects.cpp, plate.cpp): one allocation and event, the hand-over between streams, shared host helpers
 //   device_api.cpp         device-memory plumbing of the ABI (malloc / memcpy / NUMA binding)
 //   launchers_ref_abi.cpp  the reference's live extern "C" stage launchers and the sub-stage entry points of the parity tests
 //   test_hooks.cpp         libeppm_hip_test.so only: include/eppm_test.h
@@ -158,68 +159,16 @@ EPPM_HIDDEN void pm_iterate(eppm::PmBatch& b, eppm_pm_rng* rng, const float* lut
 // ---- state of the context-less launchers that test_hooks.cpp and the colour entry points share (launchers_ref_abi.cpp) ----
 EPPM_HIDDEN int launcher_finish();
 
-// ---- what a tracker (tracker.cpp) reads of a context (ctx_interp.cpp, context.cpp) ----
-// the planes of one pair in the window of eppm_interpolate* (EPPM_ERR_ARG: other dimensions / device, a pair that is not active;
-// EPPM_ERR_STATE: outside the window), and the context's stream; sets the context's device current
-EPPM_HIDDEN int ctx_track_inputs(eppm_ctx* c, int pair, int h, int w, int device, const char* what, eppm::TrackIn* in, hipStream_t* s);
+// ---- what the per-clip stage objects read of a context (context.cpp); the objects' shared core: stage_object.h ----
 EPPM_HIDDEN int ctx_device(const eppm_ctx* c, int* h, int* w);             // the device; h, w: the context's size
 EPPM_HIDDEN void ctx_stage_begin(eppm_ctx* c, const char* name);           // a stage-timing entry on the context's stream (mode 1)
 EPPM_HIDDEN void ctx_stage_end(eppm_ctx* c);
-// the launcher stream of the context-less launchers (launchers_ref_abi.cpp) runs eppm_track_step_frames through this (tracker.cpp)
-EPPM_HIDDEN int tracker_step_on(eppm_tracker* t, const eppm::TrackIn& in, hipStream_t s, eppm_ctx* timing);
-EPPM_HIDDEN int tracker_device(const eppm_tracker* t, int* h, int* w);
 
-// ---- what a temporal filter (tfilter.cpp) reads of a context (ctx_interp.cpp) ----
-// the input members of *in for every active pair in the window of eppm_interpolate* (EPPM_ERR_ARG: other dimensions / device, more active
-// pairs than nslots; EPPM_ERR_STATE: outside the window), and the context's stream; sets the context's device current
-EPPM_HIDDEN int ctx_tfilter_inputs(eppm_ctx* c, int h, int w, int device, int nslots, const char* what, eppm::TFilterArgs* in, hipStream_t* s);
-// the launcher stream of the context-less launchers (launchers_ref_abi.cpp) runs eppm_tfilter_step_frames through this (tfilter.cpp):
-// slots slot0 .. slot0 + in.n - 1 from the input members of in; cut: NULL or one flag per pair
-EPPM_HIDDEN int tfilter_step_on(eppm_tfilter* f, eppm::TFilterArgs& in, int slot0, const uint8_t* cut, hipStream_t s, eppm_ctx* timing);
-EPPM_HIDDEN int tfilter_device(const eppm_tfilter* f, int* h, int* w, int* nslots);
-
-// ---- a correspondence map (cmap.cpp) reads what a temporal filter reads of a context (ctx_tfilter_inputs) ----
-// the launcher stream of the context-less launchers (launchers_ref_abi.cpp) runs eppm_cmap_step_frames through this (cmap.cpp):
-// slots slot0 .. slot0 + in.n - 1 from the input members of in, then their render; cut: NULL or one flag per pair
-EPPM_HIDDEN int cmap_step_on(eppm_cmap* f, eppm::CMapArgs& in, int slot0, const uint8_t* cut, hipStream_t s, eppm_ctx* timing);
-EPPM_HIDDEN int cmap_device(const eppm_cmap* f, int* h, int* w, int* nslots);
-
-// ---- what a stabiliser (stabilizer.cpp) reads of a context (ctx_interp.cpp) ----
-// the input members of *in (image 2, the level-0 forward flow, occ1) for every active pair, under ctx_tfilter_inputs' rules
-EPPM_HIDDEN int ctx_stab_inputs(eppm_ctx* c, int h, int w, int device, int nslots, const char* what, eppm::StabArgs* in, hipStream_t* s);
-// the launcher stream of the context-less launchers (launchers_ref_abi.cpp) runs eppm_stab_step_frames through this (stabilizer.cpp)
+// ---- the stabiliser (stabilizer.cpp) as the object detector (objects.cpp) and the background plate (plate.cpp) step their private one ----
+// slots slot0 .. slot0 + in.n - 1 on stream s from the input members of in (image 2, the level-0 forward flow, occ1); cut: NULL or one
+// flag per pair; timing: the context whose stage-timing entries receive the stages, or NULL
 EPPM_HIDDEN int stab_step_on(eppm_stab* f, eppm::StabArgs& in, int slot0, const uint8_t* cut, hipStream_t s, eppm_ctx* timing);
-EPPM_HIDDEN int stab_device(const eppm_stab* f, int* h, int* w, int* nslots);
-// slot 0's device mask plane (h*w bytes; what eppm_stab_get_mask copies) and the distance in bytes to the next slot's: read by the object
-// detector's private stabiliser (objects.cpp)
+// slot 0's device mask plane (h*w bytes; what eppm_stab_get_mask copies) and the distance in bytes to the next slot's
 EPPM_HIDDEN const uint8_t* stab_mask_device(const eppm_stab* f, size_t* slot_stride);
-
-// slot 0's device model (a GmModel; what eppm_stab_get_model copies) and the distance in bytes to the next slot's: read by the background
-// plate's private stabiliser (plate.cpp)
+// slot 0's device model (a GmModel; what eppm_stab_get_model copies) and the distance in bytes to the next slot's
 EPPM_HIDDEN const char* stab_model_device(const eppm_stab* f, size_t* slot_stride);
-
-// ---- a background plate (plate.cpp) reads what a stabiliser reads of a context, and image 1 ----
-// slots slot0 .. slot0 + in.n - 1 from the input members of in (img1, mask, model); cut: NULL or one flag per pair
-EPPM_HIDDEN int plate_step_on(eppm_plate* f, eppm::PlateArgs& in, int slot0, const uint8_t* cut, hipStream_t s, eppm_ctx* timing);
-// the launcher stream of the context-less launchers (launchers_ref_abi.cpp) runs eppm_plate_step_frames and eppm_plate_render_frames
-// through these; path NULL: the slot's own
-EPPM_HIDDEN int plate_step_frames_on(eppm_plate* f, int slot, const void* d_rgba, size_t pitch, const uint8_t* d_mask, const double* path, int cut, hipStream_t s);
-EPPM_HIDDEN int plate_render_frames_on(eppm_plate* f, int slot, const void* d_rgba, size_t pitch, const uint8_t* d_mask, const double* path, void* d_out,
-                                       size_t out_pitch, uint8_t* d_fill, hipStream_t s);
-EPPM_HIDDEN int plate_device(const eppm_plate* f, int* h, int* w, int* nslots);
-EPPM_HIDDEN int plate_slot_check(const eppm_plate* f, int slot, bool need_states, const char* what);
-
-// ---- an object detector (objects.cpp) reads what a stabiliser and a temporal filter read of a context ----
-// the launcher stream of the context-less launchers (launchers_ref_abi.cpp) runs eppm_objects_step_frames through this (objects.cpp):
-// slots slot0 .. slot0 + in.n - 1 from the input members of in; cut: NULL or one flag per pair
-EPPM_HIDDEN int objects_step_on(eppm_objects* f, eppm::ObjArgs& in, int slot0, const uint8_t* cut, hipStream_t s, eppm_ctx* timing);
-EPPM_HIDDEN int objects_device(const eppm_objects* f, int* h, int* w, int* nslots);
-// the slot's error word after the detector's last step (waits for it): EPPM_ERR_STATE if a kernel's loop hit its cap
-EPPM_HIDDEN int objects_slot_status(eppm_objects* f, int slot, const char* what);
-
-// ---- what a cut detector (cutdet.cpp) reads of a context (ctx_interp.cpp) ----
-// the input members of *in (both raw images, the level-0 backward flow, occ1 and occ2) for every active pair, under ctx_tfilter_inputs' rules
-EPPM_HIDDEN int ctx_cutdet_inputs(eppm_ctx* c, int h, int w, int device, int nslots, const char* what, eppm::CutArgs* in, hipStream_t* s);
-// the launcher stream of the context-less launchers (launchers_ref_abi.cpp) runs eppm_cutdet_step_frames through this (cutdet.cpp)
-EPPM_HIDDEN int cutdet_step_on(eppm_cutdet* f, eppm::CutArgs& in, int slot0, hipStream_t s, eppm_ctx* timing);
-EPPM_HIDDEN int cutdet_device(const eppm_cutdet* f, int* h, int* w, int* nslots);

@@ -1,24 +1,19 @@
-// cmap.cpp -- dense correspondence maps to an anchor frame: eppm_cmap, its one allocation, its step on a context's
-// pairs and its render (the kernels: k_cmap.hip), the synchronous state calls, and the host forms eppm_cmap_step_host /
+// cmap.cpp -- dense correspondence maps to an anchor frame: eppm_cmap (a stage object, stage_object.h), its step on a
+// context's pairs or on caller planes and its render (the kernels: k_cmap.hip), the synchronous state calls, and the host forms eppm_cmap_step_host /
 // eppm_cmap_render_host.  The host forms share cmap.h's per-pixel arithmetic with the kernels.
-#include "api_internal.h"
+#include "stage_object.h"
 #include "cmap.h"
 #include "gmotion.h"
 
 using namespace eppm;
 
-struct eppm_cmap {
-    int device = 0, h = 0, w = 0, nslots = 0;
+struct eppm_cmap : StageObject {        // mem: nslots blocks `stride` bytes apart: map 0 | map 1 (h*w float2 each) | anchor | frame | layer | out (h*w words each)
     eppm_cmap_params prm{};
-    char* mem = nullptr;                // nslots blocks `stride` bytes apart: map 0 | map 1 (h*w float2 each) | anchor | frame | layer | out (h*w words each)
-    size_t bytes = 0, stride = 0;
+    size_t stride = 0;
     std::vector<uint8_t> cur, empty;    // per slot: which map is current, and whether the slot has a state at all
     std::vector<uint8_t> deflayer;      // per slot: the layer is the anchor with alpha 255 (the layer plane is not read)
     std::vector<uint8_t> rendered;      // per slot: `out` is the render of the current map, frame and layer
     std::vector<int> age;               // per slot: steps since the anchor
-    hipEvent_t done = nullptr;          // recorded after every launch and copy: the synchronous calls wait for it
-    hipStream_t last = nullptr;         // the stream of the last step: a step on another stream waits for `done` first
-    size_t px() const { return (size_t)h * w; }
     char* block(int slot) const { return mem + (size_t)slot * stride; }
     float* map(int slot, int which) const { return (float*)(block(slot) + (size_t)which * px() * 8); }
     uint32_t* words(int slot, int plane) const { return (uint32_t*)(block(slot) + px() * 16 + (size_t)plane * px() * 4); }   // 0 anchor, 1 frame, 2 layer, 3 out
@@ -41,38 +36,24 @@ int cmap_size(int h, int w, const char* what)
     return EPPM_OK;
 }
 
-// the map's last launch or copy is complete (the synchronous calls read and write its planes on the null stream)
-int wait(eppm_cmap* f)
-{
-    HIPCHK(hipSetDevice(f->device));
-    HIPCHK(hipEventSynchronize(f->done));
-    return EPPM_OK;
-}
-
 int slot_check(const eppm_cmap* f, int slot, bool need_state, const char* what)
 {
-    if (slot < 0 || slot >= f->nslots) return set_err(EPPM_ERR_ARG, "%s: slot %d, the map has %d", what, slot, f->nslots);
+    CHK(stage_slot_check(f, slot, what));
     if (need_state && f->empty[slot]) return set_err(EPPM_ERR_STATE, "%s: slot %d has never been stepped", what, slot);
     return EPPM_OK;
 }
 
-void fill_args(const eppm_cmap* f, CMapArgs& a, int slot0, int n)
+void fill_args(const eppm_cmap* f, CMapArgs& a, int slot0, int n, const uint8_t* cut)
 {
     a.mem = f->mem;
     a.slot_stride = f->stride;
     a.off_anchor = f->px() * 16;
     a.h = f->h; a.w = f->w; a.n = n; a.slot0 = slot0;
     a.thresh = f->prm.thresh; a.tear = f->prm.tear; a.use_occ = f->prm.use_occ;
-    memset(a.cur, 0, sizeof(a.cur));
-    memset(a.empty, 0, sizeof(a.empty));
-    memset(a.cut, 0, sizeof(a.cut));
-    memset(a.deflayer, 0, sizeof(a.deflayer));
-    for (int k = slot0; k < slot0 + n; k++) {
-        const uint32_t bit = 1u << (k & 31);
-        if (f->cur[k]) a.cur[k >> 5] |= bit;
-        if (f->empty[k]) a.empty[k >> 5] |= bit;
-        if (f->deflayer[k]) a.deflayer[k >> 5] |= bit;
-    }
+    slot_mask(a.cur, f->cur.data() + slot0, slot0, n);
+    slot_mask(a.empty, f->empty.data() + slot0, slot0, n);
+    slot_mask(a.deflayer, f->deflayer.data() + slot0, slot0, n);
+    slot_mask(a.cut, cut, slot0, n);
 }
 
 // `out` of one slot is its render: a launch on the stream of the last step, behind it, if something changed since the last one
@@ -81,10 +62,10 @@ int render_slot(eppm_cmap* f, int slot)
     HIPCHK(hipSetDevice(f->device));
     if (f->rendered[slot]) return EPPM_OK;
     CMapArgs a{};
-    fill_args(f, a, slot, 1);
+    fill_args(f, a, slot, 1, nullptr);
+    CHK(stage_enter(f, f->last));
     launch_cmap_render(a, f->last);
-    HIPCHK(hipGetLastError());
-    HIPCHK(hipEventRecord(f->done, f->last));
+    CHK(stage_leave(f, f->last));
     f->rendered[slot] = 1;
     return EPPM_OK;
 }
@@ -120,34 +101,22 @@ static int cmap_new(int device, int h, int w, int nslots, const eppm_cmap_params
     const eppm_cmap_params* p = in ? in : &def;
     CHK(cmap_params(p, "eppm_cmap_create"));
     CHK(cmap_size(h, w, "eppm_cmap_create"));
-    if (nslots < 1 || nslots > kTemporalMaxSlots) return set_err(EPPM_ERR_ARG, "eppm_cmap_create: %d slots outside [1, %d]", nslots, kTemporalMaxSlots);
-    HIPCHK(hipSetDevice(device));
     eppm_cmap* f = new eppm_cmap;
+    f->noun = "map";
     f->device = device; f->h = h; f->w = w; f->nslots = nslots;
     f->prm = *p;
-    f->stride = (f->px() * 32 + 255) & ~(size_t)255;
+    f->stride = up256(f->px() * 32);
     f->bytes = f->stride * nslots;
+    const int rc = stage_open(f, "eppm_cmap_create");
+    if (rc != EPPM_OK) {
+        delete f;
+        return rc;
+    }
     f->cur.assign(nslots, 0);
     f->empty.assign(nslots, 1);
     f->deflayer.assign(nslots, 1);
     f->rendered.assign(nslots, 0);
     f->age.assign(nslots, 0);
-    hipError_t e = cache_alloc((void**)&f->mem, f->bytes, false, device);
-    if (e != hipSuccess) {
-        (void)hipGetLastError();
-        const size_t bytes = f->bytes;
-        delete f;
-        return set_err(EPPM_ERR_HIP, "hipMalloc of %zu bytes (correspondence map) failed: %s", bytes, hipGetErrorString(e));
-    }
-    e = hipEventCreateWithFlags(&f->done, hipEventDisableTiming);
-    if (e == hipSuccess) e = hipEventRecord(f->done, nullptr);
-    if (e != hipSuccess) {
-        (void)hipGetLastError();
-        if (f->done) (void)hipEventDestroy(f->done);
-        cache_free(f->mem, f->bytes, false, device);
-        delete f;
-        return set_err(EPPM_ERR_HIP, "eppm_cmap_create: %s", hipGetErrorString(e));
-    }
     *out = f;
     return EPPM_OK;
 }
@@ -171,10 +140,7 @@ extern "C" int eppm_cmap_create_size(int h, int w, int nslots, int device, const
 extern "C" int eppm_cmap_destroy(eppm_cmap* f)
 {
     if (!f) return EPPM_OK;
-    (void)hipSetDevice(f->device);
-    (void)hipEventSynchronize(f->done);
-    (void)hipEventDestroy(f->done);
-    cache_free(f->mem, f->bytes, false, f->device);
+    stage_close(f);
     delete f;
     return EPPM_OK;
 }
@@ -182,7 +148,7 @@ extern "C" int eppm_cmap_destroy(eppm_cmap* f)
 extern "C" int eppm_cmap_reset(eppm_cmap* f, int slot)
 {
     if (!f) return set_err(EPPM_ERR_ARG, "eppm_cmap_reset: NULL map");
-    if (slot >= f->nslots) return set_err(EPPM_ERR_ARG, "eppm_cmap_reset: slot %d, the map has %d", slot, f->nslots);
+    if (slot >= 0) CHK(stage_slot_check(f, slot, "eppm_cmap_reset"));
     for (int k = 0; k < f->nslots; k++)
         if (slot < 0 || k == slot) {
             f->empty[k] = 1;
@@ -192,26 +158,17 @@ extern "C" int eppm_cmap_reset(eppm_cmap* f, int slot)
     return EPPM_OK;
 }
 
-int cmap_device(const eppm_cmap* f, int* h, int* w, int* nslots)
-{
-    *h = f->h;
-    *w = f->w;
-    *nslots = f->nslots;
-    return f->device;
-}
-
 // one step of slots slot0 .. slot0 + in.n - 1 on stream s, and their render; in: the pairs' planes (the other members are filled in
 // here); cut: NULL or one flag per pair.  timing: the context whose stage-timing entries receive the stages, or NULL
-int cmap_step_on(eppm_cmap* f, CMapArgs& in, int slot0, const uint8_t* cut, hipStream_t s, eppm_ctx* timing)
+static int step_on(eppm_cmap* f, CMapArgs& in, int slot0, const uint8_t* cut, hipStream_t s, eppm_ctx* timing)
 {
     const int n = in.n;
-    fill_args(f, in, slot0, n);
-    for (int k = slot0; k < slot0 + n; k++)
-        if (cut && cut[k - slot0]) in.cut[k >> 5] |= 1u << (k & 31);
-    if (s != f->last) HIPCHK(hipStreamWaitEvent(s, f->done, 0));
-    if (timing) ctx_stage_begin(timing, "cmap_step");
-    launch_cmap_step(in, s);
-    if (timing) ctx_stage_end(timing);
+    fill_args(f, in, slot0, n, cut);
+    CHK(stage_enter(f, s));
+    {
+        StageTimer t(timing, "cmap_step");
+        launch_cmap_step(in, s);
+    }
     HIPCHK(hipGetLastError());
     for (int k = slot0; k < slot0 + n; k++) {
         const bool c = cut && cut[k - slot0];
@@ -220,28 +177,43 @@ int cmap_step_on(eppm_cmap* f, CMapArgs& in, int slot0, const uint8_t* cut, hipS
         f->age[k] = c ? 0 : f->age[k] + 1;
         f->rendered[k] = 1;
     }
-    fill_args(f, in, slot0, n);         // the render reads the map the step wrote
-    if (timing) ctx_stage_begin(timing, "cmap_render");
-    launch_cmap_render(in, s);
-    if (timing) ctx_stage_end(timing);
-    HIPCHK(hipGetLastError());
-    HIPCHK(hipEventRecord(f->done, s));
-    f->last = s;
-    return EPPM_OK;
+    fill_args(f, in, slot0, n, nullptr);    // the render reads the map the step wrote
+    {
+        StageTimer t(timing, "cmap_render");
+        launch_cmap_render(in, s);
+    }
+    return stage_leave(f, s);
 }
 
 extern "C" int eppm_cmap_step(eppm_cmap* f, eppm_ctx* ctx, const uint8_t* cut)
 {
     if (!f || !ctx) return set_err(EPPM_ERR_ARG, "eppm_cmap_step: NULL argument");
-    TFilterArgs t{};                    // the temporal filter's view of a context is this step's: both raw frames, the backward flow, occ2
+    CtxPlanes c;
     hipStream_t s;
-    CHK(ctx_tfilter_inputs(ctx, f->h, f->w, f->device, f->nslots, "eppm_cmap_step", &t, &s));
+    CHK(ctx_stage_inputs(ctx, f, "eppm_cmap_step", &c, &s));
     CMapArgs in{};
-    in.img1 = t.img1; in.img2 = t.img2; in.img_pitch = t.img_pitch; in.img_stride = t.img_stride;
-    in.bwd = t.bwd; in.bwd_stride = t.bwd_stride;
-    in.occ2 = t.occ2; in.occ_stride = t.occ_stride;
-    in.n = t.n;
-    return cmap_step_on(f, in, 0, cut, s, ctx);
+    in.img1 = c.img1; in.img2 = c.img2; in.img_pitch = c.img_pitch; in.img_stride = c.img_stride;
+    in.bwd = c.bwd; in.bwd_stride = c.bwd_stride;
+    in.occ2 = c.occ2; in.occ_stride = c.occ_stride;
+    in.n = c.n;
+    return step_on(f, in, 0, cut, s, ctx);
+}
+
+// one step of one slot on caller planes, on the launcher stream
+extern "C" int eppm_cmap_step_frames(eppm_cmap* f, int slot, const void* d_rgba1, const void* d_rgba2, size_t pitch, const eppm_float2* d_flow_bwd,
+                                     const uint8_t* d_occ2, int cut)
+{
+    if (!f || !d_rgba1 || !d_rgba2 || !d_flow_bwd || !d_occ2) return set_err(EPPM_ERR_ARG, "eppm_cmap_step_frames: NULL argument");
+    CHK(stage_slot_check(f, slot, "eppm_cmap_step_frames"));
+    if (bad_pitch(pitch, f->w)) return set_err(EPPM_ERR_ARG, "eppm_cmap_step_frames: bad pitch %zu", pitch);
+    return launcher_run(f, "eppm_cmap_step_frames", [&](hipStream_t s) {
+        CMapArgs in{};
+        in.img1 = (const uint8_t*)d_rgba1; in.img2 = (const uint8_t*)d_rgba2; in.img_pitch = pitch;
+        in.bwd = (const float*)d_flow_bwd; in.occ2 = d_occ2;
+        in.n = 1;
+        const uint8_t c = cut != 0;
+        return step_on(f, in, slot, &c, s, nullptr);
+    });
 }
 
 extern "C" int eppm_cmap_age(eppm_cmap* f, int slot)
@@ -258,7 +230,7 @@ extern "C" int eppm_cmap_get_state(eppm_cmap* f, int slot, float* xy)
 {
     if (!f || !xy) return set_err(EPPM_ERR_ARG, "eppm_cmap_get_state: NULL argument");
     CHK(slot_check(f, slot, true, "eppm_cmap_get_state"));
-    CHK(wait(f));
+    CHK(stage_wait(f));
     HIPCHK(hipMemcpy(xy, f->map(slot, f->cur[slot]), f->px() * 8, hipMemcpyDeviceToHost));
     return EPPM_OK;
 }
@@ -268,15 +240,13 @@ extern "C" int eppm_cmap_set_state(eppm_cmap* f, int slot, const float* xy, cons
     if (!f || !xy || !anchor_rgb) return set_err(EPPM_ERR_ARG, "eppm_cmap_set_state: NULL argument");
     CHK(slot_check(f, slot, false, "eppm_cmap_set_state"));
     if (row_stride < (size_t)f->w * 3) return set_err(EPPM_ERR_ARG, "eppm_cmap_set_state: row_stride %zu < 3*w", row_stride);
-    CHK(wait(f));
+    CHK(stage_wait(f));
     std::vector<uint32_t> words;
     pack_words(words, anchor_rgb, row_stride, f->h, f->w, 3);
     HIPCHK(hipMemcpy(f->map(slot, f->cur[slot]), xy, f->px() * 8, hipMemcpyHostToDevice));
     HIPCHK(hipMemcpy(f->words(slot, 0), words.data(), f->px() * 4, hipMemcpyHostToDevice));
     HIPCHK(hipMemcpy(f->words(slot, 1), words.data(), f->px() * 4, hipMemcpyHostToDevice));
-    HIPCHK(hipStreamSynchronize(nullptr));
-    HIPCHK(hipEventRecord(f->done, nullptr));
-    f->last = nullptr;
+    CHK(stage_settle(f));
     f->empty[slot] = 0;
     f->rendered[slot] = 0;
     f->age[slot] = 0;
@@ -293,13 +263,11 @@ extern "C" int eppm_cmap_set_layer(eppm_cmap* f, int slot, const uint8_t* rgba, 
         return EPPM_OK;
     }
     if (row_stride < (size_t)f->w * 4) return set_err(EPPM_ERR_ARG, "eppm_cmap_set_layer: row_stride %zu < 4*w", row_stride);
-    CHK(wait(f));
+    CHK(stage_wait(f));
     std::vector<uint32_t> words;
     pack_words(words, rgba, row_stride, f->h, f->w, 4);
     HIPCHK(hipMemcpy(f->words(slot, 2), words.data(), f->px() * 4, hipMemcpyHostToDevice));
-    HIPCHK(hipStreamSynchronize(nullptr));
-    HIPCHK(hipEventRecord(f->done, nullptr));
-    f->last = nullptr;
+    CHK(stage_settle(f));
     f->deflayer[slot] = 0;
     f->rendered[slot] = 0;
     return EPPM_OK;
@@ -311,29 +279,16 @@ extern "C" int eppm_cmap_render(eppm_cmap* f, int slot, uint8_t* rgb, size_t row
     CHK(slot_check(f, slot, true, "eppm_cmap_render"));
     if (row_stride < (size_t)f->w * 3) return set_err(EPPM_ERR_ARG, "eppm_cmap_render: row_stride %zu < 3*w", row_stride);
     CHK(render_slot(f, slot));
-    CHK(wait(f));
-    std::vector<uint32_t> words(f->px());
-    HIPCHK(hipMemcpy(words.data(), f->words(slot, 3), f->px() * 4, hipMemcpyDeviceToHost));
-    for (int y = 0; y < f->h; y++) {
-        uint8_t* o = rgb + (size_t)y * row_stride;
-        const uint32_t* q = words.data() + (size_t)y * f->w;
-        for (int x = 0; x < f->w; x++) {
-            o[3 * x] = (uint8_t)q[x]; o[3 * x + 1] = (uint8_t)(q[x] >> 8); o[3 * x + 2] = (uint8_t)(q[x] >> 16);
-        }
-    }
-    return EPPM_OK;
+    return stage_get_rgb(f, f->words(slot, 3), f->h, f->w, rgb, row_stride);
 }
 
 extern "C" int eppm_cmap_render_device(eppm_cmap* f, int slot, void* d_rgba, size_t pitch)
 {
     if (!f || !d_rgba) return set_err(EPPM_ERR_ARG, "eppm_cmap_render_device: NULL argument");
     CHK(slot_check(f, slot, true, "eppm_cmap_render_device"));
-    if (pitch < (size_t)f->w * 4 || (pitch & 3)) return set_err(EPPM_ERR_ARG, "eppm_cmap_render_device: bad pitch %zu", pitch);
+    if (bad_pitch(pitch, f->w)) return set_err(EPPM_ERR_ARG, "eppm_cmap_render_device: bad pitch %zu", pitch);
     CHK(render_slot(f, slot));
-    // on the stream of the last step, behind it; the next step on any stream waits for the copy
-    HIPCHK(hipMemcpy2DAsync(d_rgba, pitch, f->words(slot, 3), (size_t)f->w * 4, (size_t)f->w * 4, f->h, hipMemcpyDeviceToDevice, f->last));
-    HIPCHK(hipEventRecord(f->done, f->last));
-    return EPPM_OK;
+    return stage_get_rgba_device(f, f->words(slot, 3), f->h, f->w, d_rgba, pitch);
 }
 
 // ---- host forms: the same step and render as sequential loops ----

@@ -1,6 +1,7 @@
-// ctx_interp.cpp -- what reads the results of a context's (context.h) last call: frame interpolation, the synthetic shutter, the tracker,
-// the temporal filter, the stabiliser and the cut detector.
+// ctx_interp.cpp -- what reads the results of a context's (context.h) last call: frame interpolation, the synthetic shutter, and the one
+// view of a context that the seven per-clip stage objects share (stage_object.h).
 #include "context.h"
+#include "stage_object.h"
 #include "interp.h"
 #include "mblur.h"
 
@@ -104,7 +105,7 @@ extern "C" int eppm_interpolate_device(eppm_ctx* c, int nt, const float* t, void
     if (!d_rgba) return set_err(EPPM_ERR_ARG, "eppm_interpolate_device: NULL d_rgba");
     for (int k = 0; k < nt; k++)
         if (!d_rgba[k]) return set_err(EPPM_ERR_ARG, "eppm_interpolate_device: NULL d_rgba[%d]", k);
-    if (pitch < (size_t)c->w * 4 || (pitch & 3)) return set_err(EPPM_ERR_ARG, "eppm_interpolate_device: bad pitch %zu", pitch);
+    if (bad_pitch(pitch, c->w)) return set_err(EPPM_ERR_ARG, "eppm_interpolate_device: bad pitch %zu", pitch);
     HIPCHK(hipSetDevice(c->device));
     CHK(itp_alloc(c));
     for (int k0 = 0; k0 < nt; k0 += kInterpChunk)
@@ -206,102 +207,38 @@ extern "C" int eppm_motion_blur_device(eppm_ctx* c, const eppm_mblur_params* p, 
     eppm_mblur_params prm;
     CHK(mblur_check(c, "eppm_motion_blur_device", p, frame, &prm));
     if (!d_rgba) return set_err(EPPM_ERR_ARG, "eppm_motion_blur_device: NULL d_rgba");
-    if (pitch < (size_t)c->w * 4 || (pitch & 3)) return set_err(EPPM_ERR_ARG, "eppm_motion_blur_device: bad pitch %zu", pitch);
+    if (bad_pitch(pitch, c->w)) return set_err(EPPM_ERR_ARG, "eppm_motion_blur_device: bad pitch %zu", pitch);
     HIPCHK(hipSetDevice(c->device));
     CHK(mbl_alloc(c));
     return mblur_run(c, prm, frame, 1, d_rgba, pitch);
 }
 
-// ---- dense point trajectories (tracker.cpp): the raw frames, the level-0 forward flow and the level-0 backward flow
-// of one pair, in the window of eppm_interpolate* ----
+// ---- the per-clip stage objects (stage_object.h): what the tracker, the temporal filter, the stabiliser, the cut
+// detector, the correspondence map, the object detector and the background plate read of a context, in the window of eppm_interpolate* ----
 
-int ctx_track_inputs(eppm_ctx* c, int pair, int h, int w, int device, const char* what, TrackIn* in, hipStream_t* s)
+int ctx_stage_inputs(eppm_ctx* c, const StageObject* o, const char* what, CtxPlanes* in, hipStream_t* s, const int* pair)
 {
-    if (c->h != h || c->w != w || c->device != device)
-        return set_err(EPPM_ERR_ARG, "%s: the tracker is %dx%d on device %d, the context %dx%d on device %d", what, w, h, device, c->w, c->h, c->device);
-    if (pair < 0 || pair >= c->n_active) return set_err(EPPM_ERR_ARG, "%s: pair %d, the context has %d active", what, pair, c->n_active);
+    if (c->h != o->h || c->w != o->w || c->device != o->device)
+        return set_err(EPPM_ERR_ARG, "%s: the %s is %dx%d on device %d, the context %dx%d on device %d", what, o->noun, o->w, o->h, o->device, c->w, c->h, c->device);
+    if (!pair && c->n_active > o->nslots)
+        return set_err(EPPM_ERR_ARG, "%s: the context has %d active pairs, the %s %d slots", what, c->n_active, o->noun, o->nslots);
+    if (pair && (*pair < 0 || *pair >= c->n_active)) return set_err(EPPM_ERR_ARG, "%s: pair %d, the context has %d active", what, *pair, c->n_active);
     if (c->flow_pending) return set_err(EPPM_ERR_STATE, "%s: an eppm_compute_begin is pending", what);
     if (!c->have_bwd || !c->bwd_images) return set_err(EPPM_ERR_STATE, "%s: needs a bidirectional call on the current images", what);
     HIPCHK(hipSetDevice(c->device));
-    in->img1 = (const uint8_t*)c->of_pair(c->raw1, pair);
-    in->img2 = (const uint8_t*)c->of_pair(c->raw2, pair);
-    in->pitch = c->raw_pitch;
-    in->fwd = c->of_pair(c->flow[0], pair);
-    in->bwd = c->of_bwd_pair(c->bflow[0], pair);
-    in->h = c->h;
-    in->w = c->w;
-    *s = c->stream;
-    return EPPM_OK;
-}
-
-// ---- motion-compensated temporal filter (tfilter.cpp): the raw frames, the level-0 backward flow and occ2 of every
-// active pair, in the window of eppm_interpolate* ----
-
-int ctx_tfilter_inputs(eppm_ctx* c, int h, int w, int device, int nslots, const char* what, TFilterArgs* in, hipStream_t* s)
-{
-    if (c->h != h || c->w != w || c->device != device)
-        return set_err(EPPM_ERR_ARG, "%s: the filter is %dx%d on device %d, the context %dx%d on device %d", what, w, h, device, c->w, c->h, c->device);
-    if (c->n_active > nslots) return set_err(EPPM_ERR_ARG, "%s: the context has %d active pairs, the filter %d slots", what, c->n_active, nslots);
-    if (c->flow_pending) return set_err(EPPM_ERR_STATE, "%s: an eppm_compute_begin is pending", what);
-    if (!c->have_bwd || !c->bwd_images) return set_err(EPPM_ERR_STATE, "%s: needs a bidirectional call on the current images", what);
-    HIPCHK(hipSetDevice(c->device));
-    in->img1 = (const uint8_t*)c->raw1;
-    in->img2 = (const uint8_t*)c->raw2;
+    const int k = pair ? *pair : 0;
+    in->img1 = (const uint8_t*)c->of_pair(c->raw1, k);
+    in->img2 = (const uint8_t*)c->of_pair(c->raw2, k);
     in->img_pitch = c->raw_pitch;
     in->img_stride = c->stride;
-    in->bwd = c->bflow[0];
-    in->bwd_stride = c->bwd_stride;
-    in->occ2 = c->occ2;
-    in->occ_stride = c->bwd_stride;
-    in->n = c->n_active;
-    *s = c->stream;
-    return EPPM_OK;
-}
-
-// ---- global camera motion and stabilisation (stabilizer.cpp): the raw image 2, the level-0 forward flow and occ1 of
-// every active pair, in the window of eppm_interpolate* ----
-
-int ctx_stab_inputs(eppm_ctx* c, int h, int w, int device, int nslots, const char* what, StabArgs* in, hipStream_t* s)
-{
-    if (c->h != h || c->w != w || c->device != device)
-        return set_err(EPPM_ERR_ARG, "%s: the stabiliser is %dx%d on device %d, the context %dx%d on device %d", what, w, h, device, c->w, c->h, c->device);
-    if (c->n_active > nslots) return set_err(EPPM_ERR_ARG, "%s: the context has %d active pairs, the stabiliser %d slots", what, c->n_active, nslots);
-    if (c->flow_pending) return set_err(EPPM_ERR_STATE, "%s: an eppm_compute_begin is pending", what);
-    if (!c->have_bwd || !c->bwd_images) return set_err(EPPM_ERR_STATE, "%s: needs a bidirectional call on the current images", what);
-    HIPCHK(hipSetDevice(c->device));
-    in->img2 = (const uint8_t*)c->raw2;
-    in->img_pitch = c->raw_pitch;
-    in->img_stride = c->stride;
-    in->fwd = c->flow[0];
+    in->fwd = c->of_pair(c->flow[0], k);
     in->fwd_stride = c->stride;
-    in->occ1 = c->occ1;
-    in->occ_stride = c->bwd_stride;
-    in->n = c->n_active;
-    *s = c->stream;
-    return EPPM_OK;
-}
-
-// ---- scene-cut detection (cutdet.cpp): both raw images, the level-0 backward flow and both masks of every active
-// pair, in the window of eppm_interpolate* ----
-
-int ctx_cutdet_inputs(eppm_ctx* c, int h, int w, int device, int nslots, const char* what, CutArgs* in, hipStream_t* s)
-{
-    if (c->h != h || c->w != w || c->device != device)
-        return set_err(EPPM_ERR_ARG, "%s: the detector is %dx%d on device %d, the context %dx%d on device %d", what, w, h, device, c->w, c->h, c->device);
-    if (c->n_active > nslots) return set_err(EPPM_ERR_ARG, "%s: the context has %d active pairs, the detector %d slots", what, c->n_active, nslots);
-    if (c->flow_pending) return set_err(EPPM_ERR_STATE, "%s: an eppm_compute_begin is pending", what);
-    if (!c->have_bwd || !c->bwd_images) return set_err(EPPM_ERR_STATE, "%s: needs a bidirectional call on the current images", what);
-    HIPCHK(hipSetDevice(c->device));
-    in->img1 = (const uint8_t*)c->raw1;
-    in->img2 = (const uint8_t*)c->raw2;
-    in->img_pitch = c->raw_pitch;
-    in->img_stride = c->stride;
-    in->bwd = c->bflow[0];
+    in->bwd = c->of_bwd_pair(c->bflow[0], k);
     in->bwd_stride = c->bwd_stride;
-    in->occ1 = c->occ1;
-    in->occ2 = c->occ2;
+    in->occ1 = c->of_bwd_pair(c->occ1, k);
+    in->occ2 = c->of_bwd_pair(c->occ2, k);
     in->occ_stride = c->bwd_stride;
-    in->n = c->n_active;
+    in->n = pair ? 1 : c->n_active;
     *s = c->stream;
     return EPPM_OK;
 }

@@ -1,7 +1,7 @@
-// cutdet.cpp -- scene-cut detection from the bidirectional flow: eppm_cutdet, its one allocation, its step on a
-// context's pairs (the kernels: k_cutdet.hip), the synchronous getters, and the host form eppm_cutdet_host.  The host form shares cutdet.h's
+// cutdet.cpp -- scene-cut detection from the bidirectional flow: eppm_cutdet (a stage object, stage_object.h), its
+// step on a context's pairs or on caller planes (the kernels: k_cutdet.hip), the synchronous getters, and the host form eppm_cutdet_host.  The host form shares cutdet.h's
 // arithmetic with the kernels.
-#include "api_internal.h"
+#include "stage_object.h"
 #include "cutdet.h"
 
 using namespace eppm;
@@ -10,16 +10,12 @@ static_assert(sizeof(CutRecord) == sizeof(eppm_cut_stats) && sizeof(CutRecord) =
 static_assert(offsetof(CutRecord, cut) == offsetof(eppm_cut_stats, cut) && offsetof(CutRecord, sad) == offsetof(eppm_cut_stats, sad), "the record is eppm_cut_stats");
 static_assert(kCutSums * 4 <= kCutSlabBytes, "a slab holds the ten sums");
 
-struct eppm_cutdet {
-    int device = 0, h = 0, w = 0, nslots = 0;
+struct eppm_cutdet : StageObject {      // mem: nslots records 128 bytes apart | nslots blocks of slabs `slab_stride` bytes apart
     int lost_permille = 0;
     int64_t r16 = -1;
     int tiles_x = 0, tiles_y = 0;
-    char* mem = nullptr;                // nslots records 128 bytes apart | nslots blocks of slabs `slab_stride` bytes apart
-    size_t bytes = 0, off_slabs = 0, slab_stride = 0;
+    size_t off_slabs = 0, slab_stride = 0;
     std::vector<uint8_t> stepped;       // per slot: it has a record
-    hipEvent_t done = nullptr;          // recorded after every step: the synchronous calls wait for it
-    hipStream_t last = nullptr;         // the stream of the last step: a step on another stream waits for `done` first
 };
 
 namespace {
@@ -35,14 +31,6 @@ int cutdet_params(const eppm_cut_params* p, const char* what)
 int size_check(int h, int w, const char* what)
 {
     if (!cut_size_ok(h, w)) return set_err(EPPM_ERR_ARG, "%s: size %dx%d out of range (w, h <= %d, h*w <= 2^26)", what, w, h, kCutMaxDim);
-    return EPPM_OK;
-}
-
-// the detector's last step is complete (the synchronous calls read its records on the null stream)
-int wait(eppm_cutdet* f)
-{
-    HIPCHK(hipSetDevice(f->device));
-    HIPCHK(hipEventSynchronize(f->done));
     return EPPM_OK;
 }
 
@@ -63,36 +51,22 @@ static int cutdet_new(int device, int h, int w, int nslots, const eppm_cut_param
     const eppm_cut_params* p = in ? in : &def;
     CHK(cutdet_params(p, "eppm_cutdet_create"));
     CHK(size_check(h, w, "eppm_cutdet_create"));
-    if (nslots < 1 || nslots > kTemporalMaxSlots) return set_err(EPPM_ERR_ARG, "eppm_cutdet_create: %d slots outside [1, %d]", nslots, kTemporalMaxSlots);
-    HIPCHK(hipSetDevice(device));
     eppm_cutdet* f = new eppm_cutdet;
+    f->noun = "detector";
     f->device = device; f->h = h; f->w = w; f->nslots = nslots;
     f->lost_permille = p->lost_permille; f->r16 = cut_r16(p->residual_max);
     f->tiles_x = (w + kCutTileW - 1) / kCutTileW;
     f->tiles_y = (h + kCutTileH - 1) / kCutTileH;
-    f->off_slabs = ((size_t)nslots * kCutRecordStride + 255) & ~(size_t)255;
-    f->slab_stride = ((size_t)f->tiles_x * f->tiles_y * kCutSlabBytes + 255) & ~(size_t)255;
+    f->off_slabs = up256((size_t)nslots * kCutRecordStride);
+    f->slab_stride = up256((size_t)f->tiles_x * f->tiles_y * kCutSlabBytes);
     f->bytes = f->off_slabs + f->slab_stride * nslots;
-    f->stepped.assign(nslots, 0);
-    hipError_t e = cache_alloc((void**)&f->mem, f->bytes, false, device);
-    if (e != hipSuccess) {
-        (void)hipGetLastError();
-        const size_t bytes = f->bytes;
-        delete f;
-        return set_err(EPPM_ERR_HIP, "hipMalloc of %zu bytes (cut detector) failed: %s", bytes, hipGetErrorString(e));
-    }
     // the records start as zeros: a slot without a step reports no cut
-    e = hipMemsetAsync(f->mem, 0, f->off_slabs, nullptr);
-    if (e == hipSuccess) e = hipEventCreateWithFlags(&f->done, hipEventDisableTiming);
-    if (e == hipSuccess) e = hipEventRecord(f->done, nullptr);
-    if (e != hipSuccess) {
-        (void)hipGetLastError();
-        if (f->done) (void)hipEventDestroy(f->done);
-        (void)hipDeviceSynchronize();
-        cache_free(f->mem, f->bytes, false, device);
+    const int rc = stage_open(f, "eppm_cutdet_create", [f] { return hipMemsetAsync(f->mem, 0, f->off_slabs, nullptr); });
+    if (rc != EPPM_OK) {
         delete f;
-        return set_err(EPPM_ERR_HIP, "eppm_cutdet_create: %s", hipGetErrorString(e));
+        return rc;
     }
+    f->stepped.assign(nslots, 0);
     *out = f;
     return EPPM_OK;
 }
@@ -116,39 +90,27 @@ extern "C" int eppm_cutdet_create_size(int h, int w, int nslots, int device, con
 extern "C" int eppm_cutdet_destroy(eppm_cutdet* f)
 {
     if (!f) return EPPM_OK;
-    (void)hipSetDevice(f->device);
-    (void)hipEventSynchronize(f->done);
-    (void)hipEventDestroy(f->done);
-    cache_free(f->mem, f->bytes, false, f->device);
+    stage_close(f);
     delete f;
     return EPPM_OK;
 }
 
-int cutdet_device(const eppm_cutdet* f, int* h, int* w, int* nslots)
-{
-    *h = f->h;
-    *w = f->w;
-    *nslots = f->nslots;
-    return f->device;
-}
-
 // one step of slots slot0 .. slot0 + in.n - 1 on stream s; in: the pairs' planes (the other members are filled in here).  timing: the
 // context whose stage-timing entries receive the stage, or NULL
-int cutdet_step_on(eppm_cutdet* f, CutArgs& in, int slot0, hipStream_t s, eppm_ctx* timing)
+static int step_on(eppm_cutdet* f, CutArgs& in, int slot0, hipStream_t s, eppm_ctx* timing)
 {
     in.mem = f->mem;
     in.off_slabs = f->off_slabs; in.slab_stride = f->slab_stride;
     in.h = f->h; in.w = f->w; in.slot0 = slot0;
     in.tiles_x = f->tiles_x; in.tiles_y = f->tiles_y;
     in.lost_permille = f->lost_permille; in.r16 = f->r16;
-    if (s != f->last) HIPCHK(hipStreamWaitEvent(s, f->done, 0));
-    if (timing) ctx_stage_begin(timing, "cutdet");
-    launch_cutdet_accumulate(in, s);
-    launch_cutdet_finish(in, s);
-    if (timing) ctx_stage_end(timing);
-    HIPCHK(hipGetLastError());
-    HIPCHK(hipEventRecord(f->done, s));
-    f->last = s;
+    CHK(stage_enter(f, s));
+    {
+        StageTimer t(timing, "cutdet");
+        launch_cutdet_accumulate(in, s);
+        launch_cutdet_finish(in, s);
+    }
+    CHK(stage_leave(f, s));
     for (int k = slot0; k < slot0 + in.n; k++) f->stepped[k] = 1;
     return EPPM_OK;
 }
@@ -156,18 +118,39 @@ int cutdet_step_on(eppm_cutdet* f, CutArgs& in, int slot0, hipStream_t s, eppm_c
 extern "C" int eppm_cutdet_step(eppm_cutdet* f, eppm_ctx* ctx)
 {
     if (!f || !ctx) return set_err(EPPM_ERR_ARG, "eppm_cutdet_step: NULL argument");
-    CutArgs in{};
+    CtxPlanes c;
     hipStream_t s;
-    CHK(ctx_cutdet_inputs(ctx, f->h, f->w, f->device, f->nslots, "eppm_cutdet_step", &in, &s));
-    return cutdet_step_on(f, in, 0, s, ctx);
+    CHK(ctx_stage_inputs(ctx, f, "eppm_cutdet_step", &c, &s));
+    CutArgs in{};
+    in.img1 = c.img1; in.img2 = c.img2; in.img_pitch = c.img_pitch; in.img_stride = c.img_stride;
+    in.bwd = c.bwd; in.bwd_stride = c.bwd_stride;
+    in.occ1 = c.occ1; in.occ2 = c.occ2; in.occ_stride = c.occ_stride;
+    in.n = c.n;
+    return step_on(f, in, 0, s, ctx);
+}
+
+// one step of one slot on caller planes, on the launcher stream
+extern "C" int eppm_cutdet_step_frames(eppm_cutdet* f, int slot, const void* d_rgba1, const void* d_rgba2, size_t pitch, const eppm_float2* d_flow_bwd,
+                                       const uint8_t* d_occ1, const uint8_t* d_occ2)
+{
+    if (!f || !d_rgba1 || !d_rgba2 || !d_flow_bwd || !d_occ1 || !d_occ2) return set_err(EPPM_ERR_ARG, "eppm_cutdet_step_frames: NULL argument");
+    CHK(stage_slot_check(f, slot, "eppm_cutdet_step_frames"));
+    if (bad_pitch(pitch, f->w)) return set_err(EPPM_ERR_ARG, "eppm_cutdet_step_frames: bad pitch %zu", pitch);
+    return launcher_run(f, "eppm_cutdet_step_frames", [&](hipStream_t s) {
+        CutArgs in{};
+        in.img1 = (const uint8_t*)d_rgba1; in.img2 = (const uint8_t*)d_rgba2; in.img_pitch = pitch;
+        in.bwd = (const float*)d_flow_bwd; in.occ1 = d_occ1; in.occ2 = d_occ2;
+        in.n = 1;
+        return step_on(f, in, slot, s, nullptr);
+    });
 }
 
 extern "C" int eppm_cutdet_get(eppm_cutdet* f, int slot, eppm_cut_stats* stats)
 {
     if (!f || !stats) return set_err(EPPM_ERR_ARG, "eppm_cutdet_get: NULL argument");
-    if (slot < 0 || slot >= f->nslots) return set_err(EPPM_ERR_ARG, "eppm_cutdet_get: slot %d, the detector has %d", slot, f->nslots);
+    CHK(stage_slot_check(f, slot, "eppm_cutdet_get"));
     if (!f->stepped[slot]) return set_err(EPPM_ERR_STATE, "eppm_cutdet_get: slot %d has not been stepped", slot);
-    CHK(wait(f));
+    CHK(stage_wait(f));
     HIPCHK(hipMemcpy(stats, f->mem + (size_t)slot * kCutRecordStride, sizeof *stats, hipMemcpyDeviceToHost));
     return EPPM_OK;
 }
@@ -176,7 +159,7 @@ extern "C" int eppm_cutdet_cuts(eppm_cutdet* f, int n, uint8_t* cut)
 {
     if (!f || !cut) return set_err(EPPM_ERR_ARG, "eppm_cutdet_cuts: NULL argument");
     if (n < 1 || n > f->nslots) return set_err(EPPM_ERR_ARG, "eppm_cutdet_cuts: %d slots, the detector has %d", n, f->nslots);
-    CHK(wait(f));
+    CHK(stage_wait(f));
     std::vector<char> rec((size_t)n * kCutRecordStride);
     HIPCHK(hipMemcpy(rec.data(), f->mem, rec.size(), hipMemcpyDeviceToHost));
     for (int k = 0; k < n; k++) {

@@ -1,7 +1,8 @@
 // launchers_ref_abi.cpp -- the reference's live extern "C" stage launchers with their exact argument lists (driver :40-62) and the
 // sub-stage entry points the parity tests drive, all on per-device state kept here (the reference keeps the equivalent in file-scope
-// textures, __constant__ tables and g_d_rand_states: SURVEY F12).
-#include "api_internal.h"
+// textures, __constant__ tables and g_d_rand_states: SURVEY F12).  The launcher stream lives here; the caller-plane steps of the per-clip
+// stage objects (each in its object's module) borrow it through launcher_run.
+#include "stage_object.h"
 #include "mblur.h"
 
 using namespace eppm;
@@ -286,7 +287,7 @@ extern "C" int eppm_flow_upsample(eppm_float2* d_out, int h, int w, const eppm_f
                                   size_t guide_pitch)
 {
     if (!d_out || !d_coarse || !d_guide || h < 1 || w < 1 || hc < 1 || wc < 1) return set_err(EPPM_ERR_ARG, "eppm_flow_upsample: bad argument");
-    if (guide_pitch < (size_t)w * 4 || (guide_pitch & 3)) return set_err(EPPM_ERR_ARG, "eppm_flow_upsample: bad pitch %zu", guide_pitch);
+    if (bad_pitch(guide_pitch, w)) return set_err(EPPM_ERR_ARG, "eppm_flow_upsample: bad pitch %zu", guide_pitch);
     if ((unsigned long long)h * (unsigned long long)guide_pitch >= (1ULL << 32) || (unsigned long long)h * (unsigned long long)w >= (1ULL << 30))
         return set_err(EPPM_ERR_ARG, "eppm_flow_upsample: size %dx%d out of range", w, h);
     LAUNCHER_BEGIN_INT;
@@ -643,7 +644,7 @@ extern "C" int eppm_interpolate_frames(void* d_rgba_out, size_t out_pitch, const
 {
     if (!d_rgba_out || !d_rgba1 || !d_rgba2 || !d_flow || !d_occ1 || !d_occ2 || h < 1 || w < 1) return set_err(EPPM_ERR_ARG, "eppm_interpolate_frames: bad argument");
     if (!(t >= 0.0f && t <= 1.0f)) return set_err(EPPM_ERR_ARG, "eppm_interpolate_frames: t = %g outside [0, 1]", t);
-    if (in_pitch < (size_t)w * 4 || out_pitch < (size_t)w * 4 || (in_pitch & 3) || (out_pitch & 3))
+    if (bad_pitch(in_pitch, w) || bad_pitch(out_pitch, w))
         return set_err(EPPM_ERR_ARG, "eppm_interpolate_frames: bad pitch %zu / %zu", in_pitch, out_pitch);
     if ((unsigned long long)h * (unsigned long long)w >= (1ULL << 31)) return set_err(EPPM_ERR_ARG, "eppm_interpolate_frames: size %dx%d out of range", w, h);
     LAUNCHER_BEGIN_INT;
@@ -672,7 +673,7 @@ extern "C" int eppm_motion_blur_frames(void* d_rgba_out, size_t out_pitch, const
     if (!d_rgba_out || !d_rgba || !d_flow || h < 1 || w < 1) return set_err(EPPM_ERR_ARG, "eppm_motion_blur_frames: bad argument");
     if (!mblur_params_ok(prm.shutter, prm.max_radius, prm.taps))
         return set_err(EPPM_ERR_ARG, "eppm_motion_blur_frames: shutter %g (0 < s <= 1), max_radius %g (1 .. 31), taps %d (1 .. 32)", prm.shutter, prm.max_radius, prm.taps);
-    if (in_pitch < (size_t)w * 4 || out_pitch < (size_t)w * 4 || (in_pitch & 3) || (out_pitch & 3))
+    if (bad_pitch(in_pitch, w) || bad_pitch(out_pitch, w))
         return set_err(EPPM_ERR_ARG, "eppm_motion_blur_frames: bad pitch %zu / %zu", in_pitch, out_pitch);
     if (h > 8192 || w > 8192 || (unsigned long long)h * (unsigned long long)w > (1ULL << 26))
         return set_err(EPPM_ERR_ARG, "eppm_motion_blur_frames: size %dx%d out of range", w, h);
@@ -693,165 +694,16 @@ extern "C" int eppm_motion_blur_frames(void* d_rgba_out, size_t out_pitch, const
     HIPCHK(hipStreamSynchronize(g_stream));
     return finish();
 }
-// ---- one track step on caller planes (k_track.hip; eppm_track_step_host is its host form) ----
-extern "C" int eppm_track_step_frames(eppm_tracker* t, const void* d_rgba1, const void* d_rgba2, size_t pitch, const eppm_float2* d_flow,
-                                      const eppm_float2* d_flow_bwd, int h, int w)
+// ---- the caller-plane steps of the per-clip stage objects (eppm_*_step_frames, eppm_plate_render_frames: each in its object's module)
+// reach the launcher stream through this ----
+int launcher_run(const StageObject* o, const char* what, const std::function<int(hipStream_t)>& fn, bool sync)
 {
-    if (!t || !d_rgba1 || !d_rgba2 || !d_flow || !d_flow_bwd) return set_err(EPPM_ERR_ARG, "eppm_track_step_frames: NULL argument");
-    int th, tw;
-    const int device = tracker_device(t, &th, &tw);
-    if (h != th || w != tw) return set_err(EPPM_ERR_ARG, "eppm_track_step_frames: %dx%d planes, the tracker is %dx%d", w, h, tw, th);
-    if (pitch < (size_t)w * 4 || (pitch & 3)) return set_err(EPPM_ERR_ARG, "eppm_track_step_frames: bad pitch %zu", pitch);
     std::lock_guard<std::mutex> lk(g_mu);
     int d = 0;
     HIPCHK(hipGetDevice(&d));
-    if (d != device) return set_err(EPPM_ERR_ARG, "eppm_track_step_frames: the tracker lives on device %d, the current device is %d", device, d);
-    TrackIn in{(const uint8_t*)d_rgba1, (const uint8_t*)d_rgba2, pitch, (const float*)d_flow, (const float*)d_flow_bwd, h, w};
-    CHK(tracker_step_on(t, in, g_stream, nullptr));
-    HIPCHK(hipStreamSynchronize(g_stream));
-    return finish();
-}
-// ---- one temporal-filter step of one slot on caller planes (k_tfilter.hip; eppm_tfilter_step_host is its host form) ----
-extern "C" int eppm_tfilter_step_frames(eppm_tfilter* f, int slot, const void* d_rgba1, const void* d_rgba2, size_t pitch,
-                                        const eppm_float2* d_flow_bwd, const uint8_t* d_occ2, int cut)
-{
-    if (!f || !d_rgba1 || !d_rgba2 || !d_flow_bwd || !d_occ2) return set_err(EPPM_ERR_ARG, "eppm_tfilter_step_frames: NULL argument");
-    int h, w, nslots;
-    const int device = tfilter_device(f, &h, &w, &nslots);
-    if (slot < 0 || slot >= nslots) return set_err(EPPM_ERR_ARG, "eppm_tfilter_step_frames: slot %d, the filter has %d", slot, nslots);
-    if (pitch < (size_t)w * 4 || (pitch & 3)) return set_err(EPPM_ERR_ARG, "eppm_tfilter_step_frames: bad pitch %zu", pitch);
-    std::lock_guard<std::mutex> lk(g_mu);
-    int d = 0;
-    HIPCHK(hipGetDevice(&d));
-    if (d != device) return set_err(EPPM_ERR_ARG, "eppm_tfilter_step_frames: the filter lives on device %d, the current device is %d", device, d);
-    TFilterArgs in{};
-    in.img1 = (const uint8_t*)d_rgba1; in.img2 = (const uint8_t*)d_rgba2; in.img_pitch = pitch;
-    in.bwd = (const float*)d_flow_bwd; in.occ2 = d_occ2;
-    in.n = 1;
-    const uint8_t c = cut != 0;
-    CHK(tfilter_step_on(f, in, slot, &c, g_stream, nullptr));
-    HIPCHK(hipStreamSynchronize(g_stream));
-    return finish();
-}
-// ---- one stabiliser step of one slot on caller planes (k_gmotion.hip; the host forms: eppm_gmotion_fit_host, eppm_stab_update_host,
-// eppm_stab_warp_host) ----
-extern "C" int eppm_stab_step_frames(eppm_stab* f, int slot, const void* d_rgba2, size_t pitch, const eppm_float2* d_flow, const uint8_t* d_occ1, int cut)
-{
-    if (!f || !d_rgba2 || !d_flow || !d_occ1) return set_err(EPPM_ERR_ARG, "eppm_stab_step_frames: NULL argument");
-    int h, w, nslots;
-    const int device = stab_device(f, &h, &w, &nslots);
-    if (slot < 0 || slot >= nslots) return set_err(EPPM_ERR_ARG, "eppm_stab_step_frames: slot %d, the stabiliser has %d", slot, nslots);
-    if (pitch < (size_t)w * 4 || (pitch & 3)) return set_err(EPPM_ERR_ARG, "eppm_stab_step_frames: bad pitch %zu", pitch);
-    std::lock_guard<std::mutex> lk(g_mu);
-    int d = 0;
-    HIPCHK(hipGetDevice(&d));
-    if (d != device) return set_err(EPPM_ERR_ARG, "eppm_stab_step_frames: the stabiliser lives on device %d, the current device is %d", device, d);
-    StabArgs in{};
-    in.img2 = (const uint8_t*)d_rgba2; in.img_pitch = pitch;
-    in.fwd = (const float*)d_flow; in.occ1 = d_occ1;
-    in.n = 1;
-    const uint8_t c = cut != 0;
-    CHK(stab_step_on(f, in, slot, &c, g_stream, nullptr));
-    HIPCHK(hipStreamSynchronize(g_stream));
-    return finish();
-}
-// ---- one cut-detector step of one slot on caller planes (k_cutdet.hip; eppm_cutdet_host is its host form) ----
-extern "C" int eppm_cutdet_step_frames(eppm_cutdet* f, int slot, const void* d_rgba1, const void* d_rgba2, size_t pitch, const eppm_float2* d_flow_bwd,
-                                       const uint8_t* d_occ1, const uint8_t* d_occ2)
-{
-    if (!f || !d_rgba1 || !d_rgba2 || !d_flow_bwd || !d_occ1 || !d_occ2) return set_err(EPPM_ERR_ARG, "eppm_cutdet_step_frames: NULL argument");
-    int h, w, nslots;
-    const int device = cutdet_device(f, &h, &w, &nslots);
-    if (slot < 0 || slot >= nslots) return set_err(EPPM_ERR_ARG, "eppm_cutdet_step_frames: slot %d, the detector has %d", slot, nslots);
-    if (pitch < (size_t)w * 4 || (pitch & 3)) return set_err(EPPM_ERR_ARG, "eppm_cutdet_step_frames: bad pitch %zu", pitch);
-    std::lock_guard<std::mutex> lk(g_mu);
-    int d = 0;
-    HIPCHK(hipGetDevice(&d));
-    if (d != device) return set_err(EPPM_ERR_ARG, "eppm_cutdet_step_frames: the detector lives on device %d, the current device is %d", device, d);
-    CutArgs in{};
-    in.img1 = (const uint8_t*)d_rgba1; in.img2 = (const uint8_t*)d_rgba2; in.img_pitch = pitch;
-    in.bwd = (const float*)d_flow_bwd; in.occ1 = d_occ1; in.occ2 = d_occ2;
-    in.n = 1;
-    CHK(cutdet_step_on(f, in, slot, g_stream, nullptr));
-    HIPCHK(hipStreamSynchronize(g_stream));
-    return finish();
-}
-// ---- one correspondence-map step of one slot on caller planes (k_cmap.hip; eppm_cmap_step_host is its host form) ----
-extern "C" int eppm_cmap_step_frames(eppm_cmap* f, int slot, const void* d_rgba1, const void* d_rgba2, size_t pitch, const eppm_float2* d_flow_bwd,
-                                     const uint8_t* d_occ2, int cut)
-{
-    if (!f || !d_rgba1 || !d_rgba2 || !d_flow_bwd || !d_occ2) return set_err(EPPM_ERR_ARG, "eppm_cmap_step_frames: NULL argument");
-    int h, w, nslots;
-    const int device = cmap_device(f, &h, &w, &nslots);
-    if (slot < 0 || slot >= nslots) return set_err(EPPM_ERR_ARG, "eppm_cmap_step_frames: slot %d, the map has %d", slot, nslots);
-    if (pitch < (size_t)w * 4 || (pitch & 3)) return set_err(EPPM_ERR_ARG, "eppm_cmap_step_frames: bad pitch %zu", pitch);
-    std::lock_guard<std::mutex> lk(g_mu);
-    int d = 0;
-    HIPCHK(hipGetDevice(&d));
-    if (d != device) return set_err(EPPM_ERR_ARG, "eppm_cmap_step_frames: the map lives on device %d, the current device is %d", device, d);
-    CMapArgs in{};
-    in.img1 = (const uint8_t*)d_rgba1; in.img2 = (const uint8_t*)d_rgba2; in.img_pitch = pitch;
-    in.bwd = (const float*)d_flow_bwd; in.occ2 = d_occ2;
-    in.n = 1;
-    const uint8_t c = cut != 0;
-    CHK(cmap_step_on(f, in, slot, &c, g_stream, nullptr));
-    HIPCHK(hipStreamSynchronize(g_stream));
-    return finish();
-}
-// ---- one object-detector step of one slot on caller planes, without a fit (k_objects.hip; the host forms: eppm_objects_label_host,
-// eppm_objects_assign_host, eppm_objects_carry_host) ----
-extern "C" int eppm_objects_step_frames(eppm_objects* f, int slot, const uint8_t* d_mask, const eppm_float2* d_flow, const eppm_float2* d_flow_bwd,
-                                        const uint8_t* d_occ2, int cut)
-{
-    if (!f || !d_mask || !d_flow) return set_err(EPPM_ERR_ARG, "eppm_objects_step_frames: NULL argument");
-    int h, w, nslots;
-    const int device = objects_device(f, &h, &w, &nslots);
-    if (slot < 0 || slot >= nslots) return set_err(EPPM_ERR_ARG, "eppm_objects_step_frames: slot %d, the detector has %d", slot, nslots);
-    std::lock_guard<std::mutex> lk(g_mu);
-    int d = 0;
-    HIPCHK(hipGetDevice(&d));
-    if (d != device) return set_err(EPPM_ERR_ARG, "eppm_objects_step_frames: the detector lives on device %d, the current device is %d", device, d);
-    ObjArgs in{};
-    in.mask = d_mask; in.fwd = (const float*)d_flow;
-    if (d_flow_bwd && d_occ2) in.bwd = (const float*)d_flow_bwd, in.occ2 = d_occ2;
-    in.n = 1;
-    const uint8_t c = cut != 0;
-    CHK(objects_step_on(f, in, slot, &c, g_stream, nullptr));
-    HIPCHK(hipStreamSynchronize(g_stream));
-    CHK(finish());
-    return objects_slot_status(f, slot, "eppm_objects_step_frames");
-}
-// ---- one background-plate step / render of one slot on caller planes, without a fit (k_plate.hip; the host forms: eppm_plate_forms_host,
-// eppm_plate_block_host, eppm_plate_accumulate_host, eppm_plate_render_host) ----
-extern "C" int eppm_plate_step_frames(eppm_plate* f, int slot, const void* d_rgba, size_t pitch, const uint8_t* d_mask, const double* path, int cut)
-{
-    if (!f || !d_rgba || !d_mask) return set_err(EPPM_ERR_ARG, "eppm_plate_step_frames: NULL argument");
-    int h, w, nslots;
-    const int device = plate_device(f, &h, &w, &nslots);
-    CHK(plate_slot_check(f, slot, false, "eppm_plate_step_frames"));
-    if (pitch < (size_t)w * 4 || (pitch & 3)) return set_err(EPPM_ERR_ARG, "eppm_plate_step_frames: bad pitch %zu", pitch);
-    std::lock_guard<std::mutex> lk(g_mu);
-    int d = 0;
-    HIPCHK(hipGetDevice(&d));
-    if (d != device) return set_err(EPPM_ERR_ARG, "eppm_plate_step_frames: the plate lives on device %d, the current device is %d", device, d);
-    CHK(plate_step_frames_on(f, slot, d_rgba, pitch, d_mask, path, cut, g_stream));
-    HIPCHK(hipStreamSynchronize(g_stream));
-    return finish();
-}
-extern "C" int eppm_plate_render_frames(eppm_plate* f, int slot, const void* d_rgba, size_t pitch, const uint8_t* d_mask, const double* path, void* d_rgba_out,
-                                        size_t out_pitch, uint8_t* d_fill)
-{
-    if (!f || !d_rgba || !d_mask || !d_rgba_out || !d_fill) return set_err(EPPM_ERR_ARG, "eppm_plate_render_frames: NULL argument");
-    int h, w, nslots;
-    const int device = plate_device(f, &h, &w, &nslots);
-    CHK(plate_slot_check(f, slot, true, "eppm_plate_render_frames"));
-    if (pitch < (size_t)w * 4 || (pitch & 3) || out_pitch < (size_t)w * 4 || (out_pitch & 3))
-        return set_err(EPPM_ERR_ARG, "eppm_plate_render_frames: bad pitch %zu / %zu", pitch, out_pitch);
-    std::lock_guard<std::mutex> lk(g_mu);
-    int d = 0;
-    HIPCHK(hipGetDevice(&d));
-    if (d != device) return set_err(EPPM_ERR_ARG, "eppm_plate_render_frames: the plate lives on device %d, the current device is %d", device, d);
-    CHK(plate_render_frames_on(f, slot, d_rgba, pitch, d_mask, path, d_rgba_out, out_pitch, d_fill, g_stream));
+    if (d != o->device) return set_err(EPPM_ERR_ARG, "%s: the %s lives on device %d, the current device is %d", what, o->noun, o->device, d);
+    CHK(fn(g_stream));
+    if (sync) HIPCHK(hipStreamSynchronize(g_stream));
     return finish();
 }
 // the C++-linkage symbol the reference's driver declares at :64 (defaults 100,100 there; the live call passes 20,20)

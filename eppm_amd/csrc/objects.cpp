@@ -1,7 +1,7 @@
-// objects.cpp -- moving-object detection: eppm_objects, its one allocation, its private stabiliser, its step on a
-// context's pairs (the kernels: k_objects.hip), the synchronous calls, and the host forms eppm_objects_label_host /
+// objects.cpp -- moving-object detection: eppm_objects (a stage object, stage_object.h), its private stabiliser,
+// its step on a context's pairs or on caller planes (the kernels: k_objects.hip), the synchronous calls, and the host forms eppm_objects_label_host /
 // eppm_objects_carry_host / eppm_objects_assign_host, which are objects.h's sequential code behind argument checks.
-#include "api_internal.h"
+#include "stage_object.h"
 #include "objects.h"
 
 using namespace eppm;
@@ -9,17 +9,12 @@ using namespace eppm;
 static_assert(sizeof(ObjRecord) == 64 && sizeof(eppm_object) == sizeof(ObjRecord), "a record is the public eppm_object");
 static_assert(sizeof(ObjCounts) == sizeof(eppm_objects_counts) && sizeof(ObjHeader) == 32, "the counts head a slot's 32-byte header");
 
-struct eppm_objects {
-    int device = 0, h = 0, w = 0, nslots = 0;
+struct eppm_objects : StageObject {     // mem: nslots blocks `stride` bytes apart: ObjArgs' layout
     eppm_objects_params prm{};
     eppm_stab* stab = nullptr;          // the private stabiliser whose mask the context form labels
-    char* mem = nullptr;                // nslots blocks `stride` bytes apart: ObjArgs' layout
-    size_t bytes = 0, stride = 0, off_root = 0, off_area = 0, off_labels = 0, off_carried = 0, off_chunks = 0, off_rec = 0, off_votes = 0, off_hdr = 0;
+    size_t stride = 0, off_root = 0, off_area = 0, off_labels = 0, off_carried = 0, off_chunks = 0, off_rec = 0, off_votes = 0, off_hdr = 0;
     int tiles_x = 0, tiles_y = 0, nchunks = 0;
     std::vector<uint8_t> empty, stepped;    // per slot: it has no state (carried plane zero, next_id 1) / it has labels and records
-    hipEvent_t done = nullptr;          // recorded after every step: the synchronous calls wait for it
-    hipStream_t last = nullptr;         // the stream of the last step: a step on another stream waits for `done` first
-    size_t px() const { return (size_t)h * w; }
     char* block(int slot) const { return mem + (size_t)slot * stride; }
     ObjHeader* hdr(int slot) const { return (ObjHeader*)(block(slot) + off_hdr); }
     int32_t* prev(int slot, int which) const { return (int32_t*)(block(slot) + off_hdr + sizeof(ObjHeader)) + which * kObjTable; }
@@ -29,8 +24,6 @@ struct eppm_objects {
 };
 
 namespace {
-
-size_t up256(size_t v) { return (v + 255) & ~(size_t)255; }
 
 int objects_params(const eppm_objects_params* p, const char* what)
 {
@@ -48,17 +41,9 @@ int size_check(int h, int w, const char* what)
     return EPPM_OK;
 }
 
-// the detector's last step is complete (the synchronous calls read and write its planes on the null stream)
-int wait(eppm_objects* f)
-{
-    HIPCHK(hipSetDevice(f->device));
-    HIPCHK(hipEventSynchronize(f->done));
-    return EPPM_OK;
-}
-
 int slot_check(const eppm_objects* f, int slot, bool need_step, const char* what)
 {
-    if (slot < 0 || slot >= f->nslots) return set_err(EPPM_ERR_ARG, "%s: slot %d, the detector has %d", what, slot, f->nslots);
+    CHK(stage_slot_check(f, slot, what));
     if (need_step && !f->stepped[slot]) return set_err(EPPM_ERR_STATE, "%s: slot %d has not been stepped", what, slot);
     return EPPM_OK;
 }
@@ -66,7 +51,7 @@ int slot_check(const eppm_objects* f, int slot, bool need_step, const char* what
 // the slot's header, after the last step; an error word that is set is the call's failure
 int header(eppm_objects* f, int slot, ObjHeader* hd, const char* what)
 {
-    CHK(wait(f));
+    CHK(stage_wait(f));
     HIPCHK(hipMemcpy(hd, f->hdr(slot), sizeof *hd, hipMemcpyDeviceToHost));
     if (hd->err)
         return set_err(EPPM_ERR_STATE, "%s: a labelling loop hit its iteration cap in slot %d (a defect of the library): its results are invalid until eppm_objects_reset", what, slot);
@@ -94,9 +79,8 @@ static int objects_new(int device, int h, int w, int nslots, const eppm_objects_
     const eppm_objects_params* p = in ? in : &def;
     CHK(objects_params(p, "eppm_objects_create"));
     CHK(size_check(h, w, "eppm_objects_create"));
-    if (nslots < 1 || nslots > kTemporalMaxSlots) return set_err(EPPM_ERR_ARG, "eppm_objects_create: %d slots outside [1, %d]", nslots, kTemporalMaxSlots);
-    HIPCHK(hipSetDevice(device));
     eppm_objects* f = new eppm_objects;
+    f->noun = "detector";
     f->device = device; f->h = h; f->w = w; f->nslots = nslots;
     f->prm = *p;
     f->tiles_x = (w + kObjTileW - 1) / kObjTileW;
@@ -113,37 +97,22 @@ static int objects_new(int device, int h, int w, int nslots, const eppm_objects_
     f->off_hdr = f->off_votes + up256(votes);
     f->stride = f->off_hdr + up256(sizeof(ObjHeader) + 2 * kObjTable * sizeof(int32_t));
     f->bytes = f->stride * nslots;
-    f->empty.assign(nslots, 1);
-    f->stepped.assign(nslots, 0);
     eppm_stab_params sp;
     eppm_stab_default_params(&sp);
     sp.tau = p->tau;
     sp.iters = p->iters;
-    const int rc = eppm_stab_create_size(h, w, nslots, device, &sp, &f->stab);
+    int rc = stage_open(f, "eppm_objects_create", [f] {
+        hipError_t e = hipSuccess;
+        for (int k = 0; k < f->nslots && e == hipSuccess; k++) e = hipMemsetAsync(f->hdr(k), 0, sizeof(ObjHeader) + 2 * kObjTable * sizeof(int32_t), nullptr);
+        return e;
+    });
+    if (rc == EPPM_OK) rc = eppm_stab_create_size(h, w, nslots, device, &sp, &f->stab);
     if (rc != EPPM_OK) {
-        delete f;
+        eppm_objects_destroy(f);
         return rc;
     }
-    hipError_t e = cache_alloc((void**)&f->mem, f->bytes, false, device);
-    if (e != hipSuccess) {
-        (void)hipGetLastError();
-        const size_t total = f->bytes;
-        eppm_stab_destroy(f->stab);
-        delete f;
-        return set_err(EPPM_ERR_HIP, "hipMalloc of %zu bytes (object detector) failed: %s", total, hipGetErrorString(e));
-    }
-    e = hipEventCreateWithFlags(&f->done, hipEventDisableTiming);
-    for (int k = 0; k < nslots && e == hipSuccess; k++) e = hipMemsetAsync(f->hdr(k), 0, sizeof(ObjHeader) + 2 * kObjTable * sizeof(int32_t), nullptr);
-    if (e == hipSuccess) e = hipEventRecord(f->done, nullptr);
-    if (e != hipSuccess) {
-        (void)hipGetLastError();
-        if (f->done) (void)hipEventDestroy(f->done);
-        (void)hipDeviceSynchronize();
-        cache_free(f->mem, f->bytes, false, device);
-        eppm_stab_destroy(f->stab);
-        delete f;
-        return set_err(EPPM_ERR_HIP, "eppm_objects_create: %s", hipGetErrorString(e));
-    }
+    f->empty.assign(nslots, 1);
+    f->stepped.assign(nslots, 0);
     *out = f;
     return EPPM_OK;
 }
@@ -167,11 +136,8 @@ extern "C" int eppm_objects_create_size(int h, int w, int nslots, int device, co
 extern "C" int eppm_objects_destroy(eppm_objects* f)
 {
     if (!f) return EPPM_OK;
-    (void)hipSetDevice(f->device);
-    (void)hipEventSynchronize(f->done);
-    (void)hipEventDestroy(f->done);
     eppm_stab_destroy(f->stab);
-    cache_free(f->mem, f->bytes, false, f->device);
+    stage_close(f);
     delete f;
     return EPPM_OK;
 }
@@ -179,8 +145,8 @@ extern "C" int eppm_objects_destroy(eppm_objects* f)
 extern "C" int eppm_objects_reset(eppm_objects* f, int slot)
 {
     if (!f) return set_err(EPPM_ERR_ARG, "eppm_objects_reset: NULL detector");
-    if (slot >= f->nslots) return set_err(EPPM_ERR_ARG, "eppm_objects_reset: slot %d, the detector has %d", slot, f->nslots);
-    CHK(wait(f));
+    if (slot >= 0) CHK(stage_slot_check(f, slot, "eppm_objects_reset"));
+    CHK(stage_wait(f));
     for (int k = 0; k < f->nslots; k++)
         if (slot < 0 || k == slot) {
             HIPCHK(hipMemset(f->hdr(k), 0, sizeof(ObjHeader)));      // the error word too
@@ -188,29 +154,12 @@ extern "C" int eppm_objects_reset(eppm_objects* f, int slot)
             f->stepped[k] = 0;
         }
     CHK(eppm_stab_reset(f->stab, slot));
-    HIPCHK(hipStreamSynchronize(nullptr));
-    HIPCHK(hipEventRecord(f->done, nullptr));
-    f->last = nullptr;
-    return EPPM_OK;
-}
-
-int objects_device(const eppm_objects* f, int* h, int* w, int* nslots)
-{
-    *h = f->h;
-    *w = f->w;
-    *nslots = f->nslots;
-    return f->device;
-}
-
-int objects_slot_status(eppm_objects* f, int slot, const char* what)
-{
-    ObjHeader hd;
-    return header(f, slot, &hd, what);
+    return stage_settle(f);
 }
 
 // one step of slots slot0 .. slot0 + in.n - 1 on stream s; in: the pairs' planes (the other members are filled in here); cut: NULL or one
 // flag per pair.  timing: the context whose stage-timing entries receive the stages, or NULL
-int objects_step_on(eppm_objects* f, ObjArgs& in, int slot0, const uint8_t* cut, hipStream_t s, eppm_ctx* timing)
+static int step_on(eppm_objects* f, ObjArgs& in, int slot0, const uint8_t* cut, hipStream_t s, eppm_ctx* timing)
 {
     in.mem = f->mem;
     in.slot_stride = f->stride;
@@ -219,23 +168,18 @@ int objects_step_on(eppm_objects* f, ObjArgs& in, int slot0, const uint8_t* cut,
     in.h = f->h; in.w = f->w; in.slot0 = slot0;
     in.tiles_x = f->tiles_x; in.tiles_y = f->tiles_y; in.nchunks = f->nchunks;
     in.connectivity = f->prm.connectivity; in.min_area = f->prm.min_area; in.max_objects = f->prm.max_objects; in.min_overlap = f->prm.min_overlap;
-    memset(in.empty, 0, sizeof(in.empty));
-    memset(in.cut, 0, sizeof(in.cut));
-    for (int k = slot0; k < slot0 + in.n; k++) {
-        const uint32_t bit = 1u << (k & 31);
-        if (f->empty[k]) in.empty[k >> 5] |= bit;
-        if (cut && cut[k - slot0]) in.cut[k >> 5] |= bit;
+    slot_mask(in.empty, f->empty.data() + slot0, slot0, in.n);
+    slot_mask(in.cut, cut, slot0, in.n);
+    CHK(stage_enter(f, s));
+    {
+        StageTimer t(timing, "objects_label");
+        launch_objects_label(in, s);
     }
-    if (s != f->last) HIPCHK(hipStreamWaitEvent(s, f->done, 0));
-    if (timing) ctx_stage_begin(timing, "objects_label");
-    launch_objects_label(in, s);
-    if (timing) ctx_stage_end(timing);
-    if (timing) ctx_stage_begin(timing, "objects_assign");
-    launch_objects_assign(in, s);
-    if (timing) ctx_stage_end(timing);
-    HIPCHK(hipGetLastError());
-    HIPCHK(hipEventRecord(f->done, s));
-    f->last = s;
+    {
+        StageTimer t(timing, "objects_assign");
+        launch_objects_assign(in, s);
+    }
+    CHK(stage_leave(f, s));
     for (int k = slot0; k < slot0 + in.n; k++) f->empty[k] = 0, f->stepped[k] = 1;
     return EPPM_OK;
 }
@@ -243,22 +187,39 @@ int objects_step_on(eppm_objects* f, ObjArgs& in, int slot0, const uint8_t* cut,
 extern "C" int eppm_objects_step(eppm_objects* f, eppm_ctx* ctx, const uint8_t* cut)
 {
     if (!f || !ctx) return set_err(EPPM_ERR_ARG, "eppm_objects_step: NULL argument");
-    StabArgs sin{};                     // the stabiliser's view of a context (image 2, the forward flow, occ1) ...
-    TFilterArgs t{};                    // ... and the temporal filter's (the backward flow, occ2)
+    CtxPlanes c;
     hipStream_t s;
-    CHK(ctx_stab_inputs(ctx, f->h, f->w, f->device, f->nslots, "eppm_objects_step", &sin, &s));
-    CHK(ctx_tfilter_inputs(ctx, f->h, f->w, f->device, f->nslots, "eppm_objects_step", &t, &s));
+    CHK(ctx_stage_inputs(ctx, f, "eppm_objects_step", &c, &s));
     ObjArgs in{};
-    in.fwd = sin.fwd; in.fwd_stride = sin.fwd_stride;
-    in.bwd = t.bwd; in.bwd_stride = t.bwd_stride;
-    in.occ2 = t.occ2; in.occ_stride = t.occ_stride;
-    in.n = sin.n;
-    ctx_stage_begin(ctx, "objects_fit");
-    const int rc = stab_step_on(f->stab, sin, 0, cut, s, nullptr);
-    ctx_stage_end(ctx);
-    CHK(rc);
+    in.fwd = c.fwd; in.fwd_stride = c.fwd_stride;
+    in.bwd = c.bwd; in.bwd_stride = c.bwd_stride;
+    in.occ2 = c.occ2; in.occ_stride = c.occ_stride;
+    in.n = c.n;
+    {
+        StageTimer t(ctx, "objects_fit");
+        StabArgs sin = stab_ctx_args(c);
+        CHK(stab_step_on(f->stab, sin, 0, cut, s, nullptr));
+    }
     in.mask = stab_mask_device(f->stab, &in.mask_stride);
-    return objects_step_on(f, in, 0, cut, s, ctx);
+    return step_on(f, in, 0, cut, s, ctx);
+}
+
+// the kernels alone for one slot on caller planes, without a fit, on the launcher stream; then the slot's error word
+extern "C" int eppm_objects_step_frames(eppm_objects* f, int slot, const uint8_t* d_mask, const eppm_float2* d_flow, const eppm_float2* d_flow_bwd,
+                                        const uint8_t* d_occ2, int cut)
+{
+    if (!f || !d_mask || !d_flow) return set_err(EPPM_ERR_ARG, "eppm_objects_step_frames: NULL argument");
+    CHK(stage_slot_check(f, slot, "eppm_objects_step_frames"));
+    CHK(launcher_run(f, "eppm_objects_step_frames", [&](hipStream_t s) {
+        ObjArgs in{};
+        in.mask = d_mask; in.fwd = (const float*)d_flow;
+        if (d_flow_bwd && d_occ2) in.bwd = (const float*)d_flow_bwd, in.occ2 = d_occ2;
+        in.n = 1;
+        const uint8_t c = cut != 0;
+        return step_on(f, in, slot, &c, s, nullptr);
+    }));
+    ObjHeader hd;
+    return header(f, slot, &hd, "eppm_objects_step_frames");
 }
 
 extern "C" int eppm_objects_get(eppm_objects* f, int slot, int max, eppm_object* records, eppm_objects_counts* counts)
@@ -313,14 +274,12 @@ extern "C" int eppm_objects_set_state(eppm_objects* f, int slot, const uint8_t* 
     if (next_id < 1 || next_id > kObjMaxNextId) return set_err(EPPM_ERR_ARG, "eppm_objects_set_state: next_id %d outside [1, 2^30]", next_id);
     for (int k = 0; k < kObjTable; k++)
         if (prev_age[k] < 0 || prev_age[k] > kObjMaxNextId) return set_err(EPPM_ERR_ARG, "eppm_objects_set_state: age %d outside [0, 2^30]", prev_age[k]);
-    CHK(wait(f));
+    CHK(stage_wait(f));
     HIPCHK(hipMemcpy(f->carried(slot), carried, f->px(), hipMemcpyHostToDevice));
     HIPCHK(hipMemcpy(f->prev(slot, 0), prev_id, kObjTable * sizeof(int32_t), hipMemcpyHostToDevice));
     HIPCHK(hipMemcpy(f->prev(slot, 1), prev_age, kObjTable * sizeof(int32_t), hipMemcpyHostToDevice));
     HIPCHK(hipMemcpy(&f->hdr(slot)->next_id, &next_id, sizeof next_id, hipMemcpyHostToDevice));
-    HIPCHK(hipStreamSynchronize(nullptr));
-    HIPCHK(hipEventRecord(f->done, nullptr));
-    f->last = nullptr;
+    CHK(stage_settle(f));
     f->empty[slot] = 0;
     return EPPM_OK;
 }

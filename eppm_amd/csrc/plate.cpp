@@ -1,23 +1,19 @@
-// plate.cpp -- background plates: eppm_plate, its one allocation, its private stabiliser, its step on a context's
-// pairs (the kernels: k_plate.hip), the synchronous calls, and the host forms eppm_plate_forms_host / eppm_plate_block_host /
+// plate.cpp -- background plates: eppm_plate (a stage object, stage_object.h), its private stabiliser, its step
+// on a context's pairs or on caller planes (the kernels: k_plate.hip), the synchronous calls, and the host forms eppm_plate_forms_host / eppm_plate_block_host /
 // eppm_plate_accumulate_host / eppm_plate_render_host, which are plate.h's sequential code behind argument checks.
-#include "api_internal.h"
+#include "stage_object.h"
 #include "plate.h"
 
 using namespace eppm;
 
 static_assert(sizeof(PlateRec) == 128 && sizeof(TfState) == 16, "a path record is 128 bytes, a canvas state one float4");
 
-struct eppm_plate {
-    int device = 0, h = 0, w = 0, ch = 0, cw = 0, nslots = 0;
+struct eppm_plate : StageObject {       // mem: nslots blocks `stride` bytes apart (PlateArgs' layout), then the scratch of the synchronous calls
+    int ch = 0, cw = 0;
     eppm_plate_params prm{};
     eppm_stab* stab = nullptr;          // the private stabiliser whose mask and model the context form uses
-    char* mem = nullptr;                // nslots blocks `stride` bytes apart (PlateArgs' layout), then the scratch of the synchronous calls
-    size_t bytes = 0, stride = 0, off_b = 0, off_br = 0, off_rec = 0, off_scratch = 0;
+    size_t stride = 0, off_b = 0, off_br = 0, off_rec = 0, off_scratch = 0;
     std::vector<uint8_t> empty, stepped, fitted;    // per slot: its canvas has no states / it has forms and a blocked plane / its last step had a fit
-    hipEvent_t done = nullptr;          // recorded after every step: the synchronous calls wait for it
-    hipStream_t last = nullptr;         // the stream of the last step: a step on another stream waits for `done` first
-    size_t px() const { return (size_t)h * w; }
     size_t cpx() const { return (size_t)ch * cw; }
     char* block(int slot) const { return mem + (size_t)slot * stride; }
     PlateRec* rec(int slot) const { return (PlateRec*)(block(slot) + off_rec); }
@@ -26,8 +22,6 @@ struct eppm_plate {
 };
 
 namespace {
-
-size_t up256(size_t v) { return (v + 255) & ~(size_t)255; }
 
 int plate_params(const eppm_plate_params* p, const char* what)
 {
@@ -47,26 +41,9 @@ int size_check(int h, int w, int mx, int my, const char* what)
     return EPPM_OK;
 }
 
-// the plate's last step is complete (the synchronous calls read and write its planes on the null stream)
-int wait(eppm_plate* f)
-{
-    HIPCHK(hipSetDevice(f->device));
-    HIPCHK(hipEventSynchronize(f->done));
-    return EPPM_OK;
-}
-
-// the synchronous call's work on the null stream is complete; the next step on any stream starts behind it
-int settle(eppm_plate* f)
-{
-    HIPCHK(hipStreamSynchronize(nullptr));
-    HIPCHK(hipEventRecord(f->done, nullptr));
-    f->last = nullptr;
-    return EPPM_OK;
-}
-
 int slot_check(const eppm_plate* f, int slot, bool need_states, const char* what)
 {
-    if (slot < 0 || slot >= f->nslots) return set_err(EPPM_ERR_ARG, "%s: slot %d, the plate has %d", what, slot, f->nslots);
+    CHK(stage_slot_check(f, slot, what));
     if (need_states && f->empty[slot]) return set_err(EPPM_ERR_STATE, "%s: slot %d is empty", what, slot);
     return EPPM_OK;
 }
@@ -75,17 +52,6 @@ int write_path(eppm_plate* f, int slot, const double* p)
 {
     HIPCHK(hipMemcpy(f->rec(slot)->p, p, 6 * sizeof(double), hipMemcpyHostToDevice));
     return EPPM_OK;
-}
-
-void words_to_rgb(const uint32_t* words, int h, int w, uint8_t* rgb, size_t row_stride)
-{
-    for (int y = 0; y < h; y++) {
-        uint8_t* o = rgb + (size_t)y * row_stride;
-        const uint32_t* q = words + (size_t)y * w;
-        for (int x = 0; x < w; x++) {
-            o[3 * x] = (uint8_t)q[x]; o[3 * x + 1] = (uint8_t)(q[x] >> 8); o[3 * x + 2] = (uint8_t)(q[x] >> 16);
-        }
-    }
 }
 
 }  // namespace
@@ -111,9 +77,8 @@ static int plate_new(int device, int h, int w, int nslots, const eppm_plate_para
     const eppm_plate_params* p = in ? in : &def;
     CHK(plate_params(p, "eppm_plate_create"));
     CHK(size_check(h, w, p->margin_x, p->margin_y, "eppm_plate_create"));
-    if (nslots < 1 || nslots > kTemporalMaxSlots) return set_err(EPPM_ERR_ARG, "eppm_plate_create: %d slots outside [1, %d]", nslots, kTemporalMaxSlots);
-    HIPCHK(hipSetDevice(device));
     eppm_plate* f = new eppm_plate;
+    f->noun = "plate";
     f->device = device; f->h = h; f->w = w; f->nslots = nslots;
     f->ch = h + 2 * p->margin_y; f->cw = w + 2 * p->margin_x;
     f->prm = *p;
@@ -123,40 +88,25 @@ static int plate_new(int device, int h, int w, int nslots, const eppm_plate_para
     f->stride = f->off_rec + up256(sizeof(PlateRec));
     f->off_scratch = f->stride * nslots;
     f->bytes = f->off_scratch + up256(f->cpx() * 4) + up256(f->cpx());
-    f->empty.assign(nslots, 1);
-    f->stepped.assign(nslots, 0);
-    f->fitted.assign(nslots, 0);
     eppm_stab_params sp;
     eppm_stab_default_params(&sp);
     sp.tau = p->tau;
     sp.iters = p->iters;
-    const int rc = eppm_stab_create_size(h, w, nslots, device, &sp, &f->stab);
+    int rc = stage_open(f, "eppm_plate_create", [f] {           // every slot's path starts as the identity
+        PlateRec r{};
+        plate_identity(r.p);
+        hipError_t e = hipSuccess;
+        for (int k = 0; k < f->nslots && e == hipSuccess; k++) e = hipMemcpy(f->rec(k), &r, sizeof r, hipMemcpyHostToDevice);
+        return e;
+    });
+    if (rc == EPPM_OK) rc = eppm_stab_create_size(h, w, nslots, device, &sp, &f->stab);
     if (rc != EPPM_OK) {
-        delete f;
+        eppm_plate_destroy(f);
         return rc;
     }
-    hipError_t e = cache_alloc((void**)&f->mem, f->bytes, false, device);
-    if (e != hipSuccess) {
-        (void)hipGetLastError();
-        const size_t total = f->bytes;
-        eppm_stab_destroy(f->stab);
-        delete f;
-        return set_err(EPPM_ERR_HIP, "hipMalloc of %zu bytes (background plate) failed: %s", total, hipGetErrorString(e));
-    }
-    PlateRec r{};
-    plate_identity(r.p);
-    e = hipEventCreateWithFlags(&f->done, hipEventDisableTiming);
-    for (int k = 0; k < nslots && e == hipSuccess; k++) e = hipMemcpy(f->rec(k), &r, sizeof r, hipMemcpyHostToDevice);
-    if (e == hipSuccess) e = hipEventRecord(f->done, nullptr);
-    if (e != hipSuccess) {
-        (void)hipGetLastError();
-        if (f->done) (void)hipEventDestroy(f->done);
-        (void)hipDeviceSynchronize();
-        cache_free(f->mem, f->bytes, false, device);
-        eppm_stab_destroy(f->stab);
-        delete f;
-        return set_err(EPPM_ERR_HIP, "eppm_plate_create: %s", hipGetErrorString(e));
-    }
+    f->empty.assign(nslots, 1);
+    f->stepped.assign(nslots, 0);
+    f->fitted.assign(nslots, 0);
     *out = f;
     return EPPM_OK;
 }
@@ -180,11 +130,8 @@ extern "C" int eppm_plate_create_size(int h, int w, int nslots, int device, cons
 extern "C" int eppm_plate_destroy(eppm_plate* f)
 {
     if (!f) return EPPM_OK;
-    (void)hipSetDevice(f->device);
-    (void)hipEventSynchronize(f->done);
-    (void)hipEventDestroy(f->done);
     eppm_stab_destroy(f->stab);
-    cache_free(f->mem, f->bytes, false, f->device);
+    stage_close(f);
     delete f;
     return EPPM_OK;
 }
@@ -192,8 +139,8 @@ extern "C" int eppm_plate_destroy(eppm_plate* f)
 extern "C" int eppm_plate_reset(eppm_plate* f, int slot)
 {
     if (!f) return set_err(EPPM_ERR_ARG, "eppm_plate_reset: NULL plate");
-    if (slot >= f->nslots) return set_err(EPPM_ERR_ARG, "eppm_plate_reset: slot %d, the plate has %d", slot, f->nslots);
-    CHK(wait(f));
+    if (slot >= 0) CHK(stage_slot_check(f, slot, "eppm_plate_reset"));
+    CHK(stage_wait(f));
     double id[6];
     plate_identity(id);
     for (int k = 0; k < f->nslots; k++)
@@ -204,7 +151,7 @@ extern "C" int eppm_plate_reset(eppm_plate* f, int slot)
             f->fitted[k] = 0;
         }
     CHK(eppm_stab_reset(f->stab, slot));
-    return settle(f);
+    return stage_settle(f);
 }
 
 extern "C" int eppm_plate_canvas_dims(const eppm_plate* f, int* ch, int* cw)
@@ -215,44 +162,31 @@ extern "C" int eppm_plate_canvas_dims(const eppm_plate* f, int* ch, int* cw)
     return EPPM_OK;
 }
 
-int plate_device(const eppm_plate* f, int* h, int* w, int* nslots)
-{
-    *h = f->h;
-    *w = f->w;
-    *nslots = f->nslots;
-    return f->device;
-}
-
 // one step of slots slot0 .. slot0 + in.n - 1 on stream s; in: the pairs' planes (the other members are filled in here); cut: NULL or one
 // flag per pair.  timing: the context whose stage-timing entries receive the stages, or NULL
-int plate_step_on(eppm_plate* f, PlateArgs& in, int slot0, const uint8_t* cut, hipStream_t s, eppm_ctx* timing)
+static int step_on(eppm_plate* f, PlateArgs& in, int slot0, const uint8_t* cut, hipStream_t s, eppm_ctx* timing)
 {
     in.mem = f->mem;
     in.slot_stride = f->stride; in.off_b = f->off_b; in.off_rec = f->off_rec;
     in.h = f->h; in.w = f->w; in.ch = f->ch; in.cw = f->cw; in.mx = f->prm.margin_x; in.my = f->prm.margin_y; in.slot0 = slot0;
     in.grow = f->prm.grow; in.accept_invalid = f->prm.accept_invalid; in.n_max = f->prm.n_max; in.min_count = f->prm.min_count;
     in.thresh = f->prm.thresh;
-    memset(in.empty, 0, sizeof(in.empty));
-    memset(in.cut, 0, sizeof(in.cut));
-    for (int k = slot0; k < slot0 + in.n; k++) {
-        const uint32_t bit = 1u << (k & 31);
-        if (f->empty[k]) in.empty[k >> 5] |= bit;
-        if (cut && cut[k - slot0]) in.cut[k >> 5] |= bit;
+    slot_mask(in.empty, f->empty.data() + slot0, slot0, in.n);
+    slot_mask(in.cut, cut, slot0, in.n);
+    CHK(stage_enter(f, s));
+    {
+        StageTimer t(timing, "plate_block");
+        launch_plate_block(in, s);
     }
-    if (s != f->last) HIPCHK(hipStreamWaitEvent(s, f->done, 0));
-    if (timing) ctx_stage_begin(timing, "plate_block");
-    launch_plate_block(in, s);
-    if (timing) ctx_stage_end(timing);
-    if (timing) ctx_stage_begin(timing, "plate_accumulate");
-    in.phase = 0;
-    launch_plate_path(in, s);
-    launch_plate_accumulate(in, s);
-    in.phase = 1;
-    launch_plate_path(in, s);
-    if (timing) ctx_stage_end(timing);
-    HIPCHK(hipGetLastError());
-    HIPCHK(hipEventRecord(f->done, s));
-    f->last = s;
+    {
+        StageTimer t(timing, "plate_accumulate");
+        in.phase = 0;
+        launch_plate_path(in, s);
+        launch_plate_accumulate(in, s);
+        in.phase = 1;
+        launch_plate_path(in, s);
+    }
+    CHK(stage_leave(f, s));
     for (int k = slot0; k < slot0 + in.n; k++) f->empty[k] = 0, f->stepped[k] = 1, f->fitted[k] = in.model != nullptr;
     return EPPM_OK;
 }
@@ -260,37 +194,41 @@ int plate_step_on(eppm_plate* f, PlateArgs& in, int slot0, const uint8_t* cut, h
 extern "C" int eppm_plate_step(eppm_plate* f, eppm_ctx* ctx, const uint8_t* cut)
 {
     if (!f || !ctx) return set_err(EPPM_ERR_ARG, "eppm_plate_step: NULL argument");
-    StabArgs sin{};                     // the stabiliser's view of a context (image 2, the forward flow, occ1) ...
-    TFilterArgs t{};                    // ... and the temporal filter's, for image 1
+    CtxPlanes c;
     hipStream_t s;
-    CHK(ctx_stab_inputs(ctx, f->h, f->w, f->device, f->nslots, "eppm_plate_step", &sin, &s));
-    CHK(ctx_tfilter_inputs(ctx, f->h, f->w, f->device, f->nslots, "eppm_plate_step", &t, &s));
+    CHK(ctx_stage_inputs(ctx, f, "eppm_plate_step", &c, &s));
     PlateArgs in{};
-    in.img1 = t.img1; in.img_pitch = t.img_pitch; in.img_stride = t.img_stride;
-    in.n = sin.n;
-    ctx_stage_begin(ctx, "plate_fit");
-    const int rc = stab_step_on(f->stab, sin, 0, cut, s, nullptr);
-    ctx_stage_end(ctx);
-    CHK(rc);
+    in.img1 = c.img1; in.img_pitch = c.img_pitch; in.img_stride = c.img_stride;
+    in.n = c.n;
+    {
+        StageTimer t(ctx, "plate_fit");
+        StabArgs sin = stab_ctx_args(c);
+        CHK(stab_step_on(f->stab, sin, 0, cut, s, nullptr));
+    }
     in.mask = stab_mask_device(f->stab, &in.mask_stride);
     in.model = stab_model_device(f->stab, &in.model_stride);
-    return plate_step_on(f, in, 0, cut, s, ctx);
+    return step_on(f, in, 0, cut, s, ctx);
 }
 
-// the step of eppm_plate_step_frames on the launcher stream s (launchers_ref_abi.cpp): path NULL: the slot's own
-int plate_step_frames_on(eppm_plate* f, int slot, const void* d_rgba, size_t pitch, const uint8_t* d_mask, const double* path, int cut, hipStream_t s)
+// the kernels alone for one slot on caller planes, without a fit, on the launcher stream; path NULL: the slot's own
+extern "C" int eppm_plate_step_frames(eppm_plate* f, int slot, const void* d_rgba, size_t pitch, const uint8_t* d_mask, const double* path, int cut)
 {
-    if (path) {
-        CHK(wait(f));
-        CHK(write_path(f, slot, path));
-        CHK(settle(f));
-    }
-    PlateArgs in{};
-    in.img1 = (const uint8_t*)d_rgba; in.img_pitch = pitch;
-    in.mask = d_mask;
-    in.n = 1;
-    const uint8_t c = cut != 0;
-    return plate_step_on(f, in, slot, &c, s, nullptr);
+    if (!f || !d_rgba || !d_mask) return set_err(EPPM_ERR_ARG, "eppm_plate_step_frames: NULL argument");
+    CHK(slot_check(f, slot, false, "eppm_plate_step_frames"));
+    if (bad_pitch(pitch, f->w)) return set_err(EPPM_ERR_ARG, "eppm_plate_step_frames: bad pitch %zu", pitch);
+    return launcher_run(f, "eppm_plate_step_frames", [&](hipStream_t s) {
+        if (path) {
+            CHK(stage_wait(f));
+            CHK(write_path(f, slot, path));
+            CHK(stage_settle(f));
+        }
+        PlateArgs in{};
+        in.img1 = (const uint8_t*)d_rgba; in.img_pitch = pitch;
+        in.mask = d_mask;
+        in.n = 1;
+        const uint8_t c = cut != 0;
+        return step_on(f, in, slot, &c, s, nullptr);
+    });
 }
 
 // a render of one slot on stream s into (out, fill); path NULL: the forms of the slot's last step with its blocked plane (mask NULL), or
@@ -298,7 +236,7 @@ int plate_step_frames_on(eppm_plate* f, int slot, const void* d_rgba, size_t pit
 static int render_on(eppm_plate* f, int slot, const uint8_t* img1, size_t pitch, const uint8_t* d_mask, const double* path, uint32_t* out, size_t out_pitch,
                      uint8_t* fill, hipStream_t s, eppm_ctx* timing)
 {
-    CHK(wait(f));
+    CHK(stage_wait(f));
     PlateRec r;
     HIPCHK(hipMemcpy(&r, f->rec(slot), sizeof r, hipMemcpyDeviceToHost));
     PlateRenderArgs a{};
@@ -314,31 +252,35 @@ static int render_on(eppm_plate* f, int slot, const uint8_t* img1, size_t pitch,
     a.blocked = (const uint8_t*)(f->block(slot) + (d_mask ? f->off_br : f->off_b));
     a.out = out; a.out_pitch = out_pitch; a.fill = fill;
     a.h = f->h; a.w = f->w; a.ch = f->ch; a.cw = f->cw; a.mx = f->prm.margin_x; a.my = f->prm.margin_y; a.min_count = f->prm.min_count;
-    if (timing) ctx_stage_begin(timing, "plate_render");
-    if (d_mask) {
-        PlateArgs b{};
-        b.mask = d_mask;
-        b.mem = f->mem; b.slot_stride = f->stride; b.off_b = f->off_br;
-        b.h = f->h; b.w = f->w; b.n = 1; b.slot0 = slot;
-        b.grow = f->prm.grow; b.accept_invalid = f->prm.accept_invalid;
-        launch_plate_block(b, s);
+    CHK(stage_enter(f, s));
+    {
+        StageTimer t(timing, "plate_render");
+        if (d_mask) {
+            PlateArgs b{};
+            b.mask = d_mask;
+            b.mem = f->mem; b.slot_stride = f->stride; b.off_b = f->off_br;
+            b.h = f->h; b.w = f->w; b.n = 1; b.slot0 = slot;
+            b.grow = f->prm.grow; b.accept_invalid = f->prm.accept_invalid;
+            launch_plate_block(b, s);
+        }
+        launch_plate_render(a, s);
     }
-    launch_plate_render(a, s);
-    if (timing) ctx_stage_end(timing);
-    HIPCHK(hipGetLastError());
-    HIPCHK(hipEventRecord(f->done, s));
-    f->last = s;
+    CHK(stage_leave(f, s));
     HIPCHK(hipStreamSynchronize(s));
     return EPPM_OK;
 }
 
-int plate_render_frames_on(eppm_plate* f, int slot, const void* d_rgba, size_t pitch, const uint8_t* d_mask, const double* path, void* d_out, size_t out_pitch,
-                           uint8_t* d_fill, hipStream_t s)
+// the render alone on caller planes against the slot's canvas, on the launcher stream (render_on waits for it itself)
+extern "C" int eppm_plate_render_frames(eppm_plate* f, int slot, const void* d_rgba, size_t pitch, const uint8_t* d_mask, const double* path, void* d_rgba_out,
+                                        size_t out_pitch, uint8_t* d_fill)
 {
-    return render_on(f, slot, (const uint8_t*)d_rgba, pitch, d_mask, path, (uint32_t*)d_out, out_pitch, d_fill, s, nullptr);
+    if (!f || !d_rgba || !d_mask || !d_rgba_out || !d_fill) return set_err(EPPM_ERR_ARG, "eppm_plate_render_frames: NULL argument");
+    CHK(slot_check(f, slot, true, "eppm_plate_render_frames"));
+    if (bad_pitch(pitch, f->w) || bad_pitch(out_pitch, f->w)) return set_err(EPPM_ERR_ARG, "eppm_plate_render_frames: bad pitch %zu / %zu", pitch, out_pitch);
+    return launcher_run(f, "eppm_plate_render_frames", [&](hipStream_t s) {
+        return render_on(f, slot, (const uint8_t*)d_rgba, pitch, d_mask, path, (uint32_t*)d_rgba_out, out_pitch, d_fill, s, nullptr);
+    }, false);
 }
-
-int plate_slot_check(const eppm_plate* f, int slot, bool need_states, const char* what) { return slot_check(f, slot, need_states, what); }
 
 extern "C" int eppm_plate_render(eppm_plate* f, eppm_ctx* ctx, int slot, uint8_t* rgb, size_t row_stride, uint8_t* fill)
 {
@@ -346,14 +288,12 @@ extern "C" int eppm_plate_render(eppm_plate* f, eppm_ctx* ctx, int slot, uint8_t
     CHK(slot_check(f, slot, true, "eppm_plate_render"));
     if (!f->stepped[slot]) return set_err(EPPM_ERR_STATE, "eppm_plate_render: slot %d has not been stepped", slot);
     if (row_stride < (size_t)f->w * 3) return set_err(EPPM_ERR_ARG, "eppm_plate_render: row_stride %zu < 3*w", row_stride);
-    TFilterArgs t{};
+    CtxPlanes c;
     hipStream_t s;
-    CHK(ctx_tfilter_inputs(ctx, f->h, f->w, f->device, f->nslots, "eppm_plate_render", &t, &s));
-    if (slot >= t.n) return set_err(EPPM_ERR_ARG, "eppm_plate_render: slot %d, the context has %d active pairs", slot, t.n);
-    CHK(render_on(f, slot, t.img1 + (size_t)slot * t.img_stride, t.img_pitch, nullptr, nullptr, f->scratch_words(), (size_t)f->w * 4, f->scratch_bytes(), s, ctx));
-    std::vector<uint32_t> words(f->px());
-    HIPCHK(hipMemcpy(words.data(), f->scratch_words(), f->px() * 4, hipMemcpyDeviceToHost));
-    words_to_rgb(words.data(), f->h, f->w, rgb, row_stride);
+    CHK(ctx_stage_inputs(ctx, f, "eppm_plate_render", &c, &s));
+    if (slot >= c.n) return set_err(EPPM_ERR_ARG, "eppm_plate_render: slot %d, the context has %d active pairs", slot, c.n);
+    CHK(render_on(f, slot, c.img1 + (size_t)slot * c.img_stride, c.img_pitch, nullptr, nullptr, f->scratch_words(), (size_t)f->w * 4, f->scratch_bytes(), s, ctx));
+    CHK(stage_get_rgb(f, f->scratch_words(), f->h, f->w, rgb, row_stride));
     if (fill) HIPCHK(hipMemcpy(fill, f->scratch_bytes(), f->px(), hipMemcpyDeviceToHost));
     return EPPM_OK;
 }
@@ -363,26 +303,24 @@ extern "C" int eppm_plate_get(eppm_plate* f, int slot, uint8_t* rgb, size_t row_
     if (!f || !rgb) return set_err(EPPM_ERR_ARG, "eppm_plate_get: NULL argument");
     CHK(slot_check(f, slot, true, "eppm_plate_get"));
     if (row_stride < (size_t)f->cw * 3) return set_err(EPPM_ERR_ARG, "eppm_plate_get: row_stride %zu < 3 * canvas width", row_stride);
-    CHK(wait(f));
+    CHK(stage_wait(f));
     launch_plate_word(f->block(slot), f->scratch_words(), f->scratch_bytes(), f->ch, f->cw, nullptr);
     HIPCHK(hipGetLastError());
-    std::vector<uint32_t> words(f->cpx());
-    HIPCHK(hipMemcpy(words.data(), f->scratch_words(), f->cpx() * 4, hipMemcpyDeviceToHost));
-    words_to_rgb(words.data(), f->ch, f->cw, rgb, row_stride);
+    CHK(stage_get_rgb(f, f->scratch_words(), f->ch, f->cw, rgb, row_stride));
     if (coverage) HIPCHK(hipMemcpy(coverage, f->scratch_bytes(), f->cpx(), hipMemcpyDeviceToHost));
-    return settle(f);
+    return stage_settle(f);
 }
 
 extern "C" int eppm_plate_get_device(eppm_plate* f, int slot, void* d_rgba, size_t pitch)
 {
     if (!f || !d_rgba) return set_err(EPPM_ERR_ARG, "eppm_plate_get_device: NULL argument");
     CHK(slot_check(f, slot, true, "eppm_plate_get_device"));
-    if (pitch < (size_t)f->cw * 4 || (pitch & 3)) return set_err(EPPM_ERR_ARG, "eppm_plate_get_device: bad pitch %zu", pitch);
-    CHK(wait(f));
+    if (bad_pitch(pitch, f->cw)) return set_err(EPPM_ERR_ARG, "eppm_plate_get_device: bad pitch %zu", pitch);
+    CHK(stage_wait(f));
     launch_plate_word(f->block(slot), f->scratch_words(), f->scratch_bytes(), f->ch, f->cw, nullptr);
     HIPCHK(hipGetLastError());
     HIPCHK(hipMemcpy2D(d_rgba, pitch, f->scratch_words(), (size_t)f->cw * 4, (size_t)f->cw * 4, f->ch, hipMemcpyDeviceToDevice));
-    return settle(f);
+    return stage_settle(f);
 }
 
 extern "C" int eppm_plate_get_mask(eppm_plate* f, int slot, uint8_t* mask)
@@ -390,7 +328,7 @@ extern "C" int eppm_plate_get_mask(eppm_plate* f, int slot, uint8_t* mask)
     if (!f || !mask) return set_err(EPPM_ERR_ARG, "eppm_plate_get_mask: NULL argument");
     CHK(slot_check(f, slot, true, "eppm_plate_get_mask"));
     if (!f->fitted[slot]) return set_err(EPPM_ERR_STATE, "eppm_plate_get_mask: the last step of slot %d had no fit", slot);
-    CHK(wait(f));
+    CHK(stage_wait(f));
     return eppm_stab_get_mask(f->stab, slot, mask);
 }
 
@@ -398,7 +336,7 @@ extern "C" int eppm_plate_get_path(eppm_plate* f, int slot, double* path)
 {
     if (!f || !path) return set_err(EPPM_ERR_ARG, "eppm_plate_get_path: NULL argument");
     CHK(slot_check(f, slot, false, "eppm_plate_get_path"));
-    CHK(wait(f));
+    CHK(stage_wait(f));
     HIPCHK(hipMemcpy(path, f->rec(slot)->p, 6 * sizeof(double), hipMemcpyDeviceToHost));
     return EPPM_OK;
 }
@@ -407,16 +345,16 @@ extern "C" int eppm_plate_set_path(eppm_plate* f, int slot, const double* path)
 {
     if (!f || !path) return set_err(EPPM_ERR_ARG, "eppm_plate_set_path: NULL argument");
     CHK(slot_check(f, slot, false, "eppm_plate_set_path"));
-    CHK(wait(f));
+    CHK(stage_wait(f));
     CHK(write_path(f, slot, path));
-    return settle(f);
+    return stage_settle(f);
 }
 
 extern "C" int eppm_plate_get_state(eppm_plate* f, int slot, float* state)
 {
     if (!f || !state) return set_err(EPPM_ERR_ARG, "eppm_plate_get_state: NULL argument");
     CHK(slot_check(f, slot, true, "eppm_plate_get_state"));
-    CHK(wait(f));
+    CHK(stage_wait(f));
     HIPCHK(hipMemcpy(state, f->block(slot), f->cpx() * sizeof(TfState), hipMemcpyDeviceToHost));
     return EPPM_OK;
 }
@@ -425,9 +363,9 @@ extern "C" int eppm_plate_set_state(eppm_plate* f, int slot, const float* state)
 {
     if (!f || !state) return set_err(EPPM_ERR_ARG, "eppm_plate_set_state: NULL argument");
     CHK(slot_check(f, slot, false, "eppm_plate_set_state"));
-    CHK(wait(f));
+    CHK(stage_wait(f));
     HIPCHK(hipMemcpy(f->block(slot), state, f->cpx() * sizeof(TfState), hipMemcpyHostToDevice));
-    CHK(settle(f));
+    CHK(stage_settle(f));
     f->empty[slot] = 0;
     return EPPM_OK;
 }

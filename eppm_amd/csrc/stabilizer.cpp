@@ -1,7 +1,7 @@
-// stabilizer.cpp -- global camera motion and video stabilisation: eppm_stab, its one allocation, its step on a
-// context's pairs (the kernels: k_gmotion.hip), the synchronous calls, and the host forms eppm_gmotion_fit_host / eppm_stab_update_host /
+// stabilizer.cpp -- global camera motion and video stabilisation: eppm_stab (a stage object, stage_object.h), its step on a
+// context's pairs or on caller planes (the kernels: k_gmotion.hip), the synchronous calls, and the host forms eppm_gmotion_fit_host / eppm_stab_update_host /
 // eppm_stab_warp_host.  The host forms share gmotion.h's arithmetic with the kernels.
-#include "api_internal.h"
+#include "stage_object.h"
 #include "gmotion.h"
 
 using namespace eppm;
@@ -9,17 +9,12 @@ using namespace eppm;
 static_assert(sizeof(GmModel) == 96 && sizeof(GmState) == 144, "the model and the state fill 240 of their 256 bytes");
 static_assert(kGmSums * 8 <= kGmSlabBytes, "a slab holds the twelve sums");
 
-struct eppm_stab {
-    int device = 0, h = 0, w = 0, nslots = 0;
+struct eppm_stab : StageObject {        // mem: nslots blocks `stride` bytes apart: slabs | model, state (256 B) | out (h*w RGBA words) | mask (h*w bytes)
     float tau = 0.0f, tau2 = 0.0f, smooth = 0.0f;
     int iters = 0;
     int tiles_x = 0, tiles_y = 0;
-    char* mem = nullptr;                // nslots blocks `stride` bytes apart: slabs | model, state (256 B) | out (h*w RGBA words) | mask (h*w bytes)
-    size_t bytes = 0, stride = 0, off_model = 0, off_out = 0, off_mask = 0;
+    size_t stride = 0, off_model = 0, off_out = 0, off_mask = 0;
     std::vector<uint8_t> empty, stepped;    // per slot: it has no path (its state counts as the identity) / it has an output, a mask and a model
-    hipEvent_t done = nullptr;          // recorded after every step: the synchronous calls wait for it
-    hipStream_t last = nullptr;         // the stream of the last step: a step on another stream waits for `done` first
-    size_t px() const { return (size_t)h * w; }
     char* block(int slot) const { return mem + (size_t)slot * stride; }
     GmModel* model(int slot) const { return (GmModel*)(block(slot) + off_model); }
     GmState* state(int slot) const { return (GmState*)(block(slot) + off_model + sizeof(GmModel)); }
@@ -44,17 +39,9 @@ int size_check(int h, int w, const char* what)
     return EPPM_OK;
 }
 
-// the stabiliser's last step is complete (the synchronous calls read and write its planes on the null stream)
-int wait(eppm_stab* f)
-{
-    HIPCHK(hipSetDevice(f->device));
-    HIPCHK(hipEventSynchronize(f->done));
-    return EPPM_OK;
-}
-
 int slot_check(const eppm_stab* f, int slot, bool need_step, const char* what)
 {
-    if (slot < 0 || slot >= f->nslots) return set_err(EPPM_ERR_ARG, "%s: slot %d, the stabiliser has %d", what, slot, f->nslots);
+    CHK(stage_slot_check(f, slot, what));
     if (need_step && !f->stepped[slot]) return set_err(EPPM_ERR_STATE, "%s: slot %d has not been stepped", what, slot);
     return EPPM_OK;
 }
@@ -83,36 +70,24 @@ static int stab_new(int device, int h, int w, int nslots, const eppm_stab_params
     const eppm_stab_params* p = in ? in : &def;
     CHK(stab_params(p, "eppm_stab_create"));
     CHK(size_check(h, w, "eppm_stab_create"));
-    if (nslots < 1 || nslots > kTemporalMaxSlots) return set_err(EPPM_ERR_ARG, "eppm_stab_create: %d slots outside [1, %d]", nslots, kTemporalMaxSlots);
-    HIPCHK(hipSetDevice(device));
     eppm_stab* f = new eppm_stab;
+    f->noun = "stabiliser";
     f->device = device; f->h = h; f->w = w; f->nslots = nslots;
     f->tau = p->tau; f->tau2 = p->tau * p->tau; f->iters = p->iters; f->smooth = p->smooth;
     f->tiles_x = (w + kGmTileW - 1) / kGmTileW;
     f->tiles_y = (h + kGmTileH - 1) / kGmTileH;
-    f->off_model = ((size_t)f->tiles_x * f->tiles_y * kGmSlabBytes + 255) & ~(size_t)255;
+    f->off_model = up256((size_t)f->tiles_x * f->tiles_y * kGmSlabBytes);
     f->off_out = f->off_model + 256;
     f->off_mask = f->off_out + f->px() * 4;
-    f->stride = (f->off_mask + f->px() + 255) & ~(size_t)255;
+    f->stride = up256(f->off_mask + f->px());
     f->bytes = f->stride * nslots;
+    const int rc = stage_open(f, "eppm_stab_create");
+    if (rc != EPPM_OK) {
+        delete f;
+        return rc;
+    }
     f->empty.assign(nslots, 1);
     f->stepped.assign(nslots, 0);
-    hipError_t e = cache_alloc((void**)&f->mem, f->bytes, false, device);
-    if (e != hipSuccess) {
-        (void)hipGetLastError();
-        const size_t bytes = f->bytes;
-        delete f;
-        return set_err(EPPM_ERR_HIP, "hipMalloc of %zu bytes (stabiliser) failed: %s", bytes, hipGetErrorString(e));
-    }
-    e = hipEventCreateWithFlags(&f->done, hipEventDisableTiming);
-    if (e == hipSuccess) e = hipEventRecord(f->done, nullptr);
-    if (e != hipSuccess) {
-        (void)hipGetLastError();
-        if (f->done) (void)hipEventDestroy(f->done);
-        cache_free(f->mem, f->bytes, false, device);
-        delete f;
-        return set_err(EPPM_ERR_HIP, "eppm_stab_create: %s", hipGetErrorString(e));
-    }
     *out = f;
     return EPPM_OK;
 }
@@ -136,10 +111,7 @@ extern "C" int eppm_stab_create_size(int h, int w, int nslots, int device, const
 extern "C" int eppm_stab_destroy(eppm_stab* f)
 {
     if (!f) return EPPM_OK;
-    (void)hipSetDevice(f->device);
-    (void)hipEventSynchronize(f->done);
-    (void)hipEventDestroy(f->done);
-    cache_free(f->mem, f->bytes, false, f->device);
+    stage_close(f);
     delete f;
     return EPPM_OK;
 }
@@ -147,18 +119,10 @@ extern "C" int eppm_stab_destroy(eppm_stab* f)
 extern "C" int eppm_stab_reset(eppm_stab* f, int slot)
 {
     if (!f) return set_err(EPPM_ERR_ARG, "eppm_stab_reset: NULL stabiliser");
-    if (slot >= f->nslots) return set_err(EPPM_ERR_ARG, "eppm_stab_reset: slot %d, the stabiliser has %d", slot, f->nslots);
+    if (slot >= 0) CHK(stage_slot_check(f, slot, "eppm_stab_reset"));
     for (int k = 0; k < f->nslots; k++)
         if (slot < 0 || k == slot) f->empty[k] = 1, f->stepped[k] = 0;
     return EPPM_OK;
-}
-
-int stab_device(const eppm_stab* f, int* h, int* w, int* nslots)
-{
-    *h = f->h;
-    *w = f->w;
-    *nslots = f->nslots;
-    return f->device;
 }
 
 const uint8_t* stab_mask_device(const eppm_stab* f, size_t* slot_stride)
@@ -173,6 +137,17 @@ const char* stab_model_device(const eppm_stab* f, size_t* slot_stride)
     return (const char*)f->model(0);
 }
 
+// what a stabiliser reads of a context: image 2, the forward flow and occ1 of every active pair
+StabArgs stab_ctx_args(const CtxPlanes& c)
+{
+    StabArgs in{};
+    in.img2 = c.img2; in.img_pitch = c.img_pitch; in.img_stride = c.img_stride;
+    in.fwd = c.fwd; in.fwd_stride = c.fwd_stride;
+    in.occ1 = c.occ1; in.occ_stride = c.occ_stride;
+    in.n = c.n;
+    return in;
+}
+
 // one step of slots slot0 .. slot0 + in.n - 1 on stream s; in: the pairs' planes (the other members are filled in here); cut: NULL or one
 // flag per pair.  timing: the context whose stage-timing entries receive the stages, or NULL
 int stab_step_on(eppm_stab* f, StabArgs& in, int slot0, const uint8_t* cut, hipStream_t s, eppm_ctx* timing)
@@ -182,26 +157,21 @@ int stab_step_on(eppm_stab* f, StabArgs& in, int slot0, const uint8_t* cut, hipS
     in.h = f->h; in.w = f->w; in.slot0 = slot0;
     in.tiles_x = f->tiles_x; in.tiles_y = f->tiles_y;
     in.iters = f->iters; in.tau2 = f->tau2; in.smooth = f->smooth;
-    memset(in.empty, 0, sizeof(in.empty));
-    memset(in.cut, 0, sizeof(in.cut));
-    for (int k = slot0; k < slot0 + in.n; k++) {
-        const uint32_t bit = 1u << (k & 31);
-        if (f->empty[k]) in.empty[k >> 5] |= bit;
-        if (cut && cut[k - slot0]) in.cut[k >> 5] |= bit;
+    slot_mask(in.empty, f->empty.data() + slot0, slot0, in.n);
+    slot_mask(in.cut, cut, slot0, in.n);
+    CHK(stage_enter(f, s));
+    {
+        StageTimer t(timing, "stab_fit");
+        for (in.pass = 0; in.pass < f->iters; in.pass++) {
+            launch_gmotion_accumulate(in, s);
+            launch_gmotion_solve(in, s);
+        }
     }
-    if (s != f->last) HIPCHK(hipStreamWaitEvent(s, f->done, 0));
-    if (timing) ctx_stage_begin(timing, "stab_fit");
-    for (in.pass = 0; in.pass < f->iters; in.pass++) {
-        launch_gmotion_accumulate(in, s);
-        launch_gmotion_solve(in, s);
+    {
+        StageTimer t(timing, "stab_warp");
+        launch_stab_warp(in, s);
     }
-    if (timing) ctx_stage_end(timing);
-    if (timing) ctx_stage_begin(timing, "stab_warp");
-    launch_stab_warp(in, s);
-    if (timing) ctx_stage_end(timing);
-    HIPCHK(hipGetLastError());
-    HIPCHK(hipEventRecord(f->done, s));
-    f->last = s;
+    CHK(stage_leave(f, s));
     for (int k = slot0; k < slot0 + in.n; k++) f->empty[k] = 0, f->stepped[k] = 1;
     return EPPM_OK;
 }
@@ -209,10 +179,27 @@ int stab_step_on(eppm_stab* f, StabArgs& in, int slot0, const uint8_t* cut, hipS
 extern "C" int eppm_stab_step(eppm_stab* f, eppm_ctx* ctx, const uint8_t* cut)
 {
     if (!f || !ctx) return set_err(EPPM_ERR_ARG, "eppm_stab_step: NULL argument");
-    StabArgs in{};
+    CtxPlanes c;
     hipStream_t s;
-    CHK(ctx_stab_inputs(ctx, f->h, f->w, f->device, f->nslots, "eppm_stab_step", &in, &s));
+    CHK(ctx_stage_inputs(ctx, f, "eppm_stab_step", &c, &s));
+    StabArgs in = stab_ctx_args(c);
     return stab_step_on(f, in, 0, cut, s, ctx);
+}
+
+// one step of one slot on caller planes, on the launcher stream
+extern "C" int eppm_stab_step_frames(eppm_stab* f, int slot, const void* d_rgba2, size_t pitch, const eppm_float2* d_flow, const uint8_t* d_occ1, int cut)
+{
+    if (!f || !d_rgba2 || !d_flow || !d_occ1) return set_err(EPPM_ERR_ARG, "eppm_stab_step_frames: NULL argument");
+    CHK(stage_slot_check(f, slot, "eppm_stab_step_frames"));
+    if (bad_pitch(pitch, f->w)) return set_err(EPPM_ERR_ARG, "eppm_stab_step_frames: bad pitch %zu", pitch);
+    return launcher_run(f, "eppm_stab_step_frames", [&](hipStream_t s) {
+        StabArgs in{};
+        in.img2 = (const uint8_t*)d_rgba2; in.img_pitch = pitch;
+        in.fwd = (const float*)d_flow; in.occ1 = d_occ1;
+        in.n = 1;
+        const uint8_t c = cut != 0;
+        return stab_step_on(f, in, slot, &c, s, nullptr);
+    });
 }
 
 extern "C" int eppm_stab_get(eppm_stab* f, int slot, uint8_t* rgb, size_t row_stride)
@@ -220,36 +207,22 @@ extern "C" int eppm_stab_get(eppm_stab* f, int slot, uint8_t* rgb, size_t row_st
     if (!f || !rgb) return set_err(EPPM_ERR_ARG, "eppm_stab_get: NULL argument");
     CHK(slot_check(f, slot, true, "eppm_stab_get"));
     if (row_stride < (size_t)f->w * 3) return set_err(EPPM_ERR_ARG, "eppm_stab_get: row_stride %zu < 3*w", row_stride);
-    CHK(wait(f));
-    std::vector<uint32_t> words(f->px());
-    HIPCHK(hipMemcpy(words.data(), f->out(slot), f->px() * 4, hipMemcpyDeviceToHost));
-    for (int y = 0; y < f->h; y++) {
-        uint8_t* o = rgb + (size_t)y * row_stride;
-        const uint32_t* q = words.data() + (size_t)y * f->w;
-        for (int x = 0; x < f->w; x++) {
-            o[3 * x] = (uint8_t)q[x]; o[3 * x + 1] = (uint8_t)(q[x] >> 8); o[3 * x + 2] = (uint8_t)(q[x] >> 16);
-        }
-    }
-    return EPPM_OK;
+    return stage_get_rgb(f, f->out(slot), f->h, f->w, rgb, row_stride);
 }
 
 extern "C" int eppm_stab_get_device(eppm_stab* f, int slot, void* d_rgba, size_t pitch)
 {
     if (!f || !d_rgba) return set_err(EPPM_ERR_ARG, "eppm_stab_get_device: NULL argument");
     CHK(slot_check(f, slot, true, "eppm_stab_get_device"));
-    if (pitch < (size_t)f->w * 4 || (pitch & 3)) return set_err(EPPM_ERR_ARG, "eppm_stab_get_device: bad pitch %zu", pitch);
-    HIPCHK(hipSetDevice(f->device));
-    // on the stream of the last step, behind it; the next step on any stream waits for the copy
-    HIPCHK(hipMemcpy2DAsync(d_rgba, pitch, f->out(slot), (size_t)f->w * 4, (size_t)f->w * 4, f->h, hipMemcpyDeviceToDevice, f->last));
-    HIPCHK(hipEventRecord(f->done, f->last));
-    return EPPM_OK;
+    if (bad_pitch(pitch, f->w)) return set_err(EPPM_ERR_ARG, "eppm_stab_get_device: bad pitch %zu", pitch);
+    return stage_get_rgba_device(f, f->out(slot), f->h, f->w, d_rgba, pitch);
 }
 
 extern "C" int eppm_stab_get_mask(eppm_stab* f, int slot, uint8_t* mask)
 {
     if (!f || !mask) return set_err(EPPM_ERR_ARG, "eppm_stab_get_mask: NULL argument");
     CHK(slot_check(f, slot, true, "eppm_stab_get_mask"));
-    CHK(wait(f));
+    CHK(stage_wait(f));
     HIPCHK(hipMemcpy(mask, f->mask(slot), f->px(), hipMemcpyDeviceToHost));
     return EPPM_OK;
 }
@@ -258,7 +231,7 @@ extern "C" int eppm_stab_get_model(eppm_stab* f, int slot, eppm_gmotion_model* m
 {
     if (!f || !model) return set_err(EPPM_ERR_ARG, "eppm_stab_get_model: NULL argument");
     CHK(slot_check(f, slot, true, "eppm_stab_get_model"));
-    CHK(wait(f));
+    CHK(stage_wait(f));
     GmModel m;
     HIPCHK(hipMemcpy(&m, f->model(slot), sizeof m, hipMemcpyDeviceToHost));
     model_out(model, m);
@@ -272,7 +245,7 @@ extern "C" int eppm_stab_get_path(eppm_stab* f, int slot, double* path, int64_t*
     GmState st;
     if (f->empty[slot]) gm_identity(&st);
     else {
-        CHK(wait(f));
+        CHK(stage_wait(f));
         HIPCHK(hipMemcpy(&st, f->state(slot), sizeof st, hipMemcpyDeviceToHost));
     }
     for (int k = 0; k < 6; k++) path[k] = st.c[k], path[6 + k] = st.s[k];
@@ -285,15 +258,13 @@ extern "C" int eppm_stab_set_path(eppm_stab* f, int slot, const double* path)
 {
     if (!f || !path) return set_err(EPPM_ERR_ARG, "eppm_stab_set_path: NULL argument");
     CHK(slot_check(f, slot, false, "eppm_stab_set_path"));
-    CHK(wait(f));
+    CHK(stage_wait(f));
     GmState st;
     gm_identity(&st);
     for (int k = 0; k < 6; k++) st.c[k] = path[k], st.s[k] = path[6 + k], st.wf[k] = 0.0f;
     st.pad[0] = st.pad[1] = 0;
     HIPCHK(hipMemcpy(f->state(slot), &st, sizeof st, hipMemcpyHostToDevice));
-    HIPCHK(hipStreamSynchronize(nullptr));
-    HIPCHK(hipEventRecord(f->done, nullptr));
-    f->last = nullptr;
+    CHK(stage_settle(f));
     f->empty[slot] = 0;
     return EPPM_OK;
 }

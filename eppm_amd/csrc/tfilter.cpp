@@ -1,21 +1,16 @@
-// tfilter.cpp -- motion-compensated temporal denoising: eppm_tfilter, its one allocation, its step on a context's
-// pairs (the kernel: k_tfilter.hip), the synchronous state calls, and the host forms eppm_tfilter_seed_host / eppm_tfilter_step_host.  The
-// host form shares tfilter.h's per-pixel arithmetic with the kernel.
-#include "api_internal.h"
+// tfilter.cpp -- motion-compensated temporal denoising: eppm_tfilter (a stage object, stage_object.h), its step on
+// a context's pairs or on caller planes (the kernel: k_tfilter.hip), the synchronous state calls, and the host forms
+// eppm_tfilter_seed_host / eppm_tfilter_step_host.  The host form shares tfilter.h's per-pixel arithmetic with the kernel.
+#include "stage_object.h"
 #include "tfilter.h"
 
 using namespace eppm;
 
-struct eppm_tfilter {
-    int device = 0, h = 0, w = 0, nslots = 0;
+struct eppm_tfilter : StageObject {     // mem: nslots blocks `stride` bytes apart: state 0 | state 1 (h*w float4 each) | out (h*w RGBA words)
     float thresh = 0.0f;
     int n_max = 0;
-    char* mem = nullptr;                // nslots blocks `stride` bytes apart: state 0 | state 1 (h*w float4 each) | out (h*w RGBA words)
-    size_t bytes = 0, stride = 0;
+    size_t stride = 0;
     std::vector<uint8_t> cur, empty;    // per slot: which state is current, and whether the slot has one at all
-    hipEvent_t done = nullptr;          // recorded after every step: the synchronous calls wait for it
-    hipStream_t last = nullptr;         // the stream of the last step: a step on another stream waits for `done` first
-    size_t px() const { return (size_t)h * w; }
     float* state(int slot, int which) const { return (float*)(mem + (size_t)slot * stride + (size_t)which * px() * 16); }
     uint32_t* out(int slot) const { return (uint32_t*)(mem + (size_t)slot * stride + px() * 32); }
 };
@@ -30,17 +25,9 @@ int tfilter_params(const eppm_tfilter_params* p, const char* what)
     return EPPM_OK;
 }
 
-// the filter's last step is complete (the synchronous calls read and write its planes on the null stream)
-int wait(eppm_tfilter* f)
-{
-    HIPCHK(hipSetDevice(f->device));
-    HIPCHK(hipEventSynchronize(f->done));
-    return EPPM_OK;
-}
-
 int slot_check(const eppm_tfilter* f, int slot, bool need_state, const char* what)
 {
-    if (slot < 0 || slot >= f->nslots) return set_err(EPPM_ERR_ARG, "%s: slot %d, the filter has %d", what, slot, f->nslots);
+    CHK(stage_slot_check(f, slot, what));
     if (need_state && f->empty[slot]) return set_err(EPPM_ERR_STATE, "%s: slot %d is empty", what, slot);
     return EPPM_OK;
 }
@@ -62,31 +49,19 @@ static int tfilter_new(int device, int h, int w, int nslots, const eppm_tfilter_
     const eppm_tfilter_params* p = in ? in : &def;
     CHK(tfilter_params(p, "eppm_tfilter_create"));
     if (h < 1 || w < 1 || (long long)h * w >= (1LL << 31)) return set_err(EPPM_ERR_ARG, "eppm_tfilter_create: size %dx%d out of range", w, h);
-    if (nslots < 1 || nslots > kTemporalMaxSlots) return set_err(EPPM_ERR_ARG, "eppm_tfilter_create: %d slots outside [1, %d]", nslots, kTemporalMaxSlots);
-    HIPCHK(hipSetDevice(device));
     eppm_tfilter* f = new eppm_tfilter;
+    f->noun = "filter";
     f->device = device; f->h = h; f->w = w; f->nslots = nslots;
     f->thresh = p->thresh; f->n_max = p->n_max;
-    f->stride = (f->px() * 36 + 255) & ~(size_t)255;
+    f->stride = up256(f->px() * 36);
     f->bytes = f->stride * nslots;
+    const int rc = stage_open(f, "eppm_tfilter_create");
+    if (rc != EPPM_OK) {
+        delete f;
+        return rc;
+    }
     f->cur.assign(nslots, 0);
     f->empty.assign(nslots, 1);
-    hipError_t e = cache_alloc((void**)&f->mem, f->bytes, false, device);
-    if (e != hipSuccess) {
-        (void)hipGetLastError();
-        const size_t bytes = f->bytes;
-        delete f;
-        return set_err(EPPM_ERR_HIP, "hipMalloc of %zu bytes (temporal filter) failed: %s", bytes, hipGetErrorString(e));
-    }
-    e = hipEventCreateWithFlags(&f->done, hipEventDisableTiming);
-    if (e == hipSuccess) e = hipEventRecord(f->done, nullptr);
-    if (e != hipSuccess) {
-        (void)hipGetLastError();
-        if (f->done) (void)hipEventDestroy(f->done);
-        cache_free(f->mem, f->bytes, false, device);
-        delete f;
-        return set_err(EPPM_ERR_HIP, "eppm_tfilter_create: %s", hipGetErrorString(e));
-    }
     *out = f;
     return EPPM_OK;
 }
@@ -110,10 +85,7 @@ extern "C" int eppm_tfilter_create_size(int h, int w, int nslots, int device, co
 extern "C" int eppm_tfilter_destroy(eppm_tfilter* f)
 {
     if (!f) return EPPM_OK;
-    (void)hipSetDevice(f->device);
-    (void)hipEventSynchronize(f->done);
-    (void)hipEventDestroy(f->done);
-    cache_free(f->mem, f->bytes, false, f->device);
+    stage_close(f);
     delete f;
     return EPPM_OK;
 }
@@ -121,23 +93,15 @@ extern "C" int eppm_tfilter_destroy(eppm_tfilter* f)
 extern "C" int eppm_tfilter_reset(eppm_tfilter* f, int slot)
 {
     if (!f) return set_err(EPPM_ERR_ARG, "eppm_tfilter_reset: NULL filter");
-    if (slot >= f->nslots) return set_err(EPPM_ERR_ARG, "eppm_tfilter_reset: slot %d, the filter has %d", slot, f->nslots);
+    if (slot >= 0) CHK(stage_slot_check(f, slot, "eppm_tfilter_reset"));
     for (int k = 0; k < f->nslots; k++)
         if (slot < 0 || k == slot) f->empty[k] = 1;
     return EPPM_OK;
 }
 
-int tfilter_device(const eppm_tfilter* f, int* h, int* w, int* nslots)
-{
-    *h = f->h;
-    *w = f->w;
-    *nslots = f->nslots;
-    return f->device;
-}
-
 // one step of slots slot0 .. slot0 + in.n - 1 on stream s; in: the pairs' planes (the state members are filled in here); cut: NULL or
 // one flag per pair.  timing: the context whose stage-timing entries receive the stage, or NULL
-int tfilter_step_on(eppm_tfilter* f, TFilterArgs& in, int slot0, const uint8_t* cut, hipStream_t s, eppm_ctx* timing)
+static int step_on(eppm_tfilter* f, TFilterArgs& in, int slot0, const uint8_t* cut, hipStream_t s, eppm_ctx* timing)
 {
     in.st0 = f->state(0, 0);
     in.st1 = f->state(0, 1);
@@ -145,22 +109,15 @@ int tfilter_step_on(eppm_tfilter* f, TFilterArgs& in, int slot0, const uint8_t* 
     in.slot_stride = f->stride;
     in.h = f->h; in.w = f->w; in.slot0 = slot0;
     in.thresh = f->thresh; in.n_max = f->n_max;
-    memset(in.cur, 0, sizeof(in.cur));
-    memset(in.empty, 0, sizeof(in.empty));
-    memset(in.cut, 0, sizeof(in.cut));
-    for (int k = slot0; k < slot0 + in.n; k++) {
-        const uint32_t bit = 1u << (k & 31);
-        if (f->cur[k]) in.cur[k >> 5] |= bit;
-        if (f->empty[k]) in.empty[k >> 5] |= bit;
-        if (cut && cut[k - slot0]) in.cut[k >> 5] |= bit;
+    slot_mask(in.cur, f->cur.data() + slot0, slot0, in.n);
+    slot_mask(in.empty, f->empty.data() + slot0, slot0, in.n);
+    slot_mask(in.cut, cut, slot0, in.n);
+    CHK(stage_enter(f, s));
+    {
+        StageTimer t(timing, "tfilter_step");
+        launch_tfilter_step(in, s);
     }
-    if (s != f->last) HIPCHK(hipStreamWaitEvent(s, f->done, 0));
-    if (timing) ctx_stage_begin(timing, "tfilter_step");
-    launch_tfilter_step(in, s);
-    if (timing) ctx_stage_end(timing);
-    HIPCHK(hipGetLastError());
-    HIPCHK(hipEventRecord(f->done, s));
-    f->last = s;
+    CHK(stage_leave(f, s));
     for (int k = slot0; k < slot0 + in.n; k++) {
         f->cur[k] ^= 1;
         f->empty[k] = 0;
@@ -171,10 +128,32 @@ int tfilter_step_on(eppm_tfilter* f, TFilterArgs& in, int slot0, const uint8_t* 
 extern "C" int eppm_tfilter_step(eppm_tfilter* f, eppm_ctx* ctx, const uint8_t* cut)
 {
     if (!f || !ctx) return set_err(EPPM_ERR_ARG, "eppm_tfilter_step: NULL argument");
-    TFilterArgs in{};
+    CtxPlanes c;
     hipStream_t s;
-    CHK(ctx_tfilter_inputs(ctx, f->h, f->w, f->device, f->nslots, "eppm_tfilter_step", &in, &s));
-    return tfilter_step_on(f, in, 0, cut, s, ctx);
+    CHK(ctx_stage_inputs(ctx, f, "eppm_tfilter_step", &c, &s));
+    TFilterArgs in{};
+    in.img1 = c.img1; in.img2 = c.img2; in.img_pitch = c.img_pitch; in.img_stride = c.img_stride;
+    in.bwd = c.bwd; in.bwd_stride = c.bwd_stride;
+    in.occ2 = c.occ2; in.occ_stride = c.occ_stride;
+    in.n = c.n;
+    return step_on(f, in, 0, cut, s, ctx);
+}
+
+// one step of one slot on caller planes, on the launcher stream
+extern "C" int eppm_tfilter_step_frames(eppm_tfilter* f, int slot, const void* d_rgba1, const void* d_rgba2, size_t pitch,
+                                        const eppm_float2* d_flow_bwd, const uint8_t* d_occ2, int cut)
+{
+    if (!f || !d_rgba1 || !d_rgba2 || !d_flow_bwd || !d_occ2) return set_err(EPPM_ERR_ARG, "eppm_tfilter_step_frames: NULL argument");
+    CHK(stage_slot_check(f, slot, "eppm_tfilter_step_frames"));
+    if (bad_pitch(pitch, f->w)) return set_err(EPPM_ERR_ARG, "eppm_tfilter_step_frames: bad pitch %zu", pitch);
+    return launcher_run(f, "eppm_tfilter_step_frames", [&](hipStream_t s) {
+        TFilterArgs in{};
+        in.img1 = (const uint8_t*)d_rgba1; in.img2 = (const uint8_t*)d_rgba2; in.img_pitch = pitch;
+        in.bwd = (const float*)d_flow_bwd; in.occ2 = d_occ2;
+        in.n = 1;
+        const uint8_t c = cut != 0;
+        return step_on(f, in, slot, &c, s, nullptr);
+    });
 }
 
 extern "C" int eppm_tfilter_get(eppm_tfilter* f, int slot, uint8_t* rgb, size_t row_stride)
@@ -182,36 +161,22 @@ extern "C" int eppm_tfilter_get(eppm_tfilter* f, int slot, uint8_t* rgb, size_t 
     if (!f || !rgb) return set_err(EPPM_ERR_ARG, "eppm_tfilter_get: NULL argument");
     CHK(slot_check(f, slot, true, "eppm_tfilter_get"));
     if (row_stride < (size_t)f->w * 3) return set_err(EPPM_ERR_ARG, "eppm_tfilter_get: row_stride %zu < 3*w", row_stride);
-    CHK(wait(f));
-    std::vector<uint32_t> words(f->px());
-    HIPCHK(hipMemcpy(words.data(), f->out(slot), f->px() * 4, hipMemcpyDeviceToHost));
-    for (int y = 0; y < f->h; y++) {
-        uint8_t* o = rgb + (size_t)y * row_stride;
-        const uint32_t* q = words.data() + (size_t)y * f->w;
-        for (int x = 0; x < f->w; x++) {
-            o[3 * x] = (uint8_t)q[x]; o[3 * x + 1] = (uint8_t)(q[x] >> 8); o[3 * x + 2] = (uint8_t)(q[x] >> 16);
-        }
-    }
-    return EPPM_OK;
+    return stage_get_rgb(f, f->out(slot), f->h, f->w, rgb, row_stride);
 }
 
 extern "C" int eppm_tfilter_get_device(eppm_tfilter* f, int slot, void* d_rgba, size_t pitch)
 {
     if (!f || !d_rgba) return set_err(EPPM_ERR_ARG, "eppm_tfilter_get_device: NULL argument");
     CHK(slot_check(f, slot, true, "eppm_tfilter_get_device"));
-    if (pitch < (size_t)f->w * 4 || (pitch & 3)) return set_err(EPPM_ERR_ARG, "eppm_tfilter_get_device: bad pitch %zu", pitch);
-    HIPCHK(hipSetDevice(f->device));
-    // on the stream of the last step, behind it; the next step on any stream waits for the copy
-    HIPCHK(hipMemcpy2DAsync(d_rgba, pitch, f->out(slot), (size_t)f->w * 4, (size_t)f->w * 4, f->h, hipMemcpyDeviceToDevice, f->last));
-    HIPCHK(hipEventRecord(f->done, f->last));
-    return EPPM_OK;
+    if (bad_pitch(pitch, f->w)) return set_err(EPPM_ERR_ARG, "eppm_tfilter_get_device: bad pitch %zu", pitch);
+    return stage_get_rgba_device(f, f->out(slot), f->h, f->w, d_rgba, pitch);
 }
 
 extern "C" int eppm_tfilter_get_state(eppm_tfilter* f, int slot, float* acc)
 {
     if (!f || !acc) return set_err(EPPM_ERR_ARG, "eppm_tfilter_get_state: NULL argument");
     CHK(slot_check(f, slot, true, "eppm_tfilter_get_state"));
-    CHK(wait(f));
+    CHK(stage_wait(f));
     HIPCHK(hipMemcpy(acc, f->state(slot, f->cur[slot]), f->px() * 16, hipMemcpyDeviceToHost));
     return EPPM_OK;
 }
@@ -220,14 +185,12 @@ extern "C" int eppm_tfilter_set_state(eppm_tfilter* f, int slot, const float* ac
 {
     if (!f || !acc) return set_err(EPPM_ERR_ARG, "eppm_tfilter_set_state: NULL argument");
     CHK(slot_check(f, slot, false, "eppm_tfilter_set_state"));
-    CHK(wait(f));
+    CHK(stage_wait(f));
     std::vector<uint32_t> words(f->px());
     for (size_t i = 0; i < f->px(); i++) words[i] = tfilter_word(TfState{acc[4 * i], acc[4 * i + 1], acc[4 * i + 2], acc[4 * i + 3]});
     HIPCHK(hipMemcpy(f->state(slot, f->cur[slot]), acc, f->px() * 16, hipMemcpyHostToDevice));
     HIPCHK(hipMemcpy(f->out(slot), words.data(), f->px() * 4, hipMemcpyHostToDevice));
-    HIPCHK(hipStreamSynchronize(nullptr));
-    HIPCHK(hipEventRecord(f->done, nullptr));
-    f->last = nullptr;
+    CHK(stage_settle(f));
     f->empty[slot] = 0;
     return EPPM_OK;
 }

@@ -1,22 +1,17 @@
-// tracker.cpp -- dense point trajectories: eppm_tracker, its allocation and its steps on a context's pair (the
-// kernels: k_track.hip), the synchronous state calls, and the host form eppm_track_step_host.  The host form shares track.h's per-point
+// tracker.cpp -- dense point trajectories: eppm_tracker (a stage object of one slot, stage_object.h), its steps on a
+// context's pair or on caller planes (the kernels: k_track.hip), the synchronous state calls, and the host form eppm_track_step_host.  The host form shares track.h's per-point
 // arithmetic with the kernels; its lists are built by sequential loops with running counters, independent of the kernels' scans.
-#include "api_internal.h"
+#include "stage_object.h"
 #include "track.h"
 
 using namespace eppm;
 
-struct eppm_tracker {
-    int device = 0, h = 0, w = 0;
+struct eppm_tracker : StageObject {
     int cap = 0, ncells = 0, ncx = 0;
     int cur = 0;                        // which of the two lists holds the live tracks
     int frame = 0;                      // the device frame counter as the steps enqueued so far leave it (the frame-0 pass is skipped otherwise)
-    char* mem = nullptr;
-    size_t bytes = 0;
     TrackRec* list[2] = {nullptr, nullptr};
     TrackDev d{};
-    hipEvent_t done = nullptr;          // recorded after every step: the synchronous calls wait for it
-    hipStream_t last = nullptr;         // the stream of the last step: a step on another stream waits for `done` first
 };
 
 namespace {
@@ -47,14 +42,6 @@ int track_params(const eppm_track_params* in, int h, int w, TrackParams* p, int*
 }
 
 bool in_frame(float x, float y, int h, int w) { return x >= 0.0f && x <= (float)(w - 1) && y >= 0.0f && y <= (float)(h - 1); }
-
-// the tracker's previous step is complete (the synchronous calls read and write its planes on the null stream)
-int wait(eppm_tracker* t)
-{
-    HIPCHK(hipSetDevice(t->device));
-    HIPCHK(hipEventSynchronize(t->done));
-    return EPPM_OK;
-}
 
 int read_counts(eppm_tracker* t, int32_t* cnt)
 {
@@ -112,28 +99,19 @@ extern "C" int eppm_tracker_create(eppm_ctx* ctx, const eppm_track_params* in, e
     size_t off[12], bytes = 0;
     for (int i = 0; i < 12; i++) {
         off[i] = bytes;
-        bytes += (sz[i] + 255) & ~(size_t)255;
+        bytes += up256(sz[i]);
     }
-    HIPCHK(hipSetDevice(device));
     eppm_tracker* t = new eppm_tracker;
-    t->device = device; t->h = h; t->w = w; t->cap = cap; t->ncells = ncells; t->ncx = ncx;
-    hipError_t e = cache_alloc((void**)&t->mem, bytes, false, device);
-    if (e != hipSuccess) {
-        (void)hipGetLastError();
+    t->noun = "tracker";
+    t->device = device; t->h = h; t->w = w; t->nslots = 1; t->bytes = bytes;
+    t->cap = cap; t->ncells = ncells; t->ncx = ncx;
+    const int rc = stage_open(t, "eppm_tracker_create", [t] {
+        const hipError_t e = hipMemsetAsync(t->mem, 0, t->bytes, nullptr);
+        return e == hipSuccess ? hipStreamSynchronize(nullptr) : e;
+    });
+    if (rc != EPPM_OK) {
         delete t;
-        return set_err(EPPM_ERR_HIP, "hipMalloc of %zu bytes (tracker) failed: %s", bytes, hipGetErrorString(e));
-    }
-    t->bytes = bytes;
-    e = hipEventCreateWithFlags(&t->done, hipEventDisableTiming);
-    if (e == hipSuccess) e = hipMemsetAsync(t->mem, 0, bytes, nullptr);
-    if (e == hipSuccess) e = hipEventRecord(t->done, nullptr);
-    if (e == hipSuccess) e = hipStreamSynchronize(nullptr);
-    if (e != hipSuccess) {
-        (void)hipGetLastError();
-        if (t->done) (void)hipEventDestroy(t->done);
-        cache_free(t->mem, t->bytes, false, device);
-        delete t;
-        return set_err(EPPM_ERR_HIP, "eppm_tracker_create: %s", hipGetErrorString(e));
+        return rc;
     }
     char* m = t->mem;
     t->list[0] = (TrackRec*)(m + off[0]);
@@ -159,45 +137,35 @@ extern "C" int eppm_tracker_create(eppm_ctx* ctx, const eppm_track_params* in, e
 extern "C" int eppm_tracker_destroy(eppm_tracker* t)
 {
     if (!t) return EPPM_OK;
-    (void)hipSetDevice(t->device);
-    (void)hipEventSynchronize(t->done);
-    (void)hipEventDestroy(t->done);
-    cache_free(t->mem, t->bytes, false, t->device);
+    stage_close(t);
     delete t;
     return EPPM_OK;
 }
 
-int tracker_device(const eppm_tracker* t, int* h, int* w)
-{
-    *h = t->h;
-    *w = t->w;
-    return t->device;
-}
-
 // one step on stream s: the frame-0 seeding pass (only while the frame counter is 0), advance, seed flags, compaction.  timing: the
 // context whose stage-timing entries receive the stages, or NULL
-int tracker_step_on(eppm_tracker* t, const TrackIn& in, hipStream_t s, eppm_ctx* timing)
+static int step_on(eppm_tracker* t, const TrackIn& in, hipStream_t s, eppm_ctx* timing)
 {
     TrackRec* cur = t->list[t->cur];
     TrackRec* next = t->list[t->cur ^ 1];
-    if (s != t->last) HIPCHK(hipStreamWaitEvent(s, t->done, 0));
+    CHK(stage_enter(t, s));
     if (t->frame == 0) {
-        if (timing) ctx_stage_begin(timing, "track_seed");
+        StageTimer tm(timing, "track_seed");
         launch_track_seed0(t->d, in, cur, s);
-        if (timing) ctx_stage_end(timing);
     }
-    if (timing) ctx_stage_begin(timing, "track_advance");
-    launch_track_advance(t->d, in, cur, s);
-    if (timing) ctx_stage_end(timing);
-    if (timing) ctx_stage_begin(timing, "track_seed");
-    launch_track_seed(t->d, in, s);
-    if (timing) ctx_stage_end(timing);
-    if (timing) ctx_stage_begin(timing, "track_compact");
-    launch_track_compact(t->d, in, cur, next, s);
-    if (timing) ctx_stage_end(timing);
-    HIPCHK(hipGetLastError());
-    HIPCHK(hipEventRecord(t->done, s));
-    t->last = s;
+    {
+        StageTimer tm(timing, "track_advance");
+        launch_track_advance(t->d, in, cur, s);
+    }
+    {
+        StageTimer tm(timing, "track_seed");
+        launch_track_seed(t->d, in, s);
+    }
+    {
+        StageTimer tm(timing, "track_compact");
+        launch_track_compact(t->d, in, cur, next, s);
+    }
+    CHK(stage_leave(t, s));
     t->cur ^= 1;
     t->frame++;
     return EPPM_OK;
@@ -206,16 +174,28 @@ int tracker_step_on(eppm_tracker* t, const TrackIn& in, hipStream_t s, eppm_ctx*
 extern "C" int eppm_track_step(eppm_tracker* t, eppm_ctx* ctx, int pair)
 {
     if (!t || !ctx) return set_err(EPPM_ERR_ARG, "eppm_track_step: NULL argument");
-    TrackIn in;
+    CtxPlanes c;
     hipStream_t s;
-    CHK(ctx_track_inputs(ctx, pair, t->h, t->w, t->device, "eppm_track_step", &in, &s));
-    return tracker_step_on(t, in, s, ctx);
+    CHK(ctx_stage_inputs(ctx, t, "eppm_track_step", &c, &s, &pair));
+    return step_on(t, TrackIn{c.img1, c.img2, c.img_pitch, c.fwd, c.bwd, t->h, t->w}, s, ctx);
+}
+
+// one step on caller planes, on the launcher stream
+extern "C" int eppm_track_step_frames(eppm_tracker* t, const void* d_rgba1, const void* d_rgba2, size_t pitch, const eppm_float2* d_flow,
+                                      const eppm_float2* d_flow_bwd, int h, int w)
+{
+    if (!t || !d_rgba1 || !d_rgba2 || !d_flow || !d_flow_bwd) return set_err(EPPM_ERR_ARG, "eppm_track_step_frames: NULL argument");
+    if (h != t->h || w != t->w) return set_err(EPPM_ERR_ARG, "eppm_track_step_frames: %dx%d planes, the tracker is %dx%d", w, h, t->w, t->h);
+    if (bad_pitch(pitch, w)) return set_err(EPPM_ERR_ARG, "eppm_track_step_frames: bad pitch %zu", pitch);
+    return launcher_run(t, "eppm_track_step_frames", [&](hipStream_t s) {
+        return step_on(t, TrackIn{(const uint8_t*)d_rgba1, (const uint8_t*)d_rgba2, pitch, (const float*)d_flow, (const float*)d_flow_bwd, h, w}, s, nullptr);
+    });
 }
 
 extern "C" int eppm_tracker_get(eppm_tracker* t, int max, int32_t* ids, int32_t* starts, float* xy, eppm_track_counts* counts)
 {
     if (!t || max < 0) return set_err(EPPM_ERR_ARG, "eppm_tracker_get: bad argument");
-    CHK(wait(t));
+    CHK(stage_wait(t));
     int32_t cnt[kTrackCntN];
     CHK(read_counts(t, cnt));
     if (counts) to_counts(cnt, counts);
@@ -235,7 +215,7 @@ extern "C" int eppm_tracker_get(eppm_tracker* t, int max, int32_t* ids, int32_t*
 extern "C" int eppm_tracker_get_ended(eppm_tracker* t, int max, int32_t* ids, int32_t* starts, float* xy, int32_t* reasons, eppm_track_counts* counts)
 {
     if (!t || max < 0) return set_err(EPPM_ERR_ARG, "eppm_tracker_get_ended: bad argument");
-    CHK(wait(t));
+    CHK(stage_wait(t));
     int32_t cnt[kTrackCntN];
     CHK(read_counts(t, cnt));
     if (counts) to_counts(cnt, counts);
@@ -267,16 +247,14 @@ extern "C" int eppm_tracker_set(eppm_tracker* t, int n, const int32_t* ids, cons
             return set_err(EPPM_ERR_ARG, "eppm_tracker_set: track %d at (%g, %g) outside the frame", i, xy[2 * i], xy[2 * i + 1]);
         r[i] = TrackRec{ids[i], starts[i], xy[2 * i], xy[2 * i + 1]};
     }
-    CHK(wait(t));
+    CHK(stage_wait(t));
     if (n > 0) HIPCHK(hipMemcpy(t->list[t->cur], r.data(), (size_t)n * sizeof(TrackRec), hipMemcpyHostToDevice));
     int32_t cnt[kTrackCntN] = {};
     cnt[kTrackCntLive] = n;
     cnt[kTrackCntNextId] = next_id;
     cnt[kTrackCntFrame] = frame;
     HIPCHK(hipMemcpy(t->d.cnt, cnt, sizeof(cnt), hipMemcpyHostToDevice));
-    HIPCHK(hipStreamSynchronize(nullptr));
-    HIPCHK(hipEventRecord(t->done, nullptr));
-    t->last = nullptr;
+    CHK(stage_settle(t));
     t->frame = frame;
     return EPPM_OK;
 }
