@@ -146,7 +146,7 @@ SYMBOLS = [
 
 # what include/eppm_test.h adds, exported by libeppm_hip_test.so and libeppm_hip_tol_test.so only (the parity tests' switches and arithmetic probes)
 TEST_SYMBOLS = ["eppm_test_set_option", "eppm_test_c2f_refine_batch", "eppm_probe_c2f_window", "eppm_probe_dispatch", "eppm_probe_fast_exp", "eppm_probe_div_const", "eppm_probe_delta_table",
-                "eppm_probe_unpack_texel", "eppm_probe_pm_parity", "eppm_probe_ctx_rng_states", "eppm_test_pm_search", "eppm_probe_search_pretest"]
+                "eppm_probe_unpack_texel", "eppm_probe_pm_parity", "eppm_probe_ctx_rng_states", "eppm_test_pm_search", "eppm_probe_search_pretest", "eppm_probe_launch_log"]
 
 _variant = None
 
@@ -205,6 +205,32 @@ def check(status, what=""):
 
 def check_launcher(what=""):
     check(lib().eppm_launcher_status(), what)
+
+
+LAUNCH_STAGES = ("smoothing", "jbu", "refine", "search", "sweep", "sweeps_merged")
+
+
+class launch_log:
+    """with launch_log() as log: ...; log.entries() -- what the launchers decided inside the block (test libraries; include/eppm_test.h,
+    eppm_probe_launch_log): [(stage name, w, h, pairs in the launch, form, extra)] in launch order."""
+
+    def __enter__(self):
+        check(lib().eppm_test_set_option(b"launch_log", 1), "launch_log on")
+        self._kept = None
+        return self
+
+    def entries(self):
+        if self._kept is not None:
+            return self._kept
+        n = lib().eppm_probe_launch_log(None, 0)
+        buf = (C.c_int * (6 * max(n, 1)))()
+        n = min(n, lib().eppm_probe_launch_log(buf, n))
+        return [(LAUNCH_STAGES[buf[6 * i]],) + tuple(buf[6 * i + 1:6 * i + 6]) for i in range(n)]
+
+    def __exit__(self, *exc):
+        self._kept = self.entries()
+        lib().eppm_test_set_option(b"launch_log", 0)
+        return False
 
 
 def probe_dispatch(stage, *args, nout=1):

@@ -22,6 +22,9 @@ int set_err(int code, const char* fmt, ...)
 }
 
 extern "C" const char* eppm_last_error(void) { return g_err; }
+
+// where the launchers note what they decided (eppm_internal.h: launch_note): nowhere, unless a test library points this at its log
+namespace eppm { std::atomic<LaunchNoteFn> g_launch_note{nullptr}; }
 #ifdef EPPM_TOL
 extern "C" const char* eppm_version(void) { return "eppm-hip 0.3 (gfx950, tolerance arithmetic: integer-domain tables in the patch term, not bit-identical to the oracle)"; }
 #else

@@ -144,6 +144,11 @@ EPPM_HIDDEN eppm::PmProblem mk_problem(const eppm::PlanesH& P, float* cost, int1
                                        int32_t* scand = nullptr, uint32_t* wl = nullptr, int16_t* seed = nullptr, float* restw = nullptr);
 EPPM_HIDDEN void search(eppm::PmBatch& b, eppm_pm_rng* rng, const float* lut, const eppm_params& prm, hipStream_t s, int launch_no = -1, bool pretest = false);
 EPPM_HIDDEN bool sweep_list_on(int mode);
+// The form of the sweeps of PatchMatch iteration `iteration`: speculative two-launch form by the pixels of the LAUNCH (problem x problems x
+// pairs), merged form (one phase A for the four sweeps) from an iteration that depends on the pixels of one PROBLEM; m: the test switch
+// "sweep_spec" (-1: the library's own decision).  Asked by pm_iterate and by eppm_probe_dispatch "patchmatch".
+EPPM_DECISION bool sweep_speculative(int iteration, long long pixels, int m);
+EPPM_DECISION bool sweeps_merged(int iteration, long long pixels, long long problem_pixels, int m);
 EPPM_HIDDEN void sweep(eppm::PmBatch& b, const float* lut, const eppm_params& prm, int dir, hipStream_t s, bool speculative = false);
 EPPM_HIDDEN void jump(eppm::PmBatch& b, const float* lut, const eppm_params& prm, hipStream_t s);
 EPPM_HIDDEN void neighbor(eppm::PmBatch& b, const float* lut, const eppm_params& prm, int launches, hipStream_t s);

@@ -6,6 +6,8 @@
 #include <stddef.h>
 #include <stdint.h>
 
+#include <atomic>
+
 #include "../../include/eppm.h"
 
 namespace eppm {
@@ -32,6 +34,18 @@ constexpr Batch kOnePair = {1, 0};
 // libraries ask the same function (include/eppm_test.h: eppm_probe_dispatch), so that a test can pick shapes on either side of a
 // threshold without repeating the constant.  Pure host arithmetic; not exported.
 #define EPPM_DECISION __attribute__((visibility("hidden")))
+// What a launcher then DID with the answer is noted where a test can read it: one entry per launch -- stage, size of a problem, pairs in
+// the launch, the form taken (the decision function's value), and the direction / iteration / level-independent extra the stage has.
+// g_launch_note is NULL for ever in the product libraries (nothing in them stores to it, and the log itself is not in them: a launch pays
+// one relaxed load); the test libraries point it at their log with the "launch_log" option (test_hooks.cpp) and read the log with
+// eppm_probe_launch_log (include/eppm_test.h).
+enum LaunchStage { kLaunchSmoothing = 0, kLaunchJbu, kLaunchRefine, kLaunchSearch, kLaunchSweep, kLaunchSweepsMerged };
+typedef void (*LaunchNoteFn)(int stage, int w, int h, int npairs, int form, int extra);
+extern EPPM_DECISION std::atomic<LaunchNoteFn> g_launch_note;
+inline void launch_note(int stage, int w, int h, int npairs, int form, int extra = 0)
+{
+    if (LaunchNoteFn f = g_launch_note.load(std::memory_order_relaxed)) f(stage, w, h, npairs, form, extra);
+}
 
 struct PlanesH {            // host-side mirror of eppm::Planes: float4 texel planes {r,g,b,census bits}, pitch in pixels
     const void* pk1;

@@ -440,7 +440,9 @@ void launch_c2f_refine(const PlanesH& P, float* flow, const float* lut, int R, f
     dim3 grid((P.w + kBlock - 1) / kBlock, (P.h + kBlock - 1) / kBlock, bt.n), block(kBlock, kBlock);
     const int per_xcd = (grid.x * grid.y + 7) / 8;
     dim3 grid1(per_xcd * 8, bt.n);               // x: padded so every XCD gets the same number of slots; y: pair
-    if (const int f = cost9 ? c2f_refine_split_factor(P.w, P.h, R, bt.n, no_split) : 0) {
+    const int f = cost9 ? c2f_refine_split_factor(P.w, P.h, R, bt.n, no_split) : 0;
+    launch_note(kLaunchRefine, P.w, P.h, bt.n, f, R);
+    if (f) {
         dim3 gridf(per_xcd * f * 8, bt.n), gs((P.w + 63) / 64, (P.h + 3) / 4, bt.n), bs(64, 4);
         with_radius(R, [&](auto r) {
             if (f == 3) hipLaunchKernelGGL((k_c2f_refine_tiled<r(), 3>), gridf, block, 0, s, P, flow, lut, cost9, bt.stride);

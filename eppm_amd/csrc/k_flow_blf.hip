@@ -156,7 +156,9 @@ void launch_flow_blf(float* out, const float* in, const uint32_t* img, int ipitc
                      const float* blf_lut, hipStream_t s, Batch bt)
 {
     dim3 block(BT_W, 8);
-    if (flow_blf_pixels_per_lane(w, h, bt.n) == 2) {
+    const int ppl = flow_blf_pixels_per_lane(w, h, bt.n);
+    launch_note(kLaunchSmoothing, w, h, bt.n, ppl);
+    if (ppl == 2) {
         hipLaunchKernelGGL(k_flow_blf<2>, dim3((w + BT_W - 1) / BT_W, (h + 15) / 16, bt.n), block, 0, s, out, in, img, ipitch, w, h, flow_pitch, blf_lut, bt.stride);
     } else {
         hipLaunchKernelGGL(k_flow_blf<1>, dim3((w + BT_W - 1) / BT_W, (h + 7) / 8, bt.n), block, 0, s, out, in, img, ipitch, w, h, flow_pitch, blf_lut, bt.stride);

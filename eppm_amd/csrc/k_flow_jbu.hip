@@ -146,7 +146,9 @@ void launch_flow_jbu(float* out, const float* in_coarse, const uint32_t* img, in
                      hipStream_t s, Batch bt)
 {
     dim3 block(JT_W, 8);
-    if (flow_blf_pixels_per_lane(w, h, bt.n) == 2) {
+    const int ppl = flow_blf_pixels_per_lane(w, h, bt.n);
+    launch_note(kLaunchJbu, w, h, bt.n, ppl);
+    if (ppl == 2) {
         hipLaunchKernelGGL(k_flow_jbu<2>, dim3((w + JT_W - 1) / JT_W, (h + 15) / 16, bt.n), block, 0, s, out, in_coarse, img, ipitch, w, h, wc, hc, blf_lut, bt.stride);
     } else {
         hipLaunchKernelGGL(k_flow_jbu<1>, dim3((w + JT_W - 1) / JT_W, (h + 7) / 8, bt.n), block, 0, s, out, in_coarse, img, ipitch, w, h, wc, hc, blf_lut, bt.stride);

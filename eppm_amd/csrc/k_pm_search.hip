@@ -320,9 +320,15 @@ void launch_pm_random_search(const PmBatch& b, const PmRngDev& rng, const float*
     if (rng.rand_tab && (R == 9 || R == 17)) {                                         // numbers drawn ahead: G waves per workgroup
         dim3 blockt(64 * num_guess);
         const bool half = pm_search_rows(b.p[0].P.w, b.p[0].P.h, R, b.n, b.npairs, true) == 2;      // (radius 9 only)
+#ifndef EPPM_TOL
+        const bool two_phase = pretest && R == 9 && pm_has_parity(b, R, EPPM_PARITY_SEARCH) && pm_search_pretest_ready(b, rng, R);   // (the caller's decision: quarter blocks)
+#else
+        const bool two_phase = false;              // the tolerance library has no two-phase kernel
+#endif
+        launch_note(kLaunchSearch, b.p[0].P.w, b.p[0].P.h, b.npairs, (two_phase || !half) ? 4 : 2, two_phase);
         if (pm_has_parity(b, R, EPPM_PARITY_SEARCH)) {                                 // column-parity target planes
 #ifndef EPPM_TOL
-            if (pretest && R == 9 && pm_search_pretest_ready(b, rng, R)) {          // (the caller's decision: quarter blocks)
+            if (two_phase) {
                 hipLaunchKernelGGL((k_pm_random_search<9, 2, true, 4, true>), grid, blockt, 0, s, b, rng, lut, R, search_range, num_guess);
                 return;
             }

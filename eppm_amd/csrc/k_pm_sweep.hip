@@ -688,9 +688,11 @@ bool launch_pm_sweep(PmBatch& b, const float* lut, int R, int seg_len, int dir, 
     if (speculative && b.p[0].spec && (R == 9 || R == 17) && seg_len <= kSpecMaxSteps) {
         if (R == 9) { launch_sweep_spec<9>(b, lut, R, dir, seg_len, g.nseg, s); launch_sweep_b<9, EPPM_LPC9_SPEC>(b, lut, seg_len, dir, g, s); }
         else { launch_sweep_spec<17>(b, lut, R, dir, seg_len, g.nseg, s); launch_sweep_b<17, EPPM_LPC17_SPEC>(b, lut, seg_len, dir, g, s); }
+        launch_note(kLaunchSweep, b.p[0].P.w, b.p[0].P.h, b.npairs, -1, dir);
         return true;
     }
     const SweepForm f = pm_sweep_form(b.p[0].P.w, b.p[0].P.h, R, seg_len, dir, b.n, b.npairs);
+    launch_note(kLaunchSweep, b.p[0].P.w, b.p[0].P.h, b.npairs, f.lpc * 4 + f.pre * 2 + f.tile, dir);      // (speculative: -1)
     if (R == 9) {
         if (f.small) launch_sweep_r<9, kLpc9Small, (EPPM_SWEEP_PRE >= 1)>(b, lut, seg_len, dir, g, f, s);
         else launch_sweep_r<9, EPPM_LPC9, (EPPM_SWEEP_PRE >= 2)>(b, lut, seg_len, dir, g, f, s);
@@ -711,6 +713,7 @@ bool launch_pm_sweeps_merged(PmBatch& b, const float* lut, int R, int seg_len, i
         if (!b.p[k].seed || !b.p[k].wl || !b.p[k].spec || !b.p[k].scand) return false;
     if (!(R == 9 || R == 17) || seg_len > kSpecMaxSteps || seg_len < 1) return false;
     const int w = b.p[0].P.w, h = b.p[0].P.h, gx = (w + kBlock - 1) / kBlock, gy = (h + kBlock - 1) / kBlock;
+    launch_note(kLaunchSweepsMerged, w, h, b.npairs, 1, iteration);
     b.merged_it = iteration;
     b.seg_len = seg_len;
     b.nseg_row = (w + seg_len - 1) / seg_len;

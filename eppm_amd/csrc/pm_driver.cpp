@@ -43,7 +43,7 @@ bool sweep_list_on(int mode) { return EPPM_SWEEP_LIST && mode != 2; }
 #ifndef EPPM_SPEC_MIN_PIXELS
 #define EPPM_SPEC_MIN_PIXELS 100000
 #endif
-static bool sweep_speculative(int iteration, long long pixels, int m)
+bool sweep_speculative(int iteration, long long pixels, int m)
 {
     return m < 0 ? (iteration >= EPPM_SPEC_FROM_ITER && pixels >= EPPM_SPEC_MIN_PIXELS) : m != 0;
 }
@@ -63,7 +63,7 @@ static bool sweep_speculative(int iteration, long long pixels, int m)
 #ifndef EPPM_MERGED_LARGE_PIXELS
 #define EPPM_MERGED_LARGE_PIXELS 65536
 #endif
-static bool sweeps_merged(int iteration, long long pixels, long long problem_pixels, int m)
+bool sweeps_merged(int iteration, long long pixels, long long problem_pixels, int m)
 {
     const int from = problem_pixels > EPPM_MERGED_LARGE_PIXELS ? EPPM_MERGED_FROM_ITER_LARGE : EPPM_MERGED_FROM_ITER;
     return m == 3 || (m < 0 && from >= 0 && iteration >= from && sweep_speculative(iteration, pixels, m));

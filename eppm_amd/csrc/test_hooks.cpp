@@ -3,6 +3,8 @@
 #define EPPM_TEST_HOOKS 1
 #include "api_internal.h"
 
+#include <array>
+
 using namespace eppm;
 
 std::atomic<int> g_opt_rand_table{1};
@@ -11,6 +13,14 @@ std::atomic<int> g_opt_no_split{0};
 std::atomic<int> g_opt_force_split{0};
 std::atomic<int> g_opt_search_pre{-1};
 std::atomic<int> g_opt_alloc_fill{-1};
+
+// "launch_log": the record behind eppm::g_launch_note; entries of six ints, capped so that a forgotten log cannot grow without bound
+static struct { std::mutex mu; std::vector<std::array<int, 6>> v; bool on = false; } g_log;
+static void launch_log_add(int stage, int w, int h, int npairs, int form, int extra)
+{
+    std::lock_guard<std::mutex> lk(g_log.mu);
+    if (g_log.on && g_log.v.size() < (size_t)1 << 16) g_log.v.push_back({stage, w, h, npairs, form, extra});
+}
 
 // "alloc_fill": the block an allocation site is about to hand out, filled with the chosen byte (api_internal.h)
 hipError_t alloc_fill(hipError_t e, void* p, size_t bytes, bool pinned)
@@ -41,6 +51,12 @@ extern "C" int eppm_test_set_option(const char* name, int value)
     if (!strcmp(name, "sweep_spec")) { g_opt_sweep_spec.store(value); return EPPM_OK; }
     if (!strcmp(name, "rand_table")) { g_opt_rand_table.store(value); return EPPM_OK; }
     if (!strcmp(name, "search_pre_from")) { g_opt_search_pre.store(value); return EPPM_OK; }
+    if (!strcmp(name, "launch_log")) {          // 1: an empty log from now on; 0: none (the entries are dropped)
+        g_launch_note.store(nullptr);
+        { std::lock_guard<std::mutex> lk(g_log.mu); g_log.v.clear(); g_log.on = value != 0; }
+        if (value) g_launch_note.store(launch_log_add);
+        return EPPM_OK;
+    }
     if (!strcmp(name, "alloc_fill")) {
         if (value < -1 || value > 255) return set_err(EPPM_ERR_ARG, "eppm_test_set_option: alloc_fill %d is neither -1 (off) nor a byte", value);
         g_opt_alloc_fill.store(value);
@@ -84,7 +100,32 @@ extern "C" int eppm_probe_dispatch(const char* stage, const int* args, int nargs
         out[0] = f.lpc; out[1] = f.pre; out[2] = f.tile;
         return EPPM_OK;
     }
+    if (!strcmp(stage, "levels")) {             // w, h, levels, level -> number of levels, and that level's w, h (eppm_level_dims of such a context)
+        CHK(shape(4, 3));
+        int H[kMaxLevels], W[kMaxLevels];
+        if (args[2] < 1 || args[2] > kMaxLevels) return set_err(EPPM_ERR_ARG, "eppm_probe_dispatch: levels %d", args[2]);
+        const int nl = pyr_init_dim(H, W, args[1], args[0], args[2], 0.5f);
+        if (args[3] < 0 || args[3] >= nl) return set_err(EPPM_ERR_ARG, "eppm_probe_dispatch: level %d of %d", args[3], nl);
+        out[0] = nl; out[1] = W[args[3]]; out[2] = H[args[3]];
+        return EPPM_OK;
+    }
+    if (!strcmp(stage, "patchmatch")) {        // w, h, iteration, problems, npairs -> sweeps speculative, sweeps merged ("sweep_spec" at -1)
+        CHK(shape(5, 2));
+        if (args[2] < 0 || args[3] < 1 || args[4] < 1) return set_err(EPPM_ERR_ARG, "eppm_probe_dispatch: iteration %d, problems %d, npairs %d", args[2], args[3], args[4]);
+        const long long problem_pixels = (long long)args[0] * args[1], pixels = problem_pixels * args[3] * args[4];
+        out[0] = sweep_speculative(args[2], pixels, -1) ? 1 : 0;
+        out[1] = sweeps_merged(args[2], pixels, problem_pixels, -1) ? 1 : 0;
+        return EPPM_OK;
+    }
     return set_err(EPPM_ERR_ARG, "eppm_probe_dispatch: unknown stage '%s'", stage);
+}
+// the launches noted since "launch_log" was switched on (eppm_internal.h: launch_note): returns their number, the first `cap` of them in out
+extern "C" int eppm_probe_launch_log(int* out, int cap)
+{
+    if (cap > 0 && !out) return 0;
+    std::lock_guard<std::mutex> lk(g_log.mu);
+    for (size_t i = 0; i < g_log.v.size() && (int)i < cap; i++) memcpy(out + 6 * i, g_log.v[i].data(), 6 * sizeof(int));
+    return (int)g_log.v.size();
 }
 // the two-phase search's decision (eppm_internal.h: pm_search_pretest) and the knobs its pre-test was built with
 extern "C" int eppm_probe_search_pretest(int iteration, int w, int h, int patch_r, int problems, int npairs, int* out, float* eps)

@@ -36,6 +36,7 @@ extern "C" {
  * "search_pre_from": -1 (default) a context's random searches take the two-phase form (pre-test on the centre rows, then the survivors
  * in full) from the iteration the library itself chooses (eppm_probe_search_pretest), k >= 0: from iteration k on -- beyond the last
  * iteration: never --, wherever the launch has a two-phase form at all (patch radius 9, quarter-block workgroups).
+ * "launch_log": 1 starts an empty record of what the launchers decide from now on (eppm_probe_launch_log), 0 (default) drops it.
  * "alloc_fill" is of another kind: it selects no kernel, it poisons memory.  -1 (default) off; 0..255: every block the library allocates
  * from then on -- a context's slab and its lazily made blocks (backward flow, interpolation, motion blur, streaming), the pinned staging
  * buffers, the state blocks of the attachments (tracker, temporal filter, stabiliser, cut detector, correspondence map, object detector),
@@ -75,8 +76,22 @@ int  eppm_probe_search_pretest(int iteration, int w, int h, int patch_r, int pro
  *   "search"     w, h, patch_r, problems, npairs, table  -> rows of a 16x16 block per workgroup: 4 (quarter block) or 2 (eighth block)
  *   "sweep"      w, h, patch_r, seg_len, dir, problems, npairs -> classic sweep: lanes per chain (0: generic kernel), up-front fetch
  *                                                           (given an evaluation cache), source tile in LDS (0: the sweep gathers)
+ *   "levels"     w, h, levels, level                     -> the pyramid a context of that size and eppm_params::levels builds: number of
+ *                                                           levels, and w, h of that level (what eppm_level_dims answers, without a context)
+ *   "patchmatch" w, h, iteration, problems, npairs       -> the sweeps of that PatchMatch iteration (0, 1, ..) with "sweep_spec" at its
+ *                                                           default: speculative two-launch form 1 / 0, merged form 1 / 0
  * problems = directions per pair in the launch (1 or 2).  EPPM_ERR_ARG for another stage or argument count. */
 int  eppm_probe_dispatch(const char* stage, const int* args, int nargs, int* out, int nout);
+/* What the launchers DID since "launch_log" was set to 1, in launch order: returns the number of entries and copies the first `cap` of them,
+ * six ints each: stage, w, h of one problem, pairs in the launch, form, extra --
+ *   0 smoothing       form = pixels per lane                                        extra 0
+ *   1 draft upsample  form = pixels per lane (k_flow_jbu<1 / 2>)                    extra 0
+ *   2 refine          form = workgroups per tile (0: not split)                     extra = patch radius
+ *   3 search          form = rows per workgroup (numbers drawn ahead only)          extra = 1: two-phase form
+ *   4 sweep           form = 4 x lanes per chain + 2 x up-front fetch + tile, or -1: speculative two-launch form;   extra = direction
+ *   5 merged sweeps   form = 1                                                      extra = iteration
+ * Entries beyond 65 536 are not recorded.  0 while the log is off. */
+int  eppm_probe_launch_log(int* out, int cap);
 /* device-side arithmetic probes (parity of the shared float formulas): y[i] = f(x[i]) for n host floats */
 int  eppm_probe_fast_exp(const float* x, float* y, int n);
 int  eppm_probe_div_const(const float* x, float* y, int n, int which); /* 0: /(.1f*.1f) 1: /(.02f*.02f) 2: unorm8 (x = 0..255) */
