@@ -11,5 +11,5 @@ when the library is missing.
 """
 from .build import build, lib_path  # noqa: F401
 from ._lib import EppmError, lib, select_library  # noqa: F401
-from .api import EPPM, EPPMBatch, Params, MBlurParams, motion_blur_sequence, TrackParams, Tracker, TemporalFilter, denoise_sequence, denoise_sequences, Stabilizer, stabilize_sequence, stabilize_sequences, CutDetector, detect_cuts, CMapParams, CorrespondenceMap, propagate_layer, propagate_layers, ObjectsParams, ObjectDetector, detect_objects, detect_objects_sequences, PlateParams, BackgroundPlate, background_plate, background_plates, remove_objects_sequence, host_register, host_unregister, pinned_empty, flow_sequence, flow_sequences, track_sequence  # noqa: F401
+from .api import EPPM, EPPMBatch, Params, MBlurParams, motion_blur_sequence, TrackParams, Tracker, TemporalFilter, denoise_sequence, denoise_sequences, Stabilizer, stabilize_sequence, stabilize_sequences, CutDetector, detect_cuts, CMapParams, CorrespondenceMap, propagate_layer, propagate_layers, ObjectsParams, ObjectDetector, detect_objects, detect_objects_sequences, PlateParams, BackgroundPlate, background_plate, background_plates, remove_objects_sequence, DefectFilter, remove_defects_sequence, remove_defects_sequences, host_register, host_unregister, pinned_empty, flow_sequence, flow_sequences, track_sequence  # noqa: F401
 from . import io, stages  # noqa: F401

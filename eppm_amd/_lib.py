@@ -68,6 +68,17 @@ class CPlateParams(C.Structure):
                 ("thresh", C.c_float), ("n_max", C.c_int), ("min_count", C.c_int)]
 
 
+class CDefectParams(C.Structure):
+    _fields_ = [("detect", C.c_float), ("agree", C.c_float), ("radius", C.c_int), ("grow", C.c_int)]
+
+
+class CDefectStats(C.Structure):
+    _fields_ = [("hit", C.c_int), ("grown", C.c_int), ("second_chance", C.c_int), ("undecided", C.c_int)]
+
+    def as_dict(self):
+        return {k: int(getattr(self, k)) for k, _ in self._fields_}
+
+
 class CObject(C.Structure):
     _fields_ = [("id", C.c_int32), ("age", C.c_int32), ("area", C.c_int32), ("x0", C.c_int32), ("y0", C.c_int32), ("x1", C.c_int32),
                 ("y1", C.c_int32), ("n_flow", C.c_int32), ("sum_x", C.c_int64), ("sum_y", C.c_int64), ("sum_qu", C.c_int64), ("sum_qv", C.c_int64)]
@@ -141,6 +152,9 @@ SYMBOLS = [
     "eppm_plate_step", "eppm_plate_step_frames", "eppm_plate_render", "eppm_plate_render_frames", "eppm_plate_get", "eppm_plate_get_device",
     "eppm_plate_get_mask", "eppm_plate_get_path", "eppm_plate_set_path", "eppm_plate_get_state", "eppm_plate_set_state",
     "eppm_plate_forms_host", "eppm_plate_block_host", "eppm_plate_accumulate_host", "eppm_plate_render_host",
+    "eppm_defect_default_params", "eppm_defect_create", "eppm_defect_create_size", "eppm_defect_destroy", "eppm_defect_reset", "eppm_defect_step",
+    "eppm_defect_step_frames", "eppm_defect_get", "eppm_defect_get_device", "eppm_defect_get_mask", "eppm_defect_get_stats",
+    "eppm_defect_get_state", "eppm_defect_set_state", "eppm_defect_step_host",
 ]
 
 

@@ -4,7 +4,7 @@ import ctypes as C
 import numpy as np
 
 from .io import cmap_seed, object_record
-from ._lib import CObject, CObjectsCounts, CObjectsParams, CPlateParams, CCMapParams, CCutParams, CCutStats, CGMotionModel, CMBlurParams, CParams, CStabParams, CTFilterParams, CTrackCounts, CTrackParams, EppmError, check, lib
+from ._lib import CDefectParams, CDefectStats, CObject, CObjectsCounts, CObjectsParams, CPlateParams, CCMapParams, CCutParams, CCutStats, CGMotionModel, CMBlurParams, CParams, CStabParams, CTFilterParams, CTrackCounts, CTrackParams, EppmError, check, lib
 
 uchar4 = np.dtype([("x", "u1"), ("y", "u1"), ("z", "u1"), ("w", "u1")])
 short2 = np.dtype([("x", "i2"), ("y", "i2")])
@@ -249,6 +249,60 @@ class TemporalFilter(_ClipObject):
         if acc.shape != (self.h, self.w, 4):
             raise EppmError(f"TemporalFilter.set_state: the state must be ({self.h},{self.w},4) float32")
         check(lib().eppm_tfilter_set_state(self._f, int(slot), acc.ctypes.data_as(C.c_void_p)), "eppm_tfilter_set_state")
+
+
+class DefectFilter(_ClipObject):
+    """Film-defect removal over the pairs of a context (eppm_defect_*): single-frame blotches (dust, dirt, dropouts)
+    are concealed from both motion-compensated neighbours.  ctx: an EPPM or an EPPMBatch; one slot per pair of it.  Every step() repairs
+    IMAGE 1 of the active pairs of the context's last compute_flow_bidirectional*, from image 2 and from the frame and backward flow the
+    step before saved; the first step of a slot (new, after reset() or after a cut) and a step whose pair is cut pass image 1 through, so
+    the first and the last frame of a clip are never repaired.  The filter is its own allocation on the context's device; close() frees it."""
+    _prefix = "defect"
+
+    def __init__(self, ctx, detect=60.0, agree=30.0, radius=3, grow=1, size=None, slots=1, device=0):
+        """ctx None: a filter without a context, for step_frames on caller planes (eppm_defect_create_size): size = (h, w), `slots` slots."""
+        self.params = CDefectParams(float(detect), float(agree), int(radius), int(grow))
+        self._open(ctx, size, slots, device)
+
+    def step_frames(self, slot, d_rgba1, d_rgba2, pitch, d_flow, d_flow_bwd, cut=False):
+        """eppm_defect_step_frames: one step of one slot on caller device planes (addresses), synchronous."""
+        check(lib().eppm_defect_step_frames(self._f, int(slot), C.c_void_p(d_rgba1), C.c_void_p(d_rgba2), C.c_size_t(pitch),
+                                            C.c_void_p(d_flow), C.c_void_p(d_flow_bwd), int(bool(cut))), "eppm_defect_step_frames")
+
+    def frame(self, slot=0):
+        """(h, w, 3) uint8: the slot's repaired image 1 of the last step."""
+        return self._rgb("get", slot)
+
+    def frames(self):
+        """The repaired frames of the context's active pairs' slots."""
+        return [self.frame(k) for k in range(getattr(self.ctx, "n", 1))]
+
+    def frame_device(self, slot, d_rgba, pitch):
+        check(lib().eppm_defect_get_device(self._f, int(slot), C.c_void_p(d_rgba), C.c_size_t(pitch)), "eppm_defect_get_device")
+
+    def mask(self, slot=0):
+        """(h, w) uint8: 0 untouched, 1 hit, 2 grown."""
+        m = np.empty((self.h, self.w), np.uint8)
+        self._call("get_mask", int(slot), m.ctypes.data_as(C.c_void_p))
+        return m
+
+    def stats(self, slot=0):
+        """dict(hit, grown, second_chance, undecided): the pixel counts of the slot's last step."""
+        st = CDefectStats()
+        self._call("get_stats", int(slot), C.byref(st))
+        return st.as_dict()
+
+    def state(self, slot=0):
+        """(frame (h, w, 3) uint8, backward flow (h, w, 2) float32, has_prev): what the slot's last step saved."""
+        rgb, bwd, has = np.empty((self.h, self.w, 3), np.uint8), np.empty((self.h, self.w, 2), np.float32), C.c_int()
+        self._call("get_state", int(slot), rgb.ctypes.data_as(C.c_void_p), bwd.ctypes.data_as(C.c_void_p), C.byref(has))
+        return rgb, bwd, bool(has.value)
+
+    def set_state(self, slot, frame, bwd, has_prev=True):
+        rgb, bwd = np.ascontiguousarray(frame, np.uint8), np.ascontiguousarray(bwd, np.float32)
+        if rgb.shape != (self.h, self.w, 3) or bwd.shape != (self.h, self.w, 2):
+            raise EppmError(f"DefectFilter.set_state: a ({self.h},{self.w},3) uint8 frame and a ({self.h},{self.w},2) float32 flow")
+        self._call("set_state", int(slot), rgb.ctypes.data_as(C.c_void_p), bwd.ctypes.data_as(C.c_void_p), int(bool(has_prev)))
 
 
 class Stabilizer(_ClipObject):
@@ -908,6 +962,107 @@ def denoise_sequences(clips, slots=8, params=None, thresh=40.0, n_max=8, tempora
         if e is not None:
             e.close()
     return out
+
+
+def _defect_split(kw):
+    """the keyword arguments of remove_defects_sequence(s): DefectFilter's go to the filter, CutDetector's to the detector"""
+    df = {k: kw.pop(k) for k in ("detect", "agree", "radius", "grow") if k in kw}
+    cut = {k: kw.pop(k) for k in ("lost_permille", "residual_max") if k in kw}
+    if kw:
+        raise TypeError(f"unknown parameter {sorted(kw)[0]}")
+    return df, cut
+
+
+def remove_defects_sequence(frames, auto_cut=False, stop_level=None, masks=False, params=None, temporal=True, **kw):
+    """A clip ((h, w, 3) uint8 frames) with its single-frame defects concealed (DefectFilter): one streaming context
+    -- set_data, then push_frame --, one bidirectional call on the device and one filter step per pair; the step of pair (k, k + 1)
+    gives frame k.  Returns len(frames) frames: the first, the last and (auto_cut=True: a CutDetector looks at every pair first) the
+    frames next to a cut are the input itself.  masks=True: (frames, masks), one (h, w) uint8 mask per frame (0 untouched, 1 hit, 2
+    grown).  kw: DefectFilter's detect / agree / radius / grow and CutDetector's lost_permille / residual_max.  params: the flow's eppm
+    Params; temporal / stop_level: the flow's temporal and draft modes.  Memory does not grow with the clip."""
+    df, cut_params = _defect_split(kw)
+    stop_level = _level(0 if stop_level is None else stop_level)
+    frames = [np.ascontiguousarray(f, np.uint8) for f in frames]
+    if len(frames) < 2:
+        raise EppmError("remove_defects_sequence: at least two frames")
+    h, w, _ = frames[0].shape
+    e = EPPM(params=params)
+    flt = det = None
+    out, ms = [], []
+    try:
+        e.init(h, w)
+        e.set_temporal(temporal)
+        e.set_stop_level(stop_level)
+        flt = DefectFilter(e, **df)
+        if auto_cut:
+            det = CutDetector(e, **cut_params)
+        for k in range(len(frames) - 1):
+            if k == 0:
+                e.set_data(frames[0], frames[1])
+            else:
+                e.push_frame(frames[k + 1])
+            e.compute_flow_bidirectional_device()
+            flt.step(_auto_cut_step(e, det) if auto_cut else None)
+            out.append(flt.frame(0))
+            if masks:
+                ms.append(flt.mask(0))
+    finally:
+        if det is not None:
+            det.close()
+        if flt is not None:
+            flt.close()
+        e.close()
+    out.append(frames[-1].copy())
+    ms.append(np.zeros((h, w), np.uint8))
+    return (out, ms) if masks else out
+
+
+def remove_defects_sequences(clips, slots=8, auto_cut=False, stop_level=None, masks=False, params=None, temporal=True, **kw):
+    """remove_defects_sequence for many clips at once: clips of one frame size and of any lengths (two frames at least) through ONE batch
+    context of min(slots, len(clips)) slots and one DefectFilter, on flow_sequences' schedule.  A slot that takes the next clip of the queue
+    passes `cut` for that step.  Returns one list of frames per clip (masks=True: (frames, masks)), each what remove_defects_sequence(clip)
+    returns.  auto_cut=True: per slot; the detector's verdicts are ORed into the schedule's cut flags."""
+    df, cut_params = _defect_split(kw)
+    stop_level = _level(0 if stop_level is None else stop_level)
+    clips = [[np.ascontiguousarray(f, np.uint8) for f in clip] for clip in clips]
+    plan = _sequence_plan([len(c) for c in clips], slots)
+    h, w, _ = clips[0][0].shape
+    out = [[] for _ in clips]
+    ms = [[] for _ in clips]
+    e = flt = det = None
+    try:
+        for t, step in enumerate(plan):
+            if t == 0:
+                e = EPPMBatch(h, w, len(step), params=params)
+                e.set_temporal(temporal)
+                e.set_stop_level(stop_level)
+                flt = DefectFilter(e, **df)
+                if auto_cut:
+                    det = CutDetector(e, **cut_params)
+                e.set_data([(clips[c][0], clips[c][1]) for c, _, _, _ in step])
+            else:
+                e.push_frames([clips[c][f] for c, f, _, _ in step], [cut for _, _, cut, _ in step])
+            e.compute_flow_bidirectional_device()
+            flags = [cut for _, _, cut, _ in step]
+            if auto_cut:
+                flags = [a or b for a, b in zip(flags, _auto_cut_step(e, det))]
+            flt.step(flags)
+            for slot, (c, _, _, keep) in enumerate(step):
+                if keep:        # the slot's pair is (frame - 1, frame) of clip c: the step's output is frame - 1
+                    out[c].append(flt.frame(slot))
+                    if masks:
+                        ms[c].append(flt.mask(slot))
+    finally:
+        if det is not None:
+            det.close()
+        if flt is not None:
+            flt.close()
+        if e is not None:
+            e.close()
+    for c, clip in enumerate(clips):
+        out[c].append(clip[-1].copy())
+        ms[c].append(np.zeros((h, w), np.uint8))
+    return (out, ms) if masks else out
 
 
 def _cmap_split(kw):

@@ -534,6 +534,39 @@ void launch_plate_render(const PlateRenderArgs& a, hipStream_t s);
 // the canvas states as RGBA words (cw words per row) and coverage bytes
 void launch_plate_word(const char* canvas, uint32_t* words, uint8_t* cov, int ch, int cw, hipStream_t s);
 
+// ---- film-defect removal (k_defect.hip; the arithmetic: defect.h) ----
+// One step covers n pairs: pair k's inputs (image 1 / image 2: RGBA words, img_pitch bytes per row; fwd / bwd: h*w float2) lie k * (their
+// stride) bytes past pair 0's and feed slot slot0 + k, whose block lies (slot0 + k) * slot_stride bytes past `mem`: saved backward plane 0
+// | 1 (h*w float2 each) | saved frame 0 | 1 | replacement | out (h*w RGBA words each) | code | mask (h*w bytes each); the slot's four
+// counters (eppm_defect_stats) lie (slot0 + k) * 16 bytes past `stats`.  The per-slot bits travel in the kernel arguments as TFilterArgs'
+// do: cur (which saved set is the previous frame's; the step writes the other) and detect (the saved set belongs to the frame before
+// image 1 and no cut follows: the step detects; otherwise it passes image 1 through).
+struct DefectArgs {
+    const uint8_t* img1;
+    const uint8_t* img2;
+    size_t img_pitch, img_stride;
+    const float* fwd;
+    size_t fwd_stride;
+    const float* bwd;
+    size_t bwd_stride;
+    char* mem;
+    size_t slot_stride;
+    int32_t* stats;
+    int h, w, n, slot0;
+    float detect, agree;
+    int radius, grow;
+    uint32_t cur[kTemporalMaxSlots / 32], active[kTemporalMaxSlots / 32];
+};
+// the planes of a slot's block, in bytes from its start (px = h*w)
+constexpr size_t defect_off_bwd(size_t px, int which) { return (size_t)which * px * 8; }
+constexpr size_t defect_off_img(size_t px, int which) { return px * 16 + (size_t)which * px * 4; }
+constexpr size_t defect_off_repl(size_t px) { return px * 24; }
+constexpr size_t defect_off_out(size_t px) { return px * 28; }
+constexpr size_t defect_off_code(size_t px) { return px * 32; }
+constexpr size_t defect_off_mask(size_t px) { return px * 33; }
+void launch_defect_detect(const DefectArgs& a, hipStream_t s);
+void launch_defect_apply(const DefectArgs& a, hipStream_t s);
+
 // ---- flow colour coding (k_color.hip) ----
 // rgba: h*w packed R | G<<8 | B<<16 (alpha 0); flow: h*w float2
 void launch_flow_to_color(uint32_t* rgba, const float* flow, int h, int w, float max_disp_x, float max_disp_y, hipStream_t s, Batch bt = kOnePair);

@@ -226,6 +226,27 @@ def tfilter_step_host(acc, img2, bu, bv, occ2, thresh=40.0, n_max=8, cut=False):
     return out, rgb
 
 
+def defect_step_host(prev, cur, nxt, bu=None, bv=None, fu=None, fv=None, detect=60.0, agree=30.0, radius=3, grow=1):
+    """One step of film-defect removal on the host (eppm_defect_step_host; bit-identical to the kernels).  cur: the
+    (h, w, 3) uint8 frame to repair; prev / nxt: its neighbours (None: the passing step); (bu, bv) / (fu, fv): the (h, w) float32 vectors
+    from cur into prev / into nxt.  Returns (rgb (h, w, 3) uint8, mask (h, w) uint8: 0 untouched, 1 hit, 2 grown, stats dict)."""
+    from ._lib import CDefectParams, CDefectStats
+    p = CDefectParams(float(detect), float(agree), int(radius), int(grow))
+    c = np.ascontiguousarray(cur, np.uint8)
+    if c.ndim != 3 or c.shape[2] != 3:
+        raise ValueError("defect_step_host: the frame must be (h, w, 3)")
+    h, w, _ = c.shape
+    imgs = [None if a is None else np.ascontiguousarray(a, np.uint8) for a in (prev, nxt)]
+    flows = [None if a is None else np.ascontiguousarray(a, np.float32) for a in (bu, bv, fu, fv)]
+    if any(a is not None and a.shape != c.shape for a in imgs) or any(a is not None and a.shape != (h, w) for a in flows):
+        raise ValueError("defect_step_host: frames (h, w, 3), flow planes (h, w)")
+    ptr = lambda a: None if a is None else a.ctypes.data_as(C.c_void_p)
+    out, mask, st = np.empty_like(c), np.empty((h, w), np.uint8), CDefectStats()
+    check(lib().eppm_defect_step_host(C.byref(p), ptr(out), ptr(mask), C.byref(st), ptr(imgs[0]), ptr(c), ptr(imgs[1]), *[ptr(a) for a in flows],
+                                      h, w), "eppm_defect_step_host")
+    return out, mask, st.as_dict()
+
+
 def cmap_seed(h, w):
     """(h, w, 2) float32: the seed of a correspondence map, map(x, y) = (x, y)."""
     m = np.empty((int(h), int(w), 2), np.float32)

@@ -425,6 +425,70 @@ int  eppm_tfilter_step_host(const eppm_tfilter_params* p, float* acc_out, uint8_
                             const float* bu, const float* bv, const uint8_t* occ2, int h, int w, int cut);
 
 /* ----------------------------------------------------------------------------------------
+ * film-defect removal: dust, dirt, dropouts and sparkle live for one frame, so a defective pixel differs from both
+ * of its motion-compensated neighbours in time while those agree with each other.  A step runs on the pair (image 1 = F_k, image 2 =
+ * F_k+1) and repairs IMAGE 1: its next side is image 2 through the level-0 forward flow, its previous side is F_k-1 through the backward
+ * flow of the step before, both of which every step saves per slot (a copy of image 1 and of the backward plane).  Per pixel: p and n are
+ * the bilinear samples of the previous and the next frame; with d(a, b) = |dR| + |dG| + |dB| the pixel is DECIDED if both samples exist
+ * and d(p, n) <= agree, and a HIT if also d(cur, p) > detect and d(cur, n) > detect.  A pixel its own two vectors do not decide gets a
+ * second chance with the component-wise lower median of the vectors of its (2 radius + 1)^2 window (coordinates clamped; a window that
+ * holds an unknown vector has no median); a pixel neither chance decides is never touched.  A decided pixel within `grow` pixels of a hit
+ * is GROWN.  Hit and grown pixels become the rounded mean of p and n; every other pixel keeps image 1's colour.  The first and the last
+ * frame of a clip are never repaired (they have one neighbour only), nor is the frame before or after a cut.  The kernels equal
+ * eppm_defect_step_host bit for bit, in both libraries.  A defect filter is a separate allocation on its context's device (34 bytes per
+ * pixel and slot), made by eppm_defect_create and freed by eppm_defect_destroy; a context that never creates one allocates and launches
+ * exactly what it did without.  A slot has_prev if its saved planes belong to the frame before image 1: a step DETECTS if has_prev and
+ * the pair is not cut, otherwise it PASSES (the output is image 1, the mask and the stats are zero); after either has_prev = !cut.
+ * -------------------------------------------------------------------------------------- */
+typedef struct eppm_defect_params {
+    float detect;                /* a hit differs from both neighbours by more than this |dR| + |dG| + |dB| (60); finite, >= 0 */
+    float agree;                 /* the two neighbours differ by at most this (30); finite, >= 0 */
+    int   radius;                /* the median window of the second chance, 0 .. 4 (3); 0: no second chance */
+    int   grow;                  /* hits are grown by this many pixels, 0 .. 4 (1) */
+} eppm_defect_params;
+typedef struct eppm_defect_stats {
+    int hit;                     /* pixels with mask 1 */
+    int grown;                   /* pixels with mask 2 */
+    int second_chance;           /* pixels decided by the median vectors */
+    int undecided;               /* pixels decided by neither chance */
+} eppm_defect_stats;
+typedef struct eppm_defect eppm_defect;
+
+int  eppm_defect_default_params(eppm_defect_params* p);
+/* p NULL: the defaults.  One slot per pair of ctx (eppm_batch_size), on its device; no slot has_prev. */
+int  eppm_defect_create(eppm_ctx* ctx, const eppm_defect_params* p, eppm_defect** out);
+/* a defect filter without a context, for eppm_defect_step_frames on caller planes: nslots slots of h x w pixels (any size from 1 x 1) */
+int  eppm_defect_create_size(int h, int w, int nslots, int device, const eppm_defect_params* p, eppm_defect** out);
+int  eppm_defect_destroy(eppm_defect* f);                  /* NULL is fine */
+int  eppm_defect_reset(eppm_defect* f, int slot);          /* the slot's next step passes; slot < 0: every slot's */
+/* One step of slots 0 .. active pairs - 1 on the pairs of ctx's last eppm_compute_bidirectional* (the raw frames and both level-0 flows):
+ * valid in the window of eppm_interpolate* (EPPM_ERR_STATE outside it); EPPM_ERR_ARG for a context of other dimensions, another device or
+ * more active pairs than the filter has slots.  cut: NULL, or one flag per active pair; non-zero: image 2 of that pair is the first frame
+ * of another clip.  A slot the step does not cover keeps its state.  Two launches, asynchronous on the context's stream: no copy, no
+ * allocation, no host synchronisation. */
+int  eppm_defect_step(eppm_defect* f, eppm_ctx* ctx, const uint8_t* cut);
+/* the same step of one slot on caller device planes of the filter's size (RGBA images of `pitch` bytes per row, h*w float2 forward and
+ * backward flow); on the launcher stream, synchronous.  Whatever the planes hold, nothing outside them is read. */
+int  eppm_defect_step_frames(eppm_defect* f, int slot, const void* d_rgba1, const void* d_rgba2, size_t pitch, const eppm_float2* d_flow,
+                             const eppm_float2* d_flow_bwd, int cut);
+/* the slot's repaired image 1 of the last step (EPPM_ERR_STATE on a slot never stepped): packed RGB to the host, synchronous ... */
+int  eppm_defect_get(eppm_defect* f, int slot, uint8_t* rgb, size_t row_stride);
+/* ... or RGBA words (alpha 255) into a device plane, asynchronous on the stream of the filter's last step */
+int  eppm_defect_get_device(eppm_defect* f, int slot, void* d_rgba, size_t pitch);
+/* synchronous: the last step's mask (h*w bytes: 0 untouched, 1 hit, 2 grown) and counts */
+int  eppm_defect_get_mask(eppm_defect* f, int slot, uint8_t* mask);
+int  eppm_defect_get_stats(eppm_defect* f, int slot, eppm_defect_stats* stats);
+/* synchronous.  The slot's saved frame (packed RGB, h*w*3), saved backward plane (h*w interleaved (x, y) floats) and has_prev
+ * (EPPM_ERR_STATE on a slot that holds none) / load them */
+int  eppm_defect_get_state(eppm_defect* f, int slot, uint8_t* rgb, float* bwd, int* has_prev);
+int  eppm_defect_set_state(eppm_defect* f, int slot, const uint8_t* rgb, const float* bwd, int has_prev);
+/* host form (no GPU needed): one step on packed RGB frames; (bu, bv): the vectors from rgb_cur into rgb_prev, (fu, fv): into rgb_next.
+ * rgb_prev or rgb_next NULL: the passing step (the flows are not read).  rgb_out must not be rgb_cur. */
+int  eppm_defect_step_host(const eppm_defect_params* p, uint8_t* rgb_out, uint8_t* mask_out, eppm_defect_stats* stats, const uint8_t* rgb_prev,
+                           const uint8_t* rgb_cur, const uint8_t* rgb_next, const float* bu, const float* bv, const float* fu, const float* fv,
+                           int h, int w);
+
+/* ----------------------------------------------------------------------------------------
  * global camera motion and video stabilisation.  One step, after eppm_compute_bidirectional* on a streamed clip's
  * next pair, (a) fits an affine camera motion to the pair's level-0 forward flow by iters passes of least squares on the inliers of the
  * pass before (pixels with occ1 == 0 and a known vector of at most 8192 px; an inlier's residual is at most tau), (b) classifies every
@@ -764,7 +828,7 @@ int  eppm_clear_stage_times(eppm_ctx* ctx);
  * "flow_blf_bwd_L<l>", "flow_blf_bwd_final" and "fb_occlusion"; an interpolation call "interp_splat", "interp_fill" and "interp_blend"
  * (mode 1, once per group of four times); a track step "track_advance", "track_seed" and "track_compact" (mode 1; the step that seeds
  * frame 0 adds a "track_seed" before "track_advance"); a compute that starts from a temporal prior "temporal_advect" (before "patchmatch") and
- * "temporal_select" (inside it: "patchmatch" includes its time); a temporal-filter step "tfilter_step"; a stabiliser step "stab_fit" (every accumulate and solve launch) and "stab_warp"; a cut-detector step "cutdet"; a motion-blur call "mblur_pack" and "mblur_gather"; a correspondence-map step "cmap_step" and "cmap_render"; an object-detector step "objects_fit" (its stabiliser's launches), "objects_label" and "objects_assign"; a background-plate step "plate_fit" (its stabiliser's launches), "plate_block" and "plate_accumulate", its render "plate_render".  Events come from a per-context pool: none is created in a steady-state step. */
+ * "temporal_select" (inside it: "patchmatch" includes its time); a temporal-filter step "tfilter_step"; a stabiliser step "stab_fit" (every accumulate and solve launch) and "stab_warp"; a cut-detector step "cutdet"; a motion-blur call "mblur_pack" and "mblur_gather"; a correspondence-map step "cmap_step" and "cmap_render"; an object-detector step "objects_fit" (its stabiliser's launches), "objects_label" and "objects_assign"; a background-plate step "plate_fit" (its stabiliser's launches), "plate_block" and "plate_accumulate", its render "plate_render"; a defect-filter step "defect_detect" and "defect_apply".  Events come from a per-context pool: none is created in a steady-state step. */
 int  eppm_enable_stage_timing(eppm_ctx* ctx, int on);
 
 const char* eppm_last_error(void);

@@ -39,6 +39,12 @@
 //                     of the motion-compensated temporal filter; the filtered frames are written to
 //                     P_dn_0000.ppm (the first frame itself), P_dn_0001.ppm ...  --denoise-thresh T (default 40) and
 //                     --denoise-frames N (the longest average, default 8) set its parameters and imply --denoise.
+//                     --remove-defects: every pair runs the bidirectional call followed by one step of the defect filter (DESIGN.md
+//                     section 23): single-frame blotches of frame k - 1 are concealed from frames k - 2 and k.  The frames are written
+//                     to P_df_0000.ppm ..., their masks (0 untouched, 1 hit, 2 grown) to P_dfm_0000.pgm ..., and P_defects.txt gets one
+//                     line per frame: its index and the counts hit, grown, second_chance, undecided.  The first and the last frame of
+//                     the clip (and, with --auto-cut, of every shot) are written as they are.  --defect-thresh D A (defaults 60 30),
+//                     --defect-radius R (0 .. 4, default 3) and --defect-grow G (0 .. 4, default 1) set its parameters and imply it.
 //                     --stabilize: every pair runs the bidirectional call followed by one step of the stabiliser (DESIGN.md section 16:
 //                     the camera motion fitted to the forward flow, the frame re-rendered from the smoothed camera path); the frames are
 //                     written to P_st_0000.ppm (the first frame itself), P_st_0001.ppm ...  --smooth S (0 .. 1, default 0.9; 1: tripod
@@ -69,6 +75,7 @@
 //                     was confirmed (0: never seen).  --remove-objects (implies --plate): a second pass renders every frame against
 //                     the finished plate: P_ro_0000.ppm ... are the frames with their moving objects painted out; the frames, masks and
 //                     paths of the first pass are kept in host memory.  The last frame has no pair of its own and is written unchanged.
+#include <algorithm>
 #include <atomic>
 #include <chrono>
 #include <cstdio>
@@ -107,6 +114,8 @@ struct Options {
     bool denoise = false;                                   // --denoise
     float dn_thresh = 40.0f;                                // --denoise-thresh
     int dn_frames = 8;                                      // --denoise-frames
+    bool defects = false;                                   // --remove-defects
+    eppm_defect_params df = {60.0f, 30.0f, 3, 1};           // --defect-thresh, --defect-radius, --defect-grow
     bool stabilize = false;                                 // --stabilize
     float smooth = 0.9f;                                    // --smooth
     bool auto_cut = false;                                  // --auto-cut
@@ -175,7 +184,8 @@ static int usage()
                     "               [--denoise] [--denoise-thresh T] [--denoise-frames N] [--stabilize] [--smooth S]\n"
                     "               [--auto-cut] [--cut-lost N] [--motion-blur S] [--blur-radius R] [--blur-taps N]\n"
                     "               [--propagate layer.ppm alpha.ppm] [--objects] [--min-area N] [--max-objects N]\n"
-                    "               [--plate] [--plate-margin MX MY] [--remove-objects]\n");
+                    "               [--plate] [--plate-margin MX MY] [--remove-objects]\n"
+                    "               [--remove-defects] [--defect-thresh D A] [--defect-radius R] [--defect-grow G]\n");
     return 2;
 }
 
@@ -212,6 +222,12 @@ static int run_sequence(const Options& o)
     eppm_cmap* cm = nullptr;
     eppm_objects* od = nullptr;
     struct PlateGuard { eppm_plate* p = nullptr; ~PlateGuard() { eppm_plate_destroy(p); } } plt;          // freed on every way out
+    struct DefectGuard {                                                                                   // freed and closed on every way out
+        eppm_defect* p = nullptr;
+        FILE* txt = nullptr;
+        ~DefectGuard() { eppm_defect_destroy(p); if (txt) fclose(txt); }
+    } dfl;
+    std::vector<unsigned char> df_rgb, df_mask;
     std::vector<std::vector<unsigned char>> ro_frames, ro_masks;          // --remove-objects: what the second pass needs of the first
     std::vector<std::vector<double>> ro_paths;
     FILE* cuts = nullptr;
@@ -234,6 +250,23 @@ static int run_sequence(const Options& o)
         if (eppm_tfilter_create(ctx, &tp, &flt) != EPPM_OK) return fail("eppm_tfilter_create");
         dn.resize((size_t)h * w * 3);
     }
+    if (o.defects) {
+        if (eppm_defect_create(ctx, &o.df, &dfl.p) != EPPM_OK) return fail("eppm_defect_create");
+        df_rgb.resize((size_t)h * w * 3);
+        df_mask.resize((size_t)h * w);
+        snprintf(name, sizeof name, "%s_defects.txt", o.prefix);
+        if (!(dfl.txt = fopen(name, "w"))) { fprintf(stderr, "cannot write %s\n", name); return fail("fopen"); }
+    }
+    // one frame of --remove-defects: the frame, its mask and its line of counts
+    auto write_defects = [&](size_t frame, const unsigned char* rgb, const unsigned char* mask, const eppm_defect_stats& ds) {
+        snprintf(name, sizeof name, "%s_df_%04zu.ppm", o.prefix, frame);
+        if (!write_ppm(name, rgb, h, w)) return false;
+        snprintf(name, sizeof name, "%s_dfm_%04zu.pgm", o.prefix, frame);
+        FILE* f = fopen(name, "wb");
+        bool ok = f && fprintf(f, "P5\n%d %d\n255\n", w, h) > 0 && fwrite(mask, 1, (size_t)h * w, f) == (size_t)h * w;
+        if (f) ok = fclose(f) == 0 && ok;
+        return ok && fprintf(dfl.txt, "%zu %d %d %d %d\n", frame, ds.hit, ds.grown, ds.second_chance, ds.undecided) > 0;
+    };
     if (o.pl_layer) {
         int hl = 0, wl = 0;
         std::vector<unsigned char> rgb((size_t)h * w * 3), alpha((size_t)h * w * 3);
@@ -326,7 +359,7 @@ static int run_sequence(const Options& o)
         if (k == 1) { if (eppm_set_images(ctx, img[0].data(), img[1].data(), (size_t)w * 3) != EPPM_OK) return fail("eppm_set_images"); }
         else if (eppm_push_image(ctx, cur.data(), (size_t)w * 3) != EPPM_OK) return fail("eppm_push_image");
         const bool last = k + 1 == o.seq.size();
-        if (!o.denoise && !o.stabilize && !o.auto_cut && !cm && !od && !plt.p && !(o.mblur && last)) { if (eppm_compute(ctx, u.data(), v.data()) != EPPM_OK) return fail("eppm_compute"); }
+        if (!o.denoise && !o.stabilize && !o.auto_cut && !cm && !od && !plt.p && !dfl.p && !(o.mblur && last)) { if (eppm_compute(ctx, u.data(), v.data()) != EPPM_OK) return fail("eppm_compute"); }
         else {
             if (eppm_compute_bidirectional(ctx, u.data(), v.data(), nullptr, nullptr, nullptr, nullptr) != EPPM_OK) return fail("eppm_compute_bidirectional");
             uint8_t cut = 0;
@@ -343,6 +376,18 @@ static int run_sequence(const Options& o)
             }
             if (o.denoise && eppm_tfilter_step(flt, ctx, o.auto_cut ? &cut : nullptr) != EPPM_OK) return fail("eppm_tfilter_step");
             if (o.stabilize && eppm_stab_step(stab, ctx, o.auto_cut ? &cut : nullptr) != EPPM_OK) return fail("eppm_stab_step");
+            if (dfl.p) {                // the step of pair (k - 1, k) gives frame k - 1
+                eppm_defect_stats ds;
+                if (eppm_defect_step(dfl.p, ctx, o.auto_cut ? &cut : nullptr) != EPPM_OK) return fail("eppm_defect_step");
+                if (eppm_defect_get(dfl.p, 0, df_rgb.data(), (size_t)w * 3) != EPPM_OK) return fail("eppm_defect_get");
+                if (eppm_defect_get_mask(dfl.p, 0, df_mask.data()) != EPPM_OK) return fail("eppm_defect_get_mask");
+                if (eppm_defect_get_stats(dfl.p, 0, &ds) != EPPM_OK) return fail("eppm_defect_get_stats");
+                if (!write_defects(k - 1, df_rgb.data(), df_mask.data(), ds)) { fprintf(stderr, "cannot write %s\n", name); return fail("write"); }
+                if (last) {             // the clip's last frame has no next neighbour
+                    std::fill(df_mask.begin(), df_mask.end(), 0);
+                    if (!write_defects(k, cur.data(), df_mask.data(), eppm_defect_stats{0, 0, 0, 0})) { fprintf(stderr, "cannot write %s\n", name); return fail("write"); }
+                }
+            }
             if (cm) {
                 if (eppm_cmap_step(cm, ctx, o.auto_cut ? &cut : nullptr) != EPPM_OK) return fail("eppm_cmap_step");
                 if (cut) pl_drawn = false;              // the layer belongs to the first shot
@@ -446,10 +491,15 @@ static int run_sequence(const Options& o)
         release();
         printf("%zu frames with %zu pixels filled from the plate -> %s_ro_0000.ppm ...\n", ro_frames.size(), filled, o.prefix);
     }
+    const bool dft_ok = !dfl.txt || fclose(dfl.txt) == 0;
+    dfl.txt = nullptr;
+    if (!dft_ok) { fprintf(stderr, "cannot write %s_defects.txt\n", o.prefix); return fail("write"); }
     const bool cuts_ok = !cuts || fclose(cuts) == 0;
     const bool obf_ok = !obf || fclose(obf) == 0;
     eppm_plate_destroy(plt.p);
     plt.p = nullptr;
+    eppm_defect_destroy(dfl.p);
+    dfl.p = nullptr;
     eppm_objects_destroy(od); eppm_cmap_destroy(cm); eppm_cutdet_destroy(det);
     eppm_stab_destroy(stab);
     eppm_tfilter_destroy(flt);
@@ -523,6 +573,18 @@ int main(int argc, char** argv)
             o.denoise = true;
         }
         else if (!strcmp(a, "--denoise-frames")) { if (!val(&v) || v < 1 || v > 255) return usage(); o.dn_frames = (int)v; o.denoise = true; }
+        else if (!strcmp(a, "--remove-defects")) o.defects = true;
+        else if (!strcmp(a, "--defect-thresh")) {
+            if (i + 2 >= argc) return usage();
+            char *e1 = nullptr, *e2 = nullptr;
+            o.df.detect = strtof(argv[i + 1], &e1);
+            o.df.agree = strtof(argv[i + 2], &e2);
+            if (!e1 || e1 == argv[i + 1] || *e1 || !e2 || e2 == argv[i + 2] || *e2) return usage();
+            i += 2;
+            o.defects = true;
+        }
+        else if (!strcmp(a, "--defect-radius")) { if (!val(&v) || v < 0 || v > 4) return usage(); o.df.radius = (int)v; o.defects = true; }
+        else if (!strcmp(a, "--defect-grow")) { if (!val(&v) || v < 0 || v > 4) return usage(); o.df.grow = (int)v; o.defects = true; }
         else if (!strcmp(a, "--stabilize")) o.stabilize = true;
         else if (!strcmp(a, "--smooth")) {
             if (i + 1 >= argc) return usage();
@@ -559,7 +621,7 @@ int main(int argc, char** argv)
             return usage();
         return run_sequence(o);
     }
-    if (o.denoise || o.stabilize || o.auto_cut || o.pl_layer || o.objects || o.plate) return usage();     // the filter, the stabiliser, the cut detector, the map and the object detector walk a clip
+    if (o.denoise || o.stabilize || o.auto_cut || o.pl_layer || o.objects || o.plate || o.defects) return usage();     // the filter, the stabiliser, the cut detector, the map and the object detector walk a clip
     if ((o.mblur && !o.mblur_file) || (o.mb_set && !o.mblur)) return usage();
     if (pos.size() == 1 || pos.size() > 3) return usage();
     if (pos.size() >= 2) { o.f1 = pos[0]; o.f2 = pos[1]; }
