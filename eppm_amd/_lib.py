@@ -159,7 +159,7 @@ SYMBOLS = [
 
 
 # what include/eppm_test.h adds, exported by libeppm_hip_test.so and libeppm_hip_tol_test.so only (the parity tests' switches and arithmetic probes)
-TEST_SYMBOLS = ["eppm_test_set_option", "eppm_test_c2f_refine_batch", "eppm_probe_c2f_window", "eppm_probe_dispatch", "eppm_probe_fast_exp", "eppm_probe_div_const", "eppm_probe_delta_table",
+TEST_SYMBOLS = ["eppm_test_set_option", "eppm_test_c2f_refine_batch", "eppm_test_c2f_refine_pre", "eppm_test_c2f_refine_probe", "eppm_probe_c2f_pretest", "eppm_probe_c2f_window", "eppm_probe_dispatch", "eppm_probe_fast_exp", "eppm_probe_div_const", "eppm_probe_delta_table",
                 "eppm_probe_unpack_texel", "eppm_probe_pm_parity", "eppm_probe_ctx_rng_states", "eppm_test_pm_search", "eppm_probe_search_pretest", "eppm_probe_launch_log"]
 
 _variant = None

@@ -90,6 +90,8 @@ static inline int opt_sweep_spec() { return g_opt_sweep_spec.load(); }
 static inline int opt_no_split() { return g_opt_no_split.load(); }
 static inline int opt_force_split() { return g_opt_force_split.load(); }
 static inline int opt_search_pre() { return g_opt_search_pre.load(); }
+EPPM_HIDDEN extern std::atomic<int> g_opt_c2f_pre;          // "c2f_pre": -1 the library's EPPM_C2F_PRE, 0 / 1 the window refine's coherent tiles one-phase / two-phase
+static inline int opt_c2f_pre() { return g_opt_c2f_pre.load(); }
 EPPM_HIDDEN extern std::atomic<int> g_opt_alloc_fill;       // "alloc_fill": -1 off, 0..255 the byte every block is filled with before it is handed out
 static inline int opt_alloc_fill() { return g_opt_alloc_fill.load(); }
 // The one place that fills (test_hooks.cpp): a no-op while "alloc_fill" is off or e is an error.  Device blocks: hipMemset, then
@@ -101,6 +103,7 @@ static constexpr int opt_sweep_spec() { return -1; }
 static constexpr int opt_no_split() { return 0; }
 static constexpr int opt_force_split() { return 0; }
 static constexpr int opt_search_pre() { return -1; }
+static constexpr int opt_c2f_pre() { return -1; }
 static constexpr int opt_alloc_fill() { return -1; }
 #endif
 

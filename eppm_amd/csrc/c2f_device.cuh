@@ -35,6 +35,20 @@
 #ifndef EPPM_C2F_WIN_WAVES
 #define EPPM_C2F_WIN_WAVES 4
 #endif
+// k_c2f_refine_win<9>, coherent tiles of the exact library: the two-phase form -- a pre-test over the
+// EPPM_C2F_PRE_ROWS centre rows of every (candidate, pass), the best estimate in full, and only what the bound cannot reject after it.
+// 0: the one-phase loop (also the two-phase form's fallback).  The test switch "c2f_pre" overrides it per launch.
+#ifndef EPPM_C2F_PRE
+#define EPPM_C2F_PRE 1
+#endif
+#ifndef EPPM_C2F_PRE_ROWS
+#define EPPM_C2F_PRE_ROWS 5
+#endif
+#ifndef EPPM_C2F_PRE_EPS
+#define EPPM_C2F_PRE_EPS 0x1p-13f             // shrinks the lower bound: >= 4 x the float error of its two sides (tests/test_refine_pretest_cpu.py)
+#endif
+#define EPPM_C2F_PRE_DMIN 0x1p-60f            // a tile with a centre-row weight sum not above this takes the one-phase loop (its costs may be 0/0)
+#define EPPM_C2F_PRE_RHSMIN 0x1p-100f         // no rejection unless best * (D_A + U) is a normal number this far from underflow
 #ifndef EPPM_C2F_SPLIT_BELOW_WAVES
 #define EPPM_C2F_SPLIT_BELOW_WAVES 1024              // fewer than 1 wave per SIMD on 256 CUs (at 256 threads per tile)
 #endif
@@ -129,6 +143,12 @@ __device__ __forceinline__ bool c2f_tile_origin(const Planes& P, int& x0, int& y
 // of 8 lanes of one tile row and 8 of the next (MI355X LDS lane groups); with the stride = 0 mod 256 B the two
 // halves fall on disjoint banks (34-texel rows cost a 2-way conflict on about every read)
 template <int R> struct C2fSrcTile { static constexpr int TWU = kBlock + 2 * R, TW = (TWU + 15) / 16 * 16; };
+// The two-phase window refine keeps its per-pixel selection keys and its survivor list in that padding (TW - TWU texels per row, never staged,
+// never read by a sample), addressed as one byte space: PADB bytes per row, the 256 8-byte keys in rows [0, KROWS), CAP 2-byte items after them.
+template <int R> struct C2fPreList {
+    static constexpr int PADB = (C2fSrcTile<R>::TW - C2fSrcTile<R>::TWU) * 16, KROWS = PADB ? (256 * 8 + PADB - 1) / PADB : 0;
+    static constexpr int CAP = PADB ? (C2fSrcTile<R>::TWU - KROWS) * (PADB / 2) : 0;
+};
 // ---------------------------------------------------------------------------------------------------
 // The same stage restructured for CDNA4 (bit-identical results).  The reference evaluates the 36
 // (candidate, pass) patch costs of a pixel one after the other, re-fetching and re-converting the 100
@@ -417,5 +437,67 @@ EPPM_UNROLL(EPPM_C2F_UNROLL)
 #pragma unroll
     for (int n = 0; n < 3; n++) { outA[n] = cs[n] / ws[n]; outB[n] = cs[3 + n] / ws[3 + n]; }
 }
+
+#ifndef EPPM_TOL
+// ---- the two-phase form of k_c2f_refine_win ----
+// c2f_pass2_win over the sample rows [I0, I1) only and for NC row candidates (3: a candidate column, 1: one candidate), the sums left
+// undivided: cs / ws [0, NC) of pass PA, [NC, 2 NC) of pass PB.  All rows: c2f_pass2_win's sums, term for term and in its order.
+template <int R, int PA, int PB, int WW, int I0, int I1, int NC>
+__device__ __forceinline__ void c2f_rows2_win(const PatchLutT<R + 1>& L, const float4* __restrict__ s_src, int TW, int tx, int ty,
+                                              const rgbf c1, const rgbf (&c2)[NC], const float4* __restrict__ s_win, int wbase,
+                                              float (&cs)[2 * NC], float (&ws)[2 * NC])
+{
+    constexpr int S = R + 1;
+    constexpr int TA = (PA == 0) ? 0 : PA - 1, TB = (PB == 0) ? 0 : PB - 1;
+    const C2fTables<R>& T = c2f_tables<R>();
+    const rgbf c1w = c2f_weight_centre(c1);
+    rgbf c2w[2 * NC];
+#pragma unroll
+    for (int n = 0; n < NC; n++) { c2w[n] = c2f_weight_centre(c2[n]); c2w[NC + n] = c2w[n]; }
+#pragma unroll
+    for (int n = 0; n < 2 * NC; n++) { cs[n] = 0.0f; ws[n] = 0.0f; }
+#pragma unroll 1
+    for (int ii = I0; ii < I1; ii++) {
+        const int rdyA = (PA == 0) ? 2 * ii - R : T.rowdy[TA][ii];
+        const int rdyB = (PB == 0) ? 2 * ii - R : T.rowdy[TB][ii];
+EPPM_UNROLL(EPPM_C2F_UNROLL)
+        for (int jj = 0; jj < S; jj++) {
+            const C2fSample smp = c2f_sample(L, c1w, s_src[(ty + 2 * ii) * TW + tx + 2 * jj], ii * S + jj);
+            const int soffA = (rdyA + ((PA != 0) ? T.off[TA][ii * S + jj].up : 0)) * (WW * 16) + ((PA == 0) ? (2 * jj - R) * 16 : T.off[TA][ii * S + jj].dx16);
+            const int soffB = (rdyB + ((PB != 0) ? T.off[TB][ii * S + jj].up : 0)) * (WW * 16) + ((PB == 0) ? (2 * jj - R) * 16 : T.off[TB][ii * S + jj].dx16);
+            const char* wa = reinterpret_cast<const char*>(s_win) + (wbase + soffA);
+            const char* wb = reinterpret_cast<const char*>(s_win) + (wbase + soffB);
+            float4 q[2 * NC];
+#pragma unroll
+            for (int n = 0; n < NC; n++) { q[n] = *reinterpret_cast<const float4*>(wa + n * (WW * 16)); q[NC + n] = *reinterpret_cast<const float4*>(wb + n * (WW * 16)); }
+            c2f_terms<2 * NC>(L, smp, c2w, q, cs, ws);
+        }
+    }
+}
+
+// one affine pass of one candidate from the LDS window, all samples in the reference's order: its cost
+template <int R, int PASS, int WW>
+__device__ __forceinline__ float c2f_one_win(const PatchLutT<R + 1>& L, const float4* __restrict__ s_src, int TW, int tx, int ty,
+                                             const rgbf c1, const rgbf c2, const float4* __restrict__ s_win, int wbase)
+{
+    constexpr int S = R + 1;
+    constexpr int TP = (PASS == 0) ? 0 : PASS - 1;
+    const C2fTables<R>& T = c2f_tables<R>();
+    const rgbf c1w = c2f_weight_centre(c1), c2w[1] = {c2f_weight_centre(c2)};
+    float cs[1] = {0.0f}, ws[1] = {0.0f};
+#pragma unroll 1
+    for (int ii = 0; ii < S; ii++) {
+        const int rdy = (PASS == 0) ? 2 * ii - R : T.rowdy[TP][ii];
+EPPM_UNROLL(EPPM_C2F_UNROLL)
+        for (int jj = 0; jj < S; jj++) {
+            const C2fSample smp = c2f_sample(L, c1w, s_src[(ty + 2 * ii) * TW + tx + 2 * jj], ii * S + jj);
+            const int soff = (rdy + ((PASS != 0) ? T.off[TP][ii * S + jj].up : 0)) * (WW * 16) + ((PASS == 0) ? (2 * jj - R) * 16 : T.off[TP][ii * S + jj].dx16);
+            const float4 q[1] = {*reinterpret_cast<const float4*>(reinterpret_cast<const char*>(s_win) + (wbase + soff))};
+            c2f_terms<1>(L, smp, c2w, q, cs, ws);
+        }
+    }
+    return cs[0] / ws[0];
+}
+#endif
 
 }  // namespace eppm

@@ -127,7 +127,7 @@ extern "C" int eppm_create_batch(eppm_ctx** out, int h, int w, int device, const
     HIPCHK(hipSetDevice(device));
     eppm_ctx* c = new eppm_ctx();
     c->device = device; c->prm = p; c->h = h; c->w = w; c->npairs = npairs; c->n_active = 1;
-    c->opt_sweep_spec = opt_sweep_spec(); c->opt_no_split = opt_no_split(); c->opt_search_pre = opt_search_pre();
+    c->opt_sweep_spec = opt_sweep_spec(); c->opt_no_split = opt_no_split(); c->opt_search_pre = opt_search_pre(); c->opt_c2f_pre = opt_c2f_pre();
     c->nl = pyr_init_dim(c->H, c->W, h, w, p.levels, 0.5f);
     const int L = c->nl - 1;
     if (c->H[L] < 1 || c->W[L] < 1 || (c->W[L] + p.seg_len - 1) / p.seg_len > 1024 || (c->H[L] + p.seg_len - 1) / p.seg_len > 1024) {

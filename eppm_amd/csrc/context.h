@@ -17,7 +17,7 @@ struct eppm_ctx {
     int device = 0;
     hipStream_t stream = nullptr;
     bool own_stream = false;
-    int opt_sweep_spec = -1, opt_no_split = 0, opt_search_pre = -1;     // kernel-variant switches, copied from the process defaults at creation (test support)
+    int opt_sweep_spec = -1, opt_no_split = 0, opt_search_pre = -1, opt_c2f_pre = -1;     // kernel-variant switches, copied from the process defaults at creation (test support)
     eppm_params prm;
     int h = 0, w = 0, nl = 0;
     int stop_level = 0;                 // draft mode (eppm_set_stop_level): levels below it are upsampled, not refined

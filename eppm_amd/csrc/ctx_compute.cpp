@@ -127,7 +127,7 @@ static int branch_c2f(eppm_ctx* c, Branch& d, int (*keep)(eppm_ctx*, int, float*
         launch_resize_flow(d.a[l], c->H[l], c->W[l], r, c->H[l + 1], c->W[l + 1], 2.0f, 2.0f, s, bt);        // refine :1082-1083
         stage_end(c, c->ev);
         stage_begin(c, c->ev, level_stage.s[kStageRefine][d.bwd][l], d.dominant);
-        launch_c2f_refine(planes(c, l, d.swap), d.a[l], c->lut_pm, c->prm.patch_r, c->c2f_cost9[l], s, bt, c->opt_no_split != 0);   // refine :1086
+        launch_c2f_refine(planes(c, l, d.swap), d.a[l], c->lut_pm, c->prm.patch_r, c->c2f_cost9[l], s, bt, c->opt_no_split != 0, c->opt_c2f_pre);   // refine :1086
         stage_end(c, c->ev, d.dominant);
         stage_begin(c, c->ev, level_stage.s[kStageBlf][d.bwd][l]);
         blf(d.b[l], d.a[l], l);                                                                              // driver :280

@@ -231,6 +231,16 @@ __device__ __forceinline__ void load_delta_tab(DeltaTab& D, const float* __restr
     for (int t = tid; t < kDeltaSlots; t += nthreads) D.t2[t] = src[256 + t];
 }
 __device__ __forceinline__ rgbf texel_rgb(const float4 t) { return rgbf{t.x, t.y, t.z}; }
+#ifndef EPPM_TOL
+// u_k of one sample: the patch term's weight with the target half of its argument left out (the pre-tests of the two-phase search and of
+// the two-phase window refine: DESIGN.md sections 3.7, 3.8)
+__device__ __forceinline__ float rest_weight_term(const rgbf c1, const float4 q1, float gsp)
+{
+    float a2 = max_abs_diff(c1, texel_rgb(q1));
+    a2 *= a2;
+    return fast_exp(div_ad2(-a2)) * gsp;
+}
+#endif
 
 __device__ __forceinline__ float4 tex_px(const float4* img, int pitch, int w, int h, int x, int y)
 {

@@ -257,7 +257,12 @@ EPPM_DECISION int c2f_refine_split_factor(int w, int h, int R, int npairs = 1, b
 bool c2f_refine_wants_split(int w, int h, int R, int npairs = 1, bool no_split = false);      // c2f_refine_split_factor(..) != 0
 bool c2f_window_span(int R, int* span_x, int* span_y);          // test support: admissible centre spread of the LDS-window kernels
 // cost9: scratch of 36 floats per pixel for launches that c2f_refine_wants_split(), or NULL
-void launch_c2f_refine(const PlanesH& P, float* flow, const float* lut, int R, float* cost9, hipStream_t s, Batch bt = kOnePair, bool no_split = false);
+// pre: the two-phase form of the radius-9 window kernel's coherent tiles: -1 as the library was built, 0 off, 1 on;
+// stat: NULL, or eight zeroed counters that kernel adds to; probe: NULL, or 73 floats per pixel and pair for the pre-test's sums (two-phase
+// form forced; both test support)
+void launch_c2f_refine(const PlanesH& P, float* flow, const float* lut, int R, float* cost9, hipStream_t s, Batch bt = kOnePair, bool no_split = false,
+                       int pre = -1, unsigned* stat = nullptr, float* probe = nullptr);
+void c2f_pretest_knobs(int R, int* on, int* row0, int* rows, int* cap, float* eps, float* dmin, float* rhsmin);      // test support: that form's knobs
 // ---- coarse to fine: joint-bilateral smoothing (k_flow_blf.hip) ----
 void launch_flow_blf(float* out, const float* in, const uint32_t* img, int ipitch, int w, int h, int flow_pitch,
                      const float* blf_lut, hipStream_t s, Batch bt = kOnePair);

@@ -138,9 +138,12 @@ __global__ __launch_bounds__(256) EPPM_C2F_OCC void k_c2f_refine_tiled(PlanesH P
 // slower than the gather kernel).  Group 0 hands its nested minimum of passes 4 and 3 to group 1 through LDS (the source
 // tile's storage, after a barrier), which finishes __min(c1,__min(c2,.)) and the candidate loop.
 // ---------------------------------------------------------------------------------------------------
-template <int R>
+// PROBE (test support): the same kernel, which also writes the pre-test's N, D_A and U of every known pixel of a two-phase tile to `probe`
+// (73 floats per pixel, pair after pair: N[pass][candidate], D_A[pass][candidate], U), so that the tests compare the sums the kernel itself forms.
+template <int R, bool PROBE = false>
 __global__ __launch_bounds__(512) __attribute__((amdgpu_waves_per_eu(EPPM_C2F_WIN_WAVES, EPPM_C2F_WIN_WAVES)))
-void k_c2f_refine_win(PlanesH Ph, float* __restrict__ flow_, const float* __restrict__ lut, size_t pstride)
+void k_c2f_refine_win(PlanesH Ph, float* __restrict__ flow_, const float* __restrict__ lut, size_t pstride, int pre, unsigned* __restrict__ stat,
+                      float* __restrict__ probe)
 {
     using W = C2fWinShape<R>;
     constexpr int TWU = C2fSrcTile<R>::TWU, TW = C2fSrcTile<R>::TW, WW = W::WW, WH = W::WH;
@@ -149,6 +152,9 @@ void k_c2f_refine_win(PlanesH Ph, float* __restrict__ flow_, const float* __rest
     __shared__ float4 s_src[TWU * TW];
     __shared__ float4 s_win[WH * WW];
     __shared__ int s_mm[4];                                          // min ccx, max ccx, min ccy, max ccy of the tile's pixels
+#ifndef EPPM_TOL
+    __shared__ int s_pre[8];                                         // two-phase form: [0] a weight sum too small, [1 + p] survivors of pass p
+#endif
     float* __restrict__ flow = pair_ptr(flow_, pstride, blockIdx.y);
     const int ptid = threadIdx.y * kBlock + threadIdx.x;            // pixel of the tile
     const int grp = threadIdx.z;                                     // pass group
@@ -160,6 +166,9 @@ void k_c2f_refine_win(PlanesH Ph, float* __restrict__ flow_, const float* __rest
     int x0, y0, part;
     if (!c2f_tile_origin<0>(P, x0, y0, part)) return;
     if (tid == 0) { s_mm[0] = 0x7fffffff; s_mm[1] = -0x7fffffff; s_mm[2] = 0x7fffffff; s_mm[3] = -0x7fffffff; }
+#ifndef EPPM_TOL
+    if (tid < 8) s_pre[tid] = 0;
+#endif
     for (int t = tid; t < TWU * TWU; t += 512) {
         const int ry = t / TWU, rx = t % TWU;
         const int sy = iclamp(y0 + ry - R, 0, P.h - 1), sx = iclamp(x0 + rx - R, 0, P.w - 1);
@@ -187,6 +196,169 @@ void k_c2f_refine_win(PlanesH Ph, float* __restrict__ flow_, const float* __rest
         }
     }
     __syncthreads();
+#ifndef EPPM_TOL
+    // ---- the two-phase form of a coherent tile; every branch that holds a barrier is workgroup-uniform ----
+    int path = 3;                                    // statistics: 0 two-phase, 1 a weight sum too small, 2 survivor list full, 3 one-phase as before
+    if (pre && coherent && mxx >= mnx) {
+        constexpr int S = R + 1, I0 = (S - EPPM_C2F_PRE_ROWS) / 2, I1 = I0 + EPPM_C2F_PRE_ROWS;
+        // The row padding of the source tile (TW - TWU texels per row, never staged, never read by a sample) carries the per-pixel
+        // selection keys (rows [0, KROWS)) and the survivor list (the other rows): byte o of that space.
+        constexpr int PADB = C2fPreList<R>::PADB, KROWS = C2fPreList<R>::KROWS, CAP = C2fPreList<R>::CAP;
+        static_assert(PADB % 8 == 0 && PADB > 0 && KROWS < TWU, "keys and items do not straddle a row's padding");
+        auto pad = [&](int o) -> char* { return reinterpret_cast<char*>(s_src) + (o / PADB) * (TW * 16) + TWU * 16 + (o % PADB); };
+        auto key_at = [&](int p) -> unsigned long long* { return reinterpret_cast<unsigned long long*>(pad(p * 8)); };
+        auto item_at = [&](int i) -> uint16_t* { return reinterpret_cast<uint16_t*>(pad(KROWS * PADB + i * 2)); };
+        const int lane = tid & 63;
+        // 1. pre-test: N = sum_A c_k w_k and D_A = sum_A w_k of this lane's 2 passes x 9 candidates ([0, 9): pass 3 (group 0) or 1,
+        // [9, 18): pass 2 or 0), U = the pixel's rest weight
+        float N[18], D[18], U = 0.0f;
+        unsigned vmask = 0;                          // bit k: candidate k = m * 3 + n lies in the image
+        rgbf c1 = {0.0f, 0.0f, 0.0f};
+        if (known) {
+            c1 = texel_rgb(s_src[(threadIdx.y + R) * TW + threadIdx.x + R]);
+#pragma unroll 1
+            for (int ii = 0; ii < S; ii++) {
+                if (ii >= I0 && ii < I1) continue;
+                const float4* __restrict__ srow = s_src + (threadIdx.y + 2 * ii) * TW + threadIdx.x;
+#pragma unroll
+                for (int jj = 0; jj < S; jj++) U += rest_weight_term(c1, srow[2 * jj], L.gsp[ii * S + jj]);
+            }
+        }
+#pragma unroll
+        for (int m = 0; m < 3; m++) {
+            const int cx = (int)(int16_t)(ccx + m - 1);
+            float cs[6] = {0.0f, 0.0f, 0.0f, 0.0f, 0.0f, 0.0f}, ws[6] = {0.0f, 0.0f, 0.0f, 0.0f, 0.0f, 0.0f};
+            if (known && !(cx < 0 || cx >= P.w)) {
+                const int wbase = ((ccy - 1 - wy0) * WW + (cx - wx0)) * 16;
+                rgbf c2[3];
+#pragma unroll
+                for (int n = 0; n < 3; n++) {
+                    c2[n] = texel_rgb(*reinterpret_cast<const float4*>(reinterpret_cast<const char*>(s_win) + wbase + n * (WW * 16)));
+                    const int cy = (int)(int16_t)(ccy + n - 1);
+                    if (!(cy < 0 || cy >= P.h)) vmask |= 1u << (m * 3 + n);
+                }
+                if (grp == 0) c2f_rows2_win<R, 3, 2, WW, I0, I1, 3>(L, s_src, TW, threadIdx.x, threadIdx.y, c1, c2, s_win, wbase, cs, ws);
+                else c2f_rows2_win<R, 1, 0, WW, I0, I1, 3>(L, s_src, TW, threadIdx.x, threadIdx.y, c1, c2, s_win, wbase, cs, ws);
+            }
+#pragma unroll
+            for (int n = 0; n < 3; n++) { N[m * 3 + n] = cs[n]; D[m * 3 + n] = ws[n]; N[9 + m * 3 + n] = cs[3 + n]; D[9 + m * 3 + n] = ws[3 + n]; }
+        }
+        if (PROBE && known) {
+            float* __restrict__ pp = probe + ((size_t)blockIdx.y * P.h * P.w + (size_t)y * P.w + x) * 73;
+            const int qa = (grp == 0 ? 3 : 1) * 9, qb = (grp == 0 ? 2 : 0) * 9;
+#pragma unroll
+            for (int k = 0; k < 9; k++) { pp[qa + k] = N[k]; pp[36 + qa + k] = D[k]; pp[qb + k] = N[9 + k]; pp[36 + qb + k] = D[9 + k]; }
+            if (grp == 1) pp[72] = U;
+        }
+        bool small = false;
+#pragma unroll
+        for (int k = 0; k < 9; k++)
+            if ((vmask >> k) & 1) small = small || !(D[k] > EPPM_C2F_PRE_DMIN) || !(D[9 + k] > EPPM_C2F_PRE_DMIN);
+        if (small) s_pre[0] = 1;
+        // 2. group 1 names k*: the candidate with the smallest estimate N / D_A over its own two passes, first index on ties; 15: none
+        if (grp == 1) {
+            int ks = 15;
+            float e_best = 0.0f;
+#pragma unroll
+            for (int k = 0; k < 9; k++) {
+                if (!((vmask >> k) & 1)) continue;
+                const float e = c2f_min(N[k] / D[k], N[9 + k] / D[9 + k]);
+                if (ks == 15 || e < e_best) { e_best = e; ks = k; }
+            }
+            *key_at(ptid) = 0xfffffffffffffff0ull | (unsigned)ks;
+        }
+        __syncthreads();
+        path = 1;
+        if (!s_pre[0]) {
+            // k* in full, both groups: B = the minimum of its four passes' costs (no cost of this tile is NaN, so the nesting of c2f_min is the minimum)
+            const int ks = (int)(*reinterpret_cast<const uint32_t*>(key_at(ptid)) & 15u);
+            const bool live = known && ks != 15;
+            if (live) {
+                const int cx = (int)(int16_t)(ccx + ks / 3 - 1);
+                const int wbase = ((ccy - 1 + ks % 3 - wy0) * WW + (cx - wx0)) * 16;
+                const rgbf c2[1] = {texel_rgb(*reinterpret_cast<const float4*>(reinterpret_cast<const char*>(s_win) + wbase))};
+                float cs[2], ws[2];
+                if (grp == 0) c2f_rows2_win<R, 3, 2, WW, 0, S, 1>(L, s_src, TW, threadIdx.x, threadIdx.y, c1, c2, s_win, wbase, cs, ws);
+                else c2f_rows2_win<R, 1, 0, WW, 0, S, 1>(L, s_src, TW, threadIdx.x, threadIdx.y, c1, c2, s_win, wbase, cs, ws);
+                const float c = c2f_min(cs[0] / ws[0], cs[1] / ws[1]);
+                atomicMin(key_at(ptid), ((unsigned long long)__float_as_uint(c) << 4) | (unsigned)ks);
+            }
+            __syncthreads();
+            // 3. reject what the bound proves worse than B; count the survivors of this lane's two passes
+            unsigned sa = 0, sb = 0, tested = 0;
+            if (live) {
+                const float B = __uint_as_float((uint32_t)(*key_at(ptid) >> 4));
+#pragma unroll
+                for (int k = 0; k < 9; k++) {
+                    if (!((vmask >> k) & 1) || k == ks) continue;
+                    const float ra = B * (D[k] + U), rb = B * (D[9 + k] + U);
+                    if (!(N[k] * (1.0f - EPPM_C2F_PRE_EPS) >= ra && ra >= EPPM_C2F_PRE_RHSMIN)) sa |= 1u << k;
+                    if (!(N[9 + k] * (1.0f - EPPM_C2F_PRE_EPS) >= rb && rb >= EPPM_C2F_PRE_RHSMIN)) sb |= 1u << k;
+                    tested += 2;
+                }
+            }
+            const int na = __popc(sa), nb = __popc(sb);
+            int ia = na, ib = nb;                    // inclusive prefix over the wave's lanes: neighbouring lanes keep neighbouring pixels
+#pragma unroll
+            for (int d = 1; d < 64; d <<= 1) {
+                const int ta = __shfl_up(ia, d), tb = __shfl_up(ib, d);
+                if (lane >= d) { ia += ta; ib += tb; }
+            }
+            const int pa = grp == 0 ? 3 : 1, pb = grp == 0 ? 2 : 0;          // wave-uniform: a wave lies in one group
+            int wa = 0, wb = 0;
+            if (lane == 63) { wa = atomicAdd(&s_pre[1 + pa], ia); wb = atomicAdd(&s_pre[1 + pb], ib); }
+            wa = __shfl(wa, 63); wb = __shfl(wb, 63);
+            if (stat && tested) { atomicAdd(stat + 4, tested); atomicAdd(stat + 5, tested - (unsigned)(na + nb)); }
+            __syncthreads();
+            // 4. the survivors of the tile, one list per pass in segments of whole 64-item chunks, evaluated by all eight waves
+            int cnt[4], chb[5];
+            chb[0] = 0;
+#pragma unroll
+            for (int p = 0; p < 4; p++) { cnt[p] = s_pre[1 + p]; chb[p + 1] = chb[p] + ((cnt[p] + 63) >> 6); }
+            path = 2;
+            if (chb[4] * 64 <= CAP) {
+                path = 0;
+                {
+                    int at = chb[pa] * 64 + wa + ia - na;
+                    for (unsigned s = sa; s; s &= s - 1) *item_at(at++) = (uint16_t)(ptid | ((__ffs(s) - 1) << 8));
+                    at = chb[pb] * 64 + wb + ib - nb;
+                    for (unsigned s = sb; s; s &= s - 1) *item_at(at++) = (uint16_t)(ptid | ((__ffs(s) - 1) << 8));
+                }
+                __syncthreads();
+                for (int c = tid >> 6; c < chb[4]; c += 8) {
+                    const int p = __builtin_amdgcn_readfirstlane((c >= chb[1]) + (c >= chb[2]) + (c >= chb[3]));
+                    const int idx = (c - chb[p]) * 64 + lane;
+                    if (idx < cnt[p]) {
+                        const unsigned it = *item_at(chb[p] * 64 + idx);
+                        const int ip = it & 255, k = it >> 8, tx = ip & (kBlock - 1), ty = ip / kBlock;
+                        const int px = x0 + tx, py = y0 + ty;
+                        const int qcx = c2f_centre(flow[(py * P.w + px) * 2], px), qcy = c2f_centre(flow[(py * P.w + px) * 2 + 1], py);
+                        const int cx = (int)(int16_t)(qcx + k / 3 - 1);
+                        const int wbase = ((qcy - 1 + k % 3 - wy0) * WW + (cx - wx0)) * 16;
+                        const rgbf q1 = texel_rgb(s_src[(ty + R) * TW + tx + R]);
+                        const rgbf q2 = texel_rgb(*reinterpret_cast<const float4*>(reinterpret_cast<const char*>(s_win) + wbase));
+                        float c_;
+                        if (p == 3) c_ = c2f_one_win<R, 3, WW>(L, s_src, TW, tx, ty, q1, q2, s_win, wbase);
+                        else if (p == 2) c_ = c2f_one_win<R, 2, WW>(L, s_src, TW, tx, ty, q1, q2, s_win, wbase);
+                        else if (p == 1) c_ = c2f_one_win<R, 1, WW>(L, s_src, TW, tx, ty, q1, q2, s_win, wbase);
+                        else c_ = c2f_one_win<R, 0, WW>(L, s_src, TW, tx, ty, q1, q2, s_win, wbase);
+                        atomicMin(key_at(ip), ((unsigned long long)__float_as_uint(c_) << 4) | (unsigned)k);
+                    }
+                }
+                __syncthreads();
+                // 5. the smallest cost, then the smallest candidate index: the reference's strict < in candidate order
+                if (stat && tid == 0) atomicAdd(stat + 0, 1u);
+                if (grp != 1 || !inimg) return;
+                if (!known) { c2f_store_flow(flow, y * P.w + x, 0, 0); return; }
+                int k = (int)(*key_at(ptid) & 15u);
+                if (k == 15) k = 4;                  // no candidate in the image: the centre stays (kernel.cu:2026)
+                c2f_store_flow(flow, y * P.w + x, (int)(int16_t)(ccx + k / 3 - 1) - x, (int)(int16_t)(ccy + k % 3 - 1) - y);
+                return;
+            }
+        }
+    }
+    if (stat && tid == 0) atomicAdd(stat + path, 1u);
+#endif
     float res[9];                                   // group 0: __min(c3,c4) per candidate; group 1: c2 then the final cost
     float res1[9];                                  // group 1: c1 (raw)
     if (known) {
@@ -410,6 +582,19 @@ bool c2f_window_span(int R, int* span_x, int* span_y)
     return true;
 }
 
+// the knobs the two-phase window refine was built with
+void c2f_pretest_knobs(int R, int* on, int* row0, int* rows, int* cap, float* eps, float* dmin, float* rhsmin)
+{
+#ifdef EPPM_TOL
+    *on = 0;                                     // the tolerance library's kernel has no two-phase form: `pre` is ignored there
+#else
+    *on = EPPM_C2F_PRE;
+#endif
+    *row0 = (R + 1 - EPPM_C2F_PRE_ROWS) / 2; *rows = EPPM_C2F_PRE_ROWS;
+    *cap = C2fPreList<9>::CAP;                   // items of a tile's survivor list
+    *eps = EPPM_C2F_PRE_EPS; *dmin = EPPM_C2F_PRE_DMIN; *rhsmin = EPPM_C2F_PRE_RHSMIN;
+}
+
 static bool c2f_table_ok(int w, int h, int R) { return (w + R < 32764) && (h + R < 32764); }      // range of the offset-table identity (c2f_device.cuh)
 
 // no_split (a context's "c2f_no_split" option): never split, so that small images go through the LDS-window kernels too
@@ -435,7 +620,10 @@ static void with_radius(int R, F&& f)
 }
 
 // cost9: scratch of 36 floats per pixel, or NULL (never split)
-void launch_c2f_refine(const PlanesH& P, float* flow, const float* lut, int R, float* cost9, hipStream_t s, Batch bt, bool no_split)
+// pre: the two-phase form of k_c2f_refine_win<9>'s coherent tiles (-1 the library's EPPM_C2F_PRE, 0 off, 1 on); stat: NULL, or eight
+// zeroed counters of that kernel (tiles two-phase / weight sum too small / list full / one-phase, pairs tested, pairs rejected)
+void launch_c2f_refine(const PlanesH& P, float* flow, const float* lut, int R, float* cost9, hipStream_t s, Batch bt, bool no_split, int pre,
+                       unsigned* stat, float* probe)
 {
     dim3 grid((P.w + kBlock - 1) / kBlock, (P.h + kBlock - 1) / kBlock, bt.n), block(kBlock, kBlock);
     const int per_xcd = (grid.x * grid.y + 7) / 8;
@@ -458,7 +646,8 @@ void launch_c2f_refine(const PlanesH& P, float* flow, const float* lut, int R, f
     }
     const bool window = (R == 9) ? EPPM_C2F_WINDOW : EPPM_C2F_WINDOW17;
     if (!window) with_radius(R, [&](auto r) { hipLaunchKernelGGL((k_c2f_refine_tiled<r(), 0>), grid1, block, 0, s, P, flow, lut, (float*)nullptr, bt.stride); });
-    else if (R == 9) hipLaunchKernelGGL((k_c2f_refine_win<9>), grid1, dim3(kBlock, kBlock, 2), 0, s, P, flow, lut, bt.stride);
+    else if (R == 9 && probe) hipLaunchKernelGGL((k_c2f_refine_win<9, true>), grid1, dim3(kBlock, kBlock, 2), 0, s, P, flow, lut, bt.stride, 1, stat, probe);
+    else if (R == 9) hipLaunchKernelGGL((k_c2f_refine_win<9>), grid1, dim3(kBlock, kBlock, 2), 0, s, P, flow, lut, bt.stride, pre < 0 ? EPPM_C2F_PRE : pre, stat, (float*)nullptr);
     else hipLaunchKernelGGL((k_c2f_refine_win4<17>), grid1, dim3(kBlock, kBlock, 4), 0, s, P, flow, lut, bt.stride);
 }
 

@@ -442,7 +442,7 @@ extern "C" void baoCudaBLFCostFilterRefine(eppm_float2* d_flow_vec, eppm_uchar4*
     if (g_launch_status != EPPM_OK) return;
     float* cost9 = nullptr;
     if ((g_launch_status = split_scratch(ds, w, h, &cost9)) != EPPM_OK) return;
-    launch_c2f_refine(P, (float*)d_flow_vec, ds->lut_pm, g_prm.patch_r, cost9, g_stream, kOnePair, opt_no_split() != 0);
+    launch_c2f_refine(P, (float*)d_flow_vec, ds->lut_pm, g_prm.patch_r, cost9, g_stream, kOnePair, opt_no_split() != 0, opt_c2f_pre());
     g_launch_status = finish();
 }
 
@@ -460,7 +460,7 @@ extern "C" void baoCudaBLF_C2F(eppm_float2** pFlowPyr, eppm_uchar4** pImgPyr1, e
     if (g_launch_status != EPPM_OK) return;
     float* cost9 = nullptr;
     if ((g_launch_status = split_scratch(ds, arrW[l], arrH[l], &cost9)) != EPPM_OK) return;
-    launch_c2f_refine(P, (float*)pFlowPyr[l], ds->lut_pm, g_prm.patch_r, cost9, g_stream, kOnePair, opt_no_split() != 0);                         // refine :1086
+    launch_c2f_refine(P, (float*)pFlowPyr[l], ds->lut_pm, g_prm.patch_r, cost9, g_stream, kOnePair, opt_no_split() != 0, opt_c2f_pre());                         // refine :1086
     g_launch_status = finish();
 }
 
@@ -468,17 +468,24 @@ extern "C" void baoCudaBLF_C2F(eppm_float2** pFlowPyr, eppm_uchar4** pImgPyr1, e
 // include/eppm_test.h: the candidate refine of npairs pairs of one size in ONE launch, as a batch context issues it (blockIdx.y = pair).
 // Caller planes unpitched, pair after pair.  A Batch has one byte stride for the texel planes and the flow, so the flow fields are spread
 // to the texel planes' stride in scratch (slot 0) for the launch and gathered back.
-extern "C" int eppm_test_c2f_refine_batch(float* d_flow, const uint32_t* d_img1, const uint32_t* d_img2, const uint8_t* d_census1,
-        const uint8_t* d_census2, int w, int h, int npairs)
+static int c2f_refine_batch(float* d_flow, const uint32_t* d_img1, const uint32_t* d_img2, const uint8_t* d_census1,
+        const uint8_t* d_census2, int w, int h, int npairs, int pre, unsigned* stat, float* d_probe = nullptr)
 {
+#ifdef EPPM_TOL
+    if (pre == 1 || d_probe) return set_err(EPPM_ERR_ARG, "the tolerance library's window refine has no two-phase form");
+#endif
     if (!d_flow || !d_img1 || !d_img2 || !d_census1 || !d_census2 || w < 1 || h < 1 || npairs < 1)
         return set_err(EPPM_ERR_ARG, "eppm_test_c2f_refine_batch: bad argument");
     LAUNCHER_BEGIN_INT;
     const size_t n = (size_t)w * h, stride = n * 16;
-    void *a = nullptr, *b = nullptr, *f = nullptr;
+    void *a = nullptr, *b = nullptr, *f = nullptr, *st = nullptr;
     CHK(get_scratch(ds, stride * npairs, &a, 2));
     CHK(get_scratch(ds, stride * npairs, &b, 3));
-    CHK(get_scratch(ds, stride * npairs, &f, 0));
+    CHK(get_scratch(ds, stride * npairs + 32, &f, 0));          // + the window kernel's eight counters, after the flow fields
+    if (stat) {
+        st = (char*)f + stride * npairs;
+        HIPCHK(hipMemsetAsync(st, 0, 32, g_stream));
+    }
     for (int p = 0; p < npairs; p++) {
         launch_pack((char*)a + p * stride, w, d_img1 + p * n, w, d_census1 + p * n, w, w, h, g_stream);
         launch_pack((char*)b + p * stride, w, d_img2 + p * n, w, d_census2 + p * n, w, w, h, g_stream);
@@ -486,9 +493,28 @@ extern "C" int eppm_test_c2f_refine_batch(float* d_flow, const uint32_t* d_img1,
     }
     PlanesH P;
     P.pk1 = a; P.pk2 = b; P.w = w; P.h = h; P.pitch = w;
-    launch_c2f_refine(P, (float*)f, ds->lut_pm, g_prm.patch_r, nullptr, g_stream, Batch{npairs, stride}, opt_no_split() != 0);
+    if (d_probe) HIPCHK(hipMemsetAsync(d_probe, 0xff, n * npairs * 73 * 4, g_stream));          // what the kernel leaves unwritten reads as NaN
+    launch_c2f_refine(P, (float*)f, ds->lut_pm, g_prm.patch_r, nullptr, g_stream, Batch{npairs, stride}, opt_no_split() != 0, pre, (unsigned*)st, d_probe);
     for (int p = 0; p < npairs; p++) CHK(copy_d2d(d_flow + p * n * 2, (char*)f + p * stride, n * 8));
+    if (stat) { HIPCHK(hipMemcpyAsync(stat, st, 32, hipMemcpyDeviceToHost, g_stream)); HIPCHK(hipStreamSynchronize(g_stream)); }
     return finish();
+}
+extern "C" int eppm_test_c2f_refine_batch(float* d_flow, const uint32_t* d_img1, const uint32_t* d_img2, const uint8_t* d_census1,
+        const uint8_t* d_census2, int w, int h, int npairs)
+{
+    return c2f_refine_batch(d_flow, d_img1, d_img2, d_census1, d_census2, w, h, npairs, opt_c2f_pre(), nullptr);
+}
+extern "C" int eppm_test_c2f_refine_pre(float* d_flow, const uint32_t* d_img1, const uint32_t* d_img2, const uint8_t* d_census1,
+        const uint8_t* d_census2, int w, int h, int npairs, int pre, unsigned* stat)
+{
+    if (!stat || pre < -1 || pre > 1) return set_err(EPPM_ERR_ARG, "eppm_test_c2f_refine_pre: bad argument");
+    return c2f_refine_batch(d_flow, d_img1, d_img2, d_census1, d_census2, w, h, npairs, pre, stat);
+}
+extern "C" int eppm_test_c2f_refine_probe(float* d_flow, const uint32_t* d_img1, const uint32_t* d_img2, const uint8_t* d_census1,
+        const uint8_t* d_census2, int w, int h, int npairs, float* d_probe)
+{
+    if (!d_probe || g_prm.patch_r != 9) return set_err(EPPM_ERR_ARG, "eppm_test_c2f_refine_probe: bad argument (patch radius 9 only)");
+    return c2f_refine_batch(d_flow, d_img1, d_img2, d_census1, d_census2, w, h, npairs, 1, nullptr, d_probe);
 }
 #endif
 

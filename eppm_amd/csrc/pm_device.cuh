@@ -273,13 +273,7 @@ constexpr int pre_row0(int S) { return (S - EPPM_SEARCH_PRE_ROWS) / 2; }        
 // A patch cost is cs / ws = sum c_k w_k / sum w_k with c_k >= 0 and w_k = gsp_k fast_exp(-(a2_k + t_k) / s): a2_k is the SOURCE half of the
 // weight's argument (the pixel against its own sample), t_k >= 0 the target half, so w_k <= u_k := gsp_k fast_exp(-a2_k / s) whatever the
 // guess.  With A = the EPPM_SEARCH_PRE_ROWS centre rows of the patch:  cs / ws >= sum_A c_k w_k / (sum_A w_k + sum_{not A} u_k).
-// u_k of one sample: patch_terms' weight with the target half of its argument left out
-__device__ __forceinline__ float rest_weight_term(const rgbf c1, const float4 q1, float gsp)
-{
-    float a2 = max_abs_diff(c1, texel_rgb(q1));
-    a2 *= a2;
-    return fast_exp(div_ad2(-a2)) * gsp;
-}
+// u_k of one sample: rest_weight_term (eppm_device.cuh)
 // sum_A c_k w_k and sum_A w_k of a guess: rows A of search_patch_dist's parity-plane form (PK = 2) -- the same loads, the same terms, row major
 template <int RT, class LUT>
 __device__ __forceinline__ void search_patch_centre_rows(const Planes& P, const LUT& L, const float4* __restrict__ s_src, int TW, int tx, int ty,

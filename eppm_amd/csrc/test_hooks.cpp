@@ -12,6 +12,7 @@ std::atomic<int> g_opt_sweep_spec{-1};
 std::atomic<int> g_opt_no_split{0};
 std::atomic<int> g_opt_force_split{0};
 std::atomic<int> g_opt_search_pre{-1};
+std::atomic<int> g_opt_c2f_pre{-1};
 std::atomic<int> g_opt_alloc_fill{-1};
 
 // "launch_log": the record behind eppm::g_launch_note; entries of six ints, capped so that a forgotten log cannot grow without bound
@@ -51,6 +52,11 @@ extern "C" int eppm_test_set_option(const char* name, int value)
     if (!strcmp(name, "sweep_spec")) { g_opt_sweep_spec.store(value); return EPPM_OK; }
     if (!strcmp(name, "rand_table")) { g_opt_rand_table.store(value); return EPPM_OK; }
     if (!strcmp(name, "search_pre_from")) { g_opt_search_pre.store(value); return EPPM_OK; }
+    if (!strcmp(name, "c2f_pre")) {
+        if (value < -1 || value > 1) return set_err(EPPM_ERR_ARG, "eppm_test_set_option: c2f_pre %d is none of -1, 0, 1", value);
+        g_opt_c2f_pre.store(value);
+        return EPPM_OK;
+    }
     if (!strcmp(name, "launch_log")) {          // 1: an empty log from now on; 0: none (the entries are dropped)
         g_launch_note.store(nullptr);
         { std::lock_guard<std::mutex> lk(g_log.mu); g_log.v.clear(); g_log.on = value != 0; }
@@ -134,6 +140,13 @@ extern "C" int eppm_probe_search_pretest(int iteration, int w, int h, int patch_
     out[0] = pm_search_pretest(iteration, w, h, patch_r, problems, npairs) ? 1 : 0;
     pm_search_pretest_knobs(patch_r, &out[1], &out[2], &out[3], eps);
     out[4] = pm_search_pretest_form(w, h, patch_r, problems, npairs) ? 1 : 0;
+    return EPPM_OK;
+}
+// the knobs of the two-phase window refine (eppm_internal.h: c2f_pretest_knobs)
+extern "C" int eppm_probe_c2f_pretest(int patch_r, int* out, float* fl)
+{
+    if (!out || !fl || patch_r != 9) return set_err(EPPM_ERR_ARG, "eppm_probe_c2f_pretest: bad argument (the two-phase form exists at patch_r 9)");
+    c2f_pretest_knobs(patch_r, &out[0], &out[1], &out[2], &out[3], &fl[0], &fl[1], &fl[2]);
     return EPPM_OK;
 }
 extern "C" int eppm_probe_fast_exp(const float* x, float* y, int n) { return probe(x, y, n, 0); }

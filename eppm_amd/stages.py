@@ -326,6 +326,42 @@ def c2f_refine_batch(flows, planes):
     return [out[k * h:(k + 1) * h] for k in range(n)]
 
 
+def c2f_refine_pre(flows, planes, pre):
+    """eppm_test_c2f_refine_pre (test library): c2f_refine_batch with the window kernel's coherent tiles one-phase (pre = 0) or two-phase
+    (pre = 1).  Returns (refined flow per pair, the kernel's counters: tiles two-phase, tiles with a weight sum too small, tiles with a full
+    survivor list, other tiles, pairs tested, pairs rejected)."""
+    n = len(flows)
+    h, w = flows[0].shape
+    f = Dev(np.concatenate([np.ascontiguousarray(x, float2) for x in flows]))
+    i1, i2, c1, c2 = (Dev(np.concatenate([np.ascontiguousarray(p[k]) for p in planes])) for k in range(4))
+    stat = (C.c_uint * 8)()
+    check(lib().eppm_test_c2f_refine_pre(f.ptr, i1.ptr, i2.ptr, c1.ptr, c2.ptr, w, h, n, int(pre), stat), "eppm_test_c2f_refine_pre")
+    out = f.get()
+    return [out[k * h:(k + 1) * h] for k in range(n)], tuple(stat[:6])
+
+
+def c2f_refine_probe(flows, planes):
+    """eppm_test_c2f_refine_probe (test library): the two-phase launch by the kernel's probing instantiation.  Returns (refined flow per pair,
+    N, D: (pairs, h, w, 4, 9) float32 -- [pass][candidate] --, U: (pairs, h, w)); NaN where the kernel formed nothing."""
+    n = len(flows)
+    h, w = flows[0].shape
+    f = Dev(np.concatenate([np.ascontiguousarray(x, float2) for x in flows]))
+    i1, i2, c1, c2 = (Dev(np.concatenate([np.ascontiguousarray(p[k]) for p in planes])) for k in range(4))
+    pr = Dev(shape=(n * h, w * 73), dtype=np.float32)
+    check(lib().eppm_test_c2f_refine_probe(f.ptr, i1.ptr, i2.ptr, c1.ptr, c2.ptr, w, h, n, pr.ptr), "eppm_test_c2f_refine_probe")
+    out, p = f.get(), pr.get().reshape(n, h, w, 73)
+    return [out[k * h:(k + 1) * h] for k in range(n)], p[..., :36].reshape(n, h, w, 4, 9), p[..., 36:72].reshape(n, h, w, 4, 9), p[..., 72]
+
+
+def probe_c2f_pretest(patch_r=9):
+    """eppm_probe_c2f_pretest (test library, no GPU needed): (on by default?, first centre row, centre rows, items of a tile's survivor
+    list, eps, smallest admissible weight sum, smallest right-hand side that may reject)"""
+    out = (C.c_int * 4)()
+    fl = (C.c_float * 3)()
+    check(lib().eppm_probe_c2f_pretest(patch_r, out, fl), "eppm_probe_c2f_pretest")
+    return bool(out[0]), out[1], out[2], out[3], fl[0], fl[1], fl[2]
+
+
 def blf_c2f(flow_coarse, P_fine, coarse_dims):
     """baoCudaBLF_C2F from level l+1 (flow_coarse) to level l (P_fine): upsample x2, x2.0, candidate refine."""
     ch, cw = coarse_dims

@@ -10,6 +10,8 @@
  * libeppm_hip_tol_test.so is the same construction on the tolerance library's objects (-DEPPM_TOL): the stage parity tests of the
  * tolerance kernels load it in child processes.  Everything below works there -- eppm_probe_c2f_window reports that build's own window
  * (50 rows) --, except that eppm_probe_delta_table(which = 0) returns EPPM_ERR_ARG: the tolerance patch term has no such table.
+ * Its window refine has no two-phase form either: eppm_probe_c2f_pretest reports it off, eppm_test_c2f_refine_pre with pre = 1 and
+ * eppm_test_c2f_refine_probe return EPPM_ERR_ARG.
  */
 #ifndef EPPM_TEST_H_
 #define EPPM_TEST_H_
@@ -36,6 +38,8 @@ extern "C" {
  * "search_pre_from": -1 (default) a context's random searches take the two-phase form (pre-test on the centre rows, then the survivors
  * in full) from the iteration the library itself chooses (eppm_probe_search_pretest), k >= 0: from iteration k on -- beyond the last
  * iteration: never --, wherever the launch has a two-phase form at all (patch radius 9, quarter-block workgroups).
+ * "c2f_pre": -1 (default) the radius-9 window refine treats its coherent tiles as the library was built (eppm_probe_c2f_pretest), 0 in the
+ * one-phase form, 1 in the two-phase form (pre-test on the centre rows, the best estimate in full, then the survivors).
  * "launch_log": 1 starts an empty record of what the launchers decide from now on (eppm_probe_launch_log), 0 (default) drops it.
  * "alloc_fill" is of another kind: it selects no kernel, it poisons memory.  -1 (default) off; 0..255: every block the library allocates
  * from then on -- a context's slab and its lazily made blocks (backward flow, interpolation, motion blur, streaming), the pinned staging
@@ -53,6 +57,22 @@ int  eppm_probe_c2f_window(int patch_r, int* span_x, int* span_y);
  * bytes.  Patch radius from eppm_set_launcher_params; never split ("c2f_no_split" or not: this entry brings no cost scratch). */
 int  eppm_test_c2f_refine_batch(float* d_flow, const uint32_t* d_img1, const uint32_t* d_img2, const uint8_t* d_census1,
                                 const uint8_t* d_census2, int w, int h, int npairs);
+/* The same launch with the form of the window kernel's coherent tiles chosen here (pre = 0 one-phase, 1 two-phase, -1 as built) and with
+ * that kernel's counters, summed over the launch, in stat[0..7] (host memory): tiles in the two-phase form, tiles sent to the one-phase loop
+ * because a centre-row weight sum was too small, because the survivor list was full, tiles one-phase for any other reason (incoherent, no
+ * known pixel, pre = 0), (candidate, pass) pairs tested, pairs rejected; the rest 0. */
+int  eppm_test_c2f_refine_pre(float* d_flow, const uint32_t* d_img1, const uint32_t* d_img2, const uint8_t* d_census1,
+                              const uint8_t* d_census2, int w, int h, int npairs, int pre, unsigned* stat);
+/* The same launch in the two-phase form by the kernel's probing instantiation (the same code, which also stores what its pre-test formed):
+ * d_probe, npairs x h x w x 73 floats of device memory, receives per pixel N[pass][candidate] (36), D_A[pass][candidate] (36) and U --
+ * pass 0 the plain grid, candidate = 3 * x offset + y offset; NaN (all bits set) where the kernel formed nothing: unknown pixels, tiles that
+ * are incoherent; 0 for candidate columns outside the image.  Patch radius 9, exact library. */
+int  eppm_test_c2f_refine_probe(float* d_flow, const uint32_t* d_img1, const uint32_t* d_img2, const uint8_t* d_census1,
+                                const uint8_t* d_census2, int w, int h, int npairs, float* d_probe);
+/* The knobs the two-phase window refine was built with (pure host code): out[0] = on by default (0 in the tolerance library, whose kernel has no such form), out[1] the first and out[2] the number of
+ * the patch rows its pre-test evaluates, out[3] the items a tile's survivor list holds; fl[0] = eps (the lower bound is shrunk by 1 - eps),
+ * fl[1] = the weight sum at or below which a tile takes the one-phase loop, fl[2] = the smallest right-hand side that may reject. */
+int  eppm_probe_c2f_pretest(int patch_r, int* out, float* fl);
 /* ONE random-search launch over npairs x ndir problems of one size, as a context issues it: the entry builds the census and texel planes,
  * the column-parity planes and the launch's numbers drawn ahead from r's current states (which it advances by one launch, as
  * eppm_pm_random_search does).  Device planes unpitched: images npairs x h x w RGBA words; d_nnf (short2) and d_cost, searched in place,
