@@ -11,5 +11,6 @@ when the library is missing.
 """
 from .build import build, lib_path  # noqa: F401
 from ._lib import EppmError, lib, select_library  # noqa: F401
-from .api import EPPM, EPPMBatch, Params, MBlurParams, motion_blur_sequence, TrackParams, Tracker, TemporalFilter, denoise_sequence, denoise_sequences, Stabilizer, stabilize_sequence, stabilize_sequences, CutDetector, detect_cuts, CMapParams, CorrespondenceMap, propagate_layer, propagate_layers, ObjectsParams, ObjectDetector, detect_objects, detect_objects_sequences, PlateParams, BackgroundPlate, background_plate, background_plates, remove_objects_sequence, DefectFilter, remove_defects_sequence, remove_defects_sequences, host_register, host_unregister, pinned_empty, flow_sequence, flow_sequences, track_sequence  # noqa: F401
+from .api import EPPM, EPPMBatch, Params, MBlurParams, TrackParams, Tracker, TemporalFilter, Stabilizer, CutDetector, CMapParams, CorrespondenceMap, ObjectsParams, ObjectDetector, PlateParams, BackgroundPlate, DefectFilter, host_register, host_unregister, pinned_empty  # noqa: F401
+from .sequences import motion_blur_sequence, denoise_sequence, denoise_sequences, stabilize_sequence, stabilize_sequences, detect_cuts, propagate_layer, propagate_layers, detect_objects, detect_objects_sequences, background_plate, background_plates, remove_objects_sequence, remove_defects_sequence, remove_defects_sequences, flow_sequence, flow_sequences, track_sequence  # noqa: F401
 from . import io, stages  # noqa: F401

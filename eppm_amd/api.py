@@ -3,7 +3,7 @@ import ctypes as C
 
 import numpy as np
 
-from .io import cmap_seed, object_record
+from .io import object_record
 from ._lib import CDefectParams, CDefectStats, CObject, CObjectsCounts, CObjectsParams, CPlateParams, CCMapParams, CCutParams, CCutStats, CGMotionModel, CMBlurParams, CParams, CStabParams, CTFilterParams, CTrackCounts, CTrackParams, EppmError, check, lib
 
 uchar4 = np.dtype([("x", "u1"), ("y", "u1"), ("z", "u1"), ("w", "u1")])
@@ -91,12 +91,12 @@ def TrackParams(params=None, **kw):
 
 
 class _Handle:
-    """An object that owns one C handle: the attribute named by _handle, destroyed by eppm_<_prefix>_destroy."""
+    """An object that owns one C handle: the attribute named by _handle, destroyed by eppm_<_prefix>_destroy (no prefix: eppm_destroy)."""
     _prefix, _handle = None, "_f"
 
     def close(self):
         if getattr(self, self._handle, None):
-            getattr(lib(), f"eppm_{self._prefix}_destroy")(getattr(self, self._handle))
+            getattr(lib(), f"eppm_{self._prefix}_destroy" if self._prefix else "eppm_destroy")(getattr(self, self._handle))
             setattr(self, self._handle, C.c_void_p())
 
     def __del__(self):
@@ -690,912 +690,62 @@ def _level(level):
     return int(level)
 
 
-def _auto_cut_step(e, det):
-    """auto_cut: one detector step on the context's last bidirectional call; every detected slot's next compute becomes a cold run
-    (temporal_reset), so the pair across the cut leaves no prior.  Returns the verdicts of the active pairs."""
-    det.step()
-    cuts = det.cuts()
-    for slot, c in enumerate(cuts):
-        if c:
-            if isinstance(e, EPPMBatch):
-                e.temporal_reset(slot)
-            else:
-                e.temporal_reset()
-    return cuts
+class _Context(_Handle):
+    """What EPPM and EPPMBatch share word for word: the calls of the ABI that take a context of either kind."""
+    _handle = "_ctx"
+
+    def _need(self):
+        """a context exists (EPPM: init has been called; a batch has one from its construction)"""
+
+    def set_stop_level(self, level):
+        """Draft mode (eppm_set_stop_level, DESIGN.md section 14): the pyramid levels below `level` are upsampled edge-aware from the level
+        above (one launch each) instead of being refined and smoothed; 0 (default): the full path.  Takes effect at the next compute; a
+        batch: for every slot."""
+        level = _level(level)
+        self._need()
+        check(lib().eppm_set_stop_level(self._ctx, level), "eppm_set_stop_level")
+
+    def stop_level(self):
+        self._need()
+        return int(lib().eppm_stop_level(self._ctx))
+
+    def set_occlusion_params(self, alpha=0.01, beta=0.5):
+        """alpha, beta of the occlusion masks' forward-backward criterion (eppm_set_occlusion_params)."""
+        self._need()
+        check(lib().eppm_set_occlusion_params(self._ctx, C.c_float(alpha), C.c_float(beta)), "eppm_set_occlusion_params")
+        self._occ_params = (float(alpha), float(beta))
+
+    def synchronize(self):
+        self._need()
+        check(lib().eppm_synchronize(self._ctx), "eppm_synchronize")
+
+    def level_dims(self):
+        self._need()
+        out = []
+        for l in range(lib().eppm_num_levels(self._ctx)):
+            h, w = C.c_int(), C.c_int()
+            check(lib().eppm_level_dims(self._ctx, l, C.byref(h), C.byref(w)), "eppm_level_dims")
+            out.append((h.value, w.value))
+        return out
+
+    def enable_stage_timing(self, on=True):
+        self._need()
+        check(lib().eppm_enable_stage_timing(self._ctx, int(on)), "eppm_enable_stage_timing")
+
+    def stage_times(self, clear=True):
+        """[(stage name, ms)] for every set_data / compute_flow since the last clear (timing enabled)."""
+        self._need()
+        cap = 1 << 16
+        names = (C.c_char_p * cap)()
+        ms = (C.c_float * cap)()
+        n = lib().eppm_stage_times(self._ctx, names, ms, cap)
+        out = [(names[i].decode(), float(ms[i])) for i in range(n)]
+        if clear:
+            check(lib().eppm_clear_stage_times(self._ctx), "eppm_clear_stage_times")
+        return out
 
 
-def detect_cuts(frames, params=None, stop_level=0, **cut_params):
-    """Scene cuts of a clip ((h, w, 3) uint8 frames): one streaming context, one bidirectional call on the device and one CutDetector step
-    per consecutive pair.  Returns (cuts, stats): one bool and one record (CutDetector.stats) per pair; cuts[k] true: frame k + 1 starts
-    another shot.  After a detected cut the next pair is a cold run.  cut_params: CutDetector's lost_permille and residual_max."""
-    stop_level = _level(stop_level)
-    frames = [np.ascontiguousarray(f, np.uint8) for f in frames]
-    if len(frames) < 2:
-        raise EppmError("detect_cuts: at least two frames")
-    h, w, _ = frames[0].shape
-    e = EPPM(params=params)
-    det = None
-    cuts, stats = [], []
-    try:
-        e.init(h, w)
-        e.set_temporal(True)
-        e.set_stop_level(stop_level)
-        det = CutDetector(e, **cut_params)
-        for k in range(len(frames) - 1):
-            if k == 0:
-                e.set_data(frames[0], frames[1])
-            else:
-                e.push_frame(frames[k + 1])
-            e.compute_flow_bidirectional_device()
-            cuts.append(_auto_cut_step(e, det)[0])
-            stats.append(det.stats(0))
-    finally:
-        if det is not None:
-            det.close()
-        e.close()
-    return cuts, stats
-
-
-def flow_sequence(frames, params=None, temporal=True, bidirectional=False, stop_level=0, auto_cut=False, **cut_params):
-    """The flows of the consecutive pairs of a clip ((h, w, 3) uint8 frames) through ONE context: the first pair by set_data, every later
-    frame by push_frame (only the new frame is uploaded and prepared), with temporal mode (each pair's PatchMatch starts from the previous
-    pair's result moved along its motion) unless temporal=False.  Returns a list of (u, v), or of (u, v, bu, bv, occ1, occ2) with
-    bidirectional=True.  Memory does not grow with the clip.  stop_level: draft mode (EPPM.set_stop_level).  auto_cut=True: every pair is
-    computed bidirectionally (its forward flow is compute_flow's) and a CutDetector (cut_params: its lost_permille / residual_max) decides
-    whether it crosses a scene cut; the pair after a cut is a cold run.  Returns (flows, cuts) then: one bool per pair, and the flow of a
-    cut pair is of no use."""
-    stop_level = _level(stop_level)
-    frames = [np.ascontiguousarray(f, np.uint8) for f in frames]
-    if len(frames) < 2:
-        raise EppmError("flow_sequence: at least two frames")
-    h, w, _ = frames[0].shape
-    e = EPPM(params=params)
-    det = None
-    out, cuts = [], []
-    try:
-        e.init(h, w)
-        e.set_temporal(temporal)
-        e.set_stop_level(stop_level)
-        if auto_cut:
-            det = CutDetector(e, **cut_params)
-        for k in range(len(frames) - 1):
-            if k == 0:
-                e.set_data(frames[0], frames[1])
-            else:
-                e.push_frame(frames[k + 1])
-            if auto_cut:
-                r = e.compute_flow_bidirectional()
-                out.append(r if bidirectional else r[:2])
-                cuts.append(_auto_cut_step(e, det)[0])
-            else:
-                out.append(e.compute_flow_bidirectional() if bidirectional else e.compute_flow())
-    finally:
-        if det is not None:
-            det.close()
-        e.close()
-    return (out, cuts) if auto_cut else out
-
-
-def motion_blur_sequence(frames, params=None, shutter=0.5, max_radius=16, taps=8, temporal=True, stop_level=0):
-    """A clip ((h, w, 3) uint8 frames) with a synthetic shutter (EPPM.motion_blur): one streaming context --
-    set_data, then push_frame --, a forward-only compute per pair and its image 1 blurred along the forward flow; the last pair is computed
-    bidirectionally and gives the clip's last frame too, blurred along the backward flow.  Returns len(frames) frames.  Memory does not grow
-    with the clip.  params: the flow's eppm Params; temporal / stop_level: the flow's temporal and draft modes."""
-    stop_level = _level(stop_level)
-    frames = [np.ascontiguousarray(f, np.uint8) for f in frames]
-    if len(frames) < 2:
-        raise EppmError("motion_blur_sequence: at least two frames")
-    h, w, _ = frames[0].shape
-    blur = dict(shutter=shutter, max_radius=max_radius, taps=taps)
-    e = EPPM(params=params)
-    out = []
-    try:
-        e.init(h, w)
-        e.set_temporal(temporal)
-        e.set_stop_level(stop_level)
-        for k in range(len(frames) - 1):
-            if k == 0:
-                e.set_data(frames[0], frames[1])
-            else:
-                e.push_frame(frames[k + 1])
-            if k < len(frames) - 2:
-                e.compute_flow()
-                out.append(e.motion_blur(frame=0, **blur))
-            else:
-                e.compute_flow_bidirectional_device()
-                out.append(e.motion_blur(frame=0, **blur))
-                out.append(e.motion_blur(frame=1, **blur))
-    finally:
-        e.close()
-    return out
-
-
-def _sequence_plan(lengths, slots):
-    """The schedule of flow_sequences, a pure function: clips of the given lengths (frames, >= 2 each) through min(slots, len(lengths))
-    slots.  Yields one list per step with one (clip, frame, new_clip, keep) per slot: frame `frame` of clip `clip` becomes the slot's image
-    2 at that step.  Step 0 is the set_data step (image 1 is the clip's frame 0, frame = 1); every later step is a push.  keep: the pair
-    the slot then holds is (frame - 1, frame) of `clip` and its flow is wanted.  A slot whose clip has ended takes the next clip of the
-    queue (frame 0 with new_clip set; the pair across the cut is not kept); a slot with nothing left is fed its last frame again."""
-    lengths = [int(n) for n in lengths]
-    if not lengths or min(lengths) < 2:
-        raise EppmError("flow_sequences: every clip needs at least two frames")
-    n = min(int(slots), len(lengths))
-    if n < 1:
-        raise EppmError("flow_sequences: at least one slot")
-    cur = [[k, 1] for k in range(n)]            # per slot: its clip and the frame that is its image 2
-    queue = list(range(n, len(lengths)))
-    yield [(k, 1, False, True) for k in range(n)]
-    while queue or any(f + 1 < lengths[c] for c, f in cur):
-        step = []
-        for slot in cur:
-            c, f = slot
-            if f + 1 < lengths[c]:
-                slot[1] = f + 1
-                step.append((c, f + 1, False, True))
-            elif queue:
-                slot[0], slot[1] = queue.pop(0), 0
-                step.append((slot[0], 0, True, False))
-            else:
-                step.append((c, f, False, False))
-        yield step
-
-
-def flow_sequences(clips, slots=8, params=None, temporal=True, bidirectional=False, stop_level=0, auto_cut=False, **cut_params):
-    """flow_sequence for many clips at once: any number of clips of one frame size and of any lengths (two frames at least) through ONE
-    batch context of min(slots, len(clips)) slots, every slot advanced by one frame per step (push_frames; temporal mode per slot unless
-    temporal=False).  A slot whose clip ends takes the next clip in the queue.  Returns one list of flows per clip, in the order given, each
-    what flow_sequence(clip) returns.  stop_level: draft mode (EPPMBatch.set_stop_level).  auto_cut=True: flow_sequence's, per slot; returns
-    (flows, cuts), one list per clip each."""
-    stop_level = _level(stop_level)
-    clips = [[np.ascontiguousarray(f, np.uint8) for f in clip] for clip in clips]
-    plan = _sequence_plan([len(c) for c in clips], slots)
-    h, w, _ = clips[0][0].shape
-    out = [[] for _ in clips]
-    cuts = [[] for _ in clips]
-    e = det = None
-    try:
-        for t, step in enumerate(plan):
-            if t == 0:
-                e = EPPMBatch(h, w, len(step), params=params)
-                e.set_temporal(temporal)
-                e.set_stop_level(stop_level)
-                if auto_cut:
-                    det = CutDetector(e, **cut_params)
-                e.set_data([(clips[c][0], clips[c][1]) for c, _, _, _ in step])
-            else:
-                e.push_frames([clips[c][f] for c, f, _, _ in step], [cut for _, _, cut, _ in step])
-            if auto_cut:
-                res = e.compute_flow_bidirectional()
-                found = _auto_cut_step(e, det)
-                if not bidirectional:
-                    res = [r[:2] for r in res]
-            else:
-                res = e.compute_flow_bidirectional() if bidirectional else e.compute_flow()
-            for slot, ((c, _, _, keep), r) in enumerate(zip(step, res)):
-                if keep:
-                    out[c].append(r)
-                    if auto_cut:
-                        cuts[c].append(found[slot])
-    finally:
-        if det is not None:
-            det.close()
-        if e is not None:
-            e.close()
-    return (out, cuts) if auto_cut else out
-
-
-def denoise_sequence(frames, params=None, thresh=40.0, n_max=8, temporal=True, stop_level=0, auto_cut=False, **cut_params):
-    """A clip ((h, w, 3) uint8 frames) denoised by the motion-compensated temporal filter (TemporalFilter): one
-    streaming context -- set_data, then push_frame --, one bidirectional call on the device and one filter step per pair.  Returns
-    len(frames) frames; the first is the input itself.  Memory does not grow with the clip.  params: the flow's eppm Params; temporal /
-    stop_level: the flow's temporal and draft modes.  auto_cut=True: a CutDetector (cut_params: its lost_permille / residual_max) looks at
-    every pair before the filter does; a frame that starts another shot restarts the filter and the flow's temporal prior, so the result
-    is what denoise_sequence returns for every shot on its own (one host read of the verdict per step)."""
-    stop_level = _level(stop_level)
-    frames = [np.ascontiguousarray(f, np.uint8) for f in frames]
-    if len(frames) < 2:
-        raise EppmError("denoise_sequence: at least two frames")
-    h, w, _ = frames[0].shape
-    e = EPPM(params=params)
-    flt = det = None
-    out = [frames[0].copy()]
-    try:
-        e.init(h, w)
-        e.set_temporal(temporal)
-        e.set_stop_level(stop_level)
-        flt = TemporalFilter(e, thresh, n_max)
-        if auto_cut:
-            det = CutDetector(e, **cut_params)
-        for k in range(len(frames) - 1):
-            if k == 0:
-                e.set_data(frames[0], frames[1])
-            else:
-                e.push_frame(frames[k + 1])
-            e.compute_flow_bidirectional_device()
-            flt.step(_auto_cut_step(e, det) if auto_cut else None)
-            out.append(flt.frame(0))
-    finally:
-        if det is not None:
-            det.close()
-        if flt is not None:
-            flt.close()
-        e.close()
-    return out
-
-
-def denoise_sequences(clips, slots=8, params=None, thresh=40.0, n_max=8, temporal=True, stop_level=0, auto_cut=False, **cut_params):
-    """denoise_sequence for many clips at once: clips of one frame size and of any lengths (two frames at least) through ONE batch context
-    of min(slots, len(clips)) slots and one TemporalFilter, on flow_sequences' schedule.  A slot that takes the next clip of the queue
-    passes `cut` for that step: its output is that clip's frame 0.  Returns one list of frames per clip, each what denoise_sequence(clip)
-    returns.  auto_cut=True: denoise_sequence's, per slot; the detector's verdicts are ORed into the schedule's cut flags."""
-    stop_level = _level(stop_level)
-    clips = [[np.ascontiguousarray(f, np.uint8) for f in clip] for clip in clips]
-    plan = _sequence_plan([len(c) for c in clips], slots)
-    h, w, _ = clips[0][0].shape
-    out = [[c[0].copy()] for c in clips]
-    e = flt = det = None
-    try:
-        for t, step in enumerate(plan):
-            if t == 0:
-                e = EPPMBatch(h, w, len(step), params=params)
-                e.set_temporal(temporal)
-                e.set_stop_level(stop_level)
-                flt = TemporalFilter(e, thresh, n_max)
-                if auto_cut:
-                    det = CutDetector(e, **cut_params)
-                e.set_data([(clips[c][0], clips[c][1]) for c, _, _, _ in step])
-            else:
-                e.push_frames([clips[c][f] for c, f, _, _ in step], [cut for _, _, cut, _ in step])
-            e.compute_flow_bidirectional_device()
-            flags = [cut for _, _, cut, _ in step]
-            if auto_cut:
-                flags = [a or b for a, b in zip(flags, _auto_cut_step(e, det))]
-            flt.step(flags)
-            for slot, (c, _, _, keep) in enumerate(step):
-                if keep:
-                    out[c].append(flt.frame(slot))
-    finally:
-        if det is not None:
-            det.close()
-        if flt is not None:
-            flt.close()
-        if e is not None:
-            e.close()
-    return out
-
-
-def _defect_split(kw):
-    """the keyword arguments of remove_defects_sequence(s): DefectFilter's go to the filter, CutDetector's to the detector"""
-    df = {k: kw.pop(k) for k in ("detect", "agree", "radius", "grow") if k in kw}
-    cut = {k: kw.pop(k) for k in ("lost_permille", "residual_max") if k in kw}
-    if kw:
-        raise TypeError(f"unknown parameter {sorted(kw)[0]}")
-    return df, cut
-
-
-def remove_defects_sequence(frames, auto_cut=False, stop_level=None, masks=False, params=None, temporal=True, **kw):
-    """A clip ((h, w, 3) uint8 frames) with its single-frame defects concealed (DefectFilter): one streaming context
-    -- set_data, then push_frame --, one bidirectional call on the device and one filter step per pair; the step of pair (k, k + 1)
-    gives frame k.  Returns len(frames) frames: the first, the last and (auto_cut=True: a CutDetector looks at every pair first) the
-    frames next to a cut are the input itself.  masks=True: (frames, masks), one (h, w) uint8 mask per frame (0 untouched, 1 hit, 2
-    grown).  kw: DefectFilter's detect / agree / radius / grow and CutDetector's lost_permille / residual_max.  params: the flow's eppm
-    Params; temporal / stop_level: the flow's temporal and draft modes.  Memory does not grow with the clip."""
-    df, cut_params = _defect_split(kw)
-    stop_level = _level(0 if stop_level is None else stop_level)
-    frames = [np.ascontiguousarray(f, np.uint8) for f in frames]
-    if len(frames) < 2:
-        raise EppmError("remove_defects_sequence: at least two frames")
-    h, w, _ = frames[0].shape
-    e = EPPM(params=params)
-    flt = det = None
-    out, ms = [], []
-    try:
-        e.init(h, w)
-        e.set_temporal(temporal)
-        e.set_stop_level(stop_level)
-        flt = DefectFilter(e, **df)
-        if auto_cut:
-            det = CutDetector(e, **cut_params)
-        for k in range(len(frames) - 1):
-            if k == 0:
-                e.set_data(frames[0], frames[1])
-            else:
-                e.push_frame(frames[k + 1])
-            e.compute_flow_bidirectional_device()
-            flt.step(_auto_cut_step(e, det) if auto_cut else None)
-            out.append(flt.frame(0))
-            if masks:
-                ms.append(flt.mask(0))
-    finally:
-        if det is not None:
-            det.close()
-        if flt is not None:
-            flt.close()
-        e.close()
-    out.append(frames[-1].copy())
-    ms.append(np.zeros((h, w), np.uint8))
-    return (out, ms) if masks else out
-
-
-def remove_defects_sequences(clips, slots=8, auto_cut=False, stop_level=None, masks=False, params=None, temporal=True, **kw):
-    """remove_defects_sequence for many clips at once: clips of one frame size and of any lengths (two frames at least) through ONE batch
-    context of min(slots, len(clips)) slots and one DefectFilter, on flow_sequences' schedule.  A slot that takes the next clip of the queue
-    passes `cut` for that step.  Returns one list of frames per clip (masks=True: (frames, masks)), each what remove_defects_sequence(clip)
-    returns.  auto_cut=True: per slot; the detector's verdicts are ORed into the schedule's cut flags."""
-    df, cut_params = _defect_split(kw)
-    stop_level = _level(0 if stop_level is None else stop_level)
-    clips = [[np.ascontiguousarray(f, np.uint8) for f in clip] for clip in clips]
-    plan = _sequence_plan([len(c) for c in clips], slots)
-    h, w, _ = clips[0][0].shape
-    out = [[] for _ in clips]
-    ms = [[] for _ in clips]
-    e = flt = det = None
-    try:
-        for t, step in enumerate(plan):
-            if t == 0:
-                e = EPPMBatch(h, w, len(step), params=params)
-                e.set_temporal(temporal)
-                e.set_stop_level(stop_level)
-                flt = DefectFilter(e, **df)
-                if auto_cut:
-                    det = CutDetector(e, **cut_params)
-                e.set_data([(clips[c][0], clips[c][1]) for c, _, _, _ in step])
-            else:
-                e.push_frames([clips[c][f] for c, f, _, _ in step], [cut for _, _, cut, _ in step])
-            e.compute_flow_bidirectional_device()
-            flags = [cut for _, _, cut, _ in step]
-            if auto_cut:
-                flags = [a or b for a, b in zip(flags, _auto_cut_step(e, det))]
-            flt.step(flags)
-            for slot, (c, _, _, keep) in enumerate(step):
-                if keep:        # the slot's pair is (frame - 1, frame) of clip c: the step's output is frame - 1
-                    out[c].append(flt.frame(slot))
-                    if masks:
-                        ms[c].append(flt.mask(slot))
-    finally:
-        if det is not None:
-            det.close()
-        if flt is not None:
-            flt.close()
-        if e is not None:
-            e.close()
-    for c, clip in enumerate(clips):
-        out[c].append(clip[-1].copy())
-        ms[c].append(np.zeros((h, w), np.uint8))
-    return (out, ms) if masks else out
-
-
-def _cmap_split(kw):
-    """the keyword arguments of propagate_layer(s): CMapParams' go to the map, CutDetector's to the detector"""
-    cm = {k: kw.pop(k) for k in ("thresh", "tear", "use_occ") if k in kw}
-    cut = {k: kw.pop(k) for k in ("lost_permille", "residual_max") if k in kw}
-    if kw:
-        raise TypeError(f"unknown parameter {sorted(kw)[0]}")
-    return cm, cut
-
-
-def propagate_layer(frames, layer_rgba, auto_cut=False, stop_level=None, maps=False, **params):
-    """A layer painted on a clip's first frame follows the surface through the clip (CorrespondenceMap): frames are
-    (h, w, 3) uint8, layer_rgba is (h, w, 4) uint8 with straight alpha in frame 0's geometry.  One streaming context -- set_data, then
-    push_frame --, one bidirectional call on the device and one map step per pair; every output frame samples the layer ONCE, at the
-    composed map.  Returns len(frames) frames; frame 0 is the layer composited through the seed map.  Memory does not grow with the clip.
-    params: CMapParams' thresh, tear and use_occ, and with auto_cut=True CutDetector's lost_permille and residual_max: a detector looks at
-    every pair before the map does, a frame that starts another shot re-anchors the map on itself, and from then on the layer is not drawn
-    (it belongs to the first shot): those frames are the input frames.  stop_level: the flow's draft mode (None: full quality).
-    maps=True: returns (frames, maps), one (h, w, 2) float32 map per frame."""
-    cm_params, cut_params = _cmap_split(dict(params))
-    if cut_params and not auto_cut:
-        raise TypeError("propagate_layer: lost_permille and residual_max need auto_cut=True")
-    frames = [np.ascontiguousarray(f, np.uint8) for f in frames]
-    if len(frames) < 2:
-        raise EppmError("propagate_layer: at least two frames")
-    h, w, _ = frames[0].shape
-    e = EPPM()
-    cm = det = None
-    out, mp = [], []
-    drawn = True
-    try:
-        e.init(h, w)
-        e.set_temporal(True)
-        if stop_level is not None:
-            e.set_stop_level(_level(stop_level))
-        cm = CorrespondenceMap(e, **cm_params)
-        if auto_cut:
-            det = CutDetector(e, **cut_params)
-        cm.set_state(0, cmap_seed(h, w), frames[0])
-        cm.set_layer(layer_rgba, 0)
-        out.append(cm.render(0))
-        if maps:
-            mp.append(cm.map(0))
-        for k in range(len(frames) - 1):
-            if k == 0:
-                e.set_data(frames[0], frames[1])
-            else:
-                e.push_frame(frames[k + 1])
-            e.compute_flow_bidirectional_device()
-            cuts = _auto_cut_step(e, det) if auto_cut else None
-            cm.step(cuts)
-            if cuts is not None and cuts[0]:
-                drawn = False
-            out.append(cm.render(0) if drawn else frames[k + 1].copy())
-            if maps:
-                mp.append(cm.map(0))
-    finally:
-        if det is not None:
-            det.close()
-        if cm is not None:
-            cm.close()
-        e.close()
-    return (out, mp) if maps else out
-
-
-def propagate_layers(clips, layers, slots=8, auto_cut=False, stop_level=None, **params):
-    """propagate_layer for many clips at once: clips of one frame size and of any lengths (two frames at least), one layer per clip, through
-    ONE batch context of min(slots, len(clips)) slots and one CorrespondenceMap, on flow_sequences' schedule.  A slot that takes the next
-    clip of the queue passes `cut` for that step and takes that clip's layer: its output is the layer over that clip's frame 0.  Returns one
-    list of frames per clip, each what propagate_layer(clip, layer) returns."""
-    cm_params, cut_params = _cmap_split(dict(params))
-    if cut_params and not auto_cut:
-        raise TypeError("propagate_layers: lost_permille and residual_max need auto_cut=True")
-    clips = [[np.ascontiguousarray(f, np.uint8) for f in clip] for clip in clips]
-    layers = list(layers)
-    if len(layers) != len(clips):
-        raise EppmError("propagate_layers: one layer per clip")
-    plan = _sequence_plan([len(c) for c in clips], slots)
-    h, w, _ = clips[0][0].shape
-    out = [[] for _ in clips]
-    e = cm = det = None
-    try:
-        for t, step in enumerate(plan):
-            if t == 0:
-                e = EPPMBatch(h, w, len(step), params=None)
-                e.set_temporal(True)
-                if stop_level is not None:
-                    e.set_stop_level(_level(stop_level))
-                cm = CorrespondenceMap(e, **cm_params)
-                if auto_cut:
-                    det = CutDetector(e, **cut_params)
-                drawn = [True] * len(step)
-                for slot, (c, _, _, _) in enumerate(step):
-                    cm.set_state(slot, cmap_seed(h, w), clips[c][0])
-                    cm.set_layer(layers[c], slot)
-                    out[c].append(cm.render(slot))
-                e.set_data([(clips[c][0], clips[c][1]) for c, _, _, _ in step])
-            else:
-                e.push_frames([clips[c][f] for c, f, _, _ in step], [cut for _, _, cut, _ in step])
-            e.compute_flow_bidirectional_device()
-            found = _auto_cut_step(e, det) if auto_cut else [False] * len(step)
-            cm.step([cut or bool(fc) for (_, _, cut, _), fc in zip(step, found)])
-            for slot, ((c, f, new_clip, keep), fc) in enumerate(zip(step, found)):
-                if new_clip:                     # the slot's map was re-anchored on frame 0 of clip c: its layer from here on
-                    cm.set_layer(layers[c], slot)
-                    drawn[slot] = True
-                    out[c].append(cm.render(slot))
-                elif keep:
-                    if fc:
-                        drawn[slot] = False
-                    out[c].append(cm.render(slot) if drawn[slot] else clips[c][f].copy())
-    finally:
-        if det is not None:
-            det.close()
-        if cm is not None:
-            cm.close()
-        if e is not None:
-            e.close()
-    return out
-
-
-def _objects_split(kw):
-    """the keyword arguments of detect_objects(_sequences): ObjectsParams' go to the detector, CutDetector's to the cut detector"""
-    ob = {k: kw.pop(k) for k in ("tau", "iters", "connectivity", "min_area", "max_objects", "min_overlap") if k in kw}
-    cut = {k: kw.pop(k) for k in ("lost_permille", "residual_max") if k in kw}
-    if kw:
-        raise TypeError(f"unknown parameter {sorted(kw)[0]}")
-    return ob, cut
-
-
-def detect_objects(frames, auto_cut=False, stop_level=None, labels=False, **params):
-    """The moving objects of every consecutive pair of a clip ((h, w, 3) uint8 frames; ObjectDetector): one
-    streaming context -- set_data, then push_frame --, one bidirectional call on the device and one detector step per pair.  Returns one
-    list of object dicts (ObjectDetector.objects) per pair: the objects of the pair's first frame; an id persists while the object is
-    followed.  Memory does not grow with the clip.  params: ObjectsParams', and with auto_cut=True CutDetector's lost_permille and
-    residual_max: a pair that the cut detector calls a cut carries nothing over, so the objects of the next pair are all new.
-    stop_level: the flow's draft mode (None: full quality).  labels=True: returns (objects, labels), one (h, w) uint8 plane per pair."""
-    ob_params, cut_params = _objects_split(dict(params))
-    if cut_params and not auto_cut:
-        raise TypeError("detect_objects: lost_permille and residual_max need auto_cut=True")
-    frames = [np.ascontiguousarray(f, np.uint8) for f in frames]
-    if len(frames) < 2:
-        raise EppmError("detect_objects: at least two frames")
-    h, w, _ = frames[0].shape
-    e = EPPM()
-    od = det = None
-    out, planes = [], []
-    try:
-        e.init(h, w)
-        e.set_temporal(True)
-        if stop_level is not None:
-            e.set_stop_level(_level(stop_level))
-        od = ObjectDetector(e, **ob_params)
-        if auto_cut:
-            det = CutDetector(e, **cut_params)
-        for k in range(len(frames) - 1):
-            if k == 0:
-                e.set_data(frames[0], frames[1])
-            else:
-                e.push_frame(frames[k + 1])
-            e.compute_flow_bidirectional_device()
-            od.step(_auto_cut_step(e, det) if auto_cut else None)
-            out.append(od.objects(0))
-            if labels:
-                planes.append(od.labels(0))
-    finally:
-        if det is not None:
-            det.close()
-        if od is not None:
-            od.close()
-        e.close()
-    return (out, planes) if labels else out
-
-
-def detect_objects_sequences(clips, slots=8, auto_cut=False, stop_level=None, labels=False, **params):
-    """detect_objects for many clips at once: clips of one frame size and of any lengths (two frames at least) through ONE batch context
-    of min(slots, len(clips)) slots and one ObjectDetector, on flow_sequences' schedule.  A slot that takes the next clip of the queue is
-    reset after that step, so the clip's ids start at 1.  Returns one list per clip, each what detect_objects(clip) returns."""
-    ob_params, cut_params = _objects_split(dict(params))
-    if cut_params and not auto_cut:
-        raise TypeError("detect_objects_sequences: lost_permille and residual_max need auto_cut=True")
-    clips = [[np.ascontiguousarray(f, np.uint8) for f in clip] for clip in clips]
-    plan = _sequence_plan([len(c) for c in clips], slots)
-    h, w, _ = clips[0][0].shape
-    out = [[] for _ in clips]
-    planes = [[] for _ in clips]
-    e = od = det = None
-    try:
-        for t, step in enumerate(plan):
-            if t == 0:
-                e = EPPMBatch(h, w, len(step), params=None)
-                e.set_temporal(True)
-                if stop_level is not None:
-                    e.set_stop_level(_level(stop_level))
-                od = ObjectDetector(e, **ob_params)
-                if auto_cut:
-                    det = CutDetector(e, **cut_params)
-                e.set_data([(clips[c][0], clips[c][1]) for c, _, _, _ in step])
-            else:
-                e.push_frames([clips[c][f] for c, f, _, _ in step], [cut for _, _, cut, _ in step])
-            e.compute_flow_bidirectional_device()
-            flags = [cut for _, _, cut, _ in step]
-            if auto_cut:
-                flags = [a or bool(b) for a, b in zip(flags, _auto_cut_step(e, det))]
-            od.step(flags)
-            for slot, (c, _, new_clip, keep) in enumerate(step):
-                if new_clip:
-                    od.reset(slot)
-                elif keep:
-                    out[c].append(od.objects(slot))
-                    if labels:
-                        planes[c].append(od.labels(slot))
-    finally:
-        if det is not None:
-            det.close()
-        if od is not None:
-            od.close()
-        if e is not None:
-            e.close()
-    return (out, planes) if labels else out
-
-
-_PLATE_KEYS = ("tau", "iters", "margin_x", "margin_y", "grow", "accept_invalid", "thresh", "n_max", "min_count")
-
-
-def _plate_split(kw):
-    """the keyword arguments of background_plate(s) and remove_objects_sequence: PlateParams' go to the plate, CutDetector's to the cut detector"""
-    pl = {k: kw.pop(k) for k in _PLATE_KEYS if k in kw}
-    cut = {k: kw.pop(k) for k in ("lost_permille", "residual_max") if k in kw}
-    if kw:
-        raise TypeError(f"unknown parameter {sorted(kw)[0]}")
-    return pl, cut
-
-
-def _plate_clip(frames, auto_cut, stop_level, params, per_pair=None):
-    """one streaming context and one BackgroundPlate over a clip; per_pair(plate, k, path): called after pair k's step with the path that
-    step used.  Returns (the frames, the plate): the plate is still open, the caller closes it; the context is closed."""
-    pl_params, cut_params = _plate_split(dict(params))
-    if cut_params and not auto_cut:
-        raise TypeError("background plate: lost_permille and residual_max need auto_cut=True")
-    frames = [np.ascontiguousarray(f, np.uint8) for f in frames]
-    if len(frames) < 2:
-        raise EppmError("background plate: at least two frames")
-    h, w, _ = frames[0].shape
-    e = EPPM()
-    pl = det = None
-    try:
-        e.init(h, w)
-        e.set_temporal(True)
-        if stop_level is not None:
-            e.set_stop_level(_level(stop_level))
-        pl = BackgroundPlate(e, **pl_params)
-        if auto_cut:
-            det = CutDetector(e, **cut_params)
-        for k in range(len(frames) - 1):
-            if k == 0:
-                e.set_data(frames[0], frames[1])
-            else:
-                e.push_frame(frames[k + 1])
-            e.compute_flow_bidirectional_device()
-            path = pl.path(0) if per_pair is not None else None
-            pl.step(_auto_cut_step(e, det) if auto_cut else None)
-            if per_pair is not None:
-                per_pair(pl, k, path)
-        return frames, pl
-    except BaseException:
-        if pl is not None:
-            pl.close()
-        raise
-    finally:
-        if det is not None:
-            det.close()
-        e.close()
-
-
-def background_plate(frames, auto_cut=False, stop_level=None, **params):
-    """The background plate of a clip ((h, w, 3) uint8 frames; BackgroundPlate): one streaming context -- set_data,
-    then push_frame --, one bidirectional call on the device and one plate step per pair.  Returns (plate, coverage): the canvas as an
-    (h + 2*margin_y, w + 2*margin_x, 3) uint8 image in the coordinates of the first frame, and per pixel how often its value was
-    confirmed (0: never seen).  The last frame of the clip has no pair of its own and is not accumulated.  params: PlateParams', and with
-    auto_cut=True CutDetector's lost_permille and residual_max: after a pair the cut detector calls a cut the path starts again at the
-    identity and the canvas is kept.  stop_level: the flow's draft mode (None: full quality)."""
-    _, pl = _plate_clip(frames, auto_cut, stop_level, params)
-    try:
-        return pl.plate(0), pl.coverage(0)
-    finally:
-        pl.close()
-
-
-def remove_objects_sequence(frames, auto_cut=False, stop_level=None, **params):
-    """The frames of a clip with their moving objects painted out from the clip's background plate, in two passes over one plate.  Pass 1
-    steps the clip as background_plate does and keeps each pair's mask and path on the host; pass 2 renders every frame against the
-    FINISHED plate (BackgroundPlate.render_frame), so a frame is also filled from what only later frames reveal.  Returns (frames, fills):
-    one (h, w, 3) uint8 image and one (h, w) uint8 fill plane (0 free, 1 filled, 2 blocked and not filled) per input frame.  The last
-    frame of a clip has no pair of its own -- no mask, no path --, so it is returned unchanged with fill 0."""
-    kept = []
-    frames, pl = _plate_clip(frames, auto_cut, stop_level, params, per_pair=lambda p, k, path: kept.append((p.mask(0), path)))
-    try:
-        out, fills = [], []
-        for k, (mask, path) in enumerate(kept):
-            o, f = pl.render_frame(0, frames[k], mask, path)
-            out.append(o)
-            fills.append(f)
-        out.append(frames[-1].copy())
-        fills.append(np.zeros(frames[-1].shape[:2], np.uint8))
-        return out, fills
-    finally:
-        pl.close()
-
-
-def background_plates(clips, slots=8, auto_cut=False, stop_level=None, **params):
-    """background_plate for many clips at once: clips of one frame size and of any lengths (two frames at least) through ONE batch context
-    of min(slots, len(clips)) slots and one BackgroundPlate, on flow_sequences' schedule.  A clip's plate is read after the step of its
-    last pair; a slot that takes the next clip of the queue is reset after that step.  Returns one (plate, coverage) per clip, each what
-    background_plate(clip) returns."""
-    pl_params, cut_params = _plate_split(dict(params))
-    if cut_params and not auto_cut:
-        raise TypeError("background_plates: lost_permille and residual_max need auto_cut=True")
-    clips = [[np.ascontiguousarray(f, np.uint8) for f in clip] for clip in clips]
-    plan = _sequence_plan([len(c) for c in clips], slots)
-    h, w, _ = clips[0][0].shape
-    out = [None for _ in clips]
-    e = pl = det = None
-    try:
-        for t, step in enumerate(plan):
-            if t == 0:
-                e = EPPMBatch(h, w, len(step), params=None)
-                e.set_temporal(True)
-                if stop_level is not None:
-                    e.set_stop_level(_level(stop_level))
-                pl = BackgroundPlate(e, **pl_params)
-                if auto_cut:
-                    det = CutDetector(e, **cut_params)
-                e.set_data([(clips[c][0], clips[c][1]) for c, _, _, _ in step])
-            else:
-                e.push_frames([clips[c][f] for c, f, _, _ in step], [cut for _, _, cut, _ in step])
-            e.compute_flow_bidirectional_device()
-            flags = [cut for _, _, cut, _ in step]
-            if auto_cut:
-                flags = [a or bool(b) for a, b in zip(flags, _auto_cut_step(e, det))]
-            pl.step(flags)
-            for slot, (c, f, new_clip, keep) in enumerate(step):
-                if new_clip:
-                    pl.reset(slot)
-                elif keep and f == len(clips[c]) - 1:
-                    out[c] = (pl.plate(slot), pl.coverage(slot))
-    finally:
-        if det is not None:
-            det.close()
-        if pl is not None:
-            pl.close()
-        if e is not None:
-            e.close()
-    return out
-
-
-def stabilize_sequence(frames, params=None, tau=1.0, iters=3, smooth=0.9, temporal=True, stop_level=0, masks=False, auto_cut=False, **cut_params):
-    """A clip ((h, w, 3) uint8 frames) re-rendered from a smoothed camera path (Stabilizer): one streaming context --
-    set_data, then push_frame --, one bidirectional call on the device and one stabiliser step per pair.  Returns len(frames) frames; the
-    first is the input itself.  masks=True: (frames, masks, models) with one motion mask of image 1 and one model per pair.  params: the
-    flow's eppm Params; temporal / stop_level: the flow's temporal and draft modes.  auto_cut=True: a CutDetector (cut_params: its
-    lost_permille / residual_max) looks at every pair before the stabiliser does; a frame that starts another shot restarts the camera
-    path and the flow's temporal prior, so the frames are what stabilize_sequence returns for every shot on its own."""
-    stop_level = _level(stop_level)
-    frames = [np.ascontiguousarray(f, np.uint8) for f in frames]
-    if len(frames) < 2:
-        raise EppmError("stabilize_sequence: at least two frames")
-    h, w, _ = frames[0].shape
-    e = EPPM(params=params)
-    stab = det = None
-    out, mk, md = [frames[0].copy()], [], []
-    try:
-        e.init(h, w)
-        e.set_temporal(temporal)
-        e.set_stop_level(stop_level)
-        stab = Stabilizer(e, tau, iters, smooth)
-        if auto_cut:
-            det = CutDetector(e, **cut_params)
-        for k in range(len(frames) - 1):
-            if k == 0:
-                e.set_data(frames[0], frames[1])
-            else:
-                e.push_frame(frames[k + 1])
-            e.compute_flow_bidirectional_device()
-            stab.step(_auto_cut_step(e, det) if auto_cut else None)
-            out.append(stab.frame(0))
-            if masks:
-                mk.append(stab.mask(0))
-                md.append(stab.model(0))
-    finally:
-        if det is not None:
-            det.close()
-        if stab is not None:
-            stab.close()
-        e.close()
-    return (out, mk, md) if masks else out
-
-
-def stabilize_sequences(clips, slots=8, params=None, tau=1.0, iters=3, smooth=0.9, temporal=True, stop_level=0, masks=False, auto_cut=False,
-                        **cut_params):
-    """stabilize_sequence for many clips at once: clips of one frame size and of any lengths (two frames at least) through ONE batch context
-    of min(slots, len(clips)) slots and one Stabilizer, on flow_sequences' schedule.  A slot that takes the next clip of the queue passes
-    `cut` for that step: its output is that clip's frame 0.  Returns one result per clip, each what stabilize_sequence(clip) returns.
-    auto_cut=True: stabilize_sequence's, per slot; the detector's verdicts are ORed into the schedule's cut flags."""
-    stop_level = _level(stop_level)
-    clips = [[np.ascontiguousarray(f, np.uint8) for f in clip] for clip in clips]
-    plan = _sequence_plan([len(c) for c in clips], slots)
-    h, w, _ = clips[0][0].shape
-    out = [[c[0].copy()] for c in clips]
-    mk, md = [[] for _ in clips], [[] for _ in clips]
-    e = stab = det = None
-    try:
-        for t, step in enumerate(plan):
-            if t == 0:
-                e = EPPMBatch(h, w, len(step), params=params)
-                e.set_temporal(temporal)
-                e.set_stop_level(stop_level)
-                stab = Stabilizer(e, tau, iters, smooth)
-                if auto_cut:
-                    det = CutDetector(e, **cut_params)
-                e.set_data([(clips[c][0], clips[c][1]) for c, _, _, _ in step])
-            else:
-                e.push_frames([clips[c][f] for c, f, _, _ in step], [cut for _, _, cut, _ in step])
-            e.compute_flow_bidirectional_device()
-            flags = [cut for _, _, cut, _ in step]
-            if auto_cut:
-                flags = [a or b for a, b in zip(flags, _auto_cut_step(e, det))]
-            stab.step(flags)
-            for slot, (c, _, _, keep) in enumerate(step):
-                if keep:
-                    out[c].append(stab.frame(slot))
-                    if masks:
-                        mk[c].append(stab.mask(slot))
-                        md[c].append(stab.model(slot))
-    finally:
-        if det is not None:
-            det.close()
-        if stab is not None:
-            stab.close()
-        if e is not None:
-            e.close()
-    return [(o, m, d) for o, m, d in zip(out, mk, md)] if masks else out
-
-
-def _track_collect(out, trk):
-    """one step's ended and live tracks into track_sequence's dictionary"""
-    e_ids, _, _, why, _ = trk.ended()
-    for i, r in zip(e_ids.tolist(), why.tolist()):
-        out[i]["reason"] = int(r)
-    ids, starts, xy = trk.tracks()
-    for i, s0, p in zip(ids.tolist(), starts.tolist(), xy):
-        if i in out:
-            out[i]["positions"].append(p)
-        else:
-            out[i] = {"start": int(s0), "positions": [p], "reason": None}
-
-
-def _track_sequence_streaming(frames, params, track_params, stop_level=0):
-    from . import io
-    h, w, _ = frames[0].shape
-    e = EPPM(params=params)
-    trk = None
-    try:
-        e.init(h, w)
-        e.set_temporal(True)
-        e.set_stop_level(stop_level)
-        for k in range(len(frames) - 1):
-            if k == 0:
-                e.set_data(frames[0], frames[1])
-            else:
-                e.push_frame(frames[k + 1])
-            e.compute_flow_bidirectional_device()
-            if trk is None:
-                trk = Tracker(e, 0, **track_params)
-                seeds = io.track_seeds(frames[0], trk.params)[:trk.capacity]
-                out = {i: {"start": 0, "positions": [xy], "reason": None} for i, xy in enumerate(seeds)}
-            trk.step()
-            _track_collect(out, trk)
-    finally:
-        if trk is not None:
-            trk.close()
-        e.close()
-    for t in out.values():
-        t["positions"] = np.asarray(t["positions"], np.float32).reshape(-1, 2)
-    return out
-
-
-def track_sequence(frames, params=None, streaming=False, stop_level=0, **track_params):
-    """Dense point trajectories through a list of (h, w, 3) uint8 frames: one bidirectional call on a batch of the consecutive pairs, then
-    one tracker step per pair.  Returns {track id: {"start": first frame, "positions": (n, 2) float32 positions in frames start ..
-    start + n - 1, "reason": the end reason 1..4, or None while alive}}.  params: the flow's eppm Params; track_params: TrackParams'.
-    streaming=True: one single-pair context instead of the batch -- push_frame and temporal mode, one bidirectional call and one tracker
-    step per pair --, so that memory does not grow with the clip; the flows from the second pair on start from a temporal prior and are
-    not bit for bit the batch's.  stop_level: draft mode (EPPM.set_stop_level): the tracker runs on the draft flows."""
-    from . import io
-    stop_level = _level(stop_level)
-    frames = [np.ascontiguousarray(f, np.uint8) for f in frames]
-    if len(frames) < 2:
-        raise EppmError("track_sequence: at least two frames")
-    if streaming:
-        return _track_sequence_streaming(frames, params, track_params, stop_level)
-    h, w, _ = frames[0].shape
-    bat = EPPMBatch(h, w, len(frames) - 1, params=params)
-    trk = None
-    try:
-        bat.set_stop_level(stop_level)
-        bat.set_data(list(zip(frames[:-1], frames[1:])))
-        bat.compute_flow_bidirectional()
-        trk = Tracker(bat, 0, **track_params)
-        seeds = io.track_seeds(frames[0], trk.params)[:trk.capacity]
-        out = {k: {"start": 0, "positions": [xy], "reason": None} for k, xy in enumerate(seeds)}
-        for k in range(len(frames) - 1):
-            trk.step(k)
-            e_ids, _, _, why, _ = trk.ended()
-            for i, r in zip(e_ids.tolist(), why.tolist()):
-                out[i]["reason"] = int(r)
-            ids, starts, xy = trk.tracks()
-            for i, s0, p in zip(ids.tolist(), starts.tolist(), xy):
-                if i in out:
-                    out[i]["positions"].append(p)
-                else:
-                    out[i] = {"start": int(s0), "positions": [p], "reason": None}
-    finally:
-        if trk is not None:
-            trk.close()
-        bat.close()
-    for t in out.values():
-        t["positions"] = np.asarray(t["positions"], np.float32).reshape(-1, 2)
-    return out
-
-
-class EPPM:
+class EPPM(_Context):
     """``init`` / ``set_data`` / ``compute_flow`` as in bao_flow_patchmatch_multiscale_cuda.h:36-44.
 
     Images are (h, w, 3) uint8 arrays in R,G,B order (the reference's ``unsigned char***``);
@@ -1655,17 +805,6 @@ class EPPM:
         self._need()
         check(lib().eppm_set_temporal(self._ctx, int(bool(on))), "eppm_set_temporal")
 
-    def set_stop_level(self, level):
-        """Draft mode (eppm_set_stop_level, DESIGN.md section 14): the pyramid levels below `level` are upsampled edge-aware from the level
-        above (one launch each) instead of being refined and smoothed; 0 (default): the full path.  Takes effect at the next compute."""
-        level = _level(level)
-        self._need()
-        check(lib().eppm_set_stop_level(self._ctx, level), "eppm_set_stop_level")
-
-    def stop_level(self):
-        self._need()
-        return int(lib().eppm_stop_level(self._ctx))
-
     def temporal_reset(self):
         """Drop the previous pair's fields: the next compute is a cold run (eppm_temporal_reset)."""
         self._need()
@@ -1691,12 +830,6 @@ class EPPM:
         u, v = self._out(out)
         check(lib().eppm_compute(self._ctx, u.ctypes.data_as(C.c_void_p), v.ctypes.data_as(C.c_void_p)), "eppm_compute")
         return u, v
-
-    def set_occlusion_params(self, alpha=0.01, beta=0.5):
-        """alpha, beta of the occlusion masks' forward-backward criterion (eppm_set_occlusion_params)."""
-        self._need()
-        check(lib().eppm_set_occlusion_params(self._ctx, C.c_float(alpha), C.c_float(beta)), "eppm_set_occlusion_params")
-        self._occ_params = (float(alpha), float(beta))
 
     def compute_flow_bidirectional(self, alpha=None, beta=None):
         """(u, v, bu, bv, occ1, occ2): the forward flow (== compute_flow), the backward flow (image 2 -> image 1) and the uint8
@@ -1791,24 +924,11 @@ class EPPM:
         self._need()
         check(lib().eppm_compute_device(self._ctx, C.c_void_p(d_flow) if d_flow else None), "eppm_compute_device")
 
-    def synchronize(self):
-        self._need()
-        check(lib().eppm_synchronize(self._ctx), "eppm_synchronize")
-
     def set_stream(self, hip_stream):
         self._need()
         check(lib().eppm_set_stream(self._ctx, C.c_void_p(hip_stream)), "eppm_set_stream")
 
     # -- introspection ---------------------------------------------------------------------
-    def level_dims(self):
-        self._need()
-        out = []
-        for l in range(lib().eppm_num_levels(self._ctx)):
-            h, w = C.c_int(), C.c_int()
-            check(lib().eppm_level_dims(self._ctx, l, C.byref(h), C.byref(w)), "eppm_level_dims")
-            out.append((h.value, w.value))
-        return out
-
     def plane(self, name, level):
         self._need()
         dims = self.level_dims()
@@ -1820,39 +940,12 @@ class EPPM:
               "eppm_get_plane")
         return a
 
-    def enable_stage_timing(self, on=True):
-        self._need()
-        check(lib().eppm_enable_stage_timing(self._ctx, int(on)), "eppm_enable_stage_timing")
-
-    def stage_times(self, clear=True):
-        """[(stage name, ms)] for every set_data / compute_flow since the last clear (timing enabled)."""
-        self._need()
-        cap = 1 << 16
-        names = (C.c_char_p * cap)()
-        ms = (C.c_float * cap)()
-        n = lib().eppm_stage_times(self._ctx, names, ms, cap)
-        out = [(names[i].decode(), float(ms[i])) for i in range(n)]
-        if clear:
-            check(lib().eppm_clear_stage_times(self._ctx), "eppm_clear_stage_times")
-        return out
-
-    def close(self):
-        if self._ctx:
-            lib().eppm_destroy(self._ctx)
-            self._ctx = C.c_void_p()
-
     def _need(self):
         if not self._ctx:
             raise EppmError("EPPM: init(h, w) has not been called")
 
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
 
-
-class EPPMBatch:
+class EPPMBatch(_Context):
     """A batch of independent pairs of one size on one GPU (eppm_create_batch): every kernel launch of the path covers all
     active pairs.  ``set_data(pairs)`` / ``compute_flow()`` mirror the single-pair class; each pair's flow is bit-identical
     to the single-pair result."""
@@ -1892,14 +985,6 @@ class EPPMBatch:
         if len(new_clip) != n:
             raise EppmError("new_clip: one flag per frame")
         return (C.c_uint8 * n)(*[int(bool(x)) for x in new_clip])
-
-    def set_stop_level(self, level):
-        """Draft mode for every slot (eppm_set_stop_level; EPPM.set_stop_level)."""
-        level = _level(level)
-        check(lib().eppm_set_stop_level(self._ctx, level), "eppm_set_stop_level")
-
-    def stop_level(self):
-        return int(lib().eppm_stop_level(self._ctx))
 
     def push_frames(self, frames, new_clip=None):
         """Slot k's image 2 becomes its image 1 and frames[k] its image 2 (eppm_batch_push_images): only the new frames are uploaded and
@@ -1960,9 +1045,6 @@ class EPPMBatch:
         Tracker, TemporalFilter)."""
         check(lib().eppm_compute_bidirectional_device(self._ctx, None, None, None, None), "eppm_compute_bidirectional_device")
 
-    def set_occlusion_params(self, alpha=0.01, beta=0.5):
-        check(lib().eppm_set_occlusion_params(self._ctx, C.c_float(alpha), C.c_float(beta)), "eppm_set_occlusion_params")
-
     def interpolate(self, times):
         """[[frame at times[k] for k] for each active pair] after compute_flow_bidirectional (eppm_batch_interpolate)."""
         ts = _times(times)
@@ -1995,41 +1077,18 @@ class EPPMBatch:
         self._pending_out = None
         return list(zip(u, v))
 
-    def synchronize(self):
-        check(lib().eppm_synchronize(self._ctx), "eppm_synchronize")
-
     def plane(self, pair, name, level):
-        dims = []
-        for l in range(lib().eppm_num_levels(self._ctx)):
-            hh, ww = C.c_int(), C.c_int()
-            check(lib().eppm_level_dims(self._ctx, l, C.byref(hh), C.byref(ww)), "eppm_level_dims")
-            dims.append((hh.value, ww.value))
-        hh, ww = dims[level]
+        hh, ww = self.level_dims()[level]
         a = np.empty((hh, ww), _PLANE_DTYPES[name])
         check(lib().eppm_batch_get_plane(self._ctx, int(pair), name.encode(), level, a.ctypes.data_as(C.c_void_p), C.c_size_t(a.nbytes)),
               "eppm_batch_get_plane")
         return a
 
-    def enable_stage_timing(self, on=True):
-        check(lib().eppm_enable_stage_timing(self._ctx, int(on)), "eppm_enable_stage_timing")
 
-    def stage_times(self, clear=True):
-        cap = 1 << 16
-        names = (C.c_char_p * cap)()
-        ms = (C.c_float * cap)()
-        n = lib().eppm_stage_times(self._ctx, names, ms, cap)
-        out = [(names[i].decode(), float(ms[i])) for i in range(n)]
-        if clear:
-            check(lib().eppm_clear_stage_times(self._ctx), "eppm_clear_stage_times")
-        return out
-
-    def close(self):
-        if self._ctx:
-            lib().eppm_destroy(self._ctx)
-            self._ctx = C.c_void_p()
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
+def __getattr__(name):
+    """The clip drivers and their helpers lived in this module before sequences.py: eppm_amd.api.<name> still finds what is defined there."""
+    from . import sequences
+    obj = getattr(sequences, name, None)
+    if getattr(obj, "__module__", None) != sequences.__name__:
+        raise AttributeError(f"module {__name__!r} has no attribute {name!r}")
+    return obj
