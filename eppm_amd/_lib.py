@@ -79,6 +79,17 @@ class CDefectStats(C.Structure):
         return {k: int(getattr(self, k)) for k, _ in self._fields_}
 
 
+class CDeflickerParams(C.Structure):
+    _fields_ = [("cell", C.c_int), ("iters", C.c_int), ("reject", C.c_float), ("tau", C.c_float), ("keep", C.c_float), ("n_min", C.c_int)]
+
+
+class CDeflickerStats(C.Structure):
+    _fields_ = [("used", C.c_int64), ("valid_cells", C.c_int32), ("cells", C.c_int32)]
+
+    def as_dict(self):
+        return {k: int(getattr(self, k)) for k, _ in self._fields_}
+
+
 class CObject(C.Structure):
     _fields_ = [("id", C.c_int32), ("age", C.c_int32), ("area", C.c_int32), ("x0", C.c_int32), ("y0", C.c_int32), ("x1", C.c_int32),
                 ("y1", C.c_int32), ("n_flow", C.c_int32), ("sum_x", C.c_int64), ("sum_y", C.c_int64), ("sum_qu", C.c_int64), ("sum_qv", C.c_int64)]
@@ -155,6 +166,9 @@ SYMBOLS = [
     "eppm_defect_default_params", "eppm_defect_create", "eppm_defect_create_size", "eppm_defect_destroy", "eppm_defect_reset", "eppm_defect_step",
     "eppm_defect_step_frames", "eppm_defect_get", "eppm_defect_get_device", "eppm_defect_get_mask", "eppm_defect_get_stats",
     "eppm_defect_get_state", "eppm_defect_set_state", "eppm_defect_step_host",
+    "eppm_deflicker_default_params", "eppm_deflicker_create", "eppm_deflicker_create_size", "eppm_deflicker_destroy", "eppm_deflicker_reset",
+    "eppm_deflicker_step", "eppm_deflicker_step_frames", "eppm_deflicker_get", "eppm_deflicker_get_device", "eppm_deflicker_get_field",
+    "eppm_deflicker_get_stats", "eppm_deflicker_get_state", "eppm_deflicker_set_state", "eppm_deflicker_step_host",
 ]
 
 

@@ -4,7 +4,7 @@ import ctypes as C
 import numpy as np
 
 from .io import object_record
-from ._lib import CDefectParams, CDefectStats, CObject, CObjectsCounts, CObjectsParams, CPlateParams, CCMapParams, CCutParams, CCutStats, CGMotionModel, CMBlurParams, CParams, CStabParams, CTFilterParams, CTrackCounts, CTrackParams, EppmError, check, lib
+from ._lib import CDefectParams, CDefectStats, CDeflickerParams, CDeflickerStats, CObject, CObjectsCounts, CObjectsParams, CPlateParams, CCMapParams, CCutParams, CCutStats, CGMotionModel, CMBlurParams, CParams, CStabParams, CTFilterParams, CTrackCounts, CTrackParams, EppmError, check, lib
 
 uchar4 = np.dtype([("x", "u1"), ("y", "u1"), ("z", "u1"), ("w", "u1")])
 short2 = np.dtype([("x", "i2"), ("y", "i2")])
@@ -303,6 +303,61 @@ class DefectFilter(_ClipObject):
         if rgb.shape != (self.h, self.w, 3) or bwd.shape != (self.h, self.w, 2):
             raise EppmError(f"DefectFilter.set_state: a ({self.h},{self.w},3) uint8 frame and a ({self.h},{self.w},2) float32 flow")
         self._call("set_state", int(slot), rgb.ctypes.data_as(C.c_void_p), bwd.ctypes.data_as(C.c_void_p), int(bool(has_prev)))
+
+
+class Deflicker(_ClipObject):
+    """Flicker removal over the pairs of a context (eppm_deflicker_*): a gain and an offset per colour on a grid of
+    cell x cell pixels, fitted to the motion-compensated reference and applied to IMAGE 2 of the active pairs of the context's last
+    compute_flow_bidirectional*.  ctx: an EPPM or an EPPMBatch; one slot per pair of it.  The reference of a slot is its previous output;
+    an empty slot (new, or after reset()) starts from its pair's image 1, and a step whose pair is cut returns image 2 itself.  The object
+    is its own allocation on the context's device; close() frees it."""
+    _prefix = "deflicker"
+
+    def __init__(self, ctx, cell=32, iters=2, reject=60.0, tau=12.0, keep=1.0, n_min=32, size=None, slots=1, device=0):
+        """ctx None: an object without a context, for step_frames on caller planes (eppm_deflicker_create_size): size = (h, w), `slots` slots."""
+        self.params = CDeflickerParams(int(cell), int(iters), float(reject), float(tau), float(keep), int(n_min))
+        self._open(ctx, size, slots, device)
+        self.cells_y, self.cells_x = -(-self.h // int(cell)), -(-self.w // int(cell))
+
+    def step_frames(self, slot, d_rgba1, d_rgba2, pitch, d_flow_bwd, d_occ2, cut=False):
+        """eppm_deflicker_step_frames: one step of one slot on caller device planes (addresses), synchronous."""
+        check(lib().eppm_deflicker_step_frames(self._f, int(slot), C.c_void_p(d_rgba1), C.c_void_p(d_rgba2), C.c_size_t(pitch),
+                                               C.c_void_p(d_flow_bwd), C.c_void_p(d_occ2), int(bool(cut))), "eppm_deflicker_step_frames")
+
+    def frame(self, slot=0):
+        """(h, w, 3) uint8: the slot's corrected image 2 of the last step."""
+        return self._rgb("get", slot)
+
+    def frames(self):
+        """The corrected frames of the context's active pairs' slots."""
+        return [self.frame(k) for k in range(getattr(self.ctx, "n", 1))]
+
+    def frame_device(self, slot, d_rgba, pitch):
+        check(lib().eppm_deflicker_get_device(self._f, int(slot), C.c_void_p(d_rgba), C.c_size_t(pitch)), "eppm_deflicker_get_device")
+
+    def field(self, slot=0):
+        """(field (cells_y, cells_x, 6) float32 {aR, aG, aB, bR, bG, bB}, valid (cells_y, cells_x) uint8) of the slot's last step."""
+        f, v = np.empty((self.cells_y, self.cells_x, 6), np.float32), np.empty((self.cells_y, self.cells_x), np.uint8)
+        self._call("get_field", int(slot), f.ctypes.data_as(C.c_void_p), v.ctypes.data_as(C.c_void_p))
+        return f, v
+
+    def stats(self, slot=0):
+        """dict(used, valid_cells, cells): the members of the slot's last pass, the cells with n_min of them, the cells of the grid."""
+        st = CDeflickerStats()
+        self._call("get_stats", int(slot), C.byref(st))
+        return st.as_dict()
+
+    def state(self, slot=0):
+        """(frame (h, w, 3) uint8, empty): the slot's reference and whether the slot counts as empty."""
+        rgb, empty = np.empty((self.h, self.w, 3), np.uint8), C.c_int()
+        self._call("get_state", int(slot), rgb.ctypes.data_as(C.c_void_p), C.byref(empty))
+        return rgb, bool(empty.value)
+
+    def set_state(self, slot, frame, empty=False):
+        rgb = np.ascontiguousarray(frame, np.uint8)
+        if rgb.shape != (self.h, self.w, 3):
+            raise EppmError(f"Deflicker.set_state: a ({self.h},{self.w},3) uint8 frame")
+        self._call("set_state", int(slot), rgb.ctypes.data_as(C.c_void_p), int(bool(empty)))
 
 
 class Stabilizer(_ClipObject):

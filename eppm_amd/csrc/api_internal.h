@@ -11,8 +11,8 @@
 //   ctx_images.cpp         set_images, push_image, prepare, the host upload of one image (the class's set_data)
 //   ctx_compute.cpp        compute in all its forms, the post-PatchMatch branch of both directions, temporal mode (the class's compute_flow)
 //   ctx_interp.cpp         frame interpolation, the synthetic shutter, the stage objects' view of a context
-//   stage_object.h/.cpp    the core of the eight per-clip stage objects (tracker.cpp, tfilter.cpp, stabilizer.cpp, cutdet.cpp, cmap.cpp,
-//                          objects.cpp, plate.cpp, defect.cpp): one allocation and event, the hand-over between streams, shared host helpers
+//   stage_object.h/.cpp    the core of the nine per-clip stage objects (tracker.cpp, tfilter.cpp, stabilizer.cpp, cutdet.cpp, cmap.cpp,
+//                          objects.cpp, plate.cpp, defect.cpp, deflicker.cpp): one allocation and event, the hand-over between streams, shared host helpers
 //   device_api.cpp         device-memory plumbing of the ABI (malloc / memcpy / NUMA binding)
 //   launchers_ref_abi.cpp  the reference's live extern "C" stage launchers and the sub-stage entry points of the parity tests
 //   test_hooks.cpp         libeppm_hip_test.so only: include/eppm_test.h

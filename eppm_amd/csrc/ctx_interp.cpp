@@ -1,5 +1,5 @@
 // ctx_interp.cpp -- what reads the results of a context's (context.h) last call: frame interpolation, the synthetic shutter, and the one
-// view of a context that the eight per-clip stage objects share (stage_object.h).
+// view of a context that the nine per-clip stage objects share (stage_object.h).
 #include "context.h"
 #include "stage_object.h"
 #include "interp.h"

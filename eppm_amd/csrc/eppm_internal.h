@@ -572,6 +572,37 @@ constexpr size_t defect_off_mask(size_t px) { return px * 33; }
 void launch_defect_detect(const DefectArgs& a, hipStream_t s);
 void launch_defect_apply(const DefectArgs& a, hipStream_t s);
 
+// ---- flicker removal (k_deflicker.hip; the arithmetic: deflicker.h) ----
+// One step covers n pairs: pair k's inputs (TFilterArgs' planes) lie k * (their stride) bytes past pair 0's and feed slot slot0 + k, whose
+// block lies (slot0 + k) * slot_stride bytes past `mem`: reference 0 | 1 (h*w RGBA words each) | sums (13 words per cell) | field (6 floats
+// per cell: the three gains, the three offsets) | valid (a byte per cell).  A step is iters x (accumulate, field) and one apply launch;
+// `pass` and `bound` are the launch's.  The per-slot bits travel in the kernel arguments as TFilterArgs' do: cur (which reference is the
+// previous output; the apply writes the other), empty (the reference is image 1) and cut (no pixel is sampled, so the output is image 2).
+struct DeflickerArgs {
+    const uint8_t* img1;
+    const uint8_t* img2;
+    size_t img_pitch, img_stride;
+    const float* bwd;
+    size_t bwd_stride;
+    const uint8_t* occ2;
+    size_t occ_stride;
+    char* mem;
+    size_t slot_stride;
+    int h, w, n, slot0;
+    int cell, cx, cy, pass, n_min;
+    float bound, keep;
+    uint32_t cur[kTemporalMaxSlots / 32], empty[kTemporalMaxSlots / 32], cut[kTemporalMaxSlots / 32];
+};
+// the planes of a slot's block, in bytes from its start (px = h*w, cells = cx*cy); sums, field and valid start on a multiple of 16
+constexpr size_t deflicker_off_ref(size_t px, int which) { return (size_t)which * px * 4; }
+constexpr size_t deflicker_off_sums(size_t px) { return (px * 8 + 15) & ~(size_t)15; }
+constexpr size_t deflicker_off_field(size_t px, size_t cells) { return deflicker_off_sums(px) + ((cells * 52 + 15) & ~(size_t)15); }
+constexpr size_t deflicker_off_valid(size_t px, size_t cells) { return deflicker_off_field(px, cells) + ((cells * 24 + 15) & ~(size_t)15); }
+constexpr size_t deflicker_slot_bytes(size_t px, size_t cells) { return deflicker_off_valid(px, cells) + cells; }
+void launch_deflicker_accumulate(const DeflickerArgs& a, hipStream_t s);
+void launch_deflicker_field(const DeflickerArgs& a, hipStream_t s);
+void launch_deflicker_apply(const DeflickerArgs& a, hipStream_t s);
+
 // ---- flow colour coding (k_color.hip) ----
 // rgba: h*w packed R | G<<8 | B<<16 (alpha 0); flow: h*w float2
 void launch_flow_to_color(uint32_t* rgba, const float* flow, int h, int w, float max_disp_x, float max_disp_y, hipStream_t s, Batch bt = kOnePair);

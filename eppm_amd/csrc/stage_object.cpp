@@ -1,5 +1,5 @@
 // stage_object.cpp -- the core of the per-clip stage objects (stage_object.h): the one open and close of their
-// allocation and event, the hand-over of an object between streams, and the small host helpers the eight modules share.
+// allocation and event, the hand-over of an object between streams, and the small host helpers the nine modules share.
 #include "stage_object.h"
 
 using namespace eppm;

@@ -247,6 +247,28 @@ def defect_step_host(prev, cur, nxt, bu=None, bv=None, fu=None, fv=None, detect=
     return out, mask, st.as_dict()
 
 
+def deflicker_step_host(ref, cur, bu, bv, occ2, cell=32, iters=2, reject=60.0, tau=12.0, keep=1.0, n_min=32, cut=False):
+    """One step of flicker removal on the host (eppm_deflicker_step_host; bit-identical to the kernels).  ref: the
+    (h, w, 3) uint8 reference (the previous output; image 1 for an empty slot); cur: image 2; (bu, bv): the backward flow image 2 -> image
+    1; occ2: the occlusion mask of image 2's pixels; cut: cur starts another clip.  Returns (rgb (h, w, 3) uint8, field (cells_y, cells_x,
+    6) float32, valid (cells_y, cells_x) uint8, stats dict)."""
+    from ._lib import CDeflickerParams, CDeflickerStats
+    p = CDeflickerParams(int(cell), int(iters), float(reject), float(tau), float(keep), int(n_min))
+    r, c = np.ascontiguousarray(ref, np.uint8), np.ascontiguousarray(cur, np.uint8)
+    bu, bv, o = np.ascontiguousarray(bu, np.float32), np.ascontiguousarray(bv, np.float32), np.ascontiguousarray(occ2, np.uint8)
+    if c.ndim != 3 or c.shape[2] != 3:
+        raise ValueError("deflicker_step_host: the frame must be (h, w, 3)")
+    h, w, _ = c.shape
+    if r.shape != c.shape or bu.shape != (h, w) or bv.shape != (h, w) or o.shape != (h, w):
+        raise ValueError("deflicker_step_host: frames (h, w, 3), flow and mask (h, w)")
+    cy, cx = -(-h // max(int(cell), 1)), -(-w // max(int(cell), 1))
+    out, field, valid, st = np.empty_like(c), np.empty((cy, cx, 6), np.float32), np.empty((cy, cx), np.uint8), CDeflickerStats()
+    check(lib().eppm_deflicker_step_host(C.byref(p), out.ctypes.data_as(C.c_void_p), field.ctypes.data_as(C.c_void_p),
+                                         valid.ctypes.data_as(C.c_void_p), C.byref(st), *[x.ctypes.data_as(C.c_void_p) for x in (r, c, bu, bv, o)],
+                                         h, w, int(bool(cut))), "eppm_deflicker_step_host")
+    return out, field, valid, st.as_dict()
+
+
 def cmap_seed(h, w):
     """(h, w, 2) float32: the seed of a correspondence map, map(x, y) = (x, y)."""
     m = np.empty((int(h), int(w), 2), np.float32)

@@ -5,7 +5,7 @@ import numpy as np
 
 from . import io
 from ._lib import EppmError
-from .api import (EPPM, BackgroundPlate, CorrespondenceMap, CutDetector, DefectFilter, EPPMBatch, ObjectDetector, Stabilizer, TemporalFilter,
+from .api import (EPPM, BackgroundPlate, CorrespondenceMap, CutDetector, DefectFilter, Deflicker, EPPMBatch, ObjectDetector, Stabilizer, TemporalFilter,
                   Tracker, _level)
 
 
@@ -138,6 +138,7 @@ class _Run:
 
 _CUT_KEYS = ("lost_permille", "residual_max")
 _DEFECT_KEYS = ("detect", "agree", "radius", "grow")
+_DEFLICKER_KEYS = ("cell", "iters", "reject", "tau", "keep", "n_min")
 _CMAP_KEYS = ("thresh", "tear", "use_occ")
 _OBJECTS_KEYS = ("tau", "iters", "connectivity", "min_area", "max_objects", "min_overlap")
 _PLATE_KEYS = ("tau", "iters", "margin_x", "margin_y", "grow", "accept_invalid", "thresh", "n_max", "min_count")
@@ -284,6 +285,40 @@ def remove_defects_sequences(clips, slots=8, auto_cut=False, stop_level=None, ma
     returns.  auto_cut=True: per slot; the detector's verdicts are ORed into the schedule's cut flags."""
     out, ms = _remove_defects("remove_defects_sequences", clips, slots, auto_cut, stop_level, masks, params, temporal, kw)
     return (out, ms) if masks else out
+
+
+def _deflicker(who, clips, slots, params, temporal, stop_level, auto_cut, fields, kw):
+    """deflicker_sequence(s): (frames, fields), one list per clip each"""
+    dk, cut_params = _split(kw, _DEFLICKER_KEYS, who, auto_cut)
+    with _Run(who, clips, slots, params, temporal, _level(stop_level), lambda e: Deflicker(e, **dk), auto_cut, cut_params) as run:
+        out, fl = [[c[0].copy()] for c in run.clips], [[] for _ in run.clips]
+        for slot, c, _, _, keep in run:
+            if keep:
+                out[c].append(run.stage.frame(slot))
+                if fields:
+                    fl[c].append(run.stage.field(slot))
+    return out, fl
+
+
+def deflicker_sequence(frames, params=None, temporal=True, stop_level=0, auto_cut=False, fields=False, **kw):
+    """A clip ((h, w, 3) uint8 frames) with its flicker removed (Deflicker): one streaming context -- set_data, then
+    push_frame --, one bidirectional call on the device and one deflicker step per pair; every frame is corrected towards the corrected
+    frame before it.  Returns len(frames) frames; the first is the input itself.  fields=True: (frames, fields), one (field, valid) per
+    pair (Deflicker.field).  kw: Deflicker's cell / iters / reject / tau / keep / n_min, and with auto_cut=True CutDetector's
+    lost_permille / residual_max: a detector looks at every pair first, and a frame that starts another shot is returned as it is and
+    becomes the reference.  params: the flow's eppm Params; temporal / stop_level: the flow's temporal and draft modes.  Memory does not
+    grow with the clip."""
+    out, fl = _deflicker("deflicker_sequence", [frames], None, params, temporal, stop_level, auto_cut, fields, kw)
+    return (out[0], fl[0]) if fields else out[0]
+
+
+def deflicker_sequences(clips, slots=8, params=None, temporal=True, stop_level=0, auto_cut=False, fields=False, **kw):
+    """deflicker_sequence for many clips at once: clips of one frame size and of any lengths (two frames at least) through ONE batch
+    context of min(slots, len(clips)) slots and one Deflicker, on flow_sequences' schedule.  A slot that takes the next clip of the queue
+    passes `cut` for that step: its output is that clip's frame 0.  Returns one list of frames per clip (fields=True: (frames, fields)),
+    each what deflicker_sequence(clip) returns.  auto_cut=True: per slot; the detector's verdicts are ORed into the schedule's cut flags."""
+    out, fl = _deflicker("deflicker_sequences", clips, slots, params, temporal, stop_level, auto_cut, fields, kw)
+    return (out, fl) if fields else out
 
 
 def _propagate(who, clips, layers, slots, auto_cut, stop_level, maps, params):

@@ -425,6 +425,71 @@ int  eppm_tfilter_step_host(const eppm_tfilter_params* p, float* acc_out, uint8_
                             const float* bu, const float* bv, const uint8_t* occ2, int h, int w, int cut);
 
 /* ----------------------------------------------------------------------------------------
+ * flicker removal: frame-to-frame brightness fluctuation that varies slowly over the picture (archive film,
+ * timelapse, mains lighting) is modelled as a gain and an offset per colour on a grid of cell x cell pixels.  A step runs on a pair and
+ * corrects IMAGE 2 towards the slot's reference, the previous step's corrected output (image 1 while the slot is empty).  A pixel whose
+ * backward vector is known, stays inside the frame and is not occluded (occ2 == 0) samples the reference bilinearly (p); it is a member of
+ * pass 0 if |v - p| summed over the colours is within `reject`, and of a later pass if the previous pass's field brings v within `tau` of
+ * p.  Per cell and colour the members' exact integer sums give the regression a = (cov + 64 N^2) / (var + 64 N^2) clamped to [0.5, 2] and
+ * b = (sum p - a sum v) / N in float64; a cell with fewer than n_min members is invalid.  The field is the (1, 2, 1) x (1, 2, 1) average
+ * over the valid cells of each 3 x 3 neighbourhood (none: gain 1, offset 0), read bilinearly between cell centres; the output is
+ * (1 + keep (a - 1)) v + keep b, rounded and clamped, and becomes the slot's next reference.  A cut step returns image 2 itself.  The
+ * kernels equal eppm_deflicker_step_host bit for bit, in both libraries.  A deflicker object is a separate allocation on its context's
+ * device (8 bytes per pixel and 77 per cell, per slot); a context that never creates one allocates and launches exactly what it did without.
+ * -------------------------------------------------------------------------------------- */
+typedef struct eppm_deflicker_params {
+    int   cell;                  /* the grid's cell, 16, 32 or 64 pixels (32) */
+    int   iters;                 /* passes, 1 .. 4 (2) */
+    float reject;                /* pass 0: largest |dR| + |dG| + |dB| between the new pixel and its sample (60); finite, >= 0 */
+    float tau;                   /* later passes: the same after the previous pass's correction (12); finite, >= 0 */
+    float keep;                  /* how much of the correction is applied, 0 .. 1 (1) */
+    int   n_min;                 /* a cell needs this many members, >= 1 (32) */
+} eppm_deflicker_params;
+typedef struct eppm_deflicker_stats {
+    int64_t used;                /* members of the last pass */
+    int32_t valid_cells;         /* cells with at least n_min of them */
+    int32_t cells;               /* cells of the grid */
+} eppm_deflicker_stats;
+typedef struct eppm_deflicker eppm_deflicker;
+
+int  eppm_deflicker_default_params(eppm_deflicker_params* p);
+/* p NULL: the defaults.  One slot per pair of ctx (eppm_batch_size), on its device; every slot empty. */
+int  eppm_deflicker_create(eppm_ctx* ctx, const eppm_deflicker_params* p, eppm_deflicker** out);
+/* an object without a context, for eppm_deflicker_step_frames on caller planes: nslots slots of h x w pixels (any size from 1 x 1) */
+int  eppm_deflicker_create_size(int h, int w, int nslots, int device, const eppm_deflicker_params* p, eppm_deflicker** out);
+int  eppm_deflicker_destroy(eppm_deflicker* f);             /* NULL is fine */
+int  eppm_deflicker_reset(eppm_deflicker* f, int slot);     /* the slot is empty again; slot < 0: every slot */
+/* One step of slots 0 .. active pairs - 1 on the pairs of ctx's last eppm_compute_bidirectional* (the raw frames, the level-0 backward flow
+ * and occ2): valid in the window of eppm_interpolate* (EPPM_ERR_STATE outside it); EPPM_ERR_ARG for a context of other dimensions, another
+ * device or more active pairs than the object has slots.  cut: NULL, or one flag per active pair; non-zero: image 2 of that pair is the
+ * first frame of another clip.  A slot the step does not cover keeps its state.  2 iters + 1 launches, asynchronous on the context's
+ * stream: no copy, no allocation, no host synchronisation. */
+int  eppm_deflicker_step(eppm_deflicker* f, eppm_ctx* ctx, const uint8_t* cut);
+/* the same step of one slot on caller device planes of the object's size (RGBA images of `pitch` bytes per row, h*w float2 backward flow,
+ * h*w mask bytes); on the launcher stream, synchronous.  d_rgba1 is read only if the slot is empty.  Whatever the planes hold, nothing
+ * outside them is read. */
+int  eppm_deflicker_step_frames(eppm_deflicker* f, int slot, const void* d_rgba1, const void* d_rgba2, size_t pitch,
+                                const eppm_float2* d_flow_bwd, const uint8_t* d_occ2, int cut);
+/* the slot's corrected image 2 of the last step (EPPM_ERR_STATE on a slot never stepped): packed RGB to the host, synchronous ... */
+int  eppm_deflicker_get(eppm_deflicker* f, int slot, uint8_t* rgb, size_t row_stride);
+/* ... or RGBA words (alpha 255) into a device plane, asynchronous on the stream of the object's last step */
+int  eppm_deflicker_get_device(eppm_deflicker* f, int slot, void* d_rgba, size_t pitch);
+/* synchronous (EPPM_ERR_STATE on a slot never stepped): the last step's field on the grid of cells_x = (w + cell - 1) / cell by cells_y =
+ * (h + cell - 1) / cell cells, cells_y * cells_x * 6 floats {aR, aG, aB, bR, bG, bB}, and
+ * a byte per cell, 1 where the last pass's own model was valid (either may be NULL); the last step's counts */
+int  eppm_deflicker_get_field(eppm_deflicker* f, int slot, float* field, uint8_t* valid);
+int  eppm_deflicker_get_stats(eppm_deflicker* f, int slot, eppm_deflicker_stats* stats);
+/* synchronous.  The slot's reference frame (packed RGB, h*w*3) and whether the slot is empty (EPPM_ERR_STATE on a slot that was never
+ * stepped nor loaded) / load them: a later eppm_deflicker_get returns the loaded frame */
+int  eppm_deflicker_get_state(eppm_deflicker* f, int slot, uint8_t* rgb, int* empty);
+int  eppm_deflicker_set_state(eppm_deflicker* f, int slot, const uint8_t* rgb, int empty);
+/* host form (no GPU needed): one step on packed RGB frames; rgb_ref: the reference (image 1 for an empty slot), rgb_cur: image 2,
+ * (bu, bv): the backward flow, occ2: the mask.  field_out: cells * 6 floats, valid_out: cells bytes.  rgb_out must not be rgb_ref. */
+int  eppm_deflicker_step_host(const eppm_deflicker_params* p, uint8_t* rgb_out, float* field_out, uint8_t* valid_out,
+                              eppm_deflicker_stats* stats, const uint8_t* rgb_ref, const uint8_t* rgb_cur, const float* bu, const float* bv,
+                              const uint8_t* occ2, int h, int w, int cut);
+
+/* ----------------------------------------------------------------------------------------
  * film-defect removal: dust, dirt, dropouts and sparkle live for one frame, so a defective pixel differs from both
  * of its motion-compensated neighbours in time while those agree with each other.  A step runs on the pair (image 1 = F_k, image 2 =
  * F_k+1) and repairs IMAGE 1: its next side is image 2 through the level-0 forward flow, its previous side is F_k-1 through the backward
@@ -828,7 +893,7 @@ int  eppm_clear_stage_times(eppm_ctx* ctx);
  * "flow_blf_bwd_L<l>", "flow_blf_bwd_final" and "fb_occlusion"; an interpolation call "interp_splat", "interp_fill" and "interp_blend"
  * (mode 1, once per group of four times); a track step "track_advance", "track_seed" and "track_compact" (mode 1; the step that seeds
  * frame 0 adds a "track_seed" before "track_advance"); a compute that starts from a temporal prior "temporal_advect" (before "patchmatch") and
- * "temporal_select" (inside it: "patchmatch" includes its time); a temporal-filter step "tfilter_step"; a stabiliser step "stab_fit" (every accumulate and solve launch) and "stab_warp"; a cut-detector step "cutdet"; a motion-blur call "mblur_pack" and "mblur_gather"; a correspondence-map step "cmap_step" and "cmap_render"; an object-detector step "objects_fit" (its stabiliser's launches), "objects_label" and "objects_assign"; a background-plate step "plate_fit" (its stabiliser's launches), "plate_block" and "plate_accumulate", its render "plate_render"; a defect-filter step "defect_detect" and "defect_apply".  Events come from a per-context pool: none is created in a steady-state step. */
+ * "temporal_select" (inside it: "patchmatch" includes its time); a temporal-filter step "tfilter_step"; a stabiliser step "stab_fit" (every accumulate and solve launch) and "stab_warp"; a cut-detector step "cutdet"; a motion-blur call "mblur_pack" and "mblur_gather"; a correspondence-map step "cmap_step" and "cmap_render"; an object-detector step "objects_fit" (its stabiliser's launches), "objects_label" and "objects_assign"; a background-plate step "plate_fit" (its stabiliser's launches), "plate_block" and "plate_accumulate", its render "plate_render"; a defect-filter step "defect_detect" and "defect_apply"; a deflicker step "deflicker_fit" (every accumulate and field launch) and "deflicker_apply".  Events come from a per-context pool: none is created in a steady-state step. */
 int  eppm_enable_stage_timing(eppm_ctx* ctx, int on);
 
 const char* eppm_last_error(void);

@@ -22,6 +22,7 @@
 #   objects     the object detector: tools/objects_times.py on both libraries -> objects_times_{exact,tol}.json
 #   plate       the background plate: tools/plate_times.py on both libraries -> plate_times_{exact,tol}.json
 #   defect      the defect filter: tools/defect_times.py on both libraries -> defect_times_{exact,tol}.json
+#   deflicker   flicker removal: tools/deflicker_times.py on both libraries -> deflicker_times_{exact,tol}.json
 #   round       everything profiles/ of a round comes from (TAG=r04_x; PMC_ONLY=1, SKIP_TESTS=1)
 set -o pipefail
 R=${GRAFT_REPO_ROOT:-$(cd "$(dirname "$0")/.." && pwd)}
@@ -162,6 +163,11 @@ defect)
   cd $R; for l in exact tol; do
     timeout -k 10 ${DEFECT_TIMEOUT:-300} python tools/defect_times.py --lib $l ${DEFECT_ARGS} > $O/defect_times_$l.json || exit 1
     cut -c1-400 $O/defect_times_$l.json
+  done ;;
+deflicker)
+  cd $R; for l in exact tol; do
+    timeout -k 10 ${DEFLICKER_TIMEOUT:-300} python tools/deflicker_times.py --lib $l ${DEFLICKER_ARGS} > $O/deflicker_times_$l.json || exit 1
+    cut -c1-400 $O/deflicker_times_$l.json
   done ;;
 inflight)
   cd $R; for S in ${INFLIGHT:-1 2 3 4 6}; do

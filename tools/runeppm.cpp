@@ -45,6 +45,10 @@
 //                     line per frame: its index and the counts hit, grown, second_chance, undecided.  The first and the last frame of
 //                     the clip (and, with --auto-cut, of every shot) are written as they are.  --defect-thresh D A (defaults 60 30),
 //                     --defect-radius R (0 .. 4, default 3) and --defect-grow G (0 .. 4, default 1) set its parameters and imply it.
+//                     --deflicker: every pair runs the bidirectional call followed by one step of flicker removal (DESIGN.md section
+//                     24): frame k is corrected towards the corrected frame k - 1 by a gain and an offset per colour on a grid of cells.
+//                     The frames are written to P_fk_0000.ppm (the first frame itself), P_fk_0001.ppm ...  --flicker-cell N (16, 32 or
+//                     64, default 32) and --flicker-keep K (0 .. 1, default 1: how much of the correction is applied) imply it.
 //                     --stabilize: every pair runs the bidirectional call followed by one step of the stabiliser (DESIGN.md section 16:
 //                     the camera motion fitted to the forward flow, the frame re-rendered from the smoothed camera path); the frames are
 //                     written to P_st_0000.ppm (the first frame itself), P_st_0001.ppm ...  --smooth S (0 .. 1, default 0.9; 1: tripod
@@ -116,6 +120,9 @@ struct Options {
     int dn_frames = 8;                                      // --denoise-frames
     bool defects = false;                                   // --remove-defects
     eppm_defect_params df = {60.0f, 30.0f, 3, 1};           // --defect-thresh, --defect-radius, --defect-grow
+    bool deflicker = false;                                 // --deflicker
+    int fk_cell = 32;                                       // --flicker-cell
+    float fk_keep = 1.0f;                                   // --flicker-keep
     bool stabilize = false;                                 // --stabilize
     float smooth = 0.9f;                                    // --smooth
     bool auto_cut = false;                                  // --auto-cut
@@ -185,7 +192,8 @@ static int usage()
                     "               [--auto-cut] [--cut-lost N] [--motion-blur S] [--blur-radius R] [--blur-taps N]\n"
                     "               [--propagate layer.ppm alpha.ppm] [--objects] [--min-area N] [--max-objects N]\n"
                     "               [--plate] [--plate-margin MX MY] [--remove-objects]\n"
-                    "               [--remove-defects] [--defect-thresh D A] [--defect-radius R] [--defect-grow G]\n");
+                    "               [--remove-defects] [--defect-thresh D A] [--defect-radius R] [--defect-grow G]\n"
+                    "               [--deflicker] [--flicker-cell N] [--flicker-keep K]\n");
     return 2;
 }
 
@@ -228,6 +236,8 @@ static int run_sequence(const Options& o)
         ~DefectGuard() { eppm_defect_destroy(p); if (txt) fclose(txt); }
     } dfl;
     std::vector<unsigned char> df_rgb, df_mask;
+    struct DeflickerGuard { eppm_deflicker* p = nullptr; ~DeflickerGuard() { eppm_deflicker_destroy(p); } } dfk;       // freed on every way out
+    std::vector<unsigned char> fk_rgb;
     std::vector<std::vector<unsigned char>> ro_frames, ro_masks;          // --remove-objects: what the second pass needs of the first
     std::vector<std::vector<double>> ro_paths;
     FILE* cuts = nullptr;
@@ -256,6 +266,14 @@ static int run_sequence(const Options& o)
         df_mask.resize((size_t)h * w);
         snprintf(name, sizeof name, "%s_defects.txt", o.prefix);
         if (!(dfl.txt = fopen(name, "w"))) { fprintf(stderr, "cannot write %s\n", name); return fail("fopen"); }
+    }
+    if (o.deflicker) {
+        eppm_deflicker_params fp;
+        eppm_deflicker_default_params(&fp);
+        fp.cell = o.fk_cell;
+        fp.keep = o.fk_keep;
+        if (eppm_deflicker_create(ctx, &fp, &dfk.p) != EPPM_OK) return fail("eppm_deflicker_create");
+        fk_rgb.resize((size_t)h * w * 3);
     }
     // one frame of --remove-defects: the frame, its mask and its line of counts
     auto write_defects = [&](size_t frame, const unsigned char* rgb, const unsigned char* mask, const eppm_defect_stats& ds) {
@@ -339,6 +357,10 @@ static int run_sequence(const Options& o)
                 snprintf(name, sizeof name, "%s_dn_0000.ppm", o.prefix);
                 if (!write_ppm(name, cur.data(), h, w)) { fprintf(stderr, "cannot write %s\n", name); if (cuts) fclose(cuts); if (obf) fclose(obf); eppm_objects_destroy(od); eppm_cmap_destroy(cm); eppm_cutdet_destroy(det); eppm_stab_destroy(stab); eppm_tfilter_destroy(flt); eppm_destroy(ctx); return 1; }
             }
+            if (dfk.p) {
+                snprintf(name, sizeof name, "%s_fk_0000.ppm", o.prefix);
+                if (!write_ppm(name, cur.data(), h, w)) { fprintf(stderr, "cannot write %s\n", name); return fail("write"); }
+            }
             if (cm) {                  // the layer through the identity map: the first frame is its own anchor
                 std::vector<float> seed((size_t)h * w * 2);
                 for (int y = 0; y < h; y++)
@@ -359,7 +381,7 @@ static int run_sequence(const Options& o)
         if (k == 1) { if (eppm_set_images(ctx, img[0].data(), img[1].data(), (size_t)w * 3) != EPPM_OK) return fail("eppm_set_images"); }
         else if (eppm_push_image(ctx, cur.data(), (size_t)w * 3) != EPPM_OK) return fail("eppm_push_image");
         const bool last = k + 1 == o.seq.size();
-        if (!o.denoise && !o.stabilize && !o.auto_cut && !cm && !od && !plt.p && !dfl.p && !(o.mblur && last)) { if (eppm_compute(ctx, u.data(), v.data()) != EPPM_OK) return fail("eppm_compute"); }
+        if (!o.denoise && !o.stabilize && !o.auto_cut && !cm && !od && !plt.p && !dfl.p && !dfk.p && !(o.mblur && last)) { if (eppm_compute(ctx, u.data(), v.data()) != EPPM_OK) return fail("eppm_compute"); }
         else {
             if (eppm_compute_bidirectional(ctx, u.data(), v.data(), nullptr, nullptr, nullptr, nullptr) != EPPM_OK) return fail("eppm_compute_bidirectional");
             uint8_t cut = 0;
@@ -376,6 +398,12 @@ static int run_sequence(const Options& o)
             }
             if (o.denoise && eppm_tfilter_step(flt, ctx, o.auto_cut ? &cut : nullptr) != EPPM_OK) return fail("eppm_tfilter_step");
             if (o.stabilize && eppm_stab_step(stab, ctx, o.auto_cut ? &cut : nullptr) != EPPM_OK) return fail("eppm_stab_step");
+            if (dfk.p) {
+                if (eppm_deflicker_step(dfk.p, ctx, o.auto_cut ? &cut : nullptr) != EPPM_OK) return fail("eppm_deflicker_step");
+                if (eppm_deflicker_get(dfk.p, 0, fk_rgb.data(), (size_t)w * 3) != EPPM_OK) return fail("eppm_deflicker_get");
+                snprintf(name, sizeof name, "%s_fk_%04zu.ppm", o.prefix, k);
+                if (!write_ppm(name, fk_rgb.data(), h, w)) { fprintf(stderr, "cannot write %s\n", name); return fail("write"); }
+            }
             if (dfl.p) {                // the step of pair (k - 1, k) gives frame k - 1
                 eppm_defect_stats ds;
                 if (eppm_defect_step(dfl.p, ctx, o.auto_cut ? &cut : nullptr) != EPPM_OK) return fail("eppm_defect_step");
@@ -500,6 +528,8 @@ static int run_sequence(const Options& o)
     plt.p = nullptr;
     eppm_defect_destroy(dfl.p);
     dfl.p = nullptr;
+    eppm_deflicker_destroy(dfk.p);
+    dfk.p = nullptr;
     eppm_objects_destroy(od); eppm_cmap_destroy(cm); eppm_cutdet_destroy(det);
     eppm_stab_destroy(stab);
     eppm_tfilter_destroy(flt);
@@ -585,6 +615,15 @@ int main(int argc, char** argv)
         }
         else if (!strcmp(a, "--defect-radius")) { if (!val(&v) || v < 0 || v > 4) return usage(); o.df.radius = (int)v; o.defects = true; }
         else if (!strcmp(a, "--defect-grow")) { if (!val(&v) || v < 0 || v > 4) return usage(); o.df.grow = (int)v; o.defects = true; }
+        else if (!strcmp(a, "--deflicker")) o.deflicker = true;
+        else if (!strcmp(a, "--flicker-cell")) { if (!val(&v) || (v != 16 && v != 32 && v != 64)) return usage(); o.fk_cell = (int)v; o.deflicker = true; }
+        else if (!strcmp(a, "--flicker-keep")) {
+            if (i + 1 >= argc) return usage();
+            char* end = nullptr;
+            o.fk_keep = strtof(argv[++i], &end);
+            if (!end || end == argv[i] || *end || !(o.fk_keep >= 0.0f && o.fk_keep <= 1.0f)) return usage();
+            o.deflicker = true;
+        }
         else if (!strcmp(a, "--stabilize")) o.stabilize = true;
         else if (!strcmp(a, "--smooth")) {
             if (i + 1 >= argc) return usage();
@@ -621,7 +660,7 @@ int main(int argc, char** argv)
             return usage();
         return run_sequence(o);
     }
-    if (o.denoise || o.stabilize || o.auto_cut || o.pl_layer || o.objects || o.plate || o.defects) return usage();     // the filter, the stabiliser, the cut detector, the map and the object detector walk a clip
+    if (o.denoise || o.stabilize || o.auto_cut || o.pl_layer || o.objects || o.plate || o.defects || o.deflicker) return usage();     // the filter, the stabiliser, the cut detector, the map and the object detector walk a clip
     if ((o.mblur && !o.mblur_file) || (o.mb_set && !o.mblur)) return usage();
     if (pos.size() == 1 || pos.size() > 3) return usage();
     if (pos.size() >= 2) { o.f1 = pos[0]; o.f2 = pos[1]; }
