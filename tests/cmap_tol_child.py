@@ -23,10 +23,10 @@ def to_device(arr):
     return p
 
 
-def rgba(img, alpha=0x5a):
+def rgba(img, alpha=0x5a, pad=0):
     h, w, _ = img.shape
-    out = np.full((h, w, 4), alpha, np.uint8)           # the alpha byte of an input frame is ignored
-    out[..., :3] = img
+    out = np.full((h, w + pad, 4), alpha, np.uint8)     # the alpha byte of an input frame is ignored; pad: pixels beyond every row (the pitch)
+    out[:, :w, :3] = img
     return out
 
 
@@ -35,7 +35,8 @@ def device_step(c, runs=2):
     import eppm_amd
     from eppm_amd._lib import lib
     h, w = c["h"], c["w"]
-    planes = [to_device(rgba(c["img1"])), to_device(rgba(c["img2"])), to_device(np.stack([c["bu"], c["bv"]], -1).astype(np.float32)),
+    pad = c.get("pad", 0)
+    planes = [to_device(rgba(c["img1"], pad=pad)), to_device(rgba(c["img2"], pad=pad)), to_device(np.stack([c["bu"], c["bv"]], -1).astype(np.float32)),
               to_device(c["occ"])]
     cm = eppm_amd.CorrespondenceMap(None, size=(h, w), thresh=c["thresh"], tear=c["tear"], use_occ=c["use_occ"])
     out = []
@@ -46,7 +47,7 @@ def device_step(c, runs=2):
             else:
                 cm.set_state(0, c["map"], c["anchor"])
             cm.set_layer(None, 0)
-            cm.step_frames(0, planes[0].value, planes[1].value, w * 4, planes[2].value, planes[3].value, c["cut"])
+            cm.step_frames(0, planes[0].value, planes[1].value, (w + pad) * 4, planes[2].value, planes[3].value, c["cut"])
             got = cm.map(0)
             cm.set_layer(c["layer"], 0)
             out.append((got, cm.render(0), cm.age(0)))
@@ -70,11 +71,11 @@ def mismatches(cases):
 
 
 def main():
-    from test_cmap_cpu import cmap_cases          # (imports conftest, which selects the test library: overridden below, before anything is loaded)
+    from test_cmap_cpu import cmap_cases, cmap_limit_cases          # (imports conftest, which selects the test library: overridden below, before anything is loaded)
     import eppm_amd
     eppm_amd.select_library("tol")
     print(eppm_amd.lib().eppm_version().decode())
-    cases = cmap_cases()
+    cases = cmap_limit_cases() if sys.argv[1:2] == ["limit"] else cmap_cases()
     bad = mismatches(cases)
     print(f"{len(cases)} cases, {len(bad)} differ from the restatement: {bad[:5]}")
     assert not bad

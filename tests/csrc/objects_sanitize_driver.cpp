@@ -19,7 +19,10 @@ int main()
     const int ns = sizeof sp / sizeof *sp;
     long objects = 0, carried_px = 0, inherited = 0;
     for (int it = 0; it < 600; it++) {
-        const int h = 1 + rnd() % 9, w = 1 + rnd() % 9;
+        // the first iterations: thin frames at kObjMaxDim and one of 65 chunks, with backward vectors that end on the last column and row
+        // and just beyond them; then small random frames
+        static const int big[3][2] = {{20, kObjMaxDim}, {kObjMaxDim, 20}, {256, 257}};
+        const int h = it < 3 ? big[it][0] : 1 + rnd() % 9, w = it < 3 ? big[it][1] : 1 + rnd() % 9;
         const size_t px = (size_t)h * w;
         const int conn = it & 1 ? 4 : 8;
         const int min_area = it % 5 == 0 ? (int)px + 1 : 1 + rnd() % 4;
@@ -34,6 +37,10 @@ int main()
             bv[i] = rnd() % 3 ? (float)(rnd() % 17) / 2.0f - 4.0f : sp[rnd() % ns];
             occ[i] = rnd() % 5 ? 0 : (uint8_t)rnd();
             prev[i] = rnd() % 3 ? (uint8_t)(rnd() % 4) : (uint8_t)rnd();
+            if (it < 3 && rnd() % 4 == 0) {
+                bu[i] = (float)(w - 1 - (int)(i % w)) + (rnd() % 2 ? 0.0f : 0.001f);
+                bv[i] = (float)(h - 1 - (int)(i / w)) + (rnd() % 2 ? 0.0f : 0.001f);
+            }
         }
         std::vector<ObjRecord> rec(max_objects);
         ObjCounts cnt{0, 0, 0, 0};

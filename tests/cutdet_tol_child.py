@@ -75,9 +75,9 @@ def mismatches(cases):
 def main():
     import eppm_amd
     eppm_amd.select_library("tol")          # before anything loads a library
-    from test_cutdet_cpu import cutdet_cases
+    from test_cutdet_cpu import cutdet_cases, cutdet_limit_cases
     print(eppm_amd.lib().eppm_version().decode())
-    cases = cutdet_cases()
+    cases = cutdet_limit_cases() if sys.argv[1:2] == ["limit"] else cutdet_cases()
     bad = mismatches(cases)
     print(f"{len(cases)} cases, {len(bad)} differ from the restatement: {bad[:5]}")
     assert not bad

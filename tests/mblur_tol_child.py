@@ -75,9 +75,9 @@ def mismatches(cases, want="want"):
 def main():
     import eppm_amd
     eppm_amd.select_library("tol")          # before anything loads a library
-    from test_mblur_cpu import cases
+    from test_mblur_cpu import LIMIT_SIZES, cases
     print(eppm_amd.lib().eppm_version().decode())
-    cs = cases(GPU_SIZES)
+    cs = cases(LIMIT_SIZES if sys.argv[1:2] == ["limit"] else GPU_SIZES)
     bad = mismatches(cs)
     print(f"{len(cs)} cases, {len(bad)} differ from the restatement: {bad[:5]}")
     assert not bad

@@ -1,7 +1,8 @@
 """Child process of tests/test_objects_gpu.py, and the home of what both share: device_case() runs one case of objects_cases() through
 set_state (or reset) + eppm_objects_step_frames + get + get_labels + get_state on a context-less detector.  As a program it selects the
 tolerance library (the pytest process holds the exact test library), runs every case twice and expects the kernels to equal the numpy
-restatement in every number: the detector has no EPPM_TOL branch.  Prints the library's version first and "PART OK" last."""
+restatement in every number: the detector has no EPPM_TOL branch.  With the argument "large K" it runs objects_large_cases(K) instead.
+Prints the library's version first and "PART OK" last."""
 import ctypes as C
 import os
 import sys
@@ -88,11 +89,11 @@ def mismatches(cases):
 
 
 def main():
-    from test_objects_cpu import objects_cases          # (imports conftest, which selects the test library: overridden below, before anything is loaded)
+    from test_objects_cpu import objects_cases, objects_large_cases          # (imports conftest, which selects the test library: overridden below, before anything is loaded)
     import eppm_amd
     eppm_amd.select_library("tol")
     print(eppm_amd.lib().eppm_version().decode())
-    cases = objects_cases()
+    cases = objects_large_cases(int(sys.argv[2])) if sys.argv[1:2] == ["large"] else objects_cases()
     bad = mismatches(cases)
     print(f"{len(cases)} cases, {len(bad)} differ from the restatement: {bad[:3]}")
     assert not bad

@@ -33,14 +33,20 @@ def from_device(p, shape, dtype):
     return out
 
 
-def rgba_of(rgb):
-    return np.ascontiguousarray(np.concatenate([rgb, np.zeros(rgb.shape[:2] + (1,), np.uint8)], axis=2))
+def rgba_of(rgb, pad=0):
+    """the image as RGBA rows of (w + pad) words"""
+    h, w, _ = rgb.shape
+    out = np.zeros((h, w + pad, 4), np.uint8)
+    out[:, :w, :3] = rgb
+    return out
 
 
 def case_planes(c):
     """the device planes of a case: [image a, image b, mask, render output (RGBA words), fill bytes]"""
+    pad = c.get("pad", 0)                      # pixels beyond every row of the images and of the render's output: pitches larger than 4 * w
     px = c["h"] * c["w"]
-    return [to_device(rgba_of(c["img"])), to_device(rgba_of(c["img_b"])), to_device(c["mask"]), to_device(nbytes=px * 4), to_device(nbytes=px)]
+    return [to_device(rgba_of(c["img"], pad)), to_device(rgba_of(c["img_b"], pad)), to_device(c["mask"]), to_device(nbytes=c["h"] * (c["w"] + pad) * 4),
+            to_device(nbytes=px)]
 
 
 def free_planes(planes):
@@ -63,9 +69,10 @@ def load_case(pl, slot, c):
 def step_case(pl, slot, c, planes, k):
     """step k (0: image a with the case's path, 1: image b with the slot's own, which is that path), then the step's render"""
     h, w = c["h"], c["w"]
-    pl.step_frames(slot, planes[k].value, w * 4, planes[2].value, c["path"] if k == 0 else None)
-    pl.render_frames(slot, planes[k].value, w * 4, planes[2].value, None if k else c["path"], planes[3].value, w * 4, planes[4].value)
-    out = from_device(planes[3], (h, w, 4), np.uint8)
+    pitch = (w + c.get("pad", 0)) * 4
+    pl.step_frames(slot, planes[k].value, pitch, planes[2].value, c["path"] if k == 0 else None)
+    pl.render_frames(slot, planes[k].value, pitch, planes[2].value, None if k else c["path"], planes[3].value, pitch, planes[4].value)
+    out = from_device(planes[3], (h, pitch // 4, 4), np.uint8)[:, :w]
     assert (out[..., 3] == 255).all()
     return np.ascontiguousarray(out[..., :3]), from_device(planes[4], (h, w), np.uint8)
 
@@ -120,11 +127,14 @@ def mismatches(cases):
 
 
 def main():
-    from test_plate_cpu import plate_cases          # (imports conftest, which selects the test library: overridden below, before anything is loaded)
+    from test_plate_cpu import plate_cases, plate_limit_cases          # (imports conftest, which selects the test library: overridden below, before anything is loaded)
     import eppm_amd
     eppm_amd.select_library("tol")
     print(eppm_amd.lib().eppm_version().decode())
-    cases = plate_cases()
+    if sys.argv[1:2] == ["limit"]:          # three sizes from the one given
+        cases = [c for k in range(3) for c in plate_limit_cases(int(sys.argv[2]) + k)]
+    else:
+        cases = plate_cases()
     bad = mismatches(cases)
     print(f"{len(cases)} cases, {len(bad)} differ from the restatement: {bad[:3]}")
     assert not bad

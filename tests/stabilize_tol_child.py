@@ -23,10 +23,10 @@ def to_device(arr):
     return p
 
 
-def rgba(img, alpha=0x5a):
+def rgba(img, alpha=0x5a, pad=0):
     h, w, _ = img.shape
-    out = np.full((h, w, 4), alpha, np.uint8)           # the alpha byte of an input frame is ignored
-    out[..., :3] = img
+    out = np.full((h, w + pad, 4), alpha, np.uint8)     # the alpha byte of an input frame is ignored; pad: pixels beyond every row (the pitch)
+    out[:, :w, :3] = img
     return out
 
 
@@ -35,7 +35,8 @@ def device_step(c, runs=2):
     import eppm_amd
     from eppm_amd._lib import lib
     h, w = c["h"], c["w"]
-    planes = [to_device(rgba(c["img2"])), to_device(np.stack([c["u"], c["v"]], -1).astype(np.float32)), to_device(c["occ"])]
+    pad = c.get("pad", 0)
+    planes = [to_device(rgba(c["img2"], pad=pad)), to_device(np.stack([c["u"], c["v"]], -1).astype(np.float32)), to_device(c["occ"])]
     stab = eppm_amd.Stabilizer(None, c["tau"], c["iters"], c["smooth"], size=(h, w))
     out = []
     try:
@@ -44,7 +45,7 @@ def device_step(c, runs=2):
                 stab.reset(0)
             else:
                 stab.set_path(0, *c["path"])
-            stab.step_frames(0, planes[0].value, w * 4, planes[1].value, planes[2].value, c["cut"])
+            stab.step_frames(0, planes[0].value, (w + pad) * 4, planes[1].value, planes[2].value, c["cut"])
             cc, ss, counts = stab.path(0, counts=True)
             out.append(dict(model=stab.model(0), mask=stab.mask(0), C=cc, S=ss, counts=counts, rgb=stab.frame(0)))
     finally:
@@ -68,9 +69,9 @@ def mismatches(cases):
 def main():
     import eppm_amd
     eppm_amd.select_library("tol")          # before anything loads a library
-    from test_stabilize_cpu import stab_cases
+    from test_stabilize_cpu import stab_cases, stab_limit_cases
     print(eppm_amd.lib().eppm_version().decode())
-    cases = stab_cases()
+    cases = stab_limit_cases() if sys.argv[1:2] == ["limit"] else stab_cases()
     bad = mismatches(cases)
     print(f"{len(cases)} cases, {len(bad)} differ from the restatement: {bad[:5]}")
     assert not bad

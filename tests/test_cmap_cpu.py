@@ -289,6 +289,25 @@ def cmap_cases():
     return _CASES
 
 
+# Thin frames at kGmMaxDim: map values and bilinear taps at coordinate 8191, vectors that end on the last column / row and one ulp beyond
+# them, 32 KiB image rows; pad: pixels beyond every row of the caller's images
+LIMIT_SIZES = [(8192, 20), (20, 8192)]
+LIMIT_CONFIGS = [CONFIGS[k] for k in (0, 1, 2, 5, 7)]
+_LIMIT = None
+
+
+def cmap_limit_cases():
+    global _LIMIT
+    if _LIMIT is None:
+        _LIMIT = [dict(_case(88000 + 10 * i + j, w, h, *cfg), pad=(0, 3, 64)[j % 3]) for i, (w, h) in enumerate(LIMIT_SIZES)
+                  for j, cfg in enumerate(LIMIT_CONFIGS)]
+        for c in _LIMIT:
+            for v in c.values():
+                if isinstance(v, np.ndarray):
+                    v.setflags(write=False)
+    return _LIMIT
+
+
 def host_step(c):
     """case c through the host forms: (map, bytes)"""
     m = io.cmap_step_host(None if c["prev"] == "empty" else c["map"], c["anchor"], c["img2"], c["bu"], c["bv"], c["occ"], c["thresh"], c["tear"],
@@ -312,6 +331,25 @@ def test_numpy_restatement_equals_the_host_forms(size):
             again = io.cmap_step_host(np_seed(c["h"], c["w"]), c["anchor"], c["img2"], c["bu"], c["bv"], c["occ"], c["thresh"], c["tear"],
                                       c["use_occ"], c["cut"])
             assert same_bits(again, got)
+
+
+@pytest.mark.parametrize("size", range(len(LIMIT_SIZES)), ids=[f"{w}x{h}" for w, h in LIMIT_SIZES])
+def test_numpy_restatement_equals_the_host_forms_at_the_size_limit(size):
+    from test_tfilter_cpu import ends_reached
+    w, h = LIMIT_SIZES[size]
+    src = open(os.path.join(ROOT, "eppm_amd", "csrc", "gmotion.h")).read()
+    assert max(w, h) == int(re.search(r"constexpr int kGmMaxDim = (\d+);", src).group(1))
+    cases = [c for c in cmap_limit_cases() if (c["w"], c["h"]) == (w, h)]
+    assert len(cases) == len(LIMIT_CONFIGS) and {c["pad"] for c in cases} == {0, 3, 64}
+    for c in cases:
+        got, rgb = host_step(c)
+        assert same_bits(got, c["want_map"]), c["name"]
+        assert np.array_equal(rgb, c["want_rgb"]), c["name"]
+        for axis, reached in ends_reached(c["bu"], c["bv"]).items():
+            assert all(reached.values()), (c["name"], axis, reached)
+        known = np_known(c["want_map"][..., 0], c["want_map"][..., 1])
+        far = c["want_map"][..., 0 if w > h else 1][known]
+        assert far.max() > max(w, h) - 2 and far.min() < 1, c["name"]          # the composed map still points at both ends of the long side
 
 
 def test_seed_and_default_layer():

@@ -10,7 +10,7 @@ import numpy as np
 import pytest
 
 from conftest import ROOT
-from test_cmap_cpu import SIZES, cmap_cases, host_step, np_known, np_seed
+from test_cmap_cpu import LIMIT_SIZES, SIZES, cmap_cases, cmap_limit_cases, host_step, np_known, np_seed
 from test_tfilter_cpu import moving_clip, same_bits
 from cmap_tol_child import mismatches, to_device
 
@@ -47,6 +47,22 @@ def test_kernels_equal_the_host_forms(size):
     c = cases[1]                                  # and against the host forms directly
     got, rgb = host_step(c)
     assert same_bits(got, c["want_map"]) and np.array_equal(rgb, c["want_rgb"])
+
+
+@pytest.mark.parametrize("size", range(len(LIMIT_SIZES)), ids=[f"{w}x{h}" for w, h in LIMIT_SIZES])
+def test_kernels_equal_the_host_forms_at_the_size_limit(size):
+    """thin frames 8192 long: map values and taps at coordinate 8191, vectors that end on the last column / row and one ulp beyond them,
+    the caller's images under a pitch larger than 4 * w"""
+    cases = [c for c in cmap_limit_cases() if (c["w"], c["h"]) == LIMIT_SIZES[size]]
+    assert len(cases) >= 3
+    bad = mismatches(cases)
+    assert not bad, bad
+
+
+def test_tolerance_library_at_the_size_limit():
+    out = subprocess.run([sys.executable, os.path.join(ROOT, "tests", "cmap_tol_child.py"), "limit"], capture_output=True, text=True, timeout=600)
+    assert out.returncode == 0 and out.stdout.strip().endswith("PART OK"), out.stdout[-2000:] + out.stderr[-2000:]
+    assert "tolerance arithmetic" in out.stdout.splitlines()[0]
 
 
 # ---- 6. the context form ----

@@ -139,10 +139,25 @@ def _threshold_case(extra, sides):
 
 @functools.lru_cache(maxsize=None)
 def _cases():
+    return _build(tuple(SIZES), tuple(CONFIGS), 17, True)
+
+
+# Thin frames at kCutMaxDim: 128 x 2 and 1 x 512 tiles, so 256 and 512 slabs under the finish kernel's 64 lanes (four and eight trips of
+# its loop), taps at coordinate 8191, the largest sums of a thin frame (black against white)
+LIMIT_SIZES = [(8192, 20), (20, 8192)]
+LIMIT_CONFIGS = [CONFIGS[k] for k in (0, 2, 3, 4, 8, 9)]
+
+
+def cutdet_limit_cases():
+    return list(_build(tuple(LIMIT_SIZES), tuple(LIMIT_CONFIGS), 5017, False))
+
+
+@functools.lru_cache(maxsize=None)
+def _build(sizes, configs, seed, thresholds):
     out = []
-    for si, (w, h) in enumerate(SIZES):
-        for ci, (flow, masks, i1, i2, permille, rmax) in enumerate(CONFIGS):
-            rng = np.random.default_rng(1000 * si + ci + 17)
+    for si, (w, h) in enumerate(sizes):
+        for ci, (flow, masks, i1, i2, permille, rmax) in enumerate(configs):
+            rng = np.random.default_rng(1000 * si + ci + seed)
             if flow == "mixed":
                 bu, bv = _mixed_flow(rng, h, w)
             else:
@@ -150,7 +165,8 @@ def _cases():
             out.append(dict(name=f"{w}x{h}-{ci}", h=h, w=w, img1=_image(rng, h, w, i1), img2=_image(rng, h, w, i2), bu=bu, bv=bv,
                             occ1=_masks(rng, h, w, masks), occ2=_masks(rng, h, w, masks), lost_permille=permille, residual_max=rmax,
                             uniform=masks != "random", threshold=None))
-    out += [_threshold_case(0, 3), _threshold_case(1, 3), _threshold_case(1, 1), _threshold_case(1, 2)]
+    if thresholds:
+        out += [_threshold_case(0, 3), _threshold_case(1, 3), _threshold_case(1, 1), _threshold_case(1, 2)]
     for c in out:
         for a in c.values():
             if isinstance(a, np.ndarray):
@@ -181,6 +197,26 @@ def test_host_form_equals_the_restatement(size):
     for c in cases:
         d = differences(c["want"], host_record(c))
         assert not d, (c["name"], d)
+
+
+@pytest.mark.parametrize("size", range(len(LIMIT_SIZES)), ids=[f"{w}x{h}" for w, h in LIMIT_SIZES])
+def test_host_form_equals_the_restatement_at_the_size_limit(size):
+    w, h = LIMIT_SIZES[size]
+    src = open(os.path.join(ROOT, "eppm_amd", "csrc", "cutdet.h")).read()
+    assert max(w, h) == int(re.search(r"constexpr int kCutMaxDim = (\d+);", src).group(1))
+    cases = [c for c in cutdet_limit_cases() if (c["w"], c["h"]) == (w, h)]
+    assert len(cases) == len(LIMIT_CONFIGS)
+    for c in cases:
+        d = differences(c["want"], host_record(c))
+        assert not d, (c["name"], d)
+    assert {bool(c["want"]["cut"]) for c in cases} == {False, True}
+    assert max(c["want"]["sad"] for c in cases) == 255 * h * w          # black against white, every pixel tracked: the luma difference is 255
+    ys, xs = np.mgrid[0:h, 0:w]
+    for c in cases[:1]:                               # the mixed field: targets exactly on the last column and row and one ulp beyond them
+        with np.errstate(all="ignore"):
+            qx, qy = xs.astype(F) + c["bu"], ys.astype(F) + c["bv"]
+        for q, n in ((qx, w), (qy, h)):
+            assert (q == F(n - 1)).any() and ((q > F(n - 1)) & (q < F(n))).any() and (q == 0).any()
 
 
 def test_the_cases_cover_what_they_claim():

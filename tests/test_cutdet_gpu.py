@@ -11,7 +11,7 @@ import pytest
 
 from conftest import ROOT
 from cutdet_tol_child import mismatches
-from test_cutdet_cpu import FIELDS, SIZES, cutdet_cases, differences
+from test_cutdet_cpu import FIELDS, LIMIT_SIZES, SIZES, cutdet_cases, cutdet_limit_cases, differences
 from test_stabilize_cpu import band_limited, moving_clip
 
 pytestmark = pytest.mark.gpu
@@ -40,6 +40,22 @@ def test_kernels_equal_the_restatement(size):
     cases = [c for c in cutdet_cases() if (c["w"], c["h"]) == SIZES[size]]
     bad = mismatches(cases)
     assert not bad, bad
+
+
+@pytest.mark.parametrize("size", range(len(LIMIT_SIZES)), ids=[f"{w}x{h}" for w, h in LIMIT_SIZES])
+def test_kernels_equal_the_restatement_at_the_size_limit(size):
+    """thin frames 8192 long: 256 and 512 slabs under the finish kernel's 64 lanes, taps at coordinate 8191, 32 KiB image rows under a
+    pitch of (w + 8) words"""
+    cases = [c for c in cutdet_limit_cases() if (c["w"], c["h"]) == LIMIT_SIZES[size]]
+    assert len(cases) >= 3
+    bad = mismatches(cases)
+    assert not bad, bad
+
+
+def test_tolerance_library_at_the_size_limit():
+    out = subprocess.run([sys.executable, os.path.join(ROOT, "tests", "cutdet_tol_child.py"), "limit"], capture_output=True, text=True, timeout=600)
+    assert out.returncode == 0 and out.stdout.strip().endswith("PART OK"), out.stdout[-2000:] + out.stderr[-2000:]
+    assert "tolerance arithmetic" in out.stdout.splitlines()[0]
 
 
 def test_tolerance_library_runs_the_same_arithmetic():

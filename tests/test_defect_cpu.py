@@ -6,6 +6,7 @@ import os
 import re
 
 import numpy as np
+import pytest
 
 from conftest import ROOT
 import eppm_amd
@@ -232,6 +233,28 @@ def defect_cases():
     return _CASES
 
 
+# Thin frames 8192 long: section 16's bound, which the objects chained with the filter obey (its own check, h*w < 2^31, lies far beyond):
+# taps and median windows at coordinate 8191, 32 KiB image rows; pad: pixels beyond every row of the caller's images
+LIMIT_SIZES = [(8192, 20), (20, 8192)]
+_LIMIT = {}
+
+
+def defect_limit_cases(size=None):
+    """the cases of LIMIT_SIZES[size], or of both sizes; built on first use"""
+    if size is None:
+        return defect_limit_cases(0) + defect_limit_cases(1)
+    if size not in _LIMIT:
+        w, h = LIMIT_SIZES[size]
+        cases = [_random_case(66000 + 10 * size + j, w, h, *RANDOM[k]) for j, k in enumerate((0, 1, 5))]
+        cases += [_planted_case(66500 + 10 * size + j, w, h, *PLANTED[k]) for j, k in enumerate((0, 1))]
+        _LIMIT[size] = [dict(_finish(c), pad=(0, 3, 64)[j % 3]) for j, c in enumerate(cases)]
+        for c in _LIMIT[size]:
+            for v in c.values():
+                if isinstance(v, np.ndarray):
+                    v.setflags(write=False)
+    return _LIMIT[size]
+
+
 def host_step(c):
     return io.defect_step_host(c["prev"], c["cur"], c["next"], c["bu"], c["bv"], c["fu"], c["fv"], **c["params"])
 
@@ -353,6 +376,25 @@ def test_host_form_equals_the_restatement_byte_for_byte():
         assert np.array_equal(mask, c["want_mask"]), (c["name"], int((mask != c["want_mask"]).sum()))
         assert np.array_equal(rgb, c["want_rgb"]), (c["name"], int((rgb != c["want_rgb"]).any(axis=-1).sum()))
         assert stats == c["want_stats"], (c["name"], stats, c["want_stats"])
+
+
+@pytest.mark.parametrize("size", range(len(LIMIT_SIZES)), ids=[f"{w}x{h}" for w, h in LIMIT_SIZES])
+def test_host_form_equals_the_restatement_at_the_size_limit(size):
+    from test_tfilter_cpu import ends_reached
+    cases = defect_limit_cases(size)
+    assert {(c["w"], c["h"]) for c in cases} == {LIMIT_SIZES[size]} and {c["pad"] for c in cases} == {0, 3, 64}
+    for c in cases:
+        rgb, mask, stats = host_step(c)
+        assert np.array_equal(mask, c["want_mask"]), (c["name"], int((mask != c["want_mask"]).sum()))
+        assert np.array_equal(rgb, c["want_rgb"]), (c["name"], int((rgb != c["want_rgb"]).any(axis=-1).sum()))
+        assert stats == c["want_stats"], (c["name"], stats, c["want_stats"])
+        if not c["planted"]:
+            for u, v in ((c["bu"], c["bv"]), (c["fu"], c["fv"])):
+                for axis, reached in ends_reached(u, v).items():
+                    assert all(reached.values()), (c["name"], axis, reached)
+        elif c["params"]["radius"] > 0:                # repairs in the first and the last columns and rows
+            m = c["want_mask"] != 0
+            assert m[:, :4].any() and m[:, -4:].any() and m[:4].any() and m[-4:].any(), c["name"]
 
 
 def test_cases_cover_every_size_and_parameter():

@@ -13,7 +13,7 @@ import pytest
 from conftest import ROOT
 from alloc_fill_child import CLIP_H, CLIP_W, DevMem, across_fills, clip, pair_inputs, put, status_of
 from defect_tol_child import bits, device_step, mismatches
-from test_defect_cpu import DEFAULTS, SIZES, _smooth, blotch_clip, clip_quality, defect_cases, host_step, np_step, psnr
+from test_defect_cpu import DEFAULTS, LIMIT_SIZES, SIZES, defect_limit_cases, _smooth, blotch_clip, clip_quality, defect_cases, host_step, np_step, psnr
 from tfilter_tol_child import rgba, to_device
 
 pytestmark = pytest.mark.gpu
@@ -40,6 +40,21 @@ def test_kernels_equal_the_host_form(size):
     bad = mismatches(cases, want=host_step)
     assert not bad, bad[:5]
     assert not mismatches(cases[:2])              # and the restatement's, directly
+
+
+@pytest.mark.parametrize("size", range(len(LIMIT_SIZES)), ids=[f"{w}x{h}" for w, h in LIMIT_SIZES])
+def test_kernels_equal_the_host_form_at_the_size_limit(size):
+    """thin frames 8192 long: taps and median windows at coordinate 8191, vectors that end on the last column / row and one ulp beyond
+    them, the caller's images under a pitch larger than 4 * w"""
+    bad = mismatches(defect_limit_cases(size))
+    assert not bad, bad
+
+
+@pytest.mark.parametrize("size", range(len(LIMIT_SIZES)), ids=[f"{w}x{h}" for w, h in LIMIT_SIZES])
+def test_tolerance_library_at_the_size_limit(size):
+    out = subprocess.run([sys.executable, os.path.join(ROOT, "tests", "defect_tol_child.py"), "limit", str(size)], capture_output=True, text=True, timeout=600)
+    assert out.returncode == 0 and out.stdout.strip().endswith("PART OK"), out.stdout[-2000:] + out.stderr[-2000:]
+    assert "tolerance arithmetic" in out.stdout.splitlines()[0]
 
 
 def test_tolerance_library_runs_the_same_arithmetic():

@@ -215,6 +215,21 @@ def deflicker_cases():
     return out
 
 
+# Thin frames 8192 long: section 16's bound, which the objects chained with this one obey (its own check, h*w < 2^31, lies far beyond),
+# at every cell size: grids of 512 / 256 / 128 cells by 2 / 1 / 1, and the same turned; pad: pixels beyond every row of the caller's images
+LIMIT_SIZES = [(8192, 20), (20, 8192)]
+LIMIT_CELLS = (16, 32, 64)
+_LIMIT = None
+
+
+def deflicker_limit_cases():
+    global _LIMIT
+    if _LIMIT is None:
+        _LIMIT = [dict(_case(7000 + 10 * i + j, w, h, dict(cell=cell), empty=j == 2), pad=(0, 3, 64)[j]) for i, (w, h) in enumerate(LIMIT_SIZES)
+                  for j, cell in enumerate(LIMIT_CELLS)]
+    return _LIMIT
+
+
 def host_case(c, ref=None):
     r = ref if ref is not None else (c["img1"] if c["empty"] else c["ref"])
     return io.deflicker_step_host(r, c["cur"], c["bu"], c["bv"], c["occ2"], cut=c["cut"], **c["params"])
@@ -307,6 +322,24 @@ def test_host_form_equals_the_restatement_bit_for_bit():
         assert same(got, want), c["name"]
         again = np_case(c, ref=want[0])             # the second step of the GPU tests: the output is the next reference
         assert same(host_case(c, ref=want[0]), again), c["name"] + " (second step)"
+
+
+@pytest.mark.parametrize("size", range(len(LIMIT_SIZES)), ids=[f"{w}x{h}" for w, h in LIMIT_SIZES])
+def test_host_form_equals_the_restatement_at_the_size_limit(size):
+    from test_tfilter_cpu import ends_reached
+    w, h = LIMIT_SIZES[size]
+    cases = [c for c in deflicker_limit_cases() if (c["w"], c["h"]) == (w, h)]
+    assert [c["params"]["cell"] for c in cases] == list(LIMIT_CELLS) and {c["pad"] for c in cases} == {0, 3, 64}
+    for c in cases:
+        want, got = np_case(c), host_case(c)
+        assert same(got, want), c["name"]
+        assert same(host_case(c, ref=want[0]), np_case(c, ref=want[0])), c["name"] + " (second step)"
+        cell = c["params"]["cell"]
+        assert want[3]["cells"] == (-(-w // cell)) * (-(-h // cell)) and max(-(-w // cell), -(-h // cell)) == 8192 // cell
+        assert 0 < want[3]["valid_cells"] < want[3]["cells"], (c["name"], want[3])
+        assert want[2].reshape(-(-h // cell), -(-w // cell))[-1, -2:].any() or want[2].reshape(-(-h // cell), -(-w // cell))[-2:, -1].any(), c["name"]
+        for axis, reached in ends_reached(c["bu"], c["bv"]).items():
+            assert reached["last"] and reached["beyond"] and reached["zero"], (c["name"], axis, reached)
 
 
 def test_cases_cover_every_size_and_parameter():

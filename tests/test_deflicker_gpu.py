@@ -10,7 +10,7 @@ import numpy as np
 import pytest
 
 from conftest import ROOT
-from test_deflicker_cpu import DEFAULTS, SIZES, deflicker_cases, flicker_clip, np_case, np_step, psnr, same
+from test_deflicker_cpu import DEFAULTS, LIMIT_SIZES, SIZES, deflicker_cases, deflicker_limit_cases, flicker_clip, np_case, np_step, psnr, same
 from test_tfilter_cpu import moving_clip
 from deflicker_tol_child import case_planes, mismatches, read, rgba, to_device
 
@@ -52,6 +52,24 @@ def test_kernels_equal_the_restatement(size):
     cases = [c for c in deflicker_cases() if (c["w"], c["h"]) == SIZES[size]]
     bad = mismatches(cases)
     assert not bad, bad
+
+
+@pytest.mark.parametrize("size", range(len(LIMIT_SIZES)), ids=[f"{w}x{h}" for w, h in LIMIT_SIZES])
+def test_kernels_equal_the_restatement_at_the_size_limit(size):
+    """thin frames 8192 long at cell 16, 32 and 64: grids 512, 256 and 128 cells long (the field kernel's cells over more than one block),
+    taps at coordinate 8191, the caller's images under a pitch larger than 4 * w; two consecutive steps"""
+    cases = [c for c in deflicker_limit_cases() if (c["w"], c["h"]) == LIMIT_SIZES[size]]
+    assert len(cases) >= 3
+    bad = mismatches(cases)
+    assert not bad, bad
+
+
+@pytest.mark.parametrize("size", range(len(LIMIT_SIZES)), ids=[f"{w}x{h}" for w, h in LIMIT_SIZES])
+def test_tolerance_library_at_the_size_limit(size):
+    out = subprocess.run([sys.executable, os.path.join(ROOT, "tests", "deflicker_tol_child.py"), "limit", str(size)], capture_output=True, text=True,
+                         timeout=600)
+    assert out.returncode == 0 and out.stdout.strip().endswith("PART OK"), out.stdout[-2000:] + out.stderr[-2000:]
+    assert "tolerance arithmetic" in out.stdout.splitlines()[0]
 
 
 def test_tolerance_library_runs_the_same_arithmetic_and_removes_flicker_on_its_own_flows():

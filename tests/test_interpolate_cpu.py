@@ -250,6 +250,70 @@ def block_edge_cases():
     return cases
 
 
+# (w, h) thin frames 8192 long: section 16's bound, which the objects fed from the same planes obey (the caller-plane form's
+# own check is h*w < 2^31): splats at coordinate 8191, fill walks along a whole row or column of 8192, 32 KiB image rows
+LIMIT_SIZES = ((8192, 20), (20, 8192))
+LIMIT_TIMES = (1e-7, 0.5, 0.7)
+_LIMIT = {}
+
+
+def limit_cases(size):
+    """the cases of LIMIT_SIZES[size], built on first use (not at import): a smooth flow with the special values; vectors that leave the
+    frame by a fraction of a pixel at both ends of the long side and land exactly on its last pixel; a single known vector in the first
+    and in the last pixel (the fill passes walk the whole long side)"""
+    if size not in _LIMIT:
+        w, h = LIMIT_SIZES[size]
+        rng = np.random.default_rng(31 + size)
+        img = lambda: rng.integers(0, 256, (h, w, 3), dtype=np.uint8)                        # noqa: E731
+        occ = lambda: rng.choice(np.array([0, 0, 0, 1, 2, 3], np.uint8), (h, w))              # noqa: E731
+        cases = []
+        add = lambda name, u, v: cases.append((f"{name}_{w}x{h}", img(), img(), u, v, occ(), occ()))   # noqa: E731
+        u, v = smooth_flow(rng, h, w, 3.0)
+        for a in (u, v):
+            idx = rng.choice(a.size, 200, replace=False)
+            a.reshape(-1)[idx[:100]] = np.nan
+            a.reshape(-1)[idx[100:]] = 1e10 * rng.choice([-1, 1], 100)
+        u[h - 1, w - 3:] = 1e9
+        add("limit_random", u, v)
+        ys, xs = np.mgrid[0:h, 0:w].astype(np.float32)
+        along, n = (xs, w) if w > h else (ys, h)
+        f = rng.uniform(-1.5, 1.5, (h, w)).astype(np.float32)
+        near, far = along < 64, along >= n - 64
+        f[near] = (-along - np.float32(0.25) * rng.integers(-2, 3, (h, w)))[near]              # ends within half a pixel of coordinate 0 ...
+        f[far] = (np.float32(n - 1) - along + np.float32(0.25) * rng.integers(-2, 3, (h, w)))[far]          # ... and of the last one
+        g = rng.uniform(-0.5, 0.5, (h, w)).astype(np.float32)
+        add("limit_ends", *((f, g) if w > h else (g, f)))
+        nan = np.full((h, w), np.nan, np.float32)
+        u, v = nan.copy(), nan.copy()
+        u[0, 0], v[0, 0] = 1.5, 0.75
+        add("limit_corner_only", u, v)
+        u, v = nan.copy(), nan.copy()
+        u[h - 1, w - 1], v[h - 1, w - 1] = -1.5, -0.75
+        add("limit_far_corner_only", u, v)
+        _LIMIT[size] = cases
+    return _LIMIT[size]
+
+
+@pytest.mark.parametrize("size", range(len(LIMIT_SIZES)), ids=[f"{w}x{h}" for w, h in LIMIT_SIZES])
+def test_host_form_equals_numpy_restatement_at_the_size_limit(size):
+    w, h = LIMIT_SIZES[size]
+    for name, a, b, u, v, o1, o2 in limit_cases(size):
+        for t in LIMIT_TIMES:
+            parts = {}
+            want = interpolate_np(a, b, u, v, o1, o2, t, parts)
+            got = io.interpolate(a, b, u, v, o1, o2, t)
+            bad = int((got != want).any(-1).sum())
+            assert bad == 0, f"{name} t={t}: {bad} of {u.size} pixels differ"
+            splat = parts["splat"]
+            if name.startswith("limit_ends") and t == 0.5:          # splats on the first and the last pixels of the long side
+                line = splat.any(axis=0 if w > h else 1)
+                assert line[0] and line[-1], name
+            if "corner_only" in name:                               # one splat: pass 1 fills its row and column, pass 2 everything else
+                assert 0 < splat.sum() <= 4 and (parts["f1"] < 0).any() and (parts["f2"] >= 0).all(), name
+                src = int(np.nonzero(np.isfinite(u).ravel())[0][0])
+                assert (parts["f2"] == src).all(), name
+
+
 @pytest.mark.parametrize("case", interpolation_cases(), ids=lambda c: c[0])
 def test_host_form_equals_numpy_restatement(case):
     name, a, b, u, v, o1, o2 = case

@@ -11,7 +11,7 @@ import numpy as np
 import pytest
 
 from conftest import GOLDEN, ROOT
-from test_interpolate_cpu import interpolation_cases
+from test_interpolate_cpu import LIMIT_SIZES, LIMIT_TIMES, interpolation_cases, limit_cases
 
 pytestmark = pytest.mark.gpu
 
@@ -33,29 +33,30 @@ def _dev(arr):
     return p
 
 
-def rgba(img, fill=0):
+def rgba(img, fill=0, pad=0):
     h, w, _ = img.shape
-    out = np.full((h, w, 4), fill, np.uint8)
-    out[..., :3] = img
+    out = np.full((h, w + pad, 4), fill, np.uint8)
+    out[:, :w, :3] = img
     return out
 
 
-def frames_kernel(img1, img2, u, v, o1, o2, times):
-    """eppm_interpolate_frames (the kernels alone on caller planes) at each time; (h, w, 3) RGB of the RGBA outputs (alpha checked 255)."""
+def frames_kernel(img1, img2, u, v, o1, o2, times, pad=0, opad=0):
+    """eppm_interpolate_frames (the kernels alone on caller planes) at each time; (h, w, 3) RGB of the RGBA outputs (alpha checked 255).
+    pad, opad: pixels beyond every row of the input images and of the output (pitches larger than 4 * w); the output's must stay as it was."""
     from eppm_amd._lib import check, lib
     L = lib()
     h, w = u.shape
-    bufs = [_dev(rgba(img1, 7)), _dev(rgba(img2, 9)), _dev(np.ascontiguousarray(np.stack([u, v], -1), np.float32)),
-            _dev(np.ascontiguousarray(o1)), _dev(np.ascontiguousarray(o2)), _dev(np.zeros((h, w, 4), np.uint8))]
+    bufs = [_dev(rgba(img1, 7, pad)), _dev(rgba(img2, 9, pad)), _dev(np.ascontiguousarray(np.stack([u, v], -1), np.float32)),
+            _dev(np.ascontiguousarray(o1)), _dev(np.ascontiguousarray(o2)), _dev(np.full((h, w + opad, 4), 0x5a, np.uint8))]
     out = []
     try:
         for t in times:
-            check(L.eppm_interpolate_frames(bufs[5], C.c_size_t(w * 4), bufs[0], bufs[1], C.c_size_t(w * 4), bufs[2], bufs[3], bufs[4], h, w,
-                                            C.c_float(t)), "eppm_interpolate_frames")
-            r = np.empty((h, w, 4), np.uint8)
+            check(L.eppm_interpolate_frames(bufs[5], C.c_size_t((w + opad) * 4), bufs[0], bufs[1], C.c_size_t((w + pad) * 4), bufs[2], bufs[3], bufs[4],
+                                            h, w, C.c_float(t)), "eppm_interpolate_frames")
+            r = np.empty((h, w + opad, 4), np.uint8)
             check(L.eppm_memcpy_d2h(r.ctypes.data_as(C.c_void_p), bufs[5], C.c_size_t(r.nbytes)), "d2h")
-            assert (r[..., 3] == 255).all()
-            out.append(r[..., :3].copy())
+            assert (r[:, :w, 3] == 255).all() and (r[:, w:] == 0x5a).all()
+            out.append(r[:, :w, :3].copy())
     finally:
         for p in bufs:
             L.eppm_free_device(p)
@@ -71,6 +72,46 @@ def _check_kernel_cases(cases, times=TIMES):
 
 def test_kernels_equal_host_form_on_the_cpu_cases():
     _check_kernel_cases(interpolation_cases())
+
+
+@pytest.mark.parametrize("size", range(len(LIMIT_SIZES)), ids=[f"{w}x{h}" for w, h in LIMIT_SIZES])
+def test_kernels_equal_host_form_at_the_size_limit(size):
+    """thin frames 8192 long: splats at coordinate 8191, vectors that leave the frame by a fraction of a pixel at both ends, fill walks
+    along the whole long side, the images and the output under pitches larger than 4 * w"""
+    from eppm_amd import io
+    for k, (name, a, b, u, v, o1, o2) in enumerate(limit_cases(size)):
+        got = frames_kernel(a, b, u, v, o1, o2, LIMIT_TIMES, pad=(3, 64, 0, 5)[k], opad=(64, 0, 3, 1)[k])
+        for t, g in zip(LIMIT_TIMES, got):
+            same(g, io.interpolate(a, b, u, v, o1, o2, t), f"{name} t={t}")
+
+
+TOL_LIMIT_CHILD = r"""
+import sys
+import numpy as np
+sys.path.insert(0, %r)
+import conftest          # (selects the test library: overridden below, before anything is loaded)
+import eppm_amd
+eppm_amd.select_library("tol")
+from test_interpolate_cpu import LIMIT_TIMES, interpolate_np, limit_cases
+from test_interpolate_gpu import frames_kernel
+print(eppm_amd.lib().eppm_version().decode())
+bad = []
+for name, a, b, u, v, o1, o2 in limit_cases(int(sys.argv[1])):
+    for t, g in zip(LIMIT_TIMES, frames_kernel(a, b, u, v, o1, o2, LIMIT_TIMES, pad=3, opad=5)):
+        n = int((g != interpolate_np(a, b, u, v, o1, o2, t)).any(-1).sum())
+        if n:
+            bad.append((name, t, n))
+print(len(bad), "differ from the restatement:", bad[:5])
+assert not bad
+print("PART OK")
+""" % os.path.join(ROOT, "tests")
+
+
+@pytest.mark.parametrize("size", range(len(LIMIT_SIZES)), ids=[f"{w}x{h}" for w, h in LIMIT_SIZES])
+def test_tolerance_library_at_the_size_limit(size):
+    out = subprocess.run([sys.executable, "-c", TOL_LIMIT_CHILD, str(size)], capture_output=True, text=True, timeout=600)
+    assert out.returncode == 0 and out.stdout.strip().endswith("PART OK"), out.stdout[-2000:] + out.stderr[-2000:]
+    assert "tolerance arithmetic" in out.stdout.splitlines()[0]
 
 
 def _bidir(a, b):

@@ -92,6 +92,11 @@ GRID = [(0.5, 16, 8), (1.0, 31, 32), (0.25, 1, 1), (1.0, 16, 1), (0.5, 31, 8), (
         (1.0, 16, 32), (0.25, 31, 8), (0.5, 1, 1)]
 
 
+# (h, w) thin frames at the widest and tallest size eppm_motion_blur_frames and the host form accept: 256 tiles along the long side,
+# movers on every border (taps clamped at coordinate 8191), 32 KiB rows under the pitches of mblur_tol_child.frames_kernel
+LIMIT_SIZES = [(20, 8192), (8192, 20)]
+
+
 def _smooth(h, w, rng, amp):
     ys, xs = np.mgrid[0:h, 0:w].astype(np.float64)
     a, b, c, d = rng.uniform(0.05, 0.25, 4)
@@ -220,6 +225,25 @@ def test_host_form_equals_the_restatement_byte_for_byte():
         assert len(bad) == 0, (c["name"], len(bad), bad[:5], got[tuple(bad[0])], c["want"][tuple(bad[0])])
         changed += int((got != c["img"]).any())
     assert changed >= len(cs) - len(SIZES)          # the cases blur: only some 1x1 / R = 1 cases may come back unchanged
+
+
+def test_host_form_equals_the_restatement_at_the_size_limit():
+    src = open(os.path.join(ROOT, "eppm_amd", "csrc", "eppm_io.cpp")).read()
+    assert "h > %d || w > %d" % (LIMIT_SIZES[1][0], LIMIT_SIZES[0][1]) in src[src.index("int eppm_motion_blur_host"):][:600]
+    cs = cases(LIMIT_SIZES)
+    assert {(c["h"], c["w"]) for c in cs} == set(LIMIT_SIZES) and len(cs) == 8
+    for c in cs:
+        got = host(c["img"], c["u"], c["v"], *c["params"])
+        bad = np.argwhere((got != c["want"]).any(axis=2))
+        assert len(bad) == 0, (c["name"], len(bad), bad[:5], got[tuple(bad[0])], c["want"][tuple(bad[0])])
+        assert (got != c["img"]).any(), c["name"]
+        if c["name"].startswith("border"):              # the movers on the far borders blur their pixels
+            far = (got != c["img"]).any(axis=2)
+            assert far[-3:].any() and far[:, -3:].any() and far[:3].any() and far[:, :3].any(), c["name"]
+    h, w = LIMIT_SIZES[0]
+    z = np.zeros((h, w + 1), F)
+    with pytest.raises(eppm_amd.EppmError):
+        host(np.zeros((h, w + 1, 3), np.uint8), z, z)
 
 
 def test_dominant_vector_crosses_a_tile_corner_and_equal_lengths_resolve_to_the_lower_index():

@@ -11,7 +11,7 @@ import pytest
 
 from conftest import GOLDEN, ROOT
 from mblur_tol_child import GPU_SIZES, mismatches
-from test_mblur_cpu import mblur_cases
+from test_mblur_cpu import LIMIT_SIZES, cases, mblur_cases
 from test_stabilize_cpu import moving_clip
 
 pytestmark = pytest.mark.gpu
@@ -41,6 +41,22 @@ def test_kernels_equal_host_form_on_the_cpu_cases():
 
 def test_tolerance_library_equals_the_restatement():
     out = subprocess.run([sys.executable, os.path.join(ROOT, "tests", "mblur_tol_child.py")], capture_output=True, text=True, timeout=600)
+    assert out.returncode == 0 and out.stdout.strip().endswith("PART OK"), out.stdout[-2000:] + out.stderr[-2000:]
+    assert "tolerance arithmetic" in out.stdout.splitlines()[0]
+
+
+@pytest.mark.parametrize("size", range(len(LIMIT_SIZES)), ids=[f"{w}x{h}" for h, w in LIMIT_SIZES])
+def test_kernels_equal_the_restatement_at_the_size_limit(size):
+    """thin frames 8192 long, the widest and tallest eppm_motion_blur_frames accepts: 256 tiles along the long side, movers on every
+    border, rows of 32 KiB under input and output pitches larger than 4 * w"""
+    mine = [c for c in cases(LIMIT_SIZES) if (c["h"], c["w"]) == LIMIT_SIZES[size]]
+    assert len(mine) >= 3
+    bad = mismatches(mine)
+    assert not bad, bad
+
+
+def test_tolerance_library_at_the_size_limit():
+    out = subprocess.run([sys.executable, os.path.join(ROOT, "tests", "mblur_tol_child.py"), "limit"], capture_output=True, text=True, timeout=600)
     assert out.returncode == 0 and out.stdout.strip().endswith("PART OK"), out.stdout[-2000:] + out.stderr[-2000:]
     assert "tolerance arithmetic" in out.stdout.splitlines()[0]
 

@@ -222,10 +222,10 @@ MASKS = ["empty", "full", "bytes", "rand30", "rand45", "rand60", "checker", "spi
 BOTH = {"full", "checker", "spiral", "comb", "diag", "stripes_dashed", "ushapes", "rand45"}
 
 
-def finish_case(c):
-    """the restatement's results of a case"""
+def finish_case(c, labelled=None):
+    """the restatement's results of a case (labelled: np_label's result on the case, if the caller has it already)"""
     h, w, M = c["h"], c["w"], c["max_objects"]
-    labels, recs, counts, comp = np_label(c["mask"], c["u"], c["v"], c["conn"], c["min_area"], M)
+    labels, recs, counts, comp = labelled or np_label(c["mask"], c["u"], c["v"], c["conn"], c["min_area"], M)
     empty = c["prev"] == "empty"
     pid, page, nxt = (np.zeros(256, np.int32), np.zeros(256, np.int32), 1) if empty else (c["prev_id"], c["prev_age"], c["next_id"])
     ids, ages, nid, nage, nxt, how = np_assign(labels, None if empty else c["carried"], counts["n"], pid, page, nxt, M, c["min_overlap"])
@@ -237,17 +237,20 @@ def finish_case(c):
     return c
 
 
-def previous_state(kind, mask, conn, min_area, M, rng):
-    """a carried plane and tables for a case: (carried, prev_id, prev_age, next_id)"""
+def previous_state(kind, mask, conn, min_area, M, rng, labels=None):
+    """a carried plane and tables for a case: (carried, prev_id, prev_age, next_id); labels: the case's labels, if the caller has them"""
     h, w = mask.shape
     pid = np.zeros(256, np.int32)
     page = np.zeros(256, np.int32)
     pid[1:] = rng.permutation(255) + 100
     page[1:] = rng.integers(0, 50, 255)
     nxt = int(rng.integers(400, 500))
-    labels = np_label(mask, np.zeros((h, w), F), np.zeros((h, w), F), conn, min_area, M)[0]
+    if labels is None:
+        labels = np_label(mask, np.zeros((h, w), F), np.zeros((h, w), F), conn, min_area, M)[0]
     if kind == "zero":
         car = np.zeros((h, w), np.uint8)
+    elif kind == "full":                                     # previous object 1 everywhere: every vote of a wave lands on one address
+        car = np.ones((h, w), np.uint8)
     elif kind == "shifted":                                  # the labels themselves, renumbered and moved by (2, 1)
         perm = np.concatenate([[0], rng.permutation(M) + 1]).astype(np.uint8)
         car = np.zeros((h, w), np.uint8)
@@ -361,6 +364,163 @@ def spans_tiles(c, n):
     return False
 
 
+# ---- the large cases: launch shapes only large or thin frames reach ----
+
+LARGE_SIZES = [(256, 256), (257, 256), (513, 257), (8192, 20), (20, 8192)]          # (w, h): 64, 65, 129, 160 and 160 chunks
+ROUND = 64                                                   # chunks per trip of k_obj_scan's loop: one per lane of its wave
+LARGE_MIN_AREA = 6
+
+
+def obj_chunk():
+    src = open(os.path.join(ROOT, "eppm_amd", "csrc", "objects.h")).read()
+    return int(re.search(r"constexpr int kObjChunk = (\d+);", src).group(1))
+
+
+def _extent(shape, y, x, w):
+    """inclusive (y0, y1, x0, x1) of a shape: a speck is one pixel, a run 6 pixels of one row, a blob 2 x 6 pixels and one more that
+    touches them by a corner only (an object of 13 pixels at connectivity 8; one of 12 and a speck at 4)"""
+    return (y, y, x, x) if shape == "speck" else (y, y, x, x + 5) if shape == "run" else (y, y + 2, x, min(x + 6, w - 1))
+
+
+def _free(m, y0, y1, x0, x1):
+    return not m[max(y0 - 1, 0):y1 + 2, max(x0 - 1, 0):x1 + 2].any()
+
+
+def _stamp(m, shape, y, x):
+    if shape == "speck":
+        m[y, x] = 1
+    elif shape == "run":
+        m[y, x:x + 6] = 1
+    else:
+        m[y:y + 2, x:x + 6] = 1
+        if x + 6 < m.shape[1]:
+            m[y + 2, x + 6] = 1
+
+
+def _thin(seq, n):
+    """n of seq, evenly, the first and the last among them"""
+    if len(seq) <= n:
+        return list(seq)
+    return [seq[i] for i in np.linspace(0, len(seq) - 1, n).round().astype(int)]
+
+
+def large_mask(kind, h, w, M, boundary):
+    """Isolated shapes on a frame: a speck (below LARGE_MIN_AREA) in every chunk, and objects whose roots (their first pixels) are chosen
+    by kind.  late: only in chunks >= boundary.  spread: about 90 over the whole frame, the last in the last chunk.  cap: M - 2 in the
+    chunks below boundary, then 20 in a row from it, so that number M + 1 falls inside a chunk >= boundary."""
+    chunk, npx = obj_chunk(), h * w
+    m = np.zeros((h, w), np.uint8)
+    for k in range(-(-npx // chunk)):
+        n = min(chunk, npx - k * chunk)
+        for t in range(n):
+            y, x = divmod(k * chunk + (389 * k + 211 + 7 * t) % n, w)
+            if _free(m, y, y, x, x):
+                m[y, x] = 1
+                break
+        else:
+            raise AssertionError(f"no room for a speck in chunk {k}")
+    cand = [("blob", y, x) for y in range(0, h - 4, 4) for x in range(0, w - 5, 8)] + [("run", h - 1, x) for x in range(0, w - 5, 8)]
+    cand = [c for c in cand if _free(m, *_extent(*c, w))]           # in the order of their roots; no two touch
+    late = [c for c in cand if c[1] * w + c[2] >= boundary * chunk]
+    if kind == "late":
+        pick = _thin(late, 40)
+    elif kind == "spread":
+        pick = _thin(cand, 90)
+    elif kind == "cap":
+        pick = _thin(cand[:len(cand) - len(late)], M - 2) + late[:20]
+    else:
+        raise ValueError(kind)
+    for c in pick:
+        _stamp(m, *c)
+    return m
+
+
+def stripe(h, w):
+    """two lines along the frame's long side, 17 pixels apart and joined at the far end: one component from index 0 through every tile"""
+    m = np.zeros((h, w), np.uint8)
+    if w >= h:
+        m[0, :] = m[17, :] = 1
+        m[0:18, w - 1] = 1
+    else:
+        m[:, 0] = m[:, 17] = 1
+        m[h - 1, 0:18] = 1
+    return m
+
+
+def stripe_sums(h, w):
+    """(area, sum_x, sum_y) of stripe(h, w) in closed form: two lines of `long` pixels and the 16 pixels between their ends"""
+    long = max(h, w)
+    along, across = long * (long - 1) + 16 * (long - 1), 17 * long + 16 * 17 // 2
+    return (2 * long + 16,) + ((along, across) if w >= h else (across, along))
+
+
+@functools.lru_cache(maxsize=None)
+def objects_large_cases(size=None):
+    """the cases of LARGE_SIZES[size], or of every size; built on the first call, never at import"""
+    if size is None:
+        return [c for k in range(len(LARGE_SIZES)) for c in objects_large_cases(k)]
+    w, h = LARGE_SIZES[size]
+    rng = np.random.default_rng(3000 + size)
+    nchunks = -(-h * w // obj_chunk())
+    second = ROUND if nchunks > ROUND else nchunks - 1      # 256 x 256 is one full round: its "late" chunk is the round's last
+    third = 2 * ROUND if nchunks > 2 * ROUND else second
+    plan = [("late", 4, 255, second, "zero"), ("late", 8, 64, second, "empty"), ("spread", 4, 128, second, "empty"),
+            ("spread", 8, 255, second, "random"), ("cap", 8, 3, second, "random"), ("cap", 4, 255, third, "zero"),
+            ("carried", 4, 128, second, "shifted"), ("carried", 8, 255, second, "shifted")]
+    if max(w, h) == 8192:
+        plan += [("stripe", 4, 1, second, "empty"), ("stripe", 8, 64, second, "full")]
+    if (w, h) == (513, 257):
+        plan += [(kind, conn, M, second, prev) for kind in ("spiral", "comb") for conn, M, prev in ((4, 1, "full"), (8, 64, "empty"))]
+    flows = ["integer", "fraction", "special"]
+    cases = []
+    for k, (kind, conn, M, boundary, prev) in enumerate(plan):
+        if kind == "stripe":
+            mask, min_area = stripe(h, w), 16
+        elif kind in ("spiral", "comb"):
+            mask, min_area = make_mask(kind, h, w, rng), 16
+        else:
+            mask, min_area = large_mask("spread" if kind == "carried" else kind, h, w, M, boundary), LARGE_MIN_AREA
+        c = dict(name=f"{w}x{h}-{kind}-c{conn}-m{M}-{prev}", h=h, w=w, kind=kind, mask=mask, conn=conn, min_area=min_area, max_objects=M,
+                 min_overlap=(4, 5, 1)[k % 3], prev=prev, cut=False, boundary=boundary)
+        c["u"], c["v"] = make_flow(flows[k % 3], h, w, rng)
+        c["bu"], c["bv"] = make_flow(flows[(k + 1) % 3], h, w, rng)
+        if k % 5 == 4:                                       # vectors that end on the frame's last column and row, and just beyond them
+            ys, xs = np.mgrid[0:h, 0:w]
+            c["bu"], c["bv"] = (F(w - 1) - xs).astype(F), (F(h - 1) - ys).astype(F)
+            c["bu"][::2, ::3] = np.nextafter(c["bu"][::2, ::3], F(1e9))
+            c["bv"][1::2, 1::3] = np.nextafter(c["bv"][1::2, 1::3], F(1e9))
+        c["occ2"] = (rng.integers(0, 4, (h, w)) * (rng.random((h, w)) < 0.2)).astype(np.uint8)
+        labelled = np_label(mask, c["u"], c["v"], conn, min_area, M)
+        if kind in ("stripe", "spiral", "comb") and prev == "full":
+            c["min_overlap"] = int(mask.sum())               # inherits only if every pixel's vote is counted
+        if kind == "carried":                                # a blob moved by (2, 1) keeps 4 votes, 5 with its corner pixel at connectivity 8:
+            c["min_overlap"] = 4 if conn == 4 else 6         # exactly enough, and one too few
+        if prev != "empty":
+            c["carried"], c["prev_id"], c["prev_age"], c["next_id"] = previous_state(prev, mask, conn, min_area, M, rng, labels=labelled[0])
+        cases.append(finish_case(c, labelled))
+    return cases
+
+
+def large_ledger(c):
+    """what a large case makes the scan and the numbering do, from the restatement's raw components alone: per chunk the roots and the
+    found roots (a root is a component's first pixel in raster order), by rounds of ROUND chunks"""
+    chunk, npx = obj_chunk(), c["h"] * c["w"]
+    nchunks = -(-npx // chunk)
+    ids, roots = np.unique(c["comp"].ravel(), return_index=True)
+    roots = roots[ids > 0]
+    areas = np.bincount(c["comp"].ravel())[1:]
+    assert len(roots) == len(areas) and np.all(np.diff(roots) > 0)
+    found = roots[areas >= c["min_area"]]
+    per_chunk = lambda r: np.bincount(r // chunk, minlength=nchunks)          # noqa: E731
+    rounds = -(-nchunks // ROUND)
+    by_round = lambda a: [int(a[k * ROUND:(k + 1) * ROUND].sum()) for k in range(rounds)]          # noqa: E731
+    tiles_x, tiles_y = -(-c["w"] // TILE_W), -(-c["h"] // TILE_H)
+    ys, xs = np.nonzero(c["comp"] == 1)
+    return dict(nchunks=nchunks, rounds=rounds, found=by_round(per_chunk(found)), components=by_round(per_chunk(roots)),
+                specks=per_chunk(roots[areas < c["min_area"]]), found_roots=found, chunk=chunk, tiles=(tiles_x, tiles_y),
+                tiles_of_first=len(set(zip((ys // TILE_H).tolist(), (xs // TILE_W).tolist()))))
+
+
 def host_case(c):
     """the host forms on a case: (labels, records with id and age, counts with next_id, carried, prev_id, prev_age)"""
     M = c["max_objects"]
@@ -405,6 +565,79 @@ def test_host_forms_equal_the_restatement(size):
     for r in io.objects_label_host(c["mask"], c["u"], c["v"], c["conn"], c["min_area"], c["max_objects"])[1]:
         assert r["centroid"] == (r["sum_x"] / r["area"], r["sum_y"] / r["area"])
         assert r["velocity"] is None if not r["n_flow"] else r["velocity"] == (r["sum_qu"] / (256.0 * r["n_flow"]), r["sum_qv"] / (256.0 * r["n_flow"]))
+
+
+LARGE_IDS = [f"{w}x{h}" for w, h in LARGE_SIZES]
+
+
+@pytest.mark.parametrize("size", range(len(LARGE_SIZES)), ids=LARGE_IDS)
+def test_host_forms_equal_the_restatement_on_large_frames(size):
+    cases = objects_large_cases(size)
+    assert len(cases) >= 8
+    for c in cases:
+        bad = differences(c, *host_case(c))
+        assert not bad, (c["name"], bad)
+
+
+@pytest.mark.parametrize("size", range(len(LARGE_SIZES)), ids=LARGE_IDS)
+def test_large_cases_reach_what_they_advertise(size):
+    """The ledger of objects_large_cases(): every case makes k_obj_scan and k_obj_number do what its kind says, computed from the
+    restatement's components alone.  A case that stops meeting its condition fails here; none is skipped."""
+    w, h = LARGE_SIZES[size]
+    cases = objects_large_cases(size)
+    kinds = [c["kind"] for c in cases]
+    assert all(kinds.count(k) == 2 for k in ("late", "spread", "cap", "carried"))
+    assert kinds.count("stripe") == (2 if max(w, h) == 8192 else 0) and kinds.count("spiral") == kinds.count("comb") == (2 if (w, h) == (513, 257) else 0)
+    assert {c["conn"] for c in cases if c["kind"] in ("late", "spread", "carried")} == {4, 8}
+    assert {c["max_objects"] for c in cases if c["kind"] == "cap"} == {3, 255}
+    assert any(c["prev"] == "empty" for c in cases) and any(c["prev"] != "empty" for c in cases)
+    want_chunks = {(256, 256): 64, (257, 256): 65, (513, 257): 129, (8192, 20): 160, (20, 8192): 160}[(w, h)]
+    for c in cases:
+        L, n, M = large_ledger(c), c["want_counts"], c["max_objects"]
+        name = c["name"]
+        assert L["nchunks"] == want_chunks and L["rounds"] == -(-want_chunks // ROUND), name
+        assert L["tiles"] == (-(-w // 64), -(-h // 16)), name
+        assert sum(L["found"]) == n["n_found"] and sum(L["components"]) == n["n_components"], name
+        later = L["rounds"] > 1                              # 256 x 256 is exactly one round: its conditions are on the round's last chunk
+        b = c["boundary"]
+        assert (b % ROUND == 0 and ROUND <= b < L["nchunks"]) if later else b == L["nchunks"] - 1, name          # a later round's first chunk
+        first_late = L["found_roots"][L["found_roots"] >= b * L["chunk"]]
+        if c["kind"] in ("late", "spread", "cap", "carried"):
+            assert L["specks"].min() >= 1, name               # below min_area in every chunk
+            assert len(first_late) > 0, name                  # found roots in round >= 2
+            if later:                                         # found roots in every later round; a cap case stops 20 objects after its boundary
+                assert (any if c["kind"] == "cap" else all)(f > 0 for f in L["found"][1:]), name
+        if c["kind"] == "late":
+            assert (L["found"][0] == 0) if later else (L["found_roots"].min() >= b * L["chunk"]), name          # the prefix entering round 2
+            assert L["components"][0] >= ROUND - 1 and n["n_found"] <= M, name
+            y, x = divmod(int(first_late[0]), w)
+            assert c["want_labels"][y, x] == 1, name          # the first found root of round 2 is object 1
+        if c["kind"] in ("spread", "carried"):
+            assert L["found"][0] > 0 and n["n_found"] <= M and n["n"] == n["n_found"], name
+            y, x = divmod(int(L["found_roots"][-1]), w)
+            assert L["found_roots"][-1] // L["chunk"] == L["nchunks"] - 1 and c["want_labels"][y, x] == n["n"], name
+        if c["kind"] == "carried":
+            how = set(c["how"])
+            assert ("inherited" in how and "below" not in how) if c["conn"] == 4 else ("below" in how and "inherited" not in how), (name, how)
+        if c["kind"] == "cap":
+            assert n["n_found"] > M and n["n"] == M, name
+            last_in, first_out = int(L["found_roots"][M - 1]), int(L["found_roots"][M])
+            assert last_in // L["chunk"] == first_out // L["chunk"] >= b and (b >= ROUND) == later, name          # crossed inside a chunk
+            for root, lab in ((last_in, M), (first_out, 0), (int(L["found_roots"][-1]), 0)):
+                assert c["want_labels"][root // w, root % w] == lab, name
+        if c["kind"] in ("stripe", "spiral", "comb"):
+            ys, xs = np.nonzero(c["mask"])
+            r = c["want_recs"][0]
+            assert n == dict(n=1, n_found=1, n_components=1, next_id=n["next_id"]) and c["comp"][0, 0] == 1, name
+            assert L["tiles_of_first"] == L["tiles"][0] * L["tiles"][1], name
+            assert (r["area"], r["sum_x"], r["sum_y"]) == (len(xs), int(xs.sum()), int(ys.sum())), name
+            if c["kind"] == "stripe":
+                assert (r["area"], r["sum_x"], r["sum_y"]) == stripe_sums(h, w), name
+                assert (r["x1"], r["y1"]) == (w - 1, 17) if w > h else (r["x1"], r["y1"]) == (17, h - 1), name
+            if c["prev"] == "full":
+                assert c["how"] == ["inherited"] and c["min_overlap"] == r["area"], name
+    names = [c["name"] for c in cases]
+    assert len(set(names)) == len(names)
 
 
 def test_raw_components_equal_scipy():

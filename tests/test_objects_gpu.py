@@ -1,5 +1,6 @@
 """GPU tests of moving-object detection: the kernels against the numpy restatement (which
-tests/test_objects_cpu.py holds equal to the host forms) in every number on objects_cases(), slot independence, the context and batch
+tests/test_objects_cpu.py holds equal to the host forms) in every number on objects_cases() and objects_large_cases() (more than 64
+chunks, thin frames 8192 long), slot independence, the context and batch
 forms against the host forms fed with the context's own planes, the tolerance library, and the end-to-end helpers."""
 import os
 import subprocess
@@ -9,7 +10,7 @@ import numpy as np
 import pytest
 
 from conftest import ROOT
-from test_objects_cpu import FIELDS, SIZES, differences, finish_case, host_case, objects_cases
+from test_objects_cpu import FIELDS, LARGE_IDS, LARGE_SIZES, SIZES, differences, finish_case, host_case, objects_cases, objects_large_cases
 from test_stabilize_cpu import moving_clip
 from objects_tol_child import case_planes, free_planes, load_case, mismatches, read_slot, step_case
 
@@ -42,6 +43,52 @@ def test_kernels_equal_the_host_forms(size):
     assert not bad, bad[:3]
     c = cases[len(cases) // 2]                    # and against the host forms directly
     assert not differences(c, *host_case(c))
+
+
+@pytest.mark.parametrize("size", range(len(LARGE_SIZES)), ids=LARGE_IDS)
+def test_kernels_equal_the_host_forms_on_large_frames(size):
+    """objects_large_cases(): more than 64 chunks (k_obj_scan's carry from round to round, k_obj_number's start value of a chunk >= 64),
+    up to 128 x 2 and 1 x 512 tiles under one component, coordinates up to 8191.  Stepped twice on one detector, read with the error word
+    checked, as above."""
+    cases = objects_large_cases(size)
+    bad = mismatches(cases)
+    assert not bad, bad[:3]
+    c = cases[len(cases) // 2]
+    assert not differences(c, *host_case(c))
+
+
+@pytest.mark.parametrize("size", range(len(LARGE_SIZES)), ids=LARGE_IDS)
+def test_tolerance_library_runs_the_same_kernels_on_large_frames(size):
+    out = subprocess.run([sys.executable, os.path.join(ROOT, "tests", "objects_tol_child.py"), "large", str(size)], capture_output=True, text=True,
+                         timeout=600)
+    assert out.returncode == 0 and out.stdout.strip().endswith("PART OK"), out.stdout[-2000:] + out.stderr[-2000:]
+    assert "tolerance arithmetic" in out.stdout.splitlines()[0]
+
+
+def test_eight_slots_hold_eight_large_cases():
+    """eight slots of one 8192 x 20 detector take eight different large cases, so that every slot's chunk counts, parent plane and tables
+    meet other data than its neighbours'; all are stepped before any is read, then stepped again in another order"""
+    import eppm_amd
+    w, h = 8192, 20
+    common = dict(conn=8, min_area=6, max_objects=64, min_overlap=4)
+    pool = objects_large_cases(LARGE_SIZES.index((w, h)))
+    picked = [finish_case(dict(c, **common)) for c in pool if c["conn"] == 8 or c["kind"] in ("late", "cap", "spread")][:8]
+    assert len(picked) == 8 and len({c["want_counts"]["n_found"] for c in picked}) >= 4
+    assert any(c["want_counts"]["n_found"] > 64 for c in picked)
+    det = eppm_amd.ObjectDetector(None, size=(h, w), slots=8, **{"connectivity" if k == "conn" else k: v for k, v in common.items()})
+    planes = [case_planes(c) for c in picked]
+    try:
+        for order in (range(8), (5, 2, 7, 0, 3, 6, 1, 4)):
+            for slot in order:
+                load_case(det, slot, picked[slot])
+            for slot in order:
+                step_case(det, slot, picked[slot], planes[slot])
+            for slot in range(8):
+                assert not differences(picked[slot], *read_slot(det, slot)), (slot, picked[slot]["name"])
+    finally:
+        det.close()
+        for p in planes:
+            free_planes(p)
 
 
 def test_slots_are_independent():
@@ -168,6 +215,34 @@ def test_context_form_equals_the_host_forms_and_leaves_the_flows_alone():
         assert status(lambda: det.objects(0)) == STATE
     finally:
         det.close(); e.close(); ref.close()
+
+
+def test_context_form_above_one_round_of_chunks():
+    """320 x 240 is 75 chunks: the context form (private stabiliser, then the nine launches on the context's stream) where the scan has a
+    second round, against the host forms fed with the context's planes"""
+    import eppm_amd
+    h, w = 240, 320
+    noisy = moving_clip(h, w, 3, seed=61)
+    e = eppm_amd.EPPM()
+    e.init(h, w)
+    det = eppm_amd.ObjectDetector(e, min_area=2)
+    host = HostDetector(min_area=2)
+    try:
+        for k in (1, 2):
+            if k == 1:
+                e.set_data(noisy[0], noisy[1])
+            else:
+                e.push_frame(noisy[2])
+            planes = e.compute_flow_bidirectional()
+            det.step()
+            want = host.step(*planes)
+            host.same(det, 0, want, f"pair {k}")
+            roots = [int(np.flatnonzero(want[0] == lab)[0]) for lab in range(1, want[2]["n"] + 1)]
+            late = [r for r in roots if r >= 64 * 1024]
+            print(f"pair {k}: counts {want[2]}, {len(late)} objects with their root in a chunk >= 64")
+            assert late and len(late) < len(roots), "the second round of the scan numbers nothing, or everything"
+    finally:
+        det.close(); e.close()
 
 
 def test_call_order_and_arguments():

@@ -195,6 +195,27 @@ def make_prior(kind, ch, cw, n_max, rng):
     return st
 
 
+def _one_case(rng, k, w, h, mx, my, pname, path):
+    """case number k of a size: the mask, grow, prior, thresh, n_max and min_count that k selects, and two images"""
+    mask_kind = MASKS[k % len(MASKS)]
+    grow = GROWS[(k // 2) % 3]
+    prior = PRIORS[(k * 4 + k // 9) % len(PRIORS)]
+    thresh = THRESH[(k // 3 + k) % 3]
+    n_max = (1, 64, 255, 8)[(k // 5) % 4]
+    min_count = MIN_COUNT[(k // 7 + k) % 3]
+    img = rng.integers(100, 141, (h, w, 3)).astype(np.uint8)
+    img_b = img.copy()
+    noise = rng.random((h, w)) < 0.5
+    img_b[noise] = (img_b[noise].astype(int) + rng.integers(-3, 4, (int(noise.sum()), 3))).astype(np.uint8)
+    far = rng.random((h, w)) < 0.1
+    img_b[far] = rng.integers(0, 256, (int(far.sum()), 3)).astype(np.uint8)
+    return dict(name=f"{w}x{h}_m{mx}.{my}_{pname}_{mask_kind}_g{grow}_{prior}_t{thresh:g}_n{n_max}_c{min_count}", w=w, h=h, mx=mx,
+                my=my, pname=pname, path=np.array(path, np.float64), mask_kind=mask_kind, mask=make_mask(mask_kind, h, w, rng),
+                grow=grow, accept=mask_kind == "bytes_accept", prior_kind=prior,
+                prior=make_prior(prior, h + 2 * my, w + 2 * mx, n_max, rng), thresh=thresh, n_max=n_max, min_count=min_count,
+                img=img, img_b=img_b)
+
+
 _CASES = None
 
 
@@ -211,26 +232,63 @@ def plate_cases():
         for mx, my in ((0, 0), (3, 2), (w, h)):
             for pname, path in case_paths(w, h, mx, my):
                 for rep in range(2):
-                    mask_kind = MASKS[k % len(MASKS)]
-                    grow = GROWS[(k // 2) % 3]
-                    prior = PRIORS[(k * 4 + k // 9) % len(PRIORS)]
-                    thresh = THRESH[(k // 3 + k) % 3]
-                    n_max = (1, 64, 255, 8)[(k // 5) % 4]
-                    min_count = MIN_COUNT[(k // 7 + k) % 3]
-                    img = rng.integers(100, 141, (h, w, 3)).astype(np.uint8)
-                    img_b = img.copy()
-                    noise = rng.random((h, w)) < 0.5
-                    img_b[noise] = (img_b[noise].astype(int) + rng.integers(-3, 4, (int(noise.sum()), 3))).astype(np.uint8)
-                    far = rng.random((h, w)) < 0.1
-                    img_b[far] = rng.integers(0, 256, (int(far.sum()), 3)).astype(np.uint8)
-                    cases.append(dict(name=f"{w}x{h}_m{mx}.{my}_{pname}_{mask_kind}_g{grow}_{prior}_t{thresh:g}_n{n_max}_c{min_count}", w=w, h=h, mx=mx,
-                                      my=my, pname=pname, path=np.array(path, np.float64), mask_kind=mask_kind, mask=make_mask(mask_kind, h, w, rng),
-                                      grow=grow, accept=mask_kind == "bytes_accept", prior_kind=prior,
-                                      prior=make_prior(prior, h + 2 * my, w + 2 * mx, n_max, rng), thresh=thresh, n_max=n_max, min_count=min_count,
-                                      img=img, img_b=img_b))
+                    cases.append(_one_case(rng, k, w, h, mx, my, pname, path))
                     k += 1
     _CASES = cases
     return cases
+
+
+# Frames and canvases at kGmMaxDim: (w, h, mx, my).  The frame at the limit leaves no room for a margin along its long side (the canvas
+# obeys the same bound: one pixel more is refused); a frame 6 / 4 short of it takes the margins (3, 2) to a canvas of exactly 8192.
+# Paths that make the canvas's first column or row sample the frame's last one (a tap at coordinate 8191), and its last one sample half a
+# pixel into the frame; pad: pixels beyond
+# every row of the caller's image and of the render's output
+LIMIT_SIZES = [(8192, 20, 0, 0), (8192, 20, 0, 2), (8186, 20, 3, 2), (20, 8192, 0, 0), (20, 8192, 3, 0), (20, 8188, 3, 2)]
+_LIMIT = {}
+
+
+def plate_limit_cases(size):
+    """the cases of LIMIT_SIZES[size]; built on first use"""
+    if size not in _LIMIT:
+        w, h, mx, my = LIMIT_SIZES[size]
+        rng = np.random.default_rng(2200 + size)
+        far = (float(w + mx - 1), 0.0) if w > h else (0.0, float(h + my - 1))          # the canvas's first column / row samples the frame's last
+        back = (0.5 - far[0], 0.0) if w > h else (0.0, 0.5 - far[1])                   # its last one samples between the frame's first two
+        paths = [("int", (1, 0, 0, 1, 3.0, -2.0)), ("sub2", (1, 0, 0, 1, -1.75, 2.3125)), ("far", (1, 0, 0, 1) + far), ("back", (1, 0, 0, 1) + back)]
+        _LIMIT[size] = [dict(_one_case(rng, 5 * size + 3 * j + 1, w, h, mx, my, *pp), pad=(0, 3, 64)[(size + j) % 3]) for j, pp in enumerate(paths)]
+    return _LIMIT[size]
+
+
+LIMIT_IDS = [f"{w}x{h}_m{mx}.{my}" for w, h, mx, my in LIMIT_SIZES]
+
+
+@pytest.mark.parametrize("size", range(len(LIMIT_SIZES)), ids=LIMIT_IDS)
+def test_host_forms_equal_the_restatement_at_the_size_limit(size):
+    w, h, mx, my = LIMIT_SIZES[size]
+    src = open(os.path.join(ROOT, "eppm_amd", "csrc", "gmotion.h")).read()
+    limit = int(re.search(r"constexpr int kGmMaxDim = (\d+);", src).group(1))
+    assert max(w + 2 * mx, h + 2 * my) == limit
+    L, out = eppm_amd.lib(), C.c_void_p()
+    pp = _lib.CPlateParams()
+    assert L.eppm_plate_default_params(C.byref(pp)) == 0
+    pp.margin_x, pp.margin_y = mx + (w > h), my + (h > w)     # one more pixel of margin along the long side: the canvas passes the bound
+    assert L.eppm_plate_create_size(h, w, 1, 0, C.byref(pp), C.byref(out)) == ARG and not out.value
+    cases = plate_limit_cases(size)
+    bad = [(c["name"], d) for c in cases for d in [differences(c, *host_case(c))] if d]
+    assert not bad, (len(bad), bad[:3])
+    for c in cases:
+        want = expected(c)
+        assert want["ok"], c["name"]
+        yc, xc = np.mgrid[0:h + 2 * my, 0:w + 2 * mx]
+        qx, qy = _position(want["fwd"], xc - mx, yc - my, h, w)
+        inside = _taps(qx, qy, h, w)[0]
+        q, n, first, last = (qx, w, inside[:, 0], inside[:, -1]) if w > h else (qy, h, inside[0], inside[-1])
+        if c["pname"] == "far":
+            assert first.any() and q[inside].max() == n - 1 and inside.sum() <= min(w + 2 * mx, h + 2 * my), c["name"]
+        if c["pname"] == "back":
+            assert last.any() and q[inside].min() == 0.5 and inside.sum() <= min(w + 2 * mx, h + 2 * my), c["name"]
+        if c["pname"] in ("int", "sub2"):
+            assert inside.mean() > 0.5 and q[inside].max() > n - 4, c["name"]
 
 
 def expected(c):

@@ -9,7 +9,7 @@ import numpy as np
 import pytest
 
 from conftest import ROOT
-from test_plate_cpu import F, IDENT, SIZES, differences, host_case, np_advance, np_coverage, np_word, plate_cases, same_bits
+from test_plate_cpu import F, IDENT, LIMIT_IDS, LIMIT_SIZES, SIZES, plate_limit_cases, differences, host_case, np_advance, np_coverage, np_word, plate_cases, same_bits
 from test_stabilize_cpu import band_limited, moving_clip
 from plate_tol_child import case_params, case_planes, device_case, device_differences, free_planes, from_device, mismatches, to_device
 
@@ -72,6 +72,22 @@ def test_slots_are_independent():
         pl.close()
         for p in planes.values():
             free_planes(p)
+
+
+@pytest.mark.parametrize("size", range(len(LIMIT_SIZES)), ids=LIMIT_IDS)
+def test_kernels_equal_the_restatement_at_the_size_limit(size):
+    """frames and canvases 8192 long, with no margin along the long side, with a margin across it, and with margins (3, 2) around a frame
+    that leaves them room: canvas taps at coordinate 8191, images and render output under a pitch larger than 4 * w"""
+    bad = mismatches(plate_limit_cases(size))
+    assert not bad, bad
+
+
+@pytest.mark.parametrize("half", [0, 3], ids=["wide", "tall"])
+def test_tolerance_library_at_the_size_limit(half):
+    out = subprocess.run([sys.executable, os.path.join(ROOT, "tests", "plate_tol_child.py"), "limit", str(half)], capture_output=True, text=True,
+                         timeout=600)
+    assert out.returncode == 0 and out.stdout.strip().endswith("PART OK"), out.stdout[-2000:] + out.stderr[-2000:]
+    assert "tolerance arithmetic" in out.stdout.splitlines()[0]
 
 
 def test_tolerance_library_runs_the_same_kernels():

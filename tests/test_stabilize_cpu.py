@@ -5,12 +5,16 @@ generator stab_cases() (the GPU tests run the kernels on the same cases), the AB
 background motion of a scene with an independently moving rectangle, tripod lock, pass-through and degenerate frames."""
 import ctypes as C
 import functools
+import os
+import re
 
 import numpy as np
 import pytest
 
 import eppm_amd
 from eppm_amd import _lib, io
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))          # (no conftest import: stabilize_tol_child.py imports this module)
 
 F = np.float32
 ARG = 1
@@ -250,10 +254,25 @@ def restate(c):
 
 @functools.lru_cache(maxsize=None)
 def stab_cases():
+    return _build(SIZES, CONFIGS, 1600)
+
+
+# Thin frames at kGmMaxDim: centred coordinates up to +-4095.5 in gm_X / gm_Y, 256 and 512 slabs (four and eight trips of the solve
+# kernel's loop over 64 lanes), warps that sample the last column and row at 8191; pad: pixels beyond every row of the caller's image
+LIMIT_SIZES = [(8192, 20), (20, 8192)]
+LIMIT_CONFIGS = [CONFIGS[k] for k in (0, 1, 3, 5, 8, 10, 11, 12)]
+
+
+@functools.lru_cache(maxsize=None)
+def stab_limit_cases():
+    return [dict(c, pad=(0, 5, 64)[k % 3]) for k, c in enumerate(_build(LIMIT_SIZES, LIMIT_CONFIGS, 9600))]
+
+
+def _build(sizes, configs, seed):
     cases = []
-    for si, (w, h) in enumerate(SIZES):
-        for ci, (kind, tau, iters, smooth, state, cut) in enumerate(CONFIGS):
-            rng = np.random.default_rng(1600 + 100 * si + ci)
+    for si, (w, h) in enumerate(sizes):
+        for ci, (kind, tau, iters, smooth, state, cut) in enumerate(configs):
+            rng = np.random.default_rng(seed + 100 * si + ci)
             u, v, occ = _flow(kind, rng, h, w)
             c = dict(name=f"{w}x{h}-{ci}-{kind}-{state}", w=w, h=h, kind=kind, tau=tau, iters=iters, smooth=smooth, state=state, cut=cut,
                      u=u, v=v, occ=occ, img2=rng.integers(0, 256, (h, w, 3), dtype=np.uint8), path=_state(state, rng, h, w, smooth))
@@ -306,6 +325,36 @@ def test_host_forms_equal_the_restatement(size):
     assert len(cases) == len(CONFIGS)
     bad = [(c["name"], d) for c in cases for d in [differences(c, host_step(c))] if d]
     assert not bad, bad
+
+
+@pytest.mark.parametrize("size", range(len(LIMIT_SIZES)), ids=[f"{w}x{h}" for w, h in LIMIT_SIZES])
+def test_host_forms_equal_the_restatement_at_the_size_limit(size):
+    w, h = LIMIT_SIZES[size]
+    src = open(os.path.join(ROOT, "eppm_amd", "csrc", "gmotion.h")).read()
+    assert max(w, h) == int(re.search(r"constexpr int kGmMaxDim = (\d+);", src).group(1))
+    assert not io_size_ok(h + (h > w), w + (w > h))          # one more along the long side is refused
+    cases = [c for c in stab_limit_cases() if (c["w"], c["h"]) == (w, h)]
+    assert len(cases) == len(LIMIT_CONFIGS) and {c["pad"] for c in cases} == {0, 5, 64}
+    bad = [(c["name"], d) for c in cases for d in [differences(c, host_step(c))] if d]
+    assert not bad, bad
+    for c in cases:
+        if c["state"] == "last":       # the warp's tap at (8191, 19) / (19, 8191): the closed side of the frame test
+            assert np.array_equal(c["want_rgb"][0, 0], c["img2"][-1, -1]) and int(c["want_rgb"].astype(bool).any(axis=2).sum()) <= 1
+        if c["state"] == "ulp":
+            assert not c["want_rgb"].any()
+        if c["state"] == "shift":
+            assert c["want_rgb"][:, -1].any() or c["want_rgb"][-1].any()
+        if c["kind"] in ("affine", "rect") and not c["cut"]:
+            assert c["want_model"]["valid"] and 0 in c["want_mask"][:, 0] and 0 in c["want_mask"][:, -1] and 0 in c["want_mask"][0] and 0 in c["want_mask"][-1]
+
+
+def io_size_ok(h, w):
+    """whether the fit's host form accepts a frame of this size"""
+    try:
+        io.gmotion_fit_host(np.zeros((h, w), F), np.zeros((h, w), F), np.ones((h, w), np.uint8))
+    except eppm_amd.EppmError:
+        return False
+    return True
 
 
 def test_the_cases_cover_what_they_claim():

@@ -10,7 +10,7 @@ import pytest
 
 from conftest import ROOT
 from stabilize_tol_child import mismatches
-from test_stabilize_cpu import OFFSETS, SIZES, band_limited, host_step, moving_clip, same_bits, same_model, stab_cases
+from test_stabilize_cpu import LIMIT_SIZES, OFFSETS, SIZES, stab_limit_cases, band_limited, host_step, moving_clip, same_bits, same_model, stab_cases
 
 pytestmark = pytest.mark.gpu
 
@@ -34,6 +34,22 @@ def test_kernels_equal_the_restatement(size):
     cases = [c for c in stab_cases() if (c["w"], c["h"]) == SIZES[size]]
     bad = mismatches(cases)
     assert not bad, bad
+
+
+@pytest.mark.parametrize("size", range(len(LIMIT_SIZES)), ids=[f"{w}x{h}" for w, h in LIMIT_SIZES])
+def test_kernels_equal_the_restatement_at_the_size_limit(size):
+    """thin frames 8192 long: gm_X / gm_Y up to +-4095.5, 256 and 512 slabs under the solve kernel's 64 lanes, the warp's taps at
+    coordinate 8191, the caller's image under a pitch larger than 4 * w"""
+    cases = [c for c in stab_limit_cases() if (c["w"], c["h"]) == LIMIT_SIZES[size]]
+    assert len(cases) >= 3
+    bad = mismatches(cases)
+    assert not bad, bad
+
+
+def test_tolerance_library_at_the_size_limit():
+    out = subprocess.run([sys.executable, os.path.join(ROOT, "tests", "stabilize_tol_child.py"), "limit"], capture_output=True, text=True, timeout=600)
+    assert out.returncode == 0 and out.stdout.strip().endswith("PART OK"), out.stdout[-2000:] + out.stderr[-2000:]
+    assert "tolerance arithmetic" in out.stdout.splitlines()[0]
 
 
 def test_tolerance_library_runs_the_same_arithmetic():

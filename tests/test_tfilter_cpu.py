@@ -160,6 +160,40 @@ def tfilter_cases():
     return _CASES
 
 
+# Thin frames at 8192, section 16's bound, which the objects chained with the filter obey (its own check, h*w < 2^31, lies far beyond):
+# taps at x = 8191 / y = 8191, 32 KiB image rows, and image planes whose pitch is larger than 4 * w (pad: pixels beyond every row)
+LIMIT_SIZES = [(8192, 20), (20, 8192)]
+LIMIT_CONFIGS = [("stepped", 40.0, 255, False), ("empty", 1e9, 8, False), ("nmax", 40.0, 255, False), ("seeded", 0.0, 8, False)]
+_LIMIT = None
+
+
+def tfilter_limit_cases():
+    global _LIMIT
+    if _LIMIT is None:
+        _LIMIT = [dict(_case(77000 + 10 * i + j, w, h, *cfg), pad=(0, 3, 64)[j % 3]) for i, (w, h) in enumerate(LIMIT_SIZES)
+                  for j, cfg in enumerate(LIMIT_CONFIGS)]
+        for c in _LIMIT:
+            for v in c.values():
+                if isinstance(v, np.ndarray):
+                    v.setflags(write=False)
+    return _LIMIT
+
+
+def ends_reached(bu, bv):
+    """what a case's vectors reach on a frame: a target exactly on the last column / row from a pixel of the first ones and of the last
+    ones, one within a pixel beyond them, and one exactly on coordinate 0 -- in x and in y"""
+    h, w = bu.shape
+    ys, xs = np.mgrid[0:h, 0:w]
+    with np.errstate(invalid="ignore", over="ignore"):
+        qx, qy = xs.astype(F) + bu, ys.astype(F) + bv
+    out = {}
+    for name, q, pos, n in (("x", qx, xs, w), ("y", qy, ys, h)):
+        out[name] = dict(last=bool((q == F(n - 1)).any()), last_from_far=bool(((q == F(n - 1)) & (pos < n // 8)).any()),
+                         first_from_far=bool(((q >= 0) & (q < 1) & (pos >= n - n // 8)).any()),
+                         beyond=bool(((q > F(n - 1)) & (q < F(n))).any()), zero=bool(((q == 0) & (pos > 0)).any()))
+    return out
+
+
 def same_bits(a, b):
     return np.array_equal(np.ascontiguousarray(a).view(np.uint32), np.ascontiguousarray(b).view(np.uint32))
 
@@ -234,6 +268,18 @@ def test_numpy_restatement_equals_the_host_form(size):
         assert np.array_equal(rgb, c["want_rgb"]), c["name"]
         if c["cut"]:
             assert np.array_equal(rgb, c["img2"]) and (got[..., 3] == 1).all()
+
+
+@pytest.mark.parametrize("size", range(len(LIMIT_SIZES)), ids=[f"{w}x{h}" for w, h in LIMIT_SIZES])
+def test_numpy_restatement_equals_the_host_form_at_the_size_limit(size):
+    cases = [c for c in tfilter_limit_cases() if (c["w"], c["h"]) == LIMIT_SIZES[size]]
+    assert len(cases) == len(LIMIT_CONFIGS) and {c["pad"] for c in cases} == {0, 3, 64}
+    for c in cases:
+        acc = io.tfilter_seed_host(c["img1"]) if c["state"] == "empty" else c["acc"]
+        got, rgb = io.tfilter_step_host(acc, c["img2"], c["bu"], c["bv"], c["occ"], c["thresh"], c["n_max"], c["cut"])
+        assert same_bits(got, c["want_acc"]) and np.array_equal(rgb, c["want_rgb"]), c["name"]
+        for axis, reached in ends_reached(c["bu"], c["bv"]).items():
+            assert all(reached.values()), (c["name"], axis, reached)
 
 
 def test_output_byte_is_total():

@@ -9,7 +9,7 @@ import numpy as np
 import pytest
 
 from conftest import ROOT
-from test_tfilter_cpu import SIZES, host_filter, moving_clip, psnr, same_bits, tfilter_cases
+from test_tfilter_cpu import LIMIT_SIZES, SIZES, tfilter_limit_cases, host_filter, moving_clip, psnr, same_bits, tfilter_cases
 from tfilter_tol_child import mismatches
 
 pytestmark = pytest.mark.gpu
@@ -38,6 +38,22 @@ def test_kernel_equals_the_host_form(size):
     c = cases[1]                                  # and against the host form directly
     got, rgb = io.tfilter_step_host(c["acc"], c["img2"], c["bu"], c["bv"], c["occ"], c["thresh"], c["n_max"], c["cut"])
     assert same_bits(got, c["want_acc"]) and np.array_equal(rgb, c["want_rgb"])
+
+
+@pytest.mark.parametrize("size", range(len(LIMIT_SIZES)), ids=[f"{w}x{h}" for w, h in LIMIT_SIZES])
+def test_kernel_equals_the_host_form_at_the_size_limit(size):
+    """thin frames 8192 long: taps at coordinate 8191, vectors that leave the frame by less than a pixel at both ends, image planes under
+    a pitch larger than 4 * w"""
+    cases = [c for c in tfilter_limit_cases() if (c["w"], c["h"]) == LIMIT_SIZES[size]]
+    assert len(cases) >= 3
+    bad = mismatches(cases)
+    assert not bad, bad
+
+
+def test_tolerance_library_at_the_size_limit():
+    out = subprocess.run([sys.executable, os.path.join(ROOT, "tests", "tfilter_tol_child.py"), "limit"], capture_output=True, text=True, timeout=600)
+    assert out.returncode == 0 and out.stdout.strip().endswith("PART OK"), out.stdout[-2000:] + out.stderr[-2000:]
+    assert "tolerance arithmetic" in out.stdout.splitlines()[0]
 
 
 # ---- 2. the context form ----

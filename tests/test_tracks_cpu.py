@@ -263,6 +263,68 @@ def tracking_cases():
     return out
 
 
+# (w, h, spacing) thin frames 8192 long -- section 16's bound, which the tracker's own check (h*w < 2^31) lies far beyond -- with spacings
+# that leave the cell count along the long side no multiple of 64: 1171 and 1639 cells (the last one partial), 3 and 4 across
+LIMIT_SHAPES = ((8192, 20, 7), (20, 8192, 5))
+
+
+@functools.lru_cache(maxsize=None)
+def limit_tracking_cases(shape):
+    """tracking_cases()' kinds on LIMIT_SHAPES[shape]: seeding from image 1, and placed tracks on the first and last pixels of the long
+    side, whose taps and motion-boundary neighbours clamp at coordinate 8191"""
+    w, h, spacing = LIMIT_SHAPES[shape]
+    rng = np.random.default_rng(120 + shape)
+    img1 = rng.integers(0, 256, (h, w, 3), dtype=np.uint8)
+    img2 = rng.integers(0, 256, (h, w, 3), dtype=np.uint8)
+    img1[h // 2:, w // 2:] = (90, 100, 110)                           # flat regions: no seeds
+    img2[:h // 3, :w // 3] = (20, 20, 20)
+    u = _smooth(rng, h, w, 9, 2.0) + f32(1.25)
+    v = _smooth(rng, h, w, 9, 1.5) - f32(0.5)
+    bu, bv = -u + _smooth(rng, h, w, 7, 0.3), -v + _smooth(rng, h, w, 7, 0.3)
+    for a in (u, v, bu, bv):                                          # unknown vectors (reasons 1, 3 and 4)
+        ys, xs = rng.integers(0, h, 60), rng.integers(0, w, 60)
+        a[ys[:20], xs[:20]], a[ys[20:40], xs[20:40]], a[ys[40:], xs[40:]] = np.nan, f32(1e10), -np.inf
+    L, along = max(h, w), (u if w > h else v)
+    sl = (slice(None), slice(L - 40, L)) if w > h else (slice(L - 40, L), slice(None))
+    along[sl] += f32(9.0)                                             # leaves the frame at the far end (2) and a motion boundary there (4)
+    blk = (slice(h // 4, h // 2), slice(w // 4, w // 2))
+    bu[blk] = u[blk]                                                  # inconsistent (3)
+    p = dict(DEFAULTS, spacing=spacing)
+    out = [("limit_seeded", img1, img2, u, v, bu, bv, p, None),
+           ("limit_capacity", img1, img2, u, v, bu, bv, dict(p, min_eig=0, capacity=1000), None)]
+    ends = [(0, 0), (w - 1, h - 1), (w - 1, 0), (0, h - 1), (w - 1.5, h - 1), (w - 1, h - 1.5), (w - 1.25, h - 1.25), (0.5, 0.5)]
+    far = [((L - 1 - d, y) if w > h else (y, L - 1 - d)) for d, y in zip(rng.uniform(0, 64, 60), rng.uniform(0, min(h, w) - 1, 60))]
+    pts = ends + far + list(zip(rng.uniform(0, w - 1, 200), rng.uniform(0, h - 1, 200)))
+    xy = np.array(pts, np.float32)
+    n = len(xy)
+    ids = np.arange(100, 100 + n, dtype=np.int32)[rng.permutation(n)]
+    out.append(("limit_placed", img1, img2, u, v, bu, bv, p, (ids, rng.integers(0, 5, n).astype(np.int32), xy, 500, 5)))
+    z = np.zeros((h, w), np.float32)
+    out.append(("limit_still", img1, img1, z + f32(0.5), z, z - f32(0.5), z, p, None))
+    return out
+
+
+@pytest.mark.parametrize("shape", range(len(LIMIT_SHAPES)), ids=[f"{w}x{h}" for w, h, _ in LIMIT_SHAPES])
+def test_host_form_equals_numpy_restatement_at_the_size_limit(shape):
+    w, h, spacing = LIMIT_SHAPES[shape]
+    ncx, ncy = -(-w // spacing), -(-h // spacing)
+    assert max(ncx, ncy) % 64 != 0 and max(ncx, ncy) > 1024 and max(w, h) % spacing != 0
+    reasons = set()
+    for case in limit_tracking_cases(shape):
+        got, want = _host(case)
+        same_state(got, want, case[0])
+        reasons |= set(want["reasons"].tolist())
+        xy = np.asarray(want["xy"], np.float32).reshape(-1, 2)
+        if case[0] in ("limit_seeded", "limit_still"):            # live tracks in the first and in the last cells of the long side
+            along = xy[:, 0 if w > h else 1]
+            assert along.min() < spacing and along.max() > max(w, h) - 2 * spacing, case[0]
+        if case[0] == "limit_capacity":
+            assert want["dropped"] > 0 and want["live"] == 1000
+        if case[0] == "limit_placed":
+            assert {1, 2, 3, 4} <= set(want["reasons"].tolist()) and want["live"] > 100
+    assert reasons == {1, 2, 3, 4}, reasons
+
+
 def _host(case, state=None):
     name, a, b, u, v, bu, bv, p, st = case
     st = state if state is not None else st

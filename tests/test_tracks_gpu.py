@@ -12,7 +12,7 @@ import numpy as np
 import pytest
 
 from conftest import ROOT
-from test_tracks_cpu import SCAN_T, TB, long_list_case, long_list_cases, long_list_steps, same_state, tracking_cases
+from test_tracks_cpu import LIMIT_SHAPES, SCAN_T, TB, limit_tracking_cases, long_list_case, long_list_cases, long_list_steps, same_state, tracking_cases
 
 pytestmark = pytest.mark.gpu
 
@@ -25,10 +25,10 @@ def _dev(arr):
     return p
 
 
-def rgba(img, fill=0):
+def rgba(img, fill=0, pad=0):
     h, w, _ = img.shape
-    out = np.full((h, w, 4), fill, np.uint8)
-    out[..., :3] = img
+    out = np.full((h, w + pad, 4), fill, np.uint8)          # pad: pixels beyond every row (a pitch larger than 4 * w)
+    out[:, :w, :3] = img
     return out
 
 
@@ -41,19 +41,19 @@ def _state(trk):
 class FramesStepper:
     """A tracker stepped through eppm_track_step_frames on device copies of the given planes."""
 
-    def __init__(self, h, w, **p):
+    def __init__(self, h, w, pad=0, **p):
         import eppm_amd
         self.e = eppm_amd.EPPM()
         self.e.init(h, w)
         self.t = eppm_amd.Tracker(self.e, **p)
-        self.h, self.w = h, w
+        self.h, self.w, self.pad = h, w, pad
 
     def step(self, a, b, u, v, bu, bv):
         from eppm_amd._lib import lib
-        bufs = [_dev(rgba(a, 7)), _dev(rgba(b, 9)), _dev(np.ascontiguousarray(np.stack([u, v], -1), np.float32)),
+        bufs = [_dev(rgba(a, 7, self.pad)), _dev(rgba(b, 9, self.pad)), _dev(np.ascontiguousarray(np.stack([u, v], -1), np.float32)),
                 _dev(np.ascontiguousarray(np.stack([bu, bv], -1), np.float32))]
         try:
-            self.t.step_frames(bufs[0].value, bufs[1].value, self.w * 4, bufs[2].value, bufs[3].value)
+            self.t.step_frames(bufs[0].value, bufs[1].value, (self.w + self.pad) * 4, bufs[2].value, bufs[3].value)
         finally:
             for p in bufs:
                 lib().eppm_free_device(p)
@@ -73,18 +73,23 @@ EMPTY = dict(ids=np.zeros(0, np.int32), starts=np.zeros(0, np.int32), xy=np.zero
 
 
 def test_kernels_equal_host_form_on_the_cpu_cases():
-    for name, a, b, u, v, bu, bv, p, st in tracking_cases():
+    check_cases(tracking_cases())
+
+
+def check_cases(cases, steps=4, pad=0):
+    """every case through `steps` chained steps of eppm_track_step_frames, each equal to the host form on the state before it; twice"""
+    for name, a, b, u, v, bu, bv, p, st in cases:
         h, w = u.shape
         runs = []
         for _ in range(2):
-            fs = FramesStepper(h, w, **p)
+            fs = FramesStepper(h, w, pad, **p)
             state = dict(EMPTY)
             if st is not None:
                 fs.t.set(*st)
                 state = dict(ids=st[0], starts=st[1], xy=st[2], next_id=st[3], frame=st[4])
             got_all = []
             imgs = (a, b)
-            for k in range(4):
+            for k in range(steps):
                 i1, i2 = imgs[k % 2], imgs[(k + 1) % 2]
                 got = fs.step(i1, i2, u, v, bu, bv)
                 same_state(got, _host_step(i1, i2, u, v, bu, bv, state, p), f"{name} step {k}")
@@ -94,6 +99,34 @@ def test_kernels_equal_host_form_on_the_cpu_cases():
             runs.append(got_all)
         for g0, g1 in zip(*runs):
             same_state(g1, g0, f"{name}: second run")
+
+
+@pytest.mark.parametrize("shape", range(len(LIMIT_SHAPES)), ids=[f"{w}x{h}" for w, h, _ in LIMIT_SHAPES])
+def test_kernels_equal_host_form_at_the_size_limit(shape):
+    """thin frames 8192 long with 1171 and 1639 cells along them (no multiple of 64, the last cell partial): seeds and tracks on the
+    first and last pixels of the long side, taps clamped at coordinate 8191, images under a pitch larger than 4 * w"""
+    check_cases(limit_tracking_cases(shape), steps=2, pad=3 + 61 * shape)
+
+
+TOL_LIMIT_CHILD = r"""
+import sys
+sys.path.insert(0, %r)
+import conftest          # (selects the test library: overridden below, before anything is loaded)
+import eppm_amd
+eppm_amd.select_library("tol")
+from test_tracks_cpu import limit_tracking_cases
+from test_tracks_gpu import check_cases
+print(eppm_amd.lib().eppm_version().decode())
+check_cases(limit_tracking_cases(int(sys.argv[1])), steps=2, pad=5)
+print("PART OK")
+""" % os.path.join(ROOT, "tests")
+
+
+@pytest.mark.parametrize("shape", range(len(LIMIT_SHAPES)), ids=[f"{w}x{h}" for w, h, _ in LIMIT_SHAPES])
+def test_tolerance_library_at_the_size_limit(shape):
+    out = subprocess.run([sys.executable, "-c", TOL_LIMIT_CHILD, str(shape)], capture_output=True, text=True, timeout=600)
+    assert out.returncode == 0 and out.stdout.strip().endswith("PART OK"), out.stdout[-2000:] + out.stderr[-2000:]
+    assert "tolerance arithmetic" in out.stdout.splitlines()[0]
 
 
 def _bidir(a, b):

@@ -23,10 +23,10 @@ def to_device(arr):
     return p
 
 
-def rgba(img, alpha=0x5a):
+def rgba(img, alpha=0x5a, pad=0):
     h, w, _ = img.shape
-    out = np.full((h, w, 4), alpha, np.uint8)           # the alpha byte of an input frame is ignored
-    out[..., :3] = img
+    out = np.full((h, w + pad, 4), alpha, np.uint8)     # the alpha byte of an input frame is ignored; pad: pixels beyond every row (the pitch)
+    out[:, :w, :3] = img
     return out
 
 
@@ -35,7 +35,8 @@ def device_step(c, runs=2):
     import eppm_amd
     from eppm_amd._lib import lib
     h, w = c["h"], c["w"]
-    planes = [to_device(rgba(c["img1"])), to_device(rgba(c["img2"])), to_device(np.stack([c["bu"], c["bv"]], -1).astype(np.float32)),
+    pad = c.get("pad", 0)
+    planes = [to_device(rgba(c["img1"], pad=pad)), to_device(rgba(c["img2"], pad=pad)), to_device(np.stack([c["bu"], c["bv"]], -1).astype(np.float32)),
               to_device(c["occ"])]
     flt = eppm_amd.TemporalFilter(None, c["thresh"], c["n_max"], size=(h, w))
     out = []
@@ -45,7 +46,7 @@ def device_step(c, runs=2):
                 flt.reset(0)
             else:
                 flt.set_state(0, c["acc"])
-            flt.step_frames(0, planes[0].value, planes[1].value, w * 4, planes[2].value, planes[3].value, c["cut"])
+            flt.step_frames(0, planes[0].value, planes[1].value, (w + pad) * 4, planes[2].value, planes[3].value, c["cut"])
             out.append((flt.state(0), flt.frame(0)))
     finally:
         flt.close()
@@ -66,11 +67,11 @@ def mismatches(cases):
 
 
 def main():
-    from test_tfilter_cpu import tfilter_cases          # (imports conftest, which selects the test library: overridden below, before anything is loaded)
+    from test_tfilter_cpu import tfilter_cases, tfilter_limit_cases          # (imports conftest, which selects the test library: overridden below, before anything is loaded)
     import eppm_amd
     eppm_amd.select_library("tol")
     print(eppm_amd.lib().eppm_version().decode())
-    cases = tfilter_cases()
+    cases = tfilter_limit_cases() if sys.argv[1:2] == ["limit"] else tfilter_cases()
     bad = mismatches(cases)
     print(f"{len(cases)} cases, {len(bad)} differ from the restatement: {bad[:5]}")
     assert not bad
