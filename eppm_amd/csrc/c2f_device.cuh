@@ -47,6 +47,11 @@
 #ifndef EPPM_C2F_PRE_EPS
 #define EPPM_C2F_PRE_EPS 0x1p-13f             // shrinks the lower bound: >= 4 x the float error of its two sides (tests/test_refine_pretest_cpu.py)
 #endif
+// A tile whose survivors exceed one list is drained in parts -- the pixels' halves, else their quarters, each through the same list -- and
+// stays in the two-phase form.  0: such a tile takes the one-phase loop after its pre-test, as before.
+#ifndef EPPM_C2F_PRE_PARTS
+#define EPPM_C2F_PRE_PARTS 1
+#endif
 #define EPPM_C2F_PRE_DMIN 0x1p-60f            // a tile with a centre-row weight sum not above this takes the one-phase loop (its costs may be 0/0)
 #define EPPM_C2F_PRE_RHSMIN 0x1p-100f         // no rejection unless best * (D_A + U) is a normal number this far from underflow
 #ifndef EPPM_C2F_SPLIT_BELOW_WAVES

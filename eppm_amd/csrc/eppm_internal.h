@@ -262,7 +262,7 @@ bool c2f_window_span(int R, int* span_x, int* span_y);          // test support:
 // form forced; both test support)
 void launch_c2f_refine(const PlanesH& P, float* flow, const float* lut, int R, float* cost9, hipStream_t s, Batch bt = kOnePair, bool no_split = false,
                        int pre = -1, unsigned* stat = nullptr, float* probe = nullptr);
-void c2f_pretest_knobs(int R, int* on, int* row0, int* rows, int* cap, float* eps, float* dmin, float* rhsmin);      // test support: that form's knobs
+void c2f_pretest_knobs(int R, int* on, int* row0, int* rows, int* cap, int* parts, float* eps, float* dmin, float* rhsmin);      // test support: that form's knobs
 // ---- coarse to fine: joint-bilateral smoothing (k_flow_blf.hip) ----
 void launch_flow_blf(float* out, const float* in, const uint32_t* img, int ipitch, int w, int h, int flow_pitch,
                      const float* blf_lut, hipStream_t s, Batch bt = kOnePair);

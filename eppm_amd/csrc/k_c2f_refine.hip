@@ -153,7 +153,7 @@ void k_c2f_refine_win(PlanesH Ph, float* __restrict__ flow_, const float* __rest
     __shared__ float4 s_win[WH * WW];
     __shared__ int s_mm[4];                                          // min ccx, max ccx, min ccy, max ccy of the tile's pixels
 #ifndef EPPM_TOL
-    __shared__ int s_pre[8];                                         // two-phase form: [0] a weight sum too small, [1 + p] survivors of pass p
+    __shared__ int s_pre[1];                                         // two-phase form: a weight sum of the tile is too small
 #endif
     float* __restrict__ flow = pair_ptr(flow_, pstride, blockIdx.y);
     const int ptid = threadIdx.y * kBlock + threadIdx.x;            // pixel of the tile
@@ -167,7 +167,7 @@ void k_c2f_refine_win(PlanesH Ph, float* __restrict__ flow_, const float* __rest
     if (!c2f_tile_origin<0>(P, x0, y0, part)) return;
     if (tid == 0) { s_mm[0] = 0x7fffffff; s_mm[1] = -0x7fffffff; s_mm[2] = 0x7fffffff; s_mm[3] = -0x7fffffff; }
 #ifndef EPPM_TOL
-    if (tid < 8) s_pre[tid] = 0;
+    if (tid == 0) s_pre[0] = 0;
 #endif
     for (int t = tid; t < TWU * TWU; t += 512) {
         const int ry = t / TWU, rx = t % TWU;
@@ -198,7 +198,7 @@ void k_c2f_refine_win(PlanesH Ph, float* __restrict__ flow_, const float* __rest
     __syncthreads();
 #ifndef EPPM_TOL
     // ---- the two-phase form of a coherent tile; every branch that holds a barrier is workgroup-uniform ----
-    int path = 3;                                    // statistics: 0 two-phase, 1 a weight sum too small, 2 survivor list full, 3 one-phase as before
+    int path = 3;                                    // statistics: 0 two-phase, 1 a weight sum too small, 2 list drained in parts (EPPM_C2F_PRE_PARTS 0: list full), 3 one-phase as before
     if (pre && coherent && mxx >= mnx) {
         constexpr int S = R + 1, I0 = (S - EPPM_C2F_PRE_ROWS) / 2, I1 = I0 + EPPM_C2F_PRE_ROWS;
         // The row padding of the source tile (TW - TWU texels per row, never staged, never read by a sample) carries the per-pixel
@@ -304,50 +304,93 @@ void k_c2f_refine_win(PlanesH Ph, float* __restrict__ flow_, const float* __rest
                 const int ta = __shfl_up(ia, d), tb = __shfl_up(ib, d);
                 if (lane >= d) { ia += ta; ib += tb; }
             }
-            const int pa = grp == 0 ? 3 : 1, pb = grp == 0 ? 2 : 0;          // wave-uniform: a wave lies in one group
-            int wa = 0, wb = 0;
-            if (lane == 63) { wa = atomicAdd(&s_pre[1 + pa], ia); wb = atomicAdd(&s_pre[1 + pb], ib); }
-            wa = __shfl(wa, 63); wb = __shfl(wb, 63);
+            // a wave = one quarter of the tile's pixels (ptid >> 6) in one pass group: its two totals, lane 63's prefix, go to the 16 words
+            // [quarter][pass] that the keys leave free at the end of their rows of padding
+            static_assert(KROWS * PADB >= 256 * 8 + 16 * 4, "the counts follow the keys");
+            auto qcnt_at = [&](int i) -> int* { return reinterpret_cast<int*>(pad(256 * 8 + i * 4)); };
+            const int wq = __builtin_amdgcn_readfirstlane((tid >> 6) & 3);
+            if (lane == 63) { *qcnt_at(wq * 4 + (grp == 0 ? 3 : 1)) = ia; *qcnt_at(wq * 4 + (grp == 0 ? 2 : 0)) = ib; }
             if (stat && tested) { atomicAdd(stat + 4, tested); atomicAdd(stat + 5, tested - (unsigned)(na + nb)); }
             __syncthreads();
-            // 4. the survivors of the tile, one list per pass in segments of whole 64-item chunks, evaluated by all eight waves
-            int cnt[4], chb[5];
-            chb[0] = 0;
+            int qc[4][4];                            // workgroup-uniform
 #pragma unroll
-            for (int p = 0; p < 4; p++) { cnt[p] = s_pre[1 + p]; chb[p + 1] = chb[p] + ((cnt[p] + 63) >> 6); }
+            for (int q = 0; q < 4; q++)
+#pragma unroll
+                for (int p = 0; p < 4; p++) qc[q][p] = __builtin_amdgcn_readfirstlane(*qcnt_at(q * 4 + p));
+            // chunks of the lists of the quarters [qlo, qhi): one list per pass, each rounded up to whole 64-item chunks
+            auto chunks_of = [&](int qlo, int qhi) {
+                int c = 0;
+#pragma unroll
+                for (int p = 0; p < 4; p++) {
+                    int s = 0;
+#pragma unroll
+                    for (int q = 0; q < 4; q++) s += (q >= qlo && q < qhi) ? qc[q][p] : 0;
+                    c += (s + 63) >> 6;
+                }
+                return c;
+            };
+            // 4. the survivors, one list per pass in segments of whole 64-item chunks, evaluated by all eight waves.  A tile whose survivors do
+            // not fit the list is drained in parts through the same list: the pixels' halves if each fits, else their quarters (a quarter holds
+            // at most 64 pixels x 8 candidates x 4 passes = 2 048 items).  Keys, items and costs are what one long list would give.
+            static_assert(64 * 8 * 4 <= CAP, "a quarter of the tile always fits the list");
+            int qw = 4;                              // quarters per part
+            if (chunks_of(0, 4) * 64 > CAP) qw = (chunks_of(0, 2) * 64 <= CAP && chunks_of(2, 4) * 64 <= CAP) ? 2 : 1;
             path = 2;
-            if (chb[4] * 64 <= CAP) {
-                path = 0;
-                {
-                    int at = chb[pa] * 64 + wa + ia - na;
-                    for (unsigned s = sa; s; s &= s - 1) *item_at(at++) = (uint16_t)(ptid | ((__ffs(s) - 1) << 8));
-                    at = chb[pb] * 64 + wb + ib - nb;
-                    for (unsigned s = sb; s; s &= s - 1) *item_at(at++) = (uint16_t)(ptid | ((__ffs(s) - 1) << 8));
-                }
-                __syncthreads();
-                for (int c = tid >> 6; c < chb[4]; c += 8) {
-                    const int p = __builtin_amdgcn_readfirstlane((c >= chb[1]) + (c >= chb[2]) + (c >= chb[3]));
-                    const int idx = (c - chb[p]) * 64 + lane;
-                    if (idx < cnt[p]) {
-                        const unsigned it = *item_at(chb[p] * 64 + idx);
-                        const int ip = it & 255, k = it >> 8, tx = ip & (kBlock - 1), ty = ip / kBlock;
-                        const int px = x0 + tx, py = y0 + ty;
-                        const int qcx = c2f_centre(flow[(py * P.w + px) * 2], px), qcy = c2f_centre(flow[(py * P.w + px) * 2 + 1], py);
-                        const int cx = (int)(int16_t)(qcx + k / 3 - 1);
-                        const int wbase = ((qcy - 1 + k % 3 - wy0) * WW + (cx - wx0)) * 16;
-                        const rgbf q1 = texel_rgb(s_src[(ty + R) * TW + tx + R]);
-                        const rgbf q2 = texel_rgb(*reinterpret_cast<const float4*>(reinterpret_cast<const char*>(s_win) + wbase));
-                        float c_;
-                        if (p == 3) c_ = c2f_one_win<R, 3, WW>(L, s_src, TW, tx, ty, q1, q2, s_win, wbase);
-                        else if (p == 2) c_ = c2f_one_win<R, 2, WW>(L, s_src, TW, tx, ty, q1, q2, s_win, wbase);
-                        else if (p == 1) c_ = c2f_one_win<R, 1, WW>(L, s_src, TW, tx, ty, q1, q2, s_win, wbase);
-                        else c_ = c2f_one_win<R, 0, WW>(L, s_src, TW, tx, ty, q1, q2, s_win, wbase);
-                        atomicMin(key_at(ip), ((unsigned long long)__float_as_uint(c_) << 4) | (unsigned)k);
+            if (qw == 4 || EPPM_C2F_PRE_PARTS) {
+                const int ba = ia - na, bb = ib - nb;            // this lane's items within its wave's
+#pragma unroll 1
+                for (int qlo = 0; qlo < 4; qlo += qw) {
+                    const int qhi = qlo + qw;
+                    int cnt[4], chb[5];
+                    chb[0] = 0;
+#pragma unroll
+                    for (int p = 0; p < 4; p++) {
+                        int s = 0;
+#pragma unroll
+                        for (int q = 0; q < 4; q++) s += (q >= qlo && q < qhi) ? qc[q][p] : 0;
+                        cnt[p] = s; chb[p + 1] = chb[p] + ((s + 63) >> 6);
                     }
+                    if (wq >= qlo && wq < qhi) {                 // wave-uniform; the waves of a part in quarter order: pixel order kept
+                        int oa = 0, ob = 0;
+#pragma unroll
+                        for (int q = 0; q < 3; q++) {
+                            const bool before = (q >= qlo && q < wq);
+                            oa += before ? (grp == 0 ? qc[q][3] : qc[q][1]) : 0;
+                            ob += before ? (grp == 0 ? qc[q][2] : qc[q][0]) : 0;
+                        }
+                        int at = (grp == 0 ? chb[3] : chb[1]) * 64 + oa + ba;
+                        for (unsigned s = sa; s; s &= s - 1) *item_at(at++) = (uint16_t)(ptid | ((__ffs(s) - 1) << 8));
+                        at = (grp == 0 ? chb[2] : chb[0]) * 64 + ob + bb;
+                        for (unsigned s = sb; s; s &= s - 1) *item_at(at++) = (uint16_t)(ptid | ((__ffs(s) - 1) << 8));
+                    }
+                    __syncthreads();
+                    for (int c = tid >> 6; c < chb[4]; c += 8) {
+                        const int p = __builtin_amdgcn_readfirstlane((c >= chb[1]) + (c >= chb[2]) + (c >= chb[3]));
+                        const int idx = (c - chb[p]) * 64 + lane;
+                        if (idx < cnt[p]) {
+                            const unsigned it = *item_at(chb[p] * 64 + idx);
+                            const int ip = it & 255, k = it >> 8, tx = ip & (kBlock - 1), ty = ip / kBlock;
+                            const int px = x0 + tx, py = y0 + ty;
+                            const int qcx = c2f_centre(flow[(py * P.w + px) * 2], px), qcy = c2f_centre(flow[(py * P.w + px) * 2 + 1], py);
+                            const int cx = (int)(int16_t)(qcx + k / 3 - 1);
+                            const int wbase = ((qcy - 1 + k % 3 - wy0) * WW + (cx - wx0)) * 16;
+                            const rgbf q1 = texel_rgb(s_src[(ty + R) * TW + tx + R]);
+                            const rgbf q2 = texel_rgb(*reinterpret_cast<const float4*>(reinterpret_cast<const char*>(s_win) + wbase));
+                            float c_;
+                            if (p == 3) c_ = c2f_one_win<R, 3, WW>(L, s_src, TW, tx, ty, q1, q2, s_win, wbase);
+                            else if (p == 2) c_ = c2f_one_win<R, 2, WW>(L, s_src, TW, tx, ty, q1, q2, s_win, wbase);
+                            else if (p == 1) c_ = c2f_one_win<R, 1, WW>(L, s_src, TW, tx, ty, q1, q2, s_win, wbase);
+                            else c_ = c2f_one_win<R, 0, WW>(L, s_src, TW, tx, ty, q1, q2, s_win, wbase);
+                            atomicMin(key_at(ip), ((unsigned long long)__float_as_uint(c_) << 4) | (unsigned)k);
+                        }
+                    }
+                    __syncthreads();                             // the list is free for the next part; after the last one the keys are final
                 }
-                __syncthreads();
                 // 5. the smallest cost, then the smallest candidate index: the reference's strict < in candidate order
-                if (stat && tid == 0) atomicAdd(stat + 0, 1u);
+                if (stat && tid == 0) {              // path 2 now: the list was drained in parts ([6] in halves, [7] in quarters)
+                    atomicAdd(stat + (qw == 4 ? 0 : 2), 1u);
+                    if (qw != 4) atomicAdd(stat + (qw == 2 ? 6 : 7), 1u);
+                }
                 if (grp != 1 || !inimg) return;
                 if (!known) { c2f_store_flow(flow, y * P.w + x, 0, 0); return; }
                 int k = (int)(*key_at(ptid) & 15u);
@@ -583,7 +626,7 @@ bool c2f_window_span(int R, int* span_x, int* span_y)
 }
 
 // the knobs the two-phase window refine was built with
-void c2f_pretest_knobs(int R, int* on, int* row0, int* rows, int* cap, float* eps, float* dmin, float* rhsmin)
+void c2f_pretest_knobs(int R, int* on, int* row0, int* rows, int* cap, int* parts, float* eps, float* dmin, float* rhsmin)
 {
 #ifdef EPPM_TOL
     *on = 0;                                     // the tolerance library's kernel has no two-phase form: `pre` is ignored there
@@ -592,6 +635,7 @@ void c2f_pretest_knobs(int R, int* on, int* row0, int* rows, int* cap, float* ep
 #endif
     *row0 = (R + 1 - EPPM_C2F_PRE_ROWS) / 2; *rows = EPPM_C2F_PRE_ROWS;
     *cap = C2fPreList<9>::CAP;                   // items of a tile's survivor list
+    *parts = EPPM_C2F_PRE_PARTS;                 // 1: a tile with more survivors is drained in parts, 0: it takes the one-phase loop
     *eps = EPPM_C2F_PRE_EPS; *dmin = EPPM_C2F_PRE_DMIN; *rhsmin = EPPM_C2F_PRE_RHSMIN;
 }
 
@@ -621,7 +665,8 @@ static void with_radius(int R, F&& f)
 
 // cost9: scratch of 36 floats per pixel, or NULL (never split)
 // pre: the two-phase form of k_c2f_refine_win<9>'s coherent tiles (-1 the library's EPPM_C2F_PRE, 0 off, 1 on); stat: NULL, or eight
-// zeroed counters of that kernel (tiles two-phase / weight sum too small / list full / one-phase, pairs tested, pairs rejected)
+// zeroed counters of that kernel (tiles two-phase with one list / weight sum too small / list drained in parts / one-phase, pairs tested, pairs
+// rejected, tiles drained in halves, in quarters)
 void launch_c2f_refine(const PlanesH& P, float* flow, const float* lut, int R, float* cost9, hipStream_t s, Batch bt, bool no_split, int pre,
                        unsigned* stat, float* probe)
 {

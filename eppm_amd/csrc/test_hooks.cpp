@@ -146,7 +146,7 @@ extern "C" int eppm_probe_search_pretest(int iteration, int w, int h, int patch_
 extern "C" int eppm_probe_c2f_pretest(int patch_r, int* out, float* fl)
 {
     if (!out || !fl || patch_r != 9) return set_err(EPPM_ERR_ARG, "eppm_probe_c2f_pretest: bad argument (the two-phase form exists at patch_r 9)");
-    c2f_pretest_knobs(patch_r, &out[0], &out[1], &out[2], &out[3], &fl[0], &fl[1], &fl[2]);
+    c2f_pretest_knobs(patch_r, &out[0], &out[1], &out[2], &out[3], &out[4], &fl[0], &fl[1], &fl[2]);
     return EPPM_OK;
 }
 extern "C" int eppm_probe_fast_exp(const float* x, float* y, int n) { return probe(x, y, n, 0); }

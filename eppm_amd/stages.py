@@ -326,10 +326,10 @@ def c2f_refine_batch(flows, planes):
     return [out[k * h:(k + 1) * h] for k in range(n)]
 
 
-def c2f_refine_pre(flows, planes, pre):
+def c2f_refine_pre(flows, planes, pre, parts=False):
     """eppm_test_c2f_refine_pre (test library): c2f_refine_batch with the window kernel's coherent tiles one-phase (pre = 0) or two-phase
-    (pre = 1).  Returns (refined flow per pair, the kernel's counters: tiles two-phase, tiles with a weight sum too small, tiles with a full
-    survivor list, other tiles, pairs tested, pairs rejected)."""
+    (pre = 1).  Returns (refined flow per pair, the kernel's counters: tiles two-phase, tiles with a weight sum too small, tiles with more
+    survivors than one list holds, other tiles, pairs tested, pairs rejected; with `parts` also: tiles drained in halves, in quarters)."""
     n = len(flows)
     h, w = flows[0].shape
     f = Dev(np.concatenate([np.ascontiguousarray(x, float2) for x in flows]))
@@ -337,7 +337,7 @@ def c2f_refine_pre(flows, planes, pre):
     stat = (C.c_uint * 8)()
     check(lib().eppm_test_c2f_refine_pre(f.ptr, i1.ptr, i2.ptr, c1.ptr, c2.ptr, w, h, n, int(pre), stat), "eppm_test_c2f_refine_pre")
     out = f.get()
-    return [out[k * h:(k + 1) * h] for k in range(n)], tuple(stat[:6])
+    return [out[k * h:(k + 1) * h] for k in range(n)], tuple(stat[:8 if parts else 6])
 
 
 def c2f_refine_probe(flows, planes):
@@ -356,10 +356,20 @@ def c2f_refine_probe(flows, planes):
 def probe_c2f_pretest(patch_r=9):
     """eppm_probe_c2f_pretest (test library, no GPU needed): (on by default?, first centre row, centre rows, items of a tile's survivor
     list, eps, smallest admissible weight sum, smallest right-hand side that may reject)"""
-    out = (C.c_int * 4)()
+    out, fl = _c2f_pretest_knobs(patch_r)
+    return bool(out[0]), out[1], out[2], out[3], fl[0], fl[1], fl[2]
+
+
+def probe_c2f_parts(patch_r=9):
+    """eppm_probe_c2f_pretest's fifth knob: does a tile with more survivors than one list holds stay two-phase, drained in parts?"""
+    return bool(_c2f_pretest_knobs(patch_r)[0][4])
+
+
+def _c2f_pretest_knobs(patch_r):
+    out = (C.c_int * 5)()
     fl = (C.c_float * 3)()
     check(lib().eppm_probe_c2f_pretest(patch_r, out, fl), "eppm_probe_c2f_pretest")
-    return bool(out[0]), out[1], out[2], out[3], fl[0], fl[1], fl[2]
+    return out, fl
 
 
 def blf_c2f(flow_coarse, P_fine, coarse_dims):

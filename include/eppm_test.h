@@ -58,9 +58,10 @@ int  eppm_probe_c2f_window(int patch_r, int* span_x, int* span_y);
 int  eppm_test_c2f_refine_batch(float* d_flow, const uint32_t* d_img1, const uint32_t* d_img2, const uint8_t* d_census1,
                                 const uint8_t* d_census2, int w, int h, int npairs);
 /* The same launch with the form of the window kernel's coherent tiles chosen here (pre = 0 one-phase, 1 two-phase, -1 as built) and with
- * that kernel's counters, summed over the launch, in stat[0..7] (host memory): tiles in the two-phase form, tiles sent to the one-phase loop
- * because a centre-row weight sum was too small, because the survivor list was full, tiles one-phase for any other reason (incoherent, no
- * known pixel, pre = 0), (candidate, pass) pairs tested, pairs rejected; the rest 0. */
+ * that kernel's counters, summed over the launch, in stat[0..7] (host memory): tiles in the two-phase form with one survivor list, tiles sent
+ * to the one-phase loop because a centre-row weight sum was too small, tiles whose survivors exceeded one list -- drained in parts, still in
+ * the two-phase form, or, in a library built without that (eppm_probe_c2f_pretest), sent to the one-phase loop --, tiles one-phase for any
+ * other reason (incoherent, no known pixel, pre = 0), (candidate, pass) pairs tested, pairs rejected, tiles drained in halves, in quarters. */
 int  eppm_test_c2f_refine_pre(float* d_flow, const uint32_t* d_img1, const uint32_t* d_img2, const uint8_t* d_census1,
                               const uint8_t* d_census2, int w, int h, int npairs, int pre, unsigned* stat);
 /* The same launch in the two-phase form by the kernel's probing instantiation (the same code, which also stores what its pre-test formed):
@@ -70,7 +71,8 @@ int  eppm_test_c2f_refine_pre(float* d_flow, const uint32_t* d_img1, const uint3
 int  eppm_test_c2f_refine_probe(float* d_flow, const uint32_t* d_img1, const uint32_t* d_img2, const uint8_t* d_census1,
                                 const uint8_t* d_census2, int w, int h, int npairs, float* d_probe);
 /* The knobs the two-phase window refine was built with (pure host code): out[0] = on by default (0 in the tolerance library, whose kernel has no such form), out[1] the first and out[2] the number of
- * the patch rows its pre-test evaluates, out[3] the items a tile's survivor list holds; fl[0] = eps (the lower bound is shrunk by 1 - eps),
+ * the patch rows its pre-test evaluates, out[3] the items a tile's survivor list holds, out[4] = 1 if a tile with more survivors is drained in
+ * parts (0: it takes the one-phase loop); fl[0] = eps (the lower bound is shrunk by 1 - eps),
  * fl[1] = the weight sum at or below which a tile takes the one-phase loop, fl[2] = the smallest right-hand side that may reject. */
 int  eppm_probe_c2f_pretest(int patch_r, int* out, float* fl);
 /* ONE random-search launch over npairs x ndir problems of one size, as a context issues it: the entry builds the census and texel planes,

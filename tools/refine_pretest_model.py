@@ -9,8 +9,10 @@ minimum over the passes.  Per coherent tile the kernel forms N = sum_A c_t w_t, 
 (k, p), the pixel's rest weight U, names k* = the candidate with the smallest min(N / D_A) over passes 1 and 0 (first index on ties),
 evaluates k*'s four passes in full (B = their minimum) and rejects every other (k, p) iff, in float32 and by products,
     N (1 - eps) >= B (D_A + U)   and   B (D_A + U) >= rhsmin.
-A tile with a valid pair whose D_A is not above dmin, or whose survivors (per pass, rounded up to whole 64-item chunks) exceed the list's
-capacity, takes the one-phase loop instead."""
+A tile with a valid pair whose D_A is not above dmin takes the one-phase loop instead.  A tile whose survivors (per pass, rounded up to
+whole 64-item chunks) exceed the list's capacity is drained through that list in parts: the halves of its pixels (tile rows 0-7, 8-15) if
+each fits, else the quarters (4 rows each), which always fit (tile_split, drain_in_parts); a library built with EPPM_C2F_PRE_PARTS = 0 sends
+it to the one-phase loop."""
 import numpy as np
 
 import search_pretest_model as M
@@ -163,11 +165,55 @@ def flow_of_best(r):
     return fx, fy
 
 
-def tile_paths(r, span_x, span_y, cap):
-    """what k_c2f_refine_win<9> counts over one launch: tiles two-phase, tiles with a weight sum too small, tiles whose survivor list is
-    full, other tiles (incoherent or without a known pixel), pairs tested, pairs rejected"""
+def quarter_survivors(r, tile):
+    """(4, 4) survivors of a tile = (slice, slice) by [quarter of its pixels: 4 tile rows, one wave per pass group][pass]"""
+    s = np.zeros((16, 16, 4, 9), bool)
+    v = (r["tested"][tile] & ~r["rej"][tile])
+    s[:v.shape[0], :v.shape[1]] = v
+    return s.reshape(4, 4, 16, 4, 9).sum((1, 2, 4))
+
+
+def tile_split(qs, cap):
+    """parts (1, 2 or 4) in which the kernel drains a tile with the survivors qs = quarter_survivors(): the coarsest split whose every
+    part fits the list, one segment of whole 64-item chunks per pass"""
+    def fits(q0, q1):
+        return int(((qs[q0:q1].sum(0) + 63) // 64).sum()) * 64 <= cap
+    if fits(0, 4):
+        return 1
+    return 2 if fits(0, 2) and fits(2, 4) else 4
+
+
+def drain_in_parts(r, tile, nparts, cap=None):
+    """The kernel's steps 4 and 5 for one tile = (slice, slice) of a refine(...) whose survivors' costs are known: the survivors go through
+    the list part by part -- per part one list per pass, pixels in tile order, a pixel's candidates in index order --, every item lowers its
+    pixel's 64-bit key (bits(cost) << 4) | k, seeded with k*'s (bits(B) << 4) | k*.  Returns (the selected candidate per pixel, 4 where a
+    pixel has no valid candidate, and the largest number of list items a part needed); cap: assert that every part fits."""
+    kstar, B = r["kstar"][tile], r["B"][tile]
+    th, tw = kstar.shape
+    key = np.where(kstar != 15, (B.view(np.uint32).astype(np.uint64) << np.uint64(4)) | kstar.astype(np.uint64), np.uint64(15))
+    surv, cost = r["tested"][tile] & ~r["rej"][tile], r["cost"][tile]
+    rows, most = 16 // nparts, 0
+    for part in range(nparts):
+        lists = [[(y, x, k) for y in range(part * rows, min((part + 1) * rows, th)) for x in range(tw) for k in range(9) if surv[y, x, p, k]]
+                 for p in range(4)]
+        items = sum((len(li) + 63) // 64 for li in lists) * 64
+        most = max(most, items)
+        assert cap is None or items <= cap, (part, nparts, items, cap)
+        for p in range(4):
+            for y, x, k in lists[p]:
+                c = cost[y, x, p, k]
+                assert not np.isnan(c)
+                key[y, x] = min(key[y, x], (np.uint64(np.float32(c).view(np.uint32)) << np.uint64(4)) | np.uint64(k))
+    best = (key & np.uint64(15)).astype(np.int64)
+    return np.where(best == 15, 4, best), most
+
+
+def tile_paths(r, span_x, span_y, cap, parts=False):
+    """what k_c2f_refine_win<9> counts over one launch: tiles two-phase with one list, tiles with a weight sum too small, tiles whose
+    survivors exceed one list, other tiles (incoherent or without a known pixel), pairs tested, pairs rejected; parts: and the tiles of the
+    third kind drained in halves, in quarters"""
     h, w = r["best"].shape
-    out = [0, 0, 0, 0, 0, 0]
+    out = [0, 0, 0, 0, 0, 0, 0, 0]
     for y0 in range(0, h, 16):
         for x0 in range(0, w, 16):
             t = (slice(y0, y0 + 16), slice(x0, x0 + 16))
@@ -185,5 +231,9 @@ def tile_paths(r, span_x, span_y, cap):
             out[4] += int(r["tested"][t].sum())
             out[5] += int(r["rej"][t].sum())
             surv = (r["tested"][t] & ~r["rej"][t]).sum((0, 1, 3))          # per pass
-            out[2 if int(((surv + 63) // 64).sum()) * 64 > cap else 0] += 1
-    return tuple(out)
+            split = tile_split(quarter_survivors(r, t), cap)
+            assert (split == 1) == (int(((surv + 63) // 64).sum()) * 64 <= cap)
+            out[0 if split == 1 else 2] += 1
+            if split != 1:
+                out[6 if split == 2 else 7] += 1
+    return tuple(out if parts else out[:6])
