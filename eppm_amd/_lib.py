@@ -9,6 +9,13 @@ class EppmError(RuntimeError):
     pass
 
 
+class _Record(C.Structure):
+    """a struct of integer fields that the library fills in"""
+
+    def as_dict(self):
+        return {k: int(getattr(self, k)) for k, _ in self._fields_}
+
+
 class CParams(C.Structure):
     _fields_ = [("patch_r", C.c_int), ("num_iter", C.c_int), ("search_range", C.c_int), ("num_guess", C.c_int),
                 ("seg_len", C.c_int), ("wmf_iters", C.c_int), ("seed", C.c_ulonglong), ("propagation", C.c_int),
@@ -72,109 +79,108 @@ class CDefectParams(C.Structure):
     _fields_ = [("detect", C.c_float), ("agree", C.c_float), ("radius", C.c_int), ("grow", C.c_int)]
 
 
-class CDefectStats(C.Structure):
+class CDefectStats(_Record):
     _fields_ = [("hit", C.c_int), ("grown", C.c_int), ("second_chance", C.c_int), ("undecided", C.c_int)]
-
-    def as_dict(self):
-        return {k: int(getattr(self, k)) for k, _ in self._fields_}
 
 
 class CDeflickerParams(C.Structure):
     _fields_ = [("cell", C.c_int), ("iters", C.c_int), ("reject", C.c_float), ("tau", C.c_float), ("keep", C.c_float), ("n_min", C.c_int)]
 
 
-class CDeflickerStats(C.Structure):
+class CDeflickerStats(_Record):
     _fields_ = [("used", C.c_int64), ("valid_cells", C.c_int32), ("cells", C.c_int32)]
 
-    def as_dict(self):
-        return {k: int(getattr(self, k)) for k, _ in self._fields_}
 
-
-class CObject(C.Structure):
+class CObject(_Record):
     _fields_ = [("id", C.c_int32), ("age", C.c_int32), ("area", C.c_int32), ("x0", C.c_int32), ("y0", C.c_int32), ("x1", C.c_int32),
                 ("y1", C.c_int32), ("n_flow", C.c_int32), ("sum_x", C.c_int64), ("sum_y", C.c_int64), ("sum_qu", C.c_int64), ("sum_qv", C.c_int64)]
 
-    def as_dict(self):
-        return {k: int(getattr(self, k)) for k, _ in self._fields_}
 
-
-class CObjectsCounts(C.Structure):
+class CObjectsCounts(_Record):
     _fields_ = [("n", C.c_int32), ("n_found", C.c_int32), ("n_components", C.c_int32), ("next_id", C.c_int32)]
 
-    def as_dict(self):
-        return {k: int(getattr(self, k)) for k, _ in self._fields_}
 
-
-class CTrackCounts(C.Structure):
+class CTrackCounts(_Record):
     _fields_ = [("live", C.c_int), ("ended", C.c_int), ("seeded", C.c_int), ("dropped", C.c_int), ("frame", C.c_int), ("next_id", C.c_int)]
-
-    def as_dict(self):
-        return {k: int(getattr(self, k)) for k, _ in self._fields_}
 
 
 _lib = None
 
-# every symbol include/eppm.h declares (tests check that the library exports all of them)
-SYMBOLS = [
-    "eppm_default_params", "eppm_create", "eppm_create_batch", "eppm_batch_size", "eppm_batch_set_images", "eppm_batch_set_images_device",
-    "eppm_batch_compute", "eppm_batch_compute_device", "eppm_batch_compute_end", "eppm_batch_get_plane", "eppm_destroy", "eppm_set_stream", "eppm_set_images", "eppm_set_images_device",
-    "eppm_compute", "eppm_compute_begin", "eppm_compute_end", "eppm_compute_device", "eppm_synchronize", "eppm_num_levels", "eppm_level_dims", "eppm_get_plane",
-    "eppm_stage_times", "eppm_clear_stage_times", "eppm_enable_stage_timing", "eppm_last_error", "eppm_version",
-    "eppm_device_count", "eppm_set_device", "eppm_malloc_device", "eppm_malloc_pitched", "eppm_free_device",
-    "eppm_memcpy_h2d", "eppm_memcpy_d2h", "eppm_memcpy2d_h2d", "eppm_memcpy2d_d2h", "eppm_memset_device",
-    "eppm_device_synchronize", "eppm_device_mem_info", "eppm_device_pci_bus_id", "eppm_bind_thread_to_device", "eppm_release_cached_memory", "eppm_set_launcher_stream", "eppm_set_launcher_params", "eppm_launcher_status",
-    "baoCudaPatchMatchMultiscalePrepare", "baoCudaCensusTransform", "baoCudaPatchMatch", "baoCudaLeftRightCheck",
-    "baoCudaOutlierRemoval", "baoCudaWeightedMedianFilter", "baoCudaFillHole", "baoCudaNNF2Flow", "baoCudaBLF_C2F",
-    "baoCudaBLFCostFilterRefine", "baoCudaFlowSmoothing", "eppm_flow_to_color", "eppm_compute_color",
-    "eppm_pm_rng_create", "eppm_pm_rng_reset", "eppm_pm_rng_destroy", "eppm_pm_rng_block_states", "eppm_pm_gen_rand_field",
-    "eppm_pm_cost_field", "eppm_pm_seg_propagate", "eppm_pm_jump_propagate", "eppm_pm_parallel_propagate", "eppm_pm_random_search", "eppm_gauss_filter_rgba", "eppm_resize_rgba",
-    "eppm_resize_flow",
-    "eppm_host_register", "eppm_host_unregister", "eppm_host_is_registered", "eppm_host_alloc", "eppm_host_free",
-    "eppm_compute_begin_into", "eppm_batch_compute_begin_into",
-    "eppm_load_ppm", "eppm_ppm_size", "eppm_save_flo", "eppm_load_flo", "eppm_flo_size", "eppm_flow_error",
-    "eppm_flow_error_border", "eppm_flow_error_percentage", "eppm_flow_cutoff", "eppm_flow_to_color_host",
-    "eppm_compute_bidirectional", "eppm_compute_bidirectional_device", "eppm_batch_compute_bidirectional", "eppm_set_occlusion_params",
-    "eppm_fb_occlusion", "eppm_fb_occlusion_host",
-    "eppm_interpolate", "eppm_interpolate_device", "eppm_batch_interpolate", "eppm_interpolate_frames", "eppm_interpolate_host",
-    "eppm_track_default_params", "eppm_track_capacity", "eppm_tracker_create", "eppm_tracker_destroy", "eppm_track_step",
-    "eppm_track_step_frames", "eppm_tracker_get", "eppm_tracker_get_ended", "eppm_tracker_set", "eppm_track_step_host", "eppm_track_seeds_host",
-    "eppm_push_image", "eppm_push_image_device", "eppm_set_temporal", "eppm_temporal_reset", "eppm_temporal_valid", "eppm_temporal_prior_host",
-    "eppm_temporal_prior",
-    "eppm_batch_set_temporal", "eppm_batch_push_images", "eppm_batch_push_images_device", "eppm_batch_temporal_valid", "eppm_batch_temporal_reset",
-    "eppm_temporal_prior_batch",
-    "eppm_set_stop_level", "eppm_stop_level", "eppm_flow_upsample",
-    "eppm_tfilter_default_params", "eppm_tfilter_create", "eppm_tfilter_create_size", "eppm_tfilter_destroy", "eppm_tfilter_reset", "eppm_tfilter_step",
-    "eppm_tfilter_step_frames", "eppm_tfilter_get", "eppm_tfilter_get_device", "eppm_tfilter_get_state", "eppm_tfilter_set_state",
-    "eppm_tfilter_seed_host", "eppm_tfilter_step_host",
-    "eppm_stab_default_params", "eppm_stab_create", "eppm_stab_create_size", "eppm_stab_destroy", "eppm_stab_reset", "eppm_stab_step",
-    "eppm_stab_step_frames", "eppm_stab_get", "eppm_stab_get_device", "eppm_stab_get_mask", "eppm_stab_get_model", "eppm_stab_get_path",
-    "eppm_stab_set_path", "eppm_gmotion_fit_host", "eppm_stab_update_host", "eppm_stab_warp_host",
-    "eppm_cutdet_default_params", "eppm_cutdet_create", "eppm_cutdet_create_size", "eppm_cutdet_destroy", "eppm_cutdet_step",
-    "eppm_cutdet_step_frames", "eppm_cutdet_get", "eppm_cutdet_cuts", "eppm_cutdet_host",
-    "eppm_mblur_default_params", "eppm_motion_blur", "eppm_motion_blur_device", "eppm_batch_motion_blur", "eppm_motion_blur_frames",
-    "eppm_motion_blur_host",
-    "eppm_cmap_default_params", "eppm_cmap_create", "eppm_cmap_create_size", "eppm_cmap_destroy", "eppm_cmap_reset", "eppm_cmap_step",
-    "eppm_cmap_step_frames", "eppm_cmap_get_state", "eppm_cmap_set_state", "eppm_cmap_set_layer", "eppm_cmap_render", "eppm_cmap_render_device",
-    "eppm_cmap_age", "eppm_cmap_step_host", "eppm_cmap_render_host",
-    "eppm_objects_default_params", "eppm_objects_create", "eppm_objects_create_size", "eppm_objects_destroy", "eppm_objects_reset",
-    "eppm_objects_step", "eppm_objects_step_frames", "eppm_objects_get", "eppm_objects_get_labels", "eppm_objects_get_state",
-    "eppm_objects_set_state", "eppm_objects_label_host", "eppm_objects_carry_host", "eppm_objects_assign_host",
-    "eppm_plate_default_params", "eppm_plate_create", "eppm_plate_create_size", "eppm_plate_destroy", "eppm_plate_reset", "eppm_plate_canvas_dims",
-    "eppm_plate_step", "eppm_plate_step_frames", "eppm_plate_render", "eppm_plate_render_frames", "eppm_plate_get", "eppm_plate_get_device",
-    "eppm_plate_get_mask", "eppm_plate_get_path", "eppm_plate_set_path", "eppm_plate_get_state", "eppm_plate_set_state",
-    "eppm_plate_forms_host", "eppm_plate_block_host", "eppm_plate_accumulate_host", "eppm_plate_render_host",
-    "eppm_defect_default_params", "eppm_defect_create", "eppm_defect_create_size", "eppm_defect_destroy", "eppm_defect_reset", "eppm_defect_step",
-    "eppm_defect_step_frames", "eppm_defect_get", "eppm_defect_get_device", "eppm_defect_get_mask", "eppm_defect_get_stats",
-    "eppm_defect_get_state", "eppm_defect_set_state", "eppm_defect_step_host",
-    "eppm_deflicker_default_params", "eppm_deflicker_create", "eppm_deflicker_create_size", "eppm_deflicker_destroy", "eppm_deflicker_reset",
-    "eppm_deflicker_step", "eppm_deflicker_step_frames", "eppm_deflicker_get", "eppm_deflicker_get_device", "eppm_deflicker_get_field",
-    "eppm_deflicker_get_stats", "eppm_deflicker_get_state", "eppm_deflicker_set_state", "eppm_deflicker_step_host",
-]
+_CODES = {"P": C.c_void_p, "S": C.c_char_p, "I": C.c_int, "Z": C.c_size_t, "F": C.c_float, "B": C.c_bool, "V": None}
 
+
+def _signatures(text):
+    """"name:ARGS" or "name:R>ARGS" per function, one letter per argument: P any pointer, S const char*, I int / int32_t, Z size_t, F float,
+    B bool; R the return type, I where it is left out, S const char*, V void -> {name: (restype, argtypes)}"""
+    out = {}
+    for item in text.split():
+        name, _, sig = item.partition(":")
+        ret, _, args = sig.rpartition(">")
+        out[name] = (_CODES[ret or "I"], [_CODES[c] for c in args])
+    return out
+
+
+# THE BINDING: every function include/eppm.h declares, in the header's order (tests/test_abi_cpu.py checks the table against the prototypes
+# and that the library exports every name).  lib() declares these types, so a call passes addresses, sizes and floats as plain numbers.
+_ABI = _signatures("""
+eppm_default_params:P eppm_create:PIIIP eppm_destroy:P eppm_set_stream:PP eppm_set_images:PPPZ eppm_host_register:PZ eppm_host_unregister:P
+eppm_host_is_registered:PZ eppm_host_alloc:PZ eppm_host_free:P eppm_set_images_device:PPPZ eppm_create_batch:PIIIPI eppm_batch_size:P
+eppm_batch_set_images:PIPPZ eppm_batch_set_images_device:PIPPZ eppm_batch_compute:PPP eppm_batch_compute_device:PP eppm_batch_compute_end:PPP
+eppm_batch_compute_begin_into:PPP eppm_batch_get_plane:PISIPZ eppm_compute:PPP eppm_compute_begin:P eppm_compute_end:PPP eppm_compute_begin_into:PPP
+eppm_compute_color:PPZFF eppm_compute_device:PP eppm_synchronize:P eppm_num_levels:P eppm_level_dims:PIPP eppm_get_plane:PSIPZ
+eppm_compute_bidirectional:PPPPPPP eppm_compute_bidirectional_device:PPPPP eppm_batch_compute_bidirectional:PPPPPPP eppm_set_occlusion_params:PFF
+eppm_set_stop_level:PI eppm_stop_level:P eppm_fb_occlusion:PPPIIFF eppm_interpolate:PIPPZ eppm_interpolate_device:PIPPZ eppm_batch_interpolate:PIPPZ
+eppm_interpolate_frames:PZPPZPPPIIF eppm_interpolate_host:PPPPPPPIIF eppm_mblur_default_params:P eppm_motion_blur:PPIPZ eppm_motion_blur_device:PPIPZ
+eppm_batch_motion_blur:PPIPZ eppm_motion_blur_frames:PZPZPIIP eppm_motion_blur_host:PPPPIIP eppm_track_default_params:P eppm_track_capacity:PII
+eppm_tracker_create:PPP eppm_tracker_destroy:P eppm_track_step:PPI eppm_track_step_frames:PPPZPPII eppm_tracker_get:PIPPPP
+eppm_tracker_get_ended:PIPPPPP eppm_tracker_set:PIPPPII eppm_track_step_host:PPPPPPPIIIPPPIIPPPPPPPP eppm_track_seeds_host:PPIIIPP eppm_push_image:PPZ
+eppm_push_image_device:PPZ eppm_set_temporal:PI eppm_temporal_reset:P eppm_temporal_valid:P eppm_temporal_prior_host:PPIII eppm_temporal_prior:PPIII
+eppm_batch_set_temporal:PI eppm_batch_push_images:PIPZP eppm_batch_push_images_device:PIPZP eppm_batch_temporal_valid:PI eppm_batch_temporal_reset:PI
+eppm_temporal_prior_batch:PPIIIIP eppm_tfilter_default_params:P eppm_tfilter_create:PPP eppm_tfilter_create_size:IIIIPP eppm_tfilter_destroy:P
+eppm_tfilter_reset:PI eppm_tfilter_step:PPP eppm_tfilter_step_frames:PIPPZPPI eppm_tfilter_get:PIPZ eppm_tfilter_get_device:PIPZ
+eppm_tfilter_get_state:PIP eppm_tfilter_set_state:PIP eppm_tfilter_seed_host:PPII eppm_tfilter_step_host:PPPPPPPPIII eppm_deflicker_default_params:P
+eppm_deflicker_create:PPP eppm_deflicker_create_size:IIIIPP eppm_deflicker_destroy:P eppm_deflicker_reset:PI eppm_deflicker_step:PPP
+eppm_deflicker_step_frames:PIPPZPPI eppm_deflicker_get:PIPZ eppm_deflicker_get_device:PIPZ eppm_deflicker_get_field:PIPP eppm_deflicker_get_stats:PIP
+eppm_deflicker_get_state:PIPP eppm_deflicker_set_state:PIPI eppm_deflicker_step_host:PPPPPPPPPPIII eppm_defect_default_params:P eppm_defect_create:PPP
+eppm_defect_create_size:IIIIPP eppm_defect_destroy:P eppm_defect_reset:PI eppm_defect_step:PPP eppm_defect_step_frames:PIPPZPPI eppm_defect_get:PIPZ
+eppm_defect_get_device:PIPZ eppm_defect_get_mask:PIP eppm_defect_get_stats:PIP eppm_defect_get_state:PIPPP eppm_defect_set_state:PIPPI
+eppm_defect_step_host:PPPPPPPPPPPII eppm_stab_default_params:P eppm_stab_create:PPP eppm_stab_create_size:IIIIPP eppm_stab_destroy:P
+eppm_stab_reset:PI eppm_stab_step:PPP eppm_stab_step_frames:PIPZPPI eppm_stab_get:PIPZ eppm_stab_get_device:PIPZ eppm_stab_get_mask:PIP
+eppm_stab_get_model:PIP eppm_stab_get_path:PIPPP eppm_stab_set_path:PIP eppm_gmotion_fit_host:PPPPIIPP eppm_stab_update_host:PPPPIP
+eppm_stab_warp_host:PPIIP eppm_cutdet_default_params:P eppm_cutdet_create:PPP eppm_cutdet_create_size:IIIIPP eppm_cutdet_destroy:P eppm_cutdet_step:PP
+eppm_cutdet_step_frames:PIPPZPPP eppm_cutdet_get:PIP eppm_cutdet_cuts:PIP eppm_cutdet_host:PPPPPPPIIP eppm_cmap_default_params:P eppm_cmap_create:PPP
+eppm_cmap_create_size:IIIIPP eppm_cmap_destroy:P eppm_cmap_reset:PI eppm_cmap_step:PPP eppm_cmap_step_frames:PIPPZPPI eppm_cmap_get_state:PIP
+eppm_cmap_set_state:PIPPZ eppm_cmap_set_layer:PIPZ eppm_cmap_render:PIPZ eppm_cmap_render_device:PIPZ eppm_cmap_age:PI eppm_cmap_step_host:PPPPPPPPIII
+eppm_cmap_render_host:PPPPPII eppm_objects_default_params:P eppm_objects_create:PPP eppm_objects_create_size:IIIIPP eppm_objects_destroy:P
+eppm_objects_reset:PI eppm_objects_step:PPP eppm_objects_step_frames:PIPPPPI eppm_objects_get:PIIPP eppm_objects_get_labels:PIP
+eppm_objects_get_state:PIPPPP eppm_objects_set_state:PIPPPI eppm_objects_label_host:PPPPIIPPP eppm_objects_carry_host:PPPPIIP
+eppm_objects_assign_host:PPPIIIPPPP eppm_plate_default_params:P eppm_plate_create:PPP eppm_plate_create_size:IIIIPP eppm_plate_destroy:P
+eppm_plate_reset:PI eppm_plate_canvas_dims:PPP eppm_plate_step:PPP eppm_plate_step_frames:PIPZPPI eppm_plate_render:PPIPZP
+eppm_plate_render_frames:PIPZPPPZP eppm_plate_get:PIPZP eppm_plate_get_device:PIPZ eppm_plate_get_mask:PIP eppm_plate_get_path:PIP
+eppm_plate_set_path:PIP eppm_plate_get_state:PIP eppm_plate_set_state:PIP eppm_plate_forms_host:PPPP eppm_plate_block_host:PPIIP
+eppm_plate_accumulate_host:PPPPIIP eppm_plate_render_host:PPIPPIIPPP eppm_stage_times:PPPI eppm_clear_stage_times:P eppm_enable_stage_timing:PI
+eppm_last_error:S> eppm_version:S> eppm_device_count:P eppm_set_device:I eppm_malloc_device:PZ eppm_malloc_pitched:PPZZ eppm_free_device:P
+eppm_memcpy_h2d:PPZ eppm_memcpy_d2h:PPZ eppm_memcpy2d_h2d:PZPZZZ eppm_memcpy2d_d2h:PZPZZZ eppm_memset_device:PIZ eppm_device_synchronize:
+eppm_device_pci_bus_id:IPZ eppm_bind_thread_to_device:IPP eppm_device_mem_info:PP eppm_release_cached_memory: eppm_set_launcher_stream:P
+eppm_set_launcher_params:P eppm_launcher_status: baoCudaPatchMatchMultiscalePrepare:V>PPPPPPPPPPIPPII baoCudaCensusTransform:V>PPPPIIZZ
+baoCudaPatchMatch:V>PPPPPPIIZZZZ baoCudaLeftRightCheck:V>PPPPIIZZ baoCudaOutlierRemoval:V>PPIIZZ baoCudaWeightedMedianFilter:V>PPPIIZZZIB
+baoCudaFillHole:V>PPPIIZZZ baoCudaNNF2Flow:V>PPIIZZ baoCudaBLF_C2F:V>PPPPPPPPPPPI baoCudaBLFCostFilterRefine:V>PPPPPIIZZ baoCudaFlowSmoothing:V>PPIIZZ
+eppm_flow_to_color:PPIIFF eppm_pm_rng_create:PIIP eppm_pm_rng_reset:P eppm_pm_rng_destroy:P eppm_pm_rng_block_states:PPZ eppm_pm_gen_rand_field:PPIIZ
+eppm_pm_cost_field:PPPPPPIIZZZZ eppm_pm_seg_propagate:PPPPPPIIZZZZI eppm_pm_jump_propagate:PPPPPPIIZZZZ eppm_pm_parallel_propagate:PPPPPPIIZZZZ
+eppm_pm_random_search:PPPPPPPIIZZZZ eppm_gauss_filter_rgba:PPZIIFI eppm_resize_rgba:PZIIPZIIF eppm_resize_flow:PIIPIIF eppm_flow_upsample:PIIPIIPZ
+eppm_load_ppm:SPIIP eppm_ppm_size:SPP eppm_save_flo:SPPII eppm_load_flo:SPPII eppm_flo_size:SPP eppm_flow_error:PPPPIIPP
+eppm_flow_error_border:PPPPIIIPP eppm_flow_error_percentage:PPPPIIIPP eppm_flow_cutoff:PPPPIIII eppm_fb_occlusion_host:PPPPPIIFF
+eppm_flow_to_color_host:PPPII""")
 
 # what include/eppm_test.h adds, exported by libeppm_hip_test.so and libeppm_hip_tol_test.so only (the parity tests' switches and arithmetic probes)
-TEST_SYMBOLS = ["eppm_test_set_option", "eppm_test_c2f_refine_batch", "eppm_test_c2f_refine_pre", "eppm_test_c2f_refine_probe", "eppm_probe_c2f_pretest", "eppm_probe_c2f_window", "eppm_probe_dispatch", "eppm_probe_fast_exp", "eppm_probe_div_const", "eppm_probe_delta_table",
-                "eppm_probe_unpack_texel", "eppm_probe_pm_parity", "eppm_probe_ctx_rng_states", "eppm_test_pm_search", "eppm_probe_search_pretest", "eppm_probe_launch_log"]
+_TEST_ABI = _signatures("""
+eppm_test_set_option:SI eppm_probe_c2f_window:IPP eppm_test_c2f_refine_batch:PPPPPIII eppm_test_c2f_refine_pre:PPPPPIIIIP
+eppm_test_c2f_refine_probe:PPPPPIIIP eppm_probe_c2f_pretest:IPP eppm_test_pm_search:PPPPPIIIIIPPP eppm_probe_search_pretest:IIIIIIPP
+eppm_probe_dispatch:SPIPI eppm_probe_launch_log:PI eppm_probe_fast_exp:PPI eppm_probe_div_const:PPII eppm_probe_delta_table:PPII
+eppm_probe_unpack_texel:PPI eppm_probe_pm_parity:PPPP eppm_probe_ctx_rng_states:PPZ""")
+
+SIGNATURES = {**_ABI, **_TEST_ABI}
+SYMBOLS, TEST_SYMBOLS = list(_ABI), list(_TEST_ABI)
 
 _variant = None
 
@@ -199,31 +205,13 @@ def lib():
         if not os.path.exists(path):
             raise EppmError(f"{path} is missing: run eppm_amd.build() (hipcc --offload-arch=gfx950); there is no CPU fallback")
         L = C.CDLL(path)
-        L.eppm_last_error.restype = C.c_char_p
-        L.eppm_version.restype = C.c_char_p
-        _plate_signatures(L)
+        for name, (res, args) in SIGNATURES.items():
+            fn = getattr(L, name, None)
+            if fn is None:      # a test hook in a product library, or a library built before the function existed (A/B runs): fails at the call
+                continue
+            fn.restype, fn.argtypes = res, args
         _lib = L
     return _lib
-
-
-def _plate_signatures(L):
-    """argument types of eppm_plate_*: size_t and pointer arguments in the middle of long lists, so they are declared, not wrapped per call"""
-    P, I, Z, F = C.c_void_p, C.c_int, C.c_size_t, C.c_float
-    sig = {
-        "eppm_plate_default_params": [P], "eppm_plate_create": [P, P, P], "eppm_plate_create_size": [I, I, I, I, P, P], "eppm_plate_destroy": [P],
-        "eppm_plate_reset": [P, I], "eppm_plate_canvas_dims": [P, P, P], "eppm_plate_step": [P, P, P],
-        "eppm_plate_step_frames": [P, I, P, Z, P, P, I], "eppm_plate_render": [P, P, I, P, Z, P],
-        "eppm_plate_render_frames": [P, I, P, Z, P, P, P, Z, P], "eppm_plate_get": [P, I, P, Z, P], "eppm_plate_get_device": [P, I, P, Z],
-        "eppm_plate_get_mask": [P, I, P], "eppm_plate_get_path": [P, I, P], "eppm_plate_set_path": [P, I, P], "eppm_plate_get_state": [P, I, P],
-        "eppm_plate_set_state": [P, I, P], "eppm_plate_forms_host": [P, P, P, P], "eppm_plate_block_host": [P, P, I, I, P],
-        "eppm_plate_accumulate_host": [P, P, P, P, I, I, P], "eppm_plate_render_host": [P, P, I, P, P, I, I, P, P, P],
-    }
-    for name, args in sig.items():
-        fn = getattr(L, name, None)
-        if fn is None:              # a library built before the plate existed still loads (A/B runs); its plate calls fail at the call
-            continue
-        fn.argtypes = args
-        fn.restype = I
 
 
 def check(status, what=""):

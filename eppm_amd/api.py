@@ -16,26 +16,34 @@ _PLANE_DTYPES = {"img1": uchar4, "img2": uchar4, "census1": np.uint8, "census2":
                  "prior1": short2, "prior2": short2, "nnf_init1": short2, "nnf_init2": short2, "cost_init1": np.float32, "cost_init2": np.float32}
 
 
-def Params(**kw):
-    """Tunables with the defaults of defs.h:31-76 (patch_r, num_iter, search_range, num_guess, seg_len, wmf_iters, seed, propagation: 0 segmented sweeps / 1 jump flood / 2 4-neighbour, levels: pyramid depth)."""
-    p = CParams()
-    check(lib().eppm_default_params(C.byref(p)), "eppm_default_params")
+def _params(struct, default_fn, noun, start=None, /, **kw):
+    """A parameter struct with the library's defaults (or a copy of `start`) and the overrides kw; an unknown key is a TypeError."""
+    p = struct()
+    if start is not None:
+        C.memmove(C.byref(p), C.byref(start), C.sizeof(p))
+    else:
+        check(getattr(lib(), default_fn)(C.byref(p)), default_fn)
     for k, v in kw.items():
         if not hasattr(p, k):
-            raise TypeError(f"unknown parameter {k}")
+            raise TypeError(f"unknown {noun} {k}")
         setattr(p, k, v)
     return p
+
+
+def Params(**kw):
+    """Tunables with the defaults of defs.h:31-76 (patch_r, num_iter, search_range, num_guess, seg_len, wmf_iters, seed, propagation: 0 segmented sweeps / 1 jump flood / 2 4-neighbour, levels: pyramid depth)."""
+    return _params(CParams, "eppm_default_params", "parameter", **kw)
 
 
 def host_register(arr):
     """Pin a numpy array's memory for DMA (eppm_host_register): set_data reads registered images, and compute_flow(out=...)
     writes registered planes, over PCIe directly -- no staging copy.  Keep the array alive until host_unregister."""
-    check(lib().eppm_host_register(C.c_void_p(arr.ctypes.data), C.c_size_t(arr.nbytes)), "eppm_host_register")
+    check(lib().eppm_host_register(arr.ctypes.data, arr.nbytes), "eppm_host_register")
     return arr
 
 
 def host_unregister(arr):
-    check(lib().eppm_host_unregister(C.c_void_p(arr.ctypes.data)), "eppm_host_unregister")
+    check(lib().eppm_host_unregister(arr.ctypes.data), "eppm_host_unregister")
 
 
 def pinned_empty(shape, dtype=np.uint8):
@@ -43,13 +51,13 @@ def pinned_empty(shape, dtype=np.uint8):
     dtype = np.dtype(dtype)
     n = int(np.prod(shape)) * dtype.itemsize
     p = C.c_void_p()
-    check(lib().eppm_host_alloc(C.byref(p), C.c_size_t(max(n, 1))), "eppm_host_alloc")
+    check(lib().eppm_host_alloc(C.byref(p), max(n, 1)), "eppm_host_alloc")
     addr = p.value
 
     class _Owner:
         def __del__(self):
             try:
-                lib().eppm_host_free(C.c_void_p(addr))
+                lib().eppm_host_free(addr)
             except Exception:
                 pass
     buf = (C.c_char * max(n, 1)).from_address(addr)
@@ -66,28 +74,13 @@ def _times(times):
 
 def MBlurParams(**kw):
     """eppm_mblur_params with the defaults of DESIGN.md section 18 (shutter 0.5, max_radius 16, taps 8)."""
-    p = CMBlurParams()
-    check(lib().eppm_mblur_default_params(C.byref(p)), "eppm_mblur_default_params")
-    for k, v in kw.items():
-        if not hasattr(p, k):
-            raise TypeError(f"unknown motion-blur parameter {k}")
-        setattr(p, k, v)
-    return p
+    return _params(CMBlurParams, "eppm_mblur_default_params", "motion-blur parameter", **kw)
 
 
 def TrackParams(params=None, **kw):
     """eppm_track_params with the defaults of DESIGN.md section 12 (spacing 8, min_eig 2500, fb_alpha 0.01, fb_beta 0.5, mb_alpha 0.01,
     mb_beta 0.002, capacity 0: 4 x the number of cells); params: a CTrackParams to start from instead."""
-    p = CTrackParams()
-    if params is not None:
-        C.memmove(C.byref(p), C.byref(params), C.sizeof(p))
-    else:
-        check(lib().eppm_track_default_params(C.byref(p)), "eppm_track_default_params")
-    for k, v in kw.items():
-        if not hasattr(p, k):
-            raise TypeError(f"unknown track parameter {k}")
-        setattr(p, k, v)
-    return p
+    return _params(CTrackParams, "eppm_track_default_params", "track parameter", params, **kw)
 
 
 class _Handle:
@@ -126,12 +119,13 @@ class _SlotObject(_Handle):
         self.nslots = int(lib().eppm_batch_size(ctx._ctx))
 
     def _call(self, fn, *args):
-        check(getattr(lib(), f"eppm_{self._prefix}_{fn}")(self._f, *args), f"eppm_{self._prefix}_{fn}")
+        name = f"eppm_{self._prefix}_{fn}"
+        check(getattr(lib(), name)(self._f, *args), name)
 
     def _rgb(self, fn, slot):
         """(h, w, 3) uint8 from eppm_<prefix>_<fn>(slot, rgb, row_stride)"""
         rgb = np.empty((self.h, self.w, 3), np.uint8)
-        self._call(fn, int(slot), rgb.ctypes.data_as(C.c_void_p), C.c_size_t(self.w * 3))
+        self._call(fn, int(slot), rgb.ctypes.data, self.w * 3)
         return rgb
 
 
@@ -150,6 +144,18 @@ class _ClipObject(_SlotObject):
     def reset(self, slot=None):
         """The slot is empty again (slot=None: every slot); what its next step starts from: the class's description."""
         self._call("reset", -1 if slot is None else int(slot))
+
+
+class _FrameObject(_ClipObject):
+    """A clip object whose step leaves one output frame per slot (eppm_<prefix>_get, eppm_<prefix>_get_device); what frame(slot) shows:
+    the class's frame."""
+
+    def frames(self):
+        """frame(k) of the context's active pairs' slots."""
+        return [self.frame(k) for k in range(getattr(self.ctx, "n", 1))]
+
+    def frame_device(self, slot, d_rgba, pitch):
+        self._call("get_device", int(slot), d_rgba, pitch)
 
 
 class Tracker(_Handle):
@@ -172,8 +178,7 @@ class Tracker(_Handle):
 
     def step_frames(self, d_rgba1, d_rgba2, pitch, d_flow, d_flow_bwd):
         """eppm_track_step_frames: one step on caller device planes (addresses), synchronous."""
-        check(lib().eppm_track_step_frames(self._t, C.c_void_p(d_rgba1), C.c_void_p(d_rgba2), C.c_size_t(pitch), C.c_void_p(d_flow),
-                                           C.c_void_p(d_flow_bwd), self.ctx.h, self.ctx.w), "eppm_track_step_frames")
+        check(lib().eppm_track_step_frames(self._t, d_rgba1, d_rgba2, pitch, d_flow, d_flow_bwd, self.ctx.h, self.ctx.w), "eppm_track_step_frames")
 
     def counts(self):
         c = CTrackCounts()
@@ -185,8 +190,7 @@ class Tracker(_Handle):
         n = self.counts()["live"]
         ids, starts, xy = np.empty(n, np.int32), np.empty(n, np.int32), np.empty((n, 2), np.float32)
         c = CTrackCounts()
-        check(lib().eppm_tracker_get(self._t, n, ids.ctypes.data_as(C.c_void_p), starts.ctypes.data_as(C.c_void_p),
-                                     xy.ctypes.data_as(C.c_void_p), C.byref(c)), "eppm_tracker_get")
+        check(lib().eppm_tracker_get(self._t, n, ids.ctypes.data, starts.ctypes.data, xy.ctypes.data, C.byref(c)), "eppm_tracker_get")
         return ids, starts, xy
 
     def ended(self):
@@ -195,8 +199,8 @@ class Tracker(_Handle):
         ids, starts, why = np.empty(n, np.int32), np.empty(n, np.int32), np.empty(n, np.int32)
         xy = np.empty((n, 2), np.float32)
         c = CTrackCounts()
-        check(lib().eppm_tracker_get_ended(self._t, n, ids.ctypes.data_as(C.c_void_p), starts.ctypes.data_as(C.c_void_p),
-                                           xy.ctypes.data_as(C.c_void_p), why.ctypes.data_as(C.c_void_p), C.byref(c)), "eppm_tracker_get_ended")
+        check(lib().eppm_tracker_get_ended(self._t, n, ids.ctypes.data, starts.ctypes.data,
+                                           xy.ctypes.data, why.ctypes.data, C.byref(c)), "eppm_tracker_get_ended")
         return ids, starts, xy, why, c.as_dict()
 
     def set(self, ids, starts, xy, next_id, frame):
@@ -206,11 +210,10 @@ class Tracker(_Handle):
         xy = np.ascontiguousarray(xy, np.float32).reshape(-1, 2)
         if not (len(ids) == len(starts) == len(xy)):
             raise EppmError("Tracker.set: ids, starts and xy of one length")
-        check(lib().eppm_tracker_set(self._t, len(ids), ids.ctypes.data_as(C.c_void_p), starts.ctypes.data_as(C.c_void_p),
-                                     xy.ctypes.data_as(C.c_void_p), int(next_id), int(frame)), "eppm_tracker_set")
+        check(lib().eppm_tracker_set(self._t, len(ids), ids.ctypes.data, starts.ctypes.data, xy.ctypes.data, int(next_id), int(frame)), "eppm_tracker_set")
 
 
-class TemporalFilter(_ClipObject):
+class TemporalFilter(_FrameObject):
     """Motion-compensated temporal denoising over the pairs of a context (eppm_tfilter_*).  ctx: an EPPM or an
     EPPMBatch; one slot per pair of it.  Every step() moves the active pairs' slots from image 1 to image 2 of the context's last
     compute_flow_bidirectional*; an empty slot (new, or after reset()) starts from its pair's image 1.  The filter is its own allocation on
@@ -224,34 +227,26 @@ class TemporalFilter(_ClipObject):
 
     def step_frames(self, slot, d_rgba1, d_rgba2, pitch, d_flow_bwd, d_occ2, cut=False):
         """eppm_tfilter_step_frames: one step of one slot on caller device planes (addresses), synchronous."""
-        check(lib().eppm_tfilter_step_frames(self._f, int(slot), C.c_void_p(d_rgba1), C.c_void_p(d_rgba2), C.c_size_t(pitch),
-                                             C.c_void_p(d_flow_bwd), C.c_void_p(d_occ2), int(bool(cut))), "eppm_tfilter_step_frames")
+        self._call("step_frames", int(slot), d_rgba1, d_rgba2, pitch, d_flow_bwd, d_occ2, int(bool(cut)))
 
     def frame(self, slot=0):
         """(h, w, 3) uint8: the slot's filtered frame."""
         return self._rgb("get", slot)
 
-    def frames(self):
-        """The filtered frames of the context's active pairs' slots."""
-        return [self.frame(k) for k in range(getattr(self.ctx, "n", 1))]
-
-    def frame_device(self, slot, d_rgba, pitch):
-        check(lib().eppm_tfilter_get_device(self._f, int(slot), C.c_void_p(d_rgba), C.c_size_t(pitch)), "eppm_tfilter_get_device")
-
     def state(self, slot=0):
         """(h, w, 4) float32 {R, G, B, n}: the slot's state."""
         acc = np.empty((self.h, self.w, 4), np.float32)
-        check(lib().eppm_tfilter_get_state(self._f, int(slot), acc.ctypes.data_as(C.c_void_p)), "eppm_tfilter_get_state")
+        self._call("get_state", int(slot), acc.ctypes.data)
         return acc
 
     def set_state(self, slot, acc):
         acc = np.ascontiguousarray(acc, np.float32)
         if acc.shape != (self.h, self.w, 4):
             raise EppmError(f"TemporalFilter.set_state: the state must be ({self.h},{self.w},4) float32")
-        check(lib().eppm_tfilter_set_state(self._f, int(slot), acc.ctypes.data_as(C.c_void_p)), "eppm_tfilter_set_state")
+        self._call("set_state", int(slot), acc.ctypes.data)
 
 
-class DefectFilter(_ClipObject):
+class DefectFilter(_FrameObject):
     """Film-defect removal over the pairs of a context (eppm_defect_*): single-frame blotches (dust, dirt, dropouts)
     are concealed from both motion-compensated neighbours.  ctx: an EPPM or an EPPMBatch; one slot per pair of it.  Every step() repairs
     IMAGE 1 of the active pairs of the context's last compute_flow_bidirectional*, from image 2 and from the frame and backward flow the
@@ -266,24 +261,16 @@ class DefectFilter(_ClipObject):
 
     def step_frames(self, slot, d_rgba1, d_rgba2, pitch, d_flow, d_flow_bwd, cut=False):
         """eppm_defect_step_frames: one step of one slot on caller device planes (addresses), synchronous."""
-        check(lib().eppm_defect_step_frames(self._f, int(slot), C.c_void_p(d_rgba1), C.c_void_p(d_rgba2), C.c_size_t(pitch),
-                                            C.c_void_p(d_flow), C.c_void_p(d_flow_bwd), int(bool(cut))), "eppm_defect_step_frames")
+        self._call("step_frames", int(slot), d_rgba1, d_rgba2, pitch, d_flow, d_flow_bwd, int(bool(cut)))
 
     def frame(self, slot=0):
         """(h, w, 3) uint8: the slot's repaired image 1 of the last step."""
         return self._rgb("get", slot)
 
-    def frames(self):
-        """The repaired frames of the context's active pairs' slots."""
-        return [self.frame(k) for k in range(getattr(self.ctx, "n", 1))]
-
-    def frame_device(self, slot, d_rgba, pitch):
-        check(lib().eppm_defect_get_device(self._f, int(slot), C.c_void_p(d_rgba), C.c_size_t(pitch)), "eppm_defect_get_device")
-
     def mask(self, slot=0):
         """(h, w) uint8: 0 untouched, 1 hit, 2 grown."""
         m = np.empty((self.h, self.w), np.uint8)
-        self._call("get_mask", int(slot), m.ctypes.data_as(C.c_void_p))
+        self._call("get_mask", int(slot), m.ctypes.data)
         return m
 
     def stats(self, slot=0):
@@ -295,17 +282,17 @@ class DefectFilter(_ClipObject):
     def state(self, slot=0):
         """(frame (h, w, 3) uint8, backward flow (h, w, 2) float32, has_prev): what the slot's last step saved."""
         rgb, bwd, has = np.empty((self.h, self.w, 3), np.uint8), np.empty((self.h, self.w, 2), np.float32), C.c_int()
-        self._call("get_state", int(slot), rgb.ctypes.data_as(C.c_void_p), bwd.ctypes.data_as(C.c_void_p), C.byref(has))
+        self._call("get_state", int(slot), rgb.ctypes.data, bwd.ctypes.data, C.byref(has))
         return rgb, bwd, bool(has.value)
 
     def set_state(self, slot, frame, bwd, has_prev=True):
         rgb, bwd = np.ascontiguousarray(frame, np.uint8), np.ascontiguousarray(bwd, np.float32)
         if rgb.shape != (self.h, self.w, 3) or bwd.shape != (self.h, self.w, 2):
             raise EppmError(f"DefectFilter.set_state: a ({self.h},{self.w},3) uint8 frame and a ({self.h},{self.w},2) float32 flow")
-        self._call("set_state", int(slot), rgb.ctypes.data_as(C.c_void_p), bwd.ctypes.data_as(C.c_void_p), int(bool(has_prev)))
+        self._call("set_state", int(slot), rgb.ctypes.data, bwd.ctypes.data, int(bool(has_prev)))
 
 
-class Deflicker(_ClipObject):
+class Deflicker(_FrameObject):
     """Flicker removal over the pairs of a context (eppm_deflicker_*): a gain and an offset per colour on a grid of
     cell x cell pixels, fitted to the motion-compensated reference and applied to IMAGE 2 of the active pairs of the context's last
     compute_flow_bidirectional*.  ctx: an EPPM or an EPPMBatch; one slot per pair of it.  The reference of a slot is its previous output;
@@ -321,24 +308,16 @@ class Deflicker(_ClipObject):
 
     def step_frames(self, slot, d_rgba1, d_rgba2, pitch, d_flow_bwd, d_occ2, cut=False):
         """eppm_deflicker_step_frames: one step of one slot on caller device planes (addresses), synchronous."""
-        check(lib().eppm_deflicker_step_frames(self._f, int(slot), C.c_void_p(d_rgba1), C.c_void_p(d_rgba2), C.c_size_t(pitch),
-                                               C.c_void_p(d_flow_bwd), C.c_void_p(d_occ2), int(bool(cut))), "eppm_deflicker_step_frames")
+        self._call("step_frames", int(slot), d_rgba1, d_rgba2, pitch, d_flow_bwd, d_occ2, int(bool(cut)))
 
     def frame(self, slot=0):
         """(h, w, 3) uint8: the slot's corrected image 2 of the last step."""
         return self._rgb("get", slot)
 
-    def frames(self):
-        """The corrected frames of the context's active pairs' slots."""
-        return [self.frame(k) for k in range(getattr(self.ctx, "n", 1))]
-
-    def frame_device(self, slot, d_rgba, pitch):
-        check(lib().eppm_deflicker_get_device(self._f, int(slot), C.c_void_p(d_rgba), C.c_size_t(pitch)), "eppm_deflicker_get_device")
-
     def field(self, slot=0):
         """(field (cells_y, cells_x, 6) float32 {aR, aG, aB, bR, bG, bB}, valid (cells_y, cells_x) uint8) of the slot's last step."""
         f, v = np.empty((self.cells_y, self.cells_x, 6), np.float32), np.empty((self.cells_y, self.cells_x), np.uint8)
-        self._call("get_field", int(slot), f.ctypes.data_as(C.c_void_p), v.ctypes.data_as(C.c_void_p))
+        self._call("get_field", int(slot), f.ctypes.data, v.ctypes.data)
         return f, v
 
     def stats(self, slot=0):
@@ -350,17 +329,17 @@ class Deflicker(_ClipObject):
     def state(self, slot=0):
         """(frame (h, w, 3) uint8, empty): the slot's reference and whether the slot counts as empty."""
         rgb, empty = np.empty((self.h, self.w, 3), np.uint8), C.c_int()
-        self._call("get_state", int(slot), rgb.ctypes.data_as(C.c_void_p), C.byref(empty))
+        self._call("get_state", int(slot), rgb.ctypes.data, C.byref(empty))
         return rgb, bool(empty.value)
 
     def set_state(self, slot, frame, empty=False):
         rgb = np.ascontiguousarray(frame, np.uint8)
         if rgb.shape != (self.h, self.w, 3):
             raise EppmError(f"Deflicker.set_state: a ({self.h},{self.w},3) uint8 frame")
-        self._call("set_state", int(slot), rgb.ctypes.data_as(C.c_void_p), int(bool(empty)))
+        self._call("set_state", int(slot), rgb.ctypes.data, int(bool(empty)))
 
 
-class Stabilizer(_ClipObject):
+class Stabilizer(_FrameObject):
     """Global camera motion and video stabilisation over the pairs of a context (eppm_stab_*).  ctx: an EPPM or an
     EPPMBatch; one slot per pair of it.  Every step() fits the camera motion of the active pairs of the context's last
     compute_flow_bidirectional*, moves the slots' paths and renders image 2 from the smoothed camera; an empty slot (new, or after reset())
@@ -374,30 +353,22 @@ class Stabilizer(_ClipObject):
 
     def step_frames(self, slot, d_rgba2, pitch, d_flow, d_occ1, cut=False):
         """eppm_stab_step_frames: one step of one slot on caller device planes (addresses), synchronous."""
-        check(lib().eppm_stab_step_frames(self._f, int(slot), C.c_void_p(d_rgba2), C.c_size_t(pitch), C.c_void_p(d_flow), C.c_void_p(d_occ1),
-                                          int(bool(cut))), "eppm_stab_step_frames")
+        self._call("step_frames", int(slot), d_rgba2, pitch, d_flow, d_occ1, int(bool(cut)))
 
     def frame(self, slot=0):
         """(h, w, 3) uint8: the slot's stabilised frame."""
         return self._rgb("get", slot)
 
-    def frames(self):
-        """The stabilised frames of the context's active pairs' slots."""
-        return [self.frame(k) for k in range(getattr(self.ctx, "n", 1))]
-
-    def frame_device(self, slot, d_rgba, pitch):
-        check(lib().eppm_stab_get_device(self._f, int(slot), C.c_void_p(d_rgba), C.c_size_t(pitch)), "eppm_stab_get_device")
-
     def mask(self, slot=0):
         """(h, w) uint8: 0 the pixel of image 1 moves with the camera, 1 it moves on its own, 2 it has no valid vector."""
         m = np.empty((self.h, self.w), np.uint8)
-        check(lib().eppm_stab_get_mask(self._f, int(slot), m.ctypes.data_as(C.c_void_p)), "eppm_stab_get_mask")
+        self._call("get_mask", int(slot), m.ctypes.data)
         return m
 
     def model(self, slot=0):
         """The camera motion of the slot's last pair: dict(p (6 float64, displacement form), n_valid, n_inliers, valid, passes)."""
         m = CGMotionModel()
-        check(lib().eppm_stab_get_model(self._f, int(slot), C.byref(m)), "eppm_stab_get_model")
+        self._call("get_model", int(slot), C.byref(m))
         return m.as_dict()
 
     def path(self, slot=0, counts=False):
@@ -405,14 +376,14 @@ class Stabilizer(_ClipObject):
         invalid_steps)."""
         p = np.empty(12, np.float64)
         n, bad = C.c_int64(), C.c_int64()
-        check(lib().eppm_stab_get_path(self._f, int(slot), p.ctypes.data_as(C.c_void_p), C.byref(n), C.byref(bad)), "eppm_stab_get_path")
+        self._call("get_path", int(slot), p.ctypes.data, C.byref(n), C.byref(bad))
         return (p[:6].copy(), p[6:].copy(), (n.value, bad.value)) if counts else (p[:6].copy(), p[6:].copy())
 
     def set_path(self, slot, c, s):
         p = np.ascontiguousarray(np.concatenate([np.asarray(c, np.float64).ravel(), np.asarray(s, np.float64).ravel()]))
         if p.shape != (12,):
             raise EppmError("Stabilizer.set_path: C and S are six numbers each")
-        check(lib().eppm_stab_set_path(self._f, int(slot), p.ctypes.data_as(C.c_void_p)), "eppm_stab_set_path")
+        self._call("set_path", int(slot), p.ctypes.data)
 
 
 class CutDetector(_SlotObject):
@@ -430,36 +401,29 @@ class CutDetector(_SlotObject):
     def step(self, ctx=None):
         """One step of every active pair's slot.  Asynchronous on the context's stream."""
         c = self.ctx if ctx is None else ctx
-        check(lib().eppm_cutdet_step(self._f, c._ctx), "eppm_cutdet_step")
+        self._call("step", c._ctx)
 
     def step_frames(self, slot, d_rgba1, d_rgba2, pitch, d_flow_bwd, d_occ1, d_occ2):
         """eppm_cutdet_step_frames: one step of one slot on caller device planes (addresses), synchronous."""
-        check(lib().eppm_cutdet_step_frames(self._f, int(slot), C.c_void_p(d_rgba1), C.c_void_p(d_rgba2), C.c_size_t(pitch), C.c_void_p(d_flow_bwd),
-                                            C.c_void_p(d_occ1), C.c_void_p(d_occ2)), "eppm_cutdet_step_frames")
+        self._call("step_frames", int(slot), d_rgba1, d_rgba2, pitch, d_flow_bwd, d_occ1, d_occ2)
 
     def stats(self, slot=0):
         """The record of the slot's last step: dict(n, c1 (4 counts), c2, n_tracked, sad, cut, stepped)."""
         st = CCutStats()
-        check(lib().eppm_cutdet_get(self._f, int(slot), C.byref(st)), "eppm_cutdet_get")
+        self._call("get", int(slot), C.byref(st))
         return st.as_dict()
 
     def cuts(self, n=None):
         """The verdicts of slots 0 .. n - 1 (default: the context's active pairs) as a list of bools: one small copy, synchronous."""
         n = int(getattr(self.ctx, "n", 1) if n is None else n)
         out = (C.c_uint8 * max(n, 1))()
-        check(lib().eppm_cutdet_cuts(self._f, n, out), "eppm_cutdet_cuts")
+        self._call("cuts", n, out)
         return [bool(x) for x in out[:n]]
 
 
 def CMapParams(**kw):
     """eppm_cmap_params with the defaults of DESIGN.md section 19 (thresh 90, tear 2, use_occ 1)."""
-    p = CCMapParams()
-    check(lib().eppm_cmap_default_params(C.byref(p)), "eppm_cmap_default_params")
-    for k, v in kw.items():
-        if not hasattr(p, k):
-            raise TypeError(f"unknown correspondence-map parameter {k}")
-        setattr(p, k, v)
-    return p
+    return _params(CCMapParams, "eppm_cmap_default_params", "correspondence-map parameter", **kw)
 
 
 class CorrespondenceMap(_ClipObject):
@@ -478,13 +442,12 @@ class CorrespondenceMap(_ClipObject):
 
     def step_frames(self, slot, d_rgba1, d_rgba2, pitch, d_flow_bwd, d_occ2, cut=False):
         """eppm_cmap_step_frames: one step of one slot on caller device planes (addresses), synchronous."""
-        check(lib().eppm_cmap_step_frames(self._f, int(slot), C.c_void_p(d_rgba1), C.c_void_p(d_rgba2), C.c_size_t(pitch),
-                                          C.c_void_p(d_flow_bwd), C.c_void_p(d_occ2), int(bool(cut))), "eppm_cmap_step_frames")
+        self._call("step_frames", int(slot), d_rgba1, d_rgba2, pitch, d_flow_bwd, d_occ2, int(bool(cut)))
 
     def map(self, slot=0):
         """(h, w, 2) float32 (sx, sy): the slot's map; a lost pixel holds (1e10, 1e10)."""
         xy = np.empty((self.h, self.w, 2), np.float32)
-        check(lib().eppm_cmap_get_state(self._f, int(slot), xy.ctypes.data_as(C.c_void_p)), "eppm_cmap_get_state")
+        self._call("get_state", int(slot), xy.ctypes.data)
         return xy
 
     state = map
@@ -501,26 +464,25 @@ class CorrespondenceMap(_ClipObject):
         a = np.ascontiguousarray(anchor, np.uint8)
         if xy.shape != (self.h, self.w, 2) or a.shape != (self.h, self.w, 3):
             raise EppmError(f"CorrespondenceMap.set_state: a ({self.h},{self.w},2) float32 map and a ({self.h},{self.w},3) uint8 anchor")
-        check(lib().eppm_cmap_set_state(self._f, int(slot), xy.ctypes.data_as(C.c_void_p), a.ctypes.data_as(C.c_void_p), C.c_size_t(self.w * 3)),
-              "eppm_cmap_set_state")
+        self._call("set_state", int(slot), xy.ctypes.data, a.ctypes.data, self.w * 3)
 
     def set_layer(self, rgba, slot=0):
         """The slot's layer: (h, w, 4) uint8 RGBA with straight alpha, in the anchor frame's geometry; None: the default layer (the anchor
         frame with alpha 255)."""
         if rgba is None:
-            check(lib().eppm_cmap_set_layer(self._f, int(slot), None, C.c_size_t(0)), "eppm_cmap_set_layer")
+            self._call("set_layer", int(slot), None, 0)
             return
         a = np.ascontiguousarray(rgba, np.uint8)
         if a.shape != (self.h, self.w, 4):
             raise EppmError(f"CorrespondenceMap.set_layer: the layer must be ({self.h},{self.w},4) uint8")
-        check(lib().eppm_cmap_set_layer(self._f, int(slot), a.ctypes.data_as(C.c_void_p), C.c_size_t(self.w * 4)), "eppm_cmap_set_layer")
+        self._call("set_layer", int(slot), a.ctypes.data, self.w * 4)
 
     def render(self, slot=0):
         """(h, w, 3) uint8: the slot's layer composited over its current frame through its map."""
         return self._rgb("render", slot)
 
     def render_device(self, slot, d_rgba, pitch):
-        check(lib().eppm_cmap_render_device(self._f, int(slot), C.c_void_p(d_rgba), C.c_size_t(pitch)), "eppm_cmap_render_device")
+        self._call("render_device", int(slot), d_rgba, pitch)
 
     def age(self, slot=0):
         """Steps since the slot's anchor frame."""
@@ -533,13 +495,7 @@ class CorrespondenceMap(_ClipObject):
 def ObjectsParams(**kw):
     """eppm_objects_params with the defaults of DESIGN.md section 20 (tau 1, iters 3, connectivity 8, min_area 16, max_objects 64,
     min_overlap 4)."""
-    p = CObjectsParams()
-    check(lib().eppm_objects_default_params(C.byref(p)), "eppm_objects_default_params")
-    for k, v in kw.items():
-        if not hasattr(p, k):
-            raise TypeError(f"unknown object-detector parameter {k}")
-        setattr(p, k, v)
-    return p
+    return _params(CObjectsParams, "eppm_objects_default_params", "object-detector parameter", **kw)
 
 
 class ObjectDetector(_ClipObject):
@@ -559,14 +515,13 @@ class ObjectDetector(_ClipObject):
 
     def step_frames(self, slot, d_mask, d_flow, d_flow_bwd=None, d_occ2=None, cut=False):
         """eppm_objects_step_frames: the kernels alone for one slot on caller device planes (addresses), synchronous."""
-        check(lib().eppm_objects_step_frames(self._f, int(slot), C.c_void_p(d_mask), C.c_void_p(d_flow), C.c_void_p(d_flow_bwd),
-                                             C.c_void_p(d_occ2), int(bool(cut))), "eppm_objects_step_frames")
+        self._call("step_frames", int(slot), d_mask, d_flow, d_flow_bwd, d_occ2, int(bool(cut)))
 
     def _get(self, slot):
         n = int(self.params.max_objects)
         rec = (CObject * n)()
         cnt = CObjectsCounts()
-        check(lib().eppm_objects_get(self._f, int(slot), n, rec, C.byref(cnt)), "eppm_objects_get")
+        self._call("get", int(slot), n, rec, C.byref(cnt))
         return rec, cnt
 
     def objects(self, slot=0):
@@ -582,7 +537,7 @@ class ObjectDetector(_ClipObject):
     def labels(self, slot=0):
         """(h, w) uint8: per pixel of image 1 the index (1 .. n) of its object in objects(slot), 0 for none."""
         lab = np.empty((self.h, self.w), np.uint8)
-        check(lib().eppm_objects_get_labels(self._f, int(slot), lab.ctypes.data_as(C.c_void_p)), "eppm_objects_get_labels")
+        self._call("get_labels", int(slot), lab.ctypes.data)
         return lab
 
     def id_map(self, slot=0):
@@ -598,8 +553,7 @@ class ObjectDetector(_ClipObject):
         car = np.empty((self.h, self.w), np.uint8)
         pid, page = np.empty(256, np.int32), np.empty(256, np.int32)
         nxt = C.c_int32()
-        check(lib().eppm_objects_get_state(self._f, int(slot), *[x.ctypes.data_as(C.c_void_p) for x in (car, pid, page)], C.byref(nxt)),
-              "eppm_objects_get_state")
+        self._call("get_state", int(slot), *[x.ctypes.data for x in (car, pid, page)], C.byref(nxt))
         return car, pid, page, int(nxt.value)
 
     def set_state(self, slot, carried, prev_id, prev_age, next_id):
@@ -609,20 +563,13 @@ class ObjectDetector(_ClipObject):
             raise EppmError(f"ObjectDetector.set_state: a ({self.h},{self.w}) uint8 plane and two tables of 256 int32")
         if not -2 ** 31 <= int(next_id) < 2 ** 31:
             raise EppmError("ObjectDetector.set_state: status 1: next_id is not an int32")
-        check(lib().eppm_objects_set_state(self._f, int(slot), *[x.ctypes.data_as(C.c_void_p) for x in (car, pid, page)], C.c_int32(int(next_id))),
-              "eppm_objects_set_state")
+        self._call("set_state", int(slot), *[x.ctypes.data for x in (car, pid, page)], int(next_id))
 
 
 def PlateParams(**kw):
     """eppm_plate_params with the defaults of DESIGN.md section 22 (tau 1, iters 3, margin_x 0, margin_y 0, grow 2, accept_invalid 0,
     thresh 40, n_max 64, min_count 2)."""
-    p = CPlateParams()
-    check(lib().eppm_plate_default_params(C.byref(p)), "eppm_plate_default_params")
-    for k, v in kw.items():
-        if not hasattr(p, k):
-            raise TypeError(f"unknown background-plate parameter {k}")
-        setattr(p, k, v)
-    return p
+    return _params(CPlateParams, "eppm_plate_default_params", "background-plate parameter", **kw)
 
 
 class BackgroundPlate(_ClipObject):
@@ -649,28 +596,26 @@ class BackgroundPlate(_ClipObject):
         p = np.ascontiguousarray(path, np.float64)
         if p.shape != (6,):
             raise EppmError("BackgroundPlate: a path is six numbers {a00, a01, a10, a11, tx, ty}")
-        return p, p.ctypes.data_as(C.c_void_p)
+        return p, p.ctypes.data
 
     def step_frames(self, slot, d_rgba, pitch, d_mask, path=None, cut=False):
         """eppm_plate_step_frames: the kernels alone for one slot on caller device planes (addresses), synchronous.  path: six float64 that
         become the slot's path for this step, None: the slot's own."""
         keep, ptr = self._path(path)
-        check(lib().eppm_plate_step_frames(self._f, int(slot), d_rgba, int(pitch), d_mask, ptr, int(bool(cut))), "eppm_plate_step_frames")
+        self._call("step_frames", int(slot), d_rgba, int(pitch), d_mask, ptr, int(bool(cut)))
 
     def render(self, slot=0, ctx=None):
         """(image 1 of the slot's last stepped pair with its blocked pixels filled from the canvas: (h, w, 3) uint8; the fill bytes: (h, w)
         uint8, 0 free, 1 filled, 2 blocked and not filled)."""
         c = self.ctx if ctx is None else ctx
         out, fill = np.empty((self.h, self.w, 3), np.uint8), np.empty((self.h, self.w), np.uint8)
-        check(lib().eppm_plate_render(self._f, c._ctx, int(slot), out.ctypes.data_as(C.c_void_p), self.w * 3, fill.ctypes.data_as(C.c_void_p)),
-              "eppm_plate_render")
+        self._call("render", c._ctx, int(slot), out.ctypes.data, self.w * 3, fill.ctypes.data)
         return out, fill
 
     def render_frames(self, slot, d_rgba, pitch, d_mask, path, d_rgba_out, out_pitch, d_fill):
         """eppm_plate_render_frames: the render alone on caller device planes (addresses) against the slot's canvas, synchronous."""
         keep, ptr = self._path(path)
-        check(lib().eppm_plate_render_frames(self._f, int(slot), d_rgba, int(pitch), d_mask, ptr, d_rgba_out, int(out_pitch), d_fill),
-              "eppm_plate_render_frames")
+        self._call("render_frames", int(slot), d_rgba, int(pitch), d_mask, ptr, d_rgba_out, int(out_pitch), d_fill)
 
     def render_frame(self, slot, frame, mask, path=None):
         """render_frames for host planes: an (h, w, 3) uint8 frame, its (h, w) uint8 mask and its path, uploaded, rendered and read back.
@@ -694,8 +639,7 @@ class BackgroundPlate(_ClipObject):
     def _get(self, slot, want_cov):
         rgb = np.empty((self.ch, self.cw, 3), np.uint8)
         cov = np.empty((self.ch, self.cw), np.uint8) if want_cov else None
-        check(lib().eppm_plate_get(self._f, int(slot), rgb.ctypes.data_as(C.c_void_p), self.cw * 3, None if cov is None else cov.ctypes.data_as(C.c_void_p)),
-              "eppm_plate_get")
+        self._call("get", int(slot), rgb.ctypes.data, self.cw * 3, None if cov is None else cov.ctypes.data)
         return rgb, cov
 
     def plate(self, slot=0):
@@ -707,35 +651,35 @@ class BackgroundPlate(_ClipObject):
         return self._get(slot, True)[1]
 
     def get_device(self, slot, d_rgba, pitch):
-        check(lib().eppm_plate_get_device(self._f, int(slot), d_rgba, int(pitch)), "eppm_plate_get_device")
+        self._call("get_device", int(slot), d_rgba, int(pitch))
 
     def mask(self, slot=0):
         """(h, w) uint8: the fit's mask of the slot's last step (0 moves with the camera, 1 moves on its own, 2 not valid)."""
         m = np.empty((self.h, self.w), np.uint8)
-        check(lib().eppm_plate_get_mask(self._f, int(slot), m.ctypes.data_as(C.c_void_p)), "eppm_plate_get_mask")
+        self._call("get_mask", int(slot), m.ctypes.data)
         return m
 
     def path(self, slot=0):
         """The slot's camera path, frame 0 -> image 1 of the next pair: six float64 {a00, a01, a10, a11, tx, ty}."""
         p = np.empty(6, np.float64)
-        check(lib().eppm_plate_get_path(self._f, int(slot), p.ctypes.data_as(C.c_void_p)), "eppm_plate_get_path")
+        self._call("get_path", int(slot), p.ctypes.data)
         return p
 
     def set_path(self, slot, path):
         keep, ptr = self._path(np.asarray(path))
-        check(lib().eppm_plate_set_path(self._f, int(slot), ptr), "eppm_plate_set_path")
+        self._call("set_path", int(slot), ptr)
 
     def state(self, slot=0):
         """(ch, cw, 4) float32: per canvas pixel the running mean {R, G, B} and its count n."""
         st = np.empty((self.ch, self.cw, 4), np.float32)
-        check(lib().eppm_plate_get_state(self._f, int(slot), st.ctypes.data_as(C.c_void_p)), "eppm_plate_get_state")
+        self._call("get_state", int(slot), st.ctypes.data)
         return st
 
     def set_state(self, slot, state):
         st = np.ascontiguousarray(state, np.float32)
         if st.shape != (self.ch, self.cw, 4):
             raise EppmError(f"BackgroundPlate.set_state: a ({self.ch},{self.cw},4) float32 array")
-        check(lib().eppm_plate_set_state(self._f, int(slot), st.ctypes.data_as(C.c_void_p)), "eppm_plate_set_state")
+        self._call("set_state", int(slot), st.ctypes.data)
 
 
 def _level(level):
@@ -767,7 +711,7 @@ class _Context(_Handle):
     def set_occlusion_params(self, alpha=0.01, beta=0.5):
         """alpha, beta of the occlusion masks' forward-backward criterion (eppm_set_occlusion_params)."""
         self._need()
-        check(lib().eppm_set_occlusion_params(self._ctx, C.c_float(alpha), C.c_float(beta)), "eppm_set_occlusion_params")
+        check(lib().eppm_set_occlusion_params(self._ctx, alpha, beta), "eppm_set_occlusion_params")
         self._occ_params = (float(alpha), float(beta))
 
     def synchronize(self):
@@ -825,8 +769,7 @@ class EPPM(_Context):
         h, w = args
         self.close()
         ctx = C.c_void_p()
-        check(lib().eppm_create(C.byref(ctx), int(h), int(w), int(self._device),
-                                C.byref(self._params) if self._params is not None else None), "eppm_create")
+        check(lib().eppm_create(C.byref(ctx), int(h), int(w), int(self._device), C.byref(self._params) if self._params is not None else None), "eppm_create")
         self._ctx, self.h, self.w = ctx, int(h), int(w)
         self._occ_params = (0.01, 0.5)          # the new context's defaults
 
@@ -837,8 +780,7 @@ class EPPM(_Context):
         b = np.ascontiguousarray(img2, np.uint8)
         if a.shape != (self.h, self.w, 3) or b.shape != (self.h, self.w, 3):
             raise EppmError(f"set_data: images must be ({self.h},{self.w},3) uint8")
-        check(lib().eppm_set_images(self._ctx, a.ctypes.data_as(C.c_void_p), b.ctypes.data_as(C.c_void_p),
-                                    C.c_size_t(self.w * 3)), "eppm_set_images")
+        check(lib().eppm_set_images(self._ctx, a.ctypes.data, b.ctypes.data, self.w * 3), "eppm_set_images")
         return True
 
     # -- streaming -------------------------------------------------------
@@ -848,11 +790,11 @@ class EPPM(_Context):
         a = np.ascontiguousarray(img, np.uint8)
         if a.shape != (self.h, self.w, 3):
             raise EppmError(f"push_frame: the image must be ({self.h},{self.w},3) uint8")
-        check(lib().eppm_push_image(self._ctx, a.ctypes.data_as(C.c_void_p), C.c_size_t(self.w * 3)), "eppm_push_image")
+        check(lib().eppm_push_image(self._ctx, a.ctypes.data, self.w * 3), "eppm_push_image")
 
     def push_frame_device(self, d_rgba, pitch):
         self._need()
-        check(lib().eppm_push_image_device(self._ctx, C.c_void_p(d_rgba), C.c_size_t(pitch)), "eppm_push_image_device")
+        check(lib().eppm_push_image_device(self._ctx, d_rgba, pitch), "eppm_push_image_device")
 
     def set_temporal(self, on=True):
         """Temporal mode (eppm_set_temporal): a compute after push_frame starts PatchMatch from the previous pair's result moved along its
@@ -883,7 +825,7 @@ class EPPM(_Context):
         by DMA directly, see host_register)."""
         self._need()
         u, v = self._out(out)
-        check(lib().eppm_compute(self._ctx, u.ctypes.data_as(C.c_void_p), v.ctypes.data_as(C.c_void_p)), "eppm_compute")
+        check(lib().eppm_compute(self._ctx, u.ctypes.data, v.ctypes.data), "eppm_compute")
         return u, v
 
     def compute_flow_bidirectional(self, alpha=None, beta=None):
@@ -897,14 +839,13 @@ class EPPM(_Context):
             self.set_occlusion_params(*self._occ_params)
         f = [np.empty((self.h, self.w), np.float32) for _ in range(4)]
         o = [np.empty((self.h, self.w), np.uint8) for _ in range(2)]
-        check(lib().eppm_compute_bidirectional(self._ctx, *[a.ctypes.data_as(C.c_void_p) for a in f + o]), "eppm_compute_bidirectional")
+        check(lib().eppm_compute_bidirectional(self._ctx, *[a.ctypes.data for a in f + o]), "eppm_compute_bidirectional")
         return (*f, *o)
 
     def compute_flow_bidirectional_device(self, d_flow=None, d_flow_bwd=None, d_occ1=None, d_occ2=None):
         """eppm_compute_bidirectional_device: asynchronous, device addresses (or None) of the two float2 flows and the two masks."""
         self._need()
-        ptrs = [C.c_void_p(p) if p else None for p in (d_flow, d_flow_bwd, d_occ1, d_occ2)]
-        check(lib().eppm_compute_bidirectional_device(self._ctx, *ptrs), "eppm_compute_bidirectional_device")
+        check(lib().eppm_compute_bidirectional_device(self._ctx, d_flow, d_flow_bwd, d_occ1, d_occ2), "eppm_compute_bidirectional_device")
 
     def interpolate(self, times):
         """Frames at the given times between image 1 (t = 0) and image 2 (t = 1) from the last compute_flow_bidirectional
@@ -913,7 +854,7 @@ class EPPM(_Context):
         ts = _times(times)
         out = [np.empty((self.h, self.w, 3), np.uint8) for _ in range(len(ts))]
         ptrs = (C.c_void_p * len(out))(*[a.ctypes.data for a in out])
-        check(lib().eppm_interpolate(self._ctx, len(ts), ts, ptrs, C.c_size_t(self.w * 3)), "eppm_interpolate")
+        check(lib().eppm_interpolate(self._ctx, len(ts), ts, ptrs, self.w * 3), "eppm_interpolate")
         return out
 
     def interpolate_device(self, times, d_ptrs, pitch):
@@ -923,7 +864,7 @@ class EPPM(_Context):
         if len(d_ptrs) != len(ts):
             raise EppmError("interpolate_device: one device plane per time")
         ptrs = (C.c_void_p * len(ts))(*d_ptrs)
-        check(lib().eppm_interpolate_device(self._ctx, len(ts), ts, ptrs, C.c_size_t(pitch)), "eppm_interpolate_device")
+        check(lib().eppm_interpolate_device(self._ctx, len(ts), ts, ptrs, pitch), "eppm_interpolate_device")
 
     def motion_blur(self, shutter=0.5, max_radius=16, taps=8, frame=0):
         """The frame as a camera with an open shutter would have recorded it (eppm_motion_blur): an (h, w, 3) uint8
@@ -933,21 +874,20 @@ class EPPM(_Context):
         self._need()
         p = MBlurParams(shutter=shutter, max_radius=max_radius, taps=taps)
         out = np.empty((self.h, self.w, 3), np.uint8)
-        check(lib().eppm_motion_blur(self._ctx, C.byref(p), int(frame), out.ctypes.data_as(C.c_void_p), C.c_size_t(self.w * 3)), "eppm_motion_blur")
+        check(lib().eppm_motion_blur(self._ctx, C.byref(p), int(frame), out.ctypes.data, self.w * 3), "eppm_motion_blur")
         return out
 
     def motion_blur_device(self, d_rgba, pitch, shutter=0.5, max_radius=16, taps=8, frame=0):
         """eppm_motion_blur_device: asynchronous on the context's stream; d_rgba: a device RGBA plane of pitch bytes per row."""
         self._need()
         p = MBlurParams(shutter=shutter, max_radius=max_radius, taps=taps)
-        check(lib().eppm_motion_blur_device(self._ctx, C.byref(p), int(frame), C.c_void_p(d_rgba), C.c_size_t(pitch)), "eppm_motion_blur_device")
+        check(lib().eppm_motion_blur_device(self._ctx, C.byref(p), int(frame), d_rgba, pitch), "eppm_motion_blur_device")
 
     def compute_flow_color(self, max_disp=(20.0, 20.0)):
         """The optional color_flow output of compute_flow (driver .cpp:308-314): (h, w, 3) uint8 R,G,B of the last flow."""
         self._need()
         rgb = np.empty((self.h, self.w, 3), np.uint8)
-        check(lib().eppm_compute_color(self._ctx, rgb.ctypes.data_as(C.c_void_p), C.c_size_t(self.w * 3),
-                                       C.c_float(max_disp[0]), C.c_float(max_disp[1])), "eppm_compute_color")
+        check(lib().eppm_compute_color(self._ctx, rgb.ctypes.data, self.w * 3, max_disp[0], max_disp[1]), "eppm_compute_color")
         return rgb
 
     def compute_flow_begin(self, out=None):
@@ -959,29 +899,28 @@ class EPPM(_Context):
         else:
             u, v = self._out(out)
             self._pending_out = (u, v)      # the copy engine writes these planes until compute_flow_end: keep them alive
-            check(lib().eppm_compute_begin_into(self._ctx, u.ctypes.data_as(C.c_void_p), v.ctypes.data_as(C.c_void_p)), "eppm_compute_begin_into")
+            check(lib().eppm_compute_begin_into(self._ctx, u.ctypes.data, v.ctypes.data), "eppm_compute_begin_into")
 
     def compute_flow_end(self, out=None):
         """Wait for compute_flow_begin; returns (disp1_x, disp1_y)."""
         self._need()
         u, v = self._out(out)
-        check(lib().eppm_compute_end(self._ctx, u.ctypes.data_as(C.c_void_p), v.ctypes.data_as(C.c_void_p)), "eppm_compute_end")
+        check(lib().eppm_compute_end(self._ctx, u.ctypes.data, v.ctypes.data), "eppm_compute_end")
         self._pending_out = None
         return u, v
 
     # -- device-resident variants (no PCIe in the timed region) ----------------------------
     def set_data_device(self, d_rgba1, d_rgba2, pitch):
         self._need()
-        check(lib().eppm_set_images_device(self._ctx, C.c_void_p(d_rgba1), C.c_void_p(d_rgba2), C.c_size_t(pitch)),
-              "eppm_set_images_device")
+        check(lib().eppm_set_images_device(self._ctx, d_rgba1, d_rgba2, pitch), "eppm_set_images_device")
 
     def compute_flow_device(self, d_flow=None):
         self._need()
-        check(lib().eppm_compute_device(self._ctx, C.c_void_p(d_flow) if d_flow else None), "eppm_compute_device")
+        check(lib().eppm_compute_device(self._ctx, d_flow), "eppm_compute_device")
 
     def set_stream(self, hip_stream):
         self._need()
-        check(lib().eppm_set_stream(self._ctx, C.c_void_p(hip_stream)), "eppm_set_stream")
+        check(lib().eppm_set_stream(self._ctx, hip_stream), "eppm_set_stream")
 
     # -- introspection ---------------------------------------------------------------------
     def plane(self, name, level):
@@ -991,8 +930,7 @@ class EPPM(_Context):
             raise EppmError(f"plane({name!r}, {level}): unknown plane or level")
         h, w = dims[level]
         a = np.empty((h, w), _PLANE_DTYPES[name])
-        check(lib().eppm_get_plane(self._ctx, name.encode(), level, a.ctypes.data_as(C.c_void_p), C.c_size_t(a.nbytes)),
-              "eppm_get_plane")
+        check(lib().eppm_get_plane(self._ctx, name.encode(), level, a.ctypes.data, a.nbytes), "eppm_get_plane")
         return a
 
     def _need(self):
@@ -1023,13 +961,12 @@ class EPPMBatch(_Context):
         for x in a + b:
             if x.shape != (self.h, self.w, 3):
                 raise EppmError(f"set_data: images must be ({self.h},{self.w},3) uint8")
-        check(lib().eppm_batch_set_images(self._ctx, len(pairs), self._ptrs(a), self._ptrs(b), C.c_size_t(self.w * 3)), "eppm_batch_set_images")
+        check(lib().eppm_batch_set_images(self._ctx, len(pairs), self._ptrs(a), self._ptrs(b), self.w * 3), "eppm_batch_set_images")
         self.n = len(pairs)
 
     def set_data_device(self, d1, d2, pitch):
         """d1, d2: lists of device addresses of RGBA planes."""
-        check(lib().eppm_batch_set_images_device(self._ctx, len(d1), self._ptrs(list(d1)), self._ptrs(list(d2)), C.c_size_t(pitch)),
-              "eppm_batch_set_images_device")
+        check(lib().eppm_batch_set_images_device(self._ctx, len(d1), self._ptrs(list(d1)), self._ptrs(list(d2)), pitch), "eppm_batch_set_images_device")
         self.n = len(d1)
 
     # -- batch streaming (DESIGN.md section 13.1): one clip per slot ----------------------------------
@@ -1049,12 +986,12 @@ class EPPMBatch(_Context):
         for x in a:
             if x.shape != (self.h, self.w, 3):
                 raise EppmError(f"push_frames: images must be ({self.h},{self.w},3) uint8")
-        check(lib().eppm_batch_push_images(self._ctx, len(a), self._ptrs(a), C.c_size_t(self.w * 3), self._cuts(new_clip, len(a))), "eppm_batch_push_images")
+        check(lib().eppm_batch_push_images(self._ctx, len(a), self._ptrs(a), self.w * 3, self._cuts(new_clip, len(a))), "eppm_batch_push_images")
 
     def push_frames_device(self, ptrs, pitch, new_clip=None):
         """ptrs: one device address of an RGBA plane per active pair (eppm_batch_push_images_device)."""
         ptrs = list(ptrs)
-        check(lib().eppm_batch_push_images_device(self._ctx, len(ptrs), self._ptrs(ptrs), C.c_size_t(pitch), self._cuts(new_clip, len(ptrs))),
+        check(lib().eppm_batch_push_images_device(self._ctx, len(ptrs), self._ptrs(ptrs), pitch, self._cuts(new_clip, len(ptrs))),
               "eppm_batch_push_images_device")
 
     def set_temporal(self, on=True):
@@ -1105,14 +1042,14 @@ class EPPMBatch(_Context):
         ts = _times(times)
         out = [[np.empty((self.h, self.w, 3), np.uint8) for _ in range(len(ts))] for _ in range(self.n)]
         flat = [a for row in out for a in row]
-        check(lib().eppm_batch_interpolate(self._ctx, len(ts), ts, self._ptrs(flat), C.c_size_t(self.w * 3)), "eppm_batch_interpolate")
+        check(lib().eppm_batch_interpolate(self._ctx, len(ts), ts, self._ptrs(flat), self.w * 3), "eppm_batch_interpolate")
         return out
 
     def motion_blur(self, shutter=0.5, max_radius=16, taps=8, frame=0):
         """[blurred frame for each active pair] (eppm_batch_motion_blur); see EPPM.motion_blur."""
         p = MBlurParams(shutter=shutter, max_radius=max_radius, taps=taps)
         out = [np.empty((self.h, self.w, 3), np.uint8) for _ in range(self.n)]
-        check(lib().eppm_batch_motion_blur(self._ctx, C.byref(p), int(frame), self._ptrs(out), C.c_size_t(self.w * 3)), "eppm_batch_motion_blur")
+        check(lib().eppm_batch_motion_blur(self._ctx, C.byref(p), int(frame), self._ptrs(out), self.w * 3), "eppm_batch_motion_blur")
         return out
 
     def compute_flow_device(self, d_flows=None):
@@ -1135,8 +1072,7 @@ class EPPMBatch(_Context):
     def plane(self, pair, name, level):
         hh, ww = self.level_dims()[level]
         a = np.empty((hh, ww), _PLANE_DTYPES[name])
-        check(lib().eppm_batch_get_plane(self._ctx, int(pair), name.encode(), level, a.ctypes.data_as(C.c_void_p), C.c_size_t(a.nbytes)),
-              "eppm_batch_get_plane")
+        check(lib().eppm_batch_get_plane(self._ctx, int(pair), name.encode(), level, a.ctypes.data, a.nbytes), "eppm_batch_get_plane")
         return a
 
 

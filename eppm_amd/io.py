@@ -7,6 +7,11 @@ import numpy as np
 from ._lib import check, lib
 
 
+def _p(a):
+    """the address of an array, NULL for None; the caller keeps the array alive over the call"""
+    return None if a is None else a.ctypes.data
+
+
 def ppm_size(path):
     h, w = C.c_int(), C.c_int()
     check(lib().eppm_ppm_size(path.encode(), C.byref(h), C.byref(w)), f"eppm_ppm_size({path})")
@@ -17,7 +22,7 @@ def load_ppm(path):
     h, w = ppm_size(path)
     img = np.zeros((h, w, 3), np.uint8)
     nc = C.c_int()
-    check(lib().eppm_load_ppm(path.encode(), img.ctypes.data_as(C.c_void_p), h, w, C.byref(nc)), f"eppm_load_ppm({path})")
+    check(lib().eppm_load_ppm(path.encode(), img.ctypes.data, h, w, C.byref(nc)), f"eppm_load_ppm({path})")
     return img if nc.value == 3 else img.reshape(-1)[:h * w].reshape(h, w)
 
 
@@ -25,7 +30,7 @@ def save_flo(path, u, v):
     u = np.ascontiguousarray(u, np.float32)
     v = np.ascontiguousarray(v, np.float32)
     h, w = u.shape
-    check(lib().eppm_save_flo(path.encode(), u.ctypes.data_as(C.c_void_p), v.ctypes.data_as(C.c_void_p), h, w), "eppm_save_flo")
+    check(lib().eppm_save_flo(path.encode(), u.ctypes.data, v.ctypes.data, h, w), "eppm_save_flo")
 
 
 def load_flo(path):
@@ -33,7 +38,7 @@ def load_flo(path):
     check(lib().eppm_flo_size(path.encode(), C.byref(h), C.byref(w)), f"eppm_flo_size({path})")
     u = np.empty((h.value, w.value), np.float32)
     v = np.empty((h.value, w.value), np.float32)
-    check(lib().eppm_load_flo(path.encode(), u.ctypes.data_as(C.c_void_p), v.ctypes.data_as(C.c_void_p), h.value, w.value), "eppm_load_flo")
+    check(lib().eppm_load_flo(path.encode(), u.ctypes.data, v.ctypes.data, h.value, w.value), "eppm_load_flo")
     return u, v
 
 
@@ -42,7 +47,7 @@ def flow_error(u, v, gu, gv, border=0):
     arrs = [np.ascontiguousarray(a, np.float32) for a in (u, v, gu, gv)]
     h, w = arrs[0].shape
     epe, aae = C.c_float(), C.c_float()
-    check(lib().eppm_flow_error_border(*[a.ctypes.data_as(C.c_void_p) for a in arrs], h, w, int(border), C.byref(epe), C.byref(aae)), "eppm_flow_error_border")
+    check(lib().eppm_flow_error_border(*[a.ctypes.data for a in arrs], h, w, int(border), C.byref(epe), C.byref(aae)), "eppm_flow_error_border")
     return epe.value, aae.value
 
 
@@ -53,8 +58,8 @@ def flow_error_percentage(u, v, gu, gv, error_thresh, want_map=False):
     h, w = arrs[0].shape
     emap = np.empty((h, w), np.uint8) if want_map else None
     frac = C.c_float()
-    check(lib().eppm_flow_error_percentage(*[a.ctypes.data_as(C.c_void_p) for a in arrs], h, w, int(error_thresh),
-                                           emap.ctypes.data_as(C.c_void_p) if want_map else None, C.byref(frac)), "eppm_flow_error_percentage")
+    check(lib().eppm_flow_error_percentage(*[a.ctypes.data for a in arrs], h, w, int(error_thresh),
+                                           emap.ctypes.data if want_map else None, C.byref(frac)), "eppm_flow_error_percentage")
     return (frac.value, emap) if want_map else frac.value
 
 
@@ -64,8 +69,7 @@ def flow_cutoff(u, v, cutoff, cut_invalid=False):
     v = np.ascontiguousarray(v, np.float32)
     uo, vo = np.empty_like(u), np.empty_like(v)
     h, w = u.shape
-    check(lib().eppm_flow_cutoff(uo.ctypes.data_as(C.c_void_p), vo.ctypes.data_as(C.c_void_p), u.ctypes.data_as(C.c_void_p),
-                                 v.ctypes.data_as(C.c_void_p), h, w, int(cutoff), int(bool(cut_invalid))), "eppm_flow_cutoff")
+    check(lib().eppm_flow_cutoff(uo.ctypes.data, vo.ctypes.data, u.ctypes.data, v.ctypes.data, h, w, int(cutoff), int(bool(cut_invalid))), "eppm_flow_cutoff")
     return uo, vo
 
 
@@ -75,7 +79,7 @@ def flow_to_color(u, v):
     v = np.ascontiguousarray(v, np.float32)
     h, w = u.shape
     rgb = np.empty((h, w, 3), np.uint8)
-    check(lib().eppm_flow_to_color_host(rgb.ctypes.data_as(C.c_void_p), u.ctypes.data_as(C.c_void_p), v.ctypes.data_as(C.c_void_p), h, w),
+    check(lib().eppm_flow_to_color_host(rgb.ctypes.data, u.ctypes.data, v.ctypes.data, h, w),
           "eppm_flow_to_color_host")
     return rgb
 
@@ -88,8 +92,7 @@ def fb_occlusion(u, v, bu, bv, alpha=0.01, beta=0.5):
     if any(a.shape != (h, w) for a in arrs):
         raise ValueError("fb_occlusion: the four planes must have one shape")
     occ = np.empty((h, w), np.uint8)
-    check(lib().eppm_fb_occlusion_host(occ.ctypes.data_as(C.c_void_p), *[a.ctypes.data_as(C.c_void_p) for a in arrs], h, w,
-                                       C.c_float(alpha), C.c_float(beta)), "eppm_fb_occlusion_host")
+    check(lib().eppm_fb_occlusion_host(occ.ctypes.data, *[a.ctypes.data for a in arrs], h, w, alpha, beta), "eppm_fb_occlusion_host")
     return occ
 
 
@@ -100,7 +103,7 @@ def temporal_prior(prev, backward=False):
     prev = np.ascontiguousarray(prev, short2)
     h, w = prev.shape
     out = np.empty((h, w), short2)
-    check(lib().eppm_temporal_prior_host(out.ctypes.data_as(C.c_void_p), prev.ctypes.data_as(C.c_void_p), h, w, int(bool(backward))),
+    check(lib().eppm_temporal_prior_host(out.ctypes.data, prev.ctypes.data, h, w, int(bool(backward))),
           "eppm_temporal_prior_host")
     return out
 
@@ -118,8 +121,7 @@ def interpolate(img1, img2, u, v, occ1, occ2, t):
     if a.shape != (h, w, 3) or b.shape != (h, w, 3) or v.shape != (h, w) or o1.shape != (h, w) or o2.shape != (h, w):
         raise ValueError("interpolate: images (h, w, 3), flow and masks (h, w)")
     out = np.empty((h, w, 3), np.uint8)
-    check(lib().eppm_interpolate_host(out.ctypes.data_as(C.c_void_p), *[x.ctypes.data_as(C.c_void_p) for x in (a, b, u, v, o1, o2)], h, w,
-                                      C.c_float(t)), "eppm_interpolate_host")
+    check(lib().eppm_interpolate_host(out.ctypes.data, *[x.ctypes.data for x in (a, b, u, v, o1, o2)], h, w, t), "eppm_interpolate_host")
     return out
 
 
@@ -136,7 +138,7 @@ def motion_blur_host(img, u, v, shutter=0.5, max_radius=16, taps=8):
     h, w = u.shape
     p = MBlurParams(shutter=shutter, max_radius=max_radius, taps=taps)
     out = np.empty((h, w, 3), np.uint8)
-    check(lib().eppm_motion_blur_host(out.ctypes.data_as(C.c_void_p), *[x.ctypes.data_as(C.c_void_p) for x in (a, u, v)], h, w, C.byref(p)),
+    check(lib().eppm_motion_blur_host(out.ctypes.data, *[x.ctypes.data for x in (a, u, v)], h, w, C.byref(p)),
           "eppm_motion_blur_host")
     return out
 
@@ -153,9 +155,9 @@ def track_seeds(img, params=None, **track_params):
     a = np.ascontiguousarray(img, np.uint8)
     h, w, _ = a.shape
     n = C.c_int()
-    check(lib().eppm_track_seeds_host(C.byref(p), a.ctypes.data_as(C.c_void_p), h, w, 0, None, C.byref(n)), "eppm_track_seeds_host")
+    check(lib().eppm_track_seeds_host(C.byref(p), a.ctypes.data, h, w, 0, None, C.byref(n)), "eppm_track_seeds_host")
     xy = np.empty((n.value, 2), np.float32)
-    check(lib().eppm_track_seeds_host(C.byref(p), a.ctypes.data_as(C.c_void_p), h, w, n.value, xy.ctypes.data_as(C.c_void_p), C.byref(n)),
+    check(lib().eppm_track_seeds_host(C.byref(p), a.ctypes.data, h, w, n.value, xy.ctypes.data, C.byref(n)),
           "eppm_track_seeds_host")
     return xy
 
@@ -181,9 +183,8 @@ def track_step_host(img1, img2, u, v, bu, bv, ids=(), starts=(), xy=(), next_id=
     o_ids, o_st, e_ids, e_st, why = (np.empty(cap, np.int32) for _ in range(5))
     o_xy, e_xy = np.empty((cap, 2), np.float32), np.empty((cap, 2), np.float32)
     cnt = CTrackCounts()
-    ptr = lambda x: x.ctypes.data_as(C.c_void_p)       # noqa: E731
-    check(lib().eppm_track_step_host(C.byref(p), ptr(a), ptr(b), *[ptr(x) for x in fl], h, w, len(ids), ptr(ids), ptr(starts), ptr(xy),
-                                     int(next_id), int(frame), ptr(o_ids), ptr(o_st), ptr(o_xy), ptr(e_ids), ptr(e_st), ptr(e_xy), ptr(why),
+    check(lib().eppm_track_step_host(C.byref(p), _p(a), _p(b), *[_p(x) for x in fl], h, w, len(ids), _p(ids), _p(starts), _p(xy),
+                                     int(next_id), int(frame), _p(o_ids), _p(o_st), _p(o_xy), _p(e_ids), _p(e_st), _p(e_xy), _p(why),
                                      C.byref(cnt)), "eppm_track_step_host")
     c = cnt.as_dict()
     n, m = c["live"], c["ended"]
@@ -203,7 +204,7 @@ def tfilter_seed_host(img):
         raise ValueError("tfilter_seed_host: the image must be (h, w, 3)")
     h, w, _ = a.shape
     acc = np.empty((h, w, 4), np.float32)
-    check(lib().eppm_tfilter_seed_host(acc.ctypes.data_as(C.c_void_p), a.ctypes.data_as(C.c_void_p), h, w), "eppm_tfilter_seed_host")
+    check(lib().eppm_tfilter_seed_host(acc.ctypes.data, a.ctypes.data, h, w), "eppm_tfilter_seed_host")
     return acc
 
 
@@ -221,8 +222,8 @@ def tfilter_step_host(acc, img2, bu, bv, occ2, thresh=40.0, n_max=8, cut=False):
     if acc.shape != (h, w, 4) or b.shape != (h, w, 3) or bv.shape != (h, w) or o.shape != (h, w):
         raise ValueError("tfilter_step_host: state (h, w, 4), image (h, w, 3), flow and mask (h, w)")
     out, rgb = np.empty((h, w, 4), np.float32), np.empty((h, w, 3), np.uint8)
-    check(lib().eppm_tfilter_step_host(C.byref(p), out.ctypes.data_as(C.c_void_p), rgb.ctypes.data_as(C.c_void_p),
-                                       *[x.ctypes.data_as(C.c_void_p) for x in (acc, b, bu, bv, o)], h, w, int(bool(cut))), "eppm_tfilter_step_host")
+    check(lib().eppm_tfilter_step_host(C.byref(p), out.ctypes.data, rgb.ctypes.data,
+                                       *[x.ctypes.data for x in (acc, b, bu, bv, o)], h, w, int(bool(cut))), "eppm_tfilter_step_host")
     return out, rgb
 
 
@@ -240,9 +241,8 @@ def defect_step_host(prev, cur, nxt, bu=None, bv=None, fu=None, fv=None, detect=
     flows = [None if a is None else np.ascontiguousarray(a, np.float32) for a in (bu, bv, fu, fv)]
     if any(a is not None and a.shape != c.shape for a in imgs) or any(a is not None and a.shape != (h, w) for a in flows):
         raise ValueError("defect_step_host: frames (h, w, 3), flow planes (h, w)")
-    ptr = lambda a: None if a is None else a.ctypes.data_as(C.c_void_p)
     out, mask, st = np.empty_like(c), np.empty((h, w), np.uint8), CDefectStats()
-    check(lib().eppm_defect_step_host(C.byref(p), ptr(out), ptr(mask), C.byref(st), ptr(imgs[0]), ptr(c), ptr(imgs[1]), *[ptr(a) for a in flows],
+    check(lib().eppm_defect_step_host(C.byref(p), _p(out), _p(mask), C.byref(st), _p(imgs[0]), _p(c), _p(imgs[1]), *[_p(a) for a in flows],
                                       h, w), "eppm_defect_step_host")
     return out, mask, st.as_dict()
 
@@ -263,8 +263,8 @@ def deflicker_step_host(ref, cur, bu, bv, occ2, cell=32, iters=2, reject=60.0, t
         raise ValueError("deflicker_step_host: frames (h, w, 3), flow and mask (h, w)")
     cy, cx = -(-h // max(int(cell), 1)), -(-w // max(int(cell), 1))
     out, field, valid, st = np.empty_like(c), np.empty((cy, cx, 6), np.float32), np.empty((cy, cx), np.uint8), CDeflickerStats()
-    check(lib().eppm_deflicker_step_host(C.byref(p), out.ctypes.data_as(C.c_void_p), field.ctypes.data_as(C.c_void_p),
-                                         valid.ctypes.data_as(C.c_void_p), C.byref(st), *[x.ctypes.data_as(C.c_void_p) for x in (r, c, bu, bv, o)],
+    check(lib().eppm_deflicker_step_host(C.byref(p), out.ctypes.data, field.ctypes.data,
+                                         valid.ctypes.data, C.byref(st), *[x.ctypes.data for x in (r, c, bu, bv, o)],
                                          h, w, int(bool(cut))), "eppm_deflicker_step_host")
     return out, field, valid, st.as_dict()
 
@@ -294,8 +294,8 @@ def cmap_step_host(cmap, anchor, img2, bu, bv, occ2, thresh=90.0, tear=2.0, use_
     if (m is not None and m.shape != (h, w, 2)) or a.shape != (h, w, 3) or b.shape != (h, w, 3) or bv.shape != (h, w) or o.shape != (h, w):
         raise ValueError("cmap_step_host: map (h, w, 2), images (h, w, 3), flow and mask (h, w)")
     out = np.empty((h, w, 2), np.float32)
-    check(lib().eppm_cmap_step_host(C.byref(p), out.ctypes.data_as(C.c_void_p), None if m is None else m.ctypes.data_as(C.c_void_p),
-                                    *[x.ctypes.data_as(C.c_void_p) for x in (a, b, bu, bv, o)], h, w, int(bool(cut))), "eppm_cmap_step_host")
+    check(lib().eppm_cmap_step_host(C.byref(p), out.ctypes.data, _p(m),
+                                    *[x.ctypes.data for x in (a, b, bu, bv, o)], h, w, int(bool(cut))), "eppm_cmap_step_host")
     return out
 
 
@@ -313,9 +313,8 @@ def cmap_render_host(cmap, cur, layer=None, anchor=None):
     if m.shape != (h, w, 2) or c.shape != (h, w, 3) or (lay is not None and lay.shape != (h, w, 4)) or (anc is not None and anc.shape != (h, w, 3)):
         raise ValueError("cmap_render_host: map (h, w, 2), frame and anchor (h, w, 3), layer (h, w, 4)")
     out = np.empty((h, w, 3), np.uint8)
-    check(lib().eppm_cmap_render_host(out.ctypes.data_as(C.c_void_p), m.ctypes.data_as(C.c_void_p), c.ctypes.data_as(C.c_void_p),
-                                      None if lay is None else lay.ctypes.data_as(C.c_void_p),
-                                      None if anc is None else anc.ctypes.data_as(C.c_void_p), h, w), "eppm_cmap_render_host")
+    check(lib().eppm_cmap_render_host(out.ctypes.data, m.ctypes.data, c.ctypes.data, _p(lay),
+                                      _p(anc), h, w), "eppm_cmap_render_host")
     return out
 
 
@@ -337,8 +336,7 @@ def gmotion_fit_host(u, v, occ1, tau=1.0, iters=3):
         raise ValueError("gmotion_fit_host: flow and mask (h, w)")
     m = CGMotionModel()
     mask = np.empty((h, w), np.uint8)
-    check(lib().eppm_gmotion_fit_host(C.byref(p), *[x.ctypes.data_as(C.c_void_p) for x in (u, v, o)], h, w, C.byref(m),
-                                      mask.ctypes.data_as(C.c_void_p)), "eppm_gmotion_fit_host")
+    check(lib().eppm_gmotion_fit_host(C.byref(p), *[x.ctypes.data for x in (u, v, o)], h, w, C.byref(m), mask.ctypes.data), "eppm_gmotion_fit_host")
     return m.as_dict(), mask
 
 
@@ -361,7 +359,7 @@ def stab_update_host(c, s, model, smooth=0.9, cut=False, counts=(0, 0)):
     m.valid = int(model["valid"])
     n = (C.c_int64 * 2)(int(counts[0]), int(counts[1]))
     wf = np.empty(6, np.float32)
-    check(lib().eppm_stab_update_host(C.byref(p), path.ctypes.data_as(C.c_void_p), n, C.byref(m), int(bool(cut)), wf.ctypes.data_as(C.c_void_p)),
+    check(lib().eppm_stab_update_host(C.byref(p), path.ctypes.data, n, C.byref(m), int(bool(cut)), wf.ctypes.data),
           "eppm_stab_update_host")
     return path[:6].copy(), path[6:].copy(), wf, (int(n[0]), int(n[1]))
 
@@ -374,7 +372,7 @@ def stab_warp_host(wf, img2):
         raise ValueError("stab_warp_host: wf (6,), image (h, w, 3)")
     h, w, _ = b.shape
     out = np.empty((h, w, 3), np.uint8)
-    check(lib().eppm_stab_warp_host(wf.ctypes.data_as(C.c_void_p), b.ctypes.data_as(C.c_void_p), h, w, out.ctypes.data_as(C.c_void_p)),
+    check(lib().eppm_stab_warp_host(wf.ctypes.data, b.ctypes.data, h, w, out.ctypes.data),
           "eppm_stab_warp_host")
     return out
 
@@ -396,7 +394,7 @@ def cutdet_host(img1, img2, bu, bv, occ1, occ2, lost_permille=530, residual_max=
     if b.shape != (h, w, 3) or any(x.shape != (h, w) for x in (bu, bv, o1, o2)):
         raise ValueError("cutdet_host: images (h, w, 3), flow and masks (h, w)")
     st = CCutStats()
-    check(lib().eppm_cutdet_host(C.byref(p), *[x.ctypes.data_as(C.c_void_p) for x in (a, b, bu, bv, o1, o2)], h, w, C.byref(st)), "eppm_cutdet_host")
+    check(lib().eppm_cutdet_host(C.byref(p), *[x.ctypes.data for x in (a, b, bu, bv, o1, o2)], h, w, C.byref(st)), "eppm_cutdet_host")
     return st.as_dict()
 
 
@@ -429,7 +427,7 @@ def objects_label_host(mask, u, v, connectivity=8, min_area=16, max_objects=64):
     labels = np.empty((h, w), np.uint8)
     rec = (CObject * max(int(max_objects), 1))()
     cnt = CObjectsCounts()
-    check(lib().eppm_objects_label_host(C.byref(p), *[x.ctypes.data_as(C.c_void_p) for x in (m, u, v)], h, w, labels.ctypes.data_as(C.c_void_p),
+    check(lib().eppm_objects_label_host(C.byref(p), *[x.ctypes.data for x in (m, u, v)], h, w, labels.ctypes.data,
                                         rec, C.byref(cnt)), "eppm_objects_label_host")
     counts = cnt.as_dict()
     del counts["next_id"]
@@ -446,7 +444,7 @@ def objects_carry_host(labels, bu, bv, occ2):
         raise ValueError("objects_carry_host: labels, flow and mask (h, w)")
     h, w = lab.shape
     out = np.empty((h, w), np.uint8)
-    check(lib().eppm_objects_carry_host(*[x.ctypes.data_as(C.c_void_p) for x in (lab, bu, bv, o)], h, w, out.ctypes.data_as(C.c_void_p)),
+    check(lib().eppm_objects_carry_host(*[x.ctypes.data for x in (lab, bu, bv, o)], h, w, out.ctypes.data),
           "eppm_objects_carry_host")
     return out
 
@@ -472,8 +470,8 @@ def objects_assign_host(labels, n, carried, prev_id, prev_age, next_id, max_obje
     h, w = lab.shape
     rec = (CObject * max(int(n), 1))()
     nxt = C.c_int32(int(next_id))
-    check(lib().eppm_objects_assign_host(C.byref(p), lab.ctypes.data_as(C.c_void_p), None if car is None else car.ctypes.data_as(C.c_void_p), h, w,
-                                         int(n), pid.ctypes.data_as(C.c_void_p), page.ctypes.data_as(C.c_void_p), C.byref(nxt), rec),
+    check(lib().eppm_objects_assign_host(C.byref(p), lab.ctypes.data, _p(car), h, w,
+                                         int(n), pid.ctypes.data, page.ctypes.data, C.byref(nxt), rec),
           "eppm_objects_assign_host")
     return [int(rec[k].id) for k in range(n)], [int(rec[k].age) for k in range(n)], pid, page, int(nxt.value)
 
@@ -481,10 +479,6 @@ def objects_assign_host(labels, n, carried, prev_id, prev_age, next_id, max_obje
 def _plate_params(margins=(0, 0), grow=2, accept_invalid=False, thresh=40.0, n_max=64, min_count=2):
     from ._lib import CPlateParams
     return CPlateParams(1.0, 3, int(margins[0]), int(margins[1]), int(grow), int(bool(accept_invalid)), float(thresh), int(n_max), int(min_count))
-
-
-def _vp(a):
-    return a.ctypes.data_as(C.c_void_p)
 
 
 def plate_forms_host(path):
@@ -495,7 +489,7 @@ def plate_forms_host(path):
         raise ValueError("plate_forms_host: a path is six numbers")
     fwd, inv = np.empty(6, np.float32), np.empty(6, np.float32)
     ok = C.c_int()
-    check(lib().eppm_plate_forms_host(_vp(p), _vp(fwd), _vp(inv), C.byref(ok)), "eppm_plate_forms_host")
+    check(lib().eppm_plate_forms_host(_p(p), _p(fwd), _p(inv), C.byref(ok)), "eppm_plate_forms_host")
     return fwd, inv, bool(ok.value)
 
 
@@ -507,7 +501,7 @@ def plate_block_host(mask, grow=2, accept_invalid=False):
     h, w = m.shape
     p = _plate_params(grow=grow, accept_invalid=accept_invalid)
     out = np.empty((h, w), np.uint8)
-    check(lib().eppm_plate_block_host(C.byref(p), _vp(m), h, w, _vp(out)), "eppm_plate_block_host")
+    check(lib().eppm_plate_block_host(C.byref(p), _p(m), h, w, _p(out)), "eppm_plate_block_host")
     return out
 
 
@@ -524,7 +518,7 @@ def plate_accumulate_host(state, fwd, img1, blocked, margins=(0, 0), thresh=40.0
     if st.shape != (h + 2 * int(margins[1]), w + 2 * int(margins[0]), 4):
         raise ValueError("plate_accumulate_host: state (h + 2*my, w + 2*mx, 4)")
     p = _plate_params(margins=margins, thresh=thresh, n_max=n_max)
-    check(lib().eppm_plate_accumulate_host(C.byref(p), _vp(f), _vp(a), _vp(b), h, w, _vp(st)), "eppm_plate_accumulate_host")
+    check(lib().eppm_plate_accumulate_host(C.byref(p), _p(f), _p(a), _p(b), h, w, _p(st)), "eppm_plate_accumulate_host")
     return st
 
 
@@ -542,7 +536,7 @@ def plate_render_host(state, inv, ok, img1, blocked, margins=(0, 0), min_count=2
         raise ValueError("plate_render_host: state (h + 2*my, w + 2*mx, 4)")
     p = _plate_params(margins=margins, min_count=min_count)
     out, fill = np.empty((h, w, 3), np.uint8), np.empty((h, w), np.uint8)
-    check(lib().eppm_plate_render_host(C.byref(p), _vp(f), int(bool(ok)), _vp(a), _vp(b), h, w, _vp(st), _vp(out), _vp(fill)),
+    check(lib().eppm_plate_render_host(C.byref(p), _p(f), int(bool(ok)), _p(a), _p(b), h, w, _p(st), _p(out), _p(fill)),
           "eppm_plate_render_host")
     return out, fill
 

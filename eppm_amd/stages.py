@@ -25,10 +25,10 @@ class Dev:
         self.ptr = C.c_void_p()
         if pitched:
             pitch = C.c_size_t()
-            check(lib().eppm_malloc_pitched(C.byref(self.ptr), C.byref(pitch), C.c_size_t(row), C.c_size_t(self.h)), "malloc_pitched")
+            check(lib().eppm_malloc_pitched(C.byref(self.ptr), C.byref(pitch), row, self.h), "malloc_pitched")
             self.pitch = pitch.value
         else:
-            check(lib().eppm_malloc_device(C.byref(self.ptr), C.c_size_t(row * self.h)), "malloc")
+            check(lib().eppm_malloc_device(C.byref(self.ptr), row * self.h), "malloc")
             self.pitch = row
         if arr is not None:
             self.put(arr)
@@ -36,14 +36,12 @@ class Dev:
     def put(self, arr):
         arr = np.ascontiguousarray(arr, self.dtype)
         row = self.w * self.dtype.itemsize
-        check(lib().eppm_memcpy2d_h2d(self.ptr, C.c_size_t(self.pitch), arr.ctypes.data_as(C.c_void_p), C.c_size_t(row),
-                                      C.c_size_t(row), C.c_size_t(self.h)), "h2d")
+        check(lib().eppm_memcpy2d_h2d(self.ptr, self.pitch, arr.ctypes.data, row, row, self.h), "h2d")
 
     def get(self):
         out = np.empty((self.h, self.w), self.dtype)
         row = self.w * self.dtype.itemsize
-        check(lib().eppm_memcpy2d_d2h(out.ctypes.data_as(C.c_void_p), C.c_size_t(row), self.ptr, C.c_size_t(self.pitch),
-                                      C.c_size_t(row), C.c_size_t(self.h)), "d2h")
+        check(lib().eppm_memcpy2d_d2h(out.ctypes.data, row, self.ptr, self.pitch, row, self.h), "d2h")
         return out
 
     def free(self):
@@ -62,21 +60,17 @@ def set_params(params=None):
     check(lib().eppm_set_launcher_params(C.byref(params) if params is not None else None), "eppm_set_launcher_params")
 
 
-def _sz(v):
-    return C.c_size_t(v)
-
-
 def probe_fast_exp(x):
     x = np.ascontiguousarray(x, np.float32)
     y = np.empty_like(x)
-    check(lib().eppm_probe_fast_exp(x.ctypes.data_as(C.c_void_p), y.ctypes.data_as(C.c_void_p), x.size), "probe_fast_exp")
+    check(lib().eppm_probe_fast_exp(x.ctypes.data, y.ctypes.data, x.size), "probe_fast_exp")
     return y
 
 
 def probe_div_const(x, which):
     x = np.ascontiguousarray(x, np.float32)
     y = np.empty_like(x)
-    check(lib().eppm_probe_div_const(x.ctypes.data_as(C.c_void_p), y.ctypes.data_as(C.c_void_p), x.size, which), "probe_div_const")
+    check(lib().eppm_probe_div_const(x.ctypes.data, y.ctypes.data, x.size, which), "probe_div_const")
     return y
 
 
@@ -84,21 +78,21 @@ def probe_delta_table(d, which):
     """the table form of a range term at the distances d (test library; include/eppm_test.h)"""
     x = np.ascontiguousarray(d, np.float32)
     y = np.empty_like(x)
-    check(lib().eppm_probe_delta_table(x.ctypes.data_as(C.c_void_p), y.ctypes.data_as(C.c_void_p), x.size, which), "probe_delta_table")
+    check(lib().eppm_probe_delta_table(x.ctypes.data, y.ctypes.data, x.size, which), "probe_delta_table")
     return y
 
 
 def gauss_filter_rgba(img, sigma, radius):
     h, w = img.shape
     a, b = Dev(img, pitched=True), Dev(shape=(h, w), dtype=uchar4, pitched=True)
-    check(lib().eppm_gauss_filter_rgba(b.ptr, a.ptr, _sz(a.pitch), h, w, C.c_float(sigma), radius), "gauss")
+    check(lib().eppm_gauss_filter_rgba(b.ptr, a.ptr, a.pitch, h, w, sigma, radius), "gauss")
     return b.get()
 
 
 def resize_rgba(img, out_h, out_w, ratio):
     h, w = img.shape
     a, b = Dev(img, pitched=True), Dev(shape=(out_h, out_w), dtype=uchar4, pitched=True)
-    check(lib().eppm_resize_rgba(b.ptr, _sz(b.pitch), out_h, out_w, a.ptr, _sz(a.pitch), h, w, C.c_float(ratio)), "resize_rgba")
+    check(lib().eppm_resize_rgba(b.ptr, b.pitch, out_h, out_w, a.ptr, a.pitch, h, w, ratio), "resize_rgba")
     return b.get()
 
 
@@ -107,7 +101,7 @@ def census_transform(img1, img2):
     h, w = img1.shape
     a, b = Dev(img1, pitched=True), Dev(img2, pitched=True)
     c1, c2 = Dev(shape=(h, w), dtype=np.uint8, pitched=True), Dev(shape=(h, w), dtype=np.uint8, pitched=True)
-    lib().baoCudaCensusTransform(c1.ptr, c2.ptr, a.ptr, b.ptr, w, h, _sz(a.pitch), _sz(c1.pitch))
+    lib().baoCudaCensusTransform(c1.ptr, c2.ptr, a.ptr, b.ptr, w, h, a.pitch, c1.pitch)
     check_launcher("baoCudaCensusTransform")
     return c1.get(), c2.get()
 
@@ -131,8 +125,7 @@ def prepare(raw1, raw2, dims):
     arrW = (C.c_int * n)(*[d[1] for d in dims])
     p4 = (C.c_size_t * n)(*[b.pitch for b in p1])
     pc = (C.c_size_t * n)(*[b.pitch for b in c1])
-    lib().baoCudaPatchMatchMultiscalePrepare(tab(p1), tab(p2), tab(c1), tab(c2), tab(t1), tab(t2), arrH, arrW, p4, pc, n,
-                                             r1.ptr, r2.ptr, h, w)
+    lib().baoCudaPatchMatchMultiscalePrepare(tab(p1), tab(p2), tab(c1), tab(c2), tab(t1), tab(t2), arrH, arrW, p4, pc, n, r1.ptr, r2.ptr, h, w)
     check_launcher("baoCudaPatchMatchMultiscalePrepare")
     return [b.get() for b in p1], [b.get() for b in p2], [b.get() for b in c1], [b.get() for b in c2]
 
@@ -158,7 +151,7 @@ class PmRng:
     def block_states(self):
         nb = ((self.w + 15) // 16) * ((self.h + 15) // 16)
         out = np.empty((nb, 6), np.uint32)
-        check(lib().eppm_pm_rng_block_states(self.p, out.ctypes.data_as(C.c_void_p), _sz(out.size)), "rng_block_states")
+        check(lib().eppm_pm_rng_block_states(self.p, out.ctypes.data, out.size), "rng_block_states")
         return out
 
     def __del__(self):
@@ -171,28 +164,27 @@ class PmRng:
 
 def pm_gen_rand_field(rng):
     nnf = Dev(shape=(rng.h, rng.w), dtype=short2)
-    check(lib().eppm_memset_device(nnf.ptr, 0, _sz(nnf.pitch * nnf.h)), "memset")
-    check(lib().eppm_pm_gen_rand_field(rng.p, nnf.ptr, rng.w, rng.h, _sz(nnf.pitch)), "pm_gen_rand_field")
+    check(lib().eppm_memset_device(nnf.ptr, 0, nnf.pitch * nnf.h), "memset")
+    check(lib().eppm_pm_gen_rand_field(rng.p, nnf.ptr, rng.w, rng.h, nnf.pitch), "pm_gen_rand_field")
     return nnf.get()
 
 
 def pm_cost_field(nnf, P):
     n, c = Dev(nnf), Dev(shape=(P.h, P.w), dtype=np.float32)
-    check(lib().eppm_pm_cost_field(c.ptr, n.ptr, *P.args(), P.w, P.h, _sz(P.i1.pitch), _sz(c.pitch), _sz(n.pitch), _sz(P.c1.pitch)),
+    check(lib().eppm_pm_cost_field(c.ptr, n.ptr, *P.args(), P.w, P.h, P.i1.pitch, c.pitch, n.pitch, P.c1.pitch),
           "pm_cost_field")
     return c.get()
 
 
 def pm_seg_propagate(cost, nnf, P, direction):
     n, c = Dev(nnf), Dev(cost)
-    check(lib().eppm_pm_seg_propagate(c.ptr, n.ptr, *P.args(), P.w, P.h, _sz(P.i1.pitch), _sz(c.pitch), _sz(n.pitch), _sz(P.c1.pitch),
-                                      direction), "pm_seg_propagate")
+    check(lib().eppm_pm_seg_propagate(c.ptr, n.ptr, *P.args(), P.w, P.h, P.i1.pitch, c.pitch, n.pitch, P.c1.pitch, direction), "pm_seg_propagate")
     return c.get(), n.get()
 
 
 def pm_jump_propagate(cost, nnf, P):
     n, c = Dev(nnf), Dev(cost)
-    check(lib().eppm_pm_jump_propagate(c.ptr, n.ptr, *P.args(), P.w, P.h, _sz(P.i1.pitch), _sz(c.pitch), _sz(n.pitch), _sz(P.c1.pitch)),
+    check(lib().eppm_pm_jump_propagate(c.ptr, n.ptr, *P.args(), P.w, P.h, P.i1.pitch, c.pitch, n.pitch, P.c1.pitch),
           "pm_jump_propagate")
     return c.get(), n.get()
 
@@ -200,15 +192,13 @@ def pm_jump_propagate(cost, nnf, P):
 def pm_parallel_propagate(cost, nnf, P):
     """One launch of the 4-neighbour propagation (baoParallelPropagate, bao_pmflow_kernel.cu:720-795)."""
     n, c = Dev(nnf), Dev(cost)
-    check(lib().eppm_pm_parallel_propagate(c.ptr, n.ptr, *P.args(), P.w, P.h, _sz(P.i1.pitch), _sz(c.pitch), _sz(n.pitch),
-                                           _sz(P.c1.pitch)), "pm_parallel_propagate")
+    check(lib().eppm_pm_parallel_propagate(c.ptr, n.ptr, *P.args(), P.w, P.h, P.i1.pitch, c.pitch, n.pitch, P.c1.pitch), "pm_parallel_propagate")
     return c.get(), n.get()
 
 
 def pm_random_search(rng, cost, nnf, P):
     n, c = Dev(nnf), Dev(cost)
-    check(lib().eppm_pm_random_search(rng.p, c.ptr, n.ptr, *P.args(), P.w, P.h, _sz(P.i1.pitch), _sz(c.pitch), _sz(n.pitch),
-                                      _sz(P.c1.pitch)), "pm_random_search")
+    check(lib().eppm_pm_random_search(rng.p, c.ptr, n.ptr, *P.args(), P.w, P.h, P.i1.pitch, c.pitch, n.pitch, P.c1.pitch), "pm_random_search")
     return c.get(), n.get()
 
 
@@ -244,7 +234,7 @@ def probe_search_pretest(iteration, w, h, patch_r=9, problems=2, npairs=1):
 def patchmatch(P):
     """baoCudaPatchMatch -> (nnf, cost)"""
     n, c = Dev(shape=(P.h, P.w), dtype=short2), Dev(shape=(P.h, P.w), dtype=np.float32)
-    lib().baoCudaPatchMatch(n.ptr, c.ptr, *P.args(), P.w, P.h, _sz(P.i1.pitch), _sz(c.pitch), _sz(n.pitch), _sz(P.c1.pitch))
+    lib().baoCudaPatchMatch(n.ptr, c.ptr, *P.args(), P.w, P.h, P.i1.pitch, c.pitch, n.pitch, P.c1.pitch)
     check_launcher("baoCudaPatchMatch")
     return n.get(), c.get()
 
@@ -252,7 +242,7 @@ def patchmatch(P):
 def left_right_check(nnf1, cost1, nnf2, cost2):
     h, w = nnf1.shape
     a, b, c, d = Dev(nnf1), Dev(cost1), Dev(nnf2), Dev(cost2)
-    lib().baoCudaLeftRightCheck(a.ptr, b.ptr, c.ptr, d.ptr, w, h, _sz(b.pitch), _sz(a.pitch))
+    lib().baoCudaLeftRightCheck(a.ptr, b.ptr, c.ptr, d.ptr, w, h, b.pitch, a.pitch)
     check_launcher("baoCudaLeftRightCheck")
     return a.get(), b.get(), c.get(), d.get()
 
@@ -260,7 +250,7 @@ def left_right_check(nnf1, cost1, nnf2, cost2):
 def outlier_removal(nnf, cost):
     h, w = nnf.shape
     a, b = Dev(nnf), Dev(cost)
-    lib().baoCudaOutlierRemoval(a.ptr, b.ptr, w, h, _sz(b.pitch), _sz(a.pitch))
+    lib().baoCudaOutlierRemoval(a.ptr, b.ptr, w, h, b.pitch, a.pitch)
     check_launcher("baoCudaOutlierRemoval")
     return a.get(), b.get()
 
@@ -268,7 +258,7 @@ def outlier_removal(nnf, cost):
 def weighted_median(nnf, img, num_iter=20, only_occlusion=True):
     h, w = nnf.shape
     a, i = Dev(nnf), Dev(img, pitched=True)
-    lib().baoCudaWeightedMedianFilter(a.ptr, None, i.ptr, w, h, _sz(i.pitch), _sz(w * 4), _sz(a.pitch), num_iter, C.c_bool(only_occlusion))
+    lib().baoCudaWeightedMedianFilter(a.ptr, None, i.ptr, w, h, i.pitch, w * 4, a.pitch, num_iter, only_occlusion)
     check_launcher("baoCudaWeightedMedianFilter")
     return a.get()
 
@@ -276,7 +266,7 @@ def weighted_median(nnf, img, num_iter=20, only_occlusion=True):
 def fill_holes(nnf, img):
     h, w = nnf.shape
     a, i = Dev(nnf), Dev(img, pitched=True)
-    lib().baoCudaFillHole(a.ptr, None, i.ptr, w, h, _sz(i.pitch), _sz(w * 4), _sz(a.pitch))
+    lib().baoCudaFillHole(a.ptr, None, i.ptr, w, h, i.pitch, w * 4, a.pitch)
     check_launcher("baoCudaFillHole")
     return a.get()
 
@@ -284,7 +274,7 @@ def fill_holes(nnf, img):
 def nnf2flow(nnf):
     h, w = nnf.shape
     a, f = Dev(nnf), Dev(shape=(h, w), dtype=float2)
-    lib().baoCudaNNF2Flow(f.ptr, a.ptr, w, h, _sz(a.pitch), _sz(f.pitch))
+    lib().baoCudaNNF2Flow(f.ptr, a.ptr, w, h, a.pitch, f.pitch)
     check_launcher("baoCudaNNF2Flow")
     return f.get()
 
@@ -292,7 +282,7 @@ def nnf2flow(nnf):
 def resize_flow(flow, out_h, out_w, ratio=2.0):
     h, w = flow.shape
     a, b = Dev(flow), Dev(shape=(out_h, out_w), dtype=float2)
-    check(lib().eppm_resize_flow(b.ptr, out_h, out_w, a.ptr, h, w, C.c_float(ratio)), "resize_flow")
+    check(lib().eppm_resize_flow(b.ptr, out_h, out_w, a.ptr, h, w, ratio), "resize_flow")
     return b.get()
 
 
@@ -302,14 +292,14 @@ def flow_upsample(coarse, img):
     h, w = img.shape
     hc, wc = coarse.shape
     a, i, b = Dev(coarse), Dev(img, pitched=True), Dev(shape=(h, w), dtype=float2)
-    check(lib().eppm_flow_upsample(b.ptr, h, w, a.ptr, hc, wc, i.ptr, _sz(i.pitch)), "eppm_flow_upsample")
+    check(lib().eppm_flow_upsample(b.ptr, h, w, a.ptr, hc, wc, i.ptr, i.pitch), "eppm_flow_upsample")
     return b.get()
 
 
 def c2f_refine(flow, P):
     """baoCudaBLFCostFilterRefine"""
     f = Dev(flow)
-    lib().baoCudaBLFCostFilterRefine(f.ptr, *P.args(), P.w, P.h, _sz(P.i1.pitch), _sz(P.c1.pitch))
+    lib().baoCudaBLFCostFilterRefine(f.ptr, *P.args(), P.w, P.h, P.i1.pitch, P.c1.pitch)
     check_launcher("baoCudaBLFCostFilterRefine")
     return f.get()
 
@@ -391,7 +381,7 @@ def blf_c2f(flow_coarse, P_fine, coarse_dims):
 def flow_smoothing(flow, img):
     h, w = flow.shape
     f, i = Dev(flow), Dev(img, pitched=True)
-    lib().baoCudaFlowSmoothing(f.ptr, i.ptr, w, h, _sz(i.pitch), _sz(f.pitch))
+    lib().baoCudaFlowSmoothing(f.ptr, i.ptr, w, h, i.pitch, f.pitch)
     check_launcher("baoCudaFlowSmoothing")
     return f.get()
 
@@ -425,5 +415,5 @@ def flow_to_color(flow, max_disp_x=20.0, max_disp_y=20.0):
     """bao_cuda_convert_flow_to_colorshow (float2 form, basic/bao_basic_cuda.cuh:839-845): (h,w) float2 -> (h,w) uchar4 {R,G,B,0}."""
     h, w = flow.shape
     f, c = Dev(flow), Dev(shape=(h, w), dtype=uchar4)
-    check(lib().eppm_flow_to_color(c.ptr, f.ptr, h, w, C.c_float(max_disp_x), C.c_float(max_disp_y)), "eppm_flow_to_color")
+    check(lib().eppm_flow_to_color(c.ptr, f.ptr, h, w, max_disp_x, max_disp_y), "eppm_flow_to_color")
     return c.get()

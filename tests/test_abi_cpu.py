@@ -44,6 +44,110 @@ def test_library_exports_every_declared_symbol():
     assert not set(_exported(eppm_amd.lib_path("tol"))) & set(_lib.TEST_SYMBOLS)          # no test hooks in it either
 
 
+_BY_VALUE = {"int": C.c_int, "int32_t": C.c_int, "size_t": C.c_size_t, "float": C.c_float, "bool": C.c_bool}
+_RETURNS = {"int": C.c_int, "void": None, "const char*": C.c_char_p}
+
+
+def _prototypes(header):
+    """{name: (restype, argtypes)} of every prototype of a header under the mapping the binding uses: a pointer is c_void_p, const char* is
+    c_char_p, and int / int32_t / size_t / float / bool are the only kinds passed by value.  Anything else is an error, not a skip."""
+    hdr = open(os.path.join(ROOT, "include", header)).read()
+    hdr = re.sub(r"/\*.*?\*/", " ", hdr, flags=re.S)
+    hdr = re.sub(r"//[^\n]*", " ", hdr)
+    out = {}
+    for ret, name, params in re.findall(r"\b(const\s+char\s*\*|int|void)\s+(\w+)\s*\(([^()]*)\)\s*;", hdr):
+        types = []
+        for prm in ([] if params.strip() in ("", "void") else params.split(",")):
+            prm = " ".join(prm.replace("*", " * ").split())
+            if "*" in prm or "[" in prm:
+                types.append(C.c_char_p if re.fullmatch(r"const char \*( \w+)?", prm) else C.c_void_p)
+                continue
+            words = [x for x in prm.split() if x != "const"]
+            assert len(words) == 2 and words[0] in _BY_VALUE, f"{header}: {name}: cannot classify the parameter {prm!r}"
+            types.append(_BY_VALUE[words[0]])
+        assert name not in out, name
+        out[name] = (_RETURNS[" ".join(ret.replace("*", " *").split()).replace(" *", "*")], types)
+    return out
+
+
+def test_signature_table_equals_the_headers():
+    """eppm_amd/_lib.py declares restype and argtypes of the whole C ABI in one table; lib() applies it.  The table must say what the two
+    headers say: the same functions (248 and 16 today), and per function the same number of arguments, the same kind of every argument
+    and the same return type."""
+    pub, hooks = _prototypes("eppm.h"), _prototypes("eppm_test.h")
+    assert len(pub) == 248 and len(hooks) == 16
+    assert list(pub) == _lib.SYMBOLS and list(hooks) == _lib.TEST_SYMBOLS             # the table follows the headers' order too
+    assert set(pub) == _declared("eppm.h") and set(hooks) == _declared("eppm_test.h")    # the prototype parse misses no declared name
+    assert set(_lib.SIGNATURES) == set(pub) | set(hooks)
+    wrong = {n: (_lib.SIGNATURES[n], want) for n, want in {**pub, **hooks}.items() if _lib.SIGNATURES[n] != want}
+    assert not wrong, wrong
+    L = eppm_amd.lib()                          # ... and the loaded library carries it
+    for n, (res, args) in _lib.SIGNATURES.items():
+        fn = getattr(L, n)
+        assert fn.restype == res and list(fn.argtypes) == args, n
+
+
+def test_addresses_arrive_whole():
+    """A pointer handed over as a bare Python integer must reach the library with all 64 bits (undeclared, ctypes would pass its low 32):
+    two host forms, every pointer once wrapped in c_void_p and once as the plain arr.ctypes.data, byte-identical results."""
+    L = eppm_amd.lib()
+    rng = np.random.default_rng(5)
+    h, w = 5, 7
+    img = rng.integers(0, 256, (h, w, 3), dtype=np.uint8)
+    u, v = [(rng.standard_normal((h, w)) * 4).astype(np.float32) for _ in range(2)]
+    acc = [np.full((h, w, 4), k + 1, np.float32) for k in range(2)]
+    rgb = [np.full((h, w, 3), k + 1, np.uint8) for k in range(2)]
+    arrays = [img, u, v] + acc + rgb
+    assert max(a.ctypes.data for a in arrays) > 2 ** 32, [hex(a.ctypes.data) for a in arrays]
+    wrapped = lambda a: C.c_void_p(a.ctypes.data)       # noqa: E731
+    bare = lambda a: a.ctypes.data                      # noqa: E731
+    for k, form in enumerate((wrapped, bare)):
+        assert L.eppm_tfilter_seed_host(form(acc[k]), form(img), h, w) == 0
+        assert L.eppm_flow_to_color_host(form(rgb[k]), form(u), form(v), h, w) == 0
+    assert acc[0].tobytes() == acc[1].tobytes() and rgb[0].tobytes() == rgb[1].tobytes()
+    assert np.array_equal(acc[1][..., :3], img.astype(np.float32)) and (acc[1][..., 3] == 1).all()         # and they are results
+    assert np.array_equal(rgb[1], eppm_amd.io.flow_to_color(u, v))
+
+
+def _values(struct):
+    return [getattr(struct, k) for k, _ in struct._fields_]
+
+
+@pytest.mark.parametrize("factory,struct,default_fn,noun,override", [
+    (eppm_amd.api.Params, _lib.CParams, "eppm_default_params", "parameter", ("patch_r", 7)),
+    (eppm_amd.api.MBlurParams, _lib.CMBlurParams, "eppm_mblur_default_params", "motion-blur parameter", ("taps", 3)),
+    (eppm_amd.api.TrackParams, _lib.CTrackParams, "eppm_track_default_params", "track parameter", ("spacing", 4)),
+    (eppm_amd.api.CMapParams, _lib.CCMapParams, "eppm_cmap_default_params", "correspondence-map parameter", ("tear", 3.5)),
+    (eppm_amd.api.ObjectsParams, _lib.CObjectsParams, "eppm_objects_default_params", "object-detector parameter", ("min_area", 5)),
+    (eppm_amd.api.PlateParams, _lib.CPlateParams, "eppm_plate_default_params", "background-plate parameter", ("margin_x", 6)),
+])
+def test_parameter_factories(factory, struct, default_fn, noun, override):
+    """The six public factories are one function underneath: each returns its own struct with the defaults of its own C default function,
+    applies an override, and refuses an unknown key with a TypeError that names its own kind of parameter."""
+    want = struct()
+    assert getattr(eppm_amd.lib(), default_fn)(C.byref(want)) == 0
+    p = factory()
+    assert type(p) is struct and _values(p) == _values(want)
+    key, value = override
+    assert getattr(want, key) != value
+    q = factory(**{key: value})
+    assert getattr(q, key) == value
+    setattr(want, key, value)
+    assert _values(q) == _values(want)                 # and nothing else moved
+    with pytest.raises(TypeError, match=f"^unknown {noun} nonsense$"):
+        factory(nonsense=1)
+
+
+def test_track_params_start_from_a_struct():
+    p = eppm_amd.api.TrackParams(min_eig=1234, fb_beta=0.25)
+    q = eppm_amd.api.TrackParams(params=p, spacing=4)
+    assert (q.spacing, q.min_eig, q.fb_beta) == (4, 1234, 0.25) and q is not p and p.spacing == 8
+    setattr(p, "spacing", 4)
+    assert _values(q) == _values(p)
+    with pytest.raises(TypeError, match="^unknown track parameter nonsense$"):
+        eppm_amd.api.TrackParams(p, nonsense=1)
+
+
 def test_test_hooks_live_in_the_test_library_only():
     """include/eppm_test.h = the switches and probes of the parity tests.  The product library exports none of them (nothing matching
     eppm_test* / eppm_probe*), the test library exports them on top of everything include/eppm.h declares, and the two are linked from the

@@ -298,7 +298,7 @@ def test_header_declares_the_deflicker_object_and_arguments_are_checked():
     assert L.eppm_deflicker_create(None, None, C.byref(f)) == ARG
     assert L.eppm_deflicker_destroy(None) == 0
     for fn in ("reset", "step", "get", "get_device", "get_field", "get_stats", "get_state", "set_state"):
-        assert getattr(L, f"eppm_deflicker_{fn}")(None, None, None, None) == ARG, fn
+        assert getattr(L, f"eppm_deflicker_{fn}")(None, 0, None, 0) == ARG, fn      # 0: NULL or zero, whichever the slot is (int slot, size_t, pointer)
     assert L.eppm_deflicker_step_frames(None, 0, None, None, C.c_size_t(0), None, None, 0) == ARG
     z, o = np.zeros((4, 4), F), np.zeros((4, 4), np.uint8)
     img = np.zeros((4, 4, 3), np.uint8)
