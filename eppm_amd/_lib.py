@@ -91,6 +91,10 @@ class CDeflickerStats(_Record):
     _fields_ = [("used", C.c_int64), ("valid_cells", C.c_int32), ("cells", C.c_int32)]
 
 
+class CYuvFormat(_Record):
+    _fields_ = [("layout", C.c_int), ("depth", C.c_int), ("msb_aligned", C.c_int), ("matrix", C.c_int), ("full_range", C.c_int), ("siting", C.c_int)]
+
+
 class CObject(_Record):
     _fields_ = [("id", C.c_int32), ("age", C.c_int32), ("area", C.c_int32), ("x0", C.c_int32), ("y0", C.c_int32), ("x1", C.c_int32),
                 ("y1", C.c_int32), ("n_flow", C.c_int32), ("sum_x", C.c_int64), ("sum_y", C.c_int64), ("sum_qu", C.c_int64), ("sum_qv", C.c_int64)]
@@ -179,6 +183,15 @@ eppm_test_c2f_refine_probe:PPPPPIIIP eppm_probe_c2f_pretest:IPP eppm_test_pm_sea
 eppm_probe_dispatch:SPIPI eppm_probe_launch_log:PI eppm_probe_fast_exp:PPI eppm_probe_div_const:PPII eppm_probe_delta_table:PPII
 eppm_probe_unpack_texel:PPI eppm_probe_pm_parity:PPPP eppm_probe_ctx_rng_states:PPZ""")
 
+# what include/eppm_yuv.h declares, in its order (tests/test_yuv_cpu.py checks it as tests/test_abi_cpu.py checks the tables above): exported
+# by all four libraries, applied by lib(), and kept out of SIGNATURES / SYMBOLS, which mirror include/eppm.h and eppm_test.h alone
+_YUV_ABI = _signatures("""
+eppm_yuv_default_format:P eppm_yuv_plane_dims:PIIIPP eppm_yuv_to_rgba:PPPPZIIP eppm_yuv_from_rgba:PPZPPIIP eppm_yuv_to_rgb_host:PPPPZII
+eppm_yuv_from_rgb_host:PPZPPII eppm_yuv_set_images:PPPPP eppm_yuv_set_images_device:PPPPP eppm_yuv_push_image:PPPP eppm_yuv_push_image_device:PPPP
+eppm_yuv_batch_set_images:PPIPPP eppm_yuv_batch_set_images_device:PPIPPP eppm_yuv_batch_push_images:PPIPPP
+eppm_yuv_batch_push_images_device:PPIPPP eppm_y4m_open_read:PSPPPPP eppm_y4m_read_frame:PPPP eppm_y4m_open_write:PSIIPII eppm_y4m_write_frame:PPP
+eppm_y4m_close:P""")
+
 SIGNATURES = {**_ABI, **_TEST_ABI}
 SYMBOLS, TEST_SYMBOLS = list(_ABI), list(_TEST_ABI)
 
@@ -205,7 +218,7 @@ def lib():
         if not os.path.exists(path):
             raise EppmError(f"{path} is missing: run eppm_amd.build() (hipcc --offload-arch=gfx950); there is no CPU fallback")
         L = C.CDLL(path)
-        for name, (res, args) in SIGNATURES.items():
+        for name, (res, args) in {**SIGNATURES, **_YUV_ABI}.items():
             fn = getattr(L, name, None)
             if fn is None:      # a test hook in a product library, or a library built before the function existed (A/B runs): fails at the call
                 continue

@@ -696,6 +696,23 @@ class _Context(_Handle):
     def _need(self):
         """a context exists (EPPM: init has been called; a batch has one from its construction)"""
 
+    # -- Y'CbCr 4:2:0 frames (eppm_amd.yuv, DESIGN.md section 25): what the _yuv methods of both contexts share
+    def _yuv_frames(self, frames, what):
+        """(format, plane pointers, strides, the frames kept alive) of host YuvFrames of one format and of the context's size"""
+        from . import yuv
+        fmt, ptrs, strides, keep = yuv.frames_args(frames, what)
+        if (keep[0].h, keep[0].w) != (self.h, self.w):
+            raise EppmError(f"{what}: frames must be {self.w} x {self.h}")
+        return fmt, ptrs, strides, keep
+
+    def _yuv_devices(self, frames, what):
+        """(plane pointers, pitches) of frames given as lists of stages.Dev planes of one pitch set and of the context's size"""
+        from . import yuv
+        for planes in frames:
+            if (planes[0].h, planes[0].w) != (self.h, self.w):
+                raise EppmError(f"{what}: frames must be {self.w} x {self.h}")
+        return yuv.device_args(frames, what)
+
     def set_stop_level(self, level):
         """Draft mode (eppm_set_stop_level): the pyramid levels below `level` are upsampled edge-aware from the level
         above (one launch each) instead of being refined and smoothed; 0 (default): the full path.  Takes effect at the next compute; a
@@ -791,6 +808,32 @@ class EPPM(_Context):
         if a.shape != (self.h, self.w, 3):
             raise EppmError(f"push_frame: the image must be ({self.h},{self.w},3) uint8")
         check(lib().eppm_push_image(self._ctx, a.ctypes.data, self.w * 3), "eppm_push_image")
+
+    # -- Y'CbCr 4:2:0 frames (eppm_amd.yuv): the context then holds what it holds after the RGB call on yuv.to_rgb ---
+    def set_data_yuv(self, frame1, frame2):
+        """set_data on two YuvFrames (eppm_yuv_set_images): the planes are uploaded as they are and converted on the device."""
+        self._need()
+        fmt, ptrs, strides, _keep = self._yuv_frames([frame1, frame2], "set_data_yuv")
+        check(lib().eppm_yuv_set_images(self._ctx, C.byref(fmt), C.byref(ptrs, 0), C.byref(ptrs, 3 * C.sizeof(C.c_void_p)), strides), "eppm_yuv_set_images")
+        return True
+
+    def push_frame_yuv(self, frame):
+        """push_frame on a YuvFrame (eppm_yuv_push_image)"""
+        self._need()
+        fmt, ptrs, strides, _keep = self._yuv_frames([frame], "push_frame_yuv")
+        check(lib().eppm_yuv_push_image(self._ctx, C.byref(fmt), ptrs, strides), "eppm_yuv_push_image")
+
+    def set_data_yuv_device(self, fmt, planes1, planes2):
+        """planes1, planes2: the format's planes as stages.Dev buffers (eppm_yuv_set_images_device): read in stream order, no RGBA copy."""
+        self._need()
+        ptrs, pitches = self._yuv_devices([planes1, planes2], "set_data_yuv_device")
+        check(lib().eppm_yuv_set_images_device(self._ctx, C.byref(fmt), C.byref(ptrs, 0), C.byref(ptrs, 3 * C.sizeof(C.c_void_p)), pitches),
+              "eppm_yuv_set_images_device")
+
+    def push_frame_yuv_device(self, fmt, planes):
+        self._need()
+        ptrs, pitches = self._yuv_devices([planes], "push_frame_yuv_device")
+        check(lib().eppm_yuv_push_image_device(self._ctx, C.byref(fmt), ptrs, pitches), "eppm_yuv_push_image_device")
 
     def push_frame_device(self, d_rgba, pitch):
         self._need()
@@ -987,6 +1030,34 @@ class EPPMBatch(_Context):
             if x.shape != (self.h, self.w, 3):
                 raise EppmError(f"push_frames: images must be ({self.h},{self.w},3) uint8")
         check(lib().eppm_batch_push_images(self._ctx, len(a), self._ptrs(a), self.w * 3, self._cuts(new_clip, len(a))), "eppm_batch_push_images")
+
+    # -- Y'CbCr 4:2:0 frames (eppm_amd.yuv) ---------------------------------------
+    def set_data_yuv(self, pairs):
+        """pairs: up to npairs (frame1, frame2) tuples of YuvFrames of one format (eppm_yuv_batch_set_images)."""
+        n = len(pairs)
+        fmt, ptrs, strides, _keep = self._yuv_frames([p[0] for p in pairs] + [p[1] for p in pairs], "set_data_yuv")
+        check(lib().eppm_yuv_batch_set_images(self._ctx, C.byref(fmt), n, C.byref(ptrs, 0), C.byref(ptrs, 3 * n * C.sizeof(C.c_void_p)), strides),
+              "eppm_yuv_batch_set_images")
+        self.n = n
+
+    def push_frames_yuv(self, frames, new_clip=None):
+        """push_frames on one YuvFrame per active pair (eppm_yuv_batch_push_images)"""
+        fmt, ptrs, strides, _keep = self._yuv_frames(list(frames), "push_frames_yuv")
+        check(lib().eppm_yuv_batch_push_images(self._ctx, C.byref(fmt), len(frames), ptrs, strides, self._cuts(new_clip, len(frames))),
+              "eppm_yuv_batch_push_images")
+
+    def set_data_yuv_device(self, fmt, planes1, planes2):
+        """planes1, planes2: per pair, the format's planes as stages.Dev buffers (eppm_yuv_batch_set_images_device)."""
+        n = len(planes1)
+        ptrs, pitches = self._yuv_devices(list(planes1) + list(planes2), "set_data_yuv_device")
+        check(lib().eppm_yuv_batch_set_images_device(self._ctx, C.byref(fmt), n, C.byref(ptrs, 0), C.byref(ptrs, 3 * n * C.sizeof(C.c_void_p)), pitches),
+              "eppm_yuv_batch_set_images_device")
+        self.n = n
+
+    def push_frames_yuv_device(self, fmt, planes, new_clip=None):
+        ptrs, pitches = self._yuv_devices(list(planes), "push_frames_yuv_device")
+        check(lib().eppm_yuv_batch_push_images_device(self._ctx, C.byref(fmt), len(planes), ptrs, pitches, self._cuts(new_clip, len(planes))),
+              "eppm_yuv_batch_push_images_device")
 
     def push_frames_device(self, ptrs, pitch, new_clip=None):
         """ptrs: one device address of an RGBA plane per active pair (eppm_batch_push_images_device)."""

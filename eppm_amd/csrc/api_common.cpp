@@ -23,6 +23,10 @@ int set_err(int code, const char* fmt, ...)
 
 extern "C" const char* eppm_last_error(void) { return g_err; }
 
+// eppm_io.cpp builds without this file too (the sanitizer drivers): its messages come here through a hook, set when the library loads
+extern int (*eppm_io_error_hook)(int code, const char* message) __attribute__((visibility("hidden")));
+static const bool g_io_hook_set = (eppm_io_error_hook = [](int code, const char* message) { return set_err(code, "%s", message); }, true);
+
 // where the launchers note what they decided (eppm_internal.h: launch_note): nowhere, unless a test library points this at its log
 namespace eppm { std::atomic<LaunchNoteFn> g_launch_note{nullptr}; }
 #ifdef EPPM_TOL

@@ -14,6 +14,7 @@
 //   stage_object.h/.cpp    the core of the nine per-clip stage objects (tracker.cpp, tfilter.cpp, stabilizer.cpp, cutdet.cpp, cmap.cpp,
 //                          objects.cpp, plate.cpp, defect.cpp, deflicker.cpp): one allocation and event, the hand-over between streams, shared host helpers
 //   device_api.cpp         device-memory plumbing of the ABI (malloc / memcpy / NUMA binding)
+//   yuv.cpp                Y'CbCr 4:2:0 frames (include/eppm_yuv.h): format checks, host forms, the context-less device calls
 //   launchers_ref_abi.cpp  the reference's live extern "C" stage launchers and the sub-stage entry points of the parity tests
 //   test_hooks.cpp         libeppm_hip_test.so only: include/eppm_test.h
 #pragma once
@@ -35,6 +36,7 @@
 #include <tuple>
 #include <vector>
 
+#include "../../include/eppm_yuv.h"
 #include "eppm_internal.h"
 #include "host_registry.h"
 
@@ -166,6 +168,12 @@ EPPM_HIDDEN void pm_iterate(eppm::PmBatch& b, eppm_pm_rng* rng, const float* lut
 
 // ---- state of the context-less launchers that test_hooks.cpp and the colour entry points share (launchers_ref_abi.cpp) ----
 EPPM_HIDDEN int launcher_finish();
+EPPM_HIDDEN hipStream_t launcher_stream();        // what eppm_set_launcher_stream set
+
+// ---- Y'CbCr 4:2:0 frames (yuv.cpp; include/eppm_yuv.h) ----
+// the argument checks every entry point shares: the format, the pitches, and the planes of nframes frames (3 pointers each); k: the coefficients
+EPPM_HIDDEN int yuv_check(const char* what, const eppm_yuv_format* f, const void* const* planes, int nframes, const size_t* pitches, int h, int w,
+                          eppm::YuvK* k);
 
 // ---- what the per-clip stage objects read of a context (context.cpp); the objects' shared core: stage_object.h ----
 EPPM_HIDDEN int ctx_device(const eppm_ctx* c, int* h, int* w);             // the device; h, w: the context's size

@@ -20,6 +20,8 @@ extern "C" int eppm_destroy(eppm_ctx* c)
         if (c->ev_rgb[q]) (void)hipEventDestroy(c->ev_rgb[q]);
     }
     if (c->ev_h2d) (void)hipEventDestroy(c->ev_h2d);
+    cache_free(c->d_yuv, c->d_yuv_bytes, false, c->device);
+    for (int q = 0; q < 2; q++) cache_free(c->h_yuv[q], c->h_yuv_bytes, true, c->device);
     cache_free(c->h_flow, c->h_flow_bytes, true, c->device);
     cache_free(c->bwd, c->bwd_bytes, false, c->device);
     cache_free(c->h_bwd, c->h_bwd_bytes, true, c->device);

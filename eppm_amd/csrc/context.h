@@ -59,6 +59,12 @@ struct eppm_ctx {
     hipEvent_t ev_rgb[2] = {nullptr, nullptr};
     hipEvent_t ev_h2d = nullptr;        // marks the DMA reads of registered caller images
     int rgb_cur = 0;
+    // Y'CbCr frames from the host (eppm_yuv_set_images* / eppm_yuv_push_image*).  Frames of depth 8 are staged in d_rgb
+    // and h_rgb (a frame is never larger than its RGB form); frames of 16-bit words in allocations of their own, made by the first such call:
+    // d_yuv, npairs x both frames, and the pinned h_yuv, double-buffered with h_rgb's events and turn (rgb_cur)
+    uint8_t* d_yuv = nullptr;
+    uint8_t* h_yuv[2] = {nullptr, nullptr};
+    size_t d_yuv_bytes = 0, h_yuv_bytes = 0;
     float* h_flow = nullptr;            // npairs x (u plane | v plane)
     std::vector<float*> out_u, out_v;   // per active pair: where eppm_compute_begin_into sent the planes directly (NULL: staging)
     eppm::HostHold out_hold;            // the registered blocks those planes lie in, in use until eppm_compute_end

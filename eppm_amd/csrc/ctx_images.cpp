@@ -1,6 +1,7 @@
 // ctx_images.cpp -- the images of a context (context.h): set_images (set_data, driver :159-168, + _prepare_data :212-215) from host and
 // device memory, the frame push of the streaming mode, and the host upload of one image that both share.
 #include "context.h"
+#include "yuv.h"
 
 using namespace eppm;
 
@@ -287,4 +288,202 @@ extern "C" int eppm_batch_push_images_device(eppm_ctx* c, int n, const void* con
         HIPCHK(hipMemcpy2DAsync(c->of_pair(c->raw1, k), c->raw_pitch, d_rgba[k], pitch, (size_t)c->w * 4, c->h, hipMemcpyDeviceToDevice, c->stream));
     push_swap(c, new_clip);
     return prepare(c, true);
+}
+
+// ---- Y'CbCr 4:2:0 frames (include/eppm_yuv.h): the calls above with k_yuv_to_rgba in the place of the RGBA copy
+// (device forms) or of k_rgb_to_rgba (host forms).  The kernel writes the slabs' raw planes directly; everything after it is shared. ----
+// device planes of slots 0 .. n - 1 (3 pointers each) -> the raw plane `raw` of every slot, a launch per chunk of the pointer table
+static void yuv_convert(eppm_ctx* c, uint32_t* raw, int n, const void* const* planes, const size_t* pitches, int layout, const YuvK& k)
+{
+    for (int k0 = 0; k0 < n; k0 += kYuvChunk) {
+        const int m = std::min(kYuvChunk, n - k0);
+        YuvSlots S = {};
+        for (int i = 0; i < m; i++)
+            for (int p = 0; p < 3; p++) S.p[i][p] = planes[3 * (k0 + i) + p];
+        launch_yuv_to_rgba(S, m, c->of_pair(raw, k0), c->raw_pitch, c->stride, pitches, c->h, c->w, layout, k, c->stream);
+    }
+}
+
+extern "C" int eppm_yuv_batch_set_images_device(eppm_ctx* c, const eppm_yuv_format* f, int n, const void* const* d1, const void* const* d2,
+                                                const size_t* pitches)
+{
+    if (!c || !d1 || !d2) return set_err(EPPM_ERR_ARG, "eppm_yuv_set_images_device: NULL argument");
+    if (n < 1 || n > c->npairs) return set_err(EPPM_ERR_ARG, "eppm_yuv_set_images_device: %d pairs, context holds %d", n, c->npairs);
+    YuvK k;
+    CHK(yuv_check("eppm_yuv_set_images_device", f, d1, n, pitches, c->h, c->w, &k));
+    CHK(yuv_check("eppm_yuv_set_images_device", f, d2, n, pitches, c->h, c->w, nullptr));
+    HIPCHK(hipSetDevice(c->device));
+    yuv_convert(c, c->raw1, n, d1, pitches, f->layout, k);
+    yuv_convert(c, c->raw2, n, d2, pitches, f->layout, k);
+    c->n_active = n;
+    c->tmp_drop();
+    return prepare(c);
+}
+extern "C" int eppm_yuv_set_images_device(eppm_ctx* c, const eppm_yuv_format* f, const void* const* d1, const void* const* d2, const size_t* pitches)
+{
+    return eppm_yuv_batch_set_images_device(c, f, 1, d1, d2, pitches);
+}
+
+extern "C" int eppm_yuv_batch_push_images_device(eppm_ctx* c, const eppm_yuv_format* f, int n, const void* const* d, const size_t* pitches,
+                                                 const uint8_t* new_clip)
+{
+    if (!c || !d) return set_err(EPPM_ERR_ARG, "eppm_yuv_batch_push_images_device: NULL argument");
+    CHK(push_check(c, "eppm_yuv_batch_push_images_device", true));
+    if (n != c->n_active) return set_err(EPPM_ERR_ARG, "eppm_yuv_batch_push_images_device: %d frames, %d pairs are active", n, c->n_active);
+    YuvK k;
+    CHK(yuv_check("eppm_yuv_batch_push_images_device", f, d, n, pitches, c->h, c->w, &k));
+    HIPCHK(hipSetDevice(c->device));
+    yuv_convert(c, c->raw1, n, d, pitches, f->layout, k);      // the old image 1's raw planes, which the swap then makes image 2's
+    push_swap(c, new_clip);
+    return prepare(c, true);
+}
+extern "C" int eppm_yuv_push_image_device(eppm_ctx* c, const eppm_yuv_format* f, const void* const* d, const size_t* pitches)
+{
+    if (!c || !d) return set_err(EPPM_ERR_ARG, "eppm_yuv_push_image_device: NULL argument");
+    CHK(push_check(c, "eppm_yuv_push_image_device"));
+    return eppm_yuv_batch_push_images_device(c, f, 1, d, pitches, nullptr);
+}
+
+// Where host frames are staged.  Depth 8: frame `fr` of pair k in its half of the slab's d_rgb plane and image 2k + fr of the pinned
+// h_rgb (wh + 2 ceil(w/2) ceil(h/2) <= 3wh bytes).  16-bit words: the same slots of d_yuv and h_yuv, made here by the first such call.
+// The planes of a frame lie packed one after the other, rows without padding.
+struct YuvStage {
+    bool wide;
+    size_t slot;            // bytes of a frame's slot in both stagings
+    size_t off[3], row[3];
+    int rows[3], np;
+    uint8_t* dev(eppm_ctx* c, int k, int fr) const { return wide ? c->d_yuv + (size_t)(2 * k + fr) * slot : c->of_pair(c->d_rgb, k) + (size_t)fr * slot; }
+};
+static int yuv_stage(eppm_ctx* c, const eppm_yuv_format& f, YuvStage* st)
+{
+    st->wide = f.depth > 8;
+    st->np = f.layout == EPPM_YUV_NV12 ? 2 : 3;
+    size_t off = 0;
+    for (int p = 0; p < 3; p++) {
+        yuv_plane_size(f, c->h, c->w, p, &st->rows[p], &st->row[p]);
+        st->off[p] = off;
+        off += st->row[p] * st->rows[p];
+    }
+    st->slot = st->wide ? off : (size_t)c->w * 3 * c->h;
+    if (st->wide && !c->d_yuv) {
+        const size_t bytes = st->slot * 2 * c->npairs;
+        const hipError_t e = cache_alloc((void**)&c->d_yuv, bytes, false, c->device);
+        if (e != hipSuccess) {
+            (void)hipGetLastError();
+            c->d_yuv = nullptr;
+            return set_err(EPPM_ERR_HIP, "hipMalloc of %zu bytes (16-bit frame staging) failed: %s", bytes, hipGetErrorString(e));
+        }
+        c->d_yuv_bytes = bytes;
+    }
+    return EPPM_OK;
+}
+// one host frame -> its staging slot, as upload_rgb sends an image.  A frame whose planes all lie in registered memory is read in place,
+// a copy per plane (the planes are the caller's, rows and planes apart as they are); any other frame is packed into its slot of this
+// turn's pinned buffer -- the planes one after the other, as they lie in the device slot -- and goes up in ONE copy.  dev[3]: where the
+// planes went
+static int upload_yuv(eppm_ctx* c, const YuvStage& st, int k, int fr, const void* const* planes, const size_t* strides, HostHold& hold, bool* direct,
+                      bool* staged, const void** dev)
+{
+    uint8_t* base = st.dev(c, k, fr);
+    size_t bytes = 0;
+    bool in_place = true;
+    for (int p = 0; p < 3; p++) {
+        dev[p] = p < st.np ? base + st.off[p] : nullptr;
+        if (p >= st.np) continue;
+        bytes = st.off[p] + st.row[p] * st.rows[p];
+        in_place = in_place && hold.add(planes[p], strides[p] * (st.rows[p] - 1) + st.row[p]);       // (blocks held for a frame that is then staged are let go with the call)
+    }
+    if (in_place) {
+        for (int p = 0; p < st.np; p++) {
+            const size_t row = st.row[p];
+            if (strides[p] == row) HIPCHK(hipMemcpyAsync(base + st.off[p], planes[p], row * st.rows[p], hipMemcpyHostToDevice, c->stream));
+            else HIPCHK(hipMemcpy2DAsync(base + st.off[p], row, planes[p], strides[p], row, st.rows[p], hipMemcpyHostToDevice, c->stream));
+        }
+        *direct = true;
+        return EPPM_OK;
+    }
+    const int q = c->rgb_cur;
+    if (!*staged) {
+        if (st.wide) HIPCHK(pinned_lazy(&c->h_yuv[q], &c->h_yuv_bytes, st.slot * 2 * c->npairs, c->device));
+        else HIPCHK(pinned_lazy(&c->h_rgb[q], &c->h_rgb_bytes, st.slot * 2 * c->npairs, c->device));
+        if (!c->ev_rgb[q]) HIPCHK(hipEventCreateWithFlags(&c->ev_rgb[q], hipEventDisableTiming));
+        else HIPCHK(hipEventSynchronize(c->ev_rgb[q]));
+    }
+    uint8_t* h = (st.wide ? c->h_yuv[q] : c->h_rgb[q]) + (size_t)(2 * k + fr) * st.slot;
+    for (int p = 0; p < st.np; p++) copy_rows(h + st.off[p], st.row[p], (const uint8_t*)planes[p], strides[p], st.row[p], st.rows[p]);
+    HIPCHK(hipMemcpyAsync(base, h, bytes, hipMemcpyHostToDevice, c->stream));
+    *staged = true;
+    return EPPM_OK;
+}
+
+static int yuv_set_images_host_impl(eppm_ctx* c, const eppm_yuv_format* f, int n, const void* const* p1, const void* const* p2, const size_t* strides,
+                                    HostHold& hold)
+{
+    YuvK k;
+    CHK(yuv_check("eppm_yuv_set_images", f, p1, n, strides, c->h, c->w, &k));
+    CHK(yuv_check("eppm_yuv_set_images", f, p2, n, strides, c->h, c->w, nullptr));
+    HIPCHK(hipSetDevice(c->device));
+    YuvStage st;
+    CHK(yuv_stage(c, *f, &st));
+    std::vector<const void*> dev[2] = {std::vector<const void*>(3 * (size_t)n), std::vector<const void*>(3 * (size_t)n)};
+    bool staged = false, direct = false;
+    for (int i = 0; i < n; i++)
+        for (int fr = 0; fr < 2; fr++) CHK(upload_yuv(c, st, i, fr, (fr ? p2 : p1) + 3 * i, strides, hold, &direct, &staged, &dev[fr][3 * i]));
+    CHK(upload_done(c, direct, staged));
+    c->n_active = n;
+    c->tmp_drop();
+    yuv_convert(c, c->raw1, n, dev[0].data(), st.row, f->layout, k);
+    yuv_convert(c, c->raw2, n, dev[1].data(), st.row, f->layout, k);
+    const int r = prepare(c);
+    if (direct) HIPCHK(hipEventSynchronize(c->ev_h2d));
+    return r;
+}
+extern "C" int eppm_yuv_batch_set_images(eppm_ctx* c, const eppm_yuv_format* f, int n, const void* const* p1, const void* const* p2, const size_t* strides)
+{
+    if (!c || !p1 || !p2) return set_err(EPPM_ERR_ARG, "eppm_yuv_set_images: NULL argument");
+    if (n < 1 || n > c->npairs) return set_err(EPPM_ERR_ARG, "eppm_yuv_set_images: %d pairs, context holds %d", n, c->npairs);
+    HostHold hold;
+    const int r = yuv_set_images_host_impl(c, f, n, p1, p2, strides, hold);
+    if (r != EPPM_OK && !hold.v.empty()) (void)hipStreamSynchronize(c->stream);     // nothing may still read the blocks when `hold` lets them go
+    return r;
+}
+extern "C" int eppm_yuv_set_images(eppm_ctx* c, const eppm_yuv_format* f, const void* const* p1, const void* const* p2, const size_t* strides)
+{
+    return eppm_yuv_batch_set_images(c, f, 1, p1, p2, strides);
+}
+
+static int yuv_push_images_host_impl(eppm_ctx* c, const eppm_yuv_format* f, int n, const void* const* planes, const size_t* strides,
+                                     const uint8_t* new_clip, HostHold& hold)
+{
+    YuvK k;
+    CHK(yuv_check("eppm_yuv_push_image", f, planes, n, strides, c->h, c->w, &k));
+    HIPCHK(hipSetDevice(c->device));
+    YuvStage st;
+    CHK(yuv_stage(c, *f, &st));
+    std::vector<const void*> dev(3 * (size_t)n);
+    bool staged = false, direct = false;
+    for (int i = 0; i < n; i++) CHK(upload_yuv(c, st, i, 1, planes + 3 * i, strides, hold, &direct, &staged, &dev[3 * i]));   // image 2's slots
+    CHK(upload_done(c, direct, staged));
+    push_swap(c, new_clip);
+    yuv_convert(c, c->raw2, n, dev.data(), st.row, f->layout, k);
+    const int r = prepare(c, true);
+    if (direct) HIPCHK(hipEventSynchronize(c->ev_h2d));
+    return r;
+}
+extern "C" int eppm_yuv_batch_push_images(eppm_ctx* c, const eppm_yuv_format* f, int n, const void* const* planes, const size_t* strides,
+                                          const uint8_t* new_clip)
+{
+    if (!c || !planes) return set_err(EPPM_ERR_ARG, "eppm_yuv_batch_push_images: NULL argument");
+    CHK(push_check(c, "eppm_yuv_batch_push_images", true));
+    if (n != c->n_active) return set_err(EPPM_ERR_ARG, "eppm_yuv_batch_push_images: %d frames, %d pairs are active", n, c->n_active);
+    HostHold hold;
+    const int r = yuv_push_images_host_impl(c, f, n, planes, strides, new_clip, hold);
+    if (r != EPPM_OK && !hold.v.empty()) (void)hipStreamSynchronize(c->stream);
+    return r;
+}
+extern "C" int eppm_yuv_push_image(eppm_ctx* c, const eppm_yuv_format* f, const void* const* planes, const size_t* strides)
+{
+    if (!c || !planes) return set_err(EPPM_ERR_ARG, "eppm_yuv_push_image: NULL argument");
+    CHK(push_check(c, "eppm_yuv_push_image"));
+    return eppm_yuv_batch_push_images(c, f, 1, planes, strides, nullptr);
 }

@@ -90,6 +90,18 @@ void launch_pack(void* texels, int tpitch, const uint32_t* img, int ipitch, cons
 void launch_delta_values(float* t2, int n, int which, hipStream_t s);
 void launch_rgb_to_rgba(uint32_t* out, int pitch_px, const uint8_t* rgb, int h, int w, hipStream_t s, Batch bt = kOnePair);
 
+// ---- Y'CbCr 4:2:0 (k_yuv.hip; the arithmetic: yuv.h) ----
+struct YuvK;
+// The plane pointers of up to kYuvChunk slots, passed to the kernel by value: no device table, no allocation, no synchronisation per call.
+constexpr int kYuvChunk = 16;
+struct YuvSlots { const void* p[kYuvChunk][3]; };
+// slots 0 .. n - 1 (n <= kYuvChunk) of S into the RGBA planes dst + slot * dst_stride (bytes), rows dst_pitch bytes apart; pitches in bytes
+void launch_yuv_to_rgba(const YuvSlots& S, int n, uint32_t* dst, size_t dst_pitch, size_t dst_stride, const size_t* pitches, int h, int w, int layout,
+                        const YuvK& k, hipStream_t s);
+bool yuv_to_rgba_vec(const void* dst, size_t dst_pitch, size_t dst_stride);     // whether that launch takes the 16-byte stores
+void launch_rgba_to_yuv(void* const* planes, const size_t* pitches, const uint32_t* src, size_t src_pitch, int h, int w, int layout, const YuvK& k,
+                        hipStream_t s);
+
 // ---- PatchMatch (k_pm_field.hip, k_pm_sweep.hip, k_pm_search.hip; shared: pm_device.cuh) ----
 // One PatchMatch problem = (source planes, target planes, NNF, cost).  The forward (1->2) and backward (2->1)
 // problems of a pair have the same size and run in the same launches (blockIdx.z / blockIdx.y selects one).

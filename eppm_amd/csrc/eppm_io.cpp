@@ -1,8 +1,9 @@
 // eppm_io.cpp -- file formats and error metrics of the reference's CLI path (main.cpp:56-69):
 // PPM reader (basic/bao_basic.cpp:137-218), Middlebury .flo (3rdparty/middlebury/flowIO.cpp:5-20,
-// :48-163), EPE/AAE (basic/bao_flow_tools.cpp:64-111).  No GPU code here.
+// :48-163), EPE/AAE (basic/bao_flow_tools.cpp:64-111); y4m files of 4:2:0 frames (include/eppm_yuv.h).  No GPU code here.
 #include <limits.h>
 #include <math.h>
+#include <stdarg.h>
 #include <stdio.h>
 #include <stdlib.h>
 #include <string.h>
@@ -14,6 +15,7 @@
 #include "interp.h"
 #include "mblur.h"
 #include "temporal.h"
+#include "yuv.h"
 
 static int read_ppm_header(FILE* f, int* type, int* w, int* h)
 {
@@ -418,4 +420,186 @@ extern "C" int eppm_motion_blur_host(uint8_t* rgb_out, const uint8_t* rgb, const
                 }
         }
     return EPPM_OK;
+}
+
+// ---- y4m (YUV4MPEG2) files: include/eppm_yuv.h.  I420 planes; the header's tags map to a format and back. ----
+// A failure's message goes to eppm_last_error through the hook below, which the library sets to its set_err (api_common.cpp).  This file
+// also builds alone, without HIP (the sanitizer drivers of the tests): there the hook stays null and a failure is its code alone.
+int (*eppm_io_error_hook)(int code, const char* message) __attribute__((visibility("hidden"))) = nullptr;
+static int y4m_err(int code, const char* fmt, ...) __attribute__((format(printf, 2, 3)));
+static int y4m_err(int code, const char* fmt, ...)
+{
+    char msg[512];
+    va_list ap;
+    va_start(ap, fmt);
+    vsnprintf(msg, sizeof(msg), fmt, ap);
+    va_end(ap);
+    return eppm_io_error_hook ? eppm_io_error_hook(code, msg) : code;
+}
+using eppm::yuv_plane_size;
+
+struct eppm_y4m {
+    FILE* f = nullptr;
+    bool writing = false;
+    int h = 0, w = 0;
+    eppm_yuv_format fmt;
+    int rows[3];
+    size_t row[3];
+};
+
+namespace {
+// a line of at most n - 1 bytes without its '\n'; -1: end of file before any byte, -2: no '\n' within n - 1 bytes or before the end
+int y4m_line(FILE* f, char* buf, int n)
+{
+    int len = 0;
+    for (;;) {
+        const int ch = fgetc(f);
+        if (ch == EOF) return len == 0 ? -1 : -2;
+        if (ch == '\n') break;
+        if (len >= n - 1) return -2;
+        buf[len++] = (char)ch;
+    }
+    buf[len] = 0;
+    return len;
+}
+int y4m_fail(eppm_y4m* y, int code)
+{
+    if (y->f) fclose(y->f);
+    delete y;
+    return code;
+}
+// the number a tag's value starts with: its leading decimal digits alone (no sign, no blanks), 0 for none, INT_MAX beyond int; *end:
+// the first character after them
+int y4m_int(const char* v, const char** end = nullptr)
+{
+    long long n = 0;
+    for (; *v >= '0' && *v <= '9'; v++) n = n > INT_MAX ? n : n * 10 + (*v - '0');
+    if (end) *end = v;
+    return n > INT_MAX ? INT_MAX : (int)n;
+}
+void y4m_dims(eppm_y4m* y)
+{
+    for (int p = 0; p < 3; p++) yuv_plane_size(y->fmt, y->h, y->w, p, &y->rows[p], &y->row[p]);
+}
+}  // namespace
+
+extern "C" int eppm_y4m_open_read(eppm_y4m** out, const char* path, int* h, int* w, eppm_yuv_format* f, int* fps_num, int* fps_den)
+{
+    if (!out || !path || !h || !w || !f) return y4m_err(EPPM_ERR_ARG, "eppm_y4m_open_read: NULL argument");
+    *out = nullptr;
+    eppm_y4m* y = new eppm_y4m;
+    y->f = fopen(path, "rb");
+    if (!y->f) { const int r = y4m_err(EPPM_ERR_ARG, "eppm_y4m_open_read: cannot open %s", path); return y4m_fail(y, r); }
+    char line[4096];
+    if (y4m_line(y->f, line, sizeof(line)) < 0 || strncmp(line, "YUV4MPEG2", 9) != 0 || (line[9] != ' ' && line[9] != 0))
+        return y4m_fail(y, y4m_err(EPPM_ERR_ARG, "eppm_y4m_open_read: %s: malformed: no YUV4MPEG2 header line", path));
+    y->fmt = eppm_yuv_format{EPPM_YUV_I420, 8, 0, EPPM_YUV_BT709, 0, EPPM_YUV_LEFT};
+    int num = 0, den = 0;
+    bool center_x = false;
+    for (char* tok = strtok(line + 9, " "); tok; tok = strtok(nullptr, " ")) {
+        const char* v = tok + 1;
+        switch (tok[0]) {
+        case 'W': y->w = y4m_int(v); break;
+        case 'H': y->h = y4m_int(v); break;
+        case 'F': {         // num:den, digits on both sides and nothing after them; anything else: unknown (0:0)
+            const char *colon = nullptr, *end = nullptr;
+            num = y4m_int(v, &colon);
+            den = *colon == ':' ? y4m_int(colon + 1, &end) : 0;
+            if (colon == v || *colon != ':' || end == colon + 1 || *end) num = den = 0;
+            break;
+        }
+        case 'I':
+            if (v[0] == 't' || v[0] == 'b' || v[0] == 'm')
+                return y4m_fail(y, y4m_err(EPPM_ERR_ARG, "eppm_y4m_open_read: %s: interlaced material (%s) is not supported", path, tok));
+            break;
+        case 'C':
+            y->fmt.siting = EPPM_YUV_LEFT;       // a tag names depth and siting both: a later tag replaces an earlier one whole
+            if (!strcmp(v, "420jpeg")) { y->fmt.depth = 8; y->fmt.siting = EPPM_YUV_CENTER; }
+            else if (!strcmp(v, "420mpeg2") || !strcmp(v, "420")) y->fmt.depth = 8;
+            else if (!strcmp(v, "420p10")) y->fmt.depth = 10;
+            else if (!strcmp(v, "420p12")) y->fmt.depth = 12;
+            else if (!strcmp(v, "420p16")) y->fmt.depth = 16;
+            else return y4m_fail(y, y4m_err(EPPM_ERR_ARG, "eppm_y4m_open_read: %s: colour space %s is not supported (4:2:0 progressive only)", path, tok));
+            break;
+        case 'X':
+            if (!strcmp(v, "COLORRANGE=FULL")) y->fmt.full_range = 1;
+            else if (!strcmp(v, "COLORRANGE=LIMITED")) y->fmt.full_range = 0;
+            else if (!strcmp(v, "EPPM_SITING=CENTER")) center_x = true;
+            break;
+        default: break;      // A (aspect) and anything unknown
+        }
+    }
+    if (y->w < 1 || y->h < 1) return y4m_fail(y, y4m_err(EPPM_ERR_ARG, "eppm_y4m_open_read: %s: malformed: missing W or H", path));
+    if (y->w > eppm::kYuvMaxDim || y->h > eppm::kYuvMaxDim) return y4m_fail(y, y4m_err(EPPM_ERR_ARG, "eppm_y4m_open_read: %s: malformed: W or H beyond %d", path, eppm::kYuvMaxDim));
+    if (center_x) y->fmt.siting = EPPM_YUV_CENTER;
+    y->fmt.matrix = y->h < 720 ? EPPM_YUV_BT601 : EPPM_YUV_BT709;
+    y4m_dims(y);
+    *h = y->h; *w = y->w; *f = y->fmt;
+    if (fps_num) *fps_num = num;
+    if (fps_den) *fps_den = den;
+    *out = y;
+    return EPPM_OK;
+}
+
+extern "C" int eppm_y4m_read_frame(eppm_y4m* y, void* const* planes, const size_t* strides, int* got)
+{
+    if (!y || !planes || !strides || !got) return y4m_err(EPPM_ERR_ARG, "eppm_y4m_read_frame: NULL argument");
+    if (y->writing) return y4m_err(EPPM_ERR_STATE, "eppm_y4m_read_frame: the file is open for writing");
+    *got = 0;
+    char line[256];
+    const int n = y4m_line(y->f, line, sizeof(line));
+    if (n == -1) return EPPM_OK;
+    if (n < 0 || strncmp(line, "FRAME", 5) != 0 || (line[5] != ' ' && line[5] != 0))
+        return y4m_err(EPPM_ERR_ARG, "eppm_y4m_read_frame: malformed: missing FRAME line");
+    for (int p = 0; p < 3; p++) {
+        if (!planes[p] || strides[p] < y->row[p]) return y4m_err(EPPM_ERR_ARG, "eppm_y4m_read_frame: NULL plane %d or stride below the row's %zu bytes", p, y->row[p]);
+        for (int r = 0; r < y->rows[p]; r++)
+            if (fread((uint8_t*)planes[p] + (size_t)r * strides[p], 1, y->row[p], y->f) != y->row[p])
+                return y4m_err(EPPM_ERR_ARG, "eppm_y4m_read_frame: malformed: truncated frame");
+    }
+    *got = 1;
+    return EPPM_OK;
+}
+
+extern "C" int eppm_y4m_open_write(eppm_y4m** out, const char* path, int h, int w, const eppm_yuv_format* f, int fps_num, int fps_den)
+{
+    if (!out || !path || !f) return y4m_err(EPPM_ERR_ARG, "eppm_y4m_open_write: NULL argument");
+    *out = nullptr;
+    const char* why = nullptr;
+    if (!eppm::yuv_format_ok(*f, &why)) return y4m_err(EPPM_ERR_ARG, "eppm_y4m_open_write: bad format: %s", why);
+    if (f->layout != EPPM_YUV_I420 || f->msb_aligned) return y4m_err(EPPM_ERR_ARG, "eppm_y4m_open_write: a y4m file holds I420 planes of low-aligned words");
+    if (h < 1 || w < 1 || h > eppm::kYuvMaxDim || w > eppm::kYuvMaxDim || fps_num < 1 || fps_den < 1) return y4m_err(EPPM_ERR_ARG, "eppm_y4m_open_write: bad size %d x %d or rate %d:%d", w, h, fps_num, fps_den);
+    eppm_y4m* y = new eppm_y4m;
+    y->writing = true;
+    y->h = h; y->w = w; y->fmt = *f;
+    y4m_dims(y);
+    y->f = fopen(path, "wb");
+    if (!y->f) { const int r = y4m_err(EPPM_ERR_ARG, "eppm_y4m_open_write: cannot open %s", path); return y4m_fail(y, r); }
+    char tag[64];
+    if (f->depth == 8) snprintf(tag, sizeof(tag), "C420%s", f->siting == EPPM_YUV_CENTER ? "jpeg" : "mpeg2");
+    else snprintf(tag, sizeof(tag), "C420p%d%s", f->depth, f->siting == EPPM_YUV_CENTER ? " XEPPM_SITING=CENTER" : "");
+    if (fprintf(y->f, "YUV4MPEG2 W%d H%d F%d:%d Ip A1:1 %s XCOLORRANGE=%s\n", w, h, fps_num, fps_den, tag, f->full_range ? "FULL" : "LIMITED") < 0)
+        return y4m_fail(y, y4m_err(EPPM_ERR_ARG, "eppm_y4m_open_write: cannot write %s", path));
+    *out = y;
+    return EPPM_OK;
+}
+
+extern "C" int eppm_y4m_write_frame(eppm_y4m* y, const void* const* planes, const size_t* strides)
+{
+    if (!y || !planes || !strides) return y4m_err(EPPM_ERR_ARG, "eppm_y4m_write_frame: NULL argument");
+    if (!y->writing) return y4m_err(EPPM_ERR_STATE, "eppm_y4m_write_frame: the file is open for reading");
+    for (int p = 0; p < 3; p++)
+        if (!planes[p] || strides[p] < y->row[p]) return y4m_err(EPPM_ERR_ARG, "eppm_y4m_write_frame: NULL plane %d or stride below the row's %zu bytes", p, y->row[p]);
+    bool ok = fputs("FRAME\n", y->f) >= 0;
+    for (int p = 0; p < 3 && ok; p++)
+        for (int r = 0; r < y->rows[p] && ok; r++) ok = fwrite((const uint8_t*)planes[p] + (size_t)r * strides[p], 1, y->row[p], y->f) == y->row[p];
+    return ok ? EPPM_OK : y4m_err(EPPM_ERR_ARG, "eppm_y4m_write_frame: write failed");
+}
+
+extern "C" int eppm_y4m_close(eppm_y4m* y)
+{
+    if (!y) return EPPM_OK;
+    const bool ok = fclose(y->f) == 0 || !y->writing;
+    delete y;
+    return ok ? EPPM_OK : y4m_err(EPPM_ERR_ARG, "eppm_y4m_close: write failed");
 }

@@ -741,3 +741,4 @@ void bao_cuda_convert_flow_to_colorshow(uchar4* rgbflow, float2* flow_vec, int h
 extern "C" int eppm_launcher_status(void) { return g_launch_status; }
 
 int launcher_finish() { return finish(); }
+hipStream_t launcher_stream() { std::lock_guard<std::mutex> lk(g_mu); return g_stream; }

@@ -3,7 +3,7 @@
 _Run is the streaming loop; every driver below it supplies a stage factory, its compute call and what it reads per slot."""
 import numpy as np
 
-from . import io
+from . import io, yuv
 from ._lib import EppmError
 from .api import (EPPM, BackgroundPlate, CorrespondenceMap, CutDetector, DefectFilter, Deflicker, EPPMBatch, ObjectDetector, Stabilizer, TemporalFilter,
                   Tracker, _level)
@@ -43,6 +43,39 @@ def _bidirectional_device(run):
     run.e.compute_flow_bidirectional_device()
 
 
+class _RgbView:
+    """The frames of a clip of YuvFrames as a driver reads them outside the context: yuv.to_rgb(frame), the bytes the context holds
+    (DESIGN.md section 25), made when asked for"""
+
+    def __init__(self, frames):
+        self.frames = frames
+
+    def __len__(self):
+        return len(self.frames)
+
+    def __getitem__(self, k):
+        if isinstance(k, slice):
+            return [yuv.to_rgb(f) for f in self.frames[k]]
+        return yuv.to_rgb(self.frames[k])
+
+    def __iter__(self):
+        return (yuv.to_rgb(f) for f in self.frames)
+
+
+def _clip_lists(who, clips):
+    """(the clips as lists, whether their frames are YuvFrames).  Every clip is read ONCE, here: a clip may be a generator (yuv.read_y4m
+    is one).  A run with a YuvFrame in it must be YuvFrames throughout, of one format and one size."""
+    clips = [list(clip) for clip in clips]
+    if not any(isinstance(f, yuv.YuvFrame) for clip in clips for f in clip):
+        return clips, False
+    first = next(f for clip in clips for f in clip)
+    for clip in clips:
+        for f in clip:
+            if not isinstance(f, yuv.YuvFrame) or f.fmt.as_dict() != first.fmt.as_dict() or (f.h, f.w) != (first.h, first.w):
+                raise EppmError(f"{who}: all frames of a run must be YuvFrames of one format and size")
+    return clips, True
+
+
 class _Run:
     """One streaming run of clips through a context, a stage object and a cut detector: the protocol every clip driver shares.
 
@@ -68,11 +101,19 @@ class _Run:
 
     def __init__(self, who, clips, slots, params, temporal, stop_level, stage=None, auto_cut=False, cut_params=None, compute=_bidirectional_device,
                  hand_over=False):
-        self.clips = [[np.ascontiguousarray(f, np.uint8) for f in clip] for clip in clips]
+        clips, is_yuv = _clip_lists(who, clips)
+        self.yuv = clips if is_yuv else None       # clips of YuvFrames go through the context's _yuv methods; run.clips: their RGB form
+        if is_yuv:
+            self.clips = [_RgbView(clip) for clip in clips]
+        else:
+            self.clips = [[np.ascontiguousarray(f, np.uint8) for f in clip] for clip in clips]
         self.single = slots is None
         if self.single and len(self.clips[0]) < 2:
             raise EppmError(f"{who}: at least two frames")
-        self.h, self.w, _ = self.clips[0][0].shape
+        if self.yuv is not None:
+            self.h, self.w = self.yuv[0][0].h, self.yuv[0][0].w
+        else:
+            self.h, self.w, _ = self.clips[0][0].shape
         self.steps = list(_sequence_plan([len(c) for c in self.clips], 1 if self.single else slots))
         self.level = None if stop_level is None else _level(stop_level)
         self.params, self.temporal, self.make_stage, self.compute, self.hand_over = params, temporal, stage, compute, hand_over
@@ -103,7 +144,13 @@ class _Run:
         e, clips = self.e, self.clips
         for t, step in enumerate(self.steps):
             self.last = t == len(self.steps) - 1
-            if t == 0:
+            if self.yuv is not None and t == 0:
+                pairs = [(self.yuv[c][0], self.yuv[c][1]) for c, _, _, _ in step]
+                e.set_data_yuv(*pairs[0]) if self.single else e.set_data_yuv(pairs)
+            elif self.yuv is not None:
+                frames = [self.yuv[c][f] for c, f, _, _ in step]
+                e.push_frame_yuv(frames[0]) if self.single else e.push_frames_yuv(frames, [new_clip for _, _, new_clip, _ in step])
+            elif t == 0:
                 pairs = [(clips[c][0], clips[c][1]) for c, _, _, _ in step]
                 e.set_data(*pairs[0]) if self.single else e.set_data(pairs)
             else:
@@ -538,27 +585,34 @@ def track_sequence(frames, params=None, streaming=False, stop_level=0, **track_p
     step per pair --, so that memory does not grow with the clip; the flows from the second pair on start from a temporal prior and are
     not bit for bit the batch's.  stop_level: draft mode (EPPM.set_stop_level): the tracker runs on the draft flows."""
     stop_level = _level(stop_level)
-    frames = [np.ascontiguousarray(f, np.uint8) for f in frames]
+    (frames,), is_yuv = _clip_lists("track_sequence", [frames])
+    as_yuv = frames if is_yuv else None
+    if not is_yuv:
+        frames = [np.ascontiguousarray(f, np.uint8) for f in frames]
     if len(frames) < 2:
         raise EppmError("track_sequence: at least two frames")
+    first = (lambda: yuv.to_rgb(frames[0])) if as_yuv is not None else (lambda: frames[0])      # the frame the seeds are read from
     if streaming:
         with _Run("track_sequence", [frames], None, params, True, stop_level) as run:
             for _ in run:
                 if run.stage is None:           # the tracker needs a computed pair
                     run.stage = Tracker(run.e, 0, **track_params)
-                    out = _track_start(frames[0], run.stage)
+                    out = _track_start(first(), run.stage)
                 run.stage.step()
                 _track_collect(out, run.stage)
     else:               # every pair at once: no frame loop to share
-        h, w, _ = frames[0].shape
+        h, w = (frames[0].h, frames[0].w) if as_yuv is not None else frames[0].shape[:2]
         bat = EPPMBatch(h, w, len(frames) - 1, params=params)
         trk = None
         try:
             bat.set_stop_level(stop_level)
-            bat.set_data(list(zip(frames[:-1], frames[1:])))
+            if as_yuv is not None:
+                bat.set_data_yuv(list(zip(frames[:-1], frames[1:])))
+            else:
+                bat.set_data(list(zip(frames[:-1], frames[1:])))
             bat.compute_flow_bidirectional()
             trk = Tracker(bat, 0, **track_params)
-            out = _track_start(frames[0], trk)
+            out = _track_start(first(), trk)
             for k in range(len(frames) - 1):
                 trk.step(k)
                 _track_collect(out, trk)

@@ -29,6 +29,14 @@
 //                     default 8): taps to each side of a pixel
 //
 //   runeppm [options] --sequence f0.ppm f1.ppm f2.ppm ... --out-prefix P [--temporal 0|1]
+//   runeppm [options] --sequence clip.y4m --out-prefix P [--y4m-out] [--yuv-matrix 601|709|2020] ...
+//
+//                     a single --sequence argument that ends in .y4m is the clip: its 4:2:0 frames go into the
+//                     context as they are (eppm_yuv_set_images / eppm_yuv_push_image: half the bytes of RGB over PCIe, converted on the
+//                     device).  --y4m-out: every frame product of the run is written as ONE file per product in the input's format and
+//                     rate (without a y4m input: 8 bit, BT.709, limited range, 25:1) instead of numbered PPMs -- P_dn.y4m, P_st.y4m,
+//                     P_fk.y4m, P_df.y4m, P_mb.y4m, P_pl.y4m, P_ro.y4m; flows, masks and text outputs are unchanged.  --yuv-matrix:
+//                     the matrix of input and output instead of the default by size (601 below 720 rows, else 709).
 //
 //                     a clip through ONE context: the first pair by eppm_set_images, every later frame by
 //                     eppm_push_image; the flow of frames k-1 -> k is written to P_<k as four digits>.flo (P_0001.flo ...).
@@ -91,6 +99,7 @@
 
 #include "bao_flow_patchmatch_multiscale_cuda.h"
 #include "eppm.h"
+#include "eppm_yuv.h"
 
 template <typename T>
 struct Array3 {       // bao_alloc<T>(n,r,c): one contiguous block reachable through row-pointer tables (bao_basic.h:146-162)
@@ -136,6 +145,8 @@ struct Options {
     bool plate = false, remove_objects = false;             // --plate, --remove-objects
     int plate_mx = 0, plate_my = 0;                         // --plate-margin
     int ob_min_area = 0, ob_max = 0;                        // --min-area, --max-objects (0: the default)
+    bool y4m_out = false;                                   // --y4m-out
+    int yuv_matrix = -1;                                    // --yuv-matrix (-1: the default by size)
 };
 
 static unsigned hash32(unsigned x)
@@ -193,7 +204,8 @@ static int usage()
                     "               [--propagate layer.ppm alpha.ppm] [--objects] [--min-area N] [--max-objects N]\n"
                     "               [--plate] [--plate-margin MX MY] [--remove-objects]\n"
                     "               [--remove-defects] [--defect-thresh D A] [--defect-radius R] [--defect-grow G]\n"
-                    "               [--deflicker] [--flicker-cell N] [--flicker-keep K]\n");
+                    "               [--deflicker] [--flicker-cell N] [--flicker-keep K]\n"
+                    "               --sequence clip.y4m --out-prefix P [--y4m-out] [--yuv-matrix 601|709|2020] [the options above]\n");
     return 2;
 }
 
@@ -205,6 +217,72 @@ static bool write_ppm(const char* name, const unsigned char* rgb, int h, int w)
     ok = fclose(f) == 0 && ok;
     return ok;
 }
+
+static bool ends_with(const char* s, const char* tail)
+{
+    const size_t n = strlen(s), m = strlen(tail);
+    return n >= m && !strcmp(s + n - m, tail);
+}
+
+// One frame of I420 planes in one block, as the y4m calls and the context's YUV calls take them
+struct YuvBuf {
+    std::vector<unsigned char> mem;
+    void* planes[3] = {nullptr, nullptr, nullptr};
+    size_t strides[3] = {0, 0, 0};
+    bool init(const eppm_yuv_format& f, int h, int w)
+    {
+        int rows[3], bytes[3];
+        size_t total = 0;
+        for (int p = 0; p < 3; p++) {
+            if (eppm_yuv_plane_dims(&f, h, w, p, &rows[p], &bytes[p]) != EPPM_OK) return false;
+            total += (size_t)rows[p] * bytes[p];
+        }
+        mem.assign(total, 0);
+        size_t off = 0;
+        for (int p = 0; p < 3; p++) { planes[p] = mem.data() + off; strides[p] = (size_t)bytes[p]; off += (size_t)rows[p] * bytes[p]; }
+        return true;
+    }
+};
+
+// Where the frame products of a clip go: numbered PPMs P_<tag>_<index>.ppm, or with --y4m-out one file P_<tag>.y4m per product, opened by
+// the product's first frame and closed with the run.  A product's frames arrive in the order of their indices.
+struct FrameOut {
+    const char* prefix = nullptr;
+    bool y4m = false;
+    eppm_yuv_format fmt;
+    int h = 0, w = 0, fps_num = 25, fps_den = 1;
+    std::vector<std::pair<std::string, eppm_y4m*>> files;
+    YuvBuf buf;
+    ~FrameOut() { close(); }
+    // closes every file; false if one could not be finished (the run then fails: a short file is no result)
+    bool close()
+    {
+        bool ok = true;
+        for (auto& f : files) ok = (eppm_y4m_close(f.second) == EPPM_OK) && ok;
+        files.clear();
+        return ok;
+    }
+    // the name of a product's first frame, or of its file, for the run's messages
+    std::string first(const char* tag) const { return std::string(prefix) + "_" + tag + (y4m ? ".y4m" : "_0000.ppm ..."); }
+    // name: the file written (or that could not be), for the caller's message
+    bool put(const char* tag, size_t index, const unsigned char* rgb, char* name, size_t name_size)
+    {
+        if (!y4m) {
+            snprintf(name, name_size, "%s_%s_%04zu.ppm", prefix, tag, index);
+            return write_ppm(name, rgb, h, w);
+        }
+        snprintf(name, name_size, "%s_%s.y4m", prefix, tag);
+        eppm_y4m* out = nullptr;
+        for (auto& f : files) if (f.first == tag) out = f.second;
+        if (!out) {
+            if (buf.mem.empty() && !buf.init(fmt, h, w)) return false;
+            if (eppm_y4m_open_write(&out, name, h, w, &fmt, fps_num, fps_den) != EPPM_OK) return false;
+            files.emplace_back(tag, out);
+        }
+        return eppm_yuv_from_rgb_host(&fmt, rgb, (size_t)w * 3, buf.planes, buf.strides, h, w) == EPPM_OK &&
+               eppm_y4m_write_frame(out, buf.planes, buf.strides) == EPPM_OK;
+    }
+};
 
 // --sequence: the clip through one context of the C ABI (frame push, temporal mode; --denoise: the temporal filter on top; --stabilize:
 // the stabiliser on top)
@@ -220,7 +298,34 @@ static int run_sequence(const Options& o)
         else if (kv.first == "propagation") prm.propagation = (int)kv.second;
     }
     int h = 0, w = 0, nch = 3;
-    if (eppm_ppm_size(o.seq[0], &h, &w) != EPPM_OK) { fprintf(stderr, "cannot read %s\n", o.seq[0]); return 1; }
+    // a y4m clip: counted once (the last pair is told apart from the others), then read frame by frame
+    struct Y4mGuard { eppm_y4m* p = nullptr; ~Y4mGuard() { eppm_y4m_close(p); } } yin;
+    const bool y4m_in = o.seq.size() == 1;
+    FrameOut frames_out;
+    eppm_yuv_default_format(&frames_out.fmt);
+    frames_out.fmt.layout = EPPM_YUV_I420;
+    size_t nframes = o.seq.size();
+    YuvBuf yuv[2];
+    if (y4m_in) {
+        eppm_yuv_format f;
+        for (int pass = 0; pass < 2; pass++) {
+            if (eppm_y4m_open_read(&yin.p, o.seq[0], &h, &w, &f, &frames_out.fps_num, &frames_out.fps_den) != EPPM_OK) { fprintf(stderr, "%s\n", eppm_last_error()); return 1; }
+            if (pass == 1) break;
+            if (!yuv[0].init(f, h, w) || !yuv[1].init(f, h, w)) { fprintf(stderr, "%s\n", eppm_last_error()); return 1; }
+            int got = 1;
+            for (nframes = 0; got; nframes += (size_t)got)
+                if (eppm_y4m_read_frame(yin.p, yuv[0].planes, yuv[0].strides, &got) != EPPM_OK) { fprintf(stderr, "%s: %s\n", o.seq[0], eppm_last_error()); return 1; }
+            eppm_y4m_close(yin.p);
+            yin.p = nullptr;
+        }
+        if (nframes < 2) { fprintf(stderr, "%s: a clip needs at least two frames\n", o.seq[0]); return 1; }
+        if (frames_out.fps_num < 1 || frames_out.fps_den < 1) { frames_out.fps_num = 25; frames_out.fps_den = 1; }
+        frames_out.fmt = f;
+    } else if (eppm_ppm_size(o.seq[0], &h, &w) != EPPM_OK) { fprintf(stderr, "cannot read %s\n", o.seq[0]); return 1; }
+    if (o.yuv_matrix >= 0) frames_out.fmt.matrix = o.yuv_matrix;
+    else if (!y4m_in) frames_out.fmt.matrix = EPPM_YUV_BT709;
+    const eppm_yuv_format yfmt = frames_out.fmt;        // of the input (a y4m clip) and of --y4m-out
+    frames_out.prefix = o.prefix; frames_out.y4m = o.y4m_out; frames_out.h = h; frames_out.w = w;
     std::vector<std::vector<unsigned char>> img(2, std::vector<unsigned char>((size_t)h * w * 3));
     std::vector<float> u((size_t)h * w), v((size_t)h * w);
     eppm_ctx* ctx = nullptr;
@@ -277,8 +382,7 @@ static int run_sequence(const Options& o)
     }
     // one frame of --remove-defects: the frame, its mask and its line of counts
     auto write_defects = [&](size_t frame, const unsigned char* rgb, const unsigned char* mask, const eppm_defect_stats& ds) {
-        snprintf(name, sizeof name, "%s_df_%04zu.ppm", o.prefix, frame);
-        if (!write_ppm(name, rgb, h, w)) return false;
+        if (!frames_out.put("df", frame, rgb, name, sizeof name)) return false;
         snprintf(name, sizeof name, "%s_dfm_%04zu.pgm", o.prefix, frame);
         FILE* f = fopen(name, "wb");
         bool ok = f && fprintf(f, "P5\n%d %d\n255\n", w, h) > 0 && fwrite(mask, 1, (size_t)h * w, f) == (size_t)h * w;
@@ -339,10 +443,16 @@ static int run_sequence(const Options& o)
         return usage();
     }
     double total = 0;
-    for (size_t k = 0; k < o.seq.size(); k++) {
+    for (size_t k = 0; k < nframes; k++) {
         int hk = 0, wk = 0;
         std::vector<unsigned char>& cur = img[k == 0 ? 0 : 1];
-        if (eppm_ppm_size(o.seq[k], &hk, &wk) != EPPM_OK || hk != h || wk != w || eppm_load_ppm(o.seq[k], cur.data(), h, w, &nch) != EPPM_OK) {
+        if (y4m_in) {       // the planes for the context, and their RGB form (eppm_yuv_to_rgb_host: the bytes the context holds) for what reads the frame here
+            YuvBuf& y = yuv[k == 0 ? 0 : 1];
+            int got = 0;
+            if (eppm_y4m_read_frame(yin.p, y.planes, y.strides, &got) != EPPM_OK || !got ||
+                eppm_yuv_to_rgb_host(&yfmt, y.planes, y.strides, cur.data(), (size_t)w * 3, h, w) != EPPM_OK)
+                return fail(o.seq[0]);
+        } else if (eppm_ppm_size(o.seq[k], &hk, &wk) != EPPM_OK || hk != h || wk != w || eppm_load_ppm(o.seq[k], cur.data(), h, w, &nch) != EPPM_OK) {
             fprintf(stderr, "cannot read %s (or its size differs from the first frame's)\n", o.seq[k]);
             if (cuts) fclose(cuts); if (obf) fclose(obf);
             eppm_objects_destroy(od); eppm_cmap_destroy(cm); eppm_cutdet_destroy(det);
@@ -354,12 +464,10 @@ static int run_sequence(const Options& o)
         if (o.remove_objects) ro_frames.push_back(cur);
         if (k == 0) {
             if (o.denoise) {
-                snprintf(name, sizeof name, "%s_dn_0000.ppm", o.prefix);
-                if (!write_ppm(name, cur.data(), h, w)) { fprintf(stderr, "cannot write %s\n", name); if (cuts) fclose(cuts); if (obf) fclose(obf); eppm_objects_destroy(od); eppm_cmap_destroy(cm); eppm_cutdet_destroy(det); eppm_stab_destroy(stab); eppm_tfilter_destroy(flt); eppm_destroy(ctx); return 1; }
+                if (!frames_out.put("dn", 0, cur.data(), name, sizeof name)) { fprintf(stderr, "cannot write %s\n", name); if (cuts) fclose(cuts); if (obf) fclose(obf); eppm_objects_destroy(od); eppm_cmap_destroy(cm); eppm_cutdet_destroy(det); eppm_stab_destroy(stab); eppm_tfilter_destroy(flt); eppm_destroy(ctx); return 1; }
             }
             if (dfk.p) {
-                snprintf(name, sizeof name, "%s_fk_0000.ppm", o.prefix);
-                if (!write_ppm(name, cur.data(), h, w)) { fprintf(stderr, "cannot write %s\n", name); return fail("write"); }
+                if (!frames_out.put("fk", 0, cur.data(), name, sizeof name)) { fprintf(stderr, "cannot write %s\n", name); return fail("write"); }
             }
             if (cm) {                  // the layer through the identity map: the first frame is its own anchor
                 std::vector<float> seed((size_t)h * w * 2);
@@ -368,19 +476,21 @@ static int run_sequence(const Options& o)
                 if (eppm_cmap_set_state(cm, 0, seed.data(), cur.data(), (size_t)w * 3) != EPPM_OK) return fail("eppm_cmap_set_state");
                 if (eppm_cmap_set_layer(cm, 0, layer.data(), (size_t)w * 4) != EPPM_OK) return fail("eppm_cmap_set_layer");
                 if (eppm_cmap_render(cm, 0, pl.data(), (size_t)w * 3) != EPPM_OK) return fail("eppm_cmap_render");
-                snprintf(name, sizeof name, "%s_pl_0000.ppm", o.prefix);
-                if (!write_ppm(name, pl.data(), h, w)) { fprintf(stderr, "cannot write %s\n", name); return fail("write"); }
+                if (!frames_out.put("pl", 0, pl.data(), name, sizeof name)) { fprintf(stderr, "cannot write %s\n", name); return fail("write"); }
             }
             if (o.stabilize) {
-                snprintf(name, sizeof name, "%s_st_0000.ppm", o.prefix);
-                if (!write_ppm(name, cur.data(), h, w)) { fprintf(stderr, "cannot write %s\n", name); if (cuts) fclose(cuts); if (obf) fclose(obf); eppm_objects_destroy(od); eppm_cmap_destroy(cm); eppm_cutdet_destroy(det); eppm_stab_destroy(stab); eppm_tfilter_destroy(flt); eppm_destroy(ctx); return 1; }
+                if (!frames_out.put("st", 0, cur.data(), name, sizeof name)) { fprintf(stderr, "cannot write %s\n", name); if (cuts) fclose(cuts); if (obf) fclose(obf); eppm_objects_destroy(od); eppm_cmap_destroy(cm); eppm_cutdet_destroy(det); eppm_stab_destroy(stab); eppm_tfilter_destroy(flt); eppm_destroy(ctx); return 1; }
             }
             continue;
         }
         const auto t0 = std::chrono::steady_clock::now();
-        if (k == 1) { if (eppm_set_images(ctx, img[0].data(), img[1].data(), (size_t)w * 3) != EPPM_OK) return fail("eppm_set_images"); }
+        if (y4m_in) {
+            if (k == 1) { if (eppm_yuv_set_images(ctx, &yfmt, yuv[0].planes, yuv[1].planes, yuv[0].strides) != EPPM_OK) return fail("eppm_yuv_set_images"); }
+            else if (eppm_yuv_push_image(ctx, &yfmt, yuv[1].planes, yuv[1].strides) != EPPM_OK) return fail("eppm_yuv_push_image");
+        }
+        else if (k == 1) { if (eppm_set_images(ctx, img[0].data(), img[1].data(), (size_t)w * 3) != EPPM_OK) return fail("eppm_set_images"); }
         else if (eppm_push_image(ctx, cur.data(), (size_t)w * 3) != EPPM_OK) return fail("eppm_push_image");
-        const bool last = k + 1 == o.seq.size();
+        const bool last = k + 1 == nframes;
         if (!o.denoise && !o.stabilize && !o.auto_cut && !cm && !od && !plt.p && !dfl.p && !dfk.p && !(o.mblur && last)) { if (eppm_compute(ctx, u.data(), v.data()) != EPPM_OK) return fail("eppm_compute"); }
         else {
             if (eppm_compute_bidirectional(ctx, u.data(), v.data(), nullptr, nullptr, nullptr, nullptr) != EPPM_OK) return fail("eppm_compute_bidirectional");
@@ -401,8 +511,7 @@ static int run_sequence(const Options& o)
             if (dfk.p) {
                 if (eppm_deflicker_step(dfk.p, ctx, o.auto_cut ? &cut : nullptr) != EPPM_OK) return fail("eppm_deflicker_step");
                 if (eppm_deflicker_get(dfk.p, 0, fk_rgb.data(), (size_t)w * 3) != EPPM_OK) return fail("eppm_deflicker_get");
-                snprintf(name, sizeof name, "%s_fk_%04zu.ppm", o.prefix, k);
-                if (!write_ppm(name, fk_rgb.data(), h, w)) { fprintf(stderr, "cannot write %s\n", name); return fail("write"); }
+                if (!frames_out.put("fk", k, fk_rgb.data(), name, sizeof name)) { fprintf(stderr, "cannot write %s\n", name); return fail("write"); }
             }
             if (dfl.p) {                // the step of pair (k - 1, k) gives frame k - 1
                 eppm_defect_stats ds;
@@ -460,24 +569,20 @@ static int run_sequence(const Options& o)
         if (eppm_save_flo(name, u.data(), v.data(), h, w) != EPPM_OK) { fprintf(stderr, "cannot write %s\n", name); if (cuts) fclose(cuts); if (obf) fclose(obf); eppm_objects_destroy(od); eppm_cmap_destroy(cm); eppm_cutdet_destroy(det); eppm_stab_destroy(stab); eppm_tfilter_destroy(flt); eppm_destroy(ctx); return 1; }
         printf("pair %zu: %.3f ms%s -> %s\n", k, ms, (o.temporal && k > 1) ? " (seeded)" : "", name);
         if (o.denoise) {
-            snprintf(name, sizeof name, "%s_dn_%04zu.ppm", o.prefix, k);
-            if (!write_ppm(name, dn.data(), h, w)) { fprintf(stderr, "cannot write %s\n", name); if (cuts) fclose(cuts); if (obf) fclose(obf); eppm_objects_destroy(od); eppm_cmap_destroy(cm); eppm_cutdet_destroy(det); eppm_stab_destroy(stab); eppm_tfilter_destroy(flt); eppm_destroy(ctx); return 1; }
+            if (!frames_out.put("dn", k, dn.data(), name, sizeof name)) { fprintf(stderr, "cannot write %s\n", name); if (cuts) fclose(cuts); if (obf) fclose(obf); eppm_objects_destroy(od); eppm_cmap_destroy(cm); eppm_cutdet_destroy(det); eppm_stab_destroy(stab); eppm_tfilter_destroy(flt); eppm_destroy(ctx); return 1; }
         }
         if (o.stabilize) {
-            snprintf(name, sizeof name, "%s_st_%04zu.ppm", o.prefix, k);
-            if (!write_ppm(name, st.data(), h, w)) { fprintf(stderr, "cannot write %s\n", name); if (cuts) fclose(cuts); if (obf) fclose(obf); eppm_objects_destroy(od); eppm_cmap_destroy(cm); eppm_cutdet_destroy(det); eppm_stab_destroy(stab); eppm_tfilter_destroy(flt); eppm_destroy(ctx); return 1; }
+            if (!frames_out.put("st", k, st.data(), name, sizeof name)) { fprintf(stderr, "cannot write %s\n", name); if (cuts) fclose(cuts); if (obf) fclose(obf); eppm_objects_destroy(od); eppm_cmap_destroy(cm); eppm_cutdet_destroy(det); eppm_stab_destroy(stab); eppm_tfilter_destroy(flt); eppm_destroy(ctx); return 1; }
         }
         if (cm) {
-            snprintf(name, sizeof name, "%s_pl_%04zu.ppm", o.prefix, k);
-            if (!write_ppm(name, pl.data(), h, w)) { fprintf(stderr, "cannot write %s\n", name); return fail("write"); }
+            if (!frames_out.put("pl", k, pl.data(), name, sizeof name)) { fprintf(stderr, "cannot write %s\n", name); return fail("write"); }
         }
         for (int fr = 0; o.mblur && fr <= (last ? 1 : 0); fr++) {       // frame k - 1 from the forward flow; the clip's last frame from the backward flow
             if (eppm_motion_blur(ctx, &o.mb, fr, mb.data(), (size_t)w * 3) != EPPM_OK) return fail("eppm_motion_blur");
-            snprintf(name, sizeof name, "%s_mb_%04zu.ppm", o.prefix, k - 1 + fr);
-            if (!write_ppm(name, mb.data(), h, w)) { fprintf(stderr, "cannot write %s\n", name); if (cuts) fclose(cuts); if (obf) fclose(obf); eppm_objects_destroy(od); eppm_cmap_destroy(cm); eppm_cutdet_destroy(det); eppm_stab_destroy(stab); eppm_tfilter_destroy(flt); eppm_destroy(ctx); return 1; }
+            if (!frames_out.put("mb", k - 1 + fr, mb.data(), name, sizeof name)) { fprintf(stderr, "cannot write %s\n", name); if (cuts) fclose(cuts); if (obf) fclose(obf); eppm_objects_destroy(od); eppm_cmap_destroy(cm); eppm_cutdet_destroy(det); eppm_stab_destroy(stab); eppm_tfilter_destroy(flt); eppm_destroy(ctx); return 1; }
         }
     }
-    printf("%zu pairs, %.3f ms per pair\n", o.seq.size() - 1, total / (double)(o.seq.size() - 1));
+    printf("%zu pairs, %.3f ms per pair\n", nframes - 1, total / (double)(nframes - 1));
     if (plt.p) {
         int ch = 0, cw = 0;
         if (eppm_plate_canvas_dims(plt.p, &ch, &cw) != EPPM_OK) return fail("eppm_plate_canvas_dims");
@@ -513,17 +618,17 @@ static int run_sequence(const Options& o)
                 }
                 for (size_t i = 0; i < px; i++) { out[3 * i] = rgba[4 * i]; out[3 * i + 1] = rgba[4 * i + 1]; out[3 * i + 2] = rgba[4 * i + 2]; filled += ro_masks[k][i] == 1; }
             }
-            snprintf(name, sizeof name, "%s_ro_%04zu.ppm", o.prefix, k);
-            if (!write_ppm(name, out.data(), h, w)) { fprintf(stderr, "cannot write %s\n", name); release(); return fail("write"); }
+            if (!frames_out.put("ro", k, out.data(), name, sizeof name)) { fprintf(stderr, "cannot write %s\n", name); release(); return fail("write"); }
         }
         release();
-        printf("%zu frames with %zu pixels filled from the plate -> %s_ro_0000.ppm ...\n", ro_frames.size(), filled, o.prefix);
+        printf("%zu frames with %zu pixels filled from the plate -> %s\n", ro_frames.size(), filled, frames_out.first("ro").c_str());
     }
     const bool dft_ok = !dfl.txt || fclose(dfl.txt) == 0;
     dfl.txt = nullptr;
     if (!dft_ok) { fprintf(stderr, "cannot write %s_defects.txt\n", o.prefix); return fail("write"); }
     const bool cuts_ok = !cuts || fclose(cuts) == 0;
     const bool obf_ok = !obf || fclose(obf) == 0;
+    const bool frames_ok = frames_out.close();
     eppm_plate_destroy(plt.p);
     plt.p = nullptr;
     eppm_defect_destroy(dfl.p);
@@ -536,6 +641,7 @@ static int run_sequence(const Options& o)
     eppm_destroy(ctx);
     if (!cuts_ok) { fprintf(stderr, "cannot write %s_cuts.txt\n", o.prefix); return 1; }
     if (!obf_ok) { fprintf(stderr, "cannot write %s_objects.txt\n", o.prefix); return 1; }
+    if (!frames_ok) { fprintf(stderr, "cannot finish the y4m files of %s: %s\n", o.prefix, eppm_last_error()); return 1; }
     return 0;
 }
 
@@ -645,12 +751,18 @@ int main(int argc, char** argv)
         }
         else if (!strcmp(a, "--min-area")) { if (!val(&v) || v < 1 || v > 0x7fffffff) return usage(); o.ob_min_area = (int)v; o.objects = true; }
         else if (!strcmp(a, "--max-objects")) { if (!val(&v) || v < 1 || v > 255) return usage(); o.ob_max = (int)v; o.objects = true; }
+        else if (!strcmp(a, "--y4m-out")) o.y4m_out = true;
+        else if (!strcmp(a, "--yuv-matrix")) {
+            if (!val(&v) || (v != 601 && v != 709 && v != 2020)) return usage();
+            o.yuv_matrix = v == 601 ? EPPM_YUV_BT601 : v == 709 ? EPPM_YUV_BT709 : EPPM_YUV_BT2020;
+        }
         else if (!strcmp(a, "--temporal")) { if (!val(&v) || (v != 0 && v != 1)) return usage(); o.temporal = (int)v; }
         else if (a[0] == '-' && a[1] == '-') return usage();
         else pos.push_back(a);
     }
     if (!o.seq.empty() || o.prefix) {
-        if (o.seq.size() < 2 || !o.prefix || !pos.empty()) return usage();
+        const bool y4m_clip = o.seq.size() == 1 && ends_with(o.seq[0], ".y4m");
+        if ((o.seq.size() < 2 && !y4m_clip) || !o.prefix || !pos.empty()) return usage();
         if (o.mblur_file || (o.mb_set && !o.mblur)) return usage();       // a clip's blurred frames are named by the prefix
         // the options of the two-image form that a clip has no meaning for are refused, not ignored
         const Options d;
@@ -660,7 +772,7 @@ int main(int argc, char** argv)
             return usage();
         return run_sequence(o);
     }
-    if (o.denoise || o.stabilize || o.auto_cut || o.pl_layer || o.objects || o.plate || o.defects || o.deflicker) return usage();     // the filter, the stabiliser, the cut detector, the map and the object detector walk a clip
+    if (o.denoise || o.stabilize || o.auto_cut || o.pl_layer || o.objects || o.plate || o.defects || o.deflicker || o.y4m_out || o.yuv_matrix >= 0) return usage();     // the filter, the stabiliser, the cut detector, the map and the object detector walk a clip
     if ((o.mblur && !o.mblur_file) || (o.mb_set && !o.mblur)) return usage();
     if (pos.size() == 1 || pos.size() > 3) return usage();
     if (pos.size() >= 2) { o.f1 = pos[0]; o.f2 = pos[1]; }
