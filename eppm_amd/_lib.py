@@ -91,6 +91,14 @@ class CDeflickerStats(_Record):
     _fields_ = [("used", C.c_int64), ("valid_cells", C.c_int32), ("cells", C.c_int32)]
 
 
+class CDeintParams(C.Structure):
+    _fields_ = [("thresh", C.c_int), ("use_occ", C.c_int)]
+
+
+class CDeintStats(_Record):
+    _fields_ = [("temporal", C.c_int64), ("spatial", C.c_int64)]
+
+
 class CYuvFormat(_Record):
     _fields_ = [("layout", C.c_int), ("depth", C.c_int), ("msb_aligned", C.c_int), ("matrix", C.c_int), ("full_range", C.c_int), ("siting", C.c_int)]
 
@@ -192,6 +200,14 @@ eppm_yuv_batch_set_images:PPIPPP eppm_yuv_batch_set_images_device:PPIPPP eppm_yu
 eppm_yuv_batch_push_images_device:PPIPPP eppm_y4m_open_read:PSPPPPP eppm_y4m_read_frame:PPPP eppm_y4m_open_write:PSIIPII eppm_y4m_write_frame:PPP
 eppm_y4m_close:P""")
 
+# what include/eppm_deint.h declares, in its order (tests/test_deint_cpu.py checks it the same way): exported by all four libraries, applied by
+# lib() next to _YUV_ABI, and kept out of SIGNATURES / SYMBOLS
+_DEINT_ABI = _signatures("""
+eppm_deint_default_params:P eppm_deint_create:PPP eppm_deint_create_size:IIIIPP eppm_deint_destroy:P eppm_deint_reset:PI eppm_deint_step:PPPP
+eppm_deint_step_frames:PIPPZPPII eppm_deint_get:PIPZ eppm_deint_get_device:PIPZ eppm_deint_get_mask:PIP eppm_deint_get_stats:PIP
+eppm_deint_get_state:PIPP eppm_deint_set_state:PIPI eppm_deint_step_host:PPPPPPPPPIIII eppm_deint_bob:PZPZIII eppm_deint_bob_stream:PZPZIIIP
+eppm_deint_bob_host:PPIII eppm_deint_y4m_open_read:PSPPPPPP""")
+
 SIGNATURES = {**_ABI, **_TEST_ABI}
 SYMBOLS, TEST_SYMBOLS = list(_ABI), list(_TEST_ABI)
 
@@ -218,7 +234,7 @@ def lib():
         if not os.path.exists(path):
             raise EppmError(f"{path} is missing: run eppm_amd.build() (hipcc --offload-arch=gfx950); there is no CPU fallback")
         L = C.CDLL(path)
-        for name, (res, args) in {**SIGNATURES, **_YUV_ABI}.items():
+        for name, (res, args) in {**SIGNATURES, **_YUV_ABI, **_DEINT_ABI}.items():
             fn = getattr(L, name, None)
             if fn is None:      # a test hook in a product library, or a library built before the function existed (A/B runs): fails at the call
                 continue

@@ -4,7 +4,7 @@ import ctypes as C
 import numpy as np
 
 from .io import object_record
-from ._lib import CDefectParams, CDefectStats, CDeflickerParams, CDeflickerStats, CObject, CObjectsCounts, CObjectsParams, CPlateParams, CCMapParams, CCutParams, CCutStats, CGMotionModel, CMBlurParams, CParams, CStabParams, CTFilterParams, CTrackCounts, CTrackParams, EppmError, check, lib
+from ._lib import CDefectParams, CDefectStats, CDeintParams, CDeintStats, CDeflickerParams, CDeflickerStats, CObject, CObjectsCounts, CObjectsParams, CPlateParams, CCMapParams, CCutParams, CCutStats, CGMotionModel, CMBlurParams, CParams, CStabParams, CTFilterParams, CTrackCounts, CTrackParams, EppmError, check, lib
 
 uchar4 = np.dtype([("x", "u1"), ("y", "u1"), ("z", "u1"), ("w", "u1")])
 short2 = np.dtype([("x", "i2"), ("y", "i2")])
@@ -336,6 +336,73 @@ class Deflicker(_FrameObject):
         rgb = np.ascontiguousarray(frame, np.uint8)
         if rgb.shape != (self.h, self.w, 3):
             raise EppmError(f"Deflicker.set_state: a ({self.h},{self.w},3) uint8 frame")
+        self._call("set_state", int(slot), rgb.ctypes.data, int(bool(empty)))
+
+
+def DeintParams(params=None, **kw):
+    """eppm_deint_params with the defaults of DESIGN.md section 26 (thresh 24, use_occ 1); params: a CDeintParams to start from instead."""
+    return _params(CDeintParams, "eppm_deint_default_params", "deinterlacer parameter", params, **kw)
+
+
+class Deinterlacer(_FrameObject):
+    """Motion-compensated deinterlacing over the pairs of a context (eppm_deint_*).  The context's frames are FIELD
+    FRAMES: a field's rows in place, the other rows filled by the line average (io.deint_bob_host).  Every step() makes the progressive
+    frame at the time of IMAGE 2 of the active pairs of the context's last compute_flow_bidirectional*: its real rows (parity) are image
+    2's, a pixel of a missing row is the slot's previous output gathered along the backward flow where the gate accepts it, the line
+    average elsewhere.  ctx: an EPPM or an EPPMBatch; one slot per pair of it.  An empty slot (new, or after reset()) starts from its
+    pair's image 1; a cut step takes nothing from the reference.  The object is its own allocation on the context's device; close() frees it."""
+    _prefix = "deint"
+
+    def __init__(self, ctx, thresh=24, use_occ=1, size=None, slots=1, device=0):
+        """ctx None: an object without a context, for step_frames on caller planes (eppm_deint_create_size): size = (h, w), `slots` slots."""
+        self.params = CDeintParams(int(thresh), int(use_occ))
+        self._open(ctx, size, slots, device)
+
+    def step(self, cut=None, parity=None, ctx=None):
+        """One step of every active pair's slot.  parity: 0 or 1 per active pair (one number for a single pair): the rows of that pair's
+        image 2 that are real.  cut: None, or one flag per active pair.  Asynchronous on the context's stream."""
+        c = self.ctx if ctx is None else ctx
+        n = getattr(c, "n", 1)
+        if parity is None:
+            raise EppmError("Deinterlacer.step: parity is required")
+        par = [parity] if np.isscalar(parity) else list(parity)
+        if len(par) != n or any(p not in (0, 1) for p in par):
+            raise EppmError("Deinterlacer.step: one parity, 0 or 1, per active pair")
+        if cut is not None and len(cut) != n:
+            raise EppmError("Deinterlacer.step: one cut flag per active pair")
+        flags = None if cut is None else (C.c_uint8 * n)(*[int(bool(x)) for x in cut])
+        self._call("step", c._ctx, flags, (C.c_uint8 * n)(*[int(p) for p in par]))
+
+    def step_frames(self, slot, d_rgba1, d_rgba2, pitch, d_flow_bwd, d_occ2, cut=False, parity=0):
+        """eppm_deint_step_frames: one step of one slot on caller device planes (addresses), synchronous."""
+        self._call("step_frames", int(slot), d_rgba1, d_rgba2, pitch, d_flow_bwd, d_occ2, int(bool(cut)), int(parity))
+
+    def frame(self, slot=0):
+        """(h, w, 3) uint8: the slot's progressive frame of the last step."""
+        return self._rgb("get", slot)
+
+    def mask(self, slot=0):
+        """(h, w) uint8: 0 real row, 1 temporal, 2 spatial."""
+        m = np.empty((self.h, self.w), np.uint8)
+        self._call("get_mask", int(slot), m.ctypes.data)
+        return m
+
+    def stats(self, slot=0):
+        """dict(temporal, spatial): the missing pixels of the slot's last step by mask value."""
+        st = CDeintStats()
+        self._call("get_stats", int(slot), C.byref(st))
+        return st.as_dict()
+
+    def state(self, slot=0):
+        """(frame (h, w, 3) uint8, empty): the slot's reference and whether the slot counts as empty."""
+        rgb, empty = np.empty((self.h, self.w, 3), np.uint8), C.c_int()
+        self._call("get_state", int(slot), rgb.ctypes.data, C.byref(empty))
+        return rgb, bool(empty.value)
+
+    def set_state(self, slot, frame, empty=False):
+        rgb = np.ascontiguousarray(frame, np.uint8)
+        if rgb.shape != (self.h, self.w, 3):
+            raise EppmError(f"Deinterlacer.set_state: a ({self.h},{self.w},3) uint8 frame")
         self._call("set_state", int(slot), rgb.ctypes.data, int(bool(empty)))
 
 

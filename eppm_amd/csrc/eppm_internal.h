@@ -615,6 +615,31 @@ void launch_deflicker_accumulate(const DeflickerArgs& a, hipStream_t s);
 void launch_deflicker_field(const DeflickerArgs& a, hipStream_t s);
 void launch_deflicker_apply(const DeflickerArgs& a, hipStream_t s);
 
+// ---- deinterlacing (k_deint.hip; the arithmetic: deint.h) ----
+// One step covers n pairs, laid out as DeflickerArgs' are; a slot's block: reference 0 | 1 (h*w RGBA words each) | mask (a byte per pixel).
+// The per-slot bits: cur (which reference is the previous output; the step writes the other), empty (the reference is image 1), cut (no
+// candidate is accepted) and parity (which rows of image 2 are real: bit set = the odd rows).
+struct DeintArgs {
+    const uint8_t* img1;
+    const uint8_t* img2;
+    size_t img_pitch, img_stride;
+    const float* bwd;
+    size_t bwd_stride;
+    const uint8_t* occ2;
+    size_t occ_stride;
+    char* mem;
+    size_t slot_stride;
+    int h, w, n, slot0;
+    int thresh, use_occ;
+    uint32_t cur[kTemporalMaxSlots / 32], empty[kTemporalMaxSlots / 32], cut[kTemporalMaxSlots / 32], parity[kTemporalMaxSlots / 32];
+};
+constexpr size_t deint_off_ref(size_t px, int which) { return (size_t)which * px * 4; }
+constexpr size_t deint_off_mask(size_t px) { return px * 8; }
+constexpr size_t deint_slot_bytes(size_t px) { return px * 9; }
+void launch_deint_step(const DeintArgs& a, hipStream_t s);
+// the full h x w frame of a field picture of parity p (fh = (h - p + 1) / 2 rows), both on caller planes; pitches in bytes
+void launch_deint_bob(uint32_t* out, size_t out_pitch, const uint32_t* field, size_t field_pitch, int h, int w, int parity, hipStream_t s);
+
 // ---- flow colour coding (k_color.hip) ----
 // rgba: h*w packed R | G<<8 | B<<16 (alpha 0); flow: h*w float2
 void launch_flow_to_color(uint32_t* rgba, const float* flow, int h, int w, float max_disp_x, float max_disp_y, hipStream_t s, Batch bt = kOnePair);

@@ -1,6 +1,7 @@
 // eppm_io.cpp -- file formats and error metrics of the reference's CLI path (main.cpp:56-69):
 // PPM reader (basic/bao_basic.cpp:137-218), Middlebury .flo (3rdparty/middlebury/flowIO.cpp:5-20,
-// :48-163), EPE/AAE (basic/bao_flow_tools.cpp:64-111); y4m files of 4:2:0 frames (include/eppm_yuv.h).  No GPU code here.
+// :48-163), EPE/AAE (basic/bao_flow_tools.cpp:64-111); y4m files of 4:2:0 frames (include/eppm_yuv.h); the
+// deinterlacer's host forms (include/eppm_deint.h).  No GPU code here.
 #include <limits.h>
 #include <math.h>
 #include <stdarg.h>
@@ -11,6 +12,8 @@
 #include <vector>
 
 #include "../../include/eppm.h"
+#include "../../include/eppm_deint.h"
+#include "deint.h"
 #include "fb_occlusion.h"
 #include "interp.h"
 #include "mblur.h"
@@ -483,19 +486,22 @@ void y4m_dims(eppm_y4m* y)
 }
 }  // namespace
 
-extern "C" int eppm_y4m_open_read(eppm_y4m** out, const char* path, int* h, int* w, eppm_yuv_format* f, int* fps_num, int* fps_den)
+// eppm_y4m_open_read (interlace NULL: interlaced files are refused) and eppm_deint_y4m_open_read (*interlace: 0 progressive, 1 top field
+// first, 2 bottom field first); who: the call's name in the messages
+static int y4m_open(const char* who, eppm_y4m** out, const char* path, int* h, int* w, eppm_yuv_format* f, int* fps_num, int* fps_den, int* interlace)
 {
-    if (!out || !path || !h || !w || !f) return y4m_err(EPPM_ERR_ARG, "eppm_y4m_open_read: NULL argument");
+    if (!out || !path || !h || !w || !f) return y4m_err(EPPM_ERR_ARG, "%s: NULL argument", who);
     *out = nullptr;
     eppm_y4m* y = new eppm_y4m;
     y->f = fopen(path, "rb");
-    if (!y->f) { const int r = y4m_err(EPPM_ERR_ARG, "eppm_y4m_open_read: cannot open %s", path); return y4m_fail(y, r); }
+    if (!y->f) { const int r = y4m_err(EPPM_ERR_ARG, "%s: cannot open %s", who, path); return y4m_fail(y, r); }
     char line[4096];
     if (y4m_line(y->f, line, sizeof(line)) < 0 || strncmp(line, "YUV4MPEG2", 9) != 0 || (line[9] != ' ' && line[9] != 0))
-        return y4m_fail(y, y4m_err(EPPM_ERR_ARG, "eppm_y4m_open_read: %s: malformed: no YUV4MPEG2 header line", path));
+        return y4m_fail(y, y4m_err(EPPM_ERR_ARG, "%s: %s: malformed: no YUV4MPEG2 header line", who, path));
     y->fmt = eppm_yuv_format{EPPM_YUV_I420, 8, 0, EPPM_YUV_BT709, 0, EPPM_YUV_LEFT};
     int num = 0, den = 0;
     bool center_x = false;
+    int mode = 0;
     for (char* tok = strtok(line + 9, " "); tok; tok = strtok(nullptr, " ")) {
         const char* v = tok + 1;
         switch (tok[0]) {
@@ -509,8 +515,9 @@ extern "C" int eppm_y4m_open_read(eppm_y4m** out, const char* path, int* h, int*
             break;
         }
         case 'I':
-            if (v[0] == 't' || v[0] == 'b' || v[0] == 'm')
-                return y4m_fail(y, y4m_err(EPPM_ERR_ARG, "eppm_y4m_open_read: %s: interlaced material (%s) is not supported", path, tok));
+            if (v[0] == 'm' || (!interlace && (v[0] == 't' || v[0] == 'b')))
+                return y4m_fail(y, y4m_err(EPPM_ERR_ARG, "%s: %s: interlaced material (%s) is not supported", who, path, tok));
+            mode = v[0] == 't' ? 1 : v[0] == 'b' ? 2 : 0;       // a later tag replaces an earlier one
             break;
         case 'C':
             y->fmt.siting = EPPM_YUV_LEFT;       // a tag names depth and siting both: a later tag replaces an earlier one whole
@@ -519,7 +526,7 @@ extern "C" int eppm_y4m_open_read(eppm_y4m** out, const char* path, int* h, int*
             else if (!strcmp(v, "420p10")) y->fmt.depth = 10;
             else if (!strcmp(v, "420p12")) y->fmt.depth = 12;
             else if (!strcmp(v, "420p16")) y->fmt.depth = 16;
-            else return y4m_fail(y, y4m_err(EPPM_ERR_ARG, "eppm_y4m_open_read: %s: colour space %s is not supported (4:2:0 progressive only)", path, tok));
+            else return y4m_fail(y, y4m_err(EPPM_ERR_ARG, "%s: %s: colour space %s is not supported (4:2:0 %s)", who, path, tok, interlace ? "only" : "progressive only"));
             break;
         case 'X':
             if (!strcmp(v, "COLORRANGE=FULL")) y->fmt.full_range = 1;
@@ -529,16 +536,24 @@ extern "C" int eppm_y4m_open_read(eppm_y4m** out, const char* path, int* h, int*
         default: break;      // A (aspect) and anything unknown
         }
     }
-    if (y->w < 1 || y->h < 1) return y4m_fail(y, y4m_err(EPPM_ERR_ARG, "eppm_y4m_open_read: %s: malformed: missing W or H", path));
-    if (y->w > eppm::kYuvMaxDim || y->h > eppm::kYuvMaxDim) return y4m_fail(y, y4m_err(EPPM_ERR_ARG, "eppm_y4m_open_read: %s: malformed: W or H beyond %d", path, eppm::kYuvMaxDim));
+    if (y->w < 1 || y->h < 1) return y4m_fail(y, y4m_err(EPPM_ERR_ARG, "%s: %s: malformed: missing W or H", who, path));
+    if (y->w > eppm::kYuvMaxDim || y->h > eppm::kYuvMaxDim) return y4m_fail(y, y4m_err(EPPM_ERR_ARG, "%s: %s: malformed: W or H beyond %d", who, path, eppm::kYuvMaxDim));
+    if (mode != 0 && y->h % 4 != 0)
+        return y4m_fail(y, y4m_err(EPPM_ERR_ARG, "%s: %s: an interlaced 4:2:0 file needs H a multiple of 4 (H%d): each field is a 4:2:0 picture", who, path, y->h));
     if (center_x) y->fmt.siting = EPPM_YUV_CENTER;
     y->fmt.matrix = y->h < 720 ? EPPM_YUV_BT601 : EPPM_YUV_BT709;
     y4m_dims(y);
     *h = y->h; *w = y->w; *f = y->fmt;
     if (fps_num) *fps_num = num;
     if (fps_den) *fps_den = den;
+    if (interlace) *interlace = mode;
     *out = y;
     return EPPM_OK;
+}
+
+extern "C" int eppm_y4m_open_read(eppm_y4m** out, const char* path, int* h, int* w, eppm_yuv_format* f, int* fps_num, int* fps_den)
+{
+    return y4m_open("eppm_y4m_open_read", out, path, h, w, f, fps_num, fps_den, nullptr);
 }
 
 extern "C" int eppm_y4m_read_frame(eppm_y4m* y, void* const* planes, const size_t* strides, int* got)
@@ -602,4 +617,62 @@ extern "C" int eppm_y4m_close(eppm_y4m* y)
     const bool ok = fclose(y->f) == 0 || !y->writing;
     delete y;
     return ok ? EPPM_OK : y4m_err(EPPM_ERR_ARG, "eppm_y4m_close: write failed");
+}
+
+// ---- deinterlacing (include/eppm_deint.h): the interlaced reader and the host forms; the arithmetic is deint.h's ----
+extern "C" int eppm_deint_y4m_open_read(eppm_y4m** out, const char* path, int* h, int* w, eppm_yuv_format* f, int* fps_num, int* fps_den, int* interlace)
+{
+    if (!interlace) return y4m_err(EPPM_ERR_ARG, "eppm_deint_y4m_open_read: NULL argument");
+    return y4m_open("eppm_deint_y4m_open_read", out, path, h, w, f, fps_num, fps_den, interlace);
+}
+
+extern "C" int eppm_deint_default_params(eppm_deint_params* p)
+{
+    if (!p) return y4m_err(EPPM_ERR_ARG, "eppm_deint_default_params: NULL");
+    p->thresh = 24;
+    p->use_occ = 1;
+    return EPPM_OK;
+}
+
+static uint32_t rgb_word(const uint8_t* rgb, size_t i) { return (uint32_t)rgb[3 * i] | (uint32_t)rgb[3 * i + 1] << 8 | (uint32_t)rgb[3 * i + 2] << 16; }
+static void rgb_store(uint8_t* rgb, size_t i, uint32_t o) { rgb[3 * i] = (uint8_t)o; rgb[3 * i + 1] = (uint8_t)(o >> 8); rgb[3 * i + 2] = (uint8_t)(o >> 16); }
+
+extern "C" int eppm_deint_step_host(const eppm_deint_params* p, uint8_t* rgb_out, uint8_t* mask_out, eppm_deint_stats* stats, const uint8_t* rgb_ref,
+                                    const uint8_t* rgb_cur, const float* bu, const float* bv, const uint8_t* occ2, int h, int w, int parity, int cut)
+{
+    if (!p) return y4m_err(EPPM_ERR_ARG, "eppm_deint_step_host: NULL parameters");
+    if (const char* why = eppm::deint_params_bad(p->thresh, p->use_occ)) return y4m_err(EPPM_ERR_ARG, "eppm_deint_step_host: %s", why);
+    if (!rgb_out || !mask_out || !stats || !rgb_ref || !rgb_cur || !bu || !bv || !occ2) return y4m_err(EPPM_ERR_ARG, "eppm_deint_step_host: NULL argument");
+    if (rgb_out == rgb_ref) return y4m_err(EPPM_ERR_ARG, "eppm_deint_step_host: the step gathers, rgb_out must not be rgb_ref");
+    if (h < 2 || w < 1 || (long long)h * w >= (1LL << 31)) return y4m_err(EPPM_ERR_ARG, "eppm_deint_step_host: size %dx%d out of range (h >= 2)", w, h);
+    if (parity != 0 && parity != 1) return y4m_err(EPPM_ERR_ARG, "eppm_deint_step_host: parity %d is not 0 or 1", parity);
+    auto R = [&](int x, int y) { return rgb_word(rgb_ref, (size_t)y * w + x); };
+    *stats = eppm_deint_stats{0, 0};
+    for (int y = 0; y < h; y++)
+        for (int x = 0; x < w; x++) {
+            const size_t i = (size_t)y * w + x;
+            if ((y & 1) == parity) {
+                rgb_store(rgb_out, i, rgb_word(rgb_cur, i));
+                mask_out[i] = 0;
+                continue;
+            }
+            const uint32_t up = rgb_word(rgb_cur, (size_t)eppm::deint_row_up(y) * w + x), dn = rgb_word(rgb_cur, (size_t)eppm::deint_row_dn(y, h) * w + x);
+            uint8_t m;
+            rgb_store(rgb_out, i, eppm::deint_missing_pixel(x, y, up, dn, bu[i], bv[i], occ2[i], cut != 0, p->use_occ, p->thresh, h, w, R, &m));
+            mask_out[i] = m;
+            stats->temporal += m == 1;
+            stats->spatial += m == 2;
+        }
+    return EPPM_OK;
+}
+
+extern "C" int eppm_deint_bob_host(uint8_t* rgb_out, const uint8_t* rgb_field, int h, int w, int parity)
+{
+    if (!rgb_out || !rgb_field) return y4m_err(EPPM_ERR_ARG, "eppm_deint_bob_host: NULL argument");
+    if (h < 2 || w < 1 || (long long)h * w >= (1LL << 31)) return y4m_err(EPPM_ERR_ARG, "eppm_deint_bob_host: size %dx%d out of range (h >= 2)", w, h);
+    if (parity != 0 && parity != 1) return y4m_err(EPPM_ERR_ARG, "eppm_deint_bob_host: parity %d is not 0 or 1", parity);
+    auto F = [&](int x, int i) { return rgb_word(rgb_field, (size_t)i * w + x); };
+    for (int y = 0; y < h; y++)
+        for (int x = 0; x < w; x++) rgb_store(rgb_out, (size_t)y * w + x, eppm::deint_bob_pixel(x, y, parity, h, F));
+    return EPPM_OK;
 }

@@ -1,5 +1,6 @@
-// stage_object.h -- the core the nine per-clip stage objects share: the tracker, the temporal filter, the
-// stabiliser, the cut detector, the correspondence map, the object detector, the background plate, the defect filter and the deflicker object.  Each is one allocation on a device
+// stage_object.h -- the core the ten per-clip stage objects share: the tracker, the temporal filter, the
+// stabiliser, the cut detector, the correspondence map, the object detector, the background plate, the defect filter, the deflicker object
+// and the deinterlacer.  Each is one allocation on a device
 // with one slot per pair of a batch, stepped from a context on the context's stream or on caller planes on the launcher stream, with
 // synchronous getters and setters on the null stream.  Host code only: no kernel and no header a kernel includes knows this file.
 #pragma once
@@ -9,7 +10,7 @@
 #include "api_internal.h"
 
 struct EPPM_HIDDEN StageObject {
-    const char* noun = "object";        // what the object calls itself in messages: "filter", "stabiliser", "detector", "map", "plate", "tracker", "defect filter", "deflicker object"
+    const char* noun = "object";        // what the object calls itself in messages: "filter", "stabiliser", "detector", "map", "plate", "tracker", "defect filter", "deflicker object", "deinterlacer"
     int device = 0, h = 0, w = 0, nslots = 0;
     char* mem = nullptr;                // the one allocation
     size_t bytes = 0;
@@ -54,7 +55,7 @@ struct EPPM_HIDDEN CtxPlanes {
     size_t occ_stride = 0;
     int n = 0;                                          // active pairs
 };
-// the window of eppm_interpolate*, once for all nine objects.  EPPM_ERR_ARG: other dimensions / device, more active pairs than slots
+// the window of eppm_interpolate*, once for all ten objects.  EPPM_ERR_ARG: other dimensions / device, more active pairs than slots
 // (pair NULL) or a pair that is not active (pair given: the tracker's one pair, whose planes *in then holds); EPPM_ERR_STATE: outside the
 // window.  Sets the context's device current; *s: the context's stream
 EPPM_HIDDEN int ctx_stage_inputs(eppm_ctx* c, const StageObject* o, const char* what, CtxPlanes* in, hipStream_t* s, const int* pair = nullptr);

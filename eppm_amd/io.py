@@ -269,6 +269,38 @@ def deflicker_step_host(ref, cur, bu, bv, occ2, cell=32, iters=2, reject=60.0, t
     return out, field, valid, st.as_dict()
 
 
+def deint_step_host(ref, cur, bu, bv, occ2, parity, thresh=24, use_occ=1, cut=False):
+    """One deinterlacer step on the host (eppm_deint_step_host; byte-identical to the kernel).  ref: the (h, w, 3)
+    uint8 reference (the previous output; image 1 for an empty slot); cur: image 2, a field frame whose rows of `parity` are real (its
+    other rows are not read); (bu, bv): the backward flow image 2 -> image 1; occ2: the occlusion mask of image 2's pixels; cut: cur
+    starts another clip.  Returns (rgb (h, w, 3) uint8, mask (h, w) uint8: 0 real row / 1 temporal / 2 spatial, stats dict)."""
+    from ._lib import CDeintParams, CDeintStats
+    p = CDeintParams(int(thresh), int(use_occ))
+    r, c = np.ascontiguousarray(ref, np.uint8), np.ascontiguousarray(cur, np.uint8)
+    bu, bv, o = np.ascontiguousarray(bu, np.float32), np.ascontiguousarray(bv, np.float32), np.ascontiguousarray(occ2, np.uint8)
+    if c.ndim != 3 or c.shape[2] != 3:
+        raise ValueError("deint_step_host: the frame must be (h, w, 3)")
+    h, w, _ = c.shape
+    if r.shape != c.shape or bu.shape != (h, w) or bv.shape != (h, w) or o.shape != (h, w):
+        raise ValueError("deint_step_host: frames (h, w, 3), flow and mask (h, w)")
+    out, mask, st = np.empty_like(c), np.empty((h, w), np.uint8), CDeintStats()
+    check(lib().eppm_deint_step_host(C.byref(p), out.ctypes.data, mask.ctypes.data, C.byref(st), *[x.ctypes.data for x in (r, c, bu, bv, o)],
+                                     h, w, int(parity), int(bool(cut))), "eppm_deint_step_host")
+    return out, mask, st.as_dict()
+
+
+def deint_bob_host(field, h, parity):
+    """The full (h, w, 3) uint8 frame of a field picture ((h - parity + 1) // 2, w, 3) of parity 0 (top) or 1 (eppm_deint_bob_host): row
+    2i + parity is field row i, every other row the line average of its neighbours."""
+    f = np.ascontiguousarray(field, np.uint8)
+    h, parity = int(h), int(parity)
+    if f.ndim != 3 or f.shape[2] != 3 or parity not in (0, 1) or f.shape[0] != (h - parity + 1) // 2:
+        raise ValueError("deint_bob_host: a field of ((h - parity + 1) // 2, w, 3) uint8 and parity 0 or 1")
+    out = np.empty((h, f.shape[1], 3), np.uint8)
+    check(lib().eppm_deint_bob_host(out.ctypes.data, f.ctypes.data, h, f.shape[1], parity), "eppm_deint_bob_host")
+    return out
+
+
 def cmap_seed(h, w):
     """(h, w, 2) float32: the seed of a correspondence map, map(x, y) = (x, y)."""
     m = np.empty((int(h), int(w), 2), np.float32)

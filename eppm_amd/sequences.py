@@ -5,7 +5,7 @@ import numpy as np
 
 from . import io, yuv
 from ._lib import EppmError
-from .api import (EPPM, BackgroundPlate, CorrespondenceMap, CutDetector, DefectFilter, Deflicker, EPPMBatch, ObjectDetector, Stabilizer, TemporalFilter,
+from .api import (EPPM, BackgroundPlate, CorrespondenceMap, CutDetector, DefectFilter, Deflicker, Deinterlacer, EPPMBatch, ObjectDetector, Stabilizer, TemporalFilter,
                   Tracker, _level)
 
 
@@ -97,10 +97,11 @@ class _Run:
     CutDetector(context, **cut_params) is stepped after every compute, its verdicts are run.found (None without auto_cut), and every
     detected slot's next compute is a cold run (temporal_reset), so the pair across the cut leaves no prior.  compute(run): the step's
     compute call; run.res is its result per slot.  hand_over: the stage outlives the run: after a run without an exception it stays open
-    and is the caller's to close; after an exception it is closed here, before the detector."""
+    and is the caller's to close; after an exception it is closed here, before the detector.  step_args: None, or step_args(step), the
+    keyword arguments stage.step gets besides the cut flags, from the step's list of (clip, frame, new_clip, keep)."""
 
     def __init__(self, who, clips, slots, params, temporal, stop_level, stage=None, auto_cut=False, cut_params=None, compute=_bidirectional_device,
-                 hand_over=False):
+                 hand_over=False, step_args=None):
         clips, is_yuv = _clip_lists(who, clips)
         self.yuv = clips if is_yuv else None       # clips of YuvFrames go through the context's _yuv methods; run.clips: their RGB form
         if is_yuv:
@@ -117,6 +118,7 @@ class _Run:
         self.steps = list(_sequence_plan([len(c) for c in self.clips], 1 if self.single else slots))
         self.level = None if stop_level is None else _level(stop_level)
         self.params, self.temporal, self.make_stage, self.compute, self.hand_over = params, temporal, stage, compute, hand_over
+        self.step_args = step_args
         self.cut_params = dict(cut_params or {}) if auto_cut else None
         self.e = self.stage = self.det = self.res = self.found = None
         self.last = False
@@ -166,7 +168,9 @@ class _Run:
                     if cut:
                         e.temporal_reset() if self.single else e.temporal_reset(slot)
                 flags = self.found if flags is None else [a or b for a, b in zip(flags, self.found)]
-            if self.make_stage is not None:
+            if self.make_stage is not None and self.step_args is not None:
+                self.stage.step(flags, **self.step_args(step))
+            elif self.make_stage is not None:
                 self.stage.step(flags)
             for slot, (c, f, new_clip, keep) in enumerate(step):
                 yield slot, c, f, new_clip, keep
@@ -186,6 +190,7 @@ class _Run:
 _CUT_KEYS = ("lost_permille", "residual_max")
 _DEFECT_KEYS = ("detect", "agree", "radius", "grow")
 _DEFLICKER_KEYS = ("cell", "iters", "reject", "tau", "keep", "n_min")
+_DEINT_KEYS = ("thresh", "use_occ")
 _CMAP_KEYS = ("thresh", "tear", "use_occ")
 _OBJECTS_KEYS = ("tau", "iters", "connectivity", "min_area", "max_objects", "min_overlap")
 _PLATE_KEYS = ("tau", "iters", "margin_x", "margin_y", "grow", "accept_invalid", "thresh", "n_max", "min_count")
@@ -366,6 +371,73 @@ def deflicker_sequences(clips, slots=8, params=None, temporal=True, stop_level=0
     each what deflicker_sequence(clip) returns.  auto_cut=True: per slot; the detector's verdicts are ORed into the schedule's cut flags."""
     out, fl = _deflicker("deflicker_sequences", clips, slots, params, temporal, stop_level, auto_cut, fields, kw)
     return (out, fl) if fields else out
+
+
+def _field_frames(who, clip, first):
+    """the 2n field frames of a clip of n interlaced frames, bobbed on the host: field frame k has parity first ^ (k & 1)"""
+    out = []
+    for frame in clip:
+        if isinstance(frame, yuv.YuvFrame):
+            fields = [yuv.to_rgb(f) for f in yuv.split_fields(frame)]
+            h = frame.h
+        else:
+            frame = np.ascontiguousarray(frame, np.uint8)
+            if frame.ndim != 3 or frame.shape[2] != 3 or frame.shape[0] < 2:
+                raise EppmError(f"{who}: frames of (h, w, 3) uint8 with h >= 2")
+            fields, h = [frame[0::2], frame[1::2]], frame.shape[0]
+        out += [io.deint_bob_host(fields[p], h, p) for p in (first, first ^ 1)]
+    return out
+
+
+def _deinterlace(who, clips, slots, tff, double_rate, masks, params, temporal, stop_level, auto_cut, kw):
+    """deinterlace_sequence(s): (frames, masks), one list per clip each"""
+    di, cut_params = _split(kw, _DEINT_KEYS, who, auto_cut)
+    stop_level = _level(stop_level)             # refused before any field is bobbed
+    first = 0 if tff else 1
+    clips = [list(clip) for clip in clips]
+    if not clips or any(len(clip) < 1 for clip in clips):
+        raise EppmError(f"{who}: at least one frame per clip")
+    clips = [_field_frames(who, clip, first) for clip in clips]
+
+    def parities(step):
+        return dict(parity=[first ^ (f & 1) for _, f, _, _ in step])
+    with _Run(who, clips, slots, params, temporal, stop_level, lambda e: Deinterlacer(e, **di), auto_cut, cut_params,
+              step_args=parities) as run:
+        bob_mask = np.where((np.arange(run.h) & 1) == first, 0, 2).astype(np.uint8)[:, None].repeat(run.w, 1)
+        out, ms = [[c[0].copy()] for c in run.clips], [[bob_mask.copy()] for _ in run.clips]
+        for slot, c, _, _, keep in run:
+            if keep:
+                out[c].append(run.stage.frame(slot))
+                if masks:
+                    ms[c].append(run.stage.mask(slot))
+    if not double_rate:
+        out, ms = [o[0::2] for o in out], [m[0::2] for m in ms]
+    return out, ms
+
+
+def deinterlace_sequence(frames, tff=True, double_rate=True, masks=False, params=None, temporal=True, stop_level=0, auto_cut=False, **kw):
+    """A clip of n interlaced frames ((h, w, 3) uint8 arrays, or YuvFrames of h % 4 == 0) as 2n progressive frames at field rate
+    (Deinterlacer).  tff: the top field (the even rows) is the first in time; False: the bottom field.  Every frame
+    is split into its two fields -- arrays by row slicing, YuvFrames by yuv.split_fields and yuv.to_rgb -- and every field is bobbed to
+    full height ON THE HOST (io.deint_bob_host; the device kernel eppm_deint_bob is for callers that hold their frames on the device).
+    The 2n field frames go through one streaming context -- set_data, then push_frame --, one bidirectional call on the device and one
+    deinterlacer step per pair; field frame f has parity first ^ (f & 1).  Returns 2n frames, the first being field frame 0 itself (the
+    bob); double_rate=False: n frames, one per first field.  masks=True: (frames, masks), one (h, w) uint8 mask per frame (0 real row, 1
+    temporal, 2 spatial).  kw: Deinterlacer's thresh / use_occ, and with auto_cut=True CutDetector's lost_permille / residual_max: a
+    detector looks at every pair first, and a field that starts another shot takes nothing from the reference.  params: the flow's eppm
+    Params; temporal / stop_level: the flow's temporal and draft modes.  Memory on the device does not grow with the clip."""
+    out, ms = _deinterlace("deinterlace_sequence", [frames], None, tff, double_rate, masks, params, temporal, stop_level, auto_cut, kw)
+    return (out[0], ms[0]) if masks else out[0]
+
+
+def deinterlace_sequences(clips, slots=8, tff=True, double_rate=True, masks=False, params=None, temporal=True, stop_level=0, auto_cut=False, **kw):
+    """deinterlace_sequence for many clips at once: clips of one frame size and of any lengths through ONE batch context of
+    min(slots, len(clips)) slots and one Deinterlacer, on flow_sequences' schedule over the clips' field frames.  A slot that takes the
+    next clip of the queue passes `cut` for that step: its output is that clip's field frame 0, bobbed.  Returns one list of frames per
+    clip (masks=True: (frames, masks)), each what deinterlace_sequence(clip) returns.  auto_cut=True: per slot; the detector's verdicts are
+    ORed into the schedule's cut flags."""
+    out, ms = _deinterlace("deinterlace_sequences", clips, slots, tff, double_rate, masks, params, temporal, stop_level, auto_cut, kw)
+    return (out, ms) if masks else out
 
 
 def _propagate(who, clips, layers, slots, auto_cut, stop_level, maps, params):

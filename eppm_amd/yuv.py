@@ -163,13 +163,14 @@ def device_args(frames, what):
 _C_TAGS = {"420jpeg": (8, CENTER), "420mpeg2": (8, LEFT), "420": (8, LEFT), "420p10": (10, LEFT), "420p12": (12, LEFT), "420p16": (16, LEFT)}
 
 
-def _y4m_header(line, path):
+def _y4m_header(line, path, interlaced=False):
     if not re.fullmatch(rb"YUV4MPEG2( .*)?", line):
         raise EppmError(f"read_y4m: {path}: malformed: no YUV4MPEG2 header line")
     h = w = 0
     fps = (0, 0)
     fmt = YuvFormat(layout=I420)
     center = False
+    mode = 0
     for tok in line.decode("ascii", "replace").split(" ")[1:]:
         if not tok:
             continue
@@ -180,11 +181,13 @@ def _y4m_header(line, path):
         elif k == "F":
             m = re.fullmatch(r"(\d+):(\d+)", v)
             fps = (min(int(m.group(1)), 2 ** 31 - 1), min(int(m.group(2)), 2 ** 31 - 1)) if m else (0, 0)       # as the library: an int each
-        elif k == "I" and v[:1] in ("t", "b", "m"):
-            raise EppmError(f"read_y4m: {path}: interlaced material ({tok}) is not supported")
+        elif k == "I":
+            if v[:1] == "m" or (not interlaced and v[:1] in ("t", "b")):
+                raise EppmError(f"read_y4m: {path}: interlaced material ({tok}) is not supported")
+            mode = {"t": 1, "b": 2}.get(v[:1], 0)
         elif k == "C":
             if v not in _C_TAGS:
-                raise EppmError(f"read_y4m: {path}: colour space {tok} is not supported (4:2:0 progressive only)")
+                raise EppmError(f"read_y4m: {path}: colour space {tok} is not supported (4:2:0 {'only' if interlaced else 'progressive only'})")
             fmt.depth, fmt.siting = _C_TAGS[v]
         elif tok == "XCOLORRANGE=FULL":
             fmt.full_range = 1
@@ -196,19 +199,30 @@ def _y4m_header(line, path):
         raise EppmError(f"read_y4m: {path}: malformed: missing W or H")
     if h > 65535 or w > 65535:
         raise EppmError(f"read_y4m: {path}: malformed: W or H beyond 65535")
+    if mode and h % 4:
+        raise EppmError(f"read_y4m: {path}: an interlaced 4:2:0 file needs H a multiple of 4 (H{h}): each field is a 4:2:0 picture")
     if center:
         fmt.siting = CENTER
     fmt.matrix = BT601 if h < 720 else BT709
-    return h, w, fmt, fps
+    return h, w, fmt, fps, mode
 
 
 class read_y4m:
     """Iterates over the frames of a y4m file as YuvFrames (I420); .h, .w, .fmt, .fps = (num, den).  matrix: BT601 / BT709 / BT2020 instead
-    of the default by size (601 below 720 rows); native: through the library's reader (eppm_y4m_*) instead of this module's."""
+    of the default by size (601 below 720 rows); native: through the library's reader (eppm_y4m_*) instead of this module's.
+    interlaced=True: It / Ib files are accepted too (eppm_deint_y4m_open_read) and .interlace says what the file
+    is: 0 progressive, 1 top field first, 2 bottom field first; the frames are whole, both fields woven (split_fields)."""
 
-    def __init__(self, path, matrix=None, native=False):
+    def __init__(self, path, matrix=None, native=False, interlaced=False):
         self.path, self._y, self._f = str(path), None, None
-        if native:
+        self.interlace = 0
+        if native and interlaced:
+            y, h, w, num, den, mode = C.c_void_p(), C.c_int(), C.c_int(), C.c_int(), C.c_int(), C.c_int()
+            self.fmt = CYuvFormat()
+            check(lib().eppm_deint_y4m_open_read(C.byref(y), self.path.encode(), C.byref(h), C.byref(w), C.byref(self.fmt), C.byref(num),
+                                                 C.byref(den), C.byref(mode)), "eppm_deint_y4m_open_read")
+            self._y, self.h, self.w, self.fps, self.interlace = y, h.value, w.value, (num.value, den.value), mode.value
+        elif native:
             y, h, w, num, den = C.c_void_p(), C.c_int(), C.c_int(), C.c_int(), C.c_int()
             self.fmt = CYuvFormat()
             check(lib().eppm_y4m_open_read(C.byref(y), self.path.encode(), C.byref(h), C.byref(w), C.byref(self.fmt), C.byref(num), C.byref(den)),
@@ -221,7 +235,7 @@ class read_y4m:
                 self.close()
                 raise EppmError(f"read_y4m: {self.path}: malformed: no YUV4MPEG2 header line")
             try:
-                self.h, self.w, self.fmt, self.fps = _y4m_header(line[:-1], self.path)
+                self.h, self.w, self.fmt, self.fps, self.interlace = _y4m_header(line[:-1], self.path, interlaced)
             except EppmError:
                 self.close()
                 raise
@@ -271,6 +285,15 @@ class read_y4m:
             self.close()
         except Exception:
             pass
+
+
+def split_fields(frame):
+    """The two fields (top, bottom) of an interlaced 4:2:0 frame as YuvFrames of the frame's format: field p is the luma rows p::2 and the
+    chroma rows p::2.  The frame needs h % 4 == 0, so that each field is itself a 4:2:0 picture.  A field's chroma sits a quarter line
+    off the siting the format names; that is not corrected."""
+    if frame.h % 4:
+        raise EppmError(f"split_fields: an interlaced 4:2:0 frame needs h a multiple of 4, not {frame.h}")
+    return tuple(YuvFrame([np.ascontiguousarray(p[par::2]) for p in frame.planes], frame.fmt) for par in (0, 1))
 
 
 def _y4m_tags(fmt):

@@ -87,6 +87,15 @@
 //                     was confirmed (0: never seen).  --remove-objects (implies --plate): a second pass renders every frame against
 //                     the finished plate: P_ro_0000.ppm ... are the frames with their moving objects painted out; the frames, masks and
 //                     paths of the first pass are kept in host memory.  The last frame has no pair of its own and is written unchanged.
+//                     --deinterlace: the clip is interlaced.  Every frame is split into its two fields, every
+//                     field is bobbed to full height on the host, and the 2n field frames go through the context: every pair runs the
+//                     bidirectional call followed by one deinterlacer step.  P_di_0000.ppm (field frame 0 itself), P_di_0001.ppm ... are
+//                     the 2n progressive frames at field rate; --single-rate keeps one frame per first field (n frames).  With
+//                     --y4m-out they go to P_di.y4m at twice the input's frame rate (--single-rate: at the input's).  The field order
+//                     of a y4m clip is its header's (It / Ib; an interlaced y4m clip is accepted only with --deinterlace); a PPM
+//                     sequence, or a y4m clip that calls itself progressive, is top field first unless --bff says bottom field first.
+//                     --deint-thresh N (0 .. 765, default 24) sets the gate and implies --deinterlace.  It is a mode of its own: the
+//                     other filters and --auto-cut do not combine with it, and no .flo files are written.
 #include <algorithm>
 #include <atomic>
 #include <chrono>
@@ -100,6 +109,7 @@
 #include "bao_flow_patchmatch_multiscale_cuda.h"
 #include "eppm.h"
 #include "eppm_yuv.h"
+#include "eppm_deint.h"
 
 template <typename T>
 struct Array3 {       // bao_alloc<T>(n,r,c): one contiguous block reachable through row-pointer tables (bao_basic.h:146-162)
@@ -147,6 +157,8 @@ struct Options {
     int ob_min_area = 0, ob_max = 0;                        // --min-area, --max-objects (0: the default)
     bool y4m_out = false;                                   // --y4m-out
     int yuv_matrix = -1;                                    // --yuv-matrix (-1: the default by size)
+    bool deint = false, bff = false, single_rate = false;   // --deinterlace, --bff, --single-rate
+    int di_thresh = 24;                                     // --deint-thresh
 };
 
 static unsigned hash32(unsigned x)
@@ -205,6 +217,7 @@ static int usage()
                     "               [--plate] [--plate-margin MX MY] [--remove-objects]\n"
                     "               [--remove-defects] [--defect-thresh D A] [--defect-radius R] [--defect-grow G]\n"
                     "               [--deflicker] [--flicker-cell N] [--flicker-keep K]\n"
+                    "               [--deinterlace] [--bff] [--deint-thresh N] [--single-rate]\n"
                     "               --sequence clip.y4m --out-prefix P [--y4m-out] [--yuv-matrix 601|709|2020] [the options above]\n");
     return 2;
 }
@@ -645,6 +658,106 @@ static int run_sequence(const Options& o)
     return 0;
 }
 
+// --sequence ... --deinterlace: an interlaced clip as progressive frames at field rate.  The calls are those of
+// eppm_amd.deinterlace_sequence: split, bob on the host, set_images / push_image, the bidirectional call, one deinterlacer step per pair
+static int run_deinterlace(const Options& o)
+{
+    eppm_params prm;
+    eppm_default_params(&prm);
+    for (auto& kv : o.opts) {
+        if (kv.first == "seed") prm.seed = (unsigned long long)kv.second;
+        else if (kv.first == "levels") prm.levels = (int)kv.second;
+        else if (kv.first == "patch_r") prm.patch_r = (int)kv.second;
+        else if (kv.first == "num_iter") prm.num_iter = (int)kv.second;
+        else if (kv.first == "propagation") prm.propagation = (int)kv.second;
+    }
+    struct Guard {          // freed on every way out
+        eppm_y4m* yin = nullptr;
+        eppm_ctx* ctx = nullptr;
+        eppm_deint* di = nullptr;
+        ~Guard() { eppm_deint_destroy(di); if (ctx) eppm_destroy(ctx); eppm_y4m_close(yin); }
+    } g;
+    auto fail = [&](const char* what) { fprintf(stderr, "%s: %s\n", what, eppm_last_error()); return 1; };
+    int h = 0, w = 0, nch = 3, interlace = 0;
+    const bool y4m_in = o.seq.size() == 1 && ends_with(o.seq[0], ".y4m");
+    FrameOut out;
+    eppm_yuv_default_format(&out.fmt);
+    out.fmt.layout = EPPM_YUV_I420;
+    YuvBuf yuv;
+    if (y4m_in) {
+        if (eppm_deint_y4m_open_read(&g.yin, o.seq[0], &h, &w, &out.fmt, &out.fps_num, &out.fps_den, &interlace) != EPPM_OK) { fprintf(stderr, "%s\n", eppm_last_error()); return 1; }
+        if (h % 4 != 0) { fprintf(stderr, "%s: --deinterlace needs a 4:2:0 clip whose height is a multiple of 4 (each field is a 4:2:0 picture), not %d\n", o.seq[0], h); return 1; }
+        if (!yuv.init(out.fmt, h, w)) return fail("eppm_yuv_plane_dims");
+        if (out.fps_num < 1 || out.fps_den < 1) { out.fps_num = 25; out.fps_den = 1; }
+    } else {
+        if (eppm_ppm_size(o.seq[0], &h, &w) != EPPM_OK) { fprintf(stderr, "cannot read %s\n", o.seq[0]); return 1; }
+        out.fmt.matrix = EPPM_YUV_BT709;
+    }
+    if (h < 2) { fprintf(stderr, "--deinterlace needs frames of at least two rows\n"); return 1; }
+    if (o.yuv_matrix >= 0) out.fmt.matrix = o.yuv_matrix;
+    const eppm_yuv_format yfmt = out.fmt;
+    const int first = interlace == 1 ? 0 : interlace == 2 ? 1 : (o.bff ? 1 : 0);        // the parity of the field that is first in time
+    if (!o.single_rate) {
+        if (out.fps_num > 0x3fffffff) { fprintf(stderr, "%s: the frame rate cannot be doubled\n", o.seq[0]); return 1; }
+        out.fps_num *= 2;
+    }
+    out.prefix = o.prefix; out.y4m = o.y4m_out; out.h = h; out.w = w;
+    const size_t row = (size_t)w * 3;
+    std::vector<unsigned char> img((size_t)h * row), field((size_t)((h + 1) / 2) * row), prev((size_t)h * row), cur((size_t)h * row), rgb((size_t)h * row);
+    if (eppm_create(&g.ctx, h, w, 0, &prm) != EPPM_OK) return fail("eppm_create");
+    const eppm_deint_params dp = {o.di_thresh, 1};
+    if (eppm_deint_create(g.ctx, &dp, &g.di) != EPPM_OK) return fail("eppm_deint_create");
+    if (eppm_set_temporal(g.ctx, o.temporal) != EPPM_OK) return fail("eppm_set_temporal");
+    if (eppm_set_stop_level(g.ctx, o.stop_level) != EPPM_OK) { fprintf(stderr, "--stop-level: %s\n", eppm_last_error()); return usage(); }
+    char name[4096];
+    size_t k = 0, written = 0;          // field frames so far, frames written
+    double total = 0;
+    for (size_t n = 0;; n++) {
+        if (y4m_in) {
+            int got = 0;
+            if (eppm_y4m_read_frame(g.yin, yuv.planes, yuv.strides, &got) != EPPM_OK) return fail(o.seq[0]);
+            if (!got) break;
+        } else {
+            if (n == o.seq.size()) break;
+            int hk = 0, wk = 0;
+            if (eppm_ppm_size(o.seq[n], &hk, &wk) != EPPM_OK || hk != h || wk != w || eppm_load_ppm(o.seq[n], img.data(), h, w, &nch) != EPPM_OK) {
+                fprintf(stderr, "cannot read %s (or its size differs from the first frame's)\n", o.seq[n]);
+                return 1;
+            }
+        }
+        for (int j = 0; j < 2; j++, k++) {
+            const int p = first ^ j, fh = (h - p + 1) / 2;
+            if (y4m_in) {           // field p of every plane: its rows p, p + 2, ... (h % 4 == 0: h / 2 luma rows, h / 4 chroma rows)
+                const void* planes[3];
+                size_t strides[3];
+                for (int q = 0; q < 3; q++) { planes[q] = (const unsigned char*)yuv.planes[q] + (size_t)p * yuv.strides[q]; strides[q] = 2 * yuv.strides[q]; }
+                if (eppm_yuv_to_rgb_host(&yfmt, planes, strides, field.data(), row, fh, w) != EPPM_OK) return fail("eppm_yuv_to_rgb_host");
+            } else
+                for (int i = 0; i < fh; i++) memcpy(&field[(size_t)i * row], &img[(size_t)(2 * i + p) * row], row);
+            prev.swap(cur);
+            if (eppm_deint_bob_host(cur.data(), field.data(), h, w, p) != EPPM_OK) return fail("eppm_deint_bob_host");
+            const unsigned char* frame = cur.data();
+            if (k > 0) {
+                const auto t0 = std::chrono::steady_clock::now();
+                if (k == 1) { if (eppm_set_images(g.ctx, prev.data(), cur.data(), row) != EPPM_OK) return fail("eppm_set_images"); }
+                else if (eppm_push_image(g.ctx, cur.data(), row) != EPPM_OK) return fail("eppm_push_image");
+                if (eppm_compute_bidirectional_device(g.ctx, nullptr, nullptr, nullptr, nullptr) != EPPM_OK) return fail("eppm_compute_bidirectional_device");
+                const uint8_t parity = (uint8_t)p;
+                if (eppm_deint_step(g.di, g.ctx, nullptr, &parity) != EPPM_OK) return fail("eppm_deint_step");
+                if (eppm_deint_get(g.di, 0, rgb.data(), row) != EPPM_OK) return fail("eppm_deint_get");
+                total += std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
+                frame = rgb.data();
+            }
+            if (o.single_rate && j == 1) continue;
+            if (!out.put("di", written++, frame, name, sizeof name)) { fprintf(stderr, "cannot write %s: %s\n", name, eppm_last_error()); return 1; }
+        }
+    }
+    if (k == 0) { fprintf(stderr, "%s: a clip needs at least one frame\n", o.seq[0]); return 1; }
+    if (!out.close()) { fprintf(stderr, "cannot finish the y4m files of %s: %s\n", o.prefix, eppm_last_error()); return 1; }
+    printf("%zu field frames (%s field first), %.3f ms per pair, %zu frames -> %s\n", k, first ? "bottom" : "top", total / (double)(k - 1), written, out.first("di").c_str());
+    return 0;
+}
+
 int main(int argc, char** argv)
 {
     Options o;
@@ -751,6 +864,10 @@ int main(int argc, char** argv)
         }
         else if (!strcmp(a, "--min-area")) { if (!val(&v) || v < 1 || v > 0x7fffffff) return usage(); o.ob_min_area = (int)v; o.objects = true; }
         else if (!strcmp(a, "--max-objects")) { if (!val(&v) || v < 1 || v > 255) return usage(); o.ob_max = (int)v; o.objects = true; }
+        else if (!strcmp(a, "--deinterlace")) o.deint = true;
+        else if (!strcmp(a, "--bff")) o.bff = true;
+        else if (!strcmp(a, "--single-rate")) o.single_rate = true;
+        else if (!strcmp(a, "--deint-thresh")) { if (!val(&v) || v < 0 || v > 765) return usage(); o.di_thresh = (int)v; o.deint = true; }
         else if (!strcmp(a, "--y4m-out")) o.y4m_out = true;
         else if (!strcmp(a, "--yuv-matrix")) {
             if (!val(&v) || (v != 601 && v != 709 && v != 2020)) return usage();
@@ -762,7 +879,8 @@ int main(int argc, char** argv)
     }
     if (!o.seq.empty() || o.prefix) {
         const bool y4m_clip = o.seq.size() == 1 && ends_with(o.seq[0], ".y4m");
-        if ((o.seq.size() < 2 && !y4m_clip) || !o.prefix || !pos.empty()) return usage();
+        if ((o.seq.size() < 2 && !y4m_clip && !(o.deint && o.seq.size() == 1)) || !o.prefix || !pos.empty()) return usage();
+        if ((o.bff || o.single_rate) && !o.deint) return usage();
         if (o.mblur_file || (o.mb_set && !o.mblur)) return usage();       // a clip's blurred frames are named by the prefix
         // the options of the two-image form that a clip has no meaning for are refused, not ignored
         const Options d;
@@ -770,8 +888,13 @@ int main(int argc, char** argv)
         for (auto& kv : o.opts) pin = pin || kv.first == "pin_caller_buffers";
         if (pin || o.sw || o.pairs != d.pairs || o.gpus != d.gpus || o.batch != d.batch || o.gt || o.fo != d.fo || o.fb || o.focc || !o.interp.empty())
             return usage();
+        if (o.deint) {          // a mode of its own: one interlaced frame is a clip of two field frames
+            if (o.denoise || o.stabilize || o.auto_cut || o.pl_layer || o.objects || o.plate || o.defects || o.deflicker || o.mblur) return usage();
+            return run_deinterlace(o);
+        }
         return run_sequence(o);
     }
+    if (o.deint || o.bff || o.single_rate) return usage();
     if (o.denoise || o.stabilize || o.auto_cut || o.pl_layer || o.objects || o.plate || o.defects || o.deflicker || o.y4m_out || o.yuv_matrix >= 0) return usage();     // the filter, the stabiliser, the cut detector, the map and the object detector walk a clip
     if ((o.mblur && !o.mblur_file) || (o.mb_set && !o.mblur)) return usage();
     if (pos.size() == 1 || pos.size() > 3) return usage();
