@@ -99,6 +99,10 @@ class CDeintStats(_Record):
     _fields_ = [("temporal", C.c_int64), ("spatial", C.c_int64)]
 
 
+class CRSParams(C.Structure):
+    _fields_ = [("readout", C.c_float), ("anchor", C.c_float), ("iters", C.c_int), ("axis", C.c_int)]
+
+
 class CYuvFormat(_Record):
     _fields_ = [("layout", C.c_int), ("depth", C.c_int), ("msb_aligned", C.c_int), ("matrix", C.c_int), ("full_range", C.c_int), ("siting", C.c_int)]
 
@@ -208,6 +212,12 @@ eppm_deint_step_frames:PIPPZPPII eppm_deint_get:PIPZ eppm_deint_get_device:PIPZ 
 eppm_deint_get_state:PIPP eppm_deint_set_state:PIPI eppm_deint_step_host:PPPPPPPPPIIII eppm_deint_bob:PZPZIII eppm_deint_bob_stream:PZPZIIIP
 eppm_deint_bob_host:PPIII eppm_deint_y4m_open_read:PSPPPPPP""")
 
+# what include/eppm_rshutter.h declares, in its order (tests/test_rshutter_cpu.py checks it the same way): exported by all four libraries,
+# applied by lib() next to _YUV_ABI and _DEINT_ABI, and kept out of SIGNATURES / SYMBOLS
+_RS_ABI = _signatures("""
+eppm_rs_default_params:P eppm_rolling_shutter:PPIPZ eppm_rolling_shutter_device:PPIPZ eppm_batch_rolling_shutter:PPIPZ
+eppm_rolling_shutter_frames:PZPZPIIIP eppm_rolling_shutter_host:PPPPIIIP""")
+
 SIGNATURES = {**_ABI, **_TEST_ABI}
 SYMBOLS, TEST_SYMBOLS = list(_ABI), list(_TEST_ABI)
 
@@ -234,7 +244,7 @@ def lib():
         if not os.path.exists(path):
             raise EppmError(f"{path} is missing: run eppm_amd.build() (hipcc --offload-arch=gfx950); there is no CPU fallback")
         L = C.CDLL(path)
-        for name, (res, args) in {**SIGNATURES, **_YUV_ABI, **_DEINT_ABI}.items():
+        for name, (res, args) in {**SIGNATURES, **_YUV_ABI, **_DEINT_ABI, **_RS_ABI}.items():
             fn = getattr(L, name, None)
             if fn is None:      # a test hook in a product library, or a library built before the function existed (A/B runs): fails at the call
                 continue

@@ -4,7 +4,7 @@ import ctypes as C
 import numpy as np
 
 from .io import object_record
-from ._lib import CDefectParams, CDefectStats, CDeintParams, CDeintStats, CDeflickerParams, CDeflickerStats, CObject, CObjectsCounts, CObjectsParams, CPlateParams, CCMapParams, CCutParams, CCutStats, CGMotionModel, CMBlurParams, CParams, CStabParams, CTFilterParams, CTrackCounts, CTrackParams, EppmError, check, lib
+from ._lib import CDefectParams, CDefectStats, CDeintParams, CDeintStats, CDeflickerParams, CDeflickerStats, CObject, CObjectsCounts, CObjectsParams, CPlateParams, CRSParams, CCMapParams, CCutParams, CCutStats, CGMotionModel, CMBlurParams, CParams, CStabParams, CTFilterParams, CTrackCounts, CTrackParams, EppmError, check, lib
 
 uchar4 = np.dtype([("x", "u1"), ("y", "u1"), ("z", "u1"), ("w", "u1")])
 short2 = np.dtype([("x", "i2"), ("y", "i2")])
@@ -75,6 +75,11 @@ def _times(times):
 def MBlurParams(**kw):
     """eppm_mblur_params with the defaults of DESIGN.md section 18 (shutter 0.5, max_radius 16, taps 8)."""
     return _params(CMBlurParams, "eppm_mblur_default_params", "motion-blur parameter", **kw)
+
+
+def RSParams(**kw):
+    """eppm_rs_params with the defaults of DESIGN.md section 27 (readout 0.5, anchor 0.5, iters 3, axis 0)."""
+    return _params(CRSParams, "eppm_rs_default_params", "rolling-shutter parameter", **kw)
 
 
 def TrackParams(params=None, **kw):
@@ -993,6 +998,24 @@ class EPPM(_Context):
         p = MBlurParams(shutter=shutter, max_radius=max_radius, taps=taps)
         check(lib().eppm_motion_blur_device(self._ctx, C.byref(p), int(frame), d_rgba, pitch), "eppm_motion_blur_device")
 
+    def rolling_shutter(self, readout=0.5, anchor=0.5, iters=3, axis=0, frame=0):
+        """The frame as a global shutter would have recorded it (eppm_rolling_shutter): an (h, w, 3) uint8 R,G,B
+        array.  frame=0: image 1 along the forward flow, after any compute of the current images; frame=1: image 2 along the backward
+        flow, after compute_flow_bidirectional.  readout: the share of the frame interval the sensor takes to read a frame (negative: last
+        line first); anchor: the position along the axis whose sampling time is the frame's; iters: fixed-point steps; axis: 0 rows are
+        read one after another, 1 columns."""
+        self._need()
+        p = RSParams(readout=readout, anchor=anchor, iters=iters, axis=axis)
+        out = np.empty((self.h, self.w, 3), np.uint8)
+        check(lib().eppm_rolling_shutter(self._ctx, C.byref(p), int(frame), out.ctypes.data, self.w * 3), "eppm_rolling_shutter")
+        return out
+
+    def rolling_shutter_device(self, d_rgba, pitch, readout=0.5, anchor=0.5, iters=3, axis=0, frame=0):
+        """eppm_rolling_shutter_device: asynchronous on the context's stream; d_rgba: a device RGBA plane of pitch bytes per row."""
+        self._need()
+        p = RSParams(readout=readout, anchor=anchor, iters=iters, axis=axis)
+        check(lib().eppm_rolling_shutter_device(self._ctx, C.byref(p), int(frame), d_rgba, pitch), "eppm_rolling_shutter_device")
+
     def compute_flow_color(self, max_disp=(20.0, 20.0)):
         """The optional color_flow output of compute_flow (driver .cpp:308-314): (h, w, 3) uint8 R,G,B of the last flow."""
         self._need()
@@ -1188,6 +1211,13 @@ class EPPMBatch(_Context):
         p = MBlurParams(shutter=shutter, max_radius=max_radius, taps=taps)
         out = [np.empty((self.h, self.w, 3), np.uint8) for _ in range(self.n)]
         check(lib().eppm_batch_motion_blur(self._ctx, C.byref(p), int(frame), self._ptrs(out), self.w * 3), "eppm_batch_motion_blur")
+        return out
+
+    def rolling_shutter(self, readout=0.5, anchor=0.5, iters=3, axis=0, frame=0):
+        """[corrected frame for each active pair] (eppm_batch_rolling_shutter); see EPPM.rolling_shutter."""
+        p = RSParams(readout=readout, anchor=anchor, iters=iters, axis=axis)
+        out = [np.empty((self.h, self.w, 3), np.uint8) for _ in range(self.n)]
+        check(lib().eppm_batch_rolling_shutter(self._ctx, C.byref(p), int(frame), self._ptrs(out), self.w * 3), "eppm_batch_rolling_shutter")
         return out
 
     def compute_flow_device(self, d_flows=None):

@@ -25,7 +25,7 @@ def _stale():
         return True
     t = min(os.path.getmtime(o) for o in outs)
     srcs = [os.path.join(_CSRC, f) for f in os.listdir(_CSRC)]
-    srcs += [os.path.join(_HERE, "..", "include", f) for f in ("eppm.h", "eppm_yuv.h", "eppm_deint.h", "eppm_test.h", "bao_flow_patchmatch_multiscale_cuda.h", "bao_basic_cuda.h")]
+    srcs += [os.path.join(_HERE, "..", "include", f) for f in ("eppm.h", "eppm_yuv.h", "eppm_deint.h", "eppm_rshutter.h", "eppm_test.h", "bao_flow_patchmatch_multiscale_cuda.h", "bao_basic_cuda.h")]
     srcs.append(os.path.join(_HERE, "..", "tools", "runeppm.cpp"))
     return any(os.path.getmtime(s) > t for s in srcs if os.path.isfile(s))
 

@@ -29,6 +29,8 @@ extern "C" int eppm_destroy(eppm_ctx* c)
     cache_free(c->h_itp, c->h_itp_bytes, true, c->device);
     cache_free(c->mbl, c->mbl_bytes, false, c->device);
     cache_free(c->h_mbl, c->h_mbl_bytes, true, c->device);
+    cache_free(c->rsh, c->rsh_bytes, false, c->device);
+    cache_free(c->h_rsh, c->h_rsh_bytes, true, c->device);
     cache_free(c->tmp, c->tmp_bytes, false, c->device);
     rng_free(c->rng);
     if (c->own_stream && c->stream) pooled_stream_destroy(c->stream, c->device);

@@ -100,6 +100,14 @@ struct eppm_ctx {
     uint64_t* mbl_tkeys = nullptr;
     uint8_t* mbl_rgb = nullptr;
     uint8_t* h_mbl = nullptr;
+    // Rolling-shutter correction (eppm_rolling_shutter*): its own allocation, made by the first such call, for npairs
+    // pairs: the velocity planes (rsh_plane float2 per pair) and the packed RGB outputs of the host-pointer forms (h*w*3 bytes per pair);
+    // h_rsh: pinned copy of those outputs, allocated on the first host-pointer call.
+    char* rsh = nullptr;
+    size_t rsh_bytes = 0, rsh_plane = 0, h_rsh_bytes = 0;
+    float* rsh_vel = nullptr;
+    uint8_t* rsh_rgb = nullptr;
+    uint8_t* h_rsh = nullptr;
     // Streaming mode (eppm_set_temporal / eppm_batch_set_temporal): its own allocation, made by the first compute
     // with the mode on: npairs blocks tmp_stride bytes apart, one per slot (the members below are slot 0's).  Level-L planes, unpitched: the
     // two displacement snapshots of the last compute (prev_fwd: the field nnf2flow converted, prev_bwd: the raw backward NNF), the two

@@ -1,9 +1,11 @@
-// ctx_interp.cpp -- what reads the results of a context's (context.h) last call: frame interpolation, the synthetic shutter, and the one
-// view of a context that the nine per-clip stage objects share (stage_object.h).
+// ctx_interp.cpp -- what reads the results of a context's (context.h) last call: frame interpolation, the synthetic shutter, rolling-shutter
+// correction, and the one view of a context that the nine per-clip stage objects share (stage_object.h).
 #include "context.h"
 #include "stage_object.h"
 #include "interp.h"
 #include "mblur.h"
+#include "rshutter.h"
+#include "../../include/eppm_rshutter.h"
 
 using namespace eppm;
 
@@ -211,6 +213,102 @@ extern "C" int eppm_motion_blur_device(eppm_ctx* c, const eppm_mblur_params* p, 
     HIPCHK(hipSetDevice(c->device));
     CHK(mbl_alloc(c));
     return mblur_run(c, prm, frame, 1, d_rgba, pitch);
+}
+
+// ---- rolling-shutter correction (include/eppm_rshutter.h): the synthetic shutter's inputs and windows.  One block of
+// the context's own, made by the first call: per pair the velocity plane (8 B/px), then the packed RGB outputs (3 B/px) ----
+
+static int rs_alloc(eppm_ctx* c)
+{
+    if (c->rsh) return EPPM_OK;
+    const size_t n = (size_t)c->h * c->w;
+    const size_t plane = (n + 31) & ~(size_t)31;
+    const size_t vel = c->npairs * plane * 8, rgb = c->npairs * n * 3;
+    Carve cv;                           // (the first size is a multiple of 256 bytes)
+    cv.plane(&c->rsh_vel, vel);
+    cv.plane(&c->rsh_rgb, rgb);
+    CHK(cv.alloc(&c->rsh, &c->rsh_bytes, vel + rgb, c->device, "rolling-shutter scratch"));
+    c->rsh_plane = plane;
+    return EPPM_OK;
+}
+
+static int rs_check(eppm_ctx* c, const char* what, const eppm_rs_params* p, int frame, eppm_rs_params* prm)
+{
+    if (p) *prm = *p;
+    else (void)eppm_rs_default_params(prm);
+    if (!rs_params_ok(prm->readout, prm->anchor, prm->iters, prm->axis))
+        return set_err(EPPM_ERR_ARG, "%s: readout %g (-1 .. 1), anchor %g (0 .. 1), iters %d (1 .. 8), axis %d (0, 1)", what, prm->readout, prm->anchor, prm->iters, prm->axis);
+    if (frame != 0 && frame != 1) return set_err(EPPM_ERR_ARG, "%s: frame %d (0: image 1, 1: image 2)", what, frame);
+    if (c->flow_pending) return set_err(EPPM_ERR_STATE, "%s: an eppm_compute_begin is pending", what);
+    if (frame == 0 && !c->have_flow) return set_err(EPPM_ERR_STATE, "%s: frame 0 needs a compute on the current images", what);
+    if (frame == 1 && (!c->have_flow || !c->have_bwd || !c->bwd_images))
+        return set_err(EPPM_ERR_STATE, "%s: frame 1 needs a bidirectional call on the current images", what);
+    return EPPM_OK;
+}
+
+// the first npairs pairs: velocity, gather into the packed RGB scratch (d_rgba NULL) or into d_rgba (pair 0)
+static int rs_run(eppm_ctx* c, const eppm_rs_params& prm, int frame, int npairs, void* d_rgba, size_t pitch)
+{
+    RShutterArgs a{};
+    a.img = (const uint8_t*)(frame ? c->raw2 : c->raw1); a.img_pitch = c->raw_pitch; a.img_stride = c->stride;
+    a.flow = frame ? c->bflow[0] : c->flow[0]; a.flow_stride = frame ? c->bwd_stride : c->stride;
+    a.vel = c->rsh_vel; a.plane = c->rsh_plane;
+    a.rgb = d_rgba ? nullptr : c->rsh_rgb;
+    a.rgba = (uint8_t*)d_rgba; a.rgba_pitch = pitch;
+    a.h = c->h; a.w = c->w;
+    a.readout = prm.readout; a.anchor = prm.anchor; a.iters = prm.iters; a.axis = prm.axis; a.frame = frame;
+    stage_begin(c, c->ev, "rs_velocity");
+    launch_rs_velocity(a, npairs, c->stream);
+    stage_end(c, c->ev);
+    stage_begin(c, c->ev, "rs_gather");
+    launch_rs_gather(a, npairs, c->stream);
+    stage_end(c, c->ev);
+    HIPCHK(hipGetLastError());
+    return EPPM_OK;
+}
+
+// host-pointer forms: the packed RGB outputs cross PCIe once (3 B/px) into the pinned copy, then into the caller's rows
+static int rs_host(eppm_ctx* c, const char* what, const eppm_rs_params* p, int frame, int npairs, uint8_t* const* rgb, size_t row_stride)
+{
+    eppm_rs_params prm;
+    CHK(rs_check(c, what, p, frame, &prm));
+    if (!rgb) return set_err(EPPM_ERR_ARG, "%s: NULL rgb", what);
+    for (int k = 0; k < npairs; k++)
+        if (!rgb[k]) return set_err(EPPM_ERR_ARG, "%s: NULL rgb[%d]", what, k);
+    if (row_stride < (size_t)c->w * 3) return set_err(EPPM_ERR_ARG, "%s: row_stride %zu < 3*w", what, row_stride);
+    HIPCHK(hipSetDevice(c->device));
+    CHK(rs_alloc(c));
+    const size_t img = (size_t)c->h * c->w * 3, row = (size_t)c->w * 3;
+    HIPCHK(pinned_lazy(&c->h_rsh, &c->h_rsh_bytes, img * c->npairs, c->device));
+    CHK(rs_run(c, prm, frame, npairs, nullptr, 0));
+    HIPCHK(hipMemcpyAsync(c->h_rsh, c->rsh_rgb, img * npairs, hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(hipStreamSynchronize(c->stream));
+    for (int k = 0; k < npairs; k++) copy_rows(rgb[k], row_stride, c->h_rsh + img * k, row, row, c->h);
+    return EPPM_OK;
+}
+
+extern "C" int eppm_rolling_shutter(eppm_ctx* c, const eppm_rs_params* p, int frame, uint8_t* rgb, size_t row_stride)
+{
+    if (!c) return set_err(EPPM_ERR_ARG, "eppm_rolling_shutter: NULL ctx");
+    return rs_host(c, "eppm_rolling_shutter", p, frame, 1, &rgb, row_stride);
+}
+
+extern "C" int eppm_batch_rolling_shutter(eppm_ctx* c, const eppm_rs_params* p, int frame, uint8_t* const* rgb, size_t row_stride)
+{
+    if (!c) return set_err(EPPM_ERR_ARG, "eppm_batch_rolling_shutter: NULL ctx");
+    return rs_host(c, "eppm_batch_rolling_shutter", p, frame, c->n_active, rgb, row_stride);
+}
+
+extern "C" int eppm_rolling_shutter_device(eppm_ctx* c, const eppm_rs_params* p, int frame, void* d_rgba, size_t pitch)
+{
+    if (!c) return set_err(EPPM_ERR_ARG, "eppm_rolling_shutter_device: NULL ctx");
+    eppm_rs_params prm;
+    CHK(rs_check(c, "eppm_rolling_shutter_device", p, frame, &prm));
+    if (!d_rgba) return set_err(EPPM_ERR_ARG, "eppm_rolling_shutter_device: NULL d_rgba");
+    if (bad_pitch(pitch, c->w)) return set_err(EPPM_ERR_ARG, "eppm_rolling_shutter_device: bad pitch %zu", pitch);
+    HIPCHK(hipSetDevice(c->device));
+    CHK(rs_alloc(c));
+    return rs_run(c, prm, frame, 1, d_rgba, pitch);
 }
 
 // ---- the per-clip stage objects (stage_object.h): what the tracker, the temporal filter, the stabiliser, the cut

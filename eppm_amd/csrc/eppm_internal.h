@@ -344,6 +344,27 @@ struct MBlurArgs {
 void launch_mblur_pack(const MBlurArgs& a, int npairs, hipStream_t s);
 void launch_mblur_gather(const MBlurArgs& a, int npairs, hipStream_t s);
 
+// ---- rolling-shutter correction (k_rshutter.hip; the per-pixel arithmetic: rshutter.h) ----
+// One launch covers npairs pairs.  Inputs of pair p lie p * (their stride) bytes past pair 0's; its velocity plane p * plane float2 and its
+// packed RGB output p*h*w*3 bytes past pair 0's.  Image: RGBA words, img_pitch bytes per row; flow: h*w float2, unpitched.  Output: packed
+// RGB (rgb != NULL) or RGBA words of pair 0 into rgba (rgba_pitch bytes per row).
+struct RShutterArgs {
+    const uint8_t* img;
+    size_t img_pitch, img_stride;
+    const float* flow;
+    size_t flow_stride;
+    float* vel;                  // the velocity of each pixel, float2, unpitched
+    size_t plane;
+    uint8_t* rgb;
+    uint8_t* rgba;
+    size_t rgba_pitch;
+    int h, w;
+    float readout, anchor;
+    int iters, axis, frame;
+};
+void launch_rs_velocity(const RShutterArgs& a, int npairs, hipStream_t s);
+void launch_rs_gather(const RShutterArgs& a, int npairs, hipStream_t s);
+
 // ---- dense point trajectories (k_track.hip; the per-point arithmetic: track.h) ----
 // The device counters of a tracker (int32 each): the live count, the next id, the frame, the last step's dropped / ended / seeded counts,
 // and what the kernels of one step hand to each other.

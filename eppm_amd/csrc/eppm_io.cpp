@@ -1,7 +1,7 @@
 // eppm_io.cpp -- file formats and error metrics of the reference's CLI path (main.cpp:56-69):
 // PPM reader (basic/bao_basic.cpp:137-218), Middlebury .flo (3rdparty/middlebury/flowIO.cpp:5-20,
 // :48-163), EPE/AAE (basic/bao_flow_tools.cpp:64-111); y4m files of 4:2:0 frames (include/eppm_yuv.h); the
-// deinterlacer's host forms (include/eppm_deint.h).  No GPU code here.
+// deinterlacer's host forms (include/eppm_deint.h); the rolling-shutter correction's host form (include/eppm_rshutter.h).  No GPU code here.
 #include <limits.h>
 #include <math.h>
 #include <stdarg.h>
@@ -13,10 +13,12 @@
 
 #include "../../include/eppm.h"
 #include "../../include/eppm_deint.h"
+#include "../../include/eppm_rshutter.h"
 #include "deint.h"
 #include "fb_occlusion.h"
 #include "interp.h"
 #include "mblur.h"
+#include "rshutter.h"
 #include "temporal.h"
 #include "yuv.h"
 
@@ -422,6 +424,48 @@ extern "C" int eppm_motion_blur_host(uint8_t* rgb_out, const uint8_t* rgb, const
                     rgb_out[i * 3] = (uint8_t)p; rgb_out[i * 3 + 1] = (uint8_t)(p >> 8); rgb_out[i * 3 + 2] = (uint8_t)(p >> 16);
                 }
         }
+    return EPPM_OK;
+}
+
+// rolling-shutter correction on host planes.  The velocity and the gather are rshutter.h's, the kernels' own, in
+// the kernels' two passes: the velocity plane first, then every output pixel.  rgb_out, rgb: h rows of w R,G,B triplets, packed.
+extern "C" int eppm_rs_default_params(eppm_rs_params* p)
+{
+    if (!p) return EPPM_ERR_ARG;
+    p->readout = 0.5f;
+    p->anchor = 0.5f;
+    p->iters = 3;
+    p->axis = 0;
+    return EPPM_OK;
+}
+
+extern "C" int eppm_rolling_shutter_host(uint8_t* rgb_out, const uint8_t* rgb, const float* u, const float* v, int h, int w, int frame,
+                                         const eppm_rs_params* params)
+{
+    eppm_rs_params prm;
+    if (params) prm = *params;
+    else (void)eppm_rs_default_params(&prm);
+    if (!rgb_out || !rgb || !u || !v || h < 1 || w < 1 || h > 8192 || w > 8192 || (long long)h * w > (1LL << 26)) return EPPM_ERR_ARG;
+    if (!eppm::rs_params_ok(prm.readout, prm.anchor, prm.iters, prm.axis) || (frame != 0 && frame != 1)) return EPPM_ERR_ARG;
+    const size_t n = (size_t)h * w;
+    const eppm::RsConst k = eppm::rs_const(prm.readout, prm.anchor, prm.axis, frame, h, w);
+    std::vector<eppm::RsVel> plane(n);
+    for (size_t i = 0; i < n; i++) plane[i] = eppm::rs_velocity(u[i], v[i], k);
+    auto vel = [&](int x, int y) { return plane[(size_t)y * w + x]; };
+    auto px = [&](int x, int y) {
+        const uint8_t* p = rgb + ((size_t)y * w + x) * 3;
+        return (uint32_t)p[0] | ((uint32_t)p[1] << 8) | ((uint32_t)p[2] << 16);
+    };
+    std::vector<uint8_t> tmp;                   // rgb_out may be rgb: the gather reads the whole frame
+    uint8_t* out = rgb_out;
+    if (rgb_out == rgb) { tmp.resize(n * 3); out = tmp.data(); }
+    for (int y = 0; y < h; y++)
+        for (int x = 0; x < w; x++) {
+            const size_t i = (size_t)y * w + x;
+            const uint32_t p = eppm::rs_gather_pixel(x, y, k, prm.iters, h, w, vel, px);
+            out[i * 3] = (uint8_t)p; out[i * 3 + 1] = (uint8_t)(p >> 8); out[i * 3 + 2] = (uint8_t)(p >> 16);
+        }
+    if (out != rgb_out) memcpy(rgb_out, out, n * 3);
     return EPPM_OK;
 }
 

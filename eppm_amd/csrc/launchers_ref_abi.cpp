@@ -4,6 +4,8 @@
 // stage objects (each in its object's module) borrow it through launcher_run.
 #include "stage_object.h"
 #include "mblur.h"
+#include "rshutter.h"
+#include "../../include/eppm_rshutter.h"
 
 using namespace eppm;
 
@@ -717,6 +719,36 @@ extern "C" int eppm_motion_blur_frames(void* d_rgba_out, size_t out_pitch, const
     a.shutter = prm.shutter; a.max_radius = prm.max_radius; a.taps = prm.taps;
     launch_mblur_pack(a, 1, g_stream);
     launch_mblur_gather(a, 1, g_stream);
+    HIPCHK(hipStreamSynchronize(g_stream));
+    return finish();
+}
+// ---- rolling-shutter correction on caller planes (k_rshutter.hip; eppm_rolling_shutter_host is its host form): one frame ----
+extern "C" int eppm_rolling_shutter_frames(void* d_rgba_out, size_t out_pitch, const void* d_rgba, size_t in_pitch, const eppm_float2* d_flow, int h, int w,
+                                           int frame, const eppm_rs_params* params)
+{
+    eppm_rs_params prm;
+    if (params) prm = *params;
+    else (void)eppm_rs_default_params(&prm);
+    if (!d_rgba_out || !d_rgba || !d_flow || h < 1 || w < 1 || (frame != 0 && frame != 1)) return set_err(EPPM_ERR_ARG, "eppm_rolling_shutter_frames: bad argument");
+    if (!rs_params_ok(prm.readout, prm.anchor, prm.iters, prm.axis))
+        return set_err(EPPM_ERR_ARG, "eppm_rolling_shutter_frames: readout %g (-1 .. 1), anchor %g (0 .. 1), iters %d (1 .. 8), axis %d (0, 1)", prm.readout, prm.anchor, prm.iters, prm.axis);
+    if (bad_pitch(in_pitch, w) || bad_pitch(out_pitch, w))
+        return set_err(EPPM_ERR_ARG, "eppm_rolling_shutter_frames: bad pitch %zu / %zu", in_pitch, out_pitch);
+    if (h > 8192 || w > 8192 || (unsigned long long)h * (unsigned long long)w > (1ULL << 26))
+        return set_err(EPPM_ERR_ARG, "eppm_rolling_shutter_frames: size %dx%d out of range", w, h);
+    LAUNCHER_BEGIN_INT;
+    RShutterArgs a{};
+    a.plane = (size_t)h * w;
+    void* scr = nullptr;
+    CHK(get_scratch(ds, a.plane * 8, &scr, 6));          // the velocity plane
+    a.img = (const uint8_t*)d_rgba; a.img_pitch = in_pitch;
+    a.flow = (const float*)d_flow;
+    a.vel = (float*)scr;
+    a.rgba = (uint8_t*)d_rgba_out; a.rgba_pitch = out_pitch;
+    a.h = h; a.w = w;
+    a.readout = prm.readout; a.anchor = prm.anchor; a.iters = prm.iters; a.axis = prm.axis; a.frame = frame;
+    launch_rs_velocity(a, 1, g_stream);
+    launch_rs_gather(a, 1, g_stream);
     HIPCHK(hipStreamSynchronize(g_stream));
     return finish();
 }

@@ -143,6 +143,25 @@ def motion_blur_host(img, u, v, shutter=0.5, max_radius=16, taps=8):
     return out
 
 
+def rolling_shutter_host(img, u, v, frame=0, readout=0.5, anchor=0.5, iters=3, axis=0):
+    """(h, w, 3) uint8 frame: img as a global shutter would have recorded it, corrected along its flow (u, v) (eppm_rolling_shutter_host,
+    DESIGN.md section 27; byte-identical to the kernels).  frame=0: the flow points to the next frame, 1: to the previous one; readout: the
+    share of the frame interval the sensor takes to read a frame, anchor: the position along the axis whose sampling time is the frame's,
+    iters: fixed-point steps, axis: 0 rows are read one after another, 1 columns."""
+    from .api import RSParams
+    a = np.ascontiguousarray(img, np.uint8)
+    u = np.ascontiguousarray(u, np.float32)
+    v = np.ascontiguousarray(v, np.float32)
+    if u.ndim != 2 or a.shape != (*u.shape, 3) or v.shape != u.shape:
+        raise ValueError("rolling_shutter_host: image (h, w, 3), flow (h, w)")
+    h, w = u.shape
+    p = RSParams(readout=readout, anchor=anchor, iters=iters, axis=axis)
+    out = np.empty((h, w, 3), np.uint8)
+    check(lib().eppm_rolling_shutter_host(out.ctypes.data, *[x.ctypes.data for x in (a, u, v)], h, w, int(frame), C.byref(p)),
+          "eppm_rolling_shutter_host")
+    return out
+
+
 def _track_params(params, kw):
     from .api import TrackParams
     return TrackParams(params, **kw)

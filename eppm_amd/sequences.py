@@ -275,6 +275,60 @@ def motion_blur_sequence(frames, params=None, shutter=0.5, max_radius=16, taps=8
     return out
 
 
+def _rolling_shutter(who, clips, slots, rs, params, temporal, stop_level, auto_cut, cut_params):
+    """rolling_shutter_sequence(s): one list of frames per clip.  Per clip, with c the pair's cut flag:
+
+        fallback = frames[0]
+        for each pair (k-1, k):
+            out[k-1] = fallback      if c else rolling_shutter(frame=0)
+            fallback = frames[k]     if c else rolling_shutter(frame=1)
+        out[n-1] = fallback
+
+    so no frame is warped along a flow across a cut.  One clip without auto_cut has no cut and needs frame=1 for its last pair only."""
+    _, cut_params = _split(cut_params, (), who, auto_cut)
+    both = auto_cut or slots is not None
+
+    def compute(run):
+        return run.e.compute_flow_bidirectional_device() if both or run.last else run.e.compute_flow()
+    with _Run(who, clips, slots, params, temporal, stop_level, None, auto_cut, cut_params, compute) as run:
+        out = [[c[0].copy()] for c in run.clips]
+        for slot, c, f, _, keep in run:
+            if slot == 0:               # once per step, every active pair
+                r0 = run.e.rolling_shutter(frame=0, **rs)
+                r1 = run.e.rolling_shutter(frame=1, **rs) if both or run.last else None
+                if run.single:
+                    r0, r1 = [r0], [r1]
+            if not keep:
+                continue
+            cut = auto_cut and bool(run.found[slot])
+            if not cut:
+                out[c][f - 1] = r0[slot]
+            out[c].append(run.clips[c][f].copy() if cut or r1 is None else r1[slot])
+    return out
+
+
+def rolling_shutter_sequence(frames, readout=0.5, anchor=0.5, iters=3, axis=0, params=None, temporal=True, stop_level=0, auto_cut=False, **cut_params):
+    """A clip ((h, w, 3) uint8 frames, or yuv.YuvFrames) with its rolling-shutter distortion removed (EPPM.rolling_shutter, DESIGN.md
+    section 27): one streaming context -- set_data, then push_frame --, a forward-only compute per pair and its image 1 corrected along the
+    forward flow; the last pair is computed bidirectionally and gives the clip's last frame too, corrected along the backward flow.
+    Returns len(frames) frames.  Memory does not grow with the clip.  readout / anchor / iters / axis: EPPM.rolling_shutter's; params: the
+    flow's eppm Params; temporal / stop_level: the flow's temporal and draft modes.  auto_cut=True: every pair is computed bidirectionally
+    and a CutDetector (cut_params: its lost_permille / residual_max) looks at it; the frames either side of a cut are corrected along the
+    flows of their own shots (the last frame of a shot along its backward flow), and a one-frame shot comes back unchanged."""
+    rs = dict(readout=readout, anchor=anchor, iters=iters, axis=axis)
+    return _rolling_shutter("rolling_shutter_sequence", [frames], None, rs, params, temporal, _level(stop_level), auto_cut, cut_params)[0]
+
+
+def rolling_shutter_sequences(clips, slots=8, readout=0.5, anchor=0.5, iters=3, axis=0, params=None, temporal=True, stop_level=0, auto_cut=False,
+                              **cut_params):
+    """rolling_shutter_sequence for many clips at once: clips of one frame size and of any lengths (two frames at least) through ONE batch
+    context of min(slots, len(clips)) slots, on flow_sequences' schedule, every pair computed bidirectionally.  A slot that takes the next
+    clip of the queue holds a pair across two clips for that step: nothing is read of it.  Returns one list of frames per clip, each what
+    rolling_shutter_sequence(clip) returns."""
+    rs = dict(readout=readout, anchor=anchor, iters=iters, axis=axis)
+    return _rolling_shutter("rolling_shutter_sequences", clips, slots, rs, params, temporal, _level(stop_level), auto_cut, cut_params)
+
+
 def _denoise(who, clips, slots, params, thresh, n_max, temporal, stop_level, auto_cut, cut_params):
     with _Run(who, clips, slots, params, temporal, stop_level, lambda e: TemporalFilter(e, thresh, n_max), auto_cut, cut_params) as run:
         out = [[c[0].copy()] for c in run.clips]

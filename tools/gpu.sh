@@ -18,6 +18,7 @@
 #   stab        the stabiliser: tools/stab_times.py on both libraries -> stab_times_{exact,tol}.json
 #   cutdet      the cut detector: tools/cutdet_times.py --shares on both libraries -> cutdet_times_{exact,tol}.json
 #   mblur       the synthetic shutter: tools/mblur_times.py on both libraries -> mblur_times_{exact,tol}.json
+#   rshutter    rolling-shutter correction: tools/rshutter_times.py on both libraries -> rshutter_times_{exact,tol}.json
 #   cmap        the correspondence map: tools/cmap_times.py on both libraries -> cmap_times_{exact,tol}.json
 #   objects     the object detector: tools/objects_times.py on both libraries -> objects_times_{exact,tol}.json
 #   plate       the background plate: tools/plate_times.py on both libraries -> plate_times_{exact,tol}.json
@@ -143,6 +144,11 @@ mblur)
   cd $R; for l in exact tol; do
     timeout -k 10 ${MBLUR_TIMEOUT:-300} python tools/mblur_times.py --lib $l ${MBLUR_ARGS} > $O/mblur_times_$l.json || exit 1
     cut -c1-400 $O/mblur_times_$l.json
+  done ;;
+rshutter)
+  cd $R; for l in exact tol; do
+    timeout -k 10 ${RSHUTTER_TIMEOUT:-300} python tools/rshutter_times.py --lib $l ${RSHUTTER_ARGS} > $O/rshutter_times_$l.json || exit 1
+    cut -c1-400 $O/rshutter_times_$l.json
   done ;;
 cmap)
   cd $R; for l in exact tol; do

@@ -27,6 +27,11 @@
 //                     (0 < S <= 1) would have recorded it: blurred along the forward flow (eppm_motion_blur), as
 //                     a P6 PPM.  --blur-radius R (1 .. 31, default 16): the longest half-vector in pixels; --blur-taps N (1 .. 32,
 //                     default 8): taps to each side of a pixel
+//   --rolling-shutter R f.ppm  after the timed window, write image 1 as a global shutter would have recorded it, R (-1 .. 1) being the
+//                     share of the frame interval the sensor takes to read a frame (negative: last line first): corrected along the
+//                     forward flow (eppm_rolling_shutter), as a P6 PPM.  --rs-anchor A (0 .. 1, default 0.5): the
+//                     position along the readout axis whose sampling time is the frame's; --rs-iters N (1 .. 8, default 3): fixed-point
+//                     steps; --rs-columns: columns are read one after another, not rows.  Not together with --motion-blur.
 //
 //   runeppm [options] --sequence f0.ppm f1.ppm f2.ppm ... --out-prefix P [--temporal 0|1]
 //   runeppm [options] --sequence clip.y4m --out-prefix P [--y4m-out] [--yuv-matrix 601|709|2020] ...
@@ -70,6 +75,10 @@
 //                     P_mb_0000.ppm, P_mb_0001.ppm ...: frame k - 1 blurred along the forward flow of the pair k - 1 -> k; the last pair
 //                     runs the bidirectional call and gives the clip's last frame too, blurred along its backward flow.  --blur-radius
 //                     and --blur-taps as above.
+//                     --rolling-shutter R (no file name here): every frame with its rolling-shutter distortion removed (DESIGN.md section
+//                     27) is written to P_rs_0000.ppm, P_rs_0001.ppm ... (P_rs.y4m with --y4m-out), from the same flows as --motion-blur's
+//                     frames.  --rs-anchor, --rs-iters and --rs-columns as above.  It is a mode of its own: the other filters,
+//                     --auto-cut and --deinterlace do not combine with it.
 //                     --propagate layer.ppm alpha.ppm: a layer painted on the first frame follows the surface through the clip
 //                     (DESIGN.md section 19): every pair runs the bidirectional call followed by one step of a correspondence map to
 //                     the first frame, and the layer (alpha: the first channel of the second file), sampled once at the map, is
@@ -110,6 +119,7 @@
 #include "eppm.h"
 #include "eppm_yuv.h"
 #include "eppm_deint.h"
+#include "eppm_rshutter.h"
 
 template <typename T>
 struct Array3 {       // bao_alloc<T>(n,r,c): one contiguous block reachable through row-pointer tables (bao_basic.h:146-162)
@@ -150,6 +160,10 @@ struct Options {
     const char* mblur_file = nullptr;                       // ... its file (the two-image form)
     eppm_mblur_params mb = {0.5f, 16.0f, 8};                // --motion-blur S, --blur-radius, --blur-taps
     bool mb_set = false;                                    // --blur-radius or --blur-taps given
+    bool rs = false;                                        // --rolling-shutter
+    const char* rs_file = nullptr;                          // ... its file (the two-image form)
+    eppm_rs_params rsp = {0.5f, 0.5f, 3, 0};                // --rolling-shutter R, --rs-anchor, --rs-iters, --rs-columns
+    bool rs_set = false;                                    // --rs-anchor, --rs-iters or --rs-columns given
     const char *pl_layer = nullptr, *pl_alpha = nullptr;    // --propagate layer.ppm alpha.ppm
     bool objects = false;                                   // --objects
     bool plate = false, remove_objects = false;             // --plate, --remove-objects
@@ -208,7 +222,8 @@ static int usage()
     fprintf(stderr, "usage: runeppm [--size WxH] [--seed N] [--levels N] [--patch-r N] [--iters N] [--propagation M] [--stop-level N]\n"
                     "               [--pin] [--pairs P] [--gpus G] [--batch B] [--gt file.flo] [--out file.flo] [--backward file.flo]\n"
                     "               [--occlusion file.pgm] [--interpolate T file.ppm]... [--motion-blur S file.ppm]\n"
-                    "               [--blur-radius R] [--blur-taps N] [img1.ppm img2.ppm [out.flo]]\n"
+                    "               [--blur-radius R] [--blur-taps N] [--rolling-shutter R file.ppm] [--rs-anchor A]\n"
+                    "               [--rs-iters N] [--rs-columns] [img1.ppm img2.ppm [out.flo]]\n"
                     "       runeppm [--seed N] [--levels N] [--patch-r N] [--iters N] [--propagation M] [--stop-level N]\n"
                     "               --sequence f0.ppm f1.ppm [f2.ppm ...] --out-prefix P [--temporal 0|1]\n"
                     "               [--denoise] [--denoise-thresh T] [--denoise-frames N] [--stabilize] [--smooth S]\n"
@@ -218,6 +233,7 @@ static int usage()
                     "               [--remove-defects] [--defect-thresh D A] [--defect-radius R] [--defect-grow G]\n"
                     "               [--deflicker] [--flicker-cell N] [--flicker-keep K]\n"
                     "               [--deinterlace] [--bff] [--deint-thresh N] [--single-rate]\n"
+                    "               [--rolling-shutter R] [--rs-anchor A] [--rs-iters N] [--rs-columns]\n"
                     "               --sequence clip.y4m --out-prefix P [--y4m-out] [--yuv-matrix 601|709|2020] [the options above]\n");
     return 2;
 }
@@ -364,7 +380,7 @@ static int run_sequence(const Options& o)
     if (eppm_create(&ctx, h, w, 0, &prm) != EPPM_OK) return fail("eppm_create");
     std::vector<unsigned char> dn, st, mb, pl, layer;
     bool pl_drawn = true;               // --propagate: no cut so far
-    if (o.mblur) mb.resize((size_t)h * w * 3);
+    if (o.mblur || o.rs) mb.resize((size_t)h * w * 3);
     char name[4096];
     if (o.stabilize) {
         eppm_stab_params sp;
@@ -504,7 +520,7 @@ static int run_sequence(const Options& o)
         else if (k == 1) { if (eppm_set_images(ctx, img[0].data(), img[1].data(), (size_t)w * 3) != EPPM_OK) return fail("eppm_set_images"); }
         else if (eppm_push_image(ctx, cur.data(), (size_t)w * 3) != EPPM_OK) return fail("eppm_push_image");
         const bool last = k + 1 == nframes;
-        if (!o.denoise && !o.stabilize && !o.auto_cut && !cm && !od && !plt.p && !dfl.p && !dfk.p && !(o.mblur && last)) { if (eppm_compute(ctx, u.data(), v.data()) != EPPM_OK) return fail("eppm_compute"); }
+        if (!o.denoise && !o.stabilize && !o.auto_cut && !cm && !od && !plt.p && !dfl.p && !dfk.p && !((o.mblur || o.rs) && last)) { if (eppm_compute(ctx, u.data(), v.data()) != EPPM_OK) return fail("eppm_compute"); }
         else {
             if (eppm_compute_bidirectional(ctx, u.data(), v.data(), nullptr, nullptr, nullptr, nullptr) != EPPM_OK) return fail("eppm_compute_bidirectional");
             uint8_t cut = 0;
@@ -593,6 +609,10 @@ static int run_sequence(const Options& o)
         for (int fr = 0; o.mblur && fr <= (last ? 1 : 0); fr++) {       // frame k - 1 from the forward flow; the clip's last frame from the backward flow
             if (eppm_motion_blur(ctx, &o.mb, fr, mb.data(), (size_t)w * 3) != EPPM_OK) return fail("eppm_motion_blur");
             if (!frames_out.put("mb", k - 1 + fr, mb.data(), name, sizeof name)) { fprintf(stderr, "cannot write %s\n", name); if (cuts) fclose(cuts); if (obf) fclose(obf); eppm_objects_destroy(od); eppm_cmap_destroy(cm); eppm_cutdet_destroy(det); eppm_stab_destroy(stab); eppm_tfilter_destroy(flt); eppm_destroy(ctx); return 1; }
+        }
+        for (int fr = 0; o.rs && fr <= (last ? 1 : 0); fr++) {          // the same two windows for the rolling-shutter correction
+            if (eppm_rolling_shutter(ctx, &o.rsp, fr, mb.data(), (size_t)w * 3) != EPPM_OK) return fail("eppm_rolling_shutter");
+            if (!frames_out.put("rs", k - 1 + fr, mb.data(), name, sizeof name)) { fprintf(stderr, "cannot write %s\n", name); return fail("write"); }
         }
     }
     printf("%zu pairs, %.3f ms per pair\n", nframes - 1, total / (double)(nframes - 1));
@@ -811,6 +831,23 @@ int main(int argc, char** argv)
             o.mb_set = true;
         }
         else if (!strcmp(a, "--blur-taps")) { if (!val(&v) || v < 1 || v > 32) return usage(); o.mb.taps = (int)v; o.mb_set = true; }
+        else if (!strcmp(a, "--rolling-shutter")) {   // the value, then (two-image form) the file, as --motion-blur
+            if (i + 1 >= argc) return usage();
+            char* end = nullptr;
+            o.rsp.readout = strtof(argv[++i], &end);
+            if (!end || end == argv[i] || *end || !(o.rsp.readout >= -1.0f && o.rsp.readout <= 1.0f)) return usage();
+            o.rs = true;
+            if (i + 1 < argc && !(argv[i + 1][0] == '-' && argv[i + 1][1] == '-')) o.rs_file = argv[++i];
+        }
+        else if (!strcmp(a, "--rs-anchor")) {
+            if (i + 1 >= argc) return usage();
+            char* end = nullptr;
+            o.rsp.anchor = strtof(argv[++i], &end);
+            if (!end || end == argv[i] || *end || !(o.rsp.anchor >= 0.0f && o.rsp.anchor <= 1.0f)) return usage();
+            o.rs_set = true;
+        }
+        else if (!strcmp(a, "--rs-iters")) { if (!val(&v) || v < 1 || v > 8) return usage(); o.rsp.iters = (int)v; o.rs_set = true; }
+        else if (!strcmp(a, "--rs-columns")) { o.rsp.axis = 1; o.rs_set = true; }
         else if (!strcmp(a, "--sequence")) { while (i + 1 < argc && !(argv[i + 1][0] == '-' && argv[i + 1][1] == '-')) o.seq.push_back(argv[++i]); if (o.seq.empty()) return usage(); }
         else if (!strcmp(a, "--out-prefix")) { if (i + 1 >= argc) return usage(); o.prefix = argv[++i]; }
         else if (!strcmp(a, "--denoise")) o.denoise = true;
@@ -882,6 +919,8 @@ int main(int argc, char** argv)
         if ((o.seq.size() < 2 && !y4m_clip && !(o.deint && o.seq.size() == 1)) || !o.prefix || !pos.empty()) return usage();
         if ((o.bff || o.single_rate) && !o.deint) return usage();
         if (o.mblur_file || (o.mb_set && !o.mblur)) return usage();       // a clip's blurred frames are named by the prefix
+        if (o.rs_file || (o.rs_set && !o.rs)) return usage();
+        if (o.rs && (o.deint || o.denoise || o.stabilize || o.auto_cut || o.pl_layer || o.objects || o.plate || o.defects || o.deflicker || o.mblur)) return usage();       // a mode of its own
         // the options of the two-image form that a clip has no meaning for are refused, not ignored
         const Options d;
         bool pin = false;
@@ -897,6 +936,7 @@ int main(int argc, char** argv)
     if (o.deint || o.bff || o.single_rate) return usage();
     if (o.denoise || o.stabilize || o.auto_cut || o.pl_layer || o.objects || o.plate || o.defects || o.deflicker || o.y4m_out || o.yuv_matrix >= 0) return usage();     // the filter, the stabiliser, the cut detector, the map and the object detector walk a clip
     if ((o.mblur && !o.mblur_file) || (o.mb_set && !o.mblur)) return usage();
+    if ((o.rs && !o.rs_file) || (o.rs_set && !o.rs) || (o.rs && o.mblur)) return usage();
     if (pos.size() == 1 || pos.size() > 3) return usage();
     if (pos.size() >= 2) { o.f1 = pos[0]; o.f2 = pos[1]; }
     if (pos.size() == 3) o.fo = pos[2];
@@ -931,6 +971,8 @@ int main(int argc, char** argv)
     for (size_t k = 0; k < o.interp.size(); k++) frames.emplace_back(h, w, 3);
     std::vector<unsigned char> blurred;             // --motion-blur output
     if (o.mblur) blurred.resize((size_t)h * w * 3);
+    std::vector<unsigned char> corrected;           // --rolling-shutter output
+    if (o.rs) corrected.resize((size_t)h * w * 3);
     std::vector<float> bu, bv;                      // backward flow and image 1's occlusion mask (--backward / --occlusion)
     std::vector<unsigned char> occ;
     std::vector<float*> bur, bvr;
@@ -958,6 +1000,10 @@ int main(int argc, char** argv)
             if (!eppm.interpolate_frame(o.interp[k].first, frames[k].p())) return 1;
         if (o.mblur && eppm_motion_blur(eppm.handle(), &o.mb, 0, blurred.data(), (size_t)w * 3) != EPPM_OK) {
             fprintf(stderr, "eppm_motion_blur: %s\n", eppm_last_error());
+            return 1;
+        }
+        if (o.rs && eppm_rolling_shutter(eppm.handle(), &o.rsp, 0, corrected.data(), (size_t)w * 3) != EPPM_OK) {
+            fprintf(stderr, "eppm_rolling_shutter: %s\n", eppm_last_error());
             return 1;
         }
     }
@@ -1069,5 +1115,6 @@ int main(int argc, char** argv)
         if (!ok) { fprintf(stderr, "cannot write %s\n", o.interp[k].second); return 1; }
     }
     if (o.mblur && !write_ppm(o.mblur_file, blurred.data(), h, w)) { fprintf(stderr, "cannot write %s\n", o.mblur_file); return 1; }
+    if (o.rs && !write_ppm(o.rs_file, corrected.data(), h, w)) { fprintf(stderr, "cannot write %s\n", o.rs_file); return 1; }
     return 0;
 }
